@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the FA-2 forward hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--variant auto] [--gather]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--variant auto] [--gather] [--dump-outputs DIR]
 
 One "step" = one forward pass of the hot path (flash_attention_forward -> C ABI -> HIP kernel) over one
 batch of synthetic input that is already resident in HBM.  The workload is BASELINE.json's metric
@@ -15,7 +15,8 @@ G-times-wider problem (weak scaling); value = total FLOPs of all ranks / max-ove
 optional exchange step of the north star, an RCCL all-gather of the output shards over xGMI, is timed
 separately after the main region and reported under "gather" (use --gather to put it inside the step).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step returned on rank 0, O and L, as
+DIR/O.npy and DIR/L.npy in float32 (see dump_outputs): the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -264,6 +265,30 @@ def strong_scaling(c, world, rank, dev, sync_all, iters=5):
             "tflops_aggregate_with_gather": round(F / t_gather / 1e12, 1)}
 
 
+DUMP_MAX_ELEMS = 1 << 22   # per array: 16 MiB of float32, so O and L together stay far below 64 MB
+
+
+def dump_outputs(out_dir, arrays, max_elems=DUMP_MAX_ELEMS, seed=0):
+    """Write each tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32.  A tensor of at most `max_elems` elements
+    is written whole, in its own shape; a larger one as the 1-D sample of its flattened values at fixed positions, drawn with
+    `seed` and sorted, the same positions for the same shape in every run.  Returns {name: (shape written, whole?)}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        n = t.numel()
+        if n <= max_elems:
+            a = t.detach().float().cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(seed).integers(0, n, size=max_elems, dtype=np.int64))
+            a = t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = (tuple(a.shape), n <= max_elems)
+    return written
+
+
 def self_launch(n):
     """`python bench.py --gpus N` outside torch.distributed.run: this process starts N fresh rank processes (one per GPU) through
     `python -m torch.distributed.run` as a CHILD, relays rank 0's JSON line and returns the children's worst exit code.  It runs
@@ -307,6 +332,9 @@ def main():
     ap.add_argument("--gather", action="store_true", help="include the RCCL all-gather of O in the timed step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the scaled-input and gather side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the O and L the last timed step returned (rank 0) as DIR/O.npy and DIR/L.npy, float32; "
+                         f"a fixed seeded sample of an array larger than {DUMP_MAX_ELEMS} elements")
     ap.add_argument("--self-launch", action="store_true",
                     help="start the rank processes from this process even for --gpus 1 (what --gpus N > 1 does when not under torch.distributed.run)")
     args = ap.parse_args()
@@ -376,7 +404,7 @@ def main():
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(args.steps):
-        step()
+        last = step()
     ev1.record()
     while not ev1.query():      # spin on the closing event: a blocking synchronize wakes the host tens of microseconds after the last
         pass                    # kernel has ended -- 0.3-0.5 % of a 20-step bracket of 0.44-ms kernels; the synchronize below then returns at once
@@ -499,6 +527,9 @@ def main():
             "lib": _lib.version(),
         }
         print(json.dumps(out))
+        if args.dump_outputs:
+            O_last, L_last = last
+            dump_outputs(args.dump_outputs, {"O": O_last, "L": L_last})
     if grouped:
         dist.destroy_process_group()
 

@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -165,7 +166,9 @@ def test_host_side_and_oracle_under_address_sanitizer():
         pytest.skip("already inside the sanitizer run")
     if not glob.glob("/opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so"):
         pytest.skip("no clang AddressSanitizer run time here")
-    env = {k: v for k, v in os.environ.items() if k not in ("LD_PRELOAD",)}
+    if os.path.exists("/dev/kfd"):
+        pytest.skip("needs a box without a GPU: the tile query would bring the device up inside the sanitized process")
+    env = dict(os.environ, PYTHON=sys.executable)
     out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "run_asan.sh")], capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, (out.stdout[-3000:], out.stderr[-3000:])
     assert " passed" in out.stdout and "failed" not in out.stdout
