@@ -28,14 +28,16 @@ LDS image of a K / V tile: two column halves of 64 rows x 128 bytes, the eight 1
 """
 from __future__ import annotations
 
-import argparse
-import sys
 
 from .isa import A, EXEC, I, Inst, Label, M0, Reg, S, V, VCC, comment, label, waitcnt
+from .stream_gen import (KARG_SIZE, NSLOT, SBUF, S_B, S_C, S_DBG, S_FINAL, S_FIRE, S_FLAG, S_G, S_H, S_HH, S_JOB, S_K32, S_K64,
+                         S_KARG, S_KDMA, S_KRS, S_KSN, S_KT0, S_KW, S_LDSW, S_LG, S_N, S_NB, S_NBH, S_NHH, S_NNT, S_NQ, S_NQI,
+                         S_NT, S_NUNIT, S_NVRS, S_NWG, S_OSN, S_PASS, S_Q, S_QI, S_QROW, S_QSB, S_QSH, S_QSN, S_SQ, S_T, S_THR,
+                         S_TOTAL, S_UNIT, S_V32, S_V64, S_VDMA, S_VRS, S_VSN, S_VW, S_WAVE, S_WGID, S_X2, StreamGen)
 
 # ------------------------------------------------------------------------------------------------- register map
 # arch VGPRs
-SBUF = (0, 64)            # two score buffers of 64 registers: group gi = 2 qh + kk at + 16 gi, inside + 8 (qb16 & 1) + 4 (kb16 & 1) + r
+# SBUF = (0, 64) (stream_gen): two score buffers of 64 registers: group gi = 2 qh + kk at + 16 gi, inside + 8 (qb16 & 1) + 4 (kb16 & 1) + r
 KF = 128                  # K fragments of the next tile: (kb16, ks) at KF + 4 (4 kb16 + ks)
 V_KR = (192, 193)         # K row-read lane bases (even / odd 32-column step)
 V_VR = (194, 195, 196, 197)   # V transposed-read lane bases (db16 & 3), the V ring's LDS offset included
@@ -89,33 +91,7 @@ def P_OP(X, qb16, kk):
     return V(X + 16 * (2 * (qb16 >> 1) + kk) + 8 * (qb16 & 1), 4)
 
 
-# SGPRs.  s4..s47 hold the kernel arguments (loaded once).
-S_KARG = S(0, 2)
-S_WGID = S(2)
-S_FINAL = S(75)
-S_Q, S_K, S_V, S_O, S_L = S(4, 2), S(6, 2), S(8, 2), S(10, 2), S(12, 2)
-S_QSB, S_QSH, S_KSB, S_KSH, S_VSB, S_VSH, S_OSB, S_OSH, S_LSB, S_LSH = (S(14 + 2 * k, 2) for k in range(10))
-S_QSN, S_KSN, S_VSN, S_OSN = S(34), S(35), S(36), S(37)
-S_N, S_H, S_NQ, S_TOTAL = S(38), S(39), S(40), S(41)
-S_C, S_THR, S_NUNIT, S_G = S(42), S(43), S(44), S(45)
-S_NBH, S_NWG = S(46), S(47)
-S_KRS, S_VRS, S_NVRS, S_SQ = S(48, 4), S(52, 4), S(56, 4), S(60, 4)   # K / V descriptors, the next job's V, a scratch one
-S_NB, S_NHH, S_NQI, S_NNT = S(64), S(65), S(66), S(67)                # the next job
-S_JOB, S_WAVE = S(68), S(69)
-S_KDMA, S_VDMA = S(70), S(71)    # source offset of the next K / V tile to stream (the wave's row base included)
-S_K32, S_V32 = S(72), S(74)      # 32 rows of K / V in bytes
-S_K64, S_V64 = S(76), S(77)
-S_LDSW = S(78)                   # 2048 * wave: the wave's piece offset inside a ring buffer
-S_LOOP, S_FLAG = S(79), S(80)
-S_QI, S_B, S_HH, S_UNIT, S_PASS, S_NT = S(81), S(83), S(84), S(85), S(86), S(87)   # the current job
-S_T = tuple(S(88 + k) for k in range(8))  # temporaries s88..s95 (S_T[0] even: usable as a 64-bit pair)
-S_QROW = (S(96), S(97))          # first row of the wave's query block qb (current job)
-S_DBG = S(98, 2)
-S_KW, S_VW = S(100), S(101)      # 8 * wave * row stride: the wave's row base inside a tile
-S_KT0 = S(86)                    # (= S_PASS, causal only) non-causal ragged: real keys in the job's last 256 = N - 256 (nq - 1)
-S_LG = S(73)                     # decode shifts: lgH | lgG << 8 | lg(G * nunit) << 16 | pow2-mode << 24
-S_FIRE = (S(0, 2), S(2, 2))      # per query block: lanes whose row maximum passed the deferral threshold (s0..s3 are free after the set-up)
-S_X2 = S(82)
+# SGPRs: the map shared by all four families is stream_gen's.
 
 # LDS map (bytes)
 KB = (0, 16384)
@@ -134,87 +110,33 @@ def tile_addr(row, c16):
     64 rows x 128 bytes, the eight chunks of a half row XOR-swizzled by (row & 6)"""
     return 8192 * (c16 >> 3) + 128 * row + 16 * ((c16 & 7) ^ (row & 6))
 
-KARG_SIZE = 192
-NSLOT = 24
 
+class Gen(StreamGen):
+    # the family's registers and LDS size, as the shared stream methods read them (stream_gen.StreamGen)
+    V_T, V_ST_LAST, V_ST_ACC, V_MC, V_MX, V_CO, V_MSV, V_LACC, V_LANE, V_IMH, V_PM, NINF = \
+        V_T, V_ST_LAST, V_ST_ACC, V_MC, V_MX, V_CO, V_MSV, V_LACC, V_LANE, V_IMH, V_PM, NINF
+    LDS_TOTAL = LDS_TOTAL
+    FAMILY, MFMA = "a16", "v_mfma_f32_16x16x32_{dtype}"
+    CVT = {"bf16": "v_cvt_pk_bf16_f32", "f16": "v_cvt_pk_f16_f32"}
+    DMA_PIECES, K_READS, V_READS = 4, 16, 32
+    DMA_GAPS = (11, 13, 15, 17, 21, 23, 25, 27)
+    # the seam's sixteen Q-staging pieces: eight behind step 0's own K / V pieces, four in the quiet end of the next phase A, four in
+    # front of step 1's own (vmcnt(8 / 12 + ...))
+    QS_GAPS = ((1, 3, 5, 7, 11, 13, 15, 17), (21, 23, 25, 27, 31, 33, 35, 37), (24, 26, 28, 30), (1, 3, 5, 7), 12)
+    O_AGPRS, ROW_BYTES, L_SN = 128, 256, 2
+    BRANCH_NEED, WALK_DOWN = None, False      # (every job walks its key tiles upwards: no S_DESC / S_NDESC)
 
-class Gen:
     def __init__(self, dtype="bf16", causal=False, name=None, stamps=False, abl=(), ring=(2, 3, 2), vread_double=4, ragged=False,
                  caps=(5, 24), split=True, soft=None):
-        assert dtype in ("bf16", "f16")
-        self.dtype = dtype
-        self.causal = causal
-        self.name = name or f"fa2_fwd_a16_{dtype}_{'c' if causal else 'n'}{'r' if ragged else ''}"
-        self.atmp = 0          # (ragged) which of the two address temporaries the next buffer operation takes
-        self.atmp_regs = (V_T[8], V_T[9])
-        self.prog: list[Inst] = []
-        self.uid = 0
-        self.mfma = "v_mfma_f32_16x16x32_" + dtype
-        self.cvt = "v_cvt_pk_bf16_f32" if dtype == "bf16" else "v_cvt_pk_f16_f32"
-        self.ool: list[list[Inst]] = []  # out-of-line blocks (rare paths), appended after the main body
-        self.soft = soft       # (limit, window) of the softmax plan's soft per-gap issue limit, or None (tile_plan.place)
-        self.caps = caps       # fillers / issue cycles a gap behind a 32x32x16 MFMA may carry in the softmax plan
-        # causal row map "split": wave w owns the 32-row blocks w (qb 0) and w + 4 (qb 1) of the job's 256 rows instead of
-        # 2 w and 2 w + 1.  Diagonal tile j (key blocks 2 j, 2 j + 1) is then hidden from query block 0 of EVERY wave for
-        # j >= 2 and fully visible to query block 1 for j < 2: the job's last steps run on one query block (half the MFMAs)
-        # for all four waves instead of on both for a shrinking set of waves -- see build()
-        assert split, "the a16 kernels use the split row map only"
-        self.split = bool(split) and causal
-        assert self.split or not causal, "a16: the causal kernels use the split row map (the contiguous map's lean bodies know two maxima per wave, not four)"
-        self.cls = None        # split seam bodies: "low" (waves 0, 1) / "high" (waves 2, 3) while their code is generated
-        self.ragged = ragged   # N is not a multiple of 256: range-checked descriptors, every offset in the VGPR operand, masked key tail
-        assert not (ragged and stamps), "the ragged kernels use the stamps' temporaries as address registers"
+        assert split, "a16: the split row map only (the contiguous map's lean bodies know two maxima per wave, not four)"
         # (the accumulating stamps use the causal kernels' mask registers: causal diagnostic builds carry the plain job-timeline
         # stamps only -- "noacc")
         if stamps and causal:
             abl = tuple(abl) + ("noacc",)
-        self.vread_double = vread_double   # phase-A gaps that carry two V transposed reads (the last read sits in gap 31 - this)
-        self.abl = set(abl)    # timing-only ablations of the steady loop (diagnostic builds; results wrong by construction)
-        self.R, self.dk, self.dv = ring   # ring depth; K(t + dk) and V(t + dv) are streamed in phase B(t): dk <= R + 1, dv <= R
-        assert 3 <= self.dk <= min(self.R + 1, 4) and 2 <= self.dv <= self.R and 4 % self.R == 0
-        self.vm = 8 * min(self.dk - 3, self.dv - 2)  # DMA pieces that may stay in flight across the mid-step barrier
-        self._cache = {}
-        self.stamps = stamps   # diagnostic build: s_memtime stamps of the job timeline go to the debug buffer
+        super().__init__(dtype, causal, name, stamps, abl, ring, vread_double, ragged, caps, split)
+        self.soft = soft       # (limit, window) of the softmax plan's soft per-gap issue limit, or None (tile_plan.place)
 
     # ------------------------------------------------------------------ small helpers
-    def e(self, *insts):
-        for x in insts:
-            if isinstance(x, (list, tuple)):
-                self.e(*x)
-            else:
-                self.prog.append(x)
-
-    def lab(self, stem):
-        self.uid += 1
-        return f".L{self.name}_{stem}_{self.uid}"
-
-    def stamp(self, slot, real=False):
-        """diagnostic builds only: dbg[(wg * 4 + wave) * NSLOT + slot] = s_memtime (or s_memrealtime)"""
-        if not self.stamps:
-            return []
-        t = S(S_T[0].idx, 2)
-        v = V(V_T[8], 2)
-        return [I("s_memrealtime" if real else "s_memtime", t), waitcnt(lgkmcnt=0),
-                I("v_mov_b32", v.sub(0), t.sub(0)), I("v_mov_b32", v.sub(1), t.sub(1)),
-                I("v_mov_b32", V(V_T[7]), 0), I("global_store_dwordx2", V(V_T[7]), v, S_DBG, offset=8 * slot)]
-
-    ASYNC_PAIRS = (S(90, 2), S(92, 2), S(94, 2), S(0, 2), S(2, 2))   # S_T[2..7], S_FIRE: idle in the epilogue
-
-    def stamp_async(self, k):
-        """diagnostic builds only: s_memtime into spare pair k WITHOUT a wait (the epilogue's LDS queue is not drained; its
-        counted lgkmcnt waits may be satisfied early by the returning s_memtime: timing-only)"""
-        return [I("s_memtime", self.ASYNC_PAIRS[k])] if self.stamps else []
-
-    def stamp_async_flush(self, slots):
-        if not self.stamps:
-            return []
-        out = [waitcnt(lgkmcnt=0), I("v_mov_b32", V(V_T[7]), 0)]
-        v = V(V_T[8], 2)
-        for k, slot in enumerate(slots):
-            t = self.ASYNC_PAIRS[k]
-            out += [I("v_mov_b32", v.sub(0), t.sub(0)), I("v_mov_b32", v.sub(1), t.sub(1)),
-                    I("global_store_dwordx2", V(V_T[7]), v, S_DBG, offset=8 * slot), I("s_nop", 7)]
-        return out
 
     def stamp_acc(self, k):
         """diagnostic builds only: acc[k] += cycles since the previous stamp_acc (its s_waitcnt drains the LDS queue as well: the
@@ -252,55 +174,6 @@ class Gen:
             out += [I("global_store_dword", V(V_T[7]), V(V_ST_ACC + k), S_DBG, offset=8 * (10 + k)),
                     I("v_mov_b32", V(V_ST_ACC + k), 0)]
         return out
-
-    def udiv(self, q: Reg, r: Reg | None, n: Reg, d: Reg, vt=None):
-        """q = n / d, r = n % d for wave-uniform 32-bit values < 2^22 (float reciprocal + one correction each way)"""
-        t0, t1 = vt if vt is not None else (V(V_T[0]), V(V_T[1]))
-        st, sr = S_T[6], S_T[7]
-        self.e(I("v_cvt_f32_u32", t0, n), I("v_cvt_f32_u32", t1, d), I("s_nop", 0), I("v_rcp_f32", t1, t1), I("s_nop", 1),
-               I("v_mul_f32", t0, t0, t1), I("v_cvt_u32_f32", t0, t0), I("s_nop", 1), I("v_readfirstlane_b32", q, t0), I("s_nop", 4),
-               I("s_mul_i32", st, q, d), I("s_sub_i32", sr, n, st),
-               # r < 0 -> q--, r += d
-               I("s_cmp_lt_i32", sr, 0), I("s_cselect_b32", st, 1, 0), I("s_sub_u32", q, q, st),
-               I("s_cmp_lt_i32", sr, 0), I("s_cselect_b32", st, d, 0), I("s_add_i32", sr, sr, st),
-               # r >= d -> q++, r -= d
-               I("s_cmp_ge_i32", sr, d), I("s_cselect_b32", st, 1, 0), I("s_add_u32", q, q, st),
-               I("s_cmp_ge_i32", sr, d), I("s_cselect_b32", st, d, 0), I("s_sub_i32", sr, sr, st))
-        if r is not None:
-            self.e(I("s_mov_b32", r, sr))
-
-    def mad64(self, dst: Reg, idx: Reg, stride: Reg):
-        """dst(64) += idx(32, unsigned) * stride(64)"""
-        lo, hi = S_T[6], S_T[7]
-        return [I("s_mul_i32", lo, idx, stride.sub(0)), I("s_mul_hi_u32", hi, idx, stride.sub(0)),
-                I("s_add_u32", dst.sub(0), dst.sub(0), lo), I("s_addc_u32", dst.sub(1), dst.sub(1), hi),
-                I("s_mul_i32", lo, idx, stride.sub(1)), I("s_add_u32", dst.sub(1), dst.sub(1), lo)]
-
-    def make_desc(self, rs: Reg, base: Reg, sb: Reg, sh: Reg, b: Reg, hh: Reg, sn=None):
-        """raw buffer descriptor of the (b, hh) slice of a tensor: base + b * sb + hh * sh.  N a multiple of 256: the range check
-        is not used (soffset is unchecked anyway; every address the kernel forms lies inside the tensor).  Ragged kernels:
-        num_records = (N - 1) * sn + 256 bytes of rows (sn: the row stride register; an int: bytes per row of L) -- loads of
-        rows past N come back as zeros, stores to them are dropped; those kernels keep every offset in the VGPR operand"""
-        tmp = S(S_T[0].idx, 2)
-        out = ([I("s_mov_b64", tmp, base)] + self.mad64(tmp, b, sb) + self.mad64(tmp, hh, sh) +
-               [I("s_mov_b32", rs.sub(0), tmp.sub(0)), I("s_and_b32", rs.sub(1), tmp.sub(1), 0xFFFF), I("s_mov_b32", rs.sub(3), 0x00020000)])
-        if not self.ragged:
-            return out + [I("s_mov_b32", rs.sub(2), 0x7FFFFFF0)]
-        assert sn is not None
-        if isinstance(sn, int):
-            return out + [I("s_mul_i32", rs.sub(2), S_N, sn)]
-        return out + [I("s_sub_u32", S_T[6], S_N, 1), I("s_mul_i32", S_T[6], S_T[6], sn), I("s_add_u32", rs.sub(2), S_T[6], 256)]
-
-    def buf_op(self, op, data, voff: Reg, rsrc: Reg, soff, **mods):
-        """a buffer operation at byte offset voff (per lane) + soff (scalar).  The scalar operand of the instruction is not
-        range-checked: the ragged kernels add it into an address temporary first (two, taken alternately: a set-up may run
-        ahead of the previous piece's load by one gap).  Returns (set-up instructions, the memory instruction)"""
-        ops = (lambda v, so: (data, v, rsrc, so) if data is not None else (v, rsrc, so))
-        if not self.ragged:
-            return [], I(op, *ops(voff, soff), offen=1, **mods)
-        tmp = V(self.atmp_regs[self.atmp])
-        self.atmp ^= 1
-        return [I("v_add_u32", tmp, soff, voff)], I(op, *ops(tmp, 0), offen=1, **mods)
 
     # ------------------------------------------------------------------ kernel prologue: arguments, lane constants
     def k_setup(self):
@@ -496,13 +369,6 @@ class Gen:
         pre, ld = self.buf_op("buffer_load_dwordx4", None, vl2 if piece & 1 else vl, rsrc, so, lds=1, tag=f"dma {which}{piece}")
         return out + pre + [I("s_nop", 0), ld]
 
-    def dma_tile(self, which, buf):
-        out = []
-        for j in range(4):
-            out += self.dma_piece(which, j, buf)
-        out.append(I("s_add_u32", S_KDMA, S_KDMA, S_K64) if which == "k" else I("s_add_u32", S_VDMA, S_VDMA, S_V64))
-        return out
-
     def q_stage(self, b: Reg, hh: Reg, qi: Reg):
         """Q rows of job (b, hh, qi) of this wave -> the wave's LDS slice by LDS-DMA, in the tile image (16 pieces of 8 rows x
         128 bytes: coalesced, ~25 cycles of issue each).  Returns (descriptor / offset setup, [pieces])"""
@@ -575,21 +441,6 @@ class Gen:
         return out
 
     # ------------------------------------------------------------------ the softmax of one tile as a list of placed operations
-    # Time line of a tile, in MFMA gaps (tau): [0, 32) = the phase A that computes its scores (QK^T chains g = 0..3, eight
-    # MFMAs each), [32, 32 + NB) = the following phase B (NB = 40 MFMAs: P.V of the previous tile plus its row sums),
-    # [32 + NB, 64 + NB) = the next phase A, at whose end P must be packed (its own P.V follows).  In steady state the
-    # physical gap (tau mod PERIOD) therefore carries operations of two tiles: a modulo reservation table keeps every gap
-    # within what hides beside an MFMA (measured, scripts/probes/mb_run + asm/microbench.py: at most five fillers per gap,
-    # issue costs v_exp 8 / three-operand VALU 5 / two-operand 4 summing to <= 24; LDS reads first in their gap).
-    NB = 40
-    PERIOD = 72
-    T_END = 104
-    LAZY_TAU = {"ms0": 28, "ms1": 29, "mr": 99, "pm": 100}   # tau of the lazy-masking operations of a diagonal tile (mask_lazy)
-
-    def lazy_tau(self):
-        """(the split row map has no 'ms' / 'mr'; its packed-P masking sits behind the last pack of the plan, which ends two gaps
-        later there: tile_plan, gap2)"""
-        return dict(self.LAZY_TAU, pm=103) if self.split else self.LAZY_TAU
 
     def tile_plan(self, init=False, lean=False):
         """placement of the per-tile softmax operations: returns [(tau, kind, payload)] sorted by tau.
@@ -697,43 +548,6 @@ class Gen:
         self._cache[key] = placed
         return placed
 
-    def a_vread_gap(self, k):
-        """phase-A gap of V transposed read k: two per gap at the start, none in the last four -- the wait in front of the barrier
-        then finds the youngest read ~130 cycles old instead of just issued"""
-        nd = self.vread_double
-        return k // 2 if k < 2 * nd else k - nd
-
-    def b_short_gaps(self):
-        """indices (0..39) of the phase-B gaps that follow a 16x16x32 row-sum MFMA"""
-        return [10 * k + 8 for k in range(4)] + [10 * k + 9 for k in range(4)]
-
-    def b_reserved(self):
-        """phase-B gap -> number of pre-reserved fillers (K reads, DMA loads, DMA scalar set-up)"""
-        r = {}
-        for k in range(16):
-            r[self.b_kread_gap(k)] = r.get(self.b_kread_gap(k), 0) + 1
-        for k in range(8):
-            g = self.b_dma_gap(k)
-            r[g] = r.get(g, 0) + 1
-            r[g - 1] = r.get(g - 1, 0) + 1
-        return r
-
-    def b_kread_gap(self, k):
-        if "kfront" in self.abl:     # (experiment) two K reads per gap from the start of the phase
-            g = k // 2
-            while g in self.b_short_gaps():
-                g += 1
-            return g
-        g = 2 * k
-        while g in self.b_short_gaps():
-            g += 1
-        return g
-
-    def b_dma_gap(self, k):
-        """phase-B gap whose FIRST filler is DMA piece k's load; its scalar set-up (soffset, M0) ends the gap before, so the MFMA
-        between them is the wait state the M0 write needs.  Distinct, two apart, clear of the short row-sum gaps."""
-        return (11, 13, 15, 17, 21, 23, 25, 27)[k]
-
     def tile_op(self, Sb, kind, payload, init, lazy=None):
         """the instructions of one placed operation, for the tile whose scores live in score buffer Sb.
         lazy = (jd, cond): the tile is diagonal tile jd of its job (if cond holds) and masked lazily (mask_lazy)"""
@@ -801,62 +615,6 @@ class Gen:
             # (in place: the 8 scores of a block's key half -> its first four registers, the B operand P^T(qb16, kk))
             return [I(self.cvt, V(Sb + 16 * g + 8 * (j >> 2) + (j & 3)), V(Sb + 16 * g + 2 * j), V(Sb + 16 * g + 2 * j + 1), tag=f"cvt g{g} {j}")]
         raise KeyError(kind)
-
-    @staticmethod
-    def op_qb(kind, payload):
-        """query block a placed softmax operation belongs to (None: not tied to one)"""
-        if kind in ("mx", "cv"):
-            return payload[0] >> 1
-        if kind == "dec":
-            return payload[0]
-        if kind in ("f", "e"):
-            return payload >> 5
-        if kind == "ms":
-            return payload
-        return None
-
-    def tile_fill(self, Sb, lo, hi, init, masks=None, abl=(), qbs=(0, 1)):
-        """[(gap - lo, [insts], is_exp)] of the tile's operations with lo <= tau < hi.  masks: causal (jd, cond): the tile is
-        diagonal tile jd of its job (when cond = (sgpr, value) holds, if given).  A job's first tile (init) gets its scores
-        masked up front -- the tests of score group g go in front of its first row-maximum operation; every other diagonal
-        tile is masked lazily (mask_lazy)"""
-        out = []
-        seen_mask = set()
-        tail = masks is not None and masks[0] == "tail"     # non-causal ragged: ("tail", j[, cond]) -- seam tile j may hold keys >= N
-        if tail:
-            masks = masks[1:]
-        jd, cond = (masks + (None,))[:2] if masks is not None else (None, None)
-        lazy = (jd, cond) if masks is not None and not init else None
-        plan = self.tile_plan(init)
-        if lazy is not None:
-            lz = self.lazy_tau()
-            if self.split and not tail:
-                # split row map: a hidden (tile, query block) is not computed at all -- no running-maximum swap ('ms' / 'mr');
-                # the packed-P masking only where this body's waves sit on the tile's diagonal and the block is computed
-                pm = self.cls is not None and (jd >> 1) in qbs and self.cls == ("low", "high")[jd & 1]
-                plan = sorted(plan + ([(lz["pm"], "pm", None)] if pm else []), key=lambda x: x[0])
-            else:
-                plan = sorted(plan + [(lz["ms0"], "ms", 0), (lz["ms1"], "ms", 1), (lz["mr"], "mr", None)] +
-                              ([] if tail else [(lz["pm"], "pm", None)]), key=lambda x: x[0])
-        for t, kind, payload in plan:
-            if not (lo <= t < hi):
-                continue
-            if self.op_qb(kind, payload) is not None and self.op_qb(kind, payload) not in qbs:
-                continue
-            if ("no_" + kind) in abl or (kind == "dec" and payload[1] >= 3 and "no_fire" in abl):
-                continue   # timing-only ablations (diagnostic build)
-            if tail:
-                assert not init
-                ins = self.mask_tail(Sb, kind, payload, jd, cond) if kind in ("ms", "mr") else self.tile_op(Sb, kind, payload, init, None)
-            else:
-                ins = self.tile_op(Sb, kind, payload, init, lazy)
-            if not ins:
-                continue
-            if masks is not None and (init or tail) and kind == "mx" and payload[1] == 0 and payload[0] not in seen_mask:
-                seen_mask.add(payload[0])
-                ins = (self.mask_tail_tests(Sb, payload[0], jd, cond) if tail else self.mask_tests(Sb, payload[0], jd, cond)) + ins
-            out.append((t - lo, ins, kind == "e"))
-        return out
 
     # ------------------------------------------------------------------ causal masks
     def group_mask_ops(self, Y, g, what):
@@ -1047,35 +805,6 @@ class Gen:
             out += self.emit_slot(mfmas[k], buckets[idx], keep_order=True)
         return out
 
-    def phase_a(self, t4, with_qk=True, cur=True, nxt=True, nxt_init=False, masks=None, steady=False, dma=(), cur_masks=None, extra=(),
-                cur_qbs=(0, 1), nxt_qbs=(0, 1)):
-        """A(t), t4 = t & 3: QK^T(t+1) -> S[1-p]  ||  V(t) reads from VB[t % R]  ||  the late softmax operations of tile t (on S[p])
-        ||  the early ones of tile t+1 (on S[1-p])"""
-        p = t4 & 1
-        X, Y = SBUF[p], SBUF[1 - p]
-        abl = self.abl if steady else set()
-        mf = self.qk_mfmas(Y, qbs=nxt_qbs) if with_qk else []
-        gaps = {}
-        add = lambda k, order, ins: gaps.setdefault(min(max(int(k), 0), 31), []).append((order, ins))
-        if cur:
-            if "novread" not in abl:
-                for k, ins in enumerate(self.v_reads(t4 % self.R)):
-                    add(self.a_vread_gap(k), 0, [ins])
-            if "nofinish" not in abl:
-                for k, ins, is_exp in self.tile_fill(X, 32 + self.NB, self.T_END, False, cur_masks, abl=abl, qbs=cur_qbs):
-                    add(k, 1 if is_exp else 2, ins)
-        if nxt and "nostart" not in abl:
-            for k, ins, is_exp in self.tile_fill(Y, 0, 32, nxt_init, masks, abl=abl, qbs=nxt_qbs):
-                add(k, 1 if is_exp else 2, ins)
-        for g, ins in extra:
-            add(g, 2, ins)
-        for g, setup, load in dma:   # LDS-DMA pieces riding in this phase (the seam's Q rows): set-up ends gap g - 1, load opens gap g
-            add(g - 1, 3, setup)
-            add(g, 0, [load])
-        if not mf:
-            return [x for k in sorted(gaps) for _, ins in sorted(gaps[k], key=lambda x: x[0]) for x in ins]
-        return self.emit_phase(mf, gaps)
-
     def pv_mfmas(self, X, qbs=(0, 1)):
         """O^T(qb16, db16) += V^T(kk, db16) . P^T(qb16, kk) as 32 slots of two MFMAs (the blocks of a query block qh share the V^T
         fragment, and so do the two slots of a (kk, db16)); behind every eight slots the row sums of two P fragments on the matrix
@@ -1093,132 +822,22 @@ class Gen:
                                if half in qbs and "no_rowsum" not in self.abl else None)   # (no_rowsum: timing-only, l stays 0)
         return out
 
-    def phase_b(self, t4, with_pv=True, nxt=True, nxt_init=False, with_kread=True, with_dma=True, steady=False,
-                pre=(), early=(), late=(), masks=None, own_gaps=None, post=(), cur_qbs=(0, 1), nxt_qbs=(0, 1)):
-        """B(t), t4 = t & 3: P.V(t) and the row sums of P(t) from S[p]  ||  the middle softmax operations of tile t+1 (on S[1-p])
-        ||  K(t+2) reads from KB[(t+2) % R]  ||  LDS-DMA V(t+dv) -> VB[(t+dv) % R], K(t+dk) -> KB[(t+dk) % R].
-        pre: instructions ahead of the phase;  early: scalar work / register loads spread over the first gaps;
-        late: further DMA pieces (the next job's Q rows) as (gap, set-up, load);  own_gaps: the gaps of this step's own pieces"""
-        p = t4 & 1
-        X, Y = SBUF[p], SBUF[1 - p]
-        abl = self.abl if steady else set()
-        mf = self.pv_mfmas(X, qbs=cur_qbs) if with_pv else []
-        NB = self.NB
-        gaps = {}
-        add = lambda k, order, ins: gaps.setdefault(min(max(int(k), 0), NB - 1), []).append((order, ins))
-        head = list(pre)
-        post, post_arg = [], list(post)
-        if with_kread and "nokread" not in abl:
-            for k, ins in enumerate(self.k_reads((t4 + 2) % self.R)):
-                add(self.b_kread_gap(k), 0, [ins])
-        if with_dma:
-            pieces = [self.dma_piece("v", j, (t4 + self.dv) % self.R) for j in range(4)] + \
-                [self.dma_piece("k", j, (t4 + self.dk) % self.R) for j in range(4)]
-            for k, pc in enumerate(pieces):
-                if "nodma" in abl:
-                    continue
-                # (with further pieces behind them -- the seam's Q rows -- this step's own go first: the counted waits
-                # assume all eight are older than the sixteen)
-                g = own_gaps[k] if own_gaps else self.b_dma_gap(k)
-                # scalar set-up (soffset, M0) at the end of the previous gap, the load first in its own: the MFMA between
-                # them is the wait state the M0 write needs
-                setup, load = [x for x in pc if not x.op.startswith("buffer_load") and x.op != "s_nop"], [x for x in pc if x.op.startswith("buffer_load")]
-                add(g - 1, 3, setup)
-                add(g, 0, load if mf else [I("s_nop", 0)] + load)
-            post += [I("s_add_u32", S_VDMA, S_VDMA, S_V64), I("s_add_u32", S_KDMA, S_KDMA, S_K64)]
-        # scalar work rides in the first gaps one UNIT at a time: an instruction that consumes SCC (the s_addc of a 64-bit
-        # add, a select or branch on a compare) stays glued to the instructions since its producer -- other fillers write
-        # SCC too (the DMA set-up's s_add_u32), and a descriptor base once lost its carry that way (check.py R9)
-        units = []
-        for ins in early:
-            d_, u_ = ins.defs_uses()
-            if ("scc", 0) in u_ and units:
-                units[-1].append(ins)
-            else:
-                units.append([ins])
-        ne = len(units)
-        for k, unit in enumerate(units):
-            add(1 + 12 * k // max(ne, 1), 2, unit)   # done before this phase's own DMA pieces (gap 15 on) and the late ones
-        for g, setup, load in late:   # (gap pairs disjoint from the own pieces': both use M0 and the scratch offset register)
-            add(g - 1, 3, setup)
-            add(g, 0, [load])
-        if nxt and "nostart" not in abl:
-            for k, ins, is_exp in self.tile_fill(Y, 32, 32 + NB, nxt_init, masks, abl=abl, qbs=nxt_qbs):
-                add(k, 1 if is_exp else 2, ins)
-        if not mf:
-            body = [x for k in sorted(gaps) for _, ins in sorted(gaps[k], key=lambda x: x[0]) for x in ins]
-        else:
-            body = self.emit_phase(mf, gaps)
-        body = head + body + post + post_arg
-        if nxt and not nxt_init or True:
-            # deferred rescale of O and the row sums by the factors the decisions of this step left (rare)
-            l_rs, l_back = self.lab("rescale"), self.lab("rescale_back")
-            body += [I("s_cmp_lg_u32", S_FLAG, 0), I("s_cbranch_scc1", Label(l_rs)), label(l_back)]
-            # (bit qb of S_FLAG: query block qb fired in this step -- only its accumulators are touched; packed multiplies: the
-            # matrix pipe is idle here.  f16 inputs fire a few times per job: P must stay below 65 504)
-            blk = [label(l_rs), I("s_nop", 15)]
-            tmp = [V(V_T[k]) for k in range(8)]
-            co = V(V_T[8], 2)      # (an even register: the factor is read as the low word of an aligned 64-bit operand)
-            for qh in range(2):
-                l_skip = self.lab("rescale_skip")
-                blk += [I("s_bitcmp1_b32", S_FLAG, qh), I("s_cbranch_scc0", Label(l_skip))]
-                for q in (2 * qh, 2 * qh + 1):
-                    blk += [I("v_mov_b32", co.sub(0), V(V_CO[q])), I("s_nop", 0)]
-                    for base in range(0, 32, 8):
-                        regs = [A(q * 32 + base + k) for k in range(8)]
-                        blk += [I("v_accvgpr_read_b32", tmp[k], regs[k]) for k in range(8)]
-                        blk += [I("v_pk_mul_f32", V(tmp[k].idx, 2), V(tmp[k].idx, 2), co, op_sel_hi=(1, 0)) for k in range(0, 8, 2)]
-                        blk += [I("v_accvgpr_write_b32", regs[k], tmp[k]) for k in range(8)]
-                    blk += [I("v_pk_mul_f32", V(V_LACC[q] + k, 2), V(V_LACC[q] + k, 2), co, op_sel_hi=(1, 0)) for k in (0, 2)]
-                    blk += [I("v_mov_b32", V(V_CO[q]), 1.0)]
-                blk += [label(l_skip)]
-            blk += [I("s_mov_b32", S_FLAG, 0), I("s_nop", 3), I("s_branch", Label(l_back))]
-            self.ool.append(blk)
-        return body
-
-    def sync_mid(self, steady=False, vm=None):
-        if vm is not None:
-            return [waitcnt(vmcnt=vm, lgkmcnt=0), I("s_barrier")]
-        if steady and "novmwait" in self.abl:
-            return [waitcnt(lgkmcnt=0), I("s_barrier")]
-        if steady and "nobarrier" in self.abl:
-            return [waitcnt(vmcnt=self.vm, lgkmcnt=0)]
-        out = [waitcnt(vmcnt=self.vm, lgkmcnt=0, comment="the DMA pieces the next reads need have landed; V fragments in"), I("s_barrier")]
-        if steady and "skew" in self.abl:   # experiment: wave w leaves the barrier 8 w cycles late
-            l1, l2 = self.lab("skew1"), self.lab("skew2")
-            out += [I("s_bitcmp1_b32", S_WAVE, 0), I("s_cbranch_scc0", Label(l1)), I("s_nop", 7), label(l1),
-                    I("s_bitcmp1_b32", S_WAVE, 1), I("s_cbranch_scc0", Label(l2)), I("s_nop", 15), label(l2)]
-        return out
-
-    def step(self, t4, a_pre=(), **kw):
-        """one tile step, t4 = t & 3"""
-        ka = {k: v for k, v in kw.items() if k in ("with_qk", "cur", "nxt", "nxt_init", "steady", "dma", "cur_masks", "extra",
-                                                   "cur_qbs", "nxt_qbs")}
-        kb = {k: v for k, v in kw.items() if k in ("with_pv", "nxt", "nxt_init", "with_kread", "with_dma", "steady", "pre", "early", "late",
-                                                   "own_gaps", "post", "cur_qbs", "nxt_qbs")}
-        if kw.get("masks") is not None:   # the masking tests of a score group sit in front of its first row-maximum operation
-            ka["masks"] = kw["masks"]
-            kb["masks"] = kw["masks"]
-        out = [comment(f"---- step {t4}: phase A")]
-        out += self.stamp_acc(2)
-        out += list(a_pre)
-        out += [waitcnt(lgkmcnt=0, comment="K fragments in")]
-        out += self.phase_a(t4, **ka)
-        out += self.stamp_acc(0)
-        out += self.sync_mid(kw.get("steady", False), kw.get("vm"))
-        out += self.stamp_acc(1)
-        if kw.get("mid_stamp") is not None:      # (diagnostic builds: the seam's steps 2 and 3 split at their barrier)
-            out += self.stamp(kw["mid_stamp"])
-        out += [comment(f"---- step {t4}: phase B")]
-        out += self.phase_b(t4, **kb)
-        return out
+    def rescale(self, qh, tmp, co):
+        """the out-of-line rescale of query half qh (bit qh of S_FLAG): the 16-row blocks 2 qh, 2 qh + 1"""
+        l_skip = self.lab("rescale_skip")
+        blk = [I("s_bitcmp1_b32", S_FLAG, qh), I("s_cbranch_scc0", Label(l_skip))]
+        for q in (2 * qh, 2 * qh + 1):
+            blk += [I("v_mov_b32", co.sub(0), V(V_CO[q])), I("s_nop", 0)]
+            for base in range(0, 32, 8):
+                regs = [A(q * 32 + base + k) for k in range(8)]
+                blk += [I("v_accvgpr_read_b32", tmp[k], regs[k]) for k in range(8)]
+                blk += [I("v_pk_mul_f32", V(tmp[k].idx, 2), V(tmp[k].idx, 2), co, op_sel_hi=(1, 0)) for k in range(0, 8, 2)]
+                blk += [I("v_accvgpr_write_b32", regs[k], tmp[k]) for k in range(8)]
+            blk += [I("v_pk_mul_f32", V(V_LACC[q] + k, 2), V(V_LACC[q] + k, 2), co, op_sel_hi=(1, 0)) for k in (0, 2)]
+            blk += [I("v_mov_b32", V(V_CO[q]), 1.0)]
+        return blk + [label(l_skip)]
 
     # ------------------------------------------------------------------ epilogue of the current job
-    def epilogue_descs(self):
-        """descriptors of the current job's O rows (S_SQ: the next job's Q rows are through by then) and L (S_NVRS: the next job's V
-        descriptor has moved to S_VRS): scalar work that rides in the gaps of the seam's last phase B instead of standing in
-        front of the epilogue"""
-        return self.make_desc(S_SQ, S_O, S_OSB, S_OSH, S_B, S_HH, S_OSN) + self.make_desc(S_NVRS, S_L, S_LSB, S_LSH, S_B, S_HH, 2)
 
     def k_epilogue(self):
         """1 / l (one Newton step), L = m + log2 l, O^T -> rows through the wave's LDS slice -> 16-byte row stores, O^T := 0.
@@ -1353,199 +972,6 @@ class Gen:
                 e(label(l_last))
         # the row sums of the next job start from zero (their registers held the epilogue's lane constants until the last store)
         e([I("v_mov_b32", V(V_LACC[q] + k), 0) for q in (1, 2, 3, 0) for k in range(4)])
-
-    # ------------------------------------------------------------------ the whole kernel
-    def build(self):
-        e = self.e
-        name = self.name
-        l_job, l_loop, l_seam, l_end = (f".L{name}_{s}" for s in ("job", "loop", "seam", "end"))
-        self.k_setup()
-        e(I("s_cmp_ge_u32", S_JOB, S_TOTAL), I("s_cbranch_scc1", Label(l_end)))
-        # ---- first job of this workgroup: decode, descriptors, first loads, pipeline fill
-        self.k_decode_next()
-        self.k_promote()
-        self.k_advance()      # (every later job is decoded in its predecessor's epilogue, under the row stores)
-        e(comment("first job: K / V descriptors, K(0..2), V(0..1) by LDS-DMA, Q rows"))
-        e(self.make_desc(S_KRS, S_K, S_KSB, S_KSH, S_B, S_HH, S_KSN), self.make_desc(S_VRS, S_V, S_VSB, S_VSH, S_B, S_HH, S_VSN))
-        e(I("s_mov_b32", S_KDMA, S_KW), I("s_mov_b32", S_VDMA, S_VW))
-        e(self.stamp(0))
-        # (the first QK^T needs the Q rows and K(0) only: they go first, and the wait in front of the first barrier leaves the other
-        # tiles in flight -- all 256 workgroups start at once and the burst is bandwidth-bound, ~7 us for everything)
-        qs_setup, qs_pieces = self.q_stage(S_B, S_HH, S_QI)
-        e(qs_setup, [pc + [I("s_nop", 0), ld] for pc, ld in qs_pieces])
-        late = []
-        for j in range(self.dk - 1):
-            (e if j == 0 else late.append)(self.dma_tile("k", j % self.R))
-            if j < self.dv - 1:
-                late.append(self.dma_tile("v", j % self.R))
-        e(late)
-        n_late = sum(1 for t in late for x in t if x.op.startswith("buffer_load"))
-        e([I("v_accvgpr_write_b32", A(k), 0) for k in range(128)])   # O^T := 0
-        e(waitcnt(vmcnt=n_late), I("s_barrier"))
-        e(self.stamp(1))
-        e(self.q_reads(), self.k_reads(0))
-        # step -1 (buffers as t4 = 3): A = QK^T(0) only; B = start(0) as init, K(1) reads, DMA V(2), K(3)
-        e(self.step(3, with_qk=True, cur=False, with_pv=False, nxt_init=True, masks=(0, (S_NT, 4)) if self.causal else None))
-        e(self.stamp(2), self.stamp_flush(), self.stamp_acc(3), self.stamp_job(3))
-        # ---- job loop
-        e(label(l_job))
-        e(I("s_lshr_b32", S_LOOP, S_NT, 2), I("s_sub_u32", S_LOOP, S_LOOP, 1),
-          I("s_cmp_eq_u32", S_LOOP, 0), I("s_cbranch_scc1", Label(l_seam)))
-        e(label(l_loop))
-        for t4 in range(4):
-            # causal: the last steady body starts the job's first diagonal tile in its last phase B
-            tailm = ("tail", 0, (S_LOOP, 1)) if self.ragged and not self.causal else None
-            e(self.step(t4, steady=True, masks=((0, (S_LOOP, 1)) if self.causal else tailm) if t4 == 3 else None))
-        e(I("s_sub_u32", S_LOOP, S_LOOP, 1), I("s_cmp_lg_u32", S_LOOP, 0), I("s_cbranch_scc1", Label(l_loop)))
-        e(label(l_seam))
-        e(self.stamp(3), self.stamp_acc(2), self.stamp_flush(), self.stamp_job(0))
-        # ---- the job's last four tiles: the next job's K / V / Q stream in, its first QK^T and softmax start run here
-        cm = self.causal
-        if True:
-            kpre = self.make_desc(S_KRS, S_K, S_KSB, S_KSH, S_NB, S_NHH, S_KSN) + [I("s_mov_b32", S_KDMA, S_KW)] + \
-                self.make_desc(S_NVRS, S_V, S_VSB, S_VSH, S_NB, S_NHH, S_VSN)
-            vpre = [I("s_mov_b32", S_VRS.sub(k), S_NVRS.sub(k)) for k in range(4)] + [I("s_mov_b32", S_VDMA, S_VW)]
-            sk, sv = 4 - self.dk, 4 - self.dv      # seam step whose phase B streams the next job's first K / V tile
-            assert sk <= 2 and sv <= 2             # (step 3 re-uses S_SQ and S_NVRS for the epilogue's descriptors)
-            qs_setup, qs_pieces = self.q_stage(S_NB, S_NHH, S_NQI)
-            for st in range(4):
-                kw = dict(masks=((st + 1,) if st < 3 else (0, (S_NNT, 4))) if cm else None, cur_masks=(st,) if cm else None)
-                if self.ragged and not cm:   # keys at or behind N in the job's last four tiles (a ragged N has at least eight)
-                    kw = dict(masks=("tail", st + 1) if st < 3 else None, cur_masks=("tail", st))
-                early, pre = [], []
-                if st == 0:
-                    # the next job's Q rows start their way into the wave's LDS slice: sixteen pieces, never more than one
-                    # DMA piece per two gaps (that rate is free beside the MFMAs): eight behind this step's own K / V pieces,
-                    # four in the quiet end of the next phase A, four in front of the next step's own.  The barrier waits
-                    # in between leave them in flight (vmcnt(8 / 12 + ...)); the one of step 2 retires them
-                    early += qs_setup
-                    kw.update(own_gaps=(1, 3, 5, 7, 11, 13, 15, 17),
-                              late=[(g, *qs_pieces[k]) for k, g in enumerate((21, 23, 25, 27, 31, 33, 35, 37))])
-                if st == 1:
-                    kw.update(vm=self.vm + 12,
-                              dma=[(g, *qs_pieces[8 + k]) for k, g in enumerate((24, 26, 28, 30))],
-                              late=[(g, *qs_pieces[12 + k]) for k, g in enumerate((1, 3, 5, 7))])
-                if st == sk:
-                    early += kpre
-                if st == sv:
-                    pre += vpre
-                if st == 2 and "noqreads" not in self.abl:   # (timing-only ablation: what the AGPR-destination reads cost)
-                    early += self.q_reads()      # slice -> a[128:191] (Q was last read by this step's phase A)
-                if st == 3:
-                    early += self.epilogue_descs()
-                    # the job's last tile: its running maxima are put aside for the epilogue before the next job's first
-                    # tile re-initialises them (its row sums stay in V_LACC until the epilogue has read them)
-                    save = [I("v_mov_b32", V(V_MSV[q]), V(V_MC[q])) for q in range(4)]
-                    if (cm and not self.split) or (self.ragged and not cm):   # (behind the tile's 'mr': until then V_MSV holds what 'ms' put aside, mask_lazy)
-                        kw.update(nxt_init=True, extra=list(kw.get("extra", ())) + [(self.LAZY_TAU["mr"] - self.PERIOD + 1, save)])
-                    else:
-                        kw.update(nxt_init=True, a_pre=save)
-                e(self.stamp(16 + st))
-                if self.split:
-                    # split row map (wave w: 32-row blocks w and w + 4).  Diagonal tile j -- key blocks 2 j, 2 j + 1 -- against
-                    # query block 0 (row block w): hidden for w < 2 j, on the diagonal for w = 2 j (D0) / 2 j + 1 (D1), visible
-                    # above; against query block 1 (row block w + 4): the same with w + 4.  So tile 0: everything runs (waves
-                    # 0 / 1 mask block 0), tile 1: block 0 only on waves 2, 3 (which mask it), tile 2: block 1 only (waves 0 / 1
-                    # mask), tile 3: block 1 on waves 2, 3 only (which mask).  Step st finishes tile st and starts tile st + 1:
-                    # two bodies per step, waves 0-1 ("low") out of line, waves 2-3 ("high") in line, each with only the MFMAs
-                    # and softmax operations of the blocks it needs -- 216 MFMA slots on the critical path instead of 288.
-                    cur_q = (((0, 1), (0, 1)), ((1,), (0, 1)), ((1,), (1,)), ((), (1,)))[st]
-                    nxt_q = (((1,), (0, 1)), ((1,), (1,)), ((), (1,)), ((0, 1), (0, 1)))[st]
-                    l_low, l_join = self.lab("low"), self.lab("low_join")
-                    e(I("s_cmp_lt_u32", S_WAVE, 2), I("s_cbranch_scc1", Label(l_low)))
-                    for ci, cls in ((1, "high"), (0, "low")):
-                        ckw = dict(kw)
-                        cq, nq_ = cur_q[ci], nxt_q[ci]
-                        ckw.update(cur_qbs=cq or (0, 1), nxt_qbs=nq_ or (0, 1))
-                        if not cq:
-                            ckw.update(cur=False, with_pv=False)
-                        if not nq_:
-                            ckw.update(with_qk=False, nxt=False)
-                        self.cls = cls
-                        if cls == "high":
-                            e(self.step(st, early=early, pre=pre, mid_stamp=20 + st if st >= 2 else None, **ckw), label(l_join))
-                        else:
-                            body, self.prog = self.prog, []
-                            e(label(l_low), self.step(st, early=early, pre=pre, **ckw), I("s_branch", Label(l_join)))
-                            self.ool.append(self.prog)
-                            self.prog = body
-                        self.cls = None
-                    continue
-                lean = cm and st >= 1 and "nolean" not in self.abl
-                half = cm and st < 3 and "nolean" not in self.abl
-                if lean:
-                    # waves below this step's diagonal tile (w < st): the tile whose softmax finishes and whose P.V runs here is
-                    # hidden from them, and so is the one that starts (steps 1, 2; step 3 starts the next job's first tile).
-                    # They take a body with the same loads, DMA pieces, waits and barriers but without those MFMAs and softmax
-                    # operations, and idle at the barriers: at the package power limit what one wave does not execute, the
-                    # others run faster (+1.2 % on c3 causal, A/B in one process).  Such a wave's running maximum was swapped for
-                    # +inf when the hidden tile started ('ms'): the lean body puts it back.
-                    l_lean, l_join = self.lab("lean"), self.lab("lean_join")
-                    e(I("s_cmp_lt_u32", S_WAVE, st), I("s_cbranch_scc1", Label(l_lean)))
-                if half:
-                    # the wave ON this step's diagonal (w == st): the tile that starts here is hidden from it -- no QK^T, no start
-                    # of its softmax (+0.2 % at c3, +1 % at N = 2048 on top of the lean bodies)
-                    l_half = self.lab("half")
-                    l_join2 = l_join if lean else self.lab("half_join")
-                    e(I("s_cmp_eq_u32", S_WAVE, st), I("s_cbranch_scc1", Label(l_half)))
-                e(self.step(st, early=early, pre=pre, **kw))
-                if lean or half:
-                    e(label(l_join if lean else l_join2))
-                    body, self.prog = self.prog, []
-                    if lean:
-                        lkw = dict(kw)
-                        lkw["a_pre"] = [I("v_mov_b32", V(V_MC[qb]), V(V_MSV[qb])) for qb in range(2)] + list(kw.get("a_pre", ()))
-                        lkw.update(dict(with_qk=False, cur=False, nxt=False, with_pv=False) if st < 3 else dict(cur=False, with_pv=False))
-                        e(label(l_lean), self.step(st, early=early, pre=pre, **lkw), I("s_branch", Label(l_join)))
-                    if half:
-                        hkw = dict(kw)
-                        # (no 'ms' runs for the hidden tile: the lean body of the next step restores from V_MSV all the same)
-                        hkw["a_pre"] = list(kw.get("a_pre", ())) + [I("v_mov_b32", V(V_MSV[qb]), V(V_MC[qb])) for qb in range(2)]
-                        hkw.update(with_qk=False, nxt=False)
-                        e(label(l_half), self.step(st, early=early, pre=pre, **hkw), I("s_branch", Label(l_join2)))
-                    self.ool.append(self.prog)
-                    self.prog = body
-        e(self.stamp(4), self.stamp_job(1))
-        self.k_epilogue()
-        e(self.stamp(5))
-        # (S_FLAG: S_FINAL as it stood in front of the epilogue's job bookkeeping; back to 0 for the next step's rescale flag)
-        e(I("s_cmp_lg_u32", S_FLAG, 0), I("s_mov_b32", S_FLAG, 0), I("s_cbranch_scc1", Label(l_end)))
-        e(self.stamp(0), self.stamp_acc(3), self.stamp_job(2))
-        e(I("s_branch", Label(l_job)))
-        e(label(l_end), self.stamp_job(2), self.stamp_job_flush(), waitcnt(vmcnt=0), self.stamp(7, real=True), self.stamp(9), I("s_endpgm"))
-        for blk in self.ool:
-            e(blk)
-        from .check import check_branch_targets, fix
-        self.prog, self.pads = fix(self.prog)
-        bad = check_branch_targets(self.prog)
-        assert not bad, ("a branch enters a block that touches fresh MFMA results", bad[:4])
-        return self.prog
-
-    # ------------------------------------------------------------------ text
-    def lds_total(self):
-        return LDS_TOTAL
-
-    def text(self):
-        lines = [f".protected {self.name}", f".globl {self.name}", ".p2align 8", f".type {self.name},@function", f"{self.name}:"]
-        lines += [x.text() for x in self.prog]
-        lines += [f".L{self.name}_fend:", f".size {self.name}, .L{self.name}_fend-{self.name}", "",
-                  '.section .rodata,"a",@progbits', ".p2align 6, 0x0", f".amdhsa_kernel {self.name}",
-                  f"  .amdhsa_group_segment_fixed_size {self.lds_total()}", "  .amdhsa_private_segment_fixed_size 0",
-                  f"  .amdhsa_kernarg_size {KARG_SIZE}", "  .amdhsa_user_sgpr_count 2", "  .amdhsa_user_sgpr_kernarg_segment_ptr 1",
-                  "  .amdhsa_system_sgpr_workgroup_id_x 1", "  .amdhsa_system_vgpr_workitem_id 0",
-                  "  .amdhsa_next_free_vgpr 512", "  .amdhsa_next_free_sgpr 102", "  .amdhsa_accum_offset 256",
-                  "  .amdhsa_reserve_vcc 1", "  .amdhsa_ieee_mode 1", "  .amdhsa_dx10_clamp 1",
-                  "  .amdhsa_float_round_mode_32 0", "  .amdhsa_float_round_mode_16_64 0",
-                  "  .amdhsa_float_denorm_mode_32 3", "  .amdhsa_float_denorm_mode_16_64 3", ".end_amdhsa_kernel", ".text", ""]
-        return "\n".join(lines)
-
-    def metadata(self):
-        return "\n".join([
-            f"  - .args:", f"      - .offset: 0", f"        .size: {KARG_SIZE}", f"        .value_kind: by_value",
-            f"    .group_segment_fixed_size: {self.lds_total()}", f"    .kernarg_segment_align: 8", f"    .kernarg_segment_size: {KARG_SIZE}",
-            f"    .max_flat_workgroup_size: 256", f"    .name: {self.name}", f"    .private_segment_fixed_size: 0",
-            f"    .sgpr_count: 108", f"    .symbol: {self.name}.kd", f"    .vgpr_count: 512", f"    .agpr_count: 256",
-            f"    .wavefront_size: 64"])
 
 
 def product_gens():

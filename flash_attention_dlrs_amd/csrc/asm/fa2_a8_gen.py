@@ -27,13 +27,15 @@ the exact maximum does not pass the threshold (the oracle's decision).
 """
 from __future__ import annotations
 
-import sys
 
-from .isa import A, EXEC, I, Inst, Label, M0, Reg, S, V, VCC, comment, label, waitcnt
+from .isa import A, EXEC, I, Label, M0, Reg, S, V, VCC, comment, label, waitcnt
+from .stream_gen import (KARG_SIZE, NSLOT, SBUF, S_C, S_DBG, S_FINAL, S_FIRE, S_FLAG, S_JOB, S_K32, S_K64, S_KARG, S_KDMA,
+                         S_KRS, S_KSN, S_KT0, S_KW, S_LDSW, S_LG, S_N, S_NQ, S_NVRS, S_OSN, S_PASS, S_Q, S_QROW, S_QSB, S_QSH,
+                         S_QSN, S_SQ, S_T, S_THR, S_V32, S_V64, S_VDMA, S_VRS, S_VSN, S_VW, S_WAVE, S_WGID, S_X2, StreamGen)
 
 # ------------------------------------------------------------------------------------------------- register map
 # arch VGPRs
-SBUF = (0, 64)            # two score buffers of 64 registers: group g = 2*qb + kb at +16 g; packed P(qb): the first 8 of + 32 qb
+# SBUF = (0, 64) (stream_gen): two score buffers of 64 registers: group g = 2*qb + kb at +16 g; packed P(qb): the first 8 of + 32 qb
 KF = 128                  # K fragments of the next tile: (kb, ks) at KF + 8 (2 kb + ks), 8 registers each
 V_KR = (160, 161, 162, 163)   # K row-read lane bases, per (ks, u): chunk 4 ks + 2 u + h
 V_VR = (164, 165, 166, 167)   # V transposed-read lane bases per 32-column block db (the V ring's LDS offset included)
@@ -98,35 +100,9 @@ def swz_v(row):
     return ((row >> 1) & 1) | (((row >> 3) & 1) << 1)
 
 
-# SGPRs.  s4..s47 hold the kernel arguments (loaded once).
-S_KARG = S(0, 2)
-S_WGID = S(2)
-S_FINAL = S(75)
-S_Q, S_K, S_V, S_O, S_L = S(4, 2), S(6, 2), S(8, 2), S(10, 2), S(12, 2)
-S_QSB, S_QSH, S_KSB, S_KSH, S_VSB, S_VSH, S_OSB, S_OSH, S_LSB, S_LSH = (S(14 + 2 * k, 2) for k in range(10))
-S_QSN, S_KSN, S_VSN, S_OSN = S(34), S(35), S(36), S(37)
-S_N, S_H, S_NQ, S_TOTAL = S(38), S(39), S(40), S(41)
-S_C, S_THR, S_NUNIT, S_G = S(42), S(43), S(44), S(45)
-S_NBH, S_NWG = S(46), S(47)
-S_KRS, S_VRS, S_NVRS, S_SQ = S(48, 4), S(52, 4), S(56, 4), S(60, 4)   # K / V descriptors, the next job's V, a scratch one
-S_NB, S_NHH, S_NQI, S_NNT = S(64), S(65), S(66), S(67)                # the next job
-S_JOB, S_WAVE = S(68), S(69)
-S_KDMA, S_VDMA = S(70), S(71)    # source offset of the next K / V tile to stream (the wave's row base included)
-S_K32, S_V32 = S(72), S(74)      # 32 rows of K / V in bytes
-S_K64, S_V64 = S(76), S(77)
-S_LDSW = S(78)                   # 2048 * wave: the wave's piece offset inside a ring buffer
-S_LOOP, S_FLAG = S(79), S(80)
-S_QI, S_B, S_HH, S_UNIT, S_PASS, S_NT = S(81), S(83), S(84), S(85), S(86), S(87)   # the current job
-S_T = tuple(S(88 + k) for k in range(8))  # temporaries s88..s95 (S_T[0] even: usable as a 64-bit pair)
-S_QROW = (S(96), S(97))          # first row of the wave's query block qb (current job)
-S_DBG = S(98, 2)
+# SGPRs: the map shared by all four families is stream_gen's.
 S_NDESC, S_DESC = S(98), S(99)   # (product builds: the debug pointer's registers) causal: the next / the current job walks its
 #                                  non-diagonal key tiles in DESCENDING order (k_decode_next)
-S_KW, S_VW = S(100), S(101)      # 8 * wave * row stride: the wave's row base inside a tile
-S_KT0 = S(86)                    # (= S_PASS, causal only) non-causal ragged: real keys in the job's last 256 = N - 256 (nq - 1)
-S_LG = S(73)                     # decode shifts: lgH | lgG << 8 | lg(G * nunit) << 16 | pow2-mode << 24
-S_FIRE = (S(0, 2), S(2, 2))      # per query block: lanes whose row maximum passed the deferral threshold (s0..s3 are free after the set-up)
-S_X2 = S(82)
 
 # LDS map (bytes)
 KB = (0, 8192, 16384, 24576)     # rings of up to four 8-KiB buffers (Gen.R of them are used)
@@ -138,16 +114,26 @@ EPI_ROW = 136                    # (= 128 + 8) byte stride of an O row in the sl
                                  # row read-back, the 4-byte column writes of 32 lanes are 2-way (free for ds_write_b32)
 LDS_TOTAL = 65536 + 4 * 16384
 
-KARG_SIZE = 192
-NSLOT = 24
 
+class Gen(StreamGen):
+    # the family's registers and LDS size, as the shared stream methods read them (stream_gen.StreamGen)
+    V_T, V_ST_LAST, V_ST_ACC, V_MC, V_MX, V_CO, V_MSV, V_LACC, V_LANE, V_IMH, V_PM, NINF = \
+        V_T, V_ST_LAST, V_ST_ACC, V_MC, V_MX, V_CO, V_MSV, V_LACC, V_LANE, V_IMH, V_PM, NINF
+    S_NDESC, S_DESC = S_NDESC, S_DESC
+    LDS_TOTAL = LDS_TOTAL
+    FAMILY, MFMA = "a8", "v_mfma_f32_32x32x64_f8f6f4"
+    CVT = {"e4m3": "v_cvt_pk_fp8_f32", "e5m2": "v_cvt_pk_bf8_f32"}
+    DMA_PIECES, K_READS, V_READS = 2, 8, 16
+    DMA_GAPS = (11, 15, 21, 25)
+    # the seam's eight Q-staging pieces: four behind step 0's own K / V pieces, two in the quiet end of the next phase A, two in
+    # front of step 1's own; the barrier wait of step 1 leaves those six in flight
+    QS_GAPS = ((1, 5, 11, 15), (21, 25, 29, 33), (24, 28), (1, 5), 6)
+    O_AGPRS, ROW_BYTES, L_SN = 128, 128, 1
+    BRANCH_NEED, WALK_DOWN = 20, True
 
-class Gen:
     def __init__(self, dtype="bf16", causal=False, name=None, stamps=False, abl=(), ring=(2, 3, 2), vread_double=4, ragged=False,
                  caps=(5, 24), split=True, scaled=True):
-        assert dtype in ("e4m3", "e5m2"), "a8: OCP fp8"
         assert split or not causal, "a8: the causal kernels use the split row map"
-        self.dtype = dtype
         # scaled: P.V on v_mfma_scale_f32_32x32x64_f8f6f4.  fp8 P leaves 8.5 log2 units of deferral (e4m3 tops out at 448): on N(0, 1)
         # inputs at scale 1 (scores of sigma 16) a row's maximum passes it in a quarter of the tile steps, and a rescale of 64
         # accumulators costs the one wave of a SIMD ~900 cycles with the other three waiting at the barrier.  Here the running maximum
@@ -156,166 +142,8 @@ class Gen:
         # access (the row sums, four registers, are scaled by an exact power of two).  The guard re-bases O when m - m_O passes KMAX.
         self.scaled = scaled
         self.fmt = dict(cbsz=1, blgp=1) if dtype == "e5m2" else {}     # operand formats of the f8f6f4 MFMAs (0 = e4m3, 1 = e5m2)
-        self.causal = causal
-        self.name = name or f"fa2_fwd_a8_{dtype}_{'c' if causal else 'n'}{'r' if ragged else ''}{'' if scaled else '_unscaled'}"
-        self.atmp = 0          # (ragged) which of the two address temporaries the next buffer operation takes
-        self.atmp_regs = (V_T[8], V_T[9])
-        self.prog: list[Inst] = []
-        self.uid = 0
-        self.mfma = "v_mfma_f32_32x32x64_f8f6f4"
-        self.cvt = "v_cvt_pk_fp8_f32" if dtype == "e4m3" else "v_cvt_pk_bf8_f32"
-        self.ool: list[list[Inst]] = []  # out-of-line blocks (rare paths), appended after the main body
-        self.caps = caps       # fillers / issue cycles a gap behind a 32x32x16 MFMA may carry in the softmax plan
-        # causal row map "split": wave w owns the 32-row blocks w (qb 0) and w + 4 (qb 1) of the job's 256 rows instead of
-        # 2 w and 2 w + 1.  Diagonal tile j (key blocks 2 j, 2 j + 1) is then hidden from query block 0 of EVERY wave for
-        # j >= 2 and fully visible to query block 1 for j < 2: the job's last steps run on one query block (half the MFMAs)
-        # for all four waves instead of on both for a shrinking set of waves -- see build()
-        self.split = bool(split) and causal
-        self.cls = None        # split seam bodies: "low" (waves 0, 1) / "high" (waves 2, 3) while their code is generated
-        self.ragged = ragged   # N is not a multiple of 256: range-checked descriptors, every offset in the VGPR operand, masked key tail
-        assert not (ragged and stamps), "the ragged kernels use the stamps' temporaries as address registers"
-        self.vread_double = vread_double   # phase-A gaps that carry two V transposed reads (the last read sits in gap 31 - this)
-        self.abl = set(abl)    # timing-only ablations of the steady loop (diagnostic builds; results wrong by construction)
-        self.R, self.dk, self.dv = ring   # ring depth; K(t + dk) and V(t + dv) are streamed in phase B(t): dk <= R + 1, dv <= R
-        assert 3 <= self.dk <= min(self.R + 1, 4) and 2 <= self.dv <= self.R and 4 % self.R == 0
-        self.vm = 4 * min(self.dk - 3, self.dv - 2)  # DMA pieces that may stay in flight across the mid-step barrier
-        self._cache = {}
-        self.stamps = stamps   # diagnostic build: s_memtime stamps of the job timeline go to the debug buffer
-        # Causal, the LIGHT job of a unit walks DOWNWARDS (the host sets bit 25 of the decode word): a unit is the heavy job
-        # (query block nq - 1 - u, key tiles upwards) followed by the light job (query block u) of the same head.  All units of a head
-        # start their heavy job at tile 0 together and leave it behind their diagonal, after 4 (nq - u) steps; a light job that walks
-        # its non-diagonal tiles 4 u - 1 .. 0 downwards is at tile 4 nq - 1 - s at step s WHATEVER its u: the light jobs of a head
-        # form one stream in lockstep (each tile fetched once for all of them) that meets the tiles in the reverse of the order
-        # the heavy jobs left them in the XCD's L2 -- instead of every light job starting again at tile 0 at a time of its own
-        # (K / V came from beyond L2 2.0 times; profiles/r02/c3_a64_rocprof.json).  The diagonal tiles stay a job's last four,
-        # and the order is a function of (query block, nq) alone: a head's result does not depend on the launch it is part of.
-        self.down = causal and not stamps and not ragged
-
-    # ------------------------------------------------------------------ small helpers
-    def e(self, *insts):
-        for x in insts:
-            if isinstance(x, (list, tuple)):
-                self.e(*x)
-            else:
-                self.prog.append(x)
-
-    def lab(self, stem):
-        self.uid += 1
-        return f".L{self.name}_{stem}_{self.uid}"
-
-    def stamp(self, slot, real=False):
-        """diagnostic builds only: dbg[(wg * 4 + wave) * NSLOT + slot] = s_memtime (or s_memrealtime)"""
-        if not self.stamps:
-            return []
-        t = S(S_T[0].idx, 2)
-        v = V(V_T[8], 2)
-        return [I("s_memrealtime" if real else "s_memtime", t), waitcnt(lgkmcnt=0),
-                I("v_mov_b32", v.sub(0), t.sub(0)), I("v_mov_b32", v.sub(1), t.sub(1)),
-                I("v_mov_b32", V(V_T[7]), 0), I("global_store_dwordx2", V(V_T[7]), v, S_DBG, offset=8 * slot)]
-
-    ASYNC_PAIRS = (S(90, 2), S(92, 2), S(94, 2), S(0, 2), S(2, 2))   # S_T[2..7], S_FIRE: idle in the epilogue
-
-    def stamp_async(self, k):
-        """diagnostic builds only: s_memtime into spare pair k WITHOUT a wait (the epilogue's LDS queue is not drained; its
-        counted lgkmcnt waits may be satisfied early by the returning s_memtime: timing-only)"""
-        return [I("s_memtime", self.ASYNC_PAIRS[k])] if self.stamps else []
-
-    def stamp_async_flush(self, slots):
-        if not self.stamps:
-            return []
-        out = [waitcnt(lgkmcnt=0), I("v_mov_b32", V(V_T[7]), 0)]
-        v = V(V_T[8], 2)
-        for k, slot in enumerate(slots):
-            t = self.ASYNC_PAIRS[k]
-            out += [I("v_mov_b32", v.sub(0), t.sub(0)), I("v_mov_b32", v.sub(1), t.sub(1)),
-                    I("global_store_dwordx2", V(V_T[7]), v, S_DBG, offset=8 * slot), I("s_nop", 7)]
-        return out
-
-    def stamp_acc(self, k):
-        """diagnostic builds only: acc[k] += cycles since the previous stamp_acc (its s_waitcnt drains the LDS queue as well: the
-        per-phase shares cost cycles of their own -- the "lite" kernels carry the job-level stamps only)"""
-        if not self.stamps or "lite" in self.abl:
-            return []
-        t = S(S_T[0].idx, 2)
-        tmp = V(V_T[9])
-        acc = [I("v_sub_u32", tmp, t.sub(0), V(V_ST_LAST)), I("v_add_u32", V(V_ST_ACC + k), V(V_ST_ACC + k), tmp)] if k < 3 else []
-        return [I("s_memtime", t), waitcnt(lgkmcnt=0)] + acc + [I("v_mov_b32", V(V_ST_LAST), t.sub(0))]
-
-    def stamp_job(self, k):
-        """lite diagnostic builds: acc[k] += cycles since the previous stamp_job, summed over ALL jobs of the workgroup
-        (0 steady loops, 1 seam bodies, 2 epilogues + job bookkeeping, 3 the pipeline fill of the first job)"""
-        if not self.stamps or "lite" not in self.abl:
-            return []
-        t = S(S_T[0].idx, 2)
-        tmp = V(V_T[9])
-        acc = [I("v_sub_u32", tmp, t.sub(0), V(V_ST_LAST)), I("v_add_u32", V(V_ST_ACC + k), V(V_ST_ACC + k), tmp)] if k < 3 else []
-        return [I("s_memtime", t), waitcnt(lgkmcnt=0)] + acc + [I("v_mov_b32", V(V_ST_LAST), t.sub(0))]
-
-    def stamp_job_flush(self):
-        if not self.stamps or "lite" not in self.abl:
-            return []
-        out = [I("v_mov_b32", V(V_T[7]), 0)]
-        for k, slot in enumerate((10, 11, 12)):
-            out += [I("global_store_dword", V(V_T[7]), V(V_ST_ACC + k), S_DBG, offset=8 * slot)]
-        return out
-
-    def stamp_flush(self):
-        if not self.stamps or "lite" in self.abl:
-            return []
-        out = [I("v_mov_b32", V(V_T[7]), 0)]
-        for k in range(3):
-            out += [I("global_store_dword", V(V_T[7]), V(V_ST_ACC + k), S_DBG, offset=8 * (10 + k)),
-                    I("v_mov_b32", V(V_ST_ACC + k), 0)]
-        return out
-
-    def udiv(self, q: Reg, r: Reg | None, n: Reg, d: Reg, vt=None):
-        """q = n / d, r = n % d for wave-uniform 32-bit values < 2^22 (float reciprocal + one correction each way)"""
-        t0, t1 = vt if vt is not None else (V(V_T[0]), V(V_T[1]))
-        st, sr = S_T[6], S_T[7]
-        self.e(I("v_cvt_f32_u32", t0, n), I("v_cvt_f32_u32", t1, d), I("s_nop", 0), I("v_rcp_f32", t1, t1), I("s_nop", 1),
-               I("v_mul_f32", t0, t0, t1), I("v_cvt_u32_f32", t0, t0), I("s_nop", 1), I("v_readfirstlane_b32", q, t0), I("s_nop", 4),
-               I("s_mul_i32", st, q, d), I("s_sub_i32", sr, n, st),
-               # r < 0 -> q--, r += d
-               I("s_cmp_lt_i32", sr, 0), I("s_cselect_b32", st, 1, 0), I("s_sub_u32", q, q, st),
-               I("s_cmp_lt_i32", sr, 0), I("s_cselect_b32", st, d, 0), I("s_add_i32", sr, sr, st),
-               # r >= d -> q++, r -= d
-               I("s_cmp_ge_i32", sr, d), I("s_cselect_b32", st, 1, 0), I("s_add_u32", q, q, st),
-               I("s_cmp_ge_i32", sr, d), I("s_cselect_b32", st, d, 0), I("s_sub_i32", sr, sr, st))
-        if r is not None:
-            self.e(I("s_mov_b32", r, sr))
-
-    def mad64(self, dst: Reg, idx: Reg, stride: Reg):
-        """dst(64) += idx(32, unsigned) * stride(64)"""
-        lo, hi = S_T[6], S_T[7]
-        return [I("s_mul_i32", lo, idx, stride.sub(0)), I("s_mul_hi_u32", hi, idx, stride.sub(0)),
-                I("s_add_u32", dst.sub(0), dst.sub(0), lo), I("s_addc_u32", dst.sub(1), dst.sub(1), hi),
-                I("s_mul_i32", lo, idx, stride.sub(1)), I("s_add_u32", dst.sub(1), dst.sub(1), lo)]
-
-    def make_desc(self, rs: Reg, base: Reg, sb: Reg, sh: Reg, b: Reg, hh: Reg, sn=None):
-        """raw buffer descriptor of the (b, hh) slice of a tensor: base + b * sb + hh * sh.  N a multiple of 256: the range check
-        is not used (soffset is unchecked anyway; every address the kernel forms lies inside the tensor).  Ragged kernels:
-        num_records = (N - 1) * sn + 128 bytes of rows (sn: the row stride register; an int: bytes per row of L) -- loads of
-        rows past N come back as zeros, stores to them are dropped; those kernels keep every offset in the VGPR operand"""
-        tmp = S(S_T[0].idx, 2)
-        out = ([I("s_mov_b64", tmp, base)] + self.mad64(tmp, b, sb) + self.mad64(tmp, hh, sh) +
-               [I("s_mov_b32", rs.sub(0), tmp.sub(0)), I("s_and_b32", rs.sub(1), tmp.sub(1), 0xFFFF), I("s_mov_b32", rs.sub(3), 0x00020000)])
-        if not self.ragged:
-            return out + [I("s_mov_b32", rs.sub(2), 0x7FFFFFF0)]
-        assert sn is not None
-        if isinstance(sn, int):
-            return out + [I("s_mul_i32", rs.sub(2), S_N, sn)]
-        return out + [I("s_sub_u32", S_T[6], S_N, 1), I("s_mul_i32", S_T[6], S_T[6], sn), I("s_add_u32", rs.sub(2), S_T[6], 128)]      # (rows of 128 bytes here)
-
-    def buf_op(self, op, data, voff: Reg, rsrc: Reg, soff, **mods):
-        """a buffer operation at byte offset voff (per lane) + soff (scalar).  The scalar operand of the instruction is not
-        range-checked: the ragged kernels add it into an address temporary first (two, taken alternately: a set-up may run
-        ahead of the previous piece's load by one gap).  Returns (set-up instructions, the memory instruction)"""
-        ops = (lambda v, so: (data, v, rsrc, so) if data is not None else (v, rsrc, so))
-        if not self.ragged:
-            return [], I(op, *ops(voff, soff), offen=1, **mods)
-        tmp = V(self.atmp_regs[self.atmp])
-        self.atmp ^= 1
-        return [I("v_add_u32", tmp, soff, voff)], I(op, *ops(tmp, 0), offen=1, **mods)
+        name = name or f"fa2_fwd_a8_{dtype}_{'c' if causal else 'n'}{'r' if ragged else ''}{'' if scaled else '_unscaled'}"
+        super().__init__(dtype, causal, name, stamps, abl, ring, vread_double, ragged, caps, split)
 
     # ------------------------------------------------------------------ kernel prologue: arguments, lane constants
     def k_setup(self):
@@ -431,88 +259,6 @@ class Gen:
                     else:
                         e(I("v_cndmask_b32", t1, 0, t2, VCC), I("v_or_b32", V(V_PM[p_]), V(V_PM[p_]), t1))
 
-    # ------------------------------------------------------------------ job decode: S_JOB (+ S_PASS) -> S_NB, S_NHH, S_NQI, S_NNT
-    def k_decode_next(self, vt=None):
-        e = self.e
-        l_else, l_done = self.lab("dec_else"), self.lab("dec_done")
-        t = S_T
-        bh = S_X2
-        l_gen = self.lab("dec_generic")
-        e(comment("job index -> (b, h), work unit, query block, tile count of the NEXT job"),
-          I("s_bitcmp1_b32", S_LG, 24), I("s_cbranch_scc0", Label(l_gen)))
-        # H, G, G * nunit powers of two and B * H a multiple of 8 (the host says so): shifts and masks only
-        e(I("s_lshr_b32", t[0], S_JOB, 3),                                   # slot
-          I("s_lshr_b32", t[1], S_LG, 16), I("s_and_b32", t[1], t[1], 255),   # lg(G nunit)
-          I("s_lshr_b32", t[2], t[0], t[1]),                                  # batch
-          I("s_lshl_b32", t[3], 1, t[1]), I("s_sub_u32", t[3], t[3], 1), I("s_and_b32", t[3], t[0], t[3]),   # r
-          I("s_lshr_b32", t[1], S_LG, 8), I("s_and_b32", t[1], t[1], 255),    # lg G
-          I("s_lshr_b32", S_UNIT, t[3], t[1]),                                # unit = r >> lgG
-          I("s_lshl_b32", t[4], 1, t[1]), I("s_sub_u32", t[4], t[4], 1), I("s_and_b32", t[4], t[3], t[4]),   # r % G
-          I("s_lshl_b32", t[2], t[2], t[1]), I("s_add_u32", t[2], t[2], t[4]), I("s_lshl_b32", t[2], t[2], 3),
-          I("s_and_b32", t[0], S_JOB, 7), I("s_add_u32", bh, t[2], t[0]),
-          I("s_and_b32", t[1], S_LG, 255),                                    # lg H
-          I("s_lshr_b32", S_NB, bh, t[1]),
-          I("s_lshl_b32", t[4], 1, t[1]), I("s_sub_u32", t[4], t[4], 1), I("s_and_b32", S_NHH, bh, t[4]))
-        l_qi = self.lab("dec_qi")
-        e(I("s_branch", Label(l_qi)), label(l_gen),
-          I("s_and_b32", t[0], S_NBH, 7), I("s_cmp_lg_u32", t[0], 0), I("s_cbranch_scc1", Label(l_else)))
-        # slot = id >> 3; GN = G * nunit; batch = slot / GN; r = slot % GN; bh = (batch * G + r % G) * 8 + (id & 7); unit = r / G
-        e(I("s_lshr_b32", t[0], S_JOB, 3), I("s_mul_i32", t[1], S_G, S_NUNIT))
-        self.udiv(t[2], t[3], t[0], t[1], vt)       # batch, r
-        self.udiv(S_UNIT, t[4], t[3], S_G, vt)      # unit = r / G, r % G
-        e(I("s_mul_i32", t[2], t[2], S_G), I("s_add_u32", t[2], t[2], t[4]), I("s_lshl_b32", t[2], t[2], 3),
-          I("s_and_b32", t[0], S_JOB, 7), I("s_add_u32", bh, t[2], t[0]), I("s_branch", Label(l_done)))
-        e(label(l_else))
-        self.udiv(bh, S_UNIT, S_JOB, S_NUNIT, vt)
-        e(label(l_done))
-        self.udiv(S_NB, S_NHH, bh, S_H, vt)
-        e(label(l_qi))
-        if self.causal:
-            # unit u, pass 0: qi = nq - 1 - u (heavy), pass 1: qi = u;  tiles = 4 (qi + 1)
-            l_p1, l_pd = self.lab("pass1"), self.lab("passd")
-            e(I("s_cmp_lg_u32", S_PASS, 0), I("s_cbranch_scc1", Label(l_p1)),
-              I("s_sub_u32", S_NQI, S_NQ, 1), I("s_sub_u32", S_NQI, S_NQI, S_UNIT), I("s_branch", Label(l_pd)),
-              label(l_p1), I("s_mov_b32", S_NQI, S_UNIT), label(l_pd),
-              I("s_add_u32", t[0], S_NQI, 1), I("s_lshl_b32", S_NNT, t[0], 2))
-            if self.down:   # the light job of a unit walks downwards (unless it is nothing but its diagonal)
-                e(I("s_lshr_b32", t[0], S_LG, 25), I("s_and_b32", t[0], t[0], S_PASS), I("s_and_b32", t[0], t[0], 1),
-                  I("s_cmp_lg_u32", S_NQI, 0), I("s_cselect_b32", S_NDESC, t[0], 0))
-        else:
-            e(I("s_mov_b32", S_NQI, S_UNIT), I("s_lshl_b32", S_NNT, S_NQ, 2))      # (4 tiles per 256 rows, N rounded up)
-
-    def k_advance(self, vt=None):
-        """S_JOB / S_PASS -> the job after the most recently decoded one, decoded into the next-job registers;
-        S_FINAL = 1 if there is none (the next-job registers then repeat the current job).  vt: two VGPR temporaries for the
-        divisions of the generic decode (default V_T[0], V_T[1])"""
-        e = self.e
-        l_fin, l_ok = self.lab("adv_final"), self.lab("adv_ok")
-        if self.causal:
-            l_adv = self.lab("adv")
-            # pass 0 -> pass 1 of the same unit unless the pair is a single tile (nq odd, middle)
-            e(I("s_cmp_lg_u32", S_PASS, 0), I("s_cbranch_scc1", Label(l_adv)),
-              I("s_sub_u32", S_T[0], S_NQ, 1), I("s_sub_u32", S_T[0], S_T[0], S_UNIT), I("s_cmp_eq_u32", S_T[0], S_UNIT),
-              I("s_cbranch_scc1", Label(l_adv)),
-              I("s_mov_b32", S_PASS, 1), I("s_branch", Label(l_ok)),
-              label(l_adv), I("s_mov_b32", S_PASS, 0), I("s_add_u32", S_JOB, S_JOB, S_NWG))
-        else:
-            e(I("s_add_u32", S_JOB, S_JOB, S_NWG))
-        e(I("s_cmp_ge_u32", S_JOB, S_TOTAL), I("s_cbranch_scc1", Label(l_fin)), label(l_ok))
-        self.k_decode_next(vt)
-        l_done = self.lab("adv_done")
-        e(I("s_branch", Label(l_done)), label(l_fin),
-          comment("no further job: the seam streams the current job's first tiles again (results discarded)"),
-          I("s_mov_b32", S_FINAL, 1), I("s_mov_b32", S_NB, S_B), I("s_mov_b32", S_NHH, S_HH), I("s_mov_b32", S_NQI, S_QI),
-          I("s_mov_b32", S_NNT, S_NT), ([I("s_mov_b32", S_NDESC, S_DESC)] if self.down else []), label(l_done))
-
-    def k_promote(self):
-        """next job -> current job"""
-        self.e(([I("s_mov_b32", S_DESC, S_NDESC)] if self.down else []),
-               I("s_mov_b32", S_B, S_NB), I("s_mov_b32", S_HH, S_NHH), I("s_mov_b32", S_QI, S_NQI), I("s_mov_b32", S_NT, S_NNT),
-               # query rows of this wave: qrow[qb] = 256 qi + 64 wave + 32 qb  (split row map: 256 qi + 32 wave + 128 qb)
-               I("s_lshl_b32", S_T[0], S_QI, 8), I("s_lshl_b32", S_T[1], S_WAVE, 5 if self.split else 6),
-               I("s_add_u32", S_QROW[0], S_T[0], S_T[1]),
-               I("s_add_u32", S_QROW[1], S_QROW[0], 128 if self.split else 32))
-
     # ------------------------------------------------------------------ LDS-DMA
     def dma_piece(self, which, piece, buf):
         """one 1-KiB LDS-DMA piece of the next K / V tile into ring buffer `buf`: piece j = rows 8 R .. 8 R + 7 (whole 128-byte rows)
@@ -529,34 +275,6 @@ class Gen:
         out.append(I("s_add_u32", M0, S_LDSW, lds0 + 4096 * piece))
         pre, ld = self.buf_op("buffer_load_dwordx4", None, vl, rsrc, so, lds=1, tag=f"dma {which}{piece}")
         return out + pre + [I("s_nop", 0), ld]
-
-    def stream_start(self, which):
-        """causal: start offset and step of the NEXT job's K / V tile stream -- upwards from tile 0, or (S_NDESC) downwards from
-        the tile under the diagonal span, 4 qi - 1.  S_K64 / S_V64 hold the signed step of the running stream (fa2_a64_gen.py)"""
-        dma, w0, s32, step = (S_KDMA, S_KW, S_K32, S_K64) if which == "k" else (S_VDMA, S_VW, S_V32, S_V64)
-        if not self.down:
-            return [I("s_mov_b32", dma, w0)]
-        t0, t1 = S_T[6], S_T[7]     # (the 64-bit multiply's scratch: free between scalar units; S_T[2..4] belong to the Q staging)
-        return [I("s_lshl_b32", t0, s32, 1), I("s_lshl_b32", t1, S_NQI, 2), I("s_sub_u32", t1, t1, 1), I("s_mul_i32", t1, t1, t0),
-                I("s_cmp_lg_u32", S_NDESC, 0), I("s_cselect_b32", t1, t1, 0), I("s_add_u32", dma, w0, t1),
-                I("s_sub_u32", t1, 0, t0), I("s_cmp_lg_u32", S_NDESC, 0), I("s_cselect_b32", step, t1, t0)]
-
-    def stream_to_diagonal(self, which):
-        """causal, the steady loop's last trip: the stream has reached the job's diagonal span -- tiles 4 qi .. 4 qi + 3, upwards"""
-        if not self.down:
-            return []
-        dma, w0, s32, step = (S_KDMA, S_KW, S_K32, S_K64) if which == "k" else (S_VDMA, S_VW, S_V32, S_V64)
-        t0, t1 = S_T[6], S_T[7]
-        return [I("s_lshl_b32", t0, s32, 1), I("s_lshl_b32", t1, S_QI, 2), I("s_mul_i32", t1, t1, t0), I("s_add_u32", t1, t1, w0),
-                I("s_cmp_eq_u32", S_LOOP, 1), I("s_cselect_b32", dma, t1, dma),
-                I("s_cmp_eq_u32", S_LOOP, 1), I("s_cselect_b32", step, t0, step)]
-
-    def dma_tile(self, which, buf):
-        out = []
-        for j in range(2):
-            out += self.dma_piece(which, j, buf)
-        out.append(I("s_add_u32", S_KDMA, S_KDMA, S_K64) if which == "k" else I("s_add_u32", S_VDMA, S_VDMA, S_V64))
-        return out
 
     def q_stage(self, b: Reg, hh: Reg, qi: Reg):
         """Q rows of job (b, hh, qi) of this wave -> the wave's LDS slice by LDS-DMA, in the K-tile image (8 pieces of 8 rows x
@@ -624,149 +342,6 @@ class Gen:
         return out
 
     # ------------------------------------------------------------------ the softmax of one tile as a list of placed operations
-    # Time line of a tile, in MFMA gaps (tau): [0, 32) = the phase A that computes its scores (QK^T chains g = 0..3, eight
-    # MFMAs each), [32, 32 + NB) = the following phase B (NB = 40 MFMAs: P.V of the previous tile plus its row sums),
-    # [32 + NB, 64 + NB) = the next phase A, at whose end P must be packed (its own P.V follows).  In steady state the
-    # physical gap (tau mod PERIOD) therefore carries operations of two tiles: a modulo reservation table keeps every gap
-    # within what hides beside an MFMA (measured, scripts/probes/mb_run + asm/microbench.py: at most five fillers per gap,
-    # issue costs v_exp 8 / three-operand VALU 5 / two-operand 4 summing to <= 24; LDS reads first in their gap).
-    NB = 40
-    PERIOD = 72
-    T_END = 104
-    LAZY_TAU = {"ms0": 28, "ms1": 29, "mr": 99, "pm": 100}   # tau of the lazy-masking operations of a diagonal tile (mask_lazy)
-
-    def lazy_tau(self):
-        """(the split row map has no 'ms' / 'mr'; its packed-P masking sits behind the last pack of the plan, which ends two gaps
-        later there: tile_plan, gap2)"""
-        return dict(self.LAZY_TAU, pm=103) if self.split else self.LAZY_TAU
-
-    def tile_plan(self, init=False, lean=False):
-        """placement of the per-tile softmax operations: returns [(tau, kind, payload)] sorted by tau.
-        kinds: 'mx' (g, j)  'dec' (qb, part)  'f' e  'e' e  'cv' (g, j)"""
-        key = "plan"
-        if key in self._cache:
-            return self._cache[key]
-        P = self.PERIOD
-        slots = [0.0] * P
-        cost = [0.0] * P
-        nexp = [0] * P
-        cap_s = [float(self.caps[0])] * P
-        cap_c = [float(self.caps[1])] * P
-        # phase B: the gap behind a 16x16x32 row-sum MFMA is half as long
-        for b in self.b_short_gaps():
-            cap_s[32 + b], cap_c[32 + b] = 2.0, 8.0
-        # pre-reserved: the V transposed reads of phase A; K reads, DMA pieces and their scalar set-up in phase B
-        for k in range(16):
-            slots[self.a_vread_gap(k)] += 1
-            cost[self.a_vread_gap(k)] += 2
-        for b, n in self.b_reserved().items():
-            slots[32 + b] += n
-            cost[32 + b] += 3 * n
-        placed = []
-
-        def place(earliest, c, kind, payload, is_exp=False):
-            t = int(earliest)
-            while True:
-                assert t < self.T_END + 40, (kind, payload)
-                g = t % P
-                if slots[g] + 1 <= cap_s[g] and cost[g] + c <= cap_c[g] and (not is_exp or nexp[g] < 2):
-                    slots[g] += 1
-                    cost[g] += c
-                    nexp[g] += int(is_exp)
-                    placed.append((t, kind, payload))
-                    return t
-                t += 1
-        # row maxima: chain g may start 3 gaps after its last QK^T MFMA (12 wait states), one operation per gap and chain
-        t_mx = {}
-        for g in range(4):
-            # (chain g's last MFMA is number 8 g + 7, or 16 qb + 14 + kb with the chains of a query block interleaved)
-            t = 16 * (g >> 1) + 18 + (g & 1)      # (a64's: the chains of query block qb are complete behind slot 16 qb + 12)
-            for j in range(8):
-                t = place(t, 5, "mx", (g, j)) + 1
-            t_mx[g] = t
-        t_dec = {}
-        for qb in range(2):
-            t = max(t_mx[2 * qb], t_mx[2 * qb + 1])
-            # (the compare and the branch on it sit in different gaps: back to back the branch waits ~30 cycles for the mask.
-            # A job's first tile has no decision to take but keeps the slots: the loop body that finishes it is the one that
-            # finishes every other tile, so both placements must agree)
-            for part in range(5):
-                # (the branch two gaps behind its compare: with one MFMA between them the scalar compare waits ~10 cycles for the
-                # mask -- microbenchmark mb_cmps_a_scmp_brs against mb_cmps_aaa_scmp_brs -- and query block 0's pair sat in the last
-                # gaps in front of the mid-step barrier; now its branch is the first thing behind the barrier)
-                # (not where the lazy masking of the contiguous row map / the ragged key tail pins 'mr' in front of the last packs)
-                gap2 = part == 4 and "fire_adjacent" not in self.abl and (self.split or not (self.causal or self.ragged))
-                t = place(t + (1 if gap2 else 0), (9, 5, 9, 4, 2)[part], "dec", (qb, part)) + 1
-            t_dec[qb] = t
-        # (causal diagonal tiles handled lazily -- mask_lazy -- add four small operations at LAZY_TAU: gaps of phase A that are
-        # nearly empty in every tile, so the plan itself does not reserve anything for them)
-        t_d2 = {qb: next(t for t, k, p_ in placed if k == "dec" and p_ == (qb, 2)) for qb in range(2)}
-        lz = self.lazy_tau()
-        assert self.split or (lz["mr"] - P < lz["ms0"] < t_d2[0] and lz["mr"] - P < lz["ms1"] < t_d2[1])
-        assert lz["pm"] < self.T_END
-        # s' = s * c - m, exp2, pack -- element order inside a group is the packing order
-        for qb in range(2):
-            t_f = t_dec[qb]
-            last_cv = {}
-            for g in (2 * qb, 2 * qb + 1):
-                t_e_prev = None
-                for r in range(16):
-                    e = 16 * g + r
-                    tf = place(t_f, 5, "f", e)
-                    t_f = tf  # keep the fma stream in order (several per gap allowed)
-                    te = place(tf + 1, 8, "e", e, is_exp=True)
-                    if r & 1:
-                        j = r >> 1
-                        tc = max(te, t_e_prev) + 1
-                        if j - 1 in last_cv.get(g, {}):
-                            tc = max(tc, last_cv[g][j - 1] + 0)
-                        tc = place(tc, 5, "cv", (g, j))
-                        last_cv.setdefault(g, {})[j] = tc
-                    t_e_prev = te
-        if self.causal or self.ragged:     # (the kernels that mask lazily)
-            assert max(t for t, k, _ in placed if k == "cv") < (lz["pm"] if self.split else min(lz["mr"], lz["pm"])), \
-                "a pack operation behind the packed-P masking"
-        placed.sort(key=lambda x: x[0])
-        assert max(t for t, _, _ in placed) < self.T_END, max(t for t, _, _ in placed)
-        self._cache[key] = placed
-        return placed
-
-    def a_vread_gap(self, k):
-        """phase-A gap of V transposed read k: two per gap at the start, none in the last four -- the wait in front of the barrier
-        then finds the youngest read ~130 cycles old instead of just issued"""
-        nd = self.vread_double
-        return k // 2 if k < 2 * nd else k - nd
-
-    def b_short_gaps(self):
-        """indices (0..39) of the phase-B gaps that follow a 16x16x32 row-sum MFMA"""
-        return [10 * k + 8 for k in range(4)] + [10 * k + 9 for k in range(4)]
-
-    def b_reserved(self):
-        """phase-B gap -> number of pre-reserved fillers (K reads, DMA loads, DMA scalar set-up)"""
-        r = {}
-        for k in range(8):
-            r[self.b_kread_gap(k)] = r.get(self.b_kread_gap(k), 0) + 1
-        for k in range(4):
-            g = self.b_dma_gap(k)
-            r[g] = r.get(g, 0) + 1
-            r[g - 1] = r.get(g - 1, 0) + 1
-        return r
-
-    def b_kread_gap(self, k):
-        if "kfront" in self.abl:     # (experiment) two K reads per gap from the start of the phase
-            g = k // 2
-            while g in self.b_short_gaps():
-                g += 1
-            return g
-        g = 2 * k
-        while g in self.b_short_gaps():
-            g += 1
-        return g
-
-    def b_dma_gap(self, k):
-        """phase-B gap whose FIRST filler is DMA piece k's load; its scalar set-up (soffset, M0) ends the gap before, so the MFMA
-        between them is the wait state the M0 write needs.  Distinct, two apart, clear of the short row-sum gaps."""
-        return (11, 15, 21, 25)[k]
 
     def tile_op(self, Sb, kind, payload, init, lazy=None):
         """the instructions of one placed operation, for the tile whose scores live in score buffer Sb.
@@ -856,87 +431,7 @@ class Gen:
                       op_sel=(0, 0, j & 1), tag=f"cvt g{g} {j}")]
         raise KeyError(kind)
 
-    @staticmethod
-    def op_qb(kind, payload):
-        """query block a placed softmax operation belongs to (None: not tied to one)"""
-        if kind in ("mx", "cv"):
-            return payload[0] >> 1
-        if kind == "dec":
-            return payload[0]
-        if kind in ("f", "e"):
-            return payload >> 5
-        if kind == "ms":
-            return payload
-        return None
-
-    def tile_fill(self, Sb, lo, hi, init, masks=None, abl=(), qbs=(0, 1)):
-        """[(gap - lo, [insts], is_exp)] of the tile's operations with lo <= tau < hi.  masks: causal (jd, cond): the tile is
-        diagonal tile jd of its job (when cond = (sgpr, value) holds, if given).  A job's first tile (init) gets its scores
-        masked up front -- the tests of score group g go in front of its first row-maximum operation; every other diagonal
-        tile is masked lazily (mask_lazy)"""
-        out = []
-        seen_mask = set()
-        tail = masks is not None and masks[0] == "tail"     # non-causal ragged: ("tail", j[, cond]) -- seam tile j may hold keys >= N
-        if tail:
-            masks = masks[1:]
-        jd, cond = (masks + (None,))[:2] if masks is not None else (None, None)
-        lazy = (jd, cond) if masks is not None and not init else None
-        plan = self.tile_plan(init)
-        if lazy is not None:
-            lz = self.lazy_tau()
-            if self.split and not tail:
-                # split row map: a hidden (tile, query block) is not computed at all -- no running-maximum swap ('ms' / 'mr');
-                # the packed-P masking only where this body's waves sit on the tile's diagonal and the block is computed
-                pm = self.cls is not None and (jd >> 1) in qbs and self.cls == ("low", "high")[jd & 1]
-                plan = sorted(plan + ([(lz["pm"], "pm", None)] if pm else []), key=lambda x: x[0])
-            else:
-                plan = sorted(plan + [(lz["ms0"], "ms", 0), (lz["ms1"], "ms", 1), (lz["mr"], "mr", None)] +
-                              ([] if tail else [(lz["pm"], "pm", None)]), key=lambda x: x[0])
-        for t, kind, payload in plan:
-            if not (lo <= t < hi):
-                continue
-            if self.op_qb(kind, payload) is not None and self.op_qb(kind, payload) not in qbs:
-                continue
-            if ("no_" + kind) in abl or (kind == "dec" and payload[1] >= 3 and "no_fire" in abl):
-                continue   # timing-only ablations (diagnostic build)
-            if tail:
-                assert not init
-                ins = self.mask_tail(Sb, kind, payload, jd, cond) if kind in ("ms", "mr") else self.tile_op(Sb, kind, payload, init, None)
-            else:
-                ins = self.tile_op(Sb, kind, payload, init, lazy)
-            if not ins:
-                continue
-            if masks is not None and (init or tail) and kind == "mx" and payload[1] == 0 and payload[0] not in seen_mask:
-                seen_mask.add(payload[0])
-                ins = (self.mask_tail_tests(Sb, payload[0], jd, cond) if tail else self.mask_tests(Sb, payload[0], jd, cond)) + ins
-            out.append((t - lo, ins, kind == "e"))
-        return out
-
     # ------------------------------------------------------------------ causal masks
-    def score_mask_ops(self, Y, g):
-        """the wave ON the diagonal (w == jd): -inf into the scores of group g = 2 qb + kb whose key lies behind the query.
-        (qb0, kb0) and (qb1, kb1) get the triangle, (qb0, kb1) is masked entirely, (qb1, kb0) not at all.  Register r of a
-        group <-> key (r & 3) + 8 (r >> 2) + 4 h, lane <-> query i"""
-        if g in (0, 3):
-            out = []
-            for r in range(16):
-                key = (r & 3) + 8 * (r >> 2)
-                out += [I("v_cmp_ge_i32", VCC, V(V_IMH), key), I("v_cndmask_b32", V(Y + 16 * g + r), NINF, V(Y + 16 * g + r), VCC)]
-            return out
-        if g == 1:
-            return [I("v_mov_b32", V(Y + 16 + r), NINF) for r in range(16)]
-        return []
-
-    def group_mask_ops(self, Y, g, what):
-        """-inf into the scores of group g: what = "tri" (key block == query block: keys behind the query) or "all".
-        Register r of a group <-> key (r & 3) + 8 (r >> 2) + 4 h, lane <-> query i"""
-        if what == "all":
-            return [I("v_mov_b32", V(Y + 16 * g + r), NINF) for r in range(16)]
-        out = []
-        for r in range(16):
-            key = (r & 3) + 8 * (r >> 2)
-            out += [I("v_cmp_ge_i32", VCC, V(V_IMH), key), I("v_cndmask_b32", V(Y + 16 * g + r), NINF, V(Y + 16 * g + r), VCC)]
-        return out
 
     def mask_lazy(self, Sb, kind, payload, lazy):
         """Diagonal tiles other than a job's first are not masked before the softmax: the row maxima are taken over all 64 keys
@@ -982,126 +477,6 @@ class Gen:
             return sel + [I("v_mov_b32", V(V_MSV[qb]), V(V_MC[qb])), I("v_cndmask_b32", V(V_MC[qb]), -NINF, V(V_MC[qb]), VCC)]
         return sel + [I("v_cndmask_b32", V(V_MC[qb]), V(V_MSV[qb]), V(V_MC[qb]), VCC) for qb in range(2)]
 
-    def mask_tail(self, Sb, kind, payload, j, cond):
-        """non-causal ragged, seam tile j (keys 64 j .. 64 j + 63 of the job's last 256; S_KT0 of them are real): a tile wholly
-        behind N gets +inf for the running maximum like a tile below the causal diagonal (mask_lazy 'ms' / 'mr')"""
-        if j == 0:
-            return []          # at least one key of tile 0 is real
-        assert cond is None
-        sel = [I("s_cmp_gt_i32", S_KT0, 64 * j), I("s_cselect_b64", VCC, -1, 0)]     # VCC: the tile holds a real key
-        if kind == "ms":
-            qb = payload
-            return sel + [I("v_mov_b32", V(V_MSV[qb]), V(V_MC[qb])), I("v_cndmask_b32", V(V_MC[qb]), -NINF, V(V_MC[qb]), VCC)]
-        return sel + [I("v_cndmask_b32", V(V_MC[qb]), V(V_MSV[qb]), V(V_MC[qb]), VCC) for qb in range(2)]
-
-    def mask_tail_tests(self, Y, g, j, cond):
-        """in front of score group g's first row-maximum operation: if some of its 32 keys lie at or behind N (and some key of
-        the tile is real: else mask_tail deals with it), -inf into those scores, out of line.  Register r of a group <-> key
-        (r & 3) + 8 (r >> 2) + 4 h of the group's 32"""
-        kb = g & 1
-        l_m, l_back = self.lab("tail"), self.lab("tail_back")
-        t = V(V_T[6])
-        blk = [label(l_m)]
-        if cond is not None:
-            blk += [I("s_cmp_eq_u32", cond[0], cond[1]), I("s_cbranch_scc0", Label(l_back))]
-        if j > 0:
-            blk += [I("s_cmp_gt_i32", S_KT0, 64 * j), I("s_cbranch_scc0", Label(l_back))]
-        # T = real keys of this group minus the lane half's offset: register r is kept iff T > (r & 3) + 8 (r >> 2)
-        # (S_X2, the job decode's scratch: the S_T temporaries may be in the middle of a descriptor computation spread over gaps)
-        blk += [I("s_sub_i32", S_X2, S_KT0, 64 * j + 32 * kb), I("v_lshrrev_b32", t, 5, V(V_LANE)), I("v_lshlrev_b32", t, 2, t),
-                I("v_sub_u32", t, S_X2, t)]
-        for r in range(16):
-            blk += [I("v_cmp_gt_i32", VCC, t, (r & 3) + 8 * (r >> 2)), I("v_cndmask_b32", V(Y + 16 * g + r), NINF, V(Y + 16 * g + r), VCC)]
-        self.ool.append(blk + [I("s_branch", Label(l_back))])
-        # in line: one compare and an untaken branch while all 32 keys of the group are real
-        return [I("s_cmp_lt_i32", S_KT0, 64 * j + 32 * kb + 32), I("s_cbranch_scc1", Label(l_m)), label(l_back)]
-
-    def fire_exact(self, Sb, qb, lazy):
-        """head of the rare rescale path of a lazily masked diagonal tile: on the wave that sits on the diagonal the row maxima
-        were taken over masked keys too -- mask this query block's scores now and take the maxima again (then the plain path
-        decides with the exact maximum; the packed-P masking later is a no-op on the -inf entries)"""
-        jd, cond = lazy
-        l_plain = self.lab("fire_plain")
-        a, b = V(V_MX[qb][0]), V(V_MX[qb][1])
-        blk = []
-        if self.split:
-            # only query block jd >> 1 has waves on the diagonal of tile jd: waves 2 p (pattern D0) and 2 p + 1 (D1), p = jd & 1
-            if qb != jd >> 1:
-                return []
-            p2 = 2 * (jd & 1)
-            l_d1, l_max = self.lab("fire_d1"), self.lab("fire_max")
-            if cond is not None:
-                blk += [I("s_cmp_eq_u32", cond[0], cond[1]), I("s_cbranch_scc0", Label(l_plain))]
-            blk += [I("s_cmp_eq_u32", S_WAVE, p2 + 1), I("s_cbranch_scc1", Label(l_d1)),
-                    I("s_cmp_eq_u32", S_WAVE, p2), I("s_cbranch_scc0", Label(l_plain))]
-            blk += self.group_mask_ops(Sb, 2 * qb, "tri") + self.group_mask_ops(Sb, 2 * qb + 1, "all") + [I("s_branch", Label(l_max))]
-            blk += [label(l_d1)] + self.group_mask_ops(Sb, 2 * qb + 1, "tri") + [label(l_max)]
-            for g, mx in ((2 * qb, a), (2 * qb + 1, b)):
-                y = lambda r: V(Sb + 16 * g + r)
-                blk += [I("v_max3_f32", mx, y(0), y(1), y(2))] + [I("v_max3_f32", mx, mx, y(2 * j + 1), y(2 * j + 2)) for j in range(1, 7)] + \
-                    [I("v_max_f32", mx, mx, y(15))]
-            blk += [I("v_max_f32", a, a, b), I("v_mov_b32", b, a), I("v_permlane32_swap_b32", a, b), I("v_max_f32", a, a, b), label(l_plain)]
-            return blk
-        if cond is not None:
-            blk += [I("s_cmp_eq_u32", cond[0], cond[1]), I("s_cbranch_scc0", Label(l_plain))]
-        blk += [I("s_cmp_eq_u32", S_WAVE, jd), I("s_cbranch_scc0", Label(l_plain))]
-        for g, mx in ((2 * qb, a), (2 * qb + 1, b)):
-            blk += self.score_mask_ops(Sb, g)
-            y = lambda r: V(Sb + 16 * g + r)
-            blk += [I("v_max3_f32", mx, y(0), y(1), y(2))] + [I("v_max3_f32", mx, mx, y(2 * j + 1), y(2 * j + 2)) for j in range(1, 7)] + \
-                [I("v_max_f32", mx, mx, y(15))]
-        blk += [I("v_max_f32", a, a, b), I("v_mov_b32", b, a), I("v_permlane32_swap_b32", a, b), I("v_max_f32", a, a, b), label(l_plain)]
-        return blk
-
-    def mask_tests(self, Y, g, jd, cond=None):
-        """causal: the tile whose softmax starts is diagonal tile jd (0..3) of its job: keys 64 jd .. 64 jd + 63 of the 256-key
-        diagonal span against this wave's rows 64 w .. 64 w + 63.  w > jd: nothing; w == jd: score groups (qb0, kb0) and
-        (qb1, kb1) get the triangle (key > query -> -inf), (qb0, kb1) is all -inf; w < jd: all -inf.  Register r of a
-        group <-> key (r & 3) + 8 (r >> 2) + 4 h, lane <-> query i.  cond: (sgpr, value): the tile is diagonal at all.
-        Returns the in-line tests for score group g (in front of its first row-maximum operation); the masking itself runs
-        out of line.  The branch sits where that row-maximum operation is legal, i.e. the MFMA -> VALU wait states have passed
-        (check.check_branch_targets verifies it on the built program)."""
-        if self.split:
-            # waves 2 p / 2 p + 1 (p = jd & 1) carry patterns D0 / D1 on query block jd >> 1 (see mask_lazy); a block wholly
-            # hidden from a wave is not computed at all by the split bodies
-            l_back = self.lab("mask_back")
-            qb, kb = g >> 1, g & 1
-            if qb != jd >> 1:
-                return []
-            p2 = 2 * (jd & 1)
-            tests = []
-            l_d0 = self.lab("mask_d0")
-            self.ool.append([label(l_d0)] + self.group_mask_ops(Y, g, "tri" if kb == 0 else "all") + [I("s_branch", Label(l_back))])
-            tests += [I("s_cmp_eq_u32", S_WAVE, p2), I("s_cbranch_scc1", Label(l_d0))]
-            if kb == 1:
-                l_d1 = self.lab("mask_d1")
-                self.ool.append([label(l_d1)] + self.group_mask_ops(Y, g, "tri") + [I("s_branch", Label(l_back))])
-                tests += [I("s_cmp_eq_u32", S_WAVE, p2 + 1), I("s_cbranch_scc1", Label(l_d1))]
-            if cond is None:
-                return tests + [label(l_back)]
-            l_tests = self.lab("mask_tests")
-            self.ool.append([label(l_tests)] + tests + [I("s_branch", Label(l_back))])
-            return [I("s_cmp_eq_u32", cond[0], cond[1]), I("s_cbranch_scc1", Label(l_tests)), label(l_back)]
-        l_eq, l_lt, l_back = self.lab("mask_eq"), self.lab("mask_lt"), self.lab("mask_back")
-        tests = []
-        eq_ops = self.score_mask_ops(Y, g)
-        if eq_ops:
-            tests += [I("s_cmp_eq_u32", S_WAVE, jd), I("s_cbranch_scc1", Label(l_eq))]
-            self.ool.append([label(l_eq)] + eq_ops + [I("s_branch", Label(l_back))])
-        if jd > 0:
-            tests += [I("s_cmp_lt_u32", S_WAVE, jd), I("s_cbranch_scc1", Label(l_lt))]
-            self.ool.append([label(l_lt)] + [I("v_mov_b32", V(Y + 16 * g + r), NINF) for r in range(16)] +
-                            [I("s_branch", Label(l_back))])
-        if cond is None:
-            return tests + [label(l_back)]
-        if not tests:
-            return []
-        # the tile is diagonal only in the loop's last trip (or for a one-tile-row job): the common path falls through one
-        # compare and one untaken branch -- a TAKEN branch over the tests cost ~25 cycles per step in the steady loop
-        l_tests = self.lab("mask_tests")
-        self.ool.append([label(l_tests)] + tests + [I("s_branch", Label(l_back))])
-        return [I("s_cmp_eq_u32", cond[0], cond[1]), I("s_cbranch_scc1", Label(l_tests)), label(l_back)]
-
     # ------------------------------------------------------------------ the two phases
     def emit_phase(self, mfmas, gaps):
         """gaps[k] = fillers behind slot k of a64's time line: (order, [insts]) with order 0 = LDS / DMA loads, 1 = exp2, 2 = the rest,
@@ -1129,35 +504,6 @@ class Gen:
         assert pos == len(ents)
         return out
 
-    def phase_a(self, t4, with_qk=True, cur=True, nxt=True, nxt_init=False, masks=None, steady=False, dma=(), cur_masks=None, extra=(),
-                cur_qbs=(0, 1), nxt_qbs=(0, 1)):
-        """A(t), t4 = t & 3: QK^T(t+1) -> S[1-p]  ||  V(t) reads from VB[t % R]  ||  the late softmax operations of tile t (on S[p])
-        ||  the early ones of tile t+1 (on S[1-p])"""
-        p = t4 & 1
-        X, Y = SBUF[p], SBUF[1 - p]
-        abl = self.abl if steady else set()
-        mf = self.qk_mfmas(Y, qbs=nxt_qbs) if with_qk else []
-        gaps = {}
-        add = lambda k, order, ins: gaps.setdefault(min(max(int(k), 0), 31), []).append((order, ins))
-        if cur:
-            if "novread" not in abl:
-                for k, ins in enumerate(self.v_reads(t4 % self.R)):
-                    add(self.a_vread_gap(k), 0, [ins])
-            if "nofinish" not in abl:
-                for k, ins, is_exp in self.tile_fill(X, 32 + self.NB, self.T_END, False, cur_masks, abl=abl, qbs=cur_qbs):
-                    add(k, 1 if is_exp else 2, ins)
-        if nxt and "nostart" not in abl:
-            for k, ins, is_exp in self.tile_fill(Y, 0, 32, nxt_init, masks, abl=abl, qbs=nxt_qbs):
-                add(k, 1 if is_exp else 2, ins)
-        for g, ins in extra:
-            add(g, 2, ins)
-        for g, setup, load in dma:   # LDS-DMA pieces riding in this phase (the seam's Q rows): set-up ends gap g - 1, load opens gap g
-            add(g - 1, 3, setup)
-            add(g, 0, [load])
-        if not mf:
-            return [x for k in sorted(gaps) for _, ins in sorted(gaps[k], key=lambda x: x[0]) for x in ins]
-        return self.emit_phase(mf, gaps)
-
     def pv_mfmas(self, X, qbs=(0, 1)):
         """O^T(qb, db) += V^T(db) . P^T(qb): 8 MFMAs of 64 cycles over all 64 keys, and the row sums of the two P operands
         (v_mfma_f32_16x16x128_f8f6f4 against the 0 / 1 operand: register 0 of V_LACC[qb] is the lane's own 64-key sum), in a list of
@@ -1180,144 +526,24 @@ class Gen:
             out[4 * k] = m
         return out
 
-    def phase_b(self, t4, with_pv=True, nxt=True, nxt_init=False, with_kread=True, with_dma=True, steady=False,
-                pre=(), early=(), late=(), masks=None, own_gaps=None, post=(), cur_qbs=(0, 1), nxt_qbs=(0, 1)):
-        """B(t), t4 = t & 3: P.V(t) and the row sums of P(t) from S[p]  ||  the middle softmax operations of tile t+1 (on S[1-p])
-        ||  K(t+2) reads from KB[(t+2) % R]  ||  LDS-DMA V(t+dv) -> VB[(t+dv) % R], K(t+dk) -> KB[(t+dk) % R].
-        pre: instructions ahead of the phase;  early: scalar work / register loads spread over the first gaps;
-        late: further DMA pieces (the next job's Q rows) as (gap, set-up, load);  own_gaps: the gaps of this step's own pieces"""
-        p = t4 & 1
-        X, Y = SBUF[p], SBUF[1 - p]
-        abl = self.abl if steady else set()
-        mf = self.pv_mfmas(X, qbs=cur_qbs) if with_pv else []
-        NB = self.NB
-        gaps = {}
-        add = lambda k, order, ins: gaps.setdefault(min(max(int(k), 0), NB - 1), []).append((order, ins))
-        head = list(pre)
-        post, post_arg = [], list(post)
-        if with_kread and "nokread" not in abl:
-            for k, ins in enumerate(self.k_reads((t4 + 2) % self.R)):
-                add(self.b_kread_gap(k), 0, [ins])
-        if with_dma:
-            pieces = [self.dma_piece("v", j, (t4 + self.dv) % self.R) for j in range(2)] + \
-                [self.dma_piece("k", j, (t4 + self.dk) % self.R) for j in range(2)]
-            for k, pc in enumerate(pieces):
-                if "nodma" in abl:
-                    continue
-                # (with further pieces behind them -- the seam's Q rows -- this step's own go first: the counted waits
-                # assume all eight are older than the sixteen)
-                g = own_gaps[k] if own_gaps else self.b_dma_gap(k)
-                # scalar set-up (soffset, M0) at the end of the previous gap, the load first in its own: the MFMA between
-                # them is the wait state the M0 write needs
-                setup, load = [x for x in pc if not x.op.startswith("buffer_load") and x.op != "s_nop"], [x for x in pc if x.op.startswith("buffer_load")]
-                add(g - 1, 3, setup)
-                add(g, 0, load if mf else [I("s_nop", 0)] + load)
-            post += [I("s_add_u32", S_VDMA, S_VDMA, S_V64), I("s_add_u32", S_KDMA, S_KDMA, S_K64)]
-        # scalar work rides in the first gaps one UNIT at a time: an instruction that consumes SCC (the s_addc of a 64-bit
-        # add, a select or branch on a compare) stays glued to the instructions since its producer -- other fillers write
-        # SCC too (the DMA set-up's s_add_u32), and a descriptor base once lost its carry that way (check.py R9)
-        units = []
-        for ins in early:
-            d_, u_ = ins.defs_uses()
-            if ("scc", 0) in u_ and units:
-                units[-1].append(ins)
-            else:
-                units.append([ins])
-        ne = len(units)
-        for k, unit in enumerate(units):
-            add(1 + 12 * k // max(ne, 1), 2, unit)   # done before this phase's own DMA pieces (gap 15 on) and the late ones
-        for g, setup, load in late:   # (gap pairs disjoint from the own pieces': both use M0 and the scratch offset register)
-            add(g - 1, 3, setup)
-            add(g, 0, [load])
-        if nxt and "nostart" not in abl:
-            for k, ins, is_exp in self.tile_fill(Y, 32, 32 + NB, nxt_init, masks, abl=abl, qbs=nxt_qbs):
-                add(k, 1 if is_exp else 2, ins)
-        if not mf:
-            body = [x for k in sorted(gaps) for _, ins in sorted(gaps[k], key=lambda x: x[0]) for x in ins]
-        else:
-            body = self.emit_phase(mf, gaps)
-        body = head + body + post + post_arg
-        if nxt and not nxt_init or True:
-            # deferred rescale of O and the row sums by the factors the decisions of this step left (rare)
-            l_rs, l_back = self.lab("rescale"), self.lab("rescale_back")
-            body += [I("s_cmp_lg_u32", S_FLAG, 0), I("s_cbranch_scc1", Label(l_rs)), label(l_back)]
-            # (bit qb of S_FLAG: query block qb fired in this step -- only its accumulators are touched; packed multiplies: the
-            # matrix pipe is idle here.  f16 inputs fire a few times per job: P must stay below 65 504)
-            blk = [label(l_rs), I("s_nop", 15)]
-            tmp = [V(V_T[k]) for k in range(8)]
-            co = V(V_T[8], 2)      # (an even register: the factor is read as the low word of an aligned 64-bit operand)
-            for qb in range(2):
-                l_skip = self.lab("rescale_skip")
-                if self.scaled:
-                    # the row sums take 2^(m_old - m), the new scale byte takes over; O only on the guard path (bit 2 + qb)
-                    l_noo = self.lab("rescale_no_o")
-                    blk += [I("s_bitcmp1_b32", S_FLAG, qb), I("s_cbranch_scc0", Label(l_skip)),
-                            I("v_mov_b32", co.sub(0), V(V_CO[qb])), I("v_mov_b32", V(V_SCL[qb]), V(V_SCP[qb]))]
-                    blk += [I("v_pk_mul_f32", V(V_LACC[qb] + k, 2), V(V_LACC[qb] + k, 2), co, op_sel_hi=(1, 0)) for k in (0, 2)]
-                    blk += [I("v_mov_b32", V(V_CO[qb]), 1.0), I("s_bitcmp1_b32", S_FLAG, 2 + qb), I("s_cbranch_scc0", Label(l_noo)),
-                            I("v_mov_b32", co.sub(0), V(V_CO2[qb]))]
-                    for base in range(0, 64, 8):
-                        regs = [A(qb * 64 + base + k) for k in range(8)]
-                        blk += [I("v_accvgpr_read_b32", tmp[k], regs[k]) for k in range(8)]
-                        blk += [I("v_pk_mul_f32", V(tmp[k].idx, 2), V(tmp[k].idx, 2), co, op_sel_hi=(1, 0)) for k in range(0, 8, 2)]
-                        blk += [I("v_accvgpr_write_b32", regs[k], tmp[k]) for k in range(8)]
-                    blk += [label(l_noo), label(l_skip)]
-                    continue
-                blk += [I("s_bitcmp1_b32", S_FLAG, qb), I("s_cbranch_scc0", Label(l_skip)), I("v_mov_b32", co.sub(0), V(V_CO[qb]))]
-                for base in range(0, 64, 8):
-                    regs = [A(qb * 64 + base + k) for k in range(8)]
-                    blk += [I("v_accvgpr_read_b32", tmp[k], regs[k]) for k in range(8)]
-                    blk += [I("v_pk_mul_f32", V(tmp[k].idx, 2), V(tmp[k].idx, 2), co, op_sel_hi=(1, 0)) for k in range(0, 8, 2)]
-                    blk += [I("v_accvgpr_write_b32", regs[k], tmp[k]) for k in range(8)]
-                blk += [I("v_pk_mul_f32", V(V_LACC[qb] + k, 2), V(V_LACC[qb] + k, 2), co, op_sel_hi=(1, 0)) for k in (0, 2)]
-                blk += [I("v_mov_b32", V(V_CO[qb]), 1.0), label(l_skip)]
-            blk += [I("s_mov_b32", S_FLAG, 0), I("s_nop", 3), I("s_branch", Label(l_back))]
-            self.ool.append(blk)
-        return body
-
-    def sync_mid(self, steady=False, vm=None):
-        if vm is not None:
-            return [waitcnt(vmcnt=vm, lgkmcnt=0), I("s_barrier")]
-        if steady and "novmwait" in self.abl:
-            return [waitcnt(lgkmcnt=0), I("s_barrier")]
-        if steady and "nobarrier" in self.abl:
-            return [waitcnt(vmcnt=self.vm, lgkmcnt=0)]
-        out = [waitcnt(vmcnt=self.vm, lgkmcnt=0, comment="the DMA pieces the next reads need have landed; V fragments in"), I("s_barrier")]
-        if steady and "skew" in self.abl:   # experiment: wave w leaves the barrier 8 w cycles late
-            l1, l2 = self.lab("skew1"), self.lab("skew2")
-            out += [I("s_bitcmp1_b32", S_WAVE, 0), I("s_cbranch_scc0", Label(l1)), I("s_nop", 7), label(l1),
-                    I("s_bitcmp1_b32", S_WAVE, 1), I("s_cbranch_scc0", Label(l2)), I("s_nop", 15), label(l2)]
-        return out
-
-    def step(self, t4, a_pre=(), **kw):
-        """one tile step, t4 = t & 3"""
-        ka = {k: v for k, v in kw.items() if k in ("with_qk", "cur", "nxt", "nxt_init", "steady", "dma", "cur_masks", "extra",
-                                                   "cur_qbs", "nxt_qbs")}
-        kb = {k: v for k, v in kw.items() if k in ("with_pv", "nxt", "nxt_init", "with_kread", "with_dma", "steady", "pre", "early", "late",
-                                                   "own_gaps", "post", "cur_qbs", "nxt_qbs")}
-        if kw.get("masks") is not None:   # the masking tests of a score group sit in front of its first row-maximum operation
-            ka["masks"] = kw["masks"]
-            kb["masks"] = kw["masks"]
-        out = [comment(f"---- step {t4}: phase A")]
-        out += self.stamp_acc(2)
-        out += list(a_pre)
-        out += [waitcnt(lgkmcnt=0, comment="K fragments in")]
-        out += self.phase_a(t4, **ka)
-        out += self.stamp_acc(0)
-        out += self.sync_mid(kw.get("steady", False), kw.get("vm"))
-        out += self.stamp_acc(1)
-        if kw.get("mid_stamp") is not None:      # (diagnostic builds: the seam's steps 2 and 3 split at their barrier)
-            out += self.stamp(kw["mid_stamp"])
-        out += [comment(f"---- step {t4}: phase B")]
-        out += self.phase_b(t4, **kb)
-        return out
+    def rescale(self, qb, tmp, co):
+        if not self.scaled:
+            return super().rescale(qb, tmp, co)
+        # the row sums take 2^(m_old - m), the new scale byte takes over; O only on the guard path (bit 2 + qb)
+        l_skip, l_noo = self.lab("rescale_skip"), self.lab("rescale_no_o")
+        blk = [I("s_bitcmp1_b32", S_FLAG, qb), I("s_cbranch_scc0", Label(l_skip)),
+               I("v_mov_b32", co.sub(0), V(V_CO[qb])), I("v_mov_b32", V(V_SCL[qb]), V(V_SCP[qb]))]
+        blk += [I("v_pk_mul_f32", V(V_LACC[qb] + k, 2), V(V_LACC[qb] + k, 2), co, op_sel_hi=(1, 0)) for k in (0, 2)]
+        blk += [I("v_mov_b32", V(V_CO[qb]), 1.0), I("s_bitcmp1_b32", S_FLAG, 2 + qb), I("s_cbranch_scc0", Label(l_noo)),
+                I("v_mov_b32", co.sub(0), V(V_CO2[qb]))]
+        for base in range(0, 64, 8):
+            regs = [A(qb * 64 + base + k) for k in range(8)]
+            blk += [I("v_accvgpr_read_b32", tmp[k], regs[k]) for k in range(8)]
+            blk += [I("v_pk_mul_f32", V(tmp[k].idx, 2), V(tmp[k].idx, 2), co, op_sel_hi=(1, 0)) for k in range(0, 8, 2)]
+            blk += [I("v_accvgpr_write_b32", regs[k], tmp[k]) for k in range(8)]
+        return blk + [label(l_noo), label(l_skip)]
 
     # ------------------------------------------------------------------ epilogue of the current job
-    def epilogue_descs(self):
-        """descriptors of the current job's O rows (S_SQ: the next job's Q rows are through by then) and L (S_NVRS: the next job's V
-        descriptor has moved to S_VRS): scalar work that rides in the gaps of the seam's last phase B instead of standing in
-        front of the epilogue"""
-        return self.make_desc(S_SQ, S_O, S_OSB, S_OSH, S_B, S_HH, S_OSN) + self.make_desc(S_NVRS, S_L, S_LSB, S_LSH, S_B, S_HH, 1)
 
     def k_epilogue(self):
         """1 / l (one Newton step), L = m + log2 l, O^T -> fp8 rows through the wave's LDS slice -> 16-byte row stores, O^T := 0.
@@ -1448,203 +674,6 @@ class Gen:
                 self.k_advance(vt=(tset[0][4], tset[0][5]))
                 e(label(l_last))
         e(zero[6], zero[7])
-
-    # ------------------------------------------------------------------ the whole kernel
-    def build(self):
-        e = self.e
-        name = self.name
-        l_job, l_loop, l_seam, l_end = (f".L{name}_{s}" for s in ("job", "loop", "seam", "end"))
-        self.k_setup()
-        e(I("s_cmp_ge_u32", S_JOB, S_TOTAL), I("s_cbranch_scc1", Label(l_end)))
-        # ---- first job of this workgroup: decode, descriptors, first loads, pipeline fill
-        self.k_decode_next()
-        self.k_promote()
-        self.k_advance()      # (every later job is decoded in its predecessor's epilogue, under the row stores)
-        e(comment("first job: K / V descriptors, K(0..2), V(0..1) by LDS-DMA, Q rows"))
-        e(self.make_desc(S_KRS, S_K, S_KSB, S_KSH, S_B, S_HH, S_KSN), self.make_desc(S_VRS, S_V, S_VSB, S_VSH, S_B, S_HH, S_VSN))
-        e(I("s_mov_b32", S_KDMA, S_KW), I("s_mov_b32", S_VDMA, S_VW))
-        e(self.stamp(0))
-        # (the first QK^T needs the Q rows and K(0) only: they go first, and the wait in front of the first barrier leaves the other
-        # tiles in flight -- all 256 workgroups start at once and the burst is bandwidth-bound, ~7 us for everything)
-        qs_setup, qs_pieces = self.q_stage(S_B, S_HH, S_QI)
-        e(qs_setup, [pc + [I("s_nop", 0), ld] for pc, ld in qs_pieces])
-        late = []
-        for j in range(self.dk - 1):
-            (e if j == 0 else late.append)(self.dma_tile("k", j % self.R))
-            if j < self.dv - 1:
-                late.append(self.dma_tile("v", j % self.R))
-        e(late)
-        n_late = sum(1 for t in late for x in t if x.op.startswith("buffer_load"))
-        e([I("v_accvgpr_write_b32", A(k), 0) for k in range(128)])   # O^T := 0
-        e(waitcnt(vmcnt=n_late), I("s_barrier"))
-        e(self.stamp(1))
-        e(self.q_reads(), self.k_reads(0))
-        # step -1 (buffers as t4 = 3): A = QK^T(0) only; B = start(0) as init, K(1) reads, DMA V(2), K(3)
-        e(self.step(3, with_qk=True, cur=False, with_pv=False, nxt_init=True, masks=(0, (S_NT, 4)) if self.causal else None))
-        e(self.stamp(2), self.stamp_flush(), self.stamp_acc(3), self.stamp_job(3))
-        # ---- job loop
-        e(label(l_job))
-        e(I("s_lshr_b32", S_LOOP, S_NT, 2), I("s_sub_u32", S_LOOP, S_LOOP, 1),
-          I("s_cmp_eq_u32", S_LOOP, 0), I("s_cbranch_scc1", Label(l_seam)))
-        e(label(l_loop))
-        for t4 in range(4):
-            # causal: the last steady body starts the job's first diagonal tile in its last phase B
-            tailm = ("tail", 0, (S_LOOP, 1)) if self.ragged and not self.causal else None
-            # (the K tile streamed in step 1 of the last trip and the V tile of its step 2 are the first of the diagonal span)
-            jump = self.stream_to_diagonal("k") if t4 == 4 - self.dk else self.stream_to_diagonal("v") if t4 == 4 - self.dv else []
-            e(self.step(t4, steady=True, masks=((0, (S_LOOP, 1)) if self.causal else tailm) if t4 == 3 else None, early=jump))
-        e(I("s_sub_u32", S_LOOP, S_LOOP, 1), I("s_cmp_lg_u32", S_LOOP, 0), I("s_cbranch_scc1", Label(l_loop)))
-        e(label(l_seam))
-        e(self.stamp(3), self.stamp_acc(2), self.stamp_flush(), self.stamp_job(0))
-        # ---- the job's last four tiles: the next job's K / V / Q stream in, its first QK^T and softmax start run here
-        cm = self.causal
-        if True:
-            kpre = self.make_desc(S_KRS, S_K, S_KSB, S_KSH, S_NB, S_NHH, S_KSN) + self.stream_start("k") + \
-                self.make_desc(S_NVRS, S_V, S_VSB, S_VSH, S_NB, S_NHH, S_VSN)
-            vpre = [I("s_mov_b32", S_VRS.sub(k), S_NVRS.sub(k)) for k in range(4)] + self.stream_start("v")
-            sk, sv = 4 - self.dk, 4 - self.dv      # seam step whose phase B streams the next job's first K / V tile
-            assert sk <= 2 and sv <= 2             # (step 3 re-uses S_SQ and S_NVRS for the epilogue's descriptors)
-            qs_setup, qs_pieces = self.q_stage(S_NB, S_NHH, S_NQI)
-            for st in range(4):
-                kw = dict(masks=((st + 1,) if st < 3 else (0, (S_NNT, 4))) if cm else None, cur_masks=(st,) if cm else None)
-                if self.ragged and not cm:   # keys at or behind N in the job's last four tiles (a ragged N has at least eight)
-                    kw = dict(masks=("tail", st + 1) if st < 3 else None, cur_masks=("tail", st))
-                early, pre = [], []
-                if st == 0:
-                    # the next job's Q rows start their way into the wave's LDS slice: sixteen pieces, never more than one
-                    # DMA piece per two gaps (that rate is free beside the MFMAs): eight behind this step's own K / V pieces,
-                    # four in the quiet end of the next phase A, four in front of the next step's own.  The barrier waits
-                    # in between leave them in flight (vmcnt(8 / 12 + ...)); the one of step 2 retires them
-                    early += qs_setup
-                    # (eight pieces here: four behind this step's own K / V pieces, two in the quiet end of the next phase A, two in
-                    # front of the next step's own; the barrier wait of step 1 leaves those six in flight)
-                    kw.update(own_gaps=(1, 5, 11, 15),
-                              late=[(g, *qs_pieces[k]) for k, g in enumerate((21, 25, 29, 33))])
-                if st == 1:
-                    kw.update(vm=self.vm + 6,
-                              dma=[(g, *qs_pieces[4 + k]) for k, g in enumerate((24, 28))],
-                              late=[(g, *qs_pieces[6 + k]) for k, g in enumerate((1, 5))])
-                if st == sk:
-                    early += kpre
-                if st == sv:
-                    pre += vpre
-                if st == 2 and "noqreads" not in self.abl:   # (timing-only ablation: what the AGPR-destination reads cost)
-                    early += self.q_reads()      # slice -> a[128:191] (Q was last read by this step's phase A)
-                if st == 3:
-                    early += self.epilogue_descs()
-                    # the job's last tile: its running maxima are put aside for the epilogue before the next job's first
-                    # tile re-initialises them (its row sums stay in V_LACC until the epilogue has read them)
-                    save = [I("v_mov_b32", V(V_MSV[qb]), V(V_MC[qb])) for qb in range(2)]
-                    if (cm and not self.split) or (self.ragged and not cm):   # (behind the tile's 'mr': until then V_MSV holds what 'ms' put aside, mask_lazy)
-                        kw.update(nxt_init=True, extra=list(kw.get("extra", ())) + [(self.LAZY_TAU["mr"] - self.PERIOD + 1, save)])
-                    else:
-                        kw.update(nxt_init=True, a_pre=save)
-                e(self.stamp(16 + st))
-                if self.split:
-                    # split row map (wave w: 32-row blocks w and w + 4).  Diagonal tile j -- key blocks 2 j, 2 j + 1 -- against
-                    # query block 0 (row block w): hidden for w < 2 j, on the diagonal for w = 2 j (D0) / 2 j + 1 (D1), visible
-                    # above; against query block 1 (row block w + 4): the same with w + 4.  So tile 0: everything runs (waves
-                    # 0 / 1 mask block 0), tile 1: block 0 only on waves 2, 3 (which mask it), tile 2: block 1 only (waves 0 / 1
-                    # mask), tile 3: block 1 on waves 2, 3 only (which mask).  Step st finishes tile st and starts tile st + 1:
-                    # two bodies per step, waves 0-1 ("low") out of line, waves 2-3 ("high") in line, each with only the MFMAs
-                    # and softmax operations of the blocks it needs -- 216 MFMA slots on the critical path instead of 288.
-                    cur_q = (((0, 1), (0, 1)), ((1,), (0, 1)), ((1,), (1,)), ((), (1,)))[st]
-                    nxt_q = (((1,), (0, 1)), ((1,), (1,)), ((), (1,)), ((0, 1), (0, 1)))[st]
-                    l_low, l_join = self.lab("low"), self.lab("low_join")
-                    e(I("s_cmp_lt_u32", S_WAVE, 2), I("s_cbranch_scc1", Label(l_low)))
-                    for ci, cls in ((1, "high"), (0, "low")):
-                        ckw = dict(kw)
-                        cq, nq_ = cur_q[ci], nxt_q[ci]
-                        ckw.update(cur_qbs=cq or (0, 1), nxt_qbs=nq_ or (0, 1))
-                        if not cq:
-                            ckw.update(cur=False, with_pv=False)
-                        if not nq_:
-                            ckw.update(with_qk=False, nxt=False)
-                        self.cls = cls
-                        if cls == "high":
-                            e(self.step(st, early=early, pre=pre, mid_stamp=20 + st if st >= 2 else None, **ckw), label(l_join))
-                        else:
-                            body, self.prog = self.prog, []
-                            e(label(l_low), self.step(st, early=early, pre=pre, **ckw), I("s_branch", Label(l_join)))
-                            self.ool.append(self.prog)
-                            self.prog = body
-                        self.cls = None
-                    continue
-                lean = cm and st >= 1 and "nolean" not in self.abl
-                half = cm and st < 3 and "nolean" not in self.abl
-                if lean:
-                    # waves below this step's diagonal tile (w < st): the tile whose softmax finishes and whose P.V runs here is
-                    # hidden from them, and so is the one that starts (steps 1, 2; step 3 starts the next job's first tile).
-                    # They take a body with the same loads, DMA pieces, waits and barriers but without those MFMAs and softmax
-                    # operations, and idle at the barriers: at the package power limit what one wave does not execute, the
-                    # others run faster (+1.2 % on c3 causal, A/B in one process).  Such a wave's running maximum was swapped for
-                    # +inf when the hidden tile started ('ms'): the lean body puts it back.
-                    l_lean, l_join = self.lab("lean"), self.lab("lean_join")
-                    e(I("s_cmp_lt_u32", S_WAVE, st), I("s_cbranch_scc1", Label(l_lean)))
-                if half:
-                    # the wave ON this step's diagonal (w == st): the tile that starts here is hidden from it -- no QK^T, no start
-                    # of its softmax (+0.2 % at c3, +1 % at N = 2048 on top of the lean bodies)
-                    l_half = self.lab("half")
-                    l_join2 = l_join if lean else self.lab("half_join")
-                    e(I("s_cmp_eq_u32", S_WAVE, st), I("s_cbranch_scc1", Label(l_half)))
-                e(self.step(st, early=early, pre=pre, **kw))
-                if lean or half:
-                    e(label(l_join if lean else l_join2))
-                    body, self.prog = self.prog, []
-                    if lean:
-                        lkw = dict(kw)
-                        lkw["a_pre"] = [I("v_mov_b32", V(V_MC[qb]), V(V_MSV[qb])) for qb in range(2)] + list(kw.get("a_pre", ()))
-                        lkw.update(dict(with_qk=False, cur=False, nxt=False, with_pv=False) if st < 3 else dict(cur=False, with_pv=False))
-                        e(label(l_lean), self.step(st, early=early, pre=pre, **lkw), I("s_branch", Label(l_join)))
-                    if half:
-                        hkw = dict(kw)
-                        # (no 'ms' runs for the hidden tile: the lean body of the next step restores from V_MSV all the same)
-                        hkw["a_pre"] = list(kw.get("a_pre", ())) + [I("v_mov_b32", V(V_MSV[qb]), V(V_MC[qb])) for qb in range(2)]
-                        hkw.update(with_qk=False, nxt=False)
-                        e(label(l_half), self.step(st, early=early, pre=pre, **hkw), I("s_branch", Label(l_join2)))
-                    self.ool.append(self.prog)
-                    self.prog = body
-        e(self.stamp(4), self.stamp_job(1))
-        self.k_epilogue()
-        e(self.stamp(5))
-        # (S_FLAG: S_FINAL as it stood in front of the epilogue's job bookkeeping; back to 0 for the next step's rescale flag)
-        e(I("s_cmp_lg_u32", S_FLAG, 0), I("s_mov_b32", S_FLAG, 0), I("s_cbranch_scc1", Label(l_end)))
-        e(self.stamp(0), self.stamp_acc(3), self.stamp_job(2))
-        e(I("s_branch", Label(l_job)))
-        e(label(l_end), self.stamp_job(2), self.stamp_job_flush(), waitcnt(vmcnt=0), self.stamp(7, real=True), self.stamp(9), I("s_endpgm"))
-        for blk in self.ool:
-            e(blk)
-        from .check import check_branch_targets, fix
-        self.prog, self.pads = fix(self.prog)
-        bad = check_branch_targets(self.prog, need=20)
-        assert not bad, ("a branch enters a block that touches fresh MFMA results", bad[:4])
-        return self.prog
-
-    # ------------------------------------------------------------------ text
-    def lds_total(self):
-        return LDS_TOTAL
-
-    def text(self):
-        lines = [f".protected {self.name}", f".globl {self.name}", ".p2align 8", f".type {self.name},@function", f"{self.name}:"]
-        lines += [x.text() for x in self.prog]
-        lines += [f".L{self.name}_fend:", f".size {self.name}, .L{self.name}_fend-{self.name}", "",
-                  '.section .rodata,"a",@progbits', ".p2align 6, 0x0", f".amdhsa_kernel {self.name}",
-                  f"  .amdhsa_group_segment_fixed_size {self.lds_total()}", "  .amdhsa_private_segment_fixed_size 0",
-                  f"  .amdhsa_kernarg_size {KARG_SIZE}", "  .amdhsa_user_sgpr_count 2", "  .amdhsa_user_sgpr_kernarg_segment_ptr 1",
-                  "  .amdhsa_system_sgpr_workgroup_id_x 1", "  .amdhsa_system_vgpr_workitem_id 0",
-                  "  .amdhsa_next_free_vgpr 512", "  .amdhsa_next_free_sgpr 102", "  .amdhsa_accum_offset 256",
-                  "  .amdhsa_reserve_vcc 1", "  .amdhsa_ieee_mode 1", "  .amdhsa_dx10_clamp 1",
-                  "  .amdhsa_float_round_mode_32 0", "  .amdhsa_float_round_mode_16_64 0",
-                  "  .amdhsa_float_denorm_mode_32 3", "  .amdhsa_float_denorm_mode_16_64 3", ".end_amdhsa_kernel", ".text", ""]
-        return "\n".join(lines)
-
-    def metadata(self):
-        return "\n".join([
-            f"  - .args:", f"      - .offset: 0", f"        .size: {KARG_SIZE}", f"        .value_kind: by_value",
-            f"    .group_segment_fixed_size: {self.lds_total()}", f"    .kernarg_segment_align: 8", f"    .kernarg_segment_size: {KARG_SIZE}",
-            f"    .max_flat_workgroup_size: 256", f"    .name: {self.name}", f"    .private_segment_fixed_size: 0",
-            f"    .sgpr_count: 108", f"    .symbol: {self.name}.kd", f"    .vgpr_count: 512", f"    .agpr_count: 256",
-            f"    .wavefront_size: 64"])
 
 
 def product_gens():
