@@ -49,9 +49,10 @@ if os.path.basename(LIB_PATH) in ("libfa2_hip_exp.so", "libfa2_hip_abl.so"):
     VARIANTS.update(EXPERIMENTAL_VARIANTS)
 
 # Every symbol include/fa2_fwd.h declares (tests/test_abi.py checks the export list against the header).
-SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", "fa2_query_tile_scaled", "fa2_version", "fa2_last_error")
+SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", "fa2_query_tile_scaled", "fa2_version", "fa2_last_error",
+           "fa2_fwd_window", "fa2_fwd_window_variant")
 # ... and include/fa2_bwd.h
-BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant")
+BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant")
 BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
 
 _lib = None
@@ -81,6 +82,12 @@ def lib():
         # int64 array (fa2_fwd below), which saves building five ctypes arrays per launch
         l.fwd_variant_addr = ctypes.CFUNCTYPE(ctypes.c_int, *([vp] * 10 + [ctypes.c_int32] * 6 + [ctypes.c_float, vp, ctypes.c_int32]))(
             ("fa2_fwd_variant", l))
+        # local attention: window_left, window_right after scale
+        win = common[:-1] + [ctypes.c_int32, ctypes.c_int32, vp]
+        l.fa2_fwd_window.restype = ctypes.c_int
+        l.fa2_fwd_window.argtypes = win
+        l.fa2_fwd_window_variant.restype = ctypes.c_int
+        l.fa2_fwd_window_variant.argtypes = win + [ctypes.c_int32]
         l.fa2_query_tile.restype = ctypes.c_int
         l.fa2_query_tile.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]
         l.fa2_query_tile_ex.restype = ctypes.c_int
@@ -92,6 +99,11 @@ def lib():
         l.fa2_bwd.argtypes = bwd
         l.fa2_bwd_variant.restype = ctypes.c_int
         l.fa2_bwd_variant.argtypes = bwd + [ctypes.c_int32]
+        bwd_win = bwd[:-1] + [ctypes.c_int32, ctypes.c_int32, vp]
+        l.fa2_bwd_window.restype = ctypes.c_int
+        l.fa2_bwd_window.argtypes = bwd_win
+        l.fa2_bwd_window_variant.restype = ctypes.c_int
+        l.fa2_bwd_window_variant.argtypes = bwd_win + [ctypes.c_int32]
         l.bwd_variant_addr = ctypes.CFUNCTYPE(ctypes.c_int, *([vp] * 19 + [ctypes.c_int32] * 6 + [ctypes.c_float, vp, ctypes.c_int32]))(
             ("fa2_bwd_variant", l))
         l.fa2_version.restype = ctypes.c_char_p
@@ -141,14 +153,25 @@ def _raw_stream(index):
         return torch.cuda.current_stream(index).cuda_stream
 
 
-def fa2_fwd(Q, K, V, O, L, dtype_enum, causal=False, scale=1.0, variant=VARIANT_AUTO):
+def fa2_fwd(Q, K, V, O, L, dtype_enum, causal=False, scale=1.0, variant=VARIANT_AUTO, window=None):
     """Launch the forward on the current stream of Q's device.  Tensors are (B, H, N, d) with
     arbitrary strides; O (B, H, N, d) and L (B, H, N, 1) are pre-allocated by the caller exactly as
-    the reference's host glue does (torch.py:50-51)."""
+    the reference's host glue does (torch.py:50-51).  window = (left, right): local attention through
+    fa2_fwd_window_variant (include/fa2_fwd.h); None is the plain call."""
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N, d = Q.shape
     LB, LH = L.stride(0), L.stride(1)
+    if window is not None:
+        wl, wr = (int(w) for w in window)
+        with torch.cuda.device(Q.device):
+            rc = lib().fa2_fwd_window_variant(
+                Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+                _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((LB, LH)),
+                B, H, N, d, int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+        if rc != 0:
+            _raise(rc)
+        return
 
     def launch():
         # one int64 array for the 18 strides (five ctypes arrays cost ~2 us), raw stream handle without the Stream object
@@ -169,14 +192,26 @@ def fa2_fwd(Q, K, V, O, L, dtype_enum, causal=False, scale=1.0, variant=VARIANT_
         _raise(rc)
 
 
-def fa2_bwd(Q, K, V, O, dO, L, dQ, dK, dV, D, dtype_enum, causal=False, scale=1.0, variant=0):
+def fa2_bwd(Q, K, V, O, dO, L, dQ, dK, dV, D, dtype_enum, causal=False, scale=1.0, variant=0, window=None):
     """Launch the backward (include/fa2_bwd.h) on the current stream of Q's device: the counterpart of the
     reference's bwd_D_kernel + bwd_kernel launches (torch.py:124-155).  All buffers, the float32 scratch D
-    (2, B, H, N, 1) included, are allocated by the caller as the reference's glue does (torch.py:101-105)."""
+    (2, B, H, N, 1) included, are allocated by the caller as the reference's glue does (torch.py:101-105).
+    window = (left, right): local attention through fa2_bwd_window_variant; None is the plain call."""
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N, d = Q.shape
     assert D.is_contiguous() and D.numel() == 2 * B * H * N
+    if window is not None:
+        wl, wr = (int(w) for w in window)
+        with torch.cuda.device(Q.device):
+            rc = lib().fa2_bwd_window_variant(
+                Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(),
+                dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), D.data_ptr(),
+                *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), _i64((L.stride(0), L.stride(1))),
+                B, H, N, d, int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+        if rc != 0:
+            _raise(rc)
+        return
 
     def launch():
         st = (ctypes.c_int64 * 34)(*Q.stride(), *K.stride(), *V.stride(), *O.stride(), *dO.stride(), *dQ.stride(),

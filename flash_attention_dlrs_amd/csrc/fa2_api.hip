@@ -54,6 +54,8 @@ int validate(const Fa2Problem &p) {
     return FA2_OK;
 }
 
+long long T_cus(long long n) { return (n * fa2_device_cus() + 128) / 256; }  // T(n) of pick_variant below
+
 // The static tile table, keyed like the reference's autotuner on (B, H, N, d) (plus dtype, causal, strides): the grid
 // size B * H * tiles decides between the key-split, 4-wave and one-workgroup-per-CU kernels.
 int pick_variant(const Fa2Problem &p) {
@@ -242,6 +244,33 @@ int run(const Fa2Problem &p, int variant) {
     }
 }
 
+// Windowed table (fa2_fwd_window): the pipelined LDS-DMA kernel where it runs -- 8 or 4 waves by grid fill, rule (3) of the static
+// table above -- else the VALU kernel.  The window makes the work per tile uniform away from the sequence ends, so one 128- or
+// 256-row tile per workgroup.
+int pick_window_variant(const Fa2Problem &p) {
+    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31) &&
+                        (int64_t)(p.N + 512) * p.os[2] * 2 < (1LL << 31);
+    if (fa2_mfma16_supports(p) && fits32) {
+        const long long wg256 = (long long)((p.N + 255) / 256) * p.B * p.H;
+        return wg256 >= T_cus(160) ? FA2_VARIANT_MFMA16D : FA2_VARIANT_MFMA16D_W4;
+    }
+    return FA2_VARIANT_GENERIC;
+}
+
+int run_window(const Fa2Problem &p, int variant) {
+    int rc = validate(p);
+    if (rc != FA2_OK) return rc;
+    if (variant == FA2_VARIANT_AUTO) variant = pick_window_variant(p);
+    switch (variant) {
+    case FA2_VARIANT_GENERIC: return fa2_launch_generic_window(p);
+    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_window(p, 8);
+    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_window(p, 4);
+    default:
+        fa2_set_error("kernel variant %d does not take a window (generic, mfma16d and mfma16d_w4 do)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
+
 Fa2Problem make_problem(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t *qs,
                         const int64_t *ks, const int64_t *vs, const int64_t *os, const int64_t *ls, int32_t B,
                         int32_t H, int32_t N, int32_t d, int32_t dtype, int32_t causal, float scale, void *stream) {
@@ -303,6 +332,50 @@ int fa2_device_cus() {
 bool Fa2DeviceLatch::need() const { return !((__atomic_load_n(&done, __ATOMIC_RELAXED) >> current_device()) & 1ull); }
 void Fa2DeviceLatch::mark() { __atomic_fetch_or(&done, 1ull << current_device(), __ATOMIC_RELAXED); }
 
+int fa2_window_normalise(int32_t N, int32_t causal, int32_t wl, int32_t wr, int32_t *causal_out, int32_t *wl_out, int32_t *wr_out,
+                         int32_t *windowed) {
+    if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    const int32_t full = N > 1 ? N - 1 : 0;  // a side of N - 1 or more removes nothing
+    int32_t l = (wl < 0 || wl >= full) ? full : wl, r = (wr < 0 || wr >= full) ? full : wr;
+    if (causal) r = 0;
+    *causal_out = causal ? 1 : 0;
+    *wl_out = l;
+    *wr_out = r;
+    *windowed = 0;
+    if (l == full && r == full) return FA2_OK;  // plain (or N = 1)
+    if (l == full && r == 0) {                  // causal
+        *causal_out = 1;
+        return FA2_OK;
+    }
+    *windowed = 1;
+    return FA2_OK;
+}
+
+namespace {
+int fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
+               const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t N,
+               int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr, void *hip_stream, int32_t variant) {
+    int32_t c = causal, l = 0, r = 0, windowed = 0;
+    if (N >= 1) {  // (N < 1 is reported by validate())
+        const int rc = fa2_window_normalise(N, causal, wl, wr, &c, &l, &r, &windowed);
+        if (rc != FA2_OK) return rc;
+    } else if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, c,
+                                scale, hip_stream);
+    if (!windowed) return run(p, variant);  // the window removes nothing beyond plain / causal attention: the same path
+    p.causal = 0;
+    p.wl = l;
+    p.wr = r;
+    return run_window(p, variant);
+}
+}  // namespace
+
 extern "C" {
 
 int fa2_fwd(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
@@ -321,6 +394,23 @@ int fa2_fwd_variant(const void *Q, const void *K, const void *V, void *O, void *
     const Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N,
                                       d, dtype_enum, causal, scale, hip_stream);
     return run(p, variant);
+}
+
+int fa2_fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                   const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
+                   int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
+                   int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fwd_window(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
+                      window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_window_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                           const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                           int32_t variant) {
+    return fwd_window(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
+                      window_left, window_right, hip_stream, variant);
 }
 
 int fa2_query_tile(int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, int32_t out4[4]) {

@@ -59,6 +59,20 @@ int run(const Fa2BwdProblem &p, int variant) {
     }
 }
 
+// Windowed backward (fa2_bwd_window): the MFMA kernel for f16 / bf16 at d = 64 / 128, the VALU kernel for the rest.
+int run_window(const Fa2BwdProblem &p, int variant) {
+    const int rc = validate(p);
+    if (rc != FA2_OK) return rc;
+    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
+    switch (variant) {
+    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_window(p);
+    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_window(p);
+    default:
+        fa2_set_error("backward kernel variant %d does not take a window (generic and mfma16 do)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
+
 Fa2BwdProblem make(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
                    void *dK, void *dV, void *D, const int64_t *qs, const int64_t *ks, const int64_t *vs,
                    const int64_t *os, const int64_t *dos, const int64_t *dqs, const int64_t *dks, const int64_t *dvs,
@@ -80,6 +94,23 @@ Fa2BwdProblem make(const void *Q, const void *K, const void *V, const void *O, c
     p.B = B; p.H = H; p.N = N; p.d = d; p.dtype = dtype; p.causal = causal ? 1 : 0; p.scale = scale;
     p.stream = (hipStream_t)stream;
     return p;
+}
+
+int bwd_window(Fa2BwdProblem p, int32_t wl, int32_t wr, int variant) {
+    int32_t c = p.causal, l = 0, r = 0, windowed = 0;
+    if (p.N >= 1) {  // (N < 1 is reported by validate())
+        const int rc = fa2_window_normalise(p.N, p.causal, wl, wr, &c, &l, &r, &windowed);
+        if (rc != FA2_OK) return rc;
+    } else if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    p.causal = c;
+    if (!windowed) return run(p, variant);  // the window removes nothing beyond plain / causal attention: the same path
+    p.causal = 0;
+    p.wl = l;
+    p.wr = r;
+    return run_window(p, variant);
 }
 
 }  // namespace
@@ -106,6 +137,29 @@ int fa2_bwd_variant(const void *Q, const void *K, const void *V, const void *O, 
     return run(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
                     dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
                variant);
+}
+
+int fa2_bwd_window(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                   void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+                   const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+                   const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+                   const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+                   float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return bwd_window(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
+                      window_left, window_right, FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_window_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                           void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+                           const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+                           const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                           int32_t variant) {
+    return bwd_window(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
+                      window_left, window_right, variant);
 }
 
 }  // extern "C"

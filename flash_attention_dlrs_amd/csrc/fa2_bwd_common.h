@@ -13,10 +13,13 @@ struct Fa2BwdProblem {
     int32_t dtype, causal;
     float scale;
     hipStream_t stream;
+    int32_t wl, wr;  // local-attention window (fa2_bwd_window), normalised as in Fa2Problem
 };
 
 int fa2_bwd_launch_generic(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p);
+int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p);
+int fa2_bwd_launch_mfma16_window(const Fa2BwdProblem &p);
 bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma32(const Fa2BwdProblem &p);
 bool fa2_bwd_mfma32_supports(const Fa2BwdProblem &p);

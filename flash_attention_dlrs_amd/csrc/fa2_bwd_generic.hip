@@ -21,6 +21,13 @@
 #include "fa2_bwd_common.h"
 #include "fa2_elem.h"
 
+// FA2_BWD_GENERIC_WINDOW (fa2_bwd_generic_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr --
+// under its own kernel names, compiled in a translation unit of its own; without the macro this file is the plain kernels, unchanged.
+#ifdef FA2_BWD_GENERIC_WINDOW
+#define bwd_main_kernel bwd_main_window_kernel
+#define bwd_D_kernel bwd_D_window_kernel
+#endif
+
 namespace {
 
 template <typename A> __device__ __forceinline__ A exp2_a(A x);
@@ -34,7 +41,12 @@ struct GArgs {
     const void *Q, *K, *V, *O, *dO, *L;
     void *dQ, *dK, *dV, *D;
     int64_t qs[4], ks[4], vs[4], os[4], dos[4], dqs[4], dks[4], dvs[4], ls[2];
+#ifdef FA2_BWD_GENERIC_WINDOW
     int H, N, d, causal, TB;
+    int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
+#else
+    int H, N, d, causal, TB;
+#endif
     double c_log2e, scale;
 };
 
@@ -105,8 +117,17 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
 
     const int nsw = (N + TB - 1) / TB;
     // causal: a key block only meets query rows >= its first key; a query block only keys <= its last row
+#ifdef FA2_BWD_GENERIC_WINDOW
+    // window: a key block meets queries [j0 - wr, j1 + wl], a query block keys [i0 - wl, i1 + wr]
+    const int wl = a.wl, wr = a.wr;
+    const int sw_lo = own_row0 - (MODE == 0 ? wr : wl), sw_hi = own_row0 + TB - 1 + (MODE == 0 ? wl : wr);
+    const int sw_begin = (sw_lo > 0 ? sw_lo : 0) / TB;
+    const int sw_end = (sw_hi < N - 1 ? sw_hi : N - 1) / TB + 1;
+    (void)nsw;
+#else
     const int sw_begin = (MODE == 0 && a.causal) ? own_row0 / TB : 0;
     const int sw_end = (MODE == 1 && a.causal) ? ((own_row0 + TB - 1 < N ? own_row0 + TB - 1 : N - 1) / TB + 1) : nsw;
+#endif
     for (int sw = sw_begin; sw < sw_end; ++sw) {
         const int sw_row0 = sw * TB;
         if (MODE == 0) {
@@ -133,7 +154,11 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
                 dp += grow[x] * vrow[x];  // :289
             }
             A p = exp2_a<A>(s * c_s - Lq[r]);  // :285
+#ifdef FA2_BWD_GENERIC_WINDOW
+            if (qi >= N || kj >= N || kj < qi - wl || kj > qi + wr) p = 0;
+#else
             if (qi >= N || kj >= N || (a.causal && kj > qi)) p = 0;
+#endif
             Ps[r * TB + c] = p;  // unrounded: MODE 1 sums it; the cast of :287 happens where it is consumed
             dSs[r * TB + c] = E::round(p * (dp - Dq[r]) * scale);  // :291
         }
@@ -196,7 +221,11 @@ template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
 
 }  // namespace
 
+#ifdef FA2_BWD_GENERIC_WINDOW
+int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p) {
+#else
 int fa2_bwd_launch_generic(const Fa2BwdProblem &p) {
+#endif
     if (p.B > 65535 || p.H > 65535) {
         fa2_set_error("generic backward: B and H must be <= 65535");
         return FA2_ERR_BAD_ARG;
@@ -209,7 +238,11 @@ int fa2_bwd_launch_generic(const Fa2BwdProblem &p) {
         a.dqs[k] = p.dqs[k]; a.dks[k] = p.dks[k]; a.dvs[k] = p.dvs[k];
     }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
+#ifdef FA2_BWD_GENERIC_WINDOW
+    a.H = p.H; a.N = p.N; a.d = p.d; a.causal = 0; a.wl = p.wl; a.wr = p.wr;
+#else
     a.H = p.H; a.N = p.N; a.d = p.d; a.causal = p.causal;
+#endif
     a.c_log2e = (double)p.scale * FA2_LOG2E;
     a.scale = (double)p.scale;
     switch (p.dtype) {

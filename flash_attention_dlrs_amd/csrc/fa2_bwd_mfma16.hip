@@ -28,6 +28,14 @@
 // the row reads and the transposed reads (the XOR-swizzled image of fa2_mfma16.hip).
 #include "fa2_bwd_common.h"
 
+// FA2_BWD_MFMA16_WINDOW (fa2_bwd_mfma16_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr; the
+// swept ranges, block skips and masks follow the two band edges -- under its own kernel names, compiled in a translation unit of
+// its own; without the macro this file is the plain kernels, unchanged.
+#ifdef FA2_BWD_MFMA16_WINDOW
+#define bwd_mfma16_kernel bwd_mfma16_window_kernel
+#define bwd_D_kernel bwd_D_window_kernel
+#endif
+
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -67,7 +75,12 @@ struct BArgs {
     float *D;
     int64_t qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];  // B, H, N strides in BYTES
     int64_t ls[2];                                                        // elements
+#ifdef FA2_BWD_MFMA16_WINDOW
     int B, H, N, causal;
+    int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
+#else
+    int B, H, N, causal;
+#endif
     float c_log2e, scale;
 };
 
@@ -132,8 +145,17 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: every block / mask decision
                                                                 // below is then a scalar branch, not an EXEC mask
+#ifdef FA2_BWD_MFMA16_WINDOW
     const int i = lane & 31, h = lane >> 5;
     const int N = a.N;
+    const int wl = a.wl, wr = a.wr;
+    // (query rows [q0, q1], keys [k0, k1]): no pair inside the band / every pair inside it
+    auto band_none = [&](int q0, int q1, int k0, int k1) { return k0 > q1 + wr || k1 < q0 - wl; };
+    auto band_all = [&](int q0, int q1, int k0, int k1) { return k0 >= q1 - wl && k1 <= q0 + wr; };
+#else
+    const int i = lane & 31, h = lane >> 5;
+    const int N = a.N;
+#endif
 
     const int nblk = (N + BO - 1) / BO, nbh = a.B * a.H;
     int bh, blk;
@@ -263,6 +285,14 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     const float c = a.c_log2e;
     float rsum = 0.0f;  // MODE 1: this lane's share of rowsum(P) of its query
     const bool is_causal = (a.causal & 1) != 0;
+#ifdef FA2_BWD_MFMA16_WINDOW
+    {  // MODE 1 sweeps the keys [i0 - wl, i1 + wr], MODE 0 the queries [j0 - wr, j1 + wl]
+        const int lo = wg0 - (MODE == 1 ? wl : wr), hi = wg0 + BO - 1 + (MODE == 1 ? wr : wl);
+        t_begin = (lo > 0 ? lo : 0) / BS;
+        t_end = (hi < N - 1 ? hi : N - 1) / BS + 1;
+        (void)is_causal;
+    }
+#else
     if (is_causal) {
         if (MODE == 1) {
             const int last = (wg0 + BO - 1 < N - 1 ? wg0 + BO - 1 : N - 1);
@@ -271,6 +301,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
             t_begin = wg0 / BS;
         }
     }
+#endif
     if (t_begin >= t_end) t_begin = t_end;  // nothing to sweep (cannot happen for N >= 1, kept for safety)
 
     if (t_begin < t_end) {
@@ -291,10 +322,15 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         // t-1 at the END of step 2t+1, after the dK wave's last use of tile t-1 in step 2t.  16 + 16 MFMAs per block.
         constexpr int POFF = LOFF + 4 * BS * 4;  // P slots: [4 key groups][2][4 KiB]
         const int kg = wave & 3;
+#ifdef FA2_BWD_MFMA16_WINDOW
+        auto blk_skip = [&](int bidx) { return band_none(bidx * 32, bidx * 32 + 31, own0, own0 + 31); };
+        auto blk_masked = [&](int bidx) { return (bidx * 32 + 32 > N) || !band_all(bidx * 32, bidx * 32 + 31, own0, own0 + 31); };
+#else
         auto blk_skip = [&](int bidx) {  // causal: all 32 queries of the block precede all 32 keys of the wave
             return is_causal && bidx * 32 + 31 < own0;
         };
         auto blk_masked = [&](int bidx) { return (bidx * 32 + 32 > N) || (is_causal && bidx * 32 < own0 + 31); };
+#endif
         for (int sidx = 2 * t_begin; sidx <= 2 * t_end; ++sidx) {
             const int t = sidx >> 1, kb = sidx & 1;
             // tile t+1 goes into the buffer of tile t-1, which the dK waves still read in the kb == 0 step
@@ -324,7 +360,11 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                                 float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(x[4 * g + j], c, -lv[j]));  // :285
                                 if (decltype(masked_)::value) {
                                     const int qry = srow0 + 8 * g + 4 * h + j;
+#ifdef FA2_BWD_MFMA16_WINDOW
+                                    if (qry >= N || orow < qry - wl || orow > qry + wr) pe = 0.0f;
+#else
                                     if (qry >= N || (is_causal && orow > qry)) pe = 0.0f;
+#endif
                                 }
                                 pv[j] = pe;
                                 x[4 * g + j] = pe;
@@ -374,7 +414,12 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         if (more) stage_load(t + 1);
         // does this wave meet the tile at all?  (causal: MODE 1 keys of the tile <= last owned query of the wave;
         // MODE 0 queries of the tile >= first owned key of the wave)
+#ifdef FA2_BWD_MFMA16_WINDOW
+        const bool active = MODE == 1 ? !band_none(own0, own0 + 31, t * BS, t * BS + BS - 1)
+                                      : !band_none(t * BS, t * BS + BS - 1, own0, own0 + 31);
+#else
         const bool active = !is_causal || (MODE == 1 ? t * BS <= own0 + 31 : t * BS + BS - 1 >= own0);
+#endif
         if (active) {
             auto first = [&](int kb, f32x16 &x0, f32x16 &x1) __attribute__((always_inline)) {
 #pragma unroll
@@ -411,7 +456,12 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
             auto soft = [&](int kb, f32x16 &x0, f32x16 &x1) __attribute__((always_inline)) {
                 const int srow0 = t * BS + kb * 32;  // first swept row of this 32-row block
                 // swept row of register r: srow0 + (r & 3) + 8 (r >> 2) + 4 h
+#ifdef FA2_BWD_MFMA16_WINDOW
+                const bool need_mask = (srow0 + 32 > N) || (MODE == 1 ? !band_all(own0, own0 + 31, srow0, srow0 + 31)
+                                                                      : !band_all(srow0, srow0 + 31, own0, own0 + 31));
+#else
                 const bool need_mask = (srow0 + 32 > N) || (is_causal && (MODE == 1 ? srow0 + 31 > own0 : srow0 < own0 + 31));
+#endif
                 auto body = [&](auto masked_) __attribute__((always_inline)) {
                     constexpr bool MASKED = decltype(masked_)::value;
 #pragma unroll
@@ -424,7 +474,11 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                             if (MASKED) {
                                 const int srow = srow0 + 8 * g + 4 * h + j;
                                 const int key = MODE == 1 ? srow : orow, qry = MODE == 1 ? orow : srow;
+#ifdef FA2_BWD_MFMA16_WINDOW
+                                if (srow >= N || key < qry - wl || key > qry + wr) p = 0.0f;
+#else
                                 if (srow >= N || (is_causal && key > qry)) p = 0.0f;
+#endif
                             }
                             if (MODE == 1) rsum += p;
                             x1[r] = roleV ? p : p * (x1[r] - dv[j]);  // :291 (the scale factor is applied once, at the end)
@@ -455,7 +509,11 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
             };
             auto skip = [&](int kb) {
                 const int srow0 = t * BS + kb * 32;
+#ifdef FA2_BWD_MFMA16_WINDOW
+                return MODE == 1 ? band_none(own0, own0 + 31, srow0, srow0 + 31) : band_none(srow0, srow0 + 31, own0, own0 + 31);
+#else
                 return is_causal && (MODE == 1 ? srow0 > own0 + 31 : srow0 + 31 < own0);
+#endif
             };
             const bool do0 = !skip(0), do1 = !skip(1);
             // (issuing both blocks' first products before any softmax arithmetic was measured SLOWER in the key-owner
@@ -552,6 +610,9 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+#ifdef FA2_BWD_MFMA16_WINDOW
+// (fa2_bwd_mfma16_supports: in the plain translation unit)
+#else
 bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p) {
     if (p.dtype != FA2_DTYPE_F16 && p.dtype != FA2_DTYPE_BF16) return false;
     if (p.d != 64 && p.d != 128) return false;
@@ -572,7 +633,12 @@ bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p) {
     return true;
 }
 
+#endif
+#ifdef FA2_BWD_MFMA16_WINDOW
+int fa2_bwd_launch_mfma16_window(const Fa2BwdProblem &p) {
+#else
 int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p) {
+#endif
     if (!fa2_bwd_mfma16_supports(p)) {
         fa2_set_error("backward mfma16: needs f16/bf16, d in {64,128}, unit d-stride, 16-byte aligned rows, scale > 0");
         return FA2_ERR_UNSUPPORTED;
@@ -589,7 +655,13 @@ int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p) {
     a.B = p.B; a.H = p.H; a.N = p.N;
     a.causal = (p.causal ? 1 : 0) | (fa2_env_int("FA2_BWD_PRIO", 1) ? 2 : 0);  // bit 1: static priority for the dV waves
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
+#ifdef FA2_BWD_MFMA16_WINDOW
     a.scale = p.scale;
+    a.wl = p.wl;
+    a.wr = p.wr;
+#else
+    a.scale = p.scale;
+#endif
     if (p.dtype == FA2_DTYPE_BF16) return p.d == 128 ? launch_d<__bf16, 128>(p, a) : launch_d<__bf16, 64>(p, a);
     return p.d == 128 ? launch_d<_Float16, 128>(p, a) : launch_d<_Float16, 64>(p, a);
 }

@@ -15,6 +15,7 @@ struct Fa2Problem {
     int32_t dtype, causal;
     float scale;
     hipStream_t stream;
+    int32_t wl, wr;  // local-attention window after fa2_window_normalise(): sides in [0, N-1], N-1 = unbounded (window launchers only)
 };
 
 // Launchers, one per translation unit.  Return FA2_OK / FA2_ERR_*; set_error() on failure.
@@ -34,6 +35,14 @@ int fa2_launch_mfma16s(const Fa2Problem &p, int waves);
 int fa2_launch_mfma16h(const Fa2Problem &p, int waves);  // dispatches to the two translation units below
 int fa2_launch_mfma16h_causal(const Fa2Problem &p, int waves);
 int fa2_launch_mfma16h_noncausal(const Fa2Problem &p, int waves);
+// Local attention (fa2_fwd_window): the windowed instantiations live in translation units of their own.
+int fa2_launch_generic_window(const Fa2Problem &p);
+int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves);
+// Validates and normalises a window (include/fa2_fwd.h): FA2_ERR_BAD_ARG for a side < -1.  On FA2_OK *windowed = 0 means the window
+// removes nothing beyond what plain (*causal_out = 0) or causal (*causal_out = 1) attention removes; *windowed = 1 means the band
+// [i - *wl_out, i + *wr_out] with both sides in [0, N - 1] (N - 1 = unbounded), the causal clamp already applied to *wr_out.
+int fa2_window_normalise(int32_t N, int32_t causal, int32_t wl, int32_t wr, int32_t *causal_out, int32_t *wl_out, int32_t *wr_out,
+                         int32_t *windowed);
 int fa2_launch_a64(const Fa2Problem &p);  // generated assembly kernel (asm/fa2_a64_gen.py)
 bool fa2_a64_supports(const Fa2Problem &p);
 int fa2_launch_a16(const Fa2Problem &p);  // the same structure on v_mfma_f32_16x16x32 (asm/fa2_a16_gen.py)

@@ -21,6 +21,12 @@
 #include "fa2_common.h"
 #include "fa2_elem.h"
 
+// FA2_GENERIC_WINDOW (fa2_generic_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr -- under
+// its own kernel name, compiled in a translation unit of its own; without the macro this file is the plain kernel, unchanged.
+#ifdef FA2_GENERIC_WINDOW
+#define fa2_fwd_generic_kernel fa2_fwd_generic_window_kernel
+#endif
+
 namespace {
 
 constexpr int kRowsPerWave = 4;
@@ -53,7 +59,12 @@ struct GenericArgs {
     const void *Q, *K, *V;
     void *O, *L;
     int64_t qs[4], ks[4], vs[4], os[4], ls[2];
+#ifdef FA2_GENERIC_WINDOW
     int N, d, causal;
+    int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
+#else
+    int N, d, causal;
+#endif
     double c_log2e;  // scale * log2(e); rounded to float for the fp32 dtypes (kernels.py:92)
 };
 
@@ -95,6 +106,15 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
         for (int cc = 0; cc < DPL; ++cc) o[r][cc] = 0;
     }
 
+#ifdef FA2_GENERIC_WINDOW
+    // Same trip count for every wave of the workgroup (barriers inside): the keys of its 16 rows, [i kBr - wl, i kBr + 15 + wr]
+    const int wl = a.wl, wr = a.wr;
+    const int kbeg = i * kBr - wl > 0 ? i * kBr - wl : 0;
+    const int kend = i * kBr + kBr + wr < N ? i * kBr + kBr + wr : N;
+    A *p_w = p_lds + (size_t)wave * kRowsPerWave * kBc;
+
+    for (int kt = kbeg; kt < kend; kt += kBc) {
+#else
     // Same trip count for every wave of the workgroup (barriers inside).
     int kend = N;
     if (a.causal) {
@@ -104,6 +124,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
     A *p_w = p_lds + (size_t)wave * kRowsPerWave * kBc;
 
     for (int kt = 0; kt < kend; kt += kBc) {
+#endif
         const int key = kt + lane;
         const bool valid = key < N;
         A dot[kRowsPerWave];
@@ -121,11 +142,22 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
 #pragma unroll
         for (int r = 0; r < kRowsPerWave; ++r) {
             A s = dot[r] * c;  // kernels.py:92
+#ifdef FA2_GENERIC_WINDOW
+            if (!valid || key < row0 + r - wl || key > row0 + r + wr) s = -INFINITY;
+            const A mx = wave_max(s);
+            const A m_new = m[r] > mx ? m[r] : mx;
+            // a row may meet whole tiles before its band starts: while its maximum is -inf, P and the rescale factor are 0
+            // (not exp2(-inf + inf))
+            const A m_use = m_new == -INFINITY ? (A)0 : m_new;
+            const A p = exp2_acc<A>(s - m_use);
+            const A coeff = exp2_acc<A>(m[r] - m_use);
+#else
             if (!valid || (a.causal && key > row0 + r)) s = -INFINITY;
             const A mx = wave_max(s);
             const A m_new = m[r] > mx ? m[r] : mx;           // :93
             const A p = exp2_acc<A>(s - m_new);              // :94
             const A coeff = exp2_acc<A>(m[r] - m_new);       // :95
+#endif
             lsum[r] = coeff * lsum[r] + p;                   // :96 (per-lane partial of the row sum)
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) o[r][cc] *= coeff;  // :97
@@ -192,7 +224,11 @@ template <class E> int launch_e(const Fa2Problem &p, const GenericArgs &a) {
 
 }  // namespace
 
+#ifdef FA2_GENERIC_WINDOW
+int fa2_launch_generic_window(const Fa2Problem &p) {
+#else
 int fa2_launch_generic(const Fa2Problem &p) {
+#endif
     if (p.B > 65535 || p.H > 65535) {
         fa2_set_error("generic kernel: B and H must be <= 65535");
         return FA2_ERR_BAD_ARG;
@@ -201,7 +237,11 @@ int fa2_launch_generic(const Fa2Problem &p) {
     a.Q = p.Q; a.K = p.K; a.V = p.V; a.O = p.O; a.L = p.L;
     for (int k = 0; k < 4; ++k) { a.qs[k] = p.qs[k]; a.ks[k] = p.ks[k]; a.vs[k] = p.vs[k]; a.os[k] = p.os[k]; }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
+#ifdef FA2_GENERIC_WINDOW
+    a.N = p.N; a.d = p.d; a.causal = 0; a.wl = p.wl; a.wr = p.wr;
+#else
     a.N = p.N; a.d = p.d; a.causal = p.causal;
+#endif
     a.c_log2e = (double)p.scale * FA2_LOG2E;
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);

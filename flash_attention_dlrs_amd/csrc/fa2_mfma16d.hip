@@ -12,6 +12,14 @@
 // zero-filled by the buffer descriptor's range check.
 #include "fa2_common.h"
 
+// FA2_MFMA16D_WINDOW (fa2_mfma16d_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr, one tile per
+// workgroup, the key loop from the 64-key unit of the tile's first visible key, blocks outside a wave's band skipped, blocks across
+// its edges masked -- under its own kernel name, compiled in a translation unit of its own; without the macro this file is the
+// plain kernel, unchanged.
+#ifdef FA2_MFMA16D_WINDOW
+#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_window_kernel
+#endif
+
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -46,7 +54,12 @@ struct DmaArgs {
     int B, H, N;
     float c_log2e;
     int group;
+#ifdef FA2_MFMA16D_WINDOW
     int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
+    int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise)
+#else
+    int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
+#endif
 };
 
 __device__ __forceinline__ void half_swap(float x, float &lo, float &hi) {
@@ -108,7 +121,12 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform (M0, scalar branches)
     const int i = lane & 31, h = lane >> 5;
+#ifdef FA2_MFMA16D_WINDOW
     const int N = a.N;
+    const int wl = a.wl, wr = a.wr;
+#else
+    const int N = a.N;
+#endif
     // T5 static form (cdna_hip_programming.md): the second-dispatched half loses VALU arbitration on every segment
     if ((a.flags & 1) && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
 
@@ -213,12 +231,20 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
     };
     auto partial = [&](f32x16 &s, int j, float &coeff, bool masked) -> bool {
         if (masked) {
+#ifdef FA2_MFMA16D_WINDOW
+            const int lim = qrow + wr < N - 1 ? qrow + wr : N - 1;
+            const int klim = lim - (j * 32 + 4 * h), klo = qrow - wl - (j * 32 + 4 * h);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if ((r & 3) + 8 * (r >> 2) > klim || (r & 3) + 8 * (r >> 2) < klo) s[r] = -INFINITY;
+#else
             int lim = N - 1;
             if (CAUSAL) lim = qrow < lim ? qrow : lim;
             const int klim = lim - (j * 32 + 4 * h);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if ((r & 3) + 8 * (r >> 2) > klim) s[r] = -INFINITY;
+#endif
         }
         float mx = fmaxf(s[0], s[1]);
 #pragma unroll
@@ -270,7 +296,11 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
                 o[db] = M::mfma(__builtin_bit_cast(frag, vf), pf[ss], o[db]);
             }
     };
+#ifdef FA2_MFMA16D_WINDOW
+    auto block_masked = [&](int j) { return (j * 32 + 32 > N) || (j * 32 < q0 + 31 - wl) || (j * 32 + 31 > q0 + wr); };
+#else
     auto block_masked = [&](int j) { return (CAUSAL && (j * 32 + 31 > q0)) || (j * 32 + 32 > N); };
+#endif
 
     for (int pass = 0; pass < npass; ++pass) {
         const int qi = pass == 0 ? qi_first : qi_second;
@@ -282,6 +312,107 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(frag, *(const u32x4 *)(qp + ks * 32));
         }
+#ifdef FA2_MFMA16D_WINDOW
+        // window: the keys of the tile's rows [qi BR - wl, qi BR + BR - 1 + wr]; the loop starts at the 64-key unit t0 of the
+        // first one.  Per wave: blocks [jlo, nb) meet its band, the others are skipped
+        kend = qi * BR + BR + wr < N ? qi * BR + BR + wr : N;
+        const int t0 = qi * BR - wl > 0 ? (qi * BR - wl) >> 6 : 0;
+        const int jlo = q0 - wl > 0 ? (q0 - wl) >> 5 : 0;
+        nt = (kend + 63) >> 6;    // V tiles (loop iterations t0 .. nt-1)
+        nblk = (kend + 31) >> 5;  // 32-key blocks of this tile
+        {
+            const int hi = q0 + 31 + wr < N - 1 ? q0 + 31 + wr : N - 1;
+            nb = (hi >> 5) + 1 < nblk ? (hi >> 5) + 1 : nblk;
+        }
+        auto act = [&](int j) { return j >= jlo && j < nb; };
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
+        // a row may meet whole blocks before its band starts: a finite floor keeps exp2(m_old - m_new) and exp2(-inf - m) at 0
+        // there instead of exp2(-inf + inf); the row's first visible key raises m above it at once (fire below)
+        m = -1e30f;
+        lsum = 0.0f;
+
+        // ---- prologue: K units t0, t0 + 1 and V tile t0 (the buffers alternate from t0 on)
+        dma_k(t0, 0);
+        dma_v(t0, 0);
+        dma_k(t0 + 1, 1);
+        dma_wait();
+        __syncthreads();
+
+        f32x16 sA, sB;
+        float coeffA = 1.0f, coeffB = 1.0f;
+        bool fireA = false, fireB = false;
+        frag pf[2];
+        if (act(2 * t0)) {
+            qk(sA, 32 * ROWB);  // block 2 t0 = rows 32..63 of K unit t0
+            fireA = partial(sA, 2 * t0, coeffA, block_masked(2 * t0));
+        }
+        __syncthreads();    // K unit t0 is overwritten by unit t0 + 2 in iteration t0
+
+        // steady iterations t: block 2t computed, blocks 2t+1 and 2t+2 inside the band for all 32 rows of the wave
+        const int ulo = q0 + 31 - wl > 0 ? (q0 + 31 - wl + 31) >> 5 : 0;  // first block without a left-edge mask
+        int umax = q0 + wr - 31 < 0 ? -1 : (q0 + wr - 31) >> 5;            // last block without a right-edge mask
+        umax = (N >> 5) - 1 < umax ? (N >> 5) - 1 : umax;
+        int t_head = (jlo + 1) >> 1 > (ulo >> 1) ? (jlo + 1) >> 1 : ulo >> 1;
+        t_head = t_head < t0 ? t0 : (t_head > nt ? nt : t_head);
+        int t_steady = umax >= 2 ? (umax - 2) / 2 + 1 : 0;
+        t_steady = t_steady < t_head ? t_head : (t_steady > nt ? nt : t_steady);
+
+        // head and tail iterations: every block guarded, edge blocks masked
+        auto guarded_step = [&](int t) __attribute__((always_inline)) {
+            const bool more = t + 1 < nt;
+            if (more) {
+                dma_k(t + 2, (t - t0) & 1);
+                dma_v(t + 1, (t + 1 - t0) & 1);
+            }
+            const int kcur = ((t + 1 - t0) & 1) * TILEB;
+            const int vcur = ((t - t0) & 1) * TILEB;
+            const int jA = 2 * t, jB = 2 * t + 1, jA2 = 2 * t + 2;
+            if (act(jA)) rescale(fireA, coeffA);
+            if (act(jB)) qk(sB, kcur);
+            if (act(jA)) {
+                finish(sA, pf);
+                pv(pf, vcur);
+            }
+            if (act(jB)) {
+                fireB = partial(sB, jB, coeffB, block_masked(jB));
+                rescale(fireB, coeffB);
+            }
+            if (act(jA2)) qk(sA, kcur + 32 * ROWB);
+            if (act(jB)) {
+                finish(sB, pf);
+                pv(pf, vcur + 32 * ROWB);
+            }
+            if (act(jA2)) fireA = partial(sA, jA2, coeffA, block_masked(jA2));
+            dma_wait();
+            __syncthreads();
+        };
+
+        int t = t0;
+        for (; t < t_head; ++t) guarded_step(t);
+        for (; t < t_steady; ++t) {
+            dma_k(t + 2, (t - t0) & 1);
+            dma_v(t + 1, (t + 1 - t0) & 1);
+            const int kcur = ((t + 1 - t0) & 1) * TILEB;  // K unit t+1: rows 0..31 = block 2t+1, rows 32..63 = block 2t+2
+            const int vcur = ((t - t0) & 1) * TILEB;      // V tile t:   rows 0..31 = block 2t,   rows 32..63 = block 2t+1
+            rescale(fireA, coeffA);
+            qk(sB, kcur);
+            finish(sA, pf);
+            pv(pf, vcur);
+            fireB = partial(sB, 2 * t + 1, coeffB, false);
+            rescale(fireB, coeffB);
+            qk(sA, kcur + 32 * ROWB);
+            finish(sB, pf);
+            pv(pf, vcur + 32 * ROWB);
+            fireA = partial(sA, 2 * t + 2, coeffA, false);
+            dma_wait();
+            __syncthreads();
+        }
+        for (; t < nt; ++t) guarded_step(t);
+
+#else
         kend = CAUSAL ? ((qi * BR + BR) < N ? (qi * BR + BR) : N) : N;
         nt = (kend + 63) >> 6;    // V tiles (= loop iterations)
         nblk = (kend + 31) >> 5;  // 32-key blocks of this tile
@@ -365,6 +496,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
             __syncthreads();
         }
 
+#endif
         // ---- epilogue (kernels.py:105-108).  A lane owns one ROW of O (columns 32db + 8g + 4h ..+3): stored straight
         // from the accumulators that is 16 eight-byte stores per lane, each instruction touching 32 rows.  Instead the
         // wave's 32 x D tile goes through its own 32*ROWB-byte slice of the (now idle) K/V buffers and leaves as
@@ -414,10 +546,14 @@ template <typename T, int D, int NW> int launch_t(const Fa2Problem &p, const Dma
     }
     const dim3 grid((unsigned)nblk), block(NW * 64);
     constexpr size_t smem = 4 * 64 * D * 2;  // 64 KiB (d = 128) / 32 KiB (d = 64)
+#ifdef FA2_MFMA16D_WINDOW
+    hipLaunchKernelGGL((fa2_fwd_mfma16d_kernel<T, D, NW, false>), grid, block, smem, p.stream, a);  // (p.causal is 0: in wr)
+#else
     if (p.causal)
         hipLaunchKernelGGL((fa2_fwd_mfma16d_kernel<T, D, NW, true>), grid, block, smem, p.stream, a);
     else
         hipLaunchKernelGGL((fa2_fwd_mfma16d_kernel<T, D, NW, false>), grid, block, smem, p.stream, a);
+#endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("mfma16d kernel launch failed: %s", hipGetErrorString(e));
@@ -433,7 +569,11 @@ template <typename T> int launch_d(const Fa2Problem &p, const DmaArgs &a, int wa
 
 }  // namespace
 
+#ifdef FA2_MFMA16D_WINDOW
+int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves) {
+#else
 int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
+#endif
     const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
     if (!fa2_mfma16_supports(p) || !fits32) {
         fa2_set_error("mfma16d kernel: needs f16/bf16, d in {64,128}, unit d-stride, 16-byte aligned rows, scale > 0, "
@@ -450,7 +590,13 @@ int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
     a.B = p.B; a.H = p.H; a.N = p.N;
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
     a.group = 1;
+#ifdef FA2_MFMA16D_WINDOW
     a.flags = fa2_env_int("FA2_FLAGS", 0);
+    a.wl = p.wl;
+    a.wr = p.wr;
+#else
+    a.flags = fa2_env_int("FA2_FLAGS", 0);
+#endif
     if (p.causal && ((p.B * p.H) & 7) == 0) {
         const int per_xcd = p.B * p.H / 8;
         int g = fa2_env_int("FA2_CAUSAL_GROUP", 2);

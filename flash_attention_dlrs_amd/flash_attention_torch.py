@@ -85,6 +85,41 @@ def forward_head_size(dtype, B, H, N, d, causal=False):
     return d
 
 
+def normalize_window(N, causal, window):
+    """Validate and normalise a local-attention window (include/fa2_fwd.h, fa2_fwd_window) -> (causal, window or None).
+
+    window = (left, right), Python ints, -1 = unbounded on that side: key j is visible to query i iff
+    i - left <= j <= i + right.  causal also requires j <= i, so right is clamped to 0.  A side >= N - 1 is unbounded; a
+    window that then removes nothing beyond plain or causal attention comes back as None (with causal set for the causal
+    case), so the caller runs the plain / causal path unchanged.  ValueError for anything but two ints >= -1."""
+    if window is None:
+        return bool(causal), None
+    if not isinstance(window, (tuple, list)) or len(window) != 2:
+        raise ValueError(f"window must be a (left, right) pair of ints, got {window!r}")
+    for w in window:
+        if isinstance(w, bool) or not isinstance(w, int):
+            raise ValueError(f"window sides must be Python ints, got {window!r}")
+        if w < -1:
+            raise ValueError(f"window sides must be >= -1 (-1 = unbounded), got {window!r}")
+    full = max(int(N) - 1, 0)
+    left, right = (full if (w < 0 or w >= full) else w for w in window)
+    if causal:
+        right = 0
+    if left == full and right == full:
+        return bool(causal), None
+    if left == full and right == 0:
+        return True, None
+    return False, (left, right)
+
+
+def window_head_size(dtype, d):
+    """Head size a windowed forward runs at: f16 / bf16 below 128 other than 64 are zero-padded to 64 or 128 (the windowed
+    matrix kernel's sizes, like the pad rule of forward_head_size); everything else runs as it is (the VALU kernel)."""
+    if dtype in (torch.float16, torch.bfloat16) and d < 128 and d != 64:
+        return 64 if d < 64 else 128
+    return d
+
+
 def _check_inputs(Q, K, V):
     dev = Q.device
     if dev.type != "cuda" or dev != K.device or dev != V.device:
@@ -95,10 +130,15 @@ def _check_inputs(Q, K, V):
         raise ValueError("Q, K, V must have same dtype")
 
 
-def _forward_impl(ctx, Q, K, V, causal, scale):
+def _forward_impl(ctx, Q, K, V, causal, scale, window=None):
     _check_inputs(Q, K, V)
     B, H, N, d = Q.shape
     dtype = convert_triton_dtype(Q.dtype)
+    if window is not None:
+        causal, window = normalize_window(N, causal, window)
+    ctx.window = window
+    if window is not None:
+        return _forward_window(ctx, Q, K, V, dtype, scale, window)
 
     # Non-power-of-2 d or d < 16: the reference pads Q, K, V on the host (torch.py:38-47) and returns the O[..., :d] view
     # of a padded O.  The forward kernels take any d (the MFMA kernels zero-fill the missing
@@ -133,14 +173,55 @@ def _forward_impl(ctx, Q, K, V, causal, scale):
     return O
 
 
-def attention_backward_recompute(Q, K, V, O, dO, L, causal=False, scale=1.0):
+def _forward_window(ctx, Q, K, V, dtype, scale, window):
+    """Local attention (normalised window): padded like the plain path where the windowed matrix kernel wants it; the
+    autotuner is not consulted (its key does not see the window)."""
+    B, H, N, d = Q.shape
+    d_proper = max(next_power_of_2(d), MIN_TENSOR_SIZE)
+    d_run = window_head_size(Q.dtype, d)
+    L = torch.empty(B, H, N, 1, dtype=Q.dtype, device=Q.device)
+    if d_run != d:
+        Qr, Kr, Vr = (pad_last_dim(t, d_run) for t in (Q, K, V))
+        Or = torch.empty_like(Qr)
+        _lib.fa2_fwd(Qr, Kr, Vr, Or, L, dtype, causal=False, scale=scale, window=window)
+        O = Or[..., :d]
+    else:
+        O = torch.empty_like(Q)
+        _lib.fa2_fwd(Q, K, V, O, L, dtype, causal=False, scale=scale, window=window)
+    ctx.save_for_backward(Q, K, V, O, L)
+    ctx.padded = d_proper != d
+    ctx.d_used = d_proper
+    ctx.d_orig = d
+    ctx.causal = False
+    ctx.scale = float(scale)
+    return O
+
+
+def window_mask(N, causal=False, window=None, device=None):
+    """(N, N) boolean mask of the visible (query, key) pairs, or None when nothing is masked (normalize_window)."""
+    causal, window = normalize_window(N, causal, window)
+    if window is None and not causal:
+        return None
+    i = torch.arange(N, device=device).view(N, 1)
+    j = torch.arange(N, device=device).view(1, N)
+    if window is None:
+        return j <= i
+    return (j >= i - window[0]) & (j <= i + window[1])
+
+
+def attention_backward_recompute(Q, K, V, O, dO, L, causal=False, scale=1.0, *, window=None):
     """dQ, dK, dV from the saved statistics in plain torch ops: a readable restatement used by the tests only
     (the product path is _backward_native below).
-    P = exp2(scale * S * log2e - L) (reference kernels.py:283-285), D = rowsum(dO * O) (kernels.py:120-166)."""
+    P = exp2(scale * S * log2e - L) (reference kernels.py:283-285), D = rowsum(dO * O) (kernels.py:120-166).
+    window: local attention, as fa2_fwd_window (P is 0 outside the band)."""
     f = torch.float64 if Q.dtype == torch.float64 else torch.float32
     q, k, v, o, do, l = (t.to(f) for t in (Q, K, V, O, dO, L))
     S = torch.matmul(q, k.transpose(-1, -2)) * (scale * math.log2(math.e))
-    if causal:
+    if window is not None:
+        mask = window_mask(Q.shape[2], causal, window, Q.device)
+        if mask is not None:
+            S = S.masked_fill(~mask, float("-inf"))
+    elif causal:
         N = Q.shape[2]
         mask = torch.ones(N, N, dtype=torch.bool, device=Q.device).tril()
         S = S.masked_fill(~mask, float("-inf"))
@@ -154,9 +235,12 @@ def attention_backward_recompute(Q, K, V, O, dO, L, causal=False, scale=1.0):
     return dQ.to(Q.dtype), dK.to(K.dtype), dV.to(V.dtype)
 
 
-def backward_native(Q, K, V, O, dO, L, causal=False, scale=1.0, variant="auto"):
+def backward_native(Q, K, V, O, dO, L, causal=False, scale=1.0, variant="auto", *, window=None):
     """Host glue of the backward launch (reference torch.py:101-155): allocate dQ, dK, dV (strides of Q, K, V) and
-    the scratch D, launch, return the gradients.  Inputs are already padded to a supported d."""
+    the scratch D, launch, return the gradients.  Inputs are already padded to a supported d.  window: local attention
+    (normalize_window); a window that reduces to plain or causal attention takes the plain launch."""
+    if window is not None:
+        causal, window = normalize_window(Q.shape[2], causal, window)
     dtype = convert_triton_dtype(Q.dtype)
     if Q.dtype in (torch.float8_e5m2, torch.float8_e4m3fn):
         raise TypeError(f"dtype {Q.dtype} not supported by the backward.")
@@ -167,7 +251,7 @@ def backward_native(Q, K, V, O, dO, L, causal=False, scale=1.0, variant="auto"):
     if dO.stride(-1) != 1:
         dO = dO.contiguous()
     _lib.fa2_bwd(Q, K, V, O, dO, L, dQ, dK, dV, D, dtype, causal=causal, scale=scale,
-                 variant=_lib.BWD_VARIANTS[variant])
+                 variant=_lib.BWD_VARIANTS[variant], window=window)
     return dQ, dK, dV
 
 
@@ -177,20 +261,21 @@ def _backward_impl(ctx, dO):
         raise ValueError("dO must have same dtype as inputs")
     if ctx.padded:   # (reference torch.py:91-100 pads in its backward as well)
         Q, K, V, O, dO = (pad_last_dim(t, ctx.d_used) for t in (Q, K, V, O, dO))
-    dQ, dK, dV = backward_native(Q, K, V, O, dO, L, ctx.causal, ctx.scale)
+    dQ, dK, dV = backward_native(Q, K, V, O, dO, L, ctx.causal, ctx.scale, window=ctx.window)
     if ctx.padded:
         d = ctx.d_orig
-        return dQ[..., :d], dK[..., :d], dV[..., :d], None, None
-    return dQ, dK, dV, None, None
+        return dQ[..., :d], dK[..., :d], dV[..., :d], None, None, None
+    return dQ, dK, dV, None, None, None
 
 
 class FlashAttention(torch.autograd.Function):
     """O = softmax(Q K^T) V with scale 1 (reference torch.py:21-84).  `FlashAttention.apply(Q, K, V)`;
-    optional extras `FlashAttention.apply(Q, K, V, causal, scale)`."""
+    optional extras `FlashAttention.apply(Q, K, V, causal, scale, window)`: window = (left, right) is local attention
+    (key j visible to query i iff i - left <= j <= i + right, -1 = unbounded; causal clamps right to 0), None the plain call."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, causal=False, scale=1.0):
-        return _forward_impl(ctx, Q, K, V, causal, scale)
+    def forward(ctx, Q, K, V, causal=False, scale=1.0, window=None):
+        return _forward_impl(ctx, Q, K, V, causal, scale, window)
 
     @staticmethod
     def backward(ctx, grad_outputs, *args):
@@ -199,11 +284,11 @@ class FlashAttention(torch.autograd.Function):
 
 class FlashAttentionDeterministic(torch.autograd.Function):
     """Same forward as FlashAttention (the reference's two forwards are identical, torch.py:161-224);
-    the recompute backward used here is deterministic by construction."""
+    the recompute backward used here is deterministic by construction.  Same optional extras (causal, scale, window)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, causal=False, scale=1.0):
-        return _forward_impl(ctx, Q, K, V, causal, scale)
+    def forward(ctx, Q, K, V, causal=False, scale=1.0, window=None):
+        return _forward_impl(ctx, Q, K, V, causal, scale, window)
 
     @staticmethod
     def backward(ctx, grad_outputs, *args):

@@ -7,17 +7,22 @@ import torch
 
 from . import _lib, autotune
 from .flash_attention_torch import (MIN_TENSOR_SIZE, backward_native, convert_triton_dtype, forward_head_size,
-                                    next_power_of_2, pad_last_dim)
+                                    next_power_of_2, normalize_window, pad_last_dim, window_head_size)
 
 
-def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="auto"):
+def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="auto", window=None):
     # Takes tensors of shape (B, H, N, d): batch, heads, context size, head dimension
     # (reference wrappers.py:14-22: bare asserts, kept).
+    # window = (left, right): local attention (FlashAttention's docstring; include/fa2_fwd.h fa2_fwd_window).
     assert Q.dim() == 4
     assert Q.shape == K.shape and K.shape == V.shape
     assert Q.dtype == K.dtype and K.dtype == V.dtype
 
     B, H, N, d = Q.shape
+    if window is not None:
+        causal, window = normalize_window(N, causal, window)
+        if window is not None:
+            return _forward_window(Q, K, V, dev, scale, variant, window)
 
     # The reference pads Q, K, V to next_pow2(d) here (wrappers.py:27-34) and slices O afterwards; the kernels take any d
     # (SURVEY section 8 row f2): head sizes the matrix cores take run as they are (nothing copied, O has exactly d columns), the
@@ -52,7 +57,28 @@ def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="a
     return O[..., :d_out], L     # (reference wrappers.py:63)
 
 
-def flash_attention_backward(Q, K, V, O, dO, L, dev, deterministic=False, *, causal=False, scale=1.0, variant="auto"):
+def _forward_window(Q, K, V, dev, scale, variant, window):
+    """Local attention with a normalised window: contiguous O, padded like the plain path where the windowed matrix kernel
+    wants it (auto only; a forced variant gets the tensors as they are); the autotuner is not consulted."""
+    B, H, N, d_out = Q.shape
+    d = d_out
+    if variant == "auto":
+        d = window_head_size(Q.dtype, d_out)
+        if d != d_out:
+            Q, K, V = (pad_last_dim(t, d) for t in (Q, K, V))
+    O = torch.empty(B, H, N, d, dtype=Q.dtype, device=dev)
+    L = torch.empty(B, H, N, 1, dtype=Q.dtype, device=dev)
+    dtype = convert_triton_dtype(Q.dtype)
+    if O.device != Q.device:
+        raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
+    _lib.fa2_fwd(Q, K, V, O, L, dtype, causal=False, scale=scale, variant=_lib.VARIANTS[variant], window=window)
+    if d != d_out:
+        O = O[..., :d_out].contiguous()
+    return O, L
+
+
+def flash_attention_backward(Q, K, V, O, dO, L, dev, deterministic=False, *, causal=False, scale=1.0, variant="auto",
+                             window=None):
     """(dQ, dK, dV) through the native backward kernels (include/fa2_bwd.h).  Same signature as the reference
     (wrappers.py:66-75); `deterministic` selects between two kernels there -- here the one implementation is
     deterministic by construction, so the flag is accepted and ignored.  d is padded like in the forward
@@ -64,5 +90,5 @@ def flash_attention_backward(Q, K, V, O, dO, L, dev, deterministic=False, *, cau
     d_pow = max(next_power_of_2(d), MIN_TENSOR_SIZE)
     if d_pow != d:
         Q, K, V, O, dO = (pad_last_dim(t, d_pow) for t in (Q, K, V, O, dO))
-    dQ, dK, dV = backward_native(Q, K, V, O, dO, L, causal=causal, scale=scale, variant=variant)
+    dQ, dK, dV = backward_native(Q, K, V, O, dO, L, causal=causal, scale=scale, variant=variant, window=window)
     return dQ[..., :d], dK[..., :d], dV[..., :d]

@@ -31,13 +31,13 @@ def shard_heads(t, world_size, rank):
     return t[:, h0:h1]
 
 
-def _default_local_forward(Q, K, V, causal, scale):
+def _default_local_forward(Q, K, V, causal, scale, window=None):
     from .flash_attention_wrappers import flash_attention_forward
-    return flash_attention_forward(Q, K, V, Q.device, causal=causal, scale=scale)
+    return flash_attention_forward(Q, K, V, Q.device, causal=causal, scale=scale, window=window)
 
 
 def flash_attention_forward_sharded(Q, K, V, *, group=None, causal=False, scale=1.0, gather=True,
-                                    gather_L=False, local_forward=None):
+                                    gather_L=False, local_forward=None, window=None):
     """Forward on this rank's head shard, optionally all-gathered.
 
     Q, K, V : this rank's shard, (B, H/G, N, d), resident on this rank's device.
@@ -45,8 +45,13 @@ def flash_attention_forward_sharded(Q, K, V, *, group=None, causal=False, scale=
       gather=False : the local shards (B, H/G, N, d), (B, H/G, N, 1) -- no collective at all.
       gather=True  : O as the full (B, H, N, d) tensor on every rank; L likewise if gather_L else local.
     `local_forward(Q, K, V, causal, scale) -> (O, L)` defaults to the HIP path; CPU tests inject one.
+    window: local attention (heads stay independent); handed to local_forward as a keyword only when it is not None, so
+    five-argument callables keep working.
     """
     fwd = local_forward or _default_local_forward
+    if window is not None:
+        fwd_plain = fwd
+        fwd = lambda q, k, v, c, s: fwd_plain(q, k, v, c, s, window=window)  # noqa: E731
     if not gather:
         return fwd(Q, K, V, causal, scale)
 
@@ -89,12 +94,12 @@ def flash_attention_forward_sharded(Q, K, V, *, group=None, causal=False, scale=
     return O_full, (L_full if gather_L else L_local)
 
 
-def _default_local_backward(Q, K, V, O, dO, L, causal, scale):
+def _default_local_backward(Q, K, V, O, dO, L, causal, scale, window=None):
     from .flash_attention_wrappers import flash_attention_backward
-    return flash_attention_backward(Q, K, V, O, dO, L, Q.device, causal=causal, scale=scale)
+    return flash_attention_backward(Q, K, V, O, dO, L, Q.device, causal=causal, scale=scale, window=window)
 
 
-def flash_attention_backward_sharded(Q, K, V, O, dO, L, *, causal=False, scale=1.0, local_backward=None):
+def flash_attention_backward_sharded(Q, K, V, O, dO, L, *, causal=False, scale=1.0, local_backward=None, window=None):
     """Backward on this rank's head shard: (dQ, dK, dV) of the local heads, shapes (B, H/G, N, d).
 
     No collective: the gradient of head h depends only on head h's Q, K, V, O, dO, L (reference bwd_kernel,
@@ -102,4 +107,6 @@ def flash_attention_backward_sharded(Q, K, V, O, dO, L, *, causal=False, scale=1
     gradients ARE its shard of the full gradients -- slice of the single-GPU result bit for bit.  If dO arrives as the
     full (B, H, N, d) tensor (e.g. from a loss computed on gathered outputs), pass `shard_heads(dO, G, rank)`."""
     bwd = local_backward or _default_local_backward
+    if window is not None:  # (as a keyword, only when set: five-argument callables keep working)
+        return bwd(Q, K, V, O, dO, L, causal, scale, window=window)
     return bwd(Q, K, V, O, dO, L, causal, scale)

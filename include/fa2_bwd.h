@@ -68,6 +68,29 @@ int fa2_bwd_variant(const void *Q, const void *K, const void *V, const void *O, 
                     int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
                     void *hip_stream, int32_t variant);
 
+/* Local (sliding-window) attention: the gradients of fa2_fwd_window's O, given its L.  Same arguments as fa2_bwd /
+ * fa2_bwd_variant plus window_left, window_right after `scale`, with the window semantics, the causal clamp
+ * (window_right -> 0), the FA2_ERR_BAD_ARG for a side < -1 and the normalisation of include/fa2_fwd.h: a window that
+ * reduces to plain or causal attention runs fa2_bwd's own path.  Variants that take a window: FA2_BWD_VARIANT_AUTO
+ * (MFMA16 where it runs, else GENERIC), FA2_BWD_VARIANT_GENERIC (f64, f32, f16, bf16) and FA2_BWD_VARIANT_MFMA16; a forced
+ * FA2_BWD_VARIANT_MFMA32 returns FA2_ERR_UNSUPPORTED. */
+int fa2_bwd_window(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                   void *dQ, void *dK, void *dV, void *D,
+                   const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                   const int64_t o_strides[4], const int64_t do_strides[4], const int64_t dq_strides[4],
+                   const int64_t dk_strides[4], const int64_t dv_strides[4], const int64_t l_strides[2],
+                   int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
+                   int32_t window_left, int32_t window_right, void *hip_stream);
+
+int fa2_bwd_window_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO,
+                           const void *L, void *dQ, void *dK, void *dV, void *D,
+                           const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                           const int64_t o_strides[4], const int64_t do_strides[4], const int64_t dq_strides[4],
+                           const int64_t dk_strides[4], const int64_t dv_strides[4], const int64_t l_strides[2],
+                           int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+                           float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                           int32_t variant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,35 @@ int fa2_fwd_variant(const void *Q, const void *K, const void *V, void *O, void *
                     int32_t dtype_enum, int32_t causal, float scale, void *hip_stream,
                     int32_t variant);
 
+/*
+ * Local (sliding-window) attention.  Same arguments as fa2_fwd / fa2_fwd_variant, plus the window after `scale`:
+ *
+ *   key j is visible to query i  iff  i - window_left <= j <= i + window_right,   a side of -1 = unbounded.
+ *
+ * causal != 0 also requires j <= i: window_right is clamped to 0.  Both sides must be >= -1, else FA2_ERR_BAD_ARG
+ * ("window" in the message) before any launch.  O = softmax(scale * Q K^T over the visible keys) V and L the log2-domain
+ * log-sum-exp over the visible keys, as fa2_fwd defines it.  Every row keeps its diagonal key, so no row is empty.
+ * Normalisation: a side >= N - 1 is unbounded; then the causal clamp; a window that removes nothing beyond plain or causal
+ * attention -- (-1, -1), (N-1, N-1), (-1, 0), causal with (-1, r) -- runs fa2_fwd's own path (plain, resp. causal = 1), so the
+ * results are bit-identical to the plain / causal call.
+ * Variants that take a window: FA2_VARIANT_AUTO (the windowed table: MFMA16D / MFMA16D_W4 where they run, else GENERIC),
+ * FA2_VARIANT_GENERIC (every dtype, any strides, any d), FA2_VARIANT_MFMA16D and FA2_VARIANT_MFMA16D_W4 (f16 / bf16,
+ * d in {64, 128}: blocks outside the band are skipped, blocks across its edges masked).  Any other forced variant returns
+ * FA2_ERR_UNSUPPORTED for a window that does not reduce.
+ */
+int fa2_fwd_window(const void *Q, const void *K, const void *V, void *O, void *L,
+                   const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                   const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t N,
+                   int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                   int32_t window_right, void *hip_stream);
+
+int fa2_fwd_window_variant(const void *Q, const void *K, const void *V, void *O, void *L,
+                           const int64_t q_strides[4], const int64_t k_strides[4],
+                           const int64_t v_strides[4], const int64_t o_strides[4],
+                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                           int32_t window_right, void *hip_stream, int32_t variant);
+
 /* Which tile the static table picks for a contiguous problem: out4 = {variant, B_r, B_c, waves}.
  * Counterpart of fwd_conf_prune + the autotuner's choice (src/autotune_configs.py:176-194). */
 int fa2_query_tile(int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, int32_t out4[4]);
