@@ -5,9 +5,11 @@ Triton launch they make is replaced by the C-ABI call fa2_fwd() of libfa2_hip.so
 a hand-written HIP/CDNA4 kernel library.  There is no CPU fallback: without the built library, or on
 non-GPU tensors, calls fail loudly.
 """
-from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttentionDeterministic,
-                                    convert_triton_dtype)
-from .flash_attention_wrappers import flash_attention_backward, flash_attention_forward
+from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttentionDeterministic, FlashAttentionVarlen,
+                                    convert_triton_dtype, varlen_mask)
+from .flash_attention_wrappers import (flash_attention_backward, flash_attention_forward, flash_attention_varlen_backward,
+                                       flash_attention_varlen_forward)
 
-__all__ = ["FlashAttention", "FlashAttentionDeterministic", "convert_triton_dtype", "MIN_TENSOR_SIZE",
-           "flash_attention_forward", "flash_attention_backward"]
+__all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
+           "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
+           "flash_attention_varlen_backward", "varlen_mask"]

@@ -50,9 +50,9 @@ if os.path.basename(LIB_PATH) in ("libfa2_hip_exp.so", "libfa2_hip_abl.so"):
 
 # Every symbol include/fa2_fwd.h declares (tests/test_abi.py checks the export list against the header).
 SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", "fa2_query_tile_scaled", "fa2_version", "fa2_last_error",
-           "fa2_fwd_window", "fa2_fwd_window_variant")
+           "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant")
 # ... and include/fa2_bwd.h
-BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant")
+BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant")
 BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
 
 _lib = None
@@ -88,6 +88,17 @@ def lib():
         l.fa2_fwd_window.argtypes = win
         l.fa2_fwd_window_variant.restype = ctypes.c_int
         l.fa2_fwd_window_variant.argtypes = win + [ctypes.c_int32]
+        # variable-length (packed): 3-element strides, L head stride, cu_seqlens, B H d, max_seqlen, total, dtype causal, scale, window
+        vl = [vp] * 5 + [i64p] * 4 + [ctypes.c_int64, vp, vp] + [ctypes.c_int32] * 9 + [ctypes.c_float] + [ctypes.c_int32] * 2 + [vp]
+        l.fa2_fwd_varlen.restype = ctypes.c_int
+        l.fa2_fwd_varlen.argtypes = vl
+        l.fa2_fwd_varlen_variant.restype = ctypes.c_int
+        l.fa2_fwd_varlen_variant.argtypes = vl + [ctypes.c_int32]
+        bvl = [vp] * 10 + [i64p] * 8 + [ctypes.c_int64, vp, vp] + [ctypes.c_int32] * 9 + [ctypes.c_float] + [ctypes.c_int32] * 2 + [vp]
+        l.fa2_bwd_varlen.restype = ctypes.c_int
+        l.fa2_bwd_varlen.argtypes = bvl
+        l.fa2_bwd_varlen_variant.restype = ctypes.c_int
+        l.fa2_bwd_varlen_variant.argtypes = bvl + [ctypes.c_int32]
         l.fa2_query_tile.restype = ctypes.c_int
         l.fa2_query_tile.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]
         l.fa2_query_tile_ex.restype = ctypes.c_int
@@ -227,5 +238,40 @@ def fa2_bwd(Q, K, V, O, dO, L, dQ, dK, dV, D, dtype_enum, causal=False, scale=1.
     else:
         with torch.cuda.device(Q.device):
             rc = launch()
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_fwd_varlen(Q, K, V, O, L, cu_q, cu_k, max_q, max_k, dtype_enum, causal=False, scale=1.0, window=None,
+                   variant=VARIANT_AUTO):
+    """Launch the variable-length forward (include/fa2_fwd.h fa2_fwd_varlen_variant) on the current stream of Q's device.
+    Q (total_q, H, d), K / V (total_k, H, d), O like Q, L (H, total_q) with unit token stride; cu_q / cu_k int32 on the
+    device.  window = (left, right) raw sides (-1 unbounded) or None."""
+    total_q, H, d = Q.shape
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_varlen_variant(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, d, int(max_q), int(max_k), total_q, K.shape[0],
+            int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_q, cu_k, max_q, max_k, dtype_enum, causal=False, scale=1.0,
+                   window=None, variant=0):
+    """Launch the variable-length backward (include/fa2_bwd.h fa2_bwd_varlen_variant).  D: contiguous scratch of
+    2 * H * total_q float32 (float64 for fp64)."""
+    total_q, H, d = Q.shape
+    assert D.is_contiguous() and D.numel() == 2 * H * total_q
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_bwd_varlen_variant(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(),
+            dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), D.data_ptr(),
+            *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), L.stride(0),
+            cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, d, int(max_q), int(max_k), total_q, K.shape[0],
+            int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
     if rc != 0:
         _raise(rc)

@@ -376,7 +376,108 @@ int fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, co
 }
 }  // namespace
 
+namespace {
+// Variable-length (packed) attention, fa2_fwd_varlen: arguments checked before any launch; the varlen table is the windowed one.
+int fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3], const int64_t k_strides[3],
+               const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
+               const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k,
+               int32_t total_q, int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr,
+               void *hip_stream, int32_t variant) {
+    const void *ptrs[9] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides};
+    const char *names[9] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides"};
+    for (int t = 0; t < 9; ++t)
+        if (!ptrs[t]) {
+            fa2_set_error("varlen: null %s", names[t]);
+            return FA2_ERR_BAD_ARG;
+        }
+    if (!cu_seqlens_q || !cu_seqlens_k) {
+        fa2_set_error("varlen: null %s", !cu_seqlens_q ? "cu_seqlens_q" : "cu_seqlens_k");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (B < 1 || B > 65535) {
+        fa2_set_error("varlen: B (number of sequences) must be in [1, 65535] (got %d)", B);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (H < 1 || H > 65535) {
+        fa2_set_error("varlen: H must be in [1, 65535] (got %d)", H);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (max_seqlen_q < 0 || max_seqlen_k < 0 || max_seqlen_q > (1 << 28) || max_seqlen_k > (1 << 28)) {
+        fa2_set_error("varlen: max_seqlen_q and max_seqlen_k must be in [0, 2^28] (got %d, %d)", max_seqlen_q, max_seqlen_k);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (total_q < 0 || total_k < 0) {
+        fa2_set_error("varlen: total_q and total_k must be >= 0 (got %d, %d)", total_q, total_k);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (dtype_enum == FA2_DTYPE_F8E5M2 || dtype_enum == FA2_DTYPE_F8E4M3) {
+        fa2_set_error("varlen: fp8 is not supported (no backward; e4m3fn cannot hold L = +inf)");
+        return FA2_ERR_UNSUPPORTED;
+    }
+    const int64_t qs4[4] = {0, q_strides[1], q_strides[0], q_strides[2]}, ks4[4] = {0, k_strides[1], k_strides[0], k_strides[2]};
+    const int64_t vs4[4] = {0, v_strides[1], v_strides[0], v_strides[2]}, os4[4] = {0, o_strides[1], o_strides[0], o_strides[2]};
+    const int64_t ls2[2] = {0, l_head_stride};
+    const int32_t nmax = max_seqlen_q > max_seqlen_k ? max_seqlen_q : max_seqlen_k;
+    // N (only for validate() and the support predicates): the longest extent, at least 1
+    Fa2Problem p = make_problem(Q, K, V, O, L, qs4, ks4, vs4, os4, ls2, B, H, nmax > 0 ? nmax : 1, d, dtype_enum, causal, scale,
+                                hip_stream);
+    int rc = validate(p);
+    if (rc != FA2_OK) return rc;
+    if (l_head_stride < 0) {
+        fa2_set_error("varlen: negative L head stride");
+        return FA2_ERR_BAD_ARG;
+    }
+    p.wl = wl;
+    p.wr = wr;
+    p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
+    p.max_q = max_seqlen_q; p.max_k = max_seqlen_k; p.total_q = total_q; p.total_k = total_k;
+    if (variant == FA2_VARIANT_AUTO) {
+        const bool fits32 = (int64_t)(p.max_k + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.max_k + 512) * p.vs[2] * 2 < (1LL << 31);
+        // 4 waves: one 128-row tile per workgroup measured faster than the 8-wave form on every packed shape benchmarked
+        // (profiles/varlen/bench_varlen.jsonl; the varlen form has no causal tile pairs to fill a 256-row workgroup)
+        if (fa2_mfma16_supports(p) && fits32) {
+            variant = FA2_VARIANT_MFMA16D_W4;
+        } else {
+            variant = FA2_VARIANT_GENERIC;
+        }
+    }
+    switch (variant) {
+    case FA2_VARIANT_GENERIC: return fa2_launch_generic_varlen(p);
+    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_varlen(p, 8);
+    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_varlen(p, 4);
+    default:
+        fa2_set_error("kernel variant %d has no varlen form (generic, mfma16d and mfma16d_w4 do)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
+}  // namespace
+
 extern "C" {
+
+int fa2_fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                   const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride,
+                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
+                   int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fwd_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d,
+                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
+                      FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_varlen_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                           const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                           int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                           int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                           void *hip_stream, int32_t variant) {
+    return fwd_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d,
+                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
+                      variant);
+}
 
 int fa2_fwd(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
             const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],

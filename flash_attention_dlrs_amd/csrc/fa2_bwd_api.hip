@@ -113,6 +113,77 @@ int bwd_window(Fa2BwdProblem p, int32_t wl, int32_t wr, int variant) {
     return run_window(p, variant);
 }
 
+// Variable-length (packed) backward, fa2_bwd_varlen: arguments checked before any launch.
+int bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ, void *dK, void *dV,
+               void *D, const int64_t *const st3[8], int64_t l_head_stride, const int32_t *cu_q, const int32_t *cu_k, int32_t B,
+               int32_t H, int32_t d, int32_t max_q, int32_t max_k, int32_t total_q, int32_t total_k, int32_t dtype, int32_t causal,
+               float scale, int32_t wl, int32_t wr, void *stream, int variant) {
+    const char *snames[8] = {"q_strides", "k_strides", "v_strides", "o_strides", "do_strides", "dq_strides", "dk_strides", "dv_strides"};
+    for (int t = 0; t < 8; ++t)
+        if (!st3[t]) {
+            fa2_set_error("varlen backward: null %s", snames[t]);
+            return FA2_ERR_BAD_ARG;
+        }
+    if (!cu_q || !cu_k) {
+        fa2_set_error("varlen backward: null %s", !cu_q ? "cu_seqlens_q" : "cu_seqlens_k");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (B < 1 || B > 65535) {
+        fa2_set_error("varlen backward: B (number of sequences) must be in [1, 65535] (got %d)", B);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (H > 65535) {
+        fa2_set_error("varlen backward: H must be <= 65535 (got %d)", H);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (max_q < 0 || max_k < 0 || max_q > (1 << 28) || max_k > (1 << 28)) {
+        fa2_set_error("varlen backward: max_seqlen_q and max_seqlen_k must be in [0, 2^28] (got %d, %d)", max_q, max_k);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (total_q < 0 || total_k < 0) {
+        fa2_set_error("varlen backward: total_q and total_k must be >= 0 (got %d, %d)", total_q, total_k);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (l_head_stride < 0) {
+        fa2_set_error("varlen backward: negative L head stride");
+        return FA2_ERR_BAD_ARG;
+    }
+    const void *ptrs[10] = {Q, K, V, O, dO, L, dQ, dK, dV, D};
+    const char *names[10] = {"Q", "K", "V", "O", "dO", "L", "dQ", "dK", "dV", "D"};
+    for (int t = 0; t < 10; ++t)
+        if (!ptrs[t]) {
+            fa2_set_error("varlen backward: null %s", names[t]);
+            return FA2_ERR_BAD_ARG;
+        }
+    int64_t s4[8][4];
+    for (int t = 0; t < 8; ++t) {
+        s4[t][0] = 0; s4[t][1] = st3[t][1]; s4[t][2] = st3[t][0]; s4[t][3] = st3[t][2];
+    }
+    const int64_t ls2[2] = {0, l_head_stride};
+    const int32_t nmax = max_q > max_k ? max_q : max_k;
+    Fa2BwdProblem p = make(Q, K, V, O, dO, L, dQ, dK, dV, D, s4[0], s4[1], s4[2], s4[3], s4[4], s4[5], s4[6], s4[7], ls2, B, H,
+                           nmax > 0 ? nmax : 1, d, dtype, causal, scale, stream);
+    const int rc = validate(p);
+    if (rc != FA2_OK) return rc;
+    p.wl = wl;
+    p.wr = wr;
+    p.cu_q = cu_q; p.cu_k = cu_k;
+    p.max_q = max_q; p.max_k = max_k; p.total_q = total_q; p.total_k = total_k;
+    // (fa2_bwd_mfma16_supports judges the 32-bit offsets on N = the longer max_seqlen: they span one sequence)
+    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
+    switch (variant) {
+    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_varlen(p);
+    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_varlen(p);
+    default:
+        fa2_set_error("backward kernel variant %d has no varlen form (generic and mfma16 do)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -160,6 +231,32 @@ int fa2_bwd_window_variant(const void *Q, const void *K, const void *V, const vo
     return bwd_window(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
                            dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
                       window_left, window_right, variant);
+}
+
+int fa2_bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                   void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                   const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
+                   int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    const int64_t *const st[8] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
+    return bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, st, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q,
+                      max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
+                      FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_varlen_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                           void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                           const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                           const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                           int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                           int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                           void *hip_stream, int32_t variant) {
+    const int64_t *const st[8] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
+    return bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, st, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q,
+                      max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream, variant);
 }
 
 }  // extern "C"

@@ -14,12 +14,18 @@ struct Fa2BwdProblem {
     float scale;
     hipStream_t stream;
     int32_t wl, wr;  // local-attention window (fa2_bwd_window), normalised as in Fa2Problem
+    // Variable-length (packed) problems (fa2_bwd_varlen), as in Fa2Problem: strides {0, head, token, dim}, ls = {0, head stride of
+    // L}, raw window sides; D is the scratch of 2 * H * total_q accumulators ([2][H][total_q]).
+    const int32_t *cu_q, *cu_k;
+    int32_t max_q, max_k, total_q, total_k;
 };
 
 int fa2_bwd_launch_generic(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p);
 int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma16_window(const Fa2BwdProblem &p);
+int fa2_bwd_launch_generic_varlen(const Fa2BwdProblem &p);
+int fa2_bwd_launch_mfma16_varlen(const Fa2BwdProblem &p);
 bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma32(const Fa2BwdProblem &p);
 bool fa2_bwd_mfma32_supports(const Fa2BwdProblem &p);

@@ -23,7 +23,14 @@
 
 // FA2_BWD_GENERIC_WINDOW (fa2_bwd_generic_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr --
 // under its own kernel names, compiled in a translation unit of its own; without the macro this file is the plain kernels, unchanged.
-#ifdef FA2_BWD_GENERIC_WINDOW
+// FA2_BWD_GENERIC_VARLEN (fa2_bwd_generic_v.hip, on top of FA2_BWD_GENERIC_WINDOW): the variable-length form -- MODE 0 owns one
+// sequence's key block and sweeps only that sequence's queries, MODE 1 the reverse; per-sequence extents, bottom-right shifted band
+// (fa2_varlen_band).  D and the row statistic are laid out [H][total_q].  A row without a visible key (L = +inf) has P = 0: its dQ
+// is 0 and its statistic stays +inf (not inf + log2(0)).
+#if defined(FA2_BWD_GENERIC_VARLEN)
+#define bwd_main_kernel bwd_main_varlen_kernel
+#define bwd_D_kernel bwd_D_varlen_kernel
+#elif defined(FA2_BWD_GENERIC_WINDOW)
 #define bwd_main_kernel bwd_main_window_kernel
 #define bwd_D_kernel bwd_D_window_kernel
 #endif
@@ -41,7 +48,12 @@ struct GArgs {
     const void *Q, *K, *V, *O, *dO, *L;
     void *dQ, *dK, *dV, *D;
     int64_t qs[4], ks[4], vs[4], os[4], dos[4], dqs[4], dks[4], dvs[4], ls[2];
-#ifdef FA2_BWD_GENERIC_WINDOW
+#if defined(FA2_BWD_GENERIC_VARLEN)
+    int H, N, d, causal, TB;
+    int wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
+    const int32_t *cu_q, *cu_k;
+    int max_q, max_k, total_q, total_k;
+#elif defined(FA2_BWD_GENERIC_WINDOW)
     int H, N, d, causal, TB;
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
 #else
@@ -55,10 +67,16 @@ template <typename E> __global__ __launch_bounds__(256) void bwd_D_kernel(const 
     using A = typename E::acc_t;
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
+#ifdef FA2_BWD_GENERIC_VARLEN
+    // D[h][token], every packed token (rows = H * total_q)
+    const int n = (int)(r % a.total_q), h = (int)(r / a.total_q);
+    const int64_t o0 = h * a.os[1] + (int64_t)n * a.os[2], g0 = h * a.dos[1] + (int64_t)n * a.dos[2];
+#else
     const int n = (int)(r % a.N);
     const long long bh = r / a.N;
     const int h = (int)(bh % a.H), b = (int)(bh / a.H);
     const int64_t o0 = b * a.os[0] + h * a.os[1] + n * a.os[2], g0 = b * a.dos[0] + h * a.dos[1] + n * a.dos[2];
+#endif
     A s = 0;
     for (int x = 0; x < a.d; ++x) s += E::load(a.O, o0 + x * a.os[3]) * E::load(a.dO, g0 + x * a.dos[3]);
     ((A *)a.D)[r] = s;
@@ -68,7 +86,11 @@ template <typename E> __global__ __launch_bounds__(256) void bwd_D_kernel(const 
 template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_kernel(const GArgs a) {
     using A = typename E::acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+#ifdef FA2_BWD_GENERIC_VARLEN
+    const int TB = a.TB, d = a.d, ld = d + 1, tid = threadIdx.x;
+#else
     const int TB = a.TB, d = a.d, ld = d + 1, N = a.N, tid = threadIdx.x;
+#endif
     A *own0 = (A *)smem_raw;        // owner rows, first operand  (MODE 0: K_j ; MODE 1: Q_i)
     A *own1 = own0 + TB * ld;       //             second operand (MODE 0: V_j ; MODE 1: dO_i)
     A *swp0 = own1 + TB * ld;       // swept rows                 (MODE 0: Q_i ; MODE 1: K_j)
@@ -82,6 +104,20 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
     A *Rs = Dq + TB;                // MODE 1: rowsum(P) of the owned query rows (see Lc below)
 
     const int b = blockIdx.y, h = blockIdx.z, blk = blockIdx.x;
+#ifdef FA2_BWD_GENERIC_VARLEN
+    // NQ queries and NK keys of sequence b; NO = the owned extent, NS = the swept one
+    int qst, NQ, kst, NK;
+    fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, qst, NQ);
+    fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
+    const int NO = MODE == 0 ? NK : NQ, NS = MODE == 0 ? NQ : NK;
+    if (blk * TB >= NO) return;  // (whole workgroup, before any barrier)
+    const int64_t qb = (int64_t)qst * a.qs[2] + h * a.qs[1], kb = (int64_t)kst * a.ks[2] + h * a.ks[1];
+    const int64_t vb = (int64_t)kst * a.vs[2] + h * a.vs[1];
+    const int64_t gb = (int64_t)qst * a.dos[2] + h * a.dos[1];
+    const int64_t lb = h * a.ls[1] + qst;
+    const long long db = (long long)h * a.total_q + qst;
+    A *Lc = (A *)a.D + (long long)a.H * a.total_q + db;
+#else
     const int64_t qb = b * a.qs[0] + h * a.qs[1], kb = b * a.ks[0] + h * a.ks[1], vb = b * a.vs[0] + h * a.vs[1];
     const int64_t gb = b * a.dos[0] + h * a.dos[1];
     const int64_t lb = b * a.ls[0] + h * a.ls[1];
@@ -90,8 +126,31 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
     // L in the I/O dtype (kernels.py:108); its rounding scales a whole row of P (bf16: by up to 2^0.125).  The
     // query-owner kernel sees full rows, measures rowsum(P) = 2^(L_true - L_stored) and hands L + log2(rowsum) on.
     A *Lc = (A *)a.D + (long long)gridDim.y * a.H * N + db;
+#endif
     const A c_s = (A)a.c_log2e, scale = (A)a.scale;
 
+#ifdef FA2_BWD_GENERIC_VARLEN
+    auto load_rows = [&](A *dst, const void *src, int64_t base, const int64_t *st, int row0, int n) {
+        for (int e = tid; e < TB * d; e += 256) {
+            const int r = e / d, x = e % d, row = row0 + r;
+            dst[r * ld + x] = row < n ? E::load(src, base + (int64_t)row * st[2] + x * st[3]) : (A)0;
+        }
+    };
+    const int own_row0 = blk * TB;
+    if (MODE == 0) {
+        load_rows(own0, a.K, kb, a.ks, own_row0, NO);
+        load_rows(own1, a.V, vb, a.vs, own_row0, NO);
+    } else {
+        load_rows(own0, a.Q, qb, a.qs, own_row0, NO);
+        load_rows(own1, a.dO, gb, a.dos, own_row0, NO);
+        if (tid < TB) {
+            const int row = own_row0 + tid;
+            Lq[tid] = row < NO ? E::load(a.L, lb + row) : (A)0;
+            Dq[tid] = row < NO ? ((const A *)a.D)[db + row] : (A)0;
+            Rs[tid] = (A)0;
+        }
+    }
+#else
     auto load_rows = [&](A *dst, const void *src, int64_t base, const int64_t *st, int row0) {
         for (int e = tid; e < TB * d; e += 256) {
             const int r = e / d, x = e % d, row = row0 + r;
@@ -112,12 +171,19 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
             Rs[tid] = (A)0;
         }
     }
+#endif
     for (int e = tid; e < TB * ld; e += 256) acc0[e] = acc1[e] = (A)0;
     __syncthreads();
 
+#if defined(FA2_BWD_GENERIC_VARLEN)
+    // the sequence's band: a key block meets queries [j0 - wr, j1 + wl], a query block keys [i0 - wl, i1 + wr]
+    int wl, wr;
+    fa2_varlen_band(NQ, NK, a.causal, a.wl, a.wr, wl, wr);
+    const int sw_lo = own_row0 - (MODE == 0 ? wr : wl), sw_hi = own_row0 + TB - 1 + (MODE == 0 ? wl : wr);
+    const int sw_begin = (sw_lo > 0 ? sw_lo : 0) / TB;
+    const int sw_end = (NS == 0 || sw_hi < 0) ? 0 : (sw_hi < NS - 1 ? sw_hi : NS - 1) / TB + 1;  // (no swept row: nothing)
+#elif defined(FA2_BWD_GENERIC_WINDOW)
     const int nsw = (N + TB - 1) / TB;
-    // causal: a key block only meets query rows >= its first key; a query block only keys <= its last row
-#ifdef FA2_BWD_GENERIC_WINDOW
     // window: a key block meets queries [j0 - wr, j1 + wl], a query block keys [i0 - wl, i1 + wr]
     const int wl = a.wl, wr = a.wr;
     const int sw_lo = own_row0 - (MODE == 0 ? wr : wl), sw_hi = own_row0 + TB - 1 + (MODE == 0 ? wl : wr);
@@ -125,11 +191,27 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
     const int sw_end = (sw_hi < N - 1 ? sw_hi : N - 1) / TB + 1;
     (void)nsw;
 #else
+    const int nsw = (N + TB - 1) / TB;
+    // causal: a key block only meets query rows >= its first key; a query block only keys <= its last row
     const int sw_begin = (MODE == 0 && a.causal) ? own_row0 / TB : 0;
     const int sw_end = (MODE == 1 && a.causal) ? ((own_row0 + TB - 1 < N ? own_row0 + TB - 1 : N - 1) / TB + 1) : nsw;
 #endif
     for (int sw = sw_begin; sw < sw_end; ++sw) {
         const int sw_row0 = sw * TB;
+#ifdef FA2_BWD_GENERIC_VARLEN
+        if (MODE == 0) {
+            load_rows(swp0, a.Q, qb, a.qs, sw_row0, NS);
+            load_rows(swp1, a.dO, gb, a.dos, sw_row0, NS);
+            if (tid < TB) {
+                const int row = sw_row0 + tid;
+                Lq[tid] = row < NS ? Lc[row] : (A)0;
+                Dq[tid] = row < NS ? ((const A *)a.D)[db + row] : (A)0;
+            }
+        } else {
+            load_rows(swp0, a.K, kb, a.ks, sw_row0, NS);
+            load_rows(swp1, a.V, vb, a.vs, sw_row0, NS);
+        }
+#else
         if (MODE == 0) {
             load_rows(swp0, a.Q, qb, a.qs, sw_row0);
             load_rows(swp1, a.dO, gb, a.dos, sw_row0);
@@ -142,6 +224,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
             load_rows(swp0, a.K, kb, a.ks, sw_row0);
             load_rows(swp1, a.V, vb, a.vs, sw_row0);
         }
+#endif
         __syncthreads();
         if (tid < TB * TB) {  // one (query r, key c) pair per thread
             const int r = tid / TB, c = tid % TB;
@@ -154,7 +237,9 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
                 dp += grow[x] * vrow[x];  // :289
             }
             A p = exp2_a<A>(s * c_s - Lq[r]);  // :285
-#ifdef FA2_BWD_GENERIC_WINDOW
+#if defined(FA2_BWD_GENERIC_VARLEN)
+            if (qi >= NQ || kj >= NK || kj < qi - wl || kj > qi + wr) p = 0;
+#elif defined(FA2_BWD_GENERIC_WINDOW)
             if (qi >= N || kj >= N || kj < qi - wl || kj > qi + wr) p = 0;
 #else
             if (qi >= N || kj >= N || (a.causal && kj > qi)) p = 0;
@@ -186,6 +271,21 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         }
         __syncthreads();
     }
+#ifdef FA2_BWD_GENERIC_VARLEN
+    for (int e = tid; e < TB * d; e += 256) {
+        const int o = e / d, x = e % d, row = own_row0 + o;
+        if (row >= NO) continue;
+        if (MODE == 0) {
+            E::store(a.dK, h * a.dks[1] + (int64_t)(kst + row) * a.dks[2] + x * a.dks[3], acc0[o * ld + x]);
+            E::store(a.dV, h * a.dvs[1] + (int64_t)(kst + row) * a.dvs[2] + x * a.dvs[3], acc1[o * ld + x]);
+        } else {  // (a row without a visible key: rowsum 0, dQ 0)
+            E::store(a.dQ, h * a.dqs[1] + (int64_t)(qst + row) * a.dqs[2] + x * a.dqs[3],
+                     Rs[o] > 0 ? acc0[o * ld + x] / Rs[o] : (A)0);
+        }
+    }
+    // L = +inf and rowsum 0 would give inf + -inf: such a row keeps +inf, and MODE 0 recomputes P = 0 for it
+    if (MODE == 1 && tid < TB && own_row0 + tid < NO) Lc[own_row0 + tid] = Rs[tid] > 0 ? Lq[tid] + log2_a<A>(Rs[tid]) : (A)INFINITY;
+#else
     for (int e = tid; e < TB * d; e += 256) {
         const int o = e / d, x = e % d, row = own_row0 + o;
         if (row >= N) continue;
@@ -197,6 +297,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         }
     }
     if (MODE == 1 && tid < TB && own_row0 + tid < N) Lc[own_row0 + tid] = Lq[tid] + log2_a<A>(Rs[tid]);
+#endif
 }
 
 template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
@@ -206,9 +307,19 @@ template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
     while (TB > 1 && need(TB) > 60 * 1024) TB >>= 1;
     a.TB = TB;
     const size_t smem = need(TB);
+#ifdef FA2_BWD_GENERIC_VARLEN
+    // one grid for both modes: blocks past a sequence's owned extent leave at once
+    const long long rows = (long long)p.H * p.total_q;
+    if (rows > 0)
+        hipLaunchKernelGGL((bwd_D_kernel<E>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, p.stream, a, rows);
+    const int gx = ((p.max_q > p.max_k ? p.max_q : p.max_k) + TB - 1) / TB;
+    if (gx == 0) return FA2_OK;
+    const dim3 grid(gx, p.B, p.H);
+#else
     const long long rows = (long long)p.B * p.H * p.N;
     hipLaunchKernelGGL((bwd_D_kernel<E>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, p.stream, a, rows);
     const dim3 grid((p.N + TB - 1) / TB, p.B, p.H);
+#endif
     hipLaunchKernelGGL((bwd_main_kernel<E, 1>), grid, dim3(256), smem, p.stream, a);  // first: leaves Lc for MODE 0
     hipLaunchKernelGGL((bwd_main_kernel<E, 0>), grid, dim3(256), smem, p.stream, a);
     const hipError_t e = hipGetLastError();
@@ -221,7 +332,9 @@ template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
 
 }  // namespace
 
-#ifdef FA2_BWD_GENERIC_WINDOW
+#if defined(FA2_BWD_GENERIC_VARLEN)
+int fa2_bwd_launch_generic_varlen(const Fa2BwdProblem &p) {
+#elif defined(FA2_BWD_GENERIC_WINDOW)
 int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p) {
 #else
 int fa2_bwd_launch_generic(const Fa2BwdProblem &p) {
@@ -238,7 +351,10 @@ int fa2_bwd_launch_generic(const Fa2BwdProblem &p) {
         a.dqs[k] = p.dqs[k]; a.dks[k] = p.dks[k]; a.dvs[k] = p.dvs[k];
     }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
-#ifdef FA2_BWD_GENERIC_WINDOW
+#if defined(FA2_BWD_GENERIC_VARLEN)
+    a.H = p.H; a.N = p.N; a.d = p.d; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
+    a.cu_q = p.cu_q; a.cu_k = p.cu_k; a.max_q = p.max_q; a.max_k = p.max_k; a.total_q = p.total_q; a.total_k = p.total_k;
+#elif defined(FA2_BWD_GENERIC_WINDOW)
     a.H = p.H; a.N = p.N; a.d = p.d; a.causal = 0; a.wl = p.wl; a.wr = p.wr;
 #else
     a.H = p.H; a.N = p.N; a.d = p.d; a.causal = p.causal;

@@ -31,7 +31,15 @@
 // FA2_BWD_MFMA16_WINDOW (fa2_bwd_mfma16_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr; the
 // swept ranges, block skips and masks follow the two band edges -- under its own kernel names, compiled in a translation unit of
 // its own; without the macro this file is the plain kernels, unchanged.
-#ifdef FA2_BWD_MFMA16_WINDOW
+// FA2_BWD_MFMA16_VARLEN (fa2_bwd_mfma16_v.hip, on top of FA2_BWD_MFMA16_WINDOW): the variable-length form -- a workgroup owns
+// one block of ONE sequence (MODE 0: its keys, MODE 1: its queries) and sweeps only that sequence's other side, with the owned
+// extent NO, the swept extent NS and the bottom-right shifted band (fa2_varlen_band); base pointers in 64 bits from the
+// sequence starts, D and the row statistic laid out [H][total_q].  A query without a visible key (L = +inf) keeps the row
+// statistic +inf and gets dQ = 0.
+#if defined(FA2_BWD_MFMA16_VARLEN)
+#define bwd_mfma16_kernel bwd_mfma16_varlen_kernel
+#define bwd_D_kernel bwd_D_varlen_kernel
+#elif defined(FA2_BWD_MFMA16_WINDOW)
 #define bwd_mfma16_kernel bwd_mfma16_window_kernel
 #define bwd_D_kernel bwd_D_window_kernel
 #endif
@@ -75,7 +83,13 @@ struct BArgs {
     float *D;
     int64_t qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];  // B, H, N strides in BYTES
     int64_t ls[2];                                                        // elements
-#ifdef FA2_BWD_MFMA16_WINDOW
+#if defined(FA2_BWD_MFMA16_VARLEN)
+    int B, H, N, causal;
+    int wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
+    int vcausal;  // the causal flag of the band (bit 0 of `causal` stays 0: no reversed block order)
+    const int32_t *cu_q, *cu_k;
+    int max_q, max_k, total_q, total_k;
+#elif defined(FA2_BWD_MFMA16_WINDOW)
     int B, H, N, causal;
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
 #else
@@ -112,6 +126,17 @@ __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" :
 template <typename T, int D> __global__ __launch_bounds__(256) void bwd_D_kernel(const BArgs a) {
     constexpr int LPR = D / 8;  // lanes per row
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+#ifdef FA2_BWD_MFMA16_VARLEN
+    // D[h][token], every packed token (rows = H * total_q)
+    const long long r = gid / LPR, rows = (long long)a.H * a.total_q;
+    const int ch = (int)(gid % LPR);
+    float s = 0.0f;
+    if (r < rows) {
+        const int n = (int)(r % a.total_q), h = (int)(r / a.total_q);
+        typedef __attribute__((ext_vector_type(8))) T Tx8;
+        const Tx8 o = *(const Tx8 *)(a.O + h * a.os[1] + (int64_t)n * a.os[2] + ch * 16);
+        const Tx8 g = *(const Tx8 *)(a.dO + h * a.dos[1] + (int64_t)n * a.dos[2] + ch * 16);
+#else
     const long long r = gid / LPR, rows = (long long)a.B * a.H * a.N;
     const int ch = (int)(gid % LPR);
     float s = 0.0f;
@@ -122,6 +147,7 @@ template <typename T, int D> __global__ __launch_bounds__(256) void bwd_D_kernel
         typedef __attribute__((ext_vector_type(8))) T Tx8;
         const Tx8 o = *(const Tx8 *)(a.O + b * a.os[0] + h * a.os[1] + (int64_t)n * a.os[2] + ch * 16);
         const Tx8 g = *(const Tx8 *)(a.dO + b * a.dos[0] + h * a.dos[1] + (int64_t)n * a.dos[2] + ch * 16);
+#endif
 #pragma unroll
         for (int j = 0; j < 8; ++j) s += (float)o[j] * (float)g[j];
     }
@@ -145,9 +171,16 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: every block / mask decision
                                                                 // below is then a scalar branch, not an EXEC mask
-#ifdef FA2_BWD_MFMA16_WINDOW
+#if defined(FA2_BWD_MFMA16_VARLEN)
+    const int i = lane & 31, h = lane >> 5;
+    const int N = MODE == 0 ? a.max_k : a.max_q;  // (only the block count: the sequence's own extents are NO and NS)
+    int qst = 0, NQ = 0, kst = 0, NK = 0, NO = 0, NS = 0, wl = 0, wr = 0;  // set once the sequence is known
+    auto band_none = [&](int q0, int q1, int k0, int k1) { return k0 > q1 + wr || k1 < q0 - wl; };
+    auto band_all = [&](int q0, int q1, int k0, int k1) { return k0 >= q1 - wl && k1 <= q0 + wr; };
+#elif defined(FA2_BWD_MFMA16_WINDOW)
     const int i = lane & 31, h = lane >> 5;
     const int N = a.N;
+    const int NO = N, NS = N;
     const int wl = a.wl, wr = a.wr;
     // (query rows [q0, q1], keys [k0, k1]): no pair inside the band / every pair inside it
     auto band_none = [&](int q0, int q1, int k0, int k1) { return k0 > q1 + wr || k1 < q0 - wl; };
@@ -172,6 +205,18 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     }
     if (MODE == 1 && (a.causal & 1)) blk = nblk - 1 - blk;  // causal: the last query blocks sweep the most keys -- start them first
     const int b = bh / a.H, hh = bh - b * a.H;
+#ifdef FA2_BWD_MFMA16_VARLEN
+    fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, qst, NQ);
+    fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
+    qst = __builtin_amdgcn_readfirstlane(qst);
+    NQ = __builtin_amdgcn_readfirstlane(NQ);
+    kst = __builtin_amdgcn_readfirstlane(kst);
+    NK = __builtin_amdgcn_readfirstlane(NK);
+    NO = MODE == 0 ? NK : NQ;
+    NS = MODE == 0 ? NQ : NK;
+    if (blk * BO >= NO) return;  // (whole workgroup, before any barrier)
+    fa2_varlen_band(NQ, NK, a.vcausal, a.wl, a.wr, wl, wr);
+#endif
     const bool roleV = MODE == 0 && wave >= 4;   // MODE 0: waves 4..7 accumulate dV^T, waves 0..3 dK^T
     // The dV waves carry the exp2 work and are the second-dispatched half, which loses every issue arbitration to the
     // older half: in-kernel stamps showed them at 2 900 busy cycles per block step against 1 950 for the dK waves, which
@@ -181,6 +226,17 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     const int orow = own0 + i;              // this lane's owned row (query in MODE 1, key in MODE 0)
 
     // swept tiles T0, T1 and owned fragments f0, f1
+#ifdef FA2_BWD_MFMA16_VARLEN
+    const char *Qs = a.Q + (int64_t)qst * a.qs[2] + hh * a.qs[1], *dOs = a.dO + (int64_t)qst * a.dos[2] + hh * a.dos[1];
+    const char *Ks = a.K + (int64_t)kst * a.ks[2] + hh * a.ks[1], *Vs = a.V + (int64_t)kst * a.vs[2] + hh * a.vs[1];
+    const char *T0p = MODE == 1 ? Ks : Qs, *T1p = MODE == 1 ? Vs : dOs;
+    const int64_t t0rs = MODE == 1 ? a.ks[2] : a.qs[2], t1rs = MODE == 1 ? a.vs[2] : a.dos[2];
+    const char *F0p = MODE == 1 ? Qs : Ks, *F1p = MODE == 1 ? dOs : Vs;
+    const int64_t f0rs = MODE == 1 ? a.qs[2] : a.ks[2], f1rs = MODE == 1 ? a.dos[2] : a.vs[2];
+    const T *Lp = (const T *)a.L + hh * a.ls[1] + qst;
+    const float *Dp = a.D + (int64_t)hh * a.total_q + qst;
+    float *Lc = a.D + (int64_t)a.H * a.total_q + (int64_t)hh * a.total_q + qst;
+#else
     const char *T0p = (MODE == 1 ? a.K + b * a.ks[0] + hh * a.ks[1] : a.Q + b * a.qs[0] + hh * a.qs[1]);
     const char *T1p = (MODE == 1 ? a.V + b * a.vs[0] + hh * a.vs[1] : a.dO + b * a.dos[0] + hh * a.dos[1]);
     const int64_t t0rs = MODE == 1 ? a.ks[2] : a.qs[2], t1rs = MODE == 1 ? a.vs[2] : a.dos[2];
@@ -189,15 +245,22 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     const int64_t f0rs = MODE == 1 ? a.qs[2] : a.ks[2], f1rs = MODE == 1 ? a.dos[2] : a.vs[2];
     const T *Lp = (const T *)a.L + b * a.ls[0] + hh * a.ls[1];
     const float *Dp = a.D + ((int64_t)b * a.H + hh) * N;
+#endif
     // fp32 row statistic written by the MODE 1 launch (which runs first) and read by MODE 0: the forward stores L in
     // the I/O dtype (kernels.py:108), whose rounding (bf16: +-0.125 at |L| ~ 50) would scale a whole row of P by up to
     // 2^0.125; the query-owner kernel sees the full row, measures rowsum(P) = 2^(L_true - L_stored) and hands
     // L_stored + log2(rowsum) on, so both kernels work with P normalised to fp32 accuracy.
+#ifndef FA2_BWD_MFMA16_VARLEN
     float *Lc = a.D + (int64_t)a.B * a.H * N + ((int64_t)b * a.H + hh) * N;
+#endif
 
     frag f0[KS], f1[KS];
     {
+#ifdef FA2_BWD_MFMA16_WINDOW
+        const int row = orow < NO ? orow : NO - 1;
+#else
         const int row = orow < N ? orow : N - 1;
+#endif
         const char *p0 = F0p + (int64_t)row * f0rs + h * 16, *p1 = F1p + (int64_t)row * f1rs + h * 16;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -208,7 +271,11 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     // per-lane row constants (MODE 1: the owned query's L and D)
     float Lown = 0.0f, Down = 0.0f;
     if (MODE == 1) {
+#ifdef FA2_BWD_MFMA16_WINDOW
+        const int row = orow < NO ? orow : NO - 1;
+#else
         const int row = orow < N ? orow : N - 1;
+#endif
         Lown = (float)Lp[row];
         Down = Dp[row];
     }
@@ -236,7 +303,13 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         r[3] = 0x00020000;
         return r;
     };
+#if defined(FA2_BWD_MFMA16_VARLEN)
+    // (NS = 0: an empty range -- every load reads 0, and nothing is swept)
+    const i32x4 rs0 = make_rsrc(T0p, NS > 0 ? (NS - 1) * (int)t0rs + ROWB : 0);
+    const i32x4 rs1 = make_rsrc(T1p, NS > 0 ? (NS - 1) * (int)t1rs + ROWB : 0);
+#else
     const i32x4 rs0 = make_rsrc(T0p, (N - 1) * (int)t0rs + ROWB), rs1 = make_rsrc(T1p, (N - 1) * (int)t1rs + ROWB);
+#endif
     const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
     int so0[PPW], so1[PPW];
 #pragma unroll
@@ -249,7 +322,11 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     // MODE 0: the row statistics L and D of the 64 swept query rows travel by LDS-DMA too (two 256-byte pieces issued by
     // wave 0; rows past N read as 0 and are masked like every other out-of-range row) -- staged through registers they
     // cost wave 0 a global-load wait of ~480 cycles per tile (in-kernel stamps)
+#if defined(FA2_BWD_MFMA16_VARLEN)
+    const i32x4 rsL = make_rsrc((const char *)Lc, NS * 4), rsD = make_rsrc((const char *)Dp, NS * 4);  // (MODE 0: NS = NQ)
+#else
     const i32x4 rsL = make_rsrc((const char *)Lc, N * 4), rsD = make_rsrc((const char *)Dp, N * 4);
+#endif
     auto stage_load = [&](int t) {  // the target buffer t & 1 must be free when this is called
         const int buf = t & 1;
 #pragma unroll
@@ -289,7 +366,11 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     {  // MODE 1 sweeps the keys [i0 - wl, i1 + wr], MODE 0 the queries [j0 - wr, j1 + wl]
         const int lo = wg0 - (MODE == 1 ? wl : wr), hi = wg0 + BO - 1 + (MODE == 1 ? wr : wl);
         t_begin = (lo > 0 ? lo : 0) / BS;
+#ifdef FA2_BWD_MFMA16_VARLEN
+        t_end = (NS == 0 || hi < 0) ? 0 : (hi < NS - 1 ? hi : NS - 1) / BS + 1;  // (nothing to sweep: no swept row, or all before 0)
+#else
         t_end = (hi < N - 1 ? hi : N - 1) / BS + 1;
+#endif
         (void)is_causal;
     }
 #else
@@ -324,7 +405,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         const int kg = wave & 3;
 #ifdef FA2_BWD_MFMA16_WINDOW
         auto blk_skip = [&](int bidx) { return band_none(bidx * 32, bidx * 32 + 31, own0, own0 + 31); };
-        auto blk_masked = [&](int bidx) { return (bidx * 32 + 32 > N) || !band_all(bidx * 32, bidx * 32 + 31, own0, own0 + 31); };
+        auto blk_masked = [&](int bidx) { return (bidx * 32 + 32 > NS) || !band_all(bidx * 32, bidx * 32 + 31, own0, own0 + 31); };
 #else
         auto blk_skip = [&](int bidx) {  // causal: all 32 queries of the block precede all 32 keys of the wave
             return is_causal && bidx * 32 + 31 < own0;
@@ -361,7 +442,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                                 if (decltype(masked_)::value) {
                                     const int qry = srow0 + 8 * g + 4 * h + j;
 #ifdef FA2_BWD_MFMA16_WINDOW
-                                    if (qry >= N || orow < qry - wl || orow > qry + wr) pe = 0.0f;
+                                    if (qry >= NS || orow < qry - wl || orow > qry + wr) pe = 0.0f;
 #else
                                     if (qry >= N || (is_causal && orow > qry)) pe = 0.0f;
 #endif
@@ -457,7 +538,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                 const int srow0 = t * BS + kb * 32;  // first swept row of this 32-row block
                 // swept row of register r: srow0 + (r & 3) + 8 (r >> 2) + 4 h
 #ifdef FA2_BWD_MFMA16_WINDOW
-                const bool need_mask = (srow0 + 32 > N) || (MODE == 1 ? !band_all(own0, own0 + 31, srow0, srow0 + 31)
+                const bool need_mask = (srow0 + 32 > NS) || (MODE == 1 ? !band_all(own0, own0 + 31, srow0, srow0 + 31)
                                                                       : !band_all(srow0, srow0 + 31, own0, own0 + 31));
 #else
                 const bool need_mask = (srow0 + 32 > N) || (is_causal && (MODE == 1 ? srow0 + 31 > own0 : srow0 < own0 + 31));
@@ -475,7 +556,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                                 const int srow = srow0 + 8 * g + 4 * h + j;
                                 const int key = MODE == 1 ? srow : orow, qry = MODE == 1 ? orow : srow;
 #ifdef FA2_BWD_MFMA16_WINDOW
-                                if (srow >= N || key < qry - wl || key > qry + wr) p = 0.0f;
+                                if (srow >= NS || key < qry - wl || key > qry + wr) p = 0.0f;
 #else
                                 if (srow >= N || (is_causal && key > qry)) p = 0.0f;
 #endif
@@ -551,9 +632,15 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         const unsigned s0 = sw[0], s1 = sw[1];
         tot = __builtin_bit_cast(float, s0) + __builtin_bit_cast(float, s1);
     }
+#ifdef FA2_BWD_MFMA16_VARLEN
+    if (orow < NO) {
+        auto store_rows = [&](char *base, const int64_t *st, f32x16 (&acc)[DB], float mul) {
+            char *op = base + (int64_t)(MODE == 1 ? qst : kst) * st[2] + hh * st[1] + (int64_t)orow * st[2] + h * 8;
+#else
     if (orow < N) {
         auto store_rows = [&](char *base, const int64_t *st, f32x16 (&acc)[DB], float mul) {
             char *op = base + b * st[0] + hh * st[1] + (int64_t)orow * st[2] + h * 8;
+#endif
 #pragma unroll
             for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -566,8 +653,14 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                 }
         };
         if (MODE == 1) {
+#ifdef FA2_BWD_MFMA16_VARLEN
+            // a query without a visible key: rowsum 0, dQ 0, and the statistic stays +inf (not inf + log2(0))
+            store_rows(a.dQ, a.dqs, acc0, tot > 0.0f ? a.scale / tot : 0.0f);
+            if (h == 0) Lc[orow] = tot > 0.0f ? Lown + __builtin_amdgcn_logf(tot) : INFINITY;
+#else
             store_rows(a.dQ, a.dqs, acc0, a.scale / tot);
             if (h == 0) Lc[orow] = Lown + __builtin_amdgcn_logf(tot);
+#endif
         } else if (!roleV) {
             store_rows(a.dK, a.dks, acc0, a.scale);
         } else {
@@ -577,6 +670,25 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
 }
 
 template <typename T, int D> int launch_d(const Fa2BwdProblem &p, const BArgs &a) {
+#ifdef FA2_BWD_MFMA16_VARLEN
+    // D over every packed token; each mode's grid from its own owned extent (MODE 1: max_q, MODE 0: max_k)
+    const long long lanes = (long long)p.H * p.total_q * (D / 8);
+    if (lanes > 0) hipLaunchKernelGGL((bwd_D_kernel<T, D>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, p.stream, a);
+    const long long nblkq = (long long)((p.max_q + 127) / 128) * p.B * p.H, nblk = (long long)((p.max_k + 127) / 128) * p.B * p.H;
+    if (nblkq > 0x7fffffffLL || nblk > 0x7fffffffLL) {
+        fa2_set_error("backward mfma16: grid too large");
+        return FA2_ERR_BAD_ARG;
+    }
+    constexpr size_t smem0 = 4 * 64 * D * 2 + 4 * 64 * 4 + 4 * 2 * 4096, smem1 = 4 * 64 * D * 2;
+    if (nblkq > 0)  // first: it leaves the fp32 row statistic the key-owner launch reads
+        hipLaunchKernelGGL((bwd_mfma16_kernel<T, D, 1, 4>), dim3((unsigned)nblkq), dim3(256), smem1, p.stream, a);
+    static Fa2DeviceLatch attr_set;
+    if (attr_set.need()) {
+        (void)hipFuncSetAttribute((const void *)bwd_mfma16_kernel<T, D, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem0);
+        attr_set.mark();
+    }
+    if (nblk > 0) hipLaunchKernelGGL((bwd_mfma16_kernel<T, D, 0>), dim3((unsigned)nblk), dim3(512), smem0, p.stream, a);
+#else
     const long long rows = (long long)p.B * p.H * p.N, lanes = rows * (D / 8);
     hipLaunchKernelGGL((bwd_D_kernel<T, D>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, p.stream, a);
     const long long nblk = (long long)((p.N + 127) / 128) * p.B * p.H;
@@ -598,6 +710,7 @@ template <typename T, int D> int launch_d(const Fa2BwdProblem &p, const BArgs &a
         attr_set.mark();
     }
     hipLaunchKernelGGL((bwd_mfma16_kernel<T, D, 0>), dim3((unsigned)nblk), dim3(512), smem0, p.stream, a);
+#endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("backward mfma16 launch failed: %s", hipGetErrorString(e));
@@ -634,7 +747,9 @@ bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p) {
 }
 
 #endif
-#ifdef FA2_BWD_MFMA16_WINDOW
+#if defined(FA2_BWD_MFMA16_VARLEN)
+int fa2_bwd_launch_mfma16_varlen(const Fa2BwdProblem &p) {
+#elif defined(FA2_BWD_MFMA16_WINDOW)
 int fa2_bwd_launch_mfma16_window(const Fa2BwdProblem &p) {
 #else
 int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p) {
@@ -655,7 +770,14 @@ int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p) {
     a.B = p.B; a.H = p.H; a.N = p.N;
     a.causal = (p.causal ? 1 : 0) | (fa2_env_int("FA2_BWD_PRIO", 1) ? 2 : 0);  // bit 1: static priority for the dV waves
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
-#ifdef FA2_BWD_MFMA16_WINDOW
+#if defined(FA2_BWD_MFMA16_VARLEN)
+    a.scale = p.scale;
+    a.wl = p.wl;
+    a.wr = p.wr;
+    a.causal &= 2;  // the mask is in the band; bit 0 would reverse the query-block order over max_q
+    a.vcausal = p.causal ? 1 : 0;
+    a.cu_q = p.cu_q; a.cu_k = p.cu_k; a.max_q = p.max_q; a.max_k = p.max_k; a.total_q = p.total_q; a.total_k = p.total_k;
+#elif defined(FA2_BWD_MFMA16_WINDOW)
     a.scale = p.scale;
     a.wl = p.wl;
     a.wr = p.wr;

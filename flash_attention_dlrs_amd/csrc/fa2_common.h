@@ -16,6 +16,10 @@ struct Fa2Problem {
     float scale;
     hipStream_t stream;
     int32_t wl, wr;  // local-attention window after fa2_window_normalise(): sides in [0, N-1], N-1 = unbounded (window launchers only)
+    // Variable-length (packed) problems (fa2_fwd_varlen, varlen launchers only): B sequences, strides {0, head, token, dim} in
+    // qs/ks/vs/os, ls = {0, head stride of L}; wl / wr are the raw sides (-1 = unbounded), causal as given.
+    const int32_t *cu_q, *cu_k;
+    int32_t max_q, max_k, total_q, total_k;
 };
 
 // Launchers, one per translation unit.  Return FA2_OK / FA2_ERR_*; set_error() on failure.
@@ -38,6 +42,9 @@ int fa2_launch_mfma16h_noncausal(const Fa2Problem &p, int waves);
 // Local attention (fa2_fwd_window): the windowed instantiations live in translation units of their own.
 int fa2_launch_generic_window(const Fa2Problem &p);
 int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves);
+// Variable-length attention (fa2_fwd_varlen): the varlen instantiations, translation units of their own as well.
+int fa2_launch_generic_varlen(const Fa2Problem &p);
+int fa2_launch_mfma16d_varlen(const Fa2Problem &p, int waves);
 // Validates and normalises a window (include/fa2_fwd.h): FA2_ERR_BAD_ARG for a side < -1.  On FA2_OK *windowed = 0 means the window
 // removes nothing beyond what plain (*causal_out = 0) or causal (*causal_out = 1) attention removes; *windowed = 1 means the band
 // [i - *wl_out, i + *wr_out] with both sides in [0, N - 1] (N - 1 = unbounded), the causal clamp already applied to *wr_out.
@@ -84,3 +91,25 @@ static inline int fa2_dtype_size(int dt) {
 }
 
 #define FA2_LOG2E 1.4426950408889634  // np.log2(np.e), src/flash_attention_kernels.py:9
+
+// Sequence b of a packed (varlen) batch: every offset read is clamped to [0, total], end < start is empty and at most max_len
+// rows are taken -- malformed offsets give wrong numbers at worst, never an access outside the tensors.
+__device__ __forceinline__ void fa2_varlen_seq(const int32_t *cu, int b, int total, int max_len, int &start, int &len) {
+    int s = cu[b], e = cu[b + 1];
+    s = s < 0 ? 0 : (s > total ? total : s);
+    e = e < 0 ? 0 : (e > total ? total : e);
+    const int n = e - s;
+    start = s;
+    len = n < 0 ? 0 : (n > max_len ? max_len : n);
+}
+
+// The band of a packed sequence of nq queries and nk keys in the windowed kernels' terms -- key j visible to query i iff
+// i - wl <= j <= i + wr -- from the raw sides (-1 unbounded; causal clamps the right side to 0), bottom-right aligned: both are
+// shifted by nk - nq.  Either side may come out negative.  |wl|, |wr| <= 2 nq + nk (max_seqlen <= 2^28 keeps i + wr in int).
+__device__ __forceinline__ void fa2_varlen_band(int nq, int nk, int causal, int wl_raw, int wr_raw, int &wl, int &wr) {
+    const int full = nq + nk;  // a side this wide removes nothing
+    const int l = (wl_raw < 0 || wl_raw > full) ? full : wl_raw;
+    const int r = causal ? 0 : ((wr_raw < 0 || wr_raw > full) ? full : wr_raw);
+    wl = l - (nk - nq);
+    wr = r + (nk - nq);
+}

@@ -23,7 +23,12 @@
 
 // FA2_GENERIC_WINDOW (fa2_generic_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr -- under
 // its own kernel name, compiled in a translation unit of its own; without the macro this file is the plain kernel, unchanged.
-#ifdef FA2_GENERIC_WINDOW
+// FA2_GENERIC_VARLEN (fa2_generic_v.hip, on top of FA2_GENERIC_WINDOW): the variable-length form -- grid (ceil(max_q / 16), B, H),
+// each workgroup reads its sequence's offsets and runs the windowed loop with the sequence's own query and key extents and the
+// bottom-right shifted band (fa2_varlen_band); a row without a visible key gets O = 0, L = +inf.
+#if defined(FA2_GENERIC_VARLEN)
+#define fa2_fwd_generic_kernel fa2_fwd_generic_varlen_kernel
+#elif defined(FA2_GENERIC_WINDOW)
 #define fa2_fwd_generic_kernel fa2_fwd_generic_window_kernel
 #endif
 
@@ -59,7 +64,12 @@ struct GenericArgs {
     const void *Q, *K, *V;
     void *O, *L;
     int64_t qs[4], ks[4], vs[4], os[4], ls[2];
-#ifdef FA2_GENERIC_WINDOW
+#if defined(FA2_GENERIC_VARLEN)
+    int N, d, causal;
+    int wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
+    const int32_t *cu_q, *cu_k;
+    int max_q, max_k, total_q, total_k;
+#elif defined(FA2_GENERIC_WINDOW)
     int N, d, causal;
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
 #else
@@ -78,13 +88,27 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x, b = blockIdx.y, h = blockIdx.z;  // kernels.py:38-40
+#ifdef FA2_GENERIC_VARLEN
+    // N = the sequence's queries, NK its keys; bases in 64 bits from the sequence starts (token stride in qs[2], ...)
+    int qst, N, kst, NK;
+    fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, qst, N);
+    fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
+    if (i * kBr >= N) return;  // (whole workgroup, before any barrier)
+    const int d = a.d;
+    const int64_t q_off = (int64_t)qst * a.qs[2] + h * a.qs[1];
+    const int64_t k_off = (int64_t)kst * a.ks[2] + h * a.ks[1];
+    const int64_t v_off = (int64_t)kst * a.vs[2] + h * a.vs[1];
+    const int64_t o_off = (int64_t)qst * a.os[2] + h * a.os[1];
+#else
     const int N = a.N, d = a.d;
+    const int NK = N;
     const char *Qb = (const char *)a.Q;
     const int64_t q_off = b * a.qs[0] + h * a.qs[1];
     const int64_t k_off = b * a.ks[0] + h * a.ks[1];
     const int64_t v_off = b * a.vs[0] + h * a.vs[1];
     const int64_t o_off = b * a.os[0] + h * a.os[1];
     (void)Qb;
+#endif
 
     // Q tile -> LDS (rows past N are clamped; their results are never stored).
     for (int idx = tid; idx < kBr * d; idx += kWaves * 64) {
@@ -108,9 +132,14 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
 
 #ifdef FA2_GENERIC_WINDOW
     // Same trip count for every wave of the workgroup (barriers inside): the keys of its 16 rows, [i kBr - wl, i kBr + 15 + wr]
+#ifdef FA2_GENERIC_VARLEN
+    int wl, wr;
+    fa2_varlen_band(N, NK, a.causal, a.wl, a.wr, wl, wr);
+#else
     const int wl = a.wl, wr = a.wr;
+#endif
     const int kbeg = i * kBr - wl > 0 ? i * kBr - wl : 0;
-    const int kend = i * kBr + kBr + wr < N ? i * kBr + kBr + wr : N;
+    const int kend = i * kBr + kBr + wr < NK ? i * kBr + kBr + wr : NK;
     A *p_w = p_lds + (size_t)wave * kRowsPerWave * kBc;
 
     for (int kt = kbeg; kt < kend; kt += kBc) {
@@ -126,7 +155,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
     for (int kt = 0; kt < kend; kt += kBc) {
 #endif
         const int key = kt + lane;
-        const bool valid = key < N;
+        const bool valid = key < NK;
         A dot[kRowsPerWave];
 #pragma unroll
         for (int r = 0; r < kRowsPerWave; ++r) dot[r] = 0;
@@ -165,7 +194,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
             p_w[r * kBc + lane] = E::round(p);               // :98 cast(P)
         }
         __syncthreads();
-        const int kmax = (N - kt) < kBc ? (N - kt) : kBc;
+        const int kmax = (NK - kt) < kBc ? (NK - kt) : kBc;
         for (int kk = 0; kk < kmax; ++kk) {
             const int64_t vb = v_off + (int64_t)(kt + kk) * a.vs[2];
             A pr[kRowsPerWave];
@@ -189,6 +218,17 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
         const int row = row0 + r;
         const A l = wave_sum(lsum[r]);
         if (row < N) {
+#ifdef FA2_GENERIC_VARLEN
+            // a row without a visible key: O = 0 and L = +inf (the backward then recomputes P = 0)
+#pragma unroll
+            for (int cc = 0; cc < DPL; ++cc) {
+                const int x = lane + 64 * cc;
+                if (x < d)
+                    E::store(a.O, o_off + (int64_t)row * a.os[2] + (int64_t)x * a.os[3], l > 0 ? o[r][cc] / l : (A)0);
+            }
+            if (lane == 0)
+                E::store(a.L, h * a.ls[1] + qst + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
+#else
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
@@ -197,12 +237,17 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
             }
             if (lane == 0)
                 E::store(a.L, b * a.ls[0] + h * a.ls[1] + row, m[r] + log2_acc<A>(l));  // :106,:108
+#endif
         }
     }
 }
 
 template <class E> int launch_e(const Fa2Problem &p, const GenericArgs &a) {
+#ifdef FA2_GENERIC_VARLEN
+    const dim3 grid((p.max_q + kBr - 1) / kBr, p.B, p.H), block(kWaves * 64);
+#else
     const dim3 grid((p.N + kBr - 1) / kBr, p.B, p.H), block(kWaves * 64);
+#endif
     const size_t smem = sizeof(typename E::acc_t) * ((size_t)kBr * p.d + (size_t)kWaves * kRowsPerWave * kBc);
     // output columns per lane: ceil(d / 64) rounded up to the next instantiation (columns >= d are skipped in the kernel)
     const int dpl = (p.d + 63) / 64;
@@ -224,7 +269,9 @@ template <class E> int launch_e(const Fa2Problem &p, const GenericArgs &a) {
 
 }  // namespace
 
-#ifdef FA2_GENERIC_WINDOW
+#if defined(FA2_GENERIC_VARLEN)
+int fa2_launch_generic_varlen(const Fa2Problem &p) {
+#elif defined(FA2_GENERIC_WINDOW)
 int fa2_launch_generic_window(const Fa2Problem &p) {
 #else
 int fa2_launch_generic(const Fa2Problem &p) {
@@ -237,7 +284,11 @@ int fa2_launch_generic(const Fa2Problem &p) {
     a.Q = p.Q; a.K = p.K; a.V = p.V; a.O = p.O; a.L = p.L;
     for (int k = 0; k < 4; ++k) { a.qs[k] = p.qs[k]; a.ks[k] = p.ks[k]; a.vs[k] = p.vs[k]; a.os[k] = p.os[k]; }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
-#ifdef FA2_GENERIC_WINDOW
+#if defined(FA2_GENERIC_VARLEN)
+    a.N = p.N; a.d = p.d; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
+    a.cu_q = p.cu_q; a.cu_k = p.cu_k; a.max_q = p.max_q; a.max_k = p.max_k; a.total_q = p.total_q; a.total_k = p.total_k;
+    if (p.max_q == 0) return FA2_OK;  // no query rows anywhere
+#elif defined(FA2_GENERIC_WINDOW)
     a.N = p.N; a.d = p.d; a.causal = 0; a.wl = p.wl; a.wr = p.wr;
 #else
     a.N = p.N; a.d = p.d; a.causal = p.causal;
@@ -247,8 +298,10 @@ int fa2_launch_generic(const Fa2Problem &p) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);
     case FA2_DTYPE_F16: return launch_e<ElemF16>(p, a);
     case FA2_DTYPE_BF16: return launch_e<ElemBF16>(p, a);
+#ifndef FA2_GENERIC_VARLEN  // (fp8 has no varlen form: no backward, and e4m3fn cannot hold L = +inf)
     case FA2_DTYPE_F8E5M2: return launch_e<ElemF8E5M2>(p, a);
     case FA2_DTYPE_F8E4M3: return launch_e<ElemF8E4M3>(p, a);
+#endif
     case FA2_DTYPE_F64: return launch_e<ElemF64>(p, a);
     default: fa2_set_error("unknown dtype enum %d", p.dtype); return FA2_ERR_UNSUPPORTED;
     }

@@ -16,7 +16,14 @@
 // workgroup, the key loop from the 64-key unit of the tile's first visible key, blocks outside a wave's band skipped, blocks across
 // its edges masked -- under its own kernel name, compiled in a translation unit of its own; without the macro this file is the
 // plain kernel, unchanged.
-#ifdef FA2_MFMA16D_WINDOW
+// FA2_MFMA16D_VARLEN (fa2_mfma16d_v.hip, on top of FA2_MFMA16D_WINDOW): the variable-length form -- one tile of ceil(max_q / BR)
+// per workgroup and sequence; the workgroup reads its sequence's offsets, leaves when its tile starts past the sequence's queries,
+// and runs the windowed loop with the query extent NQ, the key extent NK and the bottom-right shifted band (fa2_varlen_band).
+// Base pointers are built in 64 bits from the sequence starts, so the 32-bit buffer offsets only span one sequence.  A row
+// without a visible key gets O = 0 and L = +inf.
+#if defined(FA2_MFMA16D_VARLEN)
+#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_varlen_kernel
+#elif defined(FA2_MFMA16D_WINDOW)
 #define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_window_kernel
 #endif
 
@@ -54,7 +61,13 @@ struct DmaArgs {
     int B, H, N;
     float c_log2e;
     int group;
-#ifdef FA2_MFMA16D_WINDOW
+#if defined(FA2_MFMA16D_VARLEN)
+    int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
+    int wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
+    int causal;
+    const int32_t *cu_q, *cu_k;
+    int max_q, max_k, total_q, total_k;
+#elif defined(FA2_MFMA16D_WINDOW)
     int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise)
 #else
@@ -121,9 +134,12 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform (M0, scalar branches)
     const int i = lane & 31, h = lane >> 5;
-#ifdef FA2_MFMA16D_WINDOW
+#if defined(FA2_MFMA16D_VARLEN)
+    const int N = a.max_q;  // (only the tile count below: the sequence's own extents are NQ and NK)
+#elif defined(FA2_MFMA16D_WINDOW)
     const int N = a.N;
     const int wl = a.wl, wr = a.wr;
+    const int NQ = N, NK = N;
 #else
     const int N = a.N;
 #endif
@@ -153,9 +169,25 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
     const int b = bh / a.H, hh = bh - b * a.H;
     int q0 = 0, qrow = 0;  // set per pass
 
+#ifdef FA2_MFMA16D_VARLEN
+    int qst, NQ, kst, NK;
+    fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, qst, NQ);
+    fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
+    qst = __builtin_amdgcn_readfirstlane(qst);
+    NQ = __builtin_amdgcn_readfirstlane(NQ);
+    kst = __builtin_amdgcn_readfirstlane(kst);
+    NK = __builtin_amdgcn_readfirstlane(NK);
+    if (qi_first * BR >= NQ) return;  // (whole workgroup, before any barrier)
+    int wl, wr;
+    fa2_varlen_band(NQ, NK, a.causal, a.wl, a.wr, wl, wr);
+    const char *Qp = a.Q + (int64_t)qst * a.qs[2] + (int64_t)hh * a.qs[1];
+    const char *Kp = a.K + (int64_t)kst * a.ks[2] + (int64_t)hh * a.ks[1];
+    const char *Vp = a.V + (int64_t)kst * a.vs[2] + (int64_t)hh * a.vs[1];
+#else
     const char *Qp = a.Q + (int64_t)b * a.qs[0] + (int64_t)hh * a.qs[1];
     const char *Kp = a.K + (int64_t)b * a.ks[0] + (int64_t)hh * a.ks[1];
     const char *Vp = a.V + (int64_t)b * a.vs[0] + (int64_t)hh * a.vs[1];
+#endif
 
     frag qf[KS];
 
@@ -172,8 +204,14 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
         r[3] = 0x00020000;
         return r;
     };
+#ifdef FA2_MFMA16D_VARLEN
+    // (NK = 0: an empty range -- every load reads 0, and no block is active)
+    const i32x4 krsrc = make_rsrc(Kp, NK > 0 ? (NK - 1) * krs + ROWB : 0);
+    const i32x4 vrsrc = make_rsrc(Vp, NK > 0 ? (NK - 1) * vrs + ROWB : 0);
+#else
     const i32x4 krsrc = make_rsrc(Kp, (N - 1) * krs + ROWB);
     const i32x4 vrsrc = make_rsrc(Vp, (N - 1) * vrs + ROWB);
+#endif
     const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
     int kvo[PPW], vvo[PPW];
 #pragma unroll
@@ -232,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
     auto partial = [&](f32x16 &s, int j, float &coeff, bool masked) -> bool {
         if (masked) {
 #ifdef FA2_MFMA16D_WINDOW
-            const int lim = qrow + wr < N - 1 ? qrow + wr : N - 1;
+            const int lim = qrow + wr < NK - 1 ? qrow + wr : NK - 1;
             const int klim = lim - (j * 32 + 4 * h), klo = qrow - wl - (j * 32 + 4 * h);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -297,7 +335,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
             }
     };
 #ifdef FA2_MFMA16D_WINDOW
-    auto block_masked = [&](int j) { return (j * 32 + 32 > N) || (j * 32 < q0 + 31 - wl) || (j * 32 + 31 > q0 + wr); };
+    auto block_masked = [&](int j) { return (j * 32 + 32 > NK) || (j * 32 < q0 + 31 - wl) || (j * 32 + 31 > q0 + wr); };
 #else
     auto block_masked = [&](int j) { return (CAUSAL && (j * 32 + 31 > q0)) || (j * 32 + 32 > N); };
 #endif
@@ -307,7 +345,11 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
         q0 = qi * BR + wave * 32;
         qrow = q0 + i;
         {
+#ifdef FA2_MFMA16D_WINDOW
+            const int row = qrow < NQ ? qrow : NQ - 1;
+#else
             const int row = qrow < N ? qrow : N - 1;
+#endif
             const char *qp = Qp + (int64_t)row * a.qs[2] + h * 16;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(frag, *(const u32x4 *)(qp + ks * 32));
@@ -315,13 +357,13 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
 #ifdef FA2_MFMA16D_WINDOW
         // window: the keys of the tile's rows [qi BR - wl, qi BR + BR - 1 + wr]; the loop starts at the 64-key unit t0 of the
         // first one.  Per wave: blocks [jlo, nb) meet its band, the others are skipped
-        kend = qi * BR + BR + wr < N ? qi * BR + BR + wr : N;
+        kend = qi * BR + BR + wr < NK ? qi * BR + BR + wr : NK;
         const int t0 = qi * BR - wl > 0 ? (qi * BR - wl) >> 6 : 0;
         const int jlo = q0 - wl > 0 ? (q0 - wl) >> 5 : 0;
         nt = (kend + 63) >> 6;    // V tiles (loop iterations t0 .. nt-1)
         nblk = (kend + 31) >> 5;  // 32-key blocks of this tile
         {
-            const int hi = q0 + 31 + wr < N - 1 ? q0 + 31 + wr : N - 1;
+            const int hi = q0 + 31 + wr < NK - 1 ? q0 + 31 + wr : NK - 1;
             nb = (hi >> 5) + 1 < nblk ? (hi >> 5) + 1 : nblk;
         }
         auto act = [&](int j) { return j >= jlo && j < nb; };
@@ -354,7 +396,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
         // steady iterations t: block 2t computed, blocks 2t+1 and 2t+2 inside the band for all 32 rows of the wave
         const int ulo = q0 + 31 - wl > 0 ? (q0 + 31 - wl + 31) >> 5 : 0;  // first block without a left-edge mask
         int umax = q0 + wr - 31 < 0 ? -1 : (q0 + wr - 31) >> 5;            // last block without a right-edge mask
-        umax = (N >> 5) - 1 < umax ? (N >> 5) - 1 : umax;
+        umax = (NK >> 5) - 1 < umax ? (NK >> 5) - 1 : umax;
         int t_head = (jlo + 1) >> 1 > (ulo >> 1) ? (jlo + 1) >> 1 : ulo >> 1;
         t_head = t_head < t0 ? t0 : (t_head > nt ? nt : t_head);
         int t_steady = umax >= 2 ? (umax - 2) / 2 + 1 : 0;
@@ -502,7 +544,11 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
         // wave's 32 x D tile goes through its own 32*ROWB-byte slice of the (now idle) K/V buffers and leaves as
         // whole rows: ROWB/16 lanes x 16 bytes per row, 1 KiB contiguous per store instruction.
         const float l = half_swap_sum(lsum);
+#ifdef FA2_MFMA16D_VARLEN
+        const float inv = l > 0.0f ? 1.0f / l : 0.0f;  // a row without a visible key: O = 0
+#else
         const float inv = 1.0f / l;
+#endif
         {
             const int ebase = wave * 32 * ROWB;  // NW * 32 * ROWB <= 4 * TILEB
 #pragma unroll
@@ -519,6 +565,20 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
             // until the barrier below
             constexpr int RPI = 64 / CPR;  // rows per store instruction (4 at d = 128, 8 at d = 64)
             const int er = lane / CPR, ec = lane % CPR;
+#ifdef FA2_MFMA16D_VARLEN
+            char *ob = a.O + (int64_t)qst * a.os[2] + (int64_t)hh * a.os[1];
+#pragma unroll
+            for (int k = 0; k < 32 / RPI; ++k) {
+                const int r = k * RPI + er;
+                const u32x4 val = *(LDS_PTR(u32x4))(lds + ebase + lds_off<D>(r, ec));
+                if (q0 + r < NQ) *(u32x4 *)(ob + (int64_t)(q0 + r) * a.os[2] + ec * 16) = val;
+            }
+        }
+        if (qrow < NQ && h == 0) {
+            T *lp = (T *)a.L + hh * a.ls[1] + qst + qrow;
+            *lp = l > 0.0f ? (T)(m + __builtin_amdgcn_logf(l)) : (T)INFINITY;  // no visible key: L = +inf
+        }
+#else
             char *ob = a.O + (int64_t)b * a.os[0] + (int64_t)hh * a.os[1];
 #pragma unroll
             for (int k = 0; k < 32 / RPI; ++k) {
@@ -531,6 +591,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
             T *lp = (T *)a.L + b * a.ls[0] + hh * a.ls[1] + qrow;
             *lp = (T)(m + __builtin_amdgcn_logf(l));
         }
+#endif
         if (pass + 1 < npass) __syncthreads();  // the next pass's DMA reuses the slices
 
     }  // pass
@@ -538,7 +599,11 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
 
 template <typename T, int D, int NW> int launch_t(const Fa2Problem &p, const DmaArgs &a) {
     constexpr int BR = NW * 32;
+#ifdef FA2_MFMA16D_VARLEN
+    const int nq = (p.max_q + BR - 1) / BR;
+#else
     const int nq = (p.N + BR - 1) / BR;
+#endif
     const long long nblk = (long long)(p.causal ? (nq + 1) / 2 : nq) * p.B * p.H;  // causal: one workgroup per tile pair
     if (nblk > 0x7fffffffLL) {
         fa2_set_error("mfma16d: grid too large");
@@ -569,12 +634,19 @@ template <typename T> int launch_d(const Fa2Problem &p, const DmaArgs &a, int wa
 
 }  // namespace
 
-#ifdef FA2_MFMA16D_WINDOW
+#if defined(FA2_MFMA16D_VARLEN)
+int fa2_launch_mfma16d_varlen(const Fa2Problem &pv, int waves) {
+    Fa2Problem p = pv;
+    p.causal = 0;  // the causal mask is in the band (fa2_varlen_band): one tile per workgroup, no tile pairs
+    // 32-bit buffer offsets span one sequence: judged on max_seqlen x row stride, not on the packed total
+    const bool fits32 = (int64_t)(p.max_k + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.max_k + 512) * p.vs[2] * 2 < (1LL << 31);
+#elif defined(FA2_MFMA16D_WINDOW)
 int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves) {
+    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
 #else
 int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
-#endif
     const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
+#endif
     if (!fa2_mfma16_supports(p) || !fits32) {
         fa2_set_error("mfma16d kernel: needs f16/bf16, d in {64,128}, unit d-stride, 16-byte aligned rows, scale > 0, "
                       "N * row stride < 2 GiB");
@@ -590,7 +662,14 @@ int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
     a.B = p.B; a.H = p.H; a.N = p.N;
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
     a.group = 1;
-#ifdef FA2_MFMA16D_WINDOW
+#if defined(FA2_MFMA16D_VARLEN)
+    a.flags = fa2_env_int("FA2_FLAGS", 0);
+    a.wl = p.wl;
+    a.wr = p.wr;
+    a.causal = pv.causal;
+    a.cu_q = p.cu_q; a.cu_k = p.cu_k; a.max_q = p.max_q; a.max_k = p.max_k; a.total_q = p.total_q; a.total_k = p.total_k;
+    if (p.max_q == 0) return FA2_OK;  // no query rows anywhere
+#elif defined(FA2_MFMA16D_WINDOW)
     a.flags = fa2_env_int("FA2_FLAGS", 0);
     a.wl = p.wl;
     a.wr = p.wr;

@@ -293,3 +293,155 @@ class FlashAttentionDeterministic(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_outputs, *args):
         return _backward_impl(ctx, grad_outputs)
+
+
+# ---- variable-length (packed) attention: include/fa2_fwd.h fa2_fwd_varlen, include/fa2_bwd.h fa2_bwd_varlen ----
+
+def _seq_bounds(cu, total):
+    """Host copy of cu_seqlens -> [(start, end)], clamped exactly as the kernels clamp (fa2_varlen_seq), without max_seqlen."""
+    out = []
+    c = [min(max(int(x), 0), total) for x in cu.tolist()]
+    for b in range(len(c) - 1):
+        out.append((c[b], max(c[b + 1], c[b])))
+    return out
+
+
+def varlen_mask(cu_seqlens_q, cu_seqlens_k, causal=False, window=None, total_q=None, total_k=None):
+    """(total_q, total_k) boolean mask of the visible (query token, key token) pairs of a packed batch: block-diagonal over the
+    sequences, bottom-right aligned inside each -- query i of a sequence of N_q queries and N_k keys sees key j iff
+    i + (N_k - N_q) - left <= j <= i + (N_k - N_q) + right, with -1 unbounded and causal clamping right to 0 (fa2_fwd_varlen).
+    For tests and docs; built on the CPU."""
+    cq, ck = cu_seqlens_q.cpu(), cu_seqlens_k.cpu()
+    total_q = int(cq[-1]) if total_q is None else total_q
+    total_k = int(ck[-1]) if total_k is None else total_k
+    left, right = (-1, -1) if window is None else window
+    mask = torch.zeros(total_q, total_k, dtype=torch.bool)
+    for (q0, q1), (k0, k1) in zip(_seq_bounds(cq, total_q), _seq_bounds(ck, total_k)):
+        nq, nk = q1 - q0, k1 - k0
+        if nq == 0 or nk == 0:
+            continue
+        i = torch.arange(nq).view(nq, 1) + (nk - nq)
+        j = torch.arange(nk).view(1, nk)
+        m = torch.ones(nq, nk, dtype=torch.bool)
+        if left >= 0:
+            m &= j >= i - left
+        r = 0 if causal else right
+        if r >= 0:
+            m &= j <= i + r
+        mask[q0:q1, k0:k1] = m
+    return mask
+
+
+def check_varlen_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window):
+    """ValueError for what the varlen entry points cannot take (shapes, dtypes, offsets, window); the CUDA-device check is
+    _check_varlen_device's."""
+    dev = Q.device
+    if Q.dim() != 3 or K.dim() != 3 or V.dim() != 3:
+        raise ValueError(f"varlen: Q, K, V must be (total, H, d), got {tuple(Q.shape)}, {tuple(K.shape)}, {tuple(V.shape)}")
+    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
+        raise ValueError(f"varlen: K and V must be (total_k, H, d) with Q's H and d, got Q {tuple(Q.shape)}, "
+                         f"K {tuple(K.shape)}, V {tuple(V.shape)}")
+    if Q.dtype != K.dtype or K.dtype != V.dtype:
+        raise ValueError("varlen: Q, K, V must have the same dtype")
+    if Q.dtype in (torch.float8_e5m2, torch.float8_e4m3fn):
+        raise ValueError(f"varlen: dtype {Q.dtype} is not supported (no backward; e4m3fn cannot hold L = +inf)")
+    convert_triton_dtype(Q.dtype)
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32 or cu.dim() != 1 or not cu.is_contiguous():
+            raise ValueError(f"varlen: {name} must be a contiguous 1-D int32 tensor")
+        if cu.device != dev:
+            raise ValueError(f"varlen: {name} must be on Q's device ({dev}), got {cu.device}")
+        if cu.numel() < 2:
+            raise ValueError(f"varlen: {name} must have B + 1 >= 2 entries, got {cu.numel()}")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel():
+        raise ValueError(f"varlen: cu_seqlens_q and cu_seqlens_k must both have B + 1 entries, got {cu_seqlens_q.numel()} "
+                         f"and {cu_seqlens_k.numel()}")
+    for name, m in (("max_seqlen_q", max_seqlen_q), ("max_seqlen_k", max_seqlen_k)):
+        if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+            raise ValueError(f"varlen: {name} must be an int >= 0, got {m!r}")
+    if window is not None:
+        normalize_window(1, False, window)  # the sides' own rules (pair of ints >= -1); the shift is per sequence
+
+
+def _check_varlen_device(Q, K, V):
+    dev = Q.device
+    if dev.type != "cuda" or dev != K.device or dev != V.device:
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+
+
+def varlen_head_size(dtype, d, backward=False):
+    """Head size a varlen launch runs at: the forward pads like window_head_size, the backward to a power of two >= 16."""
+    if backward:
+        return max(next_power_of_2(d), MIN_TENSOR_SIZE)
+    return window_head_size(dtype, d)
+
+
+def varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, causal=False, scale=1.0, window=None,
+                   variant="auto"):
+    """(O, L) of a packed batch: O (total_q, H, d) contiguous, L (H, total_q) in the I/O dtype.  A forced variant gets the
+    tensors as they are; auto pads the head size for the matrix kernel (varlen_head_size)."""
+    _check_varlen_device(Q, K, V)
+    check_varlen_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window)
+    total_q, H, d_out = Q.shape
+    d = varlen_head_size(Q.dtype, d_out) if variant == "auto" else d_out
+    if d != d_out:
+        Q, K, V = (pad_last_dim(t, d) for t in (Q, K, V))
+    O = torch.empty(total_q, H, d, dtype=Q.dtype, device=Q.device)
+    L = torch.empty(H, total_q, dtype=Q.dtype, device=Q.device)
+    _lib.fa2_fwd_varlen(Q, K, V, O, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, convert_triton_dtype(Q.dtype),
+                        causal=causal, scale=scale, window=window, variant=_lib.VARIANTS[variant])
+    if d != d_out:
+        O = O[..., :d_out].contiguous()
+    return O, L
+
+
+def varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, causal=False, scale=1.0,
+                    window=None, variant="auto"):
+    """(dQ, dK, dV) of a packed batch from the forward's O and L (fa2_bwd_varlen): the MFMA kernel for f16 / bf16 at
+    d = 64 / 128 under AUTO, else the VALU kernel, d padded to a power of two >= 16.  Tokens outside every sequence are not
+    written (include/fa2_bwd.h)."""
+    _check_varlen_device(Q, K, V)
+    check_varlen_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window)
+    if O.shape != Q.shape or dO.shape != Q.shape or O.dtype != Q.dtype or dO.dtype != Q.dtype:
+        raise ValueError("varlen backward: O and dO must have Q's shape and dtype")
+    total_q, H, d = Q.shape
+    if L.shape != (H, total_q) or L.dtype != Q.dtype or L.stride(1) != 1:
+        raise ValueError(f"varlen backward: L must be ({H}, {total_q}) in Q's dtype with unit token stride")
+    d_pow = varlen_head_size(Q.dtype, d, backward=True)
+    if d_pow != d:
+        Q, K, V, O, dO = (pad_last_dim(t, d_pow) for t in (Q, K, V, O, dO))
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    D = torch.empty(2, H, total_q, dtype=torch.float64 if Q.dtype == torch.float64 else torch.float32, device=Q.device)
+    _lib.fa2_bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                        convert_triton_dtype(Q.dtype), causal=causal, scale=scale, window=window,
+                        variant=_lib.BWD_VARIANTS[variant])
+    if d_pow != d:
+        return dQ[..., :d], dK[..., :d], dV[..., :d]
+    return dQ, dK, dV
+
+
+class FlashAttentionVarlen(torch.autograd.Function):
+    """Packed variable-length attention (flash_attn_varlen_func's calling convention):
+    `FlashAttentionVarlen.apply(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window)`,
+    Q (total_q, H, d), K / V (total_k, H, d), bottom-right aligned causal mask and window (include/fa2_fwd.h).  Returns O;
+    the cu_seqlens and the other arguments get no gradient.  Tokens outside every sequence (cu_seqlens[-1] < total, or gaps
+    between sequences) are left unwritten in O and in the gradients, as flash-attn leaves them: such a batch must not feed
+    them on."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, scale=1.0, window=None):
+        O, L = varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal, scale=scale,
+                              window=window)
+        ctx.save_for_backward(Q, K, V, O, L, cu_seqlens_q, cu_seqlens_k)
+        ctx.args = (max_seqlen_q, max_seqlen_k, bool(causal), float(scale), window)
+        ctx.mark_non_differentiable(L)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO, *args):
+        Q, K, V, O, L, cu_q, cu_k = ctx.saved_tensors
+        max_q, max_k, causal, scale, window = ctx.args
+        if dO.stride(-1) != 1:
+            dO = dO.contiguous()
+        dQ, dK, dV = varlen_backward(Q, K, V, O, dO, L, cu_q, cu_k, max_q, max_k, causal=causal, scale=scale, window=window)
+        return dQ, dK, dV, None, None, None, None, None, None, None

@@ -7,7 +7,8 @@ import torch
 
 from . import _lib, autotune
 from .flash_attention_torch import (MIN_TENSOR_SIZE, backward_native, convert_triton_dtype, forward_head_size,
-                                    next_power_of_2, normalize_window, pad_last_dim, window_head_size)
+                                    next_power_of_2, normalize_window, pad_last_dim, varlen_backward, varlen_forward,
+                                    window_head_size)
 
 
 def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="auto", window=None):
@@ -92,3 +93,22 @@ def flash_attention_backward(Q, K, V, O, dO, L, dev, deterministic=False, *, cau
         Q, K, V, O, dO = (pad_last_dim(t, d_pow) for t in (Q, K, V, O, dO))
     dQ, dK, dV = backward_native(Q, K, V, O, dO, L, causal=causal, scale=scale, variant=variant, window=window)
     return dQ[..., :d], dK[..., :d], dV[..., :d]
+
+
+def flash_attention_varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dev, *, causal=False,
+                                   scale=1.0, window=None, variant="auto"):
+    """Packed variable-length forward (include/fa2_fwd.h fa2_fwd_varlen) -> (O, L): Q (total_q, H, d), K / V (total_k, H, d),
+    cu_seqlens int32 (B + 1) on Q's device; O (total_q, H, d), L (H, total_q).  The autotuner is not consulted."""
+    if Q.device != torch.device(dev):
+        raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
+    return varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal, scale=scale,
+                          window=window, variant=variant)
+
+
+def flash_attention_varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dev, *,
+                                    causal=False, scale=1.0, window=None, variant="auto"):
+    """(dQ, dK, dV) of flash_attention_varlen_forward (include/fa2_bwd.h fa2_bwd_varlen); deterministic."""
+    if Q.device != torch.device(dev):
+        raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
+    return varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
+                           scale=scale, window=window, variant=variant)

@@ -91,6 +91,35 @@ int fa2_bwd_window_variant(const void *Q, const void *K, const void *V, const vo
                            float scale, int32_t window_left, int32_t window_right, void *hip_stream,
                            int32_t variant);
 
+/* Variable-length (packed) attention: the gradients of fa2_fwd_varlen's O, given its L.  Layout, offsets, masks, empty
+ * rows, argument checks and the clamping of cu_seqlens as in include/fa2_fwd.h; dQ is laid out like Q, dK / dV like K / V
+ * (3-element strides {token, head, dim}).  D is a contiguous scratch of 2 * H * total_q float32 (float64 for f64).  Rows
+ * without a visible key get dQ = 0 and add nothing to dK / dV; keys no query sees get dK = dV = 0.  Tokens outside every
+ * sequence (cu_seqlens[B] < total, or gaps between sequences) are not written in dQ / dK / dV, as in the forward's O.
+ * Deterministic, no atomics.  Variants: FA2_BWD_VARIANT_AUTO (MFMA16 where it runs, else GENERIC), FA2_BWD_VARIANT_GENERIC
+ * (f64, f32, f16, bf16; d = 2^k in [16, 512], the host pads) and FA2_BWD_VARIANT_MFMA16 (f16 / bf16, d in {64, 128}, unit
+ * d-stride, 16-byte aligned rows; its 32-bit offsets are judged on max_seqlen x row stride); a forced FA2_BWD_VARIANT_MFMA32
+ * returns FA2_ERR_UNSUPPORTED. */
+int fa2_bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                   void *dQ, void *dK, void *dV, void *D,
+                   const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                   const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                   const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                   int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                   void *hip_stream);
+
+int fa2_bwd_varlen_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO,
+                           const void *L, void *dQ, void *dK, void *dV, void *D,
+                           const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                           const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                           const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                           const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                           int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                           int32_t window_right, void *hip_stream, int32_t variant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,50 @@ int fa2_fwd_window_variant(const void *Q, const void *K, const void *V, void *O,
                            int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                            int32_t window_right, void *hip_stream, int32_t variant);
 
+/*
+ * Variable-length (packed) attention: B sequences of different lengths in one call, as FlashAttention-2's
+ * flash_attn_varlen_func takes them.
+ *
+ *   Layout.   Q is (total_q, H, d), K and V are (total_k, H, d), strides {token, head, dim} in elements (3 each); O is
+ *             (total_q, H, d); L is (H, total_q) in the I/O dtype, unit stride over tokens, head stride l_head_stride.
+ *   Offsets.  cu_seqlens_q / cu_seqlens_k: device int32 arrays of B + 1 entries.  Sequence b owns query tokens
+ *             [cu_q[b], cu_q[b+1]) and key tokens [cu_k[b], cu_k[b+1]) and attends only to its own keys.  max_seqlen_q /
+ *             max_seqlen_k (host) size the grid, as in flash-attn.  Tokens outside every sequence are not written.
+ *   Causal.   Bottom-right aligned: query i of a sequence of N_q queries and N_k keys sees key j iff j <= i + (N_k - N_q);
+ *             with N_q == N_k this is fa2_fwd's causal mask.
+ *   Window.   window_left / window_right with the same shift: i + (N_k - N_q) - left <= j <= i + (N_k - N_q) + right,
+ *             -1 = unbounded; causal clamps right to 0.  With N_q == N_k this is fa2_fwd_window's definition.
+ *   Empty rows.  A row without a visible key (causal with N_q > N_k, N_k = 0, or a window) gets O = 0 and L = +inf, as
+ *             FlashAttention-2 does: fa2_bwd_varlen then recomputes P = 0 for it, its dQ row is 0, no NaN anywhere.
+ *   Lengths.  N_q = 0 and N_k = 0 are allowed.
+ *   Dtypes.   f64, f32, f16, bf16; fp8 returns FA2_ERR_UNSUPPORTED (no backward, and e4m3fn cannot hold +inf).
+ *   Safety.   Every cu_seqlens value read is clamped to [0, total]; end < start is empty; at most max_seqlen rows or keys of
+ *             a sequence are processed.  Malformed offsets give wrong numbers at worst, never an access outside the tensors.
+ *             Base pointers are built in 64 bits per sequence, so the 32-bit buffer-offset limit of the matrix kernels is
+ *             judged on max_seqlen x row stride, not on the packed total.
+ *
+ * FA2_ERR_BAD_ARG before any launch for: a null pointer, B not in [1, 65535], H not in [1, 65535], max_seqlen_q / max_seqlen_k
+ * not in [0, 2^28], total_q / total_k < 0, a window side < -1, a negative stride; the message names the argument.
+ * Variants: FA2_VARIANT_AUTO (MFMA16D_W4 where it runs, else GENERIC), FA2_VARIANT_GENERIC (f64, f32, f16,
+ * bf16, any strides, any d in [1, 512]), FA2_VARIANT_MFMA16D and FA2_VARIANT_MFMA16D_W4 (f16 / bf16, d in {64, 128}, unit
+ * d-stride, 16-byte aligned rows).  Any other forced variant returns FA2_ERR_UNSUPPORTED.
+ */
+int fa2_fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L,
+                   const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                   const int64_t o_strides[3], int64_t l_head_stride,
+                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                   int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                   void *hip_stream);
+
+int fa2_fwd_varlen_variant(const void *Q, const void *K, const void *V, void *O, void *L,
+                           const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                           const int64_t o_strides[3], int64_t l_head_stride,
+                           const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                           int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                           int32_t window_right, void *hip_stream, int32_t variant);
+
 /* Which tile the static table picks for a contiguous problem: out4 = {variant, B_r, B_c, waves}.
  * Counterpart of fwd_conf_prune + the autotuner's choice (src/autotune_configs.py:176-194). */
 int fa2_query_tile(int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, int32_t out4[4]);
