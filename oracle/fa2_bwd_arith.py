@@ -13,7 +13,9 @@ The arithmetic (csrc/ = flash_attention_dlrs_amd/csrc/):
                                                                    fa2_bwd_generic.hip:213 (float64 I/O: c stays double)
   D   = sum_x dO * O, O as stored                                   fa2_bwd_mfma16.hip:99-118, fa2_bwd_generic.hip:42-53
   S   = Q K^T;  P_u = exp2(c S - L), L as stored; 0 where masked   fa2_bwd_mfma16.hip:400 / :427, generic :135-136
-        (causal mask: key > query; rows and keys >= N: 0)
+        (causal mask: key > query; rows and keys >= N: 0;
+         window / varlen: outside band(), per sequence; a row with no visible key has L = +inf, so P = 0 and dQ = 0:
+         fa2_bwd_mfma16.hip:657-659, fa2_bwd_generic.hip:286)
   tot = sum_j P_u                                                   fa2_bwd_mfma16.hip:429 / :489-495, generic :141-145
   Lc  = L + log2 tot  (the dQ launch hands it to the dK/dV launch)  fa2_bwd_mfma16.hip:512, generic :174
   dQ  = rnd(P_u (dP - D)) K * (scale / tot)       mfma16 / mfma32:  fa2_bwd_mfma16.hip:430, :445, :511
@@ -56,8 +58,31 @@ import torch
 KERNELS = ("mfma16", "mfma32", "generic")
 # Errors the CPU tests plant in the restatement, to show that the bars catch them (tests/test_bwd_arith.py)
 PLANTS = ("no_renorm", "drop_last_key", "diag_off_by_one", "ds_other_point", "scale_twice", "scale_none", "d_unrounded_o")
+# ... and in the band of a window / varlen problem (band() below): one more key on the right or on the left of every row, the
+# band aligned top-left instead of bottom-right
+MASK_PLANTS = ("right_plus_one", "left_minus_one", "top_left")
 
 BwdArith = namedtuple("BwdArith", "dQ dK dV tol noise")
+
+
+def band(nq, nk, causal=False, window=None, device=None, plant=None):
+    """(nq, nk) visible (query, key) pairs of a window / varlen problem, bottom-right aligned (include/fa2_fwd.h): query i
+    sees key j iff i + (nk - nq) - left <= j <= i + (nk - nq) + right; a side of -1 is unbounded and causal clamps right to 0.
+    plant (tests only): right_plus_one / left_minus_one move that edge out by one key (where it is bounded), shift_one moves
+    both edges one key to the right, top_left drops the nk - nq shift."""
+    left, right = (-1, -1) if window is None else window
+    if causal:
+        right = 0
+    i = torch.arange(nq, device=device).view(nq, 1) + (0 if plant == "top_left" else nk - nq)
+    j = torch.arange(nk, device=device).view(1, nk)
+    dl = {"left_minus_one": 1, "shift_one": -1}.get(plant, 0)
+    dr = {"right_plus_one": 1, "shift_one": 1}.get(plant, 0)
+    keep = torch.ones(nq, nk, dtype=torch.bool, device=device)
+    if left >= 0:
+        keep &= j >= i - left - dl
+    if right >= 0:
+        keep &= j <= i + right + dr
+    return keep
 
 
 def c_log2e(scale, dtype):
@@ -78,16 +103,21 @@ def ulp(x, dtype):
     return torch.exp2(torch.floor(torch.log2(a))) * fi.eps
 
 
-def restate(Q, K, V, O, L, dO, causal=False, scale=1.0, kernel="mfma16", plant=None, bars=True, acc=torch.float64):
+def restate(Q, K, V, O, L, dO, causal=False, scale=1.0, kernel="mfma16", plant=None, bars=True, acc=torch.float64, *,
+            window=None, keep=None):
     """dQ, dK, dV (I/O dtype) of `kernel` for the problem, the element-wise bars and their term (3) alone (`noise`; float64,
     None if bars=False).
-    Q, K, V, O, dO: (B, H, N, d) in the I/O dtype, any strides; L: (B, H, N[, 1]) as the forward stored it.
-    `plant` puts one of PLANTS into the arithmetic (tests only); acc=torch.float32 runs the same arithmetic in fp32 (a
-    valid implementation with the kernels' precision, which the bars must accept: tests/test_bwd_arith.py)."""
-    assert kernel in KERNELS and (plant is None or plant in PLANTS)
+    Q, O, dO: (B, H, N_q, d), K, V: (B, H, N_k, d), in the I/O dtype, any strides; L: (B, H, N_q[, 1]) as the forward stored
+    it.  The visible pairs: `keep` (N_q, N_k) if given, else band(N_q, N_k, causal, window) for a window or a rectangular
+    problem, else all pairs or the causal tril.  A row without a visible key (L = +inf, as the varlen forward stores it)
+    gets P = 0 and dQ = 0, as the kernels give it.
+    `plant` puts one of PLANTS or MASK_PLANTS into the arithmetic (tests only); acc=torch.float32 runs the same arithmetic in
+    fp32 (a valid implementation with the kernels' precision, which the bars must accept: tests/test_bwd_arith.py)."""
+    assert kernel in KERNELS and (plant is None or plant in PLANTS or plant in MASK_PLANTS)
     io = Q.dtype
     f = acc
     B, H, N, d = Q.shape
+    Nk = K.shape[2]
     q, k, v, o, do = (t.to(f) for t in (Q, K, V, O, dO))
     l = L.to(f).reshape(B, H, N, 1)
     c = c_log2e(scale, io)
@@ -96,15 +126,24 @@ def restate(Q, K, V, O, L, dO, causal=False, scale=1.0, kernel="mfma16", plant=N
         scale_at_store = not scale_at_store
 
     S = torch.matmul(q, k.transpose(-1, -2))
-    keep = torch.ones(N, N, dtype=torch.bool, device=Q.device)
-    if causal:
-        keep = keep.tril(-1 if plant == "diag_off_by_one" else 0)
+    if keep is not None:
+        assert plant not in MASK_PLANTS, "a mask plant needs the band, not an explicit keep"
+        keep = keep.to(Q.device).clone()
+    elif window is not None or Nk != N or plant in MASK_PLANTS:
+        keep = band(N, Nk, causal, window, Q.device, plant if plant in MASK_PLANTS else None)
+    else:
+        keep = torch.ones(N, N, dtype=torch.bool, device=Q.device)
+        if causal:
+            keep = keep.tril(-1 if plant == "diag_off_by_one" else 0)
+    if plant == "diag_off_by_one" and (window is not None or Nk != N):     # the band's own diagonal j = i + (Nk - N)
+        keep &= ~torch.ones(N, Nk, dtype=torch.bool, device=Q.device).tril(Nk - N).triu(Nk - N)
     if plant == "drop_last_key":
-        keep[:, N - 1] = False
+        keep[..., Nk - 1] = False
     cS = (S * c).masked_fill(~keep, -math.inf)
     Pu = torch.exp2(cS - l)
     tot = Pu.sum(-1, keepdim=True)
-    Lc = l if plant == "no_renorm" else l + torch.log2(tot)
+    empty = torch.isinf(l)                             # no visible key: L = +inf stays, P = 0, dQ = 0
+    Lc = l if plant == "no_renorm" else torch.where(empty, l, l + torch.log2(tot))
     Pn = torch.exp2(cS - Lc)
     if plant == "no_renorm":
         tot = torch.ones_like(tot)
@@ -122,15 +161,16 @@ def restate(Q, K, V, O, L, dO, causal=False, scale=1.0, kernel="mfma16", plant=N
     dSu = rnd(Pu * (dP - D) * s_in, io)
     dSn = rnd(Pn * (dP - D) * s_in, io)
     Pr = rnd(Pn, io)
-    mq = s_out / tot                                   # dQ's factor at the store (per query row)
+    mq = (s_out / tot).masked_fill(empty, 0.0)         # dQ's factor at the store (per query row; 0 for an empty row)
     dQ = torch.matmul(dSu, k) * mq
     dK = torch.matmul(dSn.transpose(-1, -2), q) * s_out
     dV = torch.matmul(Pr.transpose(-1, -2), do)
     tol = noise = None
     if bars:
         absS = torch.matmul(q.abs(), k.abs().transpose(-1, -2)).masked_fill(~keep, 0)     # sum_x |q_x k_x|
-        E = (abs(c) * absS.amax() + l.abs().amax()).item() if N else 0.0
-        eps = 2.0 ** -24 * 16 * (math.sqrt(N) + math.sqrt(d) + E)
+        lf = l[~empty]                                 # (rows without a key carry L = +inf: no term of theirs)
+        E = (abs(c) * absS.amax() + lf.abs().amax()).item() if lf.numel() else 0.0
+        eps = 2.0 ** -24 * 16 * (math.sqrt(max(N, Nk)) + math.sqrt(d) + E)
         sq = abs(s_in)
         dots = torch.matmul(do.abs(), v.abs().transpose(-1, -2)) + (do * o).abs().sum(-1, keepdim=True)
         mag_dS_u = Pu * dots * sq                        # |t|' of the dS terms

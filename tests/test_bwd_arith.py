@@ -179,3 +179,103 @@ def test_old_max_norm_bar_misses_renormalization_and_last_key():
     for p in ("no_renorm", "drop_last_key"):
         bad = A.restate(Q, K, V, O, L, dO, True, 1.0, "mfma16", plant=p, bars=False)
         assert not all(ok for *_, ok in A.compare(bad[:3], ref)), p
+
+
+# ----------------------------------------------------------------------------- window and varlen
+def stored_forward_band(Q, K, V, keep, scale):
+    """O and L of a window / rectangular (one varlen sequence) problem as the forward stores them: fp64, rounded once to the
+    I/O dtype; a row without a visible key O = 0, L = +inf"""
+    from oracle.fa2_mask_probe import truth
+    O, L = truth(Q, K, V, keep, Q.dtype, scale)
+    return O.to(Q.dtype), L.to(Q.dtype)
+
+
+def rand_rect(B, H, nq, nk, d, dtype, seed, spread=1.0):
+    g = torch.Generator().manual_seed(seed)
+    Q, dO = ((torch.randn(B, H, nq, d, generator=g) * spread).to(dtype) for _ in range(2))
+    K, V = ((torch.randn(B, H, nk, d, generator=g) * spread).to(dtype) for _ in range(2))
+    return Q, K, V, dO
+
+
+# (nq, nk, window, causal): dense windows (nq = nk) and single varlen sequences, bottom-right aligned, empty rows included
+BAND_PROBLEMS = [(65, 65, (16, 15), False), (130, 130, (-1, 31), False), (100, 100, (40, 0), True), (72, 72, (0, 0), False),
+                 (40, 103, (31, -1), False), (103, 40, None, True), (64, 129, (1, 1), False), (129, 63, (-1, 0), False),
+                 (1, 33, (15, -1), True)]
+
+
+@pytest.mark.parametrize("kernel", A.KERNELS)
+@pytest.mark.parametrize("problem", BAND_PROBLEMS, ids=str)
+def test_band_restatement_matches_fp64_autograd(kernel, problem):
+    """fp32 I/O: the restatement of a window / varlen problem against fp64 autograd through the masked softmax (rows with no
+    visible key: P = 0)"""
+    nq, nk, window, causal = problem
+    Q, K, V, dO = rand_rect(1, 2, nq, nk, 32, torch.float32, seed=nq + nk)
+    scale = 0.4
+    keep = A.band(nq, nk, causal, window)
+    O, L = stored_forward_band(Q, K, V, keep, scale)
+    got = A.restate(Q, K, V, O, L, dO, causal, scale, kernel, bars=False, window=window)
+    q, k, v = (t.double().requires_grad_(True) for t in (Q, K, V))
+    S = (q @ k.transpose(-1, -2) * scale).masked_fill(~keep, -math.inf)
+    vis = keep.any(-1, keepdim=True)
+    o = torch.where(vis, torch.softmax(S.masked_fill(~vis, 0.0), -1), 0.0) @ v
+    truth = torch.autograd.grad(o, (q, k, v), dO.double())
+    for name, a, t in zip(("dQ", "dK", "dV"), got, truth):
+        assert a.dtype == torch.float32 and a.shape == t.shape
+        assert (a.double() - t).abs().max() <= 1e-5 * t.abs().max() + 1e-12, name   # (+: dQ of a one-key band is 0)
+    empty = ~vis[:, 0]
+    assert (got[0][:, :, empty] == 0).all()            # keyless rows: dQ exactly 0, not 0 * inf
+    unseen = ~keep.any(0)
+    assert (got[1][:, :, unseen] == 0).all() and (got[2][:, :, unseen] == 0).all()
+    same = A.restate(Q, K, V, O, L, dO, causal, scale, kernel, bars=False, keep=keep)
+    assert all(torch.equal(a, b) for a, b in zip(got[:3], same[:3]))
+
+
+# (shape (B, H, nq, nk, d), dtype, window, causal, scale, spread, kernel)
+BAND_BAR_CASES = [((1, 2, 257, 257, 64), torch.bfloat16, (31, 33), False, 0.3, 0.5, "mfma16"),
+                  ((1, 2, 512, 512, 128), torch.bfloat16, (128, 128), False, 1.0, 1.0, "mfma16"),
+                  ((1, 2, 300, 300, 64), torch.float16, (-1, 95), False, 0.3, 0.5, "generic"),
+                  ((1, 2, 129, 129, 64), torch.float16, (16, 0), True, 0.125, 0.5, "mfma16"),
+                  ((1, 2, 130, 197, 64), torch.bfloat16, (63, 1), False, 0.3, 0.5, "mfma16"),      # varlen: N_k - N_q = 67
+                  ((1, 2, 200, 137, 128), torch.float16, None, True, 0.3, 0.5, "mfma16"),          # 63 keyless rows
+                  ((1, 2, 161, 96, 64), torch.bfloat16, (-1, 40), False, 0.3, 0.5, "generic")]
+
+
+def _band_case(case):
+    (B, H, nq, nk, d), dtype, window, causal, scale, spread, kernel = case
+    Q, K, V, dO = rand_rect(B, H, nq, nk, d, dtype, seed=nq + 3 * nk, spread=spread)
+    O, L = stored_forward_band(Q, K, V, A.band(nq, nk, causal, window), scale)
+    return Q, K, V, O, L, dO
+
+
+def _band_id(c):
+    return f"{c[6]}-{str(c[1])[6:]}-{c[0][2]}x{c[0][3]}-w{c[2]}-causal{int(c[3])}"
+
+
+@pytest.mark.parametrize("case", BAND_BAR_CASES, ids=_band_id)
+def test_fp32_arithmetic_passes_the_bars_on_window_and_varlen(case):
+    _, dtype, window, causal, scale, _, kernel = case
+    Q, K, V, O, L, dO = _band_case(case)
+    ref = A.restate(Q, K, V, O, L, dO, causal, scale, kernel, window=window)
+    assert all(torch.isfinite(t).all() for t in ref.tol)
+    emu = A.restate(Q, K, V, O, L, dO, causal, scale, kernel, bars=False, acc=torch.float32, window=window)
+    A.assert_close(emu[:3], ref, case)
+
+
+def test_planted_errors_fail_the_bars_on_window_and_varlen():
+    """every mask plant (an edge one key out, top-left alignment) is caught on at least one window / varlen case, and
+    every one of the dense plants on at least one windowed case"""
+    caught = {p: [] for p in A.PLANTS + A.MASK_PLANTS}
+    for case in BAND_BAR_CASES:
+        _, dtype, window, causal, scale, _, kernel = case
+        Q, K, V, O, L, dO = _band_case(case)
+        ref = A.restate(Q, K, V, O, L, dO, causal, scale, kernel, window=window)
+        for p in caught:
+            bad = A.restate(Q, K, V, O, L, dO, causal, scale, kernel, plant=p, bars=False, window=window)
+            if not all(ok for *_, ok in A.compare(bad[:3], ref)):
+                caught[p].append(_band_id(case))
+    for p, by in caught.items():
+        print(f"{p}: caught by {by}")
+    assert all(caught.values()), {p: by for p, by in caught.items() if not by}
+    windowed = {_band_id(c) for c in BAND_BAR_CASES if c[2] is not None and c[0][2] == c[0][3]}
+    assert all(set(caught[p]) & windowed for p in A.PLANTS + ("right_plus_one", "left_minus_one")), caught
+    assert not set(caught["top_left"]) & windowed            # (top-left = bottom-right when N_q = N_k)

@@ -9,6 +9,7 @@ import torch
 import flash_attention_dlrs_amd as fa
 from flash_attention_dlrs_amd import _lib
 from flash_attention_dlrs_amd.flash_attention_torch import FlashAttentionVarlen, convert_triton_dtype
+from oracle import fa2_bwd_arith
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -30,18 +31,8 @@ def cu_of(lengths):
 
 
 def band(nq, nk, causal, window):
-    """(nq, nk) visible pairs of one sequence: bottom-right aligned (include/fa2_fwd.h)."""
-    left, right = (-1, -1) if window is None else window
-    if causal:
-        right = 0
-    i = torch.arange(nq, device=DEV).view(nq, 1) + (nk - nq)
-    j = torch.arange(nk, device=DEV).view(1, nk)
-    m = torch.ones(nq, nk, dtype=torch.bool, device=DEV)
-    if left >= 0:
-        m &= j >= i - left
-    if right >= 0:
-        m &= j <= i + right
-    return m
+    """(nq, nk) visible pairs of one sequence: bottom-right aligned (include/fa2_fwd.h; the rule is oracle.fa2_bwd_arith.band)."""
+    return fa2_bwd_arith.band(nq, nk, causal, window, DEV)
 
 
 def varlen_reference(Q, K, V, lq, lk, causal, scale, window, seqs=None):
