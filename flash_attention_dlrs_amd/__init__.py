@@ -6,10 +6,10 @@ a hand-written HIP/CDNA4 kernel library.  There is no CPU fallback: without the 
 non-GPU tensors, calls fail loudly.
 """
 from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttentionDeterministic, FlashAttentionVarlen,
-                                    convert_triton_dtype, varlen_mask)
+                                    convert_triton_dtype, gqa_kv_heads, varlen_mask)
 from .flash_attention_wrappers import (flash_attention_backward, flash_attention_forward, flash_attention_varlen_backward,
                                        flash_attention_varlen_forward)
 
 __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
            "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
-           "flash_attention_varlen_backward", "varlen_mask"]
+           "flash_attention_varlen_backward", "varlen_mask", "gqa_kv_heads"]

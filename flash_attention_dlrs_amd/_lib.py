@@ -50,9 +50,11 @@ if os.path.basename(LIB_PATH) in ("libfa2_hip_exp.so", "libfa2_hip_abl.so"):
 
 # Every symbol include/fa2_fwd.h declares (tests/test_abi.py checks the export list against the header).
 SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", "fa2_query_tile_scaled", "fa2_version", "fa2_last_error",
-           "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant")
+           "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant",
+           "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant")
 # ... and include/fa2_bwd.h
-BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant")
+BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
+               "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
 BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
 
 _lib = None
@@ -115,6 +117,27 @@ def lib():
         l.fa2_bwd_window.argtypes = bwd_win
         l.fa2_bwd_window_variant.restype = ctypes.c_int
         l.fa2_bwd_window_variant.argtypes = bwd_win + [ctypes.c_int32]
+        # grouped-query attention: H_kv after H (dense: the window sides after scale as well)
+        gqa = common[:10] + [ctypes.c_int32] * 7 + [ctypes.c_float, ctypes.c_int32, ctypes.c_int32, vp]
+        l.fa2_fwd_gqa.restype = ctypes.c_int
+        l.fa2_fwd_gqa.argtypes = gqa
+        l.fa2_fwd_gqa_variant.restype = ctypes.c_int
+        l.fa2_fwd_gqa_variant.argtypes = gqa + [ctypes.c_int32]
+        bgqa = bwd[:19] + [ctypes.c_int32] * 7 + [ctypes.c_float, ctypes.c_int32, ctypes.c_int32, vp]
+        l.fa2_bwd_gqa.restype = ctypes.c_int
+        l.fa2_bwd_gqa.argtypes = bgqa
+        l.fa2_bwd_gqa_variant.restype = ctypes.c_int
+        l.fa2_bwd_gqa_variant.argtypes = bgqa + [ctypes.c_int32]
+        vlg = vl[:12] + [ctypes.c_int32] * 10 + vl[21:]
+        l.fa2_fwd_varlen_gqa.restype = ctypes.c_int
+        l.fa2_fwd_varlen_gqa.argtypes = vlg
+        l.fa2_fwd_varlen_gqa_variant.restype = ctypes.c_int
+        l.fa2_fwd_varlen_gqa_variant.argtypes = vlg + [ctypes.c_int32]
+        bvlg = bvl[:21] + [ctypes.c_int32] * 10 + bvl[30:]
+        l.fa2_bwd_varlen_gqa.restype = ctypes.c_int
+        l.fa2_bwd_varlen_gqa.argtypes = bvlg
+        l.fa2_bwd_varlen_gqa_variant.restype = ctypes.c_int
+        l.fa2_bwd_varlen_gqa_variant.argtypes = bvlg + [ctypes.c_int32]
         l.bwd_variant_addr = ctypes.CFUNCTYPE(ctypes.c_int, *([vp] * 19 + [ctypes.c_int32] * 6 + [ctypes.c_float, vp, ctypes.c_int32]))(
             ("fa2_bwd_variant", l))
         l.fa2_version.restype = ctypes.c_char_p
@@ -173,6 +196,17 @@ def fa2_fwd(Q, K, V, O, L, dtype_enum, causal=False, scale=1.0, variant=VARIANT_
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N, d = Q.shape
     LB, LH = L.stride(0), L.stride(1)
+    if K.shape[1] != H:  # grouped-query: K and V with H_kv heads (fa2_fwd_gqa_variant)
+        wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+        with torch.cuda.device(Q.device):
+            rc = lib().fa2_fwd_gqa_variant(
+                Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+                _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((LB, LH)),
+                B, H, K.shape[1], N, d, int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index),
+                int(variant))
+        if rc != 0:
+            _raise(rc)
+        return
     if window is not None:
         wl, wr = (int(w) for w in window)
         with torch.cuda.device(Q.device):
@@ -212,6 +246,18 @@ def fa2_bwd(Q, K, V, O, dO, L, dQ, dK, dV, D, dtype_enum, causal=False, scale=1.
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N, d = Q.shape
     assert D.is_contiguous() and D.numel() == 2 * B * H * N
+    if K.shape[1] != H:  # grouped-query: K, V, dK, dV with H_kv heads (fa2_bwd_gqa_variant)
+        wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+        with torch.cuda.device(Q.device):
+            rc = lib().fa2_bwd_gqa_variant(
+                Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(),
+                dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), D.data_ptr(),
+                *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), _i64((L.stride(0), L.stride(1))),
+                B, H, K.shape[1], N, d, int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index),
+                int(variant))
+        if rc != 0:
+            _raise(rc)
+        return
     if window is not None:
         wl, wr = (int(w) for w in window)
         with torch.cuda.device(Q.device):
@@ -249,6 +295,16 @@ def fa2_fwd_varlen(Q, K, V, O, L, cu_q, cu_k, max_q, max_k, dtype_enum, causal=F
     device.  window = (left, right) raw sides (-1 unbounded) or None."""
     total_q, H, d = Q.shape
     wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    if K.shape[1] != H:  # grouped-query: K and V (total_k, H_kv, d)
+        with torch.cuda.device(Q.device):
+            rc = lib().fa2_fwd_varlen_gqa_variant(
+                Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+                _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
+                cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, K.shape[1], d, int(max_q), int(max_k), total_q,
+                K.shape[0], int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+        if rc != 0:
+            _raise(rc)
+        return
     with torch.cuda.device(Q.device):
         rc = lib().fa2_fwd_varlen_variant(
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
@@ -266,6 +322,17 @@ def fa2_bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_q, cu_k, max_q, max_k, d
     total_q, H, d = Q.shape
     assert D.is_contiguous() and D.numel() == 2 * H * total_q
     wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    if K.shape[1] != H:  # grouped-query: K, V, dK, dV (total_k, H_kv, d)
+        with torch.cuda.device(Q.device):
+            rc = lib().fa2_bwd_varlen_gqa_variant(
+                Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(),
+                dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), D.data_ptr(),
+                *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), L.stride(0),
+                cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, K.shape[1], d, int(max_q), int(max_k), total_q,
+                K.shape[0], int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+        if rc != 0:
+            _raise(rc)
+        return
     with torch.cuda.device(Q.device):
         rc = lib().fa2_bwd_varlen_variant(
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(),

@@ -354,6 +354,19 @@ int fa2_window_normalise(int32_t N, int32_t causal, int32_t wl, int32_t wr, int3
     return FA2_OK;
 }
 
+// H_kv must divide H (fa2_fwd_gqa / fa2_fwd_varlen_gqa and their backward twins): FA2_ERR_BAD_ARG before any launch.
+int fa2_check_gqa(int32_t H, int32_t H_kv) {
+    if (H_kv < 1) {
+        fa2_set_error("H_kv must be >= 1 (got H_kv=%d)", H_kv);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (H >= 1 && H % H_kv != 0) {
+        fa2_set_error("H_kv must divide H (got H=%d, H_kv=%d)", H, H_kv);
+        return FA2_ERR_BAD_ARG;
+    }
+    return FA2_OK;
+}
+
 namespace {
 int fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
                const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t N,
@@ -382,7 +395,7 @@ int fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, co
                const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
                const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k,
                int32_t total_q, int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr,
-               void *hip_stream, int32_t variant) {
+               void *hip_stream, int32_t variant, int32_t gqa = 1) {
     const void *ptrs[9] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides};
     const char *names[9] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides"};
     for (int t = 0; t < 9; ++t)
@@ -445,6 +458,16 @@ int fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, co
             variant = FA2_VARIANT_GENERIC;
         }
     }
+    if (gqa > 1) {  // grouped-query: K and V carry H / gqa heads
+        switch (variant) {
+        case FA2_VARIANT_GENERIC: return fa2_launch_generic_varlen_gqa(p, gqa);
+        case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_varlen_gqa(p, 8, gqa);
+        case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_varlen_gqa(p, 4, gqa);
+        default:
+            fa2_set_error("kernel variant %d has no varlen GQA form (generic, mfma16d and mfma16d_w4 do)", variant);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    }
     switch (variant) {
     case FA2_VARIANT_GENERIC: return fa2_launch_generic_varlen(p);
     case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_varlen(p, 8);
@@ -454,9 +477,129 @@ int fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, co
         return FA2_ERR_UNSUPPORTED;
     }
 }
+
+// Grouped-query attention, dense layout (fa2_fwd_gqa).  H_kv == H is fa2_fwd_window itself.  A mergeable layout -- B == 1, or the
+// batch strides of Q, O, L a multiple H of their head strides and those of K, V a multiple H_kv -- is the MHA problem of
+// B' = B * H_kv batches of g = H / H_kv heads each sharing one K / V head (head stride 0): every kernel of the dense and windowed
+// tables runs it unchanged, and the table sees the same B * H.  Any other layout runs the windowed GQA forms, a plain or causal
+// problem as the full band.
+int fwd_gqa(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
+            const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv,
+            int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr, void *hip_stream,
+            int32_t variant) {
+    int rc = fa2_check_gqa(H, H_kv);
+    if (rc != FA2_OK) return rc;
+    if (H_kv == H)
+        return fwd_window(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal,
+                          scale, wl, wr, hip_stream, variant);
+    int32_t c = causal, l = 0, r = 0, windowed = 0;
+    if (N >= 1) {  // (N < 1 is reported by validate())
+        rc = fa2_window_normalise(N, causal, wl, wr, &c, &l, &r, &windowed);
+        if (rc != FA2_OK) return rc;
+    } else if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, c,
+                                scale, hip_stream);
+    rc = validate(p);
+    if (rc != FA2_OK) return rc;
+    const int g = H / H_kv;
+    if (H_kv == 1) {  // (a size-1 head dimension may carry any stride -- torch leaves it free: only the batch stride is read)
+        p.ks[1] = p.ks[0];
+        p.vs[1] = p.vs[0];
+    }
+    bool mergeable = B == 1 || (p.qs[0] == (int64_t)H * p.qs[1] && p.os[0] == (int64_t)H * p.os[1] &&
+                                p.ls[0] == (int64_t)H * p.ls[1] && p.ks[0] == (int64_t)H_kv * p.ks[1] &&
+                                p.vs[0] == (int64_t)H_kv * p.vs[1]);
+    if (mergeable && (int64_t)B * H_kv > 65535) {
+        // the merged problem has B * H_kv batches: the generic kernel's grid takes at most 65535 of them (grid y), so a problem
+        // that would run there stays unmerged and runs the GQA form, whose grid holds the B the caller passed
+        Fa2Problem m = p;
+        m.B = (int64_t)B * H_kv > 0x7fffffff ? 0x7fffffff : B * H_kv;
+        m.H = g;
+        if (windowed) {
+            m.causal = 0;
+            m.wl = l;
+            m.wr = r;
+        }
+        const int v = variant != FA2_VARIANT_AUTO ? variant : (windowed ? pick_window_variant(m) : pick_variant(m));
+        if (v == FA2_VARIANT_GENERIC || (int64_t)B * H_kv > 0x7fffffff) mergeable = false;
+    }
+    if (mergeable) {
+        Fa2Problem m = p;
+        m.B = B * H_kv;  // (<= B * H)
+        m.H = g;
+        m.qs[0] = g * p.qs[1];
+        m.os[0] = g * p.os[1];
+        m.ls[0] = g * p.ls[1];
+        m.ks[0] = p.ks[1];
+        m.ks[1] = 0;
+        m.vs[0] = p.vs[1];
+        m.vs[1] = 0;
+        if (!windowed) return run(m, variant);
+        m.causal = 0;
+        m.wl = l;
+        m.wr = r;
+        return run_window(m, variant);
+    }
+    p.causal = 0;  // the band carries the mask: (N - 1, N - 1) plain, (N - 1, 0) causal
+    p.wl = l;
+    p.wr = r;
+    if (variant == FA2_VARIANT_AUTO) variant = pick_window_variant(p);
+    switch (variant) {
+    case FA2_VARIANT_GENERIC: return fa2_launch_generic_window_gqa(p, g);
+    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_window_gqa(p, 8, g);
+    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_window_gqa(p, 4, g);
+    default:
+        fa2_set_error("kernel variant %d has no GQA form for this layout (generic, mfma16d and mfma16d_w4 do; a layout with batch "
+                      "strides H x the head strides takes every variant)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
 }  // namespace
 
 extern "C" {
+
+int fa2_fwd_gqa(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
+                const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H,
+                int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                int32_t window_right, void *hip_stream) {
+    return fwd_gqa(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, H_kv, N, d, dtype_enum, causal, scale,
+                   window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_gqa_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                        const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                        const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum,
+                        int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                        int32_t variant) {
+    return fwd_gqa(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, H_kv, N, d, dtype_enum, causal, scale,
+                   window_left, window_right, hip_stream, variant);
+}
+
+int fa2_fwd_varlen_gqa(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                       const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride,
+                       const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t H_kv, int32_t d,
+                       int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
+                       int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fa2_fwd_varlen_gqa_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q,
+                                      cu_seqlens_k, B, H, H_kv, d, max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal,
+                                      scale, window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                               const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                               int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                               int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                               int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                               int32_t window_right, void *hip_stream, int32_t variant) {
+    const int rc = fa2_check_gqa(H, H_kv);
+    if (rc != FA2_OK) return rc;
+    return fwd_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d,
+                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
+                      variant, H >= 1 ? H / H_kv : 1);
+}
 
 int fa2_fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
                    const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride,

@@ -117,7 +117,7 @@ int bwd_window(Fa2BwdProblem p, int32_t wl, int32_t wr, int variant) {
 int bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ, void *dK, void *dV,
                void *D, const int64_t *const st3[8], int64_t l_head_stride, const int32_t *cu_q, const int32_t *cu_k, int32_t B,
                int32_t H, int32_t d, int32_t max_q, int32_t max_k, int32_t total_q, int32_t total_k, int32_t dtype, int32_t causal,
-               float scale, int32_t wl, int32_t wr, void *stream, int variant) {
+               float scale, int32_t wl, int32_t wr, void *stream, int variant, int gqa = 1) {
     const char *snames[8] = {"q_strides", "k_strides", "v_strides", "o_strides", "do_strides", "dq_strides", "dk_strides", "dv_strides"};
     for (int t = 0; t < 8; ++t)
         if (!st3[t]) {
@@ -175,6 +175,15 @@ int bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const
     p.max_q = max_q; p.max_k = max_k; p.total_q = total_q; p.total_k = total_k;
     // (fa2_bwd_mfma16_supports judges the 32-bit offsets on N = the longer max_seqlen: they span one sequence)
     if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
+    if (gqa > 1) {  // grouped-query: K, V, dK, dV carry H / gqa heads
+        switch (variant) {
+        case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_varlen_gqa(p, gqa);
+        case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_varlen_gqa(p, gqa);
+        default:
+            fa2_set_error("backward kernel variant %d has no varlen GQA form (generic and mfma16 do)", variant);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    }
     switch (variant) {
     case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_varlen(p);
     case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_varlen(p);
@@ -184,9 +193,92 @@ int bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const
     }
 }
 
+// Grouped-query backward, dense layout (fa2_bwd_gqa).  H_kv == H is fa2_bwd_window itself.  Otherwise the windowed GQA forms, with a
+// plain or causal problem as the full band (its arithmetic is the plain kernels': the same sweep, the same masks), sum dK / dV of
+// each KV head over its g query heads inside one workgroup.
+int bwd_gqa(Fa2BwdProblem p, int32_t H_kv, int32_t wl, int32_t wr, int variant) {
+    int rc = fa2_check_gqa(p.H, H_kv);
+    if (rc != FA2_OK) return rc;
+    if (H_kv == p.H) return bwd_window(p, wl, wr, variant);
+    int32_t c = p.causal, l = 0, r = 0, windowed = 0;
+    if (p.N >= 1) {  // (N < 1 is reported by validate())
+        rc = fa2_window_normalise(p.N, p.causal, wl, wr, &c, &l, &r, &windowed);
+        if (rc != FA2_OK) return rc;
+    } else if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    rc = validate(p);
+    if (rc != FA2_OK) return rc;
+    p.causal = 0;  // the band carries the mask: (N - 1, N - 1) plain, (N - 1, 0) causal
+    p.wl = l;
+    p.wr = r;
+    const int g = p.H / H_kv;
+    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
+    switch (variant) {
+    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_window_gqa(p, g);
+    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_window_gqa(p, g);
+    default:
+        fa2_set_error("backward kernel variant %d has no GQA form (generic and mfma16 do)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int fa2_bwd_gqa(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ, void *dK,
+                void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                const int64_t o_strides[4], const int64_t do_strides[4], const int64_t dq_strides[4], const int64_t dk_strides[4],
+                const int64_t dv_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d,
+                int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return bwd_gqa(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                        dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
+                   H_kv, window_left, window_right, FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_gqa_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                        void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+                        const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+                        const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+                        const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum,
+                        int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                        int32_t variant) {
+    return bwd_gqa(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                        dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
+                   H_kv, window_left, window_right, variant);
+}
+
+int fa2_bwd_varlen_gqa(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                       void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                       const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                       const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                       int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                       int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                       int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                       void *hip_stream) {
+    return fa2_bwd_varlen_gqa_variant(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides,
+                                      dq_strides, dk_strides, dv_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, H_kv, d,
+                                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left,
+                                      window_right, hip_stream, FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                               void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                               const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                               const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                               int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B,
+                               int32_t H, int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                               int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                               int32_t window_right, void *hip_stream, int32_t variant) {
+    const int rc = fa2_check_gqa(H, H_kv);
+    if (rc != FA2_OK) return rc;
+    const int64_t *const st[8] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
+    return bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, st, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q,
+                      max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream, variant,
+                      H >= 1 ? H / H_kv : 1);
+}
 
 int fa2_bwd(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
             void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],

@@ -26,6 +26,12 @@ int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma16_window(const Fa2BwdProblem &p);
 int fa2_bwd_launch_generic_varlen(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma16_varlen(const Fa2BwdProblem &p);
+// Grouped-query attention (fa2_bwd_gqa, fa2_bwd_varlen_gqa): K, V, dK, dV have p.H / gqa heads; dK / dV summed over each group in
+// the kernel (a dense problem without a window runs the windowed form as the full band)
+int fa2_bwd_launch_generic_window_gqa(const Fa2BwdProblem &p, int gqa);
+int fa2_bwd_launch_mfma16_window_gqa(const Fa2BwdProblem &p, int gqa);
+int fa2_bwd_launch_generic_varlen_gqa(const Fa2BwdProblem &p, int gqa);
+int fa2_bwd_launch_mfma16_varlen_gqa(const Fa2BwdProblem &p, int gqa);
 bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma32(const Fa2BwdProblem &p);
 bool fa2_bwd_mfma32_supports(const Fa2BwdProblem &p);

@@ -27,7 +27,17 @@
 // sequence's key block and sweeps only that sequence's queries, MODE 1 the reverse; per-sequence extents, bottom-right shifted band
 // (fa2_varlen_band).  D and the row statistic are laid out [H][total_q].  A row without a visible key (L = +inf) has P = 0: its dQ
 // is 0 and its statistic stays +inf (not inf + log2(0)).
-#if defined(FA2_BWD_GENERIC_VARLEN)
+// FA2_BWD_GENERIC_GQA (fa2_bwd_generic_wg.hip, fa2_bwd_generic_vg.hip, on top of the windowed or varlen form): grouped-query
+// attention -- K, V, dK, dV have H / gqa heads.  MODE 1 (grid z = query head h) reads KV head h / gqa; MODE 0 (grid z = KV head k)
+// sweeps the queries of its g query heads k * gqa ... k * gqa + gqa - 1 in turn into the same accumulators and stores once: the
+// group sum of dK / dV without atomics, in a fixed order.
+#if defined(FA2_BWD_GENERIC_GQA) && defined(FA2_BWD_GENERIC_VARLEN)
+#define bwd_main_kernel bwd_main_varlen_gqa_kernel
+#define bwd_D_kernel bwd_D_varlen_gqa_kernel
+#elif defined(FA2_BWD_GENERIC_GQA)
+#define bwd_main_kernel bwd_main_window_gqa_kernel
+#define bwd_D_kernel bwd_D_window_gqa_kernel
+#elif defined(FA2_BWD_GENERIC_VARLEN)
 #define bwd_main_kernel bwd_main_varlen_kernel
 #define bwd_D_kernel bwd_D_varlen_kernel
 #elif defined(FA2_BWD_GENERIC_WINDOW)
@@ -58,6 +68,9 @@ struct GArgs {
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
 #else
     int H, N, d, causal, TB;
+#endif
+#ifdef FA2_BWD_GENERIC_GQA
+    int gqa;  // query heads per KV head
 #endif
     double c_log2e, scale;
 };
@@ -111,12 +124,25 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
     fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
     const int NO = MODE == 0 ? NK : NQ, NS = MODE == 0 ? NQ : NK;
     if (blk * TB >= NO) return;  // (whole workgroup, before any barrier)
+#ifdef FA2_BWD_GENERIC_GQA
+    const int hk = MODE == 0 ? h : h / a.gqa;  // (MODE 0: grid z is the KV head; its query heads are swept below)
+    const int64_t qb = (int64_t)qst * a.qs[2] + h * a.qs[1], kb = (int64_t)kst * a.ks[2] + hk * a.ks[1];
+    const int64_t vb = (int64_t)kst * a.vs[2] + hk * a.vs[1];
+#else
     const int64_t qb = (int64_t)qst * a.qs[2] + h * a.qs[1], kb = (int64_t)kst * a.ks[2] + h * a.ks[1];
     const int64_t vb = (int64_t)kst * a.vs[2] + h * a.vs[1];
+#endif
     const int64_t gb = (int64_t)qst * a.dos[2] + h * a.dos[1];
     const int64_t lb = h * a.ls[1] + qst;
     const long long db = (long long)h * a.total_q + qst;
     A *Lc = (A *)a.D + (long long)a.H * a.total_q + db;
+#elif defined(FA2_BWD_GENERIC_GQA)
+    const int hk = MODE == 0 ? h : h / a.gqa;  // (MODE 0: grid z is the KV head; its query heads are swept below)
+    const int64_t qb = b * a.qs[0] + h * a.qs[1], kb = b * a.ks[0] + hk * a.ks[1], vb = b * a.vs[0] + hk * a.vs[1];
+    const int64_t gb = b * a.dos[0] + h * a.dos[1];
+    const int64_t lb = b * a.ls[0] + h * a.ls[1];
+    const long long db = ((long long)b * a.H + h) * N;
+    A *Lc = (A *)a.D + (long long)gridDim.y * a.H * N + db;
 #else
     const int64_t qb = b * a.qs[0] + h * a.qs[1], kb = b * a.ks[0] + h * a.ks[1], vb = b * a.vs[0] + h * a.vs[1];
     const int64_t gb = b * a.dos[0] + h * a.dos[1];
@@ -196,6 +222,21 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
     const int sw_begin = (MODE == 0 && a.causal) ? own_row0 / TB : 0;
     const int sw_end = (MODE == 1 && a.causal) ? ((own_row0 + TB - 1 < N ? own_row0 + TB - 1 : N - 1) / TB + 1) : nsw;
 #endif
+#ifdef FA2_BWD_GENERIC_GQA
+    // MODE 0: the g query heads of this KV head, in order, into the same accumulators (MODE 1: its own head, once)
+    const int ngq = MODE == 0 ? a.gqa : 1;
+    for (int gq = 0; gq < ngq; ++gq) {
+    const int hq = MODE == 0 ? h * a.gqa + gq : h;
+#ifdef FA2_BWD_GENERIC_VARLEN
+    const int64_t qb = (int64_t)qst * a.qs[2] + hq * a.qs[1], gb = (int64_t)qst * a.dos[2] + hq * a.dos[1];
+    const long long db = (long long)hq * a.total_q + qst;
+    A *Lc = (A *)a.D + (long long)a.H * a.total_q + db;
+#else
+    const int64_t qb = b * a.qs[0] + hq * a.qs[1], gb = b * a.dos[0] + hq * a.dos[1];
+    const long long db = ((long long)b * a.H + hq) * N;
+    A *Lc = (A *)a.D + (long long)gridDim.y * a.H * N + db;
+#endif
+#endif
     for (int sw = sw_begin; sw < sw_end; ++sw) {
         const int sw_row0 = sw * TB;
 #ifdef FA2_BWD_GENERIC_VARLEN
@@ -271,6 +312,9 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         }
         __syncthreads();
     }
+#ifdef FA2_BWD_GENERIC_GQA
+    }  // gq
+#endif
 #ifdef FA2_BWD_GENERIC_VARLEN
     for (int e = tid; e < TB * d; e += 256) {
         const int o = e / d, x = e % d, row = own_row0 + o;
@@ -315,13 +359,24 @@ template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
     const int gx = ((p.max_q > p.max_k ? p.max_q : p.max_k) + TB - 1) / TB;
     if (gx == 0) return FA2_OK;
     const dim3 grid(gx, p.B, p.H);
+#ifdef FA2_BWD_GENERIC_GQA
+    const dim3 grid0(gx, p.B, p.H / a.gqa);  // MODE 0: one workgroup per KV head
+#endif
 #else
     const long long rows = (long long)p.B * p.H * p.N;
     hipLaunchKernelGGL((bwd_D_kernel<E>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, p.stream, a, rows);
     const dim3 grid((p.N + TB - 1) / TB, p.B, p.H);
+#ifdef FA2_BWD_GENERIC_GQA
+    const dim3 grid0((p.N + TB - 1) / TB, p.B, p.H / a.gqa);  // MODE 0: one workgroup per KV head
 #endif
+#endif
+#ifdef FA2_BWD_GENERIC_GQA
+    hipLaunchKernelGGL((bwd_main_kernel<E, 1>), grid, dim3(256), smem, p.stream, a);  // first: leaves Lc for MODE 0
+    hipLaunchKernelGGL((bwd_main_kernel<E, 0>), grid0, dim3(256), smem, p.stream, a);
+#else
     hipLaunchKernelGGL((bwd_main_kernel<E, 1>), grid, dim3(256), smem, p.stream, a);  // first: leaves Lc for MODE 0
     hipLaunchKernelGGL((bwd_main_kernel<E, 0>), grid, dim3(256), smem, p.stream, a);
+#endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("generic backward launch failed: %s", hipGetErrorString(e));
@@ -332,7 +387,11 @@ template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
 
 }  // namespace
 
-#if defined(FA2_BWD_GENERIC_VARLEN)
+#if defined(FA2_BWD_GENERIC_GQA) && defined(FA2_BWD_GENERIC_VARLEN)
+int fa2_bwd_launch_generic_varlen_gqa(const Fa2BwdProblem &p, int gqa) {
+#elif defined(FA2_BWD_GENERIC_GQA)
+int fa2_bwd_launch_generic_window_gqa(const Fa2BwdProblem &p, int gqa) {
+#elif defined(FA2_BWD_GENERIC_VARLEN)
 int fa2_bwd_launch_generic_varlen(const Fa2BwdProblem &p) {
 #elif defined(FA2_BWD_GENERIC_WINDOW)
 int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p) {
@@ -361,6 +420,9 @@ int fa2_bwd_launch_generic(const Fa2BwdProblem &p) {
 #endif
     a.c_log2e = (double)p.scale * FA2_LOG2E;
     a.scale = (double)p.scale;
+#ifdef FA2_BWD_GENERIC_GQA
+    a.gqa = gqa;
+#endif
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);
     case FA2_DTYPE_F16: return launch_e<ElemF16>(p, a);

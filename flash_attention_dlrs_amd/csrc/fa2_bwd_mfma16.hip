@@ -36,7 +36,18 @@
 // extent NO, the swept extent NS and the bottom-right shifted band (fa2_varlen_band); base pointers in 64 bits from the
 // sequence starts, D and the row statistic laid out [H][total_q].  A query without a visible key (L = +inf) keeps the row
 // statistic +inf and gets dQ = 0.
-#if defined(FA2_BWD_MFMA16_VARLEN)
+// FA2_BWD_MFMA16_GQA (fa2_bwd_mfma16_wg.hip, fa2_bwd_mfma16_vg.hip, on top of the windowed or varlen form): grouped-query attention
+// -- K, V, dK, dV have H / gqa heads.  MODE 1 keeps its grid over (b, query head) and reads K, V at KV head hh / gqa; MODE 0 runs
+// over (b, KV head, key block) and sweeps the queries of the group's g query heads one after the other (Q, dO, L, D and the row
+// statistic of that head) into the same dK^T / dV^T accumulators, storing once at the end: the group sum without atomics or
+// workspace, in a fixed order.
+#if defined(FA2_BWD_MFMA16_GQA) && defined(FA2_BWD_MFMA16_VARLEN)
+#define bwd_mfma16_kernel bwd_mfma16_varlen_gqa_kernel
+#define bwd_D_kernel bwd_D_varlen_gqa_kernel
+#elif defined(FA2_BWD_MFMA16_GQA)
+#define bwd_mfma16_kernel bwd_mfma16_window_gqa_kernel
+#define bwd_D_kernel bwd_D_window_gqa_kernel
+#elif defined(FA2_BWD_MFMA16_VARLEN)
 #define bwd_mfma16_kernel bwd_mfma16_varlen_kernel
 #define bwd_D_kernel bwd_D_varlen_kernel
 #elif defined(FA2_BWD_MFMA16_WINDOW)
@@ -94,6 +105,9 @@ struct BArgs {
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise); causal is 0
 #else
     int B, H, N, causal;
+#endif
+#ifdef FA2_BWD_MFMA16_GQA
+    int gqa;  // query heads per KV head
 #endif
     float c_log2e, scale;
 };
@@ -190,7 +204,12 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     const int N = a.N;
 #endif
 
+#ifdef FA2_BWD_MFMA16_GQA
+    const int HO = MODE == 0 ? a.H / a.gqa : a.H;  // heads of the grid: MODE 0 KV heads, MODE 1 query heads
+    const int nblk = (N + BO - 1) / BO, nbh = a.B * HO;
+#else
     const int nblk = (N + BO - 1) / BO, nbh = a.B * a.H;
+#endif
     int bh, blk;
     {
         const int bid = blockIdx.x;
@@ -204,7 +223,12 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         }
     }
     if (MODE == 1 && (a.causal & 1)) blk = nblk - 1 - blk;  // causal: the last query blocks sweep the most keys -- start them first
+#ifdef FA2_BWD_MFMA16_GQA
+    const int b = bh / HO, hh = bh - b * HO;                 // hh: MODE 0 the KV head, MODE 1 the query head
+    const int hk = MODE == 0 ? hh : hh / a.gqa;              // the KV head
+#else
     const int b = bh / a.H, hh = bh - b * a.H;
+#endif
 #ifdef FA2_BWD_MFMA16_VARLEN
     fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, qst, NQ);
     fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
@@ -228,14 +252,27 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     // swept tiles T0, T1 and owned fragments f0, f1
 #ifdef FA2_BWD_MFMA16_VARLEN
     const char *Qs = a.Q + (int64_t)qst * a.qs[2] + hh * a.qs[1], *dOs = a.dO + (int64_t)qst * a.dos[2] + hh * a.dos[1];
+#ifdef FA2_BWD_MFMA16_GQA
+    const char *Ks = a.K + (int64_t)kst * a.ks[2] + hk * a.ks[1], *Vs = a.V + (int64_t)kst * a.vs[2] + hk * a.vs[1];
+#else
     const char *Ks = a.K + (int64_t)kst * a.ks[2] + hh * a.ks[1], *Vs = a.V + (int64_t)kst * a.vs[2] + hh * a.vs[1];
+#endif
+#ifndef FA2_BWD_MFMA16_GQA  // (GQA: the swept tiles are set per query head below)
     const char *T0p = MODE == 1 ? Ks : Qs, *T1p = MODE == 1 ? Vs : dOs;
+#endif
     const int64_t t0rs = MODE == 1 ? a.ks[2] : a.qs[2], t1rs = MODE == 1 ? a.vs[2] : a.dos[2];
     const char *F0p = MODE == 1 ? Qs : Ks, *F1p = MODE == 1 ? dOs : Vs;
     const int64_t f0rs = MODE == 1 ? a.qs[2] : a.ks[2], f1rs = MODE == 1 ? a.dos[2] : a.vs[2];
     const T *Lp = (const T *)a.L + hh * a.ls[1] + qst;
     const float *Dp = a.D + (int64_t)hh * a.total_q + qst;
     float *Lc = a.D + (int64_t)a.H * a.total_q + (int64_t)hh * a.total_q + qst;
+#elif defined(FA2_BWD_MFMA16_GQA)  // (the swept tiles T0p, T1p are set per query head below)
+    const int64_t t0rs = MODE == 1 ? a.ks[2] : a.qs[2], t1rs = MODE == 1 ? a.vs[2] : a.dos[2];
+    const char *F0p = (MODE == 1 ? a.Q + b * a.qs[0] + hh * a.qs[1] : a.K + b * a.ks[0] + hk * a.ks[1]);
+    const char *F1p = (MODE == 1 ? a.dO + b * a.dos[0] + hh * a.dos[1] : a.V + b * a.vs[0] + hk * a.vs[1]);
+    const int64_t f0rs = MODE == 1 ? a.qs[2] : a.ks[2], f1rs = MODE == 1 ? a.dos[2] : a.vs[2];
+    const T *Lp = (const T *)a.L + b * a.ls[0] + hh * a.ls[1];
+    const float *Dp = a.D + ((int64_t)b * a.H + hh) * N;
 #else
     const char *T0p = (MODE == 1 ? a.K + b * a.ks[0] + hh * a.ks[1] : a.Q + b * a.qs[0] + hh * a.qs[1]);
     const char *T1p = (MODE == 1 ? a.V + b * a.vs[0] + hh * a.vs[1] : a.dO + b * a.dos[0] + hh * a.dos[1]);
@@ -285,6 +322,28 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
     // prefetch to land.  An explicit wait the compiler can see empties its scoreboard before the loop.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt untouched
 
+#ifdef FA2_BWD_MFMA16_GQA
+    f32x16 acc0[DB];  // dQ^T (MODE 1), dK^T (MODE 0, waves 0..3) or dV^T (MODE 0, waves 4..7): summed over the group
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc0[db][r] = 0.0f;
+    float rsum = 0.0f;  // MODE 1: this lane's share of rowsum(P) of its query
+    const int ngq = MODE == 0 ? a.gqa : 1;
+    for (int gq = 0; gq < ngq; ++gq) {  // MODE 0: the group's query heads in order; MODE 1: its own head, once
+    const int hq = MODE == 0 ? hk * a.gqa + gq : hh;
+#ifdef FA2_BWD_MFMA16_VARLEN
+    const char *Qs = a.Q + (int64_t)qst * a.qs[2] + hq * a.qs[1], *dOs = a.dO + (int64_t)qst * a.dos[2] + hq * a.dos[1];
+    const char *T0p = MODE == 1 ? Ks : Qs, *T1p = MODE == 1 ? Vs : dOs;
+    const float *Dp = a.D + (int64_t)hq * a.total_q + qst;
+    float *Lc = a.D + (int64_t)a.H * a.total_q + (int64_t)hq * a.total_q + qst;
+#else
+    const char *T0p = (MODE == 1 ? a.K + b * a.ks[0] + hk * a.ks[1] : a.Q + b * a.qs[0] + hq * a.qs[1]);
+    const char *T1p = (MODE == 1 ? a.V + b * a.vs[0] + hk * a.vs[1] : a.dO + b * a.dos[0] + hq * a.dos[1]);
+    const float *Dp = a.D + ((int64_t)b * a.H + hq) * N;
+    float *Lc = a.D + (int64_t)a.B * a.H * N + ((int64_t)b * a.H + hq) * N;
+#endif
+#endif
     // swept range (causal: MODE 1 keys <= last owned query; MODE 0 queries >= first owned key)
     const int wg0 = blk * BO;
     int t_begin = 0, t_end = (N + BS - 1) / BS;
@@ -354,6 +413,9 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
                 v_off[u][db] = lds_off<D>(8 * u + 4 * h + qq, 4 * db + 2 * w + (pp >> 1)) + 8 * (pp & 1);
     }
 
+#ifdef FA2_BWD_MFMA16_GQA
+    const float c = a.c_log2e;
+#else
     f32x16 acc0[DB];  // dQ^T (MODE 1), dK^T (MODE 0, waves 0..3) or dV^T (MODE 0, waves 4..7)
 #pragma unroll
     for (int db = 0; db < DB; ++db)
@@ -361,6 +423,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         for (int r = 0; r < 16; ++r) acc0[db][r] = 0.0f;
     const float c = a.c_log2e;
     float rsum = 0.0f;  // MODE 1: this lane's share of rowsum(P) of its query
+#endif
     const bool is_causal = (a.causal & 1) != 0;
 #ifdef FA2_BWD_MFMA16_WINDOW
     {  // MODE 1 sweeps the keys [i0 - wl, i1 + wr], MODE 0 the queries [j0 - wr, j1 + wl]
@@ -623,6 +686,9 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
         if (more) stage_write(cur ^ 1);
         __syncthreads();
     }
+#ifdef FA2_BWD_MFMA16_GQA
+    }  // gq: every sweep ends on a barrier, so the next head's first tile may take either buffer
+#endif
 
     // ---- epilogue: lane (i, h) owns output row `orow`, columns 32db + 8g + 4h .. +3
     float tot = 1.0f;
@@ -635,7 +701,7 @@ __global__ __launch_bounds__(MODE == 0 ? 512 : NWQ * 64, 2) void bwd_mfma16_kern
 #ifdef FA2_BWD_MFMA16_VARLEN
     if (orow < NO) {
         auto store_rows = [&](char *base, const int64_t *st, f32x16 (&acc)[DB], float mul) {
-            char *op = base + (int64_t)(MODE == 1 ? qst : kst) * st[2] + hh * st[1] + (int64_t)orow * st[2] + h * 8;
+            char *op = base + (int64_t)(MODE == 1 ? qst : kst) * st[2] + hh * st[1] + (int64_t)orow * st[2] + h * 8;  // (GQA MODE 0: hh = hk)
 #else
     if (orow < N) {
         auto store_rows = [&](char *base, const int64_t *st, f32x16 (&acc)[DB], float mul) {
@@ -674,7 +740,11 @@ template <typename T, int D> int launch_d(const Fa2BwdProblem &p, const BArgs &a
     // D over every packed token; each mode's grid from its own owned extent (MODE 1: max_q, MODE 0: max_k)
     const long long lanes = (long long)p.H * p.total_q * (D / 8);
     if (lanes > 0) hipLaunchKernelGGL((bwd_D_kernel<T, D>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, p.stream, a);
+#ifdef FA2_BWD_MFMA16_GQA
+    const long long nblkq = (long long)((p.max_q + 127) / 128) * p.B * p.H, nblk = (long long)((p.max_k + 127) / 128) * p.B * (p.H / a.gqa);
+#else
     const long long nblkq = (long long)((p.max_q + 127) / 128) * p.B * p.H, nblk = (long long)((p.max_k + 127) / 128) * p.B * p.H;
+#endif
     if (nblkq > 0x7fffffffLL || nblk > 0x7fffffffLL) {
         fa2_set_error("backward mfma16: grid too large");
         return FA2_ERR_BAD_ARG;
@@ -709,7 +779,12 @@ template <typename T, int D> int launch_d(const Fa2BwdProblem &p, const BArgs &a
         (void)hipFuncSetAttribute((const void *)bwd_mfma16_kernel<T, D, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem0);
         attr_set.mark();
     }
+#ifdef FA2_BWD_MFMA16_GQA
+    const long long nblk0 = (long long)((p.N + 127) / 128) * p.B * (p.H / a.gqa);  // MODE 0: one key block of one KV head
+    hipLaunchKernelGGL((bwd_mfma16_kernel<T, D, 0>), dim3((unsigned)nblk0), dim3(512), smem0, p.stream, a);
+#else
     hipLaunchKernelGGL((bwd_mfma16_kernel<T, D, 0>), dim3((unsigned)nblk), dim3(512), smem0, p.stream, a);
+#endif
 #endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -747,7 +822,11 @@ bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p) {
 }
 
 #endif
-#if defined(FA2_BWD_MFMA16_VARLEN)
+#if defined(FA2_BWD_MFMA16_GQA) && defined(FA2_BWD_MFMA16_VARLEN)
+int fa2_bwd_launch_mfma16_varlen_gqa(const Fa2BwdProblem &p, int gqa) {
+#elif defined(FA2_BWD_MFMA16_GQA)
+int fa2_bwd_launch_mfma16_window_gqa(const Fa2BwdProblem &p, int gqa) {
+#elif defined(FA2_BWD_MFMA16_VARLEN)
 int fa2_bwd_launch_mfma16_varlen(const Fa2BwdProblem &p) {
 #elif defined(FA2_BWD_MFMA16_WINDOW)
 int fa2_bwd_launch_mfma16_window(const Fa2BwdProblem &p) {
@@ -781,8 +860,14 @@ int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p) {
     a.scale = p.scale;
     a.wl = p.wl;
     a.wr = p.wr;
+#ifdef FA2_BWD_MFMA16_GQA
+    if (p.wr == 0) a.causal |= 1;  // a lower band (causal): MODE 1 starts the query blocks that sweep the most keys first
+#endif
 #else
     a.scale = p.scale;
+#endif
+#ifdef FA2_BWD_MFMA16_GQA
+    a.gqa = gqa;
 #endif
     if (p.dtype == FA2_DTYPE_BF16) return p.d == 128 ? launch_d<__bf16, 128>(p, a) : launch_d<__bf16, 64>(p, a);
     return p.d == 128 ? launch_d<_Float16, 128>(p, a) : launch_d<_Float16, 64>(p, a);

@@ -45,11 +45,19 @@ int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves);
 // Variable-length attention (fa2_fwd_varlen): the varlen instantiations, translation units of their own as well.
 int fa2_launch_generic_varlen(const Fa2Problem &p);
 int fa2_launch_mfma16d_varlen(const Fa2Problem &p, int waves);
+// Grouped-query attention (fa2_fwd_gqa, fa2_fwd_varlen_gqa): K and V have p.H / gqa heads, query head h reads KV head h / gqa.  The
+// windowed GQA forms take the dense layouts the host remap cannot merge (a plain or causal problem as the full band).
+int fa2_launch_generic_window_gqa(const Fa2Problem &p, int gqa);
+int fa2_launch_mfma16d_window_gqa(const Fa2Problem &p, int waves, int gqa);
+int fa2_launch_generic_varlen_gqa(const Fa2Problem &p, int gqa);
+int fa2_launch_mfma16d_varlen_gqa(const Fa2Problem &p, int waves, int gqa);
 // Validates and normalises a window (include/fa2_fwd.h): FA2_ERR_BAD_ARG for a side < -1.  On FA2_OK *windowed = 0 means the window
 // removes nothing beyond what plain (*causal_out = 0) or causal (*causal_out = 1) attention removes; *windowed = 1 means the band
 // [i - *wl_out, i + *wr_out] with both sides in [0, N - 1] (N - 1 = unbounded), the causal clamp already applied to *wr_out.
 int fa2_window_normalise(int32_t N, int32_t causal, int32_t wl, int32_t wr, int32_t *causal_out, int32_t *wl_out, int32_t *wr_out,
                          int32_t *windowed);
+// Grouped-query attention: FA2_ERR_BAD_ARG ("H_kv" in the message) unless 1 <= H_kv and H_kv divides H (H < 1 is validate()'s).
+int fa2_check_gqa(int32_t H, int32_t H_kv);
 int fa2_launch_a64(const Fa2Problem &p);  // generated assembly kernel (asm/fa2_a64_gen.py)
 bool fa2_a64_supports(const Fa2Problem &p);
 int fa2_launch_a16(const Fa2Problem &p);  // the same structure on v_mfma_f32_16x16x32 (asm/fa2_a16_gen.py)

@@ -26,7 +26,13 @@
 // FA2_GENERIC_VARLEN (fa2_generic_v.hip, on top of FA2_GENERIC_WINDOW): the variable-length form -- grid (ceil(max_q / 16), B, H),
 // each workgroup reads its sequence's offsets and runs the windowed loop with the sequence's own query and key extents and the
 // bottom-right shifted band (fa2_varlen_band); a row without a visible key gets O = 0, L = +inf.
-#if defined(FA2_GENERIC_VARLEN)
+// FA2_GENERIC_GQA (fa2_generic_wg.hip, fa2_generic_vg.hip, on top of the windowed or varlen form): grouped-query attention -- K and V
+// have H / gqa heads and query head h reads KV head h / gqa.
+#if defined(FA2_GENERIC_GQA) && defined(FA2_GENERIC_VARLEN)
+#define fa2_fwd_generic_kernel fa2_fwd_generic_varlen_gqa_kernel
+#elif defined(FA2_GENERIC_GQA)
+#define fa2_fwd_generic_kernel fa2_fwd_generic_window_gqa_kernel
+#elif defined(FA2_GENERIC_VARLEN)
 #define fa2_fwd_generic_kernel fa2_fwd_generic_varlen_kernel
 #elif defined(FA2_GENERIC_WINDOW)
 #define fa2_fwd_generic_kernel fa2_fwd_generic_window_kernel
@@ -75,6 +81,9 @@ struct GenericArgs {
 #else
     int N, d, causal;
 #endif
+#ifdef FA2_GENERIC_GQA
+    int gqa;  // query heads per KV head
+#endif
     double c_log2e;  // scale * log2(e); rounded to float for the fp32 dtypes (kernels.py:92)
 };
 
@@ -95,10 +104,26 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
     fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
     if (i * kBr >= N) return;  // (whole workgroup, before any barrier)
     const int d = a.d;
+#ifdef FA2_GENERIC_GQA
+    const int hk = h / a.gqa;
+    const int64_t q_off = (int64_t)qst * a.qs[2] + h * a.qs[1];
+    const int64_t k_off = (int64_t)kst * a.ks[2] + hk * a.ks[1];
+    const int64_t v_off = (int64_t)kst * a.vs[2] + hk * a.vs[1];
+    const int64_t o_off = (int64_t)qst * a.os[2] + h * a.os[1];
+#else
     const int64_t q_off = (int64_t)qst * a.qs[2] + h * a.qs[1];
     const int64_t k_off = (int64_t)kst * a.ks[2] + h * a.ks[1];
     const int64_t v_off = (int64_t)kst * a.vs[2] + h * a.vs[1];
     const int64_t o_off = (int64_t)qst * a.os[2] + h * a.os[1];
+#endif
+#elif defined(FA2_GENERIC_GQA)
+    const int N = a.N, d = a.d;
+    const int NK = N;
+    const int hk = h / a.gqa;
+    const int64_t q_off = b * a.qs[0] + h * a.qs[1];
+    const int64_t k_off = b * a.ks[0] + hk * a.ks[1];
+    const int64_t v_off = b * a.vs[0] + hk * a.vs[1];
+    const int64_t o_off = b * a.os[0] + h * a.os[1];
 #else
     const int N = a.N, d = a.d;
     const int NK = N;
@@ -269,7 +294,11 @@ template <class E> int launch_e(const Fa2Problem &p, const GenericArgs &a) {
 
 }  // namespace
 
-#if defined(FA2_GENERIC_VARLEN)
+#if defined(FA2_GENERIC_GQA) && defined(FA2_GENERIC_VARLEN)
+int fa2_launch_generic_varlen_gqa(const Fa2Problem &p, int gqa) {
+#elif defined(FA2_GENERIC_GQA)
+int fa2_launch_generic_window_gqa(const Fa2Problem &p, int gqa) {
+#elif defined(FA2_GENERIC_VARLEN)
 int fa2_launch_generic_varlen(const Fa2Problem &p) {
 #elif defined(FA2_GENERIC_WINDOW)
 int fa2_launch_generic_window(const Fa2Problem &p) {
@@ -294,6 +323,9 @@ int fa2_launch_generic(const Fa2Problem &p) {
     a.N = p.N; a.d = p.d; a.causal = p.causal;
 #endif
     a.c_log2e = (double)p.scale * FA2_LOG2E;
+#ifdef FA2_GENERIC_GQA
+    a.gqa = gqa;
+#endif
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);
     case FA2_DTYPE_F16: return launch_e<ElemF16>(p, a);

@@ -21,7 +21,13 @@
 // and runs the windowed loop with the query extent NQ, the key extent NK and the bottom-right shifted band (fa2_varlen_band).
 // Base pointers are built in 64 bits from the sequence starts, so the 32-bit buffer offsets only span one sequence.  A row
 // without a visible key gets O = 0 and L = +inf.
-#if defined(FA2_MFMA16D_VARLEN)
+// FA2_MFMA16D_GQA (fa2_mfma16d_wg.hip, fa2_mfma16d_vg.hip, on top of the windowed or varlen form): grouped-query attention --
+// K and V have H / group heads and query head hh reads KV head hh / group; everything else is the form below it.
+#if defined(FA2_MFMA16D_GQA) && defined(FA2_MFMA16D_VARLEN)
+#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_varlen_gqa_kernel
+#elif defined(FA2_MFMA16D_GQA)
+#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_window_gqa_kernel
+#elif defined(FA2_MFMA16D_VARLEN)
 #define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_varlen_kernel
 #elif defined(FA2_MFMA16D_WINDOW)
 #define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_window_kernel
@@ -72,6 +78,9 @@ struct DmaArgs {
     int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise)
 #else
     int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
+#endif
+#ifdef FA2_MFMA16D_GQA
+    int gqa;  // query heads per KV head
 #endif
 };
 
@@ -180,9 +189,21 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaAr
     if (qi_first * BR >= NQ) return;  // (whole workgroup, before any barrier)
     int wl, wr;
     fa2_varlen_band(NQ, NK, a.causal, a.wl, a.wr, wl, wr);
+#ifdef FA2_MFMA16D_GQA
+    const int hk = hh / a.gqa;
+    const char *Qp = a.Q + (int64_t)qst * a.qs[2] + (int64_t)hh * a.qs[1];
+    const char *Kp = a.K + (int64_t)kst * a.ks[2] + (int64_t)hk * a.ks[1];
+    const char *Vp = a.V + (int64_t)kst * a.vs[2] + (int64_t)hk * a.vs[1];
+#else
     const char *Qp = a.Q + (int64_t)qst * a.qs[2] + (int64_t)hh * a.qs[1];
     const char *Kp = a.K + (int64_t)kst * a.ks[2] + (int64_t)hh * a.ks[1];
     const char *Vp = a.V + (int64_t)kst * a.vs[2] + (int64_t)hh * a.vs[1];
+#endif
+#elif defined(FA2_MFMA16D_GQA)
+    const int hk = hh / a.gqa;
+    const char *Qp = a.Q + (int64_t)b * a.qs[0] + (int64_t)hh * a.qs[1];
+    const char *Kp = a.K + (int64_t)b * a.ks[0] + (int64_t)hk * a.ks[1];
+    const char *Vp = a.V + (int64_t)b * a.vs[0] + (int64_t)hk * a.vs[1];
 #else
     const char *Qp = a.Q + (int64_t)b * a.qs[0] + (int64_t)hh * a.qs[1];
     const char *Kp = a.K + (int64_t)b * a.ks[0] + (int64_t)hh * a.ks[1];
@@ -634,7 +655,15 @@ template <typename T> int launch_d(const Fa2Problem &p, const DmaArgs &a, int wa
 
 }  // namespace
 
-#if defined(FA2_MFMA16D_VARLEN)
+#if defined(FA2_MFMA16D_GQA) && defined(FA2_MFMA16D_VARLEN)
+int fa2_launch_mfma16d_varlen_gqa(const Fa2Problem &pv, int waves, int gqa) {
+    Fa2Problem p = pv;
+    p.causal = 0;
+    const bool fits32 = (int64_t)(p.max_k + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.max_k + 512) * p.vs[2] * 2 < (1LL << 31);
+#elif defined(FA2_MFMA16D_GQA)
+int fa2_launch_mfma16d_window_gqa(const Fa2Problem &p, int waves, int gqa) {
+    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
+#elif defined(FA2_MFMA16D_VARLEN)
 int fa2_launch_mfma16d_varlen(const Fa2Problem &pv, int waves) {
     Fa2Problem p = pv;
     p.causal = 0;  // the causal mask is in the band (fa2_varlen_band): one tile per workgroup, no tile pairs
@@ -675,6 +704,9 @@ int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
     a.wr = p.wr;
 #else
     a.flags = fa2_env_int("FA2_FLAGS", 0);
+#endif
+#ifdef FA2_MFMA16D_GQA
+    a.gqa = gqa;
 #endif
     if (p.causal && ((p.B * p.H) & 7) == 0) {
         const int per_xcd = p.B * p.H / 8;

@@ -120,12 +120,39 @@ def window_head_size(dtype, d):
     return d
 
 
+def gqa_kv_heads(Q, K, V):
+    """The shape rule of the dense entry points: Q (B, H, N, d), K and V (B, H_kv, N, d) of one shape, H_kv >= 1 dividing H
+    (grouped-query attention; H_kv == H is plain multi-head attention, H_kv == 1 multi-query).  Returns H_kv; ValueError for
+    anything else.  Pure: takes CPU tensors as well."""
+    if Q.dim() != 4 or K.dim() != 4 or V.dim() != 4 or K.shape != V.shape or Q.shape[0] != K.shape[0] \
+            or Q.shape[2:] != K.shape[2:] or K.shape[1] < 1:
+        raise ValueError(f"Q, K, V must all be of shape (B, H, N, d), K and V (B, H_kv, N, d): got Q {tuple(Q.shape)}, "
+                         f"K {tuple(K.shape)}, V {tuple(V.shape)}")
+    H, H_kv = Q.shape[1], K.shape[1]
+    if H % H_kv != 0:
+        raise ValueError(f"the KV heads must divide the query heads: H={H}, H_kv={H_kv}")
+    return H_kv
+
+
+def expand_kv(t, H):
+    """K or V (.., H_kv, N, d) expanded to H heads the way GQA groups them (query head h reads KV head h // (H / H_kv)): the
+    repeat_interleave a caller needed before fa2_fwd_gqa existed.  For tests and references."""
+    return t if t.shape[-3] == H else t.repeat_interleave(H // t.shape[-3], dim=-3)
+
+
+def group_sum(t, H_kv):
+    """dK or dV (.., H, N, d) of expanded K / V summed back over each group of H / H_kv query heads -> (.., H_kv, N, d)."""
+    H = t.shape[-3]
+    if H == H_kv:
+        return t
+    return t.unflatten(-3, (H_kv, H // H_kv)).sum(dim=-3)
+
+
 def _check_inputs(Q, K, V):
     dev = Q.device
     if dev.type != "cuda" or dev != K.device or dev != V.device:
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
-    if Q.dim() != 4 or Q.shape != K.shape or Q.shape != V.shape:
-        raise ValueError("Q, K, V must all be of shape (B, H, N, d)")
+    gqa_kv_heads(Q, K, V)
     if Q.dtype != K.dtype or K.dtype != V.dtype:
         raise ValueError("Q, K, V must have same dtype")
 
@@ -155,14 +182,14 @@ def _forward_impl(ctx, Q, K, V, causal, scale, window=None):
         Qr, Kr, Vr = (pad_last_dim(t, d_run) for t in (Q, K, V))
         Or = torch.empty_like(Qr)
         _lib.fa2_fwd(Qr, Kr, Vr, Or, L, dtype, causal=causal, scale=scale,
-                     variant=autotune.pick(Qr, Kr, Vr, Or, L, dtype, causal, scale))
+                     variant=_pick(Qr, Kr, Vr, Or, L, dtype, causal, scale))
         O = Or[..., :d]        # (a view of the padded O, as the reference returns it: torch.py:81-82)
     else:
         O = torch.empty_like(Q)
         # static gfx950 tile table, or the on-box tuner's choice when FA2_AUTOTUNE=1 (autotune.py; reference:
         # the Triton autotuner keyed on (B, H, N, d), kernels.py:11-15)
         _lib.fa2_fwd(Q, K, V, O, L, dtype, causal=causal, scale=scale,
-                     variant=autotune.pick(Q, K, V, O, L, dtype, causal, scale))
+                     variant=_pick(Q, K, V, O, L, dtype, causal, scale))
 
     ctx.save_for_backward(Q, K, V, O, L)
     ctx.padded = padded
@@ -171,6 +198,13 @@ def _forward_impl(ctx, Q, K, V, causal, scale, window=None):
     ctx.causal = bool(causal)
     ctx.scale = float(scale)
     return O
+
+
+def _pick(Q, K, V, O, L, dtype, causal, scale):
+    """The tuner's choice -- except for grouped-query problems, whose K / V heads its key does not see: the static table."""
+    if K.shape[1] != Q.shape[1]:
+        return _lib.VARIANT_AUTO
+    return autotune.pick(Q, K, V, O, L, dtype, causal, scale)
 
 
 def _forward_window(ctx, Q, K, V, dtype, scale, window):
@@ -213,9 +247,11 @@ def attention_backward_recompute(Q, K, V, O, dO, L, causal=False, scale=1.0, *, 
     """dQ, dK, dV from the saved statistics in plain torch ops: a readable restatement used by the tests only
     (the product path is _backward_native below).
     P = exp2(scale * S * log2e - L) (reference kernels.py:283-285), D = rowsum(dO * O) (kernels.py:120-166).
-    window: local attention, as fa2_fwd_window (P is 0 outside the band)."""
+    window: local attention, as fa2_fwd_window (P is 0 outside the band).  K, V with H_kv < H heads (grouped-query): expanded
+    to H heads, dK / dV summed back over each group."""
     f = torch.float64 if Q.dtype == torch.float64 else torch.float32
-    q, k, v, o, do, l = (t.to(f) for t in (Q, K, V, O, dO, L))
+    H_kv = K.shape[1]
+    q, k, v, o, do, l = (t.to(f) for t in (Q, expand_kv(K, Q.shape[1]), expand_kv(V, Q.shape[1]), O, dO, L))
     S = torch.matmul(q, k.transpose(-1, -2)) * (scale * math.log2(math.e))
     if window is not None:
         mask = window_mask(Q.shape[2], causal, window, Q.device)
@@ -232,13 +268,15 @@ def attention_backward_recompute(Q, K, V, O, dO, L, causal=False, scale=1.0, *, 
     dS = P * (dP - D) * scale
     dQ = torch.matmul(dS, k)
     dK = torch.matmul(dS.transpose(-1, -2), q)
-    return dQ.to(Q.dtype), dK.to(K.dtype), dV.to(V.dtype)
+    return dQ.to(Q.dtype), group_sum(dK, H_kv).to(K.dtype), group_sum(dV, H_kv).to(V.dtype)
 
 
 def backward_native(Q, K, V, O, dO, L, causal=False, scale=1.0, variant="auto", *, window=None):
     """Host glue of the backward launch (reference torch.py:101-155): allocate dQ, dK, dV (strides of Q, K, V) and
     the scratch D, launch, return the gradients.  Inputs are already padded to a supported d.  window: local attention
-    (normalize_window); a window that reduces to plain or causal attention takes the plain launch."""
+    (normalize_window); a window that reduces to plain or causal attention takes the plain launch.  K, V with H_kv < H heads
+    (grouped-query, gqa_kv_heads): dK, dV come back with K's and V's shapes, summed over each group in the kernel."""
+    gqa_kv_heads(Q, K, V)
     if window is not None:
         causal, window = normalize_window(Q.shape[2], causal, window)
     dtype = convert_triton_dtype(Q.dtype)
@@ -338,9 +376,9 @@ def check_varlen_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seq
     dev = Q.device
     if Q.dim() != 3 or K.dim() != 3 or V.dim() != 3:
         raise ValueError(f"varlen: Q, K, V must be (total, H, d), got {tuple(Q.shape)}, {tuple(K.shape)}, {tuple(V.shape)}")
-    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
-        raise ValueError(f"varlen: K and V must be (total_k, H, d) with Q's H and d, got Q {tuple(Q.shape)}, "
-                         f"K {tuple(K.shape)}, V {tuple(V.shape)}")
+    if K.shape != V.shape or Q.shape[2] != K.shape[2] or K.shape[1] < 1 or Q.shape[1] % K.shape[1] != 0:
+        raise ValueError(f"varlen: K and V must be (total_k, H, d) with Q's H and d, or (total_k, H_kv, d) with H_kv dividing "
+                         f"Q's H, got Q {tuple(Q.shape)}, K {tuple(K.shape)}, V {tuple(V.shape)}")
     if Q.dtype != K.dtype or K.dtype != V.dtype:
         raise ValueError("varlen: Q, K, V must have the same dtype")
     if Q.dtype in (torch.float8_e5m2, torch.float8_e4m3fn):
@@ -423,8 +461,8 @@ def varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
 class FlashAttentionVarlen(torch.autograd.Function):
     """Packed variable-length attention (flash_attn_varlen_func's calling convention):
     `FlashAttentionVarlen.apply(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window)`,
-    Q (total_q, H, d), K / V (total_k, H, d), bottom-right aligned causal mask and window (include/fa2_fwd.h).  Returns O;
-    the cu_seqlens and the other arguments get no gradient.  Tokens outside every sequence (cu_seqlens[-1] < total, or gaps
+    Q (total_q, H, d), K / V (total_k, H, d) or (total_k, H_kv, d) with H_kv dividing H (grouped-query), bottom-right aligned
+    causal mask and window (include/fa2_fwd.h).  Returns O; the cu_seqlens and the other arguments get no gradient.  Tokens outside every sequence (cu_seqlens[-1] < total, or gaps
     between sequences) are left unwritten in O and in the gradients, as flash-attn leaves them: such a batch must not feed
     them on."""
 

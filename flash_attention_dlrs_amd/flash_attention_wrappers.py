@@ -7,7 +7,7 @@ import torch
 
 from . import _lib, autotune
 from .flash_attention_torch import (MIN_TENSOR_SIZE, backward_native, convert_triton_dtype, forward_head_size,
-                                    next_power_of_2, normalize_window, pad_last_dim, varlen_backward, varlen_forward,
+                                    gqa_kv_heads, next_power_of_2, normalize_window, pad_last_dim, varlen_backward, varlen_forward,
                                     window_head_size)
 
 
@@ -15,9 +15,11 @@ def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="a
     # Takes tensors of shape (B, H, N, d): batch, heads, context size, head dimension
     # (reference wrappers.py:14-22: bare asserts, kept).
     # window = (left, right): local attention (FlashAttention's docstring; include/fa2_fwd.h fa2_fwd_window).
+    # K and V may have H_kv heads dividing H (grouped-query attention; gqa_kv_heads raises ValueError otherwise)
     assert Q.dim() == 4
-    assert Q.shape == K.shape and K.shape == V.shape
+    assert K.dim() == 4 and K.shape == V.shape and Q.shape[0] == K.shape[0] and Q.shape[2:] == K.shape[2:]
     assert Q.dtype == K.dtype and K.dtype == V.dtype
+    gqa_kv_heads(Q, K, V)
 
     B, H, N, d = Q.shape
     if window is not None:
@@ -43,7 +45,7 @@ def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="a
     if O.device != Q.device:   # the launch runs on Q's device: an O allocated elsewhere would be a foreign pointer there
         raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
     v = _lib.VARIANTS[variant]
-    if variant == "auto" and autotune.enabled():
+    if variant == "auto" and autotune.enabled() and K.shape[1] == H:  # (the tuner's key does not see H_kv)
         v = autotune.pick(Q, K, V, O, L, dtype, causal, scale)  # the on-box tuner, FA2_AUTOTUNE=1
         if v != _lib.VARIANT_AUTO:
             try:
@@ -85,8 +87,10 @@ def flash_attention_backward(Q, K, V, O, dO, L, dev, deterministic=False, *, cau
     deterministic by construction, so the flag is accepted and ignored.  d is padded like in the forward
     (wrappers.py:91-104) and the gradients are returned as [:d] views."""
     assert Q.dim() == 4
-    assert Q.shape == K.shape and K.shape == V.shape and O.shape == Q.shape and dO.shape == Q.shape
+    assert K.dim() == 4 and K.shape == V.shape and Q.shape[0] == K.shape[0] and Q.shape[2:] == K.shape[2:]
+    assert O.shape == Q.shape and dO.shape == Q.shape
     assert Q.dtype == K.dtype and K.dtype == V.dtype and Q.dtype == dO.dtype
+    gqa_kv_heads(Q, K, V)
     d = Q.shape[-1]
     d_pow = max(next_power_of_2(d), MIN_TENSOR_SIZE)
     if d_pow != d:
@@ -97,8 +101,9 @@ def flash_attention_backward(Q, K, V, O, dO, L, dev, deterministic=False, *, cau
 
 def flash_attention_varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dev, *, causal=False,
                                    scale=1.0, window=None, variant="auto"):
-    """Packed variable-length forward (include/fa2_fwd.h fa2_fwd_varlen) -> (O, L): Q (total_q, H, d), K / V (total_k, H, d),
-    cu_seqlens int32 (B + 1) on Q's device; O (total_q, H, d), L (H, total_q).  The autotuner is not consulted."""
+    """Packed variable-length forward (include/fa2_fwd.h fa2_fwd_varlen) -> (O, L): Q (total_q, H, d), K / V (total_k, H, d)
+    or (total_k, H_kv, d) with H_kv dividing H (grouped-query, fa2_fwd_varlen_gqa), cu_seqlens int32 (B + 1) on Q's device;
+    O (total_q, H, d), L (H, total_q).  The autotuner is not consulted."""
     if Q.device != torch.device(dev):
         raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
     return varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal, scale=scale,
@@ -107,7 +112,8 @@ def flash_attention_varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seql
 
 def flash_attention_varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dev, *,
                                     causal=False, scale=1.0, window=None, variant="auto"):
-    """(dQ, dK, dV) of flash_attention_varlen_forward (include/fa2_bwd.h fa2_bwd_varlen); deterministic."""
+    """(dQ, dK, dV) of flash_attention_varlen_forward (include/fa2_bwd.h fa2_bwd_varlen, fa2_bwd_varlen_gqa); deterministic.
+    dK and dV have K's and V's shapes: (total_k, H_kv, d) for grouped-query K / V, summed over each group in the kernel."""
     if Q.device != torch.device(dev):
         raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
     return varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,

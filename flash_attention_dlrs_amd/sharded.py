@@ -26,7 +26,9 @@ def head_shard_range(H, world_size, rank):
 
 
 def shard_heads(t, world_size, rank):
-    """View of the (B, H, N, d) tensor holding this rank's heads."""
+    """View of the (B, H, N, d) tensor holding this rank's heads.  Grouped-query K / V (H_kv heads): shard them with the same
+    call; when world_size divides H_kv, rank r's query heads and KV heads are then matching groups, so the local call is the
+    GQA problem of that shard."""
     h0, h1 = head_shard_range(t.shape[1], world_size, rank)
     return t[:, h0:h1]
 

@@ -120,6 +120,51 @@ int fa2_bwd_varlen_variant(const void *Q, const void *K, const void *V, const vo
                            int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                            int32_t window_right, void *hip_stream, int32_t variant);
 
+/* Grouped-query (GQA) and multi-query attention: the gradients of fa2_fwd_gqa / fa2_fwd_varlen_gqa.  Arguments of fa2_bwd_window /
+ * fa2_bwd_varlen (and their _variant forms) with H_kv after H.  K, V, dK and dV have H_kv heads (dense (B, H_kv, N, d), varlen
+ * (total_k, H_kv, d)); Q, O, dO, L and dQ have H.  dK and dV of KV head k are the sums over query heads k g ... k g + g - 1
+ * (g = H / H_kv), formed inside one workgroup per key block in a fixed order: deterministic, no atomics, no workspace.  D keeps its
+ * size: 2 * B * H * N (dense), 2 * H * total_q (varlen).  FA2_ERR_BAD_ARG before any launch for H_kv < 1 or H % H_kv != 0
+ * ("H_kv" in the message), plus every check of the non-GQA entry point; H_kv == H runs fa2_bwd_window(_variant) /
+ * fa2_bwd_varlen(_variant) itself.  Variants: FA2_BWD_VARIANT_AUTO (MFMA16 where it runs, else GENERIC), FA2_BWD_VARIANT_GENERIC
+ * (f64, f32, f16, bf16) and FA2_BWD_VARIANT_MFMA16 (f16 / bf16, d in {64, 128}); FA2_BWD_VARIANT_MFMA32 returns
+ * FA2_ERR_UNSUPPORTED for H_kv < H. */
+int fa2_bwd_gqa(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                void *dQ, void *dK, void *dV, void *D,
+                const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                const int64_t o_strides[4], const int64_t do_strides[4], const int64_t dq_strides[4],
+                const int64_t dk_strides[4], const int64_t dv_strides[4], const int64_t l_strides[2],
+                int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+                float scale, int32_t window_left, int32_t window_right, void *hip_stream);
+
+int fa2_bwd_gqa_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                        void *dQ, void *dK, void *dV, void *D,
+                        const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                        const int64_t o_strides[4], const int64_t do_strides[4], const int64_t dq_strides[4],
+                        const int64_t dk_strides[4], const int64_t dv_strides[4], const int64_t l_strides[2],
+                        int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+                        float scale, int32_t window_left, int32_t window_right, void *hip_stream, int32_t variant);
+
+int fa2_bwd_varlen_gqa(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                       void *dQ, void *dK, void *dV, void *D,
+                       const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                       const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                       const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                       const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t H_kv,
+                       int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                       int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                       void *hip_stream);
+
+int fa2_bwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO,
+                               const void *L, void *dQ, void *dK, void *dV, void *D,
+                               const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                               const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                               const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                               const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                               int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                               int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                               int32_t window_right, void *hip_stream, int32_t variant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,57 @@ int fa2_fwd_varlen_variant(const void *Q, const void *K, const void *V, void *O,
                            int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                            int32_t window_right, void *hip_stream, int32_t variant);
 
+/*
+ * Grouped-query (GQA) and multi-query (MQA) attention: K and V have H_kv heads, 1 <= H_kv, H % H_kv == 0; with g = H / H_kv,
+ * query head h attends with KV head h / g (the contiguous grouping of flash-attn and torch's enable_gqa).  Q, O, L keep H heads.
+ *
+ *   fa2_fwd_gqa(_variant): the arguments of fa2_fwd_window(_variant) with H_kv after H; K and V are (B, H_kv, N, d) with their own
+ *   strides.  (window_left, window_right) = (-1, -1) is no window; windows are normalised as fa2_fwd_window normalises them.
+ *   fa2_fwd_varlen_gqa(_variant): the arguments of fa2_fwd_varlen(_variant) with H_kv after H; K and V are (total_k, H_kv, d).
+ *
+ * FA2_ERR_BAD_ARG before any launch for H_kv < 1 or H % H_kv != 0 ("H_kv" in the message); every check of the non-GQA entry point
+ * applies as well.  H_kv == H runs the non-GQA entry point itself (fa2_fwd_window(_variant), fa2_fwd_varlen(_variant)): the same
+ * results bit for bit, the same variants.
+ *
+ * Dense layouts.  A layout is MERGEABLE when B == 1, or when the batch strides of Q, O and L are H times their head strides and
+ * those of K and V H_kv times theirs (the contiguous (B, H, N, d) layout, a B = 1 (B, N, H, d) view); with H_kv = 1 the head
+ * stride of K and V is not read, so any stride of that size-1 dimension merges.  Such a problem runs as the MHA
+ * problem of B * H_kv batches of g heads that share one K / V head (head stride 0), on the kernels and the table of fa2_fwd /
+ * fa2_fwd_window, so every variant they take is accepted (fp8 included) and AUTO picks what it picks for the same B * H.  Any other
+ * layout runs GQA forms of the windowed kernels, a plain or causal problem as the full band: FA2_VARIANT_AUTO (MFMA16D / MFMA16D_W4
+ * for f16 / bf16 at d 64 / 128, else GENERIC), FA2_VARIANT_GENERIC (every dtype, fp8 included), FA2_VARIANT_MFMA16D and
+ * FA2_VARIANT_MFMA16D_W4.
+ * Varlen.  FA2_VARIANT_AUTO (MFMA16D_W4 where it runs, else GENERIC), FA2_VARIANT_GENERIC, FA2_VARIANT_MFMA16D and
+ * FA2_VARIANT_MFMA16D_W4, as fa2_fwd_varlen.  Any other forced variant returns FA2_ERR_UNSUPPORTED.
+ */
+int fa2_fwd_gqa(const void *Q, const void *K, const void *V, void *O, void *L,
+                const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                int32_t window_right, void *hip_stream);
+
+int fa2_fwd_gqa_variant(const void *Q, const void *K, const void *V, void *O, void *L,
+                        const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                        const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                        int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                        int32_t window_right, void *hip_stream, int32_t variant);
+
+int fa2_fwd_varlen_gqa(const void *Q, const void *K, const void *V, void *O, void *L,
+                       const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                       const int64_t o_strides[3], int64_t l_head_stride,
+                       const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t H_kv,
+                       int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                       int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                       void *hip_stream);
+
+int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void *O, void *L,
+                               const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                               const int64_t o_strides[3], int64_t l_head_stride,
+                               const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                               int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                               int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                               int32_t window_right, void *hip_stream, int32_t variant);
+
 /* Which tile the static table picks for a contiguous problem: out4 = {variant, B_r, B_c, waves}.
  * Counterpart of fwd_conf_prune + the autotuner's choice (src/autotune_configs.py:176-194). */
 int fa2_query_tile(int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, int32_t out4[4]);
