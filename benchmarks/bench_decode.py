@@ -1,0 +1,293 @@
+#!/usr/bin/env python3
+"""KV-cache decode attention timing (fa2_fwd_kvcache), bf16; JSON lines appended to profiles/decode/bench_decode.jsonl.
+
+Sides, alternated in one process after every shape has been warmed:
+  decode: flash_attention_kvcache_forward, AUTO variant and auto num_splits;
+  varlen: the route without this entry point -- flash_attention_varlen_forward with N_q tokens per sequence on the packed
+          cache (equal lengths: the (B, S, H_kv, d) cache viewed as (B S, H_kv, d); the ragged case packs the real lengths);
+  sdpa:   torch scaled_dot_product_attention with enable_gqa (the ragged case with a boolean key mask).
+Every side rotates over enough copies of K and V to exceed the 256 MiB last-level cache, so the keys come from HBM.
+
+Records:
+  kind=events   call time from device events around `iters` back-to-back calls, median / min / max over `rounds` (this includes
+                what the host takes to enqueue a call: at these sizes the host often is the limit, for every side);
+  kind=kernels  kernel time per call from a `rocprofv3 --kernel-trace --stats` run of its own (a fresh child process per shape,
+                --rocprof), average / min / max / stddev as the stats file gives them, and K + V bytes over the decode kernel time
+                as a share of the 6.29 TB/s copy rate of the chip;
+  kind=sweep    the events figure of the decode side for num_splits in {1, 2, 4, 8, 16, 32, 64} on the first four shapes (--sweep);
+  kind=sweep_kernels  the same sweep in kernel time (--rocprof DIR --sweep): one traced child per shape runs the split counts one
+                after the other, and the dispatches of the kernel trace are cut into the split counts by their order (split kernel
+                plus combine per call; one kernel for num_splits = 1)."""
+import argparse
+import csv
+import glob
+import json
+import math
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "decode", "bench_decode.jsonl")
+HBM_COPY_RATE = 6.29e12  # bytes / s, measured copy rate of the MI355X
+
+CASES = {  # name: (B, H, H_kv, N_k, d, N_q)
+    "b1_n8192": (1, 32, 8, 8192, 128, 1),
+    "b1_n131072": (1, 32, 8, 131072, 128, 1),
+    "b4_n8192": (4, 32, 8, 8192, 128, 1),
+    "b16_n4096": (16, 32, 8, 4096, 128, 1),
+    "b64_n2048": (64, 32, 8, 2048, 128, 1),
+    "mha_b8_n4096": (8, 32, 32, 4096, 128, 1),
+    "mqa_b8_n4096": (8, 32, 1, 4096, 128, 1),
+    "d64_b4_n8192": (4, 32, 8, 8192, 64, 1),
+    "nq4_b4_n8192": (4, 32, 8, 8192, 128, 4),
+    "ragged_b16": (16, 32, 8, 16384, 128, 1),  # lengths from 100 to 16384
+}
+SWEEP_CASES = ("b1_n8192", "b1_n131072", "b4_n8192", "b16_n4096")
+SWEEP_SPLITS = (1, 2, 4, 8, 16, 32, 64)
+
+
+def emit(fh, **kw):
+    line = json.dumps(kw)
+    print(line, flush=True)
+    if fh is not None:
+        fh.write(line + "\n")
+        fh.flush()
+
+
+def ragged_lengths(B, lo, hi):
+    return [int(round(math.exp(math.log(lo) + (math.log(hi) - math.log(lo)) * k / (B - 1)))) for k in range(B)]
+
+
+class Case:
+    def __init__(self, name, dev):
+        import torch
+        from flash_attention_dlrs_amd import _lib
+        from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
+        self.torch, self._lib, self.name, self.dev = torch, _lib, name, dev
+        B, H, H_kv, S, d, N_q = CASES[name]
+        self.shape = dict(B=B, H=H, H_kv=H_kv, N_k=S, d=d, N_q=N_q)
+        self.lens = ragged_lengths(B, 100, S) if name.startswith("ragged") else [S] * B
+        self.kv_bytes = 2 * 2 * H_kv * d * sum(self.lens)
+        self.copies = max(2, min(16, math.ceil(600e6 / (2 * 2 * B * H_kv * S * d))))
+        self.scale = d ** -0.5
+        self.enum = convert_triton_dtype(torch.bfloat16)
+        mk = lambda *s: (torch.randn(*s, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
+        self.Q = mk(B, H, N_q, d)
+        self.K = [mk(B, S, H_kv, d) for _ in range(self.copies)]  # the flash-attn cache layout
+        self.V = [mk(B, S, H_kv, d) for _ in range(self.copies)]
+        self.lens_dev = torch.tensor(self.lens, dtype=torch.int32, device=dev)
+        self.ragged = len(set(self.lens)) > 1
+        # varlen side: packed keys, N_q query tokens per sequence
+        self.Qp = self.Q.transpose(1, 2).reshape(B * N_q, H, d).contiguous()
+        self.cu_q = torch.arange(0, (B + 1) * N_q, N_q, dtype=torch.int32, device=dev)
+        self.cu_k = torch.tensor([0] + list(torch.tensor(self.lens).cumsum(0).tolist()), dtype=torch.int32, device=dev)
+        if self.ragged:
+            pk = lambda t: torch.cat([t[b, :n] for b, n in enumerate(self.lens)])  # noqa: E731
+            self.Kp, self.Vp = [pk(t) for t in self.K], [pk(t) for t in self.V]
+            self.mask = (torch.arange(S, device=dev).view(1, 1, 1, S) < self.lens_dev.view(B, 1, 1, 1))
+        else:
+            self.Kp, self.Vp = [t.view(B * S, H_kv, d) for t in self.K], [t.view(B * S, H_kv, d) for t in self.V]
+            self.mask = None
+        self.O = torch.empty(B, H, N_q, d, dtype=torch.bfloat16, device=dev)
+        self.L = torch.empty(B, H, N_q, dtype=torch.bfloat16, device=dev)
+        self.i = 0
+
+    def auto_splits(self):
+        s = self.shape
+        return self._lib.kvcache_num_splits(s["B"], s["H"], s["H_kv"], s["N_q"], s["N_k"], s["d"], self.enum)
+
+    def decode(self, num_splits=0):
+        """The library launch itself, outputs and workspace allocated once (what a serving loop does)."""
+        s = self.shape
+        n = num_splits or self.auto_splits()
+        words = self._lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], s["d"], n) // 4
+        ws = self.torch.empty(max(words, 1), dtype=self.torch.float32, device=self.dev)
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            self._lib.fa2_fwd_kvcache(self.Q, self.K[self.i].transpose(1, 2), self.V[self.i].transpose(1, 2), self.O, self.L,
+                                      self.lens_dev, self.enum, scale=self.scale, num_splits=n, workspace=ws)
+        return run
+
+    def varlen(self):
+        from flash_attention_dlrs_amd import flash_attention_varlen_forward
+        s = self.shape
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            flash_attention_varlen_forward(self.Qp, self.Kp[self.i], self.Vp[self.i], self.cu_q, self.cu_k, s["N_q"], max(self.lens),
+                                           self.dev, scale=self.scale)
+        return run
+
+    def sdpa(self):
+        F = self.torch.nn.functional
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            F.scaled_dot_product_attention(self.Q, self.K[self.i].transpose(1, 2), self.V[self.i].transpose(1, 2),
+                                           attn_mask=self.mask, scale=self.scale, enable_gqa=True)
+        return run
+
+
+def time_us(torch, fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def interleaved(torch, fns, iters, rounds):
+    for f in fns:
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, f in enumerate(fns):
+            ts[k].append(time_us(torch, f, iters))
+    return [dict(median_us=round(sorted(t)[len(t) // 2], 2), min_us=round(min(t), 2), max_us=round(max(t), 2)) for t in ts]
+
+
+def run_events(names, args, fh):
+    import torch
+    dev = torch.device("cuda:0")
+    for name in names:
+        c = Case(name, dev)
+        sides = {"decode": c.decode(), "varlen": c.varlen()}
+        if not args.no_sdpa:
+            sides["sdpa"] = c.sdpa()
+        res = interleaved(torch, list(sides.values()), args.iters, args.rounds)
+        emit(fh, kind="events", case=name, **c.shape, ragged=c.ragged, num_splits=c.auto_splits(), kv_bytes=c.kv_bytes,
+             **{k: r for k, r in zip(sides, res)})
+        if args.sweep and name in SWEEP_CASES:
+            fns = [c.decode(n) for n in SWEEP_SPLITS]
+            for n, r in zip(SWEEP_SPLITS, interleaved(torch, fns, args.iters, args.rounds)):
+                emit(fh, kind="sweep", case=name, **c.shape, num_splits=n, **r)
+        del c
+        torch.cuda.empty_cache()
+
+
+def run_pass(name, args):
+    """The traced child: warm, then alternate the sides; the profiler's stats file holds the kernel times."""
+    import torch
+    c = Case(name, torch.device("cuda:0"))
+    sides = [c.decode(), c.varlen()] + ([] if args.no_sdpa else [c.sdpa()])
+    for _ in range(args.iters + 3):
+        for f in sides:
+            f()
+    torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, calls=args.iters + 3, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(), **c.shape)))
+
+
+def run_sweep_pass(name, args):
+    """The traced child of the kernel-time sweep: the decode side alone, one split count after the other."""
+    import torch
+    c = Case(name, torch.device("cuda:0"))
+    for n in SWEEP_SPLITS:
+        f = c.decode(n)
+        for _ in range(args.iters + 3):
+            f()
+        torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, calls=args.iters + 3, kv_bytes=c.kv_bytes, auto_splits=c.auto_splits(), **c.shape)))
+
+
+def traced_child(out, extra, args):
+    os.makedirs(out, exist_ok=True)
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
+           os.path.abspath(__file__), "--iters", str(args.iters)] + extra + (["--no-sdpa"] if args.no_sdpa else [])
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.child_timeout)
+    if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
+        sys.stderr.write(p.stdout[-2000:] + p.stderr[-2000:])
+        sys.exit(p.returncode)
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def sweep_from_trace(out, info, fh):
+    trace = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
+    rows = [r for r in csv.DictReader(open(trace[0])) if "fa2_decode" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    pos, calls = 0, info["calls"]
+    for n in SWEEP_SPLITS:
+        per = 1 if n == 1 else 2
+        seg = rows[pos:pos + per * calls]
+        pos += per * calls
+        assert len(seg) == per * calls and all(("combine" in r["Kernel_Name"]) == (per == 2 and k % 2 == 1) for k, r in enumerate(seg)), n
+        us = [sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg[per * k:per * k + per]) / 1e3 for k in range(3, calls)]
+        avg = sum(us) / len(us)
+        emit(fh, kind="sweep_kernels", case=info["case"], num_splits=n, auto_splits=info["auto_splits"], avg_us=round(avg, 2),
+             min_us=round(min(us), 2), max_us=round(max(us), 2),
+             hbm_share=round(info["kv_bytes"] / (avg * 1e-6) / HBM_COPY_RATE, 3))
+    assert pos == len(rows)
+
+
+def side_of(kernel):
+    if "fa2_decode" in kernel:
+        return "decode"
+    if "varlen" in kernel:
+        return "varlen"
+    low = kernel.lower()
+    if "attn" in low or "fmha" in low or "attention" in low:
+        return "sdpa"
+    return None
+
+
+def run_rocprof(names, args, fh):
+    for name in names:
+        out = os.path.join(args.rocprof, name)
+        info = traced_child(out, ["--pass-case", name], args)
+        stats = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+        sides = {}
+        for row in csv.DictReader(open(stats[0])):
+            side = side_of(row["Name"])
+            if side is None:
+                continue
+            s = sides.setdefault(side, dict(avg_us=0.0, min_us=0.0, max_us=0.0, stddev_us=0.0, kernels=[]))
+            per_call = int(row["Calls"]) / info["calls"]  # launches of this kernel per call of the side
+            s["avg_us"] += float(row["AverageNs"]) * per_call / 1e3
+            s["min_us"] += float(row["MinNs"]) * per_call / 1e3
+            s["max_us"] += float(row["MaxNs"]) * per_call / 1e3
+            s["stddev_us"] += float(row["StdDev"]) * per_call / 1e3
+            s["kernels"].append("%s x%g avg %.2f us" % (row["Name"][:90], per_call, float(row["AverageNs"]) / 1e3))
+        for s in sides.values():
+            for k in ("avg_us", "min_us", "max_us", "stddev_us"):
+                s[k] = round(s[k], 2)
+        share = info["kv_bytes"] / (sides["decode"]["avg_us"] * 1e-6) / HBM_COPY_RATE if "decode" in sides else None
+        emit(fh, kind="kernels", **info, hbm_share=None if share is None else round(share, 3), **sides)
+        if args.sweep and name in SWEEP_CASES:
+            out = os.path.join(args.rocprof, name + "_sweep")
+            sweep_from_trace(out, traced_child(out, ["--sweep-case", name], args), fh)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--sweep", action="store_true", help="also time num_splits in %s on the first four shapes" % (SWEEP_SPLITS,))
+    ap.add_argument("--no-sdpa", action="store_true")
+    ap.add_argument("--rocprof", metavar="DIR", help="kernel times: one rocprofv3 --kernel-trace --stats child per shape, traces under DIR")
+    ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--pass-case", help=argparse.SUPPRESS)
+    ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
+    ap.add_argument("--out", default=OUT)
+    args = ap.parse_args()
+    if args.pass_case:
+        return run_pass(args.pass_case, args)
+    if args.sweep_case:
+        return run_sweep_pass(args.sweep_case, args)
+    names = args.cases.split(",")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as fh:
+        if args.rocprof:
+            run_rocprof(names, args, fh)
+        else:
+            run_events(names, args, fh)
+
+
+if __name__ == "__main__":
+    main()

@@ -51,11 +51,15 @@ if os.path.basename(LIB_PATH) in ("libfa2_hip_exp.so", "libfa2_hip_abl.so"):
 # Every symbol include/fa2_fwd.h declares (tests/test_abi.py checks the export list against the header).
 SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", "fa2_query_tile_scaled", "fa2_version", "fa2_last_error",
            "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant",
-           "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant")
+           "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant",
+           "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
 BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
+# KV-cache decode (fa2_fwd_kvcache) has its own small variant enum, FA2_KVCACHE_VARIANT_*
+KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
+KVCACHE_MAX_SPLITS = 128
 
 _lib = None
 
@@ -138,6 +142,17 @@ def lib():
         l.fa2_bwd_varlen_gqa.argtypes = bvlg
         l.fa2_bwd_varlen_gqa_variant.restype = ctypes.c_int
         l.fa2_bwd_varlen_gqa_variant.argtypes = bvlg + [ctypes.c_int32]
+        # KV-cache decode: 4-element strides, L strides, cache_seqlens, B H H_kv N_q S_k d dtype causal, scale, window, num_splits,
+        # workspace + its size, stream
+        kvc = [vp] * 5 + [i64p] * 5 + [vp] + [ctypes.c_int32] * 8 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, vp]
+        l.fa2_fwd_kvcache.restype = ctypes.c_int
+        l.fa2_fwd_kvcache.argtypes = kvc
+        l.fa2_fwd_kvcache_variant.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_variant.argtypes = kvc + [ctypes.c_int32]
+        l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
+        l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
+        l.fa2_kvcache_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_num_splits.argtypes = [ctypes.c_int32] * 7
         l.bwd_variant_addr = ctypes.CFUNCTYPE(ctypes.c_int, *([vp] * 19 + [ctypes.c_int32] * 6 + [ctypes.c_float, vp, ctypes.c_int32]))(
             ("fa2_bwd_variant", l))
         l.fa2_version.restype = ctypes.c_char_p
@@ -340,5 +355,37 @@ def fa2_bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_q, cu_k, max_q, max_k, d
             *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), L.stride(0),
             cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, d, int(max_q), int(max_k), total_q, K.shape[0],
             int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+    if rc != 0:
+        _raise(rc)
+
+
+def kvcache_num_splits(B, H, H_kv, N_q, S_k, d, dtype_enum):
+    """What num_splits = 0 resolves to for a decode call of this shape (fa2_kvcache_num_splits): a host heuristic on the capacity."""
+    return int(lib().fa2_kvcache_num_splits(B, H, H_kv, N_q, S_k, d, int(dtype_enum)))
+
+
+def kvcache_workspace_bytes(B, H, N_q, d, num_splits):
+    """Bytes of fp32 workspace a decode call with this num_splits needs (fa2_kvcache_workspace_bytes); 0 for num_splits <= 1."""
+    return int(lib().fa2_kvcache_workspace_bytes(B, H, N_q, d, num_splits))
+
+
+def fa2_fwd_kvcache(Q, K, V, O, L, cache_seqlens, dtype_enum, causal=False, scale=1.0, window=None, num_splits=0, workspace=None,
+                    variant=0):
+    """Launch decode attention over a padded KV cache (include/fa2_fwd.h fa2_fwd_kvcache_variant) on the current stream of Q's
+    device.  Q, O (B, H, N_q, d), K / V (B, H_kv, S_k, d) with any strides, L (B, H, N_q) with unit last stride; cache_seqlens int32
+    (B,) on the device or None; workspace: a tensor of at least kvcache_workspace_bytes(...) bytes when num_splits resolves to more
+    than 1, else None."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    ws_ptr = None if workspace is None else workspace.data_ptr()
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_kvcache_variant(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), B, H, K.shape[1], N_q, K.shape[2], d, int(dtype_enum),
+            int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, _raw_stream(Q.device.index), int(variant))
     if rc != 0:
         _raise(rc)

@@ -1,0 +1,44 @@
+// Shared declarations of the KV-cache decode kernels (fa2_fwd_kvcache, include/fa2_fwd.h): internal.
+#pragma once
+#include "fa2_common.h"
+
+// Split granularity: split s of sequence b covers keys [s c, (s + 1) c) with c = ceil(N_k(b) / num_splits) rounded up to this.
+#define FA2_KVCACHE_KEY_TILE 64
+
+// One decode problem as fa2_fwd_kvcache hands it over, arguments already checked.  Strides in elements.
+struct Fa2DecodeProblem {
+    const void *Q, *K, *V;
+    void *O, *L;
+    int64_t qs[4], ks[4], vs[4], os[4], ls[2];
+    const int32_t *seqlens;  // device, B entries, or null (N_k = S_k)
+    int32_t B, H, H_kv, N_q, S_k, d;
+    int32_t dtype, causal;
+    int32_t wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
+    float scale;
+    int32_t num_splits;  // resolved, >= 1
+    float *o_part;       // [num_splits][B * H * N_q][d]   (num_splits > 1 only)
+    float *l_part;       // [num_splits][B * H * N_q]
+    hipStream_t stream;
+};
+
+// N_k(b) and the key range [k0, k1) of split s (device side of the rule above).
+__device__ __forceinline__ void fa2_decode_split(const int32_t *seqlens, int b, int S_k, int num_splits, int s, int &nk, int &k0,
+                                                 int &k1) {
+    int n = seqlens ? seqlens[b] : S_k;
+    n = n < 0 ? 0 : (n > S_k ? S_k : n);
+    const int c = ((n + num_splits - 1) / num_splits + FA2_KVCACHE_KEY_TILE - 1) & ~(FA2_KVCACHE_KEY_TILE - 1);
+    nk = n;
+    k0 = s * c;  // <= n + 64 * num_splits
+    k1 = k0 + c < n ? k0 + c : n;
+}
+
+bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p);
+int fa2_launch_decode_generic(const Fa2DecodeProblem &p);
+// The form AUTO takes as far as the shape alone decides it (strides and alignment are the call's): the split heuristic counts
+// the workgroups of that form.
+static inline bool fa2_decode_mfma16_shape(int32_t H, int32_t H_kv, int32_t N_q, int32_t d, int32_t dtype) {
+    return (dtype == FA2_DTYPE_F16 || dtype == FA2_DTYPE_BF16) && (d == 64 || d == 128) && H_kv >= 1 &&
+           (int64_t)(H / H_kv) * N_q <= 64;
+}
+int fa2_launch_decode_combine(const Fa2DecodeProblem &p);  // second launch, num_splits > 1 only

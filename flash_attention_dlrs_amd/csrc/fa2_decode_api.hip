@@ -1,0 +1,171 @@
+// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache and its helpers, declared in
+// include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
+// two launches (split kernels, then the combine) on the caller's stream.
+#include "fa2_decode.h"
+
+namespace {
+
+// fa2_kvcache_num_splits: enough splits to put kSplitWaves x 256 workgroups on the chip, every split at least kMinSplitTiles key
+// tiles long (judged on the capacity: the lengths live on the device).  `base` is the workgroup count of the unsplit launch of
+// the form AUTO takes for the shape: B * H_kv for the matrix form, B * H * ceil(N_q / 16) for the VALU form.  The constants are
+// read off the num_splits sweep of benchmarks/bench_decode.py ("Decode attention").
+constexpr int kChipWorkgroups = 256;  // one per CU
+constexpr int kSplitWaves = 2;
+constexpr int kMinSplitTiles = 4;
+constexpr int64_t kMaxRows = 1LL << 40;  // B * H * N_q beyond this is refused: the workspace size stays far inside int64
+
+int num_splits_auto(int64_t B, int64_t H, int64_t H_kv, int64_t N_q, int64_t S_k, int32_t d, int32_t dtype) {
+    const int64_t base = fa2_decode_mfma16_shape((int32_t)H, (int32_t)H_kv, (int32_t)N_q, d, dtype) ? B * H_kv
+                                                                                                     : B * H * ((N_q + 15) / 16);
+    if (base >= kChipWorkgroups) return 1;
+    int64_t n = (kSplitWaves * kChipWorkgroups + base - 1) / base;
+    const int64_t tiles = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE;
+    const int64_t cap = tiles / kMinSplitTiles;
+    if (n > cap) n = cap;
+    if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
+    return n < 1 ? 1 : (int)n;
+}
+
+int64_t workspace_bytes(int64_t B, int64_t H, int64_t N_q, int64_t d, int64_t num_splits) {
+    if (num_splits <= 1) return 0;
+    if (num_splits > FA2_KVCACHE_MAX_SPLITS) num_splits = FA2_KVCACHE_MAX_SPLITS;
+    const int64_t rows = B * H * N_q;  // <= 2^16 * 2^16 * 2^28
+    if (rows > kMaxRows || d > 512) return INT64_MAX;  // (4 * 128 * 2^40 * 513 < 2^63)
+    return 4 * num_splits * rows * (d + 1);
+}
+
+int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
+                const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
+                float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
+                void *hip_stream, int32_t variant) {
+    const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
+    const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
+    for (int t = 0; t < 10; ++t)
+        if (!ptrs[t]) {
+            fa2_set_error("kvcache: null %s", names[t]);
+            return FA2_ERR_BAD_ARG;
+        }
+    if (B < 1 || B > 65535) {
+        fa2_set_error("kvcache: B must be in [1, 65535] (got %d)", B);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (H < 1 || H > 65535) {
+        fa2_set_error("kvcache: H must be in [1, 65535] (got %d)", H);
+        return FA2_ERR_BAD_ARG;
+    }
+    int rc = fa2_check_gqa(H, H_kv);
+    if (rc != FA2_OK) return rc;
+    if (N_q < 1 || N_q > (1 << 28)) {
+        fa2_set_error("kvcache: N_q must be in [1, 2^28] (got %d)", N_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (S_k < 1 || S_k > (1 << 28)) {
+        fa2_set_error("kvcache: S_k must be in [1, 2^28] (got %d)", S_k);
+        return FA2_ERR_BAD_ARG;
+    }
+    if ((int64_t)B * H * N_q > kMaxRows) {
+        fa2_set_error("kvcache: B * H * N_q must be <= 2^40 (got %lld)", (long long)B * H * N_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (wl < -1 || wr < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+        return FA2_ERR_BAD_ARG;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (q_strides[k] < 0 || k_strides[k] < 0 || v_strides[k] < 0 || o_strides[k] < 0) {
+            fa2_set_error("kvcache: negative strides are not supported");
+            return FA2_ERR_BAD_ARG;
+        }
+    if (l_strides[0] < 0 || l_strides[1] < 0) {
+        fa2_set_error("kvcache: negative strides are not supported (l_strides)");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (!(scale == scale)) {
+        fa2_set_error("kvcache: scale is NaN");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (num_splits < 0 || num_splits > FA2_KVCACHE_MAX_SPLITS) {
+        fa2_set_error("kvcache: num_splits must be in [0, %d] (0 = auto), got %d", FA2_KVCACHE_MAX_SPLITS, num_splits);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (dtype_enum == FA2_DTYPE_F8E5M2 || dtype_enum == FA2_DTYPE_F8E4M3) {
+        fa2_set_error("kvcache: fp8 is not supported (e4m3fn cannot hold L = +inf)");
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (fa2_dtype_size(dtype_enum) == 0) {
+        fa2_set_error("unknown dtype enum %d", dtype_enum);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (d < 1 || d > 512) {
+        fa2_set_error("d=%d must be in [1, 512]", d);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (variant != FA2_KVCACHE_VARIANT_AUTO && variant != FA2_KVCACHE_VARIANT_GENERIC && variant != FA2_KVCACHE_VARIANT_MFMA16) {
+        fa2_set_error("kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+
+    Fa2DecodeProblem p;
+    p.Q = Q; p.K = K; p.V = V; p.O = O; p.L = L;
+    for (int k = 0; k < 4; ++k) { p.qs[k] = q_strides[k]; p.ks[k] = k_strides[k]; p.vs[k] = v_strides[k]; p.os[k] = o_strides[k]; }
+    p.ls[0] = l_strides[0]; p.ls[1] = l_strides[1];
+    p.seqlens = cache_seqlens;
+    p.B = B; p.H = H; p.H_kv = H_kv; p.N_q = N_q; p.S_k = S_k; p.d = d;
+    p.dtype = dtype_enum; p.causal = causal != 0; p.wl = wl; p.wr = wr; p.scale = scale;
+    p.num_splits = num_splits == 0 ? num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum) : num_splits;
+    p.stream = (hipStream_t)hip_stream;
+    p.o_part = nullptr; p.l_part = nullptr;
+    if (p.num_splits > 1) {
+        const int64_t need = workspace_bytes(B, H, N_q, d, p.num_splits);
+        if (!workspace || workspace_bytes_given < need) {
+            fa2_set_error("kvcache: workspace of %lld bytes needed for num_splits=%d (fa2_kvcache_workspace_bytes), got %s%lld",
+                          (long long)need, p.num_splits, workspace ? "" : "null, ", (long long)workspace_bytes_given);
+            return FA2_ERR_BAD_ARG;
+        }
+        p.o_part = (float *)workspace;
+        p.l_part = p.o_part + (int64_t)p.num_splits * B * H * N_q * d;
+    }
+    if (variant == FA2_KVCACHE_VARIANT_AUTO)
+        variant = fa2_decode_mfma16_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
+    rc = variant == FA2_KVCACHE_VARIANT_MFMA16 ? fa2_launch_decode_mfma16(p) : fa2_launch_decode_generic(p);
+    if (rc != FA2_OK || p.num_splits == 1) return rc;
+    return fa2_launch_decode_combine(p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fa2_fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                    const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
+                    const int32_t *cache_seqlens, int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d,
+                    int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                    void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
+                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
+                       FA2_KVCACHE_VARIANT_AUTO);
+}
+
+int fa2_fwd_kvcache_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                            const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                            const int64_t l_strides[2], const int32_t *cache_seqlens, int32_t B, int32_t H, int32_t H_kv,
+                            int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
+                            int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
+                            void *hip_stream, int32_t variant) {
+    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
+                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
+                       variant);
+}
+
+int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {
+    if (B < 1 || H < 1 || N_q < 1 || d < 1 || B > 65535 || H > 65535 || N_q > (1 << 28)) return 0;
+    return workspace_bytes(B, H, N_q, d, num_splits);
+}
+
+int32_t fa2_kvcache_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum) {
+    if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
+    return num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum);
+}
+
+}  // extern "C"

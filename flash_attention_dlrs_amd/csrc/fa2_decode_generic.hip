@@ -1,0 +1,224 @@
+// fa2_decode_generic.hip -- the catch-all KV-cache decode kernel (fa2_fwd_kvcache, FA2_KVCACHE_VARIANT_GENERIC): every
+// supported dtype (f64, f32, f16, bf16), any strides, any d in [1, 512], any g * N_q.  The arithmetic and the work split inside
+// a workgroup are fa2_generic.hip's varlen form (16 query rows per workgroup, 4 per wave, lane = key for the scores, lane =
+// output column for P.V); on top of it the keys of one sequence are split across workgroups as the MFMA form splits them
+// (fa2_decode.h), each (split, row) writing a normalised fp32 partial O_s and its log2-domain L_s to the workspace for the
+// combine launch -- or, with one split, O and L directly in the I/O dtype.
+//
+// Stale cache rows never reach the output: K rows are loaded for keys below the split's end only (<= N_k), masked scores are
+// selected to -inf, and the P.V loop stops at the split's end, so no V row past N_k is read at all.
+//
+// K and V of a KV head are read once per QUERY head here, and a 16-row tile holds N_q useful rows: this is the fallback behind
+// fa2_decode_mfma16.hip, correct for any N_q but not a performance path at large N_q.
+#include <math.h>
+
+#include "fa2_decode.h"
+#include "fa2_elem.h"
+
+namespace {
+
+constexpr int kRowsPerWave = 4;
+constexpr int kWaves = 4;
+constexpr int kBr = kRowsPerWave * kWaves;
+constexpr int kBc = 64;  // one key per lane
+
+template <typename A> __device__ __forceinline__ A exp2_acc(A x);
+template <> __device__ __forceinline__ float exp2_acc<float>(float x) { return exp2f(x); }
+template <> __device__ __forceinline__ double exp2_acc<double>(double x) { return exp2(x); }
+template <typename A> __device__ __forceinline__ A log2_acc(A x);
+template <> __device__ __forceinline__ float log2_acc<float>(float x) { return log2f(x); }
+template <> __device__ __forceinline__ double log2_acc<double>(double x) { return log2(x); }
+
+template <typename A> __device__ __forceinline__ A wave_max(A v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const A t = __shfl_xor(v, o, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+template <typename A> __device__ __forceinline__ A wave_sum(A v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct DecodeGenericArgs {
+    const void *Q, *K, *V;
+    void *O, *L;
+    int64_t qs[4], ks[4], vs[4], os[4], ls[2];
+    const int32_t *seqlens;
+    int H, gqa, N_q, S_k, d, causal, wl, wr, num_splits, nqt;
+    float *o_part, *l_part;
+    double c_log2e;
+};
+
+// grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d / 64).
+template <class E, int DPL>
+__global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const DecodeGenericArgs a) {
+    using A = typename E::acc_t;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    A *q_lds = (A *)smem_raw;              // [kBr][d]
+    A *p_lds = q_lds + (size_t)kBr * a.d;  // [kWaves][kRowsPerWave][kBc]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int split = blockIdx.x / a.nqt, i = blockIdx.x - split * a.nqt;
+    const int b = blockIdx.y, h = blockIdx.z;
+    const int N = a.N_q, d = a.d;
+    int NK, k0, k1;
+    fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
+    const int hk = h / a.gqa;
+    const int64_t q_off = b * a.qs[0] + h * a.qs[1];
+    const int64_t k_off = b * a.ks[0] + hk * a.ks[1];
+    const int64_t v_off = b * a.vs[0] + hk * a.vs[1];
+
+    for (int idx = tid; idx < kBr * d; idx += kWaves * 64) {
+        const int r = idx / d, x = idx - r * d;
+        int row = i * kBr + r;
+        row = row < N ? row : N - 1;
+        q_lds[idx] = E::load(a.Q, q_off + (int64_t)row * a.qs[2] + (int64_t)x * a.qs[3]);
+    }
+    __syncthreads();
+
+    const A c = sizeof(A) == 8 ? (A)a.c_log2e : (A)(float)a.c_log2e;
+    const int row0 = i * kBr + wave * kRowsPerWave;
+    A m[kRowsPerWave], lsum[kRowsPerWave], o[kRowsPerWave][DPL];
+#pragma unroll
+    for (int r = 0; r < kRowsPerWave; ++r) {
+        m[r] = -INFINITY;
+        lsum[r] = 0;
+#pragma unroll
+        for (int cc = 0; cc < DPL; ++cc) o[r][cc] = 0;
+    }
+
+    // the keys of this split that the band of the workgroup's 16 rows touches (same trip count for every wave: barriers inside)
+    int wl, wr;
+    fa2_varlen_band(N, NK, a.causal, a.wl, a.wr, wl, wr);
+    const int kbeg = i * kBr - wl > k0 ? i * kBr - wl : k0;
+    const int kend = i * kBr + kBr + wr < k1 ? i * kBr + kBr + wr : k1;
+    A *p_w = p_lds + (size_t)wave * kRowsPerWave * kBc;
+
+    for (int kt = kbeg; kt < kend; kt += kBc) {
+        const int key = kt + lane;
+        const bool valid = key < kend;
+        A dot[kRowsPerWave];
+#pragma unroll
+        for (int r = 0; r < kRowsPerWave; ++r) dot[r] = 0;
+        if (valid) {
+            const int64_t kb = k_off + (int64_t)key * a.ks[2];
+            for (int x = 0; x < d; ++x) {
+                const A kx = E::load(a.K, kb + (int64_t)x * a.ks[3]);
+#pragma unroll
+                for (int r = 0; r < kRowsPerWave; ++r) dot[r] += q_lds[(wave * kRowsPerWave + r) * d + x] * kx;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsPerWave; ++r) {
+            A s = dot[r] * c;
+            if (!valid || key < row0 + r - wl || key > row0 + r + wr) s = -INFINITY;  // selected, never multiplied
+            const A mx = wave_max(s);
+            const A m_new = m[r] > mx ? m[r] : mx;
+            // while a row's maximum is -inf, P and the rescale factor are 0 (not exp2(-inf + inf))
+            const A m_use = m_new == -INFINITY ? (A)0 : m_new;
+            const A p = exp2_acc<A>(s - m_use);
+            const A coeff = exp2_acc<A>(m[r] - m_use);
+            lsum[r] = coeff * lsum[r] + p;
+#pragma unroll
+            for (int cc = 0; cc < DPL; ++cc) o[r][cc] *= coeff;
+            m[r] = m_new;
+            p_w[r * kBc + lane] = E::round(p);
+        }
+        __syncthreads();
+        const int kmax = (kend - kt) < kBc ? (kend - kt) : kBc;
+        for (int kk = 0; kk < kmax; ++kk) {
+            const int64_t vb = v_off + (int64_t)(kt + kk) * a.vs[2];
+            A pr[kRowsPerWave];
+#pragma unroll
+            for (int r = 0; r < kRowsPerWave; ++r) pr[r] = p_w[r * kBc + kk];
+#pragma unroll
+            for (int cc = 0; cc < DPL; ++cc) {
+                const int x = lane + 64 * cc;
+                if (x < d) {
+                    const A v = E::load(a.V, vb + (int64_t)x * a.vs[3]);
+#pragma unroll
+                    for (int r = 0; r < kRowsPerWave; ++r) o[r][cc] += pr[r] * v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int r = 0; r < kRowsPerWave; ++r) {
+        const int row = row0 + r;
+        const A l = wave_sum(lsum[r]);
+        if (row >= N) continue;
+        if (a.num_splits == 1) {  // a row without a visible key: O = 0, L = +inf
+            const int64_t o_off = b * a.os[0] + h * a.os[1] + (int64_t)row * a.os[2];
+#pragma unroll
+            for (int cc = 0; cc < DPL; ++cc) {
+                const int x = lane + 64 * cc;
+                if (x < d) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? o[r][cc] / l : (A)0);
+            }
+            if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
+        } else {  // every (split, row) is written, an empty split as O_s = 0, L_s = -inf: the workspace arrives uninitialised
+            const int64_t rows = (int64_t)gridDim.y * a.H * N;
+            const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + h) * N + row;
+#pragma unroll
+            for (int cc = 0; cc < DPL; ++cc) {
+                const int x = lane + 64 * cc;
+                if (x < d) a.o_part[prow * d + x] = l > 0 ? (float)(o[r][cc] / l) : 0.0f;
+            }
+            if (lane == 0) a.l_part[prow] = l > 0 ? (float)(m[r] + log2_acc<A>(l)) : -INFINITY;
+        }
+    }
+}
+
+template <class E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
+    const long long gx = (long long)a.num_splits * a.nqt;
+    if (gx > 0x7fffffffLL) {
+        fa2_set_error("kvcache generic kernel: grid too large (num_splits * ceil(N_q / 16) = %lld)", gx);
+        return FA2_ERR_BAD_ARG;
+    }
+    const dim3 grid((unsigned)gx, p.B, p.H), block(kWaves * 64);
+    const size_t smem = sizeof(typename E::acc_t) * ((size_t)kBr * p.d + (size_t)kWaves * kRowsPerWave * kBc);
+    const int dpl = (p.d + 63) / 64;
+    static Fa2DeviceLatch attr_done;  // d > 256 in double asks for more than 64 KiB of dynamic LDS: opt in, once per device
+    if (dpl > 4 && attr_done.need()) {
+        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(sizeof(typename E::acc_t) * ((size_t)kBr * 512 + (size_t)kWaves * kRowsPerWave * kBc)));
+        attr_done.mark();
+    }
+    if (dpl <= 1) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 1>), grid, block, smem, p.stream, a);
+    else if (dpl <= 2) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 2>), grid, block, smem, p.stream, a);
+    else if (dpl <= 4) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 4>), grid, block, smem, p.stream, a);
+    else hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 8>), grid, block, smem, p.stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fa2_set_error("kvcache generic kernel launch failed: %s", hipGetErrorString(e));
+        return FA2_ERR_LAUNCH;
+    }
+    return FA2_OK;
+}
+
+}  // namespace
+
+int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
+    DecodeGenericArgs a;
+    a.Q = p.Q; a.K = p.K; a.V = p.V; a.O = p.O; a.L = p.L;
+    for (int k = 0; k < 4; ++k) { a.qs[k] = p.qs[k]; a.ks[k] = p.ks[k]; a.vs[k] = p.vs[k]; a.os[k] = p.os[k]; }
+    a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
+    a.seqlens = p.seqlens;
+    a.H = p.H; a.gqa = p.H / p.H_kv; a.N_q = p.N_q; a.S_k = p.S_k; a.d = p.d; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
+    a.num_splits = p.num_splits;
+    a.nqt = (p.N_q + kBr - 1) / kBr;
+    a.o_part = p.o_part; a.l_part = p.l_part;
+    a.c_log2e = (double)p.scale * FA2_LOG2E;
+    switch (p.dtype) {
+    case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);
+    case FA2_DTYPE_F16: return launch_e<ElemF16>(p, a);
+    case FA2_DTYPE_BF16: return launch_e<ElemBF16>(p, a);
+    case FA2_DTYPE_F64: return launch_e<ElemF64>(p, a);
+    default: fa2_set_error("kvcache: dtype enum %d is not supported", p.dtype); return FA2_ERR_UNSUPPORTED;
+    }
+}

@@ -118,3 +118,53 @@ def flash_attention_varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_
         raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
     return varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
                            scale=scale, window=window, variant=variant)
+
+
+def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits):
+    """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, cache_seqlens, window, num_splits).  Pure:
+    takes CPU tensors as well (the CUDA-device check is the launch's)."""
+    if Q.dim() != 4 or K_cache.dim() != 4 or V_cache.dim() != 4 or K_cache.shape != V_cache.shape \
+            or Q.shape[0] != K_cache.shape[0] or Q.shape[3] != K_cache.shape[3] or Q.shape[2] < 1 or K_cache.shape[2] < 1:
+        raise ValueError(f"kvcache: Q must be (B, H, N_q, d) and K_cache, V_cache (B, H_kv, S_k, d) with N_q, S_k >= 1: got Q "
+                         f"{tuple(Q.shape)}, K_cache {tuple(K_cache.shape)}, V_cache {tuple(V_cache.shape)}")
+    # the head rule of the dense entry points, on views that drop the sequence axis (N_q and S_k differ here)
+    gqa_kv_heads(Q[:, :, :1], K_cache[:, :, :1], V_cache[:, :, :1])
+    if Q.dtype != K_cache.dtype or K_cache.dtype != V_cache.dtype:
+        raise ValueError("kvcache: Q, K_cache, V_cache must have the same dtype")
+    if Q.dtype in (torch.float8_e5m2, torch.float8_e4m3fn):
+        raise ValueError(f"kvcache: dtype {Q.dtype} is not supported (e4m3fn cannot hold L = +inf)")
+    convert_triton_dtype(Q.dtype)
+    if cache_seqlens is not None:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 \
+                or not cache_seqlens.is_contiguous() or cache_seqlens.numel() != Q.shape[0]:
+            raise ValueError(f"kvcache: cache_seqlens must be a contiguous int32 tensor of B = {Q.shape[0]} entries (or None)")
+        if cache_seqlens.device != Q.device:
+            raise ValueError(f"kvcache: cache_seqlens must be on Q's device ({Q.device}), got {cache_seqlens.device}")
+    if window is not None:
+        normalize_window(1, False, window)  # the sides' own rules (pair of ints >= -1); the shift is per sequence
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _lib.KVCACHE_MAX_SPLITS:
+        raise ValueError(f"kvcache: num_splits must be an int in [0, {_lib.KVCACHE_MAX_SPLITS}] (0 = auto), got {num_splits!r}")
+
+
+def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, causal=False, scale=1.0, window=None, num_splits=0,
+                                    variant="auto"):
+    """Decode attention over a padded KV cache, split-KV (include/fa2_fwd.h fa2_fwd_kvcache) -> (O, L).  Q (B, H, N_q, d);
+    K_cache, V_cache (B, H_kv, S_k, d) of capacity S_k, any strides (a flash-attn (B, S, H_kv, d) cache: pass its
+    .transpose(1, 2) view), H_kv dividing H; cache_seqlens int32 (B,) on Q's device, sequence b attends to its first
+    cache_seqlens[b] keys (None: all S_k).  causal / window are bottom-right aligned as in the varlen call.  O (B, H, N_q, d)
+    contiguous, L (B, H, N_q) log2-domain, both in Q's dtype; rows without a visible key get O = 0, L = +inf.  num_splits = 0
+    lets the library choose; variant is one of _lib.KVCACHE_VARIANTS.  No autograd, no autotuner."""
+    check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits)
+    if variant not in _lib.KVCACHE_VARIANTS:
+        raise ValueError(f"kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
+    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
+        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+    B, H, N_q, d = Q.shape
+    dtype = convert_triton_dtype(Q.dtype)
+    O = torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device)
+    L = torch.empty(B, H, N_q, dtype=Q.dtype, device=Q.device)
+    n = num_splits or _lib.kvcache_num_splits(B, H, K_cache.shape[1], N_q, K_cache.shape[2], d, dtype)
+    ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    _lib.fa2_fwd_kvcache(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, causal=causal, scale=scale, window=window, num_splits=n,
+                         workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
+    return O, L

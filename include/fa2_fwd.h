@@ -226,6 +226,63 @@ int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void
                                int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                                int32_t window_right, void *hip_stream, int32_t variant);
 
+/*
+ * Decode attention over a padded KV cache, split-KV (flash-decoding).  Forward only.
+ *
+ *   Shapes.   Q, O are (B, H, N_q, d), L is (B, H, N_q); K, V are (B, H_kv, S_k, d): S_k is the cache CAPACITY.  All strides are
+ *             element strides in that logical order, as fa2_fwd_gqa takes them (a flash-attn (B, S, H, d) cache is a transposed
+ *             view); l_strides = {LB, LH}, unit stride over N_q.  H % H_kv == 0, query head h reads KV head h / (H / H_kv).
+ *   Lengths.  cache_seqlens: device int32 array of B entries; sequence b has N_k(b) = clamp(cache_seqlens[b], 0, S_k) keys.  A null
+ *             pointer means N_k = S_k for every b.  Rows >= N_k(b) of K and V are never read: they may hold anything, NaN included.
+ *   Mask.     causal and (window_left, window_right) are fa2_fwd_varlen's definitions, bottom-right aligned with the shift
+ *             N_k(b) - N_q; with N_q = 1 causal masks nothing.  A row without a visible key gets O = 0 and L = +inf.
+ *   Dtypes.   f64, f32, f16, bf16; fp8 returns FA2_ERR_UNSUPPORTED, as in varlen.  L is the log2-domain log-sum-exp in dtype_enum.
+ *   Splits.   The keys of a sequence are split across num_splits workgroups: split s covers keys [s c, (s + 1) c) with
+ *             c = ceil(N_k(b) / num_splits) rounded up to 64.  num_splits = 0 picks fa2_kvcache_num_splits(...), a host heuristic
+ *             on the capacity.  With num_splits > 1 the split kernels leave fp32 partials in `workspace` and a second launch on the
+ *             same stream combines them; the caller owns the workspace (fa2_kvcache_workspace_bytes(...) bytes, 16-byte aligned,
+ *             uninitialised is fine) and may reuse it once the stream has passed the call.  With num_splits resolving to 1 the
+ *             workspace is neither read nor written and may be null.
+ *   Variants. FA2_KVCACHE_VARIANT_MFMA16: f16 / bf16, d in {64, 128}, unit d-stride, 16-byte aligned rows, scale > 0 and
+ *             (H / H_kv) * N_q <= 64: the query heads of a group share one matrix tile, so K and V are read once per KV head.
+ *             FA2_KVCACHE_VARIANT_GENERIC: every dtype above, any strides, any d in [1, 512], any N_q, on the VALU; K and V are read
+ *             once per query head and large N_q is correct but not a performance goal.  FA2_KVCACHE_VARIANT_AUTO: MFMA16 where it
+ *             runs, else GENERIC.  A forced MFMA16 on a problem it cannot run returns FA2_ERR_UNSUPPORTED.
+ *
+ * FA2_ERR_BAD_ARG before any launch, the message naming the argument, for: null Q / K / V / O / L or strides, B or H outside
+ * [1, 65535], H_kv < 1 or H % H_kv != 0 ("H_kv"), N_q < 1, S_k < 1, N_q or S_k > 2^28, B * H * N_q > 2^40, a window side < -1, a negative stride,
+ * num_splits < 0 or > FA2_KVCACHE_MAX_SPLITS, num_splits resolving to more than 1 with a null or too small workspace ("workspace").
+ * FA2_ERR_UNSUPPORTED for fp8, an unknown dtype or variant, d outside [1, 512].
+ */
+#define FA2_KVCACHE_VARIANT_AUTO 0
+#define FA2_KVCACHE_VARIANT_GENERIC 1
+#define FA2_KVCACHE_VARIANT_MFMA16 2
+#define FA2_KVCACHE_MAX_SPLITS 128
+
+int fa2_fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L,
+                    const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                    const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                    int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum,
+                    int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                    void *workspace, int64_t workspace_bytes, void *hip_stream);
+
+int fa2_fwd_kvcache_variant(const void *Q, const void *K, const void *V, void *O, void *L,
+                            const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                            const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                            int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum,
+                            int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                            void *workspace, int64_t workspace_bytes, void *hip_stream, int32_t variant);
+
+/* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
+ * elements plus fp32 partial L of num_splits * B * H * N_q. */
+int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits);
+
+/* What num_splits = 0 resolves to, in [1, FA2_KVCACHE_MAX_SPLITS]: 1 when the unsplit launch already has 256 workgroups, else enough
+ * splits for two workgroups per CU, every split at least 4 key tiles (256 keys) of the capacity S_k.  The unsplit launch is counted
+ * for the form AUTO takes as far as the shape decides it: B * H_kv workgroups for f16 / bf16 at d 64 / 128 with
+ * (H / H_kv) * N_q <= 64 (the matrix form), B * H * ceil(N_q / 16) otherwise (the VALU form); strides and alignment are not seen. */
+int32_t fa2_kvcache_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum);
+
 /* Which tile the static table picks for a contiguous problem: out4 = {variant, B_r, B_c, waves}.
  * Counterpart of fwd_conf_prune + the autotuner's choice (src/autotune_configs.py:176-194). */
 int fa2_query_tile(int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, int32_t out4[4]);
