@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the FA-2 forward hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--variant auto] [--gather] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--variant auto] [--gather] [--dump-outputs DIR] [--full]
 
 One "step" = one forward pass of the hot path (flash_attention_forward -> C ABI -> HIP kernel) over one
 batch of synthetic input that is already resident in HBM.  The workload is BASELINE.json's metric
@@ -14,6 +14,11 @@ N > 1 (launched by torch.distributed.run, one rank per GPU, backend nccl = RCCL)
 G-times-wider problem (weak scaling); value = total FLOPs of all ranks / max-over-ranks time.  The
 optional exchange step of the north star, an RCCL all-gather of the output shards over xGMI, is timed
 separately after the main region and reported under "gather" (use --gather to put it inside the step).
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the line.  --full adds every side
+measurement to the same line: per-launch kernel times (a second pass of K steps), the committed profile figures of the roofline
+object, `extras` (scaled inputs, no mask, backward, gather, strong scaling) and `cpu_baseline`; --no-extras and --no-cpu-baseline
+leave one of the two out of a --full run.
 
 Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step returned on rank 0, O and L, as
 DIR/O.npy and DIR/L.npy in float32 (see dump_outputs): the inputs are seeded, so two builds can be compared output for output.
@@ -330,8 +335,10 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--variant", default="auto")
     ap.add_argument("--gather", action="store_true", help="include the RCCL all-gather of O in the timed step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the scaled-input and gather side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: per-launch kernel times, profile figures, extras, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the scaled-input, backward and gather side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write the O and L the last timed step returned (rank 0) as DIR/O.npy and DIR/L.npy, float32; "
                          f"a fixed seeded sample of an array larger than {DUMP_MAX_ELEMS} elements")
@@ -391,7 +398,7 @@ def main():
     # stream).  One event PAIR PER STEP, as in round 1, put two marker packets between consecutive launches -- 9.5 us of
     # idle GPU per 457 us kernel, i.e. the measurement cost 2 % of `value`; the average launch duration is the bracket
     # divided by K (it includes the launch-to-launch gap, so it can only overstate the kernel).  Per-launch events for
-    # the median / minimum run in a second, untimed pass of the same K steps.
+    # the median / minimum run in a second, untimed pass of the same K steps (--full only).
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     sync_all()
     # (a blocking synchronize hands control back tens of microseconds after the GPU has gone idle, and an idle GPU takes as long
@@ -415,13 +422,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     kern_avg = ev0.elapsed_time(ev1) / args.steps
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for s, e in ev:
-        s.record()
-        step()
-        e.record()
-    torch.cuda.synchronize(dev)
-    kern_ms = sorted(s.elapsed_time(e) for s, e in ev)
+    kern_ms = None
+    if args.full:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for s, e in ev:
+            s.record()
+            step()
+            e.record()
+        torch.cuda.synchronize(dev)
+        kern_ms = sorted(s.elapsed_time(e) for s, e in ev)
 
     F = flops(c)
     ms_per_step = el * 1e3 / args.steps
@@ -431,7 +440,7 @@ def main():
     tile = _lib.query_tile(c["N"], c["d"], {"bf16": 2, "fp16": 1, "f32": 0, "fp8": 4}[c["dtype"]], c["causal"], B=c["B"], H=c["H"])
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (1) inputs scaled by d^-1/4 (== the usual 1/sqrt(d)): softmax no longer nearly one-hot
         s4 = c["d"] ** -0.25
         Q2, K2 = (Q.float() * s4).to(dtype), (K.float() * s4).to(dtype)
@@ -497,11 +506,11 @@ def main():
             extras["strong_scaling"] = strong_scaling(STRONG[world], world, rank, dev, sync_all)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(c)
 
     picked = {v: k for k, v in _lib.VARIANTS.items()}.get(tile[0], variant)      # the name of the kernel the table picked
-    traffic = profiled_traffic(args.config, picked) if args.variant == "auto" else None
+    traffic = profiled_traffic(args.config, picked) if args.full and args.variant == "auto" else None
     if rank == 0:
         out = {
             "metric": f"attention fwd TFLOP/s per GPU (B={c['B']},H={c['H']},N={c['N']},d={c['d']} {c['dtype']}); % MFMA peak",
@@ -514,18 +523,21 @@ def main():
                                                            "waves": tile[3]},
                        "sharding": "heads" if world > 1 else "none",
                        "flops_per_step_per_gpu": F, "pct_of_mfma_peak": round(100 * value / world / peak, 2)},
+            "full": bool(args.full),
+            # from the timed bracket itself; --full adds the profile figures and the per-launch pass below
             "roofline": {"bound": "mfma", "achieved": round(achieved, 3), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic[0] if traffic else None,
-                         "traffic_source": traffic[1] if traffic else None,
+                         "frac": round(achieved / peak, 4),
                          "algorithmic_bytes": (4 * c["d"] + 1) * c["B"] * c["H"] * c["N"] * Q.element_size(),
-                         "kernel_ms_avg": round(kern_avg, 5), "kernel_ms_median": round(kern_ms[len(kern_ms) // 2], 5),
-                         "kernel_ms_min": round(kern_ms[0], 5),
-                         "measured_mfma_only_peak": measured_peak(c["dtype"])},
+                         "kernel_ms_avg": round(kern_avg, 5)},
             "cpu_baseline": cpu,
             "extras": extras,
             "n_ranks_seen_by_rccl": dist.get_world_size() if grouped else None,
             "lib": _lib.version(),
         }
+        if args.full:
+            out["roofline"].update({"traffic": traffic[0] if traffic else None, "traffic_source": traffic[1] if traffic else None,
+                                    "kernel_ms_median": round(kern_ms[len(kern_ms) // 2], 5), "kernel_ms_min": round(kern_ms[0], 5),
+                                    "measured_mfma_only_peak": measured_peak(c["dtype"])})
         print(json.dumps(out))
         if args.dump_outputs:
             O_last, L_last = last

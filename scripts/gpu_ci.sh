@@ -15,4 +15,4 @@ step() {  # step <name> <timeout_s> <cmd...>
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 1000 python -m pytest tests -m gpu -q --timeout=900 "${PYTEST_ARGS:---maxfail=8}"
-step bench 400 python bench.py --steps 30 --warmup 5
+step bench 400 python bench.py --steps 30 --warmup 5 --full

@@ -15,7 +15,7 @@ step() {
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 1100 python -m pytest tests -m gpu -q --timeout=900 --maxfail=8
-step bench 400 python bench.py --steps 100 --warmup 20
+step bench 400 python bench.py --steps 100 --warmup 20 --full
 rm -rf gpurun_out/prof
 step prof 900 bash scripts/gpu_prof.sh
 rm -rf gpurun_out/prof_bwd

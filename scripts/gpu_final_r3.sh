@@ -16,12 +16,12 @@ step() {
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 [ -n "${SKIP_TESTS:-}" ] || step pytest_gpu 1100 python -m pytest tests -m gpu -q --timeout=900 --maxfail=8
-step bench_20_5 400 python bench.py --steps 20 --warmup 5
-step bench_100_20 400 python bench.py --steps 100 --warmup 20 --no-cpu-baseline
-step bench_c3nc 300 python bench.py --config c3_noncausal --steps 50 --warmup 10 --no-cpu-baseline --no-extras
-step bench_c4 300 python bench.py --config c4_per_gpu --steps 30 --warmup 10 --no-cpu-baseline --no-extras
-step bench_c5 300 python bench.py --config c5_per_gpu --steps 10 --warmup 3 --no-cpu-baseline --no-extras
-step bench_c2 300 python bench.py --config c2 --steps 200 --warmup 50 --no-cpu-baseline --no-extras
+step bench_20_5 400 python bench.py --steps 20 --warmup 5 --full
+step bench_100_20 400 python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline
+step bench_c3nc 300 python bench.py --config c3_noncausal --steps 50 --warmup 10 --full --no-cpu-baseline --no-extras
+step bench_c4 300 python bench.py --config c4_per_gpu --steps 30 --warmup 10 --full --no-cpu-baseline --no-extras
+step bench_c5 300 python bench.py --config c5_per_gpu --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras
+step bench_c2 300 python bench.py --config c2 --steps 200 --warmup 50 --full --no-cpu-baseline --no-extras
 PROF_OUT=prof_c3 step prof_c3 900 bash scripts/gpu_prof.sh
 PROF_OUT=prof_c4 BENCH_ARGS="--config c4_per_gpu --steps 10 --warmup 3 --no-cpu-baseline --no-extras" step prof_c4 900 bash scripts/gpu_prof.sh
 PROF_OUT=prof_c5 BENCH_ARGS="--config c5_per_gpu --steps 6 --warmup 2 --no-cpu-baseline --no-extras" step prof_c5 900 bash scripts/gpu_prof.sh

@@ -7,7 +7,7 @@ OUT=gpurun_out/kernarg.log
 for v in 0 1; do
   echo "HIP_FORCE_DEV_KERNARG=$v" >> $OUT
   HIP_FORCE_DEV_KERNARG=$v FA2_HIP_LIB=$PWD/flash_attention_dlrs_amd/libfa2_hip_stamps.so FA2_A64_KERNEL=fa2_fwd_a64_bf16_c_lite timeout -k 10 120 python benchmarks/a64_stamps.py c3 >> $OUT 2>&1 || exit 4
-  HIP_FORCE_DEV_KERNARG=$v timeout -k 10 200 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras >> $OUT 2>&1 || exit 5
+  HIP_FORCE_DEV_KERNARG=$v timeout -k 10 200 python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-extras >> $OUT 2>&1 || exit 5
 done
 grep -v amdgpu.ids $OUT | python -c "
 import sys, json

@@ -5,8 +5,8 @@ set -u
 cd "$(dirname "$0")/.."
 O=gpurun_out/r3_bounds
 mkdir -p $O
-for k in 1 2; do timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_20_5_$k.json 2> $O/bench_20_5_$k.err || exit 2; done
-timeout -k 10 200 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras > $O/bench_100_20.json 2> $O/err || exit 2
+for k in 1 2; do timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_20_5_$k.json 2> $O/bench_20_5_$k.err || exit 2; done
+timeout -k 10 200 python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-extras > $O/bench_100_20.json 2> $O/err || exit 2
 python - <<'P'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r3_bounds/bench_*.json')):

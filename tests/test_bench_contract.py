@@ -1,5 +1,5 @@
-"""bench.py prints ONE JSON line that carries the driver's contract fields, the roofline and cpu_baseline
-objects; also exercised through torch.distributed.run (world_size 1) so the N > 1 code path (process group,
+"""bench.py prints ONE JSON line that carries the driver's contract fields; a plain run measures the headline figure alone,
+--full adds the side measurements (roofline profile figures, extras, cpu_baseline) to the same line; also exercised through torch.distributed.run (world_size 1) so the N > 1 code path (process group,
 barrier, max-over-ranks, sharded gather) at least executes on one GPU."""
 import json
 import os
@@ -25,15 +25,30 @@ def _run(cmd):
     return json.loads(lines[0])
 
 
+def test_plain_run_measures_the_headline_figure_alone():
+    j = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert REQUIRED <= set(j) and j["full"] is False
+    assert j["n_gpus"] == 1 and j["steps"] == 5 and j["warmup"] == 2 and j["higher_is_better"] is True
+    assert j["unit"] == "TFLOP/s" and j["dtype"] == "bf16" and j["value"] > 0 and j["ms_per_step"] > 0
+    assert "N=4096" in j["metric"] and "variant" in j["config"]["tile"]
+    # nothing that takes a run of its own: no CPU leg, no side measurements, no per-launch pass, no profile figures
+    assert j["cpu_baseline"] is None and j["extras"] == {}
+    r = j["roofline"]
+    assert not {"kernel_ms_median", "kernel_ms_min", "traffic", "measured_mfma_only_peak"} & set(r)
+    assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and 0 < r["frac"] < 1 and r["kernel_ms_avg"] > 0
+
+
 def test_single_process_json_contract():
-    j = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2"])
-    assert REQUIRED <= set(j)
+    j = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--full"])
+    assert REQUIRED <= set(j) and j["full"] is True
     assert j["n_gpus"] == 1 and j["steps"] == 5 and j["warmup"] == 2 and j["higher_is_better"] is True
     assert j["unit"] == "TFLOP/s" and j["dtype"] == "bf16" and j["data"] == "synthetic" and j["vs_baseline"] is None
     assert "workload" in j["config"] and "model" not in j["config"]
     r = j["roofline"]
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and r["peak"] == 2500.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and 0 < r["frac"] < 1
+    assert 0 < r["kernel_ms_min"] <= r["kernel_ms_median"] and {"traffic", "traffic_source", "measured_mfma_only_peak"} <= set(r)
+    assert {"tflops_inputs_scaled_d^-1/4", "same_shape_no_mask", "backward"} <= set(j["extras"])
     c = j["cpu_baseline"]
     assert c["kind"] in ("reference", "port") and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
     assert j["value"] > 50 * c["value"]  # sanity: the GPU path is not the CPU path
@@ -42,7 +57,7 @@ def test_single_process_json_contract():
 def test_distributed_launcher_world1():
     j = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
               "--master-addr", "127.0.0.1", "--master-port", "29541", "bench.py", "--gpus", "1", "--steps", "3",
-              "--warmup", "1", "--no-cpu-baseline", "--gather"])
+              "--warmup", "1", "--full", "--no-cpu-baseline", "--gather"])
     assert j["n_gpus"] == 1 and j["value"] > 0
     # launched by torch.distributed.run the bench initialises the nccl (= RCCL) group even at world size 1 and --gather puts
     # the all-gather of O into the step
