@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""KV-cache decode attention timing (fa2_fwd_kvcache), bf16; JSON lines appended to profiles/decode/bench_decode.jsonl.
+"""KV-cache decode attention timing (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8), bf16; JSON lines appended to profiles/decode/bench_decode.jsonl.
 
 Sides, alternated in one process after every shape has been warmed:
   decode: flash_attention_kvcache_forward, AUTO variant and auto num_splits;
@@ -17,7 +17,13 @@ Records:
   kind=sweep    the events figure of the decode side for num_splits in {1, 2, 4, 8, 16, 32, 64} on the first four shapes (--sweep);
   kind=sweep_kernels  the same sweep in kernel time (--rocprof DIR --sweep): one traced child per shape runs the split counts one
                 after the other, and the dispatches of the kernel trace are cut into the split counts by their order (split kernel
-                plus combine per call; one kernel for num_splits = 1)."""
+                plus combine per call; one kernel for num_splits = 1).
+
+--kv-dtype e4m3 | e5m2 adds the fp8-cache decode (fa2_fwd_kvcache_fp8; the same K and V through quantize_kv_cache, per-(b, h_kv)
+descales) as one more side, decode_fp8, alternated with the others in the same process; records go to bench_decode_fp8.jsonl.
+The combine kernel is common to the two decode sides, so kind=kernels is then read off the kernel trace (each combine belongs
+to the split kernel in front of it; the first 3 calls of a side are its warm-up) instead of the stats file; fp8_over_16 is the
+ratio of the two decode averages and hbm_share_fp8 counts the fp8 bytes.  The sweeps then run the fp8 side."""
 import argparse
 import csv
 import glob
@@ -30,6 +36,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "decode", "bench_decode.jsonl")
+OUT_FP8 = os.path.join(ROOT, "profiles", "decode", "bench_decode_fp8.jsonl")
+KV_DTYPES = ("same", "e4m3", "e5m2")
 HBM_COPY_RATE = 6.29e12  # bytes / s, measured copy rate of the MI355X
 
 CASES = {  # name: (B, H, H_kv, N_k, d, N_q)
@@ -61,7 +69,7 @@ def ragged_lengths(B, lo, hi):
 
 
 class Case:
-    def __init__(self, name, dev):
+    def __init__(self, name, dev, kv_dtype="same"):
         import torch
         from flash_attention_dlrs_amd import _lib
         from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
@@ -93,6 +101,17 @@ class Case:
         self.O = torch.empty(B, H, N_q, d, dtype=torch.bfloat16, device=dev)
         self.L = torch.empty(B, H, N_q, dtype=torch.bfloat16, device=dev)
         self.i = 0
+        self.kv_dtype = kv_dtype
+        if kv_dtype != "same":  # the same caches in fp8, (B, S, H_kv, d) storage as well
+            from flash_attention_dlrs_amd import quantize_kv_cache
+            fmt = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}[kv_dtype]
+            self.kv_enum = convert_triton_dtype(fmt)
+            self.kv8_bytes = self.kv_bytes // 2
+
+            def q8(t):
+                t8, ds = quantize_kv_cache(t.transpose(1, 2), fmt)
+                return t8.view(torch.uint8).transpose(1, 2).contiguous().view(fmt), ds
+            self.K8, self.V8 = [q8(t) for t in self.K], [q8(t) for t in self.V]
 
     def auto_splits(self):
         s = self.shape
@@ -109,6 +128,20 @@ class Case:
             self.i = (self.i + 1) % self.copies
             self._lib.fa2_fwd_kvcache(self.Q, self.K[self.i].transpose(1, 2), self.V[self.i].transpose(1, 2), self.O, self.L,
                                       self.lens_dev, self.enum, scale=self.scale, num_splits=n, workspace=ws)
+        return run
+
+    def decode_fp8(self, num_splits=0):
+        """The fp8-cache launch, under the same conditions."""
+        s = self.shape
+        n = num_splits or self.auto_splits()
+        words = self._lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], s["d"], n) // 4
+        ws = self.torch.empty(max(words, 1), dtype=self.torch.float32, device=self.dev)
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            (K8, kd), (V8, vd) = self.K8[self.i], self.V8[self.i]
+            self._lib.fa2_fwd_kvcache_fp8(self.Q, K8.transpose(1, 2), V8.transpose(1, 2), self.O, self.L, self.lens_dev, self.enum,
+                                          self.kv_enum, k_descale=kd, v_descale=vd, scale=self.scale, num_splits=n, workspace=ws)
         return run
 
     def varlen(self):
@@ -157,17 +190,19 @@ def run_events(names, args, fh):
     import torch
     dev = torch.device("cuda:0")
     for name in names:
-        c = Case(name, dev)
+        c = Case(name, dev, args.kv_dtype)
         sides = {"decode": c.decode(), "varlen": c.varlen()}
+        if args.kv_dtype != "same":
+            sides["decode_fp8"] = c.decode_fp8()
         if not args.no_sdpa:
             sides["sdpa"] = c.sdpa()
         res = interleaved(torch, list(sides.values()), args.iters, args.rounds)
         emit(fh, kind="events", case=name, **c.shape, ragged=c.ragged, num_splits=c.auto_splits(), kv_bytes=c.kv_bytes,
              **{k: r for k, r in zip(sides, res)})
         if args.sweep and name in SWEEP_CASES:
-            fns = [c.decode(n) for n in SWEEP_SPLITS]
+            fns = [(c.decode if args.kv_dtype == "same" else c.decode_fp8)(n) for n in SWEEP_SPLITS]
             for n, r in zip(SWEEP_SPLITS, interleaved(torch, fns, args.iters, args.rounds)):
-                emit(fh, kind="sweep", case=name, **c.shape, num_splits=n, **r)
+                emit(fh, kind="sweep", case=name, kv_dtype=args.kv_dtype, **c.shape, num_splits=n, **r)
         del c
         torch.cuda.empty_cache()
 
@@ -175,31 +210,34 @@ def run_events(names, args, fh):
 def run_pass(name, args):
     """The traced child: warm, then alternate the sides; the profiler's stats file holds the kernel times."""
     import torch
-    c = Case(name, torch.device("cuda:0"))
-    sides = [c.decode(), c.varlen()] + ([] if args.no_sdpa else [c.sdpa()])
+    c = Case(name, torch.device("cuda:0"), args.kv_dtype)
+    sides = [c.decode()] + ([] if args.kv_dtype == "same" else [c.decode_fp8()]) + [c.varlen()] + ([] if args.no_sdpa else [c.sdpa()])
     for _ in range(args.iters + 3):
         for f in sides:
             f()
     torch.cuda.synchronize()
-    print(json.dumps(dict(case=name, calls=args.iters + 3, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(), **c.shape)))
+    extra = {} if args.kv_dtype == "same" else dict(kv_dtype=args.kv_dtype, kv8_bytes=c.kv8_bytes)
+    print(json.dumps(dict(case=name, calls=args.iters + 3, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(), **extra, **c.shape)))
 
 
 def run_sweep_pass(name, args):
     """The traced child of the kernel-time sweep: the decode side alone, one split count after the other."""
     import torch
-    c = Case(name, torch.device("cuda:0"))
+    c = Case(name, torch.device("cuda:0"), args.kv_dtype)
     for n in SWEEP_SPLITS:
-        f = c.decode(n)
+        f = c.decode(n) if args.kv_dtype == "same" else c.decode_fp8(n)
         for _ in range(args.iters + 3):
             f()
         torch.cuda.synchronize()
-    print(json.dumps(dict(case=name, calls=args.iters + 3, kv_bytes=c.kv_bytes, auto_splits=c.auto_splits(), **c.shape)))
+    kv = dict(kv_bytes=c.kv_bytes) if args.kv_dtype == "same" else dict(kv_bytes=c.kv8_bytes, kv_dtype=args.kv_dtype)
+    print(json.dumps(dict(case=name, calls=args.iters + 3, auto_splits=c.auto_splits(), **kv, **c.shape)))
 
 
 def traced_child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
-           os.path.abspath(__file__), "--iters", str(args.iters)] + extra + (["--no-sdpa"] if args.no_sdpa else [])
+           os.path.abspath(__file__), "--iters", str(args.iters), "--kv-dtype", args.kv_dtype] + extra + \
+        (["--no-sdpa"] if args.no_sdpa else [])
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.child_timeout)
     if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
         sys.stderr.write(p.stdout[-2000:] + p.stderr[-2000:])
@@ -219,15 +257,15 @@ def sweep_from_trace(out, info, fh):
         assert len(seg) == per * calls and all(("combine" in r["Kernel_Name"]) == (per == 2 and k % 2 == 1) for k, r in enumerate(seg)), n
         us = [sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg[per * k:per * k + per]) / 1e3 for k in range(3, calls)]
         avg = sum(us) / len(us)
-        emit(fh, kind="sweep_kernels", case=info["case"], num_splits=n, auto_splits=info["auto_splits"], avg_us=round(avg, 2),
+        emit(fh, kind="sweep_kernels", case=info["case"], kv_dtype=info.get("kv_dtype", "same"), num_splits=n, auto_splits=info["auto_splits"], avg_us=round(avg, 2),
              min_us=round(min(us), 2), max_us=round(max(us), 2),
              hbm_share=round(info["kv_bytes"] / (avg * 1e-6) / HBM_COPY_RATE, 3))
     assert pos == len(rows)
 
 
 def side_of(kernel):
-    if "fa2_decode" in kernel:
-        return "decode"
+    if "fa2_decode" in kernel:  # (the combine kernel, common to both decode sides, counts as "decode" here)
+        return "decode_fp8" if "Cache" in kernel else "decode"
     if "varlen" in kernel:
         return "varlen"
     low = kernel.lower()
@@ -236,10 +274,48 @@ def side_of(kernel):
     return None
 
 
+def sides_from_trace(out, info):
+    """Per-call kernel time of every side from the kernel trace, in dispatch order: a decode combine belongs to the split kernel
+    in front of it.  The first 3 calls of a side are its warm-up."""
+    trace = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
+    rows = sorted(csv.DictReader(open(trace[0])), key=lambda r: int(r["Start_Timestamp"]))
+    per_side, last = {}, None
+    for r in rows:
+        side = side_of(r["Kernel_Name"])
+        if side is None:
+            continue
+        if "combine" in r["Kernel_Name"] and "fa2_decode" in r["Kernel_Name"]:
+            side = last
+        elif side.startswith("decode"):
+            last = side
+        per_side.setdefault(side, []).append(r)
+    sides = {}
+    for side, rs in per_side.items():
+        per, calls = len(rs) // info["calls"], info["calls"]
+        if per * calls != len(rs) and not side.startswith("decode"):
+            continue  # a side whose launches per call vary (torch's choice) has no per-call figure here
+        assert per >= 1 and per * calls == len(rs), (side, len(rs), calls)
+        us = [sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rs[per * k:per * k + per]) / 1e3 for k in range(3, calls)]
+        avg = sum(us) / len(us)
+        sides[side] = dict(avg_us=round(avg, 2), min_us=round(min(us), 2), max_us=round(max(us), 2),
+                           stddev_us=round((sum((u - avg) ** 2 for u in us) / len(us)) ** 0.5, 2),
+                           kernels=sorted({r["Kernel_Name"][:90] for r in rs}))
+    return sides
+
+
 def run_rocprof(names, args, fh):
     for name in names:
         out = os.path.join(args.rocprof, name)
         info = traced_child(out, ["--pass-case", name], args)
+        if args.kv_dtype != "same":
+            sides = sides_from_trace(out, info)
+            d16, d8 = sides["decode"]["avg_us"], sides["decode_fp8"]["avg_us"]
+            emit(fh, kind="kernels", **info, hbm_share=round(info["kv_bytes"] / (d16 * 1e-6) / HBM_COPY_RATE, 3),
+                 hbm_share_fp8=round(info["kv8_bytes"] / (d8 * 1e-6) / HBM_COPY_RATE, 3), fp8_over_16=round(d8 / d16, 3), **sides)
+            if args.sweep and name in SWEEP_CASES:
+                out = os.path.join(args.rocprof, name + "_sweep")
+                sweep_from_trace(out, traced_child(out, ["--sweep-case", name], args), fh)
+            continue
         stats = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
         sides = {}
         for row in csv.DictReader(open(stats[0])):
@@ -274,8 +350,10 @@ def main():
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="same", help="also time the decode over an fp8 cache of this format")
+    ap.add_argument("--out", help="default: profiles/decode/bench_decode.jsonl, bench_decode_fp8.jsonl with --kv-dtype")
     args = ap.parse_args()
+    args.out = args.out or (OUT if args.kv_dtype == "same" else OUT_FP8)
     if args.pass_case:
         return run_pass(args.pass_case, args)
     if args.sweep_case:

@@ -5,7 +5,7 @@
 // Split granularity: split s of sequence b covers keys [s c, (s + 1) c) with c = ceil(N_k(b) / num_splits) rounded up to this.
 #define FA2_KVCACHE_KEY_TILE 64
 
-// One decode problem as fa2_fwd_kvcache hands it over, arguments already checked.  Strides in elements.
+// One decode problem as fa2_fwd_kvcache hands it over, arguments already checked.  Strides in elements of each tensor's dtype.
 struct Fa2DecodeProblem {
     const void *Q, *K, *V;
     void *O, *L;
@@ -13,6 +13,11 @@ struct Fa2DecodeProblem {
     const int32_t *seqlens;  // device, B entries, or null (N_k = S_k)
     int32_t B, H, H_kv, N_q, S_k, d;
     int32_t dtype, causal;
+    // fp8 KV cache (fa2_fwd_kvcache_fp8): kv_dtype is the element type of K and V (== dtype otherwise), kd / vd the device
+    // descales at [b * s[0] + h_kv * s[1]], null = 1.  K = kd * float(K8), V = vd * float(V8).
+    int32_t kv_dtype;
+    const float *kd, *vd;
+    int64_t kds[2], vds[2];
     int32_t wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
     float scale;
     int32_t num_splits;  // resolved, >= 1
@@ -30,6 +35,11 @@ __device__ __forceinline__ void fa2_decode_split(const int32_t *seqlens, int b, 
     nk = n;
     k0 = s * c;  // <= n + 64 * num_splits
     k1 = k0 + c < n ? k0 + c : n;
+}
+
+// A descale of the fp8 cache at [b, h_kv]: uniform over the workgroup, so one scalar load.  Null = 1.
+__device__ __forceinline__ float fa2_decode_descale(const float *p, int64_t s0, int64_t s1, int b, int hk) {
+    return p ? p[b * s0 + hk * s1] : 1.0f;
 }
 
 bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p);

@@ -1,5 +1,5 @@
-// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache and its helpers, declared in
-// include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
+// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8 and their
+// helpers, declared in include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
 // two launches (split kernels, then the combine) on the caller's stream.
 #include "fa2_decode.h"
 
@@ -34,11 +34,18 @@ int64_t workspace_bytes(int64_t B, int64_t H, int64_t N_q, int64_t d, int64_t nu
     return 4 * num_splits * rows * (d + 1);
 }
 
+// The descales of an fp8 cache (fa2_fwd_kvcache_fp8).  Null for the 16-bit entry points, whose cache has Q's dtype.
+struct Fp8Cache {
+    int32_t kv_dtype;
+    const float *kd, *vd;
+    const int64_t *kds, *vds;
+};
+
 int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
                 const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
                 int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
                 float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
-                void *hip_stream, int32_t variant) {
+                void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr) {
     const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
     const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
     for (int t = 0; t < 10; ++t)
@@ -89,7 +96,24 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
         fa2_set_error("kvcache: num_splits must be in [0, %d] (0 = auto), got %d", FA2_KVCACHE_MAX_SPLITS, num_splits);
         return FA2_ERR_BAD_ARG;
     }
-    if (dtype_enum == FA2_DTYPE_F8E5M2 || dtype_enum == FA2_DTYPE_F8E4M3) {
+    if (f8) {
+        if ((f8->kd && !f8->kds) || (f8->vd && !f8->vds)) {
+            fa2_set_error("kvcache fp8: null %s with a non-null descale", f8->kd && !f8->kds ? "k_descale_strides" : "v_descale_strides");
+            return FA2_ERR_BAD_ARG;
+        }
+        if ((f8->kd && (f8->kds[0] < 0 || f8->kds[1] < 0)) || (f8->vd && (f8->vds[0] < 0 || f8->vds[1] < 0))) {
+            fa2_set_error("kvcache fp8: negative strides are not supported (k_descale_strides, v_descale_strides)");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (f8->kv_dtype != FA2_DTYPE_F8E4M3 && f8->kv_dtype != FA2_DTYPE_F8E5M2) {
+            fa2_set_error("kvcache fp8: kv_dtype_enum %d must be FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", f8->kv_dtype);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (dtype_enum != FA2_DTYPE_F16 && dtype_enum != FA2_DTYPE_BF16) {
+            fa2_set_error("kvcache fp8: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16", dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    } else if (dtype_enum == FA2_DTYPE_F8E5M2 || dtype_enum == FA2_DTYPE_F8E4M3) {
         fa2_set_error("kvcache: fp8 is not supported (e4m3fn cannot hold L = +inf)");
         return FA2_ERR_UNSUPPORTED;
     }
@@ -112,6 +136,9 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     p.ls[0] = l_strides[0]; p.ls[1] = l_strides[1];
     p.seqlens = cache_seqlens;
     p.B = B; p.H = H; p.H_kv = H_kv; p.N_q = N_q; p.S_k = S_k; p.d = d;
+    p.kv_dtype = f8 ? f8->kv_dtype : dtype_enum;
+    p.kd = f8 ? f8->kd : nullptr; p.vd = f8 ? f8->vd : nullptr;
+    for (int k = 0; k < 2; ++k) { p.kds[k] = p.kd ? f8->kds[k] : 0; p.vds[k] = p.vd ? f8->vds[k] : 0; }
     p.dtype = dtype_enum; p.causal = causal != 0; p.wl = wl; p.wr = wr; p.scale = scale;
     p.num_splits = num_splits == 0 ? num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum) : num_splits;
     p.stream = (hipStream_t)hip_stream;
@@ -156,6 +183,19 @@ int fa2_fwd_kvcache_variant(const void *Q, const void *K, const void *V, void *O
     return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
                        dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
                        variant);
+}
+
+int fa2_fwd_kvcache_fp8(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                        const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
+                        const int32_t *cache_seqlens, const float *k_descale, const float *v_descale,
+                        const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                        int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale,
+                        int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
+                        int32_t variant, void *hip_stream) {
+    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
+    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
+                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
+                       variant, &f8);
 }
 
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {

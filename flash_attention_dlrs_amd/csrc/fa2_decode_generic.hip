@@ -1,5 +1,6 @@
 // fa2_decode_generic.hip -- the catch-all KV-cache decode kernel (fa2_fwd_kvcache, FA2_KVCACHE_VARIANT_GENERIC): every
-// supported dtype (f64, f32, f16, bf16), any strides, any d in [1, 512], any g * N_q.  The arithmetic and the work split inside
+// supported dtype (f64, f32, f16, bf16; an fp8 cache under f16 / bf16), any strides, any d in [1, 512], any g * N_q.  The
+// arithmetic and the work split inside
 // a workgroup are fa2_generic.hip's varlen form (16 query rows per workgroup, 4 per wave, lane = key for the scores, lane =
 // output column for P.V); on top of it the keys of one sequence are split across workgroups as the MFMA form splits them
 // (fa2_decode.h), each (split, row) writing a normalised fp32 partial O_s and its log2-domain L_s to the workspace for the
@@ -10,6 +11,10 @@
 //
 // K and V of a KV head are read once per QUERY head here, and a 16-row tile holds N_q useful rows: this is the fallback behind
 // fa2_decode_mfma16.hip, correct for any N_q but not a performance path at large N_q.
+//
+// fp8 cache (fa2_fwd_kvcache_fp8): the element type C of K and V is a template parameter beside E, that of Q, O and L.  An
+// e4m3fn / e5m2 element is converted (exactly) as it is loaded; the descales kd, vd at [b, h_kv] are folded: kd into the
+// softmax scale, vd into the fp32 normalised output before it is rounded or written as a partial.
 #include <math.h>
 
 #include "fa2_decode.h"
@@ -43,6 +48,18 @@ template <typename A> __device__ __forceinline__ A wave_sum(A v) {
     return v;
 }
 
+// fp8 cache elements: one byte, converted to fp32 (exactly) by v_cvt_f32_fp8 / v_cvt_f32_bf8 as it is loaded.
+struct CacheF8E4M3 {
+    static __device__ __forceinline__ float load(const void *p, int64_t i) {
+        return __builtin_amdgcn_cvt_f32_fp8((int)((const uint8_t *)p)[i], 0);
+    }
+};
+struct CacheF8E5M2 {
+    static __device__ __forceinline__ float load(const void *p, int64_t i) {
+        return __builtin_amdgcn_cvt_f32_bf8((int)((const uint8_t *)p)[i], 0);
+    }
+};
+
 struct DecodeGenericArgs {
     const void *Q, *K, *V;
     void *O, *L;
@@ -51,10 +68,12 @@ struct DecodeGenericArgs {
     int H, gqa, N_q, S_k, d, causal, wl, wr, num_splits, nqt;
     float *o_part, *l_part;
     double c_log2e;
+    const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
+    int64_t kds[2], vds[2];
 };
 
-// grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d / 64).
-template <class E, int DPL>
+// grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
+template <class E, class C, int DPL>
 __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const DecodeGenericArgs a) {
     using A = typename E::acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -80,7 +99,13 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
     }
     __syncthreads();
 
-    const A c = sizeof(A) == 8 ? (A)a.c_log2e : (A)(float)a.c_log2e;
+    constexpr bool F8 = !__is_same(C, E);
+    A c = sizeof(A) == 8 ? (A)a.c_log2e : (A)(float)a.c_log2e;
+    A vd = 1;
+    if constexpr (F8) {
+        c *= fa2_decode_descale(a.kd, a.kds[0], a.kds[1], b, hk);
+        vd = fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
+    }
     const int row0 = i * kBr + wave * kRowsPerWave;
     A m[kRowsPerWave], lsum[kRowsPerWave], o[kRowsPerWave][DPL];
 #pragma unroll
@@ -107,7 +132,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
         if (valid) {
             const int64_t kb = k_off + (int64_t)key * a.ks[2];
             for (int x = 0; x < d; ++x) {
-                const A kx = E::load(a.K, kb + (int64_t)x * a.ks[3]);
+                const A kx = C::load(a.K, kb + (int64_t)x * a.ks[3]);
 #pragma unroll
                 for (int r = 0; r < kRowsPerWave; ++r) dot[r] += q_lds[(wave * kRowsPerWave + r) * d + x] * kx;
             }
@@ -139,7 +164,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
                 if (x < d) {
-                    const A v = E::load(a.V, vb + (int64_t)x * a.vs[3]);
+                    const A v = C::load(a.V, vb + (int64_t)x * a.vs[3]);
 #pragma unroll
                     for (int r = 0; r < kRowsPerWave; ++r) o[r][cc] += pr[r] * v;
                 }
@@ -158,7 +183,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? o[r][cc] / l : (A)0);
+                if (x < d) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? (F8 ? o[r][cc] / l * vd : o[r][cc] / l) : (A)0);
             }
             if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
         } else {  // every (split, row) is written, an empty split as O_s = 0, L_s = -inf: the workspace arrives uninitialised
@@ -167,14 +192,14 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d) a.o_part[prow * d + x] = l > 0 ? (float)(o[r][cc] / l) : 0.0f;
+                if (x < d) a.o_part[prow * d + x] = l > 0 ? (float)(F8 ? o[r][cc] / l * vd : o[r][cc] / l) : 0.0f;
             }
             if (lane == 0) a.l_part[prow] = l > 0 ? (float)(m[r] + log2_acc<A>(l)) : -INFINITY;
         }
     }
 }
 
-template <class E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
+template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
     const long long gx = (long long)a.num_splits * a.nqt;
     if (gx > 0x7fffffffLL) {
         fa2_set_error("kvcache generic kernel: grid too large (num_splits * ceil(N_q / 16) = %lld)", gx);
@@ -185,14 +210,14 @@ template <class E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericAr
     const int dpl = (p.d + 63) / 64;
     static Fa2DeviceLatch attr_done;  // d > 256 in double asks for more than 64 KiB of dynamic LDS: opt in, once per device
     if (dpl > 4 && attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(sizeof(typename E::acc_t) * ((size_t)kBr * 512 + (size_t)kWaves * kRowsPerWave * kBc)));
         attr_done.mark();
     }
-    if (dpl <= 1) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 1>), grid, block, smem, p.stream, a);
-    else if (dpl <= 2) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 2>), grid, block, smem, p.stream, a);
-    else if (dpl <= 4) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 4>), grid, block, smem, p.stream, a);
-    else hipLaunchKernelGGL((fa2_decode_generic_kernel<E, 8>), grid, block, smem, p.stream, a);
+    if (dpl <= 1) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 1>), grid, block, smem, p.stream, a);
+    else if (dpl <= 2) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 2>), grid, block, smem, p.stream, a);
+    else if (dpl <= 4) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 4>), grid, block, smem, p.stream, a);
+    else hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 8>), grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache generic kernel launch failed: %s", hipGetErrorString(e));
@@ -214,6 +239,17 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     a.nqt = (p.N_q + kBr - 1) / kBr;
     a.o_part = p.o_part; a.l_part = p.l_part;
     a.c_log2e = (double)p.scale * FA2_LOG2E;
+    a.kd = p.kd; a.vd = p.vd;
+    for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+    if (p.kv_dtype != p.dtype) {  // fp8 cache under 16-bit Q, O, L
+        const bool e4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
+        if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_F16)
+            return e4 ? launch_e<ElemF16, CacheF8E4M3>(p, a) : launch_e<ElemF16, CacheF8E5M2>(p, a);
+        if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_BF16)
+            return e4 ? launch_e<ElemBF16, CacheF8E4M3>(p, a) : launch_e<ElemBF16, CacheF8E5M2>(p, a);
+        fa2_set_error("kvcache: cache dtype enum %d under dtype enum %d is not supported", p.kv_dtype, p.dtype);
+        return FA2_ERR_UNSUPPORTED;
+    }
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);
     case FA2_DTYPE_F16: return launch_e<ElemF16>(p, a);

@@ -1,5 +1,5 @@
-// fa2_decode_mfma16.hip -- KV-cache decode for f16 / bf16, d in {64, 128} (fa2_fwd_kvcache, FA2_KVCACHE_VARIANT_MFMA16): the
-// flash-decoding structure on the matrix cores.
+// fa2_decode_mfma16.hip -- KV-cache decode for f16 / bf16, d in {64, 128} (fa2_fwd_kvcache and fa2_fwd_kvcache_fp8,
+// FA2_KVCACHE_VARIANT_MFMA16): the flash-decoding structure on the matrix cores, over a 16-bit or an fp8 cache.
 //
 // One workgroup of four waves handles one (b, KV head, split).  The g = H / H_kv query heads of the group times the N_q query
 // positions are the R = g N_q <= 64 rows of the tile's query side (row r = head-in-group * N_q + query; padded to 32 or 64, the
@@ -16,6 +16,13 @@
 // Stale cache contents.  A chunk of a key >= the split's end (<= N_k(b)) is not loaded: it is written to LDS as zeros, for K
 // and for V (0 x NaN in the P.V MFMA would be NaN), and its score is SELECTED to -inf.  So what lies behind cache_seqlens[b]
 // is never read.
+//
+// fp8 cache (fa2_fwd_kvcache_fp8).  The cache element type C is a template parameter: T itself, or OCP e4m3fn / e5m2 with
+// per-(b, h_kv) descales kd, vd.  Only staging differs: a thread's 16-byte load holds 16 elements, v_cvt_scalef32_pk_* at scale
+// 1.0 converts them (exactly: both formats are subsets of f16 and of bf16) to two 16-byte chunks, which land in LDS chunks 2c and
+// 2c + 1 of the same swizzle.  The descales are folded, not applied per element: kd into the softmax scale of the workgroup, vd
+// into the fp32 normalisation of the output, before it is rounded or written as a partial.  A chunk past the split's end is
+// zeros before the conversion, so no stale byte (NaN and inf patterns included) is ever converted.
 //
 // Output.  num_splits == 1: O / l and L = m + log2 l in the I/O dtype, a row without a visible key as O = 0, L = +inf.
 // Otherwise every (split, row) writes the normalised fp32 partial O_s and L_s (an empty split: 0 and -inf) for the combine
@@ -49,6 +56,33 @@ template <> struct Mma<_Float16> {
     }
 };
 
+// Cache element types other than T.  cvt(w, hi) converts bytes 2 hi, 2 hi + 1 of a word to a pair of T, exactly.
+struct CacheE4M3 {};
+struct CacheE5M2 {};
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+template <typename T, typename C> struct CacheCvt;
+template <> struct CacheCvt<__bf16, CacheE4M3> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+    }
+};
+template <> struct CacheCvt<__bf16, CacheE5M2> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w, 1.0f, HI));
+    }
+};
+template <> struct CacheCvt<_Float16, CacheE4M3> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
+    }
+};
+template <> struct CacheCvt<_Float16, CacheE5M2> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w, 1.0f, HI));
+    }
+};
+
 struct DecodeMfmaArgs {
     const char *Q, *K, *V;
     char *O, *L;
@@ -58,22 +92,29 @@ struct DecodeMfmaArgs {
     int H, g, N_q, S_k, causal, wl, wr, num_splits;
     float *o_part, *l_part;
     float c_log2e;  // scale * log2(e) > 0
+    const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
+    int64_t kds[2], vds[2];
 };
 
-// Byte offset of 16-byte chunk `ch` of row `row` inside one [rows][D] 16-bit tile: the swizzle of fa2_mfma16k.hip (a function
+// Byte offset of 16-byte chunk `ch` of row `row` inside one [rows][D] 16-bit tile (the LDS tile is 16-bit for every cache
+// type): the swizzle of fa2_mfma16k.hip (a function
 // of row & 15 only), conflict-free for the row reads of K and the transposed reads of V.
 template <int D> __device__ __forceinline__ int lds_off(int row, int ch) {
     if constexpr (D == 128) return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
     else return row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4);
 }
 
-// RB = 32-row blocks of the query side, KG = key groups (RB * KG = 4 waves), BC = keys per tile (32 or 64).
-template <typename T, int D, int RB, int KG, int BC>
+// RB = 32-row blocks of the query side, KG = key groups (RB * KG = 4 waves), BC = keys per tile (32 or 64).  C: the cache
+// element type, T or CacheE4M3 / CacheE5M2.
+template <typename T, typename C, int D, int RB, int KG, int BC>
 __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(const DecodeMfmaArgs a) {
     using M = Mma<T>;
     using frag = typename M::frag;
+    constexpr bool F8 = !__is_same(C, T);
     constexpr int NT = RB * KG * 64;
-    constexpr int ROWB = D * 2, TILEB = BC * ROWB, CPR = ROWB / 16, CPT = BC * CPR / NT;
+    constexpr int ROWB = D * 2, TILEB = BC * ROWB;  // of the 16-bit LDS tile
+    constexpr int GROWB = F8 ? D : ROWB;            // bytes of a cache row in memory
+    constexpr int CPR = GROWB / 16, CPT = BC * CPR / NT;  // 16-byte loads per row, per thread and tile
     constexpr int RPI = NT / CPR;  // tile rows covered per staging pass
     constexpr int KS = D / 16, DB = D / 32, KB = BC / 32;
     constexpr int GRPB = 2 * TILEB;  // LDS per key group: K | V
@@ -118,7 +159,9 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     const int st_row = tid / CPR, st_ch = tid % CPR;
     const char *kg = a.K + b * a.ks[0] + hk * a.ks[1] + (int64_t)(kb0 + st_row) * a.ks[2] + st_ch * 16;
     const char *vg = a.V + b * a.vs[0] + hk * a.vs[1] + (int64_t)(kb0 + st_row) * a.vs[2] + st_ch * 16;
-    const int st_lds = lds_off<D>(st_row, st_ch);  // + it*RPI*ROWB (swizzle depends on row&15 only)
+    // + it*RPI*ROWB (swizzle depends on row&15 only).  fp8: the load's 16 elements are LDS chunks 2 st_ch and 2 st_ch + 1.
+    const int st_lds = lds_off<D>(st_row, F8 ? 2 * st_ch : st_ch);
+    const int st_lds1 = F8 ? lds_off<D>(st_row, 2 * st_ch + 1) : 0;
 
     u32x4 kreg[KG][CPT], vreg[KG][CPT];
     auto stage_load = [&](int s) {
@@ -137,8 +180,22 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
         for (int g = 0; g < KG; ++g)
 #pragma unroll
             for (int it = 0; it < CPT; ++it) {
-                *(LDS_PTR(u32x4))(lds + g * GRPB + st_lds + it * RPI * ROWB) = kreg[g][it];
-                *(LDS_PTR(u32x4))(lds + g * GRPB + TILEB + st_lds + it * RPI * ROWB) = vreg[g][it];
+                if constexpr (F8) {  // word j of the load = elements 4j .. 4j + 3 = words 2j, 2j + 1 of the 16-bit row
+                    using X = CacheCvt<T, C>;
+#pragma unroll
+                    for (int kv = 0; kv < 2; ++kv) {
+                        const u32x4 w = kv ? vreg[g][it] : kreg[g][it];
+                        const u32x4 lo = {X::template cvt<false>(w[0]), X::template cvt<true>(w[0]), X::template cvt<false>(w[1]),
+                                          X::template cvt<true>(w[1])};
+                        const u32x4 hi = {X::template cvt<false>(w[2]), X::template cvt<true>(w[2]), X::template cvt<false>(w[3]),
+                                          X::template cvt<true>(w[3])};
+                        *(LDS_PTR(u32x4))(lds + g * GRPB + kv * TILEB + st_lds + it * RPI * ROWB) = lo;
+                        *(LDS_PTR(u32x4))(lds + g * GRPB + kv * TILEB + st_lds1 + it * RPI * ROWB) = hi;
+                    }
+                } else {
+                    *(LDS_PTR(u32x4))(lds + g * GRPB + st_lds + it * RPI * ROWB) = kreg[g][it];
+                    *(LDS_PTR(u32x4))(lds + g * GRPB + TILEB + st_lds + it * RPI * ROWB) = vreg[g][it];
+                }
             }
     };
 
@@ -163,7 +220,12 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
     float m = -INFINITY, lsum = 0.0f;
-    const float c = a.c_log2e;
+    // fp8: one scalar load per descale and workgroup.  S = (scale kd) Q K8^T; vd waits in a scalar register for the epilogue.
+    float c = a.c_log2e, vd = 1.0f;
+    if constexpr (F8) {
+        c *= fa2_decode_descale(a.kd, a.kds[0], a.kds[1], b, hk);
+        vd = fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
+    }
     // this row's visible keys [lo, hi], and whether a tile can meet a band edge of any row
     const int lo = qi - wl, hi = (qi + wr) < (ke - 1) ? (qi + wr) : (ke - 1);
     const int lo_max = N_q - 1 - wl, hi_min = wr < (ke - 1) ? wr : (ke - 1);
@@ -290,7 +352,8 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     // ---- epilogue.  Lane (i, h) owns its row, columns 32db + 8g + 4h .. +3 for g = 0..3.
     const float l = lsum + __shfl_xor(lsum, 32, 64);
     const bool seen = l > 0.0f;
-    const float inv = seen ? 1.0f / l : 0.0f;
+    float inv = seen ? 1.0f / l : 0.0f;
+    if constexpr (F8) inv = seen ? inv * vd : 0.0f;  // O = vd (P V8) / l, in fp32
     if (row >= R) return;
     if (a.num_splits == 1) {
         char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)qi * a.os[2] + h * 8;
@@ -325,11 +388,11 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     }
 }
 
-template <typename T, int D, int RB, int KG, int BC> int launch_t(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
+template <typename T, typename C, int D, int RB, int KG, int BC> int launch_t(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
     const dim3 grid(p.num_splits, p.H_kv, p.B), block(RB * KG * 64);
     constexpr size_t smem = (size_t)KG * 2 * BC * D * 2;
     static_assert(smem <= 64 * 1024, "two workgroups per CU");
-    hipLaunchKernelGGL((fa2_decode_mfma16_kernel<T, D, RB, KG, BC>), grid, block, smem, p.stream, a);
+    hipLaunchKernelGGL((fa2_decode_mfma16_kernel<T, C, D, RB, KG, BC>), grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mfma16 kernel launch failed: %s", hipGetErrorString(e));
@@ -338,11 +401,19 @@ template <typename T, int D, int RB, int KG, int BC> int launch_t(const Fa2Decod
     return FA2_OK;
 }
 
-template <typename T> int launch_d(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
+template <typename T, typename C> int launch_d(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
     const bool one = (int64_t)a.g * p.N_q <= 32;  // one 32-row block: four key groups
-    if (p.d == 128) return one ? launch_t<T, 128, 1, 4, 32>(p, a) : launch_t<T, 128, 2, 2, 64>(p, a);
-    return one ? launch_t<T, 64, 1, 4, 64>(p, a) : launch_t<T, 64, 2, 2, 64>(p, a);
+    if (p.d == 128) return one ? launch_t<T, C, 128, 1, 4, 32>(p, a) : launch_t<T, C, 128, 2, 2, 64>(p, a);
+    return one ? launch_t<T, C, 64, 1, 4, 64>(p, a) : launch_t<T, C, 64, 2, 2, 64>(p, a);
 }
+
+template <typename T> int launch_c(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
+    if (p.kv_dtype == FA2_DTYPE_F8E4M3) return launch_d<T, CacheE4M3>(p, a);
+    if (p.kv_dtype == FA2_DTYPE_F8E5M2) return launch_d<T, CacheE5M2>(p, a);
+    return launch_d<T, T>(p, a);
+}
+
+bool fp8_cache(const Fa2DecodeProblem &p) { return p.kv_dtype == FA2_DTYPE_F8E4M3 || p.kv_dtype == FA2_DTYPE_F8E5M2; }
 
 bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
@@ -350,13 +421,15 @@ bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p) {
     if (p.dtype != FA2_DTYPE_F16 && p.dtype != FA2_DTYPE_BF16) return false;
+    if (p.kv_dtype != p.dtype && !fp8_cache(p)) return false;
     if (p.d != 64 && p.d != 128) return false;
     if (!(p.scale > 0.0f) || !(p.scale < INFINITY)) return false;
     if ((int64_t)(p.H / p.H_kv) * p.N_q > 64) return false;
     if (p.qs[3] != 1 || p.ks[3] != 1 || p.vs[3] != 1 || p.os[3] != 1) return false;
-    // 16-byte vector loads of Q/K/V rows, 8-byte stores of O: every row start must stay aligned.
+    // 16-byte vector loads of Q/K/V rows, 8-byte stores of O: every row start must stay aligned (an fp8 cache: 16 elements).
+    const int64_t kmask = fp8_cache(p) ? 15 : 7;
     for (int k = 0; k < 3; ++k)
-        if ((p.qs[k] & 7) || (p.ks[k] & 7) || (p.vs[k] & 7) || (p.os[k] & 7)) return false;
+        if ((p.qs[k] & 7) || (p.ks[k] & kmask) || (p.vs[k] & kmask) || (p.os[k] & 7)) return false;
     if (!aligned16(p.Q) || !aligned16(p.K) || !aligned16(p.V) || !aligned16(p.O)) return false;
     if (p.num_splits > 1 && !aligned16(p.o_part)) return false;
     return true;
@@ -364,15 +437,16 @@ bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p) {
 
 int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) {
     if (!fa2_decode_mfma16_supports(p)) {
-        fa2_set_error("kvcache mfma16 kernel: needs f16/bf16, d in {64,128}, g * N_q <= 64, unit d-stride, 16-byte aligned rows "
-                      "(and workspace), scale > 0");
+        fa2_set_error("kvcache mfma16 kernel: needs f16/bf16 (the cache alike, or fp8), d in {64,128}, g * N_q <= 64, unit d-stride, "
+                      "16-byte aligned rows (and workspace), scale > 0");
         return FA2_ERR_UNSUPPORTED;
     }
     DecodeMfmaArgs a;
     a.Q = (const char *)p.Q; a.K = (const char *)p.K; a.V = (const char *)p.V;
     a.O = (char *)p.O; a.L = (char *)p.L;
+    const int64_t cb = fp8_cache(p) ? 1 : 2;  // bytes per cache element
     for (int k = 0; k < 3; ++k) {
-        a.qs[k] = p.qs[k] * 2; a.ks[k] = p.ks[k] * 2; a.vs[k] = p.vs[k] * 2; a.os[k] = p.os[k] * 2;
+        a.qs[k] = p.qs[k] * 2; a.ks[k] = p.ks[k] * cb; a.vs[k] = p.vs[k] * cb; a.os[k] = p.os[k] * 2;
     }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
     a.seqlens = p.seqlens;
@@ -380,5 +454,7 @@ int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) {
     a.num_splits = p.num_splits;
     a.o_part = p.o_part; a.l_part = p.l_part;
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
-    return p.dtype == FA2_DTYPE_BF16 ? launch_d<__bf16>(p, a) : launch_d<_Float16>(p, a);
+    a.kd = p.kd; a.vd = p.vd;
+    for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+    return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }

@@ -120,19 +120,67 @@ def flash_attention_varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_
                            scale=scale, window=window, variant=variant)
 
 
-def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits):
-    """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, cache_seqlens, window, num_splits).  Pure:
-    takes CPU tensors as well (the CUDA-device check is the launch's)."""
+FP8_CACHE_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)
+
+
+def quantize_kv_cache(K, dtype):
+    """(K8, descale) of a (B, H_kv, S_k, d) cache for flash_attention_kvcache_forward's fp8 mode: one scale per (b, h_kv),
+    descale = amax over (S_k, d) / finfo(dtype).max (1 where the head is all zeros), float32 (B, H_kv); K8 = (K / descale) in dtype
+    (torch.float8_e4m3fn or torch.float8_e5m2).  Plain torch, any device."""
+    if dtype not in FP8_CACHE_DTYPES:
+        raise ValueError(f"quantize_kv_cache: dtype must be torch.float8_e4m3fn or torch.float8_e5m2, got {dtype}")
+    if K.dim() != 4:
+        raise ValueError(f"quantize_kv_cache: the cache must be (B, H_kv, S_k, d), got {tuple(K.shape)}")
+    top = torch.finfo(dtype).max
+    amax = K.detach().abs().amax(dim=(2, 3)).to(torch.float32)
+    descale = torch.where(amax > 0, amax / top, torch.ones_like(amax))
+    K8 = (K.to(torch.float32) / descale[:, :, None, None]).clamp(-top, top).to(dtype)
+    return K8, descale
+
+
+def dequantize_kv_cache(K8, descale, dtype):
+    """The inverse of quantize_kv_cache: descale * float(K8) in dtype; descale broadcasts to (B, H_kv)."""
+    B, H_kv = K8.shape[:2]
+    return (K8.to(torch.float32) * torch.broadcast_to(descale.to(torch.float32), (B, H_kv))[:, :, None, None]).to(dtype)
+
+
+def _kvcache_descale(name, t, Q, B, H_kv):
+    """A descale argument as a (B, H_kv) view whose strides the C ABI takes (0 on broadcast axes)."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"kvcache: {name} must be a float32 tensor (or None)")
+    if t.device != Q.device:
+        raise ValueError(f"kvcache: {name} must be on Q's device ({Q.device}), got {t.device}")
+    try:
+        return torch.broadcast_to(t, (B, H_kv))
+    except RuntimeError:
+        raise ValueError(f"kvcache: {name} of shape {tuple(t.shape)} does not broadcast to (B, H_kv) = ({B}, {H_kv})") from None
+
+
+def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale=None, v_descale=None):
+    """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, descales, cache_seqlens, window,
+    num_splits).  Pure: takes CPU tensors as well (the CUDA-device check is the launch's)."""
     if Q.dim() != 4 or K_cache.dim() != 4 or V_cache.dim() != 4 or K_cache.shape != V_cache.shape \
             or Q.shape[0] != K_cache.shape[0] or Q.shape[3] != K_cache.shape[3] or Q.shape[2] < 1 or K_cache.shape[2] < 1:
         raise ValueError(f"kvcache: Q must be (B, H, N_q, d) and K_cache, V_cache (B, H_kv, S_k, d) with N_q, S_k >= 1: got Q "
                          f"{tuple(Q.shape)}, K_cache {tuple(K_cache.shape)}, V_cache {tuple(V_cache.shape)}")
     # the head rule of the dense entry points, on views that drop the sequence axis (N_q and S_k differ here)
     gqa_kv_heads(Q[:, :, :1], K_cache[:, :, :1], V_cache[:, :, :1])
-    if Q.dtype != K_cache.dtype or K_cache.dtype != V_cache.dtype:
-        raise ValueError("kvcache: Q, K_cache, V_cache must have the same dtype")
-    if Q.dtype in (torch.float8_e5m2, torch.float8_e4m3fn):
-        raise ValueError(f"kvcache: dtype {Q.dtype} is not supported (e4m3fn cannot hold L = +inf)")
+    if Q.dtype in FP8_CACHE_DTYPES:
+        raise ValueError(f"kvcache: dtype {Q.dtype} is not supported for Q (e4m3fn cannot hold L = +inf)")
+    if K_cache.dtype != V_cache.dtype:
+        raise ValueError("kvcache: K_cache and V_cache must have the same dtype")
+    if K_cache.dtype in FP8_CACHE_DTYPES:  # fp8 cache: Q, O, L stay 16-bit
+        if Q.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"kvcache: an fp8 cache needs Q in float16 or bfloat16, got {Q.dtype}")
+        _kvcache_descale("k_descale", k_descale, Q, Q.shape[0], K_cache.shape[1])
+        _kvcache_descale("v_descale", v_descale, Q, Q.shape[0], K_cache.shape[1])
+    else:
+        if Q.dtype != K_cache.dtype:
+            raise ValueError("kvcache: Q, K_cache, V_cache must have the same dtype (or the caches an fp8 dtype under 16-bit Q)")
+        if k_descale is not None or v_descale is not None:
+            raise ValueError(f"kvcache: k_descale / v_descale go with an fp8 cache, not with {K_cache.dtype}")
     convert_triton_dtype(Q.dtype)
     if cache_seqlens is not None:
         if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 \
@@ -147,24 +195,36 @@ def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits):
 
 
 def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, causal=False, scale=1.0, window=None, num_splits=0,
-                                    variant="auto"):
+                                    variant="auto", k_descale=None, v_descale=None):
     """Decode attention over a padded KV cache, split-KV (include/fa2_fwd.h fa2_fwd_kvcache) -> (O, L).  Q (B, H, N_q, d);
     K_cache, V_cache (B, H_kv, S_k, d) of capacity S_k, any strides (a flash-attn (B, S, H_kv, d) cache: pass its
     .transpose(1, 2) view), H_kv dividing H; cache_seqlens int32 (B,) on Q's device, sequence b attends to its first
     cache_seqlens[b] keys (None: all S_k).  causal / window are bottom-right aligned as in the varlen call.  O (B, H, N_q, d)
     contiguous, L (B, H, N_q) log2-domain, both in Q's dtype; rows without a visible key get O = 0, L = +inf.  num_splits = 0
-    lets the library choose; variant is one of _lib.KVCACHE_VARIANTS.  No autograd, no autotuner."""
-    check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits)
+    lets the library choose; variant is one of _lib.KVCACHE_VARIANTS.  No autograd, no autotuner.
+
+    fp8 cache (fa2_fwd_kvcache_fp8): K_cache and V_cache in torch.float8_e4m3fn or torch.float8_e5m2 (both the same) under
+    float16 / bfloat16 Q.  K = k_descale * float(K_cache), V = v_descale * float(V_cache) with float32 descales on Q's device that
+    broadcast to (B, H_kv) (None: 1; they must be finite and > 0) -- quantize_kv_cache makes such a cache.  The arithmetic stays
+    16-bit: only the cache's storage is fp8."""
+    check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale, v_descale)
     if variant not in _lib.KVCACHE_VARIANTS:
         raise ValueError(f"kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
     if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
         raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
     B, H, N_q, d = Q.shape
+    H_kv = K_cache.shape[1]
     dtype = convert_triton_dtype(Q.dtype)
     O = torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device)
     L = torch.empty(B, H, N_q, dtype=Q.dtype, device=Q.device)
-    n = num_splits or _lib.kvcache_num_splits(B, H, K_cache.shape[1], N_q, K_cache.shape[2], d, dtype)
+    n = num_splits or _lib.kvcache_num_splits(B, H, H_kv, N_q, K_cache.shape[2], d, dtype)
     ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    if K_cache.dtype in FP8_CACHE_DTYPES:
+        _lib.fa2_fwd_kvcache_fp8(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
+                                 k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
+                                 v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), causal=causal, scale=scale,
+                                 window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
+        return O, L
     _lib.fa2_fwd_kvcache(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, causal=causal, scale=scale, window=window, num_splits=n,
                          workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
     return O, L

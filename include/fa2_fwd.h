@@ -236,7 +236,8 @@ int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void
  *             pointer means N_k = S_k for every b.  Rows >= N_k(b) of K and V are never read: they may hold anything, NaN included.
  *   Mask.     causal and (window_left, window_right) are fa2_fwd_varlen's definitions, bottom-right aligned with the shift
  *             N_k(b) - N_q; with N_q = 1 causal masks nothing.  A row without a visible key gets O = 0 and L = +inf.
- *   Dtypes.   f64, f32, f16, bf16; fp8 returns FA2_ERR_UNSUPPORTED, as in varlen.  L is the log2-domain log-sum-exp in dtype_enum.
+ *   Dtypes.   f64, f32, f16, bf16; fp8 returns FA2_ERR_UNSUPPORTED, as in varlen (an fp8 CACHE under 16-bit Q: fa2_fwd_kvcache_fp8
+ *             below).  L is the log2-domain log-sum-exp in dtype_enum.
  *   Splits.   The keys of a sequence are split across num_splits workgroups: split s covers keys [s c, (s + 1) c) with
  *             c = ceil(N_k(b) / num_splits) rounded up to 64.  num_splits = 0 picks fa2_kvcache_num_splits(...), a host heuristic
  *             on the capacity.  With num_splits > 1 the split kernels leave fp32 partials in `workspace` and a second launch on the
@@ -272,6 +273,39 @@ int fa2_fwd_kvcache_variant(const void *Q, const void *K, const void *V, void *O
                             int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum,
                             int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                             void *workspace, int64_t workspace_bytes, void *hip_stream, int32_t variant);
+
+/*
+ * The same decode over an fp8 KV cache.  K and V hold OCP e4m3fn or e5m2 bytes (kv_dtype_enum: FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2,
+ * the same for both) with one dequantisation scale per (sequence, KV head):
+ *
+ *     K = k_descale[b, h_kv] * float(K8),   V = v_descale[b, h_kv] * float(V8),
+ *
+ * and the result is fa2_fwd_kvcache's on those K and V: the same lengths, mask, split rule, workspace, variants and empty rows.  Q, O
+ * and L stay f16 / bf16 (dtype_enum) and the matrix work stays 16-bit: fp8 -> f16 / bf16 is exact, so the kernels stage the converted
+ * bytes, use scale * k_descale as the softmax scale of the workgroup and multiply the fp32 output by v_descale before it is rounded
+ * (or written as a partial).  With both descales 1 the result equals fa2_fwd_kvcache's on the converted cache bit for bit.
+ *
+ *   Descales. k_descale / v_descale: device fp32, element [b, h_kv] at b * strides[0] + h_kv * strides[1] (element strides, 0
+ *             broadcasts an axis); a null pointer means 1 (its strides may then be null).  The values live on the device and are not
+ *             checked: they must be finite and > 0, or O and L are undefined (no access depends on them).
+ *   Strides.  In elements of each tensor's own dtype: k_strides / v_strides count fp8 elements.
+ *   Variants. FA2_KVCACHE_VARIANT_MFMA16 under fa2_fwd_kvcache's conditions, the 16-byte row alignment counted in fp8 bytes (K and V
+ *             strides multiples of 16 elements); GENERIC takes everything else (any d in [1, 512], any strides, any N_q).
+ *   Splits.   fa2_kvcache_workspace_bytes(...) and fa2_kvcache_num_splits(..., dtype_enum) as for fa2_fwd_kvcache.
+ *
+ * Every FA2_ERR_BAD_ARG of fa2_fwd_kvcache applies unchanged; also a negative descale stride and a non-null descale with null strides.
+ * FA2_ERR_UNSUPPORTED, naming the argument, for a kv_dtype_enum that is not one of the two fp8 formats, a dtype_enum that is not
+ * f16 / bf16, d outside [1, 512], an unknown variant, a forced MFMA16 on a problem it cannot run.
+ */
+int fa2_fwd_kvcache_fp8(const void *Q, const void *K, const void *V, void *O, void *L,
+                        const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                        const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                        const float *k_descale, const float *v_descale,
+                        const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                        int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d,
+                        int32_t dtype_enum, int32_t kv_dtype_enum,
+                        int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                        void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
 /* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
  * elements plus fp32 partial L of num_splits * B * H * N_q. */
