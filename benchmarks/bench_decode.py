@@ -23,13 +23,21 @@ Records:
 descales) as one more side, decode_fp8, alternated with the others in the same process; records go to bench_decode_fp8.jsonl.
 The combine kernel is common to the two decode sides, so kind=kernels is then read off the kernel trace (each combine belongs
 to the split kernel in front of it; the first 3 calls of a side are its warm-up) instead of the stats file; fp8_over_16 is the
-ratio of the two decode averages and hbm_share_fp8 counts the fp8 bytes.  The sweeps then run the fp8 side."""
+ratio of the two decode averages and hbm_share_fp8 counts the fp8 bytes.  The sweeps then run the fp8 side.
+
+--page-size N times the paged decode (fa2_fwd_kvcache_paged) against the contiguous call of the same build on the same shapes: K
+and V of every copy are scattered into a (num_blocks, N, H_kv, d) pool under a random permutation table, and the sides are
+decode, decode_paged and gather (the route the paged call replaces: index_select of every sequence's pages into a padded cache,
+then the contiguous decode).  kind=events times all three; with --rocprof the traced child alternates decode and decode_paged
+alone and kind=kernels_paged is read off the kernel trace as in the fp8 mode (paged_over_contiguous is the ratio of the two
+averages).  Records go to bench_decode.jsonl."""
 import argparse
 import csv
 import glob
 import json
 import math
 import os
+import re
 import subprocess
 import sys
 
@@ -69,7 +77,7 @@ def ragged_lengths(B, lo, hi):
 
 
 class Case:
-    def __init__(self, name, dev, kv_dtype="same"):
+    def __init__(self, name, dev, kv_dtype="same", page_size=0):
         import torch
         from flash_attention_dlrs_amd import _lib
         from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
@@ -112,6 +120,19 @@ class Case:
                 t8, ds = quantize_kv_cache(t.transpose(1, 2), fmt)
                 return t8.view(torch.uint8).transpose(1, 2).contiguous().view(fmt), ds
             self.K8, self.V8 = [q8(t) for t in self.K], [q8(t) for t in self.V]
+        self.page_size = page_size
+        if page_size:  # every copy scattered into a flash-attn-layout pool (num_blocks, P, H_kv, d) under one random table
+            assert S % page_size == 0, (S, page_size)
+            mb = S // page_size
+            perm = torch.randperm(B * mb, generator=torch.Generator().manual_seed(0)).to(dev)
+            self.table = perm.view(B, mb).to(torch.int32)
+            self.pages = perm  # index_select argument of the gather route
+
+            def pool(t):
+                p = torch.empty(B * mb, page_size, H_kv, d, dtype=t.dtype, device=dev)
+                p[perm] = t.view(B * mb, page_size, H_kv, d)
+                return p
+            self.K_pool, self.V_pool = [pool(t) for t in self.K], [pool(t) for t in self.V]
 
     def auto_splits(self):
         s = self.shape
@@ -142,6 +163,36 @@ class Case:
             (K8, kd), (V8, vd) = self.K8[self.i], self.V8[self.i]
             self._lib.fa2_fwd_kvcache_fp8(self.Q, K8.transpose(1, 2), V8.transpose(1, 2), self.O, self.L, self.lens_dev, self.enum,
                                           self.kv_enum, k_descale=kd, v_descale=vd, scale=self.scale, num_splits=n, workspace=ws)
+        return run
+
+    def decode_paged(self, num_splits=0):
+        """The paged launch over the pools, under the same conditions."""
+        s = self.shape
+        n = num_splits or self.auto_splits()
+        words = self._lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], s["d"], n) // 4
+        ws = self.torch.empty(max(words, 1), dtype=self.torch.float32, device=self.dev)
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            self._lib.fa2_fwd_kvcache_paged(self.Q, self.K_pool[self.i].transpose(1, 2), self.V_pool[self.i].transpose(1, 2), self.O,
+                                            self.L, self.table, self.lens_dev, self.enum, self.enum, scale=self.scale, num_splits=n,
+                                            workspace=ws)
+        return run
+
+    def gather(self):
+        """The route the paged call replaces: gather every sequence's pages into a padded cache, then the contiguous decode."""
+        s = self.shape
+        n = self.auto_splits()
+        words = self._lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], s["d"], n) // 4
+        ws = self.torch.empty(max(words, 1), dtype=self.torch.float32, device=self.dev)
+        shape = (s["B"], s["N_k"], s["H_kv"], s["d"])
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            K = self.torch.index_select(self.K_pool[self.i], 0, self.pages).view(shape)
+            V = self.torch.index_select(self.V_pool[self.i], 0, self.pages).view(shape)
+            self._lib.fa2_fwd_kvcache(self.Q, K.transpose(1, 2), V.transpose(1, 2), self.O, self.L, self.lens_dev, self.enum,
+                                      scale=self.scale, num_splits=n, workspace=ws)
         return run
 
     def varlen(self):
@@ -190,7 +241,15 @@ def run_events(names, args, fh):
     import torch
     dev = torch.device("cuda:0")
     for name in names:
-        c = Case(name, dev, args.kv_dtype)
+        c = Case(name, dev, args.kv_dtype, args.page_size)
+        if args.page_size:
+            sides = {"decode": c.decode(), "decode_paged": c.decode_paged(), "gather": c.gather()}
+            res = interleaved(torch, list(sides.values()), args.iters, args.rounds)
+            emit(fh, kind="events_paged", case=name, page_size=args.page_size, **c.shape, ragged=c.ragged, num_splits=c.auto_splits(),
+                 kv_bytes=c.kv_bytes, **{k: r for k, r in zip(sides, res)})
+            del c
+            torch.cuda.empty_cache()
+            continue
         sides = {"decode": c.decode(), "varlen": c.varlen()}
         if args.kv_dtype != "same":
             sides["decode_fp8"] = c.decode_fp8()
@@ -210,13 +269,18 @@ def run_events(names, args, fh):
 def run_pass(name, args):
     """The traced child: warm, then alternate the sides; the profiler's stats file holds the kernel times."""
     import torch
-    c = Case(name, torch.device("cuda:0"), args.kv_dtype)
-    sides = [c.decode()] + ([] if args.kv_dtype == "same" else [c.decode_fp8()]) + [c.varlen()] + ([] if args.no_sdpa else [c.sdpa()])
+    c = Case(name, torch.device("cuda:0"), args.kv_dtype, args.page_size)
+    if args.page_size:  # the paged call against the contiguous one, nothing else
+        sides = [c.decode(), c.decode_paged()]
+    else:
+        sides = [c.decode()] + ([] if args.kv_dtype == "same" else [c.decode_fp8()]) + [c.varlen()] + ([] if args.no_sdpa else [c.sdpa()])
     for _ in range(args.iters + 3):
         for f in sides:
             f()
     torch.cuda.synchronize()
     extra = {} if args.kv_dtype == "same" else dict(kv_dtype=args.kv_dtype, kv8_bytes=c.kv8_bytes)
+    if args.page_size:
+        extra["page_size"] = args.page_size
     print(json.dumps(dict(case=name, calls=args.iters + 3, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(), **extra, **c.shape)))
 
 
@@ -236,7 +300,8 @@ def run_sweep_pass(name, args):
 def traced_child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
-           os.path.abspath(__file__), "--iters", str(args.iters), "--kv-dtype", args.kv_dtype] + extra + \
+           os.path.abspath(__file__), "--iters", str(args.iters), "--kv-dtype", args.kv_dtype, "--page-size", str(args.page_size)] + \
+        extra + \
         (["--no-sdpa"] if args.no_sdpa else [])
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.child_timeout)
     if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
@@ -263,8 +328,13 @@ def sweep_from_trace(out, info, fh):
     assert pos == len(rows)
 
 
+PAGED_KERNEL = re.compile(r"fa2_decode_\w+_kernel<[^>]*\btrue\b")  # the PAGED template argument of the split kernels
+
+
 def side_of(kernel):
-    if "fa2_decode" in kernel:  # (the combine kernel, common to both decode sides, counts as "decode" here)
+    if "fa2_decode" in kernel:  # (the combine kernel, common to the decode sides, counts as "decode" here)
+        if PAGED_KERNEL.search(kernel):
+            return "decode_paged"
         return "decode_fp8" if "Cache" in kernel else "decode"
     if "varlen" in kernel:
         return "varlen"
@@ -307,6 +377,13 @@ def run_rocprof(names, args, fh):
     for name in names:
         out = os.path.join(args.rocprof, name)
         info = traced_child(out, ["--pass-case", name], args)
+        if args.page_size:
+            sides = sides_from_trace(out, info)
+            flat, paged = sides["decode"]["avg_us"], sides["decode_paged"]["avg_us"]
+            emit(fh, kind="kernels_paged", **info, hbm_share=round(info["kv_bytes"] / (flat * 1e-6) / HBM_COPY_RATE, 3),
+                 hbm_share_paged=round(info["kv_bytes"] / (paged * 1e-6) / HBM_COPY_RATE, 3),
+                 paged_over_contiguous=round(paged / flat, 3), **sides)
+            continue
         if args.kv_dtype != "same":
             sides = sides_from_trace(out, info)
             d16, d8 = sides["decode"]["avg_us"], sides["decode_fp8"]["avg_us"]
@@ -351,9 +428,13 @@ def main():
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="same", help="also time the decode over an fp8 cache of this format")
+    ap.add_argument("--page-size", type=int, default=0, metavar="N",
+                    help="time the paged decode over pools of N-key pages against the contiguous decode (N must divide every N_k)")
     ap.add_argument("--out", help="default: profiles/decode/bench_decode.jsonl, bench_decode_fp8.jsonl with --kv-dtype")
     args = ap.parse_args()
     args.out = args.out or (OUT if args.kv_dtype == "same" else OUT_FP8)
+    if args.page_size and (args.kv_dtype != "same" or args.sweep):
+        ap.error("--page-size goes without --kv-dtype and --sweep")
     if args.pass_case:
         return run_pass(args.pass_case, args)
     if args.sweep_case:

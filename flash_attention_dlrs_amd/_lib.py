@@ -52,8 +52,8 @@ if os.path.basename(LIB_PATH) in ("libfa2_hip_exp.so", "libfa2_hip_abl.so"):
 SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", "fa2_query_tile_scaled", "fa2_version", "fa2_last_error",
            "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant",
            "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant",
-           "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_kvcache_workspace_bytes",
-           "fa2_kvcache_num_splits")
+           "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_fwd_kvcache_paged",
+           "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -155,6 +155,10 @@ def lib():
         l.fa2_fwd_kvcache_fp8.restype = ctypes.c_int
         l.fa2_fwd_kvcache_fp8.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, vp, i64p, i64p] + [ctypes.c_int32] * 9 + [ctypes.c_float] + \
             [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # ... over a paged cache: block_table and its row stride after cache_seqlens; num_blocks, page_size, max_blocks in S_k's place
+        l.fa2_fwd_kvcache_paged.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_paged.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64, vp, vp, i64p, i64p] + [ctypes.c_int32] * 11 + \
+            [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -417,5 +421,31 @@ def fa2_fwd_kvcache_fp8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_enum,
             None if cache_seqlens is None else cache_seqlens.data_ptr(), kd_ptr, vd_ptr, kd_st, vd_st, B, H, K.shape[1], N_q,
             K.shape[2], d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr,
             ws_bytes, int(variant), _raw_stream(Q.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_fwd_kvcache_paged(Q, K, V, O, L, block_table, cache_seqlens, dtype_enum, kv_dtype_enum, k_descale=None, v_descale=None,
+                          causal=False, scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch decode attention over a paged KV cache (include/fa2_fwd.h fa2_fwd_kvcache_paged) on the current stream of Q's device.
+    As fa2_fwd_kvcache_fp8, with K / V the page pool (num_blocks, H_kv, page_size, d), any strides, and block_table int32
+    (B, max_blocks) on the device with unit stride in its last axis; kv_dtype_enum == dtype_enum (and no descales) for a pool in
+    Q's dtype.  The kernels clamp table entries into the pool; nothing is validated here."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    ws_ptr = None if workspace is None else workspace.data_ptr()
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
+    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_kvcache_paged(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), block_table.data_ptr(), block_table.stride(0),
+            kd_ptr, vd_ptr, kd_st, vd_st, B, H, K.shape[1], N_q, K.shape[0], K.shape[2], block_table.shape[1], d,
+            int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
+            int(variant), _raw_stream(Q.device.index))
     if rc != 0:
         _raise(rc)

@@ -18,6 +18,12 @@ struct Fa2DecodeProblem {
     int32_t kv_dtype;
     const float *kd, *vd;
     int64_t kds[2], vds[2];
+    // paged cache (fa2_fwd_kvcache_paged): table non-null.  K, V are the page pool (num_blocks, H_kv, page_size, d), ks[0] / vs[0] the
+    // block stride, S_k the capacity max_blocks * page_size; key j of sequence b is row j % page_size of page
+    // table[b * table_stride + j / page_size], the entry clamped to [0, num_blocks - 1] by the kernel that reads it.
+    const int32_t *table;
+    int64_t table_stride;
+    int32_t page_size, num_blocks;
     int32_t wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
     float scale;
     int32_t num_splits;  // resolved, >= 1
@@ -40,6 +46,12 @@ __device__ __forceinline__ void fa2_decode_split(const int32_t *seqlens, int b, 
 // A descale of the fp8 cache at [b, h_kv]: uniform over the workgroup, so one scalar load.  Null = 1.
 __device__ __forceinline__ float fa2_decode_descale(const float *p, int64_t s0, int64_t s1, int b, int hk) {
     return p ? p[b * s0 + hk * s1] : 1.0f;
+}
+
+// A block-table entry as the kernels use it: clamped into the pool, so a wild entry cannot become an access outside it.
+__device__ __forceinline__ int fa2_decode_page(const int32_t *table, int64_t i, int num_blocks) {
+    const int e = table[i];
+    return e < 0 ? 0 : (e > num_blocks - 1 ? num_blocks - 1 : e);
 }
 
 bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p);

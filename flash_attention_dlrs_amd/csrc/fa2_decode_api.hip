@@ -1,5 +1,5 @@
-// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8 and their
-// helpers, declared in include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
+// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8,
+// fa2_fwd_kvcache_paged and their helpers, declared in include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
 // two launches (split kernels, then the combine) on the caller's stream.
 #include "fa2_decode.h"
 
@@ -41,11 +41,19 @@ struct Fp8Cache {
     const int64_t *kds, *vds;
 };
 
+// The block table of a paged cache (fa2_fwd_kvcache_paged).  Null for the contiguous entry points.
+struct PagedCache {
+    const int32_t *table;
+    int64_t table_stride;
+    int32_t num_blocks, page_size, max_blocks;
+};
+
+// S_k is the capacity of a contiguous cache; with `pg` it is ignored and max_blocks * page_size takes its place.
 int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
                 const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
                 int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
                 float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
-                void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr) {
+                void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr, const PagedCache *pg = nullptr) {
     const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
     const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
     for (int t = 0; t < 10; ++t)
@@ -53,6 +61,27 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
             fa2_set_error("kvcache: null %s", names[t]);
             return FA2_ERR_BAD_ARG;
         }
+    if (pg) {
+        if (!pg->table) {
+            fa2_set_error("kvcache paged: null block_table");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (pg->num_blocks < 1 || pg->page_size < 1 || pg->max_blocks < 1) {
+            fa2_set_error("kvcache paged: num_blocks, page_size and max_blocks must be >= 1 (got num_blocks=%d, page_size=%d, "
+                          "max_blocks=%d)", pg->num_blocks, pg->page_size, pg->max_blocks);
+            return FA2_ERR_BAD_ARG;
+        }
+        const int64_t cap = (int64_t)pg->max_blocks * pg->page_size;
+        if (cap > (1 << 28)) {
+            fa2_set_error("kvcache paged: the capacity max_blocks * page_size must be <= 2^28 (got %lld)", (long long)cap);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (pg->table_stride < 0) {
+            fa2_set_error("kvcache paged: negative block_table_stride");
+            return FA2_ERR_BAD_ARG;
+        }
+        S_k = (int32_t)cap;
+    }
     if (B < 1 || B > 65535) {
         fa2_set_error("kvcache: B must be in [1, 65535] (got %d)", B);
         return FA2_ERR_BAD_ARG;
@@ -139,6 +168,9 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     p.kv_dtype = f8 ? f8->kv_dtype : dtype_enum;
     p.kd = f8 ? f8->kd : nullptr; p.vd = f8 ? f8->vd : nullptr;
     for (int k = 0; k < 2; ++k) { p.kds[k] = p.kd ? f8->kds[k] : 0; p.vds[k] = p.vd ? f8->vds[k] : 0; }
+    p.table = pg ? pg->table : nullptr;
+    p.table_stride = pg ? pg->table_stride : 0;
+    p.page_size = pg ? pg->page_size : 0; p.num_blocks = pg ? pg->num_blocks : 0;
     p.dtype = dtype_enum; p.causal = causal != 0; p.wl = wl; p.wr = wr; p.scale = scale;
     p.num_splits = num_splits == 0 ? num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum) : num_splits;
     p.stream = (hipStream_t)hip_stream;
@@ -196,6 +228,26 @@ int fa2_fwd_kvcache_fp8(const void *Q, const void *K, const void *V, void *O, vo
     return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
                        dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
                        variant, &f8);
+}
+
+int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                          const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                          const int64_t l_strides[2], const int32_t *cache_seqlens, const int32_t *block_table,
+                          int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                          const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                          int32_t N_q, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t dtype_enum,
+                          int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                          int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    const bool wide = kv_dtype_enum == dtype_enum;  // the pool has Q's dtype: fa2_fwd_kvcache's checks, no descales
+    if (wide && (k_descale || v_descale)) {
+        fa2_set_error("kvcache paged: k_descale / v_descale go with an fp8 pool (kv_dtype_enum %d == dtype_enum)", kv_dtype_enum);
+        return FA2_ERR_BAD_ARG;
+    }
+    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
+    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
+    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, 0, d,
+                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
+                       variant, wide ? nullptr : &f8, &pg);
 }
 
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {

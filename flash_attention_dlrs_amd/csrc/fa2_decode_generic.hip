@@ -15,6 +15,12 @@
 // fp8 cache (fa2_fwd_kvcache_fp8): the element type C of K and V is a template parameter beside E, that of Q, O and L.  An
 // e4m3fn / e5m2 element is converted (exactly) as it is loaded; the descales kd, vd at [b, h_kv] are folded: kd into the
 // softmax scale, vd into the fp32 normalised output before it is rounded or written as a partial.
+//
+// Paged cache (fa2_fwd_kvcache_paged): PAGED is a template parameter as well, K and V a page pool behind a block table, any
+// page_size >= 1.  Key j of sequence b is row j % page_size of page table[b][j / page_size], the entry clamped to
+// [0, num_blocks - 1] before it becomes an address (a wild entry: a wrong result, never an access outside the pool).  For the
+// scores a lane looks up the page of its own key; the P.V loop walks the keys in order and looks the page up once per run of
+// keys inside a page.  Only keys below the split's end are looked up, so entries past a sequence's pages are never loaded.
 #include <math.h>
 
 #include "fa2_decode.h"
@@ -70,10 +76,14 @@ struct DecodeGenericArgs {
     double c_log2e;
     const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
     int64_t kds[2], vds[2];
+    const int32_t *table;  // paged cache only: entry [b, i] at b * table_stride + i; ks[0], vs[0] are the block strides
+    int64_t table_stride;
+    int page_size, num_blocks;
 };
 
 // grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
-template <class E, class C, int DPL>
+// PAGED: K and V are a page pool behind a block table.
+template <class E, class C, bool PAGED, int DPL>
 __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const DecodeGenericArgs a) {
     using A = typename E::acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -88,8 +98,9 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
     fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
     const int hk = h / a.gqa;
     const int64_t q_off = b * a.qs[0] + h * a.qs[1];
-    const int64_t k_off = b * a.ks[0] + hk * a.ks[1];
-    const int64_t v_off = b * a.vs[0] + hk * a.vs[1];
+    const int64_t k_off = (PAGED ? 0 : b * a.ks[0]) + hk * a.ks[1];  // (paged: the page's block term joins per key)
+    const int64_t v_off = (PAGED ? 0 : b * a.vs[0]) + hk * a.vs[1];
+    const int32_t *tab = PAGED ? a.table + b * a.table_stride : nullptr;  // this sequence's row of the block table
 
     for (int idx = tid; idx < kBr * d; idx += kWaves * 64) {
         const int r = idx / d, x = idx - r * d;
@@ -130,7 +141,11 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
         for (int r = 0; r < kRowsPerWave; ++r) dot[r] = 0;
         if (valid) {
-            const int64_t kb = k_off + (int64_t)key * a.ks[2];
+            int64_t kb = k_off + (int64_t)key * a.ks[2];
+            if constexpr (PAGED) {  // this lane's key: its page, and its row in the page
+                const int pg = key / a.page_size;
+                kb = k_off + fa2_decode_page(tab, pg, a.num_blocks) * a.ks[0] + (int64_t)(key - pg * a.page_size) * a.ks[2];
+            }
             for (int x = 0; x < d; ++x) {
                 const A kx = C::load(a.K, kb + (int64_t)x * a.ks[3]);
 #pragma unroll
@@ -155,8 +170,19 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
         }
         __syncthreads();
         const int kmax = (kend - kt) < kBc ? (kend - kt) : kBc;
+        int64_t v_page = 0;  // paged: element offset of row 0 of the current page, looked up once per run of keys inside a page
+        int v_row = 0;       //        and the next key's row in it
         for (int kk = 0; kk < kmax; ++kk) {
-            const int64_t vb = v_off + (int64_t)(kt + kk) * a.vs[2];
+            int64_t vb = v_off + (int64_t)(kt + kk) * a.vs[2];
+            if constexpr (PAGED) {
+                if (kk == 0 || v_row == a.page_size) {
+                    const int pg = (kt + kk) / a.page_size;
+                    v_row = kt + kk - pg * a.page_size;
+                    v_page = v_off + fa2_decode_page(tab, pg, a.num_blocks) * a.vs[0];
+                }
+                vb = v_page + (int64_t)v_row * a.vs[2];
+                ++v_row;
+            }
             A pr[kRowsPerWave];
 #pragma unroll
             for (int r = 0; r < kRowsPerWave; ++r) pr[r] = p_w[r * kBc + kk];
@@ -199,7 +225,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
     }
 }
 
-template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
+template <class E, class C, bool PAGED> int launch_p(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
     const long long gx = (long long)a.num_splits * a.nqt;
     if (gx > 0x7fffffffLL) {
         fa2_set_error("kvcache generic kernel: grid too large (num_splits * ceil(N_q / 16) = %lld)", gx);
@@ -210,20 +236,24 @@ template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const De
     const int dpl = (p.d + 63) / 64;
     static Fa2DeviceLatch attr_done;  // d > 256 in double asks for more than 64 KiB of dynamic LDS: opt in, once per device
     if (dpl > 4 && attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, PAGED, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(sizeof(typename E::acc_t) * ((size_t)kBr * 512 + (size_t)kWaves * kRowsPerWave * kBc)));
         attr_done.mark();
     }
-    if (dpl <= 1) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 1>), grid, block, smem, p.stream, a);
-    else if (dpl <= 2) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 2>), grid, block, smem, p.stream, a);
-    else if (dpl <= 4) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 4>), grid, block, smem, p.stream, a);
-    else hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, 8>), grid, block, smem, p.stream, a);
+    if (dpl <= 1) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 1>), grid, block, smem, p.stream, a);
+    else if (dpl <= 2) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 2>), grid, block, smem, p.stream, a);
+    else if (dpl <= 4) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 4>), grid, block, smem, p.stream, a);
+    else hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 8>), grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache generic kernel launch failed: %s", hipGetErrorString(e));
         return FA2_ERR_LAUNCH;
     }
     return FA2_OK;
+}
+
+template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
+    return p.table ? launch_p<E, C, true>(p, a) : launch_p<E, C, false>(p, a);
 }
 
 }  // namespace
@@ -241,6 +271,7 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     a.c_log2e = (double)p.scale * FA2_LOG2E;
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+    a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     if (p.kv_dtype != p.dtype) {  // fp8 cache under 16-bit Q, O, L
         const bool e4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
         if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_F16)

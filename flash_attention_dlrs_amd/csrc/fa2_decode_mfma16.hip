@@ -24,6 +24,13 @@
 // into the fp32 normalisation of the output, before it is rounded or written as a partial.  A chunk past the split's end is
 // zeros before the conversion, so no stale byte (NaN and inf patterns included) is ever converted.
 //
+// Paged cache (fa2_fwd_kvcache_paged).  PAGED is a template parameter as well: K and V are a page pool and key j of sequence b
+// is row j % page_size of page table[b][j / page_size].  Only the tile's base address differs.  With page_size % 64 == 0 a key
+// tile (32 or 64 keys on a multiple of its size) lies inside one page, so its table entry is uniform over the workgroup:
+// stage_load reads it with one scalar load per tile, clamps it to [0, num_blocks - 1] (a wild entry gives a wrong result, never
+// an access outside the pool) and folds it into the tile's 64-bit base.  The load for step s + 1 is issued a compute step ahead
+// of its use, as the tile's own loads are.  The entry of a tile at or past the split's end is not loaded.
+//
 // Output.  num_splits == 1: O / l and L = m + log2 l in the I/O dtype, a row without a visible key as O = 0, L = +inf.
 // Otherwise every (split, row) writes the normalised fp32 partial O_s and L_s (an empty split: 0 and -inf) for the combine
 // launch (fa2_decode_combine.hip); vector stores only.
@@ -94,6 +101,9 @@ struct DecodeMfmaArgs {
     float c_log2e;  // scale * log2(e) > 0
     const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
     int64_t kds[2], vds[2];
+    const int32_t *table;  // paged cache only: entry [b, i] at b * table_stride + i; ks[0], vs[0] are the block strides
+    int64_t table_stride;
+    int page_size, num_blocks;
 };
 
 // Byte offset of 16-byte chunk `ch` of row `row` inside one [rows][D] 16-bit tile (the LDS tile is 16-bit for every cache
@@ -105,8 +115,8 @@ template <int D> __device__ __forceinline__ int lds_off(int row, int ch) {
 }
 
 // RB = 32-row blocks of the query side, KG = key groups (RB * KG = 4 waves), BC = keys per tile (32 or 64).  C: the cache
-// element type, T or CacheE4M3 / CacheE5M2.
-template <typename T, typename C, int D, int RB, int KG, int BC>
+// element type, T or CacheE4M3 / CacheE5M2.  PAGED: K and V are a page pool behind a block table.
+template <typename T, typename C, bool PAGED, int D, int RB, int KG, int BC>
 __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(const DecodeMfmaArgs a) {
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -157,23 +167,53 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
 
     // ---- staging map: thread handles chunk (row = it*RPI + tid/CPR, ch = tid%CPR) of each tile.
     const int st_row = tid / CPR, st_ch = tid % CPR;
-    const char *kg = a.K + b * a.ks[0] + hk * a.ks[1] + (int64_t)(kb0 + st_row) * a.ks[2] + st_ch * 16;
-    const char *vg = a.V + b * a.vs[0] + hk * a.vs[1] + (int64_t)(kb0 + st_row) * a.vs[2] + st_ch * 16;
+    // (paged: the page and the tile's first row in it are the tile's, added in stage_load)
+    const char *kg = a.K + hk * a.ks[1] + (PAGED ? (int64_t)st_row * a.ks[2] : b * a.ks[0] + (int64_t)(kb0 + st_row) * a.ks[2]) + st_ch * 16;
+    const char *vg = a.V + hk * a.vs[1] + (PAGED ? (int64_t)st_row * a.vs[2] : b * a.vs[0] + (int64_t)(kb0 + st_row) * a.vs[2]) + st_ch * 16;
     // + it*RPI*ROWB (swizzle depends on row&15 only).  fp8: the load's 16 elements are LDS chunks 2 st_ch and 2 st_ch + 1.
     const int st_lds = lds_off<D>(st_row, F8 ? 2 * st_ch : st_ch);
     const int st_lds1 = F8 ? lds_off<D>(st_row, 2 * st_ch + 1) : 0;
 
+    // paged: the walk over the pages.  stage_load takes the tiles in order (g inside s, s = 0, 1, ...), a tile is BC keys on a
+    // multiple of BC and page_size is a multiple of 64: (pg_i, pg_row) -- the page of the next tile and the tile's first row in it
+    // -- advance by BC rows per tile and wrap at page_size, all in scalar registers, no division in the loop.
+    static_assert(!PAGED || FA2_KVCACHE_KEY_TILE % BC == 0, "a key tile must not straddle a page");
+    int pg_i = 0, pg_row = 0;
+    const int32_t *tab = nullptr;
+    if constexpr (PAGED) {
+        pg_i = kb0 / a.page_size;
+        pg_row = kb0 - pg_i * a.page_size;
+        tab = a.table + b * a.table_stride;
+    }
     u32x4 kreg[KG][CPT], vreg[KG][CPT];
     auto stage_load = [&](int s) {
 #pragma unroll
-        for (int g = 0; g < KG; ++g)
+        for (int g = 0; g < KG; ++g) {
+            int64_t kpage = 0, vpage = 0;  // paged: byte offset of the tile's first row from the pool's (hk, row 0)
+            if constexpr (PAGED) {
+                // one scalar load per tile; the entry of a tile at or past the split's end (<= N_k) is not part of the problem and
+                // may lie past the table's row: not loaded (every chunk of such a tile is zeros below)
+                if (kb0 + (KG * s + g) * BC < ke) {
+                    const int64_t e = fa2_decode_page(tab, pg_i, a.num_blocks);
+                    kpage = e * a.ks[0] + (int64_t)pg_row * a.ks[2];
+                    vpage = e * a.vs[0] + (int64_t)pg_row * a.vs[2];
+                }
+                pg_row += BC;
+                if (pg_row >= a.page_size) {
+                    pg_row = 0;
+                    ++pg_i;
+                }
+            }
 #pragma unroll
             for (int it = 0; it < CPT; ++it) {
                 const int rel = (KG * s + g) * BC + it * RPI;  // tile row 0 of this pass, relative to kb0
                 const bool ok = kb0 + rel + st_row < ke;       // past the split's end (<= N_k): zeros, never read
-                kreg[g][it] = ok ? *(const u32x4 *)(kg + (int64_t)rel * a.ks[2]) : u32x4{0, 0, 0, 0};
-                vreg[g][it] = ok ? *(const u32x4 *)(vg + (int64_t)rel * a.vs[2]) : u32x4{0, 0, 0, 0};
+                const int64_t ko = PAGED ? kpage + (int64_t)(it * RPI) * a.ks[2] : (int64_t)rel * a.ks[2];
+                const int64_t vo = PAGED ? vpage + (int64_t)(it * RPI) * a.vs[2] : (int64_t)rel * a.vs[2];
+                kreg[g][it] = ok ? *(const u32x4 *)(kg + ko) : u32x4{0, 0, 0, 0};
+                vreg[g][it] = ok ? *(const u32x4 *)(vg + vo) : u32x4{0, 0, 0, 0};
             }
+        }
     };
     auto stage_write = [&]() {
 #pragma unroll
@@ -388,11 +428,11 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     }
 }
 
-template <typename T, typename C, int D, int RB, int KG, int BC> int launch_t(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
+template <typename T, typename C, bool PAGED, int D, int RB, int KG, int BC> int launch_t(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
     const dim3 grid(p.num_splits, p.H_kv, p.B), block(RB * KG * 64);
     constexpr size_t smem = (size_t)KG * 2 * BC * D * 2;
     static_assert(smem <= 64 * 1024, "two workgroups per CU");
-    hipLaunchKernelGGL((fa2_decode_mfma16_kernel<T, C, D, RB, KG, BC>), grid, block, smem, p.stream, a);
+    hipLaunchKernelGGL((fa2_decode_mfma16_kernel<T, C, PAGED, D, RB, KG, BC>), grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mfma16 kernel launch failed: %s", hipGetErrorString(e));
@@ -401,16 +441,20 @@ template <typename T, typename C, int D, int RB, int KG, int BC> int launch_t(co
     return FA2_OK;
 }
 
-template <typename T, typename C> int launch_d(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
+template <typename T, typename C, bool PAGED> int launch_d(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
     const bool one = (int64_t)a.g * p.N_q <= 32;  // one 32-row block: four key groups
-    if (p.d == 128) return one ? launch_t<T, C, 128, 1, 4, 32>(p, a) : launch_t<T, C, 128, 2, 2, 64>(p, a);
-    return one ? launch_t<T, C, 64, 1, 4, 64>(p, a) : launch_t<T, C, 64, 2, 2, 64>(p, a);
+    if (p.d == 128) return one ? launch_t<T, C, PAGED, 128, 1, 4, 32>(p, a) : launch_t<T, C, PAGED, 128, 2, 2, 64>(p, a);
+    return one ? launch_t<T, C, PAGED, 64, 1, 4, 64>(p, a) : launch_t<T, C, PAGED, 64, 2, 2, 64>(p, a);
+}
+
+template <typename T, typename C> int launch_p(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
+    return p.table ? launch_d<T, C, true>(p, a) : launch_d<T, C, false>(p, a);
 }
 
 template <typename T> int launch_c(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
-    if (p.kv_dtype == FA2_DTYPE_F8E4M3) return launch_d<T, CacheE4M3>(p, a);
-    if (p.kv_dtype == FA2_DTYPE_F8E5M2) return launch_d<T, CacheE5M2>(p, a);
-    return launch_d<T, T>(p, a);
+    if (p.kv_dtype == FA2_DTYPE_F8E4M3) return launch_p<T, CacheE4M3>(p, a);
+    if (p.kv_dtype == FA2_DTYPE_F8E5M2) return launch_p<T, CacheE5M2>(p, a);
+    return launch_p<T, T>(p, a);
 }
 
 bool fp8_cache(const Fa2DecodeProblem &p) { return p.kv_dtype == FA2_DTYPE_F8E4M3 || p.kv_dtype == FA2_DTYPE_F8E5M2; }
@@ -432,13 +476,16 @@ bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p) {
         if ((p.qs[k] & 7) || (p.ks[k] & kmask) || (p.vs[k] & kmask) || (p.os[k] & 7)) return false;
     if (!aligned16(p.Q) || !aligned16(p.K) || !aligned16(p.V) || !aligned16(p.O)) return false;
     if (p.num_splits > 1 && !aligned16(p.o_part)) return false;
+    // paged: a key tile (32 or 64 keys on a multiple of its size) must lie inside one page; the block stride is ks[0] above
+    if (p.table && p.page_size % FA2_KVCACHE_KEY_TILE != 0) return false;
     return true;
 }
 
 int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) {
     if (!fa2_decode_mfma16_supports(p)) {
         fa2_set_error("kvcache mfma16 kernel: needs f16/bf16 (the cache alike, or fp8), d in {64,128}, g * N_q <= 64, unit d-stride, "
-                      "16-byte aligned rows (and workspace), scale > 0");
+                      "16-byte aligned rows (and workspace), scale > 0%s",
+                      p.table ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
         return FA2_ERR_UNSUPPORTED;
     }
     DecodeMfmaArgs a;
@@ -456,5 +503,6 @@ int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) {
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+    a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }

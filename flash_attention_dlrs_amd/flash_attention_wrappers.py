@@ -158,15 +158,31 @@ def _kvcache_descale(name, t, Q, B, H_kv):
         raise ValueError(f"kvcache: {name} of shape {tuple(t.shape)} does not broadcast to (B, H_kv) = ({B}, {H_kv})") from None
 
 
-def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale=None, v_descale=None):
-    """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, descales, cache_seqlens, window,
-    num_splits).  Pure: takes CPU tensors as well (the CUDA-device check is the launch's)."""
-    if Q.dim() != 4 or K_cache.dim() != 4 or V_cache.dim() != 4 or K_cache.shape != V_cache.shape \
+def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale=None, v_descale=None, block_table=None):
+    """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, descales, cache_seqlens, block_table,
+    window, num_splits).  Pure: takes CPU tensors as well (the CUDA-device check is the launch's)."""
+    if block_table is not None:  # paged: K_cache, V_cache are pools, their leading axis counts pages, B is Q's
+        if Q.dim() != 4 or K_cache.dim() != 4 or V_cache.dim() != 4 or K_cache.shape != V_cache.shape \
+                or Q.shape[3] != K_cache.shape[3] or Q.shape[2] < 1 or K_cache.shape[0] < 1 or K_cache.shape[2] < 1:
+            raise ValueError(f"kvcache: with block_table, Q must be (B, H, N_q, d) and K_cache, V_cache pools (num_blocks, H_kv, "
+                             f"page_size, d) of one shape with N_q, num_blocks, page_size >= 1: got Q {tuple(Q.shape)}, K_cache "
+                             f"{tuple(K_cache.shape)}, V_cache {tuple(V_cache.shape)}")
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 \
+                or block_table.shape[0] != Q.shape[0] or block_table.shape[1] < 1:
+            raise ValueError(f"kvcache: block_table must be an int32 tensor (B, max_blocks) with B = {Q.shape[0]}, max_blocks >= 1")
+        if block_table.stride(1) != 1 or block_table.stride(0) < 0:
+            raise ValueError(f"kvcache: block_table needs unit stride in its last axis, got strides {tuple(block_table.stride())}")
+        if block_table.device != Q.device:
+            raise ValueError(f"kvcache: block_table must be on Q's device ({Q.device}), got {block_table.device}")
+        if block_table.shape[1] * K_cache.shape[2] > 1 << 28:
+            raise ValueError(f"kvcache: the capacity max_blocks * page_size must be <= 2^28, got "
+                             f"{block_table.shape[1]} * {K_cache.shape[2]}")
+    elif Q.dim() != 4 or K_cache.dim() != 4 or V_cache.dim() != 4 or K_cache.shape != V_cache.shape \
             or Q.shape[0] != K_cache.shape[0] or Q.shape[3] != K_cache.shape[3] or Q.shape[2] < 1 or K_cache.shape[2] < 1:
         raise ValueError(f"kvcache: Q must be (B, H, N_q, d) and K_cache, V_cache (B, H_kv, S_k, d) with N_q, S_k >= 1: got Q "
                          f"{tuple(Q.shape)}, K_cache {tuple(K_cache.shape)}, V_cache {tuple(V_cache.shape)}")
     # the head rule of the dense entry points, on views that drop the sequence axis (N_q and S_k differ here)
-    gqa_kv_heads(Q[:, :, :1], K_cache[:, :, :1], V_cache[:, :, :1])
+    gqa_kv_heads(Q[:1, :, :1], K_cache[:1, :, :1], V_cache[:1, :, :1])
     if Q.dtype in FP8_CACHE_DTYPES:
         raise ValueError(f"kvcache: dtype {Q.dtype} is not supported for Q (e4m3fn cannot hold L = +inf)")
     if K_cache.dtype != V_cache.dtype:
@@ -195,7 +211,7 @@ def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k
 
 
 def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, causal=False, scale=1.0, window=None, num_splits=0,
-                                    variant="auto", k_descale=None, v_descale=None):
+                                    variant="auto", k_descale=None, v_descale=None, block_table=None):
     """Decode attention over a padded KV cache, split-KV (include/fa2_fwd.h fa2_fwd_kvcache) -> (O, L).  Q (B, H, N_q, d);
     K_cache, V_cache (B, H_kv, S_k, d) of capacity S_k, any strides (a flash-attn (B, S, H_kv, d) cache: pass its
     .transpose(1, 2) view), H_kv dividing H; cache_seqlens int32 (B,) on Q's device, sequence b attends to its first
@@ -206,8 +222,19 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     fp8 cache (fa2_fwd_kvcache_fp8): K_cache and V_cache in torch.float8_e4m3fn or torch.float8_e5m2 (both the same) under
     float16 / bfloat16 Q.  K = k_descale * float(K_cache), V = v_descale * float(V_cache) with float32 descales on Q's device that
     broadcast to (B, H_kv) (None: 1; they must be finite and > 0) -- quantize_kv_cache makes such a cache.  The arithmetic stays
-    16-bit: only the cache's storage is fp8."""
-    check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale, v_descale)
+    16-bit: only the cache's storage is fp8.
+
+    Paged cache (fa2_fwd_kvcache_paged): with block_table, an int32 (B, max_blocks) tensor on Q's device with unit stride in its
+    last axis, K_cache and V_cache are page pools (num_blocks, H_kv, page_size, d), any strides (a flash-attn (num_blocks,
+    page_size, H_kv, d) pool: pass its .transpose(1, 2) view), in Q's dtype or fp8 with descales as above.  Key j of sequence b is
+    row j % page_size of page block_table[b, j // page_size]; the capacity max_blocks * page_size takes S_k's place (cache_seqlens
+    None: every sequence uses all of it).  Pages may be shared between sequences.  The table's contents are not validated (that
+    would need a device synchronisation): the kernels clamp every entry they read to [0, num_blocks - 1], so a bad entry gives a
+    wrong result for that sequence and never an access outside the pool; entries of pages past a sequence's length, pool pages
+    no visible key maps to and the rows of a last page past the length are never read.  On the cache the pool was scattered from
+    the result equals the contiguous call's bit for bit.  variant "mfma16" needs page_size % 64 == 0; "auto" takes the generic
+    kernel for other page sizes."""
+    check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale, v_descale, block_table)
     if variant not in _lib.KVCACHE_VARIANTS:
         raise ValueError(f"kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
     if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
@@ -217,8 +244,15 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     dtype = convert_triton_dtype(Q.dtype)
     O = torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device)
     L = torch.empty(B, H, N_q, dtype=Q.dtype, device=Q.device)
-    n = num_splits or _lib.kvcache_num_splits(B, H, H_kv, N_q, K_cache.shape[2], d, dtype)
+    S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
+    n = num_splits or _lib.kvcache_num_splits(B, H, H_kv, N_q, S_k, d, dtype)
     ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    if block_table is not None:
+        _lib.fa2_fwd_kvcache_paged(Q, K_cache, V_cache, O, L, block_table, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
+                                   k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
+                                   v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), causal=causal, scale=scale,
+                                   window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
+        return O, L
     if K_cache.dtype in FP8_CACHE_DTYPES:
         _lib.fa2_fwd_kvcache_fp8(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
                                  k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),

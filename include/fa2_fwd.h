@@ -307,6 +307,43 @@ int fa2_fwd_kvcache_fp8(const void *Q, const void *K, const void *V, void *O, vo
                         int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                         void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
+/*
+ * The same decode over a PAGED KV cache: a pool of fixed-size pages and an int32 block table per sequence (vLLM, flash-attn's
+ * flash_attn_with_kvcache(..., block_table=)).  Addressing only: lengths, mask, split rule, workspace, variants, empty rows, the fp8
+ * formats and their descales are fa2_fwd_kvcache_fp8's, and on the cache a pool was scattered from the result is the contiguous
+ * call's bit for bit.  kv_dtype_enum == dtype_enum with null descales is the 16-bit (f32, f64) pool.
+ *
+ *   Pool.     K, V are logically (num_blocks, H_kv, page_size, d); k_strides / v_strides are element strides in that order, index 0
+ *             the BLOCK stride.  Any strides: a flash-attn (num_blocks, page_size, H_kv, d) pool is its transposed view.
+ *   Table.    block_table: device int32, logically (B, max_blocks), entry [b, i] at b * block_table_stride + i.  Key j of sequence
+ *             b, KV head hk, is the row at
+ *                 pool + block_table[b, j / page_size] * strides[0] + hk * strides[1] + (j % page_size) * strides[2],
+ *             formed in 64 bits.  Two sequences may name the same page.
+ *   Capacity. max_blocks * page_size plays S_k's role everywhere: N_k(b) = clamp(cache_seqlens[b], 0, max_blocks * page_size), the
+ *             split rule, and the S_k argument of fa2_kvcache_num_splits(...) that num_splits = 0 resolves to.
+ *   Entries.  The table lives on the device and is not validated.  The kernels clamp every entry they read to
+ *             [0, num_blocks - 1] before they form an address: a bad entry gives a wrong result for that sequence, never an access
+ *             outside the pool.  Entries of pages at or beyond ceil(N_k(b) / page_size) do not influence the output; pool pages no
+ *             visible key maps to, and the rows of a sequence's last page at or beyond N_k(b), are never read.
+ *   Variants. FA2_KVCACHE_VARIANT_MFMA16 under fa2_fwd_kvcache_fp8's conditions (the block stride aligned like the others) and
+ *             page_size % 64 == 0: a key tile then never straddles a page.  GENERIC takes any page_size >= 1 and everything else;
+ *             AUTO picks MFMA16 where it runs.
+ *
+ * Every error of fa2_fwd_kvcache_fp8 applies, the capacity in S_k's place.  FA2_ERR_BAD_ARG also for a null block_table, num_blocks,
+ * page_size or max_blocks < 1, max_blocks * page_size > 2^28, a negative block_table_stride, descales with kv_dtype_enum == dtype_enum.
+ */
+int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, void *L,
+                          const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                          const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                          const int32_t *block_table, int64_t block_table_stride,
+                          const float *k_descale, const float *v_descale,
+                          const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                          int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                          int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                          int32_t dtype_enum, int32_t kv_dtype_enum,
+                          int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                          void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
 /* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
  * elements plus fp32 partial L of num_splits * B * H * N_q. */
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits);
