@@ -30,7 +30,15 @@ and V of every copy are scattered into a (num_blocks, N, H_kv, d) pool under a r
 decode, decode_paged and gather (the route the paged call replaces: index_select of every sequence's pages into a padded cache,
 then the contiguous decode).  kind=events times all three; with --rocprof the traced child alternates decode and decode_paged
 alone and kind=kernels_paged is read off the kernel trace as in the fp8 mode (paged_over_contiguous is the ratio of the two
-averages).  Records go to bench_decode.jsonl."""
+averages).  Records go to bench_decode.jsonl.
+
+--append times the decode step with its cache update (fa2_fwd_kvcache_append), by device events, N_new = 1: the sides are fused
+(the one call), torch (the route it replaces: apply_rotary on Q and K, the quantisation with the given descales where the cache
+is fp8, an index_put through the block table where it is paged, then the existing decode call with the bumped lengths) and decode
+(the existing call alone, for the cost of the step beyond it).  It goes with --kv-dtype and --page-size, which then choose the
+cache.  A last record, case prefill_append, times kvcache_append alone against the torch route at N_new = 2048, B 8, H_kv 8,
+d 128 (K plus V 64 MiB): hbm_share counts the bytes read plus the bytes written (2 x 64 MiB, plus the tables) over the copy rate.
+Records: kind=events_append, bench_decode.jsonl."""
 import argparse
 import csv
 import glob
@@ -213,6 +221,149 @@ class Case:
             F.scaled_dot_product_attention(self.Q, self.K[self.i].transpose(1, 2), self.V[self.i].transpose(1, 2),
                                            attn_mask=self.mask, scale=self.scale, enable_gqa=True)
         return run
+
+    def append_setup(self):
+        """The decode step's inputs: one new token per sequence in flash-attn's (B, 1, H_kv, d) storage, rotary tables, and lengths
+        one short of the case's, so that the attention after the append is the case's."""
+        torch = self.torch
+        s, dev = self.shape, self.dev
+        mk = lambda *sh: (torch.randn(*sh, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
+        self.k_new, self.v_new = mk(s["B"], 1, s["H_kv"], s["d"]).transpose(1, 2), mk(s["B"], 1, s["H_kv"], s["d"]).transpose(1, 2)
+        ang = torch.rand(s["N_k"] + 8, s["d"] // 2, device=dev, dtype=torch.float64) * 6.283
+        self.cos, self.sin = ang.cos().to(torch.bfloat16), ang.sin().to(torch.bfloat16)
+        self.lens_before = self.lens_dev - 1
+        self.lens_out = torch.empty_like(self.lens_dev)
+        self.q_rot = torch.empty_like(self.Q)
+        fp8 = self.kv_dtype != "same"
+        self.cache_enum = self.kv_enum if fp8 else self.enum
+        if self.page_size:  # pools in the cache's dtype
+            if fp8:
+                P, perm = self.page_size, self.pages
+                pool8 = lambda t8: t8.view(torch.uint8).view(-1, P, s["H_kv"], s["d"])[torch.argsort(perm)].view(t8.dtype)  # noqa: E731
+                self.cK, self.cV = [pool8(k8) for k8, _ in self.K8], [pool8(v8) for v8, _ in self.V8]
+            else:
+                self.cK, self.cV = self.K_pool, self.V_pool
+        else:
+            self.cK, self.cV = ([k8 for k8, _ in self.K8], [v8 for v8, _ in self.V8]) if fp8 else (self.K, self.V)
+        self.kds = [kd for _, kd in self.K8] if fp8 else [None] * self.copies
+        self.vds = [vd for _, vd in self.V8] if fp8 else [None] * self.copies
+        n = self.auto_splits()
+        words = self._lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], s["d"], n) // 4
+        self.append_ws, self.append_n = torch.empty(max(words, 1), dtype=torch.float32, device=dev), n
+
+    def decode_any(self, Q, lens):
+        """The existing decode call over copy self.i of whichever cache --kv-dtype and --page-size chose."""
+        i = self.i
+        K, V = self.cK[i].transpose(1, 2), self.cV[i].transpose(1, 2)
+        kw = dict(scale=self.scale, num_splits=self.append_n, workspace=self.append_ws)
+        if self.page_size:
+            self._lib.fa2_fwd_kvcache_paged(Q, K, V, self.O, self.L, self.table, lens, self.enum, self.cache_enum,
+                                            k_descale=self.kds[i], v_descale=self.vds[i], **kw)
+        elif self.kv_dtype != "same":
+            self._lib.fa2_fwd_kvcache_fp8(Q, K, V, self.O, self.L, lens, self.enum, self.cache_enum, k_descale=self.kds[i],
+                                          v_descale=self.vds[i], **kw)
+        else:
+            self._lib.fa2_fwd_kvcache(Q, K, V, self.O, self.L, lens, self.enum, **kw)
+
+    def append_decode_alone(self):
+        def run():
+            self.i = (self.i + 1) % self.copies
+            self.decode_any(self.Q, self.lens_dev)
+        return run
+
+    def append_fused(self):
+        def run():
+            self.i = i = (self.i + 1) % self.copies
+            self._lib.fa2_fwd_kvcache_append(self.Q, self.cK[i].transpose(1, 2), self.cV[i].transpose(1, 2), self.O, self.L, self.k_new,
+                                             self.v_new, self.lens_before, self.lens_out, self.enum, self.cache_enum,
+                                             block_table=self.table if self.page_size else None, k_descale=self.kds[i],
+                                             v_descale=self.vds[i], rotary_cos=self.cos, rotary_sin=self.sin, q_rot=self.q_rot,
+                                             scale=self.scale, num_splits=self.append_n, workspace=self.append_ws)
+        return run
+
+    def append_torch(self):
+        """The route the fused call replaces, as an engine would write it in torch."""
+        from flash_attention_dlrs_amd import apply_rotary
+        torch = self.torch
+        rows = torch.arange(self.shape["B"], device=self.dev)
+
+        def run():
+            self.i = i = (self.i + 1) % self.copies
+            pos = self.lens_before.long()
+            q = apply_rotary(self.Q, self.cos, self.sin, pos[:, None, None])
+            k = apply_rotary(self.k_new, self.cos, self.sin, pos[:, None, None])[:, :, 0]
+            v = self.v_new[:, :, 0]
+            if self.kv_dtype != "same":
+                top = torch.finfo(self.cK[i].dtype).max
+                k = (k.float() / self.kds[i][:, :, None]).clamp(-top, top).to(self.cK[i].dtype)
+                v = (v.float() / self.vds[i][:, :, None]).clamp(-top, top).to(self.cV[i].dtype)
+            if self.page_size:
+                at = (self.table[rows, pos // self.page_size].long(), pos % self.page_size)
+            else:
+                at = (rows, pos)
+            # (index_put is not implemented for fp8 tensors: the bytes go through a uint8 view)
+            raw = (lambda t: t.view(torch.uint8)) if self.kv_dtype != "same" else (lambda t: t)  # noqa: E731
+            raw(self.cK[i])[at] = raw(k)
+            raw(self.cV[i])[at] = raw(v)
+            self.decode_any(q, self.lens_before + 1)
+        return run
+
+
+class PrefillAppend:
+    """kvcache_append alone at a prefill size against the torch route: N_new tokens a sequence into an empty cache."""
+
+    def __init__(self, dev, B=8, H_kv=8, N_new=2048, d=128, copies=4):
+        import torch
+        self.torch, self.shape, self.copies, self.i = torch, dict(B=B, H_kv=H_kv, N_new=N_new, d=d), copies, 0
+        mk = lambda *sh: (torch.randn(*sh, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
+        self.k_new, self.v_new = [mk(B, H_kv, N_new, d) for _ in range(copies)], [mk(B, H_kv, N_new, d) for _ in range(copies)]
+        self.K, self.V = [mk(B, H_kv, N_new, d) for _ in range(copies)], [mk(B, H_kv, N_new, d) for _ in range(copies)]
+        ang = torch.rand(N_new, d // 2, device=dev, dtype=torch.float64) * 6.283
+        self.cos, self.sin = ang.cos().to(torch.bfloat16), ang.sin().to(torch.bfloat16)
+        self.lens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.moved_bytes = 2 * 2 * 2 * B * H_kv * N_new * d + 2 * 2 * N_new * (d // 2)  # K and V read and written, the tables read
+
+    def fused(self):
+        from flash_attention_dlrs_amd import kvcache_append
+
+        def run():
+            self.i = i = (self.i + 1) % self.copies
+            kvcache_append(self.K[i], self.V[i], self.k_new[i], self.v_new[i], self.lens, rotary_cos=self.cos, rotary_sin=self.sin)
+        return run
+
+    def torch_route(self):
+        from flash_attention_dlrs_amd import apply_rotary
+        torch, s = self.torch, self.shape
+        rows = torch.arange(s["B"], device=self.lens.device)[:, None]
+        steps = torch.arange(s["N_new"], device=self.lens.device)
+
+        def run():
+            self.i = i = (self.i + 1) % self.copies
+            pos = self.lens.long()[:, None] + steps  # (B, N_new): the lengths live on the device
+            k = apply_rotary(self.k_new[i], self.cos, self.sin, pos[:, None, :])
+            self.K[i].transpose(1, 2)[rows, pos] = k.transpose(1, 2)
+            self.V[i].transpose(1, 2)[rows, pos] = self.v_new[i].transpose(1, 2)
+            return self.lens + s["N_new"]
+        return run
+
+
+def run_append(names, args, fh):
+    import torch
+    dev = torch.device("cuda:0")
+    for name in names:
+        c = Case(name, dev, args.kv_dtype, args.page_size)
+        c.append_setup()
+        sides = {"fused": c.append_fused(), "torch": c.append_torch(), "decode": c.append_decode_alone()}
+        res = interleaved(torch, list(sides.values()), args.iters, args.rounds)
+        emit(fh, kind="events_append", case=name, kv_dtype=args.kv_dtype, page_size=args.page_size, N_new=1, **c.shape, ragged=c.ragged,
+             num_splits=c.auto_splits(), **{k: r for k, r in zip(sides, res)})
+        del c
+        torch.cuda.empty_cache()
+    p = PrefillAppend(dev)
+    sides = {"fused": p.fused(), "torch": p.torch_route()}
+    res = interleaved(torch, list(sides.values()), max(args.iters // 5, 4), args.rounds)
+    emit(fh, kind="events_append", case="prefill_append", kv_dtype="same", page_size=0, **p.shape, moved_bytes=p.moved_bytes,
+         hbm_share=round(p.moved_bytes / (res[0]["median_us"] * 1e-6) / HBM_COPY_RATE, 3), **{k: r for k, r in zip(sides, res)})
 
 
 def time_us(torch, fn, iters):
@@ -430,10 +581,14 @@ def main():
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="same", help="also time the decode over an fp8 cache of this format")
     ap.add_argument("--page-size", type=int, default=0, metavar="N",
                     help="time the paged decode over pools of N-key pages against the contiguous decode (N must divide every N_k)")
+    ap.add_argument("--append", action="store_true",
+                    help="time the decode step with its cache update (fused call against the torch route), and the prefill-sized append")
     ap.add_argument("--out", help="default: profiles/decode/bench_decode.jsonl, bench_decode_fp8.jsonl with --kv-dtype")
     args = ap.parse_args()
-    args.out = args.out or (OUT if args.kv_dtype == "same" else OUT_FP8)
-    if args.page_size and (args.kv_dtype != "same" or args.sweep):
+    args.out = args.out or (OUT if args.kv_dtype == "same" or args.append else OUT_FP8)
+    if args.append and (args.sweep or args.rocprof):
+        ap.error("--append goes without --sweep and --rocprof")
+    if args.page_size and not args.append and (args.kv_dtype != "same" or args.sweep):
         ap.error("--page-size goes without --kv-dtype and --sweep")
     if args.pass_case:
         return run_pass(args.pass_case, args)
@@ -442,7 +597,9 @@ def main():
     names = args.cases.split(",")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
-        if args.rocprof:
+        if args.append:
+            run_append(names, args, fh)
+        elif args.rocprof:
             run_rocprof(names, args, fh)
         else:
             run_events(names, args, fh)

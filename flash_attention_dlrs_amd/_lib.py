@@ -53,7 +53,7 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant",
            "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant",
            "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_fwd_kvcache_paged",
-           "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits")
+           "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -158,6 +158,17 @@ def lib():
         # ... over a paged cache: block_table and its row stride after cache_seqlens; num_blocks, page_size, max_blocks in S_k's place
         l.fa2_fwd_kvcache_paged.restype = ctypes.c_int
         l.fa2_fwd_kvcache_paged.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64, vp, vp, i64p, i64p] + [ctypes.c_int32] * 11 + \
+            [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # the cache append: cache + strides, table + stride, new tokens + strides, lengths in / out, descales + strides, rotary tables +
+        # row strides, S_rot rotary_dim interleaved, Q q_rot q_strides, H N_q q_pos_per_row, B H_kv N_new S_k num_blocks page_size
+        # max_blocks d dtype kv_dtype, stream
+        l.fa2_kvcache_append.restype = ctypes.c_int
+        l.fa2_kvcache_append.argtypes = [vp, vp, i64p, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, vp, i64p, i64p, vp, vp,
+                                         ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp, vp, i64p] + [ctypes.c_int32] * 13 + [vp]
+        # ... fused with the decode attention that follows
+        l.fa2_fwd_kvcache_append.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_append.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, i64p, i64p, vp, vp,
+                                             ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp] + [ctypes.c_int32] * 13 + \
             [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
@@ -446,6 +457,73 @@ def fa2_fwd_kvcache_paged(Q, K, V, O, L, block_table, cache_seqlens, dtype_enum,
             None if cache_seqlens is None else cache_seqlens.data_ptr(), block_table.data_ptr(), block_table.stride(0),
             kd_ptr, vd_ptr, kd_st, vd_st, B, H, K.shape[1], N_q, K.shape[0], K.shape[2], block_table.shape[1], d,
             int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
+            int(variant), _raw_stream(Q.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):
+    """The pieces both append launchers pass alike: (table pointer, table stride, descale pointers and strides, rotary pointers,
+    row strides, S_rot, rotary_dim, S_k, num_blocks, page_size, max_blocks)."""
+    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
+    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
+    cos_ptr, cos_st, S_rot, rd = (None, 0, 0, 0) if rotary_cos is None else \
+        (rotary_cos.data_ptr(), rotary_cos.stride(0), rotary_cos.shape[0], 2 * rotary_cos.shape[1])
+    sin_ptr, sin_st = (None, 0) if rotary_sin is None else (rotary_sin.data_ptr(), rotary_sin.stride(0))
+    if block_table is None:
+        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, K.shape[2], 0, 0, 0
+    else:
+        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, K.shape[0], K.shape[2], block_table.shape[1]
+    return tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb
+
+
+def fa2_kvcache_append(K, V, k_new, v_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None, k_descale=None,
+                       v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, Q=None, q_rot=None,
+                       q_pos_per_row=False):
+    """Launch the cache append (include/fa2_fwd.h fa2_kvcache_append) on the current stream of k_new's device: k_new / v_new
+    (B, H_kv, N_new, d), any strides, go into the cache K / V (B, H_kv, S_k, d), or the pool (num_blocks, H_kv, page_size, d) with
+    block_table, in place; seqlens_out, an int32 (B,) tensor that is not cache_seqlens, receives the new lengths.  rotary_cos /
+    rotary_sin (S_rot, rotary_dim / 2) in k_new's dtype with unit last stride; Q (B, H, N_q, d) with them is rotated into the
+    contiguous q_rot.  Descales as in fa2_fwd_kvcache_fp8."""
+    if k_new.device.type != "cuda":
+        raise NotImplementedError("K_cache, V_cache, k_new, v_new must be on the same CUDA device")
+    B, H_kv, N_new, d = k_new.shape
+    tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
+    q_ptr, q_st, H, N_q = (None, None, 0, 0) if Q is None else (Q.data_ptr(), _i64(Q.stride()), Q.shape[1], Q.shape[2])
+    with torch.cuda.device(k_new.device):
+        rc = lib().fa2_kvcache_append(
+            K.data_ptr(), V.data_ptr(), _i64(K.stride()), _i64(V.stride()), tb_ptr, tb_st, k_new.data_ptr(), v_new.data_ptr(),
+            _i64(k_new.stride()), _i64(v_new.stride()), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), kd_ptr, vd_ptr, kd_st, vd_st,
+            cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), q_ptr, None if q_rot is None else q_rot.data_ptr(),
+            q_st, H, N_q, int(bool(q_pos_per_row)), B, H_kv, N_new, S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum),
+            _raw_stream(k_new.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_fwd_kvcache_append(Q, K, V, O, L, k_new, v_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,
+                           k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None,
+                           causal=False, scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch the fused decode step (include/fa2_fwd.h fa2_fwd_kvcache_append) on the current stream of Q's device: the append
+    above, then the decode attention over the updated cache with seqlens_out as its lengths and, with rotary tables, q_rot (a
+    contiguous (B, H, N_q, d) tensor in Q's dtype) as its Q.  The other arguments are fa2_fwd_kvcache_paged's."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    ws_ptr = None if workspace is None else workspace.data_ptr()
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_kvcache_append(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, k_new.data_ptr(),
+            v_new.data_ptr(), _i64(k_new.stride()), _i64(v_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd,
+            int(bool(rotary_interleaved)), None if q_rot is None else q_rot.data_ptr(), B, H, K.shape[1], N_q, k_new.shape[2], S_k, nb,
+            ps, mb, d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
             int(variant), _raw_stream(Q.device.index))
     if rc != 0:
         _raise(rc)

@@ -64,3 +64,31 @@ static inline bool fa2_decode_mfma16_shape(int32_t H, int32_t H_kv, int32_t N_q,
            (int64_t)(H / H_kv) * N_q <= 64;
 }
 int fa2_launch_decode_combine(const Fa2DecodeProblem &p);  // second launch, num_splits > 1 only
+
+// One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
+// each tensor's dtype.  It is the kernel's argument as well.
+struct Fa2AppendProblem {
+    void *K, *V;  // the cache (B, H_kv, capacity, d) or, with `table`, the page pool (num_blocks, H_kv, page_size, d)
+    int64_t ks[4], vs[4];
+    const int32_t *table;  // as in Fa2DecodeProblem, or null
+    int64_t table_stride;
+    int32_t page_size, num_blocks;
+    int32_t capacity;  // S_k, or max_blocks * page_size
+    const void *k_new, *v_new;  // (B, H_kv, N_new, d) in `dtype`
+    int64_t kns[4], vns[4];
+    const int32_t *seqlens;  // device, B entries: token t of sequence b becomes key clamp(seqlens[b], 0, capacity) + t
+    int32_t *seqlens_out;    // device, B entries: min(clamp(seqlens[b], 0, capacity) + N_new, capacity)
+    const float *kd, *vd;    // fp8 cache: the stored byte is fp8(x / descale); null = 1
+    int64_t kds[2], vds[2];
+    const void *cos, *sin;  // (S_rot, rotary_dim / 2) in `dtype`, unit last stride, or both null: no rotary
+    int64_t cos_stride, sin_stride;
+    int32_t S_rot, rotary_dim, interleaved;
+    const void *Q;  // (B, H, N_q, d), rotated into q_rot (contiguous) when the tables are given; null: the cache alone
+    void *q_rot;
+    int64_t qs[4];
+    int32_t H, N_q, q_pos_per_row;
+    int32_t B, H_kv, N_new, d;
+    int32_t dtype, kv_dtype;
+    hipStream_t stream;
+};
+int fa2_launch_decode_append(const Fa2AppendProblem &p);

@@ -1,6 +1,7 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8,
-// fa2_fwd_kvcache_paged and their helpers, declared in include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
-// two launches (split kernels, then the combine) on the caller's stream.
+// fa2_fwd_kvcache_paged, the cache append fa2_kvcache_append, the fused step fa2_fwd_kvcache_append and their helpers, declared in
+// include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
+// launches (the append where asked for, the split kernels, then the combine) on the caller's stream.
 #include "fa2_decode.h"
 
 namespace {
@@ -48,12 +49,14 @@ struct PagedCache {
     int32_t num_blocks, page_size, max_blocks;
 };
 
-// S_k is the capacity of a contiguous cache; with `pg` it is ignored and max_blocks * page_size takes its place.
+// S_k is the capacity of a contiguous cache; with `pg` it is ignored and max_blocks * page_size takes its place.  With `append`
+// (checked by check_append) that launch goes first, once every check here has passed.
 int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
                 const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
                 int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
                 float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
-                void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr, const PagedCache *pg = nullptr) {
+                void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr, const PagedCache *pg = nullptr,
+                const Fa2AppendProblem *append = nullptr) {
     const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
     const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
     for (int t = 0; t < 10; ++t)
@@ -187,9 +190,193 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     }
     if (variant == FA2_KVCACHE_VARIANT_AUTO)
         variant = fa2_decode_mfma16_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
+    if (append) {  // the fused step: the cache update first, on the same stream (a forced form that cannot run fails before it)
+        if (variant == FA2_KVCACHE_VARIANT_MFMA16 && !fa2_decode_mfma16_supports(p)) return fa2_launch_decode_mfma16(p);
+        rc = fa2_launch_decode_append(*append);
+        if (rc != FA2_OK) return rc;
+    }
     rc = variant == FA2_KVCACHE_VARIANT_MFMA16 ? fa2_launch_decode_mfma16(p) : fa2_launch_decode_generic(p);
     if (rc != FA2_OK || p.num_splits == 1) return rc;
     return fa2_launch_decode_combine(p);
+}
+
+// The arguments of fa2_kvcache_append as the entry points take them.
+struct AppendCall {
+    void *K, *V;
+    const int64_t *k_strides, *v_strides;
+    const int32_t *block_table;
+    int64_t block_table_stride;
+    const void *k_new, *v_new;
+    const int64_t *k_new_strides, *v_new_strides;
+    const int32_t *cache_seqlens;
+    int32_t *seqlens_out;
+    const float *k_descale, *v_descale;
+    const int64_t *k_descale_strides, *v_descale_strides;
+    const void *rotary_cos, *rotary_sin;
+    int64_t cos_stride, sin_stride;
+    int32_t S_rot, rotary_dim, rotary_interleaved;
+    const void *Q;
+    void *q_rot;
+    const int64_t *q_strides;
+    int32_t H, N_q, q_pos_per_row;
+    int32_t B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum;
+    void *hip_stream;
+};
+
+// Every check of fa2_kvcache_append, before any launch; on FA2_OK `p` is the problem to launch.
+int check_append(const AppendCall &c, Fa2AppendProblem &p) {
+    const void *ptrs[10] = {c.K, c.V, c.k_strides, c.v_strides, c.k_new, c.v_new, c.k_new_strides, c.v_new_strides, c.cache_seqlens,
+                            c.seqlens_out};
+    const char *names[10] = {"K", "V", "k_strides", "v_strides", "k_new", "v_new", "k_new_strides", "v_new_strides", "cache_seqlens",
+                             "seqlens_out"};
+    for (int t = 0; t < 10; ++t)
+        if (!ptrs[t]) {
+            fa2_set_error("kvcache append: null %s", names[t]);
+            return FA2_ERR_BAD_ARG;
+        }
+    if (c.seqlens_out == c.cache_seqlens) {
+        fa2_set_error("kvcache append: seqlens_out must not be cache_seqlens (the call does not modify its lengths)");
+        return FA2_ERR_BAD_ARG;
+    }
+    int64_t cap = c.S_k;
+    if (c.block_table) {
+        if (c.num_blocks < 1 || c.page_size < 1 || c.max_blocks < 1) {
+            fa2_set_error("kvcache append: num_blocks, page_size and max_blocks must be >= 1 (got num_blocks=%d, page_size=%d, "
+                          "max_blocks=%d)", c.num_blocks, c.page_size, c.max_blocks);
+            return FA2_ERR_BAD_ARG;
+        }
+        cap = (int64_t)c.max_blocks * c.page_size;
+        if (cap > (1 << 28)) {
+            fa2_set_error("kvcache append: the capacity max_blocks * page_size must be <= 2^28 (got %lld)", (long long)cap);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.block_table_stride < 0) {
+            fa2_set_error("kvcache append: negative block_table_stride");
+            return FA2_ERR_BAD_ARG;
+        }
+    } else if (cap < 1 || cap > (1 << 28)) {
+        fa2_set_error("kvcache append: S_k must be in [1, 2^28] (got %d)", c.S_k);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.B < 1 || c.B > 65535) {
+        fa2_set_error("kvcache append: B must be in [1, 65535] (got %d)", c.B);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.H_kv < 1 || c.H_kv > 65535) {
+        fa2_set_error("kvcache append: H_kv must be in [1, 65535] (got %d)", c.H_kv);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.N_new < 1 || c.N_new > (1 << 28)) {
+        fa2_set_error("kvcache append: N_new must be in [1, 2^28] (got %d)", c.N_new);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.Q) {
+        if (!c.q_strides) {
+            fa2_set_error("kvcache append: null q_strides with a non-null Q");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.H < 1 || c.H > 65535) {
+            fa2_set_error("kvcache append: H must be in [1, 65535] (got %d)", c.H);
+            return FA2_ERR_BAD_ARG;
+        }
+        const int rc = fa2_check_gqa(c.H, c.H_kv);
+        if (rc != FA2_OK) return rc;
+        if (c.N_q < 1 || c.N_q > (1 << 28)) {
+            fa2_set_error("kvcache append: N_q must be in [1, 2^28] (got %d)", c.N_q);
+            return FA2_ERR_BAD_ARG;
+        }
+    }
+    for (int k = 0; k < 4; ++k)
+        if (c.k_strides[k] < 0 || c.v_strides[k] < 0 || c.k_new_strides[k] < 0 || c.v_new_strides[k] < 0 || (c.Q && c.q_strides[k] < 0)) {
+            fa2_set_error("kvcache append: negative strides are not supported (k_strides, v_strides, k_new_strides, v_new_strides, "
+                          "q_strides)");
+            return FA2_ERR_BAD_ARG;
+        }
+    const bool wide = c.kv_dtype_enum == c.dtype_enum;  // the cache has the inputs' dtype
+    if (wide) {
+        if (c.k_descale || c.v_descale) {
+            fa2_set_error("kvcache append: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)", c.kv_dtype_enum);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.dtype_enum == FA2_DTYPE_F8E5M2 || c.dtype_enum == FA2_DTYPE_F8E4M3) {
+            fa2_set_error("kvcache append: dtype_enum %d: fp8 inputs are not supported (an fp8 cache takes f16 / bf16 inputs)", c.dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    } else {
+        if ((c.k_descale && !c.k_descale_strides) || (c.v_descale && !c.v_descale_strides)) {
+            fa2_set_error("kvcache append: null %s with a non-null descale",
+                          c.k_descale && !c.k_descale_strides ? "k_descale_strides" : "v_descale_strides");
+            return FA2_ERR_BAD_ARG;
+        }
+        if ((c.k_descale && (c.k_descale_strides[0] < 0 || c.k_descale_strides[1] < 0)) ||
+            (c.v_descale && (c.v_descale_strides[0] < 0 || c.v_descale_strides[1] < 0))) {
+            fa2_set_error("kvcache append: negative strides are not supported (k_descale_strides, v_descale_strides)");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.kv_dtype_enum != FA2_DTYPE_F8E4M3 && c.kv_dtype_enum != FA2_DTYPE_F8E5M2) {
+            fa2_set_error("kvcache append: kv_dtype_enum %d must be dtype_enum, FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", c.kv_dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16) {
+            fa2_set_error("kvcache append: dtype_enum %d (k_new, v_new, Q) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16 under an fp8 cache",
+                          c.dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    }
+    if (fa2_dtype_size(c.dtype_enum) == 0) {
+        fa2_set_error("unknown dtype enum %d", c.dtype_enum);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (c.d < 1 || c.d > 512) {
+        fa2_set_error("d=%d must be in [1, 512]", c.d);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    const bool rotary = c.rotary_cos || c.rotary_sin;
+    if (rotary) {
+        if (!c.rotary_cos || !c.rotary_sin) {
+            fa2_set_error("kvcache append: rotary_cos and rotary_sin go together (null %s)", c.rotary_cos ? "rotary_sin" : "rotary_cos");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.rotary_dim < 2 || c.rotary_dim > c.d || (c.rotary_dim & 1)) {
+            fa2_set_error("kvcache append: rotary_dim must be even and in [2, d = %d] (got %d)", c.d, c.rotary_dim);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.S_rot < 1) {
+            fa2_set_error("kvcache append: S_rot must be >= 1 (got %d)", c.S_rot);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.cos_stride < 0 || c.sin_stride < 0) {
+            fa2_set_error("kvcache append: negative strides are not supported (rotary_cos_stride, rotary_sin_stride)");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.Q && !c.q_rot) {
+            fa2_set_error("kvcache append: null q_rot with rotary tables and a non-null Q");
+            return FA2_ERR_BAD_ARG;
+        }
+    }
+    p.K = c.K; p.V = c.V;
+    for (int k = 0; k < 4; ++k) {
+        p.ks[k] = c.k_strides[k]; p.vs[k] = c.v_strides[k]; p.kns[k] = c.k_new_strides[k]; p.vns[k] = c.v_new_strides[k];
+        p.qs[k] = c.Q ? c.q_strides[k] : 0;
+    }
+    p.table = c.block_table;
+    p.table_stride = c.block_table ? c.block_table_stride : 0;
+    p.page_size = c.block_table ? c.page_size : 0; p.num_blocks = c.block_table ? c.num_blocks : 0;
+    p.capacity = (int32_t)cap;
+    p.k_new = c.k_new; p.v_new = c.v_new;
+    p.seqlens = c.cache_seqlens; p.seqlens_out = c.seqlens_out;
+    p.kd = wide ? nullptr : c.k_descale; p.vd = wide ? nullptr : c.v_descale;
+    for (int k = 0; k < 2; ++k) { p.kds[k] = p.kd ? c.k_descale_strides[k] : 0; p.vds[k] = p.vd ? c.v_descale_strides[k] : 0; }
+    p.cos = c.rotary_cos; p.sin = c.rotary_sin;
+    p.cos_stride = rotary ? c.cos_stride : 0; p.sin_stride = rotary ? c.sin_stride : 0;
+    p.S_rot = rotary ? c.S_rot : 1; p.rotary_dim = rotary ? c.rotary_dim : 0; p.interleaved = c.rotary_interleaved != 0;
+    p.Q = rotary ? c.Q : nullptr;  // without tables there is nothing to do to Q
+    p.q_rot = rotary ? c.q_rot : nullptr;
+    p.H = c.Q ? c.H : 0; p.N_q = c.Q ? c.N_q : 0; p.q_pos_per_row = c.q_pos_per_row != 0;
+    p.B = c.B; p.H_kv = c.H_kv; p.N_new = c.N_new; p.d = c.d;
+    p.dtype = c.dtype_enum; p.kv_dtype = c.kv_dtype_enum;
+    p.stream = (hipStream_t)c.hip_stream;
+    return FA2_OK;
 }
 
 }  // namespace
@@ -258,6 +445,54 @@ int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d
 int32_t fa2_kvcache_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
     return num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum);
+}
+
+int fa2_kvcache_append(void *K, void *V, const int64_t k_strides[4], const int64_t v_strides[4], const int32_t *block_table,
+                       int64_t block_table_stride, const void *k_new, const void *v_new, const int64_t k_new_strides[4],
+                       const int64_t v_new_strides[4], const int32_t *cache_seqlens, int32_t *seqlens_out, const float *k_descale,
+                       const float *v_descale, const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                       const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                       int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, const void *Q, void *q_rot,
+                       const int64_t q_strides[4], int32_t H, int32_t N_q, int32_t q_pos_per_row, int32_t B, int32_t H_kv,
+                       int32_t N_new, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                       int32_t dtype_enum, int32_t kv_dtype_enum, void *hip_stream) {
+    const AppendCall c = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, k_new_strides, v_new_strides,
+                          cache_seqlens, seqlens_out, k_descale, v_descale, k_descale_strides, v_descale_strides, rotary_cos, rotary_sin,
+                          rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot, q_strides, H, N_q,
+                          q_pos_per_row, B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, hip_stream};
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    return rc != FA2_OK ? rc : fa2_launch_decode_append(p);
+}
+
+int fa2_fwd_kvcache_append(const void *Q, void *K, void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
+                           const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
+                           const int32_t *cache_seqlens, int32_t *seqlens_out, const int32_t *block_table, int64_t block_table_stride,
+                           const float *k_descale, const float *v_descale, const int64_t k_descale_strides[2],
+                           const int64_t v_descale_strides[2], const void *k_new, const void *v_new, const int64_t k_new_strides[4],
+                           const int64_t v_new_strides[4], const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                           int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, void *q_rot,
+                           int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t N_new, int32_t S_k, int32_t num_blocks,
+                           int32_t page_size, int32_t max_blocks, int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal,
+                           float scale, int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace,
+                           int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    const int32_t per_row = causal || window_left >= 0 || window_right >= 0;  // flash-attn's rule for Q's rotary positions
+    const AppendCall c = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, k_new_strides, v_new_strides,
+                          cache_seqlens, seqlens_out, k_descale, v_descale, k_descale_strides, v_descale_strides, rotary_cos, rotary_sin,
+                          rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot, q_strides, H, N_q,
+                          per_row, B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, hip_stream};
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    if (rc != FA2_OK) return rc;
+    // the attention reads the rotated Q (contiguous) and the new lengths
+    const int64_t rot_strides[4] = {(int64_t)H * N_q * d, (int64_t)N_q * d, d, 1};
+    const bool rotated = p.Q != nullptr;
+    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
+    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
+    return fwd_kvcache(rotated ? q_rot : Q, K, V, O, L, rotated ? rot_strides : q_strides, k_strides, v_strides, o_strides, l_strides,
+                       seqlens_out, B, H, H_kv, N_q, S_k, d, dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
+                       workspace_bytes, hip_stream, variant, kv_dtype_enum == dtype_enum ? nullptr : &f8, block_table ? &pg : nullptr,
+                       &p);
 }
 
 }  // extern "C"

@@ -158,6 +158,132 @@ def _kvcache_descale(name, t, Q, B, H_kv):
         raise ValueError(f"kvcache: {name} of shape {tuple(t.shape)} does not broadcast to (B, H_kv) = ({B}, {H_kv})") from None
 
 
+def apply_rotary(x, cos, sin, positions, interleaved=False):
+    """Rotary embedding as the cache append applies it (include/fa2_fwd.h fa2_kvcache_append), in plain torch on any device: the
+    meaning of flash_attention_kvcache_forward's rotary_cos / rotary_sin and the yardstick of its tests, bit for bit.  x (..., d);
+    cos, sin (S_rot, rotary_dim / 2) with rotary_dim even and <= d; positions: an int tensor broadcasting to x.shape[:-1], clamped
+    to [0, S_rot - 1].  interleaved=False pairs column i with i + rotary_dim / 2 (GPT-NeoX), True pairs 2i with 2i + 1 (GPT-J);
+    columns >= rotary_dim pass through.  (x1, x2) -> (x1 c - x2 s, x2 c + x1 s) in float32 (float64 for float64 input), every
+    product, sum and difference rounded on its own, then one rounding to x.dtype."""
+    return _rotary(x, cos, sin, positions, interleaved).to(x.dtype)
+
+
+def _rotary(x, cos, sin, positions, interleaved):
+    """apply_rotary before the last rounding: float32 (float64 for float64 x), what an fp8 cache quantises."""
+    half = cos.shape[-1]
+    rd = 2 * half
+    if cos.dim() != 2 or cos.shape != sin.shape or half < 1 or rd > x.shape[-1]:
+        raise ValueError(f"apply_rotary: cos, sin must be (S_rot, rotary_dim / 2) of one shape with 2 <= rotary_dim <= d = "
+                         f"{x.shape[-1]}, got {tuple(cos.shape)}, {tuple(sin.shape)}")
+    wide = torch.float64 if x.dtype == torch.float64 else torch.float32
+    pos = torch.broadcast_to(torch.as_tensor(positions, device=x.device).long().clamp(0, cos.shape[0] - 1), x.shape[:-1])
+    c, s = cos.to(wide)[pos], sin.to(wide)[pos]  # (..., rotary_dim / 2)
+    xw = x.to(wide)
+    x1, x2 = (xw[..., 0:rd:2], xw[..., 1:rd:2]) if interleaved else (xw[..., :half], xw[..., half:rd])
+    o1 = x1 * c - x2 * s  # (torch rounds each of these operations on its own)
+    o2 = x2 * c + x1 * s
+    out = xw.clone()
+    if interleaved:
+        out[..., 0:rd:2], out[..., 1:rd:2] = o1, o2
+    else:
+        out[..., :half], out[..., half:rd] = o1, o2
+    return out
+
+
+def check_kvcache_append_args(K_cache, V_cache, k_new, v_new, cache_seqlens, k_descale=None, v_descale=None, block_table=None,
+                              rotary_cos=None, rotary_sin=None, Q=None):
+    """ValueError for what kvcache_append (and the append keywords of flash_attention_kvcache_forward) cannot take.  Pure: takes CPU
+    tensors as well."""
+    if (k_new is None) != (v_new is None):
+        raise ValueError("kvcache: k_new and v_new go together")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("kvcache: rotary_cos and rotary_sin go together")
+    if k_new is None:
+        if rotary_cos is not None:
+            raise ValueError("kvcache: rotary_cos / rotary_sin need k_new and v_new (the rotation is part of the cache update)")
+        return
+    if cache_seqlens is None:
+        raise ValueError("kvcache: k_new / v_new need cache_seqlens (the position the new tokens go to)")
+    if not isinstance(k_new, torch.Tensor) or not isinstance(v_new, torch.Tensor) or k_new.dim() != 4 or k_new.shape != v_new.shape \
+            or K_cache.dim() != 4 or K_cache.shape != V_cache.shape or k_new.shape[1] != K_cache.shape[1] \
+            or k_new.shape[3] != K_cache.shape[3] or k_new.shape[2] < 1 or (block_table is None and k_new.shape[0] != K_cache.shape[0]):
+        raise ValueError(f"kvcache: k_new, v_new must be (B, H_kv, N_new, d) of one shape with N_new >= 1, B, H_kv and d the cache's: "
+                         f"got k_new {tuple(k_new.shape)}, v_new {tuple(v_new.shape)}, K_cache {tuple(K_cache.shape)}, V_cache "
+                         f"{tuple(V_cache.shape)}")
+    B, H_kv = k_new.shape[:2]
+    if k_new.dtype != v_new.dtype or K_cache.dtype != V_cache.dtype:
+        raise ValueError("kvcache: k_new and v_new, and K_cache and V_cache, must have the same dtype")
+    if k_new.dtype in FP8_CACHE_DTYPES:
+        raise ValueError(f"kvcache: dtype {k_new.dtype} is not supported for k_new, v_new (an fp8 cache takes float16 / bfloat16)")
+    if K_cache.dtype in FP8_CACHE_DTYPES:
+        if k_new.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"kvcache: an fp8 cache needs k_new, v_new in float16 or bfloat16, got {k_new.dtype}")
+        _kvcache_descale("k_descale", k_descale, k_new, B, H_kv)
+        _kvcache_descale("v_descale", v_descale, k_new, B, H_kv)
+    else:
+        if k_new.dtype != K_cache.dtype:
+            raise ValueError("kvcache: k_new, v_new must have the cache's dtype (or the cache an fp8 dtype under 16-bit k_new, v_new)")
+        if k_descale is not None or v_descale is not None:
+            raise ValueError(f"kvcache: k_descale / v_descale go with an fp8 cache, not with {K_cache.dtype}")
+    convert_triton_dtype(k_new.dtype)
+    if Q is not None and Q.dtype != k_new.dtype:
+        raise ValueError("kvcache: k_new, v_new must have Q's dtype")
+    for name, t in (("v_new", v_new), ("K_cache", K_cache), ("V_cache", V_cache)):
+        if t.device != k_new.device:
+            raise ValueError(f"kvcache: {name} must be on k_new's device ({k_new.device}), got {t.device}")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 \
+            or not cache_seqlens.is_contiguous() or cache_seqlens.numel() != B:
+        raise ValueError(f"kvcache: cache_seqlens must be a contiguous int32 tensor of B = {B} entries")
+    if cache_seqlens.device != k_new.device:
+        raise ValueError(f"kvcache: cache_seqlens must be on k_new's device ({k_new.device}), got {cache_seqlens.device}")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 \
+                or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"kvcache: block_table must be an int32 tensor (B, max_blocks) with B = {B}, max_blocks >= 1")
+        if block_table.stride(1) != 1 or block_table.stride(0) < 0:
+            raise ValueError(f"kvcache: block_table needs unit stride in its last axis, got strides {tuple(block_table.stride())}")
+        if block_table.device != k_new.device:
+            raise ValueError(f"kvcache: block_table must be on k_new's device ({k_new.device}), got {block_table.device}")
+        if block_table.shape[1] * K_cache.shape[2] > 1 << 28:
+            raise ValueError(f"kvcache: the capacity max_blocks * page_size must be <= 2^28, got "
+                             f"{block_table.shape[1]} * {K_cache.shape[2]}")
+    if rotary_cos is not None:
+        d = k_new.shape[3]
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape != rotary_cos.shape or t.shape[0] < 1 \
+                    or not 1 <= t.shape[1] <= d // 2:
+                raise ValueError(f"kvcache: rotary_cos, rotary_sin must be (S_rot, rotary_dim / 2) of one shape with S_rot >= 1 and "
+                                 f"2 <= rotary_dim <= d = {d}, got {name} {tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+            if t.dtype != k_new.dtype:
+                raise ValueError(f"kvcache: {name} must have k_new's dtype ({k_new.dtype}), got {t.dtype}")
+            if t.stride(1) != 1 or t.stride(0) < 0:
+                raise ValueError(f"kvcache: {name} needs unit stride in its last axis, got strides {tuple(t.stride())}")
+            if t.device != k_new.device:
+                raise ValueError(f"kvcache: {name} must be on k_new's device ({k_new.device}), got {t.device}")
+
+
+def kvcache_append(K_cache, V_cache, k_new, v_new, cache_seqlens, *, k_descale=None, v_descale=None, block_table=None,
+                   rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+    """The cache update of a decode step alone (include/fa2_fwd.h fa2_kvcache_append) -> new_seqlens, int32 (B,): what an engine
+    passes as the next step's cache_seqlens.  k_new, v_new (B, H_kv, N_new, d), any strides, go into K_cache / V_cache IN PLACE at
+    key indices clamp(cache_seqlens[b], 0, capacity) + t, K rotated by rotary_cos / rotary_sin at that position (apply_rotary), both
+    quantised with the given descales where the cache is fp8, through block_table where it is paged; tokens past the capacity are
+    dropped and new_seqlens = min(cache_seqlens + N_new, capacity).  cache_seqlens is not modified.  The arguments are
+    flash_attention_kvcache_forward's; a prefill fills a cache with this call.  Two sequences that append into the same row of a
+    shared page leave either one's bytes there: copy on write is the caller's."""
+    if k_new is None or v_new is None:
+        raise ValueError("kvcache: kvcache_append needs k_new and v_new")
+    check_kvcache_append_args(K_cache, V_cache, k_new, v_new, cache_seqlens, k_descale, v_descale, block_table, rotary_cos, rotary_sin)
+    B, H_kv = k_new.shape[:2]
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_kvcache_append(K_cache, V_cache, k_new, v_new, cache_seqlens, new_seqlens, convert_triton_dtype(k_new.dtype),
+                            convert_triton_dtype(K_cache.dtype), block_table=block_table,
+                            k_descale=_kvcache_descale("k_descale", k_descale, k_new, B, H_kv),
+                            v_descale=_kvcache_descale("v_descale", v_descale, k_new, B, H_kv), rotary_cos=rotary_cos,
+                            rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+    return new_seqlens
+
+
 def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale=None, v_descale=None, block_table=None):
     """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, descales, cache_seqlens, block_table,
     window, num_splits).  Pure: takes CPU tensors as well (the CUDA-device check is the launch's)."""
@@ -211,7 +337,8 @@ def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k
 
 
 def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, causal=False, scale=1.0, window=None, num_splits=0,
-                                    variant="auto", k_descale=None, v_descale=None, block_table=None):
+                                    variant="auto", k_descale=None, v_descale=None, block_table=None, k_new=None, v_new=None,
+                                    rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
     """Decode attention over a padded KV cache, split-KV (include/fa2_fwd.h fa2_fwd_kvcache) -> (O, L).  Q (B, H, N_q, d);
     K_cache, V_cache (B, H_kv, S_k, d) of capacity S_k, any strides (a flash-attn (B, S, H_kv, d) cache: pass its
     .transpose(1, 2) view), H_kv dividing H; cache_seqlens int32 (B,) on Q's device, sequence b attends to its first
@@ -233,8 +360,19 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     wrong result for that sequence and never an access outside the pool; entries of pages past a sequence's length, pool pages
     no visible key maps to and the rows of a last page past the length are never read.  On the cache the pool was scattered from
     the result equals the contiguous call's bit for bit.  variant "mfma16" needs page_size % 64 == 0; "auto" takes the generic
-    kernel for other page sizes."""
+    kernel for other page sizes.
+
+    Append (fa2_fwd_kvcache_append): with k_new, v_new (B, H_kv, N_new, d) in Q's dtype, any strides (a flash-attn
+    (B, N_new, H_kv, d) tensor: pass its .transpose(1, 2) view), the call first updates K_cache / V_cache IN PLACE as
+    kvcache_append does -- the new tokens at key indices cache_seqlens[b] + t, quantised with the descales where the cache is fp8,
+    through block_table where it is paged -- and then attends over cache_seqlens + N_new keys (at most the capacity: tokens past it
+    are dropped).  cache_seqlens is required and not modified.  rotary_cos, rotary_sin (S_rot, rotary_dim / 2) in Q's dtype with unit
+    last stride rotate K token t at position cache_seqlens[b] + t and Q (a copy: Q itself is not modified) at cache_seqlens[b] + i for
+    row i when the call is causal or windowed, every row at cache_seqlens[b] otherwise, as flash-attn does; apply_rotary is the
+    arithmetic, bit for bit.  They need k_new / v_new."""
     check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale, v_descale, block_table)
+    check_kvcache_append_args(K_cache, V_cache, k_new, v_new, cache_seqlens, k_descale, v_descale, block_table, rotary_cos, rotary_sin,
+                              Q)
     if variant not in _lib.KVCACHE_VARIANTS:
         raise ValueError(f"kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
     if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
@@ -247,6 +385,19 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
     n = num_splits or _lib.kvcache_num_splits(B, H, H_kv, N_q, S_k, d, dtype)
     ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    if k_new is not None:
+        if k_new.shape[0] != B or k_new.device != Q.device:
+            raise ValueError(f"kvcache: k_new, v_new must have Q's batch size {B} and device ({Q.device}), got {tuple(k_new.shape)} on "
+                             f"{k_new.device}")
+        _lib.fa2_fwd_kvcache_append(Q, K_cache, V_cache, O, L, k_new, v_new, cache_seqlens, torch.empty_like(cache_seqlens), dtype,
+                                    convert_triton_dtype(K_cache.dtype), block_table=block_table,
+                                    k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
+                                    v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), rotary_cos=rotary_cos,
+                                    rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                                    q_rot=None if rotary_cos is None else torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device),
+                                    causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
+                                    variant=_lib.KVCACHE_VARIANTS[variant])
+        return O, L
     if block_table is not None:
         _lib.fa2_fwd_kvcache_paged(Q, K_cache, V_cache, O, L, block_table, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
                                    k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),

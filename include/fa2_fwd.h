@@ -344,6 +344,82 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
                           int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                           void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
+/*
+ * The write side of a decode step: puts N_new new tokens of K and V into the cache, applies rotary embedding, and writes the new
+ * lengths -- one launch (flash-attn's flash_attn_with_kvcache(..., k=, v=, rotary_cos=, rotary_sin=), without the attention).
+ *
+ *   Cache.    K, V with k_strides / v_strides are fa2_fwd_kvcache's cache (B, H_kv, S_k, d) when block_table is null (S_k is then the
+ *             capacity and num_blocks, page_size, max_blocks are ignored), else fa2_fwd_kvcache_paged's pool, table and capacity
+ *             max_blocks * page_size (S_k is then ignored).  They are written in place.  kv_dtype_enum is the cache's element type:
+ *             dtype_enum, or an fp8 format under f16 / bf16 inputs.
+ *   Tokens.   k_new, v_new: (B, H_kv, N_new, d) in dtype_enum, element strides in that order, any strides (a flash-attn
+ *             (B, N_new, H_kv, d) tensor is its transposed view).  With start(b) = clamp(cache_seqlens[b], 0, capacity), token t of
+ *             sequence b becomes key j = start(b) + t, addressed as the decode calls address key j (paged: row j % page_size of page
+ *             block_table[b, j / page_size], the entry clamped to [0, num_blocks - 1], so a wild entry is a write to a wrong page of
+ *             the pool and never one outside it; addresses in 64 bits).  Tokens with j >= capacity are dropped.  A run of tokens may
+ *             straddle pages.  Two sequences that append into the same row of a shared page leave either one's bytes there: copy on
+ *             write is the caller's, nothing detects it.
+ *   Lengths.  cache_seqlens: device int32, B entries, read only.  seqlens_out: device int32, B entries, another buffer:
+ *             seqlens_out[b] = min(start(b) + N_new, capacity) -- the cache_seqlens of the attention that follows and of the next step.
+ *   Rotary.   rotary_cos, rotary_sin: device (S_rot, rotary_dim / 2) in dtype_enum, unit stride in the last axis, row strides
+ *             rotary_cos_stride / rotary_sin_stride; both null: none.  rotary_dim is even, in [2, d]; columns >= rotary_dim pass
+ *             through.  rotary_interleaved = 0 pairs column i with i + rotary_dim / 2 (GPT-NeoX), 1 pairs 2i with 2i + 1 (GPT-J).  K
+ *             token t is rotated at position start(b) + t; V never.  Positions are clamped to S_rot - 1 before a table is read.
+ *             (x1, x2) -> (x1 c - x2 s, x2 c + x1 s) in fp32 (f64 for f64), every product, sum and difference rounded on its own (no
+ *             FMA), then one rounding to nearest even to the cache's dtype.
+ *   Q.        Optional: Q (B, H, N_q, d) with q_strides, rotated into the caller's contiguous q_rot (B, H, N_q, d) in dtype_enum; Q is
+ *             not modified.  Row i is rotated at start(b) + i when q_pos_per_row is non-zero (what a causal or windowed attention
+ *             wants), every row at start(b) otherwise.  Without tables Q and q_rot are not touched.  A null Q (H, N_q, q_strides are
+ *             then ignored) updates the cache alone: what a prefill uses to fill it.
+ *   fp8.      The stored byte is fp8(clamp(x / descale[b, h_kv], +-max)), max = 448 (e4m3fn) / 57344 (e5m2): x the fp32 value (after
+ *             rotary for K, not rounded to 16 bits in between), a correctly rounded fp32 division, conversion to nearest even -- the
+ *             rule of a cache quantised with these descales.  Descales as in fa2_fwd_kvcache_fp8; null means 1.
+ *
+ * FA2_ERR_BAD_ARG before any launch, the message naming the argument: null K / V / k_new / v_new / their strides / cache_seqlens /
+ * seqlens_out; seqlens_out == cache_seqlens; N_new < 1 or > 2^28; B or H_kv outside [1, 65535]; S_k (contiguous) outside [1, 2^28];
+ * with a table num_blocks, page_size or max_blocks < 1, max_blocks * page_size > 2^28, a negative block_table_stride; a negative
+ * stride; descales with kv_dtype_enum == dtype_enum, a descale with null or negative strides; exactly one of rotary_cos / rotary_sin;
+ * rotary_dim odd, < 2 or > d; S_rot < 1; tables and Q with a null q_rot; with Q, null q_strides, H outside [1, 65535], H % H_kv != 0
+ * ("H_kv"), N_q outside [1, 2^28].  FA2_ERR_UNSUPPORTED for a kv_dtype_enum that is neither dtype_enum nor an fp8 format, an fp8 cache
+ * under inputs that are not f16 / bf16, fp8 or unknown dtype_enum, d outside [1, 512].
+ */
+int fa2_kvcache_append(void *K, void *V, const int64_t k_strides[4], const int64_t v_strides[4],
+                       const int32_t *block_table, int64_t block_table_stride,
+                       const void *k_new, const void *v_new, const int64_t k_new_strides[4], const int64_t v_new_strides[4],
+                       const int32_t *cache_seqlens, int32_t *seqlens_out,
+                       const float *k_descale, const float *v_descale,
+                       const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                       const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                       int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                       const void *Q, void *q_rot, const int64_t q_strides[4], int32_t H, int32_t N_q, int32_t q_pos_per_row,
+                       int32_t B, int32_t H_kv, int32_t N_new, int32_t S_k,
+                       int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                       int32_t dtype_enum, int32_t kv_dtype_enum, void *hip_stream);
+
+/*
+ * The fused decode step: fa2_kvcache_append, then on the same stream the decode attention over the updated cache -- the contiguous
+ * (block_table null), fp8 (kv_dtype_enum != dtype_enum) or paged call, whichever the arguments select -- with seqlens_out as its
+ * lengths, N_k(b) = seqlens_out[b], and, when the tables are given, q_rot in Q's place.  q_pos_per_row is
+ * causal || window_left >= 0 || window_right >= 0.  Mask, split rule, num_splits, workspace, variants and empty rows are the existing
+ * calls'; so is the guarantee that rows at or beyond N_k(b) never reach the output.  cache_seqlens is not modified.  q_rot may be
+ * null without tables.  Every error of fa2_kvcache_append and of the selected decode call comes back before any launch.
+ */
+int fa2_fwd_kvcache_append(const void *Q, void *K, void *V, void *O, void *L,
+                           const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                           const int64_t o_strides[4], const int64_t l_strides[2],
+                           const int32_t *cache_seqlens, int32_t *seqlens_out,
+                           const int32_t *block_table, int64_t block_table_stride,
+                           const float *k_descale, const float *v_descale,
+                           const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                           const void *k_new, const void *v_new, const int64_t k_new_strides[4], const int64_t v_new_strides[4],
+                           const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                           int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, void *q_rot,
+                           int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t N_new, int32_t S_k,
+                           int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                           int32_t dtype_enum, int32_t kv_dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                           void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
 /* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
  * elements plus fp32 partial L of num_splits * B * H * N_q. */
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits);
