@@ -246,33 +246,52 @@ def _ulp_io(x, dtype):
     return ulp(x, torch.float16 if dtype == torch.float16 else dtype)
 
 
-def violations(O, L, O_ref, L_ref, dtype):
-    """list of the bars O, L break (empty: pass).  O, L in the I/O dtype, any device; O_ref (…, nq, d), L_ref (…, nq, 1)."""
+def _bars(O, L, O_ref, L_ref, dtype, fp32_ulps=None):
+    """the bars element by element -> (nan, misplaced +inf in L, nonzero O where the truth is 0, |O - O_ref| in bars,
+    |L - L_ref| in bars); the last two are 0 on the empty rows"""
     O, L = O.double().to(O_ref.device), L.double().to(O_ref.device).reshape(L_ref.shape)
-    out = []
     empty = torch.isinf(L_ref)
-    if torch.isnan(O).any() or torch.isnan(L).any():
-        out.append("nan")
-    if not torch.equal(torch.isinf(L) & (L > 0), empty):
-        out.append("L = +inf exactly on the empty rows")
-    zero = (O_ref == 0) | empty
-    if not (O[zero.expand_as(O)] == 0).all():
-        out.append(f"O != 0 where O_ref == 0: {int((O[zero.expand_as(O)] != 0).sum())} elements")
-    fin = ~empty
-    if dtype == torch.float64:
+    nan = torch.isnan(O).any(-1, keepdim=True) | torch.isnan(L)
+    inf = (torch.isinf(L) & (L > 0)) != empty
+    nonzero = ((O_ref == 0) | empty) & (O != 0)
+    if fp32_ulps is not None and dtype in (torch.float32, torch.float64):
+        tolO, tolL = fp32_ulps * ulp(O_ref, torch.float32), fp32_ulps * ulp(L_ref, torch.float32)
+    elif dtype == torch.float64:
         tolO = torch.full_like(O_ref, 1e-6)
         tolL = 1e-6 * L_ref.abs().clamp(min=1)
     elif dtype == torch.float32:
         tolO, tolL = 4 * ulp(O_ref, dtype), 4 * ulp(L_ref, dtype)
     else:
         tolO, tolL = _ulp_io(O_ref, dtype), _ulp_io(L_ref, dtype)
-    eo = ((O - O_ref).abs() / tolO)[fin.expand_as(O)]
+    eo = torch.where(empty, 0.0, (O - O_ref).abs() / tolO)
+    el = torch.where(empty, 0.0, (L - L_ref).abs() / tolL)
+    return nan, inf, nonzero, eo, el
+
+
+def violations(O, L, O_ref, L_ref, dtype, fp32_ulps=None):
+    """list of the bars O, L break (empty: pass).  O, L in the I/O dtype, any device; O_ref (…, nq, d), L_ref (…, nq, 1).
+    fp32_ulps (float32 / float64 I/O only): that many fp32 ulps of the truth instead of the bars above, for a result that went
+    through fp32 partials (oracle/fa2_decode_probe.py); the exact-zero and the empty-row rules stay."""
+    nan, inf, nonzero, eo, el = _bars(O, L, O_ref, L_ref, dtype, fp32_ulps)
+    out = []
+    if nan.any():
+        out.append("nan")
+    if inf.any():
+        out.append("L = +inf exactly on the empty rows")
+    if nonzero.any():
+        out.append(f"O != 0 where O_ref == 0: {int(nonzero.sum())} elements")
     if eo.numel() and eo.max() > 1:
         out.append(f"|O - O_ref| up to {eo.max().item():.3g} bars ({int((eo > 1).sum())} elements)")
-    el = ((L - L_ref).abs() / tolL)[fin]
     if el.numel() and el.max() > 1:
         out.append(f"|L - L_ref| up to {el.max().item():.3g} bars ({int((el > 1).sum())} elements)")
     return out
+
+
+def violated(O, L, O_ref, L_ref, dtype, fp32_ulps=None):
+    """violations() of each slice along the first axis at once -> bool (n,): True where the slice breaks a bar"""
+    n = O_ref.shape[0]
+    return torch.stack([(t > 1 if t.dtype.is_floating_point else t).reshape(n, -1).any(-1)
+                        for t in _bars(O, L, O_ref, L_ref, dtype, fp32_ulps)]).any(0)
 
 
 def heads_first(*ts):
