@@ -53,7 +53,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_window", "fa2_fwd_window_variant", "fa2_fwd_varlen", "fa2_fwd_varlen_variant",
            "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant",
            "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_fwd_kvcache_paged",
-           "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append")
+           "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append",
+           "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -170,6 +171,16 @@ def lib():
         l.fa2_fwd_kvcache_append.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, i64p, i64p, vp, vp,
                                              ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp] + [ctypes.c_int32] * 13 + \
             [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # packed queries over the cache: 3-element Q / O strides, L head stride, cu_seqlens_q, cache_seqlens, table + stride, descales
+        # + strides, B H H_kv total_q max_seqlen_q S_k num_blocks page_size max_blocks d dtype kv_dtype causal, scale, window,
+        # num_splits, workspace + its size, variant, stream
+        l.fa2_fwd_kvcache_varlen.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_varlen.argtypes = [vp] * 5 + [i64p] * 4 + [ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, i64p, i64p] + \
+            [ctypes.c_int32] * 13 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_varlen_workspace_bytes.restype = ctypes.c_int64
+        l.fa2_kvcache_varlen_workspace_bytes.argtypes = [ctypes.c_int32] * 4
+        l.fa2_kvcache_varlen_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_varlen_num_splits.argtypes = [ctypes.c_int32] * 8
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -525,5 +536,46 @@ def fa2_fwd_kvcache_append(Q, K, V, O, L, k_new, v_new, cache_seqlens, seqlens_o
             int(bool(rotary_interleaved)), None if q_rot is None else q_rot.data_ptr(), B, H, K.shape[1], N_q, k_new.shape[2], S_k, nb,
             ps, mb, d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
             int(variant), _raw_stream(Q.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype_enum):
+    """What num_splits = 0 resolves to for a packed-query call of this shape (fa2_kvcache_varlen_num_splits)."""
+    return int(lib().fa2_kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, int(dtype_enum)))
+
+
+def kvcache_varlen_workspace_bytes(total_q, H, d, num_splits):
+    """Bytes of fp32 workspace a packed-query call with this num_splits needs (fa2_kvcache_varlen_workspace_bytes)."""
+    return int(lib().fa2_kvcache_varlen_workspace_bytes(total_q, H, d, num_splits))
+
+
+def fa2_fwd_kvcache_varlen(Q, K, V, O, L, cu_q, max_q, cache_seqlens, dtype_enum, kv_dtype_enum, block_table=None, k_descale=None,
+                           v_descale=None, causal=False, scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch attention of packed queries over the KV cache (include/fa2_fwd.h fa2_fwd_kvcache_varlen) on the current stream of Q's
+    device.  Q, O (total_q, H, d) with any strides, L (H, total_q) with unit token stride, cu_q int32 (B + 1,) on the device; K / V
+    the cache (B, H_kv, S_k, d) or, with block_table, the pool (num_blocks, H_kv, page_size, d); the rest as fa2_fwd_kvcache_paged."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    total_q, H, d = Q.shape
+    if L.dim() != 2 or L.shape != (H, total_q) or (total_q > 1 and L.stride(1) != 1):  # the ABI takes the head stride alone
+        raise ValueError(f"fa2_fwd_kvcache_varlen: L must be (H, total_q) = ({H}, {total_q}) with unit token stride, got "
+                         f"{tuple(L.shape)} with strides {tuple(L.stride())}")
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    ws_ptr = None if workspace is None else workspace.data_ptr()
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
+    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
+    if block_table is None:
+        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, K.shape[2], 0, 0, 0
+    else:
+        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, K.shape[0], K.shape[2], block_table.shape[1]
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_kvcache_varlen(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st,
+            cu_q.numel() - 1, H, K.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum),
+            int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, int(variant), _raw_stream(Q.device.index))
     if rc != 0:
         _raise(rc)

@@ -30,6 +30,11 @@ struct Fa2DecodeProblem {
     float *o_part;       // [num_splits][B * H * N_q][d]   (num_splits > 1 only)
     float *l_part;       // [num_splits][B * H * N_q]
     hipStream_t stream;
+    // variable-length (packed) queries (fa2_fwd_kvcache_varlen): cu_q non-null.  Q, O are (total_q, H, d) with qs / os =
+    // {0, head, token, d}, L is (H, total_q) with ls = {0, head}; sequence b owns n_q(b) = fa2_varlen_seq(cu_q, b, total_q, max_q)
+    // rows from its start on, N_q holds max_q, and the partials are [num_splits][total_q * H] rows, row = token * H + head.
+    const int32_t *cu_q;
+    int32_t total_q, max_q;
 };
 
 // N_k(b) and the key range [k0, k1) of split s (device side of the rule above).
@@ -64,6 +69,19 @@ static inline bool fa2_decode_mfma16_shape(int32_t H, int32_t H_kv, int32_t N_q,
            (int64_t)(H / H_kv) * N_q <= 64;
 }
 int fa2_launch_decode_combine(const Fa2DecodeProblem &p);  // second launch, num_splits > 1 only
+
+// The query-tiled matrix form of the packed call (fa2_decode_mfma16_v.hip): a workgroup owns tq consecutive query positions of one
+// sequence for the g heads of a KV group, R = g tq <= 64 rows.
+// (g in [1, 64]: the callers have checked it, the shape test below included)
+static inline int32_t fa2_decode_varlen_tq(int32_t g, int32_t max_q) { return 64 / g < max_q ? 64 / g : max_q; }
+// H < H_kv (no whole group: g = 0) and H % H_kv != 0 are no problem of this form: a call refuses them, the heuristic counts them
+// as the VALU form's.
+static inline bool fa2_decode_mfma16_v_shape(int32_t H, int32_t H_kv, int32_t d, int32_t dtype) {
+    return (dtype == FA2_DTYPE_F16 || dtype == FA2_DTYPE_BF16) && (d == 64 || d == 128) && H_kv >= 1 && H >= H_kv && H % H_kv == 0 &&
+           H / H_kv <= 64;
+}
+bool fa2_decode_mfma16_v_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mfma16_v(const Fa2DecodeProblem &p);
 
 // One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
 // each tensor's dtype.  It is the kernel's argument as well.

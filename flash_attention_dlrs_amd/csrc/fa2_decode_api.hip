@@ -1,5 +1,5 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8,
-// fa2_fwd_kvcache_paged, the cache append fa2_kvcache_append, the fused step fa2_fwd_kvcache_append and their helpers, declared in
+// fa2_fwd_kvcache_paged, the packed-query call fa2_fwd_kvcache_varlen, the cache append fa2_kvcache_append, the fused step fa2_fwd_kvcache_append and their helpers, declared in
 // include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
 // launches (the append where asked for, the split kernels, then the combine) on the caller's stream.
 #include "fa2_decode.h"
@@ -35,6 +35,37 @@ int64_t workspace_bytes(int64_t B, int64_t H, int64_t N_q, int64_t d, int64_t nu
     return 4 * num_splits * rows * (d + 1);
 }
 
+// fa2_kvcache_varlen_num_splits: the same rule with the unsplit workgroup count of the packed launch in `base`'s place.  A
+// sequence fills ceil(n_q(b) / tq) query tiles, the lengths live on the device: the count is bounded by the grid,
+// B * ceil(max_seqlen_q / tq), and by ceil(total_q / tq) + B (every sequence ends in at most one partly filled tile), per KV
+// head of the matrix form (tq = min(64 / g, max_seqlen_q)), per query head of the VALU form (tq = 16).
+int num_splits_varlen(int64_t B, int64_t H, int64_t H_kv, int64_t total_q, int64_t max_q, int64_t S_k, int32_t d, int32_t dtype) {
+    const bool mfma = fa2_decode_mfma16_v_shape((int32_t)H, (int32_t)H_kv, d, dtype);
+    const int64_t tq = mfma ? fa2_decode_varlen_tq((int32_t)(H / H_kv), (int32_t)max_q) : 16;
+    const int64_t grid = B * ((max_q + tq - 1) / tq), packed = (total_q + tq - 1) / tq + B;
+    const int64_t base = (mfma ? H_kv : H) * (grid < packed ? grid : packed);
+    if (base >= kChipWorkgroups) return 1;
+    int64_t n = (kSplitWaves * kChipWorkgroups + base - 1) / base;
+    const int64_t cap = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE / kMinSplitTiles;
+    if (n > cap) n = cap;
+    if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
+    return n < 1 ? 1 : (int)n;
+}
+
+int64_t workspace_bytes_varlen(int64_t total_q, int64_t H, int64_t d, int64_t num_splits) {
+    if (num_splits <= 1) return 0;
+    if (num_splits > FA2_KVCACHE_MAX_SPLITS) num_splits = FA2_KVCACHE_MAX_SPLITS;
+    const int64_t rows = total_q * H;
+    if (rows > kMaxRows || d > 512) return INT64_MAX;
+    return 4 * num_splits * rows * (d + 1);
+}
+
+// The packed queries of fa2_fwd_kvcache_varlen, checked by it.  Null for the fixed-N_q entry points.
+struct VarlenQ {
+    const int32_t *cu_q;
+    int32_t total_q, max_q;
+};
+
 // The descales of an fp8 cache (fa2_fwd_kvcache_fp8).  Null for the 16-bit entry points, whose cache has Q's dtype.
 struct Fp8Cache {
     int32_t kv_dtype;
@@ -56,7 +87,8 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
                 int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
                 float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
                 void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr, const PagedCache *pg = nullptr,
-                const Fa2AppendProblem *append = nullptr) {
+                const Fa2AppendProblem *append = nullptr, const VarlenQ *vq = nullptr) {
+    // (with `vq`: N_q is max_seqlen_q, the strides are {0, head, token, d} and {0, head}, all checked by the caller)
     const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
     const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
     for (int t = 0; t < 10; ++t)
@@ -95,7 +127,7 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     }
     int rc = fa2_check_gqa(H, H_kv);
     if (rc != FA2_OK) return rc;
-    if (N_q < 1 || N_q > (1 << 28)) {
+    if (!vq && (N_q < 1 || N_q > (1 << 28))) {
         fa2_set_error("kvcache: N_q must be in [1, 2^28] (got %d)", N_q);
         return FA2_ERR_BAD_ARG;
     }
@@ -103,7 +135,7 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
         fa2_set_error("kvcache: S_k must be in [1, 2^28] (got %d)", S_k);
         return FA2_ERR_BAD_ARG;
     }
-    if ((int64_t)B * H * N_q > kMaxRows) {
+    if (!vq && (int64_t)B * H * N_q > kMaxRows) {
         fa2_set_error("kvcache: B * H * N_q must be <= 2^40 (got %lld)", (long long)B * H * N_q);
         return FA2_ERR_BAD_ARG;
     }
@@ -175,18 +207,29 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     p.table_stride = pg ? pg->table_stride : 0;
     p.page_size = pg ? pg->page_size : 0; p.num_blocks = pg ? pg->num_blocks : 0;
     p.dtype = dtype_enum; p.causal = causal != 0; p.wl = wl; p.wr = wr; p.scale = scale;
-    p.num_splits = num_splits == 0 ? num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum) : num_splits;
+    p.cu_q = vq ? vq->cu_q : nullptr;
+    p.total_q = vq ? vq->total_q : 0; p.max_q = vq ? vq->max_q : 0;
+    if (num_splits != 0) p.num_splits = num_splits;
+    else p.num_splits = vq ? num_splits_varlen(B, H, H_kv, vq->total_q, vq->max_q, S_k, d, dtype_enum) : num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum);
     p.stream = (hipStream_t)hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
-        const int64_t need = workspace_bytes(B, H, N_q, d, p.num_splits);
+        const int64_t need = vq ? workspace_bytes_varlen(vq->total_q, H, d, p.num_splits) : workspace_bytes(B, H, N_q, d, p.num_splits);
         if (!workspace || workspace_bytes_given < need) {
-            fa2_set_error("kvcache: workspace of %lld bytes needed for num_splits=%d (fa2_kvcache_workspace_bytes), got %s%lld",
-                          (long long)need, p.num_splits, workspace ? "" : "null, ", (long long)workspace_bytes_given);
+            fa2_set_error("kvcache: workspace of %lld bytes needed for num_splits=%d (%s), got %s%lld", (long long)need, p.num_splits,
+                          vq ? "fa2_kvcache_varlen_workspace_bytes" : "fa2_kvcache_workspace_bytes", workspace ? "" : "null, ",
+                          (long long)workspace_bytes_given);
             return FA2_ERR_BAD_ARG;
         }
         p.o_part = (float *)workspace;
-        p.l_part = p.o_part + (int64_t)p.num_splits * B * H * N_q * d;
+        p.l_part = p.o_part + (int64_t)p.num_splits * (vq ? (int64_t)vq->total_q * H : (int64_t)B * H * N_q) * d;
+    }
+    if (vq) {  // the packed call: its own matrix form (query-tiled), the same VALU form and combine
+        if (variant == FA2_KVCACHE_VARIANT_AUTO)
+            variant = fa2_decode_mfma16_v_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
+        rc = variant == FA2_KVCACHE_VARIANT_MFMA16 ? fa2_launch_decode_mfma16_v(p) : fa2_launch_decode_generic(p);
+        if (rc != FA2_OK || p.num_splits == 1) return rc;
+        return fa2_launch_decode_combine(p);
     }
     if (variant == FA2_KVCACHE_VARIANT_AUTO)
         variant = fa2_decode_mfma16_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
@@ -435,6 +478,66 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
     return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, 0, d,
                        dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
                        variant, wide ? nullptr : &f8, &pg);
+}
+
+int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                           const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[3], int64_t l_head_stride,
+                           const int32_t *cu_seqlens_q, const int32_t *cache_seqlens, const int32_t *block_table,
+                           int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                           const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                           int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                           int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left,
+                           int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
+                           void *hip_stream) {
+    if (!q_strides || !o_strides) {
+        fa2_set_error("kvcache varlen: null %s", !q_strides ? "q_strides" : "o_strides");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (!cu_seqlens_q) {
+        fa2_set_error("kvcache varlen: null cu_seqlens_q");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (total_q < 1) {
+        fa2_set_error("kvcache varlen: total_q must be >= 1 (got %d)", total_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (max_seqlen_q < 1 || max_seqlen_q > (1 << 28)) {
+        fa2_set_error("kvcache varlen: max_seqlen_q must be in [1, 2^28] (got %d)", max_seqlen_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (H >= 1 && (int64_t)total_q * H > kMaxRows) {
+        fa2_set_error("kvcache varlen: total_q * H must be <= 2^40 (got %lld)", (long long)total_q * H);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (l_head_stride < 0) {
+        fa2_set_error("kvcache: negative strides are not supported (l_head_stride)");
+        return FA2_ERR_BAD_ARG;
+    }
+    const bool wide = kv_dtype_enum == dtype_enum;  // the cache has Q's dtype: no descales
+    if (wide && (k_descale || v_descale)) {
+        fa2_set_error("kvcache varlen: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)", kv_dtype_enum);
+        return FA2_ERR_BAD_ARG;
+    }
+    // the packed tensors in the fixed call's terms: no batch stride, the token axis where the query position is
+    const int64_t qs[4] = {0, q_strides[1], q_strides[0], q_strides[2]}, os[4] = {0, o_strides[1], o_strides[0], o_strides[2]};
+    const int64_t ls[2] = {0, l_head_stride};
+    const VarlenQ vq = {cu_seqlens_q, total_q, max_seqlen_q};
+    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
+    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
+    return fwd_kvcache(Q, K, V, O, L, qs, k_strides, v_strides, os, ls, cache_seqlens, B, H, H_kv, max_seqlen_q, S_k, d, dtype_enum, causal,
+                       scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream, variant,
+                       wide ? nullptr : &f8, block_table ? &pg : nullptr, nullptr, &vq);
+}
+
+int64_t fa2_kvcache_varlen_workspace_bytes(int32_t total_q, int32_t H, int32_t d, int32_t num_splits) {
+    if (total_q < 1 || H < 1 || d < 1 || H > 65535) return 0;
+    return workspace_bytes_varlen(total_q, H, d, num_splits);
+}
+
+int32_t fa2_kvcache_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t d,
+                                      int32_t dtype_enum) {
+    if (B < 1 || H < 1 || H_kv < 1 || total_q < 1 || max_seqlen_q < 1 || S_k < 1) return 1;
+    return num_splits_varlen(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype_enum);
 }
 
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {

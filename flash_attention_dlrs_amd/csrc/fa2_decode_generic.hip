@@ -21,6 +21,10 @@
 // [0, num_blocks - 1] before it becomes an address (a wild entry: a wrong result, never an access outside the pool).  For the
 // scores a lane looks up the page of its own key; the P.V loop walks the keys in order and looks the page up once per run of
 // keys inside a page.  Only keys below the split's end are looked up, so entries past a sequence's pages are never loaded.
+//
+// Variable-length queries (fa2_fwd_kvcache_varlen): with cu_q the rows are packed (total_q, H, d), sequence b owns n_q(b) rows
+// from its start on (fa2_varlen_seq) and the grid's query tiles cover max_seqlen_q: a tile at or past n_q(b) leaves at once, the
+// band is the one of n_q(b) and N_k(b), and rows past n_q(b) -- the next sequence's in the packed layout -- are not stored.
 #include <math.h>
 
 #include "fa2_decode.h"
@@ -79,6 +83,8 @@ struct DecodeGenericArgs {
     const int32_t *table;  // paged cache only: entry [b, i] at b * table_stride + i; ks[0], vs[0] are the block strides
     int64_t table_stride;
     int page_size, num_blocks;
+    const int32_t *cu_q;  // packed queries: B + 1 offsets (qs[0] = os[0] = ls[0] = 0), else null
+    int total_q, max_q;
 };
 
 // grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
@@ -93,11 +99,16 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int split = blockIdx.x / a.nqt, i = blockIdx.x - split * a.nqt;
     const int b = blockIdx.y, h = blockIdx.z;
-    const int N = a.N_q, d = a.d;
+    const int d = a.d;
+    int N = a.N_q, start = 0;  // the sequence's query count and its first packed row
+    if (a.cu_q) {
+        fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, start, N);
+        if (i * kBr >= N) return;  // no rows: nothing to write, no partials
+    }
     int NK, k0, k1;
     fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
     const int hk = h / a.gqa;
-    const int64_t q_off = b * a.qs[0] + h * a.qs[1];
+    const int64_t q_off = b * a.qs[0] + h * a.qs[1] + (int64_t)start * a.qs[2];
     const int64_t k_off = (PAGED ? 0 : b * a.ks[0]) + hk * a.ks[1];  // (paged: the page's block term joins per key)
     const int64_t v_off = (PAGED ? 0 : b * a.vs[0]) + hk * a.vs[1];
     const int32_t *tab = PAGED ? a.table + b * a.table_stride : nullptr;  // this sequence's row of the block table
@@ -205,16 +216,16 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
         const A l = wave_sum(lsum[r]);
         if (row >= N) continue;
         if (a.num_splits == 1) {  // a row without a visible key: O = 0, L = +inf
-            const int64_t o_off = b * a.os[0] + h * a.os[1] + (int64_t)row * a.os[2];
+            const int64_t o_off = b * a.os[0] + h * a.os[1] + (int64_t)(start + row) * a.os[2];
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
                 if (x < d) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? (F8 ? o[r][cc] / l * vd : o[r][cc] / l) : (A)0);
             }
-            if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
+            if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + start + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
         } else {  // every (split, row) is written, an empty split as O_s = 0, L_s = -inf: the workspace arrives uninitialised
-            const int64_t rows = (int64_t)gridDim.y * a.H * N;
-            const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + h) * N + row;
+            const int64_t rows = a.cu_q ? (int64_t)a.total_q * a.H : (int64_t)gridDim.y * a.H * N;
+            const int64_t prow = (int64_t)split * rows + (a.cu_q ? (int64_t)(start + row) * a.H + h : ((int64_t)b * a.H + h) * N + row);
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
@@ -272,6 +283,7 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
+    a.cu_q = p.cu_q; a.total_q = p.total_q; a.max_q = p.max_q;  // (N_q = max_q sizes the query tiles)
     if (p.kv_dtype != p.dtype) {  // fp8 cache under 16-bit Q, O, L
         const bool e4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
         if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_F16)

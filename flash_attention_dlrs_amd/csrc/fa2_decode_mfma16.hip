@@ -34,7 +34,20 @@
 // Output.  num_splits == 1: O / l and L = m + log2 l in the I/O dtype, a row without a visible key as O = 0, L = +inf.
 // Otherwise every (split, row) writes the normalised fp32 partial O_s and L_s (an empty split: 0 and -inf) for the combine
 // launch (fa2_decode_combine.hip); vector stores only.
+//
+// Variable-length queries (fa2_fwd_kvcache_varlen).  VQ is a template parameter too, instantiated in fa2_decode_mfma16_v.hip
+// (FA2_DECODE_VARLEN_Q) alone: Q and O are packed (total_q, H, d), sequence b owns n_q(b) rows (fa2_varlen_seq), and a workgroup
+// owns tq = min(64 / g, max_seqlen_q) consecutive query positions [q0, q1) of one sequence for the g heads of the group: row
+// r = head-in-group * tq + (position - q0), R = g tq <= 64.  The grid's x axis is (split, query tile); a tile at or past n_q(b)
+// leaves at once.  The mask is the band of n_q(b) and N_k(b), the row's position counted in the SEQUENCE; the key range of
+// the split is clipped to the band of the tile's own rows [q0, q1), whole 64-key tiles outside it neither loaded nor looked up.
+// Rows at positions >= n_q(b) are computed and dropped: in the packed layout they would be the next sequence's.  With VQ false
+// q0 = 0, q1 = tq = N_q and every expression below is the fixed-N_q kernel's.
 #include "fa2_decode.h"
+
+#ifndef FA2_DECODE_VARLEN_Q
+#define FA2_DECODE_VARLEN_Q 0
+#endif
 
 namespace {
 
@@ -104,6 +117,8 @@ struct DecodeMfmaArgs {
     const int32_t *table;  // paged cache only: entry [b, i] at b * table_stride + i; ks[0], vs[0] are the block strides
     int64_t table_stride;
     int page_size, num_blocks;
+    const int32_t *cu_q;  // VQ only: B + 1 offsets into the packed rows; qs[0] = os[0] = ls[0] = 0
+    int total_q, max_q, tq, nqt;  // nqt = ceil(max_q / tq) query tiles per (split, KV head, sequence)
 };
 
 // Byte offset of 16-byte chunk `ch` of row `row` inside one [rows][D] 16-bit tile (the LDS tile is 16-bit for every cache
@@ -115,8 +130,8 @@ template <int D> __device__ __forceinline__ int lds_off(int row, int ch) {
 }
 
 // RB = 32-row blocks of the query side, KG = key groups (RB * KG = 4 waves), BC = keys per tile (32 or 64).  C: the cache
-// element type, T or CacheE4M3 / CacheE5M2.  PAGED: K and V are a page pool behind a block table.
-template <typename T, typename C, bool PAGED, int D, int RB, int KG, int BC>
+// element type, T or CacheE4M3 / CacheE5M2.  PAGED: K and V are a page pool behind a block table.  VQ: packed queries, tiled.
+template <typename T, typename C, bool PAGED, bool VQ, int D, int RB, int KG, int BC>
 __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(const DecodeMfmaArgs a) {
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -136,17 +151,28 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rb = wave % RB, grp = wave / RB;
     const int i = lane & 31, h = lane >> 5;
-    const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-    const int N_q = a.N_q, R = a.g * N_q;
+    const int hk = blockIdx.y, b = blockIdx.z;
+    // N_q: the query count of the mask; TQ: query positions of the tile, [q0, q1) the ones it owns, from packed row `start` on
+    int split = blockIdx.x, N_q = a.N_q, TQ = a.N_q, q0 = 0, start = 0;
+    if constexpr (VQ) {
+        split = blockIdx.x / a.nqt;
+        fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, start, N_q);
+        TQ = a.tq;
+        q0 = (blockIdx.x - split * a.nqt) * TQ;
+        if (q0 >= N_q) return;  // no rows: nothing to write, no partials
+    }
+    const int q1 = VQ ? (q0 + TQ < N_q ? q0 + TQ : N_q) : N_q;
+    const int R = a.g * TQ;
 
     int NK, k0, k1;
     fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
     int wl, wr;
     fa2_varlen_band(N_q, NK, a.causal, a.wl, a.wr, wl, wr);
-    // the keys of the split that the band of any row touches: [kb0, ke), kb0 on a 64-key boundary (windowed calls skip the rest)
-    const int lo_min = -wl > k0 ? (-wl & ~63) : k0;  // (k0 is a multiple of 64)
+    // the keys of the split that the band of any row of the tile touches: [kb0, ke), kb0 on a 64-key boundary (the rest is skipped)
+    const int lo_t = q0 - wl;                              // the first key the tile's first row sees
+    const int lo_min = lo_t > k0 ? (lo_t & ~63) : k0;  // (k0 is a multiple of 64)
     const int kb0 = lo_min > k0 ? lo_min : k0;
-    const int hi_end = N_q + wr;  // one past the last key the last row sees
+    const int hi_end = q1 + wr;  // one past the last key the last row sees
     const int ke = hi_end < k1 ? hi_end : k1;
     const int nt = ke > kb0 ? (ke - kb0 + BC - 1) / BC : 0;
     const int nstep = (nt + KG - 1) / KG;
@@ -154,13 +180,19 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     // ---- this lane's row: (head of the group, query position); padding rows repeat the last row and are not stored
     const int row = rb * 32 + i;
     const int rowc = row < R ? row : R - 1;
-    const int hg = rowc / N_q, qi = rowc - hg * N_q;
+    const int hg = rowc / TQ;
+    int qi = q0 + rowc - hg * TQ;  // position in the sequence
+    bool keep = row < R;
+    if constexpr (VQ) {  // positions past the sequence's last: the last row again, dropped
+        keep = keep && qi < N_q;
+        qi = qi < N_q ? qi : N_q - 1;
+    }
     const int head = hk * a.g + hg;
 
     // ---- Q fragments: B operand of S^T = K Q^T.  Lane (i, h) holds Q[row][16ks + 8h .. +7].
     frag qf[KS];
     {
-        const char *qp = a.Q + b * a.qs[0] + head * a.qs[1] + (int64_t)qi * a.qs[2] + h * 16;
+        const char *qp = a.Q + b * a.qs[0] + head * a.qs[1] + (int64_t)(start + qi) * a.qs[2] + h * 16;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(frag, *(const u32x4 *)(qp + ks * 32));
     }
@@ -268,7 +300,7 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     }
     // this row's visible keys [lo, hi], and whether a tile can meet a band edge of any row
     const int lo = qi - wl, hi = (qi + wr) < (ke - 1) ? (qi + wr) : (ke - 1);
-    const int lo_max = N_q - 1 - wl, hi_min = wr < (ke - 1) ? wr : (ke - 1);
+    const int lo_max = q1 - 1 - wl, hi_min = (q0 + wr) < (ke - 1) ? (q0 + wr) : (ke - 1);
 
     if (nstep > 0) {
         stage_load(0);
@@ -394,9 +426,9 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     const bool seen = l > 0.0f;
     float inv = seen ? 1.0f / l : 0.0f;
     if constexpr (F8) inv = seen ? inv * vd : 0.0f;  // O = vd (P V8) / l, in fp32
-    if (row >= R) return;
+    if (!keep) return;
     if (a.num_splits == 1) {
-        char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)qi * a.os[2] + h * 8;
+        char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)(start + qi) * a.os[2] + h * 8;
 #pragma unroll
         for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -408,12 +440,12 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
                 *(u32x2 *)(op + db * 64 + g * 16) = __builtin_bit_cast(u32x2, v);
             }
         if (h == 0) {
-            T *lp = (T *)a.L + b * a.ls[0] + head * a.ls[1] + qi;
+            T *lp = (T *)a.L + b * a.ls[0] + head * a.ls[1] + start + qi;
             *lp = seen ? (T)(m + __builtin_amdgcn_logf(l)) : (T)INFINITY;
         }
     } else {
-        const int64_t rows = (int64_t)gridDim.z * a.H * N_q;
-        const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + head) * N_q + qi;
+        const int64_t rows = VQ ? (int64_t)a.total_q * a.H : (int64_t)gridDim.z * a.H * N_q;
+        const int64_t prow = (int64_t)split * rows + (VQ ? (int64_t)(start + qi) * a.H + head : ((int64_t)b * a.H + head) * N_q + qi);
         float *op = a.o_part + prow * D + h * 4;
 #pragma unroll
         for (int db = 0; db < DB; ++db)
@@ -428,11 +460,18 @@ __global__ __launch_bounds__(RB * KG * 64, 2) void fa2_decode_mfma16_kernel(cons
     }
 }
 
+constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0;
+
 template <typename T, typename C, bool PAGED, int D, int RB, int KG, int BC> int launch_t(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
-    const dim3 grid(p.num_splits, p.H_kv, p.B), block(RB * KG * 64);
+    const long long gx = kVQ ? (long long)p.num_splits * a.nqt : p.num_splits;
+    if (gx > 0x7fffffffLL) {
+        fa2_set_error("kvcache mfma16 kernel: grid too large (num_splits * query tiles = %lld)", gx);
+        return FA2_ERR_BAD_ARG;
+    }
+    const dim3 grid((unsigned)gx, p.H_kv, p.B), block(RB * KG * 64);
     constexpr size_t smem = (size_t)KG * 2 * BC * D * 2;
     static_assert(smem <= 64 * 1024, "two workgroups per CU");
-    hipLaunchKernelGGL((fa2_decode_mfma16_kernel<T, C, PAGED, D, RB, KG, BC>), grid, block, smem, p.stream, a);
+    hipLaunchKernelGGL((fa2_decode_mfma16_kernel<T, C, PAGED, kVQ, D, RB, KG, BC>), grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mfma16 kernel launch failed: %s", hipGetErrorString(e));
@@ -442,7 +481,7 @@ template <typename T, typename C, bool PAGED, int D, int RB, int KG, int BC> int
 }
 
 template <typename T, typename C, bool PAGED> int launch_d(const Fa2DecodeProblem &p, const DecodeMfmaArgs &a) {
-    const bool one = (int64_t)a.g * p.N_q <= 32;  // one 32-row block: four key groups
+    const bool one = (int64_t)a.g * (kVQ ? a.tq : p.N_q) <= 32;  // one 32-row block: four key groups
     if (p.d == 128) return one ? launch_t<T, C, PAGED, 128, 1, 4, 32>(p, a) : launch_t<T, C, PAGED, 128, 2, 2, 64>(p, a);
     return one ? launch_t<T, C, PAGED, 64, 1, 4, 64>(p, a) : launch_t<T, C, PAGED, 64, 2, 2, 64>(p, a);
 }
@@ -461,14 +500,13 @@ bool fp8_cache(const Fa2DecodeProblem &p) { return p.kv_dtype == FA2_DTYPE_F8E4M
 
 bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
-}  // namespace
-
-bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p) {
+// (packed queries: the tile holds 64 / g positions, so only g itself is bounded)
+bool supports(const Fa2DecodeProblem &p) {
     if (p.dtype != FA2_DTYPE_F16 && p.dtype != FA2_DTYPE_BF16) return false;
     if (p.kv_dtype != p.dtype && !fp8_cache(p)) return false;
     if (p.d != 64 && p.d != 128) return false;
     if (!(p.scale > 0.0f) || !(p.scale < INFINITY)) return false;
-    if ((int64_t)(p.H / p.H_kv) * p.N_q > 64) return false;
+    if ((int64_t)(p.H / p.H_kv) * (kVQ ? 1 : p.N_q) > 64) return false;
     if (p.qs[3] != 1 || p.ks[3] != 1 || p.vs[3] != 1 || p.os[3] != 1) return false;
     // 16-byte vector loads of Q/K/V rows, 8-byte stores of O: every row start must stay aligned (an fp8 cache: 16 elements).
     const int64_t kmask = fp8_cache(p) ? 15 : 7;
@@ -481,10 +519,10 @@ bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p) {
     return true;
 }
 
-int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) {
-    if (!fa2_decode_mfma16_supports(p)) {
-        fa2_set_error("kvcache mfma16 kernel: needs f16/bf16 (the cache alike, or fp8), d in {64,128}, g * N_q <= 64, unit d-stride, "
-                      "16-byte aligned rows (and workspace), scale > 0%s",
+int launch(const Fa2DecodeProblem &p) {
+    if (!supports(p)) {
+        fa2_set_error("kvcache mfma16 kernel: needs f16/bf16 (the cache alike, or fp8), d in {64,128}, %s <= 64, unit d-stride, "
+                      "16-byte aligned rows (and workspace), scale > 0%s", kVQ ? "g = H / H_kv" : "g * N_q",
                       p.table ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
         return FA2_ERR_UNSUPPORTED;
     }
@@ -504,5 +542,18 @@ int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) {
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
+    a.cu_q = p.cu_q; a.total_q = p.total_q; a.max_q = p.max_q;
+    a.tq = kVQ ? fa2_decode_varlen_tq(a.g, p.max_q) : p.N_q;
+    a.nqt = kVQ ? (p.max_q + a.tq - 1) / a.tq : 1;
     return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }
+
+}  // namespace
+
+#if FA2_DECODE_VARLEN_Q
+bool fa2_decode_mfma16_v_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mfma16_v(const Fa2DecodeProblem &p) { return launch(p); }
+#else
+bool fa2_decode_mfma16_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mfma16(const Fa2DecodeProblem &p) { return launch(p); }
+#endif

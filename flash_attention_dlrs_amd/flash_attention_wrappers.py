@@ -413,3 +413,63 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     _lib.fa2_fwd_kvcache(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, causal=causal, scale=scale, window=window, num_splits=n,
                          workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
     return O, L
+
+
+def check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale=None,
+                              v_descale=None, block_table=None):
+    """ValueError for what flash_attention_varlen_kvcache_forward cannot take (the packed Q and cu_seqlens_q, max_seqlen_q, and
+    every rule of check_kvcache_args for the cache, its lengths, table, descales, window and num_splits).  Pure: takes CPU tensors
+    as well."""
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] < 1:
+        raise ValueError(f"varlen kvcache: Q must be packed (total_q, H, d) with total_q >= 1, got "
+                         f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 \
+            or not cu_seqlens_q.is_contiguous() or cu_seqlens_q.numel() < 2:
+        raise ValueError("varlen kvcache: cu_seqlens_q must be a contiguous int32 tensor of B + 1 >= 2 entries")
+    if cu_seqlens_q.device != Q.device:
+        raise ValueError(f"varlen kvcache: cu_seqlens_q must be on Q's device ({Q.device}), got {cu_seqlens_q.device}")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or not 1 <= max_seqlen_q <= 1 << 28:
+        raise ValueError(f"varlen kvcache: max_seqlen_q must be an int in [1, 2^28], got {max_seqlen_q!r}")
+    if Q.shape[0] * Q.shape[1] > 1 << 40:
+        raise ValueError(f"varlen kvcache: total_q * H must be <= 2^40, got {Q.shape[0]} * {Q.shape[1]}")
+    B = cu_seqlens_q.numel() - 1
+    # the cache's rules are the fixed-N_q call's: seen through a (B, H, 1, d) view of Q (no data is read)
+    check_kvcache_args(Q[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1, -1), K_cache, V_cache, cache_seqlens, window, num_splits,
+                       k_descale, v_descale, block_table)
+
+
+def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, causal=False,
+                                           scale=1.0, window=None, num_splits=0, variant="auto", k_descale=None, v_descale=None,
+                                           block_table=None):
+    """Attention of variable-length (packed) queries over the KV cache (include/fa2_fwd.h fa2_fwd_kvcache_varlen) -> (O, L): what a
+    chunked prefill, a mixed prefill / decode batch or the verification of draft tokens needs (flash-attn's
+    flash_attn_varlen_func(..., block_table=)).  Q (total_q, H, d), any strides; cu_seqlens_q int32 (B + 1,) on Q's device:
+    sequence b owns min(cu[b + 1] - cu[b], max_seqlen_q) rows from cu[b] on, none is legal.  K_cache, V_cache, cache_seqlens,
+    k_descale, v_descale and block_table are flash_attention_kvcache_forward's: the contiguous (B, H_kv, S_k, d) cache or a page
+    pool behind a block table, in Q's dtype or fp8.  The keys of the chunk's own tokens are already in the cache (kvcache_append puts
+    them there), so query i of sequence b stands at position cache_seqlens[b] - n_q(b) + i: causal and window are bottom-right
+    aligned per sequence.  O (total_q, H, d) contiguous, L (H, total_q) log2-domain, both in Q's dtype; rows without a visible key
+    get O = 0, L = +inf; rows outside every sequence are not written (they hold what torch.empty left).  num_splits = 0 lets the
+    library choose; variant is one of _lib.KVCACHE_VARIANTS ("mfma16": f16 / bf16, d 64 / 128, H / H_kv <= 64).  With every sequence
+    at n_q = max_seqlen_q = N_q and (H / H_kv) * N_q <= 64 the result equals flash_attention_kvcache_forward's at the same explicit
+    num_splits bit for bit.  No autograd, no autotuner."""
+    check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale, v_descale,
+                              block_table)
+    if variant not in _lib.KVCACHE_VARIANTS:
+        raise ValueError(f"varlen kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
+    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
+        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+    total_q, H, d = Q.shape
+    B, H_kv = cu_seqlens_q.numel() - 1, K_cache.shape[1]
+    dtype = convert_triton_dtype(Q.dtype)
+    O = torch.empty(total_q, H, d, dtype=Q.dtype, device=Q.device)
+    L = torch.empty(H, total_q, dtype=Q.dtype, device=Q.device)
+    S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
+    n = num_splits or _lib.kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype)
+    ws = torch.empty(_lib.kvcache_varlen_workspace_bytes(total_q, H, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    _lib.fa2_fwd_kvcache_varlen(Q, K_cache, V_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
+                                convert_triton_dtype(K_cache.dtype), block_table=block_table,
+                                k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
+                                v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), causal=causal, scale=scale,
+                                window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
+    return O, L

@@ -345,6 +345,62 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
                           void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
 /*
+ * Variable-length (packed) queries over the KV cache: every sequence brings its own number of query tokens -- a chunk of a prompt
+ * over its cached prefix (chunked prefill, prefix caching), the draft tokens of speculative decoding, one decode token -- in one
+ * call (flash-attn's flash_attn_varlen_func(..., block_table=)).  Forward only.  The keys of a chunk's own tokens are already in
+ * the cache: the caller has appended them (fa2_kvcache_append).
+ *
+ *   Queries.  Q, O are packed (total_q, H, d), strides {token, head, dim} in elements (3 each); L is (H, total_q) in the I/O dtype,
+ *             unit stride over tokens, head stride l_head_stride: fa2_fwd_varlen's layout.  cu_seqlens_q: device int32, B + 1
+ *             entries; sequence b owns the n_q(b) = clamp(cu[b + 1] - cu[b], 0, max_seqlen_q) rows from clamp(cu[b], 0, total_q)
+ *             on, every value read clamped to [0, total_q] as in fa2_fwd_varlen.  n_q(b) = 0 is legal.  Rows outside every
+ *             sequence -- gaps between sequences, the rows of a sequence past max_seqlen_q -- are neither read nor written.
+ *   Cache.    fa2_fwd_kvcache_paged's: with block_table the pool (num_blocks, H_kv, page_size, d) and its table, S_k ignored, the
+ *             capacity max_blocks * page_size; with a null block_table the contiguous cache (B, H_kv, S_k, d) of capacity S_k,
+ *             num_blocks / page_size / max_blocks ignored.  kv_dtype_enum == dtype_enum with null descales is the cache in Q's
+ *             dtype, an fp8 kv_dtype_enum the fp8 cache of fa2_fwd_kvcache_fp8.  N_k(b) = clamp(cache_seqlens[b], 0, capacity), a
+ *             null cache_seqlens the capacity.  Rows at or beyond N_k(b), pool pages no visible key maps to and table entries past
+ *             a sequence's pages are never read; table entries are clamped into the pool before an address is formed.
+ *   Mask.     fa2_fwd_varlen's band of n_q(b) queries and N_k(b) keys, bottom-right aligned per sequence: query i of sequence b
+ *             stands at position N_k(b) - n_q(b) + i.  A row without a visible key (N_k(b) < n_q(b) under causal, N_k(b) = 0, a
+ *             window) gets O = 0 and L = +inf.
+ *   Splits.   fa2_fwd_kvcache's rule on each sequence's own length, every (query tile, KV head, sequence) split alike;
+ *             num_splits = 0 picks fa2_kvcache_varlen_num_splits(...).  Workspace: fa2_kvcache_varlen_workspace_bytes(...) bytes,
+ *             16-byte aligned, uninitialised is fine; untouched (and may be null) when num_splits resolves to 1.
+ *   Variants. FA2_KVCACHE_VARIANT_MFMA16: f16 / bf16, d in {64, 128}, g = H / H_kv <= 64, unit d-stride, 16-byte aligned rows,
+ *             scale > 0, page_size % 64 == 0 when paged.  A workgroup owns tq = min(64 / g, max_seqlen_q) consecutive query
+ *             positions of one sequence for the g heads of a KV group, so K and V are read once per (KV head, query tile).  With
+ *             every n_q(b) = max_seqlen_q = N_q and g * N_q <= 64 the tile is fa2_fwd_kvcache's and, at the same explicit
+ *             num_splits, O and L equal that call's bit for bit.  FA2_KVCACHE_VARIANT_GENERIC: everything else, 16 query rows per
+ *             workgroup on the VALU.  AUTO: MFMA16 where it runs.  A forced MFMA16 it cannot run returns FA2_ERR_UNSUPPORTED.
+ *
+ * Every error of fa2_fwd_kvcache_paged applies (S_k in the capacity's place for a contiguous cache, max_seqlen_q in N_q's).
+ * FA2_ERR_BAD_ARG also for a null cu_seqlens_q, total_q < 1, max_seqlen_q < 1 or > 2^28, total_q * H > 2^40, a negative
+ * l_head_stride; the message names the argument.
+ */
+int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L,
+                           const int64_t q_strides[3], const int64_t k_strides[4], const int64_t v_strides[4],
+                           const int64_t o_strides[3], int64_t l_head_stride,
+                           const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                           const int32_t *block_table, int64_t block_table_stride,
+                           const float *k_descale, const float *v_descale,
+                           const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                           int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                           int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                           int32_t dtype_enum, int32_t kv_dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                           void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* Bytes of workspace such a call needs: 0 for num_splits <= 1, else fp32 partial O [num_splits][total_q * H][d] followed by fp32
+ * partial L [num_splits][total_q * H]. */
+int64_t fa2_kvcache_varlen_workspace_bytes(int32_t total_q, int32_t H, int32_t d, int32_t num_splits);
+
+/* What num_splits = 0 resolves to for it: fa2_kvcache_num_splits' rule with the unsplit workgroup count of the packed launch,
+ * H_kv * min(B * ceil(max_seqlen_q / tq), ceil(total_q / tq) + B) for the matrix form (H and tq = 16 for the VALU form). */
+int32_t fa2_kvcache_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                      int32_t d, int32_t dtype_enum);
+
+/*
  * The write side of a decode step: puts N_new new tokens of K and V into the cache, applies rotary embedding, and writes the new
  * lengths -- one launch (flash-attn's flash_attn_with_kvcache(..., k=, v=, rotary_cos=, rotary_sin=), without the attention).
  *
