@@ -10,9 +10,10 @@ from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttent
 from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_attention_backward, flash_attention_forward,
                                        flash_attention_kvcache_forward, flash_attention_varlen_backward,
                                        flash_attention_varlen_forward, flash_attention_varlen_kvcache_forward, kvcache_append,
-                                       quantize_kv_cache)
+                                       kvcache_append_varlen, quantize_kv_cache)
 
 __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
            "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
            "flash_attention_varlen_backward", "flash_attention_kvcache_forward", "quantize_kv_cache", "dequantize_kv_cache",
-           "varlen_mask", "gqa_kv_heads", "kvcache_append", "apply_rotary", "flash_attention_varlen_kvcache_forward"]
+           "varlen_mask", "gqa_kv_heads", "kvcache_append", "apply_rotary", "flash_attention_varlen_kvcache_forward",
+           "kvcache_append_varlen"]

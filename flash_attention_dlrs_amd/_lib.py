@@ -54,7 +54,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_gqa", "fa2_fwd_gqa_variant", "fa2_fwd_varlen_gqa", "fa2_fwd_varlen_gqa_variant",
            "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_fwd_kvcache_paged",
            "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append",
-           "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits")
+           "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits",
+           "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -177,6 +178,18 @@ def lib():
         l.fa2_fwd_kvcache_varlen.restype = ctypes.c_int
         l.fa2_fwd_kvcache_varlen.argtypes = [vp] * 5 + [i64p] * 4 + [ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, i64p, i64p] + \
             [ctypes.c_int32] * 13 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # the packed append: fa2_kvcache_append's order with 3-element k_new / v_new / Q strides, cu_seqlens_new before cache_seqlens,
+        # no N_q, and total_new max_seqlen_new in N_new's place
+        l.fa2_kvcache_append_varlen.restype = ctypes.c_int
+        l.fa2_kvcache_append_varlen.argtypes = [vp, vp, i64p, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, vp, vp, i64p, i64p, vp,
+                                                vp, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp, vp, i64p] + \
+            [ctypes.c_int32] * 13 + [vp]
+        # ... fused with the packed-query attention: fa2_fwd_kvcache_varlen's order with seqlens_out after cache_seqlens and, after the
+        # descales, k_new v_new + strides, rotary tables + row strides, S_rot rotary_dim interleaved, q_rot
+        l.fa2_fwd_kvcache_varlen_append.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_varlen_append.argtypes = [vp] * 5 + [i64p] * 4 + [ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, vp, vp, i64p, i64p,
+                                                    vp, vp, i64p, i64p, vp, vp, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + \
+            [vp] + [ctypes.c_int32] * 13 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_varlen_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_varlen_workspace_bytes.argtypes = [ctypes.c_int32] * 4
         l.fa2_kvcache_varlen_num_splits.restype = ctypes.c_int32
@@ -577,5 +590,61 @@ def fa2_fwd_kvcache_varlen(Q, K, V, O, L, cu_q, max_q, cache_seqlens, dtype_enum
             cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st,
             cu_q.numel() - 1, H, K.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum),
             int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, int(variant), _raw_stream(Q.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_kvcache_append_varlen(K, V, k_new, v_new, cu_new, max_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,
+                              k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, Q=None,
+                              q_rot=None, q_pos_per_row=False):
+    """Launch the packed cache append (include/fa2_fwd.h fa2_kvcache_append_varlen) on the current stream of k_new's device: k_new /
+    v_new packed (total_new, H_kv, d), any strides, over cu_new, an int32 (B + 1,) tensor on the device, go into the cache K / V
+    (B, H_kv, S_k, d), or the pool with block_table, in place; seqlens_out, an int32 (B,) tensor that is not cache_seqlens, receives
+    the new lengths.  Q packed (total_new, H, d) with rotary tables is rotated into the contiguous q_rot.  The rest as
+    fa2_kvcache_append."""
+    if k_new.device.type != "cuda":
+        raise NotImplementedError("K_cache, V_cache, k_new, v_new must be on the same CUDA device")
+    total_new, H_kv, d = k_new.shape
+    tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
+    q_ptr, q_st, H = (None, None, 0) if Q is None else (Q.data_ptr(), _i64(Q.stride()), Q.shape[1])
+    with torch.cuda.device(k_new.device):
+        rc = lib().fa2_kvcache_append_varlen(
+            K.data_ptr(), V.data_ptr(), _i64(K.stride()), _i64(V.stride()), tb_ptr, tb_st, k_new.data_ptr(), v_new.data_ptr(),
+            _i64(k_new.stride()), _i64(v_new.stride()), cu_new.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), kd_ptr,
+            vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), q_ptr,
+            None if q_rot is None else q_rot.data_ptr(), q_st, H, int(bool(q_pos_per_row)), cu_new.numel() - 1, H_kv, total_new,
+            int(max_new), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum), _raw_stream(k_new.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_fwd_kvcache_varlen_append(Q, K, V, O, L, k_new, v_new, cu_q, max_q, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum,
+                                  block_table=None, k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
+                                  rotary_interleaved=False, q_rot=None, causal=False, scale=1.0, window=None, num_splits=0,
+                                  workspace=None, variant=0):
+    """Launch the fused ragged step (include/fa2_fwd.h fa2_fwd_kvcache_varlen_append) on the current stream of Q's device: the packed
+    append above with cu_q as its offsets (k_new, v_new (total_q, H_kv, d)), then fa2_fwd_kvcache_varlen over the updated cache with
+    seqlens_out as its lengths and, with rotary tables, q_rot (a contiguous (total_q, H, d) tensor in Q's dtype) as its Q."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    total_q, H, d = Q.shape
+    if L.dim() != 2 or L.shape != (H, total_q) or (total_q > 1 and L.stride(1) != 1):  # the ABI takes the head stride alone
+        raise ValueError(f"fa2_fwd_kvcache_varlen_append: L must be (H, total_q) = ({H}, {total_q}) with unit token stride, got "
+                         f"{tuple(L.shape)} with strides {tuple(L.stride())}")
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    ws_ptr = None if workspace is None else workspace.data_ptr()
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_kvcache_varlen_append(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st,
+            k_new.data_ptr(), v_new.data_ptr(), _i64(k_new.stride()), _i64(v_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd,
+            int(bool(rotary_interleaved)), None if q_rot is None else q_rot.data_ptr(), cu_q.numel() - 1, H, K.shape[1], total_q,
+            int(max_q), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr,
+            int(num_splits), ws_ptr, ws_bytes, int(variant), _raw_stream(Q.device.index))
     if rc != 0:
         _raise(rc)

@@ -108,5 +108,13 @@ struct Fa2AppendProblem {
     int32_t B, H_kv, N_new, d;
     int32_t dtype, kv_dtype;
     hipStream_t stream;
+    // packed (ragged) tokens (fa2_kvcache_append_varlen): cu_new non-null.  k_new, v_new are (total_new, H_kv, d) and Q, q_rot
+    // (total_new, H, d), all over cu_new, with kns / vns / qs = {0, head, token, d}; sequence b brings the n_new(b) rows
+    // fa2_varlen_seq(cu_new, b, total_new, max_new) gives it, row i of them becomes key clamp(seqlens[b], 0, capacity) + i, and
+    // seqlens_out[b] = min(clamp(seqlens[b], 0, capacity) + n_new(b), capacity).  N_new and N_q are not read.  Offsets that are not
+    // non-decreasing may put wrong rows into the cache; every address formed is still inside the tensors: a packed row t is
+    // < total_new, its sequence b is in [0, B), its key index is < capacity, pages and positions are clamped as always.
+    const int32_t *cu_new;
+    int32_t total_new, max_new;
 };
 int fa2_launch_decode_append(const Fa2AppendProblem &p);

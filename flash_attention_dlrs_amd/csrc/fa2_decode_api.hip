@@ -1,5 +1,6 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8,
-// fa2_fwd_kvcache_paged, the packed-query call fa2_fwd_kvcache_varlen, the cache append fa2_kvcache_append, the fused step fa2_fwd_kvcache_append and their helpers, declared in
+// fa2_fwd_kvcache_paged, the packed-query call fa2_fwd_kvcache_varlen, the cache appends fa2_kvcache_append and fa2_kvcache_append_varlen,
+// the fused steps fa2_fwd_kvcache_append and fa2_fwd_kvcache_varlen_append, and their helpers, declared in
 // include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
 // launches (the append where asked for, the split kernels, then the combine) on the caller's stream.
 #include "fa2_decode.h"
@@ -227,6 +228,11 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     if (vq) {  // the packed call: its own matrix form (query-tiled), the same VALU form and combine
         if (variant == FA2_KVCACHE_VARIANT_AUTO)
             variant = fa2_decode_mfma16_v_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
+        if (append) {  // the fused ragged step: as below
+            if (variant == FA2_KVCACHE_VARIANT_MFMA16 && !fa2_decode_mfma16_v_supports(p)) return fa2_launch_decode_mfma16_v(p);
+            rc = fa2_launch_decode_append(*append);
+            if (rc != FA2_OK) return rc;
+        }
         rc = variant == FA2_KVCACHE_VARIANT_MFMA16 ? fa2_launch_decode_mfma16_v(p) : fa2_launch_decode_generic(p);
         if (rc != FA2_OK || p.num_splits == 1) return rc;
         return fa2_launch_decode_combine(p);
@@ -264,9 +270,21 @@ struct AppendCall {
     int32_t H, N_q, q_pos_per_row;
     int32_t B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum;
     void *hip_stream;
+    // fa2_kvcache_append_varlen: packed tokens over cu_seqlens_new, the strides of k_new, v_new and Q already in the fixed call's
+    // order {0, head, token, d} (packed4); N_new and N_q are then not looked at
+    bool packed = false;
+    const int32_t *cu_seqlens_new = nullptr;
+    int32_t total_new = 0, max_seqlen_new = 0;
 };
 
-// Every check of fa2_kvcache_append, before any launch; on FA2_OK `p` is the problem to launch.
+// The {token, head, d} strides of a packed tensor in the fixed call's order {batch, head, token, d}, the batch stride 0; null stays null.
+const int64_t *packed4(const int64_t *s3, int64_t (&s4)[4]) {
+    if (!s3) return nullptr;
+    s4[0] = 0; s4[1] = s3[1]; s4[2] = s3[0]; s4[3] = s3[2];
+    return s4;
+}
+
+// Every check of fa2_kvcache_append and fa2_kvcache_append_varlen, before any launch; on FA2_OK `p` is the problem to launch.
 int check_append(const AppendCall &c, Fa2AppendProblem &p) {
     const void *ptrs[10] = {c.K, c.V, c.k_strides, c.v_strides, c.k_new, c.v_new, c.k_new_strides, c.v_new_strides, c.cache_seqlens,
                             c.seqlens_out};
@@ -309,7 +327,20 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
         fa2_set_error("kvcache append: H_kv must be in [1, 65535] (got %d)", c.H_kv);
         return FA2_ERR_BAD_ARG;
     }
-    if (c.N_new < 1 || c.N_new > (1 << 28)) {
+    if (c.packed) {
+        if (!c.cu_seqlens_new) {
+            fa2_set_error("kvcache append varlen: null cu_seqlens_new");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.total_new < 1 || c.total_new > (1 << 28)) {
+            fa2_set_error("kvcache append varlen: total_new must be in [1, 2^28] (got %d)", c.total_new);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.max_seqlen_new < 1 || c.max_seqlen_new > (1 << 28)) {
+            fa2_set_error("kvcache append varlen: max_seqlen_new must be in [1, 2^28] (got %d)", c.max_seqlen_new);
+            return FA2_ERR_BAD_ARG;
+        }
+    } else if (c.N_new < 1 || c.N_new > (1 << 28)) {
         fa2_set_error("kvcache append: N_new must be in [1, 2^28] (got %d)", c.N_new);
         return FA2_ERR_BAD_ARG;
     }
@@ -324,8 +355,15 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
         }
         const int rc = fa2_check_gqa(c.H, c.H_kv);
         if (rc != FA2_OK) return rc;
-        if (c.N_q < 1 || c.N_q > (1 << 28)) {
+        if (!c.packed && (c.N_q < 1 || c.N_q > (1 << 28))) {
             fa2_set_error("kvcache append: N_q must be in [1, 2^28] (got %d)", c.N_q);
+            return FA2_ERR_BAD_ARG;
+        }
+    }
+    if (c.packed) {  // the rows one packed launch walks, held to the bound of B * H * N_q: a row's byte offset stays below 2^52
+        const int64_t slabs = c.Q && c.H > 2 * c.H_kv ? c.H : 2 * c.H_kv;
+        if (c.total_new * slabs > kMaxRows) {
+            fa2_set_error("kvcache append varlen: total_new * max(H, 2 * H_kv) must be <= 2^40 (got %lld)", (long long)(c.total_new * slabs));
             return FA2_ERR_BAD_ARG;
         }
     }
@@ -419,7 +457,59 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
     p.B = c.B; p.H_kv = c.H_kv; p.N_new = c.N_new; p.d = c.d;
     p.dtype = c.dtype_enum; p.kv_dtype = c.kv_dtype_enum;
     p.stream = (hipStream_t)c.hip_stream;
+    p.cu_new = c.packed ? c.cu_seqlens_new : nullptr;
+    p.total_new = c.packed ? c.total_new : 0; p.max_new = c.packed ? c.max_seqlen_new : 0;
     return FA2_OK;
+}
+
+// fa2_fwd_kvcache_varlen; with `append` (packed, checked by check_append) that launch goes first.
+int fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                       const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[3], int64_t l_head_stride,
+                       const int32_t *cu_seqlens_q, const int32_t *cache_seqlens, const int32_t *block_table,
+                       int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                       const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                       int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                       int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left,
+                       int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
+                       void *hip_stream, const Fa2AppendProblem *append = nullptr) {
+    if (!q_strides || !o_strides) {
+        fa2_set_error("kvcache varlen: null %s", !q_strides ? "q_strides" : "o_strides");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (!cu_seqlens_q) {
+        fa2_set_error("kvcache varlen: null cu_seqlens_q");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (total_q < 1) {
+        fa2_set_error("kvcache varlen: total_q must be >= 1 (got %d)", total_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (max_seqlen_q < 1 || max_seqlen_q > (1 << 28)) {
+        fa2_set_error("kvcache varlen: max_seqlen_q must be in [1, 2^28] (got %d)", max_seqlen_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (H >= 1 && (int64_t)total_q * H > kMaxRows) {
+        fa2_set_error("kvcache varlen: total_q * H must be <= 2^40 (got %lld)", (long long)total_q * H);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (l_head_stride < 0) {
+        fa2_set_error("kvcache: negative strides are not supported (l_head_stride)");
+        return FA2_ERR_BAD_ARG;
+    }
+    const bool wide = kv_dtype_enum == dtype_enum;  // the cache has Q's dtype: no descales
+    if (wide && (k_descale || v_descale)) {
+        fa2_set_error("kvcache varlen: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)", kv_dtype_enum);
+        return FA2_ERR_BAD_ARG;
+    }
+    // the packed tensors in the fixed call's terms: no batch stride, the token axis where the query position is
+    const int64_t qs[4] = {0, q_strides[1], q_strides[0], q_strides[2]}, os[4] = {0, o_strides[1], o_strides[0], o_strides[2]};
+    const int64_t ls[2] = {0, l_head_stride};
+    const VarlenQ vq = {cu_seqlens_q, total_q, max_seqlen_q};
+    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
+    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
+    return fwd_kvcache(Q, K, V, O, L, qs, k_strides, v_strides, os, ls, cache_seqlens, B, H, H_kv, max_seqlen_q, S_k, d, dtype_enum, causal,
+                       scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream, variant,
+                       wide ? nullptr : &f8, block_table ? &pg : nullptr, append, &vq);
 }
 
 }  // namespace
@@ -489,44 +579,10 @@ int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O,
                            int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left,
                            int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
                            void *hip_stream) {
-    if (!q_strides || !o_strides) {
-        fa2_set_error("kvcache varlen: null %s", !q_strides ? "q_strides" : "o_strides");
-        return FA2_ERR_BAD_ARG;
-    }
-    if (!cu_seqlens_q) {
-        fa2_set_error("kvcache varlen: null cu_seqlens_q");
-        return FA2_ERR_BAD_ARG;
-    }
-    if (total_q < 1) {
-        fa2_set_error("kvcache varlen: total_q must be >= 1 (got %d)", total_q);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (max_seqlen_q < 1 || max_seqlen_q > (1 << 28)) {
-        fa2_set_error("kvcache varlen: max_seqlen_q must be in [1, 2^28] (got %d)", max_seqlen_q);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (H >= 1 && (int64_t)total_q * H > kMaxRows) {
-        fa2_set_error("kvcache varlen: total_q * H must be <= 2^40 (got %lld)", (long long)total_q * H);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (l_head_stride < 0) {
-        fa2_set_error("kvcache: negative strides are not supported (l_head_stride)");
-        return FA2_ERR_BAD_ARG;
-    }
-    const bool wide = kv_dtype_enum == dtype_enum;  // the cache has Q's dtype: no descales
-    if (wide && (k_descale || v_descale)) {
-        fa2_set_error("kvcache varlen: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)", kv_dtype_enum);
-        return FA2_ERR_BAD_ARG;
-    }
-    // the packed tensors in the fixed call's terms: no batch stride, the token axis where the query position is
-    const int64_t qs[4] = {0, q_strides[1], q_strides[0], q_strides[2]}, os[4] = {0, o_strides[1], o_strides[0], o_strides[2]};
-    const int64_t ls[2] = {0, l_head_stride};
-    const VarlenQ vq = {cu_seqlens_q, total_q, max_seqlen_q};
-    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
-    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
-    return fwd_kvcache(Q, K, V, O, L, qs, k_strides, v_strides, os, ls, cache_seqlens, B, H, H_kv, max_seqlen_q, S_k, d, dtype_enum, causal,
-                       scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream, variant,
-                       wide ? nullptr : &f8, block_table ? &pg : nullptr, nullptr, &vq);
+    return fwd_kvcache_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cache_seqlens,
+                              block_table, block_table_stride, k_descale, v_descale, k_descale_strides, v_descale_strides, B, H, H_kv,
+                              total_q, max_seqlen_q, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, causal, scale,
+                              window_left, window_right, num_splits, workspace, workspace_bytes, variant, hip_stream);
 }
 
 int64_t fa2_kvcache_varlen_workspace_bytes(int32_t total_q, int32_t H, int32_t d, int32_t num_splits) {
@@ -596,6 +652,61 @@ int fa2_fwd_kvcache_append(const void *Q, void *K, void *V, void *O, void *L, co
                        seqlens_out, B, H, H_kv, N_q, S_k, d, dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
                        workspace_bytes, hip_stream, variant, kv_dtype_enum == dtype_enum ? nullptr : &f8, block_table ? &pg : nullptr,
                        &p);
+}
+
+int fa2_kvcache_append_varlen(void *K, void *V, const int64_t k_strides[4], const int64_t v_strides[4], const int32_t *block_table,
+                              int64_t block_table_stride, const void *k_new, const void *v_new, const int64_t k_new_strides[3],
+                              const int64_t v_new_strides[3], const int32_t *cu_seqlens_new, const int32_t *cache_seqlens,
+                              int32_t *seqlens_out, const float *k_descale, const float *v_descale, const int64_t k_descale_strides[2],
+                              const int64_t v_descale_strides[2], const void *rotary_cos, const void *rotary_sin,
+                              int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim,
+                              int32_t rotary_interleaved, const void *Q, void *q_rot, const int64_t q_strides[3], int32_t H,
+                              int32_t q_pos_per_row, int32_t B, int32_t H_kv, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                              int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t dtype_enum,
+                              int32_t kv_dtype_enum, void *hip_stream) {
+    int64_t kns[4], vns[4], qs[4];
+    AppendCall c = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, packed4(k_new_strides, kns),
+                    packed4(v_new_strides, vns), cache_seqlens, seqlens_out, k_descale, v_descale, k_descale_strides, v_descale_strides,
+                    rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot,
+                    packed4(q_strides, qs), H, 0, q_pos_per_row, B, H_kv, 0, S_k, num_blocks, page_size, max_blocks, d, dtype_enum,
+                    kv_dtype_enum, hip_stream};
+    c.packed = true; c.cu_seqlens_new = cu_seqlens_new; c.total_new = total_new; c.max_seqlen_new = max_seqlen_new;
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    return rc != FA2_OK ? rc : fa2_launch_decode_append(p);
+}
+
+int fa2_fwd_kvcache_varlen_append(const void *Q, void *K, void *V, void *O, void *L, const int64_t q_strides[3],
+                                  const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[3],
+                                  int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                                  const int32_t *block_table, int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                                  const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], const void *k_new,
+                                  const void *v_new, const int64_t k_new_strides[3], const int64_t v_new_strides[3],
+                                  const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                                  int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, void *q_rot, int32_t B, int32_t H,
+                                  int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                                  int32_t max_blocks, int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale,
+                                  int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
+                                  int32_t variant, void *hip_stream) {
+    const int32_t per_row = causal || window_left >= 0 || window_right >= 0;  // the fixed fused call's rule
+    int64_t kns[4], vns[4], qs[4];
+    AppendCall c = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, packed4(k_new_strides, kns),
+                    packed4(v_new_strides, vns), cache_seqlens, seqlens_out, k_descale, v_descale, k_descale_strides, v_descale_strides,
+                    rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot,
+                    packed4(q_strides, qs), H, 0, per_row, B, H_kv, 0, S_k, num_blocks, page_size, max_blocks, d, dtype_enum,
+                    kv_dtype_enum, hip_stream};
+    c.packed = true; c.cu_seqlens_new = cu_seqlens_q; c.total_new = total_q; c.max_seqlen_new = max_seqlen_q;
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    if (rc != FA2_OK) return rc;
+    // the attention reads the rotated Q (packed, contiguous) and the new lengths
+    const int64_t rot_strides[3] = {(int64_t)H * d, d, 1};
+    const bool rotated = p.Q != nullptr;
+    return fwd_kvcache_varlen(rotated ? q_rot : Q, K, V, O, L, rotated ? rot_strides : q_strides, k_strides, v_strides, o_strides,
+                              l_head_stride, cu_seqlens_q, seqlens_out, block_table, block_table_stride, k_descale, v_descale,
+                              k_descale_strides, v_descale_strides, B, H, H_kv, total_q, max_seqlen_q, S_k, num_blocks, page_size,
+                              max_blocks, d, dtype_enum, kv_dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
+                              workspace_bytes, variant, hip_stream, &p);
 }
 
 }  // extern "C"

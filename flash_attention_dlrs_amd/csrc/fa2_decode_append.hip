@@ -1,12 +1,13 @@
-// fa2_decode_append.hip -- the write side of a decode step (fa2_kvcache_append, include/fa2_fwd.h): one launch that puts the new
-// tokens' K and V into the cache (contiguous or paged, 16-bit / f32 / f64 or fp8), applies rotary embedding to K and to Q, and
-// writes the new lengths.  The decode kernels that follow read seqlens_out as their cache_seqlens and q_rot as their Q, so they
-// need no new parameter.
+// fa2_decode_append.hip -- the write side of a decode step (fa2_kvcache_append, fa2_kvcache_append_varlen, include/fa2_fwd.h): one
+// launch that puts the new tokens' K and V into the cache (contiguous or paged, 16-bit / f32 / f64 or fp8), applies rotary embedding
+// to K and to Q, and writes the new lengths.  The decode kernels that follow read seqlens_out as their cache_seqlens and q_rot as
+// their Q, so they need no new parameter.
 //
-// Work layout.  blockIdx.z is the sequence, blockIdx.y walks the row slabs of that sequence (H_kv slabs of K, H_kv of V, H of Q when
-// Q is rotated), blockIdx.x the tokens: a block is blockDim.y tokens of blockDim.x lanes, lane x owning the units x, x + blockDim.x,
-// ... of its row.  A unit is 8 columns (vector path: 16-byte loads, 16- or 8-byte stores) or one column (element path).  No index is
-// ever divided: the host picks blockDim.x as the power of two that covers a row (at most 64).
+// Work layout (the fixed form; the packed form of fa2_kvcache_append_varlen is described at the kernel).  blockIdx.z is the
+// sequence, blockIdx.y walks the row slabs of that sequence (H_kv slabs of K, H_kv of V, H of Q when Q is rotated), blockIdx.x the
+// tokens: a block is blockDim.y tokens of blockDim.x lanes, lane x owning the units x, x + blockDim.x, ... of its row.  A unit is
+// 8 columns (vector path: 16-byte loads, 16- or 8-byte stores) or one column (element path).  No index is ever divided: the host
+// picks blockDim.x as the power of two that covers a row (at most 64).
 //
 // Arithmetic (pinned: flash_attention_wrappers.apply_rotary restates it in torch and the tests compare bits).  Inputs are widened to
 // fp32 (f64 stays f64); o1 = x1 c - x2 s and o2 = x2 c + x1 s with each product and the sum or difference rounded separately -- the
@@ -159,18 +160,55 @@ template <class E, int OUT, bool VEC> __device__ __forceinline__ void do_row(con
     }
 }
 
-template <class E, int KV, bool VEC> __global__ __launch_bounds__(256) void fa2_decode_append_kernel(const Fa2AppendProblem a) {
+// PK: the packed (ragged) form, fa2_kvcache_append_varlen.  The fixed form's blockIdx.z and its B x N_new token tiles give way to a
+// flat layout over the packed rows, so a long chunk beside many one-token decodes launches no empty tiles: blockIdx.x * blockDim.y +
+// threadIdx.y is a packed row, which finds its sequence by a binary search over cu_new (once, at most 16 steps: B <= 65535) and
+// then checks with fa2_varlen_seq that the sequence owns it -- rows in no sequence do nothing.  Everything after that is the
+// fixed form's: the same Row, the same do_row, so the same bytes.
+template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) void fa2_decode_append_kernel(const Fa2AppendProblem a) {
     constexpr int64_t esz = sizeof(typename E::bits_t);
     constexpr int64_t csz = KV == 0 ? esz : 1;  // bytes of a cache element
-    const int b = blockIdx.z;
     const int cap = a.capacity;
-    int start = a.seqlens[b];
-    start = start < 0 ? 0 : (start > cap ? cap : start);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
-        const int n = start + a.N_new;  // <= 2^29
-        a.seqlens_out[b] = n < cap ? n : cap;
+    int b, start;
+    int64_t t;  // this lane's token of sequence b (K, V) or its query row (Q)
+    [[maybe_unused]] int64_t row = 0;  // PK: the packed row that token is
+    if constexpr (PK) {
+        if (blockIdx.y == 0) {  // the new lengths: one thread per sequence, sequences without tokens included
+            const int64_t flat = (((int64_t)blockIdx.x * blockDim.y + threadIdx.y) * blockDim.x) + threadIdx.x;
+            if (flat < a.B) {
+                int s, n, st = a.seqlens[flat];
+                fa2_varlen_seq(a.cu_new, (int)flat, a.total_new, a.max_new, s, n);
+                st = st < 0 ? 0 : (st > cap ? cap : st);
+                a.seqlens_out[flat] = st + n < cap ? st + n : cap;  // st + n <= 2^29
+            }
+        }
+        row = (int64_t)blockIdx.x * blockDim.y + threadIdx.y;
+        if (row >= a.total_new) return;
+        int lo = 0, hi = a.B;  // the last sequence in [0, B) whose clamped offset is <= row (sequence 0 when none is)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            int c = a.cu_new[mid];
+            c = c < 0 ? 0 : (c > a.total_new ? a.total_new : c);
+            if (c <= row) lo = mid;
+            else hi = mid;
+        }
+        b = lo;
+        int s, n;
+        fa2_varlen_seq(a.cu_new, b, a.total_new, a.max_new, s, n);
+        if (row < s || row >= (int64_t)s + n) return;  // a gap, the surplus of a span past max_new, a row behind the last offset
+        t = row - s;  // < n <= max_new <= 2^28
+        start = a.seqlens[b];
+        start = start < 0 ? 0 : (start > cap ? cap : start);
+    } else {
+        b = blockIdx.z;
+        start = a.seqlens[b];
+        start = start < 0 ? 0 : (start > cap ? cap : start);
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
+            const int n = start + a.N_new;  // <= 2^29
+            a.seqlens_out[b] = n < cap ? n : cap;
+        }
+        t = (int64_t)blockIdx.x * blockDim.y + threadIdx.y;
     }
-    const int64_t t = (int64_t)blockIdx.x * blockDim.y + threadIdx.y;  // this lane's token (K, V) or query row (Q)
     const int units = VEC ? a.d >> 3 : a.d;
     const bool rotary = a.cos != nullptr;
     const int nslab = 2 * a.H_kv + (a.Q && rotary ? a.H : 0);
@@ -179,7 +217,9 @@ template <class E, int KV, bool VEC> __global__ __launch_bounds__(256) void fa2_
         if (slab < 2 * a.H_kv) {  // a row of K (with rotary) or V (without)
             const bool is_k = slab < a.H_kv;
             const int hk = is_k ? slab : slab - a.H_kv;
-            if (t >= a.N_new || start + t >= cap) continue;  // past the capacity: dropped
+            if constexpr (!PK)
+                if (t >= a.N_new) continue;
+            if (start + t >= cap) continue;  // past the capacity: dropped
             const int j = start + (int)t;  // the key index this token gets, < capacity <= 2^28
             const int64_t *ns = is_k ? a.kns : a.vns, *cs = is_k ? a.ks : a.vs;
             int64_t off;
@@ -189,7 +229,8 @@ template <class E, int KV, bool VEC> __global__ __launch_bounds__(256) void fa2_
             } else {
                 off = (int64_t)b * cs[0] + (int64_t)hk * cs[1] + (int64_t)j * cs[2];
             }
-            r.src = (const char *)(is_k ? a.k_new : a.v_new) + ((int64_t)b * ns[0] + (int64_t)hk * ns[1] + t * ns[2]) * esz;
+            if constexpr (PK) r.src = (const char *)(is_k ? a.k_new : a.v_new) + ((int64_t)hk * ns[1] + row * ns[2]) * esz;
+            else r.src = (const char *)(is_k ? a.k_new : a.v_new) + ((int64_t)b * ns[0] + (int64_t)hk * ns[1] + t * ns[2]) * esz;
             r.dst = (char *)(is_k ? a.K : a.V) + off * csz;
             r.ss = ns[3];
             r.ds = cs[3];
@@ -203,13 +244,19 @@ template <class E, int KV, bool VEC> __global__ __launch_bounds__(256) void fa2_
             if constexpr (KV != 0)
                 r.descale = is_k ? fa2_decode_descale(a.kd, a.kds[0], a.kds[1], b, hk) : fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
             do_row<E, KV, VEC>(r, units, a.rotary_dim, a.interleaved);
-        } else {  // a row of Q, rotated into q_rot (B, H, N_q, d) contiguous, in Q's dtype
+        } else {  // a row of Q, rotated into q_rot, contiguous in Q's dtype: (B, H, N_q, d), or (total_new, H, d) when packed
             const int h = slab - 2 * a.H_kv;
-            if (t >= a.N_q) continue;
+            if constexpr (!PK)
+                if (t >= a.N_q) continue;
             int64_t pos = start + (a.q_pos_per_row ? t : 0);
             pos = pos < a.S_rot ? pos : a.S_rot - 1;
-            r.src = (const char *)a.Q + ((int64_t)b * a.qs[0] + (int64_t)h * a.qs[1] + t * a.qs[2]) * esz;
-            r.dst = (char *)a.q_rot + ((((int64_t)b * a.H + h) * a.N_q + t) * a.d) * esz;
+            if constexpr (PK) {
+                r.src = (const char *)a.Q + ((int64_t)h * a.qs[1] + row * a.qs[2]) * esz;
+                r.dst = (char *)a.q_rot + ((row * a.H + h) * a.d) * esz;
+            } else {
+                r.src = (const char *)a.Q + ((int64_t)b * a.qs[0] + (int64_t)h * a.qs[1] + t * a.qs[2]) * esz;
+                r.dst = (char *)a.q_rot + ((((int64_t)b * a.H + h) * a.N_q + t) * a.d) * esz;
+            }
             r.ss = a.qs[3];
             r.ds = 1;
             r.cos = (const char *)a.cos + pos * a.cos_stride * esz;
@@ -243,12 +290,18 @@ template <class E, int KV, bool VEC> int launch(const Fa2AppendProblem &p) {
     int tx = 1;
     while (tx < units && tx < 64) tx *= 2;
     const bool with_q = p.Q && p.cos;
-    const int64_t ntok = with_q && p.N_q > p.N_new ? p.N_q : p.N_new;
+    const int64_t ntok = p.cu_new ? p.total_new : (with_q && p.N_q > p.N_new ? p.N_q : p.N_new);
     int ty = 1;
     while (ty < ntok && tx * ty < 256) ty *= 2;
     const int64_t nslab = 2 * (int64_t)p.H_kv + (with_q ? p.H : 0);
-    const dim3 grid((unsigned)((ntok + ty - 1) / ty), (unsigned)(nslab < 65535 ? nslab : 65535), (unsigned)p.B);
-    hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC>), grid, dim3(tx, ty), 0, p.stream, p);
+    if (p.cu_new) {  // flat over the packed rows; the first B threads of the blockIdx.y == 0 blocks write the lengths
+        const int64_t rows = (ntok + ty - 1) / ty, lens = ((int64_t)p.B + tx * ty - 1) / (tx * ty);
+        const dim3 grid((unsigned)(rows > lens ? rows : lens), (unsigned)(nslab < 65535 ? nslab : 65535));
+        hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC, true>), grid, dim3(tx, ty), 0, p.stream, p);
+    } else {
+        const dim3 grid((unsigned)((ntok + ty - 1) / ty), (unsigned)(nslab < 65535 ? nslab : 65535), (unsigned)p.B);
+        hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC, false>), grid, dim3(tx, ty), 0, p.stream, p);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache append kernel launch failed: %s", hipGetErrorString(e));

@@ -284,6 +284,65 @@ def kvcache_append(K_cache, V_cache, k_new, v_new, cache_seqlens, *, k_descale=N
     return new_seqlens
 
 
+def check_kvcache_append_varlen_args(K_cache, V_cache, k_new, v_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, k_descale=None,
+                                     v_descale=None, block_table=None, rotary_cos=None, rotary_sin=None, Q=None):
+    """ValueError for what kvcache_append_varlen (and the append keywords of flash_attention_varlen_kvcache_forward) cannot take: the
+    packed k_new / v_new, cu_seqlens_new and max_seqlen_new, and every rule of check_kvcache_append_args for the cache, its lengths,
+    descales, table and rotary tables.  Q, packed (total_new, H, d), only where it is rotated along.  Pure: takes CPU tensors as
+    well."""
+    if (k_new is None) != (v_new is None):
+        raise ValueError("varlen kvcache: k_new and v_new go together")
+    if k_new is None:
+        check_kvcache_append_args(K_cache, V_cache, None, None, cache_seqlens, rotary_cos=rotary_cos, rotary_sin=rotary_sin)
+        return
+    if not isinstance(k_new, torch.Tensor) or not isinstance(v_new, torch.Tensor) or k_new.dim() != 3 or k_new.shape != v_new.shape \
+            or not 1 <= k_new.shape[0] <= 1 << 28:
+        raise ValueError(f"varlen kvcache: k_new, v_new must be packed (total_new, H_kv, d) of one shape with total_new in [1, 2^28], got "
+                         f"{tuple(k_new.shape) if isinstance(k_new, torch.Tensor) else type(k_new).__name__}, "
+                         f"{tuple(v_new.shape) if isinstance(v_new, torch.Tensor) else type(v_new).__name__}")
+    if not isinstance(cu_seqlens_new, torch.Tensor) or cu_seqlens_new.dtype != torch.int32 or cu_seqlens_new.dim() != 1 \
+            or not cu_seqlens_new.is_contiguous() or cu_seqlens_new.numel() < 2:
+        raise ValueError("varlen kvcache: cu_seqlens_new must be a contiguous int32 tensor of B + 1 >= 2 entries")
+    if cu_seqlens_new.device != k_new.device:
+        raise ValueError(f"varlen kvcache: cu_seqlens_new must be on k_new's device ({k_new.device}), got {cu_seqlens_new.device}")
+    if isinstance(max_seqlen_new, bool) or not isinstance(max_seqlen_new, int) or not 1 <= max_seqlen_new <= 1 << 28:
+        raise ValueError(f"varlen kvcache: max_seqlen_new must be an int in [1, 2^28], got {max_seqlen_new!r}")
+    if Q is not None and (not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] != k_new.shape[0] or Q.shape[2] != k_new.shape[2]):
+        raise ValueError(f"varlen kvcache: Q must be packed (total_new, H, d) with k_new's total_new and d, got "
+                         f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__} beside k_new {tuple(k_new.shape)}")
+    slabs = max(2 * k_new.shape[1], 0 if Q is None else Q.shape[1])
+    if k_new.shape[0] * slabs > 1 << 40:
+        raise ValueError(f"varlen kvcache: total_new * max(H, 2 * H_kv) must be <= 2^40, got {k_new.shape[0]} * {slabs}")
+    B = cu_seqlens_new.numel() - 1
+    # the rest is the fixed call's: the tokens seen through (B, H_kv, 1, d) views (no data is read)
+    as_fixed = lambda t: t[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1, -1)
+    check_kvcache_append_args(K_cache, V_cache, as_fixed(k_new), as_fixed(v_new), cache_seqlens, k_descale, v_descale, block_table,
+                              rotary_cos, rotary_sin, Q)
+
+
+def kvcache_append_varlen(K_cache, V_cache, k_new, v_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, *, k_descale=None,
+                          v_descale=None, block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+    """kvcache_append for a ragged batch in one launch (include/fa2_fwd.h fa2_kvcache_append_varlen) -> new_seqlens, int32 (B,).
+    k_new, v_new packed (total_new, H_kv, d), any strides; cu_seqlens_new int32 (B + 1,) on their device: sequence b brings the
+    min(cu[b + 1] - cu[b], max_seqlen_new) rows from cu[b] on, none is legal, and row cu[b] + t becomes key
+    clamp(cache_seqlens[b], 0, capacity) + t of sequence b, exactly as kvcache_append stores token t -- rotary, fp8 descales, block
+    table and the drop of tokens past the capacity included.  new_seqlens[b] = min(cache_seqlens[b] + n_new(b), capacity), for
+    sequences without tokens too.  Rows outside every sequence are not read; cache_seqlens is not modified.  What a mixed step of
+    chunked prefill and decodes hands over as one tensor goes in as it is."""
+    if k_new is None or v_new is None:
+        raise ValueError("varlen kvcache: kvcache_append_varlen needs k_new and v_new")
+    check_kvcache_append_varlen_args(K_cache, V_cache, k_new, v_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, k_descale, v_descale,
+                                     block_table, rotary_cos, rotary_sin)
+    B, H_kv = cu_seqlens_new.numel() - 1, k_new.shape[1]
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_kvcache_append_varlen(K_cache, V_cache, k_new, v_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, new_seqlens,
+                                   convert_triton_dtype(k_new.dtype), convert_triton_dtype(K_cache.dtype), block_table=block_table,
+                                   k_descale=_kvcache_descale("k_descale", k_descale, k_new, B, H_kv),
+                                   v_descale=_kvcache_descale("v_descale", v_descale, k_new, B, H_kv), rotary_cos=rotary_cos,
+                                   rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+    return new_seqlens
+
+
 def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale=None, v_descale=None, block_table=None):
     """ValueError for what flash_attention_kvcache_forward cannot take (shapes, dtypes, descales, cache_seqlens, block_table,
     window, num_splits).  Pure: takes CPU tensors as well (the CUDA-device check is the launch's)."""
@@ -416,10 +475,10 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
 
 
 def check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale=None,
-                              v_descale=None, block_table=None):
+                              v_descale=None, block_table=None, k_new=None, v_new=None, rotary_cos=None, rotary_sin=None):
     """ValueError for what flash_attention_varlen_kvcache_forward cannot take (the packed Q and cu_seqlens_q, max_seqlen_q, and
-    every rule of check_kvcache_args for the cache, its lengths, table, descales, window and num_splits).  Pure: takes CPU tensors
-    as well."""
+    every rule of check_kvcache_args for the cache, its lengths, table, descales, window and num_splits; with the append keywords,
+    every rule of check_kvcache_append_varlen_args).  Pure: takes CPU tensors as well."""
     if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] < 1:
         raise ValueError(f"varlen kvcache: Q must be packed (total_q, H, d) with total_q >= 1, got "
                          f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
@@ -436,11 +495,17 @@ def check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, c
     # the cache's rules are the fixed-N_q call's: seen through a (B, H, 1, d) view of Q (no data is read)
     check_kvcache_args(Q[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1, -1), K_cache, V_cache, cache_seqlens, window, num_splits,
                        k_descale, v_descale, block_table)
+    if k_new is not None or v_new is not None or rotary_cos is not None or rotary_sin is not None:
+        check_kvcache_append_varlen_args(K_cache, V_cache, k_new, v_new, cu_seqlens_q, max_seqlen_q, cache_seqlens, k_descale, v_descale,
+                                         block_table, rotary_cos, rotary_sin, Q)
+        if k_new.device != Q.device:
+            raise ValueError(f"varlen kvcache: k_new, v_new must be on Q's device ({Q.device}), got {k_new.device}")
 
 
 def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, causal=False,
                                            scale=1.0, window=None, num_splits=0, variant="auto", k_descale=None, v_descale=None,
-                                           block_table=None):
+                                           block_table=None, k_new=None, v_new=None, rotary_cos=None, rotary_sin=None,
+                                           rotary_interleaved=False):
     """Attention of variable-length (packed) queries over the KV cache (include/fa2_fwd.h fa2_fwd_kvcache_varlen) -> (O, L): what a
     chunked prefill, a mixed prefill / decode batch or the verification of draft tokens needs (flash-attn's
     flash_attn_varlen_func(..., block_table=)).  Q (total_q, H, d), any strides; cu_seqlens_q int32 (B + 1,) on Q's device:
@@ -452,9 +517,17 @@ def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, ma
     get O = 0, L = +inf; rows outside every sequence are not written (they hold what torch.empty left).  num_splits = 0 lets the
     library choose; variant is one of _lib.KVCACHE_VARIANTS ("mfma16": f16 / bf16, d 64 / 128, H / H_kv <= 64).  With every sequence
     at n_q = max_seqlen_q = N_q and (H / H_kv) * N_q <= 64 the result equals flash_attention_kvcache_forward's at the same explicit
-    num_splits bit for bit.  No autograd, no autotuner."""
+    num_splits bit for bit.  No autograd, no autotuner.
+
+    Append (fa2_fwd_kvcache_varlen_append): with k_new, v_new packed (total_q, H_kv, d) in Q's dtype on Q's device, any strides --
+    token i of Q, k_new and v_new is the same token -- the call first updates K_cache / V_cache IN PLACE as kvcache_append_varlen
+    does over cu_seqlens_q, and then attends over cache_seqlens + n_q(b) keys (at most the capacity).  cache_seqlens is required,
+    holds the lengths BEFORE the append and is not modified.  rotary_cos, rotary_sin (S_rot, rotary_dim / 2) rotate K token t at
+    position cache_seqlens[b] + t and Q (a copy) row i at cache_seqlens[b] + i when the call is causal or windowed, every row at
+    cache_seqlens[b] otherwise: flash_attention_kvcache_forward's rule, which a uniform batch reproduces bit for bit.  They need
+    k_new / v_new."""
     check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale, v_descale,
-                              block_table)
+                              block_table, k_new, v_new, rotary_cos, rotary_sin)
     if variant not in _lib.KVCACHE_VARIANTS:
         raise ValueError(f"varlen kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
     if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
@@ -467,6 +540,16 @@ def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, ma
     S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
     n = num_splits or _lib.kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype)
     ws = torch.empty(_lib.kvcache_varlen_workspace_bytes(total_q, H, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    if k_new is not None:
+        _lib.fa2_fwd_kvcache_varlen_append(Q, K_cache, V_cache, O, L, k_new, v_new, cu_seqlens_q, max_seqlen_q, cache_seqlens,
+                                           torch.empty_like(cache_seqlens), dtype, convert_triton_dtype(K_cache.dtype),
+                                           block_table=block_table, k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
+                                           v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), rotary_cos=rotary_cos,
+                                           rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                                           q_rot=None if rotary_cos is None else torch.empty(total_q, H, d, dtype=Q.dtype, device=Q.device),
+                                           causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
+                                           variant=_lib.KVCACHE_VARIANTS[variant])
+        return O, L
     _lib.fa2_fwd_kvcache_varlen(Q, K_cache, V_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
                                 convert_triton_dtype(K_cache.dtype), block_table=block_table,
                                 k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),

@@ -476,6 +476,70 @@ int fa2_fwd_kvcache_append(const void *Q, void *K, void *V, void *O, void *L,
                            int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                            void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
+/*
+ * The packed (ragged) form of fa2_kvcache_append: every sequence brings its own number of new tokens -- a chunk of a prompt beside
+ * one-token decodes -- in one launch.  Cache, lengths, rotary arithmetic, fp8 rule, paging and every guarantee are fa2_kvcache_append's;
+ * what differs:
+ *
+ *   Tokens.   k_new, v_new: packed (total_new, H_kv, d) in dtype_enum, strides {token, head, dim} in elements (3 each), any
+ *             non-negative strides.  cu_seqlens_new: device int32, B + 1 entries.  Sequence b brings n_new(b) =
+ *             clamp(cu[b + 1] - cu[b], 0, max_seqlen_new) rows from s(b) = cu[b] on, every offset read clamped to [0, total_new] as
+ *             in fa2_fwd_kvcache_varlen; n_new(b) = 0 is legal.  Row s(b) + t becomes key j = start(b) + t of sequence b and K is
+ *             rotated at min(j, S_rot - 1); tokens with j >= capacity are dropped.  Rows outside every sequence -- in front of the
+ *             first offset, the surplus of a span longer than max_seqlen_new, behind the last offset -- are not read.
+ *   Lengths.  seqlens_out[b] = min(start(b) + n_new(b), capacity), written for every b, sequences without tokens included.
+ *   Q.        Optional, with tables: Q packed (total_new, H, d) over the same cu_seqlens_new, q_strides {token, head, dim}, rotated
+ *             into the caller's contiguous packed q_rot (total_new, H, d).  Row i of sequence b is rotated at
+ *             min(start(b) + (q_pos_per_row ? i : 0), S_rot - 1).  Rows of q_rot outside every sequence are not written.
+ *   Work.     One thread row per packed row (a binary search over cu_seqlens_new finds its sequence), not B x max_seqlen_new
+ *             tiles: a long chunk beside many one-token decodes costs what its total_new rows cost.
+ *   Offsets.  For non-decreasing cu_seqlens_new the result is exactly the per-sequence definition above.  For offsets that are not
+ *             non-decreasing the cache may receive wrong rows; every address formed is still inside k_new / v_new / Q / q_rot (row
+ *             < total_new), the cache or pool (key index < capacity, page clamped), the block table (b < B, page slot < max_blocks)
+ *             and the rotary tables: wrong numbers at worst, never an access outside the tensors.
+ *
+ * Every error of fa2_kvcache_append applies (N_new and N_q do not exist here).  FA2_ERR_BAD_ARG also for a null cu_seqlens_new,
+ * total_new or max_seqlen_new outside [1, 2^28], total_new * max(H, 2 * H_kv) > 2^40 (H counted only with Q; the bound of B * H * N_q in
+ * the decode calls, which keeps every byte offset of a row far inside 64 bits); the message names the argument.
+ */
+int fa2_kvcache_append_varlen(void *K, void *V, const int64_t k_strides[4], const int64_t v_strides[4],
+                              const int32_t *block_table, int64_t block_table_stride,
+                              const void *k_new, const void *v_new, const int64_t k_new_strides[3], const int64_t v_new_strides[3],
+                              const int32_t *cu_seqlens_new, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                              const float *k_descale, const float *v_descale,
+                              const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                              const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                              int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                              const void *Q, void *q_rot, const int64_t q_strides[3], int32_t H, int32_t q_pos_per_row,
+                              int32_t B, int32_t H_kv, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                              int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                              int32_t dtype_enum, int32_t kv_dtype_enum, void *hip_stream);
+
+/*
+ * The fused ragged step (a mixed batch of chunked prefill and decodes in one call): fa2_kvcache_append_varlen, then on the same stream
+ * fa2_fwd_kvcache_varlen over the updated cache with seqlens_out as its cache_seqlens and cu_seqlens_q as the append's
+ * cu_seqlens_new -- total_new = total_q, max_seqlen_new = max_seqlen_q, and token i of Q, k_new and v_new is the same token.  With
+ * tables the attention reads q_rot (packed, contiguous) in Q's place; q_rot may be null without them.  q_pos_per_row is
+ * causal || window_left >= 0 || window_right >= 0, fa2_fwd_kvcache_append's rule, so a uniform batch reproduces that call.
+ * cache_seqlens holds the lengths BEFORE the append and is not modified.  Mask, split rule, num_splits, workspace, variants and
+ * empty rows are fa2_fwd_kvcache_varlen's.  Every error of both halves comes back before any launch.
+ */
+int fa2_fwd_kvcache_varlen_append(const void *Q, void *K, void *V, void *O, void *L,
+                                  const int64_t q_strides[3], const int64_t k_strides[4], const int64_t v_strides[4],
+                                  const int64_t o_strides[3], int64_t l_head_stride,
+                                  const int32_t *cu_seqlens_q, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                                  const int32_t *block_table, int64_t block_table_stride,
+                                  const float *k_descale, const float *v_descale,
+                                  const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                                  const void *k_new, const void *v_new, const int64_t k_new_strides[3], const int64_t v_new_strides[3],
+                                  const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                                  int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, void *q_rot,
+                                  int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                                  int32_t dtype_enum, int32_t kv_dtype_enum,
+                                  int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                                  void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
 /* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
  * elements plus fp32 partial L of num_splits * B * H * N_q. */
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits);
