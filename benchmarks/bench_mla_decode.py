@@ -1,0 +1,230 @@
+#!/usr/bin/env python3
+"""MLA decode timing (fa2_fwd_kvcache_mla: d = 576, d_v = 512, V = K[..., :512]), bf16, H_kv = 1; JSON lines appended to
+profiles/mla/bench_mla_decode.jsonl.  The protocol is benchmarks/bench_decode.py's: kernel times come from a
+`rocprofv3 --kernel-trace --stats` child per shape (a fresh process, under its own `timeout -k 10`; the first non-zero status ends
+the run), every side rotates over enough copies of the latent cache to exceed the 256 MiB last-level cache, and avg, min-max and
+stddev are reported per call.
+
+Sides of one child, each warmed (3 calls, not counted) and then run back to back:
+  auto:    flash_attention_mla_decode_forward's launch, AUTO variant, auto num_splits (contiguous, or paged with --page-size 64:
+           the cache scattered into a pool under a random permutation table);
+  generic: the same launch, the VALU form forced, the same num_splits;
+  sdpa:    torch scaled_dot_product_attention on the same absorbed tensors, contiguous only: K (B, 1, S, 576), V its first 512
+           columns, and the H heads of a token as the query rows of that one KV head, Q (B, 1, H N_q, 576) -- the form that
+           reads the latent cache once (no mask: the benchmark's calls have none).
+The kernel trace is cut into the sides by dispatch order (split kernel plus combine per call; one kernel for num_splits = 1; the
+rest after the last decode kernel is sdpa's).  hbm_share counts 1,152 B per visible key ONCE over the side's kernel time, as a
+share of the 6.29 TB/s copy rate: a second row tile (128 heads, or 64 heads at N_q = 2) reads the keys again and is not counted.
+
+Records:
+  kind=kernels        one per shape and cache form: the sides' avg / min / max / stddev in microseconds, auto_over_generic;
+  kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS on the four SWEEP_CASES, one traced child per shape."""
+import argparse
+import csv
+import glob
+import json
+import math
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "mla", "bench_mla_decode.jsonl")
+HBM_COPY_RATE = 6.29e12  # bytes / s, measured copy rate of the MI355X
+D, D_V = 576, 512
+
+SHAPES = ((1, 8192), (1, 65536), (16, 4096), (64, 2048), (128, 4096))  # (B, N_k)
+CASES = {f"h{H}_q{N_q}_b{B}_n{S}": (B, H, N_q, S) for H in (16, 128) for N_q in (1, 2) for B, S in SHAPES}
+SWEEP_CASES = ("h128_q1_b1_n8192", "h128_q1_b1_n65536", "h128_q1_b16_n4096", "h16_q1_b1_n65536")
+SWEEP_SPLITS = (1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def emit(fh, **kw):
+    line = json.dumps(kw)
+    print(line, flush=True)
+    if fh is not None:
+        fh.write(line + "\n")
+        fh.flush()
+
+
+class Case:
+    def __init__(self, name, dev, page_size=0):
+        import torch
+        from flash_attention_dlrs_amd import _lib
+        from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
+        self.torch, self._lib, self.dev = torch, _lib, dev
+        B, H, N_q, S = CASES[name]
+        self.shape = dict(B=B, H=H, N_q=N_q, N_k=S)
+        self.kv_bytes = 2 * D * B * S
+        self.copies = max(2, math.ceil(300e6 / self.kv_bytes))
+        self.scale = D ** -0.5
+        self.enum = convert_triton_dtype(torch.bfloat16)
+        mk = lambda *s: (torch.randn(*s, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
+        self.Q = mk(B, H, N_q, D)
+        self.KV = [mk(B, 1, S, D) for _ in range(self.copies)]
+        self.lens = torch.full((B,), S, dtype=torch.int32, device=dev)
+        self.O = torch.empty(B, H, N_q, D_V, dtype=torch.bfloat16, device=dev)
+        self.L = torch.empty(B, H, N_q, dtype=torch.bfloat16, device=dev)
+        self.i = 0
+        self.page_size, self.table = page_size, None
+        if page_size:  # every copy scattered into a pool (num_blocks, 1, P, 576) under one random table
+            mb = S // page_size
+            perm = torch.randperm(B * mb, generator=torch.Generator().manual_seed(0)).to(dev)
+            self.table = perm.view(B, mb).to(torch.int32)
+            for k, t in enumerate(self.KV):
+                p = torch.empty(B * mb, 1, page_size, D, dtype=t.dtype, device=dev)
+                p[perm] = t.view(B * mb, 1, page_size, D)
+                self.KV[k] = p
+
+    def auto_splits(self):
+        s = self.shape
+        return self._lib.kvcache_mla_num_splits(s["B"], s["H"], 1, s["N_q"], s["N_k"], D, D_V, self.enum)
+
+    def decode(self, variant, num_splits=0):
+        """The library launch itself, outputs and workspace allocated once (what a serving loop does)."""
+        s = self.shape
+        n = num_splits or self.auto_splits()
+        words = self._lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], D_V, n) // 4
+        ws = self.torch.empty(max(words, 1), dtype=self.torch.float32, device=self.dev)
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            kv = self.KV[self.i]
+            self._lib.fa2_fwd_kvcache_mla(self.Q, kv, kv[..., :D_V], self.O, self.L, self.lens, self.enum, block_table=self.table,
+                                          scale=self.scale, num_splits=n, workspace=ws, variant=self._lib.KVCACHE_MLA_VARIANTS[variant])
+        return run
+
+    def sdpa(self):
+        F = self.torch.nn.functional
+
+        def run():
+            self.i = (self.i + 1) % self.copies
+            kv = self.KV[self.i]
+            F.scaled_dot_product_attention(self.Q.view(self.Q.shape[0], 1, -1, D), kv, kv[..., :D_V], scale=self.scale)
+        return run
+
+
+def generic_iters(shape, iters):
+    """the VALU form reads the keys once per query head: fewer calls where one takes tens of milliseconds"""
+    return max(3, min(iters, int(2e8 / (shape["B"] * shape["H"] * shape["N_q"] * shape["N_k"]))))
+
+
+def run_pass(name, args):
+    """The traced child: each side warmed, then run back to back; the kernel trace holds the times."""
+    import torch
+    c = Case(name, torch.device("cuda:0"), args.page_size)
+    calls = {"auto": args.iters + 3, "generic": generic_iters(c.shape, args.iters) + 3}
+    sides = [("auto", c.decode("auto")), ("generic", c.decode("generic"))]
+    if not args.page_size and not args.no_sdpa:
+        sides.append(("sdpa", c.sdpa()))
+        calls["sdpa"] = generic_iters(c.shape, args.iters) + 3
+    for side, f in sides:
+        for _ in range(calls[side]):
+            f()
+        torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, calls=calls, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(), page_size=args.page_size, **c.shape)))
+
+
+def run_sweep_pass(name, args):
+    """The traced child of the split sweep: AUTO's variant alone, one split count after the other."""
+    import torch
+    c = Case(name, torch.device("cuda:0"))
+    for n in SWEEP_SPLITS:
+        f = c.decode("auto", n)
+        for _ in range(args.iters + 3):
+            f()
+        torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, calls=args.iters + 3, auto_splits=c.auto_splits(), kv_bytes=c.kv_bytes, **c.shape)))
+
+
+def traced_child(out, extra, args):
+    os.makedirs(out, exist_ok=True)
+    cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
+           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--page-size", str(args.page_size)] + extra + \
+        (["--no-sdpa"] if args.no_sdpa else [])
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
+        sys.stderr.write(p.stdout[-2000:] + p.stderr[-2000:])
+        sys.exit(p.returncode)
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def trace_rows(out):
+    trace = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
+    return sorted(csv.DictReader(open(trace[0])), key=lambda r: int(r["Start_Timestamp"]))
+
+
+def per_call(seg, per, calls):
+    """avg / min / max / stddev of the kernel time per call, the first 3 calls (warm-up) left out"""
+    us = [sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg[per * k:per * k + per]) / 1e3 for k in range(3, calls)]
+    avg = sum(us) / len(us)
+    return dict(avg_us=round(avg, 2), min_us=round(min(us), 2), max_us=round(max(us), 2),
+                stddev_us=round((sum((u - avg) ** 2 for u in us) / len(us)) ** 0.5, 2), calls=len(us),
+                kernels=sorted({r["Kernel_Name"][:60] for r in seg}))
+
+
+def sides_from_trace(out, info):
+    rows = trace_rows(out)
+    dec = [k for k, r in enumerate(rows) if "fa2_decode" in r["Kernel_Name"]]
+    per = 1 if info["num_splits"] == 1 else 2
+    na, ng = info["calls"]["auto"], info["calls"]["generic"]
+    assert len(dec) == per * (na + ng), (len(dec), per, na, ng)
+    fa = [rows[k] for k in dec]
+    sides = {"auto": per_call(fa[:per * na], per, na), "generic": per_call(fa[per * na:], per, ng)}
+    if "sdpa" in info["calls"]:
+        rest, ns = rows[dec[-1] + 1:], info["calls"]["sdpa"]
+        if rest and len(rest) % ns == 0:
+            sides["sdpa"] = per_call(rest, len(rest) // ns, ns)
+    return sides
+
+
+def run_rocprof(names, args, fh):
+    for name in names:
+        out = os.path.join(args.rocprof, name + (f"_p{args.page_size}" if args.page_size else ""))
+        info = traced_child(out, ["--pass-case", name], args)
+        sides = sides_from_trace(out, info)
+        a, g = sides["auto"], sides["generic"]
+        emit(fh, kind="kernels", **{k: v for k, v in info.items() if k != "calls"},
+             hbm_share=round(info["kv_bytes"] / (a["avg_us"] * 1e-6) / HBM_COPY_RATE, 3),
+             hbm_share_generic=round(info["kv_bytes"] / (g["avg_us"] * 1e-6) / HBM_COPY_RATE, 3),
+             auto_over_generic=round(a["avg_us"] / g["avg_us"], 4), ranges_overlap=a["max_us"] >= g["min_us"], **sides)
+        if args.sweep and name in SWEEP_CASES and not args.page_size:
+            out = os.path.join(args.rocprof, name + "_sweep")
+            info = traced_child(out, ["--sweep-case", name], args)
+            rows = [r for r in trace_rows(out) if "fa2_decode" in r["Kernel_Name"]]
+            pos, calls = 0, info["calls"]
+            for n in SWEEP_SPLITS:
+                per = 1 if n == 1 else 2
+                r = per_call(rows[pos:pos + per * calls], per, calls)
+                pos += per * calls
+                emit(fh, kind="sweep_kernels", case=name, num_splits=n, auto_splits=info["auto_splits"],
+                     hbm_share=round(info["kv_bytes"] / (r["avg_us"] * 1e-6) / HBM_COPY_RATE, 3), **r)
+            assert pos == len(rows)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--sweep", action="store_true", help="also time num_splits in %s on %s" % (SWEEP_SPLITS, SWEEP_CASES))
+    ap.add_argument("--no-sdpa", action="store_true")
+    ap.add_argument("--rocprof", metavar="DIR", default=os.path.join(ROOT, "bench_out", "mla_traces"),
+                    help="the traces of the rocprofv3 children go under DIR")
+    ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--page-size", type=int, default=0, metavar="N", help="the paged cache at N-key pages (64) in the contiguous one's place")
+    ap.add_argument("--pass-case", help=argparse.SUPPRESS)
+    ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
+    ap.add_argument("--out", default=OUT)
+    args = ap.parse_args()
+    if args.pass_case:
+        return run_pass(args.pass_case, args)
+    if args.sweep_case:
+        return run_sweep_pass(args.sweep_case, args)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as fh:
+        run_rocprof(args.cases.split(","), args, fh)
+
+
+if __name__ == "__main__":
+    main()

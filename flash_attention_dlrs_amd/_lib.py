@@ -55,13 +55,15 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_fwd_kvcache_paged",
            "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append",
            "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits",
-           "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append")
+           "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
 BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
 # KV-cache decode (fa2_fwd_kvcache) has its own small variant enum, FA2_KVCACHE_VARIANT_*
 KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
+# ... and the latent-cache call (fa2_fwd_kvcache_mla) its own set: FA2_KVCACHE_VARIANT_MLA16 in the d 64 / 128 matrix form's place
+KVCACHE_MLA_VARIANTS = {"auto": 0, "generic": 1, "mla16": 3}
 KVCACHE_MAX_SPLITS = 128
 
 _lib = None
@@ -194,6 +196,12 @@ def lib():
         l.fa2_kvcache_varlen_workspace_bytes.argtypes = [ctypes.c_int32] * 4
         l.fa2_kvcache_varlen_num_splits.restype = ctypes.c_int32
         l.fa2_kvcache_varlen_num_splits.argtypes = [ctypes.c_int32] * 8
+        # fa2_fwd_kvcache_paged's order without the descales, d_v after d, no kv_dtype_enum
+        l.fa2_fwd_kvcache_mla.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64] + [ctypes.c_int32] * 11 + \
+            [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_mla_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_mla_num_splits.argtypes = [ctypes.c_int32] * 8
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -482,6 +490,36 @@ def fa2_fwd_kvcache_paged(Q, K, V, O, L, block_table, cache_seqlens, dtype_enum,
             kd_ptr, vd_ptr, kd_st, vd_st, B, H, K.shape[1], N_q, K.shape[0], K.shape[2], block_table.shape[1], d,
             int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
             int(variant), _raw_stream(Q.device.index))
+    if rc != 0:
+        _raise(rc)
+
+
+def kvcache_mla_num_splits(B, H, H_kv, N_q, S_k, d, d_v, dtype_enum):
+    """What num_splits = 0 resolves to for a latent-cache decode call of this shape (fa2_kvcache_mla_num_splits)."""
+    return int(lib().fa2_kvcache_mla_num_splits(B, H, H_kv, N_q, S_k, d, d_v, int(dtype_enum)))
+
+
+def fa2_fwd_kvcache_mla(Q, K, V, O, L, cache_seqlens, dtype_enum, block_table=None, causal=False, scale=1.0, window=None, num_splits=0,
+                        workspace=None, variant=0):
+    """Launch decode attention with a value head size of its own (include/fa2_fwd.h fa2_fwd_kvcache_mla) on the current stream of
+    Q's device.  Q (B, H, N_q, d), K (B, H_kv, S_k, d), V (B, H_kv, S_k, d_v) -- V may be a view of K -- or, with block_table, the
+    pools (num_blocks, H_kv, page_size, d) / (..., d_v); O (B, H, N_q, d_v), L (B, H, N_q).  The workspace holds
+    kvcache_workspace_bytes(B, H, N_q, d_v, num_splits) bytes."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    ws_ptr = None if workspace is None else workspace.data_ptr()
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    tb_ptr, tb_st, nb, mb = (None, 0, 0, 0) if block_table is None else \
+        (block_table.data_ptr(), block_table.stride(0), K.shape[0], block_table.shape[1])
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_kvcache_mla(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, B, H, K.shape[1], N_q, nb, K.shape[2], mb, d,
+            V.shape[3], int(dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, int(variant),
+            _raw_stream(Q.device.index))
     if rc != 0:
         _raise(rc)
 

@@ -12,6 +12,9 @@ struct Fa2DecodeProblem {
     int64_t qs[4], ks[4], vs[4], os[4], ls[2];
     const int32_t *seqlens;  // device, B entries, or null (N_k = S_k)
     int32_t B, H, H_kv, N_q, S_k, d;
+    // value head size (fa2_fwd_kvcache_mla): V is (B, H_kv, S_k, d_v), O and the partials have d_v columns.  Every other entry
+    // point sets d_v = d.  V may overlap K in memory (MLA: V = K[..., :d_v]); neither is written.
+    int32_t d_v;
     int32_t dtype, causal;
     // fp8 KV cache (fa2_fwd_kvcache_fp8): kv_dtype is the element type of K and V (== dtype otherwise), kd / vd the device
     // descales at [b * s[0] + h_kv * s[1]], null = 1.  K = kd * float(K8), V = vd * float(V8).
@@ -27,7 +30,7 @@ struct Fa2DecodeProblem {
     int32_t wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
     float scale;
     int32_t num_splits;  // resolved, >= 1
-    float *o_part;       // [num_splits][B * H * N_q][d]   (num_splits > 1 only)
+    float *o_part;       // [num_splits][B * H * N_q][d_v]   (num_splits > 1 only)
     float *l_part;       // [num_splits][B * H * N_q]
     hipStream_t stream;
     // variable-length (packed) queries (fa2_fwd_kvcache_varlen): cu_q non-null.  Q, O are (total_q, H, d) with qs / os =
@@ -69,6 +72,14 @@ static inline bool fa2_decode_mfma16_shape(int32_t H, int32_t H_kv, int32_t N_q,
            (int64_t)(H / H_kv) * N_q <= 64;
 }
 int fa2_launch_decode_combine(const Fa2DecodeProblem &p);  // second launch, num_splits > 1 only
+
+// The latent-cache matrix form (fa2_decode_mla16.hip, FA2_KVCACHE_VARIANT_MLA16): d = 576, d_v = 512, V the first 512 columns of K,
+// 64 rows of a KV group per workgroup, ceil(g N_q / 64) row tiles per (split, KV head, sequence).
+static inline bool fa2_decode_mla16_shape(int32_t d, int32_t d_v, int32_t dtype) {
+    return (dtype == FA2_DTYPE_F16 || dtype == FA2_DTYPE_BF16) && d == 576 && d_v == 512;
+}
+bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16(const Fa2DecodeProblem &p);
 
 // The query-tiled matrix form of the packed call (fa2_decode_mfma16_v.hip): a workgroup owns tq consecutive query positions of one
 // sequence for the g heads of a KV group, R = g tq <= 64 rows.

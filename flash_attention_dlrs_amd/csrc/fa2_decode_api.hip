@@ -1,5 +1,5 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8,
-// fa2_fwd_kvcache_paged, the packed-query call fa2_fwd_kvcache_varlen, the cache appends fa2_kvcache_append and fa2_kvcache_append_varlen,
+// fa2_fwd_kvcache_paged, the latent-cache call fa2_fwd_kvcache_mla, the packed-query call fa2_fwd_kvcache_varlen, the cache appends fa2_kvcache_append and fa2_kvcache_append_varlen,
 // the fused steps fa2_fwd_kvcache_append and fa2_fwd_kvcache_varlen_append, and their helpers, declared in
 // include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
 // launches (the append where asked for, the split kernels, then the combine) on the caller's stream.
@@ -23,6 +23,25 @@ int num_splits_auto(int64_t B, int64_t H, int64_t H_kv, int64_t N_q, int64_t S_k
     int64_t n = (kSplitWaves * kChipWorkgroups + base - 1) / base;
     const int64_t tiles = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE;
     const int64_t cap = tiles / kMinSplitTiles;
+    if (n > cap) n = cap;
+    if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
+    return n < 1 ? 1 : (int)n;
+}
+
+// fa2_kvcache_mla_num_splits: the same rule for fa2_fwd_kvcache_mla.  The latent matrix form (fa2_decode_mla16.hip) runs ONE
+// workgroup per CU (its LDS tile and registers fill it), B * H_kv * ceil(g N_q / 64) of them unsplit, so one wave of the chip is
+// what the splits fill (kMlaSplitWaves), and a split is at least kMlaMinSplitTiles 64-key tiles long: each workgroup loads its
+// 64 x 576 Q fragments and writes 64 x 512 fp32 partials whatever its length.  The constants are read off the split sweep of
+// benchmarks/bench_mla_decode.py ("MLA decode").  Every other shape is counted as the VALU form's.
+constexpr int kMlaSplitWaves = 1;
+constexpr int kMlaMinSplitTiles = 4;
+
+int num_splits_mla(int64_t B, int64_t H, int64_t H_kv, int64_t N_q, int64_t S_k, int32_t d, int32_t d_v, int32_t dtype) {
+    if (!fa2_decode_mla16_shape(d, d_v, dtype) || H_kv < 1 || H % H_kv != 0) return num_splits_auto(B, H, H_kv, N_q, S_k, 0, dtype);
+    const int64_t base = B * H_kv * ((H / H_kv * N_q + 63) / 64);
+    if (base >= kChipWorkgroups) return 1;
+    int64_t n = (kMlaSplitWaves * kChipWorkgroups + base - 1) / base;
+    const int64_t cap = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE / kMlaMinSplitTiles;
     if (n > cap) n = cap;
     if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
     return n < 1 ? 1 : (int)n;
@@ -82,13 +101,14 @@ struct PagedCache {
 };
 
 // S_k is the capacity of a contiguous cache; with `pg` it is ignored and max_blocks * page_size takes its place.  With `append`
-// (checked by check_append) that launch goes first, once every check here has passed.
+// (checked by check_append) that launch goes first, once every check here has passed.  `mla_dv` non-null: fa2_fwd_kvcache_mla, V
+// is (B, H_kv, S_k, *mla_dv), d may reach 576 and FA2_KVCACHE_VARIANT_MLA16 is a variant; null: every other entry point, d_v = d.
 int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
                 const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
                 int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
                 float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
                 void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr, const PagedCache *pg = nullptr,
-                const Fa2AppendProblem *append = nullptr, const VarlenQ *vq = nullptr) {
+                const Fa2AppendProblem *append = nullptr, const VarlenQ *vq = nullptr, const int32_t *mla_dv = nullptr) {
     // (with `vq`: N_q is max_seqlen_q, the strides are {0, head, token, d} and {0, head}, all checked by the caller)
     const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
     const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
@@ -186,13 +206,29 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
         fa2_set_error("unknown dtype enum %d", dtype_enum);
         return FA2_ERR_UNSUPPORTED;
     }
-    if (d < 1 || d > 512) {
-        fa2_set_error("d=%d must be in [1, 512]", d);
-        return FA2_ERR_UNSUPPORTED;
-    }
-    if (variant != FA2_KVCACHE_VARIANT_AUTO && variant != FA2_KVCACHE_VARIANT_GENERIC && variant != FA2_KVCACHE_VARIANT_MFMA16) {
-        fa2_set_error("kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)", variant);
-        return FA2_ERR_UNSUPPORTED;
+    const int32_t d_v = mla_dv ? *mla_dv : d;
+    if (mla_dv) {
+        if (d < 1 || d > 576) {
+            fa2_set_error("kvcache mla: d=%d must be in [1, 576]", d);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (d_v < 1 || d_v > 512) {
+            fa2_set_error("kvcache mla: d_v=%d must be in [1, 512]", d_v);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (variant != FA2_KVCACHE_VARIANT_AUTO && variant != FA2_KVCACHE_VARIANT_GENERIC && variant != FA2_KVCACHE_VARIANT_MLA16) {
+            fa2_set_error("kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)", variant);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    } else {
+        if (d < 1 || d > 512) {
+            fa2_set_error("d=%d must be in [1, 512]", d);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (variant != FA2_KVCACHE_VARIANT_AUTO && variant != FA2_KVCACHE_VARIANT_GENERIC && variant != FA2_KVCACHE_VARIANT_MFMA16) {
+            fa2_set_error("kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)", variant);
+            return FA2_ERR_UNSUPPORTED;
+        }
     }
 
     Fa2DecodeProblem p;
@@ -200,7 +236,7 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     for (int k = 0; k < 4; ++k) { p.qs[k] = q_strides[k]; p.ks[k] = k_strides[k]; p.vs[k] = v_strides[k]; p.os[k] = o_strides[k]; }
     p.ls[0] = l_strides[0]; p.ls[1] = l_strides[1];
     p.seqlens = cache_seqlens;
-    p.B = B; p.H = H; p.H_kv = H_kv; p.N_q = N_q; p.S_k = S_k; p.d = d;
+    p.B = B; p.H = H; p.H_kv = H_kv; p.N_q = N_q; p.S_k = S_k; p.d = d; p.d_v = d_v;
     p.kv_dtype = f8 ? f8->kv_dtype : dtype_enum;
     p.kd = f8 ? f8->kd : nullptr; p.vd = f8 ? f8->vd : nullptr;
     for (int k = 0; k < 2; ++k) { p.kds[k] = p.kd ? f8->kds[k] : 0; p.vds[k] = p.vd ? f8->vds[k] : 0; }
@@ -211,11 +247,12 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
     p.cu_q = vq ? vq->cu_q : nullptr;
     p.total_q = vq ? vq->total_q : 0; p.max_q = vq ? vq->max_q : 0;
     if (num_splits != 0) p.num_splits = num_splits;
+    else if (mla_dv) p.num_splits = num_splits_mla(B, H, H_kv, N_q, S_k, d, d_v, dtype_enum);
     else p.num_splits = vq ? num_splits_varlen(B, H, H_kv, vq->total_q, vq->max_q, S_k, d, dtype_enum) : num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum);
     p.stream = (hipStream_t)hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
-        const int64_t need = vq ? workspace_bytes_varlen(vq->total_q, H, d, p.num_splits) : workspace_bytes(B, H, N_q, d, p.num_splits);
+        const int64_t need = vq ? workspace_bytes_varlen(vq->total_q, H, d, p.num_splits) : workspace_bytes(B, H, N_q, d_v, p.num_splits);
         if (!workspace || workspace_bytes_given < need) {
             fa2_set_error("kvcache: workspace of %lld bytes needed for num_splits=%d (%s), got %s%lld", (long long)need, p.num_splits,
                           vq ? "fa2_kvcache_varlen_workspace_bytes" : "fa2_kvcache_workspace_bytes", workspace ? "" : "null, ",
@@ -223,7 +260,14 @@ int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, c
             return FA2_ERR_BAD_ARG;
         }
         p.o_part = (float *)workspace;
-        p.l_part = p.o_part + (int64_t)p.num_splits * (vq ? (int64_t)vq->total_q * H : (int64_t)B * H * N_q) * d;
+        p.l_part = p.o_part + (int64_t)p.num_splits * (vq ? (int64_t)vq->total_q * H : (int64_t)B * H * N_q) * d_v;
+    }
+    if (mla_dv) {  // the latent-cache call: its own matrix form where it runs, else the VALU form; the same combine
+        if (variant == FA2_KVCACHE_VARIANT_AUTO)
+            variant = fa2_decode_mla16_supports(p) ? FA2_KVCACHE_VARIANT_MLA16 : FA2_KVCACHE_VARIANT_GENERIC;
+        rc = variant == FA2_KVCACHE_VARIANT_MLA16 ? fa2_launch_decode_mla16(p) : fa2_launch_decode_generic(p);
+        if (rc != FA2_OK || p.num_splits == 1) return rc;
+        return fa2_launch_decode_combine(p);
     }
     if (vq) {  // the packed call: its own matrix form (query-tiled), the same VALU form and combine
         if (variant == FA2_KVCACHE_VARIANT_AUTO)
@@ -568,6 +612,26 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
     return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, 0, d,
                        dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
                        variant, wide ? nullptr : &f8, &pg);
+}
+
+int fa2_fwd_kvcache_mla(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                        const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
+                        const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride, int32_t B, int32_t H,
+                        int32_t H_kv, int32_t N_q, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                        int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                        void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    // block_table null: the contiguous cache (B, H_kv, S_k, d), a pool of one page per sequence: page_size carries S_k
+    // (num_blocks and max_blocks are not read)
+    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
+    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q,
+                       block_table ? 0 : page_size, d, dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
+                       workspace_bytes, hip_stream, variant, nullptr, block_table ? &pg : nullptr, nullptr, nullptr, &d_v);
+}
+
+int32_t fa2_kvcache_mla_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t d_v,
+                                   int32_t dtype_enum) {
+    if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
+    return num_splits_mla(B, H, H_kv, N_q, S_k, d, d_v, dtype_enum);
 }
 
 int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],

@@ -24,7 +24,7 @@ struct CombineArgs {
     int64_t os[4], ls[2];
     const float *o_part, *l_part;
     int64_t rows;  // B * H * N_q
-    int H, N_q, d, num_splits;
+    int H, N_q, d, num_splits;  // d: the columns of O and of the partials (the value head size)
     const int32_t *cu_q;  // packed queries: B + 1 offsets (os[0] = ls[0] = 0), else null
     int total_q, max_q;
 };
@@ -119,7 +119,7 @@ int fa2_launch_decode_combine(const Fa2DecodeProblem &p) {
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
     a.o_part = p.o_part; a.l_part = p.l_part;
     a.rows = (int64_t)p.B * p.H * p.N_q;
-    a.H = p.H; a.N_q = p.N_q; a.d = p.d; a.num_splits = p.num_splits;
+    a.H = p.H; a.N_q = p.N_q; a.d = p.d_v; a.num_splits = p.num_splits;
     a.cu_q = p.cu_q; a.total_q = p.total_q; a.max_q = p.max_q;
     if (p.cu_q) a.rows = (int64_t)p.total_q * p.H;
     switch (p.dtype) {

@@ -1,6 +1,7 @@
 // fa2_decode_generic.hip -- the catch-all KV-cache decode kernel (fa2_fwd_kvcache, FA2_KVCACHE_VARIANT_GENERIC): every
-// supported dtype (f64, f32, f16, bf16; an fp8 cache under f16 / bf16), any strides, any d in [1, 512], any g * N_q.  The
-// arithmetic and the work split inside
+// supported dtype (f64, f32, f16, bf16; an fp8 cache under f16 / bf16), any strides, any d in [1, 512], any g * N_q -- and, for
+// fa2_fwd_kvcache_mla, d up to 576 with a value head size d_v of its own (V (B, H_kv, S_k, d_v), which may be a view of K: neither
+// is written): the score loop runs over d, a lane's output columns come from d_v.  The arithmetic and the work split inside
 // a workgroup are fa2_generic.hip's varlen form (16 query rows per workgroup, 4 per wave, lane = key for the scores, lane =
 // output column for P.V); on top of it the keys of one sequence are split across workgroups as the MFMA form splits them
 // (fa2_decode.h), each (split, row) writing a normalised fp32 partial O_s and its log2-domain L_s to the workspace for the
@@ -75,7 +76,7 @@ struct DecodeGenericArgs {
     void *O, *L;
     int64_t qs[4], ks[4], vs[4], os[4], ls[2];
     const int32_t *seqlens;
-    int H, gqa, N_q, S_k, d, causal, wl, wr, num_splits, nqt;
+    int H, gqa, N_q, S_k, d, dv, causal, wl, wr, num_splits, nqt;  // dv: columns of V, O and the partials
     float *o_part, *l_part;
     double c_log2e;
     const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
@@ -87,7 +88,7 @@ struct DecodeGenericArgs {
     int total_q, max_q;
 };
 
-// grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
+// grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d_v / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
 // PAGED: K and V are a page pool behind a block table.
 template <class E, class C, bool PAGED, int DPL>
 __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const DecodeGenericArgs a) {
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int split = blockIdx.x / a.nqt, i = blockIdx.x - split * a.nqt;
     const int b = blockIdx.y, h = blockIdx.z;
-    const int d = a.d;
+    const int d = a.d, dv = a.dv;
     int N = a.N_q, start = 0;  // the sequence's query count and its first packed row
     if (a.cu_q) {
         fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, start, N);
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d) {
+                if (x < dv) {
                     const A v = C::load(a.V, vb + (int64_t)x * a.vs[3]);
 #pragma unroll
                     for (int r = 0; r < kRowsPerWave; ++r) o[r][cc] += pr[r] * v;
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? (F8 ? o[r][cc] / l * vd : o[r][cc] / l) : (A)0);
+                if (x < dv) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? (F8 ? o[r][cc] / l * vd : o[r][cc] / l) : (A)0);
             }
             if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + start + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
         } else {  // every (split, row) is written, an empty split as O_s = 0, L_s = -inf: the workspace arrives uninitialised
@@ -229,11 +230,23 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d) a.o_part[prow * d + x] = l > 0 ? (float)(F8 ? o[r][cc] / l * vd : o[r][cc] / l) : 0.0f;
+                if (x < dv) a.o_part[prow * dv + x] = l > 0 ? (float)(F8 ? o[r][cc] / l * vd : o[r][cc] / l) : 0.0f;
             }
             if (lane == 0) a.l_part[prow] = l > 0 ? (float)(m[r] + log2_acc<A>(l)) : -INFINITY;
         }
     }
+}
+
+// More than 64 KiB of dynamic LDS (d > 256 in double) is opted into, once per device and instantiation.
+template <class E, class C, bool PAGED, int DPL>
+void launch_k(const dim3 &grid, const dim3 &block, size_t smem, hipStream_t stream, const DecodeGenericArgs &a) {
+    static Fa2DeviceLatch attr_done;
+    if (smem > 64 * 1024 && attr_done.need()) {
+        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, PAGED, DPL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(sizeof(typename E::acc_t) * ((size_t)kBr * 576 + (size_t)kWaves * kRowsPerWave * kBc)));
+        attr_done.mark();
+    }
+    hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, DPL>), grid, block, smem, stream, a);
 }
 
 template <class E, class C, bool PAGED> int launch_p(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
@@ -243,18 +256,12 @@ template <class E, class C, bool PAGED> int launch_p(const Fa2DecodeProblem &p, 
         return FA2_ERR_BAD_ARG;
     }
     const dim3 grid((unsigned)gx, p.B, p.H), block(kWaves * 64);
-    const size_t smem = sizeof(typename E::acc_t) * ((size_t)kBr * p.d + (size_t)kWaves * kRowsPerWave * kBc);
-    const int dpl = (p.d + 63) / 64;
-    static Fa2DeviceLatch attr_done;  // d > 256 in double asks for more than 64 KiB of dynamic LDS: opt in, once per device
-    if (dpl > 4 && attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, PAGED, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(sizeof(typename E::acc_t) * ((size_t)kBr * 512 + (size_t)kWaves * kRowsPerWave * kBc)));
-        attr_done.mark();
-    }
-    if (dpl <= 1) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 1>), grid, block, smem, p.stream, a);
-    else if (dpl <= 2) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 2>), grid, block, smem, p.stream, a);
-    else if (dpl <= 4) hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 4>), grid, block, smem, p.stream, a);
-    else hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, 8>), grid, block, smem, p.stream, a);
+    const size_t smem = sizeof(typename E::acc_t) * ((size_t)kBr * (p.d > p.d_v ? p.d : p.d_v) + (size_t)kWaves * kRowsPerWave * kBc);
+    const int dpl = (p.d_v + 63) / 64;
+    if (dpl <= 1) launch_k<E, C, PAGED, 1>(grid, block, smem, p.stream, a);
+    else if (dpl <= 2) launch_k<E, C, PAGED, 2>(grid, block, smem, p.stream, a);
+    else if (dpl <= 4) launch_k<E, C, PAGED, 4>(grid, block, smem, p.stream, a);
+    else launch_k<E, C, PAGED, 8>(grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache generic kernel launch failed: %s", hipGetErrorString(e));
@@ -275,7 +282,7 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     for (int k = 0; k < 4; ++k) { a.qs[k] = p.qs[k]; a.ks[k] = p.ks[k]; a.vs[k] = p.vs[k]; a.os[k] = p.os[k]; }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
     a.seqlens = p.seqlens;
-    a.H = p.H; a.gqa = p.H / p.H_kv; a.N_q = p.N_q; a.S_k = p.S_k; a.d = p.d; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
+    a.H = p.H; a.gqa = p.H / p.H_kv; a.N_q = p.N_q; a.S_k = p.S_k; a.d = p.d; a.dv = p.d_v; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
     a.num_splits = p.num_splits;
     a.nqt = (p.N_q + kBr - 1) / kBr;
     a.o_part = p.o_part; a.l_part = p.l_part;

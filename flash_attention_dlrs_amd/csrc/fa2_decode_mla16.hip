@@ -1,0 +1,430 @@
+// fa2_decode_mla16.hip -- KV-cache decode over a shared latent cache (fa2_fwd_kvcache_mla, FA2_KVCACHE_VARIANT_MLA16): multi-head
+// latent attention in its absorbed form, f16 / bf16, d = 576 (512 latent + 64 rotary columns), d_v = 512, V = K[..., :512].
+//
+// One workgroup of four waves handles one (split, 64-row tile of a KV group, KV head, sequence): the grid is
+// (num_splits * row_tiles, H_kv, B), row r = head-in-group * N_q + query as in fa2_decode_mfma16.hip, a last tile with fewer
+// than 64 rows computing its padding rows (the last row again) and dropping them.  A second row tile reads the same keys again.
+//
+// Per step the workgroup takes ONE 64-key tile of the latent cache, staged once: 64 rows of 1,152 B in an LDS image of 1,280-B
+// rows (a multiple of 256 B, so the swizzle of fa2_decode_mfma16.hip at d = 128 -- a function of row & 15 on the low four bits
+// of the 16-byte chunk index -- keeps the K row reads and the transposed V reads conflict-free; the 128 B of padding per row are
+// never read).  The score reads all 72 chunks of a row, the value side columns 0..511 of the SAME image through
+// ds_read_b64_tr_b16: the value operand is never fetched a second time.
+//
+//   S phase.   Wave w owns key block w & 1 and row block w >> 1 of S^T = K Q^T on v_mfma_f32_32x32x16: 36 k-steps, its Q
+//              fragments (36 x 4 registers) resident.
+//   Softmax.   The two key blocks of a row exchange their maxima through LDS; then the online softmax of the other decode kernels
+//              (exp2 domain, masked scores SELECTED to -inf, P rounded to the I/O dtype).  P of the 64 x 64 tile goes to LDS in
+//              the B-fragment order of the P.V MFMAs (rows of 144 B: conflict-free 16-byte reads), beside the per-row rescale
+//              factors.
+//   P.V phase. Wave w owns value columns [128 w, 128 w + 128) for all 64 rows: 4 x 2 accumulator tiles (128 registers), 32 MFMAs
+//              per step, each V fragment used for both row blocks.
+//
+// Staging goes through registers while the previous tile is computed (single-buffered, 18 x 16 bytes per thread): a wave loads
+// 16 rows, chunks 0..63 of a row with one instruction (1 KiB contiguous) and the last 8 chunks of 8 rows with another, so no
+// load crosses a row.  Addresses are 64-bit per thread.
+//
+// Stale cache contents: a key at or past the split's end (<= N_k(b)) is not loaded -- its row is written to LDS as zeros and its
+// score is selected to -inf -- so what lies behind cache_seqlens[b] is never read.  Paged cache: page_size % 64 == 0, a key
+// tile lies inside one page, its table entry is one scalar load, clamped to [0, num_blocks - 1]; the entry of a tile at or past
+// the split's end is not loaded.
+//
+// Output: num_splits == 1 writes O / l and L = m + log2 l in the I/O dtype (a row without a visible key: O = 0, L = +inf);
+// otherwise every (split, row) writes the normalised fp32 partial (an empty split: 0 and -inf) for fa2_decode_combine.hip.
+// Vector stores only, no atomics, no hand-off between workgroups.
+#include "fa2_decode.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+
+#define LDS_PTR(T) __attribute__((address_space(3))) T *
+
+template <typename T> struct Mma;
+template <> struct Mma<__bf16> {
+    using frag = bf16x8;
+    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Mma<_Float16> {
+    using frag = f16x8;
+    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+};
+
+struct DecodeMlaArgs {
+    const char *Q, *K;
+    char *O, *L;
+    int64_t qs[3], ks[3], os[3];  // B, H, N strides in BYTES (d stride is 1 element); V is K
+    int64_t ls[2];                // L strides in elements
+    const int32_t *seqlens;
+    int H, g, N_q, S_k, causal, wl, wr, num_splits, row_tiles;
+    float *o_part, *l_part;
+    float c_log2e;  // scale * log2(e) > 0
+    const int32_t *table;  // paged cache only: entry [b, i] at b * table_stride + i; ks[0] is the block stride
+    int64_t table_stride;
+    int page_size, num_blocks;
+};
+
+constexpr int kD = 576, kDV = 512, kBC = 64;
+constexpr int kCPR = kD * 2 / 16;    // 72 16-byte chunks per cache row
+constexpr int kKS = kD / 16;         // 36 k-steps of the score
+constexpr int kRowB = 1280;          // LDS row: 1,152 B + 128 B of padding
+constexpr int kTileB = kBC * kRowB;  // 80 KiB
+constexpr int kPRowB = 144;          // a row of P: 64 keys x 2 B + 16 B of padding
+constexpr int kPOff = kTileB;
+constexpr int kXmOff = kPOff + 64 * kPRowB;  // [2][64] floats: a row's maximum over each key block
+constexpr int kCfOff = kXmOff + 512;         // [64]: the rescale factor of the step
+constexpr int kXlOff = kCfOff + 256;         // [2][64]: a row's sum over each key block's keys (epilogue)
+constexpr int kMfOff = kXlOff + 512;         // [64]: a row's maximum (epilogue)
+constexpr int kSmem = kMfOff + 256;
+constexpr int kStage = kCPR * kBC / 256;     // 18 16-byte loads per thread and tile
+static_assert(kStage == 18 && kSmem <= 160 * 1024, "one workgroup per CU");
+
+// Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: fa2_decode_mfma16.hip's swizzle at d = 128.
+__device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4); }
+
+template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    LDS_PTR(char) lds = (LDS_PTR(char))smem;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kb = wave & 1, rb = wave >> 1;  // S phase: key block, row block
+    const int i = lane & 31, h = lane >> 5;
+    const int hk = blockIdx.y, b = blockIdx.z;
+    const int split = blockIdx.x / a.row_tiles, rt = blockIdx.x - split * a.row_tiles;
+    const int N_q = a.N_q, R = a.g * N_q;
+
+    int NK, k0, k1;
+    fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
+    int wl, wr;
+    fa2_varlen_band(N_q, NK, a.causal, a.wl, a.wr, wl, wr);
+    // the keys of the split that the band of any query position touches: [kb0, ke), kb0 on a 64-key boundary
+    const int lo_t = -wl;
+    const int kb0 = lo_t > k0 ? (lo_t & ~63) : k0;  // (k0 is a multiple of 64)
+    const int ke = N_q + wr < k1 ? N_q + wr : k1;
+    const int nt = ke > kb0 ? (ke - kb0 + kBC - 1) / kBC : 0;
+
+    // ---- S phase: this lane's row (head of the group, query position); padding rows repeat the last row and are not stored
+    const int srow = rt * 64 + rb * 32 + i;
+    const int srowc = srow < R ? srow : R - 1;
+    const int shg = srowc / N_q;
+    const int sqi = srowc - shg * N_q;
+
+    // ---- Q fragments: B operand of S^T = K Q^T.  Lane (i, h) holds Q[row][16ks + 8h .. +7].
+    frag qf[kKS];
+    {
+        const char *qp = a.Q + b * a.qs[0] + (int64_t)(hk * a.g + shg) * a.qs[1] + (int64_t)sqi * a.qs[2] + h * 16;
+#pragma unroll
+        for (int ks = 0; ks < kKS; ++ks) qf[ks] = __builtin_bit_cast(frag, *(const u32x4 *)(qp + ks * 32));
+    }
+
+    // ---- staging map.  Wave w stages tile rows 16w .. 16w + 15: pass it < 16 is row 16w + it, chunks 0..63 (one per lane); pass
+    // 16 + jb is rows 16w + 8jb + (lane >> 3), chunks 64 + (lane & 7).  (paged: the page's offset joins in stage_load)
+    const int sb_row = 16 * wave + (lane >> 3), sb_ch = 64 + (lane & 7);
+    const char *kbase = a.K + hk * a.ks[1] + (PAGED ? 0 : b * a.ks[0] + (int64_t)kb0 * a.ks[2]);
+    const char *kg_a = kbase + (int64_t)(16 * wave) * a.ks[2] + lane * 16;
+    const char *kg_b = kbase + (int64_t)sb_row * a.ks[2] + sb_ch * 16;
+
+    // paged: the walk over the pages, as in fa2_decode_mfma16.hip: stage_load takes the tiles in order, a tile is 64 keys on a
+    // multiple of 64 and page_size is a multiple of 64, so (pg_i, pg_row) advance by 64 rows per tile and wrap at page_size.
+    int pg_i = 0, pg_row = 0;
+    const int32_t *tab = nullptr;
+    if constexpr (PAGED) {
+        pg_i = kb0 / a.page_size;
+        pg_row = kb0 - pg_i * a.page_size;
+        tab = a.table + b * a.table_stride;
+    }
+    u32x4 sreg[kStage];
+    auto stage_load = [&](int t) {
+        const int rel = t * kBC;  // the tile's first key, relative to kb0
+        int64_t toff = (int64_t)rel * a.ks[2];
+        if constexpr (PAGED) {
+            toff = 0;
+            // one scalar load per tile; the entry of a tile at or past the split's end is not part of the problem: not loaded
+            if (kb0 + rel < ke) toff = (int64_t)fa2_decode_page(tab, pg_i, a.num_blocks) * a.ks[0] + (int64_t)pg_row * a.ks[2];
+            pg_row += kBC;
+            if (pg_row >= a.page_size) {
+                pg_row = 0;
+                ++pg_i;
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+            const bool ok = kb0 + rel + 16 * wave + it < ke;  // past the split's end (<= N_k): zeros, never read
+            sreg[it] = ok ? *(const u32x4 *)(kg_a + toff + (int64_t)it * a.ks[2]) : u32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int jb = 0; jb < 2; ++jb) {
+            const bool ok = kb0 + rel + sb_row + 8 * jb < ke;
+            sreg[16 + jb] = ok ? *(const u32x4 *)(kg_b + toff + (int64_t)(8 * jb) * a.ks[2]) : u32x4{0, 0, 0, 0};
+        }
+    };
+    auto stage_write = [&]() {
+#pragma unroll
+        for (int it = 0; it < 16; ++it) *(LDS_PTR(u32x4))(lds + lds_off(16 * wave + it, lane)) = sreg[it];
+#pragma unroll
+        for (int jb = 0; jb < 2; ++jb) *(LDS_PTR(u32x4))(lds + lds_off(sb_row + 8 * jb, sb_ch)) = sreg[16 + jb];
+    };
+
+    // ---- per-lane LDS offsets.  K row read: row 32kb + i, chunk 2ks + h.  V transposed read (ds_read_b64_tr_b16): lane 4q + p of a
+    // 16-lane group supplies row (16ks + 8u + 4h + q), columns 128w + 32db + 16(group & 1) + 4p .. +3.
+    const int k_row = 32 * kb + i;
+    const int k_swz = ((k_row & 3) << 2) | ((k_row >> 2) & 3);
+    int v_off[2][4];
+    {
+        const int w = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int db = 0; db < 4; ++db)
+                v_off[u][db] = lds_off(8 * u + 4 * h + qq, 16 * wave + 4 * db + 2 * w + (pp >> 1)) + 8 * (pp & 1);
+    }
+    const int p_wr = kPOff + (32 * rb + i) * kPRowB + ((4 * kb + h) << 4);  // + 32 ss: k-step 2kb + ss, half h
+    const int p_rd = kPOff + i * kPRowB + (h << 4);                         // + 32 rbp rows, + 32 ks
+    LDS_PTR(float) xm = (LDS_PTR(float))(lds + kXmOff);
+    LDS_PTR(float) cf = (LDS_PTR(float))(lds + kCfOff);
+    LDS_PTR(float) xl = (LDS_PTR(float))(lds + kXlOff);
+    LDS_PTR(float) mf = (LDS_PTR(float))(lds + kMfOff);
+
+    f32x16 o[4][2];  // [32 value columns 128w + 32db ..][row block]
+#pragma unroll
+    for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int rbp = 0; rbp < 2; ++rbp)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][rbp][r] = 0.0f;
+    float m = -INFINITY, lsum = 0.0f;  // of the S-phase row, lsum over this wave's key block only
+    const float c = a.c_log2e;
+    // this row's visible keys [lo, hi], and whether a tile can meet a band edge of any row
+    const int lo = sqi - wl, hi = (sqi + wr) < (ke - 1) ? (sqi + wr) : (ke - 1);
+    const int lo_max = N_q - 1 - wl, hi_min = wr < (ke - 1) ? wr : (ke - 1);
+
+    if (nt > 0) {
+        stage_load(0);
+        stage_write();
+    }
+    __syncthreads();
+
+    for (int t = 0; t < nt; ++t) {
+        const bool more = t + 1 < nt;
+        if (more) stage_load(t + 1);
+        const int tk0 = kb0 + t * kBC;
+
+        // ---- S^T = K . Q^T: this wave's 32 keys x 32 rows
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < kKS; ++ks) {
+            const u32x4 kf = *(LDS_PTR(u32x4))(lds + k_row * kRowB + (((2 * ks + h) ^ k_swz) << 4));
+            s = M::mfma(__builtin_bit_cast(frag, kf), qf[ks], s);
+        }
+        // ---- band and tail mask, selected: key(r) = tk0 + 32kb + 4h + (r & 3) + 8 (r >> 2)
+        if (tk0 < lo_max || tk0 + kBC - 1 > hi_min) {
+            const int kl = lo - (tk0 + 32 * kb + 4 * h), kh = hi - (tk0 + 32 * kb + 4 * h);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = (r & 3) + 8 * (r >> 2);
+                if (key < kl || key > kh) s[r] = -INFINITY;
+            }
+        }
+        // ---- the row's maximum over the 64 keys: this key block's, then the other wave's through LDS
+        float mx = s[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        if (h == 0) xm[kb * 64 + 32 * rb + i] = mx;
+        __syncthreads();
+        mx = fmaxf(mx, xm[(kb ^ 1) * 64 + 32 * rb + i]);
+        // ---- online softmax.  While a row's maximum is -inf (no visible key so far) P and the rescale factor are 0.
+        const float m_new = fmaxf(m, mx * c);
+        const float m_use = m_new == -INFINITY ? 0.0f : m_new;
+        const float coeff = __builtin_amdgcn_exp2f(m - m_use);
+        m = m_new;
+        float rs = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c, -m_use));
+            s[r] = p;
+            rs += p;
+        }
+        lsum = lsum * coeff + rs;
+        // registers 8ss .. 8ss + 7 are the B fragment of k-step 2kb + ss for this row, half h
+#pragma unroll
+        for (int ss = 0; ss < 2; ++ss) {
+            frag pf;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pf[j] = (T)s[8 * ss + j];  // RTNE
+            *(LDS_PTR(u32x4))(lds + p_wr + 32 * ss) = __builtin_bit_cast(u32x4, pf);
+        }
+        if (kb == 0 && h == 0) cf[32 * rb + i] = coeff;
+        __syncthreads();
+
+        // ---- O^T += V^T . P^T over this wave's 128 value columns, both row blocks
+        {
+            const float c0 = cf[i], c1 = cf[32 + i];
+            if (__any(c0 != 1.0f || c1 != 1.0f)) {
+#pragma unroll
+                for (int db = 0; db < 4; ++db)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        o[db][0][r] *= c0;
+                        o[db][1][r] *= c1;
+                    }
+            }
+        }
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const frag p0 = __builtin_bit_cast(frag, *(LDS_PTR(u32x4))(lds + p_rd + 32 * ks));
+            const frag p1 = __builtin_bit_cast(frag, *(LDS_PTR(u32x4))(lds + p_rd + 32 * kPRowB + 32 * ks));
+#pragma unroll
+            for (int db = 0; db < 4; ++db) {
+                const s16x4 vlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + ks * 16 * kRowB + v_off[0][db]));
+                const s16x4 vhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + ks * 16 * kRowB + v_off[1][db]));
+                const frag vf = __builtin_bit_cast(frag, (s16x8)__builtin_shufflevector(vlo, vhi, 0, 1, 2, 3, 4, 5, 6, 7));
+                o[db][0] = M::mfma(vf, p0, o[db][0]);
+                o[db][1] = M::mfma(vf, p1, o[db][1]);
+            }
+        }
+        __syncthreads();  // every read of this step's tile and of P has retired
+        if (more) stage_write();
+        __syncthreads();
+    }
+
+    // ---- the rows' sums and maxima to the P.V lanes
+    {
+        const float lw = lsum + __shfl_xor(lsum, 32, 64);
+        if (h == 0) {
+            xl[kb * 64 + 32 * rb + i] = lw;
+            if (kb == 0) mf[32 * rb + i] = m;
+        }
+    }
+    __syncthreads();
+
+    // ---- epilogue.  Lane (i, h) owns rows 32rbp + i of the tile, columns 128w + 32db + 8g + 4h .. +3 for g = 0..3.
+#pragma unroll
+    for (int rbp = 0; rbp < 2; ++rbp) {
+        const int row = rt * 64 + 32 * rbp + i;
+        if (row >= R) continue;
+        const int hg = row / N_q;
+        const int qi = row - hg * N_q;
+        const int head = hk * a.g + hg;
+        const float l = xl[32 * rbp + i] + xl[64 + 32 * rbp + i];
+        const float mr = mf[32 * rbp + i];
+        const bool seen = l > 0.0f;
+        const float inv = seen ? 1.0f / l : 0.0f;
+        if (a.num_splits == 1) {
+            char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)qi * a.os[2] + (128 * wave + 4 * h) * 2;
+#pragma unroll
+            for (int db = 0; db < 4; ++db)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    typedef __attribute__((ext_vector_type(4))) T Tx4;
+                    Tx4 v;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = (T)(o[db][rbp][4 * g + j] * inv);
+                    *(u32x2 *)(op + db * 64 + g * 16) = __builtin_bit_cast(u32x2, v);
+                }
+            if (wave == 0 && h == 0) {
+                T *lp = (T *)a.L + b * a.ls[0] + head * a.ls[1] + qi;
+                *lp = seen ? (T)(mr + __builtin_amdgcn_logf(l)) : (T)INFINITY;
+            }
+        } else {
+            const int64_t rows = (int64_t)gridDim.z * a.H * N_q;
+            const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + head) * N_q + qi;
+            float *op = a.o_part + prow * kDV + 128 * wave + 4 * h;
+#pragma unroll
+            for (int db = 0; db < 4; ++db)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 v;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = o[db][rbp][4 * g + j] * inv;
+                    *(f32x4 *)(op + db * 32 + g * 8) = v;
+                }
+            if (wave == 0 && h == 0) a.l_part[prow] = seen ? mr + __builtin_amdgcn_logf(l) : -INFINITY;
+        }
+    }
+}
+
+template <typename T, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
+    const long long gx = (long long)p.num_splits * a.row_tiles;
+    if (gx > 0x7fffffffLL) {
+        fa2_set_error("kvcache mla16 kernel: grid too large (num_splits * row tiles = %lld)", gx);
+        return FA2_ERR_BAD_ARG;
+    }
+    static Fa2DeviceLatch attr_done;  // more than 64 KiB of dynamic LDS: opt in, once per device
+    if (attr_done.need()) {
+        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, PAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
+        attr_done.mark();
+    }
+    const dim3 grid((unsigned)gx, p.H_kv, p.B), block(256);
+    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, PAGED>), grid, block, kSmem, p.stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fa2_set_error("kvcache mla16 kernel launch failed: %s", hipGetErrorString(e));
+        return FA2_ERR_LAUNCH;
+    }
+    return FA2_OK;
+}
+
+template <typename T> int launch_p(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
+    return p.table ? launch_t<T, true>(p, a) : launch_t<T, false>(p, a);
+}
+
+bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
+
+}  // namespace
+
+bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p) {
+    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || p.kv_dtype != p.dtype || p.cu_q) return false;
+    if (p.V != p.K) return false;  // the value operand is read from K's LDS image
+    for (int k = 0; k < 4; ++k)
+        if (p.vs[k] != p.ks[k]) return false;
+    if (!(p.scale > 0.0f) || !(p.scale < INFINITY)) return false;
+    if ((int64_t)(p.H / p.H_kv) * p.N_q > (1 << 24)) return false;  // (rows of a KV group are counted in 32 bits)
+    if (p.qs[3] != 1 || p.ks[3] != 1 || p.os[3] != 1) return false;
+    // 16-byte vector loads of Q and K rows, 8-byte stores of O: every row start must stay aligned
+    for (int k = 0; k < 3; ++k)
+        if ((p.qs[k] & 7) || (p.ks[k] & 7) || (p.os[k] & 7)) return false;
+    if (!aligned16(p.Q) || !aligned16(p.K) || !aligned16(p.O)) return false;
+    if (p.num_splits > 1 && !aligned16(p.o_part)) return false;
+    // paged: a 64-key tile must lie inside one page; the block stride is ks[0] above
+    if (p.table && p.page_size % FA2_KVCACHE_KEY_TILE != 0) return false;
+    return true;
+}
+
+int fa2_launch_decode_mla16(const Fa2DecodeProblem &p) {
+    if (!fa2_decode_mla16_supports(p)) {
+        fa2_set_error("kvcache mla16 kernel: needs f16/bf16, d = 576 and d_v = 512, V aliasing K (the same pointer and strides), unit "
+                      "d-stride, 16-byte aligned rows (and workspace), scale > 0%s",
+                      p.table ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
+        return FA2_ERR_UNSUPPORTED;
+    }
+    DecodeMlaArgs a;
+    a.Q = (const char *)p.Q; a.K = (const char *)p.K;
+    a.O = (char *)p.O; a.L = (char *)p.L;
+    for (int k = 0; k < 3; ++k) { a.qs[k] = p.qs[k] * 2; a.ks[k] = p.ks[k] * 2; a.os[k] = p.os[k] * 2; }
+    a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
+    a.seqlens = p.seqlens;
+    a.H = p.H; a.g = p.H / p.H_kv; a.N_q = p.N_q; a.S_k = p.S_k; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
+    a.num_splits = p.num_splits;
+    a.row_tiles = (int)(((int64_t)a.g * p.N_q + 63) / 64);
+    a.o_part = p.o_part; a.l_part = p.l_part;
+    a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
+    a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
+    return p.dtype == FA2_DTYPE_BF16 ? launch_p<__bf16>(p, a) : launch_p<_Float16>(p, a);
+}

@@ -428,7 +428,20 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     are dropped).  cache_seqlens is required and not modified.  rotary_cos, rotary_sin (S_rot, rotary_dim / 2) in Q's dtype with unit
     last stride rotate K token t at position cache_seqlens[b] + t and Q (a copy: Q itself is not modified) at cache_seqlens[b] + i for
     row i when the call is causal or windowed, every row at cache_seqlens[b] otherwise, as flash-attn does; apply_rotary is the
-    arithmetic, bit for bit.  They need k_new / v_new."""
+    arithmetic, bit for bit.  They need k_new / v_new.
+
+    Value head size d_v != d (fa2_fwd_kvcache_mla): a V_cache whose LAST axis differs from K_cache's, all other axes equal --
+    V_cache (B, H_kv, S_k, d_v) or a pool (num_blocks, H_kv, page_size, d_v) -- with d in [1, 576] and d_v in [1, 512]; O is
+    (B, H, N_q, d_v).  V_cache may be a view of K_cache: multi-head latent attention in its absorbed form is H_kv = 1, d = 576 and
+    V_cache = K_cache[..., :512] (flash_attention_mla_decode_forward passes exactly that).  variant is then one of
+    _lib.KVCACHE_MLA_VARIANTS: "mla16" (f16 / bf16, d = 576, d_v = 512, V_cache that view of K_cache, unit d-stride and 16-byte
+    aligned rows, contiguous or paged with page_size % 64 == 0), "generic" (everything else), "auto".  Out of scope with d_v != d,
+    each a ValueError: an fp8 cache, k_descale / v_descale, k_new / v_new (MLA rotates the last 64 columns and writes ONE tensor:
+    kvcache_append does neither) and the rotary arguments; so is flash_attention_varlen_kvcache_forward."""
+    if isinstance(K_cache, torch.Tensor) and isinstance(V_cache, torch.Tensor) and K_cache.dim() == 4 and V_cache.dim() == 4 \
+            and K_cache.shape[:3] == V_cache.shape[:3] and K_cache.shape[3] != V_cache.shape[3]:
+        return _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale, window, num_splits, variant, k_descale,
+                                    v_descale, block_table, k_new, v_new, rotary_cos, rotary_sin)
     check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k_descale, v_descale, block_table)
     check_kvcache_append_args(K_cache, V_cache, k_new, v_new, cache_seqlens, k_descale, v_descale, block_table, rotary_cos, rotary_sin,
                               Q)
@@ -472,6 +485,56 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     _lib.fa2_fwd_kvcache(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, causal=causal, scale=scale, window=window, num_splits=n,
                          workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
     return O, L
+
+
+def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale, window, num_splits, variant, k_descale, v_descale,
+                         block_table, k_new, v_new, rotary_cos, rotary_sin):
+    """flash_attention_kvcache_forward with a V_cache whose last axis differs from K_cache's (fa2_fwd_kvcache_mla)."""
+    if K_cache.dtype in FP8_CACHE_DTYPES or V_cache.dtype in FP8_CACHE_DTYPES:
+        raise ValueError(f"kvcache: an fp8 K_cache / V_cache ({K_cache.dtype}) is not supported with d_v != d")
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale), ("k_new", k_new), ("v_new", v_new), ("rotary_cos", rotary_cos),
+                    ("rotary_sin", rotary_sin)):
+        if t is not None:
+            raise ValueError(f"kvcache: {name} is not supported with d_v != d (V_cache {tuple(V_cache.shape)} under K_cache "
+                             f"{tuple(K_cache.shape)})")
+    check_kvcache_args(Q, K_cache, K_cache, cache_seqlens, window, num_splits, None, None, block_table)
+    if V_cache.dtype != K_cache.dtype:
+        raise ValueError("kvcache: K_cache and V_cache must have the same dtype")
+    d, d_v = K_cache.shape[3], V_cache.shape[3]
+    if not 1 <= d <= 576 or not 1 <= d_v <= 512:
+        raise ValueError(f"kvcache: with d_v != d, d must be in [1, 576] and d_v in [1, 512], got d = {d}, d_v = {d_v}")
+    if variant not in _lib.KVCACHE_MLA_VARIANTS:
+        raise ValueError(f"kvcache: with d_v != d, variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
+    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
+        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+    B, H, N_q, _ = Q.shape
+    H_kv = K_cache.shape[1]
+    dtype = convert_triton_dtype(Q.dtype)
+    O = torch.empty(B, H, N_q, d_v, dtype=Q.dtype, device=Q.device)
+    L = torch.empty(B, H, N_q, dtype=Q.dtype, device=Q.device)
+    S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
+    n = num_splits or _lib.kvcache_mla_num_splits(B, H, H_kv, N_q, S_k, d, d_v, dtype)
+    ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    _lib.fa2_fwd_kvcache_mla(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, block_table=block_table, causal=causal, scale=scale,
+                             window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+    return O, L
+
+
+def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=512, causal=False, scale=1.0, window=None, num_splits=0,
+                                       variant="auto", block_table=None):
+    """Multi-head latent attention decode, absorbed form, over the shared latent cache (fa2_fwd_kvcache_mla) -> (O, L).  Q
+    (B, H, N_q, d); KV_cache (B, H_kv, S_k, d) or, with block_table, the page pool (num_blocks, H_kv, page_size, d): one row per key,
+    d_v latent columns followed by the rotary ones (DeepSeek-V2 / V3 / R1, Kimi: H_kv = 1, d = 576, d_v = 512).  The score takes all
+    d columns, the value is the first d_v of the same row: the call is flash_attention_kvcache_forward(Q, KV_cache,
+    KV_cache[..., :d_v], ...) bit for bit, and every other argument is that function's.  O (B, H, N_q, d_v).  1 <= d_v < d.  The
+    cache is only read: the latent row of a new token (its last d - d_v columns rotated) is written by the caller, and an fp8
+    latent cache, the append and rotary arguments and packed queries are not supported."""
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
+        raise ValueError("mla decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < KV_cache.shape[3]:
+        raise ValueError(f"mla decode: d_v must be an int in [1, d - 1] = [1, {KV_cache.shape[3] - 1}], got {d_v!r}")
+    return flash_attention_kvcache_forward(Q, KV_cache, KV_cache[..., :d_v], cache_seqlens, dev, causal=causal, scale=scale,
+                                           window=window, num_splits=num_splits, variant=variant, block_table=block_table)
 
 
 def check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale=None,

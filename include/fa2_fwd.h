@@ -345,6 +345,53 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
                           void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
 /*
+ * Decode over a cache whose VALUE head size differs from the key's, and whose value may be a view of the key: multi-head latent
+ * attention (MLA, DeepSeek-V2 / V3 / R1, Kimi) in its absorbed form, where every query head of a token attends over ONE shared
+ * latent row per key -- 512 latent columns followed by 64 rotary columns; the score takes all 576, the value is the first 512 of
+ * the same row: H_kv = 1, d = 576, d_v = 512, V = K[..., :512].  Forward only.
+ *
+ *   Shapes.   Q is (B, H, N_q, d), K (B, H_kv, S_k, d), V (B, H_kv, S_k, d_v), O (B, H, N_q, d_v), L (B, H, N_q); d in [1, 576], d_v in
+ *             [1, 512].  V may overlap K in memory: neither is written.  Everything else is fa2_fwd_kvcache's, unchanged: lengths
+ *             and clamping, the bottom-right mask and window, empty rows (O = 0, L = +inf), the split rule, fp32 partials and the
+ *             combine launch, L in the log2 domain.
+ *   Cache.    block_table non-null: fa2_fwd_kvcache_paged's pool (num_blocks, H_kv, page_size, d) / (..., d_v), table and capacity
+ *             max_blocks * page_size.  block_table null: the contiguous cache, a pool of one page per sequence -- page_size
+ *             carries S_k, strides[0] is the batch stride, and num_blocks, max_blocks and block_table_stride are not read.
+ *   Dtypes.   f16, bf16, f32, f64 (dtype_enum, the cache alike); no fp8 cache, no descales.
+ *   Splits.   The workspace is fa2_kvcache_workspace_bytes(B, H, N_q, d_v, num_splits): the partials have d_v columns.
+ *             num_splits = 0 resolves to fa2_kvcache_mla_num_splits(...).
+ *   Variants. FA2_KVCACHE_VARIANT_MLA16 (this entry point only): f16 / bf16, d = 576 and d_v = 512, V aliasing K (the same base
+ *             pointer, the same four strides), unit d-stride, 16-byte aligned rows (and workspace), scale > 0, any H_kv and any
+ *             (H / H_kv) * N_q, contiguous or paged with page_size % 64 == 0.  One workgroup per 64 rows of a KV group stages each
+ *             64-key tile of the latent cache once and reads the value operand from the same LDS image.
+ *             FA2_KVCACHE_VARIANT_GENERIC: everything else (every dtype, any strides, any page size, a V that is a tensor of its
+ *             own).  FA2_KVCACHE_VARIANT_AUTO: MLA16 where it runs, else GENERIC.  A forced MLA16 on a problem it cannot run
+ *             returns FA2_ERR_UNSUPPORTED; FA2_KVCACHE_VARIANT_MFMA16 is not a variant of this call.
+ *
+ * Every FA2_ERR_BAD_ARG and FA2_ERR_UNSUPPORTED of fa2_fwd_kvcache_paged applies (with block_table null: S_k = page_size in the
+ * capacity's place, no table errors), the message naming the argument; FA2_ERR_UNSUPPORTED also for d outside [1, 576] and d_v outside
+ * [1, 512].  Not covered (use the d_v == d entry points): an fp8 latent cache, the append calls and rotary, packed queries.
+ */
+#define FA2_KVCACHE_VARIANT_MLA16 3
+
+int fa2_fwd_kvcache_mla(const void *Q, const void *K, const void *V, void *O, void *L,
+                        const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                        const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                        const int32_t *block_table, int64_t block_table_stride,
+                        int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                        int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                        int32_t dtype_enum,
+                        int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                        void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* What num_splits = 0 resolves to for fa2_fwd_kvcache_mla, in [1, FA2_KVCACHE_MAX_SPLITS]: for f16 / bf16 at d = 576, d_v = 512 (the
+ * matrix form, one workgroup per CU) the unsplit launch has B * H_kv * ceil((H / H_kv) * N_q / 64) workgroups; 1 when that is 256
+ * or more, else enough splits for one workgroup per CU, every split at least 4 key tiles (256 keys) of the capacity S_k.  Any
+ * other shape is counted as fa2_kvcache_num_splits counts the VALU form. */
+int32_t fa2_kvcache_mla_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t d_v,
+                                   int32_t dtype_enum);
+
+/*
  * Variable-length (packed) queries over the KV cache: every sequence brings its own number of query tokens -- a chunk of a prompt
  * over its cached prefix (chunked prefill, prefix caching), the draft tokens of speculative decoding, one decode token -- in one
  * call (flash-attn's flash_attn_varlen_func(..., block_table=)).  Forward only.  The keys of a chunk's own tokens are already in
