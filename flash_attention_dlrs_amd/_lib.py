@@ -412,6 +412,44 @@ def fa2_bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_q, cu_k, max_q, max_k, d
         _raise(rc)
 
 
+def _window_sides(window):
+    if window is None:
+        return -1, -1
+    wl, wr = window
+    return int(wl), int(wr)
+
+
+def _workspace_args(workspace):
+    """(pointer, size in bytes) of the split workspace, (None, 0) without one."""
+    return (None, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
+
+
+def _descale_args(k_descale, v_descale):
+    """(k pointer, v pointer, k strides, v strides) of the fp8 descales, None where one is not given."""
+    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
+    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
+    return kd_ptr, vd_ptr, kd_st, vd_st
+
+
+def _table_args(K, block_table):
+    """(table pointer, row stride, S_k, num_blocks, page_size, max_blocks): S_k of the contiguous cache K, or the pool K's sizes."""
+    if block_table is None:
+        return None, 0, K.shape[2], 0, 0, 0
+    return block_table.data_ptr(), block_table.stride(0), 0, K.shape[0], K.shape[2], block_table.shape[1]
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _launch(fn, anchor, *args):
+    """Call the entry point fn, args in the header's order, with anchor's device current; raise what it refuses."""
+    with torch.cuda.device(anchor.device.index):  # (the index: the context is built from it faster than from the torch.device)
+        rc = fn(*args)
+    if rc != 0:
+        _raise(rc)
+
+
 def kvcache_num_splits(B, H, H_kv, N_q, S_k, d, dtype_enum):
     """What num_splits = 0 resolves to for a decode call of this shape (fa2_kvcache_num_splits): a host heuristic on the capacity."""
     return int(lib().fa2_kvcache_num_splits(B, H, H_kv, N_q, S_k, d, int(dtype_enum)))
@@ -431,17 +469,12 @@ def fa2_fwd_kvcache(Q, K, V, O, L, cache_seqlens, dtype_enum, causal=False, scal
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N_q, d = Q.shape
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_variant(
+    _launch(lib().fa2_fwd_kvcache_variant, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
             None if cache_seqlens is None else cache_seqlens.data_ptr(), B, H, K.shape[1], N_q, K.shape[2], d, int(dtype_enum),
-            int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, _raw_stream(Q.device.index), int(variant))
-    if rc != 0:
-        _raise(rc)
+            int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
+            _raw_stream(Q.device.index), int(variant))
 
 
 def fa2_fwd_kvcache_fp8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_enum, k_descale=None, v_descale=None, causal=False, scale=1.0,
@@ -452,20 +485,12 @@ def fa2_fwd_kvcache_fp8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_enum,
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N_q, d = Q.shape
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
-    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_fp8(
+    _launch(lib().fa2_fwd_kvcache_fp8, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
-            None if cache_seqlens is None else cache_seqlens.data_ptr(), kd_ptr, vd_ptr, kd_st, vd_st, B, H, K.shape[1], N_q,
-            K.shape[2], d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr,
-            ws_bytes, int(variant), _raw_stream(Q.device.index))
-    if rc != 0:
-        _raise(rc)
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), *_descale_args(k_descale, v_descale), B, H, K.shape[1], N_q, K.shape[2], d, int(dtype_enum),
+            int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
+            int(variant), _raw_stream(Q.device.index))
 
 
 def fa2_fwd_kvcache_paged(Q, K, V, O, L, block_table, cache_seqlens, dtype_enum, kv_dtype_enum, k_descale=None, v_descale=None,
@@ -477,21 +502,13 @@ def fa2_fwd_kvcache_paged(Q, K, V, O, L, block_table, cache_seqlens, dtype_enum,
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N_q, d = Q.shape
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
-    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_paged(
+    _launch(lib().fa2_fwd_kvcache_paged, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
-            None if cache_seqlens is None else cache_seqlens.data_ptr(), block_table.data_ptr(), block_table.stride(0),
-            kd_ptr, vd_ptr, kd_st, vd_st, B, H, K.shape[1], N_q, K.shape[0], K.shape[2], block_table.shape[1], d,
-            int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), block_table.data_ptr(), block_table.stride(0), *_descale_args(k_descale, v_descale),
+            B, H, K.shape[1], N_q, K.shape[0], K.shape[2], block_table.shape[1], d, int(dtype_enum), int(kv_dtype_enum),
+            int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
             int(variant), _raw_stream(Q.device.index))
-    if rc != 0:
-        _raise(rc)
 
 
 def kvcache_mla_num_splits(B, H, H_kv, N_q, S_k, d, d_v, dtype_enum):
@@ -508,35 +525,23 @@ def fa2_fwd_kvcache_mla(Q, K, V, O, L, cache_seqlens, dtype_enum, block_table=No
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N_q, d = Q.shape
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    tb_ptr, tb_st, nb, mb = (None, 0, 0, 0) if block_table is None else \
-        (block_table.data_ptr(), block_table.stride(0), K.shape[0], block_table.shape[1])
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_mla(
+    tb_ptr, tb_st, _, nb, _, mb = _table_args(K, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
-            None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, B, H, K.shape[1], N_q, nb, K.shape[2], mb, d,
-            V.shape[3], int(dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, int(variant),
-            _raw_stream(Q.device.index))
-    if rc != 0:
-        _raise(rc)
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, B, H, K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum),
+            int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
+            int(variant), _raw_stream(Q.device.index))
 
 
 def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):
     """The pieces both append launchers pass alike: (table pointer, table stride, descale pointers and strides, rotary pointers,
     row strides, S_rot, rotary_dim, S_k, num_blocks, page_size, max_blocks)."""
-    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
-    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
-    cos_ptr, cos_st, S_rot, rd = (None, 0, 0, 0) if rotary_cos is None else \
-        (rotary_cos.data_ptr(), rotary_cos.stride(0), rotary_cos.shape[0], 2 * rotary_cos.shape[1])
-    sin_ptr, sin_st = (None, 0) if rotary_sin is None else (rotary_sin.data_ptr(), rotary_sin.stride(0))
-    if block_table is None:
-        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, K.shape[2], 0, 0, 0
-    else:
-        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, K.shape[0], K.shape[2], block_table.shape[1]
-    return tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb
+    tb_ptr, tb_st, S_k, nb, ps, mb = _table_args(K, block_table)
+    cos_st, S_rot, rd = (0, 0, 0) if rotary_cos is None else (rotary_cos.stride(0), rotary_cos.shape[0], 2 * rotary_cos.shape[1])
+    sin_st = 0 if rotary_sin is None else rotary_sin.stride(0)
+    return (tb_ptr, tb_st, *_descale_args(k_descale, v_descale), _ptr(rotary_cos), _ptr(rotary_sin), cos_st, sin_st, S_rot, rd, S_k, nb,
+            ps, mb)
 
 
 def fa2_kvcache_append(K, V, k_new, v_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None, k_descale=None,
@@ -552,16 +557,13 @@ def fa2_kvcache_append(K, V, k_new, v_new, cache_seqlens, seqlens_out, dtype_enu
     B, H_kv, N_new, d = k_new.shape
     tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
         _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
-    q_ptr, q_st, H, N_q = (None, None, 0, 0) if Q is None else (Q.data_ptr(), _i64(Q.stride()), Q.shape[1], Q.shape[2])
-    with torch.cuda.device(k_new.device):
-        rc = lib().fa2_kvcache_append(
+    q_st, H, N_q = (None, 0, 0) if Q is None else (_i64(Q.stride()), Q.shape[1], Q.shape[2])
+    _launch(lib().fa2_kvcache_append, k_new,
             K.data_ptr(), V.data_ptr(), _i64(K.stride()), _i64(V.stride()), tb_ptr, tb_st, k_new.data_ptr(), v_new.data_ptr(),
             _i64(k_new.stride()), _i64(v_new.stride()), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), kd_ptr, vd_ptr, kd_st, vd_st,
-            cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), q_ptr, None if q_rot is None else q_rot.data_ptr(),
-            q_st, H, N_q, int(bool(q_pos_per_row)), B, H_kv, N_new, S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum),
+            cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), _ptr(Q), _ptr(q_rot), q_st, H, N_q,
+            int(bool(q_pos_per_row)), B, H_kv, N_new, S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum),
             _raw_stream(k_new.device.index))
-    if rc != 0:
-        _raise(rc)
 
 
 def fa2_fwd_kvcache_append(Q, K, V, O, L, k_new, v_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,
@@ -573,22 +575,16 @@ def fa2_fwd_kvcache_append(Q, K, V, O, L, k_new, v_new, cache_seqlens, seqlens_o
     if Q.device.type != "cuda":
         raise NotImplementedError("Q, K, V must be on the same CUDA device")
     B, H, N_q, d = Q.shape
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
     tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
         _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_append(
+    _launch(lib().fa2_fwd_kvcache_append, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
             cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, k_new.data_ptr(),
             v_new.data_ptr(), _i64(k_new.stride()), _i64(v_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd,
-            int(bool(rotary_interleaved)), None if q_rot is None else q_rot.data_ptr(), B, H, K.shape[1], N_q, k_new.shape[2], S_k, nb,
-            ps, mb, d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes,
+            int(bool(rotary_interleaved)), _ptr(q_rot), B, H, K.shape[1], N_q, k_new.shape[2], S_k, nb, ps, mb, d, int(dtype_enum),
+            int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
             int(variant), _raw_stream(Q.device.index))
-    if rc != 0:
-        _raise(rc)
 
 
 def kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype_enum):
@@ -612,24 +608,14 @@ def fa2_fwd_kvcache_varlen(Q, K, V, O, L, cu_q, max_q, cache_seqlens, dtype_enum
     if L.dim() != 2 or L.shape != (H, total_q) or (total_q > 1 and L.stride(1) != 1):  # the ABI takes the head stride alone
         raise ValueError(f"fa2_fwd_kvcache_varlen: L must be (H, total_q) = ({H}, {total_q}) with unit token stride, got "
                          f"{tuple(L.shape)} with strides {tuple(L.stride())}")
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    kd_ptr, kd_st = (None, None) if k_descale is None else (k_descale.data_ptr(), _i64(k_descale.stride()))
-    vd_ptr, vd_st = (None, None) if v_descale is None else (v_descale.data_ptr(), _i64(v_descale.stride()))
-    if block_table is None:
-        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, K.shape[2], 0, 0, 0
-    else:
-        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, K.shape[0], K.shape[2], block_table.shape[1]
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_varlen(
+    tb_ptr, tb_st, S_k, nb, ps, mb = _table_args(K, block_table)
+    _launch(lib().fa2_fwd_kvcache_varlen, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
-            cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st,
+            cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, *_descale_args(k_descale, v_descale),
             cu_q.numel() - 1, H, K.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum),
-            int(bool(causal)), float(scale), wl, wr, int(num_splits), ws_ptr, ws_bytes, int(variant), _raw_stream(Q.device.index))
-    if rc != 0:
-        _raise(rc)
+            int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
+            int(variant), _raw_stream(Q.device.index))
 
 
 def fa2_kvcache_append_varlen(K, V, k_new, v_new, cu_new, max_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,
@@ -645,16 +631,13 @@ def fa2_kvcache_append_varlen(K, V, k_new, v_new, cu_new, max_new, cache_seqlens
     total_new, H_kv, d = k_new.shape
     tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
         _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
-    q_ptr, q_st, H = (None, None, 0) if Q is None else (Q.data_ptr(), _i64(Q.stride()), Q.shape[1])
-    with torch.cuda.device(k_new.device):
-        rc = lib().fa2_kvcache_append_varlen(
+    q_st, H = (None, 0) if Q is None else (_i64(Q.stride()), Q.shape[1])
+    _launch(lib().fa2_kvcache_append_varlen, k_new,
             K.data_ptr(), V.data_ptr(), _i64(K.stride()), _i64(V.stride()), tb_ptr, tb_st, k_new.data_ptr(), v_new.data_ptr(),
             _i64(k_new.stride()), _i64(v_new.stride()), cu_new.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), kd_ptr,
-            vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), q_ptr,
-            None if q_rot is None else q_rot.data_ptr(), q_st, H, int(bool(q_pos_per_row)), cu_new.numel() - 1, H_kv, total_new,
-            int(max_new), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum), _raw_stream(k_new.device.index))
-    if rc != 0:
-        _raise(rc)
+            vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), _ptr(Q), _ptr(q_rot),
+            q_st, H, int(bool(q_pos_per_row)), cu_new.numel() - 1, H_kv, total_new, int(max_new), S_k, nb, ps, mb, d, int(dtype_enum),
+            int(kv_dtype_enum), _raw_stream(k_new.device.index))
 
 
 def fa2_fwd_kvcache_varlen_append(Q, K, V, O, L, k_new, v_new, cu_q, max_q, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum,
@@ -670,19 +653,13 @@ def fa2_fwd_kvcache_varlen_append(Q, K, V, O, L, k_new, v_new, cu_q, max_q, cach
     if L.dim() != 2 or L.shape != (H, total_q) or (total_q > 1 and L.stride(1) != 1):  # the ABI takes the head stride alone
         raise ValueError(f"fa2_fwd_kvcache_varlen_append: L must be (H, total_q) = ({H}, {total_q}) with unit token stride, got "
                          f"{tuple(L.shape)} with strides {tuple(L.stride())}")
-    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
-    ws_ptr = None if workspace is None else workspace.data_ptr()
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
     tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
         _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin)
-    with torch.cuda.device(Q.device):
-        rc = lib().fa2_fwd_kvcache_varlen_append(
+    _launch(lib().fa2_fwd_kvcache_varlen_append, Q,
             Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
             cu_q.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st,
             k_new.data_ptr(), v_new.data_ptr(), _i64(k_new.stride()), _i64(v_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd,
-            int(bool(rotary_interleaved)), None if q_rot is None else q_rot.data_ptr(), cu_q.numel() - 1, H, K.shape[1], total_q,
-            int(max_q), S_k, nb, ps, mb, d, int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), wl, wr,
-            int(num_splits), ws_ptr, ws_bytes, int(variant), _raw_stream(Q.device.index))
-    if rc != 0:
-        _raise(rc)
+            int(bool(rotary_interleaved)), _ptr(q_rot), cu_q.numel() - 1, H, K.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d,
+            int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits),
+            *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))

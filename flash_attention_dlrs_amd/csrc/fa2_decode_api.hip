@@ -1,296 +1,340 @@
-// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, fa2_fwd_kvcache_fp8,
-// fa2_fwd_kvcache_paged, the latent-cache call fa2_fwd_kvcache_mla, the packed-query call fa2_fwd_kvcache_varlen, the cache appends fa2_kvcache_append and fa2_kvcache_append_varlen,
-// the fused steps fa2_fwd_kvcache_append and fa2_fwd_kvcache_varlen_append, and their helpers, declared in
-// include/fa2_fwd.h): argument checks before any launch, the split heuristic, the choice between the two kernel forms, and the
-// launches (the append where asked for, the split kernels, then the combine) on the caller's stream.
+// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache call
+// _mla, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps fa2_fwd_kvcache_append
+// and _varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
+//   1. fill   the entry point names its raw arguments in a DecodeCall (the cache update's in an AppendCall), packed strides through packed4;
+//   2. check  check_decode (check_append) tests every argument, resolves num_splits (split_count on the unsplit workgroup count of the
+//             call's form) and fills the Fa2DecodeProblem (Fa2AppendProblem); nothing is launched;
+//   3. run    run_decode takes the call's row of kForms (fixed, packed, MLA) and launches, on the caller's stream, the append of a fused
+//             step, the split kernel, then the combine.  A fused step runs all of check_append before any check of the attention.
 #include "fa2_decode.h"
 
 namespace {
 
-// fa2_kvcache_num_splits: enough splits to put kSplitWaves x 256 workgroups on the chip, every split at least kMinSplitTiles key
-// tiles long (judged on the capacity: the lengths live on the device).  `base` is the workgroup count of the unsplit launch of
-// the form AUTO takes for the shape: B * H_kv for the matrix form, B * H * ceil(N_q / 16) for the VALU form.  The constants are
-// read off the num_splits sweep of benchmarks/bench_decode.py ("Decode attention").
+// The split rule: enough splits to put `waves` x 256 workgroups on the chip, every split at least `min_tiles` key tiles long
+// (judged on the capacity: the lengths live on the device).  `base` is the workgroup count of the unsplit launch of the form AUTO
+// takes for the shape; the three heuristics below differ in how they count it and in the two constants.
 constexpr int kChipWorkgroups = 256;  // one per CU
-constexpr int kSplitWaves = 2;
-constexpr int kMinSplitTiles = 4;
 constexpr int64_t kMaxRows = 1LL << 40;  // B * H * N_q beyond this is refused: the workspace size stays far inside int64
 
-int num_splits_auto(int64_t B, int64_t H, int64_t H_kv, int64_t N_q, int64_t S_k, int32_t d, int32_t dtype) {
-    const int64_t base = fa2_decode_mfma16_shape((int32_t)H, (int32_t)H_kv, (int32_t)N_q, d, dtype) ? B * H_kv
-                                                                                                     : B * H * ((N_q + 15) / 16);
+int split_count(int64_t base, int64_t S_k, int waves, int min_tiles) {
     if (base >= kChipWorkgroups) return 1;
-    int64_t n = (kSplitWaves * kChipWorkgroups + base - 1) / base;
-    const int64_t tiles = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE;
-    const int64_t cap = tiles / kMinSplitTiles;
+    int64_t n = (waves * kChipWorkgroups + base - 1) / base;
+    const int64_t cap = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE / min_tiles;
     if (n > cap) n = cap;
     if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
     return n < 1 ? 1 : (int)n;
 }
 
-// fa2_kvcache_mla_num_splits: the same rule for fa2_fwd_kvcache_mla.  The latent matrix form (fa2_decode_mla16.hip) runs ONE
-// workgroup per CU (its LDS tile and registers fill it), B * H_kv * ceil(g N_q / 64) of them unsplit, so one wave of the chip is
-// what the splits fill (kMlaSplitWaves), and a split is at least kMlaMinSplitTiles 64-key tiles long: each workgroup loads its
-// 64 x 576 Q fragments and writes 64 x 512 fp32 partials whatever its length.  The constants are read off the split sweep of
-// benchmarks/bench_mla_decode.py ("MLA decode").  Every other shape is counted as the VALU form's.
+// The shape the heuristics judge: N_q is max_seqlen_q and total_q is read for packed queries only, d_v for the latent cache only.
+struct SplitShape {
+    int64_t B, H, H_kv, N_q, total_q, S_k;
+    int32_t d, d_v, dtype;
+};
+
+// fa2_kvcache_num_splits: base = B * H_kv for the matrix form, B * H * ceil(N_q / 16) for the VALU form.  The constants are read
+// off the num_splits sweep of benchmarks/bench_decode.py ("Decode attention").
+constexpr int kSplitWaves = 2;
+constexpr int kMinSplitTiles = 4;
+
+int num_splits_auto(const SplitShape &s) {
+    const bool mfma = fa2_decode_mfma16_shape((int32_t)s.H, (int32_t)s.H_kv, (int32_t)s.N_q, s.d, s.dtype);
+    return split_count(mfma ? s.B * s.H_kv : s.B * s.H * ((s.N_q + 15) / 16), s.S_k, kSplitWaves, kMinSplitTiles);
+}
+
+// fa2_kvcache_mla_num_splits: the latent matrix form (fa2_decode_mla16.hip) runs ONE workgroup per CU (its LDS tile and registers
+// fill it), base = B * H_kv * ceil(g N_q / 64) of them unsplit, so one wave of the chip is what the splits fill (kMlaSplitWaves),
+// and a split is at least kMlaMinSplitTiles 64-key tiles long: each workgroup loads its 64 x 576 Q fragments and writes 64 x 512
+// fp32 partials whatever its length.  The constants are read off the split sweep of benchmarks/bench_mla_decode.py (DESIGN.md,
+// "MLA decode").  Every other shape is counted as the VALU form's.
 constexpr int kMlaSplitWaves = 1;
 constexpr int kMlaMinSplitTiles = 4;
 
-int num_splits_mla(int64_t B, int64_t H, int64_t H_kv, int64_t N_q, int64_t S_k, int32_t d, int32_t d_v, int32_t dtype) {
-    if (!fa2_decode_mla16_shape(d, d_v, dtype) || H_kv < 1 || H % H_kv != 0) return num_splits_auto(B, H, H_kv, N_q, S_k, 0, dtype);
-    const int64_t base = B * H_kv * ((H / H_kv * N_q + 63) / 64);
-    if (base >= kChipWorkgroups) return 1;
-    int64_t n = (kMlaSplitWaves * kChipWorkgroups + base - 1) / base;
-    const int64_t cap = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE / kMlaMinSplitTiles;
-    if (n > cap) n = cap;
-    if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
-    return n < 1 ? 1 : (int)n;
+int num_splits_mla(const SplitShape &s) {
+    if (!fa2_decode_mla16_shape(s.d, s.d_v, s.dtype) || s.H_kv < 1 || s.H % s.H_kv != 0) {
+        SplitShape valu = s;
+        valu.d = 0;
+        return num_splits_auto(valu);
+    }
+    return split_count(s.B * s.H_kv * ((s.H / s.H_kv * s.N_q + 63) / 64), s.S_k, kMlaSplitWaves, kMlaMinSplitTiles);
 }
 
-int64_t workspace_bytes(int64_t B, int64_t H, int64_t N_q, int64_t d, int64_t num_splits) {
+// fa2_kvcache_varlen_num_splits: base is the unsplit workgroup count of the packed launch.  A sequence fills ceil(n_q(b) / tq)
+// query tiles, the lengths live on the device: the count is bounded by the grid, B * ceil(max_seqlen_q / tq), and by
+// ceil(total_q / tq) + B (every sequence ends in at most one partly filled tile), per KV head of the matrix form
+// (tq = min(64 / g, max_seqlen_q)), per query head of the VALU form (tq = 16).
+int num_splits_varlen(const SplitShape &s) {
+    const bool mfma = fa2_decode_mfma16_v_shape((int32_t)s.H, (int32_t)s.H_kv, s.d, s.dtype);
+    const int64_t tq = mfma ? fa2_decode_varlen_tq((int32_t)(s.H / s.H_kv), (int32_t)s.N_q) : 16;
+    const int64_t grid = s.B * ((s.N_q + tq - 1) / tq), packed = (s.total_q + tq - 1) / tq + s.B;
+    return split_count((mfma ? s.H_kv : s.H) * (grid < packed ? grid : packed), s.S_k, kSplitWaves, kMinSplitTiles);
+}
+
+// The fp32 workspace of a split call: o_part [num_splits][rows][d_v] then l_part [num_splits][rows], rows = B * H * N_q
+// (total_q * H for packed queries).
+int64_t workspace_bytes(int64_t rows, int64_t d_v, int64_t num_splits) {
     if (num_splits <= 1) return 0;
     if (num_splits > FA2_KVCACHE_MAX_SPLITS) num_splits = FA2_KVCACHE_MAX_SPLITS;
-    const int64_t rows = B * H * N_q;  // <= 2^16 * 2^16 * 2^28
-    if (rows > kMaxRows || d > 512) return INT64_MAX;  // (4 * 128 * 2^40 * 513 < 2^63)
-    return 4 * num_splits * rows * (d + 1);
+    if (rows > kMaxRows || d_v > 512) return INT64_MAX;  // (4 * 128 * 2^40 * 513 < 2^63)
+    return 4 * num_splits * rows * (d_v + 1);
 }
 
-// fa2_kvcache_varlen_num_splits: the same rule with the unsplit workgroup count of the packed launch in `base`'s place.  A
-// sequence fills ceil(n_q(b) / tq) query tiles, the lengths live on the device: the count is bounded by the grid,
-// B * ceil(max_seqlen_q / tq), and by ceil(total_q / tq) + B (every sequence ends in at most one partly filled tile), per KV
-// head of the matrix form (tq = min(64 / g, max_seqlen_q)), per query head of the VALU form (tq = 16).
-int num_splits_varlen(int64_t B, int64_t H, int64_t H_kv, int64_t total_q, int64_t max_q, int64_t S_k, int32_t d, int32_t dtype) {
-    const bool mfma = fa2_decode_mfma16_v_shape((int32_t)H, (int32_t)H_kv, d, dtype);
-    const int64_t tq = mfma ? fa2_decode_varlen_tq((int32_t)(H / H_kv), (int32_t)max_q) : 16;
-    const int64_t grid = B * ((max_q + tq - 1) / tq), packed = (total_q + tq - 1) / tq + B;
-    const int64_t base = (mfma ? H_kv : H) * (grid < packed ? grid : packed);
-    if (base >= kChipWorkgroups) return 1;
-    int64_t n = (kSplitWaves * kChipWorkgroups + base - 1) / base;
-    const int64_t cap = (S_k + FA2_KVCACHE_KEY_TILE - 1) / FA2_KVCACHE_KEY_TILE / kMinSplitTiles;
-    if (n > cap) n = cap;
-    if (n > FA2_KVCACHE_MAX_SPLITS) n = FA2_KVCACHE_MAX_SPLITS;
-    return n < 1 ? 1 : (int)n;
+// The arguments of an attention call as the entry points take them.  The strides are the fixed call's: {batch, head, token, d} and
+// {batch, head}; a packed entry point converts its own (packed4) and passes max_seqlen_q as N_q.
+struct DecodeCall {
+    const void *Q, *K, *V;
+    void *O, *L;
+    const int64_t *q_strides, *k_strides, *v_strides, *o_strides, *l_strides;
+    const int32_t *cache_seqlens;
+    int32_t B, H, H_kv, N_q, S_k, d, dtype_enum, causal, window_left, window_right, num_splits, variant;
+    float scale;
+    void *workspace, *hip_stream;
+    int64_t workspace_bytes;
+    // the optional parts, each behind its flag
+    const int32_t *block_table = nullptr;  // a paged cache: S_k is ignored and max_blocks * page_size takes its place
+    bool pool_only = false;                // fa2_fwd_kvcache_paged: a null block_table is refused, it is no contiguous cache
+    int64_t block_table_stride = 0;
+    int32_t num_blocks = 0, page_size = 0, max_blocks = 0;
+    bool fp8 = false;  // an fp8 cache in kv_dtype_enum with its descales; without it the cache has dtype_enum and they are null
+    int32_t kv_dtype_enum = 0;
+    const float *k_descale = nullptr, *v_descale = nullptr;
+    const int64_t *k_descale_strides = nullptr, *v_descale_strides = nullptr;
+    bool packed = false;  // fa2_fwd_kvcache_varlen: Q, O are (total_q, H, d) over cu_seqlens_q, L is (H, total_q)
+    const int32_t *cu_seqlens_q = nullptr;
+    int32_t total_q = 0, max_seqlen_q = 0;
+    bool mla = false;  // fa2_fwd_kvcache_mla: V is (B, H_kv, S_k, d_v), d may reach 576; without it d_v = d
+    int32_t d_v = 0;
+};
+
+// The three forms of the call: fixed N_q, packed queries (query-tiled), the latent cache.  Each has a matrix kernel of its own
+// beside the VALU kernel (fa2_launch_decode_generic) and the combine, which all share; `variant` is the id that forces it, and
+// AUTO, GENERIC and that id are the variants the form accepts: any other gets `unknown_variant`.
+struct DecodeForm {
+    bool (*supports)(const Fa2DecodeProblem &);
+    int (*launch)(const Fa2DecodeProblem &);
+    int32_t variant;
+    const char *unknown_variant;
+};
+const DecodeForm kForms[3] = {
+    {fa2_decode_mfma16_supports, fa2_launch_decode_mfma16, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
+    {fa2_decode_mfma16_v_supports, fa2_launch_decode_mfma16_v, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
+    {fa2_decode_mla16_supports, fa2_launch_decode_mla16, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
+};
+const DecodeForm &form_of(const DecodeCall &c) { return kForms[c.mla ? 2 : c.packed ? 1 : 0]; }
+
+// The sizes of a paged cache, for check_decode ("kvcache paged") and check_append ("kvcache append"); on FA2_OK `cap` is the capacity.
+int check_paged(const char *who, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int64_t table_stride, int64_t &cap) {
+    if (num_blocks < 1 || page_size < 1 || max_blocks < 1) {
+        fa2_set_error("%s: num_blocks, page_size and max_blocks must be >= 1 (got num_blocks=%d, page_size=%d, max_blocks=%d)", who,
+                      num_blocks, page_size, max_blocks);
+        return FA2_ERR_BAD_ARG;
+    }
+    cap = (int64_t)max_blocks * page_size;
+    if (cap > (1 << 28)) {
+        fa2_set_error("%s: the capacity max_blocks * page_size must be <= 2^28 (got %lld)", who, (long long)cap);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (table_stride < 0) {
+        fa2_set_error("%s: negative block_table_stride", who);
+        return FA2_ERR_BAD_ARG;
+    }
+    return FA2_OK;
 }
 
-int64_t workspace_bytes_varlen(int64_t total_q, int64_t H, int64_t d, int64_t num_splits) {
-    if (num_splits <= 1) return 0;
-    if (num_splits > FA2_KVCACHE_MAX_SPLITS) num_splits = FA2_KVCACHE_MAX_SPLITS;
-    const int64_t rows = total_q * H;
-    if (rows > kMaxRows || d > 512) return INT64_MAX;
-    return 4 * num_splits * rows * (d + 1);
+// The descales of an fp8 cache and their strides, for check_decode ("kvcache fp8") and check_append ("kvcache append").
+int check_descales(const char *who, const float *kd, const int64_t *kds, const float *vd, const int64_t *vds) {
+    if ((kd && !kds) || (vd && !vds)) {
+        fa2_set_error("%s: null %s with a non-null descale", who, kd && !kds ? "k_descale_strides" : "v_descale_strides");
+        return FA2_ERR_BAD_ARG;
+    }
+    if ((kd && (kds[0] < 0 || kds[1] < 0)) || (vd && (vds[0] < 0 || vds[1] < 0))) {
+        fa2_set_error("%s: negative strides are not supported (k_descale_strides, v_descale_strides)", who);
+        return FA2_ERR_BAD_ARG;
+    }
+    return FA2_OK;
 }
 
-// The packed queries of fa2_fwd_kvcache_varlen, checked by it.  Null for the fixed-N_q entry points.
-struct VarlenQ {
-    const int32_t *cu_q;
-    int32_t total_q, max_q;
-};
-
-// The descales of an fp8 cache (fa2_fwd_kvcache_fp8).  Null for the 16-bit entry points, whose cache has Q's dtype.
-struct Fp8Cache {
-    int32_t kv_dtype;
-    const float *kd, *vd;
-    const int64_t *kds, *vds;
-};
-
-// The block table of a paged cache (fa2_fwd_kvcache_paged).  Null for the contiguous entry points.
-struct PagedCache {
-    const int32_t *table;
-    int64_t table_stride;
-    int32_t num_blocks, page_size, max_blocks;
-};
-
-// S_k is the capacity of a contiguous cache; with `pg` it is ignored and max_blocks * page_size takes its place.  With `append`
-// (checked by check_append) that launch goes first, once every check here has passed.  `mla_dv` non-null: fa2_fwd_kvcache_mla, V
-// is (B, H_kv, S_k, *mla_dv), d may reach 576 and FA2_KVCACHE_VARIANT_MLA16 is a variant; null: every other entry point, d_v = d.
-int fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
-                const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
-                int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal,
-                float scale, int32_t wl, int32_t wr, int32_t num_splits, void *workspace, int64_t workspace_bytes_given,
-                void *hip_stream, int32_t variant, const Fp8Cache *f8 = nullptr, const PagedCache *pg = nullptr,
-                const Fa2AppendProblem *append = nullptr, const VarlenQ *vq = nullptr, const int32_t *mla_dv = nullptr) {
-    // (with `vq`: N_q is max_seqlen_q, the strides are {0, head, token, d} and {0, head}, all checked by the caller)
-    const void *ptrs[10] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides};
+// Every check of an attention call, before any launch; on FA2_OK `p` is the problem to launch, num_splits resolved.
+int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
+    if (c.packed) {  // what only the packed queries bring comes first
+        if (!c.q_strides || !c.o_strides) {
+            fa2_set_error("kvcache varlen: null %s", !c.q_strides ? "q_strides" : "o_strides");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (!c.cu_seqlens_q) {
+            fa2_set_error("kvcache varlen: null cu_seqlens_q");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.total_q < 1) {
+            fa2_set_error("kvcache varlen: total_q must be >= 1 (got %d)", c.total_q);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.max_seqlen_q < 1 || c.max_seqlen_q > (1 << 28)) {
+            fa2_set_error("kvcache varlen: max_seqlen_q must be in [1, 2^28] (got %d)", c.max_seqlen_q);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.H >= 1 && (int64_t)c.total_q * c.H > kMaxRows) {
+            fa2_set_error("kvcache varlen: total_q * H must be <= 2^40 (got %lld)", (long long)c.total_q * c.H);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.l_strides[1] < 0) {
+            fa2_set_error("kvcache: negative strides are not supported (l_head_stride)");
+            return FA2_ERR_BAD_ARG;
+        }
+    }
+    if (!c.fp8 && (c.k_descale || c.v_descale)) {  // (a fused step has refused them in check_append)
+        fa2_set_error(c.packed ? "kvcache varlen: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)"
+                               : "kvcache paged: k_descale / v_descale go with an fp8 pool (kv_dtype_enum %d == dtype_enum)",
+                      c.kv_dtype_enum);
+        return FA2_ERR_BAD_ARG;
+    }
+    const void *ptrs[10] = {c.Q, c.K, c.V, c.O, c.L, c.q_strides, c.k_strides, c.v_strides, c.o_strides, c.l_strides};
     const char *names[10] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides", "l_strides"};
     for (int t = 0; t < 10; ++t)
         if (!ptrs[t]) {
             fa2_set_error("kvcache: null %s", names[t]);
             return FA2_ERR_BAD_ARG;
         }
-    if (pg) {
-        if (!pg->table) {
+    int64_t cap = c.S_k;
+    const bool paged = c.pool_only || c.block_table;
+    if (paged) {
+        if (!c.block_table) {
             fa2_set_error("kvcache paged: null block_table");
             return FA2_ERR_BAD_ARG;
         }
-        if (pg->num_blocks < 1 || pg->page_size < 1 || pg->max_blocks < 1) {
-            fa2_set_error("kvcache paged: num_blocks, page_size and max_blocks must be >= 1 (got num_blocks=%d, page_size=%d, "
-                          "max_blocks=%d)", pg->num_blocks, pg->page_size, pg->max_blocks);
-            return FA2_ERR_BAD_ARG;
-        }
-        const int64_t cap = (int64_t)pg->max_blocks * pg->page_size;
-        if (cap > (1 << 28)) {
-            fa2_set_error("kvcache paged: the capacity max_blocks * page_size must be <= 2^28 (got %lld)", (long long)cap);
-            return FA2_ERR_BAD_ARG;
-        }
-        if (pg->table_stride < 0) {
-            fa2_set_error("kvcache paged: negative block_table_stride");
-            return FA2_ERR_BAD_ARG;
-        }
-        S_k = (int32_t)cap;
+        const int rc = check_paged("kvcache paged", c.num_blocks, c.page_size, c.max_blocks, c.block_table_stride, cap);
+        if (rc != FA2_OK) return rc;
     }
-    if (B < 1 || B > 65535) {
-        fa2_set_error("kvcache: B must be in [1, 65535] (got %d)", B);
+    const int32_t S_k = (int32_t)cap;
+    if (c.B < 1 || c.B > 65535) {
+        fa2_set_error("kvcache: B must be in [1, 65535] (got %d)", c.B);
         return FA2_ERR_BAD_ARG;
     }
-    if (H < 1 || H > 65535) {
-        fa2_set_error("kvcache: H must be in [1, 65535] (got %d)", H);
+    if (c.H < 1 || c.H > 65535) {
+        fa2_set_error("kvcache: H must be in [1, 65535] (got %d)", c.H);
         return FA2_ERR_BAD_ARG;
     }
-    int rc = fa2_check_gqa(H, H_kv);
-    if (rc != FA2_OK) return rc;
-    if (!vq && (N_q < 1 || N_q > (1 << 28))) {
-        fa2_set_error("kvcache: N_q must be in [1, 2^28] (got %d)", N_q);
+    const int gqa = fa2_check_gqa(c.H, c.H_kv);
+    if (gqa != FA2_OK) return gqa;
+    if (!c.packed && (c.N_q < 1 || c.N_q > (1 << 28))) {
+        fa2_set_error("kvcache: N_q must be in [1, 2^28] (got %d)", c.N_q);
         return FA2_ERR_BAD_ARG;
     }
     if (S_k < 1 || S_k > (1 << 28)) {
         fa2_set_error("kvcache: S_k must be in [1, 2^28] (got %d)", S_k);
         return FA2_ERR_BAD_ARG;
     }
-    if (!vq && (int64_t)B * H * N_q > kMaxRows) {
-        fa2_set_error("kvcache: B * H * N_q must be <= 2^40 (got %lld)", (long long)B * H * N_q);
+    if (!c.packed && (int64_t)c.B * c.H * c.N_q > kMaxRows) {
+        fa2_set_error("kvcache: B * H * N_q must be <= 2^40 (got %lld)", (long long)c.B * c.H * c.N_q);
         return FA2_ERR_BAD_ARG;
     }
-    if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
+    if (c.window_left < -1 || c.window_right < -1) {
+        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", c.window_left, c.window_right);
         return FA2_ERR_BAD_ARG;
     }
     for (int k = 0; k < 4; ++k)
-        if (q_strides[k] < 0 || k_strides[k] < 0 || v_strides[k] < 0 || o_strides[k] < 0) {
+        if (c.q_strides[k] < 0 || c.k_strides[k] < 0 || c.v_strides[k] < 0 || c.o_strides[k] < 0) {
             fa2_set_error("kvcache: negative strides are not supported");
             return FA2_ERR_BAD_ARG;
         }
-    if (l_strides[0] < 0 || l_strides[1] < 0) {
+    if (c.l_strides[0] < 0 || c.l_strides[1] < 0) {
         fa2_set_error("kvcache: negative strides are not supported (l_strides)");
         return FA2_ERR_BAD_ARG;
     }
-    if (!(scale == scale)) {
+    if (!(c.scale == c.scale)) {
         fa2_set_error("kvcache: scale is NaN");
         return FA2_ERR_BAD_ARG;
     }
-    if (num_splits < 0 || num_splits > FA2_KVCACHE_MAX_SPLITS) {
-        fa2_set_error("kvcache: num_splits must be in [0, %d] (0 = auto), got %d", FA2_KVCACHE_MAX_SPLITS, num_splits);
+    if (c.num_splits < 0 || c.num_splits > FA2_KVCACHE_MAX_SPLITS) {
+        fa2_set_error("kvcache: num_splits must be in [0, %d] (0 = auto), got %d", FA2_KVCACHE_MAX_SPLITS, c.num_splits);
         return FA2_ERR_BAD_ARG;
     }
-    if (f8) {
-        if ((f8->kd && !f8->kds) || (f8->vd && !f8->vds)) {
-            fa2_set_error("kvcache fp8: null %s with a non-null descale", f8->kd && !f8->kds ? "k_descale_strides" : "v_descale_strides");
-            return FA2_ERR_BAD_ARG;
-        }
-        if ((f8->kd && (f8->kds[0] < 0 || f8->kds[1] < 0)) || (f8->vd && (f8->vds[0] < 0 || f8->vds[1] < 0))) {
-            fa2_set_error("kvcache fp8: negative strides are not supported (k_descale_strides, v_descale_strides)");
-            return FA2_ERR_BAD_ARG;
-        }
-        if (f8->kv_dtype != FA2_DTYPE_F8E4M3 && f8->kv_dtype != FA2_DTYPE_F8E5M2) {
-            fa2_set_error("kvcache fp8: kv_dtype_enum %d must be FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", f8->kv_dtype);
+    if (c.fp8) {
+        const int rc = check_descales("kvcache fp8", c.k_descale, c.k_descale_strides, c.v_descale, c.v_descale_strides);
+        if (rc != FA2_OK) return rc;
+        if (c.kv_dtype_enum != FA2_DTYPE_F8E4M3 && c.kv_dtype_enum != FA2_DTYPE_F8E5M2) {
+            fa2_set_error("kvcache fp8: kv_dtype_enum %d must be FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", c.kv_dtype_enum);
             return FA2_ERR_UNSUPPORTED;
         }
-        if (dtype_enum != FA2_DTYPE_F16 && dtype_enum != FA2_DTYPE_BF16) {
-            fa2_set_error("kvcache fp8: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16", dtype_enum);
+        if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16) {
+            fa2_set_error("kvcache fp8: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16", c.dtype_enum);
             return FA2_ERR_UNSUPPORTED;
         }
-    } else if (dtype_enum == FA2_DTYPE_F8E5M2 || dtype_enum == FA2_DTYPE_F8E4M3) {
+    } else if (c.dtype_enum == FA2_DTYPE_F8E5M2 || c.dtype_enum == FA2_DTYPE_F8E4M3) {
         fa2_set_error("kvcache: fp8 is not supported (e4m3fn cannot hold L = +inf)");
         return FA2_ERR_UNSUPPORTED;
     }
-    if (fa2_dtype_size(dtype_enum) == 0) {
-        fa2_set_error("unknown dtype enum %d", dtype_enum);
+    if (fa2_dtype_size(c.dtype_enum) == 0) {
+        fa2_set_error("unknown dtype enum %d", c.dtype_enum);
         return FA2_ERR_UNSUPPORTED;
     }
-    const int32_t d_v = mla_dv ? *mla_dv : d;
-    if (mla_dv) {
-        if (d < 1 || d > 576) {
-            fa2_set_error("kvcache mla: d=%d must be in [1, 576]", d);
-            return FA2_ERR_UNSUPPORTED;
-        }
-        if (d_v < 1 || d_v > 512) {
-            fa2_set_error("kvcache mla: d_v=%d must be in [1, 512]", d_v);
-            return FA2_ERR_UNSUPPORTED;
-        }
-        if (variant != FA2_KVCACHE_VARIANT_AUTO && variant != FA2_KVCACHE_VARIANT_GENERIC && variant != FA2_KVCACHE_VARIANT_MLA16) {
-            fa2_set_error("kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)", variant);
-            return FA2_ERR_UNSUPPORTED;
-        }
-    } else {
-        if (d < 1 || d > 512) {
-            fa2_set_error("d=%d must be in [1, 512]", d);
-            return FA2_ERR_UNSUPPORTED;
-        }
-        if (variant != FA2_KVCACHE_VARIANT_AUTO && variant != FA2_KVCACHE_VARIANT_GENERIC && variant != FA2_KVCACHE_VARIANT_MFMA16) {
-            fa2_set_error("kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)", variant);
-            return FA2_ERR_UNSUPPORTED;
-        }
+    const int32_t d_v = c.mla ? c.d_v : c.d;
+    if (c.d < 1 || c.d > (c.mla ? 576 : 512)) {
+        fa2_set_error(c.mla ? "kvcache mla: d=%d must be in [1, 576]" : "d=%d must be in [1, 512]", c.d);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (d_v < 1 || d_v > 512) {  // (the latent cache alone: elsewhere d_v is d)
+        fa2_set_error("kvcache mla: d_v=%d must be in [1, 512]", d_v);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    const DecodeForm &form = form_of(c);
+    if (c.variant != FA2_KVCACHE_VARIANT_AUTO && c.variant != FA2_KVCACHE_VARIANT_GENERIC && c.variant != form.variant) {
+        fa2_set_error(form.unknown_variant, c.variant);
+        return FA2_ERR_UNSUPPORTED;
     }
 
-    Fa2DecodeProblem p;
-    p.Q = Q; p.K = K; p.V = V; p.O = O; p.L = L;
-    for (int k = 0; k < 4; ++k) { p.qs[k] = q_strides[k]; p.ks[k] = k_strides[k]; p.vs[k] = v_strides[k]; p.os[k] = o_strides[k]; }
-    p.ls[0] = l_strides[0]; p.ls[1] = l_strides[1];
-    p.seqlens = cache_seqlens;
-    p.B = B; p.H = H; p.H_kv = H_kv; p.N_q = N_q; p.S_k = S_k; p.d = d; p.d_v = d_v;
-    p.kv_dtype = f8 ? f8->kv_dtype : dtype_enum;
-    p.kd = f8 ? f8->kd : nullptr; p.vd = f8 ? f8->vd : nullptr;
-    for (int k = 0; k < 2; ++k) { p.kds[k] = p.kd ? f8->kds[k] : 0; p.vds[k] = p.vd ? f8->vds[k] : 0; }
-    p.table = pg ? pg->table : nullptr;
-    p.table_stride = pg ? pg->table_stride : 0;
-    p.page_size = pg ? pg->page_size : 0; p.num_blocks = pg ? pg->num_blocks : 0;
-    p.dtype = dtype_enum; p.causal = causal != 0; p.wl = wl; p.wr = wr; p.scale = scale;
-    p.cu_q = vq ? vq->cu_q : nullptr;
-    p.total_q = vq ? vq->total_q : 0; p.max_q = vq ? vq->max_q : 0;
-    if (num_splits != 0) p.num_splits = num_splits;
-    else if (mla_dv) p.num_splits = num_splits_mla(B, H, H_kv, N_q, S_k, d, d_v, dtype_enum);
-    else p.num_splits = vq ? num_splits_varlen(B, H, H_kv, vq->total_q, vq->max_q, S_k, d, dtype_enum) : num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum);
-    p.stream = (hipStream_t)hip_stream;
+    p.Q = c.Q; p.K = c.K; p.V = c.V; p.O = c.O; p.L = c.L;
+    for (int k = 0; k < 4; ++k) { p.qs[k] = c.q_strides[k]; p.ks[k] = c.k_strides[k]; p.vs[k] = c.v_strides[k]; p.os[k] = c.o_strides[k]; }
+    p.ls[0] = c.l_strides[0]; p.ls[1] = c.l_strides[1];
+    p.seqlens = c.cache_seqlens;
+    p.B = c.B; p.H = c.H; p.H_kv = c.H_kv; p.N_q = c.N_q; p.S_k = S_k; p.d = c.d; p.d_v = d_v;
+    p.kv_dtype = c.fp8 ? c.kv_dtype_enum : c.dtype_enum;
+    p.kd = c.fp8 ? c.k_descale : nullptr; p.vd = c.fp8 ? c.v_descale : nullptr;
+    for (int k = 0; k < 2; ++k) { p.kds[k] = p.kd ? c.k_descale_strides[k] : 0; p.vds[k] = p.vd ? c.v_descale_strides[k] : 0; }
+    p.table = c.block_table;
+    p.table_stride = paged ? c.block_table_stride : 0; p.page_size = paged ? c.page_size : 0; p.num_blocks = paged ? c.num_blocks : 0;
+    p.dtype = c.dtype_enum; p.causal = c.causal != 0; p.wl = c.window_left; p.wr = c.window_right; p.scale = c.scale;
+    p.cu_q = c.packed ? c.cu_seqlens_q : nullptr;
+    p.total_q = c.packed ? c.total_q : 0; p.max_q = c.packed ? c.max_seqlen_q : 0;
+    const SplitShape shape = {c.B, c.H, c.H_kv, c.N_q, c.total_q, S_k, c.d, d_v, c.dtype_enum};
+    p.num_splits = c.num_splits != 0 ? c.num_splits : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
+    p.stream = (hipStream_t)c.hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
-        const int64_t need = vq ? workspace_bytes_varlen(vq->total_q, H, d, p.num_splits) : workspace_bytes(B, H, N_q, d_v, p.num_splits);
-        if (!workspace || workspace_bytes_given < need) {
+        const int64_t rows = c.packed ? (int64_t)c.total_q * c.H : (int64_t)c.B * c.H * c.N_q;
+        const int64_t need = workspace_bytes(rows, d_v, p.num_splits);
+        if (!c.workspace || c.workspace_bytes < need) {
             fa2_set_error("kvcache: workspace of %lld bytes needed for num_splits=%d (%s), got %s%lld", (long long)need, p.num_splits,
-                          vq ? "fa2_kvcache_varlen_workspace_bytes" : "fa2_kvcache_workspace_bytes", workspace ? "" : "null, ",
-                          (long long)workspace_bytes_given);
+                          c.packed ? "fa2_kvcache_varlen_workspace_bytes" : "fa2_kvcache_workspace_bytes", c.workspace ? "" : "null, ",
+                          (long long)c.workspace_bytes);
             return FA2_ERR_BAD_ARG;
         }
-        p.o_part = (float *)workspace;
-        p.l_part = p.o_part + (int64_t)p.num_splits * (vq ? (int64_t)vq->total_q * H : (int64_t)B * H * N_q) * d_v;
+        p.o_part = (float *)c.workspace;
+        p.l_part = p.o_part + (int64_t)p.num_splits * rows * d_v;
     }
-    if (mla_dv) {  // the latent-cache call: its own matrix form where it runs, else the VALU form; the same combine
-        if (variant == FA2_KVCACHE_VARIANT_AUTO)
-            variant = fa2_decode_mla16_supports(p) ? FA2_KVCACHE_VARIANT_MLA16 : FA2_KVCACHE_VARIANT_GENERIC;
-        rc = variant == FA2_KVCACHE_VARIANT_MLA16 ? fa2_launch_decode_mla16(p) : fa2_launch_decode_generic(p);
-        if (rc != FA2_OK || p.num_splits == 1) return rc;
-        return fa2_launch_decode_combine(p);
-    }
-    if (vq) {  // the packed call: its own matrix form (query-tiled), the same VALU form and combine
-        if (variant == FA2_KVCACHE_VARIANT_AUTO)
-            variant = fa2_decode_mfma16_v_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
-        if (append) {  // the fused ragged step: as below
-            if (variant == FA2_KVCACHE_VARIANT_MFMA16 && !fa2_decode_mfma16_v_supports(p)) return fa2_launch_decode_mfma16_v(p);
-            rc = fa2_launch_decode_append(*append);
-            if (rc != FA2_OK) return rc;
-        }
-        rc = variant == FA2_KVCACHE_VARIANT_MFMA16 ? fa2_launch_decode_mfma16_v(p) : fa2_launch_decode_generic(p);
-        if (rc != FA2_OK || p.num_splits == 1) return rc;
-        return fa2_launch_decode_combine(p);
-    }
-    if (variant == FA2_KVCACHE_VARIANT_AUTO)
-        variant = fa2_decode_mfma16_supports(p) ? FA2_KVCACHE_VARIANT_MFMA16 : FA2_KVCACHE_VARIANT_GENERIC;
-    if (append) {  // the fused step: the cache update first, on the same stream (a forced form that cannot run fails before it)
-        if (variant == FA2_KVCACHE_VARIANT_MFMA16 && !fa2_decode_mfma16_supports(p)) return fa2_launch_decode_mfma16(p);
-        rc = fa2_launch_decode_append(*append);
+    return FA2_OK;
+}
+
+// The launches of a checked call, on its stream: the append of a fused step (`append` non-null) first, then the split kernel of the
+// form the variant names -- AUTO: the call's matrix form where it runs, else the VALU form -- then the combine.  A forced matrix
+// form that cannot run fails (in its launcher, which names the rule) before the cache is touched.
+int run_decode(const DecodeCall &c, const Fa2DecodeProblem &p, const Fa2AppendProblem *append) {
+    const DecodeForm &form = form_of(c);
+    const bool matrix = c.variant == FA2_KVCACHE_VARIANT_AUTO ? form.supports(p) : c.variant == form.variant;
+    if (append) {
+        if (matrix && !form.supports(p)) return form.launch(p);
+        const int rc = fa2_launch_decode_append(*append);
         if (rc != FA2_OK) return rc;
     }
-    rc = variant == FA2_KVCACHE_VARIANT_MFMA16 ? fa2_launch_decode_mfma16(p) : fa2_launch_decode_generic(p);
+    const int rc = matrix ? form.launch(p) : fa2_launch_decode_generic(p);
     if (rc != FA2_OK || p.num_splits == 1) return rc;
     return fa2_launch_decode_combine(p);
+}
+
+// Steps 2 and 3 of an attention call; `append` is the checked cache update of a fused step, or null.
+int decode(const DecodeCall &c, const Fa2AppendProblem *append) {
+    Fa2DecodeProblem p;
+    const int rc = check_decode(c, p);
+    return rc != FA2_OK ? rc : run_decode(c, p, append);
 }
 
 // The arguments of fa2_kvcache_append as the entry points take them.
@@ -345,20 +389,8 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
     }
     int64_t cap = c.S_k;
     if (c.block_table) {
-        if (c.num_blocks < 1 || c.page_size < 1 || c.max_blocks < 1) {
-            fa2_set_error("kvcache append: num_blocks, page_size and max_blocks must be >= 1 (got num_blocks=%d, page_size=%d, "
-                          "max_blocks=%d)", c.num_blocks, c.page_size, c.max_blocks);
-            return FA2_ERR_BAD_ARG;
-        }
-        cap = (int64_t)c.max_blocks * c.page_size;
-        if (cap > (1 << 28)) {
-            fa2_set_error("kvcache append: the capacity max_blocks * page_size must be <= 2^28 (got %lld)", (long long)cap);
-            return FA2_ERR_BAD_ARG;
-        }
-        if (c.block_table_stride < 0) {
-            fa2_set_error("kvcache append: negative block_table_stride");
-            return FA2_ERR_BAD_ARG;
-        }
+        const int rc = check_paged("kvcache append", c.num_blocks, c.page_size, c.max_blocks, c.block_table_stride, cap);
+        if (rc != FA2_OK) return rc;
     } else if (cap < 1 || cap > (1 << 28)) {
         fa2_set_error("kvcache append: S_k must be in [1, 2^28] (got %d)", c.S_k);
         return FA2_ERR_BAD_ARG;
@@ -428,16 +460,8 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
             return FA2_ERR_UNSUPPORTED;
         }
     } else {
-        if ((c.k_descale && !c.k_descale_strides) || (c.v_descale && !c.v_descale_strides)) {
-            fa2_set_error("kvcache append: null %s with a non-null descale",
-                          c.k_descale && !c.k_descale_strides ? "k_descale_strides" : "v_descale_strides");
-            return FA2_ERR_BAD_ARG;
-        }
-        if ((c.k_descale && (c.k_descale_strides[0] < 0 || c.k_descale_strides[1] < 0)) ||
-            (c.v_descale && (c.v_descale_strides[0] < 0 || c.v_descale_strides[1] < 0))) {
-            fa2_set_error("kvcache append: negative strides are not supported (k_descale_strides, v_descale_strides)");
-            return FA2_ERR_BAD_ARG;
-        }
+        const int rc = check_descales("kvcache append", c.k_descale, c.k_descale_strides, c.v_descale, c.v_descale_strides);
+        if (rc != FA2_OK) return rc;
         if (c.kv_dtype_enum != FA2_DTYPE_F8E4M3 && c.kv_dtype_enum != FA2_DTYPE_F8E5M2) {
             fa2_set_error("kvcache append: kv_dtype_enum %d must be dtype_enum, FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", c.kv_dtype_enum);
             return FA2_ERR_UNSUPPORTED;
@@ -506,56 +530,6 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
     return FA2_OK;
 }
 
-// fa2_fwd_kvcache_varlen; with `append` (packed, checked by check_append) that launch goes first.
-int fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
-                       const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[3], int64_t l_head_stride,
-                       const int32_t *cu_seqlens_q, const int32_t *cache_seqlens, const int32_t *block_table,
-                       int64_t block_table_stride, const float *k_descale, const float *v_descale,
-                       const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
-                       int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
-                       int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left,
-                       int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
-                       void *hip_stream, const Fa2AppendProblem *append = nullptr) {
-    if (!q_strides || !o_strides) {
-        fa2_set_error("kvcache varlen: null %s", !q_strides ? "q_strides" : "o_strides");
-        return FA2_ERR_BAD_ARG;
-    }
-    if (!cu_seqlens_q) {
-        fa2_set_error("kvcache varlen: null cu_seqlens_q");
-        return FA2_ERR_BAD_ARG;
-    }
-    if (total_q < 1) {
-        fa2_set_error("kvcache varlen: total_q must be >= 1 (got %d)", total_q);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (max_seqlen_q < 1 || max_seqlen_q > (1 << 28)) {
-        fa2_set_error("kvcache varlen: max_seqlen_q must be in [1, 2^28] (got %d)", max_seqlen_q);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (H >= 1 && (int64_t)total_q * H > kMaxRows) {
-        fa2_set_error("kvcache varlen: total_q * H must be <= 2^40 (got %lld)", (long long)total_q * H);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (l_head_stride < 0) {
-        fa2_set_error("kvcache: negative strides are not supported (l_head_stride)");
-        return FA2_ERR_BAD_ARG;
-    }
-    const bool wide = kv_dtype_enum == dtype_enum;  // the cache has Q's dtype: no descales
-    if (wide && (k_descale || v_descale)) {
-        fa2_set_error("kvcache varlen: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)", kv_dtype_enum);
-        return FA2_ERR_BAD_ARG;
-    }
-    // the packed tensors in the fixed call's terms: no batch stride, the token axis where the query position is
-    const int64_t qs[4] = {0, q_strides[1], q_strides[0], q_strides[2]}, os[4] = {0, o_strides[1], o_strides[0], o_strides[2]};
-    const int64_t ls[2] = {0, l_head_stride};
-    const VarlenQ vq = {cu_seqlens_q, total_q, max_seqlen_q};
-    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
-    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
-    return fwd_kvcache(Q, K, V, O, L, qs, k_strides, v_strides, os, ls, cache_seqlens, B, H, H_kv, max_seqlen_q, S_k, d, dtype_enum, causal,
-                       scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream, variant,
-                       wide ? nullptr : &f8, block_table ? &pg : nullptr, append, &vq);
-}
-
 }  // namespace
 
 extern "C" {
@@ -565,9 +539,9 @@ int fa2_fwd_kvcache(const void *Q, const void *K, const void *V, void *O, void *
                     const int32_t *cache_seqlens, int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d,
                     int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                     void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
-                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
-                       FA2_KVCACHE_VARIANT_AUTO);
+    return fa2_fwd_kvcache_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q,
+                                   S_k, d, dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes,
+                                   hip_stream, FA2_KVCACHE_VARIANT_AUTO);
 }
 
 int fa2_fwd_kvcache_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
@@ -576,9 +550,12 @@ int fa2_fwd_kvcache_variant(const void *Q, const void *K, const void *V, void *O
                             int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
                             int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
                             void *hip_stream, int32_t variant) {
-    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
-                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
-                       variant);
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return decode(c, nullptr);
 }
 
 int fa2_fwd_kvcache_fp8(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
@@ -588,10 +565,14 @@ int fa2_fwd_kvcache_fp8(const void *Q, const void *K, const void *V, void *O, vo
                         int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale,
                         int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
                         int32_t variant, void *hip_stream) {
-    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
-    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, S_k, d,
-                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
-                       variant, &f8);
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.fp8 = true; c.kv_dtype_enum = kv_dtype_enum;  // (whatever kv_dtype_enum holds: one that is no fp8 format is refused)
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    return decode(c, nullptr);
 }
 
 int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
@@ -602,16 +583,15 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
                           int32_t N_q, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t dtype_enum,
                           int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
                           int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream) {
-    const bool wide = kv_dtype_enum == dtype_enum;  // the pool has Q's dtype: fa2_fwd_kvcache's checks, no descales
-    if (wide && (k_descale || v_descale)) {
-        fa2_set_error("kvcache paged: k_descale / v_descale go with an fp8 pool (kv_dtype_enum %d == dtype_enum)", kv_dtype_enum);
-        return FA2_ERR_BAD_ARG;
-    }
-    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
-    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
-    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q, 0, d,
-                       dtype_enum, causal, scale, window_left, window_right, num_splits, workspace, workspace_bytes, hip_stream,
-                       variant, wide ? nullptr : &f8, &pg);
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = 0; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.pool_only = true; c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;  // (a pool in Q's dtype: no descales)
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    return decode(c, nullptr);
 }
 
 int fa2_fwd_kvcache_mla(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
@@ -620,18 +600,21 @@ int fa2_fwd_kvcache_mla(const void *Q, const void *K, const void *V, void *O, vo
                         int32_t H_kv, int32_t N_q, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
                         int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                         void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream) {
-    // block_table null: the contiguous cache (B, H_kv, S_k, d), a pool of one page per sequence: page_size carries S_k
-    // (num_blocks and max_blocks are not read)
-    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
-    return fwd_kvcache(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, cache_seqlens, B, H, H_kv, N_q,
-                       block_table ? 0 : page_size, d, dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
-                       workspace_bytes, hip_stream, variant, nullptr, block_table ? &pg : nullptr, nullptr, nullptr, &d_v);
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    // block_table null: the contiguous cache, a pool of one page per sequence: page_size carries S_k (num_blocks, max_blocks are not read)
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = block_table ? 0 : page_size; c.d = d; c.dtype_enum = dtype_enum;
+    c.causal = causal; c.scale = scale; c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    return decode(c, nullptr);
 }
 
 int32_t fa2_kvcache_mla_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t d_v,
                                    int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
-    return num_splits_mla(B, H, H_kv, N_q, S_k, d, d_v, dtype_enum);
+    return num_splits_mla({B, H, H_kv, N_q, 0, S_k, d, d_v, dtype_enum});
 }
 
 int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
@@ -643,31 +626,41 @@ int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O,
                            int32_t d, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left,
                            int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
                            void *hip_stream) {
-    return fwd_kvcache_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cache_seqlens,
-                              block_table, block_table_stride, k_descale, v_descale, k_descale_strides, v_descale_strides, B, H, H_kv,
-                              total_q, max_seqlen_q, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, causal, scale,
-                              window_left, window_right, num_splits, workspace, workspace_bytes, variant, hip_stream);
+    // the packed tensors in the fixed call's terms: no batch stride, the token axis where the query position is
+    int64_t qs[4], os[4];
+    const int64_t ls[2] = {0, l_head_stride};
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = packed4(q_strides, qs); c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    return decode(c, nullptr);
 }
 
 int64_t fa2_kvcache_varlen_workspace_bytes(int32_t total_q, int32_t H, int32_t d, int32_t num_splits) {
     if (total_q < 1 || H < 1 || d < 1 || H > 65535) return 0;
-    return workspace_bytes_varlen(total_q, H, d, num_splits);
+    return workspace_bytes((int64_t)total_q * H, d, num_splits);
 }
 
 int32_t fa2_kvcache_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t d,
                                       int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || total_q < 1 || max_seqlen_q < 1 || S_k < 1) return 1;
-    return num_splits_varlen(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype_enum);
+    return num_splits_varlen({B, H, H_kv, max_seqlen_q, total_q, S_k, d, d, dtype_enum});
 }
 
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {
     if (B < 1 || H < 1 || N_q < 1 || d < 1 || B > 65535 || H > 65535 || N_q > (1 << 28)) return 0;
-    return workspace_bytes(B, H, N_q, d, num_splits);
+    return workspace_bytes((int64_t)B * H * N_q, d, num_splits);
 }
 
 int32_t fa2_kvcache_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
-    return num_splits_auto(B, H, H_kv, N_q, S_k, d, dtype_enum);
+    return num_splits_auto({B, H, H_kv, N_q, 0, S_k, d, d, dtype_enum});
 }
 
 int fa2_kvcache_append(void *K, void *V, const int64_t k_strides[4], const int64_t v_strides[4], const int32_t *block_table,
@@ -700,22 +693,25 @@ int fa2_fwd_kvcache_append(const void *Q, void *K, void *V, void *O, void *L, co
                            float scale, int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace,
                            int64_t workspace_bytes, int32_t variant, void *hip_stream) {
     const int32_t per_row = causal || window_left >= 0 || window_right >= 0;  // flash-attn's rule for Q's rotary positions
-    const AppendCall c = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, k_new_strides, v_new_strides,
+    const AppendCall a = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, k_new_strides, v_new_strides,
                           cache_seqlens, seqlens_out, k_descale, v_descale, k_descale_strides, v_descale_strides, rotary_cos, rotary_sin,
                           rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot, q_strides, H, N_q,
                           per_row, B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, hip_stream};
     Fa2AppendProblem p;
-    const int rc = check_append(c, p);
+    const int rc = check_append(a, p);
     if (rc != FA2_OK) return rc;
-    // the attention reads the rotated Q (contiguous) and the new lengths
+    // the attention reads the rotated Q (contiguous; p.Q null: no tables, Q as it is) and the new lengths
     const int64_t rot_strides[4] = {(int64_t)H * N_q * d, (int64_t)N_q * d, d, 1};
-    const bool rotated = p.Q != nullptr;
-    const Fp8Cache f8 = {kv_dtype_enum, k_descale, v_descale, k_descale_strides, v_descale_strides};
-    const PagedCache pg = {block_table, block_table_stride, num_blocks, page_size, max_blocks};
-    return fwd_kvcache(rotated ? q_rot : Q, K, V, O, L, rotated ? rot_strides : q_strides, k_strides, v_strides, o_strides, l_strides,
-                       seqlens_out, B, H, H_kv, N_q, S_k, d, dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
-                       workspace_bytes, hip_stream, variant, kv_dtype_enum == dtype_enum ? nullptr : &f8, block_table ? &pg : nullptr,
-                       &p);
+    DecodeCall c;
+    c.Q = p.Q ? q_rot : Q; c.K = K; c.V = V; c.O = O; c.L = L; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = p.Q ? rot_strides : q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides;
+    c.l_strides = l_strides; c.cache_seqlens = seqlens_out;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    return decode(c, &p);
 }
 
 int fa2_kvcache_append_varlen(void *K, void *V, const int64_t k_strides[4], const int64_t v_strides[4], const int32_t *block_table,
@@ -753,24 +749,29 @@ int fa2_fwd_kvcache_varlen_append(const void *Q, void *K, void *V, void *O, void
                                   int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
                                   int32_t variant, void *hip_stream) {
     const int32_t per_row = causal || window_left >= 0 || window_right >= 0;  // the fixed fused call's rule
-    int64_t kns[4], vns[4], qs[4];
-    AppendCall c = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, packed4(k_new_strides, kns),
+    int64_t kns[4], vns[4], qs[4], os[4];
+    AppendCall a = {K, V, k_strides, v_strides, block_table, block_table_stride, k_new, v_new, packed4(k_new_strides, kns),
                     packed4(v_new_strides, vns), cache_seqlens, seqlens_out, k_descale, v_descale, k_descale_strides, v_descale_strides,
                     rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot,
                     packed4(q_strides, qs), H, 0, per_row, B, H_kv, 0, S_k, num_blocks, page_size, max_blocks, d, dtype_enum,
                     kv_dtype_enum, hip_stream};
-    c.packed = true; c.cu_seqlens_new = cu_seqlens_q; c.total_new = total_q; c.max_seqlen_new = max_seqlen_q;
+    a.packed = true; a.cu_seqlens_new = cu_seqlens_q; a.total_new = total_q; a.max_seqlen_new = max_seqlen_q;
     Fa2AppendProblem p;
-    const int rc = check_append(c, p);
+    const int rc = check_append(a, p);
     if (rc != FA2_OK) return rc;
-    // the attention reads the rotated Q (packed, contiguous) and the new lengths
-    const int64_t rot_strides[3] = {(int64_t)H * d, d, 1};
-    const bool rotated = p.Q != nullptr;
-    return fwd_kvcache_varlen(rotated ? q_rot : Q, K, V, O, L, rotated ? rot_strides : q_strides, k_strides, v_strides, o_strides,
-                              l_head_stride, cu_seqlens_q, seqlens_out, block_table, block_table_stride, k_descale, v_descale,
-                              k_descale_strides, v_descale_strides, B, H, H_kv, total_q, max_seqlen_q, S_k, num_blocks, page_size,
-                              max_blocks, d, dtype_enum, kv_dtype_enum, causal, scale, window_left, window_right, num_splits, workspace,
-                              workspace_bytes, variant, hip_stream, &p);
+    // the attention reads the rotated Q (packed, contiguous; p.Q null: no tables, Q as it is) and the new lengths
+    const int64_t rot_strides[4] = {0, d, (int64_t)H * d, 1}, ls[2] = {0, l_head_stride};
+    DecodeCall c;
+    c.Q = p.Q ? q_rot : Q; c.K = K; c.V = V; c.O = O; c.L = L; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = p.Q ? rot_strides : a.q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls; c.cache_seqlens = seqlens_out;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    return decode(c, &p);
 }
 
 }  // extern "C"

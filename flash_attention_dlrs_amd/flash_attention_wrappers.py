@@ -158,6 +158,50 @@ def _kvcache_descale(name, t, Q, B, H_kv):
         raise ValueError(f"kvcache: {name} of shape {tuple(t.shape)} does not broadcast to (B, H_kv) = ({B}, {H_kv})") from None
 
 
+def _descale_views(k_descale, v_descale, Q, B, H_kv):
+    """Both descales as the launchers' keywords."""
+    return dict(k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv), v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv))
+
+
+def _check_cache_seqlens(cache_seqlens, B, anchor, name, or_none=""):
+    """cache_seqlens beside the tensor `anchor`, called `name` in the messages, whose device it must share."""
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 \
+            or not cache_seqlens.is_contiguous() or cache_seqlens.numel() != B:
+        raise ValueError(f"kvcache: cache_seqlens must be a contiguous int32 tensor of B = {B} entries{or_none}")
+    if cache_seqlens.device != anchor.device:
+        raise ValueError(f"kvcache: cache_seqlens must be on {name}'s device ({anchor.device}), got {cache_seqlens.device}")
+
+
+def _check_block_table(block_table, B, page_size, anchor, name):
+    """block_table over pages of page_size rows, beside the tensor `anchor`, called `name` in the messages."""
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 \
+            or block_table.shape[0] != B or block_table.shape[1] < 1:
+        raise ValueError(f"kvcache: block_table must be an int32 tensor (B, max_blocks) with B = {B}, max_blocks >= 1")
+    if block_table.stride(1) != 1 or block_table.stride(0) < 0:
+        raise ValueError(f"kvcache: block_table needs unit stride in its last axis, got strides {tuple(block_table.stride())}")
+    if block_table.device != anchor.device:
+        raise ValueError(f"kvcache: block_table must be on {name}'s device ({anchor.device}), got {block_table.device}")
+    if block_table.shape[1] * page_size > 1 << 28:
+        raise ValueError(f"kvcache: the capacity max_blocks * page_size must be <= 2^28, got {block_table.shape[1]} * {page_size}")
+
+
+def _capacity(K_cache, block_table):
+    return K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]
+
+
+def _kvcache_outputs(Q, o_shape, l_shape, workspace_bytes):
+    """(O, L, workspace) of a cache call, allocated: the fp32 workspace of workspace_bytes bytes, None for 0 (a single split)."""
+    O = torch.empty(o_shape, dtype=Q.dtype, device=Q.device)
+    L = torch.empty(l_shape, dtype=Q.dtype, device=Q.device)
+    ws = torch.empty(workspace_bytes // 4, dtype=torch.float32, device=Q.device) if workspace_bytes else None
+    return O, L, ws
+
+
+def _check_dev(dev, Q, K_cache, V_cache):
+    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
+        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+
+
 def apply_rotary(x, cos, sin, positions, interleaved=False):
     """Rotary embedding as the cache append applies it (include/fa2_fwd.h fa2_kvcache_append), in plain torch on any device: the
     meaning of flash_attention_kvcache_forward's rotary_cos / rotary_sin and the yardstick of its tests, bit for bit.  x (..., d);
@@ -231,22 +275,9 @@ def check_kvcache_append_args(K_cache, V_cache, k_new, v_new, cache_seqlens, k_d
     for name, t in (("v_new", v_new), ("K_cache", K_cache), ("V_cache", V_cache)):
         if t.device != k_new.device:
             raise ValueError(f"kvcache: {name} must be on k_new's device ({k_new.device}), got {t.device}")
-    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 \
-            or not cache_seqlens.is_contiguous() or cache_seqlens.numel() != B:
-        raise ValueError(f"kvcache: cache_seqlens must be a contiguous int32 tensor of B = {B} entries")
-    if cache_seqlens.device != k_new.device:
-        raise ValueError(f"kvcache: cache_seqlens must be on k_new's device ({k_new.device}), got {cache_seqlens.device}")
+    _check_cache_seqlens(cache_seqlens, B, k_new, "k_new")
     if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 \
-                or block_table.shape[0] != B or block_table.shape[1] < 1:
-            raise ValueError(f"kvcache: block_table must be an int32 tensor (B, max_blocks) with B = {B}, max_blocks >= 1")
-        if block_table.stride(1) != 1 or block_table.stride(0) < 0:
-            raise ValueError(f"kvcache: block_table needs unit stride in its last axis, got strides {tuple(block_table.stride())}")
-        if block_table.device != k_new.device:
-            raise ValueError(f"kvcache: block_table must be on k_new's device ({k_new.device}), got {block_table.device}")
-        if block_table.shape[1] * K_cache.shape[2] > 1 << 28:
-            raise ValueError(f"kvcache: the capacity max_blocks * page_size must be <= 2^28, got "
-                             f"{block_table.shape[1]} * {K_cache.shape[2]}")
+        _check_block_table(block_table, B, K_cache.shape[2], k_new, "k_new")
     if rotary_cos is not None:
         d = k_new.shape[3]
         for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
@@ -278,8 +309,7 @@ def kvcache_append(K_cache, V_cache, k_new, v_new, cache_seqlens, *, k_descale=N
     new_seqlens = torch.empty_like(cache_seqlens)
     _lib.fa2_kvcache_append(K_cache, V_cache, k_new, v_new, cache_seqlens, new_seqlens, convert_triton_dtype(k_new.dtype),
                             convert_triton_dtype(K_cache.dtype), block_table=block_table,
-                            k_descale=_kvcache_descale("k_descale", k_descale, k_new, B, H_kv),
-                            v_descale=_kvcache_descale("v_descale", v_descale, k_new, B, H_kv), rotary_cos=rotary_cos,
+                            **_descale_views(k_descale, v_descale, k_new, B, H_kv), rotary_cos=rotary_cos,
                             rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
     return new_seqlens
 
@@ -337,8 +367,7 @@ def kvcache_append_varlen(K_cache, V_cache, k_new, v_new, cu_seqlens_new, max_se
     new_seqlens = torch.empty_like(cache_seqlens)
     _lib.fa2_kvcache_append_varlen(K_cache, V_cache, k_new, v_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, new_seqlens,
                                    convert_triton_dtype(k_new.dtype), convert_triton_dtype(K_cache.dtype), block_table=block_table,
-                                   k_descale=_kvcache_descale("k_descale", k_descale, k_new, B, H_kv),
-                                   v_descale=_kvcache_descale("v_descale", v_descale, k_new, B, H_kv), rotary_cos=rotary_cos,
+                                   **_descale_views(k_descale, v_descale, k_new, B, H_kv), rotary_cos=rotary_cos,
                                    rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
     return new_seqlens
 
@@ -352,16 +381,7 @@ def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k
             raise ValueError(f"kvcache: with block_table, Q must be (B, H, N_q, d) and K_cache, V_cache pools (num_blocks, H_kv, "
                              f"page_size, d) of one shape with N_q, num_blocks, page_size >= 1: got Q {tuple(Q.shape)}, K_cache "
                              f"{tuple(K_cache.shape)}, V_cache {tuple(V_cache.shape)}")
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 \
-                or block_table.shape[0] != Q.shape[0] or block_table.shape[1] < 1:
-            raise ValueError(f"kvcache: block_table must be an int32 tensor (B, max_blocks) with B = {Q.shape[0]}, max_blocks >= 1")
-        if block_table.stride(1) != 1 or block_table.stride(0) < 0:
-            raise ValueError(f"kvcache: block_table needs unit stride in its last axis, got strides {tuple(block_table.stride())}")
-        if block_table.device != Q.device:
-            raise ValueError(f"kvcache: block_table must be on Q's device ({Q.device}), got {block_table.device}")
-        if block_table.shape[1] * K_cache.shape[2] > 1 << 28:
-            raise ValueError(f"kvcache: the capacity max_blocks * page_size must be <= 2^28, got "
-                             f"{block_table.shape[1]} * {K_cache.shape[2]}")
+        _check_block_table(block_table, Q.shape[0], K_cache.shape[2], Q, "Q")
     elif Q.dim() != 4 or K_cache.dim() != 4 or V_cache.dim() != 4 or K_cache.shape != V_cache.shape \
             or Q.shape[0] != K_cache.shape[0] or Q.shape[3] != K_cache.shape[3] or Q.shape[2] < 1 or K_cache.shape[2] < 1:
         raise ValueError(f"kvcache: Q must be (B, H, N_q, d) and K_cache, V_cache (B, H_kv, S_k, d) with N_q, S_k >= 1: got Q "
@@ -384,11 +404,7 @@ def check_kvcache_args(Q, K_cache, V_cache, cache_seqlens, window, num_splits, k
             raise ValueError(f"kvcache: k_descale / v_descale go with an fp8 cache, not with {K_cache.dtype}")
     convert_triton_dtype(Q.dtype)
     if cache_seqlens is not None:
-        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 \
-                or not cache_seqlens.is_contiguous() or cache_seqlens.numel() != Q.shape[0]:
-            raise ValueError(f"kvcache: cache_seqlens must be a contiguous int32 tensor of B = {Q.shape[0]} entries (or None)")
-        if cache_seqlens.device != Q.device:
-            raise ValueError(f"kvcache: cache_seqlens must be on Q's device ({Q.device}), got {cache_seqlens.device}")
+        _check_cache_seqlens(cache_seqlens, Q.shape[0], Q, "Q", " (or None)")
     if window is not None:
         normalize_window(1, False, window)  # the sides' own rules (pair of ints >= -1); the shift is per sequence
     if isinstance(num_splits, bool) or not isinstance(num_splits, int) or not 0 <= num_splits <= _lib.KVCACHE_MAX_SPLITS:
@@ -447,24 +463,19 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
                               Q)
     if variant not in _lib.KVCACHE_VARIANTS:
         raise ValueError(f"kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
-    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
-        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+    _check_dev(dev, Q, K_cache, V_cache)
     B, H, N_q, d = Q.shape
     H_kv = K_cache.shape[1]
     dtype = convert_triton_dtype(Q.dtype)
-    O = torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device)
-    L = torch.empty(B, H, N_q, dtype=Q.dtype, device=Q.device)
-    S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
-    n = num_splits or _lib.kvcache_num_splits(B, H, H_kv, N_q, S_k, d, dtype)
-    ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    n = num_splits or _lib.kvcache_num_splits(B, H, H_kv, N_q, _capacity(K_cache, block_table), d, dtype)
+    O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d, n) if n > 1 else 0)
     if k_new is not None:
         if k_new.shape[0] != B or k_new.device != Q.device:
             raise ValueError(f"kvcache: k_new, v_new must have Q's batch size {B} and device ({Q.device}), got {tuple(k_new.shape)} on "
                              f"{k_new.device}")
         _lib.fa2_fwd_kvcache_append(Q, K_cache, V_cache, O, L, k_new, v_new, cache_seqlens, torch.empty_like(cache_seqlens), dtype,
                                     convert_triton_dtype(K_cache.dtype), block_table=block_table,
-                                    k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
-                                    v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), rotary_cos=rotary_cos,
+                                    **_descale_views(k_descale, v_descale, Q, B, H_kv), rotary_cos=rotary_cos,
                                     rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
                                     q_rot=None if rotary_cos is None else torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device),
                                     causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
@@ -472,14 +483,12 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
         return O, L
     if block_table is not None:
         _lib.fa2_fwd_kvcache_paged(Q, K_cache, V_cache, O, L, block_table, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
-                                   k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
-                                   v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), causal=causal, scale=scale,
+                                   **_descale_views(k_descale, v_descale, Q, B, H_kv), causal=causal, scale=scale,
                                    window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
         return O, L
     if K_cache.dtype in FP8_CACHE_DTYPES:
         _lib.fa2_fwd_kvcache_fp8(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
-                                 k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
-                                 v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), causal=causal, scale=scale,
+                                 **_descale_views(k_descale, v_descale, Q, B, H_kv), causal=causal, scale=scale,
                                  window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
         return O, L
     _lib.fa2_fwd_kvcache(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, causal=causal, scale=scale, window=window, num_splits=n,
@@ -505,16 +514,12 @@ def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale,
         raise ValueError(f"kvcache: with d_v != d, d must be in [1, 576] and d_v in [1, 512], got d = {d}, d_v = {d_v}")
     if variant not in _lib.KVCACHE_MLA_VARIANTS:
         raise ValueError(f"kvcache: with d_v != d, variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
-    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
-        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+    _check_dev(dev, Q, K_cache, V_cache)
     B, H, N_q, _ = Q.shape
     H_kv = K_cache.shape[1]
     dtype = convert_triton_dtype(Q.dtype)
-    O = torch.empty(B, H, N_q, d_v, dtype=Q.dtype, device=Q.device)
-    L = torch.empty(B, H, N_q, dtype=Q.dtype, device=Q.device)
-    S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
-    n = num_splits or _lib.kvcache_mla_num_splits(B, H, H_kv, N_q, S_k, d, d_v, dtype)
-    ws = torch.empty(_lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    n = num_splits or _lib.kvcache_mla_num_splits(B, H, H_kv, N_q, _capacity(K_cache, block_table), d, d_v, dtype)
+    O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d_v), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0)
     _lib.fa2_fwd_kvcache_mla(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, block_table=block_table, causal=causal, scale=scale,
                              window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
     return O, L
@@ -593,21 +598,16 @@ def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, ma
                               block_table, k_new, v_new, rotary_cos, rotary_sin)
     if variant not in _lib.KVCACHE_VARIANTS:
         raise ValueError(f"varlen kvcache: variant must be one of {sorted(_lib.KVCACHE_VARIANTS)}, got {variant!r}")
-    if Q.device != torch.device(dev) or K_cache.device != Q.device or V_cache.device != Q.device:
-        raise ValueError(f"dev={dev} is not the device of Q, K_cache, V_cache ({Q.device}, {K_cache.device}, {V_cache.device})")
+    _check_dev(dev, Q, K_cache, V_cache)
     total_q, H, d = Q.shape
     B, H_kv = cu_seqlens_q.numel() - 1, K_cache.shape[1]
     dtype = convert_triton_dtype(Q.dtype)
-    O = torch.empty(total_q, H, d, dtype=Q.dtype, device=Q.device)
-    L = torch.empty(H, total_q, dtype=Q.dtype, device=Q.device)
-    S_k = K_cache.shape[2] if block_table is None else block_table.shape[1] * K_cache.shape[2]  # the capacity
-    n = num_splits or _lib.kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, dtype)
-    ws = torch.empty(_lib.kvcache_varlen_workspace_bytes(total_q, H, d, n) // 4, dtype=torch.float32, device=Q.device) if n > 1 else None
+    n = num_splits or _lib.kvcache_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, _capacity(K_cache, block_table), d, dtype)
+    O, L, ws = _kvcache_outputs(Q, (total_q, H, d), (H, total_q), _lib.kvcache_varlen_workspace_bytes(total_q, H, d, n) if n > 1 else 0)
     if k_new is not None:
         _lib.fa2_fwd_kvcache_varlen_append(Q, K_cache, V_cache, O, L, k_new, v_new, cu_seqlens_q, max_seqlen_q, cache_seqlens,
                                            torch.empty_like(cache_seqlens), dtype, convert_triton_dtype(K_cache.dtype),
-                                           block_table=block_table, k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
-                                           v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), rotary_cos=rotary_cos,
+                                           block_table=block_table, **_descale_views(k_descale, v_descale, Q, B, H_kv), rotary_cos=rotary_cos,
                                            rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
                                            q_rot=None if rotary_cos is None else torch.empty(total_q, H, d, dtype=Q.dtype, device=Q.device),
                                            causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
@@ -615,7 +615,6 @@ def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, ma
         return O, L
     _lib.fa2_fwd_kvcache_varlen(Q, K_cache, V_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
                                 convert_triton_dtype(K_cache.dtype), block_table=block_table,
-                                k_descale=_kvcache_descale("k_descale", k_descale, Q, B, H_kv),
-                                v_descale=_kvcache_descale("v_descale", v_descale, Q, B, H_kv), causal=causal, scale=scale,
+                                **_descale_views(k_descale, v_descale, Q, B, H_kv), causal=causal, scale=scale,
                                 window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
     return O, L
