@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """MLA decode timing (fa2_fwd_kvcache_mla: d = 576, d_v = 512, V = K[..., :512]), bf16, H_kv = 1; JSON lines appended to
-profiles/mla/bench_mla_decode.jsonl.  The protocol is benchmarks/bench_decode.py's: kernel times come from a
+profiles/mla/bench_mla_decode.jsonl.  --kv-dtype e4m3 / e5m2: the same shapes, protocol and sides over an fp8 latent cache
+(fa2_fwd_kvcache_mla_fp8, the cache quantised by quantize_kv_cache with its per-sequence descale; sdpa on the dequantised bf16
+tensors); every record carries kv_dtype, and kv_bytes, hbm_share and cache_gbps count the cache's own bytes per key (576 for fp8).  The protocol is benchmarks/bench_decode.py's: kernel times come from a
 `rocprofv3 --kernel-trace --stats` child per shape (a fresh process, under its own `timeout -k 10`; the first non-zero status ends
 the run), every side rotates over enough copies of the latent cache to exceed the 256 MiB last-level cache, and avg, min-max and
 stddev are reported per call.
@@ -14,7 +16,7 @@ Sides of one child, each warmed (3 calls, not counted) and then run back to back
            reads the latent cache once (no mask: the benchmark's calls have none).
 The kernel trace is cut into the sides by dispatch order (split kernel plus combine per call; one kernel for num_splits = 1; the
 rest after the last decode kernel is sdpa's).  hbm_share counts 1,152 B per visible key ONCE over the side's kernel time, as a
-share of the 6.29 TB/s copy rate: a second row tile (128 heads, or 64 heads at N_q = 2) reads the keys again and is not counted.
+share of the 6.29 TB/s copy rate (cache_gbps: the same bytes over AUTO's time, in GB/s): a second row tile (128 heads, or 64 heads at N_q = 2) reads the keys again and is not counted.
 
 Records:
   kind=kernels        one per shape and cache form: the sides' avg / min / max / stddev in microseconds, auto_over_generic;
@@ -33,6 +35,7 @@ sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "mla", "bench_mla_decode.jsonl")
 HBM_COPY_RATE = 6.29e12  # bytes / s, measured copy rate of the MI355X
 D, D_V = 576, 512
+KV_DTYPES = ("bf16", "e4m3", "e5m2")
 
 SHAPES = ((1, 8192), (1, 65536), (16, 4096), (64, 2048), (128, 4096))  # (B, N_k)
 CASES = {f"h{H}_q{N_q}_b{B}_n{S}": (B, H, N_q, S) for H in (16, 128) for N_q in (1, 2) for B, S in SHAPES}
@@ -49,20 +52,28 @@ def emit(fh, **kw):
 
 
 class Case:
-    def __init__(self, name, dev, page_size=0):
+    def __init__(self, name, dev, page_size=0, kv_dtype="bf16"):
         import torch
+        import flash_attention_dlrs_amd as fa
         from flash_attention_dlrs_amd import _lib
         from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
         self.torch, self._lib, self.dev = torch, _lib, dev
         B, H, N_q, S = CASES[name]
         self.shape = dict(B=B, H=H, N_q=N_q, N_k=S)
-        self.kv_bytes = 2 * D * B * S
+        self.fmt = {"bf16": None, "e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}[kv_dtype]
+        self.kv_bytes = (1 if self.fmt else 2) * D * B * S
         self.copies = max(2, math.ceil(300e6 / self.kv_bytes))
         self.scale = D ** -0.5
         self.enum = convert_triton_dtype(torch.bfloat16)
         mk = lambda *s: (torch.randn(*s, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
         self.Q = mk(B, H, N_q, D)
         self.KV = [mk(B, 1, S, D) for _ in range(self.copies)]
+        self.KV16, self.descale, self.kv_enum = self.KV, None, self.enum  # KV16: what sdpa reads (fp8: the dequantised rows)
+        if self.fmt:
+            quant = [fa.quantize_kv_cache(t, self.fmt) for t in self.KV]
+            self.KV, self.descale = [q[0] for q in quant], [q[1] for q in quant]
+            self.KV16 = [fa.dequantize_kv_cache(k8, ds, torch.bfloat16) for k8, ds in quant]
+            self.kv_enum = convert_triton_dtype(self.fmt)
         self.lens = torch.full((B,), S, dtype=torch.int32, device=dev)
         self.O = torch.empty(B, H, N_q, D_V, dtype=torch.bfloat16, device=dev)
         self.L = torch.empty(B, H, N_q, dtype=torch.bfloat16, device=dev)
@@ -72,10 +83,11 @@ class Case:
             mb = S // page_size
             perm = torch.randperm(B * mb, generator=torch.Generator().manual_seed(0)).to(dev)
             self.table = perm.view(B, mb).to(torch.int32)
-            for k, t in enumerate(self.KV):
-                p = torch.empty(B * mb, 1, page_size, D, dtype=t.dtype, device=dev)
-                p[perm] = t.view(B * mb, 1, page_size, D)
-                self.KV[k] = p
+            for k, t in enumerate(self.KV):  # (scattered as raw bytes or words: the fp8 dtypes have no indexed copy)
+                raw = t.view(torch.uint8 if self.fmt else torch.int16).view(B * mb, 1, page_size, D)
+                p = torch.empty_like(raw)
+                p[perm] = raw
+                self.KV[k] = p.view(t.dtype)
 
     def auto_splits(self):
         s = self.shape
@@ -91,6 +103,12 @@ class Case:
         def run():
             self.i = (self.i + 1) % self.copies
             kv = self.KV[self.i]
+            if self.fmt:
+                ds = self.descale[self.i]
+                self._lib.fa2_fwd_kvcache_mla_fp8(self.Q, kv, kv[..., :D_V], self.O, self.L, self.lens, self.enum, self.kv_enum,
+                                                  k_descale=ds, v_descale=ds, block_table=self.table, scale=self.scale, num_splits=n,
+                                                  workspace=ws, variant=self._lib.KVCACHE_MLA_VARIANTS[variant])
+                return
             self._lib.fa2_fwd_kvcache_mla(self.Q, kv, kv[..., :D_V], self.O, self.L, self.lens, self.enum, block_table=self.table,
                                           scale=self.scale, num_splits=n, workspace=ws, variant=self._lib.KVCACHE_MLA_VARIANTS[variant])
         return run
@@ -100,7 +118,7 @@ class Case:
 
         def run():
             self.i = (self.i + 1) % self.copies
-            kv = self.KV[self.i]
+            kv = self.KV16[self.i]
             F.scaled_dot_product_attention(self.Q.view(self.Q.shape[0], 1, -1, D), kv, kv[..., :D_V], scale=self.scale)
         return run
 
@@ -113,7 +131,7 @@ def generic_iters(shape, iters):
 def run_pass(name, args):
     """The traced child: each side warmed, then run back to back; the kernel trace holds the times."""
     import torch
-    c = Case(name, torch.device("cuda:0"), args.page_size)
+    c = Case(name, torch.device("cuda:0"), args.page_size, args.kv_dtype)
     calls = {"auto": args.iters + 3, "generic": generic_iters(c.shape, args.iters) + 3}
     sides = [("auto", c.decode("auto")), ("generic", c.decode("generic"))]
     if not args.page_size and not args.no_sdpa:
@@ -123,25 +141,28 @@ def run_pass(name, args):
         for _ in range(calls[side]):
             f()
         torch.cuda.synchronize()
-    print(json.dumps(dict(case=name, calls=calls, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(), page_size=args.page_size, **c.shape)))
+    print(json.dumps(dict(case=name, calls=calls, kv_dtype=args.kv_dtype, kv_bytes=c.kv_bytes, num_splits=c.auto_splits(),
+                          page_size=args.page_size, **c.shape)))
 
 
 def run_sweep_pass(name, args):
     """The traced child of the split sweep: AUTO's variant alone, one split count after the other."""
     import torch
-    c = Case(name, torch.device("cuda:0"))
+    c = Case(name, torch.device("cuda:0"), kv_dtype=args.kv_dtype)
     for n in SWEEP_SPLITS:
         f = c.decode("auto", n)
         for _ in range(args.iters + 3):
             f()
         torch.cuda.synchronize()
-    print(json.dumps(dict(case=name, calls=args.iters + 3, auto_splits=c.auto_splits(), kv_bytes=c.kv_bytes, **c.shape)))
+    print(json.dumps(dict(case=name, calls=args.iters + 3, kv_dtype=args.kv_dtype, auto_splits=c.auto_splits(), kv_bytes=c.kv_bytes,
+                          **c.shape)))
 
 
 def traced_child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
-           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--page-size", str(args.page_size)] + extra + \
+           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--page-size", str(args.page_size), "--kv-dtype", args.kv_dtype] + \
+        extra + \
         (["--no-sdpa"] if args.no_sdpa else [])
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
@@ -155,9 +176,9 @@ def trace_rows(out):
     return sorted(csv.DictReader(open(trace[0])), key=lambda r: int(r["Start_Timestamp"]))
 
 
-def per_call(seg, per, calls):
-    """avg / min / max / stddev of the kernel time per call, the first 3 calls (warm-up) left out"""
-    us = [sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg[per * k:per * k + per]) / 1e3 for k in range(3, calls)]
+def per_call(seg, per, calls, warm=3):
+    """avg / min / max / stddev of the kernel time per call, the first `warm` calls (warm-up) left out"""
+    us = [sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg[per * k:per * k + per]) / 1e3 for k in range(warm, calls)]
     avg = sum(us) / len(us)
     return dict(avg_us=round(avg, 2), min_us=round(min(us), 2), max_us=round(max(us), 2),
                 stddev_us=round((sum((u - avg) ** 2 for u in us) / len(us)) ** 0.5, 2), calls=len(us),
@@ -173,24 +194,31 @@ def sides_from_trace(out, info):
     fa = [rows[k] for k in dec]
     sides = {"auto": per_call(fa[:per * na], per, na), "generic": per_call(fa[per * na:], per, ng)}
     if "sdpa" in info["calls"]:
-        rest, ns = rows[dec[-1] + 1:], info["calls"]["sdpa"]
-        if rest and len(rest) % ns == 0:
-            sides["sdpa"] = per_call(rest, len(rest) // ns, ns)
+        # torch's first calls may launch kernels the later ones do not: the timed calls are cut from the END of the trace, by the
+        # shortest period in which the kernel names of the last ns - 3 calls repeat
+        rest, timed = rows[dec[-1] + 1:], info["calls"]["sdpa"] - 3
+        names = [r["Kernel_Name"] for r in rest]
+        per = next((p for p in range(1, len(names) // timed + 1)
+                    if all(names[-k - 1] == names[-k - 1 - p] for k in range(p * (timed - 1)))), 0)
+        if per:
+            sides["sdpa"] = per_call(rest[-per * timed:], per, timed, warm=0)
     return sides
 
 
 def run_rocprof(names, args, fh):
     for name in names:
-        out = os.path.join(args.rocprof, name + (f"_p{args.page_size}" if args.page_size else ""))
+        out = os.path.join(args.rocprof, name + (f"_p{args.page_size}" if args.page_size else "") +
+                           ("" if args.kv_dtype == "bf16" else "_" + args.kv_dtype))
         info = traced_child(out, ["--pass-case", name], args)
         sides = sides_from_trace(out, info)
         a, g = sides["auto"], sides["generic"]
         emit(fh, kind="kernels", **{k: v for k, v in info.items() if k != "calls"},
              hbm_share=round(info["kv_bytes"] / (a["avg_us"] * 1e-6) / HBM_COPY_RATE, 3),
+             cache_gbps=round(info["kv_bytes"] / (a["avg_us"] * 1e-6) / 1e9, 1),
              hbm_share_generic=round(info["kv_bytes"] / (g["avg_us"] * 1e-6) / HBM_COPY_RATE, 3),
              auto_over_generic=round(a["avg_us"] / g["avg_us"], 4), ranges_overlap=a["max_us"] >= g["min_us"], **sides)
         if args.sweep and name in SWEEP_CASES and not args.page_size:
-            out = os.path.join(args.rocprof, name + "_sweep")
+            out = os.path.join(args.rocprof, name + "_sweep" + ("" if args.kv_dtype == "bf16" else "_" + args.kv_dtype))
             info = traced_child(out, ["--sweep-case", name], args)
             rows = [r for r in trace_rows(out) if "fa2_decode" in r["Kernel_Name"]]
             pos, calls = 0, info["calls"]
@@ -198,7 +226,7 @@ def run_rocprof(names, args, fh):
                 per = 1 if n == 1 else 2
                 r = per_call(rows[pos:pos + per * calls], per, calls)
                 pos += per * calls
-                emit(fh, kind="sweep_kernels", case=name, num_splits=n, auto_splits=info["auto_splits"],
+                emit(fh, kind="sweep_kernels", case=name, kv_dtype=args.kv_dtype, num_splits=n, auto_splits=info["auto_splits"],
                      hbm_share=round(info["kv_bytes"] / (r["avg_us"] * 1e-6) / HBM_COPY_RATE, 3), **r)
             assert pos == len(rows)
 
@@ -213,6 +241,7 @@ def main():
                     help="the traces of the rocprofv3 children go under DIR")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--page-size", type=int, default=0, metavar="N", help="the paged cache at N-key pages (64) in the contiguous one's place")
+    ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="bf16", help="the latent cache's storage: bf16, or fp8 with its descale")
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)

@@ -55,7 +55,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_kvcache", "fa2_fwd_kvcache_variant", "fa2_fwd_kvcache_fp8", "fa2_fwd_kvcache_paged",
            "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append",
            "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits",
-           "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits")
+           "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits",
+           "fa2_fwd_kvcache_mla_fp8")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -199,6 +200,10 @@ def lib():
         # fa2_fwd_kvcache_paged's order without the descales, d_v after d, no kv_dtype_enum
         l.fa2_fwd_kvcache_mla.restype = ctypes.c_int
         l.fa2_fwd_kvcache_mla.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64] + [ctypes.c_int32] * 11 + \
+            [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # ... over an fp8 latent cache: fa2_fwd_kvcache_paged's order with d_v after d
+        l.fa2_fwd_kvcache_mla_fp8.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_fp8.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64, vp, vp, i64p, i64p] + [ctypes.c_int32] * 12 + \
             [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_mla_num_splits.restype = ctypes.c_int32
         l.fa2_kvcache_mla_num_splits.argtypes = [ctypes.c_int32] * 8
@@ -532,6 +537,23 @@ def fa2_fwd_kvcache_mla(Q, K, V, O, L, cache_seqlens, dtype_enum, block_table=No
             None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, B, H, K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum),
             int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
             int(variant), _raw_stream(Q.device.index))
+
+
+def fa2_fwd_kvcache_mla_fp8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_enum, k_descale=None, v_descale=None, block_table=None,
+                            causal=False, scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch fa2_fwd_kvcache_mla over an fp8 latent cache (include/fa2_fwd.h fa2_fwd_kvcache_mla_fp8) on the current stream of Q's
+    device.  As fa2_fwd_kvcache_mla, with K / V in kv_dtype_enum (an fp8 format; dtype_enum itself: the 16-bit call) and k_descale /
+    v_descale as in fa2_fwd_kvcache_fp8: float32 tensors on the device viewed as (B, H_kv), or None for 1."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    tb_ptr, tb_st, _, nb, _, mb = _table_args(K, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla_fp8, Q,
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, *_descale_args(k_descale, v_descale), B, H,
+            K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale),
+            *_window_sides(window), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
 
 
 def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):

@@ -56,6 +56,35 @@ __device__ __forceinline__ float fa2_decode_descale(const float *p, int64_t s0, 
     return p ? p[b * s0 + hk * s1] : 1.0f;
 }
 
+// Cache element types of the matrix forms other than the I/O type T (fa2_decode_mfma16.hip, fa2_decode_mla16.hip): OCP e4m3fn and
+// e5m2, one byte each.  CacheCvt<T, C>::cvt<HI>(w) converts bytes 2 HI, 2 HI + 1 of a word to a pair of T with v_cvt_scalef32_pk_*
+// at scale 1.0: exactly, both formats are subsets of f16 and of bf16.
+struct CacheE4M3 {};
+struct CacheE5M2 {};
+typedef __attribute__((ext_vector_type(2))) __bf16 fa2_bf16x2;
+typedef __attribute__((ext_vector_type(2))) _Float16 fa2_f16x2;
+template <typename T, typename C> struct CacheCvt;
+template <> struct CacheCvt<__bf16, CacheE4M3> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (fa2_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+    }
+};
+template <> struct CacheCvt<__bf16, CacheE5M2> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (fa2_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w, 1.0f, HI));
+    }
+};
+template <> struct CacheCvt<_Float16, CacheE4M3> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (fa2_f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
+    }
+};
+template <> struct CacheCvt<_Float16, CacheE5M2> {
+    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
+        return __builtin_bit_cast(unsigned, (fa2_f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w, 1.0f, HI));
+    }
+};
+
 // A block-table entry as the kernels use it: clamped into the pool, so a wild entry cannot become an access outside it.
 __device__ __forceinline__ int fa2_decode_page(const int32_t *table, int64_t i, int num_blocks) {
     const int e = table[i];

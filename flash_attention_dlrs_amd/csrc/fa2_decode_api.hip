@@ -1,5 +1,5 @@
-// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache call
-// _mla, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps fa2_fwd_kvcache_append
+// fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache calls
+// _mla and _mla_fp8, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps fa2_fwd_kvcache_append
 // and _varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
 //   1. fill   the entry point names its raw arguments in a DecodeCall (the cache update's in an AppendCall), packed strides through packed4;
 //   2. check  check_decode (check_append) tests every argument, resolves num_splits (split_count on the unsplit workgroup count of the
@@ -101,7 +101,7 @@ struct DecodeCall {
     bool packed = false;  // fa2_fwd_kvcache_varlen: Q, O are (total_q, H, d) over cu_seqlens_q, L is (H, total_q)
     const int32_t *cu_seqlens_q = nullptr;
     int32_t total_q = 0, max_seqlen_q = 0;
-    bool mla = false;  // fa2_fwd_kvcache_mla: V is (B, H_kv, S_k, d_v), d may reach 576; without it d_v = d
+    bool mla = false;  // fa2_fwd_kvcache_mla, _mla_fp8 (with `fp8`): V is (B, H_kv, S_k, d_v), d may reach 576; without it d_v = d
     int32_t d_v = 0;
 };
 
@@ -608,6 +608,28 @@ int fa2_fwd_kvcache_mla(const void *Q, const void *K, const void *V, void *O, vo
     c.causal = causal; c.scale = scale; c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits;
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.mla = true; c.d_v = d_v;
     c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    return decode(c, nullptr);
+}
+
+int fa2_fwd_kvcache_mla_fp8(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                            const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                            const int64_t l_strides[2], const int32_t *cache_seqlens, const int32_t *block_table,
+                            int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                            const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                            int32_t N_q, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                            int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale, int32_t window_left,
+                            int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
+                            void *hip_stream) {
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    // (block_table null: the contiguous cache, page_size carries S_k, as in fa2_fwd_kvcache_mla)
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = block_table ? 0 : page_size; c.d = d; c.dtype_enum = dtype_enum;
+    c.causal = causal; c.scale = scale; c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;  // (a cache in Q's dtype: no descales, fa2_fwd_kvcache_mla's launch)
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
     return decode(c, nullptr);
 }
 

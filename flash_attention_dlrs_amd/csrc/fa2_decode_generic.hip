@@ -15,7 +15,8 @@
 //
 // fp8 cache (fa2_fwd_kvcache_fp8): the element type C of K and V is a template parameter beside E, that of Q, O and L.  An
 // e4m3fn / e5m2 element is converted (exactly) as it is loaded; the descales kd, vd at [b, h_kv] are folded: kd into the
-// softmax scale, vd into the fp32 normalised output before it is rounded or written as a partial.
+// softmax scale, vd into the fp32 normalised output before it is rounded or written as a partial.  C and (d, d_v) are independent:
+// fa2_fwd_kvcache_mla_fp8 reaches the fp8 instantiations with d up to 576 and a d_v of its own.
 //
 // Paged cache (fa2_fwd_kvcache_paged): PAGED is a template parameter as well, K and V a page pool behind a block table, any
 // page_size >= 1.  Key j of sequence b is row j % page_size of page table[b][j / page_size], the entry clamped to

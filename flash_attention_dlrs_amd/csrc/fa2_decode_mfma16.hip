@@ -76,32 +76,7 @@ template <> struct Mma<_Float16> {
     }
 };
 
-// Cache element types other than T.  cvt(w, hi) converts bytes 2 hi, 2 hi + 1 of a word to a pair of T, exactly.
-struct CacheE4M3 {};
-struct CacheE5M2 {};
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-template <typename T, typename C> struct CacheCvt;
-template <> struct CacheCvt<__bf16, CacheE4M3> {
-    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
-        return __builtin_bit_cast(unsigned, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-    }
-};
-template <> struct CacheCvt<__bf16, CacheE5M2> {
-    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
-        return __builtin_bit_cast(unsigned, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w, 1.0f, HI));
-    }
-};
-template <> struct CacheCvt<_Float16, CacheE4M3> {
-    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
-        return __builtin_bit_cast(unsigned, (f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
-    }
-};
-template <> struct CacheCvt<_Float16, CacheE5M2> {
-    template <bool HI> static __device__ __forceinline__ unsigned cvt(unsigned w) {
-        return __builtin_bit_cast(unsigned, (f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w, 1.0f, HI));
-    }
-};
+// (the cache element types other than T, CacheE4M3 / CacheE5M2, and their exact conversion CacheCvt: fa2_decode.h)
 
 struct DecodeMfmaArgs {
     const char *Q, *K, *V;

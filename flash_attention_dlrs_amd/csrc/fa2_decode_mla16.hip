@@ -1,5 +1,6 @@
-// fa2_decode_mla16.hip -- KV-cache decode over a shared latent cache (fa2_fwd_kvcache_mla, FA2_KVCACHE_VARIANT_MLA16): multi-head
-// latent attention in its absorbed form, f16 / bf16, d = 576 (512 latent + 64 rotary columns), d_v = 512, V = K[..., :512].
+// fa2_decode_mla16.hip -- KV-cache decode over a shared latent cache (fa2_fwd_kvcache_mla and _mla_fp8, FA2_KVCACHE_VARIANT_MLA16):
+// multi-head latent attention in its absorbed form, f16 / bf16 (the cache alike, or fp8 storage), d = 576 (512 latent + 64 rotary
+// columns), d_v = 512, V = K[..., :512].
 //
 // One workgroup of four waves handles one (split, 64-row tile of a KV group, KV head, sequence): the grid is
 // (num_splits * row_tiles, H_kv, B), row r = head-in-group * N_q + query as in fa2_decode_mfma16.hip, a last tile with fewer
@@ -23,6 +24,18 @@
 // Staging goes through registers while the previous tile is computed (single-buffered, 18 x 16 bytes per thread): a wave loads
 // 16 rows, chunks 0..63 of a row with one instruction (1 KiB contiguous) and the last 8 chunks of 8 rows with another, so no
 // load crosses a row.  Addresses are 64-bit per thread.
+//
+// fp8 latent cache (fa2_fwd_kvcache_mla_fp8).  The cache element type C is a template parameter: T itself, or OCP e4m3fn / e5m2 with
+// per-(b, h_kv) descales kd, vd.  Only staging differs: a row is 576 B = 36 loads of 16 bytes, a load holds 16 elements that
+// CacheCvt (fa2_decode.h) converts exactly to the two 16-byte LDS chunks 2c and 2c + 1 of the same image, so a thread stages 9
+// loads per tile instead of 18.  A wave's 16 rows are 576 loads = 9 passes of 64 lanes under the flat index f = 64 pass + lane ->
+// (row f / 36, load f % 36): consecutive lanes read consecutive 16-byte pieces (a pass is 1 KiB in at most three rows) and no load
+// crosses a row.  Of its two chunks a lane writes chunk 2c + (c >> 2 & 1) first and the other one second: the eight lanes of a
+// ds_write_b128 group then hit eight distinct 16-byte slots of the 128-B bank row (2c alone would be four slots, twice each), as
+// the 16-bit map's 64 consecutive chunks do; only a group that straddles a row keeps a 2-way conflict.  The descales are folded,
+// not applied per element: kd into the softmax scale of the workgroup, vd into the fp32 normalisation of the output, before it
+// is rounded or written as a partial (K and V are the same bytes, the two descales still independent scalars).  A row past the
+// split's end is zeros before the conversion: no stale byte, NaN and inf patterns included, is ever converted.
 //
 // Stale cache contents: a key at or past the split's end (<= N_k(b)) is not loaded -- its row is written to LDS as zeros and its
 // score is selected to -inf -- so what lies behind cache_seqlens[b] is never read.  Paged cache: page_size % 64 == 0, a key
@@ -73,6 +86,8 @@ struct DecodeMlaArgs {
     const int32_t *table;  // paged cache only: entry [b, i] at b * table_stride + i; ks[0] is the block stride
     int64_t table_stride;
     int page_size, num_blocks;
+    const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
+    int64_t kds[2], vds[2];
 };
 
 constexpr int kD = 576, kDV = 512, kBC = 64;
@@ -88,13 +103,17 @@ constexpr int kXlOff = kCfOff + 256;         // [2][64]: a row's sum over each k
 constexpr int kMfOff = kXlOff + 512;         // [64]: a row's maximum (epilogue)
 constexpr int kSmem = kMfOff + 256;
 constexpr int kStage = kCPR * kBC / 256;     // 18 16-byte loads per thread and tile
-static_assert(kStage == 18 && kSmem <= 160 * 1024, "one workgroup per CU");
+constexpr int kLPR8 = kD / 16;               // fp8 cache: 36 16-byte loads per cache row, each two LDS chunks
+constexpr int kStage8 = kLPR8 * kBC / 256;   //            9 loads per thread and tile
+static_assert(kStage == 18 && kStage8 == 9 && kSmem <= 160 * 1024, "one workgroup per CU");
 
 // Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: fa2_decode_mfma16.hip's swizzle at d = 128.
 __device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4); }
 
-template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
+// T: Q, O, L and the matrix arithmetic; C: the cache (T, or an fp8 format converted while it is staged).
+template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
     using M = Mma<T>;
+    constexpr bool F8 = !__is_same(C, T);
     using frag = typename M::frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LDS_PTR(char) lds = (LDS_PTR(char))smem;
@@ -133,10 +152,14 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
 
     // ---- staging map.  Wave w stages tile rows 16w .. 16w + 15: pass it < 16 is row 16w + it, chunks 0..63 (one per lane); pass
     // 16 + jb is rows 16w + 8jb + (lane >> 3), chunks 64 + (lane & 7).  (paged: the page's offset joins in stage_load)
+    // fp8 cache: pass ps < 9 is load f % 36 of row 16w + f / 36, f = 64 ps + lane (the file's head).
     const int sb_row = 16 * wave + (lane >> 3), sb_ch = 64 + (lane & 7);
     const char *kbase = a.K + hk * a.ks[1] + (PAGED ? 0 : b * a.ks[0] + (int64_t)kb0 * a.ks[2]);
-    const char *kg_a = kbase + (int64_t)(16 * wave) * a.ks[2] + lane * 16;
+    const char *kg_w = kbase + (int64_t)(16 * wave) * a.ks[2];  // the wave's first row
+    const char *kg_a = kg_w + lane * 16;
     const char *kg_b = kbase + (int64_t)sb_row * a.ks[2] + sb_ch * 16;
+    auto f8_row = [&](int ps) { return (64 * ps + lane) / kLPR8; };  // < 16
+    auto f8_ld = [&](int ps) { return (64 * ps + lane) % kLPR8; };
 
     // paged: the walk over the pages, as in fa2_decode_mfma16.hip: stage_load takes the tiles in order, a tile is 64 keys on a
     // multiple of 64 and page_size is a multiple of 64, so (pg_i, pg_row) advance by 64 rows per tile and wrap at page_size.
@@ -147,7 +170,7 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
         pg_row = kb0 - pg_i * a.page_size;
         tab = a.table + b * a.table_stride;
     }
-    u32x4 sreg[kStage];
+    u32x4 sreg[F8 ? kStage8 : kStage];
     auto stage_load = [&](int t) {
         const int rel = t * kBC;  // the tile's first key, relative to kb0
         int64_t toff = (int64_t)rel * a.ks[2];
@@ -161,22 +184,47 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
                 ++pg_i;
             }
         }
+        if constexpr (F8) {
 #pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const bool ok = kb0 + rel + 16 * wave + it < ke;  // past the split's end (<= N_k): zeros, never read
-            sreg[it] = ok ? *(const u32x4 *)(kg_a + toff + (int64_t)it * a.ks[2]) : u32x4{0, 0, 0, 0};
-        }
+            for (int ps = 0; ps < kStage8; ++ps) {
+                const int row = f8_row(ps);
+                const bool ok = kb0 + rel + 16 * wave + row < ke;  // past the split's end (<= N_k): zeros, never read
+                sreg[ps] = ok ? *(const u32x4 *)(kg_w + toff + (int64_t)row * a.ks[2] + f8_ld(ps) * 16) : u32x4{0, 0, 0, 0};
+            }
+        } else {
 #pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-            const bool ok = kb0 + rel + sb_row + 8 * jb < ke;
-            sreg[16 + jb] = ok ? *(const u32x4 *)(kg_b + toff + (int64_t)(8 * jb) * a.ks[2]) : u32x4{0, 0, 0, 0};
+            for (int it = 0; it < 16; ++it) {
+                const bool ok = kb0 + rel + 16 * wave + it < ke;  // past the split's end (<= N_k): zeros, never read
+                sreg[it] = ok ? *(const u32x4 *)(kg_a + toff + (int64_t)it * a.ks[2]) : u32x4{0, 0, 0, 0};
+            }
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb) {
+                const bool ok = kb0 + rel + sb_row + 8 * jb < ke;
+                sreg[16 + jb] = ok ? *(const u32x4 *)(kg_b + toff + (int64_t)(8 * jb) * a.ks[2]) : u32x4{0, 0, 0, 0};
+            }
         }
     };
     auto stage_write = [&]() {
+        if constexpr (F8) {  // word j of the load = elements 4j .. 4j + 3 = words 2j, 2j + 1 of the 16-bit row
+            using X = CacheCvt<T, C>;
 #pragma unroll
-        for (int it = 0; it < 16; ++it) *(LDS_PTR(u32x4))(lds + lds_off(16 * wave + it, lane)) = sreg[it];
+            for (int ps = 0; ps < kStage8; ++ps) {
+                const u32x4 w = sreg[ps];
+                const u32x4 c0 = {X::template cvt<false>(w[0]), X::template cvt<true>(w[0]), X::template cvt<false>(w[1]),
+                                  X::template cvt<true>(w[1])};
+                const u32x4 c1 = {X::template cvt<false>(w[2]), X::template cvt<true>(w[2]), X::template cvt<false>(w[3]),
+                                  X::template cvt<true>(w[3])};
+                const int row = 16 * wave + f8_row(ps), ld = f8_ld(ps);
+                const bool odd_first = (ld & 4) != 0;  // which of chunks 2 ld, 2 ld + 1 goes first: the bank rule at the file's head
+                *(LDS_PTR(u32x4))(lds + lds_off(row, 2 * ld + (odd_first ? 1 : 0))) = odd_first ? c1 : c0;
+                *(LDS_PTR(u32x4))(lds + lds_off(row, 2 * ld + (odd_first ? 0 : 1))) = odd_first ? c0 : c1;
+            }
+        } else {
 #pragma unroll
-        for (int jb = 0; jb < 2; ++jb) *(LDS_PTR(u32x4))(lds + lds_off(sb_row + 8 * jb, sb_ch)) = sreg[16 + jb];
+            for (int it = 0; it < 16; ++it) *(LDS_PTR(u32x4))(lds + lds_off(16 * wave + it, lane)) = sreg[it];
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb) *(LDS_PTR(u32x4))(lds + lds_off(sb_row + 8 * jb, sb_ch)) = sreg[16 + jb];
+        }
     };
 
     // ---- per-lane LDS offsets.  K row read: row 32kb + i, chunk 2ks + h.  V transposed read (ds_read_b64_tr_b16): lane 4q + p of a
@@ -207,7 +255,12 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[db][rbp][r] = 0.0f;
     float m = -INFINITY, lsum = 0.0f;  // of the S-phase row, lsum over this wave's key block only
-    const float c = a.c_log2e;
+    // fp8: one scalar load per descale and workgroup.  S = (scale kd) Q K8^T; vd waits in a scalar register for the epilogue.
+    float c = a.c_log2e, vd = 1.0f;
+    if constexpr (F8) {
+        c *= fa2_decode_descale(a.kd, a.kds[0], a.kds[1], b, hk);
+        vd = fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
+    }
     // this row's visible keys [lo, hi], and whether a tile can meet a band edge of any row
     const int lo = sqi - wl, hi = (sqi + wr) < (ke - 1) ? (sqi + wr) : (ke - 1);
     const int lo_max = N_q - 1 - wl, hi_min = wr < (ke - 1) ? wr : (ke - 1);
@@ -325,7 +378,8 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
         const float l = xl[32 * rbp + i] + xl[64 + 32 * rbp + i];
         const float mr = mf[32 * rbp + i];
         const bool seen = l > 0.0f;
-        const float inv = seen ? 1.0f / l : 0.0f;
+        float inv = seen ? 1.0f / l : 0.0f;
+        if constexpr (F8) inv = seen ? inv * vd : 0.0f;  // O = vd (P V8) / l, in fp32
         if (a.num_splits == 1) {
             char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)qi * a.os[2] + (128 * wave + 4 * h) * 2;
 #pragma unroll
@@ -360,7 +414,7 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
     }
 }
 
-template <typename T, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
+template <typename T, typename C, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
     const long long gx = (long long)p.num_splits * a.row_tiles;
     if (gx > 0x7fffffffLL) {
         fa2_set_error("kvcache mla16 kernel: grid too large (num_splits * row tiles = %lld)", gx);
@@ -368,11 +422,11 @@ template <typename T, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const 
     }
     static Fa2DeviceLatch attr_done;  // more than 64 KiB of dynamic LDS: opt in, once per device
     if (attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, PAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
+        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, C, PAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
         attr_done.mark();
     }
     const dim3 grid((unsigned)gx, p.H_kv, p.B), block(256);
-    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, PAGED>), grid, block, kSmem, p.stream, a);
+    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, C, PAGED>), grid, block, kSmem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mla16 kernel launch failed: %s", hipGetErrorString(e));
@@ -381,25 +435,34 @@ template <typename T, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const 
     return FA2_OK;
 }
 
-template <typename T> int launch_p(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
-    return p.table ? launch_t<T, true>(p, a) : launch_t<T, false>(p, a);
+template <typename T, typename C> int launch_p(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
+    return p.table ? launch_t<T, C, true>(p, a) : launch_t<T, C, false>(p, a);
 }
+
+template <typename T> int launch_c(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
+    if (p.kv_dtype == FA2_DTYPE_F8E4M3) return launch_p<T, CacheE4M3>(p, a);
+    if (p.kv_dtype == FA2_DTYPE_F8E5M2) return launch_p<T, CacheE5M2>(p, a);
+    return launch_p<T, T>(p, a);
+}
+
+bool fp8_cache(const Fa2DecodeProblem &p) { return p.kv_dtype == FA2_DTYPE_F8E4M3 || p.kv_dtype == FA2_DTYPE_F8E5M2; }
 
 bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace
 
 bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p) {
-    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || p.kv_dtype != p.dtype || p.cu_q) return false;
+    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || (p.kv_dtype != p.dtype && !fp8_cache(p)) || p.cu_q) return false;
     if (p.V != p.K) return false;  // the value operand is read from K's LDS image
     for (int k = 0; k < 4; ++k)
         if (p.vs[k] != p.ks[k]) return false;
     if (!(p.scale > 0.0f) || !(p.scale < INFINITY)) return false;
     if ((int64_t)(p.H / p.H_kv) * p.N_q > (1 << 24)) return false;  // (rows of a KV group are counted in 32 bits)
     if (p.qs[3] != 1 || p.ks[3] != 1 || p.os[3] != 1) return false;
-    // 16-byte vector loads of Q and K rows, 8-byte stores of O: every row start must stay aligned
+    // 16-byte vector loads of Q and K rows, 8-byte stores of O: every row start must stay aligned (an fp8 cache: 16 elements)
+    const int64_t kmask = fp8_cache(p) ? 15 : 7;
     for (int k = 0; k < 3; ++k)
-        if ((p.qs[k] & 7) || (p.ks[k] & 7) || (p.os[k] & 7)) return false;
+        if ((p.qs[k] & 7) || (p.ks[k] & kmask) || (p.os[k] & 7)) return false;
     if (!aligned16(p.Q) || !aligned16(p.K) || !aligned16(p.O)) return false;
     if (p.num_splits > 1 && !aligned16(p.o_part)) return false;
     // paged: a 64-key tile must lie inside one page; the block stride is ks[0] above
@@ -410,14 +473,16 @@ bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p) {
 int fa2_launch_decode_mla16(const Fa2DecodeProblem &p) {
     if (!fa2_decode_mla16_supports(p)) {
         fa2_set_error("kvcache mla16 kernel: needs f16/bf16, d = 576 and d_v = 512, V aliasing K (the same pointer and strides), unit "
-                      "d-stride, 16-byte aligned rows (and workspace), scale > 0%s",
+                      "d-stride, 16-byte aligned rows (and workspace), scale > 0%s%s",
+                      fp8_cache(p) ? "; an fp8 cache: every stride of K a multiple of 16 elements and a 16-byte aligned base" : "",
                       p.table ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
         return FA2_ERR_UNSUPPORTED;
     }
     DecodeMlaArgs a;
     a.Q = (const char *)p.Q; a.K = (const char *)p.K;
     a.O = (char *)p.O; a.L = (char *)p.L;
-    for (int k = 0; k < 3; ++k) { a.qs[k] = p.qs[k] * 2; a.ks[k] = p.ks[k] * 2; a.os[k] = p.os[k] * 2; }
+    const int64_t cb = fp8_cache(p) ? 1 : 2;  // bytes per cache element
+    for (int k = 0; k < 3; ++k) { a.qs[k] = p.qs[k] * 2; a.ks[k] = p.ks[k] * cb; a.os[k] = p.os[k] * 2; }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
     a.seqlens = p.seqlens;
     a.H = p.H; a.g = p.H / p.H_kv; a.N_q = p.N_q; a.S_k = p.S_k; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
@@ -426,5 +491,7 @@ int fa2_launch_decode_mla16(const Fa2DecodeProblem &p) {
     a.o_part = p.o_part; a.l_part = p.l_part;
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
-    return p.dtype == FA2_DTYPE_BF16 ? launch_p<__bf16>(p, a) : launch_p<_Float16>(p, a);
+    a.kd = p.kd; a.vd = p.vd;
+    for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+    return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }

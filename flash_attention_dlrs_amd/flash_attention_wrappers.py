@@ -452,7 +452,8 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
     V_cache = K_cache[..., :512] (flash_attention_mla_decode_forward passes exactly that).  variant is then one of
     _lib.KVCACHE_MLA_VARIANTS: "mla16" (f16 / bf16, d = 576, d_v = 512, V_cache that view of K_cache, unit d-stride and 16-byte
     aligned rows, contiguous or paged with page_size % 64 == 0), "generic" (everything else), "auto".  Out of scope with d_v != d,
-    each a ValueError: an fp8 cache, k_descale / v_descale, k_new / v_new (MLA rotates the last 64 columns and writes ONE tensor:
+    each a ValueError: an fp8 cache and k_descale / v_descale (flash_attention_mla_decode_forward takes an fp8 latent cache with its
+    one kv_descale), k_new / v_new (MLA rotates the last 64 columns and writes ONE tensor:
     kvcache_append does neither) and the rotary arguments; so is flash_attention_varlen_kvcache_forward."""
     if isinstance(K_cache, torch.Tensor) and isinstance(V_cache, torch.Tensor) and K_cache.dim() == 4 and V_cache.dim() == 4 \
             and K_cache.shape[:3] == V_cache.shape[:3] and K_cache.shape[3] != V_cache.shape[3]:
@@ -497,18 +498,25 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
 
 
 def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale, window, num_splits, variant, k_descale, v_descale,
-                         block_table, k_new, v_new, rotary_cos, rotary_sin):
-    """flash_attention_kvcache_forward with a V_cache whose last axis differs from K_cache's (fa2_fwd_kvcache_mla)."""
-    if K_cache.dtype in FP8_CACHE_DTYPES or V_cache.dtype in FP8_CACHE_DTYPES:
-        raise ValueError(f"kvcache: an fp8 K_cache / V_cache ({K_cache.dtype}) is not supported with d_v != d")
+                         block_table, k_new, v_new, rotary_cos, rotary_sin, latent=False, kv_descale=None):
+    """flash_attention_kvcache_forward with a V_cache whose last axis differs from K_cache's (fa2_fwd_kvcache_mla), and -- latent:
+    flash_attention_mla_decode_forward alone -- an fp8 cache with its one descale (fa2_fwd_kvcache_mla_fp8)."""
+    fp8 = K_cache.dtype in FP8_CACHE_DTYPES or V_cache.dtype in FP8_CACHE_DTYPES
+    if fp8 and not latent:
+        raise ValueError(f"kvcache: an fp8 K_cache / V_cache ({K_cache.dtype}) is not supported with d_v != d here: "
+                         f"flash_attention_mla_decode_forward takes an fp8 latent cache (kv_descale)")
     for name, t in (("k_descale", k_descale), ("v_descale", v_descale), ("k_new", k_new), ("v_new", v_new), ("rotary_cos", rotary_cos),
                     ("rotary_sin", rotary_sin)):
         if t is not None:
             raise ValueError(f"kvcache: {name} is not supported with d_v != d (V_cache {tuple(V_cache.shape)} under K_cache "
-                             f"{tuple(K_cache.shape)})")
+                             f"{tuple(K_cache.shape)})" + (": flash_attention_mla_decode_forward takes an fp8 latent cache "
+                                                           "(kv_descale)" if name.endswith("descale") else ""))
     check_kvcache_args(Q, K_cache, K_cache, cache_seqlens, window, num_splits, None, None, block_table)
     if V_cache.dtype != K_cache.dtype:
         raise ValueError("kvcache: K_cache and V_cache must have the same dtype")
+    if kv_descale is not None and not fp8:
+        raise ValueError(f"mla decode: kv_descale goes with an fp8 KV_cache, not with {K_cache.dtype}")
+    kv_descale = _kvcache_descale("kv_descale", kv_descale, Q, Q.shape[0], K_cache.shape[1])
     d, d_v = K_cache.shape[3], V_cache.shape[3]
     if not 1 <= d <= 576 or not 1 <= d_v <= 512:
         raise ValueError(f"kvcache: with d_v != d, d must be in [1, 576] and d_v in [1, 512], got d = {d}, d_v = {d_v}")
@@ -520,26 +528,40 @@ def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale,
     dtype = convert_triton_dtype(Q.dtype)
     n = num_splits or _lib.kvcache_mla_num_splits(B, H, H_kv, N_q, _capacity(K_cache, block_table), d, d_v, dtype)
     O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d_v), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0)
+    if fp8:  # the one descale of the shared row is K's and V's
+        _lib.fa2_fwd_kvcache_mla_fp8(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
+                                     k_descale=kv_descale, v_descale=kv_descale, block_table=block_table, causal=causal, scale=scale,
+                                     window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
     _lib.fa2_fwd_kvcache_mla(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, block_table=block_table, causal=causal, scale=scale,
                              window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
     return O, L
 
 
 def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=512, causal=False, scale=1.0, window=None, num_splits=0,
-                                       variant="auto", block_table=None):
+                                       variant="auto", block_table=None, kv_descale=None):
     """Multi-head latent attention decode, absorbed form, over the shared latent cache (fa2_fwd_kvcache_mla) -> (O, L).  Q
     (B, H, N_q, d); KV_cache (B, H_kv, S_k, d) or, with block_table, the page pool (num_blocks, H_kv, page_size, d): one row per key,
     d_v latent columns followed by the rotary ones (DeepSeek-V2 / V3 / R1, Kimi: H_kv = 1, d = 576, d_v = 512).  The score takes all
-    d columns, the value is the first d_v of the same row: the call is flash_attention_kvcache_forward(Q, KV_cache,
-    KV_cache[..., :d_v], ...) bit for bit, and every other argument is that function's.  O (B, H, N_q, d_v).  1 <= d_v < d.  The
-    cache is only read: the latent row of a new token (its last d - d_v columns rotated) is written by the caller, and an fp8
-    latent cache, the append and rotary arguments and packed queries are not supported."""
+    d columns, the value is the first d_v of the same row: with a cache in Q's dtype the call is flash_attention_kvcache_forward(Q,
+    KV_cache, KV_cache[..., :d_v], ...) bit for bit, and every other argument is that function's.  O (B, H, N_q, d_v) and L
+    (B, H, N_q) in Q's dtype.  1 <= d_v < d.
+
+    fp8 latent cache (fa2_fwd_kvcache_mla_fp8): KV_cache in torch.float8_e4m3fn or torch.float8_e5m2 under float16 / bfloat16 Q,
+    contiguous or a page pool; the row is kv_descale * float(KV_cache), kv_descale a float32 tensor on Q's device that broadcasts to
+    (B, H_kv) (None: 1; finite and > 0) -- the one descale of the shared row, K's and V's alike; quantize_kv_cache(KV, dtype) makes
+    both.  Only the storage is fp8: the bytes are converted exactly while they are staged, the arithmetic stays 16-bit, and with
+    kv_descale None the result is, bit for bit, that of the cache converted to Q's dtype.  variant "mla16" then needs every stride
+    of the cache a multiple of 16 elements.  kv_descale with a cache in Q's dtype is a ValueError.
+
+    The cache is only read: the latent row of a new token (its last d - d_v columns rotated, quantised where the cache is fp8) is
+    written by the caller, and the append and rotary arguments and packed queries are not supported."""
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError("mla decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < KV_cache.shape[3]:
         raise ValueError(f"mla decode: d_v must be an int in [1, d - 1] = [1, {KV_cache.shape[3] - 1}], got {d_v!r}")
-    return flash_attention_kvcache_forward(Q, KV_cache, KV_cache[..., :d_v], cache_seqlens, dev, causal=causal, scale=scale,
-                                           window=window, num_splits=num_splits, variant=variant, block_table=block_table)
+    return _kvcache_mla_forward(Q, KV_cache, KV_cache[..., :d_v], cache_seqlens, dev, causal, scale, window, num_splits, variant, None,
+                                None, block_table, None, None, None, None, latent=True, kv_descale=kv_descale)
 
 
 def check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale=None,

@@ -357,7 +357,7 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
  *   Cache.    block_table non-null: fa2_fwd_kvcache_paged's pool (num_blocks, H_kv, page_size, d) / (..., d_v), table and capacity
  *             max_blocks * page_size.  block_table null: the contiguous cache, a pool of one page per sequence -- page_size
  *             carries S_k, strides[0] is the batch stride, and num_blocks, max_blocks and block_table_stride are not read.
- *   Dtypes.   f16, bf16, f32, f64 (dtype_enum, the cache alike); no fp8 cache, no descales.
+ *   Dtypes.   f16, bf16, f32, f64 (dtype_enum, the cache alike); an fp8 cache and its descales: fa2_fwd_kvcache_mla_fp8 below.
  *   Splits.   The workspace is fa2_kvcache_workspace_bytes(B, H, N_q, d_v, num_splits): the partials have d_v columns.
  *             num_splits = 0 resolves to fa2_kvcache_mla_num_splits(...).
  *   Variants. FA2_KVCACHE_VARIANT_MLA16 (this entry point only): f16 / bf16, d = 576 and d_v = 512, V aliasing K (the same base
@@ -370,7 +370,7 @@ int fa2_fwd_kvcache_paged(const void *Q, const void *K, const void *V, void *O, 
  *
  * Every FA2_ERR_BAD_ARG and FA2_ERR_UNSUPPORTED of fa2_fwd_kvcache_paged applies (with block_table null: S_k = page_size in the
  * capacity's place, no table errors), the message naming the argument; FA2_ERR_UNSUPPORTED also for d outside [1, 576] and d_v outside
- * [1, 512].  Not covered (use the d_v == d entry points): an fp8 latent cache, the append calls and rotary, packed queries.
+ * [1, 512].  Not covered (use the d_v == d entry points): the append calls and rotary, packed queries.
  */
 #define FA2_KVCACHE_VARIANT_MLA16 3
 
@@ -390,6 +390,38 @@ int fa2_fwd_kvcache_mla(const void *Q, const void *K, const void *V, void *O, vo
  * other shape is counted as fa2_kvcache_num_splits counts the VALU form. */
 int32_t fa2_kvcache_mla_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t d_v,
                                    int32_t dtype_enum);
+
+/*
+ * fa2_fwd_kvcache_mla over an fp8 latent cache: only the STORAGE is fp8, exactly as in fa2_fwd_kvcache_fp8.  K and V are OCP e4m3fn or
+ * e5m2 bytes (kv_dtype_enum FA2_DTYPE_F8E4M3 / FA2_DTYPE_F8E5M2) under f16 / bf16 Q, O and L (dtype_enum), converted exactly to the
+ * I/O dtype while they are staged; the matrix work stays 16-bit.  K = k_descale * float(K8), V = v_descale * float(V8), the descales
+ * as in fa2_fwd_kvcache_paged: fp32 on the device at [b * strides[0] + h_kv * strides[1]], null = 1, finite and > 0; k_descale is
+ * folded into the softmax scale, v_descale into the fp32 output.  With V a view of K (the latent cache) the two are still
+ * independent scalars; a cache quantised as one tensor passes the same descale twice.  Strides of K and V are in elements of the
+ * cache dtype (bytes).
+ *
+ *   kv_dtype_enum == dtype_enum with null descales is fa2_fwd_kvcache_mla: the same checks, the same launches.
+ *   Splits and workspace do not depend on the cache dtype: fa2_kvcache_mla_num_splits, fa2_kvcache_workspace_bytes(B, H, N_q, d_v, n).
+ *   Variants. FA2_KVCACHE_VARIANT_MLA16 over an fp8 cache: fa2_fwd_kvcache_mla's rule with the row starts 16-byte aligned in BYTES --
+ *             every stride of K a multiple of 16 elements, the base 16-byte aligned -- V aliasing K, unit d-stride, page_size % 64 == 0
+ *             when paged.  FA2_KVCACHE_VARIANT_GENERIC: every d <= 576 and d_v <= 512, any strides, any page size, a V tensor of its
+ *             own.  FA2_KVCACHE_VARIANT_AUTO: MLA16 where it runs, else GENERIC.
+ *
+ * Errors: fa2_fwd_kvcache_mla's, and fa2_fwd_kvcache_paged's for the cache dtype and the descales -- a kv_dtype_enum that is neither
+ * dtype_enum nor an fp8 format and f32 / f64 Q under an fp8 cache FA2_ERR_UNSUPPORTED, descales with a 16-bit cache and negative
+ * descale strides FA2_ERR_BAD_ARG.
+ */
+int fa2_fwd_kvcache_mla_fp8(const void *Q, const void *K, const void *V, void *O, void *L,
+                            const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                            const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                            const int32_t *block_table, int64_t block_table_stride,
+                            const float *k_descale, const float *v_descale,
+                            const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                            int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                            int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                            int32_t dtype_enum, int32_t kv_dtype_enum,
+                            int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                            void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
 /*
  * Variable-length (packed) queries over the KV cache: every sequence brings its own number of query tokens -- a chunk of a prompt
