@@ -18,7 +18,14 @@ The kernel trace is cut into the sides by dispatch order (split kernel plus comb
 rest after the last decode kernel is sdpa's).  hbm_share counts 1,152 B per visible key ONCE over the side's kernel time, as a
 share of the 6.29 TB/s copy rate (cache_gbps: the same bytes over AUTO's time, in GB/s): a second row tile (128 heads, or 64 heads at N_q = 2) reads the keys again and is not counted.
 
+--append: a decode step WITH its cache update (N_new = N_q rows per sequence at cache_seqlens = N_k - N_q, rotary_dim 64).  The fused
+call (fa2_fwd_kvcache_mla_append) against what a caller does without it -- the torch restatement on the device (rotate k_pe,
+concatenate, quantise, scatter through the table, rotate and concatenate Q) followed by the read-only decode launch -- alternated
+call by call in ONE process and timed by device events around each call, --repeats runs per case; then the append launch alone
+(fa2_kvcache_mla_append) with the bytes it must move, computed from the shapes, and bytes / s at its fastest rate (200 launches back to back without a host synchronisation).
+
 Records:
+  kind=append         --append: per case, the per-run avg / min / max / stddev of both sides, their ratio, the append launch alone;
   kind=kernels        one per shape and cache form: the sides' avg / min / max / stddev in microseconds, auto_over_generic;
   kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS on the four SWEEP_CASES, one traced child per shape."""
 import argparse
@@ -231,6 +238,128 @@ def run_rocprof(names, args, fh):
             assert pos == len(rows)
 
 
+class AppendCase(Case):
+    """A decode step WITH its cache update (--append): N_new = N_q new rows per sequence at cache_seqlens = N_k - N_q, rotary_dim 64."""
+
+    def __init__(self, name, dev, page_size=0, kv_dtype="bf16"):
+        super().__init__(name, dev, page_size, kv_dtype)
+        torch, s = self.torch, self.shape
+        import flash_attention_dlrs_amd as fa
+        self.fa = fa
+        B, N = s["B"], s["N_q"]
+        mk = lambda *sh: (torch.randn(*sh, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
+        self.c_new, self.pe_new = mk(B, 1, N, D_V), mk(B, 1, N, D - D_V)
+        ang = torch.rand(s["N_k"], (D - D_V) // 2, device=dev, dtype=torch.float64) * 6.283
+        self.cos, self.sin = ang.cos().to(torch.bfloat16), ang.sin().to(torch.bfloat16)
+        self.lens = torch.full((B,), s["N_k"] - N, dtype=torch.int32, device=dev)
+        self.out = torch.empty_like(self.lens)
+        self.q_rot = torch.empty_like(self.Q)
+        self.n = self.auto_splits()
+        self.ws = torch.empty(max(self._lib.kvcache_workspace_bytes(B, s["H"], N, D_V, self.n) // 4, 1), dtype=torch.float32, device=dev)
+        # the bytes the append launch alone must move: the two sources, the cache rows, the table rows of each position, the lengths
+        csz = 1 if self.fmt else 2
+        self.append_bytes = B * N * (2 * D + csz * D + 2 * (D - D_V)) + 8 * B
+
+    def _next(self):
+        self.i = (self.i + 1) % self.copies
+        return self.KV[self.i], (self.descale[self.i] if self.fmt else None)
+
+    def fused(self):
+        kv, ds = self._next()
+        self._lib.fa2_fwd_kvcache_mla_append(self.Q, kv, self.O, self.L, self.c_new, self.pe_new, self.lens, self.out, self.enum,
+                                             self.kv_enum, block_table=self.table, kv_descale=ds, rotary_cos=self.cos,
+                                             rotary_sin=self.sin, q_rot=self.q_rot, scale=self.scale, num_splits=self.n,
+                                             workspace=self.ws)
+
+    def append_alone(self):
+        kv, ds = self._next()
+        self._lib.fa2_kvcache_mla_append(kv, self.c_new, self.pe_new, self.lens, self.out, self.enum, self.kv_enum,
+                                         block_table=self.table, kv_descale=ds, rotary_cos=self.cos, rotary_sin=self.sin)
+
+    def torch_then_decode(self):
+        """What a caller has to do without the append: rotate, concatenate, quantise, scatter through the table, rotate and
+        concatenate Q in torch on the device, then the read-only decode launch."""
+        torch, fa, s = self.torch, self.fa, self.shape
+        kv, ds = self._next()
+        B, N, P = s["B"], s["N_q"], self.page_size
+        idx = self.lens.long()[:, None] + torch.arange(N, device=self.dev)[None, :]  # (B, N) key indices
+        row = torch.cat([self.c_new, fa.apply_rotary(self.pe_new, self.cos, self.sin, idx[:, None, :])], dim=-1)
+        if self.fmt:
+            top = torch.finfo(self.fmt).max
+            row = (row.float() / ds[:, :, None, None]).clamp(-top, top).to(self.fmt)
+        raw, rows = kv.view(torch.uint8 if self.fmt else torch.int16), row.view(torch.uint8 if self.fmt else torch.int16)[:, 0]
+        if P:
+            raw[self.table.long().gather(1, idx // P), 0, idx % P] = rows
+        else:
+            raw[torch.arange(B, device=self.dev)[:, None], 0, idx] = rows
+        q = torch.cat([self.Q[..., :D_V], fa.apply_rotary(self.Q[..., D_V:], self.cos, self.sin, self.lens.long()[:, None, None])], dim=-1)
+        new_lens = self.lens + N
+        if self.fmt:
+            self._lib.fa2_fwd_kvcache_mla_fp8(q, kv, kv[..., :D_V], self.O, self.L, new_lens, self.enum, self.kv_enum, k_descale=ds,
+                                              v_descale=ds, block_table=self.table, scale=self.scale, num_splits=self.n, workspace=self.ws)
+        else:
+            self._lib.fa2_fwd_kvcache_mla(q, kv, kv[..., :D_V], self.O, self.L, new_lens, self.enum, block_table=self.table,
+                                          scale=self.scale, num_splits=self.n, workspace=self.ws)
+
+
+def stats_us(us):
+    avg = sum(us) / len(us)
+    return dict(avg_us=round(avg, 2), min_us=round(min(us), 2), max_us=round(max(us), 2),
+                stddev_us=round((sum((u - avg) ** 2 for u in us) / len(us)) ** 0.5, 2), calls=len(us))
+
+
+def run_append(names, args, fh):
+    """--append: the fused step against the torch restatement plus the decode launch, alternated call by call in this one process
+    and timed by device events around each call (both sides are several launches, so this is the time a stream spends on a step,
+    launch gaps included); then the append launch alone, with its bytes.  Repeated --repeats times: the spread of the averages."""
+    import torch
+    dev = torch.device("cuda:0")
+    for name in names:
+        c = AppendCase(name, dev, args.page_size, args.kv_dtype)
+        sides = (("fused", c.fused), ("torch_then_decode", c.torch_then_decode))
+        runs = {k: [] for k, _ in sides}
+        alone = []
+        for _ in range(args.repeats):
+            times = {k: [] for k, _ in sides}
+            for it in range(args.iters + 3):
+                for k, f in sides:
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    f()
+                    b.record()
+                    b.synchronize()
+                    if it >= 3:
+                        times[k].append(a.elapsed_time(b) * 1e3)
+            for k in times:
+                runs[k].append(stats_us(times[k]))
+            t = []
+            for it in range(args.iters + 3):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                c.append_alone()
+                b.record()
+                b.synchronize()
+                if it >= 3:
+                    t.append(a.elapsed_time(b) * 1e3)
+            alone.append(stats_us(t))
+            # ... and back to back, no host synchronisation between the calls: the stream's time per launch
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(200):
+                c.append_alone()
+            b.record()
+            b.synchronize()
+            alone[-1]["back_to_back_us"] = round(a.elapsed_time(b) * 1e3 / 200, 3)
+        f_avg, p_avg = [r["avg_us"] for r in runs["fused"]], [r["avg_us"] for r in runs["torch_then_decode"]]
+        a_min = min(r["back_to_back_us"] for r in alone)
+        emit(fh, kind="append", case=name, kv_dtype=args.kv_dtype, page_size=args.page_size, num_splits=c.n, **c.shape,
+             fused=runs["fused"], torch_then_decode=runs["torch_then_decode"],
+             fused_over_parent=[round(f / p, 4) for f, p in zip(f_avg, p_avg)],
+             ranges_overlap=max(f_avg) >= min(p_avg), append_alone=alone, append_bytes=c.append_bytes,
+             append_gbps_at_min=round(c.append_bytes / (a_min * 1e-6) / 1e9, 3),
+             append_hbm_share_at_min=round(c.append_bytes / (a_min * 1e-6) / HBM_COPY_RATE, 6))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default=",".join(CASES))
@@ -242,6 +371,9 @@ def main():
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--page-size", type=int, default=0, metavar="N", help="the paged cache at N-key pages (64) in the contiguous one's place")
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="bf16", help="the latent cache's storage: bf16, or fp8 with its descale")
+    ap.add_argument("--append", action="store_true",
+                    help="time the fused append + decode step against the torch restatement + decode, and the append launch alone")
+    ap.add_argument("--repeats", type=int, default=3, help="--append: runs per case, for the spread of the averages")
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
@@ -252,6 +384,8 @@ def main():
         return run_sweep_pass(args.sweep_case, args)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
+        if args.append:
+            return run_append(args.cases.split(","), args, fh)
         run_rocprof(args.cases.split(","), args, fh)
 
 

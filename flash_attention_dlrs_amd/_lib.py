@@ -56,7 +56,7 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append",
            "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits",
            "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits",
-           "fa2_fwd_kvcache_mla_fp8")
+           "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -207,6 +207,23 @@ def lib():
             [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_mla_num_splits.restype = ctypes.c_int32
         l.fa2_kvcache_mla_num_splits.argtypes = [ctypes.c_int32] * 8
+        # the latent-cache append: fa2_kvcache_append's order with one cache tensor and one descale, c_new / pe_new in k_new / v_new's
+        # place, d_v after d
+        l.fa2_kvcache_mla_append.restype = ctypes.c_int
+        l.fa2_kvcache_mla_append.argtypes = [vp, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, i64p, vp, vp, ctypes.c_int64,
+                                             ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp, vp, i64p] + [ctypes.c_int32] * 14 + [vp]
+        # ... packed: cu_seqlens_new before cache_seqlens, no N_q, total_new max_seqlen_new in N_new's place
+        l.fa2_kvcache_mla_append_varlen.restype = ctypes.c_int
+        l.fa2_kvcache_mla_append_varlen.argtypes = [vp, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, vp, i64p, vp, vp,
+                                                    ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp, vp, i64p] + \
+            [ctypes.c_int32] * 14 + [vp]
+        # ... fused with the latent-cache decode: Q KV O L + their strides, lengths in / out, table + stride, descale + strides,
+        # c_new pe_new + strides, rotary tables + row strides, S_rot rotary_dim interleaved, q_rot, B H H_kv N_q N_new S_k num_blocks
+        # page_size max_blocks d d_v dtype kv_dtype causal, scale, window, num_splits, workspace + its size, variant, stream
+        l.fa2_fwd_kvcache_mla_append.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_append.argtypes = [vp] * 4 + [i64p] * 4 + [vp, vp, vp, ctypes.c_int64, vp, i64p, vp, vp, i64p, i64p, vp, vp,
+                                                 ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp] + [ctypes.c_int32] * 14 + \
+            [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -683,5 +700,74 @@ def fa2_fwd_kvcache_varlen_append(Q, K, V, O, L, k_new, v_new, cu_q, max_q, cach
             cu_q.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, vd_ptr, kd_st, vd_st,
             k_new.data_ptr(), v_new.data_ptr(), _i64(k_new.stride()), _i64(v_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd,
             int(bool(rotary_interleaved)), _ptr(q_rot), cu_q.numel() - 1, H, K.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d,
+            int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits),
+            *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
+
+
+def _mla_append_args(KV, block_table, kv_descale, rotary_cos, rotary_sin):
+    """_append_args for the latent cache and its one descale: (table pointer, table stride, descale pointer, descale strides, rotary
+    pointers, row strides, S_rot, rotary_dim, S_k, num_blocks, page_size, max_blocks)."""
+    tb_ptr, tb_st, kd_ptr, _, kd_st, _, *rest = _append_args(KV, None, block_table, kv_descale, None, rotary_cos, rotary_sin)
+    return (tb_ptr, tb_st, kd_ptr, kd_st, *rest)
+
+
+def fa2_kvcache_mla_append(KV, c_new, pe_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None, kv_descale=None,
+                           rotary_cos=None, rotary_sin=None, rotary_interleaved=False, Q=None, q_rot=None, q_pos_per_row=False):
+    """Launch the latent-cache append (include/fa2_fwd.h fa2_kvcache_mla_append) on the current stream of c_new's device: c_new
+    (B, H_kv, N_new, d_v) and pe_new (B, H_kv, N_new, d - d_v), any strides, become the columns [0, d_v) and [d_v, d) of new rows of
+    KV (B, H_kv, S_k, d), or the pool (num_blocks, H_kv, page_size, d) with block_table, in place; seqlens_out, an int32 (B,) tensor
+    that is not cache_seqlens, receives the new lengths.  rotary_cos / rotary_sin (S_rot, rotary_dim / 2) rotate the columns
+    [d_v, d_v + rotary_dim), of Q (B, H, N_q, d) too, which goes to the contiguous q_rot.  kv_descale as k_descale in
+    fa2_kvcache_append."""
+    if c_new.device.type != "cuda":
+        raise NotImplementedError("KV_cache, c_new, pe_new must be on the same CUDA device")
+    B, H_kv, N_new, d_v = c_new.shape
+    tb_ptr, tb_st, kd_ptr, kd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _mla_append_args(KV, block_table, kv_descale, rotary_cos, rotary_sin)
+    q_st, H, N_q = (None, 0, 0) if Q is None else (_i64(Q.stride()), Q.shape[1], Q.shape[2])
+    _launch(lib().fa2_kvcache_mla_append, c_new,
+            KV.data_ptr(), _i64(KV.stride()), tb_ptr, tb_st, c_new.data_ptr(), pe_new.data_ptr(), _i64(c_new.stride()),
+            _i64(pe_new.stride()), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), kd_ptr, kd_st, cos_ptr, sin_ptr, cos_st, sin_st,
+            S_rot, rd, int(bool(rotary_interleaved)), _ptr(Q), _ptr(q_rot), q_st, H, N_q, int(bool(q_pos_per_row)), B, H_kv, N_new,
+            S_k, nb, ps, mb, KV.shape[3], d_v, int(dtype_enum), int(kv_dtype_enum), _raw_stream(c_new.device.index))
+
+
+def fa2_kvcache_mla_append_varlen(KV, c_new, pe_new, cu_new, max_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum,
+                                  block_table=None, kv_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, Q=None,
+                                  q_rot=None, q_pos_per_row=False):
+    """Launch the packed latent-cache append (include/fa2_fwd.h fa2_kvcache_mla_append_varlen) on the current stream of c_new's
+    device: fa2_kvcache_mla_append with c_new (total_new, H_kv, d_v), pe_new (total_new, H_kv, d - d_v) and Q, q_rot (total_new, H, d)
+    packed over cu_new, an int32 (B + 1,) tensor on the device."""
+    if c_new.device.type != "cuda":
+        raise NotImplementedError("KV_cache, c_new, pe_new must be on the same CUDA device")
+    total_new, H_kv, d_v = c_new.shape
+    tb_ptr, tb_st, kd_ptr, kd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _mla_append_args(KV, block_table, kv_descale, rotary_cos, rotary_sin)
+    q_st, H = (None, 0) if Q is None else (_i64(Q.stride()), Q.shape[1])
+    _launch(lib().fa2_kvcache_mla_append_varlen, c_new,
+            KV.data_ptr(), _i64(KV.stride()), tb_ptr, tb_st, c_new.data_ptr(), pe_new.data_ptr(), _i64(c_new.stride()),
+            _i64(pe_new.stride()), cu_new.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), kd_ptr, kd_st, cos_ptr, sin_ptr,
+            cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), _ptr(Q), _ptr(q_rot), q_st, H, int(bool(q_pos_per_row)),
+            cu_new.numel() - 1, H_kv, total_new, int(max_new), S_k, nb, ps, mb, KV.shape[3], d_v, int(dtype_enum), int(kv_dtype_enum),
+            _raw_stream(c_new.device.index))
+
+
+def fa2_fwd_kvcache_mla_append(Q, KV, O, L, c_new, pe_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,
+                               kv_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, causal=False,
+                               scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch the fused MLA decode step (include/fa2_fwd.h fa2_fwd_kvcache_mla_append) on the current stream of Q's device: the
+    append above, then the latent-cache decode over the updated KV with seqlens_out as its lengths and, with rotary tables, q_rot (a
+    contiguous (B, H, N_q, d) tensor in Q's dtype) as its Q.  O (B, H, N_q, d_v), L (B, H, N_q); the workspace holds
+    kvcache_workspace_bytes(B, H, N_q, d_v, num_splits) bytes."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    tb_ptr, tb_st, kd_ptr, kd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _mla_append_args(KV, block_table, kv_descale, rotary_cos, rotary_sin)
+    _launch(lib().fa2_fwd_kvcache_mla_append, Q,
+            Q.data_ptr(), KV.data_ptr(), O.data_ptr(), L.data_ptr(), _i64(Q.stride()), _i64(KV.stride()), _i64(O.stride()),
+            _i64((L.stride(0), L.stride(1))), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, kd_st,
+            c_new.data_ptr(), pe_new.data_ptr(), _i64(c_new.stride()), _i64(pe_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot,
+            rd, int(bool(rotary_interleaved)), _ptr(q_rot), B, H, KV.shape[1], N_q, c_new.shape[2], S_k, nb, ps, mb, d, c_new.shape[3],
             int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits),
             *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))

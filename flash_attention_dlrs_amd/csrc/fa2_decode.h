@@ -156,5 +156,12 @@ struct Fa2AppendProblem {
     // < total_new, its sequence b is in [0, B), its key index is < capacity, pages and positions are clamped as always.
     const int32_t *cu_new;
     int32_t total_new, max_new;
+    // the latent form (fa2_kvcache_mla_append, fa2_kvcache_mla_append_varlen): V null.  K is the one tensor of an MLA cache, rows of
+    // d columns whose first d_v are the value; k_new / kns are c_new, the columns [0, d_v) of a new row, pe_new / pns (shaped and
+    // strided like k_new) its columns [d_v, d), and the rotary range is [d_v, d_v + rotary_dim) -- in Q too.  kd is the row's one
+    // descale; v_new, vs, vns, vd are not read.  The other forms do not read these three.
+    const void *pe_new;
+    int64_t pns[4];
+    int32_t d_v;
 };
 int fa2_launch_decode_append(const Fa2AppendProblem &p);

@@ -363,6 +363,11 @@ struct AppendCall {
     bool packed = false;
     const int32_t *cu_seqlens_new = nullptr;
     int32_t total_new = 0, max_seqlen_new = 0;
+    // fa2_kvcache_mla_append, fa2_kvcache_mla_append_varlen: K is the one tensor of the latent cache (KV) and V, v_strides are null;
+    // k_new / k_new_strides are c_new's, v_new / v_new_strides pe_new's, k_descale / k_descale_strides the row's kv_descale, and
+    // v_descale is null.  d may reach 576 and the rotary range is [d_v, d_v + rotary_dim).
+    bool mla = false;
+    int32_t d_v = 0;
 };
 
 // The {token, head, d} strides of a packed tensor in the fixed call's order {batch, head, token, d}, the batch stride 0; null stays null.
@@ -378,9 +383,11 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
                             c.seqlens_out};
     const char *names[10] = {"K", "V", "k_strides", "v_strides", "k_new", "v_new", "k_new_strides", "v_new_strides", "cache_seqlens",
                              "seqlens_out"};
+    const char *mla_names[10] = {"KV", nullptr, "kv_strides", nullptr, "c_new", "pe_new", "c_new_strides", "pe_new_strides",
+                                 "cache_seqlens", "seqlens_out"};  // (null: the latent cache has no tensor of V's)
     for (int t = 0; t < 10; ++t)
-        if (!ptrs[t]) {
-            fa2_set_error("kvcache append: null %s", names[t]);
+        if (!ptrs[t] && !(c.mla && !mla_names[t])) {
+            fa2_set_error("kvcache append: null %s", c.mla ? mla_names[t] : names[t]);
             return FA2_ERR_BAD_ARG;
         }
     if (c.seqlens_out == c.cache_seqlens) {
@@ -444,15 +451,19 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
         }
     }
     for (int k = 0; k < 4; ++k)
-        if (c.k_strides[k] < 0 || c.v_strides[k] < 0 || c.k_new_strides[k] < 0 || c.v_new_strides[k] < 0 || (c.Q && c.q_strides[k] < 0)) {
-            fa2_set_error("kvcache append: negative strides are not supported (k_strides, v_strides, k_new_strides, v_new_strides, "
-                          "q_strides)");
+        if (c.k_strides[k] < 0 || (!c.mla && c.v_strides[k] < 0) || c.k_new_strides[k] < 0 || c.v_new_strides[k] < 0 ||
+            (c.Q && c.q_strides[k] < 0)) {
+            fa2_set_error(c.mla ? "kvcache append: negative strides are not supported (kv_strides, c_new_strides, pe_new_strides, q_strides)"
+                                : "kvcache append: negative strides are not supported (k_strides, v_strides, k_new_strides, v_new_strides, "
+                                  "q_strides)");
             return FA2_ERR_BAD_ARG;
         }
     const bool wide = c.kv_dtype_enum == c.dtype_enum;  // the cache has the inputs' dtype
     if (wide) {
         if (c.k_descale || c.v_descale) {
-            fa2_set_error("kvcache append: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)", c.kv_dtype_enum);
+            fa2_set_error(c.mla ? "kvcache append: kv_descale goes with an fp8 cache (kv_dtype_enum %d == dtype_enum)"
+                                : "kvcache append: k_descale / v_descale go with an fp8 cache (kv_dtype_enum %d == dtype_enum)",
+                          c.kv_dtype_enum);
             return FA2_ERR_BAD_ARG;
         }
         if (c.dtype_enum == FA2_DTYPE_F8E5M2 || c.dtype_enum == FA2_DTYPE_F8E4M3) {
@@ -460,6 +471,11 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
             return FA2_ERR_UNSUPPORTED;
         }
     } else {
+        if (c.mla && c.k_descale && (!c.k_descale_strides || c.k_descale_strides[0] < 0 || c.k_descale_strides[1] < 0)) {
+            fa2_set_error(c.k_descale_strides ? "kvcache append: negative strides are not supported (kv_descale_strides)"
+                                              : "kvcache append: null kv_descale_strides with a non-null kv_descale");
+            return FA2_ERR_BAD_ARG;
+        }
         const int rc = check_descales("kvcache append", c.k_descale, c.k_descale_strides, c.v_descale, c.v_descale_strides);
         if (rc != FA2_OK) return rc;
         if (c.kv_dtype_enum != FA2_DTYPE_F8E4M3 && c.kv_dtype_enum != FA2_DTYPE_F8E5M2) {
@@ -467,7 +483,8 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
             return FA2_ERR_UNSUPPORTED;
         }
         if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16) {
-            fa2_set_error("kvcache append: dtype_enum %d (k_new, v_new, Q) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16 under an fp8 cache",
+            fa2_set_error(c.mla ? "kvcache append: dtype_enum %d (c_new, pe_new, Q) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16 under an fp8 cache"
+                                : "kvcache append: dtype_enum %d (k_new, v_new, Q) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16 under an fp8 cache",
                           c.dtype_enum);
             return FA2_ERR_UNSUPPORTED;
         }
@@ -476,18 +493,29 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
         fa2_set_error("unknown dtype enum %d", c.dtype_enum);
         return FA2_ERR_UNSUPPORTED;
     }
-    if (c.d < 1 || c.d > 512) {
+    if (c.mla) {
+        if (c.d < 2 || c.d > 576) {
+            fa2_set_error("kvcache mla append: d=%d must be in [2, 576]", c.d);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (c.d_v < 1 || c.d_v > c.d - 1) {
+            fa2_set_error("kvcache mla append: d_v=%d must be in [1, d - 1 = %d]", c.d_v, c.d - 1);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    } else if (c.d < 1 || c.d > 512) {
         fa2_set_error("d=%d must be in [1, 512]", c.d);
         return FA2_ERR_UNSUPPORTED;
     }
+    const int32_t rotary_max = c.mla ? c.d - c.d_v : c.d;  // the columns the rotary range may take
     const bool rotary = c.rotary_cos || c.rotary_sin;
     if (rotary) {
         if (!c.rotary_cos || !c.rotary_sin) {
             fa2_set_error("kvcache append: rotary_cos and rotary_sin go together (null %s)", c.rotary_cos ? "rotary_sin" : "rotary_cos");
             return FA2_ERR_BAD_ARG;
         }
-        if (c.rotary_dim < 2 || c.rotary_dim > c.d || (c.rotary_dim & 1)) {
-            fa2_set_error("kvcache append: rotary_dim must be even and in [2, d = %d] (got %d)", c.d, c.rotary_dim);
+        if (c.rotary_dim < 2 || c.rotary_dim > rotary_max || (c.rotary_dim & 1)) {
+            fa2_set_error(c.mla ? "kvcache append: rotary_dim must be even and in [2, d - d_v = %d] (got %d)"
+                                : "kvcache append: rotary_dim must be even and in [2, d = %d] (got %d)", rotary_max, c.rotary_dim);
             return FA2_ERR_BAD_ARG;
         }
         if (c.S_rot < 1) {
@@ -503,11 +531,13 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
             return FA2_ERR_BAD_ARG;
         }
     }
-    p.K = c.K; p.V = c.V;
+    p.K = c.K; p.V = c.mla ? nullptr : c.V;
     for (int k = 0; k < 4; ++k) {
-        p.ks[k] = c.k_strides[k]; p.vs[k] = c.v_strides[k]; p.kns[k] = c.k_new_strides[k]; p.vns[k] = c.v_new_strides[k];
+        p.ks[k] = c.k_strides[k]; p.vs[k] = c.mla ? 0 : c.v_strides[k]; p.kns[k] = c.k_new_strides[k]; p.vns[k] = c.v_new_strides[k];
+        p.pns[k] = c.v_new_strides[k];
         p.qs[k] = c.Q ? c.q_strides[k] : 0;
     }
+    p.pe_new = c.mla ? c.v_new : nullptr; p.d_v = c.mla ? c.d_v : 0;
     p.table = c.block_table;
     p.table_stride = c.block_table ? c.block_table_stride : 0;
     p.page_size = c.block_table ? c.page_size : 0; p.num_blocks = c.block_table ? c.num_blocks : 0;
@@ -793,6 +823,84 @@ int fa2_fwd_kvcache_varlen_append(const void *Q, void *K, void *V, void *O, void
     c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
     c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
     c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    return decode(c, &p);
+}
+
+int fa2_kvcache_mla_append(void *KV, const int64_t kv_strides[4], const int32_t *block_table, int64_t block_table_stride,
+                           const void *c_new, const void *pe_new, const int64_t c_new_strides[4], const int64_t pe_new_strides[4],
+                           const int32_t *cache_seqlens, int32_t *seqlens_out, const float *kv_descale,
+                           const int64_t kv_descale_strides[2], const void *rotary_cos, const void *rotary_sin,
+                           int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim,
+                           int32_t rotary_interleaved, const void *Q, void *q_rot, const int64_t q_strides[4], int32_t H, int32_t N_q,
+                           int32_t q_pos_per_row, int32_t B, int32_t H_kv, int32_t N_new, int32_t S_k, int32_t num_blocks,
+                           int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum,
+                           void *hip_stream) {
+    AppendCall c = {KV, nullptr, kv_strides, nullptr, block_table, block_table_stride, c_new, pe_new, c_new_strides, pe_new_strides,
+                    cache_seqlens, seqlens_out, kv_descale, nullptr, kv_descale_strides, nullptr, rotary_cos, rotary_sin,
+                    rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot, q_strides, H, N_q,
+                    q_pos_per_row, B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, hip_stream};
+    c.mla = true; c.d_v = d_v;
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    return rc != FA2_OK ? rc : fa2_launch_decode_append(p);
+}
+
+int fa2_kvcache_mla_append_varlen(void *KV, const int64_t kv_strides[4], const int32_t *block_table, int64_t block_table_stride,
+                                  const void *c_new, const void *pe_new, const int64_t c_new_strides[3],
+                                  const int64_t pe_new_strides[3], const int32_t *cu_seqlens_new, const int32_t *cache_seqlens,
+                                  int32_t *seqlens_out, const float *kv_descale, const int64_t kv_descale_strides[2],
+                                  const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                                  int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, const void *Q, void *q_rot,
+                                  const int64_t q_strides[3], int32_t H, int32_t q_pos_per_row, int32_t B, int32_t H_kv,
+                                  int32_t total_new, int32_t max_seqlen_new, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                                  int32_t max_blocks, int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum,
+                                  void *hip_stream) {
+    int64_t cns[4], pns[4], qs[4];
+    AppendCall c = {KV, nullptr, kv_strides, nullptr, block_table, block_table_stride, c_new, pe_new, packed4(c_new_strides, cns),
+                    packed4(pe_new_strides, pns), cache_seqlens, seqlens_out, kv_descale, nullptr, kv_descale_strides, nullptr,
+                    rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot,
+                    packed4(q_strides, qs), H, 0, q_pos_per_row, B, H_kv, 0, S_k, num_blocks, page_size, max_blocks, d, dtype_enum,
+                    kv_dtype_enum, hip_stream};
+    c.packed = true; c.cu_seqlens_new = cu_seqlens_new; c.total_new = total_new; c.max_seqlen_new = max_seqlen_new;
+    c.mla = true; c.d_v = d_v;
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    return rc != FA2_OK ? rc : fa2_launch_decode_append(p);
+}
+
+int fa2_fwd_kvcache_mla_append(const void *Q, void *KV, void *O, void *L, const int64_t q_strides[4], const int64_t kv_strides[4],
+                               const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                               int32_t *seqlens_out, const int32_t *block_table, int64_t block_table_stride, const float *kv_descale,
+                               const int64_t kv_descale_strides[2], const void *c_new, const void *pe_new,
+                               const int64_t c_new_strides[4], const int64_t pe_new_strides[4], const void *rotary_cos,
+                               const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot,
+                               int32_t rotary_dim, int32_t rotary_interleaved, void *q_rot, int32_t B, int32_t H, int32_t H_kv,
+                               int32_t N_q, int32_t N_new, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                               int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale,
+                               int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
+                               int32_t variant, void *hip_stream) {
+    const int32_t per_row = causal || window_left >= 0 || window_right >= 0;  // the fused call's rule for Q's rotary positions
+    AppendCall a = {KV, nullptr, kv_strides, nullptr, block_table, block_table_stride, c_new, pe_new, c_new_strides, pe_new_strides,
+                    cache_seqlens, seqlens_out, kv_descale, nullptr, kv_descale_strides, nullptr, rotary_cos, rotary_sin,
+                    rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot, q_strides, H, N_q,
+                    per_row, B, H_kv, N_new, S_k, num_blocks, page_size, max_blocks, d, dtype_enum, kv_dtype_enum, hip_stream};
+    a.mla = true; a.d_v = d_v;
+    Fa2AppendProblem p;
+    const int rc = check_append(a, p);
+    if (rc != FA2_OK) return rc;
+    // the attention reads the rotated Q (contiguous; p.Q null: no tables, Q as it is), the new lengths, and V as the first d_v
+    // columns of the row it scores: the one descale is K's and V's
+    const int64_t rot_strides[4] = {(int64_t)H * N_q * d, (int64_t)N_q * d, d, 1};
+    DecodeCall c;
+    c.Q = p.Q ? q_rot : Q; c.K = KV; c.V = KV; c.O = O; c.L = L; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = p.Q ? rot_strides : q_strides; c.k_strides = kv_strides; c.v_strides = kv_strides; c.o_strides = o_strides;
+    c.l_strides = l_strides; c.cache_seqlens = seqlens_out;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = kv_descale; c.v_descale = kv_descale; c.k_descale_strides = kv_descale_strides; c.v_descale_strides = kv_descale_strides;
     return decode(c, &p);
 }
 

@@ -17,6 +17,11 @@
 // rounded division, clamped to +-finfo.max and converted by v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 (OCP formats on gfx950, nearest even).
 // Columns outside the rotary range, and V, are copied bit for bit into a cache of their own dtype.
 //
+// The latent form (LAT: fa2_kvcache_mla_append, fa2_kvcache_mla_append_varlen) writes the one tensor of an MLA cache: there are no V
+// slabs (the value is a view of the same row), a row's columns [0, d_v) come from c_new and [d_v, d) from pe_new, each with a pointer
+// and strides of its own, and the rotary range starts at column d_v -- of the cache row and of Q alike.  Inside that range the
+// pairing, the tables and the arithmetic are the ones above; one descale (kd) scales the whole row.
+//
 // Every result leaves through ordinary vector stores.
 #include "fa2_decode.h"
 #include "fa2_elem.h"
@@ -48,36 +53,51 @@ struct Row {          // one row of d columns to process, uniform over the lanes
     const char *src;  // element 0 of the input row
     char *dst;        // element 0 of the output row
     int64_t ss, ds;   // d-strides of src and dst, in elements (element path)
+    // LAT only: columns >= off are read from src2 (the element that becomes column off) with d-stride ss2, and rotated from off on
+    const char *src2;
+    int64_t ss2;
+    int off;
     const char *cos, *sin;  // the table rows of this row's position, or null: no rotary
     float descale;    // fp8 output only
 };
 
 // ---- element path: one column per unit, any strides, any dtype -------------------------------------------------------------------
 // OUT = 0: the output has E's dtype; FA2_DTYPE_F8E4M3 / FA2_DTYPE_F8E5M2: an fp8 cache.
-template <class E, int OUT> __device__ __forceinline__ void unit_elem(const Row &r, int c, int rd, int interleaved) {
+// The input element that becomes column c.
+template <class E, bool LAT> __device__ __forceinline__ const char *col_src(const Row &r, int c) {
+    constexpr int64_t esz = sizeof(typename E::bits_t);
+    if constexpr (LAT)
+        if (c >= r.off) return r.src2 + (int64_t)(c - r.off) * r.ss2 * esz;
+    return r.src + (int64_t)c * r.ss * esz;
+}
+
+template <class E, int OUT, bool LAT> __device__ __forceinline__ void unit_elem(const Row &r, int c, int rd, int interleaved) {
     using T = typename E::acc_t;  // float, or double for f64
     T v;
-    const bool rot = r.cos && c < rd;
+    const int off = LAT ? r.off : 0;
+    const int rc = c - off;  // the column inside the rotary range
+    const bool rot = r.cos && rc >= 0 && rc < rd;
     if (rot) {
         const int half = rd >> 1;
         int partner, ci;
         bool first;
-        if (interleaved) { first = !(c & 1); partner = c ^ 1; ci = c >> 1; }
-        else { first = c < half; partner = first ? c + half : c - half; ci = first ? c : c - half; }
-        v = rot_pair<T>(E::load(r.src, (int64_t)c * r.ss), E::load(r.src, (int64_t)partner * r.ss), E::load(r.cos, ci), E::load(r.sin, ci),
-                        first);
+        if (interleaved) { first = !(rc & 1); partner = rc ^ 1; ci = rc >> 1; }
+        else { first = rc < half; partner = first ? rc + half : rc - half; ci = first ? rc : rc - half; }
+        v = rot_pair<T>(E::load(col_src<E, LAT>(r, c), 0), E::load(col_src<E, LAT>(r, partner + off), 0), E::load(r.cos, ci),
+                        E::load(r.sin, ci), first);
     } else if constexpr (OUT == 0) {  // a copy, bit for bit
         using B = typename E::bits_t;
-        ((B *)r.dst)[(int64_t)c * r.ds] = ((const B *)r.src)[(int64_t)c * r.ss];
+        ((B *)r.dst)[(int64_t)c * r.ds] = *(const B *)col_src<E, LAT>(r, c);
         return;
     } else {
-        v = E::load(r.src, (int64_t)c * r.ss);
+        v = E::load(col_src<E, LAT>(r, c), 0);
     }
     if constexpr (OUT == 0) E::store(r.dst, (int64_t)c * r.ds, v);
     else ((uint8_t *)r.dst)[(int64_t)c * r.ds] = (uint8_t)fp8_pack2<OUT, false>(fp8_scaled<OUT>((float)v, r.descale), 0.0f, 0);
 }
 
 // ---- vector path: 8 columns per unit, f16 / bf16 input, unit d-strides, aligned rows, rotary_dim % 16 == 0 -----------------------
+// (LAT: off % 8 == 0 as well, so a unit lies in one source, and the rotary range, which starts at off, lies in src2)
 template <class E> __device__ __forceinline__ void widen8(const uint4 &u, float (&f)[8]) {
     const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -87,10 +107,12 @@ template <class E> __device__ __forceinline__ void widen8(const uint4 &u, float 
     }
 }
 
-template <class E, int OUT> __device__ __forceinline__ void unit_vec(const Row &r, int c, int rd, int interleaved) {
+template <class E, int OUT, bool LAT> __device__ __forceinline__ void unit_vec(const Row &r, int c, int rd, int interleaved) {
     const int col = c * 8;
-    const uint4 xu = *(const uint4 *)(r.src + (int64_t)col * 2);
-    const bool rot = r.cos && col < rd;  // rd % 16 == 0: a unit is inside the rotary range or outside it
+    const int rcol = LAT ? col - r.off : col;                 // the column inside the rotary range
+    const char *rsrc = LAT ? r.src2 : r.src;                  // ... and the source that holds the range
+    const uint4 xu = *(const uint4 *)(rcol >= 0 ? rsrc + (int64_t)rcol * 2 : r.src + (int64_t)col * 2);
+    const bool rot = r.cos && rcol >= 0 && rcol < rd;  // rd % 16 == 0: a unit is inside the rotary range or outside it
     if (!rot && OUT == 0) {
         *(uint4 *)(r.dst + (int64_t)col * 2) = xu;
         return;
@@ -100,7 +122,7 @@ template <class E, int OUT> __device__ __forceinline__ void unit_vec(const Row &
     if (rot) {
         float cs[8], sn[8];
         if (interleaved) {  // pairs (2i, 2i + 1) inside the unit, table columns col / 2 .. col / 2 + 3
-            const uint2 cu = *(const uint2 *)(r.cos + (int64_t)col), su = *(const uint2 *)(r.sin + (int64_t)col);
+            const uint2 cu = *(const uint2 *)(r.cos + (int64_t)rcol), su = *(const uint2 *)(r.sin + (int64_t)rcol);
             const uint32_t cw[2] = {cu.x, cu.y}, sw[2] = {su.x, su.y};
             float o[8];
 #pragma unroll
@@ -114,10 +136,10 @@ template <class E, int OUT> __device__ __forceinline__ void unit_vec(const Row &
             for (int k = 0; k < 8; ++k) v[k] = o[k];
         } else {  // column i with i + rd / 2: the partner unit is rd / 16 units away
             const int half = rd >> 1;
-            const bool first = col < half;
-            const int pcol = first ? col + half : col - half, ci = first ? col : col - half;
+            const bool first = rcol < half;
+            const int pcol = first ? rcol + half : rcol - half, ci = first ? rcol : rcol - half;
             float y[8];
-            widen8<E>(*(const uint4 *)(r.src + (int64_t)pcol * 2), y);
+            widen8<E>(*(const uint4 *)(rsrc + (int64_t)pcol * 2), y);
             widen8<E>(*(const uint4 *)(r.cos + (int64_t)ci * 2), cs);
             widen8<E>(*(const uint4 *)(r.sin + (int64_t)ci * 2), sn);
 #pragma unroll
@@ -153,10 +175,10 @@ struct AppBF16 : ElemBF16 {
     static __device__ __forceinline__ uint16_t narrow(float x) { return ElemBF16::bits(x); }
 };
 
-template <class E, int OUT, bool VEC> __device__ __forceinline__ void do_row(const Row &r, int units, int rd, int interleaved) {
+template <class E, int OUT, bool VEC, bool LAT> __device__ __forceinline__ void do_row(const Row &r, int units, int rd, int interleaved) {
     for (int c = threadIdx.x; c < units; c += blockDim.x) {
-        if constexpr (VEC) unit_vec<E, OUT>(r, c, rd, interleaved);
-        else unit_elem<E, OUT>(r, c, rd, interleaved);
+        if constexpr (VEC) unit_vec<E, OUT, LAT>(r, c, rd, interleaved);
+        else unit_elem<E, OUT, LAT>(r, c, rd, interleaved);
     }
 }
 
@@ -165,7 +187,9 @@ template <class E, int OUT, bool VEC> __device__ __forceinline__ void do_row(con
 // threadIdx.y is a packed row, which finds its sequence by a binary search over cu_new (once, at most 16 steps: B <= 65535) and
 // then checks with fa2_varlen_seq that the sequence owns it -- rows in no sequence do nothing.  Everything after that is the
 // fixed form's: the same Row, the same do_row, so the same bytes.
-template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) void fa2_decode_append_kernel(const Fa2AppendProblem a) {
+// LAT: the latent form (the head of this file): H_kv slabs of the one cache tensor, then H of Q.
+template <class E, int KV, bool VEC, bool PK, bool LAT>
+__global__ __launch_bounds__(256) void fa2_decode_append_kernel(const Fa2AppendProblem a) {
     constexpr int64_t esz = sizeof(typename E::bits_t);
     constexpr int64_t csz = KV == 0 ? esz : 1;  // bytes of a cache element
     const int cap = a.capacity;
@@ -211,11 +235,12 @@ template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) 
     }
     const int units = VEC ? a.d >> 3 : a.d;
     const bool rotary = a.cos != nullptr;
-    const int nslab = 2 * a.H_kv + (a.Q && rotary ? a.H : 0);
+    const int nkv = LAT ? a.H_kv : 2 * a.H_kv;
+    const int nslab = nkv + (a.Q && rotary ? a.H : 0);
     for (int slab = blockIdx.y; slab < nslab; slab += gridDim.y) {
         Row r;
-        if (slab < 2 * a.H_kv) {  // a row of K (with rotary) or V (without)
-            const bool is_k = slab < a.H_kv;
+        if (slab < nkv) {  // a row of K (with rotary) or V (without); LAT: of the latent cache, K's part in every respect
+            const bool is_k = LAT || slab < a.H_kv;
             const int hk = is_k ? slab : slab - a.H_kv;
             if constexpr (!PK)
                 if (t >= a.N_new) continue;
@@ -234,6 +259,12 @@ template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) 
             r.dst = (char *)(is_k ? a.K : a.V) + off * csz;
             r.ss = ns[3];
             r.ds = cs[3];
+            if constexpr (LAT) {
+                if constexpr (PK) r.src2 = (const char *)a.pe_new + ((int64_t)hk * a.pns[1] + row * a.pns[2]) * esz;
+                else r.src2 = (const char *)a.pe_new + ((int64_t)b * a.pns[0] + (int64_t)hk * a.pns[1] + t * a.pns[2]) * esz;
+                r.ss2 = a.pns[3];
+                r.off = a.d_v;
+            }
             r.cos = r.sin = nullptr;
             if (is_k && rotary) {
                 const int64_t pos = j < a.S_rot ? j : a.S_rot - 1;  // clamped: no length can read outside the tables
@@ -243,9 +274,9 @@ template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) 
             r.descale = 1.0f;
             if constexpr (KV != 0)
                 r.descale = is_k ? fa2_decode_descale(a.kd, a.kds[0], a.kds[1], b, hk) : fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
-            do_row<E, KV, VEC>(r, units, a.rotary_dim, a.interleaved);
+            do_row<E, KV, VEC, LAT>(r, units, a.rotary_dim, a.interleaved);
         } else {  // a row of Q, rotated into q_rot, contiguous in Q's dtype: (B, H, N_q, d), or (total_new, H, d) when packed
-            const int h = slab - 2 * a.H_kv;
+            const int h = slab - nkv;
             if constexpr (!PK)
                 if (t >= a.N_q) continue;
             int64_t pos = start + (a.q_pos_per_row ? t : 0);
@@ -259,10 +290,15 @@ template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) 
             }
             r.ss = a.qs[3];
             r.ds = 1;
+            if constexpr (LAT) {
+                r.src2 = r.src + (int64_t)a.d_v * a.qs[3] * esz;
+                r.ss2 = a.qs[3];
+                r.off = a.d_v;
+            }
             r.cos = (const char *)a.cos + pos * a.cos_stride * esz;
             r.sin = (const char *)a.sin + pos * a.sin_stride * esz;
             r.descale = 1.0f;
-            do_row<E, 0, VEC>(r, units, a.rotary_dim, a.interleaved);
+            do_row<E, 0, VEC, LAT>(r, units, a.rotary_dim, a.interleaved);
         }
     }
 }
@@ -270,13 +306,19 @@ template <class E, int KV, bool VEC, bool PK> __global__ __launch_bounds__(256) 
 bool aligned(const void *p, int64_t n) { return ((uintptr_t)p & (uintptr_t)(n - 1)) == 0; }
 bool rows8(const int64_t s[4]) { return s[3] == 1 && s[0] % 8 == 0 && s[1] % 8 == 0 && s[2] % 8 == 0; }
 
-// The vector path: 16-bit inputs, unit d-strides, every row it touches aligned to the width of its loads and stores.
+// The vector path: 16-bit inputs, unit d-strides, every row it touches aligned to the width of its loads and stores.  The latent
+// form (V null) has pe_new in v_new's place and no 8-column unit across the two sources: d_v % 8 == 0 (and so (d - d_v) % 8 == 0).
 bool vector_path(const Fa2AppendProblem &p) {
     if (p.dtype != FA2_DTYPE_F16 && p.dtype != FA2_DTYPE_BF16) return false;
     if (p.d % 8 != 0) return false;
     const int64_t cache_align = p.kv_dtype == p.dtype ? 16 : 8;
-    if (!rows8(p.kns) || !rows8(p.vns) || !rows8(p.ks) || !rows8(p.vs)) return false;
-    if (!aligned(p.k_new, 16) || !aligned(p.v_new, 16) || !aligned(p.K, cache_align) || !aligned(p.V, cache_align)) return false;
+    if (!p.V) {
+        if (p.d_v % 8 != 0 || !rows8(p.kns) || !rows8(p.pns) || !rows8(p.ks)) return false;
+        if (!aligned(p.k_new, 16) || !aligned(p.pe_new, 16) || !aligned(p.K, cache_align)) return false;
+    } else {
+        if (!rows8(p.kns) || !rows8(p.vns) || !rows8(p.ks) || !rows8(p.vs)) return false;
+        if (!aligned(p.k_new, 16) || !aligned(p.v_new, 16) || !aligned(p.K, cache_align) || !aligned(p.V, cache_align)) return false;
+    }
     if (p.cos) {
         if (p.rotary_dim % 16 != 0 || p.cos_stride % 8 != 0 || p.sin_stride % 8 != 0 || !aligned(p.cos, 16) || !aligned(p.sin, 16))
             return false;
@@ -285,7 +327,7 @@ bool vector_path(const Fa2AppendProblem &p) {
     return true;
 }
 
-template <class E, int KV, bool VEC> int launch(const Fa2AppendProblem &p) {
+template <class E, int KV, bool VEC, bool LAT> int launch_form(const Fa2AppendProblem &p) {
     const int units = VEC ? p.d / 8 : p.d;
     int tx = 1;
     while (tx < units && tx < 64) tx *= 2;
@@ -293,14 +335,14 @@ template <class E, int KV, bool VEC> int launch(const Fa2AppendProblem &p) {
     const int64_t ntok = p.cu_new ? p.total_new : (with_q && p.N_q > p.N_new ? p.N_q : p.N_new);
     int ty = 1;
     while (ty < ntok && tx * ty < 256) ty *= 2;
-    const int64_t nslab = 2 * (int64_t)p.H_kv + (with_q ? p.H : 0);
+    const int64_t nslab = (LAT ? 1 : 2) * (int64_t)p.H_kv + (with_q ? p.H : 0);
     if (p.cu_new) {  // flat over the packed rows; the first B threads of the blockIdx.y == 0 blocks write the lengths
         const int64_t rows = (ntok + ty - 1) / ty, lens = ((int64_t)p.B + tx * ty - 1) / (tx * ty);
         const dim3 grid((unsigned)(rows > lens ? rows : lens), (unsigned)(nslab < 65535 ? nslab : 65535));
-        hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC, true>), grid, dim3(tx, ty), 0, p.stream, p);
+        hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC, true, LAT>), grid, dim3(tx, ty), 0, p.stream, p);
     } else {
         const dim3 grid((unsigned)((ntok + ty - 1) / ty), (unsigned)(nslab < 65535 ? nslab : 65535), (unsigned)p.B);
-        hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC, false>), grid, dim3(tx, ty), 0, p.stream, p);
+        hipLaunchKernelGGL((fa2_decode_append_kernel<E, KV, VEC, false, LAT>), grid, dim3(tx, ty), 0, p.stream, p);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -308,6 +350,10 @@ template <class E, int KV, bool VEC> int launch(const Fa2AppendProblem &p) {
         return FA2_ERR_LAUNCH;
     }
     return FA2_OK;
+}
+
+template <class E, int KV, bool VEC> int launch(const Fa2AppendProblem &p) {
+    return p.V ? launch_form<E, KV, VEC, false>(p) : launch_form<E, KV, VEC, true>(p);
 }
 
 template <class E, bool VEC> int launch_kv(const Fa2AppendProblem &p) {

@@ -279,18 +279,23 @@ def check_kvcache_append_args(K_cache, V_cache, k_new, v_new, cache_seqlens, k_d
     if block_table is not None:
         _check_block_table(block_table, B, K_cache.shape[2], k_new, "k_new")
     if rotary_cos is not None:
-        d = k_new.shape[3]
-        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape != rotary_cos.shape or t.shape[0] < 1 \
-                    or not 1 <= t.shape[1] <= d // 2:
-                raise ValueError(f"kvcache: rotary_cos, rotary_sin must be (S_rot, rotary_dim / 2) of one shape with S_rot >= 1 and "
-                                 f"2 <= rotary_dim <= d = {d}, got {name} {tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
-            if t.dtype != k_new.dtype:
-                raise ValueError(f"kvcache: {name} must have k_new's dtype ({k_new.dtype}), got {t.dtype}")
-            if t.stride(1) != 1 or t.stride(0) < 0:
-                raise ValueError(f"kvcache: {name} needs unit stride in its last axis, got strides {tuple(t.stride())}")
-            if t.device != k_new.device:
-                raise ValueError(f"kvcache: {name} must be on k_new's device ({k_new.device}), got {t.device}")
+        _check_rotary_tables(rotary_cos, rotary_sin, k_new.shape[3], f"d = {k_new.shape[3]}", k_new, "k_new")
+
+
+def _check_rotary_tables(rotary_cos, rotary_sin, limit, bound, anchor, anchor_name):
+    """rotary_cos, rotary_sin beside the new tokens `anchor`, called `anchor_name` in the messages: rotary_dim at most `limit`, which
+    the messages spell `bound`."""
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape != rotary_cos.shape or t.shape[0] < 1 \
+                or not 1 <= t.shape[1] <= limit // 2:
+            raise ValueError(f"kvcache: rotary_cos, rotary_sin must be (S_rot, rotary_dim / 2) of one shape with S_rot >= 1 and "
+                             f"2 <= rotary_dim <= {bound}, got {name} {tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+        if t.dtype != anchor.dtype:
+            raise ValueError(f"kvcache: {name} must have {anchor_name}'s dtype ({anchor.dtype}), got {t.dtype}")
+        if t.stride(1) != 1 or t.stride(0) < 0:
+            raise ValueError(f"kvcache: {name} needs unit stride in its last axis, got strides {tuple(t.stride())}")
+        if t.device != anchor.device:
+            raise ValueError(f"kvcache: {name} must be on {anchor_name}'s device ({anchor.device}), got {t.device}")
 
 
 def kvcache_append(K_cache, V_cache, k_new, v_new, cache_seqlens, *, k_descale=None, v_descale=None, block_table=None,
@@ -498,9 +503,10 @@ def flash_attention_kvcache_forward(Q, K_cache, V_cache, cache_seqlens, dev, *, 
 
 
 def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale, window, num_splits, variant, k_descale, v_descale,
-                         block_table, k_new, v_new, rotary_cos, rotary_sin, latent=False, kv_descale=None):
+                         block_table, k_new, v_new, rotary_cos, rotary_sin, latent=False, kv_descale=None, append=None):
     """flash_attention_kvcache_forward with a V_cache whose last axis differs from K_cache's (fa2_fwd_kvcache_mla), and -- latent:
-    flash_attention_mla_decode_forward alone -- an fp8 cache with its one descale (fa2_fwd_kvcache_mla_fp8)."""
+    flash_attention_mla_decode_forward alone -- an fp8 cache with its one descale (fa2_fwd_kvcache_mla_fp8) and the fused step
+    (fa2_fwd_kvcache_mla_append): `append` is its checked (c_new, pe_new, rotary_cos, rotary_sin, rotary_interleaved)."""
     fp8 = K_cache.dtype in FP8_CACHE_DTYPES or V_cache.dtype in FP8_CACHE_DTYPES
     if fp8 and not latent:
         raise ValueError(f"kvcache: an fp8 K_cache / V_cache ({K_cache.dtype}) is not supported with d_v != d here: "
@@ -528,6 +534,18 @@ def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale,
     dtype = convert_triton_dtype(Q.dtype)
     n = num_splits or _lib.kvcache_mla_num_splits(B, H, H_kv, N_q, _capacity(K_cache, block_table), d, d_v, dtype)
     O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d_v), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0)
+    if append is not None:
+        c_new, pe_new, cos, sin, interleaved = append
+        if c_new.shape[0] != B or c_new.device != Q.device:
+            raise ValueError(f"mla decode: kv_new must have Q's batch size {B} and device ({Q.device}), got {tuple(c_new.shape)} on "
+                             f"{c_new.device}")
+        _lib.fa2_fwd_kvcache_mla_append(Q, K_cache, O, L, c_new, pe_new, cache_seqlens, torch.empty_like(cache_seqlens), dtype,
+                                        convert_triton_dtype(K_cache.dtype), block_table=block_table, kv_descale=kv_descale,
+                                        rotary_cos=cos, rotary_sin=sin, rotary_interleaved=interleaved,
+                                        q_rot=None if cos is None else torch.empty(B, H, N_q, d, dtype=Q.dtype, device=Q.device),
+                                        causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
+                                        variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
     if fp8:  # the one descale of the shared row is K's and V's
         _lib.fa2_fwd_kvcache_mla_fp8(Q, K_cache, V_cache, O, L, cache_seqlens, dtype, convert_triton_dtype(K_cache.dtype),
                                      k_descale=kv_descale, v_descale=kv_descale, block_table=block_table, causal=causal, scale=scale,
@@ -539,7 +557,8 @@ def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale,
 
 
 def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=512, causal=False, scale=1.0, window=None, num_splits=0,
-                                       variant="auto", block_table=None, kv_descale=None):
+                                       variant="auto", block_table=None, kv_descale=None, kv_new=None, rotary_cos=None, rotary_sin=None,
+                                       rotary_interleaved=False):
     """Multi-head latent attention decode, absorbed form, over the shared latent cache (fa2_fwd_kvcache_mla) -> (O, L).  Q
     (B, H, N_q, d); KV_cache (B, H_kv, S_k, d) or, with block_table, the page pool (num_blocks, H_kv, page_size, d): one row per key,
     d_v latent columns followed by the rotary ones (DeepSeek-V2 / V3 / R1, Kimi: H_kv = 1, d = 576, d_v = 512).  The score takes all
@@ -554,14 +573,141 @@ def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=5
     kv_descale None the result is, bit for bit, that of the cache converted to Q's dtype.  variant "mla16" then needs every stride
     of the cache a multiple of 16 elements.  kv_descale with a cache in Q's dtype is a ValueError.
 
-    The cache is only read: the latent row of a new token (its last d - d_v columns rotated, quantised where the cache is fp8) is
-    written by the caller, and the append and rotary arguments and packed queries are not supported."""
+    Append (fa2_fwd_kvcache_mla_append): with kv_new -- one tensor (B, H_kv, N_new, d) in Q's dtype, or the pair (c_new, pe_new)
+    with last axes d_v and d - d_v, any strides -- the call first writes the new rows into KV_cache IN PLACE as mla_kvcache_append
+    does, at key indices cache_seqlens[b] + t, and then attends over cache_seqlens + N_new keys (at most the capacity: tokens past it
+    are dropped).  cache_seqlens is required, holds the lengths before the append and is not modified.  rotary_cos, rotary_sin
+    (S_rot, rotary_dim / 2) in Q's dtype with unit last stride, rotary_dim <= d - d_v, rotate the columns [d_v, d_v + rotary_dim) of
+    the new rows at cache_seqlens[b] + t and of Q (a copy: Q itself is not modified) at cache_seqlens[b] + i for row i when the call
+    is causal or windowed, every row at cache_seqlens[b] otherwise, as flash-attn does; apply_rotary on those columns is the
+    arithmetic, bit for bit.  They need kv_new.  Without kv_new the cache is only read.  Packed queries are not supported."""
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError("mla decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < KV_cache.shape[3]:
         raise ValueError(f"mla decode: d_v must be an int in [1, d - 1] = [1, {KV_cache.shape[3] - 1}], got {d_v!r}")
+    append = None
+    if kv_new is not None or rotary_cos is not None or rotary_sin is not None:
+        check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin, Q)
+        append = (*_mla_sources(kv_new, d_v), rotary_cos, rotary_sin, rotary_interleaved)
     return _kvcache_mla_forward(Q, KV_cache, KV_cache[..., :d_v], cache_seqlens, dev, causal, scale, window, num_splits, variant, None,
-                                None, block_table, None, None, None, None, latent=True, kv_descale=kv_descale)
+                                None, block_table, None, None, None, None, latent=True, kv_descale=kv_descale, append=append)
+
+
+def _mla_sources(kv_new, d_v):
+    """(c_new, pe_new) of a kv_new argument: the pair as it is, or the two views of the one tensor."""
+    if isinstance(kv_new, torch.Tensor):
+        return kv_new[..., :d_v], kv_new[..., d_v:]
+    if isinstance(kv_new, (tuple, list)) and len(kv_new) == 2 and all(isinstance(t, torch.Tensor) for t in kv_new):
+        return kv_new[0], kv_new[1]
+    raise ValueError("mla: kv_new must be one tensor (..., d) or a pair (c_new, pe_new) of tensors")
+
+
+def check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v=512, kv_descale=None, block_table=None, rotary_cos=None, rotary_sin=None,
+                          Q=None, cu_seqlens_new=None, max_seqlen_new=None):
+    """ValueError for what mla_kvcache_append, mla_kvcache_append_varlen (with cu_seqlens_new and max_seqlen_new: kv_new packed) and
+    the append keywords of flash_attention_mla_decode_forward (with Q, which is rotated along) cannot take.  Pure: takes CPU tensors
+    as well."""
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("mla: rotary_cos and rotary_sin go together")
+    if kv_new is None:
+        if rotary_cos is not None:
+            raise ValueError("mla: rotary_cos / rotary_sin need kv_new (the rotation is part of the cache update)")
+        return
+    if cache_seqlens is None:
+        raise ValueError("mla: kv_new needs cache_seqlens (the position the new tokens go to)")
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4 or not 2 <= KV_cache.shape[3] <= 576:
+        raise ValueError("mla: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d) with d in [2, 576]")
+    d = KV_cache.shape[3]
+    if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
+        raise ValueError(f"mla: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
+    c_new, pe_new = _mla_sources(kv_new, d_v)
+    packed = cu_seqlens_new is not None or max_seqlen_new is not None
+    lead = 2 if packed else 3  # the axes in front of the columns
+    if c_new.dim() != lead + 1 or c_new.shape[:lead] != pe_new.shape[:lead] or c_new.shape[lead] != d_v or pe_new.shape[lead] != d - d_v \
+            or c_new.shape[lead - 1 if packed else 1] != KV_cache.shape[1] or c_new.shape[0 if packed else 2] < 1 \
+            or (not packed and block_table is None and c_new.shape[0] != KV_cache.shape[0]):
+        raise ValueError(f"mla: kv_new must be {'packed (total_new, H_kv, d)' if packed else '(B, H_kv, N_new, d)'} or a pair with last "
+                         f"axes d_v = {d_v} and d - d_v = {d - d_v}, at least one token, B, H_kv and d = {d} the cache's: got "
+                         f"{tuple(c_new.shape)} and {tuple(pe_new.shape)} beside KV_cache {tuple(KV_cache.shape)}")
+    if c_new.dtype != pe_new.dtype:
+        raise ValueError("mla: both tensors of kv_new must have the same dtype")
+    if c_new.dtype in FP8_CACHE_DTYPES:
+        raise ValueError(f"mla: dtype {c_new.dtype} is not supported for kv_new (an fp8 cache takes float16 / bfloat16)")
+    if packed:
+        if not isinstance(cu_seqlens_new, torch.Tensor) or cu_seqlens_new.dtype != torch.int32 or cu_seqlens_new.dim() != 1 \
+                or not cu_seqlens_new.is_contiguous() or cu_seqlens_new.numel() < 2:
+            raise ValueError("mla: cu_seqlens_new must be a contiguous int32 tensor of B + 1 >= 2 entries")
+        if cu_seqlens_new.device != c_new.device:
+            raise ValueError(f"mla: cu_seqlens_new must be on kv_new's device ({c_new.device}), got {cu_seqlens_new.device}")
+        if isinstance(max_seqlen_new, bool) or not isinstance(max_seqlen_new, int) or not 1 <= max_seqlen_new <= 1 << 28:
+            raise ValueError(f"mla: max_seqlen_new must be an int in [1, 2^28], got {max_seqlen_new!r}")
+        if c_new.shape[0] > 1 << 28 or c_new.shape[0] * 2 * c_new.shape[1] > 1 << 40:
+            raise ValueError(f"mla: total_new must be <= 2^28 and total_new * 2 * H_kv <= 2^40, got total_new = {c_new.shape[0]}")
+    B, H_kv = (cu_seqlens_new.numel() - 1, c_new.shape[1]) if packed else c_new.shape[:2]
+    if KV_cache.dtype in FP8_CACHE_DTYPES:
+        if c_new.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"mla: an fp8 cache needs kv_new in float16 or bfloat16, got {c_new.dtype}")
+        _kvcache_descale("kv_descale", kv_descale, c_new, B, H_kv)
+    else:
+        if c_new.dtype != KV_cache.dtype:
+            raise ValueError("mla: kv_new must have the cache's dtype (or the cache an fp8 dtype under 16-bit kv_new)")
+        if kv_descale is not None:
+            raise ValueError(f"mla: kv_descale goes with an fp8 KV_cache, not with {KV_cache.dtype}")
+    convert_triton_dtype(c_new.dtype)
+    if Q is not None and (packed or not isinstance(Q, torch.Tensor) or Q.dim() != 4 or Q.shape[3] != d or Q.dtype != c_new.dtype
+                          or Q.shape[0] != c_new.shape[0]):
+        raise ValueError(f"mla: Q goes with the fixed form and must be (B, H, N_q, d) in kv_new's dtype with its B and d = {d}")
+    for name, t in (("kv_new[1]", pe_new), ("KV_cache", KV_cache)):
+        if t.device != c_new.device:
+            raise ValueError(f"mla: {name} must be on kv_new's device ({c_new.device}), got {t.device}")
+    _check_cache_seqlens(cache_seqlens, B, c_new, "kv_new")
+    if block_table is not None:
+        _check_block_table(block_table, B, KV_cache.shape[2], c_new, "kv_new")
+    if rotary_cos is not None:
+        _check_rotary_tables(rotary_cos, rotary_sin, d - d_v, f"d - d_v = {d - d_v}", c_new, "kv_new")
+
+
+def mla_kvcache_append(KV_cache, kv_new, cache_seqlens, *, d_v=512, kv_descale=None, block_table=None, rotary_cos=None, rotary_sin=None,
+                       rotary_interleaved=False):
+    """The cache update of an MLA decode step alone (include/fa2_fwd.h fa2_kvcache_mla_append) -> new_seqlens, int32 (B,): what an
+    engine passes as the next step's cache_seqlens.  KV_cache is flash_attention_mla_decode_forward's latent cache, contiguous or a
+    pool with block_table, in kv_new's dtype or fp8 with its one kv_descale.  kv_new: one tensor (B, H_kv, N_new, d), or the pair
+    (c_new, pe_new) an engine holds -- the normalised latent (B, H_kv, N_new, d_v) and the un-rotated positional part
+    (B, H_kv, N_new, d - d_v) -- any strides.  Token t of sequence b becomes the row at key index clamp(cache_seqlens[b], 0, capacity)
+    + t, written IN PLACE: columns [0, d_v) from c_new, [d_v, d) from pe_new with its first rotary_dim columns rotated at that
+    position by rotary_cos / rotary_sin (apply_rotary on pe_new is the arithmetic; rotary_dim <= d - d_v), the whole row quantised
+    with kv_descale where the cache is fp8.  Tokens past the capacity are dropped and new_seqlens = min(cache_seqlens + N_new,
+    capacity); cache_seqlens is not modified.  Everything else is kvcache_append's."""
+    if kv_new is None:
+        raise ValueError("mla: mla_kvcache_append needs kv_new")
+    check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin)
+    c_new, pe_new = _mla_sources(kv_new, d_v)
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_kvcache_mla_append(KV_cache, c_new, pe_new, cache_seqlens, new_seqlens, convert_triton_dtype(c_new.dtype),
+                                convert_triton_dtype(KV_cache.dtype), block_table=block_table,
+                                kv_descale=_kvcache_descale("kv_descale", kv_descale, c_new, *c_new.shape[:2]), rotary_cos=rotary_cos,
+                                rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+    return new_seqlens
+
+
+def mla_kvcache_append_varlen(KV_cache, kv_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, *, d_v=512, kv_descale=None,
+                              block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+    """mla_kvcache_append for a ragged batch in one launch (include/fa2_fwd.h fa2_kvcache_mla_append_varlen) -> new_seqlens, int32
+    (B,).  kv_new packed: one tensor (total_new, H_kv, d) or the pair (total_new, H_kv, d_v), (total_new, H_kv, d - d_v), any strides;
+    cu_seqlens_new and max_seqlen_new as in kvcache_append_varlen: sequence b brings the min(cu[b + 1] - cu[b], max_seqlen_new) rows
+    from cu[b] on, none is legal, rows outside every sequence are not read, and new_seqlens is written for every sequence."""
+    if kv_new is None:
+        raise ValueError("mla: mla_kvcache_append_varlen needs kv_new")
+    check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin,
+                          cu_seqlens_new=cu_seqlens_new, max_seqlen_new=max_seqlen_new)
+    c_new, pe_new = _mla_sources(kv_new, d_v)
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_kvcache_mla_append_varlen(KV_cache, c_new, pe_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, new_seqlens,
+                                       convert_triton_dtype(c_new.dtype), convert_triton_dtype(KV_cache.dtype), block_table=block_table,
+                                       kv_descale=_kvcache_descale("kv_descale", kv_descale, c_new, cu_seqlens_new.numel() - 1,
+                                                                   c_new.shape[1]),
+                                       rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+    return new_seqlens
 
 
 def check_varlen_kvcache_args(Q, K_cache, V_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, window, num_splits, k_descale=None,

@@ -619,6 +619,86 @@ int fa2_fwd_kvcache_varlen_append(const void *Q, void *K, void *V, void *O, void
                                   int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                                   void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
+/*
+ * The write side of the latent (MLA) cache of fa2_fwd_kvcache_mla / _mla_fp8: fa2_kvcache_append for a cache that is ONE tensor
+ * whose rows hold d_v latent columns followed by d - d_v positional ones.  Lengths, clamps, the drop of tokens past the capacity,
+ * paging, the rotary arithmetic and the fp8 rule are fa2_kvcache_append's; what differs:
+ *
+ *   Cache.    KV: (B, H_kv, S_k, d) or, with block_table, the pool (num_blocks, H_kv, page_size, d), strides kv_strides, in
+ *             kv_dtype_enum (dtype_enum, or an fp8 format under f16 / bf16 inputs).  It is written once: the value of the decode
+ *             call is a view of the same rows.  d in [2, 576], d_v in [1, d - 1].
+ *   Sources.  A new row comes from two tensors in dtype_enum, each with strides of its own: c_new (B, H_kv, N_new, d_v) fills
+ *             columns [0, d_v), pe_new (B, H_kv, N_new, d - d_v) columns [d_v, d).  One (B, H_kv, N_new, d) tensor X is the call
+ *             with c_new = X, pe_new = X + d_v * (its d-stride) and both stride arrays X's.
+ *   Rotary.   With tables, columns [d_v, d_v + rotary_dim) -- pe_new's first rotary_dim -- are rotated at min(j, S_rot - 1) for
+ *             key index j; the pairing (i with i + rotary_dim / 2, or 2i with 2i + 1 when rotary_interleaved) is applied inside
+ *             that range, table column i belongs to pair i of it.  Columns before and behind the range are copied (16-bit / f32 /
+ *             f64 cache: bit for bit).  rotary_dim even, in [2, d - d_v].
+ *   fp8.      One descale for the whole row: kv_descale at [b * s[0] + h_kv * s[1]], null = 1, the stored byte
+ *             fp8(clamp(x / kv_descale)) of the unrounded fp32 value, as in fa2_kvcache_append.
+ *   Q.        Optional, with tables: Q (B, H, N_q, d), any strides, goes to the contiguous q_rot with the same columns
+ *             [d_v, d_v + rotary_dim) rotated at fa2_kvcache_append's positions (q_pos_per_row); every other column is copied
+ *             bit for bit.
+ *   Speed.    16-byte loads and 16- or 8-byte stores when dtype_enum is f16 / bf16, every d-stride is 1, the other strides are
+ *             multiples of 8, c_new, pe_new (and Q, q_rot, the tables) are 16-byte aligned, KV to 16 bytes (8 for an fp8 cache),
+ *             d_v % 8 == 0, d % 8 == 0 and rotary_dim % 16 == 0; one element at a time otherwise, with the same bytes.
+ *
+ * Errors as fa2_kvcache_append's, before any launch, the message naming the argument (KV, kv_strides, c_new, pe_new,
+ * c_new_strides, pe_new_strides, kv_descale, kv_descale_strides in K / V's places); FA2_ERR_UNSUPPORTED for d outside [2, 576] or
+ * d_v outside [1, d - 1], FA2_ERR_BAD_ARG for a rotary_dim that is odd or outside [2, d - d_v].
+ */
+int fa2_kvcache_mla_append(void *KV, const int64_t kv_strides[4], const int32_t *block_table, int64_t block_table_stride,
+                           const void *c_new, const void *pe_new, const int64_t c_new_strides[4], const int64_t pe_new_strides[4],
+                           const int32_t *cache_seqlens, int32_t *seqlens_out,
+                           const float *kv_descale, const int64_t kv_descale_strides[2],
+                           const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                           int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                           const void *Q, void *q_rot, const int64_t q_strides[4], int32_t H, int32_t N_q, int32_t q_pos_per_row,
+                           int32_t B, int32_t H_kv, int32_t N_new, int32_t S_k,
+                           int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                           int32_t dtype_enum, int32_t kv_dtype_enum, void *hip_stream);
+
+/*
+ * The packed (ragged) form of fa2_kvcache_mla_append, as fa2_kvcache_append_varlen is fa2_kvcache_append's: c_new
+ * (total_new, H_kv, d_v) and pe_new (total_new, H_kv, d - d_v) packed over cu_seqlens_new with strides {token, head, dim} (3
+ * each), Q and q_rot packed (total_new, H, d).  Spans, empty sequences, gaps, max_seqlen_new, the lengths and every guarantee
+ * about offsets are fa2_kvcache_append_varlen's, and so are its errors.
+ */
+int fa2_kvcache_mla_append_varlen(void *KV, const int64_t kv_strides[4], const int32_t *block_table, int64_t block_table_stride,
+                                  const void *c_new, const void *pe_new, const int64_t c_new_strides[3], const int64_t pe_new_strides[3],
+                                  const int32_t *cu_seqlens_new, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                                  const float *kv_descale, const int64_t kv_descale_strides[2],
+                                  const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                                  int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                  const void *Q, void *q_rot, const int64_t q_strides[3], int32_t H, int32_t q_pos_per_row,
+                                  int32_t B, int32_t H_kv, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                                  int32_t dtype_enum, int32_t kv_dtype_enum, void *hip_stream);
+
+/*
+ * The fused MLA decode step: fa2_kvcache_mla_append, then on the same stream fa2_fwd_kvcache_mla (kv_dtype_enum == dtype_enum) or
+ * fa2_fwd_kvcache_mla_fp8 over the updated cache with K = V = KV, v_strides = kv_strides, kv_descale for both descales, seqlens_out as
+ * its cache_seqlens and, with tables, q_rot (contiguous (B, H, N_q, d)) as its Q; q_rot may be null without them.  q_pos_per_row
+ * is causal || window_left >= 0 || window_right >= 0.  S_k is the capacity of a contiguous cache (block_table null), unlike
+ * fa2_fwd_kvcache_mla, which passes it in page_size.  cache_seqlens holds the lengths BEFORE the append and is not modified.
+ * num_splits and the workspace are fa2_kvcache_mla_num_splits' and fa2_kvcache_workspace_bytes(B, H, N_q, d_v, num_splits); the
+ * variants are fa2_fwd_kvcache_mla's.  Every error of both halves comes back before any launch, and a forced
+ * FA2_KVCACHE_VARIANT_MLA16 that cannot run the problem fails before the cache is written.
+ */
+int fa2_fwd_kvcache_mla_append(const void *Q, void *KV, void *O, void *L,
+                               const int64_t q_strides[4], const int64_t kv_strides[4], const int64_t o_strides[4],
+                               const int64_t l_strides[2], const int32_t *cache_seqlens, int32_t *seqlens_out,
+                               const int32_t *block_table, int64_t block_table_stride,
+                               const float *kv_descale, const int64_t kv_descale_strides[2],
+                               const void *c_new, const void *pe_new, const int64_t c_new_strides[4], const int64_t pe_new_strides[4],
+                               const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                               int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, void *q_rot,
+                               int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t N_new, int32_t S_k,
+                               int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                               int32_t dtype_enum, int32_t kv_dtype_enum,
+                               int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                               void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
 /* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
  * elements plus fp32 partial L of num_splits * B * H * N_q. */
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits);
