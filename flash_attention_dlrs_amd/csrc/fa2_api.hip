@@ -7,12 +7,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "fa2_common.h"
+#include "fa2_host.h"
 
 namespace {
 thread_local char g_err[512] = "";
-
-bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 
 int validate(const Fa2Problem &p) {
     if (!p.Q || !p.K || !p.V || !p.O || !p.L) {
@@ -54,23 +52,42 @@ int validate(const Fa2Problem &p) {
     return FA2_OK;
 }
 
-long long T_cus(long long n) { return (n * fa2_device_cus() + 128) / 256; }  // T(n) of pick_variant below
+// The thresholds of the tables below were measured on the full chip (256 CUs) and are written in tiles / jobs per 256 CUs: T(n) scales
+// them to the CU count of the current device (a partitioned or smaller part fills at proportionally smaller grids).
+struct Tiles {
+    const int cus = fa2_device_cus();
+    long long operator()(long long n) const { return (n * cus + 128) / 256; }
+};
+
+// n rows (and 512 of overrun) of K and V -- and of O, unless the problem is packed -- stay below the 2 GiB of a 32-bit buffer offset
+bool fits32(const Fa2Problem &p, int64_t n) {
+    const auto fits = [n](int64_t row) { return (n + 512) * row * 2 < (1LL << 31); };
+    return fits(p.ks[2]) && fits(p.vs[2]) && (p.cu_q || fits(p.os[2]));
+}
+
+long long tiles256(const Fa2Problem &p) { return (long long)((p.N + 255) / 256) * p.B * p.H; }
+
+// The jobs of a persistent grid of one 8-wave workgroup per CU (256-row tiles, tile PAIRS when causal), and whether they fill
+// `cus` CUs evenly: its time goes in steps of whole jobs per CU, and at most 20 % may be lost to them.
+long long jobs256(const Fa2Problem &p) {
+    const int nq256 = (p.N + 255) / 256;
+    return (long long)(p.causal ? (nq256 + 1) / 2 : nq256) * p.B * p.H;
+}
+bool even(long long jobs, int cus) {
+    const double x = (double)jobs / (double)cus;
+    return x <= 1.0 ? x >= 0.6 : (double)((jobs + cus - 1) / cus) / x <= 1.2;
+}
 
 // The static tile table, keyed like the reference's autotuner on (B, H, N, d) (plus dtype, causal, strides): the grid
 // size B * H * tiles decides between the key-split, 4-wave and one-workgroup-per-CU kernels.
 int pick_variant(const Fa2Problem &p) {
-    // The thresholds below were measured on the full chip (256 CUs) and are written in tiles / jobs per 256 CUs: T(n) scales
-    // them to the CU count of the current device (a partitioned or smaller part fills at proportionally smaller grids).
-    const int cus = fa2_device_cus();
-    auto T = [cus](long long n) { return (n * cus + 128) / 256; };
+    const Tiles T;
     if (fa2_mfma16_supports(p)) {
         // Software-pipelined kernel with LDS-DMA staging.  8 waves x 32 rows halves the K/V traffic per query
         // row; it needs enough 256-row tiles to fill 256 CUs, otherwise the 128-row tile spreads the work wider.
         // (N * row stride >= 2 GiB does not fit the 32-bit buffer offsets: fall back to the first MFMA kernel.)
-        const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31) &&
-                            (int64_t)(p.N + 512) * p.os[2] * 2 < (1LL << 31);
-        const long long wg256 = (long long)((p.N + 255) / 256) * p.B * p.H;
-        if (!fits32) return wg256 >= T(512) ? FA2_VARIANT_MFMA16_W8 : FA2_VARIANT_MFMA16;
+        const long long wg256 = tiles256(p);
+        if (!fits32(p, p.N)) return wg256 >= T(512) ? FA2_VARIANT_MFMA16_W8 : FA2_VARIANT_MFMA16;
         // d = 128, N a multiple of 256: the generated assembly kernel A64 (4 waves x 64 rows, one wave per SIMD, O / Q / V^T in
         // the accumulator file) wins from 64 jobs of 256 rows on -- a quarter of the CUs busy -- non-causal, and causal from
         // 192 jobs (or 96 when a job has at least eight key tiles); below that the key-split kernels keep more CUs busy.
@@ -87,13 +104,12 @@ int pick_variant(const Fa2Problem &p) {
         // CUs busy (64 jobs: 13.1 us for MFMA16K_R2K4 against 17.0)
         // (f16 at the reference's scale of 1 -- rescales every few tiles, see A64 below -- causal: only from 384 jobs = 192 units on;
         // at 128 units the 8-wave kernels lead by 3 .. 13 %, profiles/r03/mid_grid_f16_d64.jsonl)
-        const bool f16_hot64 = p.dtype == FA2_DTYPE_F16 && p.scale > 0.5f;
-        if (fa2_a64d_supports(p) && wg256 >= T(p.causal ? (f16_hot64 ? 384 : 192) : 160)) return FA2_VARIANT_A64D;
+        const bool f16_hot = p.dtype == FA2_DTYPE_F16 && p.scale > 0.5f;
+        if (fa2_a64d_supports(p) && wg256 >= T(p.causal ? (f16_hot ? 384 : 192) : 160)) return FA2_VARIANT_A64D;
         // f16 at the reference's scale of 1 rescales every few tiles (P must stay below 65 504); with one wave per SIMD a rescale is
         // ~2 000 cycles with three waves waiting, which the 8-wave kernels hide.  On a full chip A64 still leads; on half-filled
         // grids it loses 12 .. 30 % to them (profiles/r03/mid_grid_f16.jsonl: 64 jobs 30.9 vs 21.5 us, 128 jobs 32.0 vs 27.0, causal
         // N = 2048 128 jobs 60.1 vs 45.2), where bf16 -- which never rescales -- wins.  At softmax scales <= 0.5 f16 behaves like bf16.
-        const bool f16_hot = p.dtype == FA2_DTYPE_F16 && p.scale > 0.5f;
         const bool a64_grid = f16_hot ? wg256 >= T(256)
                                       : (p.causal ? (wg256 >= T(192) || (wg256 >= T(96) && p.N >= 2048)) : wg256 >= T(64));
         if (fa2_a64_supports(p) && a64_grid) {
@@ -134,17 +150,14 @@ int pick_variant(const Fa2Problem &p) {
         // MFMA16H -12..16 % / -5..10 %, 384 tiles (1.5 jobs per CU): MFMA16D_W4 -5 %; d = 128 causal, 384 tiles: MFMA16H
         // -16..19 %; d = 64 causal, 768 tiles (1.5 pairs per CU): MFMA16D_W4
         // -20 %, 256 tiles: MFMA16D_W4 -25 %.
-        const int nq256 = (p.N + 255) / 256;
-        const long long jobs = (long long)(p.causal ? (nq256 + 1) / 2 : nq256) * p.B * p.H;  // of MFMA16H
-        const double x = (double)jobs / (double)cus;
-        const bool even = x <= 1.0 ? x >= 0.6 : (double)((jobs + cus - 1) / cus) / x <= 1.2;  // <= 20 % lost to whole jobs
+        const bool even_h = even(jobs256(p), T.cus);  // MFMA16H's jobs: <= 20 % lost to whole jobs
         // (two full rounds of the 8-wave key-split workgroups: B1 H16 N4096 98 vs 105 us, B1 H8 N8192 173 vs 191; at
         // 1.5 rounds -- 384 tiles -- it loses 50 %)
         if (p.causal && p.d == 128 && wg128 > T(448) && wg128 <= T(512) && p.N >= 4096) return FA2_VARIANT_MFMA16K;
         if (p.d == 128) {
-            if (p.causal ? wg256 < T(320) : (wg256 < T(160) || !even)) return FA2_VARIANT_MFMA16D_W4;
+            if (p.causal ? wg256 < T(320) : (wg256 < T(160) || !even_h)) return FA2_VARIANT_MFMA16D_W4;
         } else {
-            if (wg256 < T(160) || !even) return FA2_VARIANT_MFMA16D_W4;
+            if (wg256 < T(160) || !even_h) return FA2_VARIANT_MFMA16D_W4;
         }
         // 8-wave tiles: MFMA16H (persistent grid, next-job prefetch, hand-ordered steady loop).  Against MFMA16D on
         // MI355X (benchmarks/lottery.py, alternating order): non-causal +4.4 % (d = 128, N = 4096), +3.4 % (N = 8192),
@@ -164,128 +177,139 @@ int pick_variant(const Fa2Problem &p) {
         // 8 waves (one workgroup per CU) when the job count -- 256-row tiles, tile pairs when causal -- fills the 256 CUs
         // evenly, else 4 waves: the rule of the bf16 table above, checked on 52 fp8 shapes (benchmarks/mid_grid_fp8.py,
         // profiles/r01/mid_grid_fp8.jsonl; the old single threshold lost up to 20 % at 1.5 jobs per CU).
-        const int nq256 = (p.N + 255) / 256;
-        const long long wg256 = (long long)nq256 * p.B * p.H;
-        const long long jobs = (long long)(p.causal ? (nq256 + 1) / 2 : nq256) * p.B * p.H;
-        const double x = (double)jobs / (double)cus;
-        const bool even = x <= 1.0 ? x >= 0.6 : (double)((jobs + cus - 1) / cus) / x <= 1.2;
+        const long long wg256 = tiles256(p);
+        const bool even_x = even(jobs256(p), T.cus);
         // the generated kernel (N a multiple of 256): best or equal on every even grid from 192 jobs on, +5 .. +9 % from 512 jobs on
         // (causal: +8 .. +19 %, profiles/r03/mid_grid_fp8_a8_causal.jsonl, a8_causal_vs_mfma8x.jsonl); at 1.5 jobs per CU (384) its
         // whole-job steps lose 10 % to the 4-wave kernel like the 8-wave one's
-        if (fa2_a8_supports(p) && wg256 >= T(192) && even) return FA2_VARIANT_A8;
-        return wg256 >= T(160) && even ? FA2_VARIANT_MFMA8X : FA2_VARIANT_MFMA8X_W4;
+        if (fa2_a8_supports(p) && wg256 >= T(192) && even_x) return FA2_VARIANT_A8;
+        return wg256 >= T(160) && even_x ? FA2_VARIANT_MFMA8X : FA2_VARIANT_MFMA8X_W4;
     }
     if (fa2_mfma32_supports(p)) return FA2_VARIANT_MFMA32;
     // 16-bit head sizes other than 64 / 128 (multiples of 8): the first MFMA kernel with the missing columns zero-filled
     // on load; 8 waves when there are enough 256-row tiles for the 256 CUs
     if (fa2_mfma16_supports_dp(p))
-        return (long long)((p.N + 255) / 256) * p.B * p.H >= T(512) ? FA2_VARIANT_MFMA16_W8 : FA2_VARIANT_MFMA16;
+        return tiles256(p) >= T(512) ? FA2_VARIANT_MFMA16_W8 : FA2_VARIANT_MFMA16;
     return FA2_VARIANT_GENERIC;
 }
 
-int run(const Fa2Problem &p, int variant) {
-    int rc = validate(p);
-    if (rc != FA2_OK) return rc;
-    if (variant == FA2_VARIANT_AUTO) variant = pick_variant(p);
-    switch (variant) {
-    case FA2_VARIANT_GENERIC: return fa2_launch_generic(p);
-    case FA2_VARIANT_MFMA16: return fa2_launch_mfma16(p, 4);
-    case FA2_VARIANT_MFMA16_W8: return fa2_launch_mfma16(p, 8);
-    case FA2_VARIANT_MFMA32: return fa2_launch_mfma32(p);
+// The dense table: every variant id with its launcher and its tile (B_r, B_c, waves), which fa2_query_tile_scaled reports.  The
+// experimental kernels, their A/B schedules and the timing-only ablations (wrong results by construction) are rows of the
+// experiments and ablation builds only.
+using P = const Fa2Problem &;
+struct DenseRow {
+    int id;
+    int (*launch)(P);
+    int B_r, B_c, waves;
+};
+const DenseRow kDense[] = {
+    {FA2_VARIANT_GENERIC, fa2_launch_generic, 16, 64, 4},
+    {FA2_VARIANT_MFMA16, [](P p) { return fa2_launch_mfma16(p, 4); }, 128, 64, 4},
+    {FA2_VARIANT_MFMA16_W8, [](P p) { return fa2_launch_mfma16(p, 8); }, 256, 64, 8},
+    {FA2_VARIANT_MFMA32, fa2_launch_mfma32, 128, 32, 4},
+    {FA2_VARIANT_MFMA8X, [](P p) { return fa2_launch_mfma8x(p, 8); }, 256, 64, 8},
+    {FA2_VARIANT_MFMA8X_W4, [](P p) { return fa2_launch_mfma8x(p, 4); }, 128, 64, 4},
+    {FA2_VARIANT_MFMA16K, [](P p) { return fa2_launch_mfma16k(p, 42); }, 128, 64, 8},
+    {FA2_VARIANT_MFMA16K_R2K2, [](P p) { return fa2_launch_mfma16k(p, 22); }, 64, 64, 4},
+    {FA2_VARIANT_MFMA16K_R2K4, [](P p) { return fa2_launch_mfma16k(p, 24); }, 64, 64, 8},
+    {FA2_VARIANT_MFMA16D, [](P p) { return fa2_launch_mfma16d(p, 8); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16D_W4, [](P p) { return fa2_launch_mfma16d(p, 4); }, 128, 32, 4},
+    {FA2_VARIANT_MFMA16H, [](P p) { return fa2_launch_mfma16h(p, 8); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16H_W4, [](P p) { return fa2_launch_mfma16h(p, 4); }, 128, 32, 4},
+    {FA2_VARIANT_A64, fa2_launch_a64, 256, 64, 4},
+    {FA2_VARIANT_A16, fa2_launch_a16, 256, 64, 4},
+    {FA2_VARIANT_A8, fa2_launch_a8, 256, 64, 4},
+    {FA2_VARIANT_A64D, fa2_launch_a64d, 256, 64, 4},
 #ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA16P: return fa2_launch_mfma16p(p, 4, 0);
-    case FA2_VARIANT_MFMA16P_W8: return fa2_launch_mfma16p(p, 8, 64);
-    case FA2_VARIANT_MFMA16X: return fa2_launch_mfma16x(p, 0);
-    case FA2_VARIANT_MFMA8: return fa2_launch_mfma8(p, 8);
-    case FA2_VARIANT_MFMA8_W4: return fa2_launch_mfma8(p, 4);
+    {FA2_VARIANT_MFMA16P, [](P p) { return fa2_launch_mfma16p(p, 4, 0); }, 128, 32, 4},
+    {FA2_VARIANT_MFMA16P_W8, [](P p) { return fa2_launch_mfma16p(p, 8, 64); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16X, [](P p) { return fa2_launch_mfma16x(p, 0); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA8, [](P p) { return fa2_launch_mfma8(p, 8); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA8_W4, [](P p) { return fa2_launch_mfma8(p, 4); }, 128, 32, 4},
+    {FA2_VARIANT_MFMA8U, [](P p) { return fa2_launch_mfma8x(p, 12); }, 128, 64, 4},
+    {FA2_VARIANT_MFMA16S, [](P p) { return fa2_launch_mfma16s(p, 8); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16S_W4, [](P p) { return fa2_launch_mfma16s(p, 4); }, 128, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 1, [](P p) { return fa2_launch_mfma16x(p, 1); }, 256, 32, 4},   // ablations (FA2_ABLATIONS builds)
+    {FA2_VARIANT_MFMA16X + 2048 * 3, [](P p) { return fa2_launch_mfma16x(p, 3); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 4, [](P p) { return fa2_launch_mfma16x(p, 4); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 7, [](P p) { return fa2_launch_mfma16x(p, 7); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 8, [](P p) { return fa2_launch_mfma16x(p, 8); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 15, [](P p) { return fa2_launch_mfma16x(p, 15); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 16, [](P p) { return fa2_launch_mfma16x(p, 16); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 32, [](P p) { return fa2_launch_mfma16x(p, 32); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16X + 2048 * 48, [](P p) { return fa2_launch_mfma16x(p, 48); }, 256, 32, 4},
+    {FA2_VARIANT_MFMA16P + 16, [](P p) { return fa2_launch_mfma16p(p, 4, 1); }, 128, 32, 4},     // experimental schedules (A/B only)
+    {FA2_VARIANT_MFMA16P_W8 + 16, [](P p) { return fa2_launch_mfma16p(p, 8, 1); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 32, [](P p) { return fa2_launch_mfma16p(p, 8, 2); }, 256, 32, 8},   // ablations: only in -DFA2_ABLATIONS builds
+    {FA2_VARIANT_MFMA16P_W8 + 64, [](P p) { return fa2_launch_mfma16p(p, 8, 4); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 128, [](P p) { return fa2_launch_mfma16p(p, 8, 8); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 224, [](P p) { return fa2_launch_mfma16p(p, 8, 14); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 256, [](P p) { return fa2_launch_mfma16p(p, 8, 16); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 512, [](P p) { return fa2_launch_mfma16p(p, 8, 32); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 736, [](P p) { return fa2_launch_mfma16p(p, 8, 46); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 192 * 16, [](P p) { return fa2_launch_mfma16p(p, 8, 192); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P_W8 + 1024, [](P p) { return fa2_launch_mfma16p(p, 8, 0); }, 256, 32, 8},
+    {FA2_VARIANT_MFMA16P + 1024, [](P p) { return fa2_launch_mfma16p(p, 4, 64); }, 128, 32, 4},
 #endif
-    case FA2_VARIANT_MFMA8X: return fa2_launch_mfma8x(p, 8);
-    case FA2_VARIANT_MFMA8X_W4: return fa2_launch_mfma8x(p, 4);
-#ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA8U: return fa2_launch_mfma8x(p, 12);
-#endif
-    case FA2_VARIANT_MFMA16K: return fa2_launch_mfma16k(p, 42);
-    case FA2_VARIANT_MFMA16K_R2K2: return fa2_launch_mfma16k(p, 22);
-    case FA2_VARIANT_MFMA16K_R2K4: return fa2_launch_mfma16k(p, 24);
-    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d(p, 8);
-    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d(p, 4);
-    case FA2_VARIANT_MFMA16H: return fa2_launch_mfma16h(p, 8);
-    case FA2_VARIANT_MFMA16H_W4: return fa2_launch_mfma16h(p, 4);
-    case FA2_VARIANT_A64: return fa2_launch_a64(p);
-    case FA2_VARIANT_A16: return fa2_launch_a16(p);
-    case FA2_VARIANT_A8: return fa2_launch_a8(p);
-    case FA2_VARIANT_A64D: return fa2_launch_a64d(p);
-#ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA16S: return fa2_launch_mfma16s(p, 8);
-    case FA2_VARIANT_MFMA16S_W4: return fa2_launch_mfma16s(p, 4);
-    case FA2_VARIANT_MFMA16X + 2048 * 1: return fa2_launch_mfma16x(p, 1);   // ablations (FA2_ABLATIONS builds)
-    case FA2_VARIANT_MFMA16X + 2048 * 3: return fa2_launch_mfma16x(p, 3);
-    case FA2_VARIANT_MFMA16X + 2048 * 4: return fa2_launch_mfma16x(p, 4);
-    case FA2_VARIANT_MFMA16X + 2048 * 7: return fa2_launch_mfma16x(p, 7);
-    case FA2_VARIANT_MFMA16X + 2048 * 8: return fa2_launch_mfma16x(p, 8);
-    case FA2_VARIANT_MFMA16X + 2048 * 15: return fa2_launch_mfma16x(p, 15);
-    case FA2_VARIANT_MFMA16X + 2048 * 16: return fa2_launch_mfma16x(p, 16);
-    case FA2_VARIANT_MFMA16X + 2048 * 32: return fa2_launch_mfma16x(p, 32);
-    case FA2_VARIANT_MFMA16X + 2048 * 48: return fa2_launch_mfma16x(p, 48);
-    case FA2_VARIANT_MFMA16P + 16: return fa2_launch_mfma16p(p, 4, 1);     // experimental schedules (A/B only)
-    case FA2_VARIANT_MFMA16P_W8 + 16: return fa2_launch_mfma16p(p, 8, 1);
-    case FA2_VARIANT_MFMA16P_W8 + 32: return fa2_launch_mfma16p(p, 8, 2);   // ablations: only in -DFA2_ABLATIONS builds
-    case FA2_VARIANT_MFMA16P_W8 + 64: return fa2_launch_mfma16p(p, 8, 4);
-    case FA2_VARIANT_MFMA16P_W8 + 128: return fa2_launch_mfma16p(p, 8, 8);
-    case FA2_VARIANT_MFMA16P_W8 + 224: return fa2_launch_mfma16p(p, 8, 14);
-    case FA2_VARIANT_MFMA16P_W8 + 256: return fa2_launch_mfma16p(p, 8, 16);
-    case FA2_VARIANT_MFMA16P_W8 + 512: return fa2_launch_mfma16p(p, 8, 32);
-    case FA2_VARIANT_MFMA16P_W8 + 736: return fa2_launch_mfma16p(p, 8, 46);
-    case FA2_VARIANT_MFMA16P_W8 + 192 * 16: return fa2_launch_mfma16p(p, 8, 192);
-    case FA2_VARIANT_MFMA16P_W8 + 1024: return fa2_launch_mfma16p(p, 8, 0);
-    case FA2_VARIANT_MFMA16P + 1024: return fa2_launch_mfma16p(p, 4, 64);
-#endif
-    default: fa2_set_error("unknown kernel variant %d", variant); return FA2_ERR_BAD_ARG;
-    }
+};
+const DenseRow *dense_row(int id) {
+    for (const DenseRow &row : kDense)
+        if (row.id == id) return &row;
+    return nullptr;
 }
 
 // Windowed table (fa2_fwd_window): the pipelined LDS-DMA kernel where it runs -- 8 or 4 waves by grid fill, rule (3) of the static
 // table above -- else the VALU kernel.  The window makes the work per tile uniform away from the sequence ends, so one 128- or
 // 256-row tile per workgroup.
 int pick_window_variant(const Fa2Problem &p) {
-    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31) &&
-                        (int64_t)(p.N + 512) * p.os[2] * 2 < (1LL << 31);
-    if (fa2_mfma16_supports(p) && fits32) {
-        const long long wg256 = (long long)((p.N + 255) / 256) * p.B * p.H;
-        return wg256 >= T_cus(160) ? FA2_VARIANT_MFMA16D : FA2_VARIANT_MFMA16D_W4;
-    }
-    return FA2_VARIANT_GENERIC;
+    const Tiles T;
+    if (!fa2_mfma16_supports(p) || !fits32(p, p.N)) return FA2_VARIANT_GENERIC;
+    return tiles256(p) >= T(160) ? FA2_VARIANT_MFMA16D : FA2_VARIANT_MFMA16D_W4;
 }
 
-int run_window(const Fa2Problem &p, int variant) {
-    int rc = validate(p);
-    if (rc != FA2_OK) return rc;
-    if (variant == FA2_VARIANT_AUTO) variant = pick_window_variant(p);
+// Varlen table: the windowed one's kernels, the 32-bit offsets judged on one sequence (max_seqlen_k x row stride, not the packed
+// total).  4 waves: one 128-row tile per workgroup measured faster than the 8-wave form on every packed shape benchmarked
+// (profiles/varlen/bench_varlen.jsonl; the varlen form has no causal tile pairs to fill a 256-row workgroup)
+int pick_varlen_variant(const Fa2Problem &p) {
+    return fa2_mfma16_supports(p) && fits32(p, p.max_k) ? FA2_VARIANT_MFMA16D_W4 : FA2_VARIANT_GENERIC;
+}
+
+// The table of the other four forms (FA2_FORM_WINDOW .. FA2_FORM_VARLEN_GQA): each takes GENERIC, MFMA16D and MFMA16D_W4 and
+// refuses any other id with its own sentence.
+struct FormRow {
+    int (*generic)(P, int g);
+    int (*mfma16d)(P, int waves, int g);
+    const char *other;
+};
+const FormRow kForms[4] = {
+    {[](P p, int) { return fa2_launch_generic_window(p); }, [](P p, int waves, int) { return fa2_launch_mfma16d_window(p, waves); },
+     "kernel variant %d does not take a window (generic, mfma16d and mfma16d_w4 do)"},
+    {[](P p, int) { return fa2_launch_generic_varlen(p); }, [](P p, int waves, int) { return fa2_launch_mfma16d_varlen(p, waves); },
+     "kernel variant %d has no varlen form (generic, mfma16d and mfma16d_w4 do)"},
+    {fa2_launch_generic_window_gqa, fa2_launch_mfma16d_window_gqa,
+     "kernel variant %d has no GQA form for this layout (generic, mfma16d and mfma16d_w4 do; a layout with batch strides H x the head "
+     "strides takes every variant)"},
+    {fa2_launch_generic_varlen_gqa, fa2_launch_mfma16d_varlen_gqa,
+     "kernel variant %d has no varlen GQA form (generic, mfma16d and mfma16d_w4 do)"},
+};
+
+// Step 3: the launch of a checked problem in its form, AUTO resolved by the form's table.
+int run_fwd(const Fa2Problem &p, Fa2Form form, int variant) {
+    if (form.kind == FA2_FORM_DENSE) {
+        const DenseRow *row = dense_row(variant == FA2_VARIANT_AUTO ? pick_variant(p) : variant);
+        if (row) return row->launch(p);
+        fa2_set_error("unknown kernel variant %d", variant);
+        return FA2_ERR_BAD_ARG;
+    }
+    const bool packed = form.kind == FA2_FORM_VARLEN || form.kind == FA2_FORM_VARLEN_GQA;
+    if (variant == FA2_VARIANT_AUTO) variant = packed ? pick_varlen_variant(p) : pick_window_variant(p);
+    const FormRow &row = kForms[form.kind - FA2_FORM_WINDOW];
     switch (variant) {
-    case FA2_VARIANT_GENERIC: return fa2_launch_generic_window(p);
-    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_window(p, 8);
-    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_window(p, 4);
-    default:
-        fa2_set_error("kernel variant %d does not take a window (generic, mfma16d and mfma16d_w4 do)", variant);
-        return FA2_ERR_UNSUPPORTED;
+    case FA2_VARIANT_GENERIC: return row.generic(p, form.g);
+    case FA2_VARIANT_MFMA16D: return row.mfma16d(p, 8, form.g);
+    case FA2_VARIANT_MFMA16D_W4: return row.mfma16d(p, 4, form.g);
+    default: fa2_set_error(row.other, variant); return FA2_ERR_UNSUPPORTED;
     }
-}
-
-Fa2Problem make_problem(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t *qs,
-                        const int64_t *ks, const int64_t *vs, const int64_t *os, const int64_t *ls, int32_t B,
-                        int32_t H, int32_t N, int32_t d, int32_t dtype, int32_t causal, float scale, void *stream) {
-    Fa2Problem p;
-    memset(&p, 0, sizeof(p));
-    p.Q = Q; p.K = K; p.V = V; p.O = O; p.L = L;
-    if (qs && ks && vs && os && ls) {
-        for (int k = 0; k < 4; ++k) { p.qs[k] = qs[k]; p.ks[k] = ks[k]; p.vs[k] = vs[k]; p.os[k] = os[k]; }
-        p.ls[0] = ls[0]; p.ls[1] = ls[1];
-    } else {
-        p.Q = nullptr;  // fails validate()
-    }
-    p.B = B; p.H = H; p.N = N; p.d = d; p.dtype = dtype; p.causal = causal ? 1 : 0; p.scale = scale;
-    p.stream = (hipStream_t)stream;
-    return p;
 }
 }  // namespace
 
@@ -334,10 +358,8 @@ void Fa2DeviceLatch::mark() { __atomic_fetch_or(&done, 1ull << current_device(),
 
 int fa2_window_normalise(int32_t N, int32_t causal, int32_t wl, int32_t wr, int32_t *causal_out, int32_t *wl_out, int32_t *wr_out,
                          int32_t *windowed) {
-    if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
-    }
+    const int rc = fa2_check_window_sides(wl, wr);
+    if (rc != FA2_OK) return rc;
     const int32_t full = N > 1 ? N - 1 : 0;  // a side of N - 1 or more removes nothing
     int32_t l = (wl < 0 || wl >= full) ? full : wl, r = (wr < 0 || wr >= full) ? full : wr;
     if (causal) r = 0;
@@ -368,205 +390,184 @@ int fa2_check_gqa(int32_t H, int32_t H_kv) {
 }
 
 namespace {
-int fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
-               const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t N,
-               int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr, void *hip_stream, int32_t variant) {
-    int32_t c = causal, l = 0, r = 0, windowed = 0;
-    if (N >= 1) {  // (N < 1 is reported by validate())
-        const int rc = fa2_window_normalise(N, causal, wl, wr, &c, &l, &r, &windowed);
-        if (rc != FA2_OK) return rc;
-    } else if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
-    }
-    Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, c,
-                                scale, hip_stream);
-    if (!windowed) return run(p, variant);  // the window removes nothing beyond plain / causal attention: the same path
-    p.causal = 0;
-    p.wl = l;
-    p.wr = r;
-    return run_window(p, variant);
-}
-}  // namespace
+// Step 1: the raw arguments of any of the ten forward entry points.  A dense call has 4-element strides {batch, head, token, d}, L's
+// two and N; a packed one 3-element strides {token, head, d} and the parts behind `packed`.  Window sides of (-1, -1) are no window.
+struct FwdCall {
+    const void *Q, *K, *V;
+    void *O, *L;
+    const int64_t *q_strides, *k_strides, *v_strides, *o_strides, *l_strides;
+    int32_t B, H, N, d, dtype_enum, causal;
+    float scale;
+    void *hip_stream;
+    int32_t variant;
+    int32_t window_left = -1, window_right = -1;
+    bool gqa = false;  // fa2_fwd_gqa, fa2_fwd_varlen_gqa: K and V have H_kv heads
+    int32_t H_kv = 0;
+    bool packed = false;  // fa2_fwd_varlen, fa2_fwd_varlen_gqa: B sequences over cu_seqlens_*, L is (H, total_q)
+    const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k = nullptr;
+    int32_t max_seqlen_q = 0, max_seqlen_k = 0, total_q = 0, total_k = 0;
+    int64_t l_head_stride = 0;
+};
 
-namespace {
-// Variable-length (packed) attention, fa2_fwd_varlen: arguments checked before any launch; the varlen table is the windowed one.
-int fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3], const int64_t k_strides[3],
-               const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
-               const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k,
-               int32_t total_q, int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr,
-               void *hip_stream, int32_t variant, int32_t gqa = 1) {
-    const void *ptrs[9] = {Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides};
-    const char *names[9] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides"};
-    for (int t = 0; t < 9; ++t)
-        if (!ptrs[t]) {
-            fa2_set_error("varlen: null %s", names[t]);
-            return FA2_ERR_BAD_ARG;
-        }
-    if (!cu_seqlens_q || !cu_seqlens_k) {
-        fa2_set_error("varlen: null %s", !cu_seqlens_q ? "cu_seqlens_q" : "cu_seqlens_k");
-        return FA2_ERR_BAD_ARG;
+// Step 2: every argument tested, in the one order tests/golden/train_host_calls.json records -- H_kv, then a packed call's pointers
+// and sizes or a dense call's window, then validate() -- yielding the problem to launch and the form that runs it.
+//
+// Dense grouped-query attention (H_kv < H).  A mergeable layout -- B == 1, or the batch strides of Q, O, L a multiple H of their
+// head strides and those of K, V a multiple H_kv -- is the MHA problem of B' = B * H_kv batches of g = H / H_kv heads each sharing
+// one K / V head (head stride 0): every kernel of the dense and windowed tables runs it unchanged, and the table sees the same
+// B * H.  Any other layout runs the windowed GQA forms, a plain or causal problem as the full band.
+int check_fwd(const FwdCall &c, Fa2Problem &p, Fa2Form &form) {
+    form = {FA2_FORM_DENSE, 1};
+    if (c.gqa) {  // H_kv must divide H: FA2_ERR_BAD_ARG before anything else
+        const int rc = fa2_check_gqa(c.H, c.H_kv);
+        if (rc != FA2_OK) return rc;
+        if (c.H >= 1) form.g = c.H / c.H_kv;
     }
-    if (B < 1 || B > 65535) {
-        fa2_set_error("varlen: B (number of sequences) must be in [1, 65535] (got %d)", B);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (H < 1 || H > 65535) {
-        fa2_set_error("varlen: H must be in [1, 65535] (got %d)", H);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (max_seqlen_q < 0 || max_seqlen_k < 0 || max_seqlen_q > (1 << 28) || max_seqlen_k > (1 << 28)) {
-        fa2_set_error("varlen: max_seqlen_q and max_seqlen_k must be in [0, 2^28] (got %d, %d)", max_seqlen_q, max_seqlen_k);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (total_q < 0 || total_k < 0) {
-        fa2_set_error("varlen: total_q and total_k must be >= 0 (got %d, %d)", total_q, total_k);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (dtype_enum == FA2_DTYPE_F8E5M2 || dtype_enum == FA2_DTYPE_F8E4M3) {
-        fa2_set_error("varlen: fp8 is not supported (no backward; e4m3fn cannot hold L = +inf)");
-        return FA2_ERR_UNSUPPORTED;
-    }
-    const int64_t qs4[4] = {0, q_strides[1], q_strides[0], q_strides[2]}, ks4[4] = {0, k_strides[1], k_strides[0], k_strides[2]};
-    const int64_t vs4[4] = {0, v_strides[1], v_strides[0], v_strides[2]}, os4[4] = {0, o_strides[1], o_strides[0], o_strides[2]};
-    const int64_t ls2[2] = {0, l_head_stride};
-    const int32_t nmax = max_seqlen_q > max_seqlen_k ? max_seqlen_q : max_seqlen_k;
-    // N (only for validate() and the support predicates): the longest extent, at least 1
-    Fa2Problem p = make_problem(Q, K, V, O, L, qs4, ks4, vs4, os4, ls2, B, H, nmax > 0 ? nmax : 1, d, dtype_enum, causal, scale,
-                                hip_stream);
-    int rc = validate(p);
-    if (rc != FA2_OK) return rc;
-    if (l_head_stride < 0) {
-        fa2_set_error("varlen: negative L head stride");
-        return FA2_ERR_BAD_ARG;
-    }
-    p.wl = wl;
-    p.wr = wr;
-    p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
-    p.max_q = max_seqlen_q; p.max_k = max_seqlen_k; p.total_q = total_q; p.total_k = total_k;
-    if (variant == FA2_VARIANT_AUTO) {
-        const bool fits32 = (int64_t)(p.max_k + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.max_k + 512) * p.vs[2] * 2 < (1LL << 31);
-        // 4 waves: one 128-row tile per workgroup measured faster than the 8-wave form on every packed shape benchmarked
-        // (profiles/varlen/bench_varlen.jsonl; the varlen form has no causal tile pairs to fill a 256-row workgroup)
-        if (fa2_mfma16_supports(p) && fits32) {
-            variant = FA2_VARIANT_MFMA16D_W4;
-        } else {
-            variant = FA2_VARIANT_GENERIC;
-        }
-    }
-    if (gqa > 1) {  // grouped-query: K and V carry H / gqa heads
-        switch (variant) {
-        case FA2_VARIANT_GENERIC: return fa2_launch_generic_varlen_gqa(p, gqa);
-        case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_varlen_gqa(p, 8, gqa);
-        case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_varlen_gqa(p, 4, gqa);
-        default:
-            fa2_set_error("kernel variant %d has no varlen GQA form (generic, mfma16d and mfma16d_w4 do)", variant);
+    memset(&p, 0, sizeof(p));
+    p.Q = c.Q; p.K = c.K; p.V = c.V; p.O = c.O; p.L = c.L;
+    p.B = c.B; p.H = c.H; p.d = c.d; p.dtype = c.dtype_enum; p.causal = c.causal ? 1 : 0; p.scale = c.scale;
+    p.stream = (hipStream_t)c.hip_stream;
+    if (c.packed) {
+        const void *ptrs[9] = {c.Q, c.K, c.V, c.O, c.L, c.q_strides, c.k_strides, c.v_strides, c.o_strides};
+        const char *names[9] = {"Q", "K", "V", "O", "L", "q_strides", "k_strides", "v_strides", "o_strides"};
+        int rc = fa2_check_nonnull("varlen", ptrs, names, 9);
+        if (rc == FA2_OK) rc = fa2_check_packed("varlen", c, true);
+        if (rc != FA2_OK) return rc;
+        if (c.dtype_enum == FA2_DTYPE_F8E5M2 || c.dtype_enum == FA2_DTYPE_F8E4M3) {
+            fa2_set_error("varlen: fp8 is not supported (no backward; e4m3fn cannot hold L = +inf)");
             return FA2_ERR_UNSUPPORTED;
         }
-    }
-    switch (variant) {
-    case FA2_VARIANT_GENERIC: return fa2_launch_generic_varlen(p);
-    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_varlen(p, 8);
-    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_varlen(p, 4);
-    default:
-        fa2_set_error("kernel variant %d has no varlen form (generic, mfma16d and mfma16d_w4 do)", variant);
-        return FA2_ERR_UNSUPPORTED;
-    }
-}
-
-// Grouped-query attention, dense layout (fa2_fwd_gqa).  H_kv == H is fa2_fwd_window itself.  A mergeable layout -- B == 1, or the
-// batch strides of Q, O, L a multiple H of their head strides and those of K, V a multiple H_kv -- is the MHA problem of
-// B' = B * H_kv batches of g = H / H_kv heads each sharing one K / V head (head stride 0): every kernel of the dense and windowed
-// tables runs it unchanged, and the table sees the same B * H.  Any other layout runs the windowed GQA forms, a plain or causal
-// problem as the full band.
-int fwd_gqa(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
-            const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv,
-            int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t wl, int32_t wr, void *hip_stream,
-            int32_t variant) {
-    int rc = fa2_check_gqa(H, H_kv);
-    if (rc != FA2_OK) return rc;
-    if (H_kv == H)
-        return fwd_window(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal,
-                          scale, wl, wr, hip_stream, variant);
-    int32_t c = causal, l = 0, r = 0, windowed = 0;
-    if (N >= 1) {  // (N < 1 is reported by validate())
-        rc = fa2_window_normalise(N, causal, wl, wr, &c, &l, &r, &windowed);
+        fa2_packed_strides4(c.q_strides, p.qs); fa2_packed_strides4(c.k_strides, p.ks);
+        fa2_packed_strides4(c.v_strides, p.vs); fa2_packed_strides4(c.o_strides, p.os);
+        fa2_set_packed(c, p);
+        rc = validate(p);
         if (rc != FA2_OK) return rc;
-    } else if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
+        if (c.l_head_stride < 0) {
+            fa2_set_error("varlen: negative L head stride");
+            return FA2_ERR_BAD_ARG;
+        }
+        form.kind = form.g > 1 ? FA2_FORM_VARLEN_GQA : FA2_FORM_VARLEN;
+        return FA2_OK;
     }
-    Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, c,
-                                scale, hip_stream);
+    Fa2Window w;
+    int rc = fa2_window_of(c.N, c.causal, c.window_left, c.window_right, w);
+    if (rc != FA2_OK) return rc;
+    if (c.q_strides && c.k_strides && c.v_strides && c.o_strides && c.l_strides) {
+        for (int k = 0; k < 4; ++k) { p.qs[k] = c.q_strides[k]; p.ks[k] = c.k_strides[k]; p.vs[k] = c.v_strides[k]; p.os[k] = c.o_strides[k]; }
+        p.ls[0] = c.l_strides[0]; p.ls[1] = c.l_strides[1];
+    } else {
+        p.Q = nullptr;  // fails validate()
+    }
+    p.N = c.N;
+    p.causal = w.causal;
     rc = validate(p);
     if (rc != FA2_OK) return rc;
-    const int g = H / H_kv;
+    if (w.windowed) {  // (a window that removes nothing beyond plain / causal attention stays the dense form)
+        form.kind = FA2_FORM_WINDOW;
+        p.causal = 0;
+        p.wl = w.wl;
+        p.wr = w.wr;
+    }
+    if (form.g == 1) return FA2_OK;
+    const int g = form.g, H_kv = c.H_kv;
     if (H_kv == 1) {  // (a size-1 head dimension may carry any stride -- torch leaves it free: only the batch stride is read)
         p.ks[1] = p.ks[0];
         p.vs[1] = p.vs[0];
     }
-    bool mergeable = B == 1 || (p.qs[0] == (int64_t)H * p.qs[1] && p.os[0] == (int64_t)H * p.os[1] &&
-                                p.ls[0] == (int64_t)H * p.ls[1] && p.ks[0] == (int64_t)H_kv * p.ks[1] &&
-                                p.vs[0] == (int64_t)H_kv * p.vs[1]);
-    if (mergeable && (int64_t)B * H_kv > 65535) {
+    bool mergeable = c.B == 1 || (p.qs[0] == (int64_t)c.H * p.qs[1] && p.os[0] == (int64_t)c.H * p.os[1] &&
+                                  p.ls[0] == (int64_t)c.H * p.ls[1] && p.ks[0] == (int64_t)H_kv * p.ks[1] &&
+                                  p.vs[0] == (int64_t)H_kv * p.vs[1]);
+    if (mergeable && (int64_t)c.B * H_kv > 65535) {
         // the merged problem has B * H_kv batches: the generic kernel's grid takes at most 65535 of them (grid y), so a problem
         // that would run there stays unmerged and runs the GQA form, whose grid holds the B the caller passed
         Fa2Problem m = p;
-        m.B = (int64_t)B * H_kv > 0x7fffffff ? 0x7fffffff : B * H_kv;
+        m.B = (int64_t)c.B * H_kv > 0x7fffffff ? 0x7fffffff : c.B * H_kv;
         m.H = g;
-        if (windowed) {
-            m.causal = 0;
-            m.wl = l;
-            m.wr = r;
-        }
-        const int v = variant != FA2_VARIANT_AUTO ? variant : (windowed ? pick_window_variant(m) : pick_variant(m));
-        if (v == FA2_VARIANT_GENERIC || (int64_t)B * H_kv > 0x7fffffff) mergeable = false;
+        const int v = c.variant != FA2_VARIANT_AUTO ? c.variant : (w.windowed ? pick_window_variant(m) : pick_variant(m));
+        if (v == FA2_VARIANT_GENERIC || (int64_t)c.B * H_kv > 0x7fffffff) mergeable = false;
     }
     if (mergeable) {
-        Fa2Problem m = p;
-        m.B = B * H_kv;  // (<= B * H)
-        m.H = g;
-        m.qs[0] = g * p.qs[1];
-        m.os[0] = g * p.os[1];
-        m.ls[0] = g * p.ls[1];
-        m.ks[0] = p.ks[1];
-        m.ks[1] = 0;
-        m.vs[0] = p.vs[1];
-        m.vs[1] = 0;
-        if (!windowed) return run(m, variant);
-        m.causal = 0;
-        m.wl = l;
-        m.wr = r;
-        return run_window(m, variant);
+        p.B = c.B * H_kv;  // (<= B * H)
+        p.H = g;
+        p.qs[0] = g * p.qs[1];
+        p.os[0] = g * p.os[1];
+        p.ls[0] = g * p.ls[1];
+        p.ks[0] = p.ks[1];
+        p.ks[1] = 0;
+        p.vs[0] = p.vs[1];
+        p.vs[1] = 0;
+        return FA2_OK;
     }
+    form.kind = FA2_FORM_WINDOW_GQA;
     p.causal = 0;  // the band carries the mask: (N - 1, N - 1) plain, (N - 1, 0) causal
-    p.wl = l;
-    p.wr = r;
-    if (variant == FA2_VARIANT_AUTO) variant = pick_window_variant(p);
-    switch (variant) {
-    case FA2_VARIANT_GENERIC: return fa2_launch_generic_window_gqa(p, g);
-    case FA2_VARIANT_MFMA16D: return fa2_launch_mfma16d_window_gqa(p, 8, g);
-    case FA2_VARIANT_MFMA16D_W4: return fa2_launch_mfma16d_window_gqa(p, 4, g);
-    default:
-        fa2_set_error("kernel variant %d has no GQA form for this layout (generic, mfma16d and mfma16d_w4 do; a layout with batch "
-                      "strides H x the head strides takes every variant)", variant);
-        return FA2_ERR_UNSUPPORTED;
-    }
+    p.wl = w.wl;
+    p.wr = w.wr;
+    return FA2_OK;
+}
+
+int fwd(const FwdCall &c) {
+    Fa2Problem p;
+    Fa2Form form;
+    const int rc = check_fwd(c, p, form);
+    return rc != FA2_OK ? rc : run_fwd(p, form, c.variant);
+}
+
+// What every entry point fills alike (a packed one: 3-element strides, no l_strides, no N); the rest each adds its own.
+FwdCall dense_call(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t *qs, const int64_t *ks, const int64_t *vs,
+                   const int64_t *os, const int64_t *ls, int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+                   float scale, void *hip_stream, int32_t variant) {
+    FwdCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.q_strides = qs; c.k_strides = ks; c.v_strides = vs; c.o_strides = os; c.l_strides = ls;
+    c.B = B; c.H = H; c.N = N; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale; c.hip_stream = hip_stream;
+    c.variant = variant;
+    return c;
 }
 }  // namespace
 
+// Every entry point fills a call and hands it to fwd(); X is X_variant with FA2_VARIANT_AUTO.
 extern "C" {
+
+int fa2_fwd(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+            const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+            const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+            int32_t causal, float scale, void *hip_stream) {
+    return fa2_fwd_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
+                           hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                    const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                    const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+                    int32_t causal, float scale, void *hip_stream, int32_t variant) {
+    return fwd(dense_call(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
+                          hip_stream, variant));
+}
+
+int fa2_fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                   const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
+                   int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
+                   int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fa2_fwd_window_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal,
+                                  scale, window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_window_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                           const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                           int32_t variant) {
+    FwdCall c = dense_call(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
+                           hip_stream, variant);
+    c.window_left = window_left; c.window_right = window_right;
+    return fwd(c);
+}
 
 int fa2_fwd_gqa(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4], const int64_t k_strides[4],
                 const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2], int32_t B, int32_t H,
                 int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                 int32_t window_right, void *hip_stream) {
-    return fwd_gqa(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, H_kv, N, d, dtype_enum, causal, scale,
-                   window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
+    return fa2_fwd_gqa_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, H_kv, N, d, dtype_enum, causal,
+                               scale, window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
 }
 
 int fa2_fwd_gqa_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
@@ -574,8 +575,33 @@ int fa2_fwd_gqa_variant(const void *Q, const void *K, const void *V, void *O, vo
                         const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum,
                         int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
                         int32_t variant) {
-    return fwd_gqa(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, H_kv, N, d, dtype_enum, causal, scale,
-                   window_left, window_right, hip_stream, variant);
+    FwdCall c = dense_call(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
+                           hip_stream, variant);
+    c.window_left = window_left; c.window_right = window_right;
+    c.gqa = true; c.H_kv = H_kv;
+    return fwd(c);
+}
+
+int fa2_fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                   const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride,
+                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
+                   int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fa2_fwd_varlen_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B,
+                                  H, d, max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left,
+                                  window_right, hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_varlen_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                           const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                           int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                           int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                           void *hip_stream, int32_t variant) {
+    FwdCall c = dense_call(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale,
+                           hip_stream, variant);
+    fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
+    return fwd(c);
 }
 
 int fa2_fwd_varlen_gqa(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
@@ -594,67 +620,11 @@ int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void
                                int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
                                int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                                int32_t window_right, void *hip_stream, int32_t variant) {
-    const int rc = fa2_check_gqa(H, H_kv);
-    if (rc != FA2_OK) return rc;
-    return fwd_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d,
-                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
-                      variant, H >= 1 ? H / H_kv : 1);
-}
-
-int fa2_fwd_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
-                   const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride,
-                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
-                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
-                   int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
-    return fwd_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d,
-                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
-                      FA2_VARIANT_AUTO);
-}
-
-int fa2_fwd_varlen_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
-                           const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
-                           int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
-                           int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
-                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
-                           void *hip_stream, int32_t variant) {
-    return fwd_varlen(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d,
-                      max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
-                      variant);
-}
-
-int fa2_fwd(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
-            const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
-            const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
-            int32_t causal, float scale, void *hip_stream) {
-    const Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N,
-                                      d, dtype_enum, causal, scale, hip_stream);
-    return run(p, FA2_VARIANT_AUTO);
-}
-
-int fa2_fwd_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
-                    const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
-                    const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
-                    int32_t causal, float scale, void *hip_stream, int32_t variant) {
-    const Fa2Problem p = make_problem(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N,
-                                      d, dtype_enum, causal, scale, hip_stream);
-    return run(p, variant);
-}
-
-int fa2_fwd_window(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
-                   const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4], const int64_t l_strides[2],
-                   int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, float scale,
-                   int32_t window_left, int32_t window_right, void *hip_stream) {
-    return fwd_window(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
-                      window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
-}
-
-int fa2_fwd_window_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
-                           const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
-                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
-                           int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
-                           int32_t variant) {
-    return fwd_window(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_strides, B, H, N, d, dtype_enum, causal, scale,
-                      window_left, window_right, hip_stream, variant);
+    FwdCall c = dense_call(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale,
+                           hip_stream, variant);
+    fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
+    c.gqa = true; c.H_kv = H_kv;
+    return fwd(c);
 }
 
 int fa2_query_tile(int32_t N, int32_t d, int32_t dtype_enum, int32_t causal, int32_t out4[4]) {
@@ -671,54 +641,15 @@ int fa2_query_tile_scaled(int32_t B, int32_t H, int32_t N, int32_t d, int32_t dt
         fa2_set_error("out4 is null");
         return FA2_ERR_BAD_ARG;
     }
-    // A contiguous (B, H, N, d) problem with aligned dummy pointers: only the table is consulted.
+    // A contiguous (B, H, N, d) call with aligned dummy pointers: only the checks and the table are consulted.
+    const int64_t st[4] = {(int64_t)H * N * d, (int64_t)N * d, d, 1}, ls[2] = {(int64_t)H * N, N};
+    void *const ptr = (void *)0x1000;
     Fa2Problem p;
-    memset(&p, 0, sizeof(p));
-    p.Q = p.K = p.V = (const void *)0x1000;
-    p.O = p.L = (void *)0x1000;
-    p.B = B; p.H = H; p.N = N; p.d = d; p.dtype = dtype_enum; p.causal = causal ? 1 : 0; p.scale = scale;
-    const int64_t s[4] = {(int64_t)H * N * d, (int64_t)N * d, d, 1};
-    for (int k = 0; k < 4; ++k) p.qs[k] = p.ks[k] = p.vs[k] = p.os[k] = s[k];
-    p.ls[0] = (int64_t)H * N; p.ls[1] = N;
-    const int rc = validate(p);
+    Fa2Form form;
+    const int rc = check_fwd(dense_call(ptr, ptr, ptr, ptr, ptr, st, st, st, st, ls, B, H, N, d, dtype_enum, causal, scale, nullptr, 0), p, form);
     if (rc != FA2_OK) return rc;
-    const int v = pick_variant(p);
-    out4[0] = v;
-    switch (v) {
-    case FA2_VARIANT_MFMA16: out4[1] = 128; out4[2] = 64; out4[3] = 4; break;
-    case FA2_VARIANT_MFMA16_W8: out4[1] = 256; out4[2] = 64; out4[3] = 8; break;
-#ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA16P: out4[1] = 128; out4[2] = 32; out4[3] = 4; break;
-    case FA2_VARIANT_MFMA16P_W8: out4[1] = 256; out4[2] = 32; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA16X: out4[1] = 256; out4[2] = 32; out4[3] = 4; break;
-#endif
-    case FA2_VARIANT_A64: out4[1] = 256; out4[2] = 64; out4[3] = 4; break;
-    case FA2_VARIANT_A16: out4[1] = 256; out4[2] = 64; out4[3] = 4; break;
-    case FA2_VARIANT_A8: out4[1] = 256; out4[2] = 64; out4[3] = 4; break;
-    case FA2_VARIANT_A64D: out4[1] = 256; out4[2] = 64; out4[3] = 4; break;
-#ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA8: out4[1] = 256; out4[2] = 32; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA8_W4: out4[1] = 128; out4[2] = 32; out4[3] = 4; break;
-#endif
-    case FA2_VARIANT_MFMA8X: out4[1] = 256; out4[2] = 64; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA8X_W4: out4[1] = 128; out4[2] = 64; out4[3] = 4; break;
-#ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA8U: out4[1] = 128; out4[2] = 64; out4[3] = 4; break;
-#endif
-    case FA2_VARIANT_MFMA16K: out4[1] = 128; out4[2] = 64; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA16K_R2K2: out4[1] = 64; out4[2] = 64; out4[3] = 4; break;
-    case FA2_VARIANT_MFMA16K_R2K4: out4[1] = 64; out4[2] = 64; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA16D: out4[1] = 256; out4[2] = 32; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA16D_W4: out4[1] = 128; out4[2] = 32; out4[3] = 4; break;
-    case FA2_VARIANT_MFMA16H: out4[1] = 256; out4[2] = 32; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA16H_W4: out4[1] = 128; out4[2] = 32; out4[3] = 4; break;
-#ifdef FA2_EXPERIMENTS
-    case FA2_VARIANT_MFMA16S: out4[1] = 256; out4[2] = 32; out4[3] = 8; break;
-    case FA2_VARIANT_MFMA16S_W4: out4[1] = 128; out4[2] = 32; out4[3] = 4; break;
-#endif
-    case FA2_VARIANT_MFMA32: out4[1] = 128; out4[2] = 32; out4[3] = 4; break;
-    default: out4[1] = 16; out4[2] = 64; out4[3] = 4; break;
-    }
+    const DenseRow &row = *dense_row(pick_variant(p));  // (every id pick_variant returns has a row)
+    out4[0] = row.id; out4[1] = row.B_r; out4[2] = row.B_c; out4[3] = row.waves;
     return FA2_OK;
 }
 

@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "fa2_bwd_common.h"
+#include "fa2_host.h"
 
 namespace {
 
@@ -44,198 +45,196 @@ int validate(const Fa2BwdProblem &p) {
     return FA2_OK;
 }
 
-int run(const Fa2BwdProblem &p, int variant) {
-    const int rc = validate(p);
-    if (rc != FA2_OK) return rc;
+// The table of the five forms (FA2_FORM_DENSE .. FA2_FORM_VARLEN_GQA): each takes GENERIC and MFMA16 -- AUTO: MFMA16 (f16 / bf16 at
+// d = 64 / 128) where it runs, else the VALU kernel -- and refuses any other id with its own sentence.  The dense form alone also
+// has MFMA32, and what it refuses is FA2_ERR_BAD_ARG.  (fa2_bwd_mfma16_supports judges the 32-bit offsets of a packed problem on
+// N = the longer max_seqlen: they span one sequence.)
+using P = const Fa2BwdProblem &;
+struct FormRow {
+    int (*generic)(P, int g);
+    int (*mfma16)(P, int g);
+    const char *other;
+};
+const FormRow kForms[5] = {
+    {[](P p, int) { return fa2_bwd_launch_generic(p); }, [](P p, int) { return fa2_bwd_launch_mfma16(p); },
+     "unknown backward kernel variant %d"},
+    {[](P p, int) { return fa2_bwd_launch_generic_window(p); }, [](P p, int) { return fa2_bwd_launch_mfma16_window(p); },
+     "backward kernel variant %d does not take a window (generic and mfma16 do)"},
+    {[](P p, int) { return fa2_bwd_launch_generic_varlen(p); }, [](P p, int) { return fa2_bwd_launch_mfma16_varlen(p); },
+     "backward kernel variant %d has no varlen form (generic and mfma16 do)"},
+    {fa2_bwd_launch_generic_window_gqa, fa2_bwd_launch_mfma16_window_gqa, "backward kernel variant %d has no GQA form (generic and mfma16 do)"},
+    {fa2_bwd_launch_generic_varlen_gqa, fa2_bwd_launch_mfma16_varlen_gqa,
+     "backward kernel variant %d has no varlen GQA form (generic and mfma16 do)"},
+};
+
+// Step 3: the launch of a checked problem in its form.
+int run_bwd(const Fa2BwdProblem &p, Fa2Form form, int variant) {
+    const bool dense = form.kind == FA2_FORM_DENSE;
     if (variant == FA2_BWD_VARIANT_AUTO)
-        variant = fa2_bwd_mfma16_supports(p)   ? FA2_BWD_VARIANT_MFMA16
-                  : fa2_bwd_mfma32_supports(p) ? FA2_BWD_VARIANT_MFMA32
-                                               : FA2_BWD_VARIANT_GENERIC;
-    switch (variant) {
-    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic(p);
-    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16(p);
-    case FA2_BWD_VARIANT_MFMA32: return fa2_bwd_launch_mfma32(p);
-    default: fa2_set_error("unknown backward kernel variant %d", variant); return FA2_ERR_BAD_ARG;
-    }
+        variant = fa2_bwd_mfma16_supports(p)            ? FA2_BWD_VARIANT_MFMA16
+                  : dense && fa2_bwd_mfma32_supports(p) ? FA2_BWD_VARIANT_MFMA32
+                                                        : FA2_BWD_VARIANT_GENERIC;
+    const FormRow &row = kForms[form.kind];
+    if (variant == FA2_BWD_VARIANT_GENERIC) return row.generic(p, form.g);
+    if (variant == FA2_BWD_VARIANT_MFMA16) return row.mfma16(p, form.g);
+    if (variant == FA2_BWD_VARIANT_MFMA32 && dense) return fa2_bwd_launch_mfma32(p);
+    fa2_set_error(row.other, variant);
+    return dense ? FA2_ERR_BAD_ARG : FA2_ERR_UNSUPPORTED;
 }
 
-// Windowed backward (fa2_bwd_window): the MFMA kernel for f16 / bf16 at d = 64 / 128, the VALU kernel for the rest.
-int run_window(const Fa2BwdProblem &p, int variant) {
-    const int rc = validate(p);
-    if (rc != FA2_OK) return rc;
-    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
-    switch (variant) {
-    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_window(p);
-    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_window(p);
-    default:
-        fa2_set_error("backward kernel variant %d does not take a window (generic and mfma16 do)", variant);
-        return FA2_ERR_UNSUPPORTED;
-    }
-}
+// Step 1: the raw arguments of any of the ten backward entry points, as FwdCall (fa2_api.hip) holds the forward's.  `strides`: of
+// Q, K, V, O, dO, dQ, dK, dV in that order, 4 elements each, 3 in a packed call.
+struct BwdCall {
+    const void *Q, *K, *V, *O, *dO, *L;
+    void *dQ, *dK, *dV, *D;
+    const int64_t *strides[8], *l_strides;
+    int32_t B, H, N, d, dtype_enum, causal;
+    float scale;
+    void *hip_stream;
+    int32_t variant;
+    int32_t window_left = -1, window_right = -1;
+    bool gqa = false;  // fa2_bwd_gqa, fa2_bwd_varlen_gqa: K, V, dK, dV have H_kv heads
+    int32_t H_kv = 0;
+    bool packed = false;  // fa2_bwd_varlen, fa2_bwd_varlen_gqa
+    const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k = nullptr;
+    int32_t max_seqlen_q = 0, max_seqlen_k = 0, total_q = 0, total_k = 0;
+    int64_t l_head_stride = 0;
+};
 
-Fa2BwdProblem make(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
-                   void *dK, void *dV, void *D, const int64_t *qs, const int64_t *ks, const int64_t *vs,
-                   const int64_t *os, const int64_t *dos, const int64_t *dqs, const int64_t *dks, const int64_t *dvs,
-                   const int64_t *ls, int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype, int32_t causal,
-                   float scale, void *stream) {
-    Fa2BwdProblem p;
+// Step 2: check_fwd's order (tests/golden/train_host_calls.json), with the packed call's own: its stride pointers, sizes and L's
+// head stride before its tensors.  Grouped-query attention (H_kv < H) always runs the GQA forms -- a dense problem without a window
+// as the full band: the same sweep, the same masks -- which sum dK / dV of each KV head over its g query heads inside one workgroup.
+int check_bwd(const BwdCall &c, Fa2BwdProblem &p, Fa2Form &form) {
+    form = {FA2_FORM_DENSE, 1};
+    if (c.gqa) {
+        const int rc = fa2_check_gqa(c.H, c.H_kv);
+        if (rc != FA2_OK) return rc;
+        if (c.H >= 1) form.g = c.H / c.H_kv;
+    }
     memset(&p, 0, sizeof(p));
-    p.Q = Q; p.K = K; p.V = V; p.O = O; p.dO = dO; p.L = L;
-    p.dQ = dQ; p.dK = dK; p.dV = dV; p.D = D;
-    if (qs && ks && vs && os && dos && dqs && dks && dvs && ls) {
-        for (int k = 0; k < 4; ++k) {
-            p.qs[k] = qs[k]; p.ks[k] = ks[k]; p.vs[k] = vs[k]; p.os[k] = os[k]; p.dos[k] = dos[k];
-            p.dqs[k] = dqs[k]; p.dks[k] = dks[k]; p.dvs[k] = dvs[k];
+    p.Q = c.Q; p.K = c.K; p.V = c.V; p.O = c.O; p.dO = c.dO; p.L = c.L;
+    p.dQ = c.dQ; p.dK = c.dK; p.dV = c.dV; p.D = c.D;
+    p.B = c.B; p.H = c.H; p.d = c.d; p.dtype = c.dtype_enum; p.causal = c.causal ? 1 : 0; p.scale = c.scale;
+    p.stream = (hipStream_t)c.hip_stream;
+    int64_t *const strides[8] = {p.qs, p.ks, p.vs, p.os, p.dos, p.dqs, p.dks, p.dvs};
+    if (c.packed) {
+        const char *snames[8] = {"q_strides", "k_strides", "v_strides", "o_strides", "do_strides", "dq_strides", "dk_strides", "dv_strides"};
+        int rc = fa2_check_nonnull("varlen backward", (const void *const *)c.strides, snames, 8);
+        if (rc == FA2_OK) rc = fa2_check_packed("varlen backward", c, false);
+        if (rc != FA2_OK) return rc;
+        if (c.l_head_stride < 0) {
+            fa2_set_error("varlen backward: negative L head stride");
+            return FA2_ERR_BAD_ARG;
         }
-        p.ls[0] = ls[0]; p.ls[1] = ls[1];
+        const void *ptrs[10] = {c.Q, c.K, c.V, c.O, c.dO, c.L, c.dQ, c.dK, c.dV, c.D};
+        const char *names[10] = {"Q", "K", "V", "O", "dO", "L", "dQ", "dK", "dV", "D"};
+        rc = fa2_check_nonnull("varlen backward", ptrs, names, 10);
+        if (rc != FA2_OK) return rc;
+        for (int t = 0; t < 8; ++t) fa2_packed_strides4(c.strides[t], strides[t]);
+        fa2_set_packed(c, p);
+        form.kind = form.g > 1 ? FA2_FORM_VARLEN_GQA : FA2_FORM_VARLEN;
+        return validate(p);
+    }
+    Fa2Window w;
+    int rc = fa2_window_of(c.N, c.causal, c.window_left, c.window_right, w);
+    if (rc != FA2_OK) return rc;
+    bool all = c.l_strides;
+    for (int t = 0; t < 8; ++t) all = all && c.strides[t];
+    if (all) {
+        for (int t = 0; t < 8; ++t)
+            for (int k = 0; k < 4; ++k) strides[t][k] = c.strides[t][k];
+        p.ls[0] = c.l_strides[0]; p.ls[1] = c.l_strides[1];
     } else {
         p.Q = nullptr;  // fails validate()
     }
-    p.B = B; p.H = H; p.N = N; p.d = d; p.dtype = dtype; p.causal = causal ? 1 : 0; p.scale = scale;
-    p.stream = (hipStream_t)stream;
-    return p;
-}
-
-int bwd_window(Fa2BwdProblem p, int32_t wl, int32_t wr, int variant) {
-    int32_t c = p.causal, l = 0, r = 0, windowed = 0;
-    if (p.N >= 1) {  // (N < 1 is reported by validate())
-        const int rc = fa2_window_normalise(p.N, p.causal, wl, wr, &c, &l, &r, &windowed);
-        if (rc != FA2_OK) return rc;
-    } else if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
-    }
-    p.causal = c;
-    if (!windowed) return run(p, variant);  // the window removes nothing beyond plain / causal attention: the same path
-    p.causal = 0;
-    p.wl = l;
-    p.wr = r;
-    return run_window(p, variant);
-}
-
-// Variable-length (packed) backward, fa2_bwd_varlen: arguments checked before any launch.
-int bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ, void *dK, void *dV,
-               void *D, const int64_t *const st3[8], int64_t l_head_stride, const int32_t *cu_q, const int32_t *cu_k, int32_t B,
-               int32_t H, int32_t d, int32_t max_q, int32_t max_k, int32_t total_q, int32_t total_k, int32_t dtype, int32_t causal,
-               float scale, int32_t wl, int32_t wr, void *stream, int variant, int gqa = 1) {
-    const char *snames[8] = {"q_strides", "k_strides", "v_strides", "o_strides", "do_strides", "dq_strides", "dk_strides", "dv_strides"};
-    for (int t = 0; t < 8; ++t)
-        if (!st3[t]) {
-            fa2_set_error("varlen backward: null %s", snames[t]);
-            return FA2_ERR_BAD_ARG;
-        }
-    if (!cu_q || !cu_k) {
-        fa2_set_error("varlen backward: null %s", !cu_q ? "cu_seqlens_q" : "cu_seqlens_k");
-        return FA2_ERR_BAD_ARG;
-    }
-    if (B < 1 || B > 65535) {
-        fa2_set_error("varlen backward: B (number of sequences) must be in [1, 65535] (got %d)", B);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (H > 65535) {
-        fa2_set_error("varlen backward: H must be <= 65535 (got %d)", H);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (max_q < 0 || max_k < 0 || max_q > (1 << 28) || max_k > (1 << 28)) {
-        fa2_set_error("varlen backward: max_seqlen_q and max_seqlen_k must be in [0, 2^28] (got %d, %d)", max_q, max_k);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (total_q < 0 || total_k < 0) {
-        fa2_set_error("varlen backward: total_q and total_k must be >= 0 (got %d, %d)", total_q, total_k);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
-    }
-    if (l_head_stride < 0) {
-        fa2_set_error("varlen backward: negative L head stride");
-        return FA2_ERR_BAD_ARG;
-    }
-    const void *ptrs[10] = {Q, K, V, O, dO, L, dQ, dK, dV, D};
-    const char *names[10] = {"Q", "K", "V", "O", "dO", "L", "dQ", "dK", "dV", "D"};
-    for (int t = 0; t < 10; ++t)
-        if (!ptrs[t]) {
-            fa2_set_error("varlen backward: null %s", names[t]);
-            return FA2_ERR_BAD_ARG;
-        }
-    int64_t s4[8][4];
-    for (int t = 0; t < 8; ++t) {
-        s4[t][0] = 0; s4[t][1] = st3[t][1]; s4[t][2] = st3[t][0]; s4[t][3] = st3[t][2];
-    }
-    const int64_t ls2[2] = {0, l_head_stride};
-    const int32_t nmax = max_q > max_k ? max_q : max_k;
-    Fa2BwdProblem p = make(Q, K, V, O, dO, L, dQ, dK, dV, D, s4[0], s4[1], s4[2], s4[3], s4[4], s4[5], s4[6], s4[7], ls2, B, H,
-                           nmax > 0 ? nmax : 1, d, dtype, causal, scale, stream);
-    const int rc = validate(p);
-    if (rc != FA2_OK) return rc;
-    p.wl = wl;
-    p.wr = wr;
-    p.cu_q = cu_q; p.cu_k = cu_k;
-    p.max_q = max_q; p.max_k = max_k; p.total_q = total_q; p.total_k = total_k;
-    // (fa2_bwd_mfma16_supports judges the 32-bit offsets on N = the longer max_seqlen: they span one sequence)
-    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
-    if (gqa > 1) {  // grouped-query: K, V, dK, dV carry H / gqa heads
-        switch (variant) {
-        case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_varlen_gqa(p, gqa);
-        case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_varlen_gqa(p, gqa);
-        default:
-            fa2_set_error("backward kernel variant %d has no varlen GQA form (generic and mfma16 do)", variant);
-            return FA2_ERR_UNSUPPORTED;
-        }
-    }
-    switch (variant) {
-    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_varlen(p);
-    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_varlen(p);
-    default:
-        fa2_set_error("backward kernel variant %d has no varlen form (generic and mfma16 do)", variant);
-        return FA2_ERR_UNSUPPORTED;
-    }
-}
-
-// Grouped-query backward, dense layout (fa2_bwd_gqa).  H_kv == H is fa2_bwd_window itself.  Otherwise the windowed GQA forms, with a
-// plain or causal problem as the full band (its arithmetic is the plain kernels': the same sweep, the same masks), sum dK / dV of
-// each KV head over its g query heads inside one workgroup.
-int bwd_gqa(Fa2BwdProblem p, int32_t H_kv, int32_t wl, int32_t wr, int variant) {
-    int rc = fa2_check_gqa(p.H, H_kv);
-    if (rc != FA2_OK) return rc;
-    if (H_kv == p.H) return bwd_window(p, wl, wr, variant);
-    int32_t c = p.causal, l = 0, r = 0, windowed = 0;
-    if (p.N >= 1) {  // (N < 1 is reported by validate())
-        rc = fa2_window_normalise(p.N, p.causal, wl, wr, &c, &l, &r, &windowed);
-        if (rc != FA2_OK) return rc;
-    } else if (wl < -1 || wr < -1) {
-        fa2_set_error("window sides must be >= -1 (-1 = unbounded), got window=(%d, %d)", wl, wr);
-        return FA2_ERR_BAD_ARG;
-    }
+    p.N = c.N;
+    p.causal = w.causal;
     rc = validate(p);
     if (rc != FA2_OK) return rc;
-    p.causal = 0;  // the band carries the mask: (N - 1, N - 1) plain, (N - 1, 0) causal
-    p.wl = l;
-    p.wr = r;
-    const int g = p.H / H_kv;
-    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16_supports(p) ? FA2_BWD_VARIANT_MFMA16 : FA2_BWD_VARIANT_GENERIC;
-    switch (variant) {
-    case FA2_BWD_VARIANT_GENERIC: return fa2_bwd_launch_generic_window_gqa(p, g);
-    case FA2_BWD_VARIANT_MFMA16: return fa2_bwd_launch_mfma16_window_gqa(p, g);
-    default:
-        fa2_set_error("backward kernel variant %d has no GQA form (generic and mfma16 do)", variant);
-        return FA2_ERR_UNSUPPORTED;
+    if (w.windowed || form.g > 1) {  // the band carries the mask; a GQA call's always: (N - 1, N - 1) plain, (N - 1, 0) causal
+        form.kind = form.g > 1 ? FA2_FORM_WINDOW_GQA : FA2_FORM_WINDOW;
+        p.causal = 0;
+        p.wl = w.wl;
+        p.wr = w.wr;
     }
+    return FA2_OK;
+}
+
+int bwd(const BwdCall &c) {
+    Fa2BwdProblem p;
+    Fa2Form form;
+    const int rc = check_bwd(c, p, form);
+    return rc != FA2_OK ? rc : run_bwd(p, form, c.variant);
+}
+
+// What every entry point fills alike (a packed one: 3-element strides, no l_strides, no N); the rest each adds its own.
+BwdCall dense_call(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ, void *dK, void *dV,
+                   void *D, const int64_t *qs, const int64_t *ks, const int64_t *vs, const int64_t *os, const int64_t *dos,
+                   const int64_t *dqs, const int64_t *dks, const int64_t *dvs, const int64_t *ls, int32_t B, int32_t H, int32_t N,
+                   int32_t d, int32_t dtype_enum, int32_t causal, float scale, void *hip_stream, int32_t variant) {
+    BwdCall c = {Q, K, V, O, dO, L, dQ, dK, dV, D, {qs, ks, vs, os, dos, dqs, dks, dvs}, ls};
+    c.B = B; c.H = H; c.N = N; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale; c.hip_stream = hip_stream;
+    c.variant = variant;
+    return c;
 }
 
 }  // namespace
 
+// Every entry point fills a call and hands it to bwd(); X is X_variant with FA2_BWD_VARIANT_AUTO.
 extern "C" {
+
+int fa2_bwd(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+            void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+            const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+            const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+            const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+            float scale, void *hip_stream) {
+    return fa2_bwd_variant(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream, FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                    void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+                    const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+                    const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+                    const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+                    int32_t causal, float scale, void *hip_stream, int32_t variant) {
+    return bwd(dense_call(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                          dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream, variant));
+}
+
+int fa2_bwd_window(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                   void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+                   const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+                   const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+                   const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
+                   float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fa2_bwd_window_variant(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                                  dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, window_left, window_right,
+                                  hip_stream, FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_window_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                           void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
+                           const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
+                           const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
+                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
+                           int32_t variant) {
+    BwdCall c = dense_call(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream, variant);
+    c.window_left = window_left; c.window_right = window_right;
+    return bwd(c);
+}
 
 int fa2_bwd_gqa(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ, void *dK,
                 void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
                 const int64_t o_strides[4], const int64_t do_strides[4], const int64_t dq_strides[4], const int64_t dk_strides[4],
                 const int64_t dv_strides[4], const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d,
                 int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
-    return bwd_gqa(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
-                        dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
-                   H_kv, window_left, window_right, FA2_BWD_VARIANT_AUTO);
+    return fa2_bwd_gqa_variant(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                               dk_strides, dv_strides, l_strides, B, H, H_kv, N, d, dtype_enum, causal, scale, window_left,
+                               window_right, hip_stream, FA2_BWD_VARIANT_AUTO);
 }
 
 int fa2_bwd_gqa_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
@@ -245,9 +244,38 @@ int fa2_bwd_gqa_variant(const void *Q, const void *K, const void *V, const void 
                         const int64_t l_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N, int32_t d, int32_t dtype_enum,
                         int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
                         int32_t variant) {
-    return bwd_gqa(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
-                        dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
-                   H_kv, window_left, window_right, variant);
+    BwdCall c = dense_call(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream, variant);
+    c.window_left = window_left; c.window_right = window_right;
+    c.gqa = true; c.H_kv = H_kv;
+    return bwd(c);
+}
+
+int fa2_bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                   void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                   const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
+                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
+                   int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fa2_bwd_varlen_variant(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                                  dk_strides, dv_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q, max_seqlen_k,
+                                  total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
+                                  FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_varlen_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                           void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                           const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                           const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                           int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                           int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                           void *hip_stream, int32_t variant) {
+    BwdCall c = dense_call(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale, hip_stream, variant);
+    fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
+    return bwd(c);
 }
 
 int fa2_bwd_varlen_gqa(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
@@ -272,83 +300,11 @@ int fa2_bwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, cons
                                int32_t H, int32_t H_kv, int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
                                int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                                int32_t window_right, void *hip_stream, int32_t variant) {
-    const int rc = fa2_check_gqa(H, H_kv);
-    if (rc != FA2_OK) return rc;
-    const int64_t *const st[8] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
-    return bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, st, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q,
-                      max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream, variant,
-                      H >= 1 ? H / H_kv : 1);
-}
-
-int fa2_bwd(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
-            void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
-            const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
-            const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
-            const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
-            float scale, void *hip_stream) {
-    return run(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
-                    dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
-               FA2_BWD_VARIANT_AUTO);
-}
-
-int fa2_bwd_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
-                    void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
-                    const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
-                    const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
-                    const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
-                    int32_t causal, float scale, void *hip_stream, int32_t variant) {
-    return run(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
-                    dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
-               variant);
-}
-
-int fa2_bwd_window(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
-                   void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
-                   const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
-                   const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
-                   const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum, int32_t causal,
-                   float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
-    return bwd_window(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
-                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
-                      window_left, window_right, FA2_BWD_VARIANT_AUTO);
-}
-
-int fa2_bwd_window_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
-                           void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[4], const int64_t k_strides[4],
-                           const int64_t v_strides[4], const int64_t o_strides[4], const int64_t do_strides[4],
-                           const int64_t dq_strides[4], const int64_t dk_strides[4], const int64_t dv_strides[4],
-                           const int64_t l_strides[2], int32_t B, int32_t H, int32_t N, int32_t d, int32_t dtype_enum,
-                           int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream,
-                           int32_t variant) {
-    return bwd_window(make(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
-                           dk_strides, dv_strides, l_strides, B, H, N, d, dtype_enum, causal, scale, hip_stream),
-                      window_left, window_right, variant);
-}
-
-int fa2_bwd_varlen(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
-                   void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
-                   const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
-                   const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
-                   const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t d,
-                   int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
-                   int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
-    const int64_t *const st[8] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
-    return bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, st, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q,
-                      max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream,
-                      FA2_BWD_VARIANT_AUTO);
-}
-
-int fa2_bwd_varlen_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
-                           void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
-                           const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
-                           const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
-                           int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
-                           int32_t d, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
-                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
-                           void *hip_stream, int32_t variant) {
-    const int64_t *const st[8] = {q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides, dv_strides};
-    return bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, st, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, d, max_seqlen_q,
-                      max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left, window_right, hip_stream, variant);
+    BwdCall c = dense_call(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale, hip_stream, variant);
+    fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
+    c.gqa = true; c.H_kv = H_kv;
+    return bwd(c);
 }
 
 }  // extern "C"
