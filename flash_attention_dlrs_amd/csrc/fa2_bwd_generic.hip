@@ -47,13 +47,6 @@
 
 namespace {
 
-template <typename A> __device__ __forceinline__ A exp2_a(A x);
-template <> __device__ __forceinline__ float exp2_a<float>(float x) { return exp2f(x); }
-template <> __device__ __forceinline__ double exp2_a<double>(double x) { return exp2(x); }
-template <typename A> __device__ __forceinline__ A log2_a(A x);
-template <> __device__ __forceinline__ float log2_a<float>(float x) { return log2f(x); }
-template <> __device__ __forceinline__ double log2_a<double>(double x) { return log2(x); }
-
 struct GArgs {
     const void *Q, *K, *V, *O, *dO, *L;
     void *dQ, *dK, *dV, *D;
@@ -277,7 +270,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
                 s += qrow[x] * krow[x];   // kernels.py:283
                 dp += grow[x] * vrow[x];  // :289
             }
-            A p = exp2_a<A>(s * c_s - Lq[r]);  // :285
+            A p = exp2_acc<A>(s * c_s - Lq[r]);  // :285
 #if defined(FA2_BWD_GENERIC_VARLEN)
             if (qi >= NQ || kj >= NK || kj < qi - wl || kj > qi + wr) p = 0;
 #elif defined(FA2_BWD_GENERIC_WINDOW)
@@ -328,7 +321,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         }
     }
     // L = +inf and rowsum 0 would give inf + -inf: such a row keeps +inf, and MODE 0 recomputes P = 0 for it
-    if (MODE == 1 && tid < TB && own_row0 + tid < NO) Lc[own_row0 + tid] = Rs[tid] > 0 ? Lq[tid] + log2_a<A>(Rs[tid]) : (A)INFINITY;
+    if (MODE == 1 && tid < TB && own_row0 + tid < NO) Lc[own_row0 + tid] = Rs[tid] > 0 ? Lq[tid] + log2_acc<A>(Rs[tid]) : (A)INFINITY;
 #else
     for (int e = tid; e < TB * d; e += 256) {
         const int o = e / d, x = e % d, row = own_row0 + o;
@@ -340,7 +333,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
             E::store(a.dQ, b * a.dqs[0] + h * a.dqs[1] + row * a.dqs[2] + x * a.dqs[3], acc0[o * ld + x] / Rs[o]);
         }
     }
-    if (MODE == 1 && tid < TB && own_row0 + tid < N) Lc[own_row0 + tid] = Lq[tid] + log2_a<A>(Rs[tid]);
+    if (MODE == 1 && tid < TB && own_row0 + tid < N) Lc[own_row0 + tid] = Lq[tid] + log2_acc<A>(Rs[tid]);
 #endif
 }
 

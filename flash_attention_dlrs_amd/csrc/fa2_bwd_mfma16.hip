@@ -27,6 +27,7 @@
 // of the second product is X's row index: cdna_hip_programming.md section 3), and one LDS image per tile serves
 // the row reads and the transposed reads (the XOR-swizzled image of fa2_mfma16.hip).
 #include "fa2_bwd_common.h"
+#include "fa2_mfma.h"
 
 // FA2_BWD_MFMA16_WINDOW (fa2_bwd_mfma16_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr; the
 // swept ranges, block skips and masks follow the two band edges -- under its own kernel names, compiled in a translation unit of
@@ -57,33 +58,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
-
-template <int V> struct IC { static constexpr int value = V; };
-
 #ifndef FA2_BWD_PIPE
 #define FA2_BWD_PIPE 0  // measured: 41-45 spills, 27 % slower (two more score tiles do not fit 256 registers)
 #endif
@@ -111,30 +85,6 @@ struct BArgs {
 #endif
     float c_log2e, scale;
 };
-
-// 16-byte-chunk swizzle of fa2_mfma16.hip: conflict-free ds_read_b128 row reads and ds_read_b64_tr_b16 reads
-template <int D> __device__ __forceinline__ int lds_off(int row, int ch) {
-    if constexpr (D == 128) return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
-    else return row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4);
-}
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-// One LDS-DMA piece (64 lanes x 16 bytes, lane-linear in LDS); inline asm and our own vmcnt wait, as in fa2_mfma16d.hip
-__device__ __forceinline__ void dma16(const i32x4 rsrc, unsigned lds_base, int voffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma4(const i32x4 rsrc, unsigned lds_base, int voffset) {  // 64 lanes x 4 bytes
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ---- D[b, h, n] = sum_x O * dO  (kernels.py:115-166): D/8 lanes per row, 16 bytes of each operand per lane
 template <typename T, int D> __global__ __launch_bounds__(256) void bwd_D_kernel(const BArgs a) {

@@ -14,13 +14,9 @@
 // keys and both gradients (128 accumulators; one wave per SIMD either way at d = 128 -- the owned rows alone are 128
 // registers in fp32), the workgroup sweeps the query rows.
 #include "fa2_bwd_common.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
 
 struct B32Args {
     const char *Q, *K, *V, *O, *dO, *L;
@@ -31,9 +27,6 @@ struct B32Args {
     int B, H, N, causal;
     float c_log2e, scale;
 };
-
-// 16-byte chunk `ch` of row `row` in a [32][D] fp32 tile (fa2_mfma32.hip)
-template <int D> __device__ __forceinline__ int lds_off32(int row, int ch) { return row * (D * 4) + ((ch ^ (row & 15)) << 4); }
 
 // D[b, h, n] = sum_x O * dO  (kernels.py:115-166): D/4 lanes per row, 16 bytes of each operand per lane
 template <int D> __global__ __launch_bounds__(256) void bwd32_D_kernel(const B32Args a) {

@@ -44,37 +44,13 @@
 // Rows at positions >= n_q(b) are computed and dropped: in the packed layout they would be the next sequence's.  With VQ false
 // q0 = 0, q1 = tq = N_q and every expression below is the fixed-N_q kernel's.
 #include "fa2_decode.h"
+#include "fa2_mfma.h"
 
 #ifndef FA2_DECODE_VARLEN_Q
 #define FA2_DECODE_VARLEN_Q 0
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 // (the cache element types other than T, CacheE4M3 / CacheE5M2, and their exact conversion CacheCvt: fa2_decode.h)
 
@@ -95,14 +71,6 @@ struct DecodeMfmaArgs {
     const int32_t *cu_q;  // VQ only: B + 1 offsets into the packed rows; qs[0] = os[0] = ls[0] = 0
     int total_q, max_q, tq, nqt;  // nqt = ceil(max_q / tq) query tiles per (split, KV head, sequence)
 };
-
-// Byte offset of 16-byte chunk `ch` of row `row` inside one [rows][D] 16-bit tile (the LDS tile is 16-bit for every cache
-// type): the swizzle of fa2_mfma16k.hip (a function
-// of row & 15 only), conflict-free for the row reads of K and the transposed reads of V.
-template <int D> __device__ __forceinline__ int lds_off(int row, int ch) {
-    if constexpr (D == 128) return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
-    else return row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4);
-}
 
 // RB = 32-row blocks of the query side, KG = key groups (RB * KG = 4 waves), BC = keys per tile (32 or 64).  C: the cache
 // element type, T or CacheE4M3 / CacheE5M2.  PAGED: K and V are a page pool behind a block table.  VQ: packed queries, tiled.

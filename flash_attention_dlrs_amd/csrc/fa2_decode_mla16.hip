@@ -7,7 +7,7 @@
 // than 64 rows computing its padding rows (the last row again) and dropping them.  A second row tile reads the same keys again.
 //
 // Per step the workgroup takes ONE 64-key tile of the latent cache, staged once: 64 rows of 1,152 B in an LDS image of 1,280-B
-// rows (a multiple of 256 B, so the swizzle of fa2_decode_mfma16.hip at d = 128 -- a function of row & 15 on the low four bits
+// rows (a multiple of 256 B, so the 16-bit tile swizzle (fa2_mfma.h) at d = 128 -- a function of row & 15 on the low four bits
 // of the 16-byte chunk index -- keeps the K row reads and the transposed V reads conflict-free; the 128 B of padding per row are
 // never read).  The score reads all 72 chunks of a row, the value side columns 0..511 of the SAME image through
 // ds_read_b64_tr_b16: the value operand is never fetched a second time.
@@ -46,33 +46,9 @@
 // otherwise every (split, row) writes the normalised fp32 partial (an empty split: 0 and -inf) for fa2_decode_combine.hip.
 // Vector stores only, no atomics, no hand-off between workgroups.
 #include "fa2_decode.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct DecodeMlaArgs {
     const char *Q, *K;
@@ -107,8 +83,8 @@ constexpr int kLPR8 = kD / 16;               // fp8 cache: 36 16-byte loads per 
 constexpr int kStage8 = kLPR8 * kBC / 256;   //            9 loads per thread and tile
 static_assert(kStage == 18 && kStage8 == 9 && kSmem <= 160 * 1024, "one workgroup per CU");
 
-// Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: fa2_decode_mfma16.hip's swizzle at d = 128.
-__device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4); }
+// Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: the d = 128 swizzle on rows of kRowB bytes.
+__device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ swz<128>(row)) << 4); }
 
 // T: Q, O, L and the matrix arithmetic; C: the cache (T, or an fp8 format converted while it is staged).
 template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {

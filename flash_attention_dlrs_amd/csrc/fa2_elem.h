@@ -1,11 +1,33 @@
-// Element types of the generic (VALU) kernels: load to / round in / store from the accumulate type.
-// Shared by the forward (fa2_generic.hip) and backward (fa2_bwd_generic.hip) catch-all kernels.
+// Element types of the generic (VALU) kernels: load to / round in / store from the accumulate type; exp2 / log2 in the
+// accumulate type and the wave-wide reductions.
+// Shared by the forward (fa2_generic.hip), backward (fa2_bwd_generic.hip) and decode catch-all kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 namespace {
+
+template <typename A> __device__ __forceinline__ A exp2_acc(A x);
+template <> __device__ __forceinline__ float exp2_acc<float>(float x) { return exp2f(x); }
+template <> __device__ __forceinline__ double exp2_acc<double>(double x) { return exp2(x); }
+template <typename A> __device__ __forceinline__ A log2_acc(A x);
+template <> __device__ __forceinline__ float log2_acc<float>(float x) { return log2f(x); }
+template <> __device__ __forceinline__ double log2_acc<double>(double x) { return log2(x); }
+
+template <typename A> __device__ __forceinline__ A wave_max(A v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const A t = __shfl_xor(v, o, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+template <typename A> __device__ __forceinline__ A wave_sum(A v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 __device__ __forceinline__ float round_fmt(float x, int mbits, int emin, float maxv, bool has_inf) {
     if (x == 0.0f || isnan(x)) return x;

@@ -45,27 +45,6 @@ constexpr int kWaves = 4;
 constexpr int kBr = kRowsPerWave * kWaves;  // 16 = the reference's smallest B_r
 constexpr int kBc = 64;                     // one key per lane
 
-template <typename A> __device__ __forceinline__ A exp2_acc(A x);
-template <> __device__ __forceinline__ float exp2_acc<float>(float x) { return exp2f(x); }
-template <> __device__ __forceinline__ double exp2_acc<double>(double x) { return exp2(x); }
-template <typename A> __device__ __forceinline__ A log2_acc(A x);
-template <> __device__ __forceinline__ float log2_acc<float>(float x) { return log2f(x); }
-template <> __device__ __forceinline__ double log2_acc<double>(double x) { return log2(x); }
-
-template <typename A> __device__ __forceinline__ A wave_max(A v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const A t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-template <typename A> __device__ __forceinline__ A wave_sum(A v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct GenericArgs {
     const void *Q, *K, *V;
     void *O, *L;

@@ -7,10 +7,11 @@
 // LDS-DMA writes lane-linearly (M0 base + lane * 16), so rows cannot be padded: the tile image is plain
 // 256-byte (d = 128) or 128-byte (d = 64) rows with the 16-byte chunks XOR-swizzled THROUGH THE SOURCE
 // ADDRESS (the lane that fills (row, slot) fetches global chunk slot ^ f(row)) and the same XOR on every read.
-// f is the involution of fa2_mfma16.hip's lds_off(): conflict-free for the ds_read_b128 row reads of K and for
+// f is the involution swz() of lds_off() (fa2_mfma.h): conflict-free for the ds_read_b128 row reads of K and for
 // the ds_read_b64_tr_b16 transposed reads of V.  Rows past N (and the "negative" rows of K unit 0) are
 // zero-filled by the buffer descriptor's range check.
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 // FA2_MFMA16D_WINDOW (fa2_mfma16d_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr, one tile per
 // workgroup, the key loop from the 64-key unit of the tile's first visible key, blocks outside a wave's band skipped, blocks across
@@ -34,30 +35,6 @@
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct DmaArgs {
     const char *Q, *K, *V;
@@ -83,47 +60,6 @@ struct DmaArgs {
     int gqa;  // query heads per KV head
 #endif
 };
-
-__device__ __forceinline__ void half_swap(float x, float &lo, float &hi) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned a = r[0], b = r[1];  // scalars first: bit_cast on a vector element reads element 0 (clang bug)
-    lo = __builtin_bit_cast(float, a);
-    hi = __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ float half_swap_max(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float half_swap_sum(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return lo + hi;
-}
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-// One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset) to LDS at lds_base + lane*16.
-// Inline asm ON PURPOSE: with the builtin, hipcc cannot tell the DMA's destination buffer from the buffer being
-// read and puts `s_waitcnt vmcnt(0)` in front of the first ds_read of the V tile -- the transfer then has a
-// quarter of an iteration to land instead of a whole one.  The compiler does not see these loads: the
-// `s_waitcnt vmcnt(0)` in front of the publishing barrier is ours (dma_wait()).  M0 is saved and restored.
-__device__ __forceinline__ void dma16(const i32x4 rsrc, unsigned lds_base, int voffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// chunk swizzle of a row inside a [64][D] 16-bit tile (function of row & 15 only)
-template <int D> __device__ __forceinline__ int swz(int row) {
-    if constexpr (D == 128) return ((row & 3) << 2) | ((row >> 2) & 3);
-    else return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
-}
-template <int D> __device__ __forceinline__ int lds_off(int row, int ch) { return row * (D * 2) + ((ch ^ swz<D>(row)) << 4); }
 
 template <typename T, int D, int NW, bool CAUSAL>
 __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaArgs a) {

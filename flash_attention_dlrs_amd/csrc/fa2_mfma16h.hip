@@ -7,6 +7,7 @@
 //       per-lane base register plus an immediate (no address arithmetic in the loop).
 // Arithmetic, layouts and the tail / causal-diagonal path are those of fa2_mfma16d.hip (variant "mfma16h").
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 #ifndef FA2_H_ENTRY
 #define FA2_H_ENTRY fa2_launch_mfma16h
@@ -25,39 +26,6 @@ extern "C" int fa2_debug_read_stamps(unsigned long long *host_out) {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
-
-template <int V> struct IC { static constexpr int value = V; };
-
 struct DmaArgs {
     const char *Q, *K, *V;
     char *O, *L;
@@ -68,47 +36,6 @@ struct DmaArgs {
     int group;
     int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
 };
-
-__device__ __forceinline__ void half_swap(float x, float &lo, float &hi) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned a = r[0], b = r[1];  // scalars first: bit_cast on a vector element reads element 0 (clang bug)
-    lo = __builtin_bit_cast(float, a);
-    hi = __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ float half_swap_max(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float half_swap_sum(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return lo + hi;
-}
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-// One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset) to LDS at lds_base + lane*16.
-// Inline asm ON PURPOSE: with the builtin, hipcc cannot tell the DMA's destination buffer from the buffer being
-// read and puts `s_waitcnt vmcnt(0)` in front of the first ds_read of the V tile -- the transfer then has a
-// quarter of an iteration to land instead of a whole one.  The compiler does not see these loads: the
-// `s_waitcnt vmcnt(0)` in front of the publishing barrier is ours (dma_wait()).  M0 is saved and restored.
-__device__ __forceinline__ void dma16(const i32x4 rsrc, unsigned lds_base, int voffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// chunk swizzle of a row inside a [64][D] 16-bit tile (function of row & 15 only)
-template <int D> __device__ __forceinline__ int swz(int row) {
-    if constexpr (D == 128) return ((row & 3) << 2) | ((row >> 2) & 3);
-    else return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
-}
-template <int D> __device__ __forceinline__ int lds_off(int row, int ch) { return row * (D * 2) + ((ch ^ swz<D>(row)) << 4); }
 
 // Raw-buffer stores for the epilogue: rows past N fall outside the descriptor and are dropped by the range check,
 // so every wave issues the SAME number of store instructions whatever N is -- the counted `s_waitcnt vmcnt(NST)`

@@ -8,33 +8,9 @@
 // partial softmaxes are merged exactly as two key tiles are (O = O0 2^(m0-m) + O1 2^(m1-m), same for l).  No global
 // workspace, no second launch.  Results differ from the four-wave kernels only by the association of the fp32 sums.
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct Mfma16kArgs {
     const char *Q, *K, *V;
@@ -44,17 +20,6 @@ struct Mfma16kArgs {
     int B, H, N;
     float c_log2e;  // scale * log2(e) > 0
 };
-
-// Byte offset of 16-byte chunk `ch` of row `row` inside one [64][D] 16-bit tile.
-// D = 128 (256-B rows): chunk ^= ((row&3)<<2 | (row>>2)&3).  A ds_read_b128 lane group reads 16 rows
-//   distinct mod 16 at one chunk -> 16 different 16-B slots of the 256-B bank row; a transposed read's
-//   half-wave touches rows 4n..4n+3 x one 64-B span -> the (row&3)<<2 term moves each row to its own span.
-// D = 64 (128-B rows, two rows per bank row): chunk ^= ((row>>1)&1)<<2 | (row>>2)&3, same argument with
-//   row&1 selecting the half of the bank row.
-template <int D> __device__ __forceinline__ int lds_off(int row, int ch) {
-    if constexpr (D == 128) return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
-    else return row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4);
-}
 
 // RB = 32-row blocks of the Q tile, KG = key groups: RB * KG waves.  (4, 2): 128-row tile, eight waves; (2, 2): 64-row tile,
 // four waves -- twice the workgroups; (2, 4): 64-row tile, eight waves, a quarter of the sequential depth (d = 64 only:

@@ -19,32 +19,9 @@
 // ds_read_b64_tr_b16 transposed reads of V (four consecutive rows land in four different 64-B spans
 // of the 256-B bank row), and every read offset is lane_base + immediate -- two address registers.
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct PipeArgs {
     const char *Q, *K, *V;
@@ -55,28 +32,6 @@ struct PipeArgs {
     float c_log2e;
     int group;  // causal launch order: (b,h) groups interleaved per XCD batch (1 = one group at a time)
 };
-
-// Exchange between the two 32-lane halves of the wave with v_permlane32_swap (VALU, no LDS trip):
-// r[0][l] = x[l & 31], r[1][l] = x[32 + (l & 31)].  NB: the elements are copied to scalars before the
-// bit cast -- __builtin_bit_cast applied directly to a vector ELEMENT (r[1]) reads element 0 with this
-// clang (ROCm 7.2), which silently turned the exchange into a no-op.
-__device__ __forceinline__ void half_swap(float x, float &lo, float &hi) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned a = r[0], b = r[1];
-    lo = __builtin_bit_cast(float, a);
-    hi = __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ float half_swap_max(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float half_swap_sum(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return lo + hi;
-}
 
 // OPT bit 0: operand prefetch -- the LDS reads of a phase's MFMA operands are issued one phase ahead
 // (K fragments of the next QK^T during P.V, V fragments of P.V at the start of QK^T).

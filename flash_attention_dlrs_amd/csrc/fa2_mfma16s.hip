@@ -16,33 +16,9 @@
 // LDS images: K rows swizzled by fK(row) = (row & 3) | ((row >> 3) & 3) << 2 (= the MFMA row m: conflict-free
 // ds_read_b128 of the 16x16x32 A operand), V rows by fV of fa2_mfma16d.hip (conflict-free transposed reads).
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct SArgs {
     const char *Q, *K, *V;
@@ -54,16 +30,6 @@ struct SArgs {
     int group;
     int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
 };
-
-// LDS-DMA piece (see fa2_mfma16d.hip: inline asm on purpose; the vmcnt wait is ours)
-__device__ __forceinline__ void dma16(const i32x4 rsrc, unsigned lds_base, int voffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // 16-byte-chunk swizzles of a 256-byte row (functions of row & 31 / row & 15)
 __device__ __forceinline__ int swzK(int row) { return (row & 3) | (((row >> 3) & 3) << 2); }
@@ -186,8 +152,8 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16s_kernel(const SArgs
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const u32x4 kf = *(LDS_PTR(u32x4))(lds + koff + k_off[T2][ks]);
-                s.t[T2][0] = M::mfma(__builtin_bit_cast(frag, kf), qf[0][ks], s.t[T2][0]);
-                s.t[T2][1] = M::mfma(__builtin_bit_cast(frag, kf), qf[1][ks], s.t[T2][1]);
+                s.t[T2][0] = M::mfma16(__builtin_bit_cast(frag, kf), qf[0][ks], s.t[T2][0]);
+                s.t[T2][1] = M::mfma16(__builtin_bit_cast(frag, kf), qf[1][ks], s.t[T2][1]);
             }
     };
     // row maximum over the four lanes (n, n + 16, n + 32, n + 48) that share a query: rescale branch only
@@ -269,8 +235,8 @@ __global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16s_kernel(const SArgs
             const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + voff + v_off[0][dt]));
             const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + voff + v_off[1][dt]));
             const s16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            o[dt][0] = M::mfma(__builtin_bit_cast(frag, vf), pf[0], o[dt][0]);
-            o[dt][1] = M::mfma(__builtin_bit_cast(frag, vf), pf[1], o[dt][1]);
+            o[dt][0] = M::mfma16(__builtin_bit_cast(frag, vf), pf[0], o[dt][0]);
+            o[dt][1] = M::mfma16(__builtin_bit_cast(frag, vf), pf[1], o[dt][1]);
         }
     };
     auto block_masked = [&](int j) { return (CAUSAL && (j * 32 + 31 > q0)) || (j * 32 + 32 > N); };

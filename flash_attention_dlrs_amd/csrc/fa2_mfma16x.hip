@@ -16,36 +16,13 @@
 //     phase 1:  S_next[qb] = K_blk(j+1) . Q[qb]^T   (16 MFMA)  ||  P_j[qb] = exp2(S_j[qb]*c - m[qb]), row sums, cvt
 //     phase 2:  O[qb]     += V_blk(j)^T . P_j[qb]^T (16 MFMA)  ||  row max of S_next[qb], rescale decision
 // K is staged in 64-row units offset by 32 rows against V (unit u = keys 64u-32 .. 64u+31), three K units and two
-// V tiles in LDS, filled by LDS-DMA (buffer_load ... lds, inline asm as in fa2_mfma16d.hip: source-side XOR swizzle of
+// V tiles in LDS, filled by LDS-DMA (buffer_load ... lds, dma16() as in fa2_mfma16d.hip: source-side XOR swizzle of
 // the 16-byte chunks, conflict-free row and transposed reads), one DMA piece per even step of the first half
 // iteration, one barrier per 64 keys.
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-    using frag = bf16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<_Float16> {
-    using frag = f16x8;
-    static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct XArgs {
     const char *Q, *K, *V;
@@ -56,40 +33,6 @@ struct XArgs {
     float c_log2e;
     int group;
 };
-
-// v_permlane32_swap exchange between the wave's two 32-lane halves (see fa2_mfma16p.hip for the
-// __builtin_bit_cast-on-a-vector-element pitfall that the scalar copies avoid).
-__device__ __forceinline__ void half_swap(float x, float &lo, float &hi) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned a = r[0], b = r[1];
-    lo = __builtin_bit_cast(float, a);
-    hi = __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ float half_swap_max(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float half_swap_sum(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return lo + hi;
-}
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-// one 1-KiB LDS-DMA piece (see fa2_mfma16d.hip: inline asm on purpose; our own vmcnt wait before the barrier)
-__device__ __forceinline__ void dma16(const i32x4 rsrc, unsigned lds_base, int voffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// 16-byte chunk swizzle of a 256-byte row (function of row & 15), fa2_mfma16.hip lds_off()
-__device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int lds_off(int row, int ch) { return row * 256 + ((ch ^ swz(row)) << 4); }
 
 // ABL (timing-only ablations, -DFA2_ABLATIONS builds): 1 = no exp/sum, 2 = no row max, 4 = no LDS operand reads in
 // the steady loop, 8 = no staging (global loads, LDS writes, barrier) in the steady loop.
@@ -165,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void fa2_fwd_mfma16x_kernel(const XArgs a) 
 #pragma unroll
     for (int pp = 0; pp < PPW; ++pp) {
         const int row = 4 * (wave + 4 * pp) + (lane >> 4), slot = lane & 15;
-        const int chunk = slot ^ swz(row);
+        const int chunk = slot ^ swz<D>(row);
         kvo[pp] = row * krs + chunk * 16;
         vvo[pp] = row * vrs + chunk * 16;
     }
@@ -192,7 +135,7 @@ __global__ __launch_bounds__(256, 1) void fa2_fwd_mfma16x_kernel(const XArgs a) 
 
     int k_off[KS];  // K row read: row (half*32 + i), chunk 2ks + h
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) k_off[ks] = lds_off(i, 2 * ks + h);
+    for (int ks = 0; ks < KS; ++ks) k_off[ks] = lds_off<D>(i, 2 * ks + h);
     int v_off[2][DB];  // V transposed read (fa2_mfma16.hip): u = keys +0..3 / +8..11 of the 16-key step
     {
         const int w = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
@@ -200,7 +143,7 @@ __global__ __launch_bounds__(256, 1) void fa2_fwd_mfma16x_kernel(const XArgs a) 
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int db = 0; db < DB; ++db)
-                v_off[u][db] = VBASE + lds_off(8 * u + 4 * h + qq, 4 * db + 2 * w + (pp >> 1)) + 8 * (pp & 1);
+                v_off[u][db] = VBASE + lds_off<D>(8 * u + 4 * h + qq, 4 * db + 2 * w + (pp >> 1)) + 8 * (pp & 1);
     }
 
     f32x16 o[QB][DB];

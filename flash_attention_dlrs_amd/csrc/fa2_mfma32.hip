@@ -16,13 +16,9 @@
 //     QK^T  k-step 4c+jj, lane half h  <->  d   = 8c + 4h + jj
 //     PV    k-step r,     lane half h  <->  key = (r&3) + 8(r>>2) + 4h   (= row of accumulator register r)
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
 
 struct Mfma32Args {
     const char *Q, *K, *V;
@@ -33,9 +29,6 @@ struct Mfma32Args {
     float c_log2e;
     int dbytes;  // row bytes of the head size the caller passed (<= 4 D): the DP kernels zero-fill the rest
 };
-
-// 16-byte chunk `ch` of row `row` in a [32][D] fp32 tile: chunk ^= row & 15 (low four chunk bits).
-template <int D> __device__ __forceinline__ int lds_off32(int row, int ch) { return row * (D * 4) + ((ch ^ (row & 15)) << 4); }
 
 // DP: the head size is a multiple of 4 below D (e.g. the reference's d = 40 and d = 8 padding
 // cases, torch.py:38-47): 16-byte chunks at or past a.dbytes are zero-filled on load and never stored -- no host padding.

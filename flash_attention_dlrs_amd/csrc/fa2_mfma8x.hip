@@ -26,6 +26,7 @@
 // the compiler's schedule, which clusters the MFMAs instead of spreading them through the exp2 stream -- it needs the
 // hand-ordered sub-steps of fa2_mfma16h.hip to pay.
 #include "fa2_common.h"
+#include "fa2_mfma.h"
 
 #ifndef FA2_8X_MSUM
 #define FA2_8X_MSUM 1  // row sums by a 16x16x128 MFMA against a 0/1 operand instead of v_add_f32
@@ -49,34 +50,6 @@ extern "C" int fa2_debug_read_stamps(unsigned long long *host_out) {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
-
-// E4M3 = true: OCP e4m3fn (v_mfma ... fp8_fp8, v_cvt_pk_fp8_f32); false: e5m2 (bf8).
-template <bool E4M3> struct F8 {
-    static __device__ __forceinline__ f32x16 mfma(i32x8 a, i32x8 b, f32x16 c) {
-        if constexpr (E4M3) return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 1, 1, 0, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mfma_sum(i32x8 a, i32x8 b, f32x4 c) {  // 16x16x128
-        if constexpr (E4M3) return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 1, 1, 0, 0, 0, 0);
-    }
-    static constexpr int kOnes = E4M3 ? 0x38383838 : 0x3c3c3c3c;  // four fp8 1.0
-    // two floats -> two fp8 (RTNE) into the low (hi = false) or high half of `old`
-    template <bool HI> static __device__ __forceinline__ int cvt_pk(float x, float y, int old) {
-        if constexpr (E4M3) return __builtin_amdgcn_cvt_pk_fp8_f32(x, y, old, HI);
-        else return __builtin_amdgcn_cvt_pk_bf8_f32(x, y, old, HI);
-    }
-};
-
 struct F8Args {
     const char *Q, *K, *V;
     char *O, *L;
@@ -87,41 +60,6 @@ struct F8Args {
     int group;
     float thr;  // deferral threshold of the running maximum, log2 units (launch_t)
 };
-
-__device__ __forceinline__ void half_swap(float x, float &lo, float &hi) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned a = r[0], b = r[1];  // scalars first: bit_cast on a vector element reads element 0 (clang bug)
-    lo = __builtin_bit_cast(float, a);
-    hi = __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ float half_swap_max(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float half_swap_sum(float x) {
-    float lo, hi;
-    half_swap(x, lo, hi);
-    return lo + hi;
-}
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
-// One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset) to LDS at lds_base + lane*16.
-// Inline asm ON PURPOSE: with the builtin, hipcc cannot tell the DMA's destination buffer from the buffer being
-// read and puts `s_waitcnt vmcnt(0)` in front of the first ds_read of the V tile -- the transfer then has a
-// quarter of an iteration to land instead of a whole one.  The compiler does not see these loads: the
-// `s_waitcnt vmcnt(0)` in front of the publishing barrier is ours (dma_wait()).  M0 is saved and restored.
-__device__ __forceinline__ void dma16(const i32x4 rsrc, unsigned lds_base, int voffset) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lds_base), "v"(voffset), "s"(rsrc)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // K image: 16-byte chunk c of row r at r*128 + ((c ^ g(r)) << 4); g is a bijection of (r >> 1) & 7 together with
 // r & 1 selecting the half of the 256-byte bank row: 16 rows distinct mod 16 -> 16 distinct slots (ds_read_b128).
@@ -262,7 +200,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void fa2_fwd_mfma8x_kernel(const F8Ar
                 kf[e] = (int)ka[e];
                 kf[4 + e] = (int)kb[e];
             }
-            s = M::mfma(kf, qf[st], s);
+            s = M::mfma64(kf, qf[st], s);
         }
     };
     // running max over one 64-key unit u (blocks 2u, 2u+1), decided BEFORE either block of P is rounded
@@ -358,7 +296,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void fa2_fwd_mfma8x_kernel(const F8Ar
                 va[2 * q] = vf[0];
                 va[2 * q + 1] = vf[1];
             }
-            o[db] = M::mfma(va, pf, o[db]);
+            o[db] = M::mfma64(va, pf, o[db]);
         }
     };
     auto unit_masked = [&](int u) __attribute__((always_inline)) { return (CAUSAL && (u * 64 + 63 > q0)) || (u * 64 + 64 > N); };

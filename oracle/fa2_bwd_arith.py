@@ -9,23 +9,23 @@ Everything is float64 except at the points where the kernel rounds; rnd() is RTN
 torch's conversion, and the identity for float32 / float64 I/O (those kernels keep P and dS in their accumulator type).
 
 The arithmetic (csrc/ = flash_attention_dlrs_amd/csrc/):
-  c   = fp32(scale * log2 e), the product formed in double       fa2_bwd_mfma16.hip:591, fa2_bwd_mfma32.hip:346,
-                                                                   fa2_bwd_generic.hip:213 (float64 I/O: c stays double)
-  D   = sum_x dO * O, O as stored                                   fa2_bwd_mfma16.hip:99-118, fa2_bwd_generic.hip:42-53
-  S   = Q K^T;  P_u = exp2(c S - L), L as stored; 0 where masked   fa2_bwd_mfma16.hip:400 / :427, generic :135-136
+  c   = fp32(scale * log2 e), the product formed in double       fa2_bwd_mfma16.hip:801, fa2_bwd_mfma32.hip:339,
+                                                                   fa2_bwd_generic.hip:414, :149 (float64 I/O: c stays double)
+  D   = sum_x dO * O, O as stored                                   fa2_bwd_mfma16.hip:90-121, fa2_bwd_generic.hip:72-89
+  S   = Q K^T;  P_u = exp2(c S - L), L as stored; 0 where masked   fa2_bwd_mfma16.hip:525 / :539, :567-576, generic :270-280
         (causal mask: key > query; rows and keys >= N: 0;
          window / varlen: outside band(), per sequence; a row with no visible key has L = +inf, so P = 0 and dQ = 0:
-         fa2_bwd_mfma16.hip:657-659, fa2_bwd_generic.hip:286)
-  tot = sum_j P_u                                                   fa2_bwd_mfma16.hip:429 / :489-495, generic :141-145
-  Lc  = L + log2 tot  (the dQ launch hands it to the dK/dV launch)  fa2_bwd_mfma16.hip:512, generic :174
-  dQ  = rnd(P_u (dP - D)) K * (scale / tot)       mfma16 / mfma32:  fa2_bwd_mfma16.hip:430, :445, :511
-      = rnd(P_u (dP - D) scale) K / tot           generic:          fa2_bwd_generic.hip:138, :171
-  P_n = exp2(c S - Lc), masked                                      fa2_bwd_mfma16.hip:324-327, generic :135-136
-  dV  = rnd(P_n)^T dO                                               fa2_bwd_mfma16.hip:356 (dV waves), generic :151
-  dK  = rnd(P_n (dP - D))^T Q * scale             mfma16 / mfma32:  fa2_bwd_mfma16.hip:348, :356, :514
-      = rnd(P_n (dP - D) scale)^T Q               generic:          fa2_bwd_generic.hip:138, :152
-  and the final RTNE cast of each gradient to the I/O dtype (fa2_bwd_mfma16.hip:506, generic E::store).
-mfma32 is mfma16's arithmetic in fp32 (fa2_bwd_mfma32.hip:214-222, :277-281): rnd is the identity there.
+         fa2_bwd_mfma16.hip:673-675, fa2_bwd_generic.hip:318-324)
+  tot = sum_j P_u                                                   fa2_bwd_mfma16.hip:577 / :644-650, generic :285-289
+  Lc  = L + log2 tot  (the dQ launch hands it to the dK/dV launch)  fa2_bwd_mfma16.hip:678, generic :336
+  dQ  = rnd(P_u (dP - D)) K * (scale / tot)       mfma16 / mfma32:  fa2_bwd_mfma16.hip:578, :593, :677
+      = rnd(P_u (dP - D) scale) K / tot           generic:          fa2_bwd_generic.hip:282, :333
+  P_n = exp2(c S - Lc), masked                                      fa2_bwd_mfma16.hip:454-463, generic :270-280
+  dV  = rnd(P_n)^T dO                                               fa2_bwd_mfma16.hip:490 (dV waves), generic :295
+  dK  = rnd(P_n (dP - D))^T Q * scale             mfma16 / mfma32:  fa2_bwd_mfma16.hip:482, :490, :681
+      = rnd(P_n (dP - D) scale)^T Q               generic:          fa2_bwd_generic.hip:282, :296
+  and the final RTNE cast of each gradient to the I/O dtype (fa2_bwd_mfma16.hip:667, generic E::store).
+mfma32 is mfma16's arithmetic in fp32 (fa2_bwd_mfma32.hip:207-215, :270-274): rnd is the identity there.
 
 What the restatement does NOT imitate (the kernels' liberties, covered by the bars below): every sum is exact here and
 fp32 in the kernels, in the matrix pipe's order; exp2 is exact here and v_exp_f32 / exp2f (1 ulp) there; Lc is exact here

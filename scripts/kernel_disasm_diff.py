@@ -1,11 +1,17 @@
-"""Compare the gfx950 disassembly of every kernel symbol between two builds of flash_attention_dlrs_amd/csrc.
+"""Compare the gfx950 code of every kernel symbol between two builds of flash_attention_dlrs_amd/csrc.
 
-    python scripts/kernel_disasm_diff.py OLD_CSRC_DIR NEW_CSRC_DIR
+    python scripts/kernel_disasm_diff.py [--suffix SUFFIX] OLD_CSRC_DIR NEW_CSRC_DIR
 
 Each directory holds the objects `make` left there (fa2_*.o).  The device code object of every object file is unbundled
-(clang-offload-bundler), disassembled (llvm-objdump -d) and split per function symbol.  Every symbol of the old build must
-exist in the new one with the same instructions; symbols only in the new build are listed.  Exit status 1 on a difference.
+(clang-offload-bundler), disassembled (llvm-objdump -d) and split per function symbol; the code-object metadata of every
+kernel is read from the notes (llvm-readelf --notes): VGPR, AGPR and SGPR counts, spills, LDS bytes, scratch bytes, kernarg
+size, max workgroup size.  Every symbol of the old build must exist in the same object of the new one with the same
+instructions and the same metadata; symbols only in the new build are listed.  Exit status 1 on a difference.
+
+--suffix names the objects to compare: "" (the default) for the library's own fa2_*.o, or one of _abl, _st, _var, _exp,
+_asan for the objects of the other builds (fa2_*_abl.o, ...).
 """
+import argparse
 import glob
 import os
 import re
@@ -15,16 +21,12 @@ import tempfile
 
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+SUFFIXES = ("_asan", "_abl", "_exp", "_st", "_var")
+META = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".group_segment_fixed_size",
+        ".private_segment_fixed_size", ".kernarg_segment_size", ".max_flat_workgroup_size")
 
 
-def symbols(obj, tmp):
-    fat = os.path.join(tmp, "fatbin")
-    dev = os.path.join(tmp, "dev.co")
-    if subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, os.path.join(tmp, "host.o")],
-                      capture_output=True).returncode != 0:
-        return {}
-    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                           f"--targets={TARGET}", f"--output={dev}"])
+def disassembly(dev):
     text = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", dev], text=True)
     out, name, body = {}, None, []
     for line in text.splitlines():
@@ -40,28 +42,77 @@ def symbols(obj, tmp):
     return out
 
 
-def collect(d):
+def metadata(dev):
+    """{kernel name: {key: value}} from the amdhsa.kernels list of the code object's metadata note."""
+    text = subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", dev], text=True)
+    out, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^  (-| ) (\.\w+):\s*(\S.*)?$", line)  # the scalar fields of one list entry, not its nested .args
+        if not m:
+            if not line.startswith("    "):
+                cur = None  # left the amdhsa.kernels list
+            continue
+        if m.group(1) == "-":
+            cur = {}
+        if cur is None:
+            continue
+        cur[m.group(2)] = m.group(3)
+        if m.group(2) == ".name":
+            out[m.group(3)] = cur
+    return {k: {f: v.get(f) for f in META} for k, v in out.items()}
+
+
+def symbols(obj, tmp):
+    """{symbol: (instructions, metadata or None)} of the device code in one host object."""
+    fat = os.path.join(tmp, "fatbin")
+    dev = os.path.join(tmp, "dev.co")
+    if subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, os.path.join(tmp, "host.o")],
+                      capture_output=True).returncode != 0:
+        return {}
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
+                           f"--targets={TARGET}", f"--output={dev}"])
+    meta = metadata(dev)
+    return {k: (v, meta.get(k)) for k, v in disassembly(dev).items()}
+
+
+def collect(d, suffix):
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for obj in sorted(glob.glob(os.path.join(d, "fa2_*.o"))):
-            if obj.endswith(("_asan.o", "_abl.o", "_exp.o", "_st.o", "_var.o", "_blob.o")):
+        for obj in sorted(glob.glob(os.path.join(d, f"fa2_*{suffix}.o"))):
+            stem = os.path.basename(obj)[:-2]
+            if "_blob" in stem or (not suffix and stem.endswith(SUFFIXES)):
                 continue
+            unit = stem[:len(stem) - len(suffix)] if suffix else stem
             for k, v in symbols(obj, tmp).items():
-                res[k] = v
+                res[f"{unit}: {k}"] = v
     return res
 
 
 def main():
-    old, new = collect(sys.argv[1]), collect(sys.argv[2])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--suffix", default="", choices=("",) + SUFFIXES, help="object suffix to compare (default: none)")
+    ap.add_argument("old")
+    ap.add_argument("new")
+    args = ap.parse_args()
+    old, new = collect(args.old, args.suffix), collect(args.new, args.suffix)
+    kernels = sum(1 for v in old.values() if v[1] is not None)
     changed = [k for k in old if k not in new or new[k] != old[k]]
     added = sorted(k for k in new if k not in old)
-    print(f"{len(old)} kernel symbols in the old build, {len(old) - len(changed)} identical, {len(changed)} changed or missing")
+    print(f"{len(old)} symbols ({kernels} kernels with metadata) in the old build, {len(old) - len(changed)} identical, "
+          f"{len(changed)} changed or missing")
     for k in changed:
-        print("  CHANGED" if k in new else "  MISSING", k)
+        if k not in new:
+            print("  MISSING", k)
+            continue
+        what = [w for w, i in (("instructions", 0), ("metadata", 1)) if new[k][i] != old[k][i]]
+        print("  CHANGED", k, "(" + ", ".join(what) + ")")
+        if "metadata" in what:
+            print("    old", old[k][1])
+            print("    new", new[k][1])
     print(f"{len(added)} new symbols")
     for k in added:
         print("  NEW", k)
-    return 1 if changed else 0
+    return 1 if changed or added else 0
 
 
 if __name__ == "__main__":
