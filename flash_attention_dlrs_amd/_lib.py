@@ -56,7 +56,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_kvcache_workspace_bytes", "fa2_kvcache_num_splits", "fa2_kvcache_append", "fa2_fwd_kvcache_append",
            "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits",
            "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits",
-           "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append")
+           "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append",
+           "fa2_fwd_kvcache_mla_varlen", "fa2_kvcache_mla_varlen_num_splits", "fa2_fwd_kvcache_mla_varlen_append")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -224,6 +225,18 @@ def lib():
         l.fa2_fwd_kvcache_mla_append.argtypes = [vp] * 4 + [i64p] * 4 + [vp, vp, vp, ctypes.c_int64, vp, i64p, vp, vp, i64p, i64p, vp, vp,
                                                  ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp] + [ctypes.c_int32] * 14 + \
             [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # packed queries over the latent cache: fa2_fwd_kvcache_varlen's order with one cache tensor and one descale, d_v after d
+        l.fa2_fwd_kvcache_mla_varlen.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_varlen.argtypes = [vp] * 4 + [i64p] * 3 + [ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, i64p] + \
+            [ctypes.c_int32] * 14 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_mla_varlen_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_mla_varlen_num_splits.argtypes = [ctypes.c_int32] * 9
+        # ... fused with the packed latent-cache append: seqlens_out after cache_seqlens and, after the descale, c_new pe_new + strides,
+        # rotary tables + row strides, S_rot rotary_dim interleaved, q_rot
+        l.fa2_fwd_kvcache_mla_varlen_append.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_varlen_append.argtypes = [vp] * 4 + [i64p] * 3 + [ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, vp, i64p, vp,
+                                                        vp, i64p, i64p, vp, vp, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + \
+            [vp] + [ctypes.c_int32] * 14 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -771,3 +784,57 @@ def fa2_fwd_kvcache_mla_append(Q, KV, O, L, c_new, pe_new, cache_seqlens, seqlen
             rd, int(bool(rotary_interleaved)), _ptr(q_rot), B, H, KV.shape[1], N_q, c_new.shape[2], S_k, nb, ps, mb, d, c_new.shape[3],
             int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits),
             *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
+
+
+def kvcache_mla_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, d_v, dtype_enum):
+    """What num_splits = 0 resolves to for a packed-query call over the latent cache (fa2_kvcache_mla_varlen_num_splits)."""
+    return int(lib().fa2_kvcache_mla_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, d_v, int(dtype_enum)))
+
+
+def _check_packed_l(who, L, H, total_q):
+    if L.dim() != 2 or L.shape != (H, total_q) or (total_q > 1 and L.stride(1) != 1):  # the ABI takes the head stride alone
+        raise ValueError(f"{who}: L must be (H, total_q) = ({H}, {total_q}) with unit token stride, got {tuple(L.shape)} with strides "
+                         f"{tuple(L.stride())}")
+
+
+def fa2_fwd_kvcache_mla_varlen(Q, KV, O, L, cu_q, max_q, cache_seqlens, dtype_enum, kv_dtype_enum, d_v, block_table=None, kv_descale=None,
+                               causal=False, scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch attention of packed queries over the latent cache (include/fa2_fwd.h fa2_fwd_kvcache_mla_varlen) on the current stream
+    of Q's device.  Q (total_q, H, d), O (total_q, H, d_v), any strides, L (H, total_q) with unit token stride, cu_q int32 (B + 1,) on
+    the device; KV the latent cache (B, H_kv, S_k, d) or, with block_table, the pool (num_blocks, H_kv, page_size, d); kv_descale a
+    float32 tensor viewed as (B, H_kv), or None for 1.  The workspace holds kvcache_varlen_workspace_bytes(total_q, H, d_v,
+    num_splits) bytes."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    total_q, H, d = Q.shape
+    _check_packed_l("fa2_fwd_kvcache_mla_varlen", L, H, total_q)
+    tb_ptr, tb_st, S_k, nb, ps, mb = _table_args(KV, block_table)
+    kd_ptr, _, kd_st, _ = _descale_args(kv_descale, None)
+    _launch(lib().fa2_fwd_kvcache_mla_varlen, Q,
+            Q.data_ptr(), KV.data_ptr(), O.data_ptr(), L.data_ptr(), _i64(Q.stride()), _i64(KV.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, kd_ptr, kd_st,
+            cu_q.numel() - 1, H, KV.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d, int(d_v), int(dtype_enum), int(kv_dtype_enum),
+            int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
+            int(variant), _raw_stream(Q.device.index))
+
+
+def fa2_fwd_kvcache_mla_varlen_append(Q, KV, O, L, c_new, pe_new, cu_q, max_q, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum,
+                                      block_table=None, kv_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False,
+                                      q_rot=None, causal=False, scale=1.0, window=None, num_splits=0, workspace=None, variant=0):
+    """Launch the fused ragged MLA step (include/fa2_fwd.h fa2_fwd_kvcache_mla_varlen_append) on the current stream of Q's device:
+    fa2_kvcache_mla_append_varlen with cu_q as its offsets (c_new (total_q, H_kv, d_v), pe_new (total_q, H_kv, d - d_v)), then
+    fa2_fwd_kvcache_mla_varlen over the updated KV with seqlens_out as its lengths and, with rotary tables, q_rot (a contiguous
+    (total_q, H, d) tensor in Q's dtype) as its Q."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    total_q, H, d = Q.shape
+    _check_packed_l("fa2_fwd_kvcache_mla_varlen_append", L, H, total_q)
+    tb_ptr, tb_st, kd_ptr, kd_st, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _mla_append_args(KV, block_table, kv_descale, rotary_cos, rotary_sin)
+    _launch(lib().fa2_fwd_kvcache_mla_varlen_append, Q,
+            Q.data_ptr(), KV.data_ptr(), O.data_ptr(), L.data_ptr(), _i64(Q.stride()), _i64(KV.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(), tb_ptr, tb_st, kd_ptr, kd_st, c_new.data_ptr(),
+            pe_new.data_ptr(), _i64(c_new.stride()), _i64(pe_new.stride()), cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd,
+            int(bool(rotary_interleaved)), _ptr(q_rot), cu_q.numel() - 1, H, KV.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d,
+            c_new.shape[2], int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window),
+            int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))

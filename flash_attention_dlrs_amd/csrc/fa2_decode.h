@@ -123,6 +123,11 @@ static inline bool fa2_decode_mfma16_v_shape(int32_t H, int32_t H_kv, int32_t d,
 bool fa2_decode_mfma16_v_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mfma16_v(const Fa2DecodeProblem &p);
 
+// The query-tiled form of the latent-cache matrix kernel (fa2_decode_mla16_v.hip, fa2_fwd_kvcache_mla_varlen): the g n_q(b) rows of a
+// (sequence, KV head) position-major, 64 of them per workgroup, ceil(g max_seqlen_q / 64) tiles per (split, KV head, sequence).
+bool fa2_decode_mla16_v_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_v(const Fa2DecodeProblem &p);
+
 // One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
 // each tensor's dtype.  It is the kernel's argument as well.
 struct Fa2AppendProblem {

@@ -1,10 +1,10 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache calls
-// _mla and _mla_fp8, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps fa2_fwd_kvcache_append
-// and _varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
+// _mla, _mla_fp8 and _mla_varlen, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
+// fa2_fwd_kvcache_append, _varlen_append, _mla_append and _mla_varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
 //   1. fill   the entry point names its raw arguments in a DecodeCall (the cache update's in an AppendCall), packed strides through packed4;
 //   2. check  check_decode (check_append) tests every argument, resolves num_splits (split_count on the unsplit workgroup count of the
 //             call's form) and fills the Fa2DecodeProblem (Fa2AppendProblem); nothing is launched;
-//   3. run    run_decode takes the call's row of kForms (fixed, packed, MLA) and launches, on the caller's stream, the append of a fused
+//   3. run    run_decode takes the call's row of kForms (fixed, packed, MLA, packed MLA) and launches, on the caller's stream, the append of a fused
 //             step, the split kernel, then the combine.  A fused step runs all of check_append before any check of the attention.
 #include "fa2_decode.h"
 
@@ -69,6 +69,26 @@ int num_splits_varlen(const SplitShape &s) {
     return split_count((mfma ? s.H_kv : s.H) * (grid < packed ? grid : packed), s.S_k, kSplitWaves, kMinSplitTiles);
 }
 
+// fa2_kvcache_mla_varlen_num_splits: the packed bound above on the tile count of the query-tiled latent form
+// (fa2_decode_mla16_v.hip): a sequence fills ceil(g n_q(b) / 64) row tiles per KV head, so the unsplit launch is at most the grid,
+// B * ceil(g max_seqlen_q / 64), and at most ceil(g total_q / 64) + B.  One wave of the chip as for the fixed latent call, but a
+// split is at least kMlaVarlenMinSplitTiles = 8 key tiles long, not 4: the combine's packed path costs more per split than the fixed
+// one, and the split sweep of benchmarks/bench_mla_varlen.py has 8-tile splits ahead of 4-tile ones, outside both sides' ranges,
+// wherever the two differ ("MLA decode: packed queries").  Every other shape is counted as
+// fa2_kvcache_varlen_num_splits counts the VALU form.
+constexpr int kMlaVarlenMinSplitTiles = 8;
+
+int num_splits_mla_varlen(const SplitShape &s) {
+    if (!fa2_decode_mla16_shape(s.d, s.d_v, s.dtype) || s.H_kv < 1 || s.H % s.H_kv != 0) {
+        SplitShape valu = s;
+        valu.d = 0;
+        return num_splits_varlen(valu);
+    }
+    const int64_t g = s.H / s.H_kv;
+    const int64_t grid = s.B * ((g * s.N_q + 63) / 64), packed = (g * s.total_q + 63) / 64 + s.B;
+    return split_count(s.H_kv * (grid < packed ? grid : packed), s.S_k, kMlaSplitWaves, kMlaVarlenMinSplitTiles);
+}
+
 // The fp32 workspace of a split call: o_part [num_splits][rows][d_v] then l_part [num_splits][rows], rows = B * H * N_q
 // (total_q * H for packed queries).
 int64_t workspace_bytes(int64_t rows, int64_t d_v, int64_t num_splits) {
@@ -98,28 +118,29 @@ struct DecodeCall {
     int32_t kv_dtype_enum = 0;
     const float *k_descale = nullptr, *v_descale = nullptr;
     const int64_t *k_descale_strides = nullptr, *v_descale_strides = nullptr;
-    bool packed = false;  // fa2_fwd_kvcache_varlen: Q, O are (total_q, H, d) over cu_seqlens_q, L is (H, total_q)
+    bool packed = false;  // fa2_fwd_kvcache_varlen, _mla_varlen (with `mla`): Q, O are (total_q, H, d) over cu_seqlens_q, L is (H, total_q)
     const int32_t *cu_seqlens_q = nullptr;
     int32_t total_q = 0, max_seqlen_q = 0;
-    bool mla = false;  // fa2_fwd_kvcache_mla, _mla_fp8 (with `fp8`): V is (B, H_kv, S_k, d_v), d may reach 576; without it d_v = d
+    bool mla = false;  // fa2_fwd_kvcache_mla, _mla_fp8 (with `fp8`), _mla_varlen (with `packed`): V is (B, H_kv, S_k, d_v), d may reach 576; without it d_v = d
     int32_t d_v = 0;
 };
 
-// The three forms of the call: fixed N_q, packed queries (query-tiled), the latent cache.  Each has a matrix kernel of its own
-// beside the VALU kernel (fa2_launch_decode_generic) and the combine, which all share; `variant` is the id that forces it, and
-// AUTO, GENERIC and that id are the variants the form accepts: any other gets `unknown_variant`.
+// The four forms of the call: fixed N_q, packed queries (query-tiled), the latent cache, packed queries over the latent cache.  Each
+// has a matrix kernel of its own beside the VALU kernel (fa2_launch_decode_generic) and the combine, which all share; `variant` is
+// the id that forces it, and AUTO, GENERIC and that id are the variants the form accepts: any other gets `unknown_variant`.
 struct DecodeForm {
     bool (*supports)(const Fa2DecodeProblem &);
     int (*launch)(const Fa2DecodeProblem &);
     int32_t variant;
     const char *unknown_variant;
 };
-const DecodeForm kForms[3] = {
+const DecodeForm kForms[4] = {
     {fa2_decode_mfma16_supports, fa2_launch_decode_mfma16, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mfma16_v_supports, fa2_launch_decode_mfma16_v, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mla16_supports, fa2_launch_decode_mla16, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
+    {fa2_decode_mla16_v_supports, fa2_launch_decode_mla16_v, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
 };
-const DecodeForm &form_of(const DecodeCall &c) { return kForms[c.mla ? 2 : c.packed ? 1 : 0]; }
+const DecodeForm &form_of(const DecodeCall &c) { return kForms[c.packed && c.mla ? 3 : c.mla ? 2 : c.packed ? 1 : 0]; }
 
 // The sizes of a paged cache, for check_decode ("kvcache paged") and check_append ("kvcache append"); on FA2_OK `cap` is the capacity.
 int check_paged(const char *who, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int64_t table_stride, int64_t &cap) {
@@ -296,7 +317,7 @@ int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
     p.cu_q = c.packed ? c.cu_seqlens_q : nullptr;
     p.total_q = c.packed ? c.total_q : 0; p.max_q = c.packed ? c.max_seqlen_q : 0;
     const SplitShape shape = {c.B, c.H, c.H_kv, c.N_q, c.total_q, S_k, c.d, d_v, c.dtype_enum};
-    p.num_splits = c.num_splits != 0 ? c.num_splits : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
+    p.num_splits = c.num_splits != 0 ? c.num_splits : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
     p.stream = (hipStream_t)c.hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
@@ -705,6 +726,38 @@ int32_t fa2_kvcache_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_
     return num_splits_varlen({B, H, H_kv, max_seqlen_q, total_q, S_k, d, d, dtype_enum});
 }
 
+int fa2_fwd_kvcache_mla_varlen(const void *Q, const void *KV, void *O, void *L, const int64_t q_strides[3], const int64_t kv_strides[4],
+                               const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
+                               const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride,
+                               const float *kv_descale, const int64_t kv_descale_strides[2], int32_t B, int32_t H, int32_t H_kv,
+                               int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                               int32_t max_blocks, int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal,
+                               float scale, int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace,
+                               int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    // the packed tensors in the fixed call's terms, as in fa2_fwd_kvcache_varlen; V is the first d_v columns of the row K scores, the
+    // one descale K's and V's, as in fa2_fwd_kvcache_mla_append
+    int64_t qs[4], os[4];
+    const int64_t ls[2] = {0, l_head_stride};
+    DecodeCall c;
+    c.Q = Q; c.K = KV; c.V = KV; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = packed4(q_strides, qs); c.k_strides = kv_strides; c.v_strides = kv_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = kv_descale; c.v_descale = kv_descale; c.k_descale_strides = kv_descale_strides; c.v_descale_strides = kv_descale_strides;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    return decode(c, nullptr);
+}
+
+int32_t fa2_kvcache_mla_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                          int32_t d, int32_t d_v, int32_t dtype_enum) {
+    if (B < 1 || H < 1 || H_kv < 1 || total_q < 1 || max_seqlen_q < 1 || S_k < 1) return 1;
+    return num_splits_mla_varlen({B, H, H_kv, max_seqlen_q, total_q, S_k, d, d_v, dtype_enum});
+}
+
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {
     if (B < 1 || H < 1 || N_q < 1 || d < 1 || B > 65535 || H > 65535 || N_q > (1 << 28)) return 0;
     return workspace_bytes((int64_t)B * H * N_q, d, num_splits);
@@ -901,6 +954,47 @@ int fa2_fwd_kvcache_mla_append(const void *Q, void *KV, void *O, void *L, const 
     c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
     c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
     c.k_descale = kv_descale; c.v_descale = kv_descale; c.k_descale_strides = kv_descale_strides; c.v_descale_strides = kv_descale_strides;
+    return decode(c, &p);
+}
+
+int fa2_fwd_kvcache_mla_varlen_append(const void *Q, void *KV, void *O, void *L, const int64_t q_strides[3], const int64_t kv_strides[4],
+                                      const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
+                                      const int32_t *cache_seqlens, int32_t *seqlens_out, const int32_t *block_table,
+                                      int64_t block_table_stride, const float *kv_descale, const int64_t kv_descale_strides[2],
+                                      const void *c_new, const void *pe_new, const int64_t c_new_strides[3],
+                                      const int64_t pe_new_strides[3], const void *rotary_cos, const void *rotary_sin,
+                                      int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim,
+                                      int32_t rotary_interleaved, void *q_rot, int32_t B, int32_t H, int32_t H_kv, int32_t total_q,
+                                      int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                                      int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t causal, float scale,
+                                      int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace,
+                                      int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    const int32_t per_row = causal || window_left >= 0 || window_right >= 0;  // the fused call's rule for Q's rotary positions
+    int64_t cns[4], pns[4], qs[4], os[4];
+    AppendCall a = {KV, nullptr, kv_strides, nullptr, block_table, block_table_stride, c_new, pe_new, packed4(c_new_strides, cns),
+                    packed4(pe_new_strides, pns), cache_seqlens, seqlens_out, kv_descale, nullptr, kv_descale_strides, nullptr,
+                    rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, Q, q_rot,
+                    packed4(q_strides, qs), H, 0, per_row, B, H_kv, 0, S_k, num_blocks, page_size, max_blocks, d, dtype_enum,
+                    kv_dtype_enum, hip_stream};
+    a.packed = true; a.cu_seqlens_new = cu_seqlens_q; a.total_new = total_q; a.max_seqlen_new = max_seqlen_q;
+    a.mla = true; a.d_v = d_v;
+    Fa2AppendProblem p;
+    const int rc = check_append(a, p);
+    if (rc != FA2_OK) return rc;
+    // the attention reads the rotated Q (packed, contiguous; p.Q null: no tables, Q as it is), the new lengths, and V as the first d_v
+    // columns of the row it scores: the one descale is K's and V's
+    const int64_t rot_strides[4] = {0, d, (int64_t)H * d, 1}, ls[2] = {0, l_head_stride};
+    DecodeCall c;
+    c.Q = p.Q ? q_rot : Q; c.K = KV; c.V = KV; c.O = O; c.L = L; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = p.Q ? rot_strides : a.q_strides; c.k_strides = kv_strides; c.v_strides = kv_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls; c.cache_seqlens = seqlens_out;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = kv_descale; c.v_descale = kv_descale; c.k_descale_strides = kv_descale_strides; c.v_descale_strides = kv_descale_strides;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
     return decode(c, &p);
 }
 

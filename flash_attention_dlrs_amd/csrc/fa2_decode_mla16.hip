@@ -45,8 +45,26 @@
 // Output: num_splits == 1 writes O / l and L = m + log2 l in the I/O dtype (a row without a visible key: O = 0, L = +inf);
 // otherwise every (split, row) writes the normalised fp32 partial (an empty split: 0 and -inf) for fa2_decode_combine.hip.
 // Vector stores only, no atomics, no hand-off between workgroups.
+//
+// Variable-length queries (fa2_fwd_kvcache_mla_varlen).  VQ is a template parameter, instantiated in fa2_decode_mla16_v.hip
+// (FA2_DECODE_VARLEN_Q) alone: Q and O are packed (total_q, H, d) / (total_q, H, d_v), L is (H, total_q), sequence b owns n_q(b)
+// rows from start(b) on (fa2_varlen_seq).  The g n_q(b) rows of one (sequence, KV head) are flattened POSITION-major, row =
+// position * g + head-in-group, and a workgroup owns rows [64 t, 64 t + 64) of them: every tile but a sequence's last is full for
+// any g, and a tile covers the contiguous positions [q0, q1) = [64 t / g, min((64 t + 63) / g + 1, n_q(b))).  The grid's x axis is
+// (split, ceil(g max_seqlen_q / 64) tiles); a tile with 64 t >= g n_q(b) leaves at once, before any barrier, and writes nothing.
+// (Sequence b takes its (split, tile) pairs rotated by b along x, so that the tiles with rows of short sequences do not sit a fixed
+// gridDim.x workgroup ids apart: see the kernel's head.)
+// Padding rows repeat the sequence's last row and are dropped: no neighbour's packed row is read or written.  The mask is the band
+// of n_q(b) and N_k(b), the row's position counted in the SEQUENCE; the split's key range is clipped to the band of the tile's own
+// [q0, q1), whole 64-key tiles outside it neither loaded nor looked up.  The partial row is split * total_q * H + (start +
+// position) * H + head, what the combine expects for cu_q.  With VQ false q0 = 0, q1 = N_q, start = 0, rows are head-major as
+// above and every expression below is the fixed-N_q kernel's.
 #include "fa2_decode.h"
 #include "fa2_mfma.h"
+
+#ifndef FA2_DECODE_VARLEN_Q
+#define FA2_DECODE_VARLEN_Q 0
+#endif
 
 namespace {
 
@@ -64,6 +82,8 @@ struct DecodeMlaArgs {
     int page_size, num_blocks;
     const float *kd, *vd;  // fp8 cache only: descales at [b * kds[0] + h_kv * kds[1]], null = 1
     int64_t kds[2], vds[2];
+    const int32_t *cu_q;  // VQ only: B + 1 offsets into the packed rows; qs[0] = os[0] = ls[0] = 0, N_q holds max_q
+    int total_q;
 };
 
 constexpr int kD = 576, kDV = 512, kBC = 64;
@@ -86,8 +106,10 @@ static_assert(kStage == 18 && kStage8 == 9 && kSmem <= 160 * 1024, "one workgrou
 // Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: the d = 128 swizzle on rows of kRowB bytes.
 __device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ swz<128>(row)) << 4); }
 
-// T: Q, O, L and the matrix arithmetic; C: the cache (T, or an fp8 format converted while it is staged).
-template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
+// T: Q, O, L and the matrix arithmetic; C: the cache (T, or an fp8 format converted while it is staged).  VQ: packed queries,
+// rows position-major.
+template <typename T, typename C, bool PAGED, bool VQ>
+__global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
     using M = Mma<T>;
     constexpr bool F8 = !__is_same(C, T);
     using frag = typename M::frag;
@@ -99,29 +121,51 @@ template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 
     const int kb = wave & 1, rb = wave >> 1;  // S phase: key block, row block
     const int i = lane & 31, h = lane >> 5;
     const int hk = blockIdx.y, b = blockIdx.z;
-    const int split = blockIdx.x / a.row_tiles, rt = blockIdx.x - split * a.row_tiles;
-    const int N_q = a.N_q, R = a.g * N_q;
+    int bx = blockIdx.x;
+    if constexpr (VQ) {
+        // The hardware deals consecutive workgroup ids round the chip's shader engines.  With tile t of every sequence at x = t the
+        // tiles that have rows sit gridDim.x ids apart where the sequences are short (one-token decodes beside a long chunk), and
+        // where that stride is a multiple of the number of engines they all land on ONE engine's 8 CUs, at one workgroup per CU
+        // (measured: 63 one-token sequences under max_seqlen_q = 256 took 955 us, 123 us alone).  So sequence b takes its (split,
+        // tile) pairs rotated by b: a long sequence's tiles stay on consecutive ids, the first tiles of consecutive sequences sit
+        // gridDim.x - 1 ids apart.  A bijection of the same grid.
+        bx += blockIdx.z % gridDim.x;  // (gridDim.x <= 128 splits * 2^18 row tiles: the sum stays far inside an int)
+        bx -= bx >= (int)gridDim.x ? (int)gridDim.x : 0;
+    }
+    const int split = bx / a.row_tiles, rt = bx - split * a.row_tiles;
+    // N_q: the query count of the mask and of the rows, from packed row `start` on; [q0, q1): the positions the tile's rows lie in
+    int N_q = a.N_q, start = 0;
+    if constexpr (VQ) {
+        fa2_varlen_seq(a.cu_q, b, a.total_q, a.N_q, start, N_q);
+        if (rt * 64 >= a.g * N_q) return;  // no rows: nothing to write, no partials (uniform: before any barrier)
+    }
+    const int R = a.g * N_q;
+    const int q0 = VQ ? rt * 64 / a.g : 0;
+    const int q1 = VQ ? ((rt * 64 + 63) / a.g + 1 < N_q ? (rt * 64 + 63) / a.g + 1 : N_q) : N_q;
 
     int NK, k0, k1;
     fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
     int wl, wr;
     fa2_varlen_band(N_q, NK, a.causal, a.wl, a.wr, wl, wr);
-    // the keys of the split that the band of any query position touches: [kb0, ke), kb0 on a 64-key boundary
-    const int lo_t = -wl;
+    // the keys of the split that the band of any query position of the tile touches: [kb0, ke), kb0 on a 64-key boundary
+    const int lo_t = q0 - wl;
     const int kb0 = lo_t > k0 ? (lo_t & ~63) : k0;  // (k0 is a multiple of 64)
-    const int ke = N_q + wr < k1 ? N_q + wr : k1;
+    const int ke = q1 + wr < k1 ? q1 + wr : k1;
     const int nt = ke > kb0 ? (ke - kb0 + kBC - 1) / kBC : 0;
 
-    // ---- S phase: this lane's row (head of the group, query position); padding rows repeat the last row and are not stored
+    // ---- S phase: this lane's row (head of the group, query position); padding rows repeat the last row and are not stored.
+    // Fixed N_q: row = head * N_q + position.  VQ: row = position * g + head.
     const int srow = rt * 64 + rb * 32 + i;
     const int srowc = srow < R ? srow : R - 1;
-    const int shg = srowc / N_q;
-    const int sqi = srowc - shg * N_q;
+    const int sdiv = srowc / (VQ ? a.g : N_q);
+    const int srem = srowc - sdiv * (VQ ? a.g : N_q);
+    const int shg = VQ ? srem : sdiv;
+    const int sqi = VQ ? sdiv : srem;
 
     // ---- Q fragments: B operand of S^T = K Q^T.  Lane (i, h) holds Q[row][16ks + 8h .. +7].
     frag qf[kKS];
     {
-        const char *qp = a.Q + b * a.qs[0] + (int64_t)(hk * a.g + shg) * a.qs[1] + (int64_t)sqi * a.qs[2] + h * 16;
+        const char *qp = a.Q + b * a.qs[0] + (int64_t)(hk * a.g + shg) * a.qs[1] + (int64_t)(start + sqi) * a.qs[2] + h * 16;
 #pragma unroll
         for (int ks = 0; ks < kKS; ++ks) qf[ks] = __builtin_bit_cast(frag, *(const u32x4 *)(qp + ks * 32));
     }
@@ -239,7 +283,7 @@ template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 
     }
     // this row's visible keys [lo, hi], and whether a tile can meet a band edge of any row
     const int lo = sqi - wl, hi = (sqi + wr) < (ke - 1) ? (sqi + wr) : (ke - 1);
-    const int lo_max = N_q - 1 - wl, hi_min = wr < (ke - 1) ? wr : (ke - 1);
+    const int lo_max = q1 - 1 - wl, hi_min = (q0 + wr) < (ke - 1) ? (q0 + wr) : (ke - 1);
 
     if (nt > 0) {
         stage_load(0);
@@ -348,8 +392,10 @@ template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 
     for (int rbp = 0; rbp < 2; ++rbp) {
         const int row = rt * 64 + 32 * rbp + i;
         if (row >= R) continue;
-        const int hg = row / N_q;
-        const int qi = row - hg * N_q;
+        const int ediv = row / (VQ ? a.g : N_q);  // (recomputed, not carried from the S phase: no register lives across the loop)
+        const int erem = row - ediv * (VQ ? a.g : N_q);
+        const int hg = VQ ? erem : ediv;
+        const int qi = VQ ? ediv : erem;
         const int head = hk * a.g + hg;
         const float l = xl[32 * rbp + i] + xl[64 + 32 * rbp + i];
         const float mr = mf[32 * rbp + i];
@@ -357,7 +403,7 @@ template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 
         float inv = seen ? 1.0f / l : 0.0f;
         if constexpr (F8) inv = seen ? inv * vd : 0.0f;  // O = vd (P V8) / l, in fp32
         if (a.num_splits == 1) {
-            char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)qi * a.os[2] + (128 * wave + 4 * h) * 2;
+            char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)(start + qi) * a.os[2] + (128 * wave + 4 * h) * 2;
 #pragma unroll
             for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -369,12 +415,12 @@ template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 
                     *(u32x2 *)(op + db * 64 + g * 16) = __builtin_bit_cast(u32x2, v);
                 }
             if (wave == 0 && h == 0) {
-                T *lp = (T *)a.L + b * a.ls[0] + head * a.ls[1] + qi;
+                T *lp = (T *)a.L + b * a.ls[0] + head * a.ls[1] + start + qi;
                 *lp = seen ? (T)(mr + __builtin_amdgcn_logf(l)) : (T)INFINITY;
             }
         } else {
-            const int64_t rows = (int64_t)gridDim.z * a.H * N_q;
-            const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + head) * N_q + qi;
+            const int64_t rows = VQ ? (int64_t)a.total_q * a.H : (int64_t)gridDim.z * a.H * N_q;
+            const int64_t prow = (int64_t)split * rows + (VQ ? (int64_t)(start + qi) * a.H + head : ((int64_t)b * a.H + head) * N_q + qi);
             float *op = a.o_part + prow * kDV + 128 * wave + 4 * h;
 #pragma unroll
             for (int db = 0; db < 4; ++db)
@@ -390,6 +436,8 @@ template <typename T, typename C, bool PAGED> __global__ __launch_bounds__(256, 
     }
 }
 
+constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0;
+
 template <typename T, typename C, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
     const long long gx = (long long)p.num_splits * a.row_tiles;
     if (gx > 0x7fffffffLL) {
@@ -398,11 +446,11 @@ template <typename T, typename C, bool PAGED> int launch_t(const Fa2DecodeProble
     }
     static Fa2DeviceLatch attr_done;  // more than 64 KiB of dynamic LDS: opt in, once per device
     if (attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, C, PAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
+        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, C, PAGED, kVQ>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
         attr_done.mark();
     }
     const dim3 grid((unsigned)gx, p.H_kv, p.B), block(256);
-    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, C, PAGED>), grid, block, kSmem, p.stream, a);
+    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, C, PAGED, kVQ>), grid, block, kSmem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mla16 kernel launch failed: %s", hipGetErrorString(e));
@@ -425,10 +473,9 @@ bool fp8_cache(const Fa2DecodeProblem &p) { return p.kv_dtype == FA2_DTYPE_F8E4M
 
 bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
-}  // namespace
-
-bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p) {
-    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || (p.kv_dtype != p.dtype && !fp8_cache(p)) || p.cu_q) return false;
+// (packed queries: N_q holds max_seqlen_q, so the row bound below is the grid's)
+bool supports(const Fa2DecodeProblem &p) {
+    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || (p.kv_dtype != p.dtype && !fp8_cache(p)) || (p.cu_q != nullptr) != kVQ) return false;
     if (p.V != p.K) return false;  // the value operand is read from K's LDS image
     for (int k = 0; k < 4; ++k)
         if (p.vs[k] != p.ks[k]) return false;
@@ -446,8 +493,8 @@ bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p) {
     return true;
 }
 
-int fa2_launch_decode_mla16(const Fa2DecodeProblem &p) {
-    if (!fa2_decode_mla16_supports(p)) {
+int launch(const Fa2DecodeProblem &p) {
+    if (!supports(p)) {
         fa2_set_error("kvcache mla16 kernel: needs f16/bf16, d = 576 and d_v = 512, V aliasing K (the same pointer and strides), unit "
                       "d-stride, 16-byte aligned rows (and workspace), scale > 0%s%s",
                       fp8_cache(p) ? "; an fp8 cache: every stride of K a multiple of 16 elements and a 16-byte aligned base" : "",
@@ -469,5 +516,16 @@ int fa2_launch_decode_mla16(const Fa2DecodeProblem &p) {
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+    a.cu_q = p.cu_q; a.total_q = p.total_q;
     return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }
+
+}  // namespace
+
+#if FA2_DECODE_VARLEN_Q
+bool fa2_decode_mla16_v_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_v(const Fa2DecodeProblem &p) { return launch(p); }
+#else
+bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16(const Fa2DecodeProblem &p) { return launch(p); }
+#endif

@@ -580,7 +580,8 @@ def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=5
     (S_rot, rotary_dim / 2) in Q's dtype with unit last stride, rotary_dim <= d - d_v, rotate the columns [d_v, d_v + rotary_dim) of
     the new rows at cache_seqlens[b] + t and of Q (a copy: Q itself is not modified) at cache_seqlens[b] + i for row i when the call
     is causal or windowed, every row at cache_seqlens[b] otherwise, as flash-attn does; apply_rotary on those columns is the
-    arithmetic, bit for bit.  They need kv_new.  Without kv_new the cache is only read.  Packed queries are not supported."""
+    arithmetic, bit for bit.  They need kv_new.  Without kv_new the cache is only read.  Packed (ragged) queries over the same cache:
+    flash_attention_mla_varlen_decode_forward."""
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError("mla decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < KV_cache.shape[3]:
@@ -785,4 +786,96 @@ def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, ma
                                 convert_triton_dtype(K_cache.dtype), block_table=block_table,
                                 **_descale_views(k_descale, v_descale, Q, B, H_kv), causal=causal, scale=scale,
                                 window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_VARIANTS[variant])
+    return O, L
+
+
+def check_mla_varlen_args(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v=512, window=None, num_splits=0, kv_descale=None,
+                          block_table=None, kv_new=None, rotary_cos=None, rotary_sin=None):
+    """ValueError for what flash_attention_mla_varlen_decode_forward cannot take: the packed Q, cu_seqlens_q and max_seqlen_q by the
+    rules of check_varlen_kvcache_args, the latent cache, d_v, kv_descale, cache_seqlens, block_table, window and num_splits by those
+    of flash_attention_mla_decode_forward, and with kv_new or the rotary tables every rule of check_mla_append_args for packed tokens
+    over the same cu_seqlens_q.  Pure: takes CPU tensors as well."""
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] < 1:
+        raise ValueError(f"mla varlen decode: Q must be packed (total_q, H, d) with total_q >= 1, got "
+                         f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
+        raise ValueError("mla varlen decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    d = KV_cache.shape[3]
+    if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
+        raise ValueError(f"mla varlen decode: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
+    if not 1 <= d <= 576 or d_v > 512:
+        raise ValueError(f"mla varlen decode: d must be in [1, 576] and d_v in [1, 512], got d = {d}, d_v = {d_v}")
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 \
+            or not cu_seqlens_q.is_contiguous() or cu_seqlens_q.numel() < 2:
+        raise ValueError("mla varlen decode: cu_seqlens_q must be a contiguous int32 tensor of B + 1 >= 2 entries")
+    if cu_seqlens_q.device != Q.device:
+        raise ValueError(f"mla varlen decode: cu_seqlens_q must be on Q's device ({Q.device}), got {cu_seqlens_q.device}")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or not 1 <= max_seqlen_q <= 1 << 28:
+        raise ValueError(f"mla varlen decode: max_seqlen_q must be an int in [1, 2^28], got {max_seqlen_q!r}")
+    if Q.shape[0] * Q.shape[1] > 1 << 40:
+        raise ValueError(f"mla varlen decode: total_q * H must be <= 2^40, got {Q.shape[0]} * {Q.shape[1]}")
+    B = cu_seqlens_q.numel() - 1
+    fp8 = KV_cache.dtype in FP8_CACHE_DTYPES
+    if kv_descale is not None and not fp8:
+        raise ValueError(f"mla varlen decode: kv_descale goes with an fp8 KV_cache, not with {KV_cache.dtype}")
+    # the cache's rules are the fixed-N_q call's: seen through a (B, H, 1, d) view of Q (no data is read), K and V the one tensor
+    check_kvcache_args(Q[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1, -1), KV_cache, KV_cache, cache_seqlens, window, num_splits,
+                       None, None, block_table)
+    _kvcache_descale("kv_descale", kv_descale, Q, B, KV_cache.shape[1])
+    if kv_new is not None or rotary_cos is not None or rotary_sin is not None:
+        check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin,
+                              cu_seqlens_new=cu_seqlens_q, max_seqlen_new=max_seqlen_q)
+        c_new = _mla_sources(kv_new, d_v)[0]
+        if c_new.shape[0] != Q.shape[0] or c_new.dtype != Q.dtype or c_new.device != Q.device:
+            raise ValueError(f"mla varlen decode: kv_new must have Q's total_q = {Q.shape[0]}, dtype ({Q.dtype}) and device ({Q.device}), "
+                             f"got {tuple(c_new.shape)} in {c_new.dtype} on {c_new.device}")
+
+
+def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, d_v=512, causal=False,
+                                              scale=1.0, window=None, num_splits=0, variant="auto", block_table=None, kv_descale=None,
+                                              kv_new=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+    """Multi-head latent attention of variable-length (packed) queries over the shared latent cache (include/fa2_fwd.h
+    fa2_fwd_kvcache_mla_varlen) -> (O, L): the verification of MTP / draft tokens, a mixed step of a prefill chunk beside one-token
+    decodes, a prefix-cached chunk, in one call.  Q (total_q, H, d), any strides; cu_seqlens_q int32 (B + 1,) on Q's device and
+    max_seqlen_q as in flash_attention_varlen_kvcache_forward: sequence b owns min(cu[b + 1] - cu[b], max_seqlen_q) rows from cu[b]
+    on, none is legal, and query i of it stands at position cache_seqlens[b] - n_q(b) + i (causal and window bottom-right aligned per
+    sequence).  KV_cache, d_v, cache_seqlens, block_table and kv_descale are flash_attention_mla_decode_forward's: the contiguous
+    (B, H_kv, S_k, d) latent cache or a page pool, in Q's dtype or fp8 with its one descale.  O (total_q, H, d_v) contiguous, L
+    (H, total_q) log2-domain, both in Q's dtype; rows without a visible key get O = 0, L = +inf; rows outside every sequence are not
+    written.  num_splits = 0 lets the library choose; variant is one of _lib.KVCACHE_MLA_VARIANTS: "mla16" (f16 / bf16, d = 576,
+    d_v = 512, unit d-stride and 16-byte aligned rows, contiguous or paged with page_size % 64 == 0, any H / H_kv), "generic"
+    (everything else), "auto".  With every sequence at n_q = max_seqlen_q = N_q the result equals
+    flash_attention_mla_decode_forward's at the same explicit num_splits bit for bit.  No autograd, no autotuner.
+
+    Append (fa2_fwd_kvcache_mla_varlen_append): with kv_new -- one packed tensor (total_q, H_kv, d) in Q's dtype on Q's device, or the
+    pair (c_new, pe_new) with last axes d_v and d - d_v, any strides, token i of Q and kv_new the same token -- the call first writes
+    the new rows into KV_cache IN PLACE as mla_kvcache_append_varlen does over cu_seqlens_q, and then attends over cache_seqlens +
+    n_q(b) keys (at most the capacity).  cache_seqlens is required, holds the lengths BEFORE the append and is not modified.
+    rotary_cos, rotary_sin rotate the columns [d_v, d_v + rotary_dim) of new row t at cache_seqlens[b] + t and of Q (a copy) row i at
+    cache_seqlens[b] + i when the call is causal or windowed, every row at cache_seqlens[b] otherwise:
+    flash_attention_mla_decode_forward's rule.  They need kv_new."""
+    check_mla_varlen_args(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, window, num_splits, kv_descale, block_table,
+                          kv_new, rotary_cos, rotary_sin)
+    if variant not in _lib.KVCACHE_MLA_VARIANTS:
+        raise ValueError(f"mla varlen decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
+    _check_dev(dev, Q, KV_cache, KV_cache)
+    total_q, H, d = Q.shape
+    B, H_kv = cu_seqlens_q.numel() - 1, KV_cache.shape[1]
+    dtype = convert_triton_dtype(Q.dtype)
+    n = num_splits or _lib.kvcache_mla_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, _capacity(KV_cache, block_table), d, d_v, dtype)
+    O, L, ws = _kvcache_outputs(Q, (total_q, H, d_v), (H, total_q), _lib.kvcache_varlen_workspace_bytes(total_q, H, d_v, n) if n > 1 else 0)
+    kd = _kvcache_descale("kv_descale", kv_descale, Q, B, H_kv)
+    if kv_new is not None:
+        c_new, pe_new = _mla_sources(kv_new, d_v)
+        _lib.fa2_fwd_kvcache_mla_varlen_append(Q, KV_cache, O, L, c_new, pe_new, cu_seqlens_q, max_seqlen_q, cache_seqlens,
+                                               torch.empty_like(cache_seqlens), dtype, convert_triton_dtype(KV_cache.dtype),
+                                               block_table=block_table, kv_descale=kd, rotary_cos=rotary_cos, rotary_sin=rotary_sin,
+                                               rotary_interleaved=rotary_interleaved,
+                                               q_rot=None if rotary_cos is None else torch.empty(total_q, H, d, dtype=Q.dtype, device=Q.device),
+                                               causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
+                                               variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
+    _lib.fa2_fwd_kvcache_mla_varlen(Q, KV_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
+                                    convert_triton_dtype(KV_cache.dtype), d_v, block_table=block_table, kv_descale=kd, causal=causal,
+                                    scale=scale, window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
     return O, L

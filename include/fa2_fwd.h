@@ -699,6 +699,72 @@ int fa2_fwd_kvcache_mla_append(const void *Q, void *KV, void *O, void *L,
                                int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
                                void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
+/*
+ * Variable-length (packed) queries over the latent cache: fa2_fwd_kvcache_varlen's queries on fa2_fwd_kvcache_mla's cache -- the
+ * verification of MTP / draft tokens, a prefill chunk beside one-token decodes, a prefix-cached chunk, in one call.  Forward only.
+ *
+ *   Queries.  fa2_fwd_kvcache_varlen's: Q packed (total_q, H, d), O packed (total_q, H, d_v), strides {token, head, dim}; L
+ *             (H, total_q) with head stride l_head_stride; cu_seqlens_q, max_seqlen_q, n_q(b) and the untouched rows as there.
+ *   Cache.    KV with kv_strides is the one tensor of the latent cache: (B, H_kv, S_k, d) with a null block_table (num_blocks,
+ *             page_size, max_blocks ignored), else the pool (num_blocks, H_kv, page_size, d) behind the table (S_k ignored).  The call
+ *             is the attention with K = V = KV and v_strides = kv_strides: the score takes all d columns, the value the first d_v
+ *             of the same row.  d in [1, 576], d_v in [1, 512].  kv_dtype_enum == dtype_enum with a null kv_descale is the cache
+ *             in Q's dtype; an fp8 kv_dtype_enum the fp8 cache of fa2_fwd_kvcache_mla_fp8 with kv_descale (at [b *
+ *             kv_descale_strides[0] + h_kv * kv_descale_strides[1]], null = 1) as K's and V's descale.  A V tensor of its own is
+ *             not supported with packed queries.
+ *   Mask.     fa2_fwd_kvcache_varlen's.
+ *   Splits.   num_splits = 0 picks fa2_kvcache_mla_varlen_num_splits(...).  Workspace: fa2_kvcache_varlen_workspace_bytes(total_q,
+ *             H, d_v, num_splits) bytes, 16-byte aligned.
+ *   Variants. fa2_fwd_kvcache_mla's.  FA2_KVCACHE_VARIANT_MLA16: f16 / bf16, d = 576, d_v = 512, the cache in that dtype, e4m3 or
+ *             e5m2, unit d-stride, 16-byte aligned rows (an fp8 cache: every stride a multiple of 16 elements), scale > 0,
+ *             page_size % 64 == 0 when paged; any H_kv, any g = H / H_kv.  The g n_q(b) rows of a (sequence, KV head) are taken
+ *             position-major, row = position * g + head, 64 to a workgroup, so the cache is read once per 64 rows whatever g.
+ *             With every n_q(b) = max_seqlen_q = N_q O and L equal fa2_fwd_kvcache_mla's (_mla_fp8's) at the same explicit
+ *             num_splits bit for bit.  GENERIC: everything else.  AUTO: MLA16 where it runs.
+ *
+ * Every error of fa2_fwd_kvcache_varlen and of fa2_fwd_kvcache_mla applies, with their messages.
+ */
+int fa2_fwd_kvcache_mla_varlen(const void *Q, const void *KV, void *O, void *L,
+                               const int64_t q_strides[3], const int64_t kv_strides[4], const int64_t o_strides[3],
+                               int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                               const int32_t *block_table, int64_t block_table_stride,
+                               const float *kv_descale, const int64_t kv_descale_strides[2],
+                               int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                               int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                               int32_t dtype_enum, int32_t kv_dtype_enum,
+                               int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                               void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* What num_splits = 0 resolves to for it: fa2_kvcache_mla_num_splits' rule (enough splits for one workgroup per CU) on the unsplit
+ * workgroup count of the query-tiled latent form, H_kv * min(B * ceil(g * max_seqlen_q / 64), ceil(g * total_q / 64) + B) with
+ * g = H / H_kv, every split at least 8 key tiles (512 keys) of the capacity, for f16 / bf16 at d 576 / d_v 512; every other shape as
+ * fa2_kvcache_varlen_num_splits counts the VALU form. */
+int32_t fa2_kvcache_mla_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                          int32_t d, int32_t d_v, int32_t dtype_enum);
+
+/*
+ * The fused ragged MLA step: fa2_kvcache_mla_append_varlen over cu_seqlens_q (total_new = total_q, max_seqlen_new = max_seqlen_q;
+ * c_new, pe_new packed (total_q, H_kv, d_v) / (total_q, H_kv, d - d_v)), then on the same stream fa2_fwd_kvcache_mla_varlen over the
+ * updated cache with seqlens_out as its cache_seqlens and, with tables, q_rot (packed, contiguous (total_q, H, d)) as its Q; q_rot
+ * may be null without them.  q_pos_per_row is causal || window_left >= 0 || window_right >= 0.  cache_seqlens holds the lengths
+ * BEFORE the append and is not modified.  Every error of both halves comes back before any launch, and a forced
+ * FA2_KVCACHE_VARIANT_MLA16 that cannot run the problem fails before the cache is written.
+ */
+int fa2_fwd_kvcache_mla_varlen_append(const void *Q, void *KV, void *O, void *L,
+                                      const int64_t q_strides[3], const int64_t kv_strides[4], const int64_t o_strides[3],
+                                      int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                      int32_t *seqlens_out, const int32_t *block_table, int64_t block_table_stride,
+                                      const float *kv_descale, const int64_t kv_descale_strides[2],
+                                      const void *c_new, const void *pe_new, const int64_t c_new_strides[3],
+                                      const int64_t pe_new_strides[3],
+                                      const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                                      int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                      void *q_rot, int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q,
+                                      int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                                      int32_t dtype_enum, int32_t kv_dtype_enum,
+                                      int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                                      void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
 /* Bytes of workspace a call with this num_splits needs: 0 for num_splits <= 1, else fp32 partial O of num_splits * B * H * N_q * d
  * elements plus fp32 partial L of num_splits * B * H * N_q. */
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits);
