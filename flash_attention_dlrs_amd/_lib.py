@@ -57,7 +57,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_kvcache_varlen", "fa2_kvcache_varlen_workspace_bytes", "fa2_kvcache_varlen_num_splits",
            "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits",
            "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append",
-           "fa2_fwd_kvcache_mla_varlen", "fa2_kvcache_mla_varlen_num_splits", "fa2_fwd_kvcache_mla_varlen_append")
+           "fa2_fwd_kvcache_mla_varlen", "fa2_kvcache_mla_varlen_num_splits", "fa2_fwd_kvcache_mla_varlen_append",
+           "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
@@ -66,6 +67,9 @@ BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
 KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
 # ... and the latent-cache call (fa2_fwd_kvcache_mla) its own set: FA2_KVCACHE_VARIANT_MLA16 in the d 64 / 128 matrix form's place
 KVCACHE_MLA_VARIANTS = {"auto": 0, "generic": 1, "mla16": 3}
+# ... and the packed forward with a value head size of its own (fa2_fwd_varlen_dv): FA2_VARIANT_MFMA16DV is a variant of it alone
+VARIANT_MFMA16DV = 28
+VARLEN_DV_VARIANTS = {"auto": VARIANT_AUTO, "generic": VARIANT_GENERIC, "mfma16dv": VARIANT_MFMA16DV}
 KVCACHE_MAX_SPLITS = 128
 
 _lib = None
@@ -144,6 +148,12 @@ def lib():
         l.fa2_fwd_varlen_gqa.argtypes = vlg
         l.fa2_fwd_varlen_gqa_variant.restype = ctypes.c_int
         l.fa2_fwd_varlen_gqa_variant.argtypes = vlg + [ctypes.c_int32]
+        # a value head size of its own: d_v after d
+        vld = vl[:12] + [ctypes.c_int32] * 11 + vl[21:]
+        l.fa2_fwd_varlen_dv.restype = ctypes.c_int
+        l.fa2_fwd_varlen_dv.argtypes = vld
+        l.fa2_fwd_varlen_dv_variant.restype = ctypes.c_int
+        l.fa2_fwd_varlen_dv_variant.argtypes = vld + [ctypes.c_int32]
         bvlg = bvl[:21] + [ctypes.c_int32] * 10 + bvl[30:]
         l.fa2_bwd_varlen_gqa.restype = ctypes.c_int
         l.fa2_bwd_varlen_gqa.argtypes = bvlg
@@ -414,6 +424,23 @@ def fa2_fwd_varlen(Q, K, V, O, L, cu_q, cu_k, max_q, max_k, dtype_enum, causal=F
             _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
             cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, d, int(max_q), int(max_k), total_q, K.shape[0],
             int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_fwd_varlen_dv(Q, K, V, O, L, cu_q, cu_k, max_q, max_k, dtype_enum, causal=False, scale=1.0, window=None,
+                      variant=VARIANT_AUTO):
+    """Launch the variable-length forward with a value head size of its own (include/fa2_fwd.h fa2_fwd_varlen_dv_variant) on the
+    current stream of Q's device.  Q (total_q, H, d), K (total_k, H_kv, d), V (total_k, H_kv, d_v), O (total_q, H, d_v), any
+    strides; L (H, total_q) with unit token stride; cu_q / cu_k int32 on the device.  window = (left, right) raw sides or None."""
+    total_q, H, d = Q.shape
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_fwd_varlen_dv_variant(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, K.shape[1], d, V.shape[2], int(max_q), int(max_k), total_q,
+            K.shape[0], int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
     if rc != 0:
         _raise(rc)
 

@@ -311,6 +311,23 @@ int run_fwd(const Fa2Problem &p, Fa2Form form, int variant) {
     default: fa2_set_error(row.other, variant); return FA2_ERR_UNSUPPORTED;
     }
 }
+
+// fa2_fwd_varlen_dv: a checked packed problem with a value head size of its own (p.dv).  The matrix kernel where it runs (d 192 /
+// d_v 128, 16-bit), else the VALU form; at d_v == d AUTO is the varlen table itself and GENERIC the varlen (GQA) kernel itself, so
+// the bits are fa2_fwd_varlen_gqa_variant's.
+int run_fwd_dv(const Fa2Problem &p, Fa2Form form, int variant) {
+    if (variant == FA2_VARIANT_AUTO) {
+        if (p.dv == p.d) return run_fwd(p, form, FA2_VARIANT_AUTO);
+        variant = fa2_mfma16dv_supports(p) ? FA2_VARIANT_MFMA16DV : FA2_VARIANT_GENERIC;
+    }
+    switch (variant) {
+    case FA2_VARIANT_GENERIC: return p.dv == p.d ? run_fwd(p, form, FA2_VARIANT_GENERIC) : fa2_launch_generic_varlen_dv(p, form.g);
+    case FA2_VARIANT_MFMA16DV: return fa2_launch_mfma16dv(p, form.g);
+    default:
+        fa2_set_error("kernel variant %d is not one of fa2_fwd_varlen_dv's (generic and mfma16dv are)", variant);
+        return FA2_ERR_UNSUPPORTED;
+    }
+}
 }  // namespace
 
 int fa2_launch_mfma16h(const Fa2Problem &p, int waves) {
@@ -390,7 +407,7 @@ int fa2_check_gqa(int32_t H, int32_t H_kv) {
 }
 
 namespace {
-// Step 1: the raw arguments of any of the ten forward entry points.  A dense call has 4-element strides {batch, head, token, d}, L's
+// Step 1: the raw arguments of any of the twelve forward entry points.  A dense call has 4-element strides {batch, head, token, d}, L's
 // two and N; a packed one 3-element strides {token, head, d} and the parts behind `packed`.  Window sides of (-1, -1) are no window.
 struct FwdCall {
     const void *Q, *K, *V;
@@ -407,6 +424,8 @@ struct FwdCall {
     const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k = nullptr;
     int32_t max_seqlen_q = 0, max_seqlen_k = 0, total_q = 0, total_k = 0;
     int64_t l_head_stride = 0;
+    bool has_dv = false;  // fa2_fwd_varlen_dv (a packed GQA call): V and O have d_v columns
+    int32_t d_v = 0;
 };
 
 // Step 2: every argument tested, in the one order tests/golden/train_host_calls.json records -- H_kv, then a packed call's pointers
@@ -445,6 +464,13 @@ int check_fwd(const FwdCall &c, Fa2Problem &p, Fa2Form &form) {
         if (c.l_head_stride < 0) {
             fa2_set_error("varlen: negative L head stride");
             return FA2_ERR_BAD_ARG;
+        }
+        if (c.has_dv) {  // (after every check of fa2_fwd_varlen_gqa)
+            if (c.d_v < 1 || c.d_v > 512) {
+                fa2_set_error("varlen: d_v=%d must be in [1, 512]", c.d_v);
+                return FA2_ERR_BAD_ARG;
+            }
+            p.dv = c.d_v;
         }
         form.kind = form.g > 1 ? FA2_FORM_VARLEN_GQA : FA2_FORM_VARLEN;
         return FA2_OK;
@@ -509,7 +535,8 @@ int fwd(const FwdCall &c) {
     Fa2Problem p;
     Fa2Form form;
     const int rc = check_fwd(c, p, form);
-    return rc != FA2_OK ? rc : run_fwd(p, form, c.variant);
+    if (rc != FA2_OK) return rc;
+    return c.has_dv ? run_fwd_dv(p, form, c.variant) : run_fwd(p, form, c.variant);
 }
 
 // What every entry point fills alike (a packed one: 3-element strides, no l_strides, no N); the rest each adds its own.
@@ -624,6 +651,30 @@ int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void
                            hip_stream, variant);
     fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
     c.gqa = true; c.H_kv = H_kv;
+    return fwd(c);
+}
+
+int fa2_fwd_varlen_dv(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                      const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], int64_t l_head_stride,
+                      const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t H_kv, int32_t d,
+                      int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t dtype_enum,
+                      int32_t causal, float scale, int32_t window_left, int32_t window_right, void *hip_stream) {
+    return fa2_fwd_varlen_dv_variant(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, l_head_stride, cu_seqlens_q,
+                                     cu_seqlens_k, B, H, H_kv, d, d_v, max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal,
+                                     scale, window_left, window_right, hip_stream, FA2_VARIANT_AUTO);
+}
+
+int fa2_fwd_varlen_dv_variant(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                              const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                              int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                              int32_t H_kv, int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                              int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                              int32_t window_right, void *hip_stream, int32_t variant) {
+    FwdCall c = dense_call(Q, K, V, O, L, q_strides, k_strides, v_strides, o_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale,
+                           hip_stream, variant);
+    fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
+    c.gqa = true; c.H_kv = H_kv;
+    c.has_dv = true; c.d_v = d_v;
     return fwd(c);
 }
 

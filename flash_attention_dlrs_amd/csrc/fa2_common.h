@@ -20,6 +20,7 @@ struct Fa2Problem {
     // qs/ks/vs/os, ls = {0, head stride of L}; wl / wr are the raw sides (-1 = unbounded), causal as given.
     const int32_t *cu_q, *cu_k;
     int32_t max_q, max_k, total_q, total_k;
+    int32_t dv;  // fa2_fwd_varlen_dv only: V's and O's last axis (d is Q's and K's); 0 in every other call
 };
 
 // Launchers, one per translation unit.  Return FA2_OK / FA2_ERR_*; set_error() on failure.
@@ -51,6 +52,12 @@ int fa2_launch_generic_window_gqa(const Fa2Problem &p, int gqa);
 int fa2_launch_mfma16d_window_gqa(const Fa2Problem &p, int waves, int gqa);
 int fa2_launch_generic_varlen_gqa(const Fa2Problem &p, int gqa);
 int fa2_launch_mfma16d_varlen_gqa(const Fa2Problem &p, int waves, int gqa);
+// A value head size of its own (fa2_fwd_varlen_dv): V and O have p.dv columns, the scores run over p.d.  The VALU form is the varlen
+// GQA instantiation of fa2_generic.hip under FA2_GENERIC_DV (fa2_generic_vgd.hip); the matrix kernel (fa2_mfma16dv.hip) takes
+// d = 192, d_v = 128.  gqa = 1 without grouped heads.
+int fa2_launch_generic_varlen_dv(const Fa2Problem &p, int gqa);
+int fa2_launch_mfma16dv(const Fa2Problem &p, int gqa);
+bool fa2_mfma16dv_supports(const Fa2Problem &p);
 // Validates and normalises a window (include/fa2_fwd.h): FA2_ERR_BAD_ARG for a side < -1.  On FA2_OK *windowed = 0 means the window
 // removes nothing beyond what plain (*causal_out = 0) or causal (*causal_out = 1) attention removes; *windowed = 1 means the band
 // [i - *wl_out, i + *wr_out] with both sides in [0, N - 1] (N - 1 = unbounded), the causal clamp already applied to *wr_out.

@@ -28,7 +28,11 @@
 // bottom-right shifted band (fa2_varlen_band); a row without a visible key gets O = 0, L = +inf.
 // FA2_GENERIC_GQA (fa2_generic_wg.hip, fa2_generic_vg.hip, on top of the windowed or varlen form): grouped-query attention -- K and V
 // have H / gqa heads and query head h reads KV head h / gqa.
-#if defined(FA2_GENERIC_GQA) && defined(FA2_GENERIC_VARLEN)
+// FA2_GENERIC_DV (fa2_generic_vgd.hip, on top of the varlen GQA form): a value head size of its own -- the score loop runs over d,
+// the output columns per lane come from d_v, LDS holds the Q tile at d -- under its own kernel name (fa2_fwd_varlen_dv at d_v != d).
+#if defined(FA2_GENERIC_DV)
+#define fa2_fwd_generic_kernel fa2_fwd_generic_varlen_dv_kernel
+#elif defined(FA2_GENERIC_GQA) && defined(FA2_GENERIC_VARLEN)
 #define fa2_fwd_generic_kernel fa2_fwd_generic_varlen_gqa_kernel
 #elif defined(FA2_GENERIC_GQA)
 #define fa2_fwd_generic_kernel fa2_fwd_generic_window_gqa_kernel
@@ -63,10 +67,13 @@ struct GenericArgs {
 #ifdef FA2_GENERIC_GQA
     int gqa;  // query heads per KV head
 #endif
+#ifdef FA2_GENERIC_DV
+    int dv;  // columns of V and O
+#endif
     double c_log2e;  // scale * log2(e); rounded to float for the fp32 dtypes (kernels.py:92)
 };
 
-// DPL = output columns per lane = ceil(d / 64).
+// DPL = output columns per lane = ceil(d / 64) (FA2_GENERIC_DV: ceil(d_v / 64)).
 template <class E, int DPL>
 __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const GenericArgs a) {
     using A = typename E::acc_t;
@@ -112,6 +119,11 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
     const int64_t v_off = b * a.vs[0] + h * a.vs[1];
     const int64_t o_off = b * a.os[0] + h * a.os[1];
     (void)Qb;
+#endif
+#ifdef FA2_GENERIC_DV
+    const int dv = a.dv;
+#else
+    const int dv = d;  // V's and O's columns
 #endif
 
     // Q tile -> LDS (rows past N are clamped; their results are never stored).
@@ -207,7 +219,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d) {
+                if (x < dv) {
                     const A v = E::load(a.V, vb + (int64_t)x * a.vs[3]);
 #pragma unroll
                     for (int r = 0; r < kRowsPerWave; ++r) o[r][cc] += pr[r] * v;  // :98
@@ -227,7 +239,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d)
+                if (x < dv)
                     E::store(a.O, o_off + (int64_t)row * a.os[2] + (int64_t)x * a.os[3], l > 0 ? o[r][cc] / l : (A)0);
             }
             if (lane == 0)
@@ -236,7 +248,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_fwd_generic_kernel(const Gene
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
-                if (x < d)
+                if (x < dv)
                     E::store(a.O, o_off + (int64_t)row * a.os[2] + (int64_t)x * a.os[3], o[r][cc] / l);  // :105,:107
             }
             if (lane == 0)
@@ -254,7 +266,11 @@ template <class E> int launch_e(const Fa2Problem &p, const GenericArgs &a) {
 #endif
     const size_t smem = sizeof(typename E::acc_t) * ((size_t)kBr * p.d + (size_t)kWaves * kRowsPerWave * kBc);
     // output columns per lane: ceil(d / 64) rounded up to the next instantiation (columns >= d are skipped in the kernel)
+#ifdef FA2_GENERIC_DV
+    const int dpl = (p.dv + 63) / 64;
+#else
     const int dpl = (p.d + 63) / 64;
+#endif
     if (dpl <= 1) hipLaunchKernelGGL((fa2_fwd_generic_kernel<E, 1>), grid, block, smem, p.stream, a);
     else if (dpl <= 2) hipLaunchKernelGGL((fa2_fwd_generic_kernel<E, 2>), grid, block, smem, p.stream, a);
     else if (dpl <= 4) hipLaunchKernelGGL((fa2_fwd_generic_kernel<E, 4>), grid, block, smem, p.stream, a);
@@ -273,7 +289,9 @@ template <class E> int launch_e(const Fa2Problem &p, const GenericArgs &a) {
 
 }  // namespace
 
-#if defined(FA2_GENERIC_GQA) && defined(FA2_GENERIC_VARLEN)
+#if defined(FA2_GENERIC_DV)
+int fa2_launch_generic_varlen_dv(const Fa2Problem &p, int gqa) {
+#elif defined(FA2_GENERIC_GQA) && defined(FA2_GENERIC_VARLEN)
 int fa2_launch_generic_varlen_gqa(const Fa2Problem &p, int gqa) {
 #elif defined(FA2_GENERIC_GQA)
 int fa2_launch_generic_window_gqa(const Fa2Problem &p, int gqa) {
@@ -304,6 +322,9 @@ int fa2_launch_generic(const Fa2Problem &p) {
     a.c_log2e = (double)p.scale * FA2_LOG2E;
 #ifdef FA2_GENERIC_GQA
     a.gqa = gqa;
+#endif
+#ifdef FA2_GENERIC_DV
+    a.dv = p.dv;
 #endif
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);

@@ -433,6 +433,36 @@ def varlen_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen
     return O, L
 
 
+def check_varlen_dv_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window):
+    """check_varlen_args with the V rule relaxed for a value head size of its own (fa2_fwd_varlen_dv): V.shape[:2] == K.shape[:2],
+    any last axis in [1, 512]."""
+    if Q.dim() != 3 or K.dim() != 3 or V.dim() != 3:
+        raise ValueError(f"varlen: Q, K, V must be (total, H, d), got {tuple(Q.shape)}, {tuple(K.shape)}, {tuple(V.shape)}")
+    if V.shape[:2] != K.shape[:2] or not 1 <= V.shape[2] <= 512:
+        raise ValueError(f"varlen: V must be (total_k, H_kv, d_v) with K's total_k and H_kv and d_v in [1, 512], got "
+                         f"K {tuple(K.shape)}, V {tuple(V.shape)}")
+    check_varlen_args(Q, K, K, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window)  # (every rule but V's shape)
+    if V.dtype != K.dtype:
+        raise ValueError("varlen: Q, K, V must have the same dtype")
+
+
+def mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, causal=False, scale=1.0, window=None,
+                        variant="auto"):
+    """(O, L) of a packed batch with a value head size of its own (fa2_fwd_varlen_dv; un-absorbed MLA prefill at d 192 / d_v 128):
+    O (total_q, H, d_v) contiguous, L (H, total_q) in the I/O dtype.  The tensors go to the library as they are, strides included:
+    no head-size padding under any variant."""
+    _check_varlen_device(Q, K, V)
+    check_varlen_dv_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window)
+    if variant not in _lib.VARLEN_DV_VARIANTS:
+        raise ValueError(f"mla prefill: variant must be one of {sorted(_lib.VARLEN_DV_VARIANTS)}, got {variant!r}")
+    total_q, H, _ = Q.shape
+    O = torch.empty(total_q, H, V.shape[2], dtype=Q.dtype, device=Q.device)
+    L = torch.empty(H, total_q, dtype=Q.dtype, device=Q.device)
+    _lib.fa2_fwd_varlen_dv(Q, K, V, O, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, convert_triton_dtype(Q.dtype),
+                           causal=causal, scale=scale, window=window, variant=_lib.VARLEN_DV_VARIANTS[variant])
+    return O, L
+
+
 def varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, causal=False, scale=1.0,
                     window=None, variant="auto"):
     """(dQ, dK, dV) of a packed batch from the forward's O and L (fa2_bwd_varlen): the MFMA kernel for f16 / bf16 at

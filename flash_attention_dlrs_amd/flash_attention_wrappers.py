@@ -7,8 +7,8 @@ import torch
 
 from . import _lib, autotune
 from .flash_attention_torch import (MIN_TENSOR_SIZE, backward_native, convert_triton_dtype, forward_head_size,
-                                    gqa_kv_heads, next_power_of_2, normalize_window, pad_last_dim, varlen_backward, varlen_forward,
-                                    window_head_size)
+                                    gqa_kv_heads, mla_prefill_forward, next_power_of_2, normalize_window, pad_last_dim,
+                                    varlen_backward, varlen_forward, window_head_size)
 
 
 def flash_attention_forward(Q, K, V, dev, *, causal=False, scale=1.0, variant="auto", window=None):
@@ -118,6 +118,20 @@ def flash_attention_varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_
         raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
     return varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
                            scale=scale, window=window, variant=variant)
+
+
+def flash_attention_mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dev, *, causal=False,
+                                        scale=1.0, window=None, variant="auto"):
+    """Packed forward with a value head size of its own (include/fa2_fwd.h fa2_fwd_varlen_dv) -> (O, L): un-absorbed MLA prefill,
+    Q (total_q, H, d), K (total_k, H_kv, d), V (total_k, H_kv, d_v) with H_kv dividing H, cu_seqlens int32 (B + 1) on Q's device;
+    O (total_q, H, d_v) contiguous, L (H, total_q).  Strided inputs are passed through -- the two views of a fused (total, H,
+    192 + 128) up-projection buffer are a valid K and V -- and no head size is padded: "auto" runs the matrix kernel for f16 / bf16
+    at d 192 / d_v 128 and the VALU kernel on anything else, "generic" and "mfma16dv" force one (_lib.VARLEN_DV_VARIANTS).
+    Forward only."""
+    if Q.device != torch.device(dev):
+        raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
+    return mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal, scale=scale,
+                               window=window, variant=variant)
 
 
 FP8_CACHE_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)

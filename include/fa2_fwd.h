@@ -227,6 +227,42 @@ int fa2_fwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, void
                                int32_t window_right, void *hip_stream, int32_t variant);
 
 /*
+ * Packed attention with a value head size of its own (un-absorbed MLA prefill: d = 192 = 128 "nope" + 64 rotary columns,
+ * d_v = 128).  Forward only.
+ *
+ *   fa2_fwd_varlen_dv(_variant): the arguments of fa2_fwd_varlen_gqa(_variant) with d_v after d.  Q is (total_q, H, d), K is
+ *   (total_k, H_kv, d), V is (total_k, H_kv, d_v), O is (total_q, H, d_v), L is (H, total_q); strides in elements, three per
+ *   tensor.  d and d_v lie in [1, 512], H % H_kv == 0.  Offsets and their clamping, the bottom-right causal mask and window, empty
+ *   rows (O = 0, L = +inf), zero-length sequences, tokens outside every sequence (not written), L's definition and dtype and the
+ *   64-bit per-sequence base pointers are fa2_fwd_varlen's.  f64, f32, f16, bf16; fp8 returns FA2_ERR_UNSUPPORTED.
+ *
+ * Every error of fa2_fwd_varlen_gqa applies, from the same checks in the same order; then FA2_ERR_BAD_ARG ("d_v" in the message)
+ * for d_v outside [1, 512], before any launch.
+ * Variants of this entry point only: FA2_VARIANT_AUTO (MFMA16DV where it runs, else GENERIC; at d_v == d the table of
+ * fa2_fwd_varlen_gqa), FA2_VARIANT_GENERIC (every dtype above, any strides, any d and d_v; at d_v == d the kernel and the bits of
+ * fa2_fwd_varlen_gqa_variant(GENERIC)) and FA2_VARIANT_MFMA16DV (f16 / bf16, d == 192, d_v == 128, unit d-stride, 16-byte aligned
+ * rows of Q, K, V and O, scale > 0, max_seqlen_k x row stride below 2 GiB).  A forced MFMA16DV on a problem it cannot take, and any
+ * other forced variant, return FA2_ERR_UNSUPPORTED.
+ */
+#define FA2_VARIANT_MFMA16DV 28 /* fa2_fwd_varlen_dv only: f16/bf16, d = 192, d_v = 128; MFMA16D_W4's tile with a two-image K unit */
+
+int fa2_fwd_varlen_dv(const void *Q, const void *K, const void *V, void *O, void *L,
+                      const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                      const int64_t o_strides[3], int64_t l_head_stride,
+                      const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t H_kv,
+                      int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                      int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                      void *hip_stream);
+
+int fa2_fwd_varlen_dv_variant(const void *Q, const void *K, const void *V, void *O, void *L,
+                              const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                              const int64_t o_strides[3], int64_t l_head_stride,
+                              const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                              int32_t H_kv, int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k,
+                              int32_t total_q, int32_t total_k, int32_t dtype_enum, int32_t causal, float scale,
+                              int32_t window_left, int32_t window_right, void *hip_stream, int32_t variant);
+
+/*
  * Decode attention over a padded KV cache, split-KV (flash-decoding).  Forward only.
  *
  *   Shapes.   Q, O are (B, H, N_q, d), L is (B, H, N_q); K, V are (B, H_kv, S_k, d): S_k is the cache CAPACITY.  All strides are
