@@ -4,7 +4,10 @@ every group size, mask and split count; bit-identities at equal explicit num_spl
 batch, the uniform batch against flash_attention_mla_decode_forward, paged against contiguous, fp8 at descale None against the
 converted cache, the same call twice); stale rows, unused pages and a poisoned workspace that must not reach the output; canaries
 around O, L and the workspace, packed rows outside every sequence untouched, inputs unchanged; fp8 caches with descales; the fused
-ragged step against the append followed by the attention; strided and misaligned Q."""
+ragged step against the append followed by the attention; strided and misaligned Q.  On the sequences of more than one key tile
+or split, O is about 0.5 / sqrt(n) and these absolute bars cannot see a dropped 64-key tile, a band one key off, a wrong split edge
+or a row answered with its neighbour's keys, and the bit-identities run the same row map on both sides:
+tests/test_decode_mla_varlen_probe_gpu.py pins which keys each packed row reads, to one output ulp."""
 import functools
 import math
 
