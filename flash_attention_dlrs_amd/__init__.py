@@ -5,13 +5,14 @@ Triton launch they make is replaced by the C-ABI call fa2_fwd() of libfa2_hip.so
 a hand-written HIP/CDNA4 kernel library.  There is no CPU fallback: without the built library, or on
 non-GPU tensors, calls fail loudly.
 """
-from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttentionDeterministic, FlashAttentionVarlen,
-                                    convert_triton_dtype, gqa_kv_heads, varlen_mask)
+from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttentionDeterministic, FlashAttentionMLAPrefill,
+                                    FlashAttentionVarlen, convert_triton_dtype, gqa_kv_heads, varlen_mask)
 from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_attention_backward, flash_attention_forward,
                                        flash_attention_kvcache_forward, flash_attention_mla_decode_forward,
                                        flash_attention_varlen_backward, check_mla_append_args, mla_kvcache_append,
                                        mla_kvcache_append_varlen, check_mla_varlen_args,
-                                       flash_attention_mla_varlen_decode_forward, flash_attention_mla_prefill_forward,
+                                       flash_attention_mla_varlen_decode_forward, flash_attention_mla_prefill_backward,
+                                       flash_attention_mla_prefill_forward,
                                        flash_attention_varlen_forward, flash_attention_varlen_kvcache_forward, kvcache_append,
                                        kvcache_append_varlen, quantize_kv_cache)
 
@@ -21,4 +22,4 @@ __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarle
            "varlen_mask", "gqa_kv_heads", "kvcache_append", "apply_rotary", "flash_attention_varlen_kvcache_forward",
            "kvcache_append_varlen", "flash_attention_mla_decode_forward", "mla_kvcache_append", "mla_kvcache_append_varlen",
            "check_mla_append_args", "flash_attention_mla_varlen_decode_forward", "check_mla_varlen_args",
-           "flash_attention_mla_prefill_forward"]
+           "flash_attention_mla_prefill_forward", "flash_attention_mla_prefill_backward", "FlashAttentionMLAPrefill"]

@@ -61,8 +61,11 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
-               "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant")
+               "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
+               "fa2_bwd_varlen_dv", "fa2_bwd_varlen_dv_variant")
 BWD_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2, "mfma32": 3}
+# ... and the packed backward with a value head size of its own (fa2_bwd_varlen_dv): FA2_BWD_VARIANT_MFMA16DV is a variant of it alone
+BWD_VARLEN_DV_VARIANTS = {"auto": 0, "generic": 1, "mfma16dv": 4}
 # KV-cache decode (fa2_fwd_kvcache) has its own small variant enum, FA2_KVCACHE_VARIANT_*
 KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
 # ... and the latent-cache call (fa2_fwd_kvcache_mla) its own set: FA2_KVCACHE_VARIANT_MLA16 in the d 64 / 128 matrix form's place
@@ -159,6 +162,11 @@ def lib():
         l.fa2_bwd_varlen_gqa.argtypes = bvlg
         l.fa2_bwd_varlen_gqa_variant.restype = ctypes.c_int
         l.fa2_bwd_varlen_gqa_variant.argtypes = bvlg + [ctypes.c_int32]
+        bvld = bvl[:21] + [ctypes.c_int32] * 11 + bvl[30:]  # d_v after d
+        l.fa2_bwd_varlen_dv.restype = ctypes.c_int
+        l.fa2_bwd_varlen_dv.argtypes = bvld
+        l.fa2_bwd_varlen_dv_variant.restype = ctypes.c_int
+        l.fa2_bwd_varlen_dv_variant.argtypes = bvld + [ctypes.c_int32]
         # KV-cache decode: 4-element strides, L strides, cache_seqlens, B H H_kv N_q S_k d dtype causal, scale, window, num_splits,
         # workspace + its size, stream
         kvc = [vp] * 5 + [i64p] * 5 + [vp] + [ctypes.c_int32] * 8 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, vp]
@@ -470,6 +478,25 @@ def fa2_bwd_varlen(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_q, cu_k, max_q, max_k, d
             *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), L.stride(0),
             cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, d, int(max_q), int(max_k), total_q, K.shape[0],
             int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
+    if rc != 0:
+        _raise(rc)
+
+
+def fa2_bwd_varlen_dv(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_q, cu_k, max_q, max_k, dtype_enum, causal=False, scale=1.0,
+                      window=None, variant=0):
+    """Launch the variable-length backward with a value head size of its own (include/fa2_bwd.h fa2_bwd_varlen_dv_variant).
+    Q, dQ (total_q, H, d), K, dK (total_k, H_kv, d), V, dV (total_k, H_kv, d_v), O, dO (total_q, H, d_v), any strides; L (H, total_q)
+    with unit token stride; D: contiguous scratch of 2 * H * total_q float32 (float64 for fp64)."""
+    total_q, H, d = Q.shape
+    assert D.is_contiguous() and D.numel() == 2 * H * total_q
+    wl, wr = (-1, -1) if window is None else (int(w) for w in window)
+    with torch.cuda.device(Q.device):
+        rc = lib().fa2_bwd_varlen_dv_variant(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), L.data_ptr(),
+            dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(), D.data_ptr(),
+            *(_i64(t.stride()) for t in (Q, K, V, O, dO, dQ, dK, dV)), L.stride(0),
+            cu_q.data_ptr(), cu_k.data_ptr(), cu_q.numel() - 1, H, K.shape[1], d, V.shape[2], int(max_q), int(max_k), total_q,
+            K.shape[0], int(dtype_enum), int(bool(causal)), float(scale), wl, wr, _raw_stream(Q.device.index), int(variant))
     if rc != 0:
         _raise(rc)
 

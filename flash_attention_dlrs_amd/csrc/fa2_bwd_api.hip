@@ -8,7 +8,8 @@ namespace {
 
 bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 
-int validate(const Fa2BwdProblem &p) {
+// any_d: fa2_bwd_varlen_dv, whose d follows the forward call's rule (nothing pads it)
+int validate(const Fa2BwdProblem &p, bool any_d = false) {
     if (!p.Q || !p.K || !p.V || !p.O || !p.dO || !p.L || !p.dQ || !p.dK || !p.dV || !p.D) {
         fa2_set_error("null tensor pointer");
         return FA2_ERR_BAD_ARG;
@@ -25,7 +26,12 @@ int validate(const Fa2BwdProblem &p) {
         fa2_set_error("backward: dtype enum %d is not supported (f64, f32, f16, bf16)", p.dtype);
         return FA2_ERR_UNSUPPORTED;
     }
-    if (!is_pow2(p.d) || p.d < 16 || p.d > 512) {  // the glue pads d exactly as in the forward (torch.py:95-99)
+    if (any_d) {
+        if (p.d > 512) {
+            fa2_set_error("d=%d must be in [1, 512]", p.d);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    } else if (!is_pow2(p.d) || p.d < 16 || p.d > 512) {  // the glue pads d exactly as in the forward (torch.py:95-99)
         fa2_set_error("d=%d must be a power of two in [16, 512] (pad on the host as the reference does)", p.d);
         return FA2_ERR_UNSUPPORTED;
     }
@@ -82,7 +88,18 @@ int run_bwd(const Fa2BwdProblem &p, Fa2Form form, int variant) {
     return dense ? FA2_ERR_BAD_ARG : FA2_ERR_UNSUPPORTED;
 }
 
-// Step 1: the raw arguments of any of the ten backward entry points, as FwdCall (fa2_api.hip) holds the forward's.  `strides`: of
+// fa2_bwd_varlen_dv: a checked packed problem with a value head size of its own (p.dv).  At d_v == d it is the varlen (GQA) call
+// itself, through the table above; else the matrix kernel where it runs (d 192 / d_v 128, 16-bit) or the VALU form.
+int run_bwd_dv(const Fa2BwdProblem &p, Fa2Form form, int variant) {
+    if (p.dv == p.d) return run_bwd(p, form, variant);
+    if (variant == FA2_BWD_VARIANT_AUTO) variant = fa2_bwd_mfma16dv_supports(p) ? FA2_BWD_VARIANT_MFMA16DV : FA2_BWD_VARIANT_GENERIC;
+    if (variant == FA2_BWD_VARIANT_GENERIC) return fa2_bwd_launch_generic_varlen_dv(p, form.g);
+    if (variant == FA2_BWD_VARIANT_MFMA16DV) return fa2_bwd_launch_mfma16dv(p, form.g);
+    fa2_set_error("backward kernel variant %d is not one of fa2_bwd_varlen_dv's at d_v != d (generic and mfma16dv are)", variant);
+    return FA2_ERR_UNSUPPORTED;
+}
+
+// Step 1: the raw arguments of any of the twelve backward entry points, as FwdCall (fa2_api.hip) holds the forward's.  `strides`: of
 // Q, K, V, O, dO, dQ, dK, dV in that order, 4 elements each, 3 in a packed call.
 struct BwdCall {
     const void *Q, *K, *V, *O, *dO, *L;
@@ -99,6 +116,8 @@ struct BwdCall {
     const int32_t *cu_seqlens_q = nullptr, *cu_seqlens_k = nullptr;
     int32_t max_seqlen_q = 0, max_seqlen_k = 0, total_q = 0, total_k = 0;
     int64_t l_head_stride = 0;
+    bool has_dv = false;  // fa2_bwd_varlen_dv (a packed GQA call): V, O, dO, dV have d_v columns
+    int32_t d_v = 0;
 };
 
 // Step 2: check_fwd's order (tests/golden/train_host_calls.json), with the packed call's own: its stride pointers, sizes and L's
@@ -133,7 +152,14 @@ int check_bwd(const BwdCall &c, Fa2BwdProblem &p, Fa2Form &form) {
         for (int t = 0; t < 8; ++t) fa2_packed_strides4(c.strides[t], strides[t]);
         fa2_set_packed(c, p);
         form.kind = form.g > 1 ? FA2_FORM_VARLEN_GQA : FA2_FORM_VARLEN;
-        return validate(p);
+        rc = validate(p, c.has_dv);
+        if (rc != FA2_OK || !c.has_dv) return rc;
+        if (c.d_v < 1 || c.d_v > 512) {  // (after every check of fa2_bwd_varlen_gqa, as check_fwd orders it)
+            fa2_set_error("varlen backward: d_v=%d must be in [1, 512]", c.d_v);
+            return FA2_ERR_BAD_ARG;
+        }
+        p.dv = c.d_v;
+        return FA2_OK;
     }
     Fa2Window w;
     int rc = fa2_window_of(c.N, c.causal, c.window_left, c.window_right, w);
@@ -164,7 +190,8 @@ int bwd(const BwdCall &c) {
     Fa2BwdProblem p;
     Fa2Form form;
     const int rc = check_bwd(c, p, form);
-    return rc != FA2_OK ? rc : run_bwd(p, form, c.variant);
+    if (rc != FA2_OK) return rc;
+    return c.has_dv ? run_bwd_dv(p, form, c.variant) : run_bwd(p, form, c.variant);
 }
 
 // What every entry point fills alike (a packed one: 3-element strides, no l_strides, no N); the rest each adds its own.
@@ -304,6 +331,36 @@ int fa2_bwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, cons
                            dk_strides, dv_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale, hip_stream, variant);
     fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
     c.gqa = true; c.H_kv = H_kv;
+    return bwd(c);
+}
+
+int fa2_bwd_varlen_dv(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L, void *dQ,
+                      void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                      const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                      const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                      int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                      int32_t H_kv, int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                      int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                      void *hip_stream) {
+    return fa2_bwd_varlen_dv_variant(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides,
+                                     dq_strides, dk_strides, dv_strides, l_head_stride, cu_seqlens_q, cu_seqlens_k, B, H, H_kv, d, d_v,
+                                     max_seqlen_q, max_seqlen_k, total_q, total_k, dtype_enum, causal, scale, window_left,
+                                     window_right, hip_stream, FA2_BWD_VARIANT_AUTO);
+}
+
+int fa2_bwd_varlen_dv_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                              void *dQ, void *dK, void *dV, void *D, const int64_t q_strides[3], const int64_t k_strides[3],
+                              const int64_t v_strides[3], const int64_t o_strides[3], const int64_t do_strides[3],
+                              const int64_t dq_strides[3], const int64_t dk_strides[3], const int64_t dv_strides[3],
+                              int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B,
+                              int32_t H, int32_t H_kv, int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k,
+                              int32_t total_q, int32_t total_k, int32_t dtype_enum, int32_t causal, float scale,
+                              int32_t window_left, int32_t window_right, void *hip_stream, int32_t variant) {
+    BwdCall c = dense_call(Q, K, V, O, dO, L, dQ, dK, dV, D, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+                           dk_strides, dv_strides, nullptr, B, H, 0, d, dtype_enum, causal, scale, hip_stream, variant);
+    fa2_call_packed(c, l_head_stride, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, total_q, total_k, window_left, window_right);
+    c.gqa = true; c.H_kv = H_kv;
+    c.has_dv = true; c.d_v = d_v;
     return bwd(c);
 }
 

@@ -18,6 +18,7 @@ struct Fa2BwdProblem {
     // L}, raw window sides; D is the scratch of 2 * H * total_q accumulators ([2][H][total_q]).
     const int32_t *cu_q, *cu_k;
     int32_t max_q, max_k, total_q, total_k;
+    int32_t dv;  // fa2_bwd_varlen_dv: the last axis of V, O, dO, dV (Q, K, dQ, dK keep d); 0 in every other call
 };
 
 int fa2_bwd_launch_generic(const Fa2BwdProblem &p);
@@ -33,5 +34,10 @@ int fa2_bwd_launch_mfma16_window_gqa(const Fa2BwdProblem &p, int gqa);
 int fa2_bwd_launch_generic_varlen_gqa(const Fa2BwdProblem &p, int gqa);
 int fa2_bwd_launch_mfma16_varlen_gqa(const Fa2BwdProblem &p, int gqa);
 bool fa2_bwd_mfma16_supports(const Fa2BwdProblem &p);
+// A value head size of its own (fa2_bwd_varlen_dv, p.dv != p.d): the varlen GQA VALU form over any (d, d_v), and the matrix kernel
+// at d 192 / d_v 128 (fa2_bwd_mfma16dv.hip)
+int fa2_bwd_launch_generic_varlen_dv(const Fa2BwdProblem &p, int gqa);
+int fa2_bwd_launch_mfma16dv(const Fa2BwdProblem &p, int gqa);
+bool fa2_bwd_mfma16dv_supports(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma32(const Fa2BwdProblem &p);
 bool fa2_bwd_mfma32_supports(const Fa2BwdProblem &p);

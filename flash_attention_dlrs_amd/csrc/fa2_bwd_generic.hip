@@ -31,7 +31,13 @@
 // attention -- K, V, dK, dV have H / gqa heads.  MODE 1 (grid z = query head h) reads KV head h / gqa; MODE 0 (grid z = KV head k)
 // sweeps the queries of its g query heads k * gqa ... k * gqa + gqa - 1 in turn into the same accumulators and stores once: the
 // group sum of dK / dV without atomics, in a fixed order.
-#if defined(FA2_BWD_GENERIC_GQA) && defined(FA2_BWD_GENERIC_VARLEN)
+// FA2_BWD_GENERIC_DV (fa2_bwd_generic_vgd.hip, on top of the varlen GQA form): a value head size of its own (fa2_bwd_varlen_dv) -- V,
+// O, dO and dV have a.dv columns: the second owned / swept operand, the dV accumulator, dP = dO V^T and D = rowsum(dO * O) run
+// over dv, everything on the Q / K / dQ / dK side over d.
+#if defined(FA2_BWD_GENERIC_DV)
+#define bwd_main_kernel bwd_main_varlen_dv_kernel
+#define bwd_D_kernel bwd_D_varlen_dv_kernel
+#elif defined(FA2_BWD_GENERIC_GQA) && defined(FA2_BWD_GENERIC_VARLEN)
 #define bwd_main_kernel bwd_main_varlen_gqa_kernel
 #define bwd_D_kernel bwd_D_varlen_gqa_kernel
 #elif defined(FA2_BWD_GENERIC_GQA)
@@ -65,6 +71,9 @@ struct GArgs {
 #ifdef FA2_BWD_GENERIC_GQA
     int gqa;  // query heads per KV head
 #endif
+#ifdef FA2_BWD_GENERIC_DV
+    int dv;  // columns of V, O, dO, dV
+#endif
     double c_log2e, scale;
 };
 
@@ -84,7 +93,11 @@ template <typename E> __global__ __launch_bounds__(256) void bwd_D_kernel(const 
     const int64_t o0 = b * a.os[0] + h * a.os[1] + n * a.os[2], g0 = b * a.dos[0] + h * a.dos[1] + n * a.dos[2];
 #endif
     A s = 0;
+#ifdef FA2_BWD_GENERIC_DV
+    for (int x = 0; x < a.dv; ++x) s += E::load(a.O, o0 + x * a.os[3]) * E::load(a.dO, g0 + x * a.dos[3]);
+#else
     for (int x = 0; x < a.d; ++x) s += E::load(a.O, o0 + x * a.os[3]) * E::load(a.dO, g0 + x * a.dos[3]);
+#endif
     ((A *)a.D)[r] = s;
 }
 
@@ -97,6 +110,16 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
 #else
     const int TB = a.TB, d = a.d, ld = d + 1, N = a.N, tid = threadIdx.x;
 #endif
+#ifdef FA2_BWD_GENERIC_DV
+    const int dv = a.dv, ldv = dv + 1;  // the second operands and dV: dv columns
+    A *own0 = (A *)smem_raw;        // owner rows, first operand  (MODE 0: K_j ; MODE 1: Q_i)
+    A *own1 = own0 + TB * ld;       //             second operand (MODE 0: V_j ; MODE 1: dO_i)
+    A *swp0 = own1 + TB * ldv;      // swept rows                 (MODE 0: Q_i ; MODE 1: K_j)
+    A *swp1 = swp0 + TB * ld;       //                            (MODE 0: dO_i; MODE 1: V_j)
+    A *acc0 = swp1 + TB * ldv;      // outputs: MODE 0 dK, MODE 1 dQ
+    A *acc1 = acc0 + TB * ld;       //          MODE 0 dV
+    A *Ps = acc1 + TB * ldv;        // [query r][key c]
+#else
     A *own0 = (A *)smem_raw;        // owner rows, first operand  (MODE 0: K_j ; MODE 1: Q_i)
     A *own1 = own0 + TB * ld;       //             second operand (MODE 0: V_j ; MODE 1: dO_i)
     A *swp0 = own1 + TB * ld;       // swept rows                 (MODE 0: Q_i ; MODE 1: K_j)
@@ -104,6 +127,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
     A *acc0 = swp1 + TB * ld;       // outputs: MODE 0 dK, MODE 1 dQ
     A *acc1 = acc0 + TB * ld;       //          MODE 0 dV
     A *Ps = acc1 + TB * ld;         // [query r][key c]
+#endif
     A *dSs = Ps + TB * TB;
     A *Lq = dSs + TB * TB;          // per query row of the current pairing
     A *Dq = Lq + TB;
@@ -155,13 +179,23 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
             dst[r * ld + x] = row < n ? E::load(src, base + (int64_t)row * st[2] + x * st[3]) : (A)0;
         }
     };
+#ifdef FA2_BWD_GENERIC_DV
+    auto load_rows_v = [&](A *dst, const void *src, int64_t base, const int64_t *st, int row0, int n) {  // load_rows over dv columns
+        for (int e = tid; e < TB * dv; e += 256) {
+            const int r = e / dv, x = e % dv, row = row0 + r;
+            dst[r * ldv + x] = row < n ? E::load(src, base + (int64_t)row * st[2] + x * st[3]) : (A)0;
+        }
+    };
+#else
+#define load_rows_v load_rows
+#endif
     const int own_row0 = blk * TB;
     if (MODE == 0) {
         load_rows(own0, a.K, kb, a.ks, own_row0, NO);
-        load_rows(own1, a.V, vb, a.vs, own_row0, NO);
+        load_rows_v(own1, a.V, vb, a.vs, own_row0, NO);
     } else {
         load_rows(own0, a.Q, qb, a.qs, own_row0, NO);
-        load_rows(own1, a.dO, gb, a.dos, own_row0, NO);
+        load_rows_v(own1, a.dO, gb, a.dos, own_row0, NO);
         if (tid < TB) {
             const int row = own_row0 + tid;
             Lq[tid] = row < NO ? E::load(a.L, lb + row) : (A)0;
@@ -191,7 +225,12 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         }
     }
 #endif
+#ifdef FA2_BWD_GENERIC_DV
+    for (int e = tid; e < TB * ld; e += 256) acc0[e] = (A)0;
+    for (int e = tid; e < TB * ldv; e += 256) acc1[e] = (A)0;
+#else
     for (int e = tid; e < TB * ld; e += 256) acc0[e] = acc1[e] = (A)0;
+#endif
     __syncthreads();
 
 #if defined(FA2_BWD_GENERIC_VARLEN)
@@ -235,7 +274,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
 #ifdef FA2_BWD_GENERIC_VARLEN
         if (MODE == 0) {
             load_rows(swp0, a.Q, qb, a.qs, sw_row0, NS);
-            load_rows(swp1, a.dO, gb, a.dos, sw_row0, NS);
+            load_rows_v(swp1, a.dO, gb, a.dos, sw_row0, NS);
             if (tid < TB) {
                 const int row = sw_row0 + tid;
                 Lq[tid] = row < NS ? Lc[row] : (A)0;
@@ -243,7 +282,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
             }
         } else {
             load_rows(swp0, a.K, kb, a.ks, sw_row0, NS);
-            load_rows(swp1, a.V, vb, a.vs, sw_row0, NS);
+            load_rows_v(swp1, a.V, vb, a.vs, sw_row0, NS);
         }
 #else
         if (MODE == 0) {
@@ -263,6 +302,13 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         if (tid < TB * TB) {  // one (query r, key c) pair per thread
             const int r = tid / TB, c = tid % TB;
             const A *qrow = (MODE == 0 ? swp0 : own0) + r * ld, *krow = (MODE == 0 ? own0 : swp0) + c * ld;
+#ifdef FA2_BWD_GENERIC_DV
+            const A *grow = (MODE == 0 ? swp1 : own1) + r * ldv, *vrow = (MODE == 0 ? own1 : swp1) + c * ldv;
+            const int qi = (MODE == 0 ? sw_row0 : own_row0) + r, kj = (MODE == 0 ? own_row0 : sw_row0) + c;
+            A s = 0, dp = 0;
+            for (int x = 0; x < d; ++x) s += qrow[x] * krow[x];     // kernels.py:283
+            for (int x = 0; x < dv; ++x) dp += grow[x] * vrow[x];  // :289
+#else
             const A *grow = (MODE == 0 ? swp1 : own1) + r * ld, *vrow = (MODE == 0 ? own1 : swp1) + c * ld;
             const int qi = (MODE == 0 ? sw_row0 : own_row0) + r, kj = (MODE == 0 ? own_row0 : sw_row0) + c;
             A s = 0, dp = 0;
@@ -270,6 +316,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
                 s += qrow[x] * krow[x];   // kernels.py:283
                 dp += grow[x] * vrow[x];  // :289
             }
+#endif
             A p = exp2_acc<A>(s * c_s - Lq[r]);  // :285
 #if defined(FA2_BWD_GENERIC_VARLEN)
             if (qi >= NQ || kj >= NK || kj < qi - wl || kj > qi + wr) p = 0;
@@ -287,6 +334,24 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
             for (int c = 0; c < TB; ++c) t += Ps[tid * TB + c];
             Rs[tid] += t;
         }
+#ifdef FA2_BWD_GENERIC_DV
+        for (int e = tid; e < TB * d; e += 256) {
+            const int o = e / d, x = e % d;
+            A t = 0;  // MODE 0, o = key c: dK[c] += sum_r dS[r][c] Q[r] (:293); MODE 1, o = query r: dQ[r] += sum_c dS[r][c] K[c] (:317)
+            if (MODE == 0)
+                for (int r = 0; r < TB; ++r) t += dSs[r * TB + o] * swp0[r * ld + x];
+            else
+                for (int c = 0; c < TB; ++c) t += dSs[o * TB + c] * swp0[c * ld + x];
+            acc0[o * ld + x] += t;
+        }
+        if (MODE == 0)
+            for (int e = tid; e < TB * dv; e += 256) {  // dV[c] += sum_r P[r][c] dO[r]   (:287)
+                const int o = e / dv, x = e % dv;
+                A av = 0;
+                for (int r = 0; r < TB; ++r) av += E::round(Ps[r * TB + o]) * swp1[r * ldv + x];
+                acc1[o * ldv + x] += av;
+            }
+#else
         for (int e = tid; e < TB * d; e += 256) {
             const int o = e / d, x = e % d;
             if (MODE == 0) {  // o = key c:  dV[c] += sum_r P[r][c] dO[r],  dK[c] += sum_r dS[r][c] Q[r]   (:287, :293)
@@ -303,6 +368,7 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
                 acc0[o * ld + x] += aq;
             }
         }
+#endif
         __syncthreads();
     }
 #ifdef FA2_BWD_GENERIC_GQA
@@ -314,12 +380,21 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
         if (row >= NO) continue;
         if (MODE == 0) {
             E::store(a.dK, h * a.dks[1] + (int64_t)(kst + row) * a.dks[2] + x * a.dks[3], acc0[o * ld + x]);
+#ifndef FA2_BWD_GENERIC_DV
             E::store(a.dV, h * a.dvs[1] + (int64_t)(kst + row) * a.dvs[2] + x * a.dvs[3], acc1[o * ld + x]);
+#endif
         } else {  // (a row without a visible key: rowsum 0, dQ 0)
             E::store(a.dQ, h * a.dqs[1] + (int64_t)(qst + row) * a.dqs[2] + x * a.dqs[3],
                      Rs[o] > 0 ? acc0[o * ld + x] / Rs[o] : (A)0);
         }
     }
+#ifdef FA2_BWD_GENERIC_DV
+    if (MODE == 0)
+        for (int e = tid; e < TB * dv; e += 256) {
+            const int o = e / dv, x = e % dv, row = own_row0 + o;
+            if (row < NO) E::store(a.dV, h * a.dvs[1] + (int64_t)(kst + row) * a.dvs[2] + x * a.dvs[3], acc1[o * ldv + x]);
+        }
+#endif
     // L = +inf and rowsum 0 would give inf + -inf: such a row keeps +inf, and MODE 0 recomputes P = 0 for it
     if (MODE == 1 && tid < TB && own_row0 + tid < NO) Lc[own_row0 + tid] = Rs[tid] > 0 ? Lq[tid] + log2_acc<A>(Rs[tid]) : (A)INFINITY;
 #else
@@ -340,7 +415,11 @@ template <typename E, int MODE> __global__ __launch_bounds__(256) void bwd_main_
 template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
     using A = typename E::acc_t;
     int TB = 16;
+#ifdef FA2_BWD_GENERIC_DV
+    auto need = [&](int tb) { return (size_t)(3 * tb * (p.d + 1) + 3 * tb * (p.dv + 1) + 2 * tb * tb + 3 * tb) * sizeof(A); };
+#else
     auto need = [&](int tb) { return (size_t)(6 * tb * (p.d + 1) + 2 * tb * tb + 3 * tb) * sizeof(A); };
+#endif
     while (TB > 1 && need(TB) > 60 * 1024) TB >>= 1;
     a.TB = TB;
     const size_t smem = need(TB);
@@ -380,7 +459,9 @@ template <typename E> int launch_e(const Fa2BwdProblem &p, GArgs &a) {
 
 }  // namespace
 
-#if defined(FA2_BWD_GENERIC_GQA) && defined(FA2_BWD_GENERIC_VARLEN)
+#if defined(FA2_BWD_GENERIC_DV)
+int fa2_bwd_launch_generic_varlen_dv(const Fa2BwdProblem &p, int gqa) {
+#elif defined(FA2_BWD_GENERIC_GQA) && defined(FA2_BWD_GENERIC_VARLEN)
 int fa2_bwd_launch_generic_varlen_gqa(const Fa2BwdProblem &p, int gqa) {
 #elif defined(FA2_BWD_GENERIC_GQA)
 int fa2_bwd_launch_generic_window_gqa(const Fa2BwdProblem &p, int gqa) {
@@ -415,6 +496,9 @@ int fa2_bwd_launch_generic(const Fa2BwdProblem &p) {
     a.scale = (double)p.scale;
 #ifdef FA2_BWD_GENERIC_GQA
     a.gqa = gqa;
+#endif
+#ifdef FA2_BWD_GENERIC_DV
+    a.dv = p.dv;
 #endif
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);

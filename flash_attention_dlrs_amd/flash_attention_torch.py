@@ -463,6 +463,56 @@ def mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_s
     return O, L
 
 
+def mla_prefill_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, causal=False, scale=1.0,
+                         window=None, variant="auto"):
+    """(dQ, dK, dV) of mla_prefill_forward from its O and L (fa2_bwd_varlen_dv), with Q's, K's and V's shapes: the matrix kernel for
+    f16 / bf16 at d 192 / d_v 128 under "auto", else the VALU kernel at the head sizes given.  The tensors go to the library as they
+    are, strides included: no head-size padding under any variant.  Tokens outside every sequence are not written."""
+    check_varlen_dv_args(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, window)
+    if variant not in _lib.BWD_VARLEN_DV_VARIANTS:
+        raise ValueError(f"mla prefill backward: variant must be one of {sorted(_lib.BWD_VARLEN_DV_VARIANTS)}, got {variant!r}")
+    total_q, H, _ = Q.shape
+    o_shape = (total_q, H, V.shape[2])
+    if tuple(O.shape) != o_shape or tuple(dO.shape) != o_shape or O.dtype != Q.dtype or dO.dtype != Q.dtype:
+        raise ValueError(f"mla prefill backward: O and dO must be {o_shape} in Q's dtype, got {tuple(O.shape)} {O.dtype} and "
+                         f"{tuple(dO.shape)} {dO.dtype}")
+    if tuple(L.shape) != (H, total_q) or L.dtype != Q.dtype or L.stride(1) != 1:
+        raise ValueError(f"mla prefill backward: L must be ({H}, {total_q}) in Q's dtype with unit token stride")
+    _check_varlen_device(Q, K, V)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    D = torch.empty(2, H, total_q, dtype=torch.float64 if Q.dtype == torch.float64 else torch.float32, device=Q.device)
+    _lib.fa2_bwd_varlen_dv(Q, K, V, O, dO, L, dQ, dK, dV, D, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                           convert_triton_dtype(Q.dtype), causal=causal, scale=scale, window=window,
+                           variant=_lib.BWD_VARLEN_DV_VARIANTS[variant])
+    return dQ, dK, dV
+
+
+class FlashAttentionMLAPrefill(torch.autograd.Function):
+    """Packed attention with a value head size of its own (un-absorbed MLA prefill, d 192 / d_v 128):
+    `FlashAttentionMLAPrefill.apply(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, scale, window)`,
+    Q (total_q, H, d), K (total_k, H_kv, d), V (total_k, H_kv, d_v) with H_kv dividing H, FlashAttentionVarlen's masks and
+    conventions.  Returns O (total_q, H, d_v); the cu_seqlens and the other arguments get no gradient.  K may be the broadcast of a
+    shared rotary head (`expand`): autograd sums its gradient."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False, scale=1.0, window=None):
+        O, L = mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal, scale=scale,
+                                   window=window)
+        ctx.save_for_backward(Q, K, V, O, L, cu_seqlens_q, cu_seqlens_k)
+        ctx.args = (max_seqlen_q, max_seqlen_k, bool(causal), float(scale), window)
+        ctx.mark_non_differentiable(L)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO, *args):
+        Q, K, V, O, L, cu_q, cu_k = ctx.saved_tensors
+        max_q, max_k, causal, scale, window = ctx.args
+        if dO.stride(-1) != 1:
+            dO = dO.contiguous()
+        dQ, dK, dV = mla_prefill_backward(Q, K, V, O, dO, L, cu_q, cu_k, max_q, max_k, causal=causal, scale=scale, window=window)
+        return dQ, dK, dV, None, None, None, None, None, None, None
+
+
 def varlen_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, causal=False, scale=1.0,
                     window=None, variant="auto"):
     """(dQ, dK, dV) of a packed batch from the forward's O and L (fa2_bwd_varlen): the MFMA kernel for f16 / bf16 at

@@ -7,7 +7,7 @@ import torch
 
 from . import _lib, autotune
 from .flash_attention_torch import (MIN_TENSOR_SIZE, backward_native, convert_triton_dtype, forward_head_size,
-                                    gqa_kv_heads, mla_prefill_forward, next_power_of_2, normalize_window, pad_last_dim,
+                                    gqa_kv_heads, mla_prefill_backward, mla_prefill_forward, next_power_of_2, normalize_window, pad_last_dim,
                                     varlen_backward, varlen_forward, window_head_size)
 
 
@@ -126,12 +126,23 @@ def flash_attention_mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max
     Q (total_q, H, d), K (total_k, H_kv, d), V (total_k, H_kv, d_v) with H_kv dividing H, cu_seqlens int32 (B + 1) on Q's device;
     O (total_q, H, d_v) contiguous, L (H, total_q).  Strided inputs are passed through -- the two views of a fused (total, H,
     192 + 128) up-projection buffer are a valid K and V -- and no head size is padded: "auto" runs the matrix kernel for f16 / bf16
-    at d 192 / d_v 128 and the VALU kernel on anything else, "generic" and "mfma16dv" force one (_lib.VARLEN_DV_VARIANTS).
-    Forward only."""
+    at d 192 / d_v 128 and the VALU kernel on anything else, "generic" and "mfma16dv" force one (_lib.VARLEN_DV_VARIANTS)."""
     if Q.device != torch.device(dev):
         raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
     return mla_prefill_forward(Q, K, V, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal, scale=scale,
                                window=window, variant=variant)
+
+
+def flash_attention_mla_prefill_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dev, *,
+                                         causal=False, scale=1.0, window=None, variant="auto"):
+    """(dQ, dK, dV) of flash_attention_mla_prefill_forward (include/fa2_bwd.h fa2_bwd_varlen_dv) with Q's, K's and V's shapes;
+    deterministic.  O and dO are (total_q, H, d_v), L (H, total_q); dK and dV are summed over each group of query heads in the
+    kernel.  Strided tensors are passed through and no head size is padded: "auto" runs the matrix kernel for f16 / bf16 at d 192 /
+    d_v 128 and the VALU kernel on anything else, "generic" and "mfma16dv" force one (_lib.BWD_VARLEN_DV_VARIANTS)."""
+    if Q.device != torch.device(dev):
+        raise ValueError(f"dev={dev} is not the device of Q, K, V ({Q.device})")
+    return mla_prefill_backward(Q, K, V, O, dO, L, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=causal,
+                                scale=scale, window=window, variant=variant)
 
 
 FP8_CACHE_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)

@@ -165,6 +165,44 @@ int fa2_bwd_varlen_gqa_variant(const void *Q, const void *K, const void *V, cons
                                int32_t total_k, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
                                int32_t window_right, void *hip_stream, int32_t variant);
 
+/* A value head size of its own: the gradients of fa2_fwd_varlen_dv's O, given its L (un-absorbed MLA prefill: d = 192 for Q / K,
+ * d_v = 128 for V).  Arguments of fa2_bwd_varlen_gqa(_variant) with d_v after d: Q, K, dQ, dK have last axis d; V, O, dO, dV have
+ * last axis d_v; L is (H, total_q) in dtype_enum as the forward stored it; D is the scratch of 2 * H * total_q float32 (float64 for
+ * f64), its first half rowsum(dO * O) over the d_v columns.  Offsets and their clamping, the bottom-right causal mask and window,
+ * empty rows (L = +inf: dQ row 0, the statistic stays +inf), zero-length sequences, tokens outside every sequence left unwritten in
+ * all three gradients and the 64-bit per-sequence bases are fa2_bwd_varlen's; dK / dV of a KV head are summed over its query heads
+ * inside one workgroup, in a fixed order.  Nothing pads a head size: d follows the forward call's rule -- d in [1, 512], with the
+ * forward's codes outside it -- and not the power-of-two rule of the other backward calls; d_v outside [1, 512] is
+ * FA2_ERR_BAD_ARG ("d_v" in the message), tested after every check of fa2_bwd_varlen_gqa.  The two views of one fused
+ * (total, H_kv, d + d_v) buffer are a valid K and V, and a valid dK and dV.
+ * Variants at d_v != d: FA2_BWD_VARIANT_AUTO (MFMA16DV where it runs, else GENERIC), FA2_BWD_VARIANT_GENERIC (f64, f32, f16, bf16;
+ * any strides, any (d, d_v) in [1, 512]; VALU) and FA2_BWD_VARIANT_MFMA16DV (f16 / bf16 at exactly d 192 / d_v 128, unit d-stride,
+ * row and head strides multiples of 8 elements and 16-byte aligned pointers on all eight tensors, 0 < scale < inf, and
+ * (max(max_seqlen_q, max_seqlen_k) + 64) x row stride below 2 GiB on the five inputs); any other id returns FA2_ERR_UNSUPPORTED
+ * with the id in the message.  At d_v == d the call IS fa2_bwd_varlen_gqa_variant -- the same kernels, the same bits -- and
+ * AUTO, GENERIC and FA2_BWD_VARIANT_MFMA16 mean what they mean there. */
+#define FA2_BWD_VARIANT_MFMA16DV 4 /* fa2_bwd_varlen_dv alone: f16 / bf16, d = 192 and d_v = 128; MFMA */
+
+int fa2_bwd_varlen_dv(const void *Q, const void *K, const void *V, const void *O, const void *dO, const void *L,
+                      void *dQ, void *dK, void *dV, void *D,
+                      const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                      const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                      const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                      const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H, int32_t H_kv,
+                      int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q, int32_t total_k,
+                      int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                      void *hip_stream);
+
+int fa2_bwd_varlen_dv_variant(const void *Q, const void *K, const void *V, const void *O, const void *dO,
+                              const void *L, void *dQ, void *dK, void *dV, void *D,
+                              const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                              const int64_t o_strides[3], const int64_t do_strides[3], const int64_t dq_strides[3],
+                              const int64_t dk_strides[3], const int64_t dv_strides[3], int64_t l_head_stride,
+                              const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int32_t B, int32_t H,
+                              int32_t H_kv, int32_t d, int32_t d_v, int32_t max_seqlen_q, int32_t max_seqlen_k,
+                              int32_t total_q, int32_t total_k, int32_t dtype_enum, int32_t causal, float scale,
+                              int32_t window_left, int32_t window_right, void *hip_stream, int32_t variant);
+
 #ifdef __cplusplus
 }
 #endif
