@@ -10,7 +10,8 @@ from .flash_attention_torch import (MIN_TENSOR_SIZE, FlashAttention, FlashAttent
 from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_attention_backward, flash_attention_forward,
                                        flash_attention_kvcache_forward, flash_attention_mla_decode_forward,
                                        flash_attention_varlen_backward, check_mla_append_args, mla_kvcache_append,
-                                       mla_kvcache_append_varlen, check_mla_varlen_args,
+                                       mla_kvcache_append_varlen, check_mla_varlen_args, check_mla_sparse_args,
+                                       flash_attention_mla_sparse_decode_forward,
                                        flash_attention_mla_varlen_decode_forward, flash_attention_mla_prefill_backward,
                                        flash_attention_mla_prefill_forward,
                                        flash_attention_varlen_forward, flash_attention_varlen_kvcache_forward, kvcache_append,
@@ -22,4 +23,5 @@ __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarle
            "varlen_mask", "gqa_kv_heads", "kvcache_append", "apply_rotary", "flash_attention_varlen_kvcache_forward",
            "kvcache_append_varlen", "flash_attention_mla_decode_forward", "mla_kvcache_append", "mla_kvcache_append_varlen",
            "check_mla_append_args", "flash_attention_mla_varlen_decode_forward", "check_mla_varlen_args",
-           "flash_attention_mla_prefill_forward", "flash_attention_mla_prefill_backward", "FlashAttentionMLAPrefill"]
+           "flash_attention_mla_prefill_forward", "flash_attention_mla_prefill_backward", "FlashAttentionMLAPrefill",
+           "flash_attention_mla_sparse_decode_forward", "check_mla_sparse_args"]

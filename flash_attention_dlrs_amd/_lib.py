@@ -58,7 +58,7 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits",
            "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append",
            "fa2_fwd_kvcache_mla_varlen", "fa2_kvcache_mla_varlen_num_splits", "fa2_fwd_kvcache_mla_varlen_append",
-           "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant")
+           "fa2_fwd_kvcache_mla_sparse", "fa2_kvcache_mla_sparse_num_splits", "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -255,6 +255,14 @@ def lib():
         l.fa2_fwd_kvcache_mla_varlen_append.argtypes = [vp] * 4 + [i64p] * 3 + [ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int64, vp, i64p, vp,
                                                         vp, i64p, i64p, vp, vp, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + \
             [vp] + [ctypes.c_int32] * 14 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # key lists over the latent cache: fa2_fwd_kvcache_mla_fp8's order with indices, their strides and topk after cache_seqlens, no
+        # causal and no window sides
+        l.fa2_fwd_kvcache_mla_sparse.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_sparse.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, i64p, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, i64p,
+                                                                         i64p] + [ctypes.c_int32] * 11 + \
+            [ctypes.c_float, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_mla_sparse_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_mla_sparse_num_splits.argtypes = [ctypes.c_int32] * 8
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -638,6 +646,30 @@ def fa2_fwd_kvcache_mla_fp8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_e
             None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, *_descale_args(k_descale, v_descale), B, H,
             K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale),
             *_window_sides(window), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
+
+
+def kvcache_mla_sparse_num_splits(B, H, H_kv, N_q, topk, d, d_v, dtype_enum):
+    """What num_splits = 0 resolves to for a sparse latent-cache call of this shape (fa2_kvcache_mla_sparse_num_splits): the splits run
+    over the topk slots of the lists."""
+    return int(lib().fa2_kvcache_mla_sparse_num_splits(B, H, H_kv, N_q, topk, d, d_v, int(dtype_enum)))
+
+
+def fa2_fwd_kvcache_mla_sparse(Q, K, V, O, L, indices, cache_seqlens, dtype_enum, kv_dtype_enum, k_descale=None, v_descale=None,
+                               block_table=None, scale=1.0, num_splits=0, workspace=None, variant=0):
+    """Launch sparse MLA decode (include/fa2_fwd.h fa2_fwd_kvcache_mla_sparse) on the current stream of Q's device.  As
+    fa2_fwd_kvcache_mla_fp8 without a mask: indices is an int32 tensor on the device viewed as (B, H_kv, N_q, topk) (expanded views
+    are fine: their strides are passed on), entry [b, hk, qi, s] a key position of sequence b, no key outside [0, N_k(b))."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    tb_ptr, tb_st, _, nb, _, mb = _table_args(K, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla_sparse, Q,
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), indices.data_ptr(), _i64(indices.stride()), indices.shape[3],
+            tb_ptr, tb_st, *_descale_args(k_descale, v_descale), B, H, K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3],
+            int(dtype_enum), int(kv_dtype_enum), float(scale), int(num_splits), *_workspace_args(workspace), int(variant),
+            _raw_stream(Q.device.index))
 
 
 def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):

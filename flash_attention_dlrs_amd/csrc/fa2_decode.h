@@ -38,6 +38,12 @@ struct Fa2DecodeProblem {
     // rows from its start on, N_q holds max_q, and the partials are [num_splits][total_q * H] rows, row = token * H + head.
     const int32_t *cu_q;
     int32_t total_q, max_q;
+    // per-query key lists (fa2_fwd_kvcache_mla_sparse): indices non-null.  Entry [b, h_kv, qi, s] at the element strides is[4] is a
+    // key position of sequence b, no key outside [0, N_k(b)); topk slots per list, the splits run over the slots
+    // (fa2_decode_split_slots), causal / wl / wr are not read.
+    const int32_t *indices;
+    int64_t is[4];
+    int32_t topk;
 };
 
 // N_k(b) and the key range [k0, k1) of split s (device side of the rule above).
@@ -49,6 +55,17 @@ __device__ __forceinline__ void fa2_decode_split(const int32_t *seqlens, int b, 
     nk = n;
     k0 = s * c;  // <= n + 64 * num_splits
     k1 = k0 + c < n ? k0 + c : n;
+}
+
+// The sparse call: N_k(b) and the SLOT range [s0, s1) of split s over a list of topk slots, c = ceil(topk / num_splits) rounded up
+// to the key tile.  With the identity list over N_k(b) = topk keys these are fa2_decode_split's k0, k1.
+__device__ __forceinline__ void fa2_decode_split_slots(const int32_t *seqlens, int b, int S_k, int topk, int num_splits, int s, int &nk,
+                                                       int &s0, int &s1) {
+    const int n = seqlens ? seqlens[b] : S_k;
+    nk = n < 0 ? 0 : (n > S_k ? S_k : n);
+    const int c = ((topk + num_splits - 1) / num_splits + FA2_KVCACHE_KEY_TILE - 1) & ~(FA2_KVCACHE_KEY_TILE - 1);
+    s0 = s * c;  // <= topk + 64 * num_splits
+    s1 = s0 + c < topk ? s0 + c : topk;
 }
 
 // A descale of the fp8 cache at [b, h_kv]: uniform over the workgroup, so one scalar load.  Null = 1.
@@ -127,6 +144,13 @@ int fa2_launch_decode_mfma16_v(const Fa2DecodeProblem &p);
 // (sequence, KV head) position-major, 64 of them per workgroup, ceil(g max_seqlen_q / 64) tiles per (split, KV head, sequence).
 bool fa2_decode_mla16_v_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla16_v(const Fa2DecodeProblem &p);
+
+// The sparse call (fa2_fwd_kvcache_mla_sparse).  Matrix form (fa2_decode_mla16_s.hip): the list-addressed instantiations of the latent
+// kernel, 64 heads of one (sequence, KV head, query position) per workgroup, ceil(g / 64) head tiles.  VALU form
+// (fa2_decode_sparse_generic.hip): 16 heads of one KV group at one query position per workgroup, every dtype, any d / d_v, any V.
+bool fa2_decode_mla16_s_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_s(const Fa2DecodeProblem &p);
+int fa2_launch_decode_sparse_generic(const Fa2DecodeProblem &p);
 
 // One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
 // each tensor's dtype.  It is the kernel's argument as well.

@@ -59,11 +59,38 @@
 // [q0, q1), whole 64-key tiles outside it neither loaded nor looked up.  The partial row is split * total_q * H + (start +
 // position) * H + head, what the combine expects for cu_q.  With VQ false q0 = 0, q1 = N_q, start = 0, rows are head-major as
 // above and every expression below is the fixed-N_q kernel's.
+//
+// Per-query key lists (fa2_fwd_kvcache_mla_sparse).  SP is a template parameter, instantiated in fa2_decode_mla16_s.hip
+// (FA2_DECODE_SPARSE) alone; the argument struct of the other units is what it was.  Every (sequence, KV head, query position)
+// attends over the keys its list of topk int32 entries names.  A workgroup owns 64 HEADS of one (sequence, KV head, position) --
+// ceil(g / 64) head tiles, padding rows repeat the group's last head and are dropped -- so its 64 rows share ONE list; the grid is
+// (B * N_q * num_splits * head tiles, H_kv), the workgroups of one list on consecutive ids, and holds B * N_q in the hundreds of
+// thousands (a sparse prefill chunk is B = 1, N_q in the thousands).  With N_q = 1 and `start` the position, every row expression of
+// the fixed-N_q kernel holds as it stands.  The splits run over the SLOTS of the list (fa2_decode_split_slots): [k0, k1), kb0, ke and
+// a tile's tk0 are slot numbers there, and a step takes the 64 slots of a tile.
+//   The list.   A wave reads the 64 entries of a tile once, one slot per lane (256 B coalesced with unit slot stride).  An entry j is
+//               a key where 0 <= j < N_k(b) and its slot lies before the split's end; the validity of the 64 slots is a 64-bit wave
+//               mask.  Two tiles ahead of the one in LDS: the entries of tile t + 3 are issued while the rows of tile t + 1 are
+//               loaded, those of tile t + 2 are judged then and (paged) their table entries issued -- entry j is row j % page_size of
+//               page table[b][j / page_size], one lookup per lane, ANY page size, clamped into the pool where it is used -- so neither
+//               dependent load is waited for in the step that issues it.
+//   Staging.    Each lane forms the 64-bit offset of its slot's row, position * row stride (+ page * block stride).  A wave brings
+//               its 16 rows' offsets to lanes 0..15 with one shuffle; row `it` then takes its offset with a lane read at a constant
+//               lane and is loaded as the dense kernel loads it (1 KiB + the 128-B tail, whose rows take theirs with a shuffle, as
+//               do the passes of the fp8 map, which cross rows).  The mask gates the loads: a slot that is no key is never turned
+//               into a table index or an address, its row is zeros in LDS.
+//   S phase.    The mask replaces the band test, a bit per key(r): a slot that is no key is selected to -inf.  A key listed twice is
+//               staged and counted twice.  A row without a valid entry: O = 0, L = +inf.
+// The LDS image, the swizzle, the S / softmax / P.V phases, the epilogue and the partial layout are the dense kernel's: on the
+// identity list over N_k = topk keys O and L equal the dense call's bit for bit at the same num_splits.
 #include "fa2_decode.h"
 #include "fa2_mfma.h"
 
 #ifndef FA2_DECODE_VARLEN_Q
 #define FA2_DECODE_VARLEN_Q 0
+#endif
+#ifndef FA2_DECODE_SPARSE
+#define FA2_DECODE_SPARSE 0
 #endif
 
 namespace {
@@ -84,6 +111,11 @@ struct DecodeMlaArgs {
     int64_t kds[2], vds[2];
     const int32_t *cu_q;  // VQ only: B + 1 offsets into the packed rows; qs[0] = os[0] = ls[0] = 0, N_q holds max_q
     int total_q;
+#if FA2_DECODE_SPARSE
+    const int32_t *idx;  // SP only (the struct of the other units is what it was): entry [b, hk, qi, slot] at the element strides is[4]
+    int64_t is[4];
+    int topk, B;
+#endif
 };
 
 constexpr int kD = 576, kDV = 512, kBC = 64;
@@ -106,9 +138,11 @@ static_assert(kStage == 18 && kStage8 == 9 && kSmem <= 160 * 1024, "one workgrou
 // Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: the d = 128 swizzle on rows of kRowB bytes.
 __device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ swz<128>(row)) << 4); }
 
+template <bool V> struct Bool { static constexpr bool value = V; };  // a compile-time flag as a lambda's argument
+
 // T: Q, O, L and the matrix arithmetic; C: the cache (T, or an fp8 format converted while it is staged).  VQ: packed queries,
-// rows position-major.
-template <typename T, typename C, bool PAGED, bool VQ>
+// rows position-major.  SP: per-query key lists (the file's head), the rows of a workgroup heads of ONE query position.
+template <typename T, typename C, bool PAGED, bool VQ, bool SP>
 __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
     using M = Mma<T>;
     constexpr bool F8 = !__is_same(C, T);
@@ -120,8 +154,17 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kb = wave & 1, rb = wave >> 1;  // S phase: key block, row block
     const int i = lane & 31, h = lane >> 5;
-    const int hk = blockIdx.y, b = blockIdx.z;
     int bx = blockIdx.x;
+    int sp_b = 0, sp_qi = 0;
+    if constexpr (SP) {
+        // x = ((b * N_q + position) * num_splits + split) * row_tiles + head tile: the workgroups that share a list sit on
+        // consecutive ids, and the axis holds B * N_q in the hundreds of thousands (a sparse prefill chunk)
+        const int per = a.num_splits * a.row_tiles, tok = bx / per;
+        bx -= tok * per;
+        sp_b = tok / a.N_q;
+        sp_qi = tok - sp_b * a.N_q;
+    }
+    const int hk = blockIdx.y, b = SP ? sp_b : blockIdx.z;
     if constexpr (VQ) {
         // The hardware deals consecutive workgroup ids round the chip's shader engines.  With tile t of every sequence at x = t the
         // tiles that have rows sit gridDim.x ids apart where the sequences are short (one-token decodes beside a long chunk), and
@@ -135,6 +178,10 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     const int split = bx / a.row_tiles, rt = bx - split * a.row_tiles;
     // N_q: the query count of the mask and of the rows, from packed row `start` on; [q0, q1): the positions the tile's rows lie in
     int N_q = a.N_q, start = 0;
+    if constexpr (SP) {  // one position, `start`, whose g heads are the rows: every row expression below then holds as it stands
+        N_q = 1;
+        start = sp_qi;
+    }
     if constexpr (VQ) {
         fa2_varlen_seq(a.cu_q, b, a.total_q, a.N_q, start, N_q);
         if (rt * 64 >= a.g * N_q) return;  // no rows: nothing to write, no partials (uniform: before any barrier)
@@ -143,14 +190,23 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     const int q0 = VQ ? rt * 64 / a.g : 0;
     const int q1 = VQ ? ((rt * 64 + 63) / a.g + 1 < N_q ? (rt * 64 + 63) / a.g + 1 : N_q) : N_q;
 
-    int NK, k0, k1;
-    fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
-    int wl, wr;
-    fa2_varlen_band(N_q, NK, a.causal, a.wl, a.wr, wl, wr);
+    int NK, k0, k1;  // SP: [k0, k1) are SLOTS of the list, and so are kb0, ke and tk0 below; there is no band
+    int wl = 0, wr = 0, spB = 0;
+    [[maybe_unused]] const int32_t *ip = nullptr;  // SP: the list of this (sequence, KV head, position)
+    if constexpr (SP) {
+#if FA2_DECODE_SPARSE
+        fa2_decode_split_slots(a.seqlens, b, a.S_k, a.topk, a.num_splits, split, NK, k0, k1);
+        ip = a.idx + b * a.is[0] + hk * a.is[1] + sp_qi * a.is[2];
+        spB = a.B;
+#endif
+    } else {
+        fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
+        fa2_varlen_band(N_q, NK, a.causal, a.wl, a.wr, wl, wr);
+    }
     // the keys of the split that the band of any query position of the tile touches: [kb0, ke), kb0 on a 64-key boundary
     const int lo_t = q0 - wl;
-    const int kb0 = lo_t > k0 ? (lo_t & ~63) : k0;  // (k0 is a multiple of 64)
-    const int ke = q1 + wr < k1 ? q1 + wr : k1;
+    const int kb0 = SP ? k0 : lo_t > k0 ? (lo_t & ~63) : k0;  // (k0 is a multiple of 64)
+    const int ke = SP ? k1 : q1 + wr < k1 ? q1 + wr : k1;
     const int nt = ke > kb0 ? (ke - kb0 + kBC - 1) / kBC : 0;
 
     // ---- S phase: this lane's row (head of the group, query position); padding rows repeat the last row and are not stored.
@@ -174,7 +230,7 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     // 16 + jb is rows 16w + 8jb + (lane >> 3), chunks 64 + (lane & 7).  (paged: the page's offset joins in stage_load)
     // fp8 cache: pass ps < 9 is load f % 36 of row 16w + f / 36, f = 64 ps + lane (the file's head).
     const int sb_row = 16 * wave + (lane >> 3), sb_ch = 64 + (lane & 7);
-    const char *kbase = a.K + hk * a.ks[1] + (PAGED ? 0 : b * a.ks[0] + (int64_t)kb0 * a.ks[2]);
+    const char *kbase = a.K + hk * a.ks[1] + (PAGED ? 0 : b * a.ks[0] + (SP ? 0 : (int64_t)kb0 * a.ks[2]));
     const char *kg_w = kbase + (int64_t)(16 * wave) * a.ks[2];  // the wave's first row
     const char *kg_a = kg_w + lane * 16;
     const char *kg_b = kbase + (int64_t)sb_row * a.ks[2] + sb_ch * 16;
@@ -186,12 +242,85 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     int pg_i = 0, pg_row = 0;
     const int32_t *tab = nullptr;
     if constexpr (PAGED) {
-        pg_i = kb0 / a.page_size;
-        pg_row = kb0 - pg_i * a.page_size;
+        if constexpr (!SP) {
+            pg_i = kb0 / a.page_size;
+            pg_row = kb0 - pg_i * a.page_size;
+        }
         tab = a.table + b * a.table_stride;
     }
+    // SP: the list walks three tiles ahead of the compute.  `j_b` is the RAW entry of slot (tile, lane) two tiles after the one in
+    // LDS, in flight since the last step; sp_advance(tn) takes it for tile tn: its validity becomes the wave mask m_a, its row (in
+    // its page) rw_a, the raw table entry e_a is issued, and the entries of tile tn + 1 are issued into j_b.  The next step's
+    // stage_load reads rows through (m_a, rw_a, e_a): neither the index load nor the table load is waited for in the step that
+    // issues it.  An entry that is no key (outside [0, N_k), or a slot at or past the split's end, which is not even loaded) never
+    // becomes a table index or an address: its row is zeros in LDS and its score is selected to -inf through the mask.
+    unsigned long long m_cur = 0, m_a = 0;
+    int rw_a = 0, e_a = 0, j_b = -1;
+    auto sp_idx = [&](int t) {
+#if FA2_DECODE_SPARSE
+        const int slot = k0 + t * kBC + lane;  // one slot per lane: 256 B of a list with unit slot stride
+        if (slot < k1) return ip[slot * a.is[3]];
+#endif
+        return (int)-1;
+    };
+    auto sp_advance = [&](int tn) {
+        const bool ok = k0 + tn * kBC + lane < k1 && j_b >= 0 && j_b < NK;
+        m_a = __ballot(ok);
+        rw_a = j_b;
+        if constexpr (PAGED) {
+            const int pg = j_b / a.page_size;
+            rw_a = j_b - pg * a.page_size;
+            e_a = ok ? tab[pg] : 0;  // raw: clamped where it is used
+        }
+        j_b = sp_idx(tn + 1);
+    };
+    // the byte offset of the row that lane `src` of the wave holds, out of the per-lane offsets `offv` of the tile's 64 rows;
+    // U: src is uniform (two lane reads), else two shuffles
+    auto sp_off = [&](int64_t offv, int src, auto uniform) {
+        constexpr bool U = decltype(uniform)::value;
+        const int lo = (int)offv, hi = (int)(offv >> 32);
+        const unsigned l = U ? __builtin_amdgcn_readlane(lo, src) : __shfl(lo, src, 64);
+        const int u = U ? __builtin_amdgcn_readlane(hi, src) : __shfl(hi, src, 64);
+        return (int64_t)u << 32 | l;
+    };
+    auto sp_offv = [&]() {  // this lane's row of the tile (m_a, rw_a, e_a) describe: position * row stride + (page term), 64-bit
+        int64_t offv = (int64_t)rw_a * a.ks[2];
+        if constexpr (PAGED) offv += (int64_t)(e_a < 0 ? 0 : (e_a > a.num_blocks - 1 ? a.num_blocks - 1 : e_a)) * a.ks[0];
+        return offv;
+    };
+
     u32x4 sreg[F8 ? kStage8 : kStage];
     auto stage_load = [&](int t) {
+        if constexpr (SP) {  // tile t is the one (m_a, rw_a, e_a) describe
+            const int64_t offv = sp_offv();
+            if constexpr (F8) {
+#pragma unroll
+                for (int ps = 0; ps < kStage8; ++ps) {
+                    const int src = 16 * wave + f8_row(ps);
+                    const bool ok = (m_a >> src) & 1;
+                    const int64_t off = sp_off(offv, src, Bool<false>{});
+                    sreg[ps] = ok ? *(const u32x4 *)(kbase + off + f8_ld(ps) * 16) : u32x4{0, 0, 0, 0};
+                }
+            } else {
+                // the wave's own 16 rows brought to lanes 0..15 first (one shuffle): row `it` is then a lane read at a constant
+                // lane, its validity a constant bit (16 wave + it as the lane would keep 16 scalar registers alive across the loop)
+                const int64_t offw = sp_off(offv, 16 * wave + (lane & 15), Bool<false>{});
+                const unsigned mw = (unsigned)(m_a >> (16 * wave));
+#pragma unroll
+                for (int it = 0; it < 16; ++it) {
+                    const bool ok = (mw >> it) & 1;  // uniform
+                    const int64_t off = sp_off(offw, it, Bool<true>{});
+                    sreg[it] = ok ? *(const u32x4 *)(kbase + off + lane * 16) : u32x4{0, 0, 0, 0};
+                }
+#pragma unroll
+                for (int jb = 0; jb < 2; ++jb) {
+                    const bool ok = (m_a >> (sb_row + 8 * jb)) & 1;
+                    const int64_t off = sp_off(offv, sb_row + 8 * jb, Bool<false>{});
+                    sreg[16 + jb] = ok ? *(const u32x4 *)(kbase + off + sb_ch * 16) : u32x4{0, 0, 0, 0};
+                }
+            }
+            return;
+        }
         const int rel = t * kBC;  // the tile's first key, relative to kb0
         int64_t toff = (int64_t)rel * a.ks[2];
         if constexpr (PAGED) {
@@ -286,7 +415,13 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     const int lo_max = q1 - 1 - wl, hi_min = (q0 + wr) < (ke - 1) ? (q0 + wr) : (ke - 1);
 
     if (nt > 0) {
+        if constexpr (SP) {
+            j_b = sp_idx(0);
+            sp_advance(0);
+            m_cur = m_a;
+        }
         stage_load(0);
+        if constexpr (SP) sp_advance(1);
         stage_write();
     }
     __syncthreads();
@@ -294,6 +429,9 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     for (int t = 0; t < nt; ++t) {
         const bool more = t + 1 < nt;
         if (more) stage_load(t + 1);
+        const unsigned long long m_nxt = m_a;  // SP: of tile t + 1
+        if constexpr (SP)
+            if (more) sp_advance(t + 2);
         const int tk0 = kb0 + t * kBC;
 
         // ---- S^T = K . Q^T: this wave's 32 keys x 32 rows
@@ -305,8 +443,17 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
             const u32x4 kf = *(LDS_PTR(u32x4))(lds + k_row * kRowB + (((2 * ks + h) ^ k_swz) << 4));
             s = M::mfma(__builtin_bit_cast(frag, kf), qf[ks], s);
         }
-        // ---- band and tail mask, selected: key(r) = tk0 + 32kb + 4h + (r & 3) + 8 (r >> 2)
-        if (tk0 < lo_max || tk0 + kBC - 1 > hi_min) {
+        // ---- band and tail mask, selected: key(r) = tk0 + 32kb + 4h + (r & 3) + 8 (r >> 2).  SP: the list's validity mask in
+        // the band test's place, a bit per key(r)
+        if constexpr (SP) {
+            const unsigned mh = kb ? (unsigned)(m_cur >> 32) : (unsigned)m_cur;  // this wave's key block (uniform)
+            if (mh != 0xffffffffu) {
+                const unsigned mv = mh >> (4 * h);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!((mv >> ((r & 3) + 8 * (r >> 2))) & 1)) s[r] = -INFINITY;
+            }
+        } else if (tk0 < lo_max || tk0 + kBC - 1 > hi_min) {
             const int kl = lo - (tk0 + 32 * kb + 4 * h), kh = hi - (tk0 + 32 * kb + 4 * h);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -374,6 +521,7 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
         }
         __syncthreads();  // every read of this step's tile and of P has retired
         if (more) stage_write();
+        m_cur = m_nxt;
         __syncthreads();
     }
 
@@ -419,16 +567,24 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
                 *lp = seen ? (T)(mr + __builtin_amdgcn_logf(l)) : (T)INFINITY;
             }
         } else {
-            const int64_t rows = VQ ? (int64_t)a.total_q * a.H : (int64_t)gridDim.z * a.H * N_q;
-            const int64_t prow = (int64_t)split * rows + (VQ ? (int64_t)(start + qi) * a.H + head : ((int64_t)b * a.H + head) * N_q + qi);
+            // (SP: the rows of all B * N_q positions, this one's position `start`)
+            const int64_t rows = VQ ? (int64_t)a.total_q * a.H : (int64_t)(SP ? spB : gridDim.z) * a.H * (SP ? a.N_q : N_q);
+            const int64_t prow = (int64_t)split * rows + (VQ   ? (int64_t)(start + qi) * a.H + head
+                                                          : SP ? ((int64_t)b * a.H + head) * a.N_q + start
+                                                               : ((int64_t)b * a.H + head) * N_q + qi);
             float *op = a.o_part + prow * kDV + 128 * wave + 4 * h;
+            float invp = inv;
+            // SP: the products of this branch are kept apart from the one-split branch's.  The compiler otherwise hoists a product the
+            // two branches share above them, and the one-split branch then rounds that fp32 product to f16 (two roundings) where the
+            // dense kernel's v_fma_mixlo_f16 rounds once: one ulp of one element in some 10^5, against the bit-for-bit tests
+            if constexpr (SP) asm volatile("" : "+v"(invp));
 #pragma unroll
             for (int db = 0; db < 4; ++db)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f32x4 v;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = o[db][rbp][4 * g + j] * inv;
+                    for (int j = 0; j < 4; ++j) v[j] = o[db][rbp][4 * g + j] * invp;
                     *(f32x4 *)(op + db * 32 + g * 8) = v;
                 }
             if (wave == 0 && h == 0) a.l_part[prow] = seen ? mr + __builtin_amdgcn_logf(l) : -INFINITY;
@@ -436,21 +592,22 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     }
 }
 
-constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0;
+constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0, kSP = FA2_DECODE_SPARSE != 0;
 
 template <typename T, typename C, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
-    const long long gx = (long long)p.num_splits * a.row_tiles;
+    const long long gx = (long long)p.num_splits * a.row_tiles * (kSP ? (long long)p.B * p.N_q : 1);
     if (gx > 0x7fffffffLL) {
-        fa2_set_error("kvcache mla16 kernel: grid too large (num_splits * row tiles = %lld)", gx);
+        fa2_set_error(kSP ? "kvcache mla sparse: grid too large (B * N_q * num_splits * head tiles = %lld)"
+                          : "kvcache mla16 kernel: grid too large (num_splits * row tiles = %lld)", gx);
         return FA2_ERR_BAD_ARG;
     }
     static Fa2DeviceLatch attr_done;  // more than 64 KiB of dynamic LDS: opt in, once per device
     if (attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, C, PAGED, kVQ>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
+        (void)hipFuncSetAttribute((const void *)fa2_decode_mla16_kernel<T, C, PAGED, kVQ, kSP>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
         attr_done.mark();
     }
-    const dim3 grid((unsigned)gx, p.H_kv, p.B), block(256);
-    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, C, PAGED, kVQ>), grid, block, kSmem, p.stream, a);
+    const dim3 grid((unsigned)gx, p.H_kv, kSP ? 1 : p.B), block(256);
+    hipLaunchKernelGGL((fa2_decode_mla16_kernel<T, C, PAGED, kVQ, kSP>), grid, block, kSmem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mla16 kernel launch failed: %s", hipGetErrorString(e));
@@ -475,12 +632,14 @@ bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 // (packed queries: N_q holds max_seqlen_q, so the row bound below is the grid's)
 bool supports(const Fa2DecodeProblem &p) {
-    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || (p.kv_dtype != p.dtype && !fp8_cache(p)) || (p.cu_q != nullptr) != kVQ) return false;
+    if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || (p.kv_dtype != p.dtype && !fp8_cache(p)) || (p.cu_q != nullptr) != kVQ ||
+        (p.indices != nullptr) != kSP)
+        return false;
     if (p.V != p.K) return false;  // the value operand is read from K's LDS image
     for (int k = 0; k < 4; ++k)
         if (p.vs[k] != p.ks[k]) return false;
     if (!(p.scale > 0.0f) || !(p.scale < INFINITY)) return false;
-    if ((int64_t)(p.H / p.H_kv) * p.N_q > (1 << 24)) return false;  // (rows of a KV group are counted in 32 bits)
+    if (!kSP && (int64_t)(p.H / p.H_kv) * p.N_q > (1 << 24)) return false;  // (rows of a KV group are counted in 32 bits)
     if (p.qs[3] != 1 || p.ks[3] != 1 || p.os[3] != 1) return false;
     // 16-byte vector loads of Q and K rows, 8-byte stores of O: every row start must stay aligned (an fp8 cache: 16 elements)
     const int64_t kmask = fp8_cache(p) ? 15 : 7;
@@ -489,7 +648,7 @@ bool supports(const Fa2DecodeProblem &p) {
     if (!aligned16(p.Q) || !aligned16(p.K) || !aligned16(p.O)) return false;
     if (p.num_splits > 1 && !aligned16(p.o_part)) return false;
     // paged: a 64-key tile must lie inside one page; the block stride is ks[0] above
-    if (p.table && p.page_size % FA2_KVCACHE_KEY_TILE != 0) return false;
+    if (!kSP && p.table && p.page_size % FA2_KVCACHE_KEY_TILE != 0) return false;  // (a list addresses every row on its own)
     return true;
 }
 
@@ -498,7 +657,7 @@ int launch(const Fa2DecodeProblem &p) {
         fa2_set_error("kvcache mla16 kernel: needs f16/bf16, d = 576 and d_v = 512, V aliasing K (the same pointer and strides), unit "
                       "d-stride, 16-byte aligned rows (and workspace), scale > 0%s%s",
                       fp8_cache(p) ? "; an fp8 cache: every stride of K a multiple of 16 elements and a 16-byte aligned base" : "",
-                      p.table ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
+                      p.table && !kSP ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
         return FA2_ERR_UNSUPPORTED;
     }
     DecodeMlaArgs a;
@@ -510,19 +669,26 @@ int launch(const Fa2DecodeProblem &p) {
     a.seqlens = p.seqlens;
     a.H = p.H; a.g = p.H / p.H_kv; a.N_q = p.N_q; a.S_k = p.S_k; a.causal = p.causal; a.wl = p.wl; a.wr = p.wr;
     a.num_splits = p.num_splits;
-    a.row_tiles = (int)(((int64_t)a.g * p.N_q + 63) / 64);
+    a.row_tiles = (int)(((int64_t)a.g * (kSP ? 1 : p.N_q) + 63) / 64);
     a.o_part = p.o_part; a.l_part = p.l_part;
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.cu_q = p.cu_q; a.total_q = p.total_q;
+#if FA2_DECODE_SPARSE
+    a.idx = p.indices; a.topk = p.topk; a.B = p.B;
+    for (int k = 0; k < 4; ++k) a.is[k] = p.is[k];
+#endif
     return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }
 
 }  // namespace
 
-#if FA2_DECODE_VARLEN_Q
+#if FA2_DECODE_SPARSE
+bool fa2_decode_mla16_s_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_s(const Fa2DecodeProblem &p) { return launch(p); }
+#elif FA2_DECODE_VARLEN_Q
 bool fa2_decode_mla16_v_supports(const Fa2DecodeProblem &p) { return supports(p); }
 int fa2_launch_decode_mla16_v(const Fa2DecodeProblem &p) { return launch(p); }
 #else

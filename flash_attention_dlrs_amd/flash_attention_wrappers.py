@@ -904,3 +904,83 @@ def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seq
                                     convert_triton_dtype(KV_cache.dtype), d_v, block_table=block_table, kv_descale=kd, causal=causal,
                                     scale=scale, window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
     return O, L
+
+
+def _sparse_indices(indices, B, H_kv, N_q):
+    """The (B, H_kv, N_q, topk) view of an indices argument: 4-D as it is, (B, N_q, topk) expanded over the KV heads without a copy."""
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or indices.dim() not in (3, 4):
+        raise ValueError(f"mla sparse decode: indices must be an int32 tensor (B, H_kv, N_q, topk) or (B, N_q, topk), got "
+                         f"{(tuple(indices.shape), indices.dtype) if isinstance(indices, torch.Tensor) else type(indices).__name__}")
+    view = indices if indices.dim() == 4 else indices.unsqueeze(1).expand(-1, H_kv, -1, -1)
+    if view.shape[:3] != (B, H_kv, N_q) or view.shape[3] < 1:
+        raise ValueError(f"mla sparse decode: indices must be (B, H_kv, N_q, topk) = ({B}, {H_kv}, {N_q}, topk) or (B, N_q, topk) with "
+                         f"topk >= 1, got {tuple(indices.shape)}")
+    if view.shape[3] > 1 << 28:
+        raise ValueError(f"mla sparse decode: topk must be <= 2^28, got {view.shape[3]}")
+    if any(s < 0 for s in view.stride()):
+        raise ValueError(f"mla sparse decode: indices with negative strides are not supported, got {tuple(view.stride())}")
+    return view
+
+
+def check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v=512, num_splits=0, kv_descale=None, block_table=None):
+    """ValueError for what flash_attention_mla_sparse_decode_forward cannot take: Q, the latent cache, d_v, cache_seqlens, block_table
+    and num_splits by the rules of flash_attention_mla_decode_forward; indices int32 on Q's device, (B, H_kv, N_q, topk) or
+    (B, N_q, topk) with B and N_q Q's and topk >= 1; kv_descale with a cache in Q's dtype, and an fp8 cache WITHOUT its kv_descale (a
+    quantised cache has one: this call does not read None as 1).  Pure: takes CPU tensors as well."""
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 4:
+        raise ValueError(f"mla sparse decode: Q must be a tensor (B, H, N_q, d), got "
+                         f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
+        raise ValueError("mla sparse decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    d = KV_cache.shape[3]
+    if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
+        raise ValueError(f"mla sparse decode: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
+    if not 1 <= d <= 576 or d_v > 512:
+        raise ValueError(f"mla sparse decode: d must be in [1, 576] and d_v in [1, 512], got d = {d}, d_v = {d_v}")
+    fp8 = KV_cache.dtype in FP8_CACHE_DTYPES
+    if kv_descale is not None and not fp8:
+        raise ValueError(f"mla sparse decode: kv_descale goes with an fp8 KV_cache, not with {KV_cache.dtype}")
+    if fp8 and kv_descale is None:
+        raise ValueError(f"mla sparse decode: an fp8 KV_cache ({KV_cache.dtype}) needs its kv_descale (quantize_kv_cache returns it)")
+    check_kvcache_args(Q, KV_cache, KV_cache, cache_seqlens, None, num_splits, None, None, block_table)
+    _kvcache_descale("kv_descale", kv_descale, Q, Q.shape[0], KV_cache.shape[1])
+    view = _sparse_indices(indices, Q.shape[0], KV_cache.shape[1], Q.shape[2])
+    if view.device != Q.device:
+        raise ValueError(f"mla sparse decode: indices must be on Q's device ({Q.device}), got {view.device}")
+
+
+def flash_attention_mla_sparse_decode_forward(Q, KV_cache, indices, cache_seqlens, dev, *, d_v=512, scale=1.0, num_splits=0,
+                                              variant="auto", kv_descale=None, block_table=None, **mask):
+    """Sparse multi-head latent attention over the shared latent cache (include/fa2_fwd.h fa2_fwd_kvcache_mla_sparse) -> (O, L): every
+    (sequence, KV head, query position) attends over exactly the keys its list names (DeepSeek-V3.2's sparse attention: an indexer
+    picks about 2,048 keys per query token, in decode and in a sparse prefill chunk alike).  No row is gathered: each listed row is
+    read where it lies.  Q (B, H, N_q, d); KV_cache, d_v, cache_seqlens, block_table and kv_descale are
+    flash_attention_mla_decode_forward's -- the contiguous (B, H_kv, S_k, d) latent cache or a page pool of ANY page size, in Q's dtype
+    or fp8 with its kv_descale (required here).  indices: int32 on Q's device, (B, H_kv, N_q, topk), any non-negative strides, or
+    (B, N_q, topk), expanded over the KV heads without a copy.  Entry [b, hk, qi, s] is a logical key position of sequence b; an entry
+    < 0 or >= N_k(b) = clamp(cache_seqlens[b]) is no key (pad a shorter list with -1), a key listed twice counts twice, and a row
+    without a valid entry gets O = 0, L = +inf.  The list is the mask: there is no causal and no window argument (both are a
+    ValueError; the indexer respects causality).  O (B, H, N_q, d_v) contiguous, L (B, H, N_q) log2-domain, both in Q's dtype.
+    num_splits = 0 lets the library choose (the splits run over the slots of the list); variant is one of _lib.KVCACHE_MLA_VARIANTS:
+    "mla16" (f16 / bf16, d = 576, d_v = 512, unit d-stride and 16-byte aligned rows, any H / H_kv, any page size), "generic" (everything
+    else), "auto".  The append side is mla_kvcache_append, called first.  No autograd, no autotuner."""
+    for name in mask:
+        if name in ("causal", "window"):
+            raise ValueError(f"mla sparse decode: there is no {name} argument: the index list is the mask (the indexer respects "
+                             f"causality; leave out what a position must not see)")
+        raise TypeError(f"flash_attention_mla_sparse_decode_forward() got an unexpected keyword argument {name!r}")
+    check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v, num_splits, kv_descale, block_table)
+    if variant not in _lib.KVCACHE_MLA_VARIANTS:
+        raise ValueError(f"mla sparse decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
+    _check_dev(dev, Q, KV_cache, KV_cache)
+    B, H, N_q, d = Q.shape
+    H_kv = KV_cache.shape[1]
+    view = _sparse_indices(indices, B, H_kv, N_q)
+    dtype = convert_triton_dtype(Q.dtype)
+    n = num_splits or _lib.kvcache_mla_sparse_num_splits(B, H, H_kv, N_q, view.shape[3], d, d_v, dtype)
+    O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d_v), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0)
+    kd = _kvcache_descale("kv_descale", kv_descale, Q, B, H_kv)
+    _lib.fa2_fwd_kvcache_mla_sparse(Q, KV_cache, KV_cache[..., :d_v], O, L, view, cache_seqlens, dtype, convert_triton_dtype(KV_cache.dtype),
+                                    k_descale=kd, v_descale=kd, block_table=block_table, scale=scale, num_splits=n, workspace=ws,
+                                    variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+    return O, L

@@ -779,6 +779,56 @@ int32_t fa2_kvcache_mla_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, in
                                           int32_t d, int32_t d_v, int32_t dtype_enum);
 
 /*
+ * Sparse MLA decode: every (sequence, KV head, query position) brings a list of key indices and attends over exactly those keys of
+ * the latent cache (DeepSeek-V3.2's sparse attention, decode and sparse prefill chunks alike: an indexer picks the keys, this call is
+ * the attention).  No row of the cache is gathered: each listed row is read where it lies.  Forward only.
+ *
+ *   Tensors.  fa2_fwd_kvcache_mla_fp8's: Q (B, H, N_q, d), the latent cache K (B, H_kv, S_k, d) or, with block_table, the pool
+ *             (num_blocks, H_kv, page_size, d), V the first d_v columns of the same rows (or a tensor of its own: GENERIC), O
+ *             (B, H, N_q, d_v), L (B, H, N_q) in the log2 domain; d in [1, 576], d_v in [1, 512], H_kv dividing H.  block_table null:
+ *             the contiguous cache, page_size carries S_k, as in fa2_fwd_kvcache_mla.
+ *   Indices.  int32 on the device, (B, H_kv, N_q, topk) with four element strides (index_strides, each >= 0, 0 allowed: one list
+ *             for every KV head, say); topk >= 1.  Entry [b, hk, qi, s] is a logical key position j of sequence b -- through a
+ *             block table row j % page_size of page block_table[b, j / page_size], the entry clamped into the pool, ANY page size.
+ *             An entry with j < 0 or j >= N_k(b) (the clamp of cache_seqlens[b]; null: S_k) is no key: it is never turned into an
+ *             address and its score is selected to -inf -- a shorter list is padded with -1.  A key listed twice counts twice.  A
+ *             row without a valid entry gives O = 0 and L = +inf.
+ *   Mask.     None: the list is the mask (the indexer respects causality).
+ *   Splits.   Over the SLOTS of the list: split s covers slots [s c, (s + 1) c), c = ceil(topk / num_splits) rounded up to 64.
+ *             Partials, workspace (fa2_kvcache_workspace_bytes(B, H, N_q, d_v, num_splits)) and the combine launch are
+ *             fa2_fwd_kvcache_mla's.  num_splits = 0 resolves to fa2_kvcache_mla_sparse_num_splits(...).
+ *   fp8.      As fa2_fwd_kvcache_mla_fp8: storage only, descales at [b, h_kv], folded into the softmax scale and the fp32 output;
+ *             kv_dtype_enum == dtype_enum with null descales is the 16-bit (or f32 / f64) cache.  Unlike there a null descale is
+ *             not read as 1: an fp8 cache brings both (a quantised cache has one; pass it twice), else FA2_ERR_BAD_ARG.
+ *   Variants. FA2_KVCACHE_VARIANT_MLA16: f16 / bf16, the cache alike or fp8, d = 576 and d_v = 512, V aliasing K, the alignment
+ *             rules of fa2_fwd_kvcache_mla(_fp8), any H_kv and H / H_kv, contiguous or paged with any page size: a workgroup owns 64
+ *             heads of one (sequence, KV head, query position).  FA2_KVCACHE_VARIANT_GENERIC: everything else.  AUTO: MLA16 where
+ *             it runs, else GENERIC.  A forced MLA16 on a problem it cannot run returns FA2_ERR_UNSUPPORTED.
+ *
+ * Errors: fa2_fwd_kvcache_mla_fp8's, and FA2_ERR_BAD_ARG for null indices or index_strides, a negative index stride, topk < 1 and a
+ * launch grid that does not fit, and a null k_descale or v_descale with an fp8 cache; all before any launch.
+ */
+int fa2_fwd_kvcache_mla_sparse(const void *Q, const void *K, const void *V, void *O, void *L,
+                               const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                               const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                               const int32_t *indices, const int64_t index_strides[4], int32_t topk,
+                               const int32_t *block_table, int64_t block_table_stride,
+                               const float *k_descale, const float *v_descale,
+                               const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                               int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                               int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                               int32_t dtype_enum, int32_t kv_dtype_enum,
+                               float scale, int32_t num_splits,
+                               void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* What num_splits = 0 resolves to for it: fa2_kvcache_mla_num_splits' rule with topk in S_k's place and, for f16 / bf16 at d 576 /
+ * d_v 512, B * N_q * H_kv * ceil((H / H_kv) / 64) unsplit workgroups: 1 when that is 256 or more, else enough splits for one
+ * workgroup per CU, every split at least 4 tiles (256 slots) of the list.  Any other shape is counted as the VALU form's,
+ * B * N_q * H_kv * ceil((H / H_kv) / 16) workgroups under fa2_kvcache_num_splits' constants. */
+int32_t fa2_kvcache_mla_sparse_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t topk, int32_t d, int32_t d_v,
+                                          int32_t dtype_enum);
+
+/*
  * The fused ragged MLA step: fa2_kvcache_mla_append_varlen over cu_seqlens_q (total_new = total_q, max_seqlen_new = max_seqlen_q;
  * c_new, pe_new packed (total_q, H_kv, d_v) / (total_q, H_kv, d - d_v)), then on the same stream fa2_fwd_kvcache_mla_varlen over the
  * updated cache with seqlens_out as its cache_seqlens and, with tables, q_rot (packed, contiguous (total_q, H, d)) as its Q; q_rot
