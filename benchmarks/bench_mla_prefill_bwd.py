@@ -37,7 +37,8 @@ from bench_mla_prefill import BATCHES, CASES, D, D_V, visible_pairs  # noqa: E40
 
 OUT = os.path.join(ROOT, "profiles", "mla", "bench_mla_prefill_bwd.jsonl")
 PER = 3  # kernels of one backward call: D, the query owner, the key owner
-OURS = ("bwd_mfma16dv_kernel", "bwd_D_dv_kernel", "bwd_main_varlen", "bwd_D_varlen", "bwd_mfma16_varlen")  # the library's, by name
+# the library's, by name (the VALU kernels are bwd_main_kernel<E, MODE, F> / bwd_D_kernel<E, F> whatever the form)
+OURS = ("bwd_mfma16dv_kernel", "bwd_D_dv_kernel", "bwd_main_kernel", "bwd_D_kernel", "bwd_D_varlen", "bwd_mfma16_varlen")
 
 
 class Case:

@@ -21,6 +21,8 @@ struct Fa2BwdProblem {
     int32_t dv;  // fa2_bwd_varlen_dv: the last axis of V, O, dO, dV (Q, K, dQ, dK keep d); 0 in every other call
 };
 
+// The six fa2_bwd_launch_generic* are all in fa2_bwd_generic.hip (the attention form is a parameter of its kernel templates); the
+// matrix kernels' forms are a translation unit each.
 int fa2_bwd_launch_generic(const Fa2BwdProblem &p);
 int fa2_bwd_launch_mfma16(const Fa2BwdProblem &p);
 int fa2_bwd_launch_generic_window(const Fa2BwdProblem &p);

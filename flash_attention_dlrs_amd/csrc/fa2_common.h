@@ -23,7 +23,8 @@ struct Fa2Problem {
     int32_t dv;  // fa2_fwd_varlen_dv only: V's and O's last axis (d is Q's and K's); 0 in every other call
 };
 
-// Launchers, one per translation unit.  Return FA2_OK / FA2_ERR_*; set_error() on failure.
+// Launchers, one per translation unit -- but the six fa2_launch_generic* of fa2_generic.hip, whose one kernel template takes the
+// attention form as a parameter.  Return FA2_OK / FA2_ERR_*; set_error() on failure.
 int fa2_launch_generic(const Fa2Problem &p);
 int fa2_launch_mfma16(const Fa2Problem &p, int waves);
 int fa2_launch_mfma32(const Fa2Problem &p);
@@ -40,10 +41,10 @@ int fa2_launch_mfma16s(const Fa2Problem &p, int waves);
 int fa2_launch_mfma16h(const Fa2Problem &p, int waves);  // dispatches to the two translation units below
 int fa2_launch_mfma16h_causal(const Fa2Problem &p, int waves);
 int fa2_launch_mfma16h_noncausal(const Fa2Problem &p, int waves);
-// Local attention (fa2_fwd_window): the windowed instantiations live in translation units of their own.
+// Local attention (fa2_fwd_window): the matrix kernel's windowed instantiations live in a translation unit of their own.
 int fa2_launch_generic_window(const Fa2Problem &p);
 int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves);
-// Variable-length attention (fa2_fwd_varlen): the varlen instantiations, translation units of their own as well.
+// Variable-length attention (fa2_fwd_varlen): the matrix kernel's varlen instantiations, a translation unit of their own as well.
 int fa2_launch_generic_varlen(const Fa2Problem &p);
 int fa2_launch_mfma16d_varlen(const Fa2Problem &p, int waves);
 // Grouped-query attention (fa2_fwd_gqa, fa2_fwd_varlen_gqa): K and V have p.H / gqa heads, query head h reads KV head h / gqa.  The
@@ -53,8 +54,8 @@ int fa2_launch_mfma16d_window_gqa(const Fa2Problem &p, int waves, int gqa);
 int fa2_launch_generic_varlen_gqa(const Fa2Problem &p, int gqa);
 int fa2_launch_mfma16d_varlen_gqa(const Fa2Problem &p, int waves, int gqa);
 // A value head size of its own (fa2_fwd_varlen_dv): V and O have p.dv columns, the scores run over p.d.  The VALU form is the varlen
-// GQA instantiation of fa2_generic.hip under FA2_GENERIC_DV (fa2_generic_vgd.hip); the matrix kernel (fa2_mfma16dv.hip) takes
-// d = 192, d_v = 128.  gqa = 1 without grouped heads.
+// GQA instantiation of fa2_generic.hip with the kDv form bit; the matrix kernel (fa2_mfma16dv.hip) takes d = 192, d_v = 128.
+// gqa = 1 without grouped heads.
 int fa2_launch_generic_varlen_dv(const Fa2Problem &p, int gqa);
 int fa2_launch_mfma16dv(const Fa2Problem &p, int gqa);
 bool fa2_mfma16dv_supports(const Fa2Problem &p);
