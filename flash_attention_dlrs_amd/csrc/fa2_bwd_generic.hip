@@ -37,7 +37,7 @@ namespace {
 // kDv (with kVarlen and kGqa): a value head size of its own (fa2_bwd_varlen_dv) -- V, O, dO and dV have a.dv columns: the second
 // owned / swept operand, the dV accumulator, dP = dO V^T and D = rowsum(dO * O) run over dv, everything on the Q / K / dQ / dK
 // side over d.
-constexpr int kWindow = 1, kVarlen = 2, kGqa = 4, kDv = 8;
+// (the bits themselves: fa2_common.h)
 
 struct GArgs {  // fields a form does not use are 0
     const void *Q, *K, *V, *O, *dO, *L;

@@ -23,8 +23,9 @@ struct Fa2Problem {
     int32_t dv;  // fa2_fwd_varlen_dv only: V's and O's last axis (d is Q's and K's); 0 in every other call
 };
 
-// Launchers, one per translation unit -- but the six fa2_launch_generic* of fa2_generic.hip, whose one kernel template takes the
-// attention form as a parameter.  Return FA2_OK / FA2_ERR_*; set_error() on failure.
+// Launchers, one per translation unit -- but the six fa2_launch_generic* of fa2_generic.hip and the five fa2_launch_mfma16d* of
+// fa2_mfma16d.hip, whose one kernel template takes the attention form as a parameter.  Return FA2_OK / FA2_ERR_*; set_error() on
+// failure.
 int fa2_launch_generic(const Fa2Problem &p);
 int fa2_launch_mfma16(const Fa2Problem &p, int waves);
 int fa2_launch_mfma32(const Fa2Problem &p);
@@ -41,10 +42,10 @@ int fa2_launch_mfma16s(const Fa2Problem &p, int waves);
 int fa2_launch_mfma16h(const Fa2Problem &p, int waves);  // dispatches to the two translation units below
 int fa2_launch_mfma16h_causal(const Fa2Problem &p, int waves);
 int fa2_launch_mfma16h_noncausal(const Fa2Problem &p, int waves);
-// Local attention (fa2_fwd_window): the matrix kernel's windowed instantiations live in a translation unit of their own.
+// Local attention (fa2_fwd_window).
 int fa2_launch_generic_window(const Fa2Problem &p);
 int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves);
-// Variable-length attention (fa2_fwd_varlen): the matrix kernel's varlen instantiations, a translation unit of their own as well.
+// Variable-length attention (fa2_fwd_varlen).
 int fa2_launch_generic_varlen(const Fa2Problem &p);
 int fa2_launch_mfma16d_varlen(const Fa2Problem &p, int waves);
 // Grouped-query attention (fa2_fwd_gqa, fa2_fwd_varlen_gqa): K and V have p.H / gqa heads, query head h reads KV head h / gqa.  The
@@ -107,6 +108,12 @@ static inline int fa2_dtype_size(int dt) {
 }
 
 #define FA2_LOG2E 1.4426950408889634  // np.log2(np.e), src/flash_attention_kernels.py:9
+
+// The attention forms of the kernel templates that take them as a parameter F (fa2_generic_kernel.h, fa2_bwd_generic.hip,
+// fa2_mfma16d_kernel.h): a set of these bits, 0 = plain attention.  kWindow: the band i - wl <= j <= i + wr;
+// kVarlen (with kWindow): packed sequences; kGqa (with kWindow): H / gqa KV heads; kDv (VALU kernels, with kVarlen and kGqa): a value
+// head size of its own.  What a bit means inside a kernel is described at the head of that kernel's file.
+constexpr int kWindow = 1, kVarlen = 2, kGqa = 4, kDv = 8;
 
 // Sequence b of a packed (varlen) batch: every offset read is clamped to [0, total], end < start is empty and at most max_len
 // rows are taken -- malformed offsets give wrong numbers at worst, never an access outside the tensors.

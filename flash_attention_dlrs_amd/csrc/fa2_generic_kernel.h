@@ -38,7 +38,7 @@ namespace fa2_generic {
 // kGqa (with kWindow): grouped-query attention -- K and V have H / gqa heads and query head h reads KV head h / gqa.
 // kDv (with kVarlen and kGqa): a value head size of its own (fa2_fwd_varlen_dv at d_v != d) -- the score loop runs over d, the
 // output columns per lane come from d_v, LDS holds the Q tile at d.
-constexpr int kWindow = 1, kVarlen = 2, kGqa = 4, kDv = 8;
+// (the bits themselves: fa2_common.h)
 
 constexpr int kRowsPerWave = 4;
 constexpr int kWaves = 4;

@@ -1,623 +1,23 @@
-// fa2_mfma16d.hip -- the software-pipelined f16 / bf16 kernel of fa2_mfma16p.hip with LDS-DMA staging
-// (variant "mfma16d").  Same arithmetic (src/flash_attention_kernels.py:84-108), same 32-key block schedule
-// (QK^T of block j+1 under the softmax of block j), same K-unit / V-tile scheme; what changes is how a tile
-// gets from HBM/L2 into LDS: `buffer_load_dwordx4 ... lds` writes 1 KiB per wave-instruction straight into
-// LDS -- no staging registers, no ds_write_b128 (ablation of fa2_mfma16p.hip: its LDS writes cost ~11 %).
-//
-// LDS-DMA writes lane-linearly (M0 base + lane * 16), so rows cannot be padded: the tile image is plain
-// 256-byte (d = 128) or 128-byte (d = 64) rows with the 16-byte chunks XOR-swizzled THROUGH THE SOURCE
-// ADDRESS (the lane that fills (row, slot) fetches global chunk slot ^ f(row)) and the same XOR on every read.
-// f is the involution swz() of lds_off() (fa2_mfma.h): conflict-free for the ds_read_b128 row reads of K and for
-// the ds_read_b64_tr_b16 transposed reads of V.  Rows past N (and the "negative" rows of K unit 0) are
-// zero-filled by the buffer descriptor's range check.
-#include "fa2_common.h"
-#include "fa2_mfma.h"
+// fa2_mfma16d.hip -- the launchers of the LDS-DMA forward kernel (fa2_mfma16d_kernel.h, variant "mfma16d"), one per attention form,
+// and its bf16 instantiations; the f16 ones compile in fa2_mfma16d_f16.hip.
+#include "fa2_mfma16d_kernel.h"
 
-// FA2_MFMA16D_WINDOW (fa2_mfma16d_w.hip): the local-attention form -- key j visible to query i iff i - wl <= j <= i + wr, one tile per
-// workgroup, the key loop from the 64-key unit of the tile's first visible key, blocks outside a wave's band skipped, blocks across
-// its edges masked -- under its own kernel name, compiled in a translation unit of its own; without the macro this file is the
-// plain kernel, unchanged.
-// FA2_MFMA16D_VARLEN (fa2_mfma16d_v.hip, on top of FA2_MFMA16D_WINDOW): the variable-length form -- one tile of ceil(max_q / BR)
-// per workgroup and sequence; the workgroup reads its sequence's offsets, leaves when its tile starts past the sequence's queries,
-// and runs the windowed loop with the query extent NQ, the key extent NK and the bottom-right shifted band (fa2_varlen_band).
-// Base pointers are built in 64 bits from the sequence starts, so the 32-bit buffer offsets only span one sequence.  A row
-// without a visible key gets O = 0 and L = +inf.
-// FA2_MFMA16D_GQA (fa2_mfma16d_wg.hip, fa2_mfma16d_vg.hip, on top of the windowed or varlen form): grouped-query attention --
-// K and V have H / group heads and query head hh reads KV head hh / group; everything else is the form below it.
-#if defined(FA2_MFMA16D_GQA) && defined(FA2_MFMA16D_VARLEN)
-#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_varlen_gqa_kernel
-#elif defined(FA2_MFMA16D_GQA)
-#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_window_gqa_kernel
-#elif defined(FA2_MFMA16D_VARLEN)
-#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_varlen_kernel
-#elif defined(FA2_MFMA16D_WINDOW)
-#define fa2_fwd_mfma16d_kernel fa2_fwd_mfma16d_window_kernel
-#endif
+using namespace fa2_mfma16d;
 
 namespace {
 
-struct DmaArgs {
-    const char *Q, *K, *V;
-    char *O, *L;
-    int64_t qs[3], ks[3], vs[3], os[3];  // B, H, N strides in bytes
-    int64_t ls[2];
-    int B, H, N;
-    float c_log2e;
-    int group;
-#if defined(FA2_MFMA16D_VARLEN)
-    int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
-    int wl, wr;  // raw window sides (-1 = unbounded), shifted per sequence by fa2_varlen_band
-    int causal;
-    const int32_t *cu_q, *cu_k;
-    int max_q, max_k, total_q, total_k;
-#elif defined(FA2_MFMA16D_WINDOW)
-    int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
-    int wl, wr;  // window sides, normalised to [0, N - 1] (fa2_window_normalise)
-#else
-    int flags;  // experiment switches (FA2_FLAGS): 1 = static priority for waves 4..7
-#endif
-#ifdef FA2_MFMA16D_GQA
-    int gqa;  // query heads per KV head
-#endif
-};
-
-template <typename T, int D, int NW, bool CAUSAL>
-__global__ __launch_bounds__(NW * 64, 2) void fa2_fwd_mfma16d_kernel(const DmaArgs a) {
-    using M = Mma<T>;
-    using frag = typename M::frag;
-    constexpr int BR = NW * 32;
-    constexpr int ROWB = D * 2, CPR = ROWB / 16;   // bytes per row, 16-byte chunks per row
-    constexpr int TILEB = 64 * ROWB;               // K unit = V tile = 64 rows
-    constexpr int RPP = 1024 / ROWB;               // rows per 1-KiB DMA piece (4 or 8)
-    constexpr int PIECES = TILEB / 1024, PPW = PIECES / NW;  // pieces per tile, per wave
-    constexpr int VBASE = 2 * TILEB;               // LDS: Kunit0 | Kunit1 | Vtile0 | Vtile1
-    constexpr int KS = D / 16, DB = D / 32;
-    static_assert(PPW >= 1, "too many waves for this tile");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    LDS_PTR(char) lds = (LDS_PTR(char))smem;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform (M0, scalar branches)
-    const int i = lane & 31, h = lane >> 5;
-#if defined(FA2_MFMA16D_VARLEN)
-    const int N = a.max_q;  // (only the tile count below: the sequence's own extents are NQ and NK)
-#elif defined(FA2_MFMA16D_WINDOW)
-    const int N = a.N;
-    const int wl = a.wl, wr = a.wr;
-    const int NQ = N, NK = N;
-#else
-    const int N = a.N;
-#endif
-    // T5 static form (cdna_hip_programming.md): the second-dispatched half loses VALU arbitration on every segment
-    if ((a.flags & 1) && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-
-    // Causal: a workgroup owns the PAIR of Q tiles (nq-1-p, p) of one (b, h) and runs them back to back, heavy one
-    // first -- every workgroup then does the same amount of work (nq+1 tile-steps), so the 256 CUs finish together
-    // instead of trailing off through the light tiles; the pair shares its K/V through L2.  Non-causal: one tile.
-    const int nq = (N + BR - 1) / BR, nbh = a.B * a.H;
-    const int nunit = CAUSAL ? (nq + 1) / 2 : nq;  // work units (tile pairs / tiles) per (b, h)
-    int bh, unit;
-    {
-        const int bid = blockIdx.x;
-        if ((nbh & 7) == 0) {  // whole (b, h) groups per XCD (speed only)
-            const int slot = bid >> 3, G = a.group;
-            const int batch = slot / (G * nunit), r = slot - batch * (G * nunit);
-            bh = (batch * G + r % G) * 8 + (bid & 7);
-            unit = r / G;
-        } else {
-            bh = bid / nunit;
-            unit = bid % nunit;
-        }
-    }
-    const int qi_first = CAUSAL ? nq - 1 - unit : unit, qi_second = unit;
-    const int npass = (CAUSAL && qi_second != qi_first) ? 2 : 1;
-    const int b = bh / a.H, hh = bh - b * a.H;
-    int q0 = 0, qrow = 0;  // set per pass
-
-#ifdef FA2_MFMA16D_VARLEN
-    int qst, NQ, kst, NK;
-    fa2_varlen_seq(a.cu_q, b, a.total_q, a.max_q, qst, NQ);
-    fa2_varlen_seq(a.cu_k, b, a.total_k, a.max_k, kst, NK);
-    qst = __builtin_amdgcn_readfirstlane(qst);
-    NQ = __builtin_amdgcn_readfirstlane(NQ);
-    kst = __builtin_amdgcn_readfirstlane(kst);
-    NK = __builtin_amdgcn_readfirstlane(NK);
-    if (qi_first * BR >= NQ) return;  // (whole workgroup, before any barrier)
-    int wl, wr;
-    fa2_varlen_band(NQ, NK, a.causal, a.wl, a.wr, wl, wr);
-#ifdef FA2_MFMA16D_GQA
-    const int hk = hh / a.gqa;
-    const char *Qp = a.Q + (int64_t)qst * a.qs[2] + (int64_t)hh * a.qs[1];
-    const char *Kp = a.K + (int64_t)kst * a.ks[2] + (int64_t)hk * a.ks[1];
-    const char *Vp = a.V + (int64_t)kst * a.vs[2] + (int64_t)hk * a.vs[1];
-#else
-    const char *Qp = a.Q + (int64_t)qst * a.qs[2] + (int64_t)hh * a.qs[1];
-    const char *Kp = a.K + (int64_t)kst * a.ks[2] + (int64_t)hh * a.ks[1];
-    const char *Vp = a.V + (int64_t)kst * a.vs[2] + (int64_t)hh * a.vs[1];
-#endif
-#elif defined(FA2_MFMA16D_GQA)
-    const int hk = hh / a.gqa;
-    const char *Qp = a.Q + (int64_t)b * a.qs[0] + (int64_t)hh * a.qs[1];
-    const char *Kp = a.K + (int64_t)b * a.ks[0] + (int64_t)hk * a.ks[1];
-    const char *Vp = a.V + (int64_t)b * a.vs[0] + (int64_t)hk * a.vs[1];
-#else
-    const char *Qp = a.Q + (int64_t)b * a.qs[0] + (int64_t)hh * a.qs[1];
-    const char *Kp = a.K + (int64_t)b * a.ks[0] + (int64_t)hh * a.ks[1];
-    const char *Vp = a.V + (int64_t)b * a.vs[0] + (int64_t)hh * a.vs[1];
-#endif
-
-    frag qf[KS];
-
-    // ---- DMA staging.  Piece p of a tile = rows RPP*p .. RPP*p+RPP-1 = 1 KiB of LDS; wave w issues pieces
-    // w, w+NW, ...  Lane l fills LDS (row = RPP*p + l / CPR, slot = l % CPR) with global chunk slot ^ f(row).
-    const int krs = (int)a.ks[2], vrs = (int)a.vs[2];
-    // descriptors built from wave-uniform scalars: {base lo, base hi, bytes, flags}; raw buffer (stride 0)
-    auto make_rsrc = [&](const char *base, int bytes) {
-        const uint64_t ba = (uint64_t)base;
-        i32x4 r;
-        r[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)ba);
-        r[1] = __builtin_amdgcn_readfirstlane((int)((uint32_t)(ba >> 32) & 0xffffu));
-        r[2] = __builtin_amdgcn_readfirstlane(bytes);
-        r[3] = 0x00020000;
-        return r;
-    };
-#ifdef FA2_MFMA16D_VARLEN
-    // (NK = 0: an empty range -- every load reads 0, and no block is active)
-    const i32x4 krsrc = make_rsrc(Kp, NK > 0 ? (NK - 1) * krs + ROWB : 0);
-    const i32x4 vrsrc = make_rsrc(Vp, NK > 0 ? (NK - 1) * vrs + ROWB : 0);
-#else
-    const i32x4 krsrc = make_rsrc(Kp, (N - 1) * krs + ROWB);
-    const i32x4 vrsrc = make_rsrc(Vp, (N - 1) * vrs + ROWB);
-#endif
-    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
-    int kvo[PPW], vvo[PPW];
-#pragma unroll
-    for (int pp = 0; pp < PPW; ++pp) {
-        const int row = RPP * (wave + pp * NW) + lane / CPR, slot = lane % CPR;
-        const int chunk = slot ^ swz<D>(row);
-        kvo[pp] = row * krs + chunk * 16;
-        vvo[pp] = row * vrs + chunk * 16;
-    }
-    auto dma_k = [&](int u, int buf) {  // K unit u = keys 64u-32 .. 64u+31 -> LDS K buffer buf
-        const int base = (u * 64 - 32) * krs;  // in the VGPR offset: range-checked ("negative" rows wrap -> zero)
-#pragma unroll
-        for (int pp = 0; pp < PPW; ++pp) dma16(krsrc, lds_base + buf * TILEB + (wave + pp * NW) * 1024, kvo[pp] + base);
-    };
-    auto dma_v = [&](int t, int buf) {
-        const int base = t * 64 * vrs;
-#pragma unroll
-        for (int pp = 0; pp < PPW; ++pp)
-            dma16(vrsrc, lds_base + VBASE + buf * TILEB + (wave + pp * NW) * 1024, vvo[pp] + base);
-    };
-
-    int kend = 0, nt = 0, nblk = 0, nb = 0;  // set per pass
-
-    // ---- per-lane swizzled read offsets
-    int k_off[KS];  // K row read: row (half*32 + i), chunk 2ks + h
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) k_off[ks] = lds_off<D>(i, 2 * ks + h);
-    int v_off[2][DB];  // V transposed read (see fa2_mfma16.hip): u = keys +0..3 / +8..11 of the 16-key step
-    {
-        const int w = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-                v_off[u][db] = VBASE + lds_off<D>(8 * u + 4 * h + qq, 4 * db + 2 * w + (pp >> 1)) + 8 * (pp & 1);
-    }
-
-    f32x16 o[DB];
-    float m = -INFINITY, lsum = 0.0f;
-    const float c = a.c_log2e;
-    // Rescale threshold in log2 units: P may reach 2^kThr before the running max is raised.  bf16 P has the
-    // fp32 exponent range (24 leaves 2^24 * N far below fp32 overflow in l and O); f16 P must stay below 65504.
-    // On N(0,1) inputs at scale 1 (score sigma ~ 16 log2 units) a threshold of 8 still fired ~20 times per wave
-    // and 4096 keys -- each time the whole workgroup waits at the next barrier -- 24 makes it rare.
-    constexpr float kThr = sizeof(T) == 2 && __is_same(T, _Float16) ? 12.0f : 60.0f;  // bf16: 60 (round 2): see fa2_a64.hip
-
-    auto qk = [&](f32x16 &s, int koff) {  // koff = buffer base + half * 32 rows
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const u32x4 kf = *(LDS_PTR(u32x4))(lds + koff + k_off[ks]);
-            s = M::mfma(__builtin_bit_cast(frag, kf), qf[ks], s);
-        }
-    };
-    auto partial = [&](f32x16 &s, int j, float &coeff, bool masked) -> bool {
-        if (masked) {
-#ifdef FA2_MFMA16D_WINDOW
-            const int lim = qrow + wr < NK - 1 ? qrow + wr : NK - 1;
-            const int klim = lim - (j * 32 + 4 * h), klo = qrow - wl - (j * 32 + 4 * h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if ((r & 3) + 8 * (r >> 2) > klim || (r & 3) + 8 * (r >> 2) < klo) s[r] = -INFINITY;
-#else
-            int lim = N - 1;
-            if (CAUSAL) lim = qrow < lim ? qrow : lim;
-            const int klim = lim - (j * 32 + 4 * h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if ((r & 3) + 8 * (r >> 2) > klim) s[r] = -INFINITY;
-#endif
-        }
-        float mx = fmaxf(s[0], s[1]);
-#pragma unroll
-        for (int r = 2; r < 16; ++r) mx = fmaxf(mx, s[r]);
-        mx = half_swap_max(mx) * c;
-        const bool fire = !__all(mx - m <= kThr);  // deferred running max, see fa2_mfma16p.hip
-        coeff = 1.0f;
-        if (fire) {
-            const float m_new = fmaxf(m, mx);
-            coeff = __builtin_amdgcn_exp2f(m - m_new);
-            m = m_new;
-        }
-        return fire;
-    };
-    auto finish = [&](f32x16 &s, frag (&pf)[2]) {
-        float rs = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c, -m));
-            rs += p;
-            pf[r >> 3][r & 7] = (T)p;
-        }
-        lsum += rs;
-    };
-    auto rescale = [&](bool fire, float coeff) {
-        if (fire) {
-            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float x = o[db][r];
-                    asm volatile("v_mul_f32 %0, %0, %1" : "+v"(x) : "v"(coeff));
-                    o[db][r] = x;
-                }
-            asm volatile("s_nop 7" ::: "memory");
-            lsum *= coeff;
-        }
-    };
-    auto pv = [&](frag (&pf)[2], int voff) {  // voff = buffer base + half * 32 rows
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const int rowb = voff + ss * 16 * ROWB;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + rowb + v_off[0][db]));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(lds + rowb + v_off[1][db]));
-                const s16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                o[db] = M::mfma(__builtin_bit_cast(frag, vf), pf[ss], o[db]);
-            }
-    };
-#ifdef FA2_MFMA16D_WINDOW
-    auto block_masked = [&](int j) { return (j * 32 + 32 > NK) || (j * 32 < q0 + 31 - wl) || (j * 32 + 31 > q0 + wr); };
-#else
-    auto block_masked = [&](int j) { return (CAUSAL && (j * 32 + 31 > q0)) || (j * 32 + 32 > N); };
-#endif
-
-    for (int pass = 0; pass < npass; ++pass) {
-        const int qi = pass == 0 ? qi_first : qi_second;
-        q0 = qi * BR + wave * 32;
-        qrow = q0 + i;
-        {
-#ifdef FA2_MFMA16D_WINDOW
-            const int row = qrow < NQ ? qrow : NQ - 1;
-#else
-            const int row = qrow < N ? qrow : N - 1;
-#endif
-            const char *qp = Qp + (int64_t)row * a.qs[2] + h * 16;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(frag, *(const u32x4 *)(qp + ks * 32));
-        }
-#ifdef FA2_MFMA16D_WINDOW
-        // window: the keys of the tile's rows [qi BR - wl, qi BR + BR - 1 + wr]; the loop starts at the 64-key unit t0 of the
-        // first one.  Per wave: blocks [jlo, nb) meet its band, the others are skipped
-        kend = qi * BR + BR + wr < NK ? qi * BR + BR + wr : NK;
-        const int t0 = qi * BR - wl > 0 ? (qi * BR - wl) >> 6 : 0;
-        const int jlo = q0 - wl > 0 ? (q0 - wl) >> 5 : 0;
-        nt = (kend + 63) >> 6;    // V tiles (loop iterations t0 .. nt-1)
-        nblk = (kend + 31) >> 5;  // 32-key blocks of this tile
-        {
-            const int hi = q0 + 31 + wr < NK - 1 ? q0 + 31 + wr : NK - 1;
-            nb = (hi >> 5) + 1 < nblk ? (hi >> 5) + 1 : nblk;
-        }
-        auto act = [&](int j) { return j >= jlo && j < nb; };
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-        // a row may meet whole blocks before its band starts: a finite floor keeps exp2(m_old - m_new) and exp2(-inf - m) at 0
-        // there instead of exp2(-inf + inf); the row's first visible key raises m above it at once (fire below)
-        m = -1e30f;
-        lsum = 0.0f;
-
-        // ---- prologue: K units t0, t0 + 1 and V tile t0 (the buffers alternate from t0 on)
-        dma_k(t0, 0);
-        dma_v(t0, 0);
-        dma_k(t0 + 1, 1);
-        dma_wait();
-        __syncthreads();
-
-        f32x16 sA, sB;
-        float coeffA = 1.0f, coeffB = 1.0f;
-        bool fireA = false, fireB = false;
-        frag pf[2];
-        if (act(2 * t0)) {
-            qk(sA, 32 * ROWB);  // block 2 t0 = rows 32..63 of K unit t0
-            fireA = partial(sA, 2 * t0, coeffA, block_masked(2 * t0));
-        }
-        __syncthreads();    // K unit t0 is overwritten by unit t0 + 2 in iteration t0
-
-        // steady iterations t: block 2t computed, blocks 2t+1 and 2t+2 inside the band for all 32 rows of the wave
-        const int ulo = q0 + 31 - wl > 0 ? (q0 + 31 - wl + 31) >> 5 : 0;  // first block without a left-edge mask
-        int umax = q0 + wr - 31 < 0 ? -1 : (q0 + wr - 31) >> 5;            // last block without a right-edge mask
-        umax = (NK >> 5) - 1 < umax ? (NK >> 5) - 1 : umax;
-        int t_head = (jlo + 1) >> 1 > (ulo >> 1) ? (jlo + 1) >> 1 : ulo >> 1;
-        t_head = t_head < t0 ? t0 : (t_head > nt ? nt : t_head);
-        int t_steady = umax >= 2 ? (umax - 2) / 2 + 1 : 0;
-        t_steady = t_steady < t_head ? t_head : (t_steady > nt ? nt : t_steady);
-
-        // head and tail iterations: every block guarded, edge blocks masked
-        auto guarded_step = [&](int t) __attribute__((always_inline)) {
-            const bool more = t + 1 < nt;
-            if (more) {
-                dma_k(t + 2, (t - t0) & 1);
-                dma_v(t + 1, (t + 1 - t0) & 1);
-            }
-            const int kcur = ((t + 1 - t0) & 1) * TILEB;
-            const int vcur = ((t - t0) & 1) * TILEB;
-            const int jA = 2 * t, jB = 2 * t + 1, jA2 = 2 * t + 2;
-            if (act(jA)) rescale(fireA, coeffA);
-            if (act(jB)) qk(sB, kcur);
-            if (act(jA)) {
-                finish(sA, pf);
-                pv(pf, vcur);
-            }
-            if (act(jB)) {
-                fireB = partial(sB, jB, coeffB, block_masked(jB));
-                rescale(fireB, coeffB);
-            }
-            if (act(jA2)) qk(sA, kcur + 32 * ROWB);
-            if (act(jB)) {
-                finish(sB, pf);
-                pv(pf, vcur + 32 * ROWB);
-            }
-            if (act(jA2)) fireA = partial(sA, jA2, coeffA, block_masked(jA2));
-            dma_wait();
-            __syncthreads();
-        };
-
-        int t = t0;
-        for (; t < t_head; ++t) guarded_step(t);
-        for (; t < t_steady; ++t) {
-            dma_k(t + 2, (t - t0) & 1);
-            dma_v(t + 1, (t + 1 - t0) & 1);
-            const int kcur = ((t + 1 - t0) & 1) * TILEB;  // K unit t+1: rows 0..31 = block 2t+1, rows 32..63 = block 2t+2
-            const int vcur = ((t - t0) & 1) * TILEB;      // V tile t:   rows 0..31 = block 2t,   rows 32..63 = block 2t+1
-            rescale(fireA, coeffA);
-            qk(sB, kcur);
-            finish(sA, pf);
-            pv(pf, vcur);
-            fireB = partial(sB, 2 * t + 1, coeffB, false);
-            rescale(fireB, coeffB);
-            qk(sA, kcur + 32 * ROWB);
-            finish(sB, pf);
-            pv(pf, vcur + 32 * ROWB);
-            fireA = partial(sA, 2 * t + 2, coeffA, false);
-            dma_wait();
-            __syncthreads();
-        }
-        for (; t < nt; ++t) guarded_step(t);
-
-#else
-        kend = CAUSAL ? ((qi * BR + BR) < N ? (qi * BR + BR) : N) : N;
-        nt = (kend + 63) >> 6;    // V tiles (= loop iterations)
-        nblk = (kend + 31) >> 5;  // 32-key blocks of this tile
-        nb = nblk;                // ... of this wave (causal: up to its diagonal block)
-        if (CAUSAL) nb = (q0 >> 5) + 1 < nblk ? (q0 >> 5) + 1 : nblk;
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-        m = -INFINITY;
-        lsum = 0.0f;
-
-        // ---- prologue: K units 0, 1 and V tile 0
-        dma_k(0, 0);
-        dma_v(0, 0);
-        dma_k(1, 1);
-        dma_wait();
-        __syncthreads();
-
-        f32x16 sA, sB;
-        float coeffA = 1.0f, coeffB = 1.0f;
-        bool fireA = false, fireB = false;
-        frag pf[2];
-        qk(sA, 32 * ROWB);  // block 0 = rows 32..63 of K unit 0
-        fireA = partial(sA, 0, coeffA, block_masked(0));
-        __syncthreads();    // K unit 0 is overwritten by unit 2 in iteration 0
-
-        int jm = nb;
-        if (CAUSAL) jm = (q0 >> 5) < jm ? (q0 >> 5) : jm;
-        if ((N >> 5) < jm) jm = N >> 5;
-        int t_steady = (jm - 1) / 2;
-        t_steady = t_steady < 0 ? 0 : (t_steady > nt ? nt : t_steady);
-
-        int t = 0;
-        for (; t < t_steady; ++t) {
-            // both target buffers were released by the barrier that ended iteration t-1; the DMA has the whole
-            // iteration to land and is published by the barrier at its end
-            dma_k(t + 2, t & 1);
-            dma_v(t + 1, (t + 1) & 1);
-            const int kcur = ((t + 1) & 1) * TILEB;  // K unit t+1: rows 0..31 = block 2t+1, rows 32..63 = block 2t+2
-            const int vcur = (t & 1) * TILEB;        // V tile t:   rows 0..31 = block 2t,   rows 32..63 = block 2t+1
-            rescale(fireA, coeffA);
-            qk(sB, kcur);
-            finish(sA, pf);
-            pv(pf, vcur);
-            fireB = partial(sB, 2 * t + 1, coeffB, false);
-            rescale(fireB, coeffB);
-            qk(sA, kcur + 32 * ROWB);
-            finish(sB, pf);
-            pv(pf, vcur + 32 * ROWB);
-            fireA = partial(sA, 2 * t + 2, coeffA, false);
-            dma_wait();  // this wave's pieces of (K unit t+2, V tile t+1) have landed; the barrier publishes them
-            __syncthreads();
-        }
-        for (; t < nt; ++t) {
-            const bool more = t + 1 < nt;
-            if (more) {
-                dma_k(t + 2, t & 1);
-                dma_v(t + 1, (t + 1) & 1);
-            }
-            const int kcur = ((t + 1) & 1) * TILEB;
-            const int vcur = (t & 1) * TILEB;
-            const int jA = 2 * t, jB = 2 * t + 1, jA2 = 2 * t + 2;
-            if (jA < nb) rescale(fireA, coeffA);
-            if (jB < nb) qk(sB, kcur);
-            if (jA < nb) {
-                finish(sA, pf);
-                pv(pf, vcur);
-            }
-            if (jB < nb) {
-                fireB = partial(sB, jB, coeffB, block_masked(jB));
-                rescale(fireB, coeffB);
-            }
-            if (jA2 < nb) qk(sA, kcur + 32 * ROWB);
-            if (jB < nb) {
-                finish(sB, pf);
-                pv(pf, vcur + 32 * ROWB);
-            }
-            if (jA2 < nb) fireA = partial(sA, jA2, coeffA, block_masked(jA2));
-            dma_wait();
-            __syncthreads();
-        }
-
-#endif
-        // ---- epilogue (kernels.py:105-108).  A lane owns one ROW of O (columns 32db + 8g + 4h ..+3): stored straight
-        // from the accumulators that is 16 eight-byte stores per lane, each instruction touching 32 rows.  Instead the
-        // wave's 32 x D tile goes through its own 32*ROWB-byte slice of the (now idle) K/V buffers and leaves as
-        // whole rows: ROWB/16 lanes x 16 bytes per row, 1 KiB contiguous per store instruction.
-        const float l = half_swap_sum(lsum);
-#ifdef FA2_MFMA16D_VARLEN
-        const float inv = l > 0.0f ? 1.0f / l : 0.0f;  // a row without a visible key: O = 0
-#else
-        const float inv = 1.0f / l;
-#endif
-        {
-            const int ebase = wave * 32 * ROWB;  // NW * 32 * ROWB <= 4 * TILEB
-#pragma unroll
-            for (int db = 0; db < DB; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    typedef __attribute__((ext_vector_type(4))) T Tx4;
-                    Tx4 v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = (T)(o[db][4 * g + j] * inv);
-                    *(LDS_PTR(u32x2))(lds + ebase + lds_off<D>(i, 4 * db + g) + 8 * h) = __builtin_bit_cast(u32x2, v);
-                }
-            // same wave wrote and reads: LDS executes a wave's accesses in order; no other wave touches this slice
-            // until the barrier below
-            constexpr int RPI = 64 / CPR;  // rows per store instruction (4 at d = 128, 8 at d = 64)
-            const int er = lane / CPR, ec = lane % CPR;
-#ifdef FA2_MFMA16D_VARLEN
-            char *ob = a.O + (int64_t)qst * a.os[2] + (int64_t)hh * a.os[1];
-#pragma unroll
-            for (int k = 0; k < 32 / RPI; ++k) {
-                const int r = k * RPI + er;
-                const u32x4 val = *(LDS_PTR(u32x4))(lds + ebase + lds_off<D>(r, ec));
-                if (q0 + r < NQ) *(u32x4 *)(ob + (int64_t)(q0 + r) * a.os[2] + ec * 16) = val;
-            }
-        }
-        if (qrow < NQ && h == 0) {
-            T *lp = (T *)a.L + hh * a.ls[1] + qst + qrow;
-            *lp = l > 0.0f ? (T)(m + __builtin_amdgcn_logf(l)) : (T)INFINITY;  // no visible key: L = +inf
-        }
-#else
-            char *ob = a.O + (int64_t)b * a.os[0] + (int64_t)hh * a.os[1];
-#pragma unroll
-            for (int k = 0; k < 32 / RPI; ++k) {
-                const int r = k * RPI + er;
-                const u32x4 val = *(LDS_PTR(u32x4))(lds + ebase + lds_off<D>(r, ec));
-                if (q0 + r < N) *(u32x4 *)(ob + (int64_t)(q0 + r) * a.os[2] + ec * 16) = val;
-            }
-        }
-        if (qrow < N && h == 0) {
-            T *lp = (T *)a.L + b * a.ls[0] + hh * a.ls[1] + qrow;
-            *lp = (T)(m + __builtin_amdgcn_logf(l));
-        }
-#endif
-        if (pass + 1 < npass) __syncthreads();  // the next pass's DMA reuses the slices
-
-    }  // pass
-}
-
-template <typename T, int D, int NW> int launch_t(const Fa2Problem &p, const DmaArgs &a) {
-    constexpr int BR = NW * 32;
-#ifdef FA2_MFMA16D_VARLEN
-    const int nq = (p.max_q + BR - 1) / BR;
-#else
-    const int nq = (p.N + BR - 1) / BR;
-#endif
-    const long long nblk = (long long)(p.causal ? (nq + 1) / 2 : nq) * p.B * p.H;  // causal: one workgroup per tile pair
-    if (nblk > 0x7fffffffLL) {
-        fa2_set_error("mfma16d: grid too large");
-        return FA2_ERR_BAD_ARG;
-    }
-    const dim3 grid((unsigned)nblk), block(NW * 64);
-    constexpr size_t smem = 4 * 64 * D * 2;  // 64 KiB (d = 128) / 32 KiB (d = 64)
-#ifdef FA2_MFMA16D_WINDOW
-    hipLaunchKernelGGL((fa2_fwd_mfma16d_kernel<T, D, NW, false>), grid, block, smem, p.stream, a);  // (p.causal is 0: in wr)
-#else
-    if (p.causal)
-        hipLaunchKernelGGL((fa2_fwd_mfma16d_kernel<T, D, NW, true>), grid, block, smem, p.stream, a);
-    else
-        hipLaunchKernelGGL((fa2_fwd_mfma16d_kernel<T, D, NW, false>), grid, block, smem, p.stream, a);
-#endif
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fa2_set_error("mfma16d kernel launch failed: %s", hipGetErrorString(e));
-        return FA2_ERR_LAUNCH;
-    }
-    return FA2_OK;
-}
-
-template <typename T> int launch_d(const Fa2Problem &p, const DmaArgs &a, int waves) {
-    if (p.d == 128) return waves == 8 ? launch_t<T, 128, 8>(p, a) : launch_t<T, 128, 4>(p, a);
-    return waves == 8 ? launch_t<T, 64, 8>(p, a) : launch_t<T, 64, 4>(p, a);
-}
-
-}  // namespace
-
-#if defined(FA2_MFMA16D_GQA) && defined(FA2_MFMA16D_VARLEN)
-int fa2_launch_mfma16d_varlen_gqa(const Fa2Problem &pv, int waves, int gqa) {
+template <int F> int launch_form(const Fa2Problem &pv, int waves, int gqa) {
     Fa2Problem p = pv;
-    p.causal = 0;
-    const bool fits32 = (int64_t)(p.max_k + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.max_k + 512) * p.vs[2] * 2 < (1LL << 31);
-#elif defined(FA2_MFMA16D_GQA)
-int fa2_launch_mfma16d_window_gqa(const Fa2Problem &p, int waves, int gqa) {
-    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
-#elif defined(FA2_MFMA16D_VARLEN)
-int fa2_launch_mfma16d_varlen(const Fa2Problem &pv, int waves) {
-    Fa2Problem p = pv;
-    p.causal = 0;  // the causal mask is in the band (fa2_varlen_band): one tile per workgroup, no tile pairs
-    // 32-bit buffer offsets span one sequence: judged on max_seqlen x row stride, not on the packed total
-    const bool fits32 = (int64_t)(p.max_k + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.max_k + 512) * p.vs[2] * 2 < (1LL << 31);
-#elif defined(FA2_MFMA16D_WINDOW)
-int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves) {
-    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
-#else
-int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
-    const bool fits32 = (int64_t)(p.N + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(p.N + 512) * p.vs[2] * 2 < (1LL << 31);
-#endif
+    if constexpr (F & kVarlen) p.causal = 0;  // the causal mask is in the band (fa2_varlen_band): one tile per workgroup, no tile pairs
+    // 32-bit buffer offsets span one sequence: kVarlen is judged on max_seqlen x row stride, not on the packed total
+    const int nk = F & kVarlen ? p.max_k : p.N;
+    const bool fits32 = (int64_t)(nk + 512) * p.ks[2] * 2 < (1LL << 31) && (int64_t)(nk + 512) * p.vs[2] * 2 < (1LL << 31);
     if (!fa2_mfma16_supports(p) || !fits32) {
         fa2_set_error("mfma16d kernel: needs f16/bf16, d in {64,128}, unit d-stride, 16-byte aligned rows, scale > 0, "
                       "N * row stride < 2 GiB");
         return FA2_ERR_UNSUPPORTED;
     }
-    DmaArgs a;
+    DmaArgs a = {};
     a.Q = (const char *)p.Q; a.K = (const char *)p.K; a.V = (const char *)p.V;
     a.O = (char *)p.O; a.L = (char *)p.L;
     for (int k = 0; k < 3; ++k) {
@@ -627,23 +27,14 @@ int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
     a.B = p.B; a.H = p.H; a.N = p.N;
     a.c_log2e = (float)((double)p.scale * FA2_LOG2E);
     a.group = 1;
-#if defined(FA2_MFMA16D_VARLEN)
     a.flags = fa2_env_int("FA2_FLAGS", 0);
-    a.wl = p.wl;
-    a.wr = p.wr;
-    a.causal = pv.causal;
-    a.cu_q = p.cu_q; a.cu_k = p.cu_k; a.max_q = p.max_q; a.max_k = p.max_k; a.total_q = p.total_q; a.total_k = p.total_k;
-    if (p.max_q == 0) return FA2_OK;  // no query rows anywhere
-#elif defined(FA2_MFMA16D_WINDOW)
-    a.flags = fa2_env_int("FA2_FLAGS", 0);
-    a.wl = p.wl;
-    a.wr = p.wr;
-#else
-    a.flags = fa2_env_int("FA2_FLAGS", 0);
-#endif
-#ifdef FA2_MFMA16D_GQA
-    a.gqa = gqa;
-#endif
+    if constexpr (F & kWindow) { a.wl = p.wl; a.wr = p.wr; }
+    if constexpr (F & kVarlen) {
+        a.causal = pv.causal;
+        a.cu_q = p.cu_q; a.cu_k = p.cu_k; a.max_q = p.max_q; a.max_k = p.max_k; a.total_q = p.total_q; a.total_k = p.total_k;
+        if (p.max_q == 0) return FA2_OK;  // no query rows anywhere
+    }
+    if constexpr (F & kGqa) a.gqa = gqa;
     if (p.causal && ((p.B * p.H) & 7) == 0) {
         const int per_xcd = p.B * p.H / 8;
         int g = fa2_env_int("FA2_CAUSAL_GROUP", 2);
@@ -651,5 +42,15 @@ int fa2_launch_mfma16d(const Fa2Problem &p, int waves) {
         while (per_xcd % g) --g;
         a.group = g;
     }
-    return p.dtype == FA2_DTYPE_BF16 ? launch_d<__bf16>(p, a, waves) : launch_d<_Float16>(p, a, waves);
+    return p.dtype == FA2_DTYPE_BF16 ? launch_d<__bf16, F>(p, a, waves) : launch_f16<F>(p, a, waves);
+}
+
+}  // namespace
+
+int fa2_launch_mfma16d(const Fa2Problem &p, int waves) { return launch_form<0>(p, waves, 1); }
+int fa2_launch_mfma16d_window(const Fa2Problem &p, int waves) { return launch_form<kWindow>(p, waves, 1); }
+int fa2_launch_mfma16d_varlen(const Fa2Problem &p, int waves) { return launch_form<kWindow | kVarlen>(p, waves, 1); }
+int fa2_launch_mfma16d_window_gqa(const Fa2Problem &p, int waves, int gqa) { return launch_form<kWindow | kGqa>(p, waves, gqa); }
+int fa2_launch_mfma16d_varlen_gqa(const Fa2Problem &p, int waves, int gqa) {
+    return launch_form<kWindow | kVarlen | kGqa>(p, waves, gqa);
 }

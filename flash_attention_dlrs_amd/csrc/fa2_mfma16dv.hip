@@ -1,7 +1,7 @@
 // fa2_mfma16dv.hip -- the packed (varlen, GQA) f16 / bf16 forward at d = 192, d_v = 128 (variant "mfma16dv", fa2_fwd_varlen_dv):
 // un-absorbed MLA prefill, where a head's query and key are 128 "nope" columns followed by 64 rotary ones and its value is 128 wide.
 //
-// It is the varlen GQA form of fa2_mfma16d.hip (fa2_mfma16d_vg.hip) written out for this one shape: 4 waves x 32 query rows per
+// It is the varlen GQA form of fa2_mfma16d_kernel.h (F = kWindow | kVarlen | kGqa) written out for this one shape: 4 waves x 32 query rows per
 // workgroup, one tile per workgroup and sequence, the 64-key K unit / V tile ring filled by LDS-DMA, QK^T of block j + 1 under the
 // softmax of block j, the band of fa2_varlen_seq / fa2_varlen_band with blocks outside a wave's band skipped and blocks across its
 // edges masked, a row without a visible key O = 0 and L = +inf.  (The form it starts from runs the causal mask as a band and has no

@@ -1,6 +1,6 @@
 """Compare the gfx950 code of every kernel symbol between two builds of flash_attention_dlrs_amd/csrc.
 
-    python scripts/kernel_disasm_diff.py [--suffix SUFFIX] OLD_CSRC_DIR NEW_CSRC_DIR
+    python scripts/kernel_disasm_diff.py [--suffix SUFFIX] [--rename REGEX=REPL ...] [--kernarg-info] OLD_CSRC_DIR NEW_CSRC_DIR
 
 Each directory holds the objects `make` left there (fa2_*.o).  The device code object of every object file is unbundled
 (clang-offload-bundler), disassembled (llvm-objdump -d) and split per function symbol; the code-object metadata of every
@@ -8,8 +8,20 @@ kernel is read from the notes (llvm-readelf --notes): VGPR, AGPR and SGPR counts
 size, max workgroup size.  Every symbol of the old build must exist in the same object of the new one with the same
 instructions and the same metadata; symbols only in the new build are listed.  Exit status 1 on a difference.
 
+llvm-objdump prints "..." for the zero bytes that pad the last instruction of a symbol up to the next symbol's alignment; whether
+a symbol has them depends on what follows it in its object, not on its code, so these lines are left out of the comparison (a
+kernel that moved to another unit would otherwise differ from itself).
+
 --suffix names the objects to compare: "" (the default) for the library's own fa2_*.o, or one of _abl, _st, _var, _exp,
 _asan for the objects of the other builds (fa2_*_abl.o, ...).
+
+--rename REGEX=REPL (repeatable) maps an old symbol to its new unit and name: each is applied with re.sub to the old build's
+keys, which read "<unit>: <mangled symbol>", before the two builds are matched.  --kernarg-info reports a changed
+.kernarg_segment_size but does not count it as a difference (a kernel whose argument struct grew fields it never reads).
+Example, a kernel that left its stub unit and macro-given name for a template argument of the plain kernel's file:
+
+    --rename '^fa2_mfma16d_w: _ZN12_GLOBAL__N_129fa2_fwd_mfma16d_window_kernelI(.*)EEvNS=fa2_mfma16d:
+              _ZN11fa2_mfma16d22fa2_fwd_mfma16d_kernelI\\g<1>Li1EEEvNS'        (one argument, no line break)
 """
 import argparse
 import glob
@@ -35,7 +47,7 @@ def disassembly(dev):
             if name:
                 out[name] = body
             name, body = m.group(1), []
-        elif name and line.strip():
+        elif name and line.strip() and line.strip() != "...":  # ("...": zero padding up to the next symbol's alignment)
             body.append(re.sub(r"\s*//.*$", "", line).strip())  # drop the address / encoding comments
     if name:
         out[name] = body
@@ -91,10 +103,21 @@ def collect(d, suffix):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--suffix", default="", choices=("",) + SUFFIXES, help="object suffix to compare (default: none)")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL", help="re.sub applied to the old build's keys")
+    ap.add_argument("--kernarg-info", action="store_true", help="a changed .kernarg_segment_size is reported, not counted")
     ap.add_argument("old")
     ap.add_argument("new")
     args = ap.parse_args()
     old, new = collect(args.old, args.suffix), collect(args.new, args.suffix)
+    for pat, repl in (r.split("=", 1) for r in args.rename):
+        old = {re.sub(pat, repl, k): v for k, v in old.items()}
+    if args.kernarg_info:
+        moved = [k for k in old if k in new and old[k][1] and new[k][1]
+                 and old[k][1][".kernarg_segment_size"] != new[k][1][".kernarg_segment_size"]]
+        print(f"{len(moved)} kernels with another .kernarg_segment_size (informational)")
+        for k in moved:
+            print("  KERNARG", k, old[k][1][".kernarg_segment_size"], "->", new[k][1][".kernarg_segment_size"])
+            new[k] = (new[k][0], dict(new[k][1], **{".kernarg_segment_size": old[k][1][".kernarg_segment_size"]}))
     kernels = sum(1 for v in old.values() if v[1] is not None)
     changed = [k for k in old if k not in new or new[k] != old[k]]
     added = sorted(k for k in new if k not in old)
