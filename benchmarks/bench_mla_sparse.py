@@ -6,8 +6,8 @@ its own `timeout -k 10`; the first non-zero status ends the run), every side rot
 the 256 MiB last-level cache, each side is warmed (3 calls, not counted) and then run back to back, and avg, min-max and stddev are
 reported per call.  A one-element fill launched after every call marks the call boundaries in the trace; it is not counted.
 
-Lists: for every (b, qi) topk distinct positions of [0, N_k), in random order (an indexer's top-k is not sorted), one list for the
-KV head.  Sides of one child:
+Lists: for every (b, qi) topk distinct positions of [0, N_k), in random order (torch.topk's lists are not sorted by position), one list
+for the KV head; --sorted puts each list in ascending position, as fa2_topk_indices emits it.  Sides of one child:
   auto          the sparse launch, AUTO variant, auto num_splits;
   generic       the same launch, the VALU form forced, the same num_splits;
   gather_dense  the only earlier route: torch index_select of the listed rows into a temporary (B N_q, 1, topk, 576) cache, then the
@@ -53,7 +53,7 @@ def emit(fh, **kw):
 
 
 class Case:
-    def __init__(self, name, dev, kv_dtype="bf16"):
+    def __init__(self, name, dev, kv_dtype="bf16", sort_lists=False):
         import torch
         import flash_attention_dlrs_amd as fa
         from flash_attention_dlrs_amd import _lib
@@ -76,6 +76,8 @@ class Case:
             self.kv_enum = convert_triton_dtype(self.fmt)
         g = torch.Generator(device=dev).manual_seed(0)
         self.idx = torch.stack([torch.rand(N_q, S, device=dev, generator=g).argsort(-1)[:, :TOPK] for _ in range(B)]).to(torch.int32)
+        if sort_lists:  # --sorted: what an indexer that emits its lists in ascending key position hands over
+            self.idx = self.idx.sort(-1).values
         self.flat = (self.idx.long() + torch.arange(B, device=dev).view(B, 1, 1) * S).view(-1)  # row numbers of the (B S, 576) cache
         self.lens = torch.full((B,), S, dtype=torch.int32, device=dev)
         self.lens1 = torch.full((B * N_q,), TOPK, dtype=torch.int32, device=dev)
@@ -181,7 +183,7 @@ def timed(c, f, calls):
 def run_pass(name, args):
     """The traced child: each side warmed, then run back to back; the kernel trace holds the times."""
     import torch
-    c = Case(name, torch.device("cuda:0"), args.kv_dtype)
+    c = Case(name, torch.device("cuda:0"), args.kv_dtype, args.sorted)
     torch.cuda.synchronize()
     c.mark.fill_(0.0)  # the first marker: what lies before it is set-up
     sides = [("auto", c.sparse("auto")), ("generic", c.sparse("generic")), ("gather_dense", c.gather_dense()),
@@ -190,7 +192,8 @@ def run_pass(name, args):
     for side, f in sides:
         calls[side] = side_iters(side, c.shape, args.iters) + 3
         timed(c, f, calls[side])
-    print(json.dumps(dict(case=name, calls=calls, order=[s for s, _ in sides], kv_dtype=args.kv_dtype, num_splits=c.sparse_splits(),
+    print(json.dumps(dict(case=name, calls=calls, order=[s for s, _ in sides], kv_dtype=args.kv_dtype, lists="sorted" if args.sorted else "random",
+                          num_splits=c.sparse_splits(),
                           dense_topk_splits=c.dense1_splits(), **c.shape)))
 
 
@@ -208,7 +211,7 @@ def run_sweep_pass(name, args):
 def traced_child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
-           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--kv-dtype", args.kv_dtype] + extra
+           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--kv-dtype", args.kv_dtype] + (["--sorted"] if args.sorted else []) + extra
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
         sys.stderr.write(p.stdout[-2000:] + p.stderr[-2000:])
@@ -275,6 +278,7 @@ def main():
                     help="the traces of the rocprofv3 children go under DIR")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="bf16", help="the latent cache's storage: bf16, or e4m3 with its descale")
+    ap.add_argument("--sorted", action="store_true", help="every list in ascending key position (records carry lists=sorted)")
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)

@@ -15,7 +15,8 @@ from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_
                                        flash_attention_mla_varlen_decode_forward, flash_attention_mla_prefill_backward,
                                        flash_attention_mla_prefill_forward,
                                        flash_attention_varlen_forward, flash_attention_varlen_kvcache_forward, kvcache_append,
-                                       kvcache_append_varlen, quantize_kv_cache)
+                                       kvcache_append_varlen, quantize_kv_cache, check_mla_indexer_args,
+                                       flash_attention_mla_indexer_topk, mla_indexer_logits, quantize_index_keys, topk_indices)
 
 __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
            "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
@@ -24,4 +25,5 @@ __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarle
            "kvcache_append_varlen", "flash_attention_mla_decode_forward", "mla_kvcache_append", "mla_kvcache_append_varlen",
            "check_mla_append_args", "flash_attention_mla_varlen_decode_forward", "check_mla_varlen_args",
            "flash_attention_mla_prefill_forward", "flash_attention_mla_prefill_backward", "FlashAttentionMLAPrefill",
-           "flash_attention_mla_sparse_decode_forward", "check_mla_sparse_args"]
+           "flash_attention_mla_sparse_decode_forward", "check_mla_sparse_args", "flash_attention_mla_indexer_topk",
+           "mla_indexer_logits", "topk_indices", "check_mla_indexer_args", "quantize_index_keys"]

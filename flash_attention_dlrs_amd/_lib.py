@@ -58,7 +58,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_kvcache_append_varlen", "fa2_fwd_kvcache_varlen_append", "fa2_fwd_kvcache_mla", "fa2_kvcache_mla_num_splits",
            "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append",
            "fa2_fwd_kvcache_mla_varlen", "fa2_kvcache_mla_varlen_num_splits", "fa2_fwd_kvcache_mla_varlen_append",
-           "fa2_fwd_kvcache_mla_sparse", "fa2_kvcache_mla_sparse_num_splits", "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant")
+           "fa2_fwd_kvcache_mla_sparse", "fa2_kvcache_mla_sparse_num_splits", "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant",
+           "fa2_mla_indexer_logits", "fa2_topk_indices", "fa2_mla_indexer_topk", "fa2_mla_indexer_workspace_bytes")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -70,6 +71,8 @@ BWD_VARLEN_DV_VARIANTS = {"auto": 0, "generic": 1, "mfma16dv": 4}
 KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
 # ... and the latent-cache call (fa2_fwd_kvcache_mla) its own set: FA2_KVCACHE_VARIANT_MLA16 in the d 64 / 128 matrix form's place
 KVCACHE_MLA_VARIANTS = {"auto": 0, "generic": 1, "mla16": 3}
+# ... and the MLA indexer (fa2_mla_indexer_logits, fa2_mla_indexer_topk) its own: FA2_INDEXER_VARIANT_*
+INDEXER_VARIANTS = {"auto": 0, "generic": 1, "idx16": 2}
 # ... and the packed forward with a value head size of its own (fa2_fwd_varlen_dv): FA2_VARIANT_MFMA16DV is a variant of it alone
 VARIANT_MFMA16DV = 28
 VARLEN_DV_VARIANTS = {"auto": VARIANT_AUTO, "generic": VARIANT_GENERIC, "mfma16dv": VARIANT_MFMA16DV}
@@ -263,6 +266,17 @@ def lib():
             [ctypes.c_float, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_mla_sparse_num_splits.restype = ctypes.c_int32
         l.fa2_kvcache_mla_sparse_num_splits.argtypes = [ctypes.c_int32] * 8
+        # the MLA indexer: five tensors, their five stride arrays, cache_seqlens, the table and its stride, eight sizes, the two dtypes,
+        # causal; then variant (scores alone) or topk, indices, their strides, variant (both); the selection alone has a list of its own
+        idx = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64] + [ctypes.c_int32] * 11
+        l.fa2_mla_indexer_logits.restype = ctypes.c_int
+        l.fa2_mla_indexer_logits.argtypes = idx + [ctypes.c_int32, vp]
+        l.fa2_mla_indexer_topk.restype = ctypes.c_int
+        l.fa2_mla_indexer_topk.argtypes = idx + [ctypes.c_int32, vp, i64p, ctypes.c_int32, vp]
+        l.fa2_topk_indices.restype = ctypes.c_int
+        l.fa2_topk_indices.argtypes = [vp, i64p, vp] + [ctypes.c_int32] * 5 + [vp, i64p, vp]
+        l.fa2_mla_indexer_workspace_bytes.restype = ctypes.c_int64
+        l.fa2_mla_indexer_workspace_bytes.argtypes = [ctypes.c_int32] * 3
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -670,6 +684,56 @@ def fa2_fwd_kvcache_mla_sparse(Q, K, V, O, L, indices, cache_seqlens, dtype_enum
             tb_ptr, tb_st, *_descale_args(k_descale, v_descale), B, H, K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3],
             int(dtype_enum), int(kv_dtype_enum), float(scale), int(num_splits), *_workspace_args(workspace), int(variant),
             _raw_stream(Q.device.index))
+
+
+def mla_indexer_workspace_bytes(B, N_q, S_k):
+    """Bytes of the contiguous fp32 logits buffer (B, N_q, S_k) of an indexer call (fa2_mla_indexer_workspace_bytes)."""
+    return int(lib().fa2_mla_indexer_workspace_bytes(B, N_q, S_k))
+
+
+def _indexer_args(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal):
+    """The arguments fa2_mla_indexer_logits and fa2_mla_indexer_topk share, in the header's order up to `causal`."""
+    B, H_I, N_q, d_I = q_idx.shape
+    if block_table is None:
+        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, k_idx.shape[1], 0, 0, 0
+    else:
+        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, k_idx.shape[0], k_idx.shape[1], block_table.shape[1]
+    return (q_idx.data_ptr(), weights.data_ptr(), k_idx.data_ptr(), _ptr(k_scale), logits.data_ptr(), _i64(q_idx.stride()),
+            _i64(weights.stride()), _i64(k_idx.stride()), None if k_scale is None else _i64(k_scale.stride()), _i64(logits.stride()),
+            _ptr(cache_seqlens), tb_ptr, tb_st, B, H_I, N_q, S_k, nb, ps, mb, d_I, int(dtype_enum), int(k_dtype_enum), int(bool(causal)))
+
+
+def fa2_mla_indexer_logits(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, dtype_enum, k_dtype_enum, block_table=None, causal=True,
+                           variant=0):
+    """Launch the index scores (include/fa2_fwd.h fa2_mla_indexer_logits) on the current stream of q_idx's device: q_idx
+    (B, H_I, N_q, d_I), weights fp32 (B, H_I, N_q), k_idx (B, S_k, d_I) or the pool (num_blocks, page_size, d_I) with block_table,
+    k_scale fp32 shaped like k_idx's rows or None, logits fp32 (B, N_q, capacity), written for j < n(b, qi).  Any strides."""
+    if q_idx.device.type != "cuda":
+        raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
+    _launch(lib().fa2_mla_indexer_logits, q_idx,
+            *_indexer_args(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal),
+            int(variant), _raw_stream(q_idx.device.index))
+
+
+def fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_seqlens, dtype_enum, k_dtype_enum, block_table=None,
+                         causal=True, variant=0):
+    """Launch scores and selection on one stream (fa2_mla_indexer_topk): as fa2_mla_indexer_logits, then indices int32
+    (B, N_q, topk) from the logits buffer."""
+    if q_idx.device.type != "cuda":
+        raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
+    _launch(lib().fa2_mla_indexer_topk, q_idx,
+            *_indexer_args(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal),
+            indices.shape[2], indices.data_ptr(), _i64(indices.stride()), int(variant), _raw_stream(q_idx.device.index))
+
+
+def fa2_topk_indices(logits, indices, cache_seqlens, causal=True):
+    """Launch the selection alone (fa2_topk_indices) on the current stream of logits' device: logits fp32 (B, N_q, S_k), any
+    strides, indices int32 (B, N_q, topk)."""
+    if logits.device.type != "cuda":
+        raise NotImplementedError("logits must be on a CUDA device")
+    B, N_q, S_k = logits.shape
+    _launch(lib().fa2_topk_indices, logits, logits.data_ptr(), _i64(logits.stride()), _ptr(cache_seqlens), B, N_q, S_k, indices.shape[2],
+            int(bool(causal)), indices.data_ptr(), _i64(indices.stride()), _raw_stream(logits.device.index))
 
 
 def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):

@@ -984,3 +984,150 @@ def flash_attention_mla_sparse_decode_forward(Q, KV_cache, indices, cache_seqlen
                                     k_descale=kd, v_descale=kd, block_table=block_table, scale=scale, num_splits=n, workspace=ws,
                                     variant=_lib.KVCACHE_MLA_VARIANTS[variant])
     return O, L
+
+
+INDEXER_Q_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
+
+
+def quantize_index_keys(k, dtype):
+    """(k8, k_scale) of index keys (..., d_I) for the indexer's fp8 cache: one POWER-OF-TWO scale per row, the smallest with
+    amax(row) / scale <= finfo(dtype).max (1 for a row of zeros), float32 of shape k.shape[:-1]; k8 = (k / scale) in dtype
+    (torch.float8_e4m3fn or torch.float8_e5m2).  The division is exact, so k8.float() * k_scale[..., None] is exact in fp32 as
+    well.  Plain torch, any device."""
+    if dtype not in FP8_CACHE_DTYPES:
+        raise ValueError(f"quantize_index_keys: dtype must be torch.float8_e4m3fn or torch.float8_e5m2, got {dtype}")
+    if not isinstance(k, torch.Tensor) or k.dim() < 1 or not k.dtype.is_floating_point:
+        raise ValueError("quantize_index_keys: k must be a floating-point tensor (..., d_I)")
+    top = torch.finfo(dtype).max
+    amax = k.detach().abs().amax(dim=-1).to(torch.float32)
+    m, e = torch.frexp(amax / top)  # amax / top = m 2^e, m in [0.5, 1): ceil(log2) is e, or e - 1 at m = 0.5
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e - (m == 0.5).to(e.dtype)), torch.ones_like(amax))
+    k8 = (k.to(torch.float32) / scale[..., None]).clamp(-top, top).to(dtype)
+    return k8, scale
+
+
+def _indexer_capacity(k_idx, block_table):
+    return k_idx.shape[1] if block_table is None else block_table.shape[1] * k_idx.shape[1]
+
+
+def check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk=2048, k_scale=None, block_table=None):
+    """ValueError, naming the argument, for what flash_attention_mla_indexer_topk cannot take: q_idx (B, H_I, N_q, d_I) in f16, bf16
+    or f32 with d_I <= 576; weights float32 (B, H_I, N_q); k_idx (B, S_k, d_I), or the pool (num_blocks, page_size, d_I) with an int32
+    block_table (B, max_blocks), in q_idx's dtype or fp8 under f16 / bf16; k_scale float32 shaped like k_idx's rows, required with an
+    fp8 k_idx; cache_seqlens int32 (B,) or None; topk an int in [1, 2^28]; everything on q_idx's device.  Pure: takes CPU tensors."""
+    who = "mla indexer"
+    if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 4:
+        raise ValueError(f"{who}: q_idx must be a tensor (B, H_I, N_q, d_I), got "
+                         f"{tuple(q_idx.shape) if isinstance(q_idx, torch.Tensor) else type(q_idx).__name__}")
+    if q_idx.dtype not in INDEXER_Q_DTYPES:
+        raise ValueError(f"{who}: q_idx must be float16, bfloat16 or float32, got {q_idx.dtype}")
+    B, H_I, N_q, d_I = q_idx.shape
+    if min(B, H_I, N_q) < 1 or not 1 <= d_I <= 576:
+        raise ValueError(f"{who}: q_idx needs B, H_I, N_q >= 1 and d_I in [1, 576], got {tuple(q_idx.shape)}")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (B, H_I, N_q):
+        raise ValueError(f"{who}: weights must be a float32 tensor (B, H_I, N_q) = ({B}, {H_I}, {N_q})")
+    if not isinstance(k_idx, torch.Tensor) or k_idx.dim() != 3 or k_idx.shape[2] != d_I or k_idx.shape[1] < 1:
+        raise ValueError(f"{who}: k_idx must be a tensor (B, S_k, d_I) or a pool (num_blocks, page_size, d_I) with d_I = {d_I}")
+    fp8 = k_idx.dtype in FP8_CACHE_DTYPES
+    if fp8 and q_idx.dtype == torch.float32:
+        raise ValueError(f"{who}: an fp8 k_idx ({k_idx.dtype}) goes with float16 / bfloat16 q_idx, not float32")
+    if not fp8 and k_idx.dtype != q_idx.dtype:
+        raise ValueError(f"{who}: k_idx must have q_idx's dtype ({q_idx.dtype}) or an fp8 dtype, got {k_idx.dtype}")
+    if block_table is None:
+        if k_idx.shape[0] != B:
+            raise ValueError(f"{who}: k_idx must be (B, S_k, d_I) with B = {B}, got {tuple(k_idx.shape)} (a pool needs its block_table)")
+    else:
+        _check_block_table(block_table, B, k_idx.shape[1], q_idx, "q_idx")
+    if fp8 and k_scale is None:
+        raise ValueError(f"{who}: an fp8 k_idx ({k_idx.dtype}) needs its k_scale (quantize_index_keys returns it)")
+    if k_scale is not None and (not isinstance(k_scale, torch.Tensor) or k_scale.dtype != torch.float32
+                                or tuple(k_scale.shape) != tuple(k_idx.shape[:2])):
+        raise ValueError(f"{who}: k_scale must be a float32 tensor shaped like k_idx's rows {tuple(k_idx.shape[:2])}")
+    if cache_seqlens is not None:
+        _check_cache_seqlens(cache_seqlens, B, q_idx, "q_idx", " (or None)")
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= 1 << 28:
+        raise ValueError(f"{who}: topk must be an int in [1, 2^28], got {topk!r}")
+    if _indexer_capacity(k_idx, block_table) > 1 << 28:
+        raise ValueError(f"{who}: the capacity must be <= 2^28")
+    for name, t in (("weights", weights), ("k_idx", k_idx), ("k_scale", k_scale)):
+        if t is not None and t.device != q_idx.device:
+            raise ValueError(f"{who}: {name} must be on q_idx's device ({q_idx.device}), got {t.device}")
+    for name, t in (("q_idx", q_idx), ("weights", weights), ("k_idx", k_idx), ("k_scale", k_scale)):
+        if t is not None and any(s < 0 for s in t.stride()):
+            raise ValueError(f"{who}: {name} with negative strides is not supported")
+
+
+def _indexer_variant(variant):
+    if variant not in _lib.INDEXER_VARIANTS:
+        raise ValueError(f"mla indexer: variant must be one of {sorted(_lib.INDEXER_VARIANTS)}, got {variant!r}")
+    return _lib.INDEXER_VARIANTS[variant]
+
+
+def _indexer_dev(dev, q_idx):
+    if q_idx.device != torch.device(dev):
+        raise ValueError(f"dev={dev} is not the device of q_idx ({q_idx.device})")
+
+
+def mla_indexer_logits(q_idx, weights, k_idx, cache_seqlens, dev, *, causal=True, k_scale=None, block_table=None, variant="auto"):
+    """The index scores of the MLA indexer alone (include/fa2_fwd.h fa2_mla_indexer_logits) -> logits float32 (B, N_q, capacity):
+    logits[b, qi, j] = k_scale[b, j] * sum_h weights[b, h, qi] * relu(q_idx[b, h, qi] . k_idx[b, j]) for the candidates j < n(b, qi)
+    of query qi (position N_k(b) - N_q + qi; causal: keys 0 .. position, else all N_k(b)).  Entries at j >= n(b, qi) are NOT written:
+    the buffer comes from torch.empty.  Arguments as flash_attention_mla_indexer_topk."""
+    check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, 1, k_scale, block_table)
+    v = _indexer_variant(variant)
+    _indexer_dev(dev, q_idx)
+    B, _, N_q, _ = q_idx.shape
+    logits = torch.empty((B, N_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
+    _lib.fa2_mla_indexer_logits(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, convert_triton_dtype(q_idx.dtype),
+                                convert_triton_dtype(k_idx.dtype), block_table=block_table, causal=causal, variant=v)
+    return logits
+
+
+def topk_indices(logits, cache_seqlens, topk, *, N_q=None, causal=True):
+    """The selection of the MLA indexer alone (fa2_topk_indices), over any float32 logits (B, N_q, S_k) of any non-negative strides
+    (or (B * N_q, S_k) with N_q given) -> indices int32 (B, N_q, topk).  Row (b, qi) has n candidates, entries j < n with n as in
+    mla_indexer_logits; nothing else of the row is read.  Its list is the min(topk, n) candidates first under (value descending,
+    position ascending) -- -0.0 equals +0.0, a NaN ranks as -inf -- emitted in ascending position, the rest of the row -1."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() not in (2, 3):
+        raise ValueError("topk indices: logits must be a float32 tensor (B, N_q, S_k)")
+    if logits.dim() == 2:
+        if isinstance(N_q, bool) or not isinstance(N_q, int) or N_q < 1 or logits.shape[0] % N_q:
+            raise ValueError(f"topk indices: two-dimensional logits (B * N_q, S_k) need N_q, an int >= 1 dividing {logits.shape[0]}, got {N_q!r}")
+        logits = logits.unflatten(0, (logits.shape[0] // N_q, N_q))
+    elif N_q is not None and N_q != logits.shape[1]:
+        raise ValueError(f"topk indices: N_q = {N_q!r} is not the logits' ({logits.shape[1]})")
+    B, nq, S_k = logits.shape
+    if min(B, nq, S_k) < 1 or S_k > 1 << 28 or any(s < 0 for s in logits.stride()):
+        raise ValueError(f"topk indices: logits must be (B, N_q, S_k) with every size >= 1, S_k <= 2^28 and no negative stride, got "
+                         f"{tuple(logits.shape)}, strides {tuple(logits.stride())}")
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= 1 << 28:
+        raise ValueError(f"topk indices: topk must be an int in [1, 2^28], got {topk!r}")
+    if cache_seqlens is not None:
+        _check_cache_seqlens(cache_seqlens, B, logits, "logits", " (or None)")
+    indices = torch.empty((B, nq, topk), dtype=torch.int32, device=logits.device)
+    _lib.fa2_topk_indices(logits, indices, cache_seqlens, causal=causal)
+    return indices
+
+
+def flash_attention_mla_indexer_topk(q_idx, weights, k_idx, cache_seqlens, dev, topk=2048, causal=True, k_scale=None, block_table=None,
+                                     variant="auto", return_logits=False):
+    """The MLA indexer (DeepSeek-V3.2's lightning indexer; include/fa2_fwd.h fa2_mla_indexer_topk) -> indices int32 (B, N_q, topk),
+    the key lists flash_attention_mla_sparse_decode_forward takes: scores and selection on one stream, no (B, N_q, H_I, N_k)
+    intermediate.  q_idx (B, H_I, N_q, d_I) in f16, bf16 or f32, any strides; weights float32 (B, H_I, N_q), any softmax or head
+    scale already folded in; k_idx the index-key cache (B, S_k, d_I) -- one shared head -- or, with block_table (B, max_blocks)
+    int32, the pool (num_blocks, page_size, d_I) of ANY page size, in q_idx's dtype or fp8 under f16 / bf16 with k_scale (float32,
+    shaped like the rows, > 0; quantize_index_keys makes both); cache_seqlens int32 (B,) or None (= the capacity).  Query qi of
+    sequence b stands at position N_k(b) - N_q + qi; causal: its candidates are the keys up to that position, else all N_k(b).
+    The list holds the min(topk, n) candidates of highest score (ties: the lower position), in ASCENDING position, padded with -1.
+    variant is one of _lib.INDEXER_VARIANTS: "idx16" (f16 / bf16, d_I = 128, H_I <= 64, unit column strides, 16-byte aligned
+    rows), "generic" (everything else), "auto".  return_logits: (indices, logits), the float32 (B, N_q, capacity) scores, written
+    for the candidates only.  No autograd."""
+    check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk, k_scale, block_table)
+    v = _indexer_variant(variant)
+    _indexer_dev(dev, q_idx)
+    B, _, N_q, _ = q_idx.shape
+    logits = torch.empty((B, N_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
+    indices = torch.empty((B, N_q, topk), dtype=torch.int32, device=q_idx.device)
+    _lib.fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_seqlens, convert_triton_dtype(q_idx.dtype),
+                              convert_triton_dtype(k_idx.dtype), block_table=block_table, causal=causal, variant=v)
+    return (indices, logits) if return_logits else indices

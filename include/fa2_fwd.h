@@ -829,6 +829,71 @@ int32_t fa2_kvcache_mla_sparse_num_splits(int32_t B, int32_t H, int32_t H_kv, in
                                           int32_t dtype_enum);
 
 /*
+ * The MLA indexer (DeepSeek-V3.2's lightning indexer): the stage in front of fa2_fwd_kvcache_mla_sparse.  It scores every cached
+ * token against every query token and makes the key lists that call takes.  Three entry points: the scores alone, the selection
+ * alone over any fp32 logits, and both on one stream.
+ *
+ *   Tensors.  q_idx (B, H_I, N_q, d_I), four element strides; weights fp32 (B, H_I, N_q), three element strides (any softmax or
+ *             head scale already folded in); the index-key cache k_idx (B, S_k, d_I) -- one shared head, as the latent cache -- or,
+ *             with block_table, the pool (num_blocks, page_size, d_I), k_strides = {batch or block, row, column}; k_scale fp32
+ *             (B, S_k) or (num_blocks, page_size), addressed like the rows, k_scale_strides = {batch or block, row}.  Key j of
+ *             sequence b in a pool is row j % page_size of page block_table[b, j / page_size], the entry clamped into the pool, ANY
+ *             page size; the capacity max_blocks * page_size takes S_k's place.  cache_seqlens as everywhere: null = S_k, clamped.
+ *   Dtypes.   q_idx f16, bf16 or f32; k_idx alike, or e4m3fn / e5m2 under f16 / bf16 (storage only: bytes are converted exactly,
+ *             the arithmetic stays 16-bit).  k_scale > 0 is optional over a 16-bit or f32 cache and required over an fp8 one.
+ *   Scores.   logit[b, qi, j] = k_scale[b, j] * sum_h weights[b, h, qi] * max(0, q_idx[b, h, qi, :] . k_idx[b, j, :]), fp32.
+ *   Mask.     Query qi stands at position p = N_k(b) - N_q + qi (bottom-right).  causal != 0: its candidates are the keys
+ *             0 .. min(p, N_k(b) - 1), none for p < 0; causal == 0: all N_k(b) keys.  n(b, qi) is their count.
+ *   Logits.   fp32 (B, N_q, S_k) at three element strides.  Entry [b, qi, j] is written for j < n(b, qi); no other entry is written
+ *             by the score kernels or read by the selection.
+ *   Lists.    Values compare as numbers (-0.0 == +0.0, a NaN ranks as -inf).  The list of (b, qi) is the min(topk, n) candidates
+ *             that come first under (value descending, position ascending), EMITTED IN ASCENDING POSITION into
+ *             indices[b, qi, 0 .. topk), the rest of the row -1; with n <= topk it is 0 .. n - 1 and no logit is read.  indices is
+ *             int32 (B, N_q, topk) at three element strides -- the three-dimensional form fa2_fwd_kvcache_mla_sparse's Python
+ *             surface takes.  A function of the logits alone: the same logits give the same bytes.
+ *   Variants. FA2_INDEXER_VARIANT_IDX16: f16 / bf16 (the cache alike or fp8), d_I = 128, H_I <= 64, unit column strides, 16-byte
+ *             aligned rows, contiguous or paged, on v_mfma_f32_16x16x32.  FA2_INDEXER_VARIANT_GENERIC: everything else, on the VALU.
+ *             AUTO: IDX16 where it runs, else GENERIC.  A forced IDX16 on a problem it cannot run returns FA2_ERR_UNSUPPORTED.
+ *
+ * FA2_ERR_BAD_ARG before any launch, the message naming the argument, for: a null q_idx / weights / k_idx / logits (indices) or
+ * stride array, a negative stride, B outside [1, 65535], H_I < 1, N_q or S_k outside [1, 2^28], the paged sizes of
+ * fa2_fwd_kvcache_paged, topk outside [1, 2^28], an fp8 cache without k_scale, k_scale without its strides, a launch grid that does
+ * not fit.  FA2_ERR_UNSUPPORTED for d_I outside [1, 576], a dtype_enum that is not f16 / bf16 / f32, a k_dtype_enum that is neither
+ * dtype_enum nor an fp8 format, fp8 under f32, an unknown variant.
+ */
+#define FA2_INDEXER_VARIANT_AUTO 0
+#define FA2_INDEXER_VARIANT_GENERIC 1
+#define FA2_INDEXER_VARIANT_IDX16 2
+
+int fa2_mla_indexer_logits(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                           const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],
+                           const int64_t k_scale_strides[2], const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                           const int32_t *block_table, int64_t block_table_stride,
+                           int32_t B, int32_t H_I, int32_t N_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                           int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal,
+                           int32_t variant, void *hip_stream);
+
+/* The selection alone, over any fp32 logits (B, N_q, S_k): one workgroup per (b, qi) row, a radix select over an order-preserving
+ * 32-bit image of the values, then one ordered compaction pass. */
+int fa2_topk_indices(const float *logits, const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                     int32_t B, int32_t N_q, int32_t S_k, int32_t topk, int32_t causal,
+                     int32_t *indices, const int64_t index_strides[3], void *hip_stream);
+
+/* Both on one stream: fa2_mla_indexer_logits into the caller's `logits` buffer (fa2_mla_indexer_workspace_bytes(B, N_q, capacity)
+ * bytes when contiguous), then fa2_topk_indices over it.  Every error of both halves comes back before any launch. */
+int fa2_mla_indexer_topk(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                         const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],
+                         const int64_t k_scale_strides[2], const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                         const int32_t *block_table, int64_t block_table_stride,
+                         int32_t B, int32_t H_I, int32_t N_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                         int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal,
+                         int32_t topk, int32_t *indices, const int64_t index_strides[3], int32_t variant, void *hip_stream);
+
+/* Bytes of the contiguous fp32 logits buffer (B, N_q, S_k): 4 * B * N_q * S_k, 0 if a size is < 1, INT64_MAX where that product
+ * does not fit. */
+int64_t fa2_mla_indexer_workspace_bytes(int32_t B, int32_t N_q, int32_t S_k);
+
+/*
  * The fused ragged MLA step: fa2_kvcache_mla_append_varlen over cu_seqlens_q (total_new = total_q, max_seqlen_new = max_seqlen_q;
  * c_new, pe_new packed (total_q, H_kv, d_v) / (total_q, H_kv, d - d_v)), then on the same stream fa2_fwd_kvcache_mla_varlen over the
  * updated cache with seqlens_out as its cache_seqlens and, with tables, q_rot (packed, contiguous (total_q, H, d)) as its Q; q_rot
