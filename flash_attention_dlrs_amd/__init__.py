@@ -16,7 +16,10 @@ from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_
                                        flash_attention_mla_prefill_forward,
                                        flash_attention_varlen_forward, flash_attention_varlen_kvcache_forward, kvcache_append,
                                        kvcache_append_varlen, quantize_kv_cache, check_mla_indexer_args,
-                                       flash_attention_mla_indexer_topk, mla_indexer_logits, quantize_index_keys, topk_indices)
+                                       flash_attention_mla_indexer_topk, mla_indexer_logits, quantize_index_keys, topk_indices,
+                                       check_mla_sparse_varlen_args, flash_attention_mla_sparse_varlen_decode_forward,
+                                       check_mla_indexer_varlen_args, mla_indexer_logits_varlen, topk_indices_varlen,
+                                       flash_attention_mla_indexer_topk_varlen)
 
 __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
            "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
@@ -26,4 +29,6 @@ __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarle
            "check_mla_append_args", "flash_attention_mla_varlen_decode_forward", "check_mla_varlen_args",
            "flash_attention_mla_prefill_forward", "flash_attention_mla_prefill_backward", "FlashAttentionMLAPrefill",
            "flash_attention_mla_sparse_decode_forward", "check_mla_sparse_args", "flash_attention_mla_indexer_topk",
-           "mla_indexer_logits", "topk_indices", "check_mla_indexer_args", "quantize_index_keys"]
+           "mla_indexer_logits", "topk_indices", "check_mla_indexer_args", "quantize_index_keys",
+           "flash_attention_mla_sparse_varlen_decode_forward", "check_mla_sparse_varlen_args", "mla_indexer_logits_varlen",
+           "topk_indices_varlen", "flash_attention_mla_indexer_topk_varlen", "check_mla_indexer_varlen_args"]

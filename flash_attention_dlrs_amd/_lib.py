@@ -59,7 +59,9 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_kvcache_mla_fp8", "fa2_kvcache_mla_append", "fa2_kvcache_mla_append_varlen", "fa2_fwd_kvcache_mla_append",
            "fa2_fwd_kvcache_mla_varlen", "fa2_kvcache_mla_varlen_num_splits", "fa2_fwd_kvcache_mla_varlen_append",
            "fa2_fwd_kvcache_mla_sparse", "fa2_kvcache_mla_sparse_num_splits", "fa2_fwd_varlen_dv", "fa2_fwd_varlen_dv_variant",
-           "fa2_mla_indexer_logits", "fa2_topk_indices", "fa2_mla_indexer_topk", "fa2_mla_indexer_workspace_bytes")
+           "fa2_mla_indexer_logits", "fa2_topk_indices", "fa2_mla_indexer_topk", "fa2_mla_indexer_workspace_bytes",
+           "fa2_fwd_kvcache_mla_sparse_varlen", "fa2_kvcache_mla_sparse_varlen_num_splits", "fa2_mla_indexer_logits_varlen",
+           "fa2_topk_indices_varlen", "fa2_mla_indexer_topk_varlen", "fa2_mla_indexer_varlen_workspace_bytes")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -277,6 +279,24 @@ def lib():
         l.fa2_topk_indices.argtypes = [vp, i64p, vp] + [ctypes.c_int32] * 5 + [vp, i64p, vp]
         l.fa2_mla_indexer_workspace_bytes.restype = ctypes.c_int64
         l.fa2_mla_indexer_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        # key lists of packed queries: fa2_fwd_kvcache_mla_sparse's order with 3-element Q / O / index strides, the L head stride,
+        # cu_seqlens_q before cache_seqlens, and total_q max_seqlen_q in N_q's place
+        l.fa2_fwd_kvcache_mla_sparse_varlen.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_sparse_varlen.argtypes = [vp] * 5 + [i64p] * 4 + [ctypes.c_int64, vp, vp, vp, i64p, ctypes.c_int32, vp,
+                                                                                ctypes.c_int64, vp, vp, i64p, i64p] + \
+            [ctypes.c_int32] * 12 + [ctypes.c_float, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_mla_sparse_varlen_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_mla_sparse_varlen_num_splits.argtypes = [ctypes.c_int32] * 7
+        # the packed indexer: the fixed calls' order with cu_seqlens_q before cache_seqlens and total_q max_seqlen_q in N_q's place
+        idxv = [vp] * 5 + [i64p] * 5 + [vp, vp, vp, ctypes.c_int64] + [ctypes.c_int32] * 12
+        l.fa2_mla_indexer_logits_varlen.restype = ctypes.c_int
+        l.fa2_mla_indexer_logits_varlen.argtypes = idxv + [ctypes.c_int32, vp]
+        l.fa2_mla_indexer_topk_varlen.restype = ctypes.c_int
+        l.fa2_mla_indexer_topk_varlen.argtypes = idxv + [ctypes.c_int32, vp, i64p, ctypes.c_int32, vp]
+        l.fa2_topk_indices_varlen.restype = ctypes.c_int
+        l.fa2_topk_indices_varlen.argtypes = [vp, i64p, vp, vp] + [ctypes.c_int32] * 6 + [vp, i64p, vp]
+        l.fa2_mla_indexer_varlen_workspace_bytes.restype = ctypes.c_int64
+        l.fa2_mla_indexer_varlen_workspace_bytes.argtypes = [ctypes.c_int32] * 2
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -734,6 +754,86 @@ def fa2_topk_indices(logits, indices, cache_seqlens, causal=True):
     B, N_q, S_k = logits.shape
     _launch(lib().fa2_topk_indices, logits, logits.data_ptr(), _i64(logits.stride()), _ptr(cache_seqlens), B, N_q, S_k, indices.shape[2],
             int(bool(causal)), indices.data_ptr(), _i64(indices.stride()), _raw_stream(logits.device.index))
+
+
+def kvcache_mla_sparse_varlen_num_splits(total_q, H, H_kv, topk, d, d_v, dtype_enum):
+    """What num_splits = 0 resolves to for a packed sparse latent-cache call (fa2_kvcache_mla_sparse_varlen_num_splits): the fixed
+    call's count with total_q tokens in B * N_q's place."""
+    return int(lib().fa2_kvcache_mla_sparse_varlen_num_splits(total_q, H, H_kv, topk, d, d_v, int(dtype_enum)))
+
+
+def fa2_fwd_kvcache_mla_sparse_varlen(Q, K, V, O, L, indices, cu_q, max_q, cache_seqlens, dtype_enum, kv_dtype_enum, k_descale=None,
+                                      v_descale=None, block_table=None, scale=1.0, num_splits=0, workspace=None, variant=0):
+    """Launch sparse MLA decode of packed queries (include/fa2_fwd.h fa2_fwd_kvcache_mla_sparse_varlen) on the current stream of Q's
+    device.  Q (total_q, H, d), O (total_q, H, d_v), any strides, L (H, total_q) with unit token stride, cu_q int32 (B + 1,) on the
+    device; indices an int32 tensor on the device viewed as (total_q, H_kv, topk) (expanded views are fine), entry [t, hk, s] a key
+    position of the sequence that owns packed row t.  The cache side is fa2_fwd_kvcache_mla_sparse's.  The workspace holds
+    kvcache_varlen_workspace_bytes(total_q, H, d_v, num_splits) bytes."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    total_q, H, d = Q.shape
+    _check_packed_l("fa2_fwd_kvcache_mla_sparse_varlen", L, H, total_q)
+    tb_ptr, tb_st, _, nb, _, mb = _table_args(K, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla_sparse_varlen, Q,
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), L.stride(0), cu_q.data_ptr(), _ptr(cache_seqlens),
+            indices.data_ptr(), _i64(indices.stride()), indices.shape[2], tb_ptr, tb_st, *_descale_args(k_descale, v_descale),
+            cu_q.numel() - 1, H, K.shape[1], total_q, int(max_q), nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum), int(kv_dtype_enum),
+            float(scale), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
+
+
+def mla_indexer_varlen_workspace_bytes(total_q, S_k):
+    """Bytes of the contiguous fp32 logits buffer (total_q, S_k) of a packed indexer call (fa2_mla_indexer_varlen_workspace_bytes)."""
+    return int(lib().fa2_mla_indexer_varlen_workspace_bytes(total_q, S_k))
+
+
+def _indexer_varlen_args(q_idx, weights, k_idx, k_scale, logits, cu_q, max_q, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal):
+    """The arguments fa2_mla_indexer_logits_varlen and fa2_mla_indexer_topk_varlen share, in the header's order up to `causal`."""
+    total_q, H_I, d_I = q_idx.shape
+    if block_table is None:
+        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, k_idx.shape[1], 0, 0, 0
+    else:
+        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, k_idx.shape[0], k_idx.shape[1], block_table.shape[1]
+    return (q_idx.data_ptr(), weights.data_ptr(), k_idx.data_ptr(), _ptr(k_scale), logits.data_ptr(), _i64(q_idx.stride()),
+            _i64(weights.stride()), _i64(k_idx.stride()), None if k_scale is None else _i64(k_scale.stride()), _i64(logits.stride()),
+            cu_q.data_ptr(), _ptr(cache_seqlens), tb_ptr, tb_st, cu_q.numel() - 1, H_I, total_q, int(max_q), S_k, nb, ps, mb, d_I,
+            int(dtype_enum), int(k_dtype_enum), int(bool(causal)))
+
+
+def fa2_mla_indexer_logits_varlen(q_idx, weights, k_idx, k_scale, logits, cu_q, max_q, cache_seqlens, dtype_enum, k_dtype_enum,
+                                  block_table=None, causal=True, variant=0):
+    """Launch the index scores of packed queries (include/fa2_fwd.h fa2_mla_indexer_logits_varlen) on the current stream of q_idx's
+    device: q_idx (total_q, H_I, d_I), weights fp32 (total_q, H_I), logits fp32 (total_q, capacity), cu_q int32 (B + 1,) on the
+    device; the key side as fa2_mla_indexer_logits.  Any strides."""
+    if q_idx.device.type != "cuda":
+        raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
+    _launch(lib().fa2_mla_indexer_logits_varlen, q_idx,
+            *_indexer_varlen_args(q_idx, weights, k_idx, k_scale, logits, cu_q, max_q, cache_seqlens, block_table, dtype_enum, k_dtype_enum,
+                                  causal),
+            int(variant), _raw_stream(q_idx.device.index))
+
+
+def fa2_mla_indexer_topk_varlen(q_idx, weights, k_idx, k_scale, logits, indices, cu_q, max_q, cache_seqlens, dtype_enum, k_dtype_enum,
+                                block_table=None, causal=True, variant=0):
+    """Launch scores and selection of packed queries on one stream (fa2_mla_indexer_topk_varlen): as fa2_mla_indexer_logits_varlen,
+    then indices int32 (total_q, topk) from the logits buffer."""
+    if q_idx.device.type != "cuda":
+        raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
+    _launch(lib().fa2_mla_indexer_topk_varlen, q_idx,
+            *_indexer_varlen_args(q_idx, weights, k_idx, k_scale, logits, cu_q, max_q, cache_seqlens, block_table, dtype_enum, k_dtype_enum,
+                                  causal),
+            indices.shape[1], indices.data_ptr(), _i64(indices.stride()), int(variant), _raw_stream(q_idx.device.index))
+
+
+def fa2_topk_indices_varlen(logits, indices, cu_q, max_q, cache_seqlens, causal=True):
+    """Launch the packed selection alone (fa2_topk_indices_varlen) on the current stream of logits' device: logits fp32
+    (total_q, S_k), any strides, indices int32 (total_q, topk)."""
+    if logits.device.type != "cuda":
+        raise NotImplementedError("logits must be on a CUDA device")
+    total_q, S_k = logits.shape
+    _launch(lib().fa2_topk_indices_varlen, logits, logits.data_ptr(), _i64(logits.stride()), cu_q.data_ptr(), _ptr(cache_seqlens),
+            cu_q.numel() - 1, total_q, int(max_q), S_k, indices.shape[1], int(bool(causal)), indices.data_ptr(), _i64(indices.stride()),
+            _raw_stream(logits.device.index))
 
 
 def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):

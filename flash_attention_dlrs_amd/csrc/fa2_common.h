@@ -126,6 +126,25 @@ __device__ __forceinline__ void fa2_varlen_seq(const int32_t *cu, int b, int tot
     len = n < 0 ? 0 : (n > max_len ? max_len : n);
 }
 
+// The sequence that owns packed row t (0 <= t < total), for the kernels that take one packed row per workgroup (the sparse latent
+// call's packed forms, the packed selection of the indexer): the last b in [0, B) whose clamped offset is <= t (sequence 0 when none
+// is) by a binary search, at most 16 steps for B <= 65535 -- t is uniform, so every step is a scalar load -- then fa2_varlen_seq of
+// that b.  False where b does not own t: a gap between sequences, the surplus of a span past max_len, a row at or past the last
+// offset.  Any contents of cu give b in [0, B) and start + len <= total.
+__device__ __forceinline__ bool fa2_varlen_owner(const int32_t *cu, int B, int total, int max_len, int t, int &b, int &start, int &len) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        int c = cu[mid];
+        c = c < 0 ? 0 : (c > total ? total : c);
+        if (c <= t) lo = mid;
+        else hi = mid;
+    }
+    b = lo;
+    fa2_varlen_seq(cu, b, total, max_len, start, len);
+    return t >= start && t - start < len;
+}
+
 // The band of a packed sequence of nq queries and nk keys in the windowed kernels' terms -- key j visible to query i iff
 // i - wl <= j <= i + wr -- from the raw sides (-1 unbounded; causal clamps the right side to 0), bottom-right aligned: both are
 // shifted by nk - nq.  Either side may come out negative.  |wl|, |wr| <= 2 nq + nk (max_seqlen <= 2^28 keeps i + wr in int).

@@ -152,6 +152,15 @@ bool fa2_decode_mla16_s_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla16_s(const Fa2DecodeProblem &p);
 int fa2_launch_decode_sparse_generic(const Fa2DecodeProblem &p);
 
+// The packed sparse call (fa2_fwd_kvcache_mla_sparse_varlen): cu_q AND indices non-null.  Q, O, L and the partials are the packed
+// call's (above), is = {0, KV head, token, slot}: entry [t, h_kv, s] is a key position of the sequence that owns packed row t
+// (fa2_varlen_owner).  The grids run over total_q tokens in B * N_q's place; a workgroup whose row no sequence owns leaves at once and
+// writes nothing, as the combine (which walks the sequences' own rows) then reads and writes nothing of it.  The packed instantiations
+// of both forms, a translation unit each (fa2_decode_mla16_sv.hip, fa2_decode_sparse_generic_v.hip).
+bool fa2_decode_mla16_sv_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_sv(const Fa2DecodeProblem &p);
+int fa2_launch_decode_sparse_generic_v(const Fa2DecodeProblem &p);
+
 // One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
 // each tensor's dtype.  It is the kernel's argument as well.
 struct Fa2AppendProblem {

@@ -1,5 +1,5 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache calls
-// _mla, _mla_fp8, _mla_varlen and the key-list call _mla_sparse, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
+// _mla, _mla_fp8, _mla_varlen and the key-list calls _mla_sparse and _mla_sparse_varlen, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
 // fa2_fwd_kvcache_append, _varlen_append, _mla_append and _mla_varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
 //   1. fill   the entry point names its raw arguments in a DecodeCall (the cache update's in an AppendCall), packed strides through packed4;
 //   2. check  check_decode (check_append) tests every argument, resolves num_splits (split_count on the unsplit workgroup count of the
@@ -100,6 +100,15 @@ int num_splits_mla_sparse(const SplitShape &s) {
     return split_count(tok * ((g + 63) / 64), s.S_k, kMlaSplitWaves, kMlaMinSplitTiles);
 }
 
+// fa2_kvcache_mla_sparse_varlen_num_splits: num_splits_mla_sparse on total_q packed rows in B * N_q's place.  Both packed forms give a
+// workgroup ONE packed row, so the unsplit count is total_q * H_kv * head tiles however the rows fall into sequences.
+int num_splits_mla_sparse_varlen(const SplitShape &s) {
+    SplitShape rows = s;
+    rows.B = s.total_q;
+    rows.N_q = 1;
+    return num_splits_mla_sparse(rows);
+}
+
 // The fp32 workspace of a split call: o_part [num_splits][rows][d_v] then l_part [num_splits][rows], rows = B * H * N_q
 // (total_q * H for packed queries).
 int64_t workspace_bytes(int64_t rows, int64_t d_v, int64_t num_splits) {
@@ -132,7 +141,9 @@ struct DecodeCall {
     bool packed = false;  // fa2_fwd_kvcache_varlen, _mla_varlen (with `mla`): Q, O are (total_q, H, d) over cu_seqlens_q, L is (H, total_q)
     const int32_t *cu_seqlens_q = nullptr;
     int32_t total_q = 0, max_seqlen_q = 0;
-    bool sparse = false;  // fa2_fwd_kvcache_mla_sparse (with `mla`): every (b, h_kv, position) attends over its own list of key indices
+    // fa2_fwd_kvcache_mla_sparse (with `mla`): every (b, h_kv, position) attends over its own list of key indices; with `packed`
+    // (fa2_fwd_kvcache_mla_sparse_varlen) every (packed row, h_kv), index_strides already {0, KV head, token, slot}
+    bool sparse = false;
     const int32_t *indices = nullptr;
     const int64_t *index_strides = nullptr;
     int32_t topk = 0;
@@ -140,8 +151,8 @@ struct DecodeCall {
     int32_t d_v = 0;
 };
 
-// The five forms of the call: fixed N_q, packed queries (query-tiled), the latent cache, packed queries over the latent cache, key
-// lists over the latent cache.  Each has a matrix kernel of its own beside a VALU kernel (`generic`: fa2_launch_decode_generic, the
+// The six forms of the call: fixed N_q, packed queries (query-tiled), the latent cache, packed queries over the latent cache, key
+// lists over the latent cache, key lists of packed queries over the latent cache.  Each has a matrix kernel of its own beside a VALU kernel (`generic`: fa2_launch_decode_generic, the
 // lists their own) and the combine, which all share; `variant` is the id that forces the matrix kernel, and AUTO, GENERIC and that id
 // are the variants the form accepts: any other gets `unknown_variant`.
 struct DecodeForm {
@@ -151,15 +162,19 @@ struct DecodeForm {
     const char *unknown_variant;
     int (*generic)(const Fa2DecodeProblem &) = fa2_launch_decode_generic;
 };
-const DecodeForm kForms[5] = {
+const DecodeForm kForms[6] = {
     {fa2_decode_mfma16_supports, fa2_launch_decode_mfma16, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mfma16_v_supports, fa2_launch_decode_mfma16_v, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mla16_supports, fa2_launch_decode_mla16, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
     {fa2_decode_mla16_v_supports, fa2_launch_decode_mla16_v, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
     {fa2_decode_mla16_s_supports, fa2_launch_decode_mla16_s, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla sparse: unknown variant %d (auto 0, generic 1, mla16 3)",
      fa2_launch_decode_sparse_generic},
+    {fa2_decode_mla16_sv_supports, fa2_launch_decode_mla16_sv, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla sparse: unknown variant %d (auto 0, generic 1, mla16 3)",
+     fa2_launch_decode_sparse_generic_v},
 };
-const DecodeForm &form_of(const DecodeCall &c) { return kForms[c.sparse ? 4 : c.packed && c.mla ? 3 : c.mla ? 2 : c.packed ? 1 : 0]; }
+const DecodeForm &form_of(const DecodeCall &c) {
+    return kForms[c.sparse && c.packed ? 5 : c.sparse ? 4 : c.packed && c.mla ? 3 : c.mla ? 2 : c.packed ? 1 : 0];
+}
 
 // The sizes of a paged cache, for check_decode ("kvcache paged") and check_append ("kvcache append"); on FA2_OK `cap` is the capacity.
 int check_paged(const char *who, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int64_t table_stride, int64_t &cap) {
@@ -358,7 +373,7 @@ int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
     p.indices = c.sparse ? c.indices : nullptr; p.topk = c.sparse ? c.topk : 0;
     for (int k = 0; k < 4; ++k) p.is[k] = c.sparse ? c.index_strides[k] : 0;
     const SplitShape shape = {c.B, c.H, c.H_kv, c.N_q, c.total_q, c.sparse ? c.topk : S_k, c.d, d_v, c.dtype_enum};  // (the lists: splits over slots)
-    p.num_splits = c.num_splits != 0 ? c.num_splits : c.sparse ? num_splits_mla_sparse(shape) : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
+    p.num_splits = c.num_splits != 0 ? c.num_splits : c.sparse && c.packed ? num_splits_mla_sparse_varlen(shape) : c.sparse ? num_splits_mla_sparse(shape) : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
     p.stream = (hipStream_t)c.hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
@@ -758,6 +773,43 @@ int32_t fa2_kvcache_mla_sparse_num_splits(int32_t B, int32_t H, int32_t H_kv, in
                                           int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || topk < 1) return 1;
     return num_splits_mla_sparse({B, H, H_kv, N_q, 0, topk, d, d_v, dtype_enum});
+}
+
+int fa2_fwd_kvcache_mla_sparse_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],
+                                      const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[3],
+                                      int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                      const int32_t *indices, const int64_t index_strides[3], int32_t topk, const int32_t *block_table,
+                                      int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                                      const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], int32_t B, int32_t H,
+                                      int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t num_blocks, int32_t page_size,
+                                      int32_t max_blocks, int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum, float scale,
+                                      int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    // the packed tensors in the fixed call's terms, as in fa2_fwd_kvcache_mla_varlen; the lists {token, KV head, slot} alike: no batch
+    // stride, the token axis where the query position is
+    int64_t qs[4], os[4], is[4];
+    const int64_t ls[2] = {0, l_head_stride};
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = packed4(q_strides, qs); c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls;
+    // (block_table null: the contiguous cache, page_size carries S_k, as in fa2_fwd_kvcache_mla_sparse); the list is the mask: no band
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = block_table ? 0 : page_size; c.d = d; c.dtype_enum = dtype_enum;
+    c.causal = 0; c.scale = scale; c.window_left = -1; c.window_right = -1; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = kv_dtype_enum != dtype_enum; c.kv_dtype_enum = kv_dtype_enum;
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    c.sparse = true; c.indices = indices; c.topk = topk;
+    c.index_strides = index_strides ? is : nullptr;
+    if (index_strides) { is[0] = 0; is[1] = index_strides[1]; is[2] = index_strides[0]; is[3] = index_strides[2]; }
+    return decode(c, nullptr);
+}
+
+int32_t fa2_kvcache_mla_sparse_varlen_num_splits(int32_t total_q, int32_t H, int32_t H_kv, int32_t topk, int32_t d, int32_t d_v,
+                                                 int32_t dtype_enum) {
+    if (total_q < 1 || H < 1 || H_kv < 1 || topk < 1) return 1;
+    return num_splits_mla_sparse_varlen({1, H, H_kv, 1, total_q, topk, d, d_v, dtype_enum});
 }
 
 int fa2_fwd_kvcache_varlen(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[3],

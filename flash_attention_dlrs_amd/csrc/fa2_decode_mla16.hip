@@ -83,6 +83,15 @@
 //               staged and counted twice.  A row without a valid entry: O = 0, L = +inf.
 // The LDS image, the swizzle, the S / softmax / P.V phases, the epilogue and the partial layout are the dense kernel's: on the
 // identity list over N_k = topk keys O and L equal the dense call's bit for bit at the same num_splits.
+//
+// Per-query key lists of packed queries (fa2_fwd_kvcache_mla_sparse_varlen).  SP and VQ together, instantiated in
+// fa2_decode_mla16_sv.hip alone: Q, O, L and the partial rows are the packed call's, the list of packed row t is entry [t, h_kv] and
+// names key positions of the sequence that owns t.  The x axis is (t * num_splits + split) * head tiles + head tile over total_q
+// tokens, however they fall into sequences.  The workgroup finds the owner of its row (fa2_varlen_owner: a uniform binary search
+// over cu_q on scalar loads, at most 16 steps, then fa2_varlen_seq) and takes N_k(b), the table row and the descales of that b; a row
+// no sequence owns leaves at once, before any barrier, and writes nothing -- what the query-tiled packed form does with a tile
+// without rows.  With `start` the packed row and N_q = 1 every expression below is the list-addressed kernel's: the query tiling of
+// VQ (the rotation along x, position-major rows, [q0, q1)) is taken with VQ && !SP alone, the packed partial layout with VQ.
 #include "fa2_decode.h"
 #include "fa2_mfma.h"
 
@@ -161,11 +170,21 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
         // consecutive ids, and the axis holds B * N_q in the hundreds of thousands (a sparse prefill chunk)
         const int per = a.num_splits * a.row_tiles, tok = bx / per;
         bx -= tok * per;
-        sp_b = tok / a.N_q;
-        sp_qi = tok - sp_b * a.N_q;
+        if constexpr (VQ) {
+#if FA2_DECODE_SPARSE && FA2_DECODE_VARLEN_Q
+            // packed: tok < total_q is a packed row.  Its owner, or nothing to do (uniform: before any barrier)
+            int st, n;
+            if (!fa2_varlen_owner(a.cu_q, a.B, a.total_q, a.N_q, tok, sp_b, st, n)) return;
+            sp_qi = tok;  // (qs[0] = os[0] = ls[0] = is[0] = 0: the packed row is the position of every address below)
+#endif
+        } else {
+            sp_b = tok / a.N_q;
+            sp_qi = tok - sp_b * a.N_q;
+        }
     }
+    constexpr bool VT = VQ && !SP;  // the query-tiled packed form
     const int hk = blockIdx.y, b = SP ? sp_b : blockIdx.z;
-    if constexpr (VQ) {
+    if constexpr (VT) {
         // The hardware deals consecutive workgroup ids round the chip's shader engines.  With tile t of every sequence at x = t the
         // tiles that have rows sit gridDim.x ids apart where the sequences are short (one-token decodes beside a long chunk), and
         // where that stride is a multiple of the number of engines they all land on ONE engine's 8 CUs, at one workgroup per CU
@@ -182,13 +201,13 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
         N_q = 1;
         start = sp_qi;
     }
-    if constexpr (VQ) {
+    if constexpr (VT) {
         fa2_varlen_seq(a.cu_q, b, a.total_q, a.N_q, start, N_q);
         if (rt * 64 >= a.g * N_q) return;  // no rows: nothing to write, no partials (uniform: before any barrier)
     }
     const int R = a.g * N_q;
-    const int q0 = VQ ? rt * 64 / a.g : 0;
-    const int q1 = VQ ? ((rt * 64 + 63) / a.g + 1 < N_q ? (rt * 64 + 63) / a.g + 1 : N_q) : N_q;
+    const int q0 = VT ? rt * 64 / a.g : 0;
+    const int q1 = VT ? ((rt * 64 + 63) / a.g + 1 < N_q ? (rt * 64 + 63) / a.g + 1 : N_q) : N_q;
 
     int NK, k0, k1;  // SP: [k0, k1) are SLOTS of the list, and so are kb0, ke and tk0 below; there is no band
     int wl = 0, wr = 0, spB = 0;
@@ -213,10 +232,10 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     // Fixed N_q: row = head * N_q + position.  VQ: row = position * g + head.
     const int srow = rt * 64 + rb * 32 + i;
     const int srowc = srow < R ? srow : R - 1;
-    const int sdiv = srowc / (VQ ? a.g : N_q);
-    const int srem = srowc - sdiv * (VQ ? a.g : N_q);
-    const int shg = VQ ? srem : sdiv;
-    const int sqi = VQ ? sdiv : srem;
+    const int sdiv = srowc / (VT ? a.g : N_q);
+    const int srem = srowc - sdiv * (VT ? a.g : N_q);
+    const int shg = VT ? srem : sdiv;
+    const int sqi = VT ? sdiv : srem;
 
     // ---- Q fragments: B operand of S^T = K Q^T.  Lane (i, h) holds Q[row][16ks + 8h .. +7].
     frag qf[kKS];
@@ -540,10 +559,10 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     for (int rbp = 0; rbp < 2; ++rbp) {
         const int row = rt * 64 + 32 * rbp + i;
         if (row >= R) continue;
-        const int ediv = row / (VQ ? a.g : N_q);  // (recomputed, not carried from the S phase: no register lives across the loop)
-        const int erem = row - ediv * (VQ ? a.g : N_q);
-        const int hg = VQ ? erem : ediv;
-        const int qi = VQ ? ediv : erem;
+        const int ediv = row / (VT ? a.g : N_q);  // (recomputed, not carried from the S phase: no register lives across the loop)
+        const int erem = row - ediv * (VT ? a.g : N_q);
+        const int hg = VT ? erem : ediv;
+        const int qi = VT ? ediv : erem;
         const int head = hk * a.g + hg;
         const float l = xl[32 * rbp + i] + xl[64 + 32 * rbp + i];
         const float mr = mf[32 * rbp + i];
@@ -595,9 +614,11 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
 constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0, kSP = FA2_DECODE_SPARSE != 0;
 
 template <typename T, typename C, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
-    const long long gx = (long long)p.num_splits * a.row_tiles * (kSP ? (long long)p.B * p.N_q : 1);
+    // (the lists: one position a workgroup, over B * N_q positions or, packed, total_q rows)
+    const long long gx = (long long)p.num_splits * a.row_tiles * (kSP ? (kVQ ? (long long)p.total_q : (long long)p.B * p.N_q) : 1);
     if (gx > 0x7fffffffLL) {
-        fa2_set_error(kSP ? "kvcache mla sparse: grid too large (B * N_q * num_splits * head tiles = %lld)"
+        fa2_set_error(kSP && kVQ ? "kvcache mla sparse varlen: grid too large (total_q * num_splits * head tiles = %lld)"
+                      : kSP      ? "kvcache mla sparse: grid too large (B * N_q * num_splits * head tiles = %lld)"
                           : "kvcache mla16 kernel: grid too large (num_splits * row tiles = %lld)", gx);
         return FA2_ERR_BAD_ARG;
     }
@@ -685,7 +706,10 @@ int launch(const Fa2DecodeProblem &p) {
 
 }  // namespace
 
-#if FA2_DECODE_SPARSE
+#if FA2_DECODE_SPARSE && FA2_DECODE_VARLEN_Q
+bool fa2_decode_mla16_sv_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_sv(const Fa2DecodeProblem &p) { return launch(p); }
+#elif FA2_DECODE_SPARSE
 bool fa2_decode_mla16_s_supports(const Fa2DecodeProblem &p) { return supports(p); }
 int fa2_launch_decode_mla16_s(const Fa2DecodeProblem &p) { return launch(p); }
 #elif FA2_DECODE_VARLEN_Q

@@ -17,12 +17,25 @@
 // table[b][j / page_size], the entry clamped to [0, num_blocks - 1].  The lane leaves the element offset of its V row (or -1) in
 // LDS, and the P.V loop walks the 64 slots in order, skipping those that are no key: only listed rows below N_k(b) are ever read,
 // and a key listed twice is read and counted twice.
+//
+// Packed queries (fa2_fwd_kvcache_mla_sparse_varlen).  VQ is a template parameter, instantiated in fa2_decode_sparse_generic_v.hip
+// (FA2_DECODE_SPARSE_VARLEN) alone: the x axis runs over total_q packed rows in B * N_q's place, the workgroup finds the sequence
+// that owns its row (fa2_varlen_owner: a uniform binary search over cu_q, then fa2_varlen_seq) and takes N_k(b), the table row and the
+// descales of that b; a row no sequence owns leaves at once, before any barrier, and writes nothing.  Q, O, L and the lists have no
+// batch stride there (the packed row is the position of every address), and the partial row is token * H + head, the combine's for
+// cu_q.  Everything else is the fixed form's.
 #include <math.h>
 
 #include "fa2_decode.h"
 #include "fa2_elem.h"
 
+#ifndef FA2_DECODE_SPARSE_VARLEN
+#define FA2_DECODE_SPARSE_VARLEN 0
+#endif
+
 namespace {
+
+constexpr bool kVQ = FA2_DECODE_SPARSE_VARLEN != 0;
 
 constexpr int kRowsPerWave = 4;
 constexpr int kWaves = 4;
@@ -54,10 +67,12 @@ struct SparseGenericArgs {
     const int32_t *table;  // paged cache: entry [b, i] at b * table_stride + i; ks[0], vs[0] are the block strides.  Null: contiguous
     int64_t table_stride;
     int page_size, num_blocks;
+    const int32_t *cu_q;  // VQ only: B + 1 offsets into the packed rows; qs[0] = os[0] = ls[0] = is[0] = 0, N_q holds max_seqlen_q
+    int total_q;
 };
 
-// grid (B * N_q * num_splits * nht, H_kv); DPL = output columns per lane = ceil(d_v / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
-template <class E, class C, int DPL>
+// grid (B * N_q * num_splits * nht, H_kv), VQ: total_q in B * N_q's place; DPL = output columns per lane = ceil(d_v / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
+template <class E, class C, int DPL, bool VQ>
 __global__ __launch_bounds__(kWaves * 64) void fa2_decode_sparse_generic_kernel(const SparseGenericArgs a) {
     using A = typename E::acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -70,7 +85,12 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_sparse_generic_kernel(
     const int per = a.num_splits * a.nht, tok = bx / per;
     bx -= tok * per;
     const int split = bx / a.nht, ht = bx - split * a.nht;
-    const int b = tok / a.N_q, qi = tok - b * a.N_q;
+    int b = tok / a.N_q, qi = tok - b * a.N_q;
+    if constexpr (VQ) {  // tok < total_q is a packed row: its owner, or nothing to do (uniform: before any barrier)
+        int st, n;
+        if (!fa2_varlen_owner(a.cu_q, a.B, a.total_q, a.N_q, tok, b, st, n)) return;
+        qi = tok;
+    }
     const int hk = blockIdx.y;
     const int d = a.d, dv = a.dv, g = a.gqa;
     int NK, s0, s1;
@@ -185,8 +205,8 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_sparse_generic_kernel(
             }
             if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + qi, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
         } else {  // every (split, row) is written, an empty split as O_s = 0, L_s = -inf: the workspace arrives uninitialised
-            const int64_t rows = (int64_t)a.B * a.H * a.N_q;
-            const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + h) * a.N_q + qi;
+            const int64_t rows = VQ ? (int64_t)a.total_q * a.H : (int64_t)a.B * a.H * a.N_q;
+            const int64_t prow = (int64_t)split * rows + (VQ ? (int64_t)qi * a.H + h : ((int64_t)b * a.H + h) * a.N_q + qi);
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
@@ -204,17 +224,18 @@ template <class E, class C, int DPL>
 void launch_k(const dim3 &grid, const dim3 &block, size_t smem, hipStream_t stream, const SparseGenericArgs &a) {
     static Fa2DeviceLatch attr_done;
     if (smem > 64 * 1024 && attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_sparse_generic_kernel<E, C, DPL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)fa2_decode_sparse_generic_kernel<E, C, DPL, kVQ>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)smem_bytes(sizeof(typename E::acc_t), 576));
         attr_done.mark();
     }
-    hipLaunchKernelGGL((fa2_decode_sparse_generic_kernel<E, C, DPL>), grid, block, smem, stream, a);
+    hipLaunchKernelGGL((fa2_decode_sparse_generic_kernel<E, C, DPL, kVQ>), grid, block, smem, stream, a);
 }
 
 template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const SparseGenericArgs &a) {
-    const long long gx = (long long)p.B * p.N_q * a.num_splits * a.nht;
+    const long long gx = (kVQ ? (long long)p.total_q : (long long)p.B * p.N_q) * a.num_splits * a.nht;
     if (gx > 0x7fffffffLL) {
-        fa2_set_error("kvcache mla sparse: grid too large (B * N_q * num_splits * ceil(g / 16) = %lld)", gx);
+        fa2_set_error(kVQ ? "kvcache mla sparse varlen: grid too large (total_q * num_splits * ceil(g / 16) = %lld)"
+                          : "kvcache mla sparse: grid too large (B * N_q * num_splits * ceil(g / 16) = %lld)", gx);
         return FA2_ERR_BAD_ARG;
     }
     const dim3 grid((unsigned)gx, p.H_kv), block(kWaves * 64);
@@ -234,7 +255,11 @@ template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const Sp
 
 }  // namespace
 
+#if FA2_DECODE_SPARSE_VARLEN
+int fa2_launch_decode_sparse_generic_v(const Fa2DecodeProblem &p) {
+#else
 int fa2_launch_decode_sparse_generic(const Fa2DecodeProblem &p) {
+#endif
     SparseGenericArgs a;
     a.Q = p.Q; a.K = p.K; a.V = p.V; a.O = p.O; a.L = p.L;
     for (int k = 0; k < 4; ++k) { a.qs[k] = p.qs[k]; a.ks[k] = p.ks[k]; a.vs[k] = p.vs[k]; a.os[k] = p.os[k]; a.is[k] = p.is[k]; }
@@ -248,6 +273,7 @@ int fa2_launch_decode_sparse_generic(const Fa2DecodeProblem &p) {
     a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
+    a.cu_q = p.cu_q; a.total_q = p.total_q;
     if (p.kv_dtype != p.dtype) {  // fp8 cache under 16-bit Q, O, L
         const bool e4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
         if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_F16)

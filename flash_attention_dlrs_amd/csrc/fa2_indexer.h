@@ -21,6 +21,14 @@ struct Fa2IndexerProblem {
     int32_t *idx;  // (B, N_q, topk)
     int64_t is[3];
     hipStream_t stream;
+    // packed (ragged) queries (the _varlen entry points): cu_q non-null.  Q is (total_q, H, d), W (total_q, H), LG (total_q, S_k), idx
+    // (total_q, topk), their strides in the fixed call's order with a batch stride of 0 -- {0, head, token, d}, {0, head, token},
+    // {0, row, column}, {0, row, slot} -- so the packed row takes the query position's place in every address.  Sequence b owns
+    // n_q(b) = fa2_varlen_seq(cu_q, b, total_q, max_q) rows from its start on, query i of them standing at N_k(b) - n_q(b) + i; N_q
+    // holds max_q.  The packed instantiations of the three kernels, a translation unit each (fa2_indexer_mfma16_v.hip,
+    // fa2_indexer_generic_v.hip, fa2_indexer_topk_v.hip).
+    const int32_t *cu_q;
+    int32_t total_q, max_q;
 };
 
 // n(b, qi): the candidate count of query qi of sequence b.  Position p = N_k(b) - N_q + qi; causal: keys 0 .. min(p, N_k(b) - 1), none
@@ -41,3 +49,8 @@ int fa2_launch_indexer_mfma16(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_generic(const Fa2IndexerProblem &p);
 // Selection (fa2_indexer_topk.hip): reads LG, lgs, seqlens, B, N_q, S_k, causal, topk, idx, is, stream.
 int fa2_launch_topk_indices(const Fa2IndexerProblem &p);
+// ... and their packed forms
+bool fa2_indexer_mfma16_v_supports(const Fa2IndexerProblem &p);
+int fa2_launch_indexer_mfma16_v(const Fa2IndexerProblem &p);
+int fa2_launch_indexer_generic_v(const Fa2IndexerProblem &p);
+int fa2_launch_topk_indices_v(const Fa2IndexerProblem &p);

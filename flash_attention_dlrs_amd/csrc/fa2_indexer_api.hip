@@ -1,5 +1,5 @@
 // fa2_indexer_api.hip -- host side of the MLA indexer (include/fa2_fwd.h): fa2_mla_indexer_logits, fa2_topk_indices, fa2_mla_indexer_topk
-// and fa2_mla_indexer_workspace_bytes.  One call struct and one check order of its own, beside the attention calls' DecodeCall
+// and fa2_mla_indexer_workspace_bytes, and their packed (_varlen) forms.  One call struct and one check order of its own, beside the attention calls' DecodeCall
 // (fa2_decode_api.hip): every check runs before any launch, then the score kernel of the form the variant names -- AUTO: the matrix
 // form where it runs, else the VALU form -- and the selection, on the call's stream.
 #include "fa2_indexer.h"
@@ -22,6 +22,32 @@ struct IndexerCall {
     int32_t *indices;
     const int64_t *index_strides;
     void *hip_stream;
+    // the _varlen entry points: packed queries over cu_seqlens_q, every stride array already in the fixed call's order with a batch
+    // stride of 0 (PackedStrides), N_q holding max_seqlen_q
+    bool packed = false;
+    const int32_t *cu_seqlens_q = nullptr;
+    int32_t total_q = 0;
+};
+
+// The stride arrays of a packed call in the fixed call's order: {token, head, column} -> {0, head, token, column}, {token, head} ->
+// {0, head, token}, {row, column} -> {0, row, column}; null stays null.
+struct PackedStrides {
+    int64_t q[4], w[3], lg[3], idx[3];
+    const int64_t *q4(const int64_t *s) {
+        if (!s) return nullptr;
+        q[0] = 0; q[1] = s[1]; q[2] = s[0]; q[3] = s[2];
+        return q;
+    }
+    const int64_t *w3(const int64_t *s) {
+        if (!s) return nullptr;
+        w[0] = 0; w[1] = s[1]; w[2] = s[0];
+        return w;
+    }
+    static const int64_t *rows3(const int64_t *s, int64_t (&out)[3]) {
+        if (!s) return nullptr;
+        out[0] = 0; out[1] = s[0]; out[2] = s[1];
+        return out;
+    }
 };
 
 bool is_fp8(int32_t dt) { return dt == FA2_DTYPE_F8E4M3 || dt == FA2_DTYPE_F8E5M2; }
@@ -76,7 +102,20 @@ int check_indexer(const IndexerCall &c, Fa2IndexerProblem &p) {
         fa2_set_error("mla indexer: H_I must be >= 1 (got %d)", c.H_I);
         return FA2_ERR_BAD_ARG;
     }
-    if (c.N_q < 1 || c.N_q > (1 << 28)) {
+    if (c.packed) {
+        if (!c.cu_seqlens_q) {
+            fa2_set_error("%s varlen: null cu_seqlens_q", who);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.total_q < 1 || c.total_q > (1 << 28)) {
+            fa2_set_error("%s varlen: total_q must be in [1, 2^28] (got %d)", who, c.total_q);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.N_q < 1 || c.N_q > (1 << 28)) {
+            fa2_set_error("%s varlen: max_seqlen_q must be in [1, 2^28] (got %d)", who, c.N_q);
+            return FA2_ERR_BAD_ARG;
+        }
+    } else if (c.N_q < 1 || c.N_q > (1 << 28)) {
         fa2_set_error("%s: N_q must be in [1, 2^28] (got %d)", who, c.N_q);
         return FA2_ERR_BAD_ARG;
     }
@@ -134,7 +173,7 @@ int check_indexer(const IndexerCall &c, Fa2IndexerProblem &p) {
             return FA2_ERR_BAD_ARG;
         }
     }
-    if (c.select && (long long)c.B * c.N_q > 0x7fffffffLL) {
+    if (c.select && !c.packed && (long long)c.B * c.N_q > 0x7fffffffLL) {  // (packed: total_q rows, <= 2^28)
         fa2_set_error("%s: grid too large (B * N_q = %lld)", who, (long long)c.B * c.N_q);
         return FA2_ERR_BAD_ARG;
     }
@@ -145,6 +184,8 @@ int check_indexer(const IndexerCall &c, Fa2IndexerProblem &p) {
     p.seqlens = c.cache_seqlens;
     p.B = c.B; p.N_q = c.N_q; p.S_k = (int32_t)cap; p.causal = c.causal != 0;
     p.stream = (hipStream_t)c.hip_stream;
+    p.cu_q = c.packed ? c.cu_seqlens_q : nullptr;
+    p.total_q = c.packed ? c.total_q : 0; p.max_q = c.packed ? c.N_q : 0;
     if (c.scores) {
         p.Q = c.q_idx; p.W = c.weights; p.K = c.k_idx; p.KS = c.k_scale;
         for (int k = 0; k < 4; ++k) p.qs[k] = c.q_strides[k];
@@ -166,11 +207,15 @@ int run_indexer(const IndexerCall &c) {
     int rc = check_indexer(c, p);
     if (rc != FA2_OK) return rc;
     if (c.scores) {
-        const bool matrix = c.variant == FA2_INDEXER_VARIANT_AUTO ? fa2_indexer_mfma16_supports(p) : c.variant == FA2_INDEXER_VARIANT_IDX16;
-        rc = matrix ? fa2_launch_indexer_mfma16(p) : fa2_launch_indexer_generic(p);  // (a forced matrix form that cannot run: refused there)
+        const bool fits = c.packed ? fa2_indexer_mfma16_v_supports(p) : fa2_indexer_mfma16_supports(p);
+        const bool matrix = c.variant == FA2_INDEXER_VARIANT_AUTO ? fits : c.variant == FA2_INDEXER_VARIANT_IDX16;
+        // (a forced matrix form that cannot run: refused there)
+        if (c.packed) rc = matrix ? fa2_launch_indexer_mfma16_v(p) : fa2_launch_indexer_generic_v(p);
+        else rc = matrix ? fa2_launch_indexer_mfma16(p) : fa2_launch_indexer_generic(p);
         if (rc != FA2_OK) return rc;
     }
-    return c.select ? fa2_launch_topk_indices(p) : FA2_OK;
+    if (!c.select) return FA2_OK;
+    return c.packed ? fa2_launch_topk_indices_v(p) : fa2_launch_topk_indices(p);
 }
 
 }  // namespace
@@ -211,6 +256,48 @@ int64_t fa2_mla_indexer_workspace_bytes(int32_t B, int32_t N_q, int32_t S_k) {
     if (B < 1 || N_q < 1 || S_k < 1) return 0;
     const int64_t rows = (int64_t)B * N_q;  // < 2^47
     return rows > INT64_MAX / (4 * (int64_t)S_k) ? INT64_MAX : 4 * rows * S_k;
+}
+
+int fa2_mla_indexer_logits_varlen(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                  const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                  const int64_t k_scale_strides[2], const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                                  const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride, int32_t B,
+                                  int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                                  int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal,
+                                  int32_t variant, void *hip_stream) {
+    PackedStrides s;
+    return run_indexer({true, false, q_idx, weights, k_idx, k_scale, logits, s.q4(q_strides), s.w3(w_strides), k_strides, k_scale_strides,
+                        PackedStrides::rows3(logit_strides, s.lg), cache_seqlens, block_table, block_table_stride, B, H_I, max_seqlen_q,
+                        S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum, causal, variant, 0, nullptr, nullptr,
+                        hip_stream, true, cu_seqlens_q, total_q});
+}
+
+int fa2_topk_indices_varlen(const float *logits, const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                            const int32_t *cache_seqlens, int32_t B, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t topk,
+                            int32_t causal, int32_t *indices, const int64_t index_strides[2], void *hip_stream) {
+    PackedStrides s;
+    return run_indexer({false, true, nullptr, nullptr, nullptr, nullptr, const_cast<float *>(logits), nullptr, nullptr, nullptr, nullptr,
+                        PackedStrides::rows3(logit_strides, s.lg), cache_seqlens, nullptr, 0, B, 0, max_seqlen_q, S_k, 0, 0, 0, 0, 0, 0,
+                        causal, 0, topk, indices, PackedStrides::rows3(index_strides, s.idx), hip_stream, true, cu_seqlens_q, total_q});
+}
+
+int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                const int64_t k_scale_strides[2], const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                                const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride, int32_t B,
+                                int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                                int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal, int32_t topk,
+                                int32_t *indices, const int64_t index_strides[2], int32_t variant, void *hip_stream) {
+    PackedStrides s;
+    return run_indexer({true, true, q_idx, weights, k_idx, k_scale, logits, s.q4(q_strides), s.w3(w_strides), k_strides, k_scale_strides,
+                        PackedStrides::rows3(logit_strides, s.lg), cache_seqlens, block_table, block_table_stride, B, H_I, max_seqlen_q,
+                        S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum, causal, variant, topk, indices,
+                        PackedStrides::rows3(index_strides, s.idx), hip_stream, true, cu_seqlens_q, total_q});
+}
+
+int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k) {
+    if (total_q < 1 || S_k < 1) return 0;
+    return 4 * (int64_t)total_q * S_k;  // < 2^64
 }
 
 }  // extern "C"

@@ -21,11 +21,23 @@
 //
 // Paged cache: key j is row j % page_size of page table[b][j / page_size] for ANY page size -- the staging thread looks its own
 // row up (one division and one clamped table entry per 16-byte load), so no page size falls to the VALU form.
+//
+// Packed queries (fa2_mla_indexer_logits_varlen).  VQ is a template parameter, instantiated in fa2_indexer_mfma16_v.hip
+// (FA2_INDEXER_VARLEN) alone.  The grid is (key chunks * ceil(max_seqlen_q / 8), B): the block takes its sequence's start and
+// n_q(b) from cu_q (fa2_varlen_seq), leaves at once -- uniform, before any barrier -- when its first position is at or past n_q(b),
+// counts the candidates with n_q(b) in N_q's place, and reads Q, W and writes the logits at packed row start + position (no batch
+// stride).  A query block never crosses a sequence.  Everything else is the fixed form's.
 #include "fa2_decode.h"
 #include "fa2_indexer.h"
 #include "fa2_mfma.h"
 
+#ifndef FA2_INDEXER_VARLEN
+#define FA2_INDEXER_VARLEN 0
+#endif
+
 namespace {
+
+constexpr bool kVQ = FA2_INDEXER_VARLEN != 0;
 
 struct Idx16Args {
     const char *Q, *K;
@@ -40,6 +52,8 @@ struct Idx16Args {
     int page_size, num_blocks;
     int H, N_q, S_k, causal;
     int chunk, nqb;  // keys per workgroup (a multiple of 64), query blocks per sequence
+    const int32_t *cu_q;  // VQ only: B + 1 offsets into the packed rows; qs[0] = ws[0] = lgs[0] = 0, N_q holds max_seqlen_q
+    int total_q;
 };
 
 constexpr int kTileKeys = 64;
@@ -47,7 +61,7 @@ constexpr int kRowB = 256;                     // a 16-bit LDS row of 128 column
 constexpr int kTileB = kTileKeys * kRowB;      // 16 KiB
 constexpr int kPartB = kIdxQB * 4 * 64 * 4;    // [position][wave][key] fp32 shares
 
-template <typename T, typename C, bool PAGED>
+template <typename T, typename C, bool PAGED, bool VQ>
 __global__ __launch_bounds__(256) void fa2_indexer_mfma16_kernel(const Idx16Args a) {
     using M = Mma<T>;
     using frag = typename M::frag;
@@ -62,14 +76,31 @@ __global__ __launch_bounds__(256) void fa2_indexer_mfma16_kernel(const Idx16Args
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4;
     const int b = blockIdx.y;
-    const int ck = blockIdx.x / a.nqb, q0 = (blockIdx.x - ck * a.nqb) * kIdxQB;
+    unsigned bx = blockIdx.x;
+    if constexpr (VQ) {
+        // The hardware deals consecutive workgroup ids round the chip's XCDs.  With query block 0 of every key chunk at x = chunk *
+        // nqb, the blocks of a one-token sequence that have a position sit nqb ids apart, and where nqb is a multiple of the number
+        // of XCDs they all land on ONE of them (measured: a 256-token chunk beside 63 one-token decodes, nqb = 32, took 2,596 us in
+        // the indexer against 300 us for the two fixed calls).  So sequence b takes its blocks rotated by b, as the query-tiled
+        // latent kernel does (fa2_decode_mla16.hip): the blocks of a chunk stay neighbours, the live blocks of consecutive
+        // sequences sit on consecutive ids.  A bijection of the same grid.
+        bx += blockIdx.y % gridDim.x;  // (< 2^31 + 2^16: inside an unsigned)
+        bx -= bx >= gridDim.x ? gridDim.x : 0;
+    }
+    const int ck = (int)bx / a.nqb, q0 = ((int)bx - ck * a.nqb) * kIdxQB;
 
+    // N_q: the query count of the sequence, from packed row `start` on
+    int N_q = a.N_q, start = 0;
+    if constexpr (VQ) {
+        fa2_varlen_seq(a.cu_q, b, a.total_q, a.N_q, start, N_q);
+        if (q0 >= N_q) return;  // no position of this block (uniform: before any barrier)
+    }
     // the candidate counts of the block's positions (0 for a position past N_q), non-decreasing: the last is the block's bound
     int cnt[kIdxQB];
     int bound = 0;
 #pragma unroll
     for (int p = 0; p < kIdxQB; ++p) {
-        cnt[p] = q0 + p < a.N_q ? fa2_indexer_count(a.seqlens, b, a.S_k, a.N_q, q0 + p, a.causal) : 0;
+        cnt[p] = q0 + p < N_q ? fa2_indexer_count(a.seqlens, b, a.S_k, N_q, q0 + p, a.causal) : 0;
         bound = cnt[p] > bound ? cnt[p] : bound;
     }
     const int k0 = ck * a.chunk;
@@ -83,16 +114,16 @@ __global__ __launch_bounds__(256) void fa2_indexer_mfma16_kernel(const Idx16Args
 #pragma unroll
     for (int p = 0; p < kIdxQB; ++p) {
         const int qi = q0 + p;
-        const bool live = qi < a.N_q;
+        const bool live = qi < N_q;
         const int head = 16 * wave + n;
-        const char *qp = a.Q + b * a.qs[0] + (int64_t)head * a.qs[1] + (int64_t)qi * a.qs[2] + g * 16;
+        const char *qp = a.Q + b * a.qs[0] + (int64_t)head * a.qs[1] + (int64_t)(start + qi) * a.qs[2] + g * 16;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
             qf[p][ks] = __builtin_bit_cast(frag, live && head < a.H ? *(const u32x4 *)(qp + ks * 64) : u32x4{0, 0, 0, 0});
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int hh = 16 * wave + 4 * g + r;
-            wv[p][r] = live && hh < a.H ? a.W[b * a.ws[0] + hh * a.ws[1] + qi * a.ws[2]] : 0.0f;
+            wv[p][r] = live && hh < a.H ? a.W[b * a.ws[0] + hh * a.ws[1] + (start + qi) * a.ws[2]] : 0.0f;
         }
     }
 
@@ -187,7 +218,7 @@ __global__ __launch_bounds__(256) void fa2_indexer_mfma16_kernel(const Idx16Args
                 if ((p & 3) != wave || j >= cnt[p]) continue;
                 const float s = ((part[(p * 4 + 0) * 64 + lane] + part[(p * 4 + 1) * 64 + lane]) + part[(p * 4 + 2) * 64 + lane]) +
                                 part[(p * 4 + 3) * 64 + lane];
-                a.LG[b * a.lgs[0] + (int64_t)(q0 + p) * a.lgs[1] + (int64_t)j * a.lgs[2]] = s * ksc;
+                a.LG[b * a.lgs[0] + (int64_t)(start + q0 + p) * a.lgs[1] + (int64_t)j * a.lgs[2]] = s * ksc;
             }
         }
         if (more) stage_write();
@@ -201,7 +232,7 @@ template <typename T, typename C, bool PAGED> int launch_t(const Fa2IndexerProbl
         fa2_set_error("mla indexer: grid too large (query blocks * key chunks = %lld)", gx);
         return FA2_ERR_BAD_ARG;
     }
-    hipLaunchKernelGGL((fa2_indexer_mfma16_kernel<T, C, PAGED>), dim3((unsigned)gx, p.B), dim3(256), 0, p.stream, a);
+    hipLaunchKernelGGL((fa2_indexer_mfma16_kernel<T, C, PAGED, kVQ>), dim3((unsigned)gx, p.B), dim3(256), 0, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("mla indexer idx16 kernel launch failed: %s", hipGetErrorString(e));
@@ -222,9 +253,8 @@ template <typename T> int launch_c(const Fa2IndexerProblem &p, const Idx16Args &
 
 bool fp8_cache(const Fa2IndexerProblem &p) { return p.k_dtype == FA2_DTYPE_F8E4M3 || p.k_dtype == FA2_DTYPE_F8E5M2; }
 
-}  // namespace
-
-bool fa2_indexer_mfma16_supports(const Fa2IndexerProblem &p) {
+bool supports(const Fa2IndexerProblem &p) {
+    if ((p.cu_q != nullptr) != kVQ) return false;
     if (p.dtype != FA2_DTYPE_F16 && p.dtype != FA2_DTYPE_BF16) return false;
     if (p.k_dtype != p.dtype && !fp8_cache(p)) return false;
     if (p.d != 128 || p.H > 64) return false;
@@ -238,8 +268,8 @@ bool fa2_indexer_mfma16_supports(const Fa2IndexerProblem &p) {
     return true;
 }
 
-int fa2_launch_indexer_mfma16(const Fa2IndexerProblem &p) {
-    if (!fa2_indexer_mfma16_supports(p)) {
+int launch(const Fa2IndexerProblem &p) {
+    if (!supports(p)) {
         fa2_set_error("mla indexer idx16 kernel: needs f16/bf16 q_idx (the cache alike, or fp8), d_I = 128, H_I <= 64, unit column "
                       "strides, 16-byte aligned rows");
         return FA2_ERR_UNSUPPORTED;
@@ -254,7 +284,21 @@ int fa2_launch_indexer_mfma16(const Fa2IndexerProblem &p) {
     // The two regimes.  A decode step (one or two positions: one query block a sequence) is bound by the read of the cache and wants
     // the chip full: 256-key chunks, four tiles a workgroup.  A prefill chunk (hundreds of query blocks) is bound by the matrix
     // work; its workgroups are many already, and a 2,048-key chunk re-reads the 128 KiB of a block's Q fragments once per 32 tiles.
+    // (packed: the query blocks that have positions are at most the grid's, and at most ceil(total_q / 8) + B)
     a.nqb = (p.N_q + kIdxQB - 1) / kIdxQB;
-    a.chunk = (long long)p.B * a.nqb >= 256 ? 2048 : 256;
+    long long blocks = (long long)p.B * a.nqb;
+    if (kVQ && (p.total_q + kIdxQB - 1) / kIdxQB + (long long)p.B < blocks) blocks = (p.total_q + kIdxQB - 1) / kIdxQB + (long long)p.B;
+    a.chunk = blocks >= 256 ? 2048 : 256;
+    a.cu_q = p.cu_q; a.total_q = p.total_q;
     return p.dtype == FA2_DTYPE_BF16 ? launch_c<__bf16>(p, a) : launch_c<_Float16>(p, a);
 }
+
+}  // namespace
+
+#if FA2_INDEXER_VARLEN
+bool fa2_indexer_mfma16_v_supports(const Fa2IndexerProblem &p) { return supports(p); }
+int fa2_launch_indexer_mfma16_v(const Fa2IndexerProblem &p) { return launch(p); }
+#else
+bool fa2_indexer_mfma16_supports(const Fa2IndexerProblem &p) { return supports(p); }
+int fa2_launch_indexer_mfma16(const Fa2IndexerProblem &p) { return launch(p); }
+#endif

@@ -17,9 +17,20 @@
 //      is a function of the logits alone, and slots ascend with the position.
 //
 // Only entries j < n(b, qi) of a row are read.  Stores are plain vector stores.
+//
+// Packed queries (fa2_topk_indices_varlen).  VQ is a template parameter, instantiated in fa2_indexer_topk_v.hip (FA2_INDEXER_VARLEN)
+// alone: one workgroup per packed row, which finds the sequence that owns it (fa2_varlen_owner: a uniform binary search over cu_q,
+// then fa2_varlen_seq) and counts its candidates with n_q(b) in N_q's place; a row no sequence owns leaves at once and writes
+// nothing.  The logits row and the list are the packed row's (no batch stride).  The rest is the fixed form's.
 #include "fa2_indexer.h"
 
+#ifndef FA2_INDEXER_VARLEN
+#define FA2_INDEXER_VARLEN 0
+#endif
+
 namespace {
+
+constexpr bool kVQ = FA2_INDEXER_VARLEN != 0;
 
 constexpr int kThreads = 1024, kWaves = kThreads / 64;
 
@@ -30,20 +41,26 @@ __device__ __forceinline__ uint32_t image(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ __launch_bounds__(kThreads) void fa2_topk_indices_kernel(const Fa2IndexerProblem a) {
+template <bool VQ> __global__ __launch_bounds__(kThreads) void fa2_topk_indices_kernel(const Fa2IndexerProblem a) {
     __shared__ int hist[256];
     __shared__ int wsum[kWaves];
     __shared__ uint32_t s_prefix;
     __shared__ int s_rem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x / a.N_q, qi = blockIdx.x - b * a.N_q;
-    const int n = fa2_indexer_count(a.seqlens, b, a.S_k, a.N_q, qi, a.causal);
-    int32_t *out = a.idx + b * a.is[0] + (int64_t)qi * a.is[1];
+    int b = blockIdx.x / a.N_q, qi = blockIdx.x - b * a.N_q, N_q = a.N_q, row = qi;  // row: of the logits and the lists within b's
+    if constexpr (VQ) {  // blockIdx.x < total_q is a packed row: its owner, or nothing to do (uniform: before any barrier)
+        int start;
+        row = blockIdx.x;
+        if (!fa2_varlen_owner(a.cu_q, a.B, a.total_q, a.max_q, row, b, start, N_q)) return;
+        qi = row - start;
+    }
+    const int n = fa2_indexer_count(a.seqlens, b, a.S_k, N_q, qi, a.causal);
+    int32_t *out = a.idx + b * a.is[0] + (int64_t)row * a.is[1];
     if (n <= a.topk) {  // the identity prefix, no logit read
         for (int s = tid; s < a.topk; s += kThreads) out[(int64_t)s * a.is[2]] = s < n ? s : -1;
         return;
     }
-    const float *lg = a.LG + b * a.lgs[0] + (int64_t)qi * a.lgs[1];
+    const float *lg = a.LG + b * a.lgs[0] + (int64_t)row * a.lgs[1];
 
     // ---- 1. the threshold image: the topk-th largest
     uint32_t prefix = 0, mask = 0;
@@ -106,13 +123,17 @@ __global__ __launch_bounds__(kThreads) void fa2_topk_indices_kernel(const Fa2Ind
 
 }  // namespace
 
+#if FA2_INDEXER_VARLEN
+int fa2_launch_topk_indices_v(const Fa2IndexerProblem &p) {
+#else
 int fa2_launch_topk_indices(const Fa2IndexerProblem &p) {
-    const long long gx = (long long)p.B * p.N_q;
+#endif
+    const long long gx = kVQ ? (long long)p.total_q : (long long)p.B * p.N_q;
     if (gx > 0x7fffffffLL) {
         fa2_set_error("topk indices: grid too large (B * N_q = %lld)", gx);
         return FA2_ERR_BAD_ARG;
     }
-    hipLaunchKernelGGL(fa2_topk_indices_kernel, dim3((unsigned)gx), dim3(kThreads), 0, p.stream, p);
+    hipLaunchKernelGGL(fa2_topk_indices_kernel<kVQ>, dim3((unsigned)gx), dim3(kThreads), 0, p.stream, p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("topk indices kernel launch failed: %s", hipGetErrorString(e));

@@ -1131,3 +1131,186 @@ def flash_attention_mla_indexer_topk(q_idx, weights, k_idx, cache_seqlens, dev, 
     _lib.fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_seqlens, convert_triton_dtype(q_idx.dtype),
                               convert_triton_dtype(k_idx.dtype), block_table=block_table, causal=causal, variant=v)
     return (indices, logits) if return_logits else indices
+
+
+def _check_cu_seqlens_q(who, cu_seqlens_q, max_seqlen_q, anchor, anchor_name):
+    """cu_seqlens_q and max_seqlen_q of a packed call, by the rules of check_mla_varlen_args; returns B."""
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 \
+            or not cu_seqlens_q.is_contiguous() or cu_seqlens_q.numel() < 2:
+        raise ValueError(f"{who}: cu_seqlens_q must be a contiguous int32 tensor of B + 1 >= 2 entries")
+    if cu_seqlens_q.device != anchor.device:
+        raise ValueError(f"{who}: cu_seqlens_q must be on {anchor_name}'s device ({anchor.device}), got {cu_seqlens_q.device}")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or not 1 <= max_seqlen_q <= 1 << 28:
+        raise ValueError(f"{who}: max_seqlen_q must be an int in [1, 2^28], got {max_seqlen_q!r}")
+    return cu_seqlens_q.numel() - 1
+
+
+def _sparse_varlen_indices(indices, total_q, H_kv):
+    """The (total_q, H_kv, topk) view of a packed indices argument: 3-D as it is, (total_q, topk) expanded over the KV heads without a
+    copy."""
+    who = "mla sparse varlen decode"
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or indices.dim() not in (2, 3):
+        raise ValueError(f"{who}: indices must be an int32 tensor (total_q, H_kv, topk) or (total_q, topk), got "
+                         f"{(tuple(indices.shape), indices.dtype) if isinstance(indices, torch.Tensor) else type(indices).__name__}")
+    view = indices if indices.dim() == 3 else indices.unsqueeze(1).expand(-1, H_kv, -1)
+    if view.shape[:2] != (total_q, H_kv) or view.shape[2] < 1:
+        raise ValueError(f"{who}: indices must be (total_q, H_kv, topk) = ({total_q}, {H_kv}, topk) or (total_q, topk) with topk >= 1, "
+                         f"got {tuple(indices.shape)}")
+    if view.shape[2] > 1 << 28:
+        raise ValueError(f"{who}: topk must be <= 2^28, got {view.shape[2]}")
+    if any(s < 0 for s in view.stride()):
+        raise ValueError(f"{who}: indices with negative strides are not supported, got {tuple(view.stride())}")
+    return view
+
+
+def check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v=512, num_splits=0, kv_descale=None,
+                                 block_table=None):
+    """ValueError for what flash_attention_mla_sparse_varlen_decode_forward cannot take: the packed Q, cu_seqlens_q and max_seqlen_q by
+    the rules of check_mla_varlen_args; the latent cache, d_v, cache_seqlens, block_table, num_splits and kv_descale by those of
+    check_mla_sparse_args (an fp8 cache needs its kv_descale); indices int32 on Q's device, (total_q, H_kv, topk) or (total_q, topk)
+    with topk >= 1.  Pure: takes CPU tensors as well."""
+    who = "mla sparse varlen decode"
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] < 1:
+        raise ValueError(f"{who}: Q must be packed (total_q, H, d) with total_q >= 1, got "
+                         f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
+        raise ValueError(f"{who}: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    d = KV_cache.shape[3]
+    if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
+        raise ValueError(f"{who}: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
+    if not 1 <= d <= 576 or d_v > 512:
+        raise ValueError(f"{who}: d must be in [1, 576] and d_v in [1, 512], got d = {d}, d_v = {d_v}")
+    B = _check_cu_seqlens_q(who, cu_seqlens_q, max_seqlen_q, Q, "Q")
+    if Q.shape[0] * Q.shape[1] > 1 << 40:
+        raise ValueError(f"{who}: total_q * H must be <= 2^40, got {Q.shape[0]} * {Q.shape[1]}")
+    fp8 = KV_cache.dtype in FP8_CACHE_DTYPES
+    if kv_descale is not None and not fp8:
+        raise ValueError(f"{who}: kv_descale goes with an fp8 KV_cache, not with {KV_cache.dtype}")
+    if fp8 and kv_descale is None:
+        raise ValueError(f"{who}: an fp8 KV_cache ({KV_cache.dtype}) needs its kv_descale (quantize_kv_cache returns it)")
+    # the cache's rules are the fixed-N_q call's: seen through a (B, H, 1, d) view of Q (no data is read), K and V the one tensor
+    check_kvcache_args(Q[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1, -1), KV_cache, KV_cache, cache_seqlens, None, num_splits,
+                       None, None, block_table)
+    _kvcache_descale("kv_descale", kv_descale, Q, B, KV_cache.shape[1])
+    view = _sparse_varlen_indices(indices, Q.shape[0], KV_cache.shape[1])
+    if view.device != Q.device:
+        raise ValueError(f"{who}: indices must be on Q's device ({Q.device}), got {view.device}")
+
+
+def flash_attention_mla_sparse_varlen_decode_forward(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, d_v=512,
+                                                     scale=1.0, num_splits=0, variant="auto", kv_descale=None, block_table=None, **mask):
+    """Sparse multi-head latent attention of variable-length (packed) queries (include/fa2_fwd.h fa2_fwd_kvcache_mla_sparse_varlen)
+    -> (O, L): flash_attention_mla_sparse_decode_forward for a ragged step -- a prefill chunk beside one-token decodes, draft tokens
+    of a different count per sequence -- in one call.  Q (total_q, H, d), any strides; cu_seqlens_q int32 (B + 1,) on Q's device and
+    max_seqlen_q as in flash_attention_mla_varlen_decode_forward: sequence b owns min(cu[b + 1] - cu[b], max_seqlen_q) rows from cu[b]
+    on, none is legal.  indices: int32 on Q's device, (total_q, H_kv, topk), any non-negative strides, or (total_q, topk) -- what
+    flash_attention_mla_indexer_topk_varlen returns -- expanded over the KV heads without a copy.  Entry [t, hk, s] is a logical key
+    position of THE SEQUENCE THAT OWNS packed row t; an entry < 0 or >= N_k(b) of that sequence is no key, a key listed twice counts
+    twice, a row without a valid entry gets O = 0, L = +inf.  KV_cache, d_v, cache_seqlens, block_table and kv_descale are
+    flash_attention_mla_sparse_decode_forward's; so are causal= and window= (both a ValueError: the list is the mask), num_splits and
+    variant.  O (total_q, H, d_v) contiguous, L (H, total_q) log2-domain, both in Q's dtype; rows outside every sequence are not
+    written.  Sequence b's rows equal flash_attention_mla_sparse_decode_forward's on that sequence alone, bit for bit at the same
+    explicit num_splits.  The append side is mla_kvcache_append_varlen, called first.  No autograd, no autotuner."""
+    for name in mask:
+        if name in ("causal", "window"):
+            raise ValueError(f"mla sparse varlen decode: there is no {name} argument: the index list is the mask (the indexer respects "
+                             f"causality; leave out what a position must not see)")
+        raise TypeError(f"flash_attention_mla_sparse_varlen_decode_forward() got an unexpected keyword argument {name!r}")
+    check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, num_splits, kv_descale, block_table)
+    if variant not in _lib.KVCACHE_MLA_VARIANTS:
+        raise ValueError(f"mla sparse varlen decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
+    _check_dev(dev, Q, KV_cache, KV_cache)
+    total_q, H, d = Q.shape
+    B, H_kv = cu_seqlens_q.numel() - 1, KV_cache.shape[1]
+    view = _sparse_varlen_indices(indices, total_q, H_kv)
+    dtype = convert_triton_dtype(Q.dtype)
+    n = num_splits or _lib.kvcache_mla_sparse_varlen_num_splits(total_q, H, H_kv, view.shape[2], d, d_v, dtype)
+    O, L, ws = _kvcache_outputs(Q, (total_q, H, d_v), (H, total_q), _lib.kvcache_varlen_workspace_bytes(total_q, H, d_v, n) if n > 1 else 0)
+    kd = _kvcache_descale("kv_descale", kv_descale, Q, B, H_kv)
+    _lib.fa2_fwd_kvcache_mla_sparse_varlen(Q, KV_cache, KV_cache[..., :d_v], O, L, view, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
+                                           convert_triton_dtype(KV_cache.dtype), k_descale=kd, v_descale=kd, block_table=block_table,
+                                           scale=scale, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+    return O, L
+
+
+def check_mla_indexer_varlen_args(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk=2048, k_scale=None,
+                                  block_table=None):
+    """ValueError, naming the argument, for what flash_attention_mla_indexer_topk_varlen cannot take: q_idx packed (total_q, H_I, d_I)
+    and weights float32 (total_q, H_I); cu_seqlens_q and max_seqlen_q by the rules of check_mla_varlen_args; everything else by the
+    rules of check_mla_indexer_args.  Pure: takes CPU tensors."""
+    who = "mla indexer varlen"
+    if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 3 or q_idx.shape[0] < 1:
+        raise ValueError(f"{who}: q_idx must be packed (total_q, H_I, d_I) with total_q >= 1, got "
+                         f"{tuple(q_idx.shape) if isinstance(q_idx, torch.Tensor) else type(q_idx).__name__}")
+    total_q, H_I, _ = q_idx.shape
+    if total_q > 1 << 28:
+        raise ValueError(f"{who}: total_q must be <= 2^28, got {total_q}")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (total_q, H_I):
+        raise ValueError(f"{who}: weights must be a float32 tensor (total_q, H_I) = ({total_q}, {H_I})")
+    B = _check_cu_seqlens_q(who, cu_seqlens_q, max_seqlen_q, q_idx, "q_idx")
+    # the key side's rules are the fixed call's: seen through (B, H_I, 1, d_I) / (B, H_I, 1) views of the first row (no data is read)
+    check_mla_indexer_args(q_idx[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1, -1), weights[:1].transpose(0, 1).unsqueeze(0).expand(B, -1, -1),
+                           k_idx, cache_seqlens, topk, k_scale, block_table)
+    for name, t in (("q_idx", q_idx), ("weights", weights)):
+        if any(s < 0 for s in t.stride()):
+            raise ValueError(f"{who}: {name} with negative strides is not supported")
+    if weights.device != q_idx.device:
+        raise ValueError(f"{who}: weights must be on q_idx's device ({q_idx.device}), got {weights.device}")
+
+
+def mla_indexer_logits_varlen(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, causal=True, k_scale=None,
+                              block_table=None, variant="auto"):
+    """The index scores of packed queries alone (include/fa2_fwd.h fa2_mla_indexer_logits_varlen) -> logits float32
+    (total_q, capacity): row start(b) + i holds mla_indexer_logits' row of query i of sequence b, which stands at position
+    N_k(b) - n_q(b) + i; entries at and past its candidate count, and rows no sequence owns, are NOT written: the buffer comes from
+    torch.empty.  Arguments as flash_attention_mla_indexer_topk_varlen."""
+    check_mla_indexer_varlen_args(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, 1, k_scale, block_table)
+    v = _indexer_variant(variant)
+    _indexer_dev(dev, q_idx)
+    logits = torch.empty((q_idx.shape[0], _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
+    _lib.fa2_mla_indexer_logits_varlen(q_idx, weights, k_idx, k_scale, logits, cu_seqlens_q, max_seqlen_q, cache_seqlens,
+                                       convert_triton_dtype(q_idx.dtype), convert_triton_dtype(k_idx.dtype), block_table=block_table,
+                                       causal=causal, variant=v)
+    return logits
+
+
+def topk_indices_varlen(logits, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk, *, causal=True):
+    """The selection of the MLA indexer over packed rows (fa2_topk_indices_varlen): float32 logits (total_q, S_k) of any non-negative
+    strides -> indices int32 (total_q, topk).  Row start(b) + i is query i of sequence b and has topk_indices' candidates with n_q(b)
+    in N_q's place; its list is topk_indices'.  A row no sequence owns is not written."""
+    who = "topk indices varlen"
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError(f"{who}: logits must be a float32 tensor (total_q, S_k)")
+    total_q, S_k = logits.shape
+    if min(total_q, S_k) < 1 or max(total_q, S_k) > 1 << 28 or any(s < 0 for s in logits.stride()):
+        raise ValueError(f"{who}: logits must be (total_q, S_k) with both sizes in [1, 2^28] and no negative stride, got "
+                         f"{tuple(logits.shape)}, strides {tuple(logits.stride())}")
+    B = _check_cu_seqlens_q(who, cu_seqlens_q, max_seqlen_q, logits, "logits")
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= 1 << 28:
+        raise ValueError(f"{who}: topk must be an int in [1, 2^28], got {topk!r}")
+    if cache_seqlens is not None:
+        _check_cache_seqlens(cache_seqlens, B, logits, "logits", " (or None)")
+    indices = torch.empty((total_q, topk), dtype=torch.int32, device=logits.device)
+    _lib.fa2_topk_indices_varlen(logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, causal=causal)
+    return indices
+
+
+def flash_attention_mla_indexer_topk_varlen(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, topk=2048, causal=True,
+                                            k_scale=None, block_table=None, variant="auto", return_logits=False):
+    """The MLA indexer over variable-length (packed) queries (include/fa2_fwd.h fa2_mla_indexer_topk_varlen) -> indices int32
+    (total_q, topk), the key lists flash_attention_mla_sparse_varlen_decode_forward takes as they are.  q_idx (total_q, H_I, d_I) in
+    f16, bf16 or f32, any strides; weights float32 (total_q, H_I); cu_seqlens_q int32 (B + 1,) on q_idx's device and max_seqlen_q as
+    in flash_attention_mla_varlen_decode_forward; k_idx, k_scale, cache_seqlens, block_table, topk, causal, variant and return_logits
+    are flash_attention_mla_indexer_topk's.  Query i of sequence b stands at position N_k(b) - n_q(b) + i.  Sequence b's rows equal
+    flash_attention_mla_indexer_topk's on that sequence alone, byte for byte; rows no sequence owns are not written.  return_logits:
+    (indices, logits), the float32 (total_q, capacity) scores.  No autograd."""
+    check_mla_indexer_varlen_args(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk, k_scale, block_table)
+    v = _indexer_variant(variant)
+    _indexer_dev(dev, q_idx)
+    total_q = q_idx.shape[0]
+    logits = torch.empty((total_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
+    indices = torch.empty((total_q, topk), dtype=torch.int32, device=q_idx.device)
+    _lib.fa2_mla_indexer_topk_varlen(q_idx, weights, k_idx, k_scale, logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens,
+                                     convert_triton_dtype(q_idx.dtype), convert_triton_dtype(k_idx.dtype), block_table=block_table,
+                                     causal=causal, variant=v)
+    return (indices, logits) if return_logits else indices

@@ -829,6 +829,48 @@ int32_t fa2_kvcache_mla_sparse_num_splits(int32_t B, int32_t H, int32_t H_kv, in
                                           int32_t dtype_enum);
 
 /*
+ * Sparse MLA decode of packed (ragged) queries: fa2_fwd_kvcache_mla_sparse over the packed tensors of fa2_fwd_kvcache_mla_varlen -- a
+ * prefill chunk beside one-token decodes, or draft tokens of a different count per sequence, in one call.
+ *
+ *   Tensors.  Q (total_q, H, d), O (total_q, H, d_v) with three element strides {token, head, column}, L (H, total_q) with unit token
+ *             stride and l_head_stride; cu_seqlens_q int32 on the device, B + 1 entries, and max_seqlen_q as in
+ *             fa2_fwd_kvcache_mla_varlen: sequence b owns min(clamp(cu[b + 1]) - clamp(cu[b]), max_seqlen_q) rows from clamp(cu[b])
+ *             on, the clamp to [0, total_q]; none is legal.  K, V, cache_seqlens, block_table, the descales: fa2_fwd_kvcache_mla_sparse's.
+ *   Indices.  int32 on the device, (total_q, H_kv, topk) with three element strides {token, KV head, slot}, each >= 0, 0 allowed.
+ *             Entry [t, hk, s] is a logical key position of THE SEQUENCE THAT OWNS packed row t; it is no key when < 0 or
+ *             >= N_k(b) of that sequence.  Duplicates, a row without a valid entry (O = 0, L = +inf), the splits over the slots, the
+ *             fp8 cache with its required descales and the block table of any page size are fa2_fwd_kvcache_mla_sparse's.
+ *   Rows.     Row t belongs to the last sequence b in [0, B) whose clamped offset is <= t, if t lies in that sequence's rows.  A row
+ *             no sequence owns -- at or past the clamped cu_seqlens_q[B], or past max_seqlen_q within its sequence -- is neither
+ *             read nor written, in O, L and the workspace alike: what fa2_fwd_kvcache_mla_varlen does with it.  Offsets that do not
+ *             ascend may give wrong results; every address formed lies inside the tensors for any contents of cu_seqlens_q.
+ *   Splits.   The workspace holds fa2_kvcache_varlen_workspace_bytes(total_q, H, d_v, num_splits) bytes; num_splits = 0 resolves to
+ *             fa2_kvcache_mla_sparse_varlen_num_splits(...).
+ *   Variants. As fa2_fwd_kvcache_mla_sparse: a workgroup owns 64 (GENERIC: 16) heads of one (packed row, KV head).
+ *
+ * Errors: fa2_fwd_kvcache_mla_sparse's and the packed call's (null cu_seqlens_q, total_q < 1, max_seqlen_q outside [1, 2^28]), all
+ * before any launch.
+ */
+int fa2_fwd_kvcache_mla_sparse_varlen(const void *Q, const void *K, const void *V, void *O, void *L,
+                                      const int64_t q_strides[3], const int64_t k_strides[4], const int64_t v_strides[4],
+                                      const int64_t o_strides[3], int64_t l_head_stride,
+                                      const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                      const int32_t *indices, const int64_t index_strides[3], int32_t topk,
+                                      const int32_t *block_table, int64_t block_table_stride,
+                                      const float *k_descale, const float *v_descale,
+                                      const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                                      int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q,
+                                      int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                                      int32_t dtype_enum, int32_t kv_dtype_enum,
+                                      float scale, int32_t num_splits,
+                                      void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* What num_splits = 0 resolves to for it: fa2_kvcache_mla_sparse_num_splits with total_q tokens in B * N_q's place.  The workgroup
+ * count does not depend on how the tokens fall into sequences: a workgroup owns the heads of one packed row. */
+int32_t fa2_kvcache_mla_sparse_varlen_num_splits(int32_t total_q, int32_t H, int32_t H_kv, int32_t topk, int32_t d, int32_t d_v,
+                                                 int32_t dtype_enum);
+
+/*
  * The MLA indexer (DeepSeek-V3.2's lightning indexer): the stage in front of fa2_fwd_kvcache_mla_sparse.  It scores every cached
  * token against every query token and makes the key lists that call takes.  Three entry points: the scores alone, the selection
  * alone over any fp32 logits, and both on one stream.
@@ -892,6 +934,52 @@ int fa2_mla_indexer_topk(const void *q_idx, const float *weights, const void *k_
 /* Bytes of the contiguous fp32 logits buffer (B, N_q, S_k): 4 * B * N_q * S_k, 0 if a size is < 1, INT64_MAX where that product
  * does not fit. */
 int64_t fa2_mla_indexer_workspace_bytes(int32_t B, int32_t N_q, int32_t S_k);
+
+/*
+ * The MLA indexer over packed (ragged) queries: the three entry points above for the packed step fa2_fwd_kvcache_mla_sparse_varlen
+ * takes.  cu_seqlens_q (int32 on the device, B + 1 entries) and max_seqlen_q are fa2_fwd_kvcache_mla_varlen's: sequence b owns
+ * n_q(b) = min(clamp(cu[b + 1]) - clamp(cu[b]), max_seqlen_q) rows from clamp(cu[b]) on, none is legal.
+ *
+ *   Tensors.  q_idx (total_q, H_I, d_I) with three element strides {token, head, column}; weights fp32 (total_q, H_I), two strides
+ *             {token, head}; logits fp32 (total_q, S_k), two strides {row, column}; indices int32 (total_q, topk), two strides
+ *             {row, slot} -- the two-dimensional form fa2_fwd_kvcache_mla_sparse_varlen's Python surface expands over the KV heads.
+ *             k_idx, k_scale, cache_seqlens and block_table are the fixed calls'.
+ *   Mask.     Query i of sequence b stands at position N_k(b) - n_q(b) + i; its candidate count n is the fixed call's with n_q(b)
+ *             in N_q's place.
+ *   Rows.     The score kernels walk the sequences (a query block of 8 positions lies inside one sequence), the selection takes one
+ *             workgroup per packed row and finds its owner as fa2_fwd_kvcache_mla_sparse_varlen does.  A row no sequence owns is
+ *             neither scored nor selected: nothing of its logits row or its list is written.
+ *   The formula of the logits, which entries are written, the order and tie rule of the lists, the -1 padding and "a function of the
+ *   logits alone" are the fixed calls': sequence b of a packed call gives the bytes the fixed call gives on that sequence alone.
+ *
+ * Errors: the fixed calls' (N_q's range is max_seqlen_q's), and FA2_ERR_BAD_ARG for a null cu_seqlens_q and total_q outside
+ * [1, 2^28]; all before any launch.
+ */
+int fa2_mla_indexer_logits_varlen(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                  const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                  const int64_t k_scale_strides[2], const int64_t logit_strides[2],
+                                  const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                  const int32_t *block_table, int64_t block_table_stride,
+                                  int32_t B, int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks,
+                                  int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                                  int32_t causal, int32_t variant, void *hip_stream);
+
+int fa2_topk_indices_varlen(const float *logits, const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                            const int32_t *cache_seqlens, int32_t B, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                            int32_t topk, int32_t causal, int32_t *indices, const int64_t index_strides[2], void *hip_stream);
+
+int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                const int64_t k_scale_strides[2], const int64_t logit_strides[2],
+                                const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                const int32_t *block_table, int64_t block_table_stride,
+                                int32_t B, int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks,
+                                int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                                int32_t causal, int32_t topk, int32_t *indices, const int64_t index_strides[2], int32_t variant,
+                                void *hip_stream);
+
+/* Bytes of the contiguous fp32 logits buffer (total_q, S_k): 4 * total_q * S_k, 0 if a size is < 1. */
+int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k);
 
 /*
  * The fused ragged MLA step: fa2_kvcache_mla_append_varlen over cu_seqlens_q (total_new = total_q, max_seqlen_new = max_seqlen_q;
