@@ -593,10 +593,10 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
                                                                : ((int64_t)b * a.H + head) * N_q + qi);
             float *op = a.o_part + prow * kDV + 128 * wave + 4 * h;
             float invp = inv;
-            // SP: the products of this branch are kept apart from the one-split branch's.  The compiler otherwise hoists a product the
-            // two branches share above them, and the one-split branch then rounds that fp32 product to f16 (two roundings) where the
-            // dense kernel's v_fma_mixlo_f16 rounds once: one ulp of one element in some 10^5, against the bit-for-bit tests
-            if constexpr (SP) asm volatile("" : "+v"(invp));
+            // SP, VQ: the products of this branch are kept apart from the one-split branch's.  The compiler otherwise hoists a product
+            // the two branches share above them, and the one-split branch then rounds that fp32 product to f16 (two roundings) where
+            // the fixed dense kernel's v_fma_mixlo_f16 rounds once: one ulp of one element in some 10^5, against the bit-for-bit tests
+            if constexpr (SP || VQ) asm volatile("" : "+v"(invp));
 #pragma unroll
             for (int db = 0; db < 4; ++db)
 #pragma unroll

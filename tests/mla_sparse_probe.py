@@ -61,9 +61,9 @@ def lists(n_q, topk, device=None):
     return idx.to(torch.int32).to(device)
 
 
-def valid(idx):
-    """(B, 1, N_q, topk) bool: the slots that are keys of their sequence"""
-    nk = torch.tensor(LENS, device=idx.device).view(B, 1, 1, 1)
+def valid(idx, lens=LENS):
+    """(B, 1, N_q, topk) bool: the slots that are keys of their sequence (lens: the B lengths, this batch's by default)"""
+    nk = torch.tensor(list(lens), device=idx.device).view(len(lens), 1, 1, 1)
     return (idx >= 0) & (idx < nk)
 
 
@@ -75,8 +75,8 @@ def gathered_queries(H, n_q, uniform=False, device=None):
 
 def gather(rows, src, keep, H):
     """rows (B, n, 576): the rows a sequence can reach; src, keep (B, 1, N_q, T): the row every slot reads and whether it counts ->
-    K (B * N_q, 1, T, 576), keep (B * N_q, 1, H, T).  A slot that does not count reads row 0."""
-    n_q, T = src.shape[2], src.shape[3]
+    K (B * N_q, 1, T, 576), keep (B * N_q, 1, H, T).  A slot that does not count reads row 0.  B is src's."""
+    B, n_q, T = src.shape[0], src.shape[2], src.shape[3]
     s = torch.where(keep, src, torch.zeros_like(src)).long().view(B, n_q * T)
     K = torch.gather(rows, 1, s.unsqueeze(-1).expand(-1, -1, rows.shape[-1])).view(B * n_q, 1, T, rows.shape[-1])
     return K, keep.reshape(B * n_q, 1, 1, T).expand(-1, -1, H, -1)
@@ -97,19 +97,20 @@ def restate(Q, K, keep, num_splits, dtype):
     return M.restate(Q, K, M.value_of(K), keep, [K.shape[2]] * K.shape[0], num_splits, dtype)
 
 
-def pool(KV, page=PAGE, seed=7, spare=5):
-    """the contiguous cache (B, 1, S_K, 576) scattered into a pool of B * max_blocks + spare pages under a seeded permutation ->
-    (pool (num_blocks, 1, page, 576), table (B, max_blocks) int32); rows of a last page past S_K and the spare pages hold decoys (the
-    rows of sequence 0, whose length is 0)"""
-    mb = -(-S_K // page)
+def pool(KV, page=PAGE, seed=7, spare=5, decoy=0):
+    """the contiguous cache (B, H_kv, S_k, 576) scattered into a pool of B * max_blocks + spare pages under a seeded permutation ->
+    (pool (num_blocks, H_kv, page, 576), table (B, max_blocks) int32); rows of a last page past S_k and the spare pages hold decoys (the
+    rows of sequence `decoy`, whose length is 0).  B, H_kv and S_k are KV's."""
+    B, h_kv, s_k = KV.shape[:3]
+    mb = -(-s_k // page)
     nb = B * mb + spare
     perm = torch.randperm(nb, generator=torch.Generator().manual_seed(seed)).to(KV.device)
     table = perm[:B * mb].view(B, mb)
-    padded = KV[:1, :, :1].expand(B, 1, mb * page, KV.shape[-1]).clone()
-    padded[:, :, :S_K] = KV
-    pl = torch.empty(nb, 1, page, KV.shape[-1], dtype=KV.dtype, device=KV.device)
-    pl[table.reshape(-1)] = padded.view(B, 1, mb, page, -1).permute(0, 2, 1, 3, 4).reshape(B * mb, 1, page, -1)
-    pl[perm[B * mb:]] = KV[0, :, :page].unsqueeze(0).expand(spare, -1, -1, -1)
+    padded = KV[decoy:decoy + 1, :, :1].expand(B, h_kv, mb * page, KV.shape[-1]).clone()
+    padded[:, :, :s_k] = KV
+    pl = torch.empty(nb, h_kv, page, KV.shape[-1], dtype=KV.dtype, device=KV.device)
+    pl[table.reshape(-1)] = padded.view(B, h_kv, mb, page, -1).permute(0, 2, 1, 3, 4).reshape(B * mb, h_kv, page, -1)
+    pl[perm[B * mb:]] = KV[decoy, :, :page].unsqueeze(0).expand(spare, -1, -1, -1)
     return pl, table.to(torch.int32).contiguous()
 
 

@@ -4,7 +4,9 @@ equal, BIT FOR BIT at an explicit and equal num_splits, the fixed call run per s
 views, so NaN and -0.0 count; no tolerance enters.  Also: a uniform batch against the fixed batched call, paged against the same
 fixed results at page sizes 1, 16, 48 and 64, rows no list names (and rows behind N_k(b)) and the workspace filled with NaN / inf,
 canary arenas round O, L and the workspace -- under malformed cu_seqlens_q as well --, rows no sequence owns left unwritten, and the
-fp64 truth of tests/test_decode_mla_sparse_gpu.py under check_forward's bars."""
+fp64 truth of tests/test_decode_mla_sparse_gpu.py under check_forward's bars.  Both sides of these identities run the same row
+expressions, on random data: tests/test_decode_mla_sparse_varlen_probe_gpu.py pins which sequence, list and keys each packed row reads,
+to one output ulp."""
 import functools
 import math
 

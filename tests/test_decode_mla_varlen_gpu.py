@@ -126,17 +126,19 @@ def test_forward_against_fp64_truth(rotation, dtype, variant):
 @pytest.mark.parametrize("variant,g,h_kv,causal,window,n", [("mla16", 40, 1, True, None, 3), ("mla16", 128, 1, False, (100, 50), 1),
                                                             ("mla16", 16, 2, True, (64, 0), 7), ("generic", 5, 1, True, None, 2)], ids=ids)
 def test_each_sequence_alone_equals_its_rows_in_the_batch(variant, g, h_kv, causal, window, n):
-    Q, KV = queries(g, h_kv, BF16), cache(h_kv, BF16)
-    kw = dict(causal=causal, window=window, num_splits=n, variant=variant)
-    O, L = call(Q, KV, **kw)
-    O2, L2 = call(Q, KV, **kw)
-    assert torch.equal(O, O2) and torch.equal(L, L2)                                    # the same call twice
-    start = 0
-    for b, (nq, nk) in enumerate(zip(N_Q, N_K)):
-        if nq:
-            Ob, Lb = call(Q[start:start + nq], KV[b:b + 1], [nq], [nk], nq, **kw)
-            assert torch.equal(Ob, O[start:start + nq]) and torch.equal(Lb, L[:, start:start + nq]), (b, nq, nk)
-        start += nq
+    """in bf16 and in f16 (the one-split case among them)"""
+    for dtype in (BF16, F16):
+        Q, KV = queries(g, h_kv, dtype), cache(h_kv, dtype)
+        kw = dict(causal=causal, window=window, num_splits=n, variant=variant)
+        O, L = call(Q, KV, **kw)
+        O2, L2 = call(Q, KV, **kw)
+        assert torch.equal(O, O2) and torch.equal(L, L2), dtype                         # the same call twice
+        start = 0
+        for b, (nq, nk) in enumerate(zip(N_Q, N_K)):
+            if nq:
+                Ob, Lb = call(Q[start:start + nq], KV[b:b + 1], [nq], [nk], nq, **kw)
+                assert torch.equal(Ob, O[start:start + nq]) and torch.equal(Lb, L[:, start:start + nq]), (dtype, b, nq, nk)
+            start += nq
 
 
 @gpu
@@ -144,21 +146,23 @@ def test_each_sequence_alone_equals_its_rows_in_the_batch(variant, g, h_kv, caus
 @pytest.mark.parametrize("variant", ["mla16", "generic"])
 @pytest.mark.parametrize("g,n_q", [(16, 1), (16, 2), (128, 1), (128, 2)])
 def test_uniform_batch_equals_the_fixed_call_bit_for_bit(g, n_q, variant, cache_dtype):
+    """in bf16 and in f16: at one split the f16 epilogue must round each product once, as the fixed kernel's does"""
     lens = [0, 1, 64, 65, 700, 1280, 3]
     nb = len(lens)
-    gen = torch.Generator().manual_seed(g + n_q)
-    Q = (torch.randn(nb, g, n_q, D, generator=gen) * 0.5).to(BF16).to(DEV)
-    KV = cache(1, BF16)[:nb, :, :1280]
-    kd = None
-    if cache_dtype is not None:
-        KV, kd = fa.quantize_kv_cache(KV, cache_dtype)
-    Qp = Q.transpose(1, 2).reshape(nb * n_q, g, D)
-    for causal, window, n in ((False, None, 1), (True, None, 4), (False, (100, 50), 3), (True, (64, 0), 16)):
-        kw = dict(causal=causal, window=window, scale=SCALE, num_splits=n, variant=variant, kv_descale=kd)
-        O, L = fa.flash_attention_mla_decode_forward(Q, KV, lens_of(lens), DEV, **kw)
-        Op, Lp = fa.flash_attention_mla_varlen_decode_forward(Qp, KV, cu_of([n_q] * nb), n_q, lens_of(lens), DEV, **kw)
-        assert torch.equal(Op.view(nb, n_q, g, D_V).transpose(1, 2), O), (causal, window, n)
-        assert torch.equal(Lp.view(g, nb, n_q).permute(1, 0, 2), L), (causal, window, n)
+    for dtype in (BF16, F16):
+        gen = torch.Generator().manual_seed(g + n_q)
+        Q = (torch.randn(nb, g, n_q, D, generator=gen) * 0.5).to(dtype).to(DEV)
+        KV = cache(1, dtype)[:nb, :, :1280]
+        kd = None
+        if cache_dtype is not None:
+            KV, kd = fa.quantize_kv_cache(KV, cache_dtype)
+        Qp = Q.transpose(1, 2).reshape(nb * n_q, g, D)
+        for causal, window, n in ((False, None, 1), (True, None, 4), (False, (100, 50), 3), (True, (64, 0), 16)):
+            kw = dict(causal=causal, window=window, scale=SCALE, num_splits=n, variant=variant, kv_descale=kd)
+            O, L = fa.flash_attention_mla_decode_forward(Q, KV, lens_of(lens), DEV, **kw)
+            Op, Lp = fa.flash_attention_mla_varlen_decode_forward(Qp, KV, cu_of([n_q] * nb), n_q, lens_of(lens), DEV, **kw)
+            assert torch.equal(Op.view(nb, n_q, g, D_V).transpose(1, 2), O), (dtype, causal, window, n)
+            assert torch.equal(Lp.view(g, nb, n_q).permute(1, 0, 2), L), (dtype, causal, window, n)
 
 
 def scatter(KV, page, seed, n_k, fill=float("nan"), share=True):

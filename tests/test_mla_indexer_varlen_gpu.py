@@ -3,13 +3,16 @@ topk_indices_varlen).  Exact-arithmetic data, as tests/test_mla_indexer_gpu.py m
 restatement (tests/mla_indexer_restatement.py) on that sequence alone bit for bit, and equal the fixed call on that sequence's slice bit
 for bit; the lists equal exactly.  Paged against contiguous bit for bit, a logits buffer pre-filled with a NaN pattern whose
 non-candidates keep their bits, the selection alone on the fixed selection test's seven kinds of logits, and the lists end to end
-through flash_attention_mla_sparse_varlen_decode_forward against the per-sequence fixed pipeline and the dense packed call."""
+through flash_attention_mla_sparse_varlen_decode_forward against the per-sequence fixed pipeline and the dense packed call.  The edge
+batch of tests/mla_sparse_varlen_probe.py (a leading empty sequence, two in a row, a trailing one, B = 11) through the selection and
+the fused call, for the owner search they share with the packed sparse kernels."""
 import functools
 
 import pytest
 import torch
 
 import flash_attention_dlrs_amd as fa
+import mla_sparse_varlen_probe as EV
 from flash_attention_dlrs_amd import _lib
 from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
 from mla_indexer_restatement import candidate_mask, logits_f64, paged, topk_lists
@@ -268,13 +271,8 @@ def test_end_to_end_equals_the_per_sequence_fixed_pipeline_bit_for_bit(dtype):
 def test_end_to_end_identity_lists_equal_the_dense_packed_call_bit_for_bit(dtype):
     """every sequence holds 640 keys and topk = 640: the causal indexer's list of a query is the identity up to its position, the
     split boundaries of slots and keys coincide, and the packed sparse call on the lists is flash_attention_mla_varlen_decode_forward
-    with causal=True, bit for bit at equal split counts -- and the fixed dense call on each sequence's slice.
-
-    f16 at ONE split is held against the fixed dense call alone.  The one-split epilogue of the dense packed kernel's f16
-    instantiations rounds a few products twice (fp32 product, then v_cvt_f16_f32) where the fixed dense, the fixed sparse and the packed
-    sparse instantiations round once (v_fma_mixlo_f16): 372 + 24 against 384 + 12 such instructions in the generated code of the four
-    units, the effect fa2_decode_mla16.hip describes at its split branch.  That is one ulp of an element in some 10^5 of the dense
-    PACKED call, whose own tests pin bits in bf16 only; with more than one split the last rounding is the combine's, shared by all."""
+    with causal=True, bit for bit at equal split counts, one split among them in both dtypes -- and the fixed dense call on each
+    sequence's slice."""
     H, N_k, scale = 64, 640, 576 ** -0.5
     Q, KV, q_idx, k_idx, w = latent(dtype, H, N_k, 61)
     idx = fa.flash_attention_mla_indexer_topk_varlen(q_idx, w, k_idx, cu_of(), MAX_Q, None, DEV, topk=N_k)
@@ -288,8 +286,7 @@ def test_end_to_end_identity_lists_equal_the_dense_packed_call_bit_for_bit(dtype
         Od, Ld = fa.flash_attention_mla_varlen_decode_forward(Q, KV, cu_of(), MAX_Q, None, DEV, causal=True, scale=scale, num_splits=n,
                                                               variant="mla16")
         assert not torch.isnan(O.float()).any()
-        if dtype == BF16 or n > 1:
-            assert torch.equal(bits16(O), bits16(Od)) and torch.equal(bits16(L), bits16(Ld)), (dtype, n)
+        assert torch.equal(bits16(O), bits16(Od)) and torch.equal(bits16(L), bits16(Ld)), (dtype, n)
         for b in range(B):
             if NQ[b] == 0:
                 continue
@@ -297,3 +294,85 @@ def test_end_to_end_identity_lists_equal_the_dense_packed_call_bit_for_bit(dtype
             Ob, Lb = fa.flash_attention_mla_decode_forward(Q[s:e].transpose(0, 1)[None], KV[b:b + 1], None, DEV, causal=True, scale=scale,
                                                            num_splits=n, variant="mla16")
             assert torch.equal(bits16(O[s:e]), bits16(Ob[0].transpose(0, 1))) and torch.equal(bits16(L[:, s:e]), bits16(Lb[0])), (dtype, n, b)
+
+
+# ---- the edge batch of tests/mla_sparse_varlen_probe.py through the other two users of fa2_varlen_owner's search: a leading empty
+# sequence, two empty sequences in a row, a trailing one, B = 11 (a search four steps deep), a sequence without a key
+E_NQ, E_LENS, E_CU, E_B, E_TOTAL, E_SK, E_MAXQ = EV.N_Q, EV.N_K, EV.CU, EV.B, EV.TOTAL, EV.S_K, EV.MAX_Q
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(H=40):
+    """exact_case's data on the edge batch: fp32 masters and the packed fp64 truth (total_q, S_k), the restatement on each sequence alone"""
+    g = torch.Generator().manual_seed(1000 * H + 11)
+    q = torch.randint(-2, 3, (E_TOTAL, H, D_I), generator=g).float().to(DEV)
+    k = torch.randint(-2, 3, (E_B, E_SK, D_I), generator=g).float().to(DEV)
+    w = (torch.randint(-16, 17, (E_TOTAL, H), generator=g).float() / 8).to(DEV)
+    ks = (2.0 ** torch.randint(-2, 3, (E_B, E_SK), generator=g).float()).to(DEV)
+    truth = torch.zeros(E_TOTAL, E_SK, dtype=F64, device=DEV)
+    for b in range(E_B):
+        if E_NQ[b]:
+            s, e = E_CU[b], E_CU[b + 1]
+            truth[s:e] = logits_f64(q[s:e].transpose(0, 1)[None], w[s:e].transpose(0, 1)[None], k[b:b + 1], ks[b:b + 1])[0]
+    assert truth.abs().max() < 2 ** 24 / 32 and torch.equal(truth * 32, (truth * 32).round())
+    return q, w, k, ks, truth
+
+
+@functools.lru_cache(maxsize=None)
+def edge_mask(causal):
+    """bool (total_q, S_k): the candidates of every packed row, by its own sequence's n_q(b) and N_k(b)"""
+    mask = torch.zeros(E_TOTAL, E_SK, dtype=torch.bool, device=DEV)
+    for b in range(E_B):
+        if E_NQ[b]:
+            mask[E_CU[b]:E_CU[b + 1]] = candidate_mask(E_LENS[b:b + 1], 1, E_NQ[b], E_SK, causal, DEV)[0]
+    return mask
+
+
+@functools.lru_cache(maxsize=None)
+def edge_lists(topk, causal):
+    """the restatement's lists of the truth, sequence by sequence -> int32 (total_q, topk) on the CPU"""
+    truth = edge_case()[4]
+    out = torch.empty(E_TOTAL, topk, dtype=torch.int32)
+    for b in range(E_B):
+        if E_NQ[b]:
+            out[E_CU[b]:E_CU[b + 1]] = topk_lists(truth[None, E_CU[b]:E_CU[b + 1]], E_LENS[b:b + 1], topk, causal)[0]
+    return out
+
+
+@pytest.mark.parametrize("topk", TOPKS)
+@pytest.mark.parametrize("causal", [True, False])
+def test_edge_batch_of_empty_sequences_finds_every_row_s_owner(causal, topk):
+    """the selection alone on given logits, then scores and selection under both score forms: lists equal to the restatement per
+    sequence exactly, logits equal to it bit for bit on the candidates, and in pre-filled buffers nothing else written"""
+    q, w, k, ks, truth = edge_case()
+    cu, lens = cu_of(E_CU), lens_of(E_LENS)
+    mask, want = edge_mask(causal), edge_lists(topk, causal)
+    assert not mask[0].any() and E_LENS[EV.OWNER[0]] == 0                                 # the row of the sequence without a key
+    assert (want[0] == -1).all() and (want[E_CU[8]:E_CU[9], 0] >= 0).all()
+    junk = torch.where(torch.arange(E_SK, device=DEV) % 2 == 0, float("nan"), float("inf")).expand(E_TOTAL, E_SK)
+    given = torch.where(mask, truth.float(), junk)
+    idx, whole, sl = arena(E_TOTAL * topk, torch.int32, -77)
+    idx = idx.view(E_TOTAL, topk)
+    _lib.fa2_topk_indices_varlen(given, idx, cu, E_MAXQ, lens, causal=causal)
+    torch.cuda.synchronize()
+    assert canaries_intact(whole, sl, -77)
+    assert torch.equal(idx.cpu(), want), (causal, topk, (idx.cpu() != want).nonzero()[:5].tolist())
+    assert torch.equal(fa.topk_indices_varlen(given, cu, E_MAXQ, lens, topk, causal=causal).cpu(), want)
+    for variant in ("idx16", "generic"):
+        what = (variant, causal, topk)
+        indices, logits = fa.flash_attention_mla_indexer_topk_varlen(q.to(BF16), w, k.to(BF16), cu, E_MAXQ, lens, DEV, topk=topk,
+                                                                     causal=causal, k_scale=ks, variant=variant, return_logits=True)
+        assert indices.shape == (E_TOTAL, topk) and logits.shape == (E_TOTAL, E_SK) and logits.dtype == F32
+        zero = torch.zeros((), dtype=F64, device=DEV)
+        assert torch.equal(torch.where(mask, logits.double(), zero), torch.where(mask, truth, zero)), what
+        assert torch.equal(indices.cpu(), want), (what, (indices.cpu() != want).nonzero()[:5].tolist())
+        # pre-filled buffers in canary arenas: non-candidates keep their bits
+        lg, lg_all, lg_sl = arena(E_TOTAL * E_SK, torch.int32, NAN_PATTERN)
+        ix, ix_all, ix_sl = arena(E_TOTAL * topk, torch.int32, -77)
+        lg, ix = lg.view(E_TOTAL, E_SK).view(F32), ix.view(E_TOTAL, topk)
+        _lib.fa2_mla_indexer_topk_varlen(q.to(BF16), w, k.to(BF16), ks, lg, ix, cu, E_MAXQ, lens, convert_triton_dtype(BF16),
+                                         convert_triton_dtype(BF16), causal=causal, variant=_lib.INDEXER_VARIANTS[variant])
+        torch.cuda.synchronize()
+        assert canaries_intact(lg_all, lg_sl, NAN_PATTERN) and canaries_intact(ix_all, ix_sl, -77), what
+        assert (lg.view(torch.int32)[~mask] == NAN_PATTERN).all(), what
+        assert torch.equal(lg[mask].view(torch.int32), logits[mask].view(torch.int32)) and torch.equal(ix.cpu(), want), what
