@@ -20,7 +20,10 @@ for the KV head; --sorted puts each list in ascending position, as fa2_topk_indi
 Records:
   kind=kernels        one per shape and cache dtype: the sides' avg / min / max / stddev in microseconds, the ratios of AUTO to each
                       other side, and whether AUTO's min-max range overlaps the gather route's and the VALU form's;
-  kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS on SWEEP_CASES, one traced child per shape."""
+  kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS on SWEEP_CASES, one traced child per shape;
+  kind=kv_format      --kv-format fp8_ds: the sparse AUTO launch over the tile-scaled fp8 cache (656-byte rows, kv_format="fp8_ds")
+                      beside the same launch over the bf16 cache and over the e4m3 one-descale cache of the same rows, the three sides
+                      ALTERNATING call by call in one child, the same lists and num_splits; the record carries kv_format."""
 import argparse
 import csv
 import glob
@@ -197,6 +200,50 @@ def run_pass(name, args):
                           dense_topk_splits=c.dense1_splits(), **c.shape)))
 
 
+DS_SIDES = ("fp8_ds", "bf16", "e4m3")
+
+
+def run_format_pass(name, args):
+    """The traced child of --kv-format fp8_ds: the three caches of the same rows, one call of each in turn."""
+    import torch
+    import flash_attention_dlrs_amd as fa
+    c = Case(name, torch.device("cuda:0"), "bf16", args.sorted)
+    s, n, idx = c.shape, c.sparse_splits(), c.idx.unsqueeze(1)
+    ws = c._ws(s["B"] * s["H"] * s["N_q"], n)
+    ds = [fa.quantize_mla_cache_ds(t) for t in c.KV]
+    e4 = [fa.quantize_kv_cache(t, torch.float8_e4m3fn) for t in c.KV]
+    e4_enum = c._lib.FA2_DTYPE_F8E4M3
+
+    def run(side, i):
+        if side == "fp8_ds":
+            c._lib.fa2_fwd_kvcache_mla_sparse_ds(c.Q, ds[i], c.O, c.L, idx, c.lens, c.enum, scale=c.scale, num_splits=n, workspace=ws)
+        else:
+            kv, d, enum = (c.KV[i], None, c.enum) if side == "bf16" else (e4[i][0], e4[i][1], e4_enum)
+            c._lib.fa2_fwd_kvcache_mla_sparse(c.Q, kv, kv[..., :D_V], c.O, c.L, idx, c.lens, c.enum, enum, k_descale=d, v_descale=d,
+                                              scale=c.scale, num_splits=n, workspace=ws)
+    torch.cuda.synchronize()
+    c.mark.fill_(0.0)
+    rounds = side_iters("auto", s, args.iters) + 3
+    for r in range(rounds):
+        for side in DS_SIDES:
+            run(side, r % c.copies)
+            c.mark.fill_(1.0)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, rounds=rounds, kv_format="fp8_ds", lists="sorted" if args.sorted else "random", num_splits=n, **s)))
+
+
+def run_format(names, args, fh):
+    for name in names:
+        out = os.path.join(args.rocprof, name + "_fp8_ds")
+        info = traced_child(out, ["--format-case", name], args)
+        calls = call_times(out, info["rounds"] * len(DS_SIDES))
+        sides = {side: stats(calls[k::len(DS_SIDES)]) for k, side in enumerate(DS_SIDES)}
+        emit(fh, kind="kv_format", **{k: v for k, v in info.items() if k != "rounds"},
+             ds_over_bf16=round(sides["fp8_ds"]["avg_us"] / sides["bf16"]["avg_us"], 4),
+             ds_over_e4m3=round(sides["fp8_ds"]["avg_us"] / sides["e4m3"]["avg_us"], 4),
+             bf16_ranges_overlap=sides["fp8_ds"]["max_us"] >= sides["bf16"]["min_us"] and sides["bf16"]["max_us"] >= sides["fp8_ds"]["min_us"], **sides)
+
+
 def run_sweep_pass(name, args):
     """The traced child of the split sweep: AUTO's variant alone, one split count after the other."""
     import torch
@@ -279,6 +326,8 @@ def main():
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="bf16", help="the latent cache's storage: bf16, or e4m3 with its descale")
     ap.add_argument("--sorted", action="store_true", help="every list in ascending key position (records carry lists=sorted)")
+    ap.add_argument("--kv-format", choices=("fp8_ds",), help="time the tile-scaled fp8 cache beside the bf16 and e4m3 caches (kind=kv_format)")
+    ap.add_argument("--format-case", help=argparse.SUPPRESS)
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
@@ -287,9 +336,11 @@ def main():
         return run_pass(args.pass_case, args)
     if args.sweep_case:
         return run_sweep_pass(args.sweep_case, args)
+    if args.format_case:
+        return run_format_pass(args.format_case, args)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
-        run_rocprof(args.cases.split(","), args, fh)
+        (run_format if args.kv_format else run_rocprof)(args.cases.split(","), args, fh)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,10 @@ Sides of one child, each the pair of calls (score + selection kernels, then the 
               without padding.  On the uniform batch it is the fixed call itself, and so is `padded`.
 
 Records: kind=kernels, one per shape: the sides' avg / min / max / stddev in microseconds, each side's indexer and attention share,
-packed over the other two, and whether packed's min-max range touches theirs."""
+packed over the other two, and whether packed's min-max range touches theirs.
+--kv-format fp8_ds: kind=kv_format instead, appended to profiles/mla/bench_mla_sparse.jsonl with packed=true -- the packed ATTENTION call
+alone (the lists made once, by the packed indexer, before the timed calls) over the tile-scaled fp8 cache, the bf16 cache and the e4m3
+one-descale cache of the same rows, the three sides alternating call by call in one child."""
 import argparse
 import json
 import math
@@ -156,6 +159,50 @@ def run_pass(name, args):
                           groups=[[nb, n] for _, nb, n in c.groups], **c.shape)))
 
 
+DS_SIDES = ("fp8_ds", "bf16", "e4m3")
+
+
+def run_format_pass(name, args):
+    """The traced child of --kv-format fp8_ds: the three caches of the same rows, one packed attention call over each in turn."""
+    import torch
+    import flash_attention_dlrs_amd as fa
+    c = Case(name, torch.device("cuda:0"))
+    n, lib = c.packed_splits(), c._lib
+    ws = c._ws(c.total * H, n)
+    lib.fa2_mla_indexer_topk_varlen(c.qi, c.w, c.KI[0], None, c.lg, c.ix, c.cu, c.max_q, c.lens, c.enum, c.enum)
+    idx = c.ix.unsqueeze(1)
+    ds = [fa.quantize_mla_cache_ds(t) for t in c.KV]
+    e4 = [fa.quantize_kv_cache(t, torch.float8_e4m3fn) for t in c.KV]
+
+    def run(side, i):
+        if side == "fp8_ds":
+            lib.fa2_fwd_kvcache_mla_sparse_varlen_ds(c.Q, ds[i], c.O, c.L, idx, c.cu, c.max_q, c.lens, c.enum, scale=c.scale, num_splits=n,
+                                                     workspace=ws)
+        else:
+            kv, d, enum = (c.KV[i], None, c.enum) if side == "bf16" else (e4[i][0], e4[i][1], lib.FA2_DTYPE_F8E4M3)
+            lib.fa2_fwd_kvcache_mla_sparse_varlen(c.Q, kv, kv[..., :D_V], c.O, c.L, idx, c.cu, c.max_q, c.lens, c.enum, enum, k_descale=d,
+                                                  v_descale=d, scale=c.scale, num_splits=n, workspace=ws)
+    torch.cuda.synchronize()
+    c.mark.fill_(0.0)
+    for r in range(args.iters + 3):
+        for side in DS_SIDES:
+            run(side, r % c.copies)
+            c.mark.fill_(1.0)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, rounds=args.iters + 3, kv_format="fp8_ds", packed=True, num_splits=n, **c.shape)))
+
+
+def run_format(names, args, fh):
+    for name in names:
+        out = os.path.join(args.rocprof, name + "_fp8_ds")
+        info = traced_child(out, ["--format-case", name], args)
+        calls = call_times(out, info["rounds"] * len(DS_SIDES))
+        sides = {side: stats(calls[k::len(DS_SIDES)]) for k, side in enumerate(DS_SIDES)}
+        emit(fh, kind="kv_format", **{k: v for k, v in info.items() if k != "rounds"},
+             ds_over_bf16=round(sides["fp8_ds"]["avg_us"] / sides["bf16"]["avg_us"], 4),
+             ds_over_e4m3=round(sides["fp8_ds"]["avg_us"] / sides["e4m3"]["avg_us"], 4), **sides)
+
+
 def traced_child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
@@ -222,13 +269,18 @@ def main():
                     help="the traces of the rocprofv3 children go under DIR")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--kv-format", choices=("fp8_ds",), help="time the attention over the tile-scaled fp8 cache beside bf16 and e4m3")
+    ap.add_argument("--format-case", help=argparse.SUPPRESS)
+    ap.add_argument("--out")
     args = ap.parse_args()
     if args.pass_case:
         return run_pass(args.pass_case, args)
+    if args.format_case:
+        return run_format_pass(args.format_case, args)
+    args.out = args.out or (os.path.join(os.path.dirname(OUT), "bench_mla_sparse.jsonl") if args.kv_format else OUT)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
-        run_rocprof(args.cases.split(","), args, fh)
+        (run_format if args.kv_format else run_rocprof)(args.cases.split(","), args, fh)
 
 
 if __name__ == "__main__":

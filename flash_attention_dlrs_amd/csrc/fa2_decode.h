@@ -44,7 +44,17 @@ struct Fa2DecodeProblem {
     const int32_t *indices;
     int64_t is[4];
     int32_t topk;
+    // the tile-scaled fp8 latent cache (fa2_fwd_kvcache_mla_sparse_ds, _varlen_ds): kv_format == FA2_KV_FORMAT_FP8_DS.  K == V is a BYTE
+    // tensor of kFa2DsRowBytes-byte rows (below), ks == vs are in BYTES with ks[3] = 1, d = 576, d_v = 512, kv_dtype == dtype (the rotary
+    // columns' and the matrix arithmetic's), no descales.  0: every other call.
+    int32_t kv_format;
 };
+
+// A row of the tile-scaled fp8 latent cache (vLLM's fp8_ds_mla, FlashMLA's sparse fp8 layout): 512 e4m3fn bytes, 4 fp32 scales (scale t
+// belongs to columns 128 t .. 128 t + 127 of this row), 64 rotary columns in Q's 16-bit dtype T.  It stands for the 576-column row
+// D[c] = T(fp32(byte c) * scale[c / 128]) (one fp32 product, RTNE, rounded once more to T, RTNE), D[512 + r] the stored element.
+#define FA2_KV_FORMAT_FP8_DS 1
+constexpr int kFa2DsNope = 512, kFa2DsScaleOff = 512, kFa2DsRopeOff = 528, kFa2DsRowBytes = 656;
 
 // N_k(b) and the key range [k0, k1) of split s (device side of the rule above).
 __device__ __forceinline__ void fa2_decode_split(const int32_t *seqlens, int b, int S_k, int num_splits, int s, int &nk, int &k0,
@@ -78,6 +88,7 @@ __device__ __forceinline__ float fa2_decode_descale(const float *p, int64_t s0, 
 // at scale 1.0: exactly, both formats are subsets of f16 and of bf16.
 struct CacheE4M3 {};
 struct CacheE5M2 {};
+struct CacheDS {};  // the tile-scaled row above: converted AND scaled while it is staged (fa2_decode_mla16_sd.hip)
 typedef __attribute__((ext_vector_type(2))) __bf16 fa2_bf16x2;
 typedef __attribute__((ext_vector_type(2))) _Float16 fa2_f16x2;
 template <typename T, typename C> struct CacheCvt;
@@ -160,6 +171,13 @@ int fa2_launch_decode_sparse_generic(const Fa2DecodeProblem &p);
 bool fa2_decode_mla16_sv_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla16_sv(const Fa2DecodeProblem &p);
 int fa2_launch_decode_sparse_generic_v(const Fa2DecodeProblem &p);
+
+// The sparse calls over the tile-scaled fp8 cache (kv_format above): the list-addressed instantiations of the latent kernel with the row
+// dequantised while it is staged (fa2_decode_mla16_sd.hip, _sdv.hip: fixed, packed), and the VALU forms' loader of the layout.
+bool fa2_decode_mla16_sd_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_sd(const Fa2DecodeProblem &p);
+bool fa2_decode_mla16_sdv_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_sdv(const Fa2DecodeProblem &p);
 
 // One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
 // each tensor's dtype.  It is the kernel's argument as well.

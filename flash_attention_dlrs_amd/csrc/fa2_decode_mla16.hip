@@ -92,6 +92,15 @@
 // no sequence owns leaves at once, before any barrier, and writes nothing -- what the query-tiled packed form does with a tile
 // without rows.  With `start` the packed row and N_q = 1 every expression below is the list-addressed kernel's: the query tiling of
 // VQ (the rotation along x, position-major rows, [q0, q1)) is taken with VQ && !SP alone, the packed partial layout with VQ.
+//
+// Tile-scaled fp8 latent cache (fa2_fwd_kvcache_mla_sparse_ds, _varlen_ds).  C = CacheDS, SP only, instantiated in fa2_decode_mla16_sd.hip
+// and _sdv.hip (FA2_DECODE_DS) alone.  A row is 656 bytes (fa2_decode.h): 512 e4m3 bytes, 4 fp32 scales of its 128-column tiles, 64 rotary
+// columns in T.  Only staging differs, 41 loads of 16 bytes a row: 8 passes of latent bytes, a half-wave a row, lane (hv, ld) bytes 16 ld ..
+// + 15 of row 2 ps + hv with the scale of ITS tile ld >> 3 (a dword load of its own); two passes of rotary pieces as the 16-bit tail.
+// stage_write converts a byte pair exactly to fp32, multiplies each by the scale (fp32, RTNE), rounds once more to T and writes the fp8
+// map's chunks 2 ld, 2 ld + 1 -- the LDS image is the 16-bit kernel's over the dequantised row.  Nothing is folded into the softmax scale
+// or the output: O and L are the 16-bit instantiation's on the dequantised cache bit for bit.  A slot that is no key loads neither bytes
+// nor scale.
 #include "fa2_decode.h"
 #include "fa2_mfma.h"
 
@@ -100,6 +109,12 @@
 #endif
 #ifndef FA2_DECODE_SPARSE
 #define FA2_DECODE_SPARSE 0
+#endif
+#ifndef FA2_DECODE_DS
+#define FA2_DECODE_DS 0
+#endif
+#if FA2_DECODE_DS && !FA2_DECODE_SPARSE
+#error "the tile-scaled cache is read through key lists only"
 #endif
 
 namespace {
@@ -142,7 +157,8 @@ constexpr int kSmem = kMfOff + 256;
 constexpr int kStage = kCPR * kBC / 256;     // 18 16-byte loads per thread and tile
 constexpr int kLPR8 = kD / 16;               // fp8 cache: 36 16-byte loads per cache row, each two LDS chunks
 constexpr int kStage8 = kLPR8 * kBC / 256;   //            9 loads per thread and tile
-static_assert(kStage == 18 && kStage8 == 9 && kSmem <= 160 * 1024, "one workgroup per CU");
+constexpr int kStageDS = kFa2DsNope / 16 * kBC / 256 + 2;  // tile-scaled cache: 8 loads of 16 latent bytes + 2 of rotary columns
+static_assert(kStage == 18 && kStage8 == 9 && kStageDS == 10 && kSmem <= 160 * 1024, "one workgroup per CU");
 
 // Byte offset of 16-byte chunk `ch` (< 72) of row `row` in the tile: the d = 128 swizzle on rows of kRowB bytes.
 __device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ swz<128>(row)) << 4); }
@@ -154,7 +170,9 @@ template <bool V> struct Bool { static constexpr bool value = V; };  // a compil
 template <typename T, typename C, bool PAGED, bool VQ, bool SP>
 __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMlaArgs a) {
     using M = Mma<T>;
-    constexpr bool F8 = !__is_same(C, T);
+    constexpr bool DS = __is_same(C, CacheDS);  // the tile-scaled row: dequantised to T while it is staged, nothing folded
+    constexpr bool F8 = !__is_same(C, T) && !DS;
+    static_assert(!DS || SP, "the tile-scaled cache is read through key lists only");
     using frag = typename M::frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LDS_PTR(char) lds = (LDS_PTR(char))smem;
@@ -308,11 +326,35 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
         return offv;
     };
 
-    u32x4 sreg[F8 ? kStage8 : kStage];
+    u32x4 sreg[DS ? kStageDS : F8 ? kStage8 : kStage];
+    [[maybe_unused]] float dsc[DS ? 8 : 1];  // DS: the scale of this lane's column tile in the row of each latent pass
     auto stage_load = [&](int t) {
         if constexpr (SP) {  // tile t is the one (m_a, rw_a, e_a) describe
             const int64_t offv = sp_offv();
-            if constexpr (F8) {
+            if constexpr (DS) {
+                // latent bytes: pass ps is rows 2 ps, 2 ps + 1 of the wave's 16, a half-wave a row: lane (hv, ld) takes bytes 16 ld ..
+                // + 15, all of scale tile ld >> 3 in every pass, and that tile's scale of the row with them (a dword of its own: 8
+                // registers, no exchange).  The wave's offsets come to lanes 0..15 first, as in the 16-bit map: a pass's two rows are
+                // then lane reads at constant lanes and a select.  A slot that is no key loads neither bytes nor scale: zeros times 0.
+                const int64_t offw = sp_off(offv, 16 * wave + (lane & 15), Bool<false>{});
+                const unsigned mw = (unsigned)(m_a >> (16 * wave));
+                const int hv = lane >> 5, ld = lane & 31;
+#pragma unroll
+                for (int ps = 0; ps < 8; ++ps) {
+                    const int64_t o0 = sp_off(offw, 2 * ps, Bool<true>{}), o1 = sp_off(offw, 2 * ps + 1, Bool<true>{});
+                    const bool ok = (mw >> (2 * ps + hv)) & 1;
+                    const char *rp = kbase + (hv ? o1 : o0);
+                    sreg[ps] = ok ? *(const u32x4 *)(rp + ld * 16) : u32x4{0, 0, 0, 0};
+                    dsc[ps] = ok ? *(const float *)(rp + kFa2DsScaleOff + 4 * (ld >> 3)) : 0.0f;
+                }
+                // rotary columns: the 16-bit map's tail, 8 rows a pass, the 16-byte piece lane & 7 of the row's last 128 bytes
+#pragma unroll
+                for (int jb = 0; jb < 2; ++jb) {
+                    const bool ok = (m_a >> (sb_row + 8 * jb)) & 1;
+                    const int64_t off = sp_off(offv, sb_row + 8 * jb, Bool<false>{});
+                    sreg[8 + jb] = ok ? *(const u32x4 *)(kbase + off + kFa2DsRopeOff + (lane & 7) * 16) : u32x4{0, 0, 0, 0};
+                }
+            } else if constexpr (F8) {
 #pragma unroll
                 for (int ps = 0; ps < kStage8; ++ps) {
                     const int src = 16 * wave + f8_row(ps);
@@ -373,7 +415,36 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
         }
     };
     auto stage_write = [&]() {
-        if constexpr (F8) {  // word j of the load = elements 4j .. 4j + 3 = words 2j, 2j + 1 of the 16-bit row
+        if constexpr (DS) {
+            // bytes 2 HI, 2 HI + 1 of a word: two exact fp32 values, each times the row's tile scale (one fp32 product, RTNE), each
+            // rounded once more to T (RTNE).  The product is pinned in its fp32 register: a multiply fused into the conversion
+            // (v_fma_mix*) would round once, and the row must be what the 16-bit call reads from the dequantised cache, bit for bit
+            typedef __attribute__((ext_vector_type(2))) T Tx2;
+            auto pair = [](unsigned w, auto hi, float sc) {
+                const auto f = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, decltype(hi)::value);
+                float x = f[0] * sc, y = f[1] * sc;
+                asm("" : "+v"(x));
+                asm("" : "+v"(y));
+                const Tx2 t = {(T)x, (T)y};
+                return __builtin_bit_cast(unsigned, t);
+            };
+            const int hv = lane >> 5, ld = lane & 31;
+            const bool odd_first = (ld & 4) != 0;  // the fp8 map's bank rule: the eight lanes of a write group, eight distinct slots
+#pragma unroll
+            for (int ps = 0; ps < 8; ++ps) {
+                const u32x4 w = sreg[ps];
+                const float sc = dsc[ps];
+                const u32x4 c0 = {pair(w[0], Bool<false>{}, sc), pair(w[0], Bool<true>{}, sc), pair(w[1], Bool<false>{}, sc),
+                                  pair(w[1], Bool<true>{}, sc)};
+                const u32x4 c1 = {pair(w[2], Bool<false>{}, sc), pair(w[2], Bool<true>{}, sc), pair(w[3], Bool<false>{}, sc),
+                                  pair(w[3], Bool<true>{}, sc)};
+                const int row = 16 * wave + 2 * ps + hv;
+                *(LDS_PTR(u32x4))(lds + lds_off(row, 2 * ld + (odd_first ? 1 : 0))) = odd_first ? c1 : c0;
+                *(LDS_PTR(u32x4))(lds + lds_off(row, 2 * ld + (odd_first ? 0 : 1))) = odd_first ? c0 : c1;
+            }
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb) *(LDS_PTR(u32x4))(lds + lds_off(sb_row + 8 * jb, sb_ch)) = sreg[8 + jb];
+        } else if constexpr (F8) {  // word j of the load = elements 4j .. 4j + 3 = words 2j, 2j + 1 of the 16-bit row
             using X = CacheCvt<T, C>;
 #pragma unroll
             for (int ps = 0; ps < kStage8; ++ps) {
@@ -611,7 +682,7 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     }
 }
 
-constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0, kSP = FA2_DECODE_SPARSE != 0;
+constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0, kSP = FA2_DECODE_SPARSE != 0, kDS = FA2_DECODE_DS != 0;
 
 template <typename T, typename C, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
     // (the lists: one position a workgroup, over B * N_q positions or, packed, total_q rows)
@@ -642,9 +713,13 @@ template <typename T, typename C> int launch_p(const Fa2DecodeProblem &p, const 
 }
 
 template <typename T> int launch_c(const Fa2DecodeProblem &p, const DecodeMlaArgs &a) {
+#if FA2_DECODE_DS
+    return launch_p<T, CacheDS>(p, a);  // the only cache of these units
+#else
     if (p.kv_dtype == FA2_DTYPE_F8E4M3) return launch_p<T, CacheE4M3>(p, a);
     if (p.kv_dtype == FA2_DTYPE_F8E5M2) return launch_p<T, CacheE5M2>(p, a);
     return launch_p<T, T>(p, a);
+#endif
 }
 
 bool fp8_cache(const Fa2DecodeProblem &p) { return p.kv_dtype == FA2_DTYPE_F8E4M3 || p.kv_dtype == FA2_DTYPE_F8E5M2; }
@@ -653,6 +728,12 @@ bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
 // (packed queries: N_q holds max_seqlen_q, so the row bound below is the grid's)
 bool supports(const Fa2DecodeProblem &p) {
+    if ((p.kv_format == FA2_KV_FORMAT_FP8_DS) != kDS) return false;
+    if (kDS) {  // K is bytes and its strides are: a row is 41 loads of 16 bytes, every row start 16-byte aligned
+        if (p.kv_dtype != p.dtype) return false;
+        for (int k = 0; k < 3; ++k)
+            if (p.ks[k] & 15) return false;
+    }
     if (!fa2_decode_mla16_shape(p.d, p.d_v, p.dtype) || (p.kv_dtype != p.dtype && !fp8_cache(p)) || (p.cu_q != nullptr) != kVQ ||
         (p.indices != nullptr) != kSP)
         return false;
@@ -674,6 +755,12 @@ bool supports(const Fa2DecodeProblem &p) {
 }
 
 int launch(const Fa2DecodeProblem &p) {
+    if (kDS && !supports(p)) {
+        fa2_set_error("kvcache mla16 kernel over the fp8_ds cache: needs f16/bf16 Q, unit last strides, a 16-byte aligned cache base and row, "
+                      "head and batch / block strides that are multiples of 16 bytes (other layouts: the generic kernel), 16-byte aligned "
+                      "Q and O rows (and workspace), scale > 0");
+        return FA2_ERR_UNSUPPORTED;
+    }
     if (!supports(p)) {
         fa2_set_error("kvcache mla16 kernel: needs f16/bf16, d = 576 and d_v = 512, V aliasing K (the same pointer and strides), unit "
                       "d-stride, 16-byte aligned rows (and workspace), scale > 0%s%s",
@@ -684,7 +771,7 @@ int launch(const Fa2DecodeProblem &p) {
     DecodeMlaArgs a;
     a.Q = (const char *)p.Q; a.K = (const char *)p.K;
     a.O = (char *)p.O; a.L = (char *)p.L;
-    const int64_t cb = fp8_cache(p) ? 1 : 2;  // bytes per cache element
+    const int64_t cb = kDS || fp8_cache(p) ? 1 : 2;  // bytes per cache element (the tile-scaled cache: strides in bytes)
     for (int k = 0; k < 3; ++k) { a.qs[k] = p.qs[k] * 2; a.ks[k] = p.ks[k] * cb; a.os[k] = p.os[k] * 2; }
     a.ls[0] = p.ls[0]; a.ls[1] = p.ls[1];
     a.seqlens = p.seqlens;
@@ -706,7 +793,13 @@ int launch(const Fa2DecodeProblem &p) {
 
 }  // namespace
 
-#if FA2_DECODE_SPARSE && FA2_DECODE_VARLEN_Q
+#if FA2_DECODE_DS && FA2_DECODE_VARLEN_Q
+bool fa2_decode_mla16_sdv_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_sdv(const Fa2DecodeProblem &p) { return launch(p); }
+#elif FA2_DECODE_DS
+bool fa2_decode_mla16_sd_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_sd(const Fa2DecodeProblem &p) { return launch(p); }
+#elif FA2_DECODE_SPARSE && FA2_DECODE_VARLEN_Q
 bool fa2_decode_mla16_sv_supports(const Fa2DecodeProblem &p) { return supports(p); }
 int fa2_launch_decode_mla16_sv(const Fa2DecodeProblem &p) { return launch(p); }
 #elif FA2_DECODE_SPARSE

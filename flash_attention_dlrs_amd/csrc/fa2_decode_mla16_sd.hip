@@ -1,0 +1,5 @@
+// List-addressed instantiations of fa2_decode_mla16.hip over the tile-scaled fp8 latent cache (fa2_fwd_kvcache_mla_sparse_ds): SP with
+// the cache type CacheDS, alone in their translation unit -- every other unit keeps its code and its argument struct.
+#define FA2_DECODE_SPARSE 1
+#define FA2_DECODE_DS 1
+#include "fa2_decode_mla16.hip"

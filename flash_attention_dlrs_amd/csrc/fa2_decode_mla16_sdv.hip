@@ -1,0 +1,6 @@
+// List-addressed instantiations of fa2_decode_mla16.hip over the tile-scaled fp8 latent cache and packed queries
+// (fa2_fwd_kvcache_mla_sparse_varlen_ds): SP and VQ with the cache type CacheDS, alone in their translation unit.
+#define FA2_DECODE_SPARSE 1
+#define FA2_DECODE_VARLEN_Q 1
+#define FA2_DECODE_DS 1
+#include "fa2_decode_mla16.hip"

@@ -54,6 +54,33 @@ struct CacheF8E5M2 {
     }
 };
 
+// The tile-scaled fp8 latent cache (fa2_decode.h, kv_format FP8_DS) under Q's 16-bit type E: `i` is the BYTE offset of the row (the
+// strides of such a cache are in bytes), element x of it is E(fp32(byte x) * scale[x >> 7]) for x < 512 -- one fp32 product, rounded
+// once more to E, what the matrix form leaves in LDS -- and the stored 16-bit element 512 + x' after the scales.  Byte and unaligned
+// dword / 16-bit loads (memcpy): any alignment runs.
+template <class E> struct CacheFp8DS {
+    static __device__ __forceinline__ float load(const void *p, int64_t i, int x) {
+        const uint8_t *row = (const uint8_t *)p + i;
+        if (x < kFa2DsNope) {
+            float sc;
+            __builtin_memcpy(&sc, row + kFa2DsScaleOff + 4 * (x >> 7), 4);
+            float v = __builtin_amdgcn_cvt_f32_fp8((int)row[x], 0) * sc;
+            asm("" : "+v"(v));  // the fp32 product as it stands, then the rounding to E: never one fused operation
+            return E::round(v);
+        }
+        uint16_t h;
+        __builtin_memcpy(&h, row + kFa2DsRopeOff + 2 * (x - kFa2DsNope), 2);
+        return E::load(&h, 0);
+    }
+};
+// Element x of the cache row at offset `row`: the tile-scaled layout by row and column, every other cache type at row + x * stride.
+template <class C> constexpr bool kIsDS = false;
+template <class E> constexpr bool kIsDS<CacheFp8DS<E>> = true;
+template <class C> __device__ __forceinline__ auto cache_at(const void *p, int64_t row, int x, int64_t stride) {
+    if constexpr (kIsDS<C>) return C::load(p, row, x);
+    else return C::load(p, row + (int64_t)x * stride);
+}
+
 struct SparseGenericArgs {
     const void *Q, *K, *V;
     void *O, *L;
@@ -109,7 +136,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_sparse_generic_kernel(
     }
     __syncthreads();
 
-    constexpr bool F8 = !__is_same(C, E);
+    constexpr bool F8 = !__is_same(C, E) && !kIsDS<C>;  // (the tile-scaled cache has no descales: its scales are in the rows)
     A c = sizeof(A) == 8 ? (A)a.c_log2e : (A)(float)a.c_log2e;
     A vd = 1;
     if constexpr (F8) {
@@ -147,7 +174,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_sparse_generic_kernel(
                 vb = v_off + e * a.vs[0] + row * a.vs[2];
             }
             for (int x = 0; x < d; ++x) {
-                const A kx = C::load(a.K, kb + (int64_t)x * a.ks[3]);
+                const A kx = cache_at<C>(a.K, kb, x, a.ks[3]);
 #pragma unroll
                 for (int r = 0; r < kRowsPerWave; ++r) dot[r] += q_lds[(wave * kRowsPerWave + r) * d + x] * kx;
             }
@@ -181,7 +208,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_sparse_generic_kernel(
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
                 if (x < dv) {
-                    const A v = C::load(a.V, vr + (int64_t)x * a.vs[3]);
+                    const A v = cache_at<C>(a.V, vr, x, a.vs[3]);
 #pragma unroll
                     for (int r = 0; r < kRowsPerWave; ++r) o[r][cc] += pr[r] * v;
                 }
@@ -241,10 +268,14 @@ template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const Sp
     const dim3 grid((unsigned)gx, p.H_kv), block(kWaves * 64);
     const size_t smem = smem_bytes(sizeof(typename E::acc_t), p.d);
     const int dpl = (p.d_v + 63) / 64;
-    if (dpl <= 1) launch_k<E, C, 1>(grid, block, smem, p.stream, a);
-    else if (dpl <= 2) launch_k<E, C, 2>(grid, block, smem, p.stream, a);
-    else if (dpl <= 4) launch_k<E, C, 4>(grid, block, smem, p.stream, a);
-    else launch_k<E, C, 8>(grid, block, smem, p.stream, a);
+    if constexpr (kIsDS<C>) {  // (the format fixes d_v = 512)
+        launch_k<E, C, 8>(grid, block, smem, p.stream, a);
+    } else {
+        if (dpl <= 1) launch_k<E, C, 1>(grid, block, smem, p.stream, a);
+        else if (dpl <= 2) launch_k<E, C, 2>(grid, block, smem, p.stream, a);
+        else if (dpl <= 4) launch_k<E, C, 4>(grid, block, smem, p.stream, a);
+        else launch_k<E, C, 8>(grid, block, smem, p.stream, a);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mla sparse generic kernel launch failed: %s", hipGetErrorString(e));
@@ -274,6 +305,12 @@ int fa2_launch_decode_sparse_generic(const Fa2DecodeProblem &p) {
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     a.cu_q = p.cu_q; a.total_q = p.total_q;
+    if (p.kv_format == FA2_KV_FORMAT_FP8_DS) {  // the tile-scaled fp8 cache under 16-bit Q, O, L: strides in bytes
+        if (p.dtype == FA2_DTYPE_F16) return launch_e<ElemF16, CacheFp8DS<ElemF16>>(p, a);
+        if (p.dtype == FA2_DTYPE_BF16) return launch_e<ElemBF16, CacheFp8DS<ElemBF16>>(p, a);
+        fa2_set_error("kvcache mla sparse: the fp8_ds cache needs f16 / bf16 Q (dtype enum %d)", p.dtype);
+        return FA2_ERR_UNSUPPORTED;
+    }
     if (p.kv_dtype != p.dtype) {  // fp8 cache under 16-bit Q, O, L
         const bool e4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
         if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_F16)

@@ -906,6 +906,61 @@ def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seq
     return O, L
 
 
+KV_FORMATS = ("fp8_ds",)
+DS_ROW_BYTES, DS_NOPE, DS_TILE, DS_ROPE = 656, 512, 128, 64  # the fp8_ds row: 512 e4m3 bytes, 4 fp32 tile scales, 64 16-bit rotary columns
+
+
+def quantize_mla_cache_ds(kv):
+    """A latent cache (..., 576) in float16 / bfloat16 -> the tile-scaled fp8 cache (..., 656) uint8 of kv_format="fp8_ds" (vLLM's
+    fp8_ds_mla, FlashMLA's sparse fp8 layout).  Per row: bytes 0..511 the latent columns in e4m3fn, byte = e4m3(x / scale); bytes
+    512..527 four float32 scales, one per 128-column tile of THIS row, scale = max(amax(tile), 1e-4) / 448; bytes 528..655 the 64
+    rotary columns as they are.  Plain torch, any device; the stand-in for an engine's cache writer."""
+    if not isinstance(kv, torch.Tensor) or kv.dtype not in (torch.float16, torch.bfloat16) or kv.dim() < 1 or kv.shape[-1] != DS_NOPE + DS_ROPE:
+        raise ValueError(f"quantize_mla_cache_ds: kv must be a float16 / bfloat16 tensor (..., {DS_NOPE + DS_ROPE})")
+    x = kv[..., :DS_NOPE].to(torch.float32).unflatten(-1, (DS_NOPE // DS_TILE, DS_TILE))
+    scale = x.abs().amax(dim=-1).clamp(min=1e-4) / 448.0
+    b8 = (x / scale[..., None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).flatten(-2)
+    out = torch.empty(kv.shape[:-1] + (DS_ROW_BYTES,), dtype=torch.uint8, device=kv.device)
+    out[..., :DS_NOPE] = b8.view(torch.uint8)
+    out[..., DS_NOPE:DS_ROW_BYTES - 2 * DS_ROPE] = scale.contiguous().view(torch.uint8)
+    out[..., DS_ROW_BYTES - 2 * DS_ROPE:] = kv[..., DS_NOPE:].contiguous().view(torch.uint8)
+    return out
+
+
+def dequantize_mla_cache_ds(kv8, dtype):
+    """The rows an fp8_ds cache (..., 656) uint8 stands for, (..., 576) in dtype (float16 / bfloat16, the rotary columns' own):
+    column c < 512 is (float32(e4m3 byte c) * scale[c // 128]).to(dtype) -- one float32 product, then one rounding to dtype -- and
+    column 512 + r the stored element.  kv_format="fp8_ds" computes the 16-bit call's result on exactly these rows."""
+    if not isinstance(kv8, torch.Tensor) or kv8.dtype != torch.uint8 or kv8.dim() < 1 or kv8.shape[-1] != DS_ROW_BYTES:
+        raise ValueError(f"dequantize_mla_cache_ds: kv8 must be a uint8 tensor (..., {DS_ROW_BYTES})")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"dequantize_mla_cache_ds: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+    b = kv8[..., :DS_NOPE].contiguous().view(torch.float8_e4m3fn).to(torch.float32).unflatten(-1, (DS_NOPE // DS_TILE, DS_TILE))
+    s = kv8[..., DS_NOPE:DS_ROW_BYTES - 2 * DS_ROPE].contiguous().view(torch.float32)
+    rope = kv8[..., DS_ROW_BYTES - 2 * DS_ROPE:].contiguous().view(dtype)
+    return torch.cat(((b * s[..., None]).flatten(-2).to(dtype), rope), dim=-1)
+
+
+def _check_ds_cache(who, Q, KV_cache, kv_format, d_v, kv_descale):
+    """The rules kv_format="fp8_ds" adds; returns a stand-in of the cache in Q's dtype with 576 columns (no data, a broadcast scalar) on
+    which the remaining rules (heads, batch, block_table, cache_seqlens, num_splits) are the 16-bit call's."""
+    if kv_format not in KV_FORMATS:
+        raise ValueError(f"{who}: kv_format must be None or one of {KV_FORMATS}, got {kv_format!r}")
+    if KV_cache.dtype != torch.uint8 or KV_cache.shape[3] != DS_ROW_BYTES or KV_cache.stride(3) != 1:
+        raise ValueError(f"{who}: kv_format='fp8_ds' needs KV_cache in torch.uint8 with a last axis of {DS_ROW_BYTES} bytes and unit last "
+                         f"stride, got {KV_cache.dtype}, shape {tuple(KV_cache.shape)}, strides {tuple(KV_cache.stride())}")
+    if Q.dtype not in (torch.float16, torch.bfloat16) or Q.shape[-1] != DS_NOPE + DS_ROPE:
+        raise ValueError(f"{who}: kv_format='fp8_ds' needs Q in float16 / bfloat16 (the dtype of the row's rotary columns) with a last "
+                         f"axis of {DS_NOPE + DS_ROPE}, got {Q.dtype}, shape {tuple(Q.shape)}")
+    if isinstance(d_v, bool) or d_v != DS_NOPE:
+        raise ValueError(f"{who}: kv_format='fp8_ds' fixes d_v = {DS_NOPE}, got {d_v!r}")
+    if kv_descale is not None:
+        raise ValueError(f"{who}: kv_format='fp8_ds' takes no kv_descale: the scales are in the rows")
+    if any(s < 0 for s in KV_cache.stride()):
+        raise ValueError(f"{who}: KV_cache with negative strides is not supported")
+    return torch.empty((), dtype=Q.dtype, device=Q.device).expand(*KV_cache.shape[:3], DS_NOPE + DS_ROPE)
+
+
 def _sparse_indices(indices, B, H_kv, N_q):
     """The (B, H_kv, N_q, topk) view of an indices argument: 4-D as it is, (B, N_q, topk) expanded over the KV heads without a copy."""
     if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or indices.dim() not in (3, 4):
@@ -922,7 +977,7 @@ def _sparse_indices(indices, B, H_kv, N_q):
     return view
 
 
-def check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v=512, num_splits=0, kv_descale=None, block_table=None):
+def check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v=512, num_splits=0, kv_descale=None, block_table=None, kv_format=None):
     """ValueError for what flash_attention_mla_sparse_decode_forward cannot take: Q, the latent cache, d_v, cache_seqlens, block_table
     and num_splits by the rules of flash_attention_mla_decode_forward; indices int32 on Q's device, (B, H_kv, N_q, topk) or
     (B, N_q, topk) with B and N_q Q's and topk >= 1; kv_descale with a cache in Q's dtype, and an fp8 cache WITHOUT its kv_descale (a
@@ -932,6 +987,8 @@ def check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v=512, num_spli
                          f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError("mla sparse decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    if kv_format is not None:  # the tile-scaled byte cache: its own rules, then the 16-bit call's on a stand-in of its rows
+        KV_cache = _check_ds_cache("mla sparse decode", Q, KV_cache, kv_format, d_v, kv_descale)
     d = KV_cache.shape[3]
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
         raise ValueError(f"mla sparse decode: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
@@ -950,7 +1007,7 @@ def check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v=512, num_spli
 
 
 def flash_attention_mla_sparse_decode_forward(Q, KV_cache, indices, cache_seqlens, dev, *, d_v=512, scale=1.0, num_splits=0,
-                                              variant="auto", kv_descale=None, block_table=None, **mask):
+                                              variant="auto", kv_descale=None, block_table=None, kv_format=None, **mask):
     """Sparse multi-head latent attention over the shared latent cache (include/fa2_fwd.h fa2_fwd_kvcache_mla_sparse) -> (O, L): every
     (sequence, KV head, query position) attends over exactly the keys its list names (DeepSeek-V3.2's sparse attention: an indexer
     picks about 2,048 keys per query token, in decode and in a sparse prefill chunk alike).  No row is gathered: each listed row is
@@ -963,13 +1020,21 @@ def flash_attention_mla_sparse_decode_forward(Q, KV_cache, indices, cache_seqlen
     ValueError; the indexer respects causality).  O (B, H, N_q, d_v) contiguous, L (B, H, N_q) log2-domain, both in Q's dtype.
     num_splits = 0 lets the library choose (the splits run over the slots of the list); variant is one of _lib.KVCACHE_MLA_VARIANTS:
     "mla16" (f16 / bf16, d = 576, d_v = 512, unit d-stride and 16-byte aligned rows, any H / H_kv, any page size), "generic" (everything
-    else), "auto".  The append side is mla_kvcache_append, called first.  No autograd, no autotuner."""
+    else), "auto".  The append side is mla_kvcache_append, called first.  No autograd, no autotuner.
+
+    kv_format="fp8_ds" (fa2_fwd_kvcache_mla_sparse_ds): KV_cache is the tile-scaled fp8 cache an engine running DeepSeek-V3.2 holds
+    (vLLM's fp8_ds_mla, FlashMLA's sparse fp8 layout), a torch.uint8 tensor (B, H_kv, S_k, 656) or pool (num_blocks, H_kv, page_size, 656)
+    with unit last stride: per key 512 e4m3fn latent bytes, 4 float32 scales (one per 128-column tile of that row) and the 64 rotary
+    columns in Q's dtype.  Q is float16 / bfloat16 with d = 576, d_v is 512, kv_descale None.  The result is this call's on
+    dequantize_mla_cache_ds(KV_cache, Q.dtype) bit for bit at the same num_splits and variant; no row is dequantised in memory, rows
+    no list names are never read.  "mla16" needs 16-byte aligned rows (base, and the three outer strides in bytes); "auto" takes
+    "generic" otherwise.  quantize_mla_cache_ds makes such a cache."""
     for name in mask:
         if name in ("causal", "window"):
             raise ValueError(f"mla sparse decode: there is no {name} argument: the index list is the mask (the indexer respects "
                              f"causality; leave out what a position must not see)")
         raise TypeError(f"flash_attention_mla_sparse_decode_forward() got an unexpected keyword argument {name!r}")
-    check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v, num_splits, kv_descale, block_table)
+    check_mla_sparse_args(Q, KV_cache, indices, cache_seqlens, d_v, num_splits, kv_descale, block_table, kv_format)
     if variant not in _lib.KVCACHE_MLA_VARIANTS:
         raise ValueError(f"mla sparse decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
     _check_dev(dev, Q, KV_cache, KV_cache)
@@ -979,6 +1044,10 @@ def flash_attention_mla_sparse_decode_forward(Q, KV_cache, indices, cache_seqlen
     dtype = convert_triton_dtype(Q.dtype)
     n = num_splits or _lib.kvcache_mla_sparse_num_splits(B, H, H_kv, N_q, view.shape[3], d, d_v, dtype)
     O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d_v), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0)
+    if kv_format is not None:
+        _lib.fa2_fwd_kvcache_mla_sparse_ds(Q, KV_cache, O, L, view, cache_seqlens, dtype, block_table=block_table, scale=scale,
+                                           num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
     kd = _kvcache_descale("kv_descale", kv_descale, Q, B, H_kv)
     _lib.fa2_fwd_kvcache_mla_sparse(Q, KV_cache, KV_cache[..., :d_v], O, L, view, cache_seqlens, dtype, convert_triton_dtype(KV_cache.dtype),
                                     k_descale=kd, v_descale=kd, block_table=block_table, scale=scale, num_splits=n, workspace=ws,
@@ -1164,7 +1233,7 @@ def _sparse_varlen_indices(indices, total_q, H_kv):
 
 
 def check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v=512, num_splits=0, kv_descale=None,
-                                 block_table=None):
+                                 block_table=None, kv_format=None):
     """ValueError for what flash_attention_mla_sparse_varlen_decode_forward cannot take: the packed Q, cu_seqlens_q and max_seqlen_q by
     the rules of check_mla_varlen_args; the latent cache, d_v, cache_seqlens, block_table, num_splits and kv_descale by those of
     check_mla_sparse_args (an fp8 cache needs its kv_descale); indices int32 on Q's device, (total_q, H_kv, topk) or (total_q, topk)
@@ -1175,6 +1244,8 @@ def check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_
                          f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError(f"{who}: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    if kv_format is not None:  # as in check_mla_sparse_args
+        KV_cache = _check_ds_cache(who, Q, KV_cache, kv_format, d_v, kv_descale)
     d = KV_cache.shape[3]
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
         raise ValueError(f"{who}: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
@@ -1198,7 +1269,8 @@ def check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_
 
 
 def flash_attention_mla_sparse_varlen_decode_forward(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, d_v=512,
-                                                     scale=1.0, num_splits=0, variant="auto", kv_descale=None, block_table=None, **mask):
+                                                     scale=1.0, num_splits=0, variant="auto", kv_descale=None, block_table=None,
+                                                     kv_format=None, **mask):
     """Sparse multi-head latent attention of variable-length (packed) queries (include/fa2_fwd.h fa2_fwd_kvcache_mla_sparse_varlen)
     -> (O, L): flash_attention_mla_sparse_decode_forward for a ragged step -- a prefill chunk beside one-token decodes, draft tokens
     of a different count per sequence -- in one call.  Q (total_q, H, d), any strides; cu_seqlens_q int32 (B + 1,) on Q's device and
@@ -1210,13 +1282,16 @@ def flash_attention_mla_sparse_varlen_decode_forward(Q, KV_cache, indices, cu_se
     flash_attention_mla_sparse_decode_forward's; so are causal= and window= (both a ValueError: the list is the mask), num_splits and
     variant.  O (total_q, H, d_v) contiguous, L (H, total_q) log2-domain, both in Q's dtype; rows outside every sequence are not
     written.  Sequence b's rows equal flash_attention_mla_sparse_decode_forward's on that sequence alone, bit for bit at the same
-    explicit num_splits.  The append side is mla_kvcache_append_varlen, called first.  No autograd, no autotuner."""
+    explicit num_splits.  The append side is mla_kvcache_append_varlen, called first.  No autograd, no autotuner.
+    kv_format="fp8_ds" (fa2_fwd_kvcache_mla_sparse_varlen_ds): the tile-scaled fp8 byte cache, as in
+    flash_attention_mla_sparse_decode_forward."""
     for name in mask:
         if name in ("causal", "window"):
             raise ValueError(f"mla sparse varlen decode: there is no {name} argument: the index list is the mask (the indexer respects "
                              f"causality; leave out what a position must not see)")
         raise TypeError(f"flash_attention_mla_sparse_varlen_decode_forward() got an unexpected keyword argument {name!r}")
-    check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, num_splits, kv_descale, block_table)
+    check_mla_sparse_varlen_args(Q, KV_cache, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, num_splits, kv_descale, block_table,
+                                 kv_format)
     if variant not in _lib.KVCACHE_MLA_VARIANTS:
         raise ValueError(f"mla sparse varlen decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
     _check_dev(dev, Q, KV_cache, KV_cache)
@@ -1226,6 +1301,11 @@ def flash_attention_mla_sparse_varlen_decode_forward(Q, KV_cache, indices, cu_se
     dtype = convert_triton_dtype(Q.dtype)
     n = num_splits or _lib.kvcache_mla_sparse_varlen_num_splits(total_q, H, H_kv, view.shape[2], d, d_v, dtype)
     O, L, ws = _kvcache_outputs(Q, (total_q, H, d_v), (H, total_q), _lib.kvcache_varlen_workspace_bytes(total_q, H, d_v, n) if n > 1 else 0)
+    if kv_format is not None:
+        _lib.fa2_fwd_kvcache_mla_sparse_varlen_ds(Q, KV_cache, O, L, view, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
+                                                  block_table=block_table, scale=scale, num_splits=n, workspace=ws,
+                                                  variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
     kd = _kvcache_descale("kv_descale", kv_descale, Q, B, H_kv)
     _lib.fa2_fwd_kvcache_mla_sparse_varlen(Q, KV_cache, KV_cache[..., :d_v], O, L, view, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
                                            convert_triton_dtype(KV_cache.dtype), k_descale=kd, v_descale=kd, block_table=block_table,

@@ -871,6 +871,51 @@ int32_t fa2_kvcache_mla_sparse_varlen_num_splits(int32_t total_q, int32_t H, int
                                                  int32_t dtype_enum);
 
 /*
+ * Sparse MLA decode over the tile-scaled fp8 latent cache ("fp8_ds": vLLM's fp8_ds_mla, FlashMLA's sparse fp8 layout), fixed and
+ * packed: fa2_fwd_kvcache_mla_sparse and fa2_fwd_kvcache_mla_sparse_varlen with ONE byte tensor KV in K's, V's and the descales' place.
+ *
+ *   Row.      656 bytes per key: bytes 0 .. 511 the 512 latent columns in OCP e4m3fn; bytes 512 .. 527 four fp32 scales, scale t of
+ *             columns 128 t .. 128 t + 127 of THIS row; bytes 528 .. 655 the 64 rotary columns in Q's 16-bit dtype T, unquantised.
+ *             The row stands for the 576-column row D in T: D[c] = T(fp32(byte c) * scale[c / 128]) for c < 512 -- one fp32
+ *             product, round to nearest even, rounded once more to T, round to nearest even, subnormals kept -- and D[512 + r] the
+ *             stored element.  K = D, V = D[:512]: d = 576 and d_v = 512 are the format's.
+ *   Tensors.  KV (B, H_kv, S_k, 656) bytes or, with block_table, the pool (num_blocks, H_kv, page_size, 656), any page size; the three
+ *             outer strides kv_strides = {batch or block, KV head, row} are in BYTES, each >= 0, the last stride is 1.  block_table
+ *             null: the contiguous cache, page_size carries S_k.  Q, O, L, the lists, cache_seqlens and the workspace are the sparse
+ *             calls'; dtype_enum (Q, O, L, the rotary columns) is FA2_DTYPE_F16 or FA2_DTYPE_BF16.
+ *   Result.   The 16-bit sparse call's on the dequantised cache D, bit for bit at the same num_splits and variant: the scales are
+ *             applied while a row is staged, nothing is folded into the softmax scale or the output.  A slot that is no key is never
+ *             turned into an address: neither bytes nor scales of rows no list names, or behind cache_seqlens[b], are read.
+ *   Splits.   fa2_kvcache_mla_sparse_num_splits / _varlen_num_splits at d 576, d_v 512; the workspace as for those calls at d_v 512.
+ *   Variants. FA2_KVCACHE_VARIANT_MLA16 needs 16-byte aligned rows: KV's base and the three strides multiples of 16 bytes (and the
+ *             Q / O / workspace rules of fa2_fwd_kvcache_mla).  FA2_KVCACHE_VARIANT_GENERIC: any alignment.  AUTO: MLA16 where it
+ *             runs, else GENERIC.  A forced MLA16 on a problem it cannot run returns FA2_ERR_UNSUPPORTED.
+ *
+ * Errors: FA2_ERR_BAD_ARG for a null KV or kv_strides and a negative kv stride, FA2_ERR_UNSUPPORTED for a dtype_enum other than
+ * F16 / BF16, then the sparse calls'; all before any launch.
+ */
+int fa2_fwd_kvcache_mla_sparse_ds(const void *Q, const void *KV, void *O, void *L,
+                                  const int64_t q_strides[4], const int64_t kv_strides[3],
+                                  const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                                  const int32_t *indices, const int64_t index_strides[4], int32_t topk,
+                                  const int32_t *block_table, int64_t block_table_stride,
+                                  int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                                  int32_t dtype_enum, float scale, int32_t num_splits,
+                                  void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+int fa2_fwd_kvcache_mla_sparse_varlen_ds(const void *Q, const void *KV, void *O, void *L,
+                                         const int64_t q_strides[3], const int64_t kv_strides[3],
+                                         const int64_t o_strides[3], int64_t l_head_stride,
+                                         const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                         const int32_t *indices, const int64_t index_strides[3], int32_t topk,
+                                         const int32_t *block_table, int64_t block_table_stride,
+                                         int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q,
+                                         int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                                         int32_t dtype_enum, float scale, int32_t num_splits,
+                                         void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/*
  * The MLA indexer (DeepSeek-V3.2's lightning indexer): the stage in front of fa2_fwd_kvcache_mla_sparse.  It scores every cached
  * token against every query token and makes the key lists that call takes.  Three entry points: the scores alone, the selection
  * alone over any fp32 logits, and both on one stream.
