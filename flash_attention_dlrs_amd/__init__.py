@@ -19,7 +19,8 @@ from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_
                                        flash_attention_mla_indexer_topk, mla_indexer_logits, quantize_index_keys, topk_indices,
                                        check_mla_sparse_varlen_args, flash_attention_mla_sparse_varlen_decode_forward,
                                        check_mla_indexer_varlen_args, mla_indexer_logits_varlen, topk_indices_varlen,
-                                       flash_attention_mla_indexer_topk_varlen, quantize_mla_cache_ds, dequantize_mla_cache_ds)
+                                       flash_attention_mla_indexer_topk_varlen, quantize_mla_cache_ds, dequantize_mla_cache_ds,
+                                       check_mla_indexer_append_args, mla_indexer_append, mla_indexer_append_varlen)
 
 __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
            "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
@@ -32,4 +33,5 @@ __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarle
            "mla_indexer_logits", "topk_indices", "check_mla_indexer_args", "quantize_index_keys",
            "flash_attention_mla_sparse_varlen_decode_forward", "check_mla_sparse_varlen_args", "mla_indexer_logits_varlen",
            "topk_indices_varlen", "flash_attention_mla_indexer_topk_varlen", "check_mla_indexer_varlen_args",
-           "quantize_mla_cache_ds", "dequantize_mla_cache_ds"]
+           "quantize_mla_cache_ds", "dequantize_mla_cache_ds", "mla_indexer_append", "mla_indexer_append_varlen",
+           "check_mla_indexer_append_args"]

@@ -62,7 +62,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_mla_indexer_logits", "fa2_topk_indices", "fa2_mla_indexer_topk", "fa2_mla_indexer_workspace_bytes",
            "fa2_fwd_kvcache_mla_sparse_varlen", "fa2_kvcache_mla_sparse_varlen_num_splits", "fa2_mla_indexer_logits_varlen",
            "fa2_topk_indices_varlen", "fa2_mla_indexer_topk_varlen", "fa2_mla_indexer_varlen_workspace_bytes",
-           "fa2_fwd_kvcache_mla_sparse_ds", "fa2_fwd_kvcache_mla_sparse_varlen_ds")
+           "fa2_fwd_kvcache_mla_sparse_ds", "fa2_fwd_kvcache_mla_sparse_varlen_ds", "fa2_kvcache_mla_append_ds",
+           "fa2_kvcache_mla_append_varlen_ds", "fa2_mla_indexer_append", "fa2_mla_indexer_append_varlen")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -242,6 +243,19 @@ def lib():
         l.fa2_kvcache_mla_append_varlen.argtypes = [vp, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, vp, i64p, vp, vp,
                                                     ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [vp, vp, i64p] + \
             [ctypes.c_int32] * 14 + [vp]
+        # ... into the tile-scaled fp8 cache: no descale, no Q, no d / d_v / kv_dtype; KV's three strides in bytes
+        l.fa2_kvcache_mla_append_ds.restype = ctypes.c_int
+        l.fa2_kvcache_mla_append_ds.argtypes = [vp, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, vp, ctypes.c_int64,
+                                                ctypes.c_int64] + [ctypes.c_int32] * 11 + [vp]
+        l.fa2_kvcache_mla_append_varlen_ds.restype = ctypes.c_int
+        l.fa2_kvcache_mla_append_varlen_ds.argtypes = [vp, i64p, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, vp, vp, vp, vp, ctypes.c_int64,
+                                                       ctypes.c_int64] + [ctypes.c_int32] * 12 + [vp]
+        # the index-key append: cache + strides, scale + strides, table + stride, k_new + strides, (cu_seqlens_new,) lengths in / out,
+        # B N_new (total_new max_seqlen_new) S_k num_blocks page_size max_blocks d_I dtype k_dtype, stream
+        l.fa2_mla_indexer_append.restype = ctypes.c_int
+        l.fa2_mla_indexer_append.argtypes = [vp, i64p, vp, i64p, vp, ctypes.c_int64, vp, i64p, vp, vp] + [ctypes.c_int32] * 9 + [vp]
+        l.fa2_mla_indexer_append_varlen.restype = ctypes.c_int
+        l.fa2_mla_indexer_append_varlen.argtypes = [vp, i64p, vp, i64p, vp, ctypes.c_int64, vp, i64p, vp, vp, vp] + [ctypes.c_int32] * 10 + [vp]
         # ... fused with the latent-cache decode: Q KV O L + their strides, lengths in / out, table + stride, descale + strides,
         # c_new pe_new + strides, rotary tables + row strides, S_rot rotary_dim interleaved, q_rot, B H H_kv N_q N_new S_k num_blocks
         # page_size max_blocks d d_v dtype kv_dtype causal, scale, window, num_splits, workspace + its size, variant, stream
@@ -1053,6 +1067,50 @@ def fa2_kvcache_mla_append_varlen(KV, c_new, pe_new, cu_new, max_new, cache_seql
             cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)), _ptr(Q), _ptr(q_rot), q_st, H, int(bool(q_pos_per_row)),
             cu_new.numel() - 1, H_kv, total_new, int(max_new), S_k, nb, ps, mb, KV.shape[3], d_v, int(dtype_enum), int(kv_dtype_enum),
             _raw_stream(c_new.device.index))
+
+
+def fa2_kvcache_mla_append_ds(KV, c_new, pe_new, cache_seqlens, seqlens_out, dtype_enum, block_table=None, rotary_cos=None,
+                              rotary_sin=None, rotary_interleaved=False, cu_new=None, max_new=None):
+    """Launch the latent append into the tile-scaled fp8 cache (include/fa2_fwd.h fa2_kvcache_mla_append_ds; with cu_new, an int32
+    (B + 1,) tensor, and max_new the packed fa2_kvcache_mla_append_varlen_ds) on the current stream of c_new's device.  KV: uint8
+    (B, H_kv, S_k, 656) or the pool with block_table, unit last stride; c_new (..., 512), pe_new (..., 64) in f16 / bf16, any strides."""
+    if c_new.device.type != "cuda":
+        raise NotImplementedError("KV_cache, c_new, pe_new must be on the same CUDA device")
+    tb_ptr, tb_st, _, _, cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, S_k, nb, ps, mb = \
+        _mla_append_args(KV, block_table, None, rotary_cos, rotary_sin)
+    head = (KV.data_ptr(), _i64(KV.stride()[:3]), tb_ptr, tb_st, c_new.data_ptr(), pe_new.data_ptr(), _i64(c_new.stride()),
+            _i64(pe_new.stride()))
+    rot = (cos_ptr, sin_ptr, cos_st, sin_st, S_rot, rd, int(bool(rotary_interleaved)))
+    tail = (S_k, nb, ps, mb, int(dtype_enum), _raw_stream(c_new.device.index))
+    if cu_new is None:
+        B, H_kv, N_new, _ = c_new.shape
+        _launch(lib().fa2_kvcache_mla_append_ds, c_new, *head, cache_seqlens.data_ptr(), seqlens_out.data_ptr(), *rot, B, H_kv, N_new, *tail)
+    else:
+        total_new, H_kv, _ = c_new.shape
+        _launch(lib().fa2_kvcache_mla_append_varlen_ds, c_new, *head, cu_new.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(),
+                *rot, cu_new.numel() - 1, H_kv, total_new, int(max_new), *tail)
+
+
+def fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, seqlens_out, dtype_enum, k_dtype_enum, block_table=None, cu_new=None,
+                           max_new=None):
+    """Launch the index-key append (include/fa2_fwd.h fa2_mla_indexer_append; with cu_new and max_new the packed
+    fa2_mla_indexer_append_varlen) on the current stream of k_new's device: k_new (B, N_new, d_I) or packed (total_new, d_I) goes into
+    k_idx (B, S_k, d_I) or the pool (num_blocks, page_size, d_I), quantised with one scale per row into k_scale where k_idx is fp8."""
+    if k_new.device.type != "cuda":
+        raise NotImplementedError("k_idx, k_new must be on the same CUDA device")
+    if block_table is None:
+        tb_ptr, tb_st, S_k, nb, ps, mb = None, 0, k_idx.shape[1], 0, 0, 0
+    else:
+        tb_ptr, tb_st, S_k, nb, ps, mb = block_table.data_ptr(), block_table.stride(0), 0, k_idx.shape[0], k_idx.shape[1], block_table.shape[1]
+    head = (k_idx.data_ptr(), _i64(k_idx.stride()), _ptr(k_scale), None if k_scale is None else _i64(k_scale.stride()), tb_ptr, tb_st,
+            k_new.data_ptr(), _i64(k_new.stride()))
+    tail = (S_k, nb, ps, mb, k_idx.shape[2], int(dtype_enum), int(k_dtype_enum), _raw_stream(k_new.device.index))
+    if cu_new is None:
+        _launch(lib().fa2_mla_indexer_append, k_new, *head, cache_seqlens.data_ptr(), seqlens_out.data_ptr(), k_new.shape[0],
+                k_new.shape[1], *tail)
+    else:
+        _launch(lib().fa2_mla_indexer_append_varlen, k_new, *head, cu_new.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(),
+                cu_new.numel() - 1, k_new.shape[0], int(max_new), *tail)
 
 
 def fa2_fwd_kvcache_mla_append(Q, KV, O, L, c_new, pe_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,

@@ -221,3 +221,39 @@ struct Fa2AppendProblem {
     int32_t d_v;
 };
 int fa2_launch_decode_append(const Fa2AppendProblem &p);
+
+// One QUANTISING append (fa2_decode_append_q.hip), arguments already checked: rows whose bytes depend on a maximum over a group of
+// their columns, so a group of lanes owns a row and reduces across lanes.  It is the kernel's argument as well.  Three modes:
+//   FA2_APPENDQ_DS    fa2_kvcache_mla_append_ds, _varlen_ds: `cache` is the tile-scaled byte cache above, cs = {batch or block, KV head,
+//                     row} in BYTES, d = 512; src / sns are c_new, src2 / sns2 pe_new (64 columns, rotated from column 0 on with the tables)
+//   FA2_APPENDQ_IDX8  fa2_mla_indexer_append, _varlen over an fp8 k_idx (cache_dtype): one power-of-two scale per row of d columns goes
+//                     to `scale` at [b or block] * scs[0] + row * scs[1]; cs in elements, cs[1] = 0 (one shared head, H_kv = 1), cds
+//                     the cache's column stride; no src2, no tables
+//   FA2_APPENDQ_COPY  ... over a k_idx in src's dtype: the row is copied bit for bit, `scale` null
+// Sequences, lengths, the clamps, the drop past the capacity, paging and the packed spans are Fa2AppendProblem's.
+#define FA2_APPENDQ_DS 0
+#define FA2_APPENDQ_IDX8 1
+#define FA2_APPENDQ_COPY 2
+struct Fa2AppendQProblem {
+    int32_t mode;
+    void *cache;
+    int64_t cs[3], cds;
+    float *scale;
+    int64_t scs[2];
+    const int32_t *table;
+    int64_t table_stride;
+    int32_t page_size, num_blocks, capacity;
+    const void *src, *src2;  // (B, H_kv, N_new, ...) in `dtype`, strides in elements: {batch, head, token, column}, batch 0 when packed
+    int64_t sns[4], sns2[4];
+    const int32_t *seqlens;
+    int32_t *seqlens_out;
+    const void *cos, *sin;
+    int64_t cos_stride, sin_stride;
+    int32_t S_rot, rotary_dim, interleaved;
+    int32_t B, H_kv, N_new, d;
+    int32_t dtype, cache_dtype;
+    const int32_t *cu_new;  // packed: non-null, with total_new and max_new (N_new is then not read)
+    int32_t total_new, max_new;
+    hipStream_t stream;
+};
+int fa2_launch_decode_append_q(const Fa2AppendQProblem &p);

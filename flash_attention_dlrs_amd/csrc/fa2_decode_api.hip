@@ -663,6 +663,37 @@ int check_append(const AppendCall &c, Fa2AppendProblem &p) {
     return FA2_OK;
 }
 
+// fa2_kvcache_mla_append_ds, _varlen_ds: the latent append's checks on a call of the format's d / d_v with the cache in the inputs'
+// dtype (no descale, no Q), then the format's own; `c` comes with mla set.  On FA2_OK `q` is the problem to launch.
+int check_append_ds(AppendCall &c, const int64_t kv_strides[3], Fa2AppendQProblem &q) {
+    const int64_t ks[4] = {kv_strides ? kv_strides[0] : 0, kv_strides ? kv_strides[1] : 0, kv_strides ? kv_strides[2] : 0, 1};
+    c.k_strides = kv_strides ? ks : nullptr;
+    c.d = kFa2DsNope + 64; c.d_v = kFa2DsNope; c.kv_dtype_enum = c.dtype_enum;
+    Fa2AppendProblem p;
+    const int rc = check_append(c, p);
+    if (rc != FA2_OK) return rc;
+    if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16) {
+        fa2_set_error("kvcache mla append ds: dtype_enum %d (c_new, pe_new, the rotary columns) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16",
+                      c.dtype_enum);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    q = Fa2AppendQProblem{};
+    q.mode = FA2_APPENDQ_DS;
+    q.cache = p.K; q.cds = 1;
+    for (int k = 0; k < 3; ++k) q.cs[k] = p.ks[k];  // bytes
+    q.table = p.table; q.table_stride = p.table_stride; q.page_size = p.page_size; q.num_blocks = p.num_blocks; q.capacity = p.capacity;
+    q.src = p.k_new; q.src2 = p.pe_new;
+    for (int k = 0; k < 4; ++k) { q.sns[k] = p.kns[k]; q.sns2[k] = p.pns[k]; }
+    q.seqlens = p.seqlens; q.seqlens_out = p.seqlens_out;
+    q.cos = p.cos; q.sin = p.sin; q.cos_stride = p.cos_stride; q.sin_stride = p.sin_stride;
+    q.S_rot = p.S_rot; q.rotary_dim = p.rotary_dim; q.interleaved = p.interleaved;
+    q.B = p.B; q.H_kv = p.H_kv; q.N_new = p.N_new; q.d = kFa2DsNope;
+    q.dtype = p.dtype; q.cache_dtype = FA2_DTYPE_F8E4M3;
+    q.cu_new = p.cu_new; q.total_new = p.total_new; q.max_new = p.max_new;
+    q.stream = p.stream;
+    return FA2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1115,6 +1146,41 @@ int fa2_kvcache_mla_append_varlen(void *KV, const int64_t kv_strides[4], const i
     Fa2AppendProblem p;
     const int rc = check_append(c, p);
     return rc != FA2_OK ? rc : fa2_launch_decode_append(p);
+}
+
+int fa2_kvcache_mla_append_ds(void *KV, const int64_t kv_strides[3], const int32_t *block_table, int64_t block_table_stride,
+                              const void *c_new, const void *pe_new, const int64_t c_new_strides[4], const int64_t pe_new_strides[4],
+                              const int32_t *cache_seqlens, int32_t *seqlens_out, const void *rotary_cos, const void *rotary_sin,
+                              int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim,
+                              int32_t rotary_interleaved, int32_t B, int32_t H_kv, int32_t N_new, int32_t S_k, int32_t num_blocks,
+                              int32_t page_size, int32_t max_blocks, int32_t dtype_enum, void *hip_stream) {
+    AppendCall c = {KV, nullptr, nullptr, nullptr, block_table, block_table_stride, c_new, pe_new, c_new_strides, pe_new_strides,
+                    cache_seqlens, seqlens_out, nullptr, nullptr, nullptr, nullptr, rotary_cos, rotary_sin, rotary_cos_stride,
+                    rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, nullptr, nullptr, nullptr, 0, 0, 0, B, H_kv, N_new, S_k,
+                    num_blocks, page_size, max_blocks, 0, dtype_enum, 0, hip_stream};
+    c.mla = true;
+    Fa2AppendQProblem q;
+    const int rc = check_append_ds(c, kv_strides, q);
+    return rc != FA2_OK ? rc : fa2_launch_decode_append_q(q);
+}
+
+int fa2_kvcache_mla_append_varlen_ds(void *KV, const int64_t kv_strides[3], const int32_t *block_table, int64_t block_table_stride,
+                                     const void *c_new, const void *pe_new, const int64_t c_new_strides[3],
+                                     const int64_t pe_new_strides[3], const int32_t *cu_seqlens_new, const int32_t *cache_seqlens,
+                                     int32_t *seqlens_out, const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                                     int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, int32_t B,
+                                     int32_t H_kv, int32_t total_new, int32_t max_seqlen_new, int32_t S_k, int32_t num_blocks,
+                                     int32_t page_size, int32_t max_blocks, int32_t dtype_enum, void *hip_stream) {
+    int64_t cns[4], pns[4];
+    AppendCall c = {KV, nullptr, nullptr, nullptr, block_table, block_table_stride, c_new, pe_new, packed4(c_new_strides, cns),
+                    packed4(pe_new_strides, pns), cache_seqlens, seqlens_out, nullptr, nullptr, nullptr, nullptr, rotary_cos, rotary_sin,
+                    rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, nullptr, nullptr, nullptr, 0, 0, 0, B,
+                    H_kv, 0, S_k, num_blocks, page_size, max_blocks, 0, dtype_enum, 0, hip_stream};
+    c.packed = true; c.cu_seqlens_new = cu_seqlens_new; c.total_new = total_new; c.max_seqlen_new = max_seqlen_new;
+    c.mla = true;
+    Fa2AppendQProblem q;
+    const int rc = check_append_ds(c, kv_strides, q);
+    return rc != FA2_OK ? rc : fa2_launch_decode_append_q(q);
 }
 
 int fa2_fwd_kvcache_mla_append(const void *Q, void *KV, void *O, void *L, const int64_t q_strides[4], const int64_t kv_strides[4],

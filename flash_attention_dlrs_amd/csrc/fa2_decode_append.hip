@@ -11,7 +11,7 @@
 //
 // Arithmetic (pinned: flash_attention_wrappers.apply_rotary restates it in torch and the tests compare bits).  Inputs are widened to
 // fp32 (f64 stays f64); o1 = x1 c - x2 s and o2 = x2 c + x1 s with each product and the sum or difference rounded separately -- the
-// helpers below sit under `#pragma clang fp contract(off)`, because hipcc contracts a * b - c * d into an FMA by default and the
+// helpers (fa2_append_arith.h) sit under `#pragma clang fp contract(off)`, because hipcc contracts a * b - c * d into an FMA by default and the
 // __fmul_rn / __fsub_rn spellings are plain operators in its headers, which contract just the same; one rounding to nearest even to
 // the cache dtype.  For an fp8 cache the fp32 value (not rounded to 16 bits in between) is divided by the descale with the correctly
 // rounded division, clamped to +-finfo.max and converted by v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 (OCP formats on gfx950, nearest even).
@@ -24,31 +24,11 @@
 //
 // Every result leaves through ordinary vector stores.
 #include "fa2_decode.h"
-#include "fa2_elem.h"
+#include "fa2_append_arith.h"
 
 namespace {
 
-// ---- the pinned arithmetic -------------------------------------------------------------------------------------------------------
-#pragma clang fp contract(off)
-// One output of a rotary pair: `x` is the column being written, `y` its partner; `first` is the x1 side (o1 = x1 c - x2 s), else
-// the x2 side (o2 = x2 c + x1 s).
-template <class T> __device__ __forceinline__ T rot_pair(T x, T y, T c, T s, bool first) {
-    const T xc = x * c;
-    const T ys = y * s;
-    return first ? xc - ys : xc + ys;
-}
-#pragma clang fp contract(fast)
-
-template <int KV> __device__ __forceinline__ float fp8_scaled(float x, float ds) {
-    constexpr float top = KV == FA2_DTYPE_F8E4M3 ? 448.0f : 57344.0f;
-    return fminf(fmaxf(__fdiv_rn(x, ds), -top), top);
-}
-// two fp32 -> two fp8 bytes in the low (hi = false) or high half of `old`
-template <int KV, bool HI> __device__ __forceinline__ int fp8_pack2(float a, float b, int old) {
-    if constexpr (KV == FA2_DTYPE_F8E4M3) return __builtin_amdgcn_cvt_pk_fp8_f32(a, b, old, HI);
-    else return __builtin_amdgcn_cvt_pk_bf8_f32(a, b, old, HI);
-}
-
+// (the pinned arithmetic -- rot_pair, fp8_scaled, fp8_pack2 -- widen8 and the element types: fa2_append_arith.h)
 struct Row {          // one row of d columns to process, uniform over the lanes of a row
     const char *src;  // element 0 of the input row
     char *dst;        // element 0 of the output row
@@ -98,15 +78,6 @@ template <class E, int OUT, bool LAT> __device__ __forceinline__ void unit_elem(
 
 // ---- vector path: 8 columns per unit, f16 / bf16 input, unit d-strides, aligned rows, rotary_dim % 16 == 0 -----------------------
 // (LAT: off % 8 == 0 as well, so a unit lies in one source, and the rotary range, which starts at off, lies in src2)
-template <class E> __device__ __forceinline__ void widen8(const uint4 &u, float (&f)[8]) {
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = E::widen((uint16_t)(w[k] & 0xffffu));
-        f[2 * k + 1] = E::widen((uint16_t)(w[k] >> 16));
-    }
-}
-
 template <class E, int OUT, bool LAT> __device__ __forceinline__ void unit_vec(const Row &r, int c, int rd, int interleaved) {
     const int col = c * 8;
     const int rcol = LAT ? col - r.off : col;                 // the column inside the rotary range
@@ -160,20 +131,6 @@ template <class E, int OUT, bool LAT> __device__ __forceinline__ void unit_vec(c
         *(uint2 *)(r.dst + (int64_t)col) = make_uint2((uint32_t)lo, (uint32_t)hi);
     }
 }
-
-// The element types of this kernel: fa2_elem.h's load / store plus the raw 16-bit conversions of the vector path.
-struct AppF64 : ElemF64 { using bits_t = uint64_t; };
-struct AppF32 : ElemF32 { using bits_t = uint32_t; };
-struct AppF16 : ElemF16 {
-    using bits_t = uint16_t;
-    static __device__ __forceinline__ float widen(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
-    static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
-};
-struct AppBF16 : ElemBF16 {
-    using bits_t = uint16_t;
-    static __device__ __forceinline__ float widen(uint16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
-    static __device__ __forceinline__ uint16_t narrow(float x) { return ElemBF16::bits(x); }
-};
 
 template <class E, int OUT, bool VEC, bool LAT> __device__ __forceinline__ void do_row(const Row &r, int units, int rd, int interleaved) {
     for (int c = threadIdx.x; c < units; c += blockDim.x) {

@@ -1,8 +1,10 @@
 // fa2_indexer_api.hip -- host side of the MLA indexer (include/fa2_fwd.h): fa2_mla_indexer_logits, fa2_topk_indices, fa2_mla_indexer_topk
 // and fa2_mla_indexer_workspace_bytes, and their packed (_varlen) forms.  One call struct and one check order of its own, beside the attention calls' DecodeCall
 // (fa2_decode_api.hip): every check runs before any launch, then the score kernel of the form the variant names -- AUTO: the matrix
-// form where it runs, else the VALU form -- and the selection, on the call's stream.
+// form where it runs, else the VALU form -- and the selection, on the call's stream.  fa2_mla_indexer_append and _varlen, the write side of
+// the index-key cache, are here too: their checks, then the quantising append kernel (fa2_decode_append_q.hip).
 #include "fa2_indexer.h"
+#include "fa2_decode.h"
 
 namespace {
 
@@ -218,9 +220,134 @@ int run_indexer(const IndexerCall &c) {
     return c.packed ? fa2_launch_topk_indices_v(p) : fa2_launch_topk_indices(p);
 }
 
+// The arguments of fa2_mla_indexer_append; the packed call brings k_new_strides as {0, token, column} and N_new = 0.
+struct IndexAppendCall {
+    void *k_idx;
+    const int64_t *k_strides;
+    float *k_scale;
+    const int64_t *k_scale_strides;
+    const int32_t *block_table;
+    int64_t block_table_stride;
+    const void *k_new;
+    const int64_t *k_new_strides;
+    const int32_t *cache_seqlens;
+    int32_t *seqlens_out;
+    int32_t B, N_new, S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum;
+    void *hip_stream;
+    const int32_t *cu_seqlens_new = nullptr;  // packed: non-null
+    int32_t total_new = 0, max_seqlen_new = 0;
+    bool packed = false;
+};
+
+// Every check of the index-key append, before any launch; then the launch.
+int run_index_append(const IndexAppendCall &c) {
+    const char *who = "mla indexer append";
+    const void *ptrs[6] = {c.k_idx, c.k_strides, c.k_new, c.k_new_strides, c.cache_seqlens, c.seqlens_out};
+    const char *names[6] = {"k_idx", "k_strides", "k_new", "k_new_strides", "cache_seqlens", "seqlens_out"};
+    for (int t = 0; t < 6; ++t)
+        if (!ptrs[t]) return bad("mla indexer append: null %s", names[t]);
+    if (c.seqlens_out == c.cache_seqlens) return bad("mla indexer append: %s must not be cache_seqlens (the call does not modify its lengths)", "seqlens_out");
+    for (int k = 0; k < 3; ++k)
+        if (c.k_strides[k] < 0 || c.k_new_strides[k] < 0) return bad("mla indexer append: negative strides are not supported (%s)", "k_strides, k_new_strides");
+    if (c.B < 1 || c.B > 65535) {
+        fa2_set_error("%s: B must be in [1, 65535] (got %d)", who, c.B);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.packed) {
+        if (!c.cu_seqlens_new) return bad("mla indexer append varlen: null %s", "cu_seqlens_new");
+        if (c.total_new < 1 || c.total_new > (1 << 28) || c.max_seqlen_new < 1 || c.max_seqlen_new > (1 << 28)) {
+            fa2_set_error("%s varlen: total_new and max_seqlen_new must be in [1, 2^28] (got %d, %d)", who, c.total_new, c.max_seqlen_new);
+            return FA2_ERR_BAD_ARG;
+        }
+    } else if (c.N_new < 1 || c.N_new > (1 << 28)) {
+        fa2_set_error("%s: N_new must be in [1, 2^28] (got %d)", who, c.N_new);
+        return FA2_ERR_BAD_ARG;
+    }
+    int64_t cap = c.S_k;
+    if (c.block_table) {
+        if (c.num_blocks < 1 || c.page_size < 1 || c.max_blocks < 1) {
+            fa2_set_error("%s: num_blocks, page_size and max_blocks must be >= 1 (got num_blocks=%d, page_size=%d, max_blocks=%d)", who,
+                          c.num_blocks, c.page_size, c.max_blocks);
+            return FA2_ERR_BAD_ARG;
+        }
+        cap = (int64_t)c.max_blocks * c.page_size;
+        if (c.block_table_stride < 0) return bad("mla indexer append: negative %s", "block_table_stride");
+    }
+    if (cap < 1 || cap > (1 << 28)) {
+        fa2_set_error(c.block_table ? "%s: the capacity max_blocks * page_size must be in [1, 2^28] (got %lld)" : "%s: S_k must be in [1, 2^28] (got %lld)",
+                      who, (long long)cap);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16 && c.dtype_enum != FA2_DTYPE_F32) {
+        fa2_set_error("%s: dtype_enum %d (k_new) must be FA2_DTYPE_F16, FA2_DTYPE_BF16 or FA2_DTYPE_F32", who, c.dtype_enum);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    const bool quant = c.k_dtype_enum != c.dtype_enum;
+    if (quant) {
+        if (!is_fp8(c.k_dtype_enum)) {
+            fa2_set_error("%s: k_dtype_enum %d must be dtype_enum or FA2_DTYPE_F8E4M3 / FA2_DTYPE_F8E5M2", who, c.k_dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (c.dtype_enum == FA2_DTYPE_F32) {
+            fa2_set_error("%s: an fp8 k_idx (k_dtype_enum %d) goes with f16 / bf16 k_new, not f32", who, c.k_dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+        if (!c.k_scale || !c.k_scale_strides) return bad("mla indexer append: null %s with an fp8 cache", !c.k_scale ? "k_scale" : "k_scale_strides");
+        if (c.k_scale_strides[0] < 0 || c.k_scale_strides[1] < 0) return bad("mla indexer append: negative strides are not supported (%s)", "k_scale_strides");
+    } else if (c.k_scale) {
+        fa2_set_error("%s: k_scale goes with an fp8 cache (k_dtype_enum %d == dtype_enum)", who, c.k_dtype_enum);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.d_I < 1 || c.d_I > 576) {
+        fa2_set_error("%s: d_I=%d must be in [1, 576]", who, c.d_I);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    Fa2AppendQProblem q{};
+    q.mode = quant ? FA2_APPENDQ_IDX8 : FA2_APPENDQ_COPY;
+    q.cache = c.k_idx;
+    q.cs[0] = c.k_strides[0]; q.cs[1] = 0; q.cs[2] = c.k_strides[1]; q.cds = c.k_strides[2];
+    q.scale = quant ? c.k_scale : nullptr;
+    for (int k = 0; k < 2; ++k) q.scs[k] = quant ? c.k_scale_strides[k] : 0;
+    q.table = c.block_table;
+    q.table_stride = c.block_table ? c.block_table_stride : 0;
+    q.page_size = c.block_table ? c.page_size : 0; q.num_blocks = c.block_table ? c.num_blocks : 0;
+    q.capacity = (int32_t)cap;
+    q.src = c.k_new;
+    q.sns[0] = c.k_new_strides[0]; q.sns[1] = 0; q.sns[2] = c.k_new_strides[1]; q.sns[3] = c.k_new_strides[2];
+    q.seqlens = c.cache_seqlens; q.seqlens_out = c.seqlens_out;
+    q.B = c.B; q.H_kv = 1; q.N_new = c.N_new; q.d = c.d_I;
+    q.dtype = c.dtype_enum; q.cache_dtype = c.k_dtype_enum;
+    q.cu_new = c.packed ? c.cu_seqlens_new : nullptr;
+    q.total_new = c.packed ? c.total_new : 0; q.max_new = c.packed ? c.max_seqlen_new : 0;
+    q.stream = (hipStream_t)c.hip_stream;
+    return fa2_launch_decode_append_q(q);
+}
+
 }  // namespace
 
 extern "C" {
+
+int fa2_mla_indexer_append(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                           const int32_t *block_table, int64_t block_table_stride, const void *k_new, const int64_t k_new_strides[3],
+                           const int32_t *cache_seqlens, int32_t *seqlens_out, int32_t B, int32_t N_new, int32_t S_k, int32_t num_blocks,
+                           int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                           void *hip_stream) {
+    return run_index_append({k_idx, k_strides, k_scale, k_scale_strides, block_table, block_table_stride, k_new, k_new_strides,
+                             cache_seqlens, seqlens_out, B, N_new, S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum,
+                             hip_stream});
+}
+
+int fa2_mla_indexer_append_varlen(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                                  const int32_t *block_table, int64_t block_table_stride, const void *k_new,
+                                  const int64_t k_new_strides[2], const int32_t *cu_seqlens_new, const int32_t *cache_seqlens,
+                                  int32_t *seqlens_out, int32_t B, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum,
+                                  int32_t k_dtype_enum, void *hip_stream) {
+    int64_t ns[3];
+    return run_index_append({k_idx, k_strides, k_scale, k_scale_strides, block_table, block_table_stride, k_new,
+                             PackedStrides::rows3(k_new_strides, ns), cache_seqlens, seqlens_out, B, 0, S_k, num_blocks, page_size,
+                             max_blocks, d_I, dtype_enum, k_dtype_enum, hip_stream, cu_seqlens_new, total_new, max_seqlen_new, true});
+}
 
 int fa2_mla_indexer_logits(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
                            const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],

@@ -693,8 +693,31 @@ def check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v=512, kv_descale=N
         _check_rotary_tables(rotary_cos, rotary_sin, d - d_v, f"d - d_v = {d - d_v}", c_new, "kv_new")
 
 
+def _mla_append_ds(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin, rotary_interleaved, kv_format,
+                   cu_seqlens_new=None, max_seqlen_new=None):
+    """mla_kvcache_append / _varlen with kv_format: _check_ds_cache's rules with kv_new in Q's place, then the 16-bit append's on a
+    stand-in of the cache's rows, then the launch."""
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
+        raise ValueError("mla: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    c_new, pe_new = _mla_sources(kv_new, DS_NOPE)
+    row = torch.empty((), dtype=c_new.dtype, device=c_new.device).expand(c_new.shape[-1] + pe_new.shape[-1])  # kv_new's dtype and width
+    stand_in = _check_ds_cache("mla append", row, KV_cache, kv_format, d_v, kv_descale, q_name="kv_new")
+    if KV_cache.device != c_new.device:
+        raise ValueError(f"mla: KV_cache must be on kv_new's device ({c_new.device}), got {KV_cache.device}")
+    check_mla_append_args(stand_in, (c_new, pe_new), cache_seqlens, DS_NOPE, None, block_table, rotary_cos, rotary_sin,
+                          cu_seqlens_new=cu_seqlens_new, max_seqlen_new=max_seqlen_new)
+    if cu_seqlens_new is not None and block_table is None and KV_cache.shape[0] != cu_seqlens_new.numel() - 1:
+        raise ValueError(f"mla: a contiguous KV_cache must have cu_seqlens_new's B = {cu_seqlens_new.numel() - 1} sequences, got "
+                         f"{tuple(KV_cache.shape)} (a pool needs its block_table)")
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_kvcache_mla_append_ds(KV_cache, c_new, pe_new, cache_seqlens, new_seqlens, convert_triton_dtype(c_new.dtype),
+                                   block_table=block_table, rotary_cos=rotary_cos, rotary_sin=rotary_sin,
+                                   rotary_interleaved=rotary_interleaved, cu_new=cu_seqlens_new, max_new=max_seqlen_new)
+    return new_seqlens
+
+
 def mla_kvcache_append(KV_cache, kv_new, cache_seqlens, *, d_v=512, kv_descale=None, block_table=None, rotary_cos=None, rotary_sin=None,
-                       rotary_interleaved=False):
+                       rotary_interleaved=False, kv_format=None):
     """The cache update of an MLA decode step alone (include/fa2_fwd.h fa2_kvcache_mla_append) -> new_seqlens, int32 (B,): what an
     engine passes as the next step's cache_seqlens.  KV_cache is flash_attention_mla_decode_forward's latent cache, contiguous or a
     pool with block_table, in kv_new's dtype or fp8 with its one kv_descale.  kv_new: one tensor (B, H_kv, N_new, d), or the pair
@@ -703,9 +726,18 @@ def mla_kvcache_append(KV_cache, kv_new, cache_seqlens, *, d_v=512, kv_descale=N
     + t, written IN PLACE: columns [0, d_v) from c_new, [d_v, d) from pe_new with its first rotary_dim columns rotated at that
     position by rotary_cos / rotary_sin (apply_rotary on pe_new is the arithmetic; rotary_dim <= d - d_v), the whole row quantised
     with kv_descale where the cache is fp8.  Tokens past the capacity are dropped and new_seqlens = min(cache_seqlens + N_new,
-    capacity); cache_seqlens is not modified.  Everything else is kvcache_append's."""
+    capacity); cache_seqlens is not modified.  Everything else is kvcache_append's.
+
+    kv_format="fp8_ds" (fa2_kvcache_mla_append_ds): KV_cache is the tile-scaled fp8 cache of
+    flash_attention_mla_sparse_decode_forward, torch.uint8 (B, H_kv, S_k, 656) or the pool (num_blocks, H_kv, page_size, 656) of any
+    page size with unit last stride; kv_new is float16 / bfloat16 (576 columns, or the pair 512 + 64), d_v is 512, kv_descale None.
+    The 656 bytes a token gets are quantize_mla_cache_ds(r) bit for bit (the CPU's correctly rounded division), r the row this call
+    stores in a cache of kv_new's dtype, for every row whose latent columns are finite; one launch, lengths included."""
     if kv_new is None:
         raise ValueError("mla: mla_kvcache_append needs kv_new")
+    if kv_format is not None:
+        return _mla_append_ds(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                              kv_format)
     check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin)
     c_new, pe_new = _mla_sources(kv_new, d_v)
     new_seqlens = torch.empty_like(cache_seqlens)
@@ -717,13 +749,17 @@ def mla_kvcache_append(KV_cache, kv_new, cache_seqlens, *, d_v=512, kv_descale=N
 
 
 def mla_kvcache_append_varlen(KV_cache, kv_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, *, d_v=512, kv_descale=None,
-                              block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+                              block_table=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, kv_format=None):
     """mla_kvcache_append for a ragged batch in one launch (include/fa2_fwd.h fa2_kvcache_mla_append_varlen) -> new_seqlens, int32
     (B,).  kv_new packed: one tensor (total_new, H_kv, d) or the pair (total_new, H_kv, d_v), (total_new, H_kv, d - d_v), any strides;
     cu_seqlens_new and max_seqlen_new as in kvcache_append_varlen: sequence b brings the min(cu[b + 1] - cu[b], max_seqlen_new) rows
-    from cu[b] on, none is legal, rows outside every sequence are not read, and new_seqlens is written for every sequence."""
+    from cu[b] on, none is legal, rows outside every sequence are not read, and new_seqlens is written for every sequence.
+    kv_format="fp8_ds" as in mla_kvcache_append (fa2_kvcache_mla_append_varlen_ds)."""
     if kv_new is None:
         raise ValueError("mla: mla_kvcache_append_varlen needs kv_new")
+    if kv_format is not None:
+        return _mla_append_ds(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                              kv_format, cu_seqlens_new, max_seqlen_new)
     check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin,
                           cu_seqlens_new=cu_seqlens_new, max_seqlen_new=max_seqlen_new)
     c_new, pe_new = _mla_sources(kv_new, d_v)
@@ -914,7 +950,8 @@ def quantize_mla_cache_ds(kv):
     """A latent cache (..., 576) in float16 / bfloat16 -> the tile-scaled fp8 cache (..., 656) uint8 of kv_format="fp8_ds" (vLLM's
     fp8_ds_mla, FlashMLA's sparse fp8 layout).  Per row: bytes 0..511 the latent columns in e4m3fn, byte = e4m3(x / scale); bytes
     512..527 four float32 scales, one per 128-column tile of THIS row, scale = max(amax(tile), 1e-4) / 448; bytes 528..655 the 64
-    rotary columns as they are.  Plain torch, any device; the stand-in for an engine's cache writer."""
+    rotary columns as they are.  Plain torch, any device: the statement mla_kvcache_append(kv_format="fp8_ds"), the cache writer, is held
+    to bit for bit (on the CPU, whose division is correctly rounded)."""
     if not isinstance(kv, torch.Tensor) or kv.dtype not in (torch.float16, torch.bfloat16) or kv.dim() < 1 or kv.shape[-1] != DS_NOPE + DS_ROPE:
         raise ValueError(f"quantize_mla_cache_ds: kv must be a float16 / bfloat16 tensor (..., {DS_NOPE + DS_ROPE})")
     x = kv[..., :DS_NOPE].to(torch.float32).unflatten(-1, (DS_NOPE // DS_TILE, DS_TILE))
@@ -941,8 +978,8 @@ def dequantize_mla_cache_ds(kv8, dtype):
     return torch.cat(((b * s[..., None]).flatten(-2).to(dtype), rope), dim=-1)
 
 
-def _check_ds_cache(who, Q, KV_cache, kv_format, d_v, kv_descale):
-    """The rules kv_format="fp8_ds" adds; returns a stand-in of the cache in Q's dtype with 576 columns (no data, a broadcast scalar) on
+def _check_ds_cache(who, Q, KV_cache, kv_format, d_v, kv_descale, q_name="Q"):
+    """The rules kv_format="fp8_ds" adds (q_name: what the messages call the 16-bit tensor beside the cache); returns a stand-in of the cache in Q's dtype with 576 columns (no data, a broadcast scalar) on
     which the remaining rules (heads, batch, block_table, cache_seqlens, num_splits) are the 16-bit call's."""
     if kv_format not in KV_FORMATS:
         raise ValueError(f"{who}: kv_format must be None or one of {KV_FORMATS}, got {kv_format!r}")
@@ -950,7 +987,7 @@ def _check_ds_cache(who, Q, KV_cache, kv_format, d_v, kv_descale):
         raise ValueError(f"{who}: kv_format='fp8_ds' needs KV_cache in torch.uint8 with a last axis of {DS_ROW_BYTES} bytes and unit last "
                          f"stride, got {KV_cache.dtype}, shape {tuple(KV_cache.shape)}, strides {tuple(KV_cache.stride())}")
     if Q.dtype not in (torch.float16, torch.bfloat16) or Q.shape[-1] != DS_NOPE + DS_ROPE:
-        raise ValueError(f"{who}: kv_format='fp8_ds' needs Q in float16 / bfloat16 (the dtype of the row's rotary columns) with a last "
+        raise ValueError(f"{who}: kv_format='fp8_ds' needs {q_name} in float16 / bfloat16 (the dtype of the row's rotary columns) with a last "
                          f"axis of {DS_NOPE + DS_ROPE}, got {Q.dtype}, shape {tuple(Q.shape)}")
     if isinstance(d_v, bool) or d_v != DS_NOPE:
         raise ValueError(f"{who}: kv_format='fp8_ds' fixes d_v = {DS_NOPE}, got {d_v!r}")
@@ -1073,6 +1110,82 @@ def quantize_index_keys(k, dtype):
     scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e - (m == 0.5).to(e.dtype)), torch.ones_like(amax))
     k8 = (k.to(torch.float32) / scale[..., None]).clamp(-top, top).to(dtype)
     return k8, scale
+
+
+def check_mla_indexer_append_args(k_idx, k_new, cache_seqlens, k_scale=None, block_table=None, cu_seqlens_new=None, max_seqlen_new=None):
+    """ValueError, naming the argument, for what mla_indexer_append and (with cu_seqlens_new and max_seqlen_new: k_new packed)
+    mla_indexer_append_varlen cannot take.  Pure: takes CPU tensors."""
+    who = "mla indexer append"
+    packed = cu_seqlens_new is not None or max_seqlen_new is not None
+    if not isinstance(k_idx, torch.Tensor) or k_idx.dim() != 3 or k_idx.shape[1] < 1 or not 1 <= k_idx.shape[2] <= 576:
+        raise ValueError(f"{who}: k_idx must be a tensor (B, S_k, d_I) or a pool (num_blocks, page_size, d_I) with d_I in [1, 576]")
+    if not isinstance(k_new, torch.Tensor) or k_new.dim() != (2 if packed else 3) or k_new.shape[-1] != k_idx.shape[2] \
+            or min(k_new.shape) < 1 or k_new.shape[-2] > 1 << 28:
+        raise ValueError(f"{who}: k_new must be {'packed (total_new, d_I)' if packed else '(B, N_new, d_I)'} with at least one token and "
+                         f"k_idx's d_I = {k_idx.shape[2]}, got {tuple(k_new.shape) if isinstance(k_new, torch.Tensor) else type(k_new).__name__}")
+    if k_new.dtype not in INDEXER_Q_DTYPES:
+        raise ValueError(f"{who}: k_new must be float16, bfloat16 or float32, got {k_new.dtype}")
+    fp8 = k_idx.dtype in FP8_CACHE_DTYPES
+    if fp8 and k_new.dtype == torch.float32:
+        raise ValueError(f"{who}: an fp8 k_idx ({k_idx.dtype}) goes with float16 / bfloat16 k_new, not float32")
+    if not fp8 and k_idx.dtype != k_new.dtype:
+        raise ValueError(f"{who}: k_idx must have k_new's dtype ({k_new.dtype}) or an fp8 dtype, got {k_idx.dtype}")
+    if fp8 and k_scale is None:
+        raise ValueError(f"{who}: an fp8 k_idx ({k_idx.dtype}) needs its k_scale (the scales are written beside the bytes)")
+    if not fp8 and k_scale is not None:
+        raise ValueError(f"{who}: k_scale goes with an fp8 k_idx, not with {k_idx.dtype}")
+    if k_scale is not None and (not isinstance(k_scale, torch.Tensor) or k_scale.dtype != torch.float32
+                                or tuple(k_scale.shape) != tuple(k_idx.shape[:2])):
+        raise ValueError(f"{who}: k_scale must be a float32 tensor shaped like k_idx's rows {tuple(k_idx.shape[:2])}")
+    if packed:
+        if not isinstance(cu_seqlens_new, torch.Tensor) or cu_seqlens_new.dtype != torch.int32 or cu_seqlens_new.dim() != 1 \
+                or not cu_seqlens_new.is_contiguous() or cu_seqlens_new.numel() < 2:
+            raise ValueError(f"{who}: cu_seqlens_new must be a contiguous int32 tensor of B + 1 >= 2 entries")
+        if isinstance(max_seqlen_new, bool) or not isinstance(max_seqlen_new, int) or not 1 <= max_seqlen_new <= 1 << 28:
+            raise ValueError(f"{who}: max_seqlen_new must be an int in [1, 2^28], got {max_seqlen_new!r}")
+    B = cu_seqlens_new.numel() - 1 if packed else k_new.shape[0]
+    if block_table is None:
+        if k_idx.shape[0] != B:
+            raise ValueError(f"{who}: k_idx must be (B, S_k, d_I) with B = {B}, got {tuple(k_idx.shape)} (a pool needs its block_table)")
+    else:
+        _check_block_table(block_table, B, k_idx.shape[1], k_new, "k_new")
+    _check_cache_seqlens(cache_seqlens, B, k_new, "k_new")
+    if _indexer_capacity(k_idx, block_table) > 1 << 28:
+        raise ValueError(f"{who}: the capacity must be <= 2^28")
+    for name, t in (("k_idx", k_idx), ("k_scale", k_scale), ("cu_seqlens_new", cu_seqlens_new)):
+        if t is not None and t.device != k_new.device:
+            raise ValueError(f"{who}: {name} must be on k_new's device ({k_new.device}), got {t.device}")
+    for name, t in (("k_idx", k_idx), ("k_new", k_new), ("k_scale", k_scale)):
+        if t is not None and any(s < 0 for s in t.stride()):
+            raise ValueError(f"{who}: {name} with negative strides is not supported")
+
+
+def mla_indexer_append(k_idx, k_new, cache_seqlens, *, k_scale=None, block_table=None):
+    """The write side of the indexer's key cache (include/fa2_fwd.h fa2_mla_indexer_append) -> new_seqlens, int32 (B,).  k_idx is the
+    cache flash_attention_mla_indexer_topk reads, (B, S_k, d_I) or with block_table the pool (num_blocks, page_size, d_I) of any page
+    size; k_new (B, N_new, d_I), any strides, already rotated and transformed as the indexer expects (this call applies neither).  Token
+    t of sequence b becomes the row at key index clamp(cache_seqlens[b], 0, capacity) + t, IN PLACE; tokens past the capacity are
+    dropped, new_seqlens = min(cache_seqlens + N_new, capacity), cache_seqlens is not modified.  An fp8 k_idx (e4m3 / e5m2) takes
+    float16 / bfloat16 k_new and needs k_scale, float32 shaped like the cache's rows, any strides: the byte row and the scale written
+    are quantize_index_keys(row, k_idx.dtype) bit for bit (on the CPU, whose division is correctly rounded) for rows with amax 0 or
+    >= 2^-64 -- one power-of-two scale per row, 1 for a row of zeros.  A k_idx in k_new's dtype (f16, bf16, f32) takes k_scale=None and
+    the rows are copied bit for bit.  One launch, lengths included."""
+    check_mla_indexer_append_args(k_idx, k_new, cache_seqlens, k_scale, block_table)
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, new_seqlens, convert_triton_dtype(k_new.dtype),
+                                convert_triton_dtype(k_idx.dtype), block_table=block_table)
+    return new_seqlens
+
+
+def mla_indexer_append_varlen(k_idx, k_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, *, k_scale=None, block_table=None):
+    """mla_indexer_append for a ragged batch in one launch (fa2_mla_indexer_append_varlen) -> new_seqlens, int32 (B,).  k_new packed
+    (total_new, d_I), any strides; cu_seqlens_new and max_seqlen_new as in kvcache_append_varlen: sequence b brings the
+    min(cu[b + 1] - cu[b], max_seqlen_new) rows from cu[b] on, none is legal, rows outside every sequence are not read."""
+    check_mla_indexer_append_args(k_idx, k_new, cache_seqlens, k_scale, block_table, cu_seqlens_new, max_seqlen_new)
+    new_seqlens = torch.empty_like(cache_seqlens)
+    _lib.fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, new_seqlens, convert_triton_dtype(k_new.dtype),
+                                convert_triton_dtype(k_idx.dtype), block_table=block_table, cu_new=cu_seqlens_new, max_new=max_seqlen_new)
+    return new_seqlens
 
 
 def _indexer_capacity(k_idx, block_table):

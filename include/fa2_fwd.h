@@ -712,6 +712,45 @@ int fa2_kvcache_mla_append_varlen(void *KV, const int64_t kv_strides[4], const i
                                   int32_t dtype_enum, int32_t kv_dtype_enum, void *hip_stream);
 
 /*
+ * The latent append into the tile-scaled fp8 cache ("fp8_ds", the 656-byte row of fa2_fwd_kvcache_mla_sparse_ds below), fixed and
+ * packed: fa2_kvcache_mla_append / _varlen with the byte tensor KV in the cache's place, kv_strides = {batch or block, KV head, row}
+ * in BYTES (each >= 0, the last stride is 1), and without kv_descale, d, d_v (576, 512: the format's), kv_dtype_enum and the Q
+ * arguments (the sparse calls have no fused append; Q stays the caller's).  dtype_enum (c_new, pe_new, the tables, the row's rotary
+ * columns) is FA2_DTYPE_F16 or FA2_DTYPE_BF16.
+ *
+ *   Row.      Let r be the 576-column row fa2_kvcache_mla_append stores for the token in a cache of dtype_enum: columns 0 .. 511 c_new
+ *             bit for bit, 512 .. 575 pe_new with its first rotary_dim columns rotated at the row's position and rounded once.  The
+ *             656 bytes written: for each 128-column tile t, amax_t = max |r[c]| in fp32, scale_t = max(amax_t, 1e-4f) / 448
+ *             (correctly rounded division), stored as its fp32 bits at byte 512 + 4 t; byte c < 512 is
+ *             e4m3(clamp(r[c] / scale_(c / 128), +-448)), correctly rounded division, round to nearest even; bytes 528 .. 655 are
+ *             r[512 .. 575].  A row with a non-finite latent column gets unspecified bytes; it still writes only its own 656.
+ *   Rest.     Lengths and their clamps, the drop of tokens past the capacity, paging (any page size; S_k is the capacity of a contiguous
+ *             cache), the clamp of table entries, seqlens_out, and the packed form's spans, gaps and empty sequences are
+ *             fa2_kvcache_mla_append's and fa2_kvcache_mla_append_varlen's.
+ *   Speed.    One wave per row, one 16-byte load and one 8-byte store per lane, when every d-stride is 1, the other strides of c_new
+ *             and pe_new are multiples of 8 elements, both are 16-byte aligned, KV and its strides are multiples of 8 bytes, and the
+ *             tables have 16-byte aligned rows with rotary_dim % 16 == 0; one element at a time otherwise, with the same bytes.
+ *
+ * Errors: fa2_kvcache_mla_append's, then FA2_ERR_UNSUPPORTED for a dtype_enum other than F16 / BF16; all before any launch.
+ */
+int fa2_kvcache_mla_append_ds(void *KV, const int64_t kv_strides[3], const int32_t *block_table, int64_t block_table_stride,
+                              const void *c_new, const void *pe_new, const int64_t c_new_strides[4], const int64_t pe_new_strides[4],
+                              const int32_t *cache_seqlens, int32_t *seqlens_out,
+                              const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                              int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                              int32_t B, int32_t H_kv, int32_t N_new, int32_t S_k,
+                              int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t dtype_enum, void *hip_stream);
+
+int fa2_kvcache_mla_append_varlen_ds(void *KV, const int64_t kv_strides[3], const int32_t *block_table, int64_t block_table_stride,
+                                     const void *c_new, const void *pe_new, const int64_t c_new_strides[3],
+                                     const int64_t pe_new_strides[3],
+                                     const int32_t *cu_seqlens_new, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                                     const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                                     int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                     int32_t B, int32_t H_kv, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                                     int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t dtype_enum, void *hip_stream);
+
+/*
  * The fused MLA decode step: fa2_kvcache_mla_append, then on the same stream fa2_fwd_kvcache_mla (kv_dtype_enum == dtype_enum) or
  * fa2_fwd_kvcache_mla_fp8 over the updated cache with K = V = KV, v_strides = kv_strides, kv_descale for both descales, seqlens_out as
  * its cache_seqlens and, with tables, q_rot (contiguous (B, H, N_q, d)) as its Q; q_rot may be null without them.  q_pos_per_row
@@ -1025,6 +1064,39 @@ int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const v
 
 /* Bytes of the contiguous fp32 logits buffer (total_q, S_k): 4 * total_q * S_k, 0 if a size is < 1. */
 int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k);
+
+/*
+ * The write side of the indexer's key cache, fixed and packed: k_new (B, N_new, d_I), or packed (total_new, d_I) over cu_seqlens_new,
+ * in dtype_enum (F16, BF16, F32) with any strides, goes into k_idx -- (B, S_k, d_I) or, with block_table, the pool
+ * (num_blocks, page_size, d_I) of any page size, strides k_strides in elements -- at key indices clamp(cache_seqlens[b], 0, capacity)
+ * + t, and seqlens_out receives the new lengths.  No rotary and no transform: the keys come as the indexer reads them.
+ *
+ *   fp8.      k_dtype_enum FA2_DTYPE_F8E4M3 / F8E5M2 under F16 / BF16 k_new, k_scale (fp32, entry [b or block, row] at
+ *             k_scale_strides) required.  Per row: amax = max |x| in fp32, q = amax / top (top the format's largest finite value,
+ *             correctly rounded division) = m 2^e with m in [0.5, 1); scale = 2^e, or 2^(e - 1) at m = 0.5 -- the smallest power of two
+ *             with amax / scale <= top -- and 1 for a row of zeros; byte = fp8(clamp(x / scale, +-top)).  Stated for rows with amax 0
+ *             or >= 2^-64 and finite.
+ *   Copy.     k_dtype_enum == dtype_enum, k_scale null: the rows are copied bit for bit.
+ *   Rest.     Lengths, the drop past the capacity, paging, and the packed spans are fa2_kvcache_append's and _varlen's.
+ *
+ * Errors: FA2_ERR_BAD_ARG for a null k_idx, k_strides, k_new, k_new_strides, cache_seqlens, seqlens_out (or seqlens_out ==
+ * cache_seqlens), a negative stride, sizes out of range, a null k_scale / k_scale_strides with an fp8 cache and a k_scale without one;
+ * FA2_ERR_UNSUPPORTED for the dtypes and d_I outside [1, 576]; all before any launch.
+ */
+int fa2_mla_indexer_append(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                           const int32_t *block_table, int64_t block_table_stride,
+                           const void *k_new, const int64_t k_new_strides[3],
+                           const int32_t *cache_seqlens, int32_t *seqlens_out,
+                           int32_t B, int32_t N_new, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                           int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, void *hip_stream);
+
+int fa2_mla_indexer_append_varlen(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                                  const int32_t *block_table, int64_t block_table_stride,
+                                  const void *k_new, const int64_t k_new_strides[2],
+                                  const int32_t *cu_seqlens_new, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                                  int32_t B, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                                  int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, void *hip_stream);
 
 /*
  * The fused ragged MLA step: fa2_kvcache_mla_append_varlen over cu_seqlens_q (total_new = total_q, max_seqlen_new = max_seqlen_q;
