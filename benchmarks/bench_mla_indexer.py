@@ -14,7 +14,13 @@ Sides of one child (causal, every sequence full):
 
 Records (kind=kernels): per shape and key dtype the sides' avg / min / max / stddev in microseconds, for `auto` and `generic` the score
 and the selection kernel apart (score_*, select_*), the ratios of AUTO to the other sides and whether the min-max ranges overlap; for a
-prefill chunk the score kernel's TFLOP/s (2 H_I d_I per causal query-key pair)."""
+prefill chunk the score kernel's TFLOP/s (2 H_I d_I per causal query-key pair).
+
+--q-dtype e4m3 (with --k-dtype e4m3): q_idx quantised per (token, head) by quantize_index_keys, its scale folded into the weights, through
+the fp8-query entry point -- `auto` is then the fp8 matrix form idx8 and `generic` its VALU form -- and one more side:
+  idx16    the 16-bit call on the SAME queries widened to bf16 (exactly) over the same e4m3 keys and weights: what an engine ran before.
+Those records carry q_dtype, the score kernels' ratio idx8 / idx16 (score_auto_over_idx16), whether their min-max ranges overlap, and
+idx16's TFLOP/s beside idx8's on a prefill chunk."""
 import argparse
 import csv
 import glob
@@ -45,7 +51,7 @@ def emit(fh, **kw):
 
 
 class Case:
-    def __init__(self, name, dev, k_dtype="bf16"):
+    def __init__(self, name, dev, k_dtype="bf16", q_dtype="bf16"):
         import torch
         import flash_attention_dlrs_amd as fa
         from flash_attention_dlrs_amd import _lib
@@ -59,6 +65,10 @@ class Case:
         mk = lambda *s: torch.randn(*s, device=dev).to(torch.bfloat16)  # noqa: E731
         self.q = mk(B, H_I, N_q, D_I)
         self.w = torch.randn(B, H_I, N_q, device=dev) * H_I ** -0.5
+        self.q8 = None
+        if q_dtype == "e4m3":  # fp8 queries: the bytes, the same values widened to bf16 for the idx16 side, the scale in the weights
+            self.q8, q_scale = fa.quantize_index_keys(self.q, torch.float8_e4m3fn)
+            self.q, self.w, self.q8_enum = self.q8.to(torch.bfloat16), self.w * q_scale, convert_triton_dtype(torch.float8_e4m3fn)
         self.K = [mk(B, S, D_I) for _ in range(self.copies)]
         self.scale, self.k_enum = [None] * self.copies, self.enum
         if self.fmt:
@@ -77,11 +87,13 @@ class Case:
         self.i = (self.i + 1) % self.copies
         return self.K[self.i], self.scale[self.i]
 
-    def indexer(self, variant):
+    def indexer(self, variant, q8=False):
+        q, enum, table = (self.q8, self.q8_enum, self._lib.INDEXER_Q8_VARIANTS) if q8 else (self.q, self.enum, self._lib.INDEXER_VARIANTS)
+
         def run():
             k, ks = self._next()
-            self._lib.fa2_mla_indexer_topk(self.q, self.w, k, ks, self.logits, self.indices, self.lens, self.enum, self.k_enum,
-                                           causal=True, variant=self._lib.INDEXER_VARIANTS[variant])
+            self._lib.fa2_mla_indexer_topk(q, self.w, k, ks, self.logits, self.indices, self.lens, enum, self.k_enum, causal=True,
+                                           variant=table[variant])
         return run
 
     def torch_route(self):
@@ -103,7 +115,7 @@ class Case:
 def side_iters(side, shape, iters):
     """the VALU form and the torch route take tens of milliseconds on the large shapes: fewer calls there"""
     work = shape["B"] * shape["N_q"] * shape["N_k"] * H_I * D_I
-    return max(3, min(iters, int({"auto": 2e13, "torch": 4e12, "generic": 4e11}[side] / work)))
+    return max(3, min(iters, int({"auto": 2e13, "idx16": 2e13, "torch": 4e12, "generic": 4e11}[side] / work)))
 
 
 def timed(c, f, calls):
@@ -116,21 +128,23 @@ def timed(c, f, calls):
 def run_pass(name, args):
     """The traced child: each side warmed, then run back to back; the kernel trace holds the times."""
     import torch
-    c = Case(name, torch.device("cuda:0"), args.k_dtype)
+    c = Case(name, torch.device("cuda:0"), args.k_dtype, args.q_dtype)
     torch.cuda.synchronize()
     c.mark.fill_(0.0)  # the first marker: what lies before it is set-up
-    sides = [("auto", c.indexer("auto")), ("generic", c.indexer("generic")), ("torch", c.torch_route())]
+    q8 = args.q_dtype == "e4m3"
+    sides = [("auto", c.indexer("auto", q8))] + ([("idx16", c.indexer("idx16"))] if q8 else []) + \
+        [("generic", c.indexer("generic", q8)), ("torch", c.torch_route())]
     calls = {}
     for side, f in sides:
         calls[side] = side_iters(side, c.shape, args.iters) + 3
         timed(c, f, calls[side])
-    print(json.dumps(dict(case=name, calls=calls, order=[s for s, _ in sides], k_dtype=args.k_dtype, **c.shape)))
+    print(json.dumps(dict(case=name, calls=calls, order=[s for s, _ in sides], k_dtype=args.k_dtype, q_dtype=args.q_dtype, **c.shape)))
 
 
 def traced_child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
-           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--k-dtype", args.k_dtype] + extra
+           "--", sys.executable, os.path.abspath(__file__), "--iters", str(args.iters), "--k-dtype", args.k_dtype, "--q-dtype", args.q_dtype] + extra
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:  # a failed child ends the run: nothing more is started on the GPU
         sys.stderr.write(p.stdout[-2000:] + p.stderr[-2000:])
@@ -169,7 +183,7 @@ def stats(calls, split, warm=3):
 
 def run_rocprof(names, args, fh):
     for name in names:
-        out = os.path.join(args.rocprof, name + "_" + args.k_dtype)
+        out = os.path.join(args.rocprof, name + "_" + args.k_dtype + ("_q8" if args.q_dtype == "e4m3" else ""))
         info = traced_child(out, ["--pass-case", name], args)
         calls = call_times(out, sum(info["calls"].values()))
         sides, pos = {}, 0
@@ -181,6 +195,12 @@ def run_rocprof(names, args, fh):
         if info["N_q"] > 8:  # a prefill chunk: causal pairs only
             pairs = info["B"] * sum(info["N_k"] - info["N_q"] + qi + 1 for qi in range(info["N_q"]))
             extra["score_tflops"] = round(2 * H_I * D_I * pairs / (a["score_avg_us"] * 1e-6) / 1e12, 1)
+            if "idx16" in sides:
+                extra["idx16_score_tflops"] = round(2 * H_I * D_I * pairs / (sides["idx16"]["score_avg_us"] * 1e-6) / 1e12, 1)
+        if "idx16" in sides:  # the two matrix forms' score kernels over the same keys
+            x = sides["idx16"]
+            extra["score_auto_over_idx16"] = round(a["score_avg_us"] / x["score_avg_us"], 4)
+            extra["score_idx16_ranges_overlap"] = a["score_max_us"] >= x["score_min_us"] and x["score_max_us"] >= a["score_min_us"]
         emit(fh, kind="kernels", **{k: v for k, v in info.items() if k not in ("calls", "order")},
              auto_over_torch=round(a["avg_us"] / sides["torch"]["avg_us"], 4), torch_ranges_overlap=a["max_us"] >= sides["torch"]["min_us"],
              auto_over_generic=round(a["avg_us"] / sides["generic"]["avg_us"], 4),
@@ -195,9 +215,12 @@ def main():
                     help="the traces of the rocprofv3 children go under DIR")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--k-dtype", choices=K_DTYPES, default="bf16", help="the index keys' storage: bf16, or e4m3 with its per-row scale")
+    ap.add_argument("--q-dtype", choices=K_DTYPES, default="bf16", help="q_idx: bf16, or e4m3 (needs --k-dtype e4m3) with its scale in the weights")
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
+    if args.q_dtype == "e4m3" and args.k_dtype != "e4m3":
+        ap.error("--q-dtype e4m3 needs --k-dtype e4m3: fp8 queries go over fp8 keys")
     if args.pass_case:
         return run_pass(args.pass_case, args)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

@@ -63,7 +63,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_fwd_kvcache_mla_sparse_varlen", "fa2_kvcache_mla_sparse_varlen_num_splits", "fa2_mla_indexer_logits_varlen",
            "fa2_topk_indices_varlen", "fa2_mla_indexer_topk_varlen", "fa2_mla_indexer_varlen_workspace_bytes",
            "fa2_fwd_kvcache_mla_sparse_ds", "fa2_fwd_kvcache_mla_sparse_varlen_ds", "fa2_kvcache_mla_append_ds",
-           "fa2_kvcache_mla_append_varlen_ds", "fa2_mla_indexer_append", "fa2_mla_indexer_append_varlen")
+           "fa2_kvcache_mla_append_varlen_ds", "fa2_mla_indexer_append", "fa2_mla_indexer_append_varlen",
+           "fa2_mla_indexer_logits_q8", "fa2_mla_indexer_topk_q8", "fa2_mla_indexer_logits_varlen_q8", "fa2_mla_indexer_topk_varlen_q8")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -77,6 +78,8 @@ KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
 KVCACHE_MLA_VARIANTS = {"auto": 0, "generic": 1, "mla16": 3}
 # ... and the MLA indexer (fa2_mla_indexer_logits, fa2_mla_indexer_topk) its own: FA2_INDEXER_VARIANT_*
 INDEXER_VARIANTS = {"auto": 0, "generic": 1, "idx16": 2}
+# ... and its fp8-query entry points (the _q8 calls) theirs: FA2_INDEXER_VARIANT_IDX8 in IDX16's place, each set refusing the other's
+INDEXER_Q8_VARIANTS = {"auto": 0, "generic": 1, "idx8": 3}
 # ... and the packed forward with a value head size of its own (fa2_fwd_varlen_dv): FA2_VARIANT_MFMA16DV is a variant of it alone
 VARIANT_MFMA16DV = 28
 VARLEN_DV_VARIANTS = {"auto": VARIANT_AUTO, "generic": VARIANT_GENERIC, "mfma16dv": VARIANT_MFMA16DV}
@@ -290,6 +293,10 @@ def lib():
         l.fa2_mla_indexer_logits.argtypes = idx + [ctypes.c_int32, vp]
         l.fa2_mla_indexer_topk.restype = ctypes.c_int
         l.fa2_mla_indexer_topk.argtypes = idx + [ctypes.c_int32, vp, i64p, ctypes.c_int32, vp]
+        l.fa2_mla_indexer_logits_q8.restype = ctypes.c_int  # fp8 queries: the same lists
+        l.fa2_mla_indexer_logits_q8.argtypes = l.fa2_mla_indexer_logits.argtypes
+        l.fa2_mla_indexer_topk_q8.restype = ctypes.c_int
+        l.fa2_mla_indexer_topk_q8.argtypes = l.fa2_mla_indexer_topk.argtypes
         l.fa2_topk_indices.restype = ctypes.c_int
         l.fa2_topk_indices.argtypes = [vp, i64p, vp] + [ctypes.c_int32] * 5 + [vp, i64p, vp]
         l.fa2_mla_indexer_workspace_bytes.restype = ctypes.c_int64
@@ -316,6 +323,10 @@ def lib():
         l.fa2_mla_indexer_logits_varlen.argtypes = idxv + [ctypes.c_int32, vp]
         l.fa2_mla_indexer_topk_varlen.restype = ctypes.c_int
         l.fa2_mla_indexer_topk_varlen.argtypes = idxv + [ctypes.c_int32, vp, i64p, ctypes.c_int32, vp]
+        l.fa2_mla_indexer_logits_varlen_q8.restype = ctypes.c_int
+        l.fa2_mla_indexer_logits_varlen_q8.argtypes = l.fa2_mla_indexer_logits_varlen.argtypes
+        l.fa2_mla_indexer_topk_varlen_q8.restype = ctypes.c_int
+        l.fa2_mla_indexer_topk_varlen_q8.argtypes = l.fa2_mla_indexer_topk_varlen.argtypes
         l.fa2_topk_indices_varlen.restype = ctypes.c_int
         l.fa2_topk_indices_varlen.argtypes = [vp, i64p, vp, vp] + [ctypes.c_int32] * 6 + [vp, i64p, vp]
         l.fa2_mla_indexer_varlen_workspace_bytes.restype = ctypes.c_int64
@@ -734,6 +745,11 @@ def mla_indexer_workspace_bytes(B, N_q, S_k):
     return int(lib().fa2_mla_indexer_workspace_bytes(B, N_q, S_k))
 
 
+def _indexer_entry(name, dtype_enum):
+    """The entry point `name` of the library, or its `_q8` form when q_idx is fp8 (dtype_enum an fp8 format): the same argument list."""
+    return getattr(lib(), name + "_q8" if int(dtype_enum) in (FA2_DTYPE_F8E4M3, FA2_DTYPE_F8E5M2) else name)
+
+
 def _indexer_args(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal):
     """The arguments fa2_mla_indexer_logits and fa2_mla_indexer_topk share, in the header's order up to `causal`."""
     B, H_I, N_q, d_I = q_idx.shape
@@ -750,10 +766,12 @@ def fa2_mla_indexer_logits(q_idx, weights, k_idx, k_scale, logits, cache_seqlens
                            variant=0):
     """Launch the index scores (include/fa2_fwd.h fa2_mla_indexer_logits) on the current stream of q_idx's device: q_idx
     (B, H_I, N_q, d_I), weights fp32 (B, H_I, N_q), k_idx (B, S_k, d_I) or the pool (num_blocks, page_size, d_I) with block_table,
-    k_scale fp32 shaped like k_idx's rows or None, logits fp32 (B, N_q, capacity), written for j < n(b, qi).  Any strides."""
+    k_scale fp32 shaped like k_idx's rows or None, logits fp32 (B, N_q, capacity), written for j < n(b, qi).  Any strides.  An fp8
+    dtype_enum (fp8 q_idx over an fp8 k_idx; no q_scale, the caller folds it into weights) goes to fa2_mla_indexer_logits_q8, and
+    likewise in the three calls below."""
     if q_idx.device.type != "cuda":
         raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
-    _launch(lib().fa2_mla_indexer_logits, q_idx,
+    _launch(_indexer_entry("fa2_mla_indexer_logits", dtype_enum), q_idx,
             *_indexer_args(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal),
             int(variant), _raw_stream(q_idx.device.index))
 
@@ -764,7 +782,7 @@ def fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_
     (B, N_q, topk) from the logits buffer."""
     if q_idx.device.type != "cuda":
         raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
-    _launch(lib().fa2_mla_indexer_topk, q_idx,
+    _launch(_indexer_entry("fa2_mla_indexer_topk", dtype_enum), q_idx,
             *_indexer_args(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, block_table, dtype_enum, k_dtype_enum, causal),
             indices.shape[2], indices.data_ptr(), _i64(indices.stride()), int(variant), _raw_stream(q_idx.device.index))
 
@@ -861,7 +879,7 @@ def fa2_mla_indexer_logits_varlen(q_idx, weights, k_idx, k_scale, logits, cu_q, 
     device; the key side as fa2_mla_indexer_logits.  Any strides."""
     if q_idx.device.type != "cuda":
         raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
-    _launch(lib().fa2_mla_indexer_logits_varlen, q_idx,
+    _launch(_indexer_entry("fa2_mla_indexer_logits_varlen", dtype_enum), q_idx,
             *_indexer_varlen_args(q_idx, weights, k_idx, k_scale, logits, cu_q, max_q, cache_seqlens, block_table, dtype_enum, k_dtype_enum,
                                   causal),
             int(variant), _raw_stream(q_idx.device.index))
@@ -873,7 +891,7 @@ def fa2_mla_indexer_topk_varlen(q_idx, weights, k_idx, k_scale, logits, indices,
     then indices int32 (total_q, topk) from the logits buffer."""
     if q_idx.device.type != "cuda":
         raise NotImplementedError("q_idx, weights, k_idx must be on the same CUDA device")
-    _launch(lib().fa2_mla_indexer_topk_varlen, q_idx,
+    _launch(_indexer_entry("fa2_mla_indexer_topk_varlen", dtype_enum), q_idx,
             *_indexer_varlen_args(q_idx, weights, k_idx, k_scale, logits, cu_q, max_q, cache_seqlens, block_table, dtype_enum, k_dtype_enum,
                                   causal),
             indices.shape[1], indices.data_ptr(), _i64(indices.stride()), int(variant), _raw_stream(q_idx.device.index))

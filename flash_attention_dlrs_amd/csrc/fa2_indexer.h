@@ -54,3 +54,13 @@ bool fa2_indexer_mfma16_v_supports(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_mfma16_v(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_generic_v(const Fa2IndexerProblem &p);
 int fa2_launch_topk_indices_v(const Fa2IndexerProblem &p);
+// fp8 queries (the _q8 entry points, `dtype` and `k_dtype` both fp8).  Matrix form (fa2_indexer_mfma8.hip, FA2_INDEXER_VARIANT_IDX8):
+// 64 index heads of kIdx8QB query positions against 64-key tiles on v_mfma_f32_16x16x128_f8f6f4, fixed and packed (_v); the VALU form's
+// fp8-query instantiations (fa2_indexer_generic_q8.hip, _q8_v), in units of their own so the 16-bit units keep their code.
+constexpr int kIdx8QB = 16;  // query positions per workgroup
+bool fa2_indexer_mfma8_supports(const Fa2IndexerProblem &p);
+int fa2_launch_indexer_mfma8(const Fa2IndexerProblem &p);
+bool fa2_indexer_mfma8_v_supports(const Fa2IndexerProblem &p);
+int fa2_launch_indexer_mfma8_v(const Fa2IndexerProblem &p);
+int fa2_launch_indexer_generic_q8(const Fa2IndexerProblem &p);
+int fa2_launch_indexer_generic_q8_v(const Fa2IndexerProblem &p);

@@ -1,5 +1,5 @@
 // fa2_indexer_api.hip -- host side of the MLA indexer (include/fa2_fwd.h): fa2_mla_indexer_logits, fa2_topk_indices, fa2_mla_indexer_topk
-// and fa2_mla_indexer_workspace_bytes, and their packed (_varlen) forms.  One call struct and one check order of its own, beside the attention calls' DecodeCall
+// and fa2_mla_indexer_workspace_bytes, their packed (_varlen) forms and the fp8-query (_q8) forms of the four score-bearing calls.  One call struct and one check order of its own, beside the attention calls' DecodeCall
 // (fa2_decode_api.hip): every check runs before any launch, then the score kernel of the form the variant names -- AUTO: the matrix
 // form where it runs, else the VALU form -- and the selection, on the call's stream.  fa2_mla_indexer_append and _varlen, the write side of
 // the index-key cache, are here too: their checks, then the quantising append kernel (fa2_decode_append_q.hip).
@@ -29,6 +29,8 @@ struct IndexerCall {
     bool packed = false;
     const int32_t *cu_seqlens_q = nullptr;
     int32_t total_q = 0;
+    // the _q8 entry points: fp8 q_idx AND k_idx, the variants AUTO / GENERIC / IDX8
+    bool q8 = false;
 };
 
 // The stride arrays of a packed call in the fixed call's order: {token, head, column} -> {0, head, token, column}, {token, head} ->
@@ -142,11 +144,23 @@ int check_indexer(const IndexerCall &c, Fa2IndexerProblem &p) {
         return FA2_ERR_BAD_ARG;
     }
     if (c.scores) {
-        if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16 && c.dtype_enum != FA2_DTYPE_F32) {
+        if (c.q8) {
+            if (!is_fp8(c.dtype_enum)) {
+                fa2_set_error("mla indexer q8: dtype_enum %d (q_idx) must be FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", c.dtype_enum);
+                return FA2_ERR_UNSUPPORTED;
+            }
+            if (!is_fp8(c.k_dtype_enum)) {
+                fa2_set_error("mla indexer q8: k_dtype_enum %d must be FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", c.k_dtype_enum);
+                return FA2_ERR_UNSUPPORTED;
+            }
+            if (!c.k_scale) {
+                fa2_set_error("mla indexer: null k_scale with an fp8 cache (k_dtype_enum %d)", c.k_dtype_enum);
+                return FA2_ERR_BAD_ARG;
+            }
+        } else if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16 && c.dtype_enum != FA2_DTYPE_F32) {
             fa2_set_error("mla indexer: dtype_enum %d (q_idx) must be FA2_DTYPE_F16, FA2_DTYPE_BF16 or FA2_DTYPE_F32", c.dtype_enum);
             return FA2_ERR_UNSUPPORTED;
-        }
-        if (c.k_dtype_enum != c.dtype_enum) {
+        } else if (c.k_dtype_enum != c.dtype_enum) {
             if (!is_fp8(c.k_dtype_enum)) {
                 fa2_set_error("mla indexer: k_dtype_enum %d must be dtype_enum or FA2_DTYPE_F8E4M3 / FA2_DTYPE_F8E5M2", c.k_dtype_enum);
                 return FA2_ERR_UNSUPPORTED;
@@ -164,8 +178,10 @@ int check_indexer(const IndexerCall &c, Fa2IndexerProblem &p) {
             fa2_set_error("mla indexer: d_I=%d must be in [1, 576]", c.d_I);
             return FA2_ERR_UNSUPPORTED;
         }
-        if (c.variant != FA2_INDEXER_VARIANT_AUTO && c.variant != FA2_INDEXER_VARIANT_GENERIC && c.variant != FA2_INDEXER_VARIANT_IDX16) {
-            fa2_set_error("mla indexer: unknown variant %d (auto 0, generic 1, idx16 2)", c.variant);
+        if (c.variant != FA2_INDEXER_VARIANT_AUTO && c.variant != FA2_INDEXER_VARIANT_GENERIC &&
+            c.variant != (c.q8 ? FA2_INDEXER_VARIANT_IDX8 : FA2_INDEXER_VARIANT_IDX16)) {
+            fa2_set_error(c.q8 ? "mla indexer q8: unknown variant %d (auto 0, generic 1, idx8 3)"
+                               : "mla indexer: unknown variant %d (auto 0, generic 1, idx16 2)", c.variant);
             return FA2_ERR_UNSUPPORTED;
         }
         // the largest grid a score form takes (the VALU form's: 256 keys of one position per workgroup)
@@ -208,7 +224,13 @@ int run_indexer(const IndexerCall &c) {
     Fa2IndexerProblem p;
     int rc = check_indexer(c, p);
     if (rc != FA2_OK) return rc;
-    if (c.scores) {
+    if (c.scores && c.q8) {  // fp8 queries: the forms of their own, chosen by the same rule
+        const bool fits = c.packed ? fa2_indexer_mfma8_v_supports(p) : fa2_indexer_mfma8_supports(p);
+        const bool matrix = c.variant == FA2_INDEXER_VARIANT_AUTO ? fits : c.variant == FA2_INDEXER_VARIANT_IDX8;
+        if (c.packed) rc = matrix ? fa2_launch_indexer_mfma8_v(p) : fa2_launch_indexer_generic_q8_v(p);
+        else rc = matrix ? fa2_launch_indexer_mfma8(p) : fa2_launch_indexer_generic_q8(p);
+        if (rc != FA2_OK) return rc;
+    } else if (c.scores) {
         const bool fits = c.packed ? fa2_indexer_mfma16_v_supports(p) : fa2_indexer_mfma16_supports(p);
         const bool matrix = c.variant == FA2_INDEXER_VARIANT_AUTO ? fits : c.variant == FA2_INDEXER_VARIANT_IDX16;
         // (a forced matrix form that cannot run: refused there)
@@ -425,6 +447,58 @@ int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const v
 int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k) {
     if (total_q < 1 || S_k < 1) return 0;
     return 4 * (int64_t)total_q * S_k;  // < 2^64
+}
+
+// fp8 queries: the same argument lists through the same checks, `q8` set (include/fa2_fwd.h).
+int fa2_mla_indexer_logits_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                           const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],
+                           const int64_t k_scale_strides[2], const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                           const int32_t *block_table, int64_t block_table_stride, int32_t B, int32_t H_I, int32_t N_q, int32_t S_k,
+                           int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum,
+                           int32_t k_dtype_enum, int32_t causal, int32_t variant, void *hip_stream) {
+    return run_indexer({true, false, q_idx, weights, k_idx, k_scale, logits, q_strides, w_strides, k_strides, k_scale_strides, logit_strides,
+                        cache_seqlens, block_table, block_table_stride, B, H_I, N_q, S_k, num_blocks, page_size, max_blocks, d_I,
+                        dtype_enum, k_dtype_enum, causal, variant, 0, nullptr, nullptr, hip_stream, false, nullptr, 0, true});
+}
+
+int fa2_mla_indexer_topk_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                         const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],
+                         const int64_t k_scale_strides[2], const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                         const int32_t *block_table, int64_t block_table_stride, int32_t B, int32_t H_I, int32_t N_q, int32_t S_k,
+                         int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                         int32_t causal, int32_t topk, int32_t *indices, const int64_t index_strides[3], int32_t variant,
+                         void *hip_stream) {
+    return run_indexer({true, true, q_idx, weights, k_idx, k_scale, logits, q_strides, w_strides, k_strides, k_scale_strides, logit_strides,
+                        cache_seqlens, block_table, block_table_stride, B, H_I, N_q, S_k, num_blocks, page_size, max_blocks, d_I,
+                        dtype_enum, k_dtype_enum, causal, variant, topk, indices, index_strides, hip_stream, false, nullptr, 0, true});
+}
+
+int fa2_mla_indexer_logits_varlen_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                  const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                  const int64_t k_scale_strides[2], const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                                  const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride, int32_t B,
+                                  int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                                  int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal,
+                                  int32_t variant, void *hip_stream) {
+    PackedStrides s;
+    return run_indexer({true, false, q_idx, weights, k_idx, k_scale, logits, s.q4(q_strides), s.w3(w_strides), k_strides, k_scale_strides,
+                        PackedStrides::rows3(logit_strides, s.lg), cache_seqlens, block_table, block_table_stride, B, H_I, max_seqlen_q,
+                        S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum, causal, variant, 0, nullptr, nullptr,
+                        hip_stream, true, cu_seqlens_q, total_q, true});
+}
+
+int fa2_mla_indexer_topk_varlen_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                const int64_t k_scale_strides[2], const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                                const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride, int32_t B,
+                                int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                                int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal, int32_t topk,
+                                int32_t *indices, const int64_t index_strides[2], int32_t variant, void *hip_stream) {
+    PackedStrides s;
+    return run_indexer({true, true, q_idx, weights, k_idx, k_scale, logits, s.q4(q_strides), s.w3(w_strides), k_strides, k_scale_strides,
+                        PackedStrides::rows3(logit_strides, s.lg), cache_seqlens, block_table, block_table_stride, B, H_I, max_seqlen_q,
+                        S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum, causal, variant, topk, indices,
+                        PackedStrides::rows3(index_strides, s.idx), hip_stream, true, cu_seqlens_q, total_q, true});
 }
 
 }  // extern "C"

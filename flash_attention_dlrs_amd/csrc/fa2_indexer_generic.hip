@@ -18,6 +18,9 @@
 #ifndef FA2_INDEXER_VARLEN
 #define FA2_INDEXER_VARLEN 0
 #endif
+#ifndef FA2_INDEXER_Q8
+#define FA2_INDEXER_Q8 0
+#endif
 
 namespace {
 
@@ -103,6 +106,19 @@ template <class E, class C = E> int launch_e(const Fa2IndexerProblem &p) {
 
 }  // namespace
 
+#if FA2_INDEXER_Q8
+// fp8 q_idx (the _q8 entry points, which have checked the pair): the query bytes converted exactly as they are loaded, like the
+// cache's; fp32 arithmetic as everywhere here.  These instantiations alone are fa2_indexer_generic_q8.hip's and _q8_v.hip's.
+#if FA2_INDEXER_VARLEN
+int fa2_launch_indexer_generic_q8_v(const Fa2IndexerProblem &p) {
+#else
+int fa2_launch_indexer_generic_q8(const Fa2IndexerProblem &p) {
+#endif
+    const bool k4 = p.k_dtype == FA2_DTYPE_F8E4M3;
+    if (p.dtype == FA2_DTYPE_F8E4M3) return k4 ? launch_e<CacheF8E4M3, CacheF8E4M3>(p) : launch_e<CacheF8E4M3, CacheF8E5M2>(p);
+    return k4 ? launch_e<CacheF8E5M2, CacheF8E4M3>(p) : launch_e<CacheF8E5M2, CacheF8E5M2>(p);
+}
+#else
 #if FA2_INDEXER_VARLEN
 int fa2_launch_indexer_generic_v(const Fa2IndexerProblem &p) {
 #else
@@ -120,3 +136,4 @@ int fa2_launch_indexer_generic(const Fa2IndexerProblem &p) {
     default: fa2_set_error("mla indexer: dtype enum %d is not supported", p.dtype); return FA2_ERR_UNSUPPORTED;
     }
 }
+#endif

@@ -67,6 +67,12 @@ template <bool E4M3> struct F8 {
     }
 };
 
+// v_mfma_f32_16x16x128_f8f6f4 with a format of its own per operand (FA: A's, FB: B's; 0 = e4m3, 1 = e5m2; cbsz / blgp), unscaled
+// (constant zero scales select the plain instruction): D = A . B^T + c, the 128 columns of a row in one instruction.
+template <int FA, int FB> __device__ __forceinline__ f32x4 mfma_f8_16x16x128(i32x8 a, i32x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, 0, 0, 0, 0);
+}
+
 // Exchange between the two 32-lane halves of the wave with v_permlane32_swap (VALU, no LDS trip):
 // r[0][l] = x[l & 31], r[1][l] = x[32 + (l & 31)].  NB: the elements are copied to scalars before the
 // bit cast -- __builtin_bit_cast applied directly to a vector ELEMENT (r[1]) reads element 0 with this

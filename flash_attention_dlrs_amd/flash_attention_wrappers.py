@@ -1099,7 +1099,9 @@ def quantize_index_keys(k, dtype):
     """(k8, k_scale) of index keys (..., d_I) for the indexer's fp8 cache: one POWER-OF-TWO scale per row, the smallest with
     amax(row) / scale <= finfo(dtype).max (1 for a row of zeros), float32 of shape k.shape[:-1]; k8 = (k / scale) in dtype
     (torch.float8_e4m3fn or torch.float8_e5m2).  The division is exact, so k8.float() * k_scale[..., None] is exact in fp32 as
-    well.  Plain torch, any device."""
+    well.  Plain torch, any device.  It is also the way to make fp8 QUERIES for the indexer: quantize_index_keys(q_idx, dtype)
+    gives (q8, q_scale) with one scale per (token, head); the indexer calls take q8 and NO q_scale -- multiply q_scale (moved to
+    weights' layout) into weights."""
     if dtype not in FP8_CACHE_DTYPES:
         raise ValueError(f"quantize_index_keys: dtype must be torch.float8_e4m3fn or torch.float8_e5m2, got {dtype}")
     if not isinstance(k, torch.Tensor) or k.dim() < 1 or not k.dtype.is_floating_point:
@@ -1194,15 +1196,17 @@ def _indexer_capacity(k_idx, block_table):
 
 def check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk=2048, k_scale=None, block_table=None):
     """ValueError, naming the argument, for what flash_attention_mla_indexer_topk cannot take: q_idx (B, H_I, N_q, d_I) in f16, bf16
-    or f32 with d_I <= 576; weights float32 (B, H_I, N_q); k_idx (B, S_k, d_I), or the pool (num_blocks, page_size, d_I) with an int32
-    block_table (B, max_blocks), in q_idx's dtype or fp8 under f16 / bf16; k_scale float32 shaped like k_idx's rows, required with an
-    fp8 k_idx; cache_seqlens int32 (B,) or None; topk an int in [1, 2^28]; everything on q_idx's device.  Pure: takes CPU tensors."""
+    or f32, or fp8 over an fp8 k_idx, with d_I <= 576; weights float32 (B, H_I, N_q); k_idx (B, S_k, d_I), or the pool (num_blocks,
+    page_size, d_I) with an int32 block_table (B, max_blocks), in q_idx's dtype or fp8 under f16 / bf16 / fp8 (the two fp8 formats
+    need not match); k_scale float32 shaped like k_idx's rows, required with an fp8 k_idx; cache_seqlens int32 (B,) or None; topk an int in [1, 2^28]; everything on q_idx's device.  Pure: takes CPU tensors."""
     who = "mla indexer"
     if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 4:
         raise ValueError(f"{who}: q_idx must be a tensor (B, H_I, N_q, d_I), got "
                          f"{tuple(q_idx.shape) if isinstance(q_idx, torch.Tensor) else type(q_idx).__name__}")
-    if q_idx.dtype not in INDEXER_Q_DTYPES:
-        raise ValueError(f"{who}: q_idx must be float16, bfloat16 or float32, got {q_idx.dtype}")
+    q8 = q_idx.dtype in FP8_CACHE_DTYPES
+    if q_idx.dtype not in INDEXER_Q_DTYPES and not q8:
+        raise ValueError(f"{who}: q_idx must be float16, bfloat16 or float32, or float8_e4m3fn / float8_e5m2 over an fp8 k_idx, "
+                         f"got {q_idx.dtype}")
     B, H_I, N_q, d_I = q_idx.shape
     if min(B, H_I, N_q) < 1 or not 1 <= d_I <= 576:
         raise ValueError(f"{who}: q_idx needs B, H_I, N_q >= 1 and d_I in [1, 576], got {tuple(q_idx.shape)}")
@@ -1211,6 +1215,8 @@ def check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk=2048, k_sc
     if not isinstance(k_idx, torch.Tensor) or k_idx.dim() != 3 or k_idx.shape[2] != d_I or k_idx.shape[1] < 1:
         raise ValueError(f"{who}: k_idx must be a tensor (B, S_k, d_I) or a pool (num_blocks, page_size, d_I) with d_I = {d_I}")
     fp8 = k_idx.dtype in FP8_CACHE_DTYPES
+    if q8 and not fp8:
+        raise ValueError(f"{who}: k_idx must be float8_e4m3fn or float8_e5m2 under an fp8 q_idx ({q_idx.dtype}), got {k_idx.dtype}")
     if fp8 and q_idx.dtype == torch.float32:
         raise ValueError(f"{who}: an fp8 k_idx ({k_idx.dtype}) goes with float16 / bfloat16 q_idx, not float32")
     if not fp8 and k_idx.dtype != q_idx.dtype:
@@ -1239,10 +1245,17 @@ def check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk=2048, k_sc
             raise ValueError(f"{who}: {name} with negative strides is not supported")
 
 
-def _indexer_variant(variant):
-    if variant not in _lib.INDEXER_VARIANTS:
-        raise ValueError(f"mla indexer: variant must be one of {sorted(_lib.INDEXER_VARIANTS)}, got {variant!r}")
-    return _lib.INDEXER_VARIANTS[variant]
+def _indexer_variant(variant, q_idx):
+    """The variant's number.  The matrix forms go with the queries' width -- "idx8" with an fp8 q_idx (_lib.INDEXER_Q8_VARIANTS, the
+    _q8 entry points), "idx16" with f16 / bf16 (_lib.INDEXER_VARIANTS) -- and each call refuses the other's."""
+    q8 = q_idx.dtype in FP8_CACHE_DTYPES
+    mine, other = (_lib.INDEXER_Q8_VARIANTS, _lib.INDEXER_VARIANTS) if q8 else (_lib.INDEXER_VARIANTS, _lib.INDEXER_Q8_VARIANTS)
+    if variant in mine:
+        return mine[variant]
+    if isinstance(variant, str) and variant in other:
+        raise ValueError(f"mla indexer: variant {variant!r} does not go with {'an fp8' if q8 else 'a 16-bit or float32'} q_idx "
+                         f"({q_idx.dtype}); its variants are {sorted(mine)}")
+    raise ValueError(f"mla indexer: variant must be one of {sorted(set(mine) | set(other))}, got {variant!r}")
 
 
 def _indexer_dev(dev, q_idx):
@@ -1254,9 +1267,10 @@ def mla_indexer_logits(q_idx, weights, k_idx, cache_seqlens, dev, *, causal=True
     """The index scores of the MLA indexer alone (include/fa2_fwd.h fa2_mla_indexer_logits) -> logits float32 (B, N_q, capacity):
     logits[b, qi, j] = k_scale[b, j] * sum_h weights[b, h, qi] * relu(q_idx[b, h, qi] . k_idx[b, j]) for the candidates j < n(b, qi)
     of query qi (position N_k(b) - N_q + qi; causal: keys 0 .. position, else all N_k(b)).  Entries at j >= n(b, qi) are NOT written:
-    the buffer comes from torch.empty.  Arguments as flash_attention_mla_indexer_topk."""
+    the buffer comes from torch.empty.  Arguments as flash_attention_mla_indexer_topk (an fp8 q_idx included: no q_scale, its scale
+    goes into weights)."""
     check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, 1, k_scale, block_table)
-    v = _indexer_variant(variant)
+    v = _indexer_variant(variant, q_idx)
     _indexer_dev(dev, q_idx)
     B, _, N_q, _ = q_idx.shape
     logits = torch.empty((B, N_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
@@ -1302,10 +1316,13 @@ def flash_attention_mla_indexer_topk(q_idx, weights, k_idx, cache_seqlens, dev, 
     sequence b stands at position N_k(b) - N_q + qi; causal: its candidates are the keys up to that position, else all N_k(b).
     The list holds the min(topk, n) candidates of highest score (ties: the lower position), in ASCENDING position, padded with -1.
     variant is one of _lib.INDEXER_VARIANTS: "idx16" (f16 / bf16, d_I = 128, H_I <= 64, unit column strides, 16-byte aligned
-    rows), "generic" (everything else), "auto".  return_logits: (indices, logits), the float32 (B, N_q, capacity) scores, written
+    rows), "generic" (everything else), "auto".  fp8 QUERIES: q_idx in float8_e4m3fn or float8_e5m2 over an fp8 k_idx (either
+    format) goes to the fp8 x fp8 entry points (fa2_mla_indexer_topk_q8), whose matrix form is "idx8" (v_mfma_f32_16x16x128_f8f6f4,
+    same conditions) in "idx16"'s place.  There is NO q_scale argument: quantise with quantize_index_keys(q, dtype) -> (q8, scale),
+    one power-of-two scale per (token, head), and multiply that scale into weights, as the model's own code does.  return_logits: (indices, logits), the float32 (B, N_q, capacity) scores, written
     for the candidates only.  No autograd."""
     check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk, k_scale, block_table)
-    v = _indexer_variant(variant)
+    v = _indexer_variant(variant, q_idx)
     _indexer_dev(dev, q_idx)
     B, _, N_q, _ = q_idx.shape
     logits = torch.empty((B, N_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
@@ -1458,7 +1475,7 @@ def mla_indexer_logits_varlen(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q,
     N_k(b) - n_q(b) + i; entries at and past its candidate count, and rows no sequence owns, are NOT written: the buffer comes from
     torch.empty.  Arguments as flash_attention_mla_indexer_topk_varlen."""
     check_mla_indexer_varlen_args(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, 1, k_scale, block_table)
-    v = _indexer_variant(variant)
+    v = _indexer_variant(variant, q_idx)
     _indexer_dev(dev, q_idx)
     logits = torch.empty((q_idx.shape[0], _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
     _lib.fa2_mla_indexer_logits_varlen(q_idx, weights, k_idx, k_scale, logits, cu_seqlens_q, max_seqlen_q, cache_seqlens,
@@ -1492,13 +1509,13 @@ def flash_attention_mla_indexer_topk_varlen(q_idx, weights, k_idx, cu_seqlens_q,
                                             k_scale=None, block_table=None, variant="auto", return_logits=False):
     """The MLA indexer over variable-length (packed) queries (include/fa2_fwd.h fa2_mla_indexer_topk_varlen) -> indices int32
     (total_q, topk), the key lists flash_attention_mla_sparse_varlen_decode_forward takes as they are.  q_idx (total_q, H_I, d_I) in
-    f16, bf16 or f32, any strides; weights float32 (total_q, H_I); cu_seqlens_q int32 (B + 1,) on q_idx's device and max_seqlen_q as
+    f16, bf16 or f32, or fp8 over an fp8 k_idx (no q_scale: its scale goes into weights), any strides; weights float32 (total_q, H_I); cu_seqlens_q int32 (B + 1,) on q_idx's device and max_seqlen_q as
     in flash_attention_mla_varlen_decode_forward; k_idx, k_scale, cache_seqlens, block_table, topk, causal, variant and return_logits
     are flash_attention_mla_indexer_topk's.  Query i of sequence b stands at position N_k(b) - n_q(b) + i.  Sequence b's rows equal
     flash_attention_mla_indexer_topk's on that sequence alone, byte for byte; rows no sequence owns are not written.  return_logits:
     (indices, logits), the float32 (total_q, capacity) scores.  No autograd."""
     check_mla_indexer_varlen_args(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk, k_scale, block_table)
-    v = _indexer_variant(variant)
+    v = _indexer_variant(variant, q_idx)
     _indexer_dev(dev, q_idx)
     total_q = q_idx.shape[0]
     logits = torch.empty((total_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)

@@ -1066,6 +1066,60 @@ int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const v
 int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k);
 
 /*
+ * The MLA indexer with fp8 QUERIES (the _q8 entry points): the four score-bearing calls above, argument for argument, with q_idx in
+ * e4m3fn or e5m2 (OCP) as DeepSeek-V3.2's inference code holds it.  k_idx is in either fp8 format too, and the two need not match.
+ *
+ *   Scores.   logit[b, qi, j] = k_scale[b, j] * sum_h weights[b, h, qi] * max(0, q8[b, h, qi, :] . k8[b, j, :]), fp32, where q8 . k8 is
+ *             the sum of the exact products of the STORED fp8 values.  There is NO q_scale argument: the caller quantises q_idx per
+ *             (token, head) and multiplies that scale into `weights`, as the model's own code does.  k_scale is required.
+ *   Dtypes.   dtype_enum and k_dtype_enum are each FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2; anything else is FA2_ERR_UNSUPPORTED, the
+ *             message naming the argument.
+ *   Variants. FA2_INDEXER_VARIANT_IDX8: d_I = 128, H_I <= 64, unit column strides, 16-byte aligned rows, contiguous or paged at any
+ *             page size, fixed or packed, on v_mfma_f32_16x16x128_f8f6f4 -- one instruction is the whole dot product of 16 heads
+ *             against 16 keys.  GENERIC: everything else, on the VALU, the bytes converted exactly as they are loaded.  AUTO: IDX8
+ *             where it runs, else GENERIC.  A forced IDX8 on a problem it cannot run returns FA2_ERR_UNSUPPORTED; IDX16 and every
+ *             other value are refused with a message that lists these three.
+ *   The mask, the candidate counts, which logits are written, the paging rule, the lists, the packed rows, the workspace functions
+ *   and every other check, its order and its message are those of the 16-bit calls.
+ */
+#define FA2_INDEXER_VARIANT_IDX8 3
+
+int fa2_mla_indexer_logits_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                              const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],
+                              const int64_t k_scale_strides[2], const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                              const int32_t *block_table, int64_t block_table_stride,
+                              int32_t B, int32_t H_I, int32_t N_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                              int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal,
+                              int32_t variant, void *hip_stream);
+
+int fa2_mla_indexer_topk_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                            const int64_t q_strides[4], const int64_t w_strides[3], const int64_t k_strides[3],
+                            const int64_t k_scale_strides[2], const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                            const int32_t *block_table, int64_t block_table_stride,
+                            int32_t B, int32_t H_I, int32_t N_q, int32_t S_k, int32_t num_blocks, int32_t page_size,
+                            int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, int32_t causal,
+                            int32_t topk, int32_t *indices, const int64_t index_strides[3], int32_t variant, void *hip_stream);
+
+int fa2_mla_indexer_logits_varlen_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                     const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                     const int64_t k_scale_strides[2], const int64_t logit_strides[2],
+                                     const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                     const int32_t *block_table, int64_t block_table_stride,
+                                     int32_t B, int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks,
+                                     int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                                     int32_t causal, int32_t variant, void *hip_stream);
+
+int fa2_mla_indexer_topk_varlen_q8(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,
+                                   const int64_t q_strides[3], const int64_t w_strides[2], const int64_t k_strides[3],
+                                   const int64_t k_scale_strides[2], const int64_t logit_strides[2],
+                                   const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                   const int32_t *block_table, int64_t block_table_stride,
+                                   int32_t B, int32_t H_I, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks,
+                                   int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                                   int32_t causal, int32_t topk, int32_t *indices, const int64_t index_strides[2], int32_t variant,
+                                   void *hip_stream);
+
+/*
  * The write side of the indexer's key cache, fixed and packed: k_new (B, N_new, d_I), or packed (total_new, d_I) over cu_seqlens_new,
  * in dtype_enum (F16, BF16, F32) with any strides, goes into k_idx -- (B, S_k, d_I) or, with block_table, the pool
  * (num_blocks, page_size, d_I) of any page size, strides k_strides in elements -- at key indices clamp(cache_seqlens[b], 0, capacity)
