@@ -20,7 +20,8 @@ from .flash_attention_wrappers import (apply_rotary, dequantize_kv_cache, flash_
                                        check_mla_sparse_varlen_args, flash_attention_mla_sparse_varlen_decode_forward,
                                        check_mla_indexer_varlen_args, mla_indexer_logits_varlen, topk_indices_varlen,
                                        flash_attention_mla_indexer_topk_varlen, quantize_mla_cache_ds, dequantize_mla_cache_ds,
-                                       check_mla_indexer_append_args, mla_indexer_append, mla_indexer_append_varlen)
+                                       check_mla_indexer_append_args, mla_indexer_append, mla_indexer_append_varlen,
+                                       hadamard_rotate, mla_indexer_prepare_queries, mla_indexer_prepare_queries_varlen)
 
 __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarlen", "convert_triton_dtype", "MIN_TENSOR_SIZE",
            "flash_attention_forward", "flash_attention_backward", "flash_attention_varlen_forward",
@@ -34,4 +35,4 @@ __all__ = ["FlashAttention", "FlashAttentionDeterministic", "FlashAttentionVarle
            "flash_attention_mla_sparse_varlen_decode_forward", "check_mla_sparse_varlen_args", "mla_indexer_logits_varlen",
            "topk_indices_varlen", "flash_attention_mla_indexer_topk_varlen", "check_mla_indexer_varlen_args",
            "quantize_mla_cache_ds", "dequantize_mla_cache_ds", "mla_indexer_append", "mla_indexer_append_varlen",
-           "check_mla_indexer_append_args"]
+           "check_mla_indexer_append_args", "hadamard_rotate", "mla_indexer_prepare_queries", "mla_indexer_prepare_queries_varlen"]

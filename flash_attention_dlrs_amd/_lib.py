@@ -4,6 +4,7 @@ Replaces the `fwd_kernel[grid](...)` Triton launch of the reference
 (src/flash_attention_torch.py:59-74, src/flash_attention_wrappers.py:46-61).
 """
 import ctypes
+import gc
 import os
 
 import torch
@@ -64,7 +65,9 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_topk_indices_varlen", "fa2_mla_indexer_topk_varlen", "fa2_mla_indexer_varlen_workspace_bytes",
            "fa2_fwd_kvcache_mla_sparse_ds", "fa2_fwd_kvcache_mla_sparse_varlen_ds", "fa2_kvcache_mla_append_ds",
            "fa2_kvcache_mla_append_varlen_ds", "fa2_mla_indexer_append", "fa2_mla_indexer_append_varlen",
-           "fa2_mla_indexer_logits_q8", "fa2_mla_indexer_topk_q8", "fa2_mla_indexer_logits_varlen_q8", "fa2_mla_indexer_topk_varlen_q8")
+           "fa2_mla_indexer_logits_q8", "fa2_mla_indexer_topk_q8", "fa2_mla_indexer_logits_varlen_q8", "fa2_mla_indexer_topk_varlen_q8",
+           "fa2_mla_indexer_prepare_q", "fa2_mla_indexer_prepare_q_varlen", "fa2_mla_indexer_append_rot",
+           "fa2_mla_indexer_append_varlen_rot")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -259,6 +262,21 @@ def lib():
         l.fa2_mla_indexer_append.argtypes = [vp, i64p, vp, i64p, vp, ctypes.c_int64, vp, i64p, vp, vp] + [ctypes.c_int32] * 9 + [vp]
         l.fa2_mla_indexer_append_varlen.restype = ctypes.c_int
         l.fa2_mla_indexer_append_varlen.argtypes = [vp, i64p, vp, i64p, vp, ctypes.c_int64, vp, i64p, vp, vp, vp] + [ctypes.c_int32] * 10 + [vp]
+        # ... rotated and transformed on the way (the _rot forms): the tables, their row strides, S_rot rotary_dim interleaved hadamard
+        # after the lengths
+        rot = [vp, vp, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4
+        l.fa2_mla_indexer_append_rot.restype = ctypes.c_int
+        l.fa2_mla_indexer_append_rot.argtypes = [vp, i64p, vp, i64p, vp, ctypes.c_int64, vp, i64p, vp, vp] + rot + [ctypes.c_int32] * 9 + [vp]
+        l.fa2_mla_indexer_append_varlen_rot.restype = ctypes.c_int
+        l.fa2_mla_indexer_append_varlen_rot.argtypes = [vp, i64p, vp, i64p, vp, ctypes.c_int64, vp, i64p, vp, vp, vp] + rot + \
+            [ctypes.c_int32] * 10 + [vp]
+        # the query preparation: q_idx weights + strides, the two outputs, (cu_seqlens_q,) cache_seqlens, the tables as above,
+        # weight_scale, B H_I N_q (total_q max_seqlen_q) d_I dtype out_dtype, stream
+        l.fa2_mla_indexer_prepare_q.restype = ctypes.c_int
+        l.fa2_mla_indexer_prepare_q.argtypes = [vp, i64p, vp, i64p, vp, vp, vp] + rot + [ctypes.c_float] + [ctypes.c_int32] * 6 + [vp]
+        l.fa2_mla_indexer_prepare_q_varlen.restype = ctypes.c_int
+        l.fa2_mla_indexer_prepare_q_varlen.argtypes = [vp, i64p, vp, i64p, vp, vp, vp, vp] + rot + [ctypes.c_float] + \
+            [ctypes.c_int32] * 7 + [vp]
         # ... fused with the latent-cache decode: Q KV O L + their strides, lengths in / out, table + stride, descale + strides,
         # c_new pe_new + strides, rotary tables + row strides, S_rot rotary_dim interleaved, q_rot, B H H_kv N_q N_new S_k num_blocks
         # page_size max_blocks d d_v dtype kv_dtype causal, scale, window, num_splits, workspace + its size, variant, stream
@@ -340,6 +358,12 @@ def lib():
         l.fa2_version.restype = ctypes.c_char_p
         l.fa2_last_error.restype = ctypes.c_char_p
         _lib = l
+        # One full collection now, at load.  With torch imported a full collection of the interpreter takes 35 - 40 ms (measured),
+        # and when the next one falls is a matter of how many objects the imports have allocated: a few lines more in this package
+        # moved it INTO a loop of 50 launches of 0.45 ms, which then read 60 ms for 22 (the kernels' own times unchanged).  After
+        # this call the young generations are empty and the old one is counted as long-lived, so the next full collection waits
+        # for a quarter as many new objects as the process holds -- not for some launch a few hundred allocations away.
+        gc.collect()
     return _lib
 
 
@@ -1109,11 +1133,39 @@ def fa2_kvcache_mla_append_ds(KV, c_new, pe_new, cache_seqlens, seqlens_out, dty
                 *rot, cu_new.numel() - 1, H_kv, total_new, int(max_new), *tail)
 
 
+def _rot_args(rotary_cos, rotary_sin, rotary_interleaved, hadamard):
+    """The tables, their row strides, S_rot, rotary_dim, interleaved and hadamard as the front end's entry points take them."""
+    if rotary_cos is None:
+        return (None, None, 0, 0, 0, 0, 0, int(bool(hadamard)))
+    return (rotary_cos.data_ptr(), rotary_sin.data_ptr(), rotary_cos.stride(0), rotary_sin.stride(0), rotary_cos.shape[0],
+            2 * rotary_cos.shape[1], int(bool(rotary_interleaved)), int(bool(hadamard)))
+
+
+def fa2_mla_indexer_prepare_q(q_idx, weights, q_out, weights_out, cache_seqlens, dtype_enum, out_dtype_enum, weight_scale=1.0,
+                              rotary_cos=None, rotary_sin=None, rotary_interleaved=False, hadamard=True, cu_q=None, max_q=None):
+    """Launch the indexer's query preparation (include/fa2_fwd.h fa2_mla_indexer_prepare_q; with cu_q and max_q the packed
+    fa2_mla_indexer_prepare_q_varlen) on the current stream of q_idx's device: q_idx (B, H_I, N_q, 128) or packed (total_q, H_I, 128),
+    weights float32 in q_idx's leading shape, the contiguous outputs in those shapes."""
+    if q_idx.device.type != "cuda":
+        raise NotImplementedError("q_idx, weights must be on the same CUDA device")
+    head = (q_idx.data_ptr(), _i64(q_idx.stride()), weights.data_ptr(), _i64(weights.stride()), q_out.data_ptr(), weights_out.data_ptr())
+    rot = _rot_args(rotary_cos, rotary_sin, rotary_interleaved, hadamard)
+    tail = (q_idx.shape[-1], int(dtype_enum), int(out_dtype_enum), _raw_stream(q_idx.device.index))
+    if cu_q is None:
+        B, H_I, N_q, _ = q_idx.shape
+        _launch(lib().fa2_mla_indexer_prepare_q, q_idx, *head, _ptr(cache_seqlens), *rot, float(weight_scale), B, H_I, N_q, *tail)
+    else:
+        total_q, H_I, _ = q_idx.shape
+        _launch(lib().fa2_mla_indexer_prepare_q_varlen, q_idx, *head, cu_q.data_ptr(), _ptr(cache_seqlens), *rot, float(weight_scale),
+                cu_q.numel() - 1, H_I, total_q, int(max_q), *tail)
+
+
 def fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, seqlens_out, dtype_enum, k_dtype_enum, block_table=None, cu_new=None,
-                           max_new=None):
+                           max_new=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, hadamard=False):
     """Launch the index-key append (include/fa2_fwd.h fa2_mla_indexer_append; with cu_new and max_new the packed
     fa2_mla_indexer_append_varlen) on the current stream of k_new's device: k_new (B, N_new, d_I) or packed (total_new, d_I) goes into
-    k_idx (B, S_k, d_I) or the pool (num_blocks, page_size, d_I), quantised with one scale per row into k_scale where k_idx is fp8."""
+    k_idx (B, S_k, d_I) or the pool (num_blocks, page_size, d_I), quantised with one scale per row into k_scale where k_idx is fp8.
+    With rotary tables or hadamard: the _rot entry points, the row rotated and transformed before it is stored."""
     if k_new.device.type != "cuda":
         raise NotImplementedError("k_idx, k_new must be on the same CUDA device")
     if block_table is None:
@@ -1123,12 +1175,14 @@ def fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, seqlens_out, dt
     head = (k_idx.data_ptr(), _i64(k_idx.stride()), _ptr(k_scale), None if k_scale is None else _i64(k_scale.stride()), tb_ptr, tb_st,
             k_new.data_ptr(), _i64(k_new.stride()))
     tail = (S_k, nb, ps, mb, k_idx.shape[2], int(dtype_enum), int(k_dtype_enum), _raw_stream(k_new.device.index))
+    prep = rotary_cos is not None or hadamard
+    rot = _rot_args(rotary_cos, rotary_sin, rotary_interleaved, hadamard) if prep else ()
     if cu_new is None:
-        _launch(lib().fa2_mla_indexer_append, k_new, *head, cache_seqlens.data_ptr(), seqlens_out.data_ptr(), k_new.shape[0],
-                k_new.shape[1], *tail)
+        _launch(lib().fa2_mla_indexer_append_rot if prep else lib().fa2_mla_indexer_append, k_new, *head, cache_seqlens.data_ptr(),
+                seqlens_out.data_ptr(), *rot, k_new.shape[0], k_new.shape[1], *tail)
     else:
-        _launch(lib().fa2_mla_indexer_append_varlen, k_new, *head, cu_new.data_ptr(), cache_seqlens.data_ptr(), seqlens_out.data_ptr(),
-                cu_new.numel() - 1, k_new.shape[0], int(max_new), *tail)
+        _launch(lib().fa2_mla_indexer_append_varlen_rot if prep else lib().fa2_mla_indexer_append_varlen, k_new, *head, cu_new.data_ptr(),
+                cache_seqlens.data_ptr(), seqlens_out.data_ptr(), *rot, cu_new.numel() - 1, k_new.shape[0], int(max_new), *tail)
 
 
 def fa2_fwd_kvcache_mla_append(Q, KV, O, L, c_new, pe_new, cache_seqlens, seqlens_out, dtype_enum, kv_dtype_enum, block_table=None,

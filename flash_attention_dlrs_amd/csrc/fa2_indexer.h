@@ -64,3 +64,30 @@ bool fa2_indexer_mfma8_v_supports(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_mfma8_v(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_generic_q8(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_generic_q8_v(const Fa2IndexerProblem &p);
+
+// The indexer's front end (fa2_indexer_prep.hip; include/fa2_fwd.h fa2_mla_indexer_prepare_q, fa2_mla_indexer_append_rot and their
+// packed forms): rotary, the 128-point Hadamard transform and the row quantisation of index queries and keys, one launch each.
+// Query form: arguments already checked; strides in elements, the packed call's in the fixed call's order with a batch stride of 0 and
+// N_q holding max_q, as Fa2IndexerProblem's.  It is the kernel's argument as well.
+struct Fa2IndexerPrepProblem {
+    const void *Q;    // (B, H, N_q, 128) in `dtype`, unit column stride
+    const float *W;   // (B, H, N_q)
+    void *QO;         // contiguous (B, H, N_q, 128) in `out_dtype`; packed: (total_q, H, 128)
+    float *WO;        // contiguous (B, H, N_q); packed: (total_q, H)
+    int64_t qs[3], ws[3];
+    const int32_t *seqlens;  // read with tables only
+    const void *cos, *sin;   // (S_rot, rotary_dim / 2) in `dtype`, unit last stride, or both null
+    int64_t cos_stride, sin_stride;
+    int32_t S_rot, rotary_dim, interleaved, hadamard;
+    float weight_scale;
+    int32_t B, H, N_q;
+    int32_t dtype, out_dtype;
+    const int32_t *cu_q;  // packed: non-null, with total_q and max_q
+    int32_t total_q, max_q;
+    hipStream_t stream;
+};
+int fa2_launch_indexer_prep_q(const Fa2IndexerPrepProblem &p);
+// Key form: the index-key append's problem (fa2_decode.h; mode FA2_APPENDQ_IDX8 or _COPY, d = 128, 16-bit src with a unit column
+// stride) with its rotary fields set or `hadamard`, the row transformed before it is stored.
+struct Fa2AppendQProblem;
+int fa2_launch_indexer_prep_k(const Fa2AppendQProblem &p, bool hadamard);

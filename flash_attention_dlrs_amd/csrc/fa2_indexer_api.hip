@@ -2,7 +2,9 @@
 // and fa2_mla_indexer_workspace_bytes, their packed (_varlen) forms and the fp8-query (_q8) forms of the four score-bearing calls.  One call struct and one check order of its own, beside the attention calls' DecodeCall
 // (fa2_decode_api.hip): every check runs before any launch, then the score kernel of the form the variant names -- AUTO: the matrix
 // form where it runs, else the VALU form -- and the selection, on the call's stream.  fa2_mla_indexer_append and _varlen, the write side of
-// the index-key cache, are here too: their checks, then the quantising append kernel (fa2_decode_append_q.hip).
+// the index-key cache, are here too: their checks, then the quantising append kernel (fa2_decode_append_q.hip).  So is the indexer's front
+// end -- fa2_mla_indexer_prepare_q, fa2_mla_indexer_append_rot and their packed forms: rotary, the Hadamard transform and the row
+// quantisation of queries and keys (fa2_indexer_prep.hip).
 #include "fa2_indexer.h"
 #include "fa2_decode.h"
 
@@ -259,7 +261,47 @@ struct IndexAppendCall {
     const int32_t *cu_seqlens_new = nullptr;  // packed: non-null
     int32_t total_new = 0, max_seqlen_new = 0;
     bool packed = false;
+    // the _rot entry points: the row is rotated and transformed before it is stored (fa2_indexer_prep.hip)
+    const void *rotary_cos = nullptr, *rotary_sin = nullptr;
+    int64_t rotary_cos_stride = 0, rotary_sin_stride = 0;
+    int32_t S_rot = 0, rotary_dim = 0, rotary_interleaved = 0, hadamard = 0;
 };
+
+// The rotary tables of the front end's calls: both or neither, rotary_dim even in [2, 128].
+int check_prep_rotary(const char *who, const void *cos, const void *sin, int64_t cs, int64_t ss, int32_t S_rot, int32_t rd) {
+    if ((cos == nullptr) != (sin == nullptr)) {
+        fa2_set_error("%s: rotary_cos and rotary_sin go together (null %s)", who, cos ? "rotary_sin" : "rotary_cos");
+        return FA2_ERR_BAD_ARG;
+    }
+    if (!cos) return FA2_OK;
+    if (S_rot < 1 || rd < 2 || rd > 128 || rd % 2 != 0) {
+        fa2_set_error("%s: S_rot must be >= 1 and rotary_dim even in [2, 128] (got S_rot=%d, rotary_dim=%d)", who, S_rot, rd);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (cs < 0 || ss < 0) {
+        fa2_set_error("%s: negative strides are not supported (rotary_cos_stride, rotary_sin_stride)", who);
+        return FA2_ERR_BAD_ARG;
+    }
+    return FA2_OK;
+}
+
+// What the front end's kernels take: rows of 128 columns in f16 / bf16 with a unit column stride.  `what`: the rows' argument.
+int check_prep_rows(const char *who, const char *what, int32_t d_I, int32_t dtype_enum, int64_t col_stride) {
+    if (d_I != 128) {
+        fa2_set_error("%s: d_I=%d: rotary and the Hadamard transform take d_I = 128", who, d_I);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (dtype_enum != FA2_DTYPE_F16 && dtype_enum != FA2_DTYPE_BF16) {
+        fa2_set_error("%s: dtype_enum %d (%s) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16 (f32 rows are not rotated or transformed)", who,
+                      dtype_enum, what);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (col_stride != 1) {
+        fa2_set_error("%s: %s needs a unit column stride (got %lld)", who, what, (long long)col_stride);
+        return FA2_ERR_BAD_ARG;
+    }
+    return FA2_OK;
+}
 
 // Every check of the index-key append, before any launch; then the launch.
 int run_index_append(const IndexAppendCall &c) {
@@ -324,6 +366,10 @@ int run_index_append(const IndexAppendCall &c) {
         fa2_set_error("%s: d_I=%d must be in [1, 576]", who, c.d_I);
         return FA2_ERR_UNSUPPORTED;
     }
+    if (int rc = check_prep_rotary(who, c.rotary_cos, c.rotary_sin, c.rotary_cos_stride, c.rotary_sin_stride, c.S_rot, c.rotary_dim)) return rc;
+    const bool prep = c.rotary_cos || c.hadamard;
+    if (prep)
+        if (int rc = check_prep_rows(who, "k_new", c.d_I, c.dtype_enum, c.k_new_strides[2])) return rc;
     Fa2AppendQProblem q{};
     q.mode = quant ? FA2_APPENDQ_IDX8 : FA2_APPENDQ_COPY;
     q.cache = c.k_idx;
@@ -342,7 +388,98 @@ int run_index_append(const IndexAppendCall &c) {
     q.cu_new = c.packed ? c.cu_seqlens_new : nullptr;
     q.total_new = c.packed ? c.total_new : 0; q.max_new = c.packed ? c.max_seqlen_new : 0;
     q.stream = (hipStream_t)c.hip_stream;
-    return fa2_launch_decode_append_q(q);
+    if (!prep) return fa2_launch_decode_append_q(q);
+    q.cos = c.rotary_cos; q.sin = c.rotary_sin;
+    q.cos_stride = c.rotary_cos_stride; q.sin_stride = c.rotary_sin_stride;
+    q.S_rot = c.S_rot; q.rotary_dim = c.rotary_cos ? c.rotary_dim : 0; q.interleaved = c.rotary_interleaved != 0;
+    return fa2_launch_indexer_prep_k(q, c.hadamard != 0);
+}
+
+// The arguments of fa2_mla_indexer_prepare_q; the packed call brings its strides in the fixed call's order (PackedStrides) and N_q = 0.
+struct PrepareQCall {
+    const void *q_idx;
+    const int64_t *q_strides;
+    const float *weights;
+    const int64_t *w_strides;
+    void *q_out;
+    float *weights_out;
+    const int32_t *cache_seqlens;
+    const void *rotary_cos, *rotary_sin;
+    int64_t rotary_cos_stride, rotary_sin_stride;
+    int32_t S_rot, rotary_dim, rotary_interleaved, hadamard;
+    float weight_scale;
+    int32_t B, H_I, N_q, d_I, dtype_enum, out_dtype_enum;
+    void *hip_stream;
+    const int32_t *cu_seqlens_q = nullptr;  // packed: non-null
+    int32_t total_q = 0, max_seqlen_q = 0;
+    bool packed = false;
+};
+
+// Every check of the query preparation, before any launch; then the launch.
+int run_prepare_q(const PrepareQCall &c) {
+    const char *who = c.packed ? "mla indexer prepare queries varlen" : "mla indexer prepare queries";
+    const void *ptrs[6] = {c.q_idx, c.q_strides, c.weights, c.w_strides, c.q_out, c.weights_out};
+    const char *names[6] = {"q_idx", "q_strides", "weights", "w_strides", "q_out", "weights_out"};
+    for (int t = 0; t < 6; ++t)
+        if (!ptrs[t]) {
+            fa2_set_error("%s: null %s", who, names[t]);
+            return FA2_ERR_BAD_ARG;
+        }
+    for (int k = 0; k < 4; ++k)
+        if (c.q_strides[k] < 0 || (k < 3 && c.w_strides[k] < 0)) {
+            fa2_set_error("%s: negative strides are not supported (q_strides, w_strides)", who);
+            return FA2_ERR_BAD_ARG;
+        }
+    if (c.B < 1 || c.B > 65535 || c.H_I < 1 || c.H_I > 65536) {
+        fa2_set_error("%s: B must be in [1, 65535] and H_I in [1, 65536] (got %d, %d)", who, c.B, c.H_I);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.packed) {
+        if (!c.cu_seqlens_q) {
+            fa2_set_error("%s: null cu_seqlens_q", who);
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.total_q < 1 || c.total_q > (1 << 28) || c.max_seqlen_q < 1 || c.max_seqlen_q > (1 << 28)) {
+            fa2_set_error("%s: total_q and max_seqlen_q must be in [1, 2^28] (got %d, %d)", who, c.total_q, c.max_seqlen_q);
+            return FA2_ERR_BAD_ARG;
+        }
+    } else if (c.N_q < 1 || (int64_t)c.B * c.N_q > (1 << 28)) {
+        fa2_set_error("%s: N_q must be >= 1 and B * N_q <= 2^28 (got B=%d, N_q=%d)", who, c.B, c.N_q);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (int rc = check_prep_rows(who, "q_idx", c.d_I, c.dtype_enum, c.q_strides[3])) return rc;
+    if (c.out_dtype_enum != c.dtype_enum && !is_fp8(c.out_dtype_enum)) {
+        fa2_set_error("%s: out_dtype_enum %d must be dtype_enum or FA2_DTYPE_F8E4M3 / FA2_DTYPE_F8E5M2", who, c.out_dtype_enum);
+        return FA2_ERR_UNSUPPORTED;
+    }
+    if (int rc = check_prep_rotary(who, c.rotary_cos, c.rotary_sin, c.rotary_cos_stride, c.rotary_sin_stride, c.S_rot, c.rotary_dim)) return rc;
+    if (c.rotary_cos && !c.cache_seqlens) {
+        fa2_set_error("%s: null cache_seqlens with rotary tables (a query's position is counted from its sequence's length)", who);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (!(c.weight_scale - c.weight_scale == 0.0f)) {
+        fa2_set_error("%s: weight_scale must be finite", who);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (((uintptr_t)c.q_out & 15) != 0) {
+        fa2_set_error("%s: q_out must be 16-byte aligned", who);
+        return FA2_ERR_BAD_ARG;
+    }
+    Fa2IndexerPrepProblem p{};
+    p.Q = c.q_idx; p.W = c.weights; p.QO = c.q_out; p.WO = c.weights_out;
+    for (int k = 0; k < 3; ++k) { p.qs[k] = c.q_strides[k]; p.ws[k] = c.w_strides[k]; }
+    p.seqlens = c.cache_seqlens;
+    p.cos = c.rotary_cos; p.sin = c.rotary_sin;
+    p.cos_stride = c.rotary_cos_stride; p.sin_stride = c.rotary_sin_stride;
+    p.S_rot = c.S_rot; p.rotary_dim = c.rotary_cos ? c.rotary_dim : 0; p.interleaved = c.rotary_interleaved != 0;
+    p.hadamard = c.hadamard != 0;
+    p.weight_scale = c.weight_scale;
+    p.B = c.B; p.H = c.H_I; p.N_q = c.packed ? c.max_seqlen_q : c.N_q;
+    p.dtype = c.dtype_enum; p.out_dtype = c.out_dtype_enum;
+    p.cu_q = c.packed ? c.cu_seqlens_q : nullptr;
+    p.total_q = c.packed ? c.total_q : 0; p.max_q = c.packed ? c.max_seqlen_q : 0;
+    p.stream = (hipStream_t)c.hip_stream;
+    return fa2_launch_indexer_prep_q(p);
 }
 
 }  // namespace
@@ -369,6 +506,57 @@ int fa2_mla_indexer_append_varlen(void *k_idx, const int64_t k_strides[3], float
     return run_index_append({k_idx, k_strides, k_scale, k_scale_strides, block_table, block_table_stride, k_new,
                              PackedStrides::rows3(k_new_strides, ns), cache_seqlens, seqlens_out, B, 0, S_k, num_blocks, page_size,
                              max_blocks, d_I, dtype_enum, k_dtype_enum, hip_stream, cu_seqlens_new, total_new, max_seqlen_new, true});
+}
+
+int fa2_mla_indexer_append_rot(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                               const int32_t *block_table, int64_t block_table_stride, const void *k_new, const int64_t k_new_strides[3],
+                               const int32_t *cache_seqlens, int32_t *seqlens_out, const void *rotary_cos, const void *rotary_sin,
+                               int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim,
+                               int32_t rotary_interleaved, int32_t hadamard, int32_t B, int32_t N_new, int32_t S_k, int32_t num_blocks,
+                               int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum,
+                               void *hip_stream) {
+    return run_index_append({k_idx, k_strides, k_scale, k_scale_strides, block_table, block_table_stride, k_new, k_new_strides,
+                             cache_seqlens, seqlens_out, B, N_new, S_k, num_blocks, page_size, max_blocks, d_I, dtype_enum, k_dtype_enum,
+                             hip_stream, nullptr, 0, 0, false, rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot,
+                             rotary_dim, rotary_interleaved, hadamard});
+}
+
+int fa2_mla_indexer_append_varlen_rot(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                                      const int32_t *block_table, int64_t block_table_stride, const void *k_new,
+                                      const int64_t k_new_strides[2], const int32_t *cu_seqlens_new, const int32_t *cache_seqlens,
+                                      int32_t *seqlens_out, const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                                      int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                      int32_t hadamard, int32_t B, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                                      int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d_I, int32_t dtype_enum,
+                                      int32_t k_dtype_enum, void *hip_stream) {
+    int64_t ns[3];
+    return run_index_append({k_idx, k_strides, k_scale, k_scale_strides, block_table, block_table_stride, k_new,
+                             PackedStrides::rows3(k_new_strides, ns), cache_seqlens, seqlens_out, B, 0, S_k, num_blocks, page_size,
+                             max_blocks, d_I, dtype_enum, k_dtype_enum, hip_stream, cu_seqlens_new, total_new, max_seqlen_new, true,
+                             rotary_cos, rotary_sin, rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved,
+                             hadamard});
+}
+
+int fa2_mla_indexer_prepare_q(const void *q_idx, const int64_t q_strides[4], const float *weights, const int64_t w_strides[3],
+                              void *q_out, float *weights_out, const int32_t *cache_seqlens, const void *rotary_cos,
+                              const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride, int32_t S_rot,
+                              int32_t rotary_dim, int32_t rotary_interleaved, int32_t hadamard, float weight_scale, int32_t B,
+                              int32_t H_I, int32_t N_q, int32_t d_I, int32_t dtype_enum, int32_t out_dtype_enum, void *hip_stream) {
+    return run_prepare_q({q_idx, q_strides, weights, w_strides, q_out, weights_out, cache_seqlens, rotary_cos, rotary_sin,
+                          rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, hadamard, weight_scale, B, H_I,
+                          N_q, d_I, dtype_enum, out_dtype_enum, hip_stream});
+}
+
+int fa2_mla_indexer_prepare_q_varlen(const void *q_idx, const int64_t q_strides[3], const float *weights, const int64_t w_strides[2],
+                                     void *q_out, float *weights_out, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                     const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                                     int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                     int32_t hadamard, float weight_scale, int32_t B, int32_t H_I, int32_t total_q,
+                                     int32_t max_seqlen_q, int32_t d_I, int32_t dtype_enum, int32_t out_dtype_enum, void *hip_stream) {
+    PackedStrides s;
+    return run_prepare_q({q_idx, s.q4(q_strides), weights, s.w3(w_strides), q_out, weights_out, cache_seqlens, rotary_cos, rotary_sin,
+                          rotary_cos_stride, rotary_sin_stride, S_rot, rotary_dim, rotary_interleaved, hadamard, weight_scale, B, H_I, 0,
+                          d_I, dtype_enum, out_dtype_enum, hip_stream, cu_seqlens_q, total_q, max_seqlen_q, true});
 }
 
 int fa2_mla_indexer_logits(const void *q_idx, const float *weights, const void *k_idx, const float *k_scale, float *logits,

@@ -3,6 +3,8 @@
 flash_attention_forward(Q, K, V, dev) -> (O, L) is the entry point of the reference's correctness
 script (src/test_correctness.py:34) and the only place the log2-domain log-sum-exp L is exposed.
 """
+import math
+
 import torch
 
 from . import _lib, autotune
@@ -1162,32 +1164,145 @@ def check_mla_indexer_append_args(k_idx, k_new, cache_seqlens, k_scale=None, blo
             raise ValueError(f"{who}: {name} with negative strides is not supported")
 
 
-def mla_indexer_append(k_idx, k_new, cache_seqlens, *, k_scale=None, block_table=None):
+def hadamard_rotate(x):
+    """The 128-point Hadamard transform of the indexer's front end, in plain torch on any device: the meaning of hadamard=True in
+    mla_indexer_prepare_queries / mla_indexer_append and the yardstick of their tests, bit for bit.  x (..., 128) in float16 /
+    bfloat16 (any floating dtype runs) -> H x / sqrt(128) in x.dtype, H the natural-order (Sylvester) Walsh-Hadamard matrix.  In
+    float32 (float64 for float64 x): seven butterfly stages of stride s = 1, 2, 4, ..., 64 in that order, every pair (c, c + s) with bit s
+    of c clear becoming (a + b, a - b), each result rounded on its own; one multiplication by float32(128 ** -0.5); one rounding to
+    x.dtype.  A stage is a set of independent additions, so a kernel may visit its pairs in any order and still give these bits."""
+    if not isinstance(x, torch.Tensor) or not x.dtype.is_floating_point or x.dim() < 1 or x.shape[-1] != 128:
+        raise ValueError(f"hadamard_rotate: x must be a floating-point tensor (..., 128), got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    wide = torch.float64 if x.dtype == torch.float64 else torch.float32
+    h = x.to(wide)
+    for k in range(7):
+        h = h.reshape(*x.shape[:-1], 64 >> k, 2, 1 << k)  # column c = (i, bit k of c, c mod 2^k)
+        a, b = h[..., 0, :], h[..., 1, :]
+        h = torch.stack((a + b, a - b), dim=-2)
+    return (h.reshape(x.shape) * torch.tensor(128 ** -0.5, dtype=wide, device=x.device)).to(x.dtype)
+
+
+def _check_prep_rows(who, name, t, rotary_cos, rotary_sin):
+    """The rows the indexer's front end rotates or transforms: `t`, called `name`, (..., 128) in f16 / bf16 with a unit column stride;
+    the tables as the cache appends take them, rotary_dim <= 128."""
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError(f"{who}: rotary_cos and rotary_sin go together")
+    if t.shape[-1] != 128:
+        raise ValueError(f"{who}: {name} needs d_I = 128 under hadamard=True or rotary_cos / rotary_sin, got d_I = {t.shape[-1]}")
+    if t.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{who}: {name} must be float16 or bfloat16 under hadamard=True or rotary_cos / rotary_sin, got {t.dtype}")
+    if t.stride(-1) != 1:
+        raise ValueError(f"{who}: {name} needs a unit column stride, got strides {tuple(t.stride())}")
+    if rotary_cos is not None:
+        if isinstance(rotary_cos, torch.Tensor) and rotary_cos.dim() == 2 and 2 * rotary_cos.shape[1] > 128:
+            raise ValueError(f"{who}: rotary_dim = {2 * rotary_cos.shape[1]} must be even and <= 128 (rotary_cos, rotary_sin are "
+                             f"(S_rot, rotary_dim / 2))")
+        _check_rotary_tables(rotary_cos, rotary_sin, 128, "d_I = 128", t, name)
+
+
+def mla_indexer_append(k_idx, k_new, cache_seqlens, *, k_scale=None, block_table=None, rotary_cos=None, rotary_sin=None,
+                       rotary_interleaved=False, hadamard=False):
     """The write side of the indexer's key cache (include/fa2_fwd.h fa2_mla_indexer_append) -> new_seqlens, int32 (B,).  k_idx is the
     cache flash_attention_mla_indexer_topk reads, (B, S_k, d_I) or with block_table the pool (num_blocks, page_size, d_I) of any page
-    size; k_new (B, N_new, d_I), any strides, already rotated and transformed as the indexer expects (this call applies neither).  Token
-    t of sequence b becomes the row at key index clamp(cache_seqlens[b], 0, capacity) + t, IN PLACE; tokens past the capacity are
+    size; k_new (B, N_new, d_I), any strides, already rotated and transformed as the indexer expects (this call applies neither unless
+    the keywords at the end ask for it).  Token t of sequence b becomes the row at key index clamp(cache_seqlens[b], 0, capacity) + t, IN PLACE; tokens past the capacity are
     dropped, new_seqlens = min(cache_seqlens + N_new, capacity), cache_seqlens is not modified.  An fp8 k_idx (e4m3 / e5m2) takes
     float16 / bfloat16 k_new and needs k_scale, float32 shaped like the cache's rows, any strides: the byte row and the scale written
     are quantize_index_keys(row, k_idx.dtype) bit for bit (on the CPU, whose division is correctly rounded) for rows with amax 0 or
     >= 2^-64 -- one power-of-two scale per row, 1 for a row of zeros.  A k_idx in k_new's dtype (f16, bf16, f32) takes k_scale=None and
-    the rows are copied bit for bit.  One launch, lengths included."""
+    the rows are copied bit for bit.  One launch, lengths included.
+    rotary_cos / rotary_sin ((S_rot, rotary_dim / 2) in k_new's dtype, rotary_dim even and <= 128), rotary_interleaved, hadamard:
+    the model's preparation of a key inside the same launch (fa2_mla_indexer_append_rot; d_I = 128, f16 / bf16 k_new with a unit
+    column stride).  The row stored is then h = hadamard_rotate(apply_rotary(row, cos, sin, key index, interleaved)) -- either step
+    alone where only one is asked for -- quantised as above into an fp8 k_idx, as it is into a 16-bit one."""
     check_mla_indexer_append_args(k_idx, k_new, cache_seqlens, k_scale, block_table)
+    if rotary_cos is not None or rotary_sin is not None or hadamard:
+        _check_prep_rows("mla indexer append", "k_new", k_new, rotary_cos, rotary_sin)
     new_seqlens = torch.empty_like(cache_seqlens)
     _lib.fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, new_seqlens, convert_triton_dtype(k_new.dtype),
-                                convert_triton_dtype(k_idx.dtype), block_table=block_table)
+                                convert_triton_dtype(k_idx.dtype), block_table=block_table, rotary_cos=rotary_cos, rotary_sin=rotary_sin,
+                                rotary_interleaved=rotary_interleaved, hadamard=hadamard)
     return new_seqlens
 
 
-def mla_indexer_append_varlen(k_idx, k_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, *, k_scale=None, block_table=None):
+def mla_indexer_append_varlen(k_idx, k_new, cu_seqlens_new, max_seqlen_new, cache_seqlens, *, k_scale=None, block_table=None,
+                              rotary_cos=None, rotary_sin=None, rotary_interleaved=False, hadamard=False):
     """mla_indexer_append for a ragged batch in one launch (fa2_mla_indexer_append_varlen) -> new_seqlens, int32 (B,).  k_new packed
     (total_new, d_I), any strides; cu_seqlens_new and max_seqlen_new as in kvcache_append_varlen: sequence b brings the
-    min(cu[b + 1] - cu[b], max_seqlen_new) rows from cu[b] on, none is legal, rows outside every sequence are not read."""
+    min(cu[b + 1] - cu[b], max_seqlen_new) rows from cu[b] on, none is legal, rows outside every sequence are not read.  The rotary
+    and hadamard keywords are mla_indexer_append's (fa2_mla_indexer_append_varlen_rot)."""
     check_mla_indexer_append_args(k_idx, k_new, cache_seqlens, k_scale, block_table, cu_seqlens_new, max_seqlen_new)
+    if rotary_cos is not None or rotary_sin is not None or hadamard:
+        _check_prep_rows("mla indexer append", "k_new", k_new, rotary_cos, rotary_sin)
     new_seqlens = torch.empty_like(cache_seqlens)
     _lib.fa2_mla_indexer_append(k_idx, k_scale, k_new, cache_seqlens, new_seqlens, convert_triton_dtype(k_new.dtype),
-                                convert_triton_dtype(k_idx.dtype), block_table=block_table, cu_new=cu_seqlens_new, max_new=max_seqlen_new)
+                                convert_triton_dtype(k_idx.dtype), block_table=block_table, cu_new=cu_seqlens_new, max_new=max_seqlen_new,
+                                rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved, hadamard=hadamard)
     return new_seqlens
+
+
+def _prepare_queries(q_idx, weights, cache_seqlens, B, dtype, weight_scale, rotary_cos, rotary_sin, rotary_interleaved, hadamard,
+                     cu_seqlens_q=None, max_seqlen_q=None):
+    """The checks and the launch mla_indexer_prepare_queries and its packed form share; q_idx's leading shape is weights' shape."""
+    who = "mla indexer prepare queries"
+    if dtype is not None and dtype not in FP8_CACHE_DTYPES and dtype != q_idx.dtype:
+        raise ValueError(f"{who}: dtype must be torch.float8_e4m3fn, torch.float8_e5m2 or None (q_idx's own), got {dtype}")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(q_idx.shape[:-1]):
+        raise ValueError(f"{who}: weights must be a float32 tensor shaped like q_idx's rows {tuple(q_idx.shape[:-1])}")
+    _check_prep_rows(who, "q_idx", q_idx, rotary_cos, rotary_sin)
+    if min(q_idx.shape) < 1:
+        raise ValueError(f"{who}: q_idx needs every size >= 1, got {tuple(q_idx.shape)}")
+    if cache_seqlens is not None or rotary_cos is not None:
+        _check_cache_seqlens(cache_seqlens, B, q_idx, "q_idx")
+    if weights.device != q_idx.device:
+        raise ValueError(f"{who}: weights must be on q_idx's device ({q_idx.device}), got {weights.device}")
+    for name, t in (("q_idx", q_idx), ("weights", weights)):
+        if any(s < 0 for s in t.stride()):
+            raise ValueError(f"{who}: {name} with negative strides is not supported")
+    if not isinstance(weight_scale, (int, float)) or isinstance(weight_scale, bool) or not math.isfinite(weight_scale):
+        raise ValueError(f"{who}: weight_scale must be a finite number, got {weight_scale!r}")
+    out_dtype = q_idx.dtype if dtype is None else dtype
+    q_out = torch.empty(q_idx.shape, dtype=out_dtype, device=q_idx.device)
+    weights_out = torch.empty(weights.shape, dtype=torch.float32, device=q_idx.device)
+    _lib.fa2_mla_indexer_prepare_q(q_idx, weights, q_out, weights_out, cache_seqlens, convert_triton_dtype(q_idx.dtype),
+                                   convert_triton_dtype(out_dtype), weight_scale=weight_scale, rotary_cos=rotary_cos,
+                                   rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved, hadamard=hadamard, cu_q=cu_seqlens_q,
+                                   max_q=max_seqlen_q)
+    return q_out, weights_out
+
+
+def mla_indexer_prepare_queries(q_idx, weights, cache_seqlens, *, dtype=torch.float8_e4m3fn, weight_scale=1.0, rotary_cos=None,
+                                rotary_sin=None, rotary_interleaved=False, hadamard=True):
+    """The indexer's front end for the queries in one launch (include/fa2_fwd.h fa2_mla_indexer_prepare_q) -> (q_out, weights_out),
+    exactly what flash_attention_mla_indexer_topk takes.  q_idx (B, H_I, N_q, 128) in float16 / bfloat16, any non-negative strides
+    with a unit column stride; weights float32 (B, H_I, N_q), any strides; cache_seqlens int32 (B,), the lengths AFTER the step's
+    append (None is legal without tables): query qi of sequence b stands at cache_seqlens[b] - N_q + qi, clamped into the tables.
+    Per row: r = apply_rotary(row, rotary_cos, rotary_sin, position, rotary_interleaved) (tables (S_rot, rotary_dim / 2) in q_idx's
+    dtype, rotary_dim even and <= 128; None: r = row), h = hadamard_rotate(r) (hadamard=False: h = r), then
+    (q_out, q_scale) = quantize_index_keys(h, dtype) bit for bit for rows with amax 0 or >= 2^-64 and weights_out = (weights *
+    weight_scale) * q_scale in float32, each product rounded on its own; dtype=None: q_out = h in q_idx's dtype and weights_out =
+    weights * weight_scale.  Both outputs are contiguous.  weight_scale carries the model's softmax_scale * H_I ** -0.5."""
+    if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 4:
+        raise ValueError(f"mla indexer prepare queries: q_idx must be a tensor (B, H_I, N_q, 128), got "
+                         f"{tuple(q_idx.shape) if isinstance(q_idx, torch.Tensor) else type(q_idx).__name__}")
+    return _prepare_queries(q_idx, weights, cache_seqlens, q_idx.shape[0], dtype, weight_scale, rotary_cos, rotary_sin,
+                            rotary_interleaved, hadamard)
+
+
+def mla_indexer_prepare_queries_varlen(q_idx, weights, cu_seqlens_q, max_seqlen_q, cache_seqlens, *, dtype=torch.float8_e4m3fn,
+                                       weight_scale=1.0, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, hadamard=True):
+    """mla_indexer_prepare_queries for packed queries (fa2_mla_indexer_prepare_q_varlen) -> (q_out, weights_out), what
+    flash_attention_mla_indexer_topk_varlen takes.  q_idx (total_q, H_I, 128), weights (total_q, H_I); cu_seqlens_q and max_seqlen_q
+    as in that call: sequence b owns n_q(b) = min(cu[b + 1] - cu[b], max_seqlen_q) rows from cu[b] on, query i of them stands at
+    cache_seqlens[b] - n_q(b) + i.  Rows that no sequence owns are not written: the outputs come from torch.empty."""
+    who = "mla indexer prepare queries"
+    if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 3:
+        raise ValueError(f"{who}: q_idx must be a packed tensor (total_q, H_I, 128), got "
+                         f"{tuple(q_idx.shape) if isinstance(q_idx, torch.Tensor) else type(q_idx).__name__}")
+    B = _check_cu_seqlens_q(who, cu_seqlens_q, max_seqlen_q, q_idx, "q_idx")
+    return _prepare_queries(q_idx, weights, cache_seqlens, B, dtype, weight_scale, rotary_cos, rotary_sin, rotary_interleaved, hadamard,
+                            cu_seqlens_q, max_seqlen_q)
 
 
 def _indexer_capacity(k_idx, block_table):

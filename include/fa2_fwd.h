@@ -1153,6 +1153,69 @@ int fa2_mla_indexer_append_varlen(void *k_idx, const int64_t k_strides[3], float
                                   int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, void *hip_stream);
 
 /*
+ * The indexer's front end: what the model does to index queries and keys before the score kernel reads them, one launch for the
+ * queries and one for the keys (fa2_indexer_prep.hip).  A row x of d_I = 128 columns in dtype_enum (F16 / BF16) at position p becomes
+ *
+ *   1. r = rotary(x) over columns [0, rotary_dim) from column 0 on, at table row clamp(p, 0, S_rot - 1), rounded to dtype_enum -- the
+ *      rotation of fa2_kvcache_append (pairs (i, i + rotary_dim / 2), or (2i, 2i + 1) with rotary_interleaved; every product, sum and
+ *      difference rounded to fp32 on its own).  Null tables: r = x.
+ *   2. h = H r / sqrt(128) with H the natural-order (Sylvester) 128 x 128 Walsh-Hadamard matrix: in fp32, seven butterfly stages of
+ *      stride 1, 2, 4, ..., 64 in that order, each pair (c, c + s) with bit s of c clear becoming (a + b, a - b), every result rounded
+ *      to fp32 on its own; one multiplication by (float)2^-3.5; one rounding to dtype_enum.  hadamard == 0: h = r.
+ *   3. an fp8 destination takes fp8(clamp(h / scale)) with fa2_mla_indexer_append's power-of-two row scale of h (same statement, same
+ *      caveat: rows with amax 0 or >= 2^-64); a destination in dtype_enum takes h and has no scale.
+ *
+ * fa2_mla_indexer_prepare_q: q_idx (B, H_I, N_q, 128) at q_strides (elements, unit column stride), weights fp32 (B, H_I, N_q) at
+ * w_strides; query qi of sequence b stands at p = cache_seqlens[b] - N_q + qi (lengths AFTER the step's append; cache_seqlens is read
+ * with tables only and may be null without them).  q_out is contiguous (B, H_I, N_q, 128) in out_dtype_enum (F8E4M3, F8E5M2 or
+ * dtype_enum), weights_out contiguous fp32 (B, H_I, N_q) = (weights * weight_scale) * scale, each product rounded on its own, the
+ * scale 1 for a 16-bit q_out: exactly the operands of fa2_mla_indexer_topk (_q8 over fp8).  _varlen: q_idx packed (total_q, H_I, 128),
+ * weights (total_q, H_I), the outputs contiguous in those shapes; query i of sequence b stands at cache_seqlens[b] - n_q(b) + i and
+ * rows that no sequence owns are neither read nor written.
+ *
+ * fa2_mla_indexer_append_rot / _varlen_rot: fa2_mla_indexer_append / _varlen with steps 1 - 3 applied to a row before it is stored,
+ * its position the key index clamp(cache_seqlens[b], 0, capacity) + t it is written at.  Lengths, the drop past the capacity, paging
+ * and the packed spans are that call's.  Without tables and with hadamard == 0 it IS that call.
+ *
+ * Errors, all before any launch: FA2_ERR_BAD_ARG for null pointers, negative strides, a column stride other than 1, one table
+ * without the other, tables without cache_seqlens, S_rot < 1, rotary_dim odd or outside [2, 128], negative table strides, sizes out
+ * of range, a non-finite weight_scale; FA2_ERR_UNSUPPORTED for d_I != 128, dtype_enum other than F16 / BF16 and a destination that
+ * is neither fp8 nor dtype_enum.
+ */
+int fa2_mla_indexer_prepare_q(const void *q_idx, const int64_t q_strides[4], const float *weights, const int64_t w_strides[3],
+                              void *q_out, float *weights_out, const int32_t *cache_seqlens,
+                              const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                              int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, int32_t hadamard, float weight_scale,
+                              int32_t B, int32_t H_I, int32_t N_q, int32_t d_I, int32_t dtype_enum, int32_t out_dtype_enum,
+                              void *hip_stream);
+
+int fa2_mla_indexer_prepare_q_varlen(const void *q_idx, const int64_t q_strides[3], const float *weights, const int64_t w_strides[2],
+                                     void *q_out, float *weights_out, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                     const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                                     int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                     int32_t hadamard, float weight_scale, int32_t B, int32_t H_I, int32_t total_q,
+                                     int32_t max_seqlen_q, int32_t d_I, int32_t dtype_enum, int32_t out_dtype_enum, void *hip_stream);
+
+int fa2_mla_indexer_append_rot(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                               const int32_t *block_table, int64_t block_table_stride,
+                               const void *k_new, const int64_t k_new_strides[3],
+                               const int32_t *cache_seqlens, int32_t *seqlens_out,
+                               const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride, int64_t rotary_sin_stride,
+                               int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved, int32_t hadamard,
+                               int32_t B, int32_t N_new, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                               int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, void *hip_stream);
+
+int fa2_mla_indexer_append_varlen_rot(void *k_idx, const int64_t k_strides[3], float *k_scale, const int64_t k_scale_strides[2],
+                                      const int32_t *block_table, int64_t block_table_stride,
+                                      const void *k_new, const int64_t k_new_strides[2],
+                                      const int32_t *cu_seqlens_new, const int32_t *cache_seqlens, int32_t *seqlens_out,
+                                      const void *rotary_cos, const void *rotary_sin, int64_t rotary_cos_stride,
+                                      int64_t rotary_sin_stride, int32_t S_rot, int32_t rotary_dim, int32_t rotary_interleaved,
+                                      int32_t hadamard, int32_t B, int32_t total_new, int32_t max_seqlen_new, int32_t S_k,
+                                      int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                                      int32_t d_I, int32_t dtype_enum, int32_t k_dtype_enum, void *hip_stream);
+
+/*
  * The fused ragged MLA step: fa2_kvcache_mla_append_varlen over cu_seqlens_q (total_new = total_q, max_seqlen_new = max_seqlen_q;
  * c_new, pe_new packed (total_q, H_kv, d_v) / (total_q, H_kv, d - d_v)), then on the same stream fa2_fwd_kvcache_mla_varlen over the
  * updated cache with seqlens_out as its cache_seqlens and, with tables, q_rot (packed, contiguous (total_q, H, d)) as its Q; q_rot
