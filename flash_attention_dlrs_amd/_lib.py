@@ -67,7 +67,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_kvcache_mla_append_varlen_ds", "fa2_mla_indexer_append", "fa2_mla_indexer_append_varlen",
            "fa2_mla_indexer_logits_q8", "fa2_mla_indexer_topk_q8", "fa2_mla_indexer_logits_varlen_q8", "fa2_mla_indexer_topk_varlen_q8",
            "fa2_mla_indexer_prepare_q", "fa2_mla_indexer_prepare_q_varlen", "fa2_mla_indexer_append_rot",
-           "fa2_mla_indexer_append_varlen_rot")
+           "fa2_mla_indexer_append_varlen_rot",
+           "fa2_topk_indices_split", "fa2_topk_indices_varlen_split", "fa2_topk_workspace_bytes", "fa2_topk_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -349,6 +350,16 @@ def lib():
         l.fa2_topk_indices_varlen.argtypes = [vp, i64p, vp, vp] + [ctypes.c_int32] * 6 + [vp, i64p, vp]
         l.fa2_mla_indexer_varlen_workspace_bytes.restype = ctypes.c_int64
         l.fa2_mla_indexer_varlen_workspace_bytes.argtypes = [ctypes.c_int32] * 2
+        # the split-row selection: the selection's lists with num_splits, workspace, workspace_bytes before the stream
+        split = [ctypes.c_int32, vp, ctypes.c_int64, vp]
+        l.fa2_topk_indices_split.restype = ctypes.c_int
+        l.fa2_topk_indices_split.argtypes = l.fa2_topk_indices.argtypes[:-1] + split
+        l.fa2_topk_indices_varlen_split.restype = ctypes.c_int
+        l.fa2_topk_indices_varlen_split.argtypes = l.fa2_topk_indices_varlen.argtypes[:-1] + split
+        l.fa2_topk_workspace_bytes.restype = ctypes.c_int64
+        l.fa2_topk_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
+        l.fa2_topk_num_splits.restype = ctypes.c_int32
+        l.fa2_topk_num_splits.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
         l.fa2_kvcache_workspace_bytes.restype = ctypes.c_int64
         l.fa2_kvcache_workspace_bytes.argtypes = [ctypes.c_int32] * 5
         l.fa2_kvcache_num_splits.restype = ctypes.c_int32
@@ -811,14 +822,29 @@ def fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_
             indices.shape[2], indices.data_ptr(), _i64(indices.stride()), int(variant), _raw_stream(q_idx.device.index))
 
 
-def fa2_topk_indices(logits, indices, cache_seqlens, causal=True):
+def topk_num_splits(rows, S_k, topk):
+    """What num_splits = 0 resolves to for a selection of `rows` rows (B * N_q, or total_q) over S_k keys (fa2_topk_num_splits)."""
+    return int(lib().fa2_topk_num_splits(rows, S_k, topk))
+
+
+def topk_workspace_bytes(rows, num_splits):
+    """Bytes of workspace a split selection needs (fa2_topk_workspace_bytes); 0 for num_splits <= 1."""
+    return int(lib().fa2_topk_workspace_bytes(rows, num_splits))
+
+
+def fa2_topk_indices(logits, indices, cache_seqlens, causal=True, num_splits=None, workspace=None):
     """Launch the selection alone (fa2_topk_indices) on the current stream of logits' device: logits fp32 (B, N_q, S_k), any
-    strides, indices int32 (B, N_q, topk)."""
+    strides, indices int32 (B, N_q, topk).  With num_splits (0: the heuristic) the row-split form (fa2_topk_indices_split): workspace
+    a tensor of topk_workspace_bytes(B * N_q, num_splits) bytes of any contents, or None where the count resolves to 1."""
     if logits.device.type != "cuda":
         raise NotImplementedError("logits must be on a CUDA device")
     B, N_q, S_k = logits.shape
-    _launch(lib().fa2_topk_indices, logits, logits.data_ptr(), _i64(logits.stride()), _ptr(cache_seqlens), B, N_q, S_k, indices.shape[2],
-            int(bool(causal)), indices.data_ptr(), _i64(indices.stride()), _raw_stream(logits.device.index))
+    args = (logits.data_ptr(), _i64(logits.stride()), _ptr(cache_seqlens), B, N_q, S_k, indices.shape[2], int(bool(causal)),
+            indices.data_ptr(), _i64(indices.stride()))
+    if num_splits is None:
+        _launch(lib().fa2_topk_indices, logits, *args, _raw_stream(logits.device.index))
+    else:
+        _launch(lib().fa2_topk_indices_split, logits, *args, int(num_splits), *_workspace_args(workspace), _raw_stream(logits.device.index))
 
 
 def kvcache_mla_sparse_varlen_num_splits(total_q, H, H_kv, topk, d, d_v, dtype_enum):
@@ -921,15 +947,20 @@ def fa2_mla_indexer_topk_varlen(q_idx, weights, k_idx, k_scale, logits, indices,
             indices.shape[1], indices.data_ptr(), _i64(indices.stride()), int(variant), _raw_stream(q_idx.device.index))
 
 
-def fa2_topk_indices_varlen(logits, indices, cu_q, max_q, cache_seqlens, causal=True):
+def fa2_topk_indices_varlen(logits, indices, cu_q, max_q, cache_seqlens, causal=True, num_splits=None, workspace=None):
     """Launch the packed selection alone (fa2_topk_indices_varlen) on the current stream of logits' device: logits fp32
-    (total_q, S_k), any strides, indices int32 (total_q, topk)."""
+    (total_q, S_k), any strides, indices int32 (total_q, topk).  With num_splits the row-split form (fa2_topk_indices_varlen_split),
+    as fa2_topk_indices, rows = total_q."""
     if logits.device.type != "cuda":
         raise NotImplementedError("logits must be on a CUDA device")
     total_q, S_k = logits.shape
-    _launch(lib().fa2_topk_indices_varlen, logits, logits.data_ptr(), _i64(logits.stride()), cu_q.data_ptr(), _ptr(cache_seqlens),
-            cu_q.numel() - 1, total_q, int(max_q), S_k, indices.shape[1], int(bool(causal)), indices.data_ptr(), _i64(indices.stride()),
-            _raw_stream(logits.device.index))
+    args = (logits.data_ptr(), _i64(logits.stride()), cu_q.data_ptr(), _ptr(cache_seqlens), cu_q.numel() - 1, total_q, int(max_q), S_k,
+            indices.shape[1], int(bool(causal)), indices.data_ptr(), _i64(indices.stride()))
+    if num_splits is None:
+        _launch(lib().fa2_topk_indices_varlen, logits, *args, _raw_stream(logits.device.index))
+    else:
+        _launch(lib().fa2_topk_indices_varlen_split, logits, *args, int(num_splits), *_workspace_args(workspace),
+                _raw_stream(logits.device.index))
 
 
 def _append_args(K, k_new, block_table, k_descale, v_descale, rotary_cos, rotary_sin):

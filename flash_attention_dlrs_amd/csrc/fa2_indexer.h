@@ -54,6 +54,14 @@ bool fa2_indexer_mfma16_v_supports(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_mfma16_v(const Fa2IndexerProblem &p);
 int fa2_launch_indexer_generic_v(const Fa2IndexerProblem &p);
 int fa2_launch_topk_indices_v(const Fa2IndexerProblem &p);
+// Split-row selection (fa2_indexer_topk_split.hip, packed: _v; fa2_topk_indices_split): `splits` >= 2 workgroups a row, each over
+// `chunk` positions (a multiple of 1,024, splits * chunk >= S_k), rows <= 65,535; `workspace` 16-byte aligned, of
+// fa2_topk_split_bytes(rows, splits) bytes with any contents.  The same fields of the problem as the selection above.
+constexpr int kTopkBins0 = 2048, kTopkBins1 = 2048, kTopkBins2 = 1024, kTopkBins = kTopkBins0 + kTopkBins1 + kTopkBins2;
+constexpr int kTopkMaxSplits = 256;
+inline int64_t fa2_topk_split_bytes(int64_t rows, int splits) { return rows * (4 * (int64_t)kTopkBins + 8 * (int64_t)splits); }
+int fa2_launch_topk_indices_split(const Fa2IndexerProblem &p, int splits, int chunk, void *workspace);
+int fa2_launch_topk_indices_split_v(const Fa2IndexerProblem &p, int splits, int chunk, void *workspace);
 // fp8 queries (the _q8 entry points, `dtype` and `k_dtype` both fp8).  Matrix form (fa2_indexer_mfma8.hip, FA2_INDEXER_VARIANT_IDX8):
 // 64 index heads of kIdx8QB query positions against 64-key tiles on v_mfma_f32_16x16x128_f8f6f4, fixed and packed (_v); the VALU form's
 // fp8-query instantiations (fa2_indexer_generic_q8.hip, _q8_v), in units of their own so the 16-bit units keep their code.

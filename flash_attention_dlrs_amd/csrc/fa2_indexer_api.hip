@@ -4,7 +4,8 @@
 // form where it runs, else the VALU form -- and the selection, on the call's stream.  fa2_mla_indexer_append and _varlen, the write side of
 // the index-key cache, are here too: their checks, then the quantising append kernel (fa2_decode_append_q.hip).  So is the indexer's front
 // end -- fa2_mla_indexer_prepare_q, fa2_mla_indexer_append_rot and their packed forms: rotary, the Hadamard transform and the row
-// quantisation of queries and keys (fa2_indexer_prep.hip).
+// quantisation of queries and keys (fa2_indexer_prep.hip).  And the selection with a row split over several workgroups
+// (fa2_topk_indices_split, _varlen_split, fa2_topk_workspace_bytes, fa2_topk_num_splits; fa2_indexer_topk_split.hip).
 #include "fa2_indexer.h"
 #include "fa2_decode.h"
 
@@ -33,6 +34,11 @@ struct IndexerCall {
     int32_t total_q = 0;
     // the _q8 entry points: fp8 q_idx AND k_idx, the variants AUTO / GENERIC / IDX8
     bool q8 = false;
+    // the _split entry points of the selection: num_splits as the caller gave it (0: the heuristic) and the workspace
+    bool split = false;
+    int32_t num_splits = 1;
+    void *workspace = nullptr;
+    int64_t workspace_bytes = 0;
 };
 
 // The stride arrays of a packed call in the fixed call's order: {token, head, column} -> {0, head, token, column}, {token, head} ->
@@ -222,9 +228,50 @@ int check_indexer(const IndexerCall &c, Fa2IndexerProblem &p) {
     return FA2_OK;
 }
 
+// The split count and the chunk of a selection, after check_indexer: 1 for the one-workgroup kernel (every call but the _split entry
+// points; there num_splits 1, a heuristic that says 1, and a row of one chunk).  Else the count clamped to the chunks of 1,024
+// positions the capacity holds, the chunk ceil(S_k / count) rounded up to 1,024, and the count once more the chunks that hold a
+// position; then the workspace's checks.
+int resolve_splits(const IndexerCall &c, const Fa2IndexerProblem &p, int &splits, int &chunk) {
+    splits = 1;
+    chunk = 0;
+    if (!c.split) return FA2_OK;
+    if (c.num_splits < 0 || c.num_splits > kTopkMaxSplits) {
+        fa2_set_error("topk indices: num_splits must be in [0, %d] (got %d)", kTopkMaxSplits, c.num_splits);
+        return FA2_ERR_BAD_ARG;
+    }
+    const int64_t rows = c.packed ? (int64_t)c.total_q : (int64_t)c.B * c.N_q;
+    int ns = c.num_splits ? c.num_splits : fa2_topk_num_splits(rows, p.S_k, p.topk);
+    const int most = (p.S_k + 1023) / 1024;
+    ns = ns < most ? ns : most;
+    if (ns <= 1) return FA2_OK;
+    const int ch = ((p.S_k + ns - 1) / ns + 1023) / 1024 * 1024;
+    ns = (p.S_k + ch - 1) / ch;
+    if (ns <= 1) return FA2_OK;
+    if (!c.workspace || ((uintptr_t)c.workspace & 15) != 0) {
+        fa2_set_error(!c.workspace ? "topk indices: null workspace with num_splits = %d" : "topk indices: workspace must be 16-byte aligned (num_splits = %d)", ns);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (c.workspace_bytes < fa2_topk_split_bytes(rows, ns)) {
+        fa2_set_error("topk indices: workspace_bytes = %lld is short of the %lld bytes %lld rows at num_splits = %d need", (long long)c.workspace_bytes,
+                      (long long)fa2_topk_split_bytes(rows, ns), (long long)rows, ns);
+        return FA2_ERR_BAD_ARG;
+    }
+    if (rows > 65535) {
+        fa2_set_error("topk indices: grid too large for num_splits = %d (rows = %lld, the split form takes 65535)", ns, (long long)rows);
+        return FA2_ERR_BAD_ARG;
+    }
+    splits = ns;
+    chunk = ch;
+    return FA2_OK;
+}
+
 int run_indexer(const IndexerCall &c) {
     Fa2IndexerProblem p;
     int rc = check_indexer(c, p);
+    if (rc != FA2_OK) return rc;
+    int splits, chunk;
+    rc = resolve_splits(c, p, splits, chunk);
     if (rc != FA2_OK) return rc;
     if (c.scores && c.q8) {  // fp8 queries: the forms of their own, chosen by the same rule
         const bool fits = c.packed ? fa2_indexer_mfma8_v_supports(p) : fa2_indexer_mfma8_supports(p);
@@ -241,6 +288,7 @@ int run_indexer(const IndexerCall &c) {
         if (rc != FA2_OK) return rc;
     }
     if (!c.select) return FA2_OK;
+    if (splits > 1) return c.packed ? fa2_launch_topk_indices_split_v(p, splits, chunk, c.workspace) : fa2_launch_topk_indices_split(p, splits, chunk, c.workspace);
     return c.packed ? fa2_launch_topk_indices_v(p) : fa2_launch_topk_indices(p);
 }
 
@@ -635,6 +683,39 @@ int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const v
 int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k) {
     if (total_q < 1 || S_k < 1) return 0;
     return 4 * (int64_t)total_q * S_k;  // < 2^64
+}
+
+// The selection with a row split over num_splits workgroups: the same argument lists through the same checks, then resolve_splits.
+int fa2_topk_indices_split(const float *logits, const int64_t logit_strides[3], const int32_t *cache_seqlens, int32_t B, int32_t N_q,
+                           int32_t S_k, int32_t topk, int32_t causal, int32_t *indices, const int64_t index_strides[3],
+                           int32_t num_splits, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    return run_indexer({false, true, nullptr, nullptr, nullptr, nullptr, const_cast<float *>(logits), nullptr, nullptr, nullptr, nullptr,
+                        logit_strides, cache_seqlens, nullptr, 0, B, 0, N_q, S_k, 0, 0, 0, 0, 0, 0, causal, 0, topk, indices, index_strides,
+                        hip_stream, false, nullptr, 0, false, true, num_splits, workspace, workspace_bytes});
+}
+
+int fa2_topk_indices_varlen_split(const float *logits, const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                                  const int32_t *cache_seqlens, int32_t B, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                  int32_t topk, int32_t causal, int32_t *indices, const int64_t index_strides[2], int32_t num_splits,
+                                  void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    PackedStrides s;
+    return run_indexer({false, true, nullptr, nullptr, nullptr, nullptr, const_cast<float *>(logits), nullptr, nullptr, nullptr, nullptr,
+                        PackedStrides::rows3(logit_strides, s.lg), cache_seqlens, nullptr, 0, B, 0, max_seqlen_q, S_k, 0, 0, 0, 0, 0, 0,
+                        causal, 0, topk, indices, PackedStrides::rows3(index_strides, s.idx), hip_stream, true, cu_seqlens_q, total_q,
+                        false, true, num_splits, workspace, workspace_bytes});
+}
+
+int64_t fa2_topk_workspace_bytes(int64_t rows, int32_t num_splits) {
+    if (rows < 1 || rows > (1LL << 31) || num_splits < 2 || num_splits > kTopkMaxSplits) return 0;
+    return fa2_topk_split_bytes(rows, num_splits);
+}
+
+// The conservative form, not measured: split only below 256 rows (one row a CU keeps the chip busy without it), to about one chip
+// wave of workgroups -- 256 CUs over the rows -- and never to chunks shorter than 1,024 positions.  1 below 8,192 keys: a condition.
+int32_t fa2_topk_num_splits(int64_t rows, int32_t S_k, int32_t topk) {
+    if (rows < 1 || rows >= 256 || S_k < 8192 || topk >= S_k) return 1;
+    const int64_t want = (256 + rows - 1) / rows, most = ((int64_t)S_k + 1023) / 1024;  // want in [2, 256]
+    return (int32_t)(want < most ? want : most);
 }
 
 // fp8 queries: the same argument lists through the same checks, `q8` set (include/fa2_fwd.h).

@@ -1394,11 +1394,24 @@ def mla_indexer_logits(q_idx, weights, k_idx, cache_seqlens, dev, *, causal=True
     return logits
 
 
-def topk_indices(logits, cache_seqlens, topk, *, N_q=None, causal=True):
+def _selection_splits(who, name, value, rows, S_k, topk, device):
+    """(count, workspace) of a selection of `rows` rows over S_k keys: `value` in [0, 256] (ValueError otherwise), 0 resolved by the
+    library's heuristic (_lib.topk_num_splits); the workspace a fresh uint8 tensor, None where the count is 1."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= 256:
+        raise ValueError(f"{who}: {name} must be an int in [0, 256] (0: the heuristic, 1: one workgroup a row), got {value!r}")
+    count = value or _lib.topk_num_splits(rows, S_k, topk)
+    if count <= 1:
+        return 1, None
+    return count, torch.empty(_lib.topk_workspace_bytes(rows, count), dtype=torch.uint8, device=device)
+
+
+def topk_indices(logits, cache_seqlens, topk, *, N_q=None, causal=True, num_splits=0):
     """The selection of the MLA indexer alone (fa2_topk_indices), over any float32 logits (B, N_q, S_k) of any non-negative strides
     (or (B * N_q, S_k) with N_q given) -> indices int32 (B, N_q, topk).  Row (b, qi) has n candidates, entries j < n with n as in
     mla_indexer_logits; nothing else of the row is read.  Its list is the min(topk, n) candidates first under (value descending,
-    position ascending) -- -0.0 equals +0.0, a NaN ranks as -inf -- emitted in ascending position, the rest of the row -1."""
+    position ascending) -- -0.0 equals +0.0, a NaN ranks as -inf -- emitted in ascending position, the rest of the row -1.
+    num_splits: the workgroups a row is split over (fa2_topk_indices_split), 0 the library's choice (1 below 8,192 keys), 1 the
+    one-workgroup kernel, up to 256; the bytes are the same for every count."""
     if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() not in (2, 3):
         raise ValueError("topk indices: logits must be a float32 tensor (B, N_q, S_k)")
     if logits.dim() == 2:
@@ -1415,13 +1428,17 @@ def topk_indices(logits, cache_seqlens, topk, *, N_q=None, causal=True):
         raise ValueError(f"topk indices: topk must be an int in [1, 2^28], got {topk!r}")
     if cache_seqlens is not None:
         _check_cache_seqlens(cache_seqlens, B, logits, "logits", " (or None)")
+    count, workspace = _selection_splits("topk indices", "num_splits", num_splits, B * nq, S_k, topk, logits.device)
     indices = torch.empty((B, nq, topk), dtype=torch.int32, device=logits.device)
-    _lib.fa2_topk_indices(logits, indices, cache_seqlens, causal=causal)
+    if count == 1:
+        _lib.fa2_topk_indices(logits, indices, cache_seqlens, causal=causal)
+    else:
+        _lib.fa2_topk_indices(logits, indices, cache_seqlens, causal=causal, num_splits=count, workspace=workspace)
     return indices
 
 
 def flash_attention_mla_indexer_topk(q_idx, weights, k_idx, cache_seqlens, dev, topk=2048, causal=True, k_scale=None, block_table=None,
-                                     variant="auto", return_logits=False):
+                                     variant="auto", return_logits=False, select_splits=0):
     """The MLA indexer (DeepSeek-V3.2's lightning indexer; include/fa2_fwd.h fa2_mla_indexer_topk) -> indices int32 (B, N_q, topk),
     the key lists flash_attention_mla_sparse_decode_forward takes: scores and selection on one stream, no (B, N_q, H_I, N_k)
     intermediate.  q_idx (B, H_I, N_q, d_I) in f16, bf16 or f32, any strides; weights float32 (B, H_I, N_q), any softmax or head
@@ -1435,15 +1452,25 @@ def flash_attention_mla_indexer_topk(q_idx, weights, k_idx, cache_seqlens, dev, 
     format) goes to the fp8 x fp8 entry points (fa2_mla_indexer_topk_q8), whose matrix form is "idx8" (v_mfma_f32_16x16x128_f8f6f4,
     same conditions) in "idx16"'s place.  There is NO q_scale argument: quantise with quantize_index_keys(q, dtype) -> (q8, scale),
     one power-of-two scale per (token, head), and multiply that scale into weights, as the model's own code does.  return_logits: (indices, logits), the float32 (B, N_q, capacity) scores, written
-    for the candidates only.  No autograd."""
+    for the candidates only.  select_splits: topk_indices' num_splits for the selection; a count of 1 is the fused call
+    (fa2_mla_indexer_topk), a larger one the score call and then the split selection on the same stream -- the same lists.  No
+    autograd."""
     check_mla_indexer_args(q_idx, weights, k_idx, cache_seqlens, topk, k_scale, block_table)
     v = _indexer_variant(variant, q_idx)
     _indexer_dev(dev, q_idx)
     B, _, N_q, _ = q_idx.shape
-    logits = torch.empty((B, N_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
+    cap = _indexer_capacity(k_idx, block_table)
+    count, workspace = _selection_splits("mla indexer", "select_splits", select_splits, B * N_q, cap, topk, q_idx.device)
+    logits = torch.empty((B, N_q, cap), dtype=torch.float32, device=q_idx.device)
     indices = torch.empty((B, N_q, topk), dtype=torch.int32, device=q_idx.device)
-    _lib.fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_seqlens, convert_triton_dtype(q_idx.dtype),
-                              convert_triton_dtype(k_idx.dtype), block_table=block_table, causal=causal, variant=v)
+    dtypes = (convert_triton_dtype(q_idx.dtype), convert_triton_dtype(k_idx.dtype))
+    if count == 1:
+        _lib.fa2_mla_indexer_topk(q_idx, weights, k_idx, k_scale, logits, indices, cache_seqlens, *dtypes, block_table=block_table,
+                                  causal=causal, variant=v)
+    else:
+        _lib.fa2_mla_indexer_logits(q_idx, weights, k_idx, k_scale, logits, cache_seqlens, *dtypes, block_table=block_table,
+                                    causal=causal, variant=v)
+        _lib.fa2_topk_indices(logits, indices, cache_seqlens, causal=causal, num_splits=count, workspace=workspace)
     return (indices, logits) if return_logits else indices
 
 
@@ -1599,10 +1626,11 @@ def mla_indexer_logits_varlen(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q,
     return logits
 
 
-def topk_indices_varlen(logits, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk, *, causal=True):
+def topk_indices_varlen(logits, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk, *, causal=True, num_splits=0):
     """The selection of the MLA indexer over packed rows (fa2_topk_indices_varlen): float32 logits (total_q, S_k) of any non-negative
     strides -> indices int32 (total_q, topk).  Row start(b) + i is query i of sequence b and has topk_indices' candidates with n_q(b)
-    in N_q's place; its list is topk_indices'.  A row no sequence owns is not written."""
+    in N_q's place; its list is topk_indices'.  A row no sequence owns is not written.  num_splits: as topk_indices'
+    (fa2_topk_indices_varlen_split), the rows total_q."""
     who = "topk indices varlen"
     if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2:
         raise ValueError(f"{who}: logits must be a float32 tensor (total_q, S_k)")
@@ -1615,27 +1643,41 @@ def topk_indices_varlen(logits, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk,
         raise ValueError(f"{who}: topk must be an int in [1, 2^28], got {topk!r}")
     if cache_seqlens is not None:
         _check_cache_seqlens(cache_seqlens, B, logits, "logits", " (or None)")
+    count, workspace = _selection_splits(who, "num_splits", num_splits, total_q, S_k, topk, logits.device)
     indices = torch.empty((total_q, topk), dtype=torch.int32, device=logits.device)
-    _lib.fa2_topk_indices_varlen(logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, causal=causal)
+    if count == 1:
+        _lib.fa2_topk_indices_varlen(logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, causal=causal)
+    else:
+        _lib.fa2_topk_indices_varlen(logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, causal=causal, num_splits=count,
+                                     workspace=workspace)
     return indices
 
 
 def flash_attention_mla_indexer_topk_varlen(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, topk=2048, causal=True,
-                                            k_scale=None, block_table=None, variant="auto", return_logits=False):
+                                            k_scale=None, block_table=None, variant="auto", return_logits=False, select_splits=0):
     """The MLA indexer over variable-length (packed) queries (include/fa2_fwd.h fa2_mla_indexer_topk_varlen) -> indices int32
     (total_q, topk), the key lists flash_attention_mla_sparse_varlen_decode_forward takes as they are.  q_idx (total_q, H_I, d_I) in
     f16, bf16 or f32, or fp8 over an fp8 k_idx (no q_scale: its scale goes into weights), any strides; weights float32 (total_q, H_I); cu_seqlens_q int32 (B + 1,) on q_idx's device and max_seqlen_q as
     in flash_attention_mla_varlen_decode_forward; k_idx, k_scale, cache_seqlens, block_table, topk, causal, variant and return_logits
     are flash_attention_mla_indexer_topk's.  Query i of sequence b stands at position N_k(b) - n_q(b) + i.  Sequence b's rows equal
     flash_attention_mla_indexer_topk's on that sequence alone, byte for byte; rows no sequence owns are not written.  return_logits:
-    (indices, logits), the float32 (total_q, capacity) scores.  No autograd."""
+    (indices, logits), the float32 (total_q, capacity) scores.  select_splits: flash_attention_mla_indexer_topk's, the rows total_q.
+    No autograd."""
     check_mla_indexer_varlen_args(q_idx, weights, k_idx, cu_seqlens_q, max_seqlen_q, cache_seqlens, topk, k_scale, block_table)
     v = _indexer_variant(variant, q_idx)
     _indexer_dev(dev, q_idx)
     total_q = q_idx.shape[0]
-    logits = torch.empty((total_q, _indexer_capacity(k_idx, block_table)), dtype=torch.float32, device=q_idx.device)
+    cap = _indexer_capacity(k_idx, block_table)
+    count, workspace = _selection_splits("mla indexer varlen", "select_splits", select_splits, total_q, cap, topk, q_idx.device)
+    logits = torch.empty((total_q, cap), dtype=torch.float32, device=q_idx.device)
     indices = torch.empty((total_q, topk), dtype=torch.int32, device=q_idx.device)
-    _lib.fa2_mla_indexer_topk_varlen(q_idx, weights, k_idx, k_scale, logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens,
-                                     convert_triton_dtype(q_idx.dtype), convert_triton_dtype(k_idx.dtype), block_table=block_table,
-                                     causal=causal, variant=v)
+    dtypes = (convert_triton_dtype(q_idx.dtype), convert_triton_dtype(k_idx.dtype))
+    if count == 1:
+        _lib.fa2_mla_indexer_topk_varlen(q_idx, weights, k_idx, k_scale, logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens,
+                                         *dtypes, block_table=block_table, causal=causal, variant=v)
+    else:
+        _lib.fa2_mla_indexer_logits_varlen(q_idx, weights, k_idx, k_scale, logits, cu_seqlens_q, max_seqlen_q, cache_seqlens, *dtypes,
+                                           block_table=block_table, causal=causal, variant=v)
+        _lib.fa2_topk_indices_varlen(logits, indices, cu_seqlens_q, max_seqlen_q, cache_seqlens, causal=causal, num_splits=count,
+                                     workspace=workspace)
     return (indices, logits) if return_logits else indices

@@ -1066,6 +1066,42 @@ int fa2_mla_indexer_topk_varlen(const void *q_idx, const float *weights, const v
 int64_t fa2_mla_indexer_varlen_workspace_bytes(int32_t total_q, int32_t S_k);
 
 /*
+ * The selection with a row SPLIT over num_splits workgroups (long rows at few rows: one workgroup per row leaves the chip idle).
+ * Arguments, semantics and bytes are fa2_topk_indices' (fa2_topk_indices_varlen's): the lists are a function of the logits alone, and
+ * for every input the split form writes exactly what the one-workgroup form writes.
+ *
+ *   num_splits  0: fa2_topk_num_splits(rows, S_k, topk).  1: the one-workgroup kernel, no workspace read.  2 .. 256: split s of a row
+ *               covers the positions [s * c, (s + 1) * c), c = ceil(S_k / num_splits) rounded up to 1,024, after num_splits has been
+ *               clamped to ceil(S_k / 1024) and to the ceil(S_k / c) chunks that hold a position; a count that comes out as 1 takes
+ *               the one-workgroup kernel.  rows = B * N_q (total_q in the packed call).
+ *   workspace   device memory, 16-byte aligned, fa2_topk_workspace_bytes(rows, the count after the clamp) bytes at least -- so
+ *               sized for the count asked for is always enough.  ANY contents: the call clears what it counts in, on its stream.
+ *   Launches.   Consecutive launches on hip_stream and nothing else: no workgroup waits for another, no memset node, so the call
+ *               can be captured in a graph.  Only integer counts are accumulated.
+ *
+ * Errors: fa2_topk_indices' first, in their order; then FA2_ERR_BAD_ARG, before any launch and naming the argument, for num_splits
+ * outside [0, 256], a null, misaligned or short workspace where the resolved count is > 1, and more than 65,535 rows in the split
+ * form (its grid is (splits, rows)).
+ */
+int fa2_topk_indices_split(const float *logits, const int64_t logit_strides[3], const int32_t *cache_seqlens,
+                           int32_t B, int32_t N_q, int32_t S_k, int32_t topk, int32_t causal,
+                           int32_t *indices, const int64_t index_strides[3], int32_t num_splits, void *workspace,
+                           int64_t workspace_bytes, void *hip_stream);
+
+int fa2_topk_indices_varlen_split(const float *logits, const int64_t logit_strides[2], const int32_t *cu_seqlens_q,
+                                  const int32_t *cache_seqlens, int32_t B, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                  int32_t topk, int32_t causal, int32_t *indices, const int64_t index_strides[2],
+                                  int32_t num_splits, void *workspace, int64_t workspace_bytes, void *hip_stream);
+
+/* Bytes of the split selection's workspace: per row three int32 histograms (2,048 + 2,048 + 1,024 bins) and num_splits pairs of
+ * int32 counts, rows * (20,480 + 8 * num_splits); 0 for rows < 1 or num_splits outside [2, 256]. */
+int64_t fa2_topk_workspace_bytes(int64_t rows, int32_t num_splits);
+
+/* What num_splits = 0 resolves to: a count in [1, 256] whose chunk holds 1,024 positions at least, 1 whenever S_k < 8,192 or
+ * topk >= S_k, non-increasing in rows. */
+int32_t fa2_topk_num_splits(int64_t rows, int32_t S_k, int32_t topk);
+
+/*
  * The MLA indexer with fp8 QUERIES (the _q8 entry points): the four score-bearing calls above, argument for argument, with q_idx in
  * e4m3fn or e5m2 (OCP) as DeepSeek-V3.2's inference code holds it.  k_idx is in either fp8 format too, and the two need not match.
  *
