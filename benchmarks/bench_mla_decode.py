@@ -24,8 +24,17 @@ concatenate, quantise, scatter through the table, rotate and concatenate Q) foll
 call by call in ONE process and timed by device events around each call, --repeats runs per case; then the append launch alone
 (fa2_kvcache_mla_append) with the bytes it must move, computed from the shapes, and bytes / s at its fastest rate (200 launches back to back without a host synchronisation).
 
+--kv-format fp8_ds: the dense call over the tile-scaled fp8 cache (fa2_fwd_kvcache_mla_ds, 656-byte rows) on DS_CASES (H 128 / 16, B 1 /
+16 / 128, N_q 1 / 2, N_k 2,048 / 8,192), AUTO variant and the dense auto num_splits, beside the routes it stands next to, over the same
+rows: the 16-bit call, the one-descale e4m3 call, `torch` dequantisation of the whole cache followed by the 16-bit call
+(dequantize_mla_cache_ds: its torch kernels are part of that side's time) and, at N_k = 2,048, the list form over fp8_ds on the identity
+list at its own auto num_splits (the route the dense form replaces).  The sides ALTERNATE call by call in one traced child, a mark
+kernel between them, as benchmarks/bench_mla_sparse.py --kv-format fp8_ds does; the copies are sized by the smallest row (576 B).
+
 Records:
-  kind=append         --append: per case, the per-run avg / min / max / stddev of both sides, their ratio, the append launch alone;
+  kind=kv_format      --kv-format fp8_ds: per shape the sides' avg / min / max / stddev, fp8_ds over each other side, and for each whether
+                      the min-max ranges overlap;
+  kind=append        --append: per case, the per-run avg / min / max / stddev of both sides, their ratio, the append launch alone;
   kind=kernels        one per shape and cache form: the sides' avg / min / max / stddev in microseconds, auto_over_generic;
   kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS on the four SWEEP_CASES, one traced child per shape."""
 import argparse
@@ -48,6 +57,9 @@ SHAPES = ((1, 8192), (1, 65536), (16, 4096), (64, 2048), (128, 4096))  # (B, N_k
 CASES = {f"h{H}_q{N_q}_b{B}_n{S}": (B, H, N_q, S) for H in (16, 128) for N_q in (1, 2) for B, S in SHAPES}
 SWEEP_CASES = ("h128_q1_b1_n8192", "h128_q1_b1_n65536", "h128_q1_b16_n4096", "h16_q1_b1_n65536")
 SWEEP_SPLITS = (1, 2, 4, 8, 16, 32, 64, 128)
+# --kv-format fp8_ds: the shapes of the comparison with the list form (N_k = topk = 2,048) and of a longer dense walk
+DS_CASES = {f"h{H}_q{N_q}_b{B}_n{S}": (B, H, N_q, S) for H in (128, 16) for N_q in (1, 2) for B in (1, 16, 128) for S in (2048, 8192)}
+DS_SIDES = ("fp8_ds", "bf16", "e4m3", "torch_dequant", "list_identity")  # the last at N_k = 2,048 only
 
 
 def emit(fh, **kw):
@@ -59,17 +71,18 @@ def emit(fh, **kw):
 
 
 class Case:
-    def __init__(self, name, dev, page_size=0, kv_dtype="bf16"):
+    def __init__(self, name, dev, page_size=0, kv_dtype="bf16", copy_row_bytes=0):
+        """copy_row_bytes: the bytes per key that size the number of copies (--kv-format: the smallest row of the sides), else the cache's"""
         import torch
         import flash_attention_dlrs_amd as fa
         from flash_attention_dlrs_amd import _lib
         from flash_attention_dlrs_amd.flash_attention_torch import convert_triton_dtype
         self.torch, self._lib, self.dev = torch, _lib, dev
-        B, H, N_q, S = CASES[name]
+        B, H, N_q, S = CASES[name] if name in CASES else DS_CASES[name]
         self.shape = dict(B=B, H=H, N_q=N_q, N_k=S)
         self.fmt = {"bf16": None, "e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}[kv_dtype]
         self.kv_bytes = (1 if self.fmt else 2) * D * B * S
-        self.copies = max(2, math.ceil(300e6 / self.kv_bytes))
+        self.copies = max(2, math.ceil(300e6 / (copy_row_bytes * B * S if copy_row_bytes else self.kv_bytes)))
         self.scale = D ** -0.5
         self.enum = convert_triton_dtype(torch.bfloat16)
         mk = lambda *s: (torch.randn(*s, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
@@ -163,6 +176,67 @@ def run_sweep_pass(name, args):
         torch.cuda.synchronize()
     print(json.dumps(dict(case=name, calls=args.iters + 3, kv_dtype=args.kv_dtype, auto_splits=c.auto_splits(), kv_bytes=c.kv_bytes,
                           **c.shape)))
+
+
+def run_format_pass(name, args):
+    """The traced child of --kv-format fp8_ds: the caches of the same rows, one call of each side in turn, a mark after every call."""
+    import torch
+    import flash_attention_dlrs_amd as fa
+    c = Case(name, torch.device("cuda:0"), copy_row_bytes=D)
+    lib, s = c._lib, c.shape
+    ds = [fa.quantize_mla_cache_ds(t) for t in c.KV]
+    e4 = [fa.quantize_kv_cache(t, torch.float8_e4m3fn) for t in c.KV]
+    n = c.auto_splits()
+    ws = torch.empty(max(lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], D_V, n) // 4, 1), dtype=torch.float32, device=c.dev)
+    kw = dict(scale=c.scale, num_splits=n, workspace=ws)
+    sides = [x for x in DS_SIDES if x != "list_identity" or s["N_k"] == 2048]
+    n_list, ws_list, idx = 0, None, None
+    if "list_identity" in sides:  # topk = N_k: every key once, in order, at the list form's own split count
+        n_list = lib.kvcache_mla_sparse_num_splits(s["B"], s["H"], 1, s["N_q"], s["N_k"], D, D_V, c.enum)
+        ws_list = torch.empty(max(lib.kvcache_workspace_bytes(s["B"], s["H"], s["N_q"], D_V, n_list) // 4, 1), dtype=torch.float32, device=c.dev)
+        idx = torch.arange(s["N_k"], dtype=torch.int32, device=c.dev).expand(s["B"], 1, s["N_q"], s["N_k"])
+
+    def run(side, i):
+        if side == "fp8_ds":
+            lib.fa2_fwd_kvcache_mla_ds(c.Q, ds[i], c.O, c.L, c.lens, c.enum, **kw)
+        elif side == "bf16":
+            lib.fa2_fwd_kvcache_mla(c.Q, c.KV[i], c.KV[i][..., :D_V], c.O, c.L, c.lens, c.enum, **kw)
+        elif side == "e4m3":
+            kv, d = e4[i]
+            lib.fa2_fwd_kvcache_mla_fp8(c.Q, kv, kv[..., :D_V], c.O, c.L, c.lens, c.enum, lib.FA2_DTYPE_F8E4M3, k_descale=d, v_descale=d, **kw)
+        elif side == "torch_dequant":
+            kv = fa.dequantize_mla_cache_ds(ds[i], torch.bfloat16)
+            lib.fa2_fwd_kvcache_mla(c.Q, kv, kv[..., :D_V], c.O, c.L, c.lens, c.enum, **kw)
+        else:
+            lib.fa2_fwd_kvcache_mla_sparse_ds(c.Q, ds[i], c.O, c.L, idx, c.lens, c.enum, scale=c.scale, num_splits=n_list, workspace=ws_list)
+    mark = torch.zeros(1, device=c.dev)
+    torch.cuda.synchronize()
+    mark.fill_(0.0)
+    rounds = args.iters + 3
+    for r in range(rounds):
+        for k, side in enumerate(sides):  # (the three sides that read the fp8_ds copies take different ones in a round)
+            run(side, (r + k * c.copies // len(sides)) % c.copies)
+            mark.fill_(1.0)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, rounds=rounds, sides=sides, kv_format="fp8_ds", num_splits=n, list_num_splits=n_list, copies=c.copies, **s)))
+
+
+def overlap(a, b):
+    return a["max_us"] >= b["min_us"] and b["max_us"] >= a["min_us"]
+
+
+def run_format(names, args, fh):
+    from bench_mla_sparse import call_times, stats  # the trace cut at the marks: one segment per call
+    for name in names:
+        out = os.path.join(args.rocprof, name + "_fp8_ds")
+        info = traced_child(out, ["--format-case", name], args)
+        order = info.pop("sides")
+        calls = call_times(out, info["rounds"] * len(order))
+        sides = {side: stats(calls[k::len(order)]) for k, side in enumerate(order)}
+        new = sides["fp8_ds"]
+        emit(fh, kind="kv_format", **{k: v for k, v in info.items() if k != "rounds"},
+             ds_over={side: round(new["avg_us"] / t["avg_us"], 4) for side, t in sides.items() if side != "fp8_ds"},
+             ranges_overlap={side: overlap(new, t) for side, t in sides.items() if side != "fp8_ds"}, **sides)
 
 
 def traced_child(out, extra, args):
@@ -362,7 +436,7 @@ def run_append(names, args, fh):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--cases", default=None, help="default: every case (of DS_CASES with --kv-format)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--sweep", action="store_true", help="also time num_splits in %s on %s" % (SWEEP_SPLITS, SWEEP_CASES))
     ap.add_argument("--no-sdpa", action="store_true")
@@ -374,10 +448,16 @@ def main():
     ap.add_argument("--append", action="store_true",
                     help="time the fused append + decode step against the torch restatement + decode, and the append launch alone")
     ap.add_argument("--repeats", type=int, default=3, help="--append: runs per case, for the spread of the averages")
+    ap.add_argument("--kv-format", choices=("fp8_ds",),
+                    help="time the dense call over the tile-scaled fp8 cache beside the 16-bit, e4m3, torch-dequantise and list routes (kind=kv_format)")
+    ap.add_argument("--format-case", help=argparse.SUPPRESS)
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
+    if args.format_case:
+        return run_format_pass(args.format_case, args)
+    names = (args.cases or ",".join(DS_CASES if args.kv_format else CASES)).split(",")
     if args.pass_case:
         return run_pass(args.pass_case, args)
     if args.sweep_case:
@@ -385,8 +465,8 @@ def main():
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
         if args.append:
-            return run_append(args.cases.split(","), args, fh)
-        run_rocprof(args.cases.split(","), args, fh)
+            return run_append(names, args, fh)
+        (run_format if args.kv_format else run_rocprof)(names, args, fh)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,15 @@ Sides of one child:
              the padded one).
 The kernel trace is cut into the sides by dispatch order (split kernel plus combine per launch; one kernel for num_splits = 1).
 
+--kv-format fp8_ds: the packed call over the tile-scaled fp8 cache (fa2_fwd_kvcache_mla_varlen_ds), AUTO variant and the packed auto
+num_splits, beside the 16-bit packed call, the one-descale e4m3 packed call, `torch` dequantisation of the whole cache followed by the
+16-bit packed call and, where every sequence holds 2,048 keys (verify2, uniform1), the packed list form over fp8_ds on the identity
+list at its own auto num_splits (every key for every row: the list has no causal edge, so with 2 query tokens it scores one key more
+for the first).  The sides ALTERNATE call by call in one traced child, a mark kernel between them, as benchmarks/bench_mla_decode.py
+--kv-format fp8_ds does; the copies are sized by the smallest row (576 B).
+
 Records:
+  kind=kv_format      --kv-format fp8_ds: per shape the sides' avg / min / max / stddev, fp8_ds over each other side, ranges_overlap;
   kind=kernels        one per shape: the sides' avg / min / max / stddev in microseconds, auto_over_generic, auto_over_padded,
                       auto_over_per_count and whether AUTO's and generic's min-max ranges overlap;
   kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS, one traced child per shape."""
@@ -36,7 +44,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_mla_decode import D, D_V, emit, per_call, trace_rows  # noqa: E402
+from bench_mla_decode import D, D_V, DS_SIDES, emit, overlap, per_call, trace_rows  # noqa: E402
 
 OUT = os.path.join(ROOT, "profiles", "mla", "bench_mla_varlen.jsonl")
 KV_DTYPES = ("bf16", "e4m3")
@@ -49,7 +57,7 @@ CASES = {f"{name}_h{H}": (name, H) for name in BATCHES for H in (16, 128)}
 
 
 class Case:
-    def __init__(self, name, dev, kv_dtype="bf16"):
+    def __init__(self, name, dev, kv_dtype="bf16", copy_row_bytes=0):
         import torch
         import flash_attention_dlrs_amd as fa
         from flash_attention_dlrs_amd import _lib
@@ -64,7 +72,7 @@ class Case:
                           score_rows_x_keys=H * sum(q * k for q, k in zip(n_q, n_k)))
         self.fmt = {"bf16": None, "e4m3": torch.float8_e4m3fn}[kv_dtype]
         self.kv_bytes = (1 if self.fmt else 2) * D * sum(n_k)  # the bytes of the visible keys, once
-        self.copies = max(2, math.ceil(300e6 / ((1 if self.fmt else 2) * D * self.B * self.S)))
+        self.copies = max(2, math.ceil(300e6 / ((copy_row_bytes or (1 if self.fmt else 2) * D) * self.B * self.S)))
         self.scale = D ** -0.5
         self.enum = convert_triton_dtype(torch.bfloat16)
         mk = lambda *s: (torch.randn(*s, device=dev) * 0.8).to(torch.bfloat16)  # noqa: E731
@@ -173,6 +181,62 @@ def run_sweep_pass(name, args):
     print(json.dumps(dict(case=name, calls=args.iters + 3, kv_dtype=args.kv_dtype, auto_splits=c.auto_splits(), **c.shape)))
 
 
+def run_format_pass(name, args):
+    """The traced child of --kv-format fp8_ds: the caches of the same rows, one call of each side in turn, a mark after every call."""
+    import torch
+    import flash_attention_dlrs_amd as fa
+    c = Case(name, torch.device("cuda:0"), copy_row_bytes=D)
+    lib = c._lib
+    ds = [fa.quantize_mla_cache_ds(t) for t in c.KV]
+    e4 = [fa.quantize_kv_cache(t, torch.float8_e4m3fn) for t in c.KV]
+    n = c.auto_splits()
+    ws = torch.empty(max(lib.kvcache_varlen_workspace_bytes(c.total_q, c.H, D_V, n) // 4, 1), dtype=torch.float32, device=c.dev)
+    kw = dict(causal=True, scale=c.scale, num_splits=n, workspace=ws)
+    sides = [x for x in DS_SIDES if x != "list_identity" or all(k == 2048 for _, _, k in c.groups)]
+    n_list, ws_list, idx = 0, None, None
+    if "list_identity" in sides:
+        n_list = lib.kvcache_mla_sparse_varlen_num_splits(c.total_q, c.H, 1, c.S, D, D_V, c.enum)
+        ws_list = torch.empty(max(lib.kvcache_varlen_workspace_bytes(c.total_q, c.H, D_V, n_list) // 4, 1), dtype=torch.float32, device=c.dev)
+        idx = torch.arange(c.S, dtype=torch.int32, device=c.dev).expand(c.total_q, 1, c.S)
+
+    def run(side, i):
+        if side == "fp8_ds":
+            lib.fa2_fwd_kvcache_mla_varlen_ds(c.Q, ds[i], c.O, c.L, c.cu, c.max_q, c.lens, c.enum, **kw)
+        elif side == "e4m3":
+            lib.fa2_fwd_kvcache_mla_varlen(c.Q, e4[i][0], c.O, c.L, c.cu, c.max_q, c.lens, c.enum, lib.FA2_DTYPE_F8E4M3, D_V, kv_descale=e4[i][1], **kw)
+        elif side == "list_identity":
+            lib.fa2_fwd_kvcache_mla_sparse_varlen_ds(c.Q, ds[i], c.O, c.L, idx, c.cu, c.max_q, c.lens, c.enum, scale=c.scale, num_splits=n_list,
+                                                     workspace=ws_list)
+        else:
+            kv = c.KV[i] if side == "bf16" else fa.dequantize_mla_cache_ds(ds[i], torch.bfloat16)
+            lib.fa2_fwd_kvcache_mla_varlen(c.Q, kv, c.O, c.L, c.cu, c.max_q, c.lens, c.enum, c.enum, D_V, **kw)
+    mark = torch.zeros(1, device=c.dev)
+    torch.cuda.synchronize()
+    mark.fill_(0.0)
+    rounds = args.iters + 3
+    for r in range(rounds):
+        for k, side in enumerate(sides):  # (the three sides that read the fp8_ds copies take different ones in a round)
+            run(side, (r + k * c.copies // len(sides)) % c.copies)
+            mark.fill_(1.0)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, rounds=rounds, sides=sides, kv_format="fp8_ds", packed=True, num_splits=n, list_num_splits=n_list,
+                          copies=c.copies, **c.shape)))
+
+
+def run_format(names, args, fh):
+    from bench_mla_sparse import call_times, stats  # the trace cut at the marks: one segment per call
+    for name in names:
+        out = os.path.join(args.rocprof, "varlen_" + name + "_fp8_ds")
+        info = child(out, ["--format-case", name], args)
+        order = info.pop("sides")
+        calls = call_times(out, info["rounds"] * len(order))
+        sides = {side: stats(calls[k::len(order)]) for k, side in enumerate(order)}
+        new = sides["fp8_ds"]
+        emit(fh, kind="kv_format", **{k: v for k, v in info.items() if k != "rounds"},
+             ds_over={side: round(new["avg_us"] / t["avg_us"], 4) for side, t in sides.items() if side != "fp8_ds"},
+             ranges_overlap={side: overlap(new, t) for side, t in sides.items() if side != "fp8_ds"}, **sides)
+
+
 def child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
@@ -221,17 +285,22 @@ def main():
                     help="the traces of the rocprofv3 children go under DIR")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="bf16", help="the latent cache's storage: bf16, or fp8 with its descale")
+    ap.add_argument("--kv-format", choices=("fp8_ds",),
+                    help="time the packed call over the tile-scaled fp8 cache beside the 16-bit, e4m3, torch-dequantise and list routes (kind=kv_format)")
+    ap.add_argument("--format-case", help=argparse.SUPPRESS)
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
+    if args.format_case:
+        return run_format_pass(args.format_case, args)
     if args.pass_case:
         return run_pass(args.pass_case, args)
     if args.sweep_case:
         return run_sweep_pass(args.sweep_case, args)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
-        run_rocprof(args.cases.split(","), args, fh)
+        (run_format if args.kv_format else run_rocprof)(args.cases.split(","), args, fh)
 
 
 if __name__ == "__main__":

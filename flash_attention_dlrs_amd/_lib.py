@@ -68,7 +68,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_mla_indexer_logits_q8", "fa2_mla_indexer_topk_q8", "fa2_mla_indexer_logits_varlen_q8", "fa2_mla_indexer_topk_varlen_q8",
            "fa2_mla_indexer_prepare_q", "fa2_mla_indexer_prepare_q_varlen", "fa2_mla_indexer_append_rot",
            "fa2_mla_indexer_append_varlen_rot",
-           "fa2_topk_indices_split", "fa2_topk_indices_varlen_split", "fa2_topk_workspace_bytes", "fa2_topk_num_splits")
+           "fa2_topk_indices_split", "fa2_topk_indices_varlen_split", "fa2_topk_workspace_bytes", "fa2_topk_num_splits",
+           "fa2_fwd_kvcache_mla_ds", "fa2_fwd_kvcache_mla_varlen_ds")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -336,6 +337,13 @@ def lib():
         l.fa2_fwd_kvcache_mla_sparse_varlen_ds.argtypes = [vp] * 4 + [i64p] * 3 + [ctypes.c_int64, vp, vp, vp, i64p, ctypes.c_int32, vp,
                                                                                    ctypes.c_int64] + \
             [ctypes.c_int32] * 9 + [ctypes.c_float, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32, vp]
+        # the two dense latent calls over the same cache: fa2_fwd_kvcache_mla's / _mla_varlen's order with that KV pointer and its byte strides
+        l.fa2_fwd_kvcache_mla_ds.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_ds.argtypes = [vp] * 4 + [i64p] * 4 + [vp, vp, ctypes.c_int64] + [ctypes.c_int32] * 9 + \
+            [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_fwd_kvcache_mla_varlen_ds.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_varlen_ds.argtypes = [vp] * 4 + [i64p] * 3 + [ctypes.c_int64, vp, vp, vp, ctypes.c_int64] + \
+            [ctypes.c_int32] * 11 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         # the packed indexer: the fixed calls' order with cu_seqlens_q before cache_seqlens and total_q max_seqlen_q in N_q's place
         idxv = [vp] * 5 + [i64p] * 5 + [vp, vp, vp, ctypes.c_int64] + [ctypes.c_int32] * 12
         l.fa2_mla_indexer_logits_varlen.restype = ctypes.c_int
@@ -902,6 +910,35 @@ def fa2_fwd_kvcache_mla_sparse_varlen_ds(Q, KV, O, L, indices, cu_q, max_q, cach
             indices.data_ptr(), _i64(indices.stride()), indices.shape[2], tb_ptr, tb_st, cu_q.numel() - 1, H, KV.shape[1], total_q,
             int(max_q), nb, KV.shape[2], mb, int(dtype_enum), float(scale), int(num_splits), *_workspace_args(workspace), int(variant),
             _raw_stream(Q.device.index))
+
+
+def fa2_fwd_kvcache_mla_ds(Q, KV, O, L, cache_seqlens, dtype_enum, block_table=None, causal=False, scale=1.0, window=None, num_splits=0,
+                           workspace=None, variant=0):
+    """Launch dense MLA decode over the tile-scaled fp8 cache (include/fa2_fwd.h fa2_fwd_kvcache_mla_ds) on the current stream of Q's
+    device: KV as in fa2_fwd_kvcache_mla_sparse_ds, the rest as fa2_fwd_kvcache_mla."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, KV must be on the same CUDA device")
+    B, H, N_q, _ = Q.shape
+    tb_ptr, tb_st, _, nb, _, mb = _table_args(KV, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla_ds, Q, Q.data_ptr(), KV.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(KV.stride()[:3]), _i64(O.stride()), _i64((L.stride(0), L.stride(1))), _ptr(cache_seqlens),
+            tb_ptr, tb_st, B, H, KV.shape[1], N_q, nb, KV.shape[2], mb, int(dtype_enum), int(bool(causal)), float(scale),
+            *_window_sides(window), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
+
+
+def fa2_fwd_kvcache_mla_varlen_ds(Q, KV, O, L, cu_q, max_q, cache_seqlens, dtype_enum, block_table=None, causal=False, scale=1.0,
+                                  window=None, num_splits=0, workspace=None, variant=0):
+    """Launch dense MLA decode of packed queries over the tile-scaled fp8 cache (fa2_fwd_kvcache_mla_varlen_ds): the packed tensors of
+    fa2_fwd_kvcache_mla_varlen, the cache of fa2_fwd_kvcache_mla_sparse_ds."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, KV must be on the same CUDA device")
+    total_q, H, _ = Q.shape
+    _check_packed_l("fa2_fwd_kvcache_mla_varlen_ds", L, H, total_q)
+    tb_ptr, tb_st, S_k, nb, ps, mb = _table_args(KV, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla_varlen_ds, Q, Q.data_ptr(), KV.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(KV.stride()[:3]), _i64(O.stride()), L.stride(0), cu_q.data_ptr(), _ptr(cache_seqlens), tb_ptr, tb_st,
+            cu_q.numel() - 1, H, KV.shape[1], total_q, int(max_q), S_k, nb, ps, mb, int(dtype_enum), int(bool(causal)), float(scale),
+            *_window_sides(window), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
 
 
 def mla_indexer_varlen_workspace_bytes(total_q, S_k):

@@ -113,6 +113,33 @@ template <> struct CacheCvt<_Float16, CacheE5M2> {
     }
 };
 
+// The VALU forms' loader of the tile-scaled row (fa2_decode_generic.hip, fa2_decode_sparse_generic.hip) under Q's 16-bit type E, an
+// element type of fa2_elem.h: `i` is the BYTE offset of the row (the strides of such a cache are in bytes), element x of it is
+// E(fp32(byte x) * scale[x >> 7]) for x < 512 -- one fp32 product, rounded once more to E, what the matrix form leaves in LDS -- and the
+// stored 16-bit element 512 + x' after the scales.  Byte and unaligned dword / 16-bit loads (memcpy): any alignment runs.
+template <class E> struct CacheFp8DS {
+    static __device__ __forceinline__ float load(const void *p, int64_t i, int x) {
+        const uint8_t *row = (const uint8_t *)p + i;
+        if (x < kFa2DsNope) {
+            float sc;
+            __builtin_memcpy(&sc, row + kFa2DsScaleOff + 4 * (x >> 7), 4);
+            float v = __builtin_amdgcn_cvt_f32_fp8((int)row[x], 0) * sc;
+            asm("" : "+v"(v));  // the fp32 product as it stands, then the rounding to E: never one fused operation
+            return E::round(v);
+        }
+        uint16_t h;
+        __builtin_memcpy(&h, row + kFa2DsRopeOff + 2 * (x - kFa2DsNope), 2);
+        return E::load(&h, 0);
+    }
+};
+// Element x of the cache row at offset `row`: the tile-scaled layout by row and column, every other cache type at row + x * stride.
+template <class C> constexpr bool kIsDS = false;
+template <class E> constexpr bool kIsDS<CacheFp8DS<E>> = true;
+template <class C> __device__ __forceinline__ auto cache_at(const void *p, int64_t row, int x, int64_t stride) {
+    if constexpr (kIsDS<C>) return C::load(p, row, x);
+    else return C::load(p, row + (int64_t)x * stride);
+}
+
 // A block-table entry as the kernels use it: clamped into the pool, so a wild entry cannot become an access outside it.
 __device__ __forceinline__ int fa2_decode_page(const int32_t *table, int64_t i, int num_blocks) {
     const int e = table[i];
@@ -178,6 +205,14 @@ bool fa2_decode_mla16_sd_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla16_sd(const Fa2DecodeProblem &p);
 bool fa2_decode_mla16_sdv_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla16_sdv(const Fa2DecodeProblem &p);
+
+// The dense calls over the tile-scaled fp8 cache (fa2_fwd_kvcache_mla_ds, _varlen_ds): kv_format as above, indices null.  The dense
+// instantiations of the latent kernel with the row dequantised while it is staged, every row of a tile at tile base + r * row stride
+// (fa2_decode_mla16_d.hip, _dv.hip: fixed, query-tiled packed); the VALU form is fa2_launch_decode_generic with the layout's loader.
+bool fa2_decode_mla16_d_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_d(const Fa2DecodeProblem &p);
+bool fa2_decode_mla16_dv_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla16_dv(const Fa2DecodeProblem &p);
 
 // One cache append as fa2_kvcache_append hands it over (fa2_decode_append.hip), arguments already checked.  Strides in elements of
 // each tensor's dtype.  It is the kernel's argument as well.

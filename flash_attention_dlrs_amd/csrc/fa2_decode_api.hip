@@ -149,12 +149,13 @@ struct DecodeCall {
     int32_t topk = 0;
     bool mla = false;  // fa2_fwd_kvcache_mla, _mla_fp8 (with `fp8`), _mla_varlen (with `packed`): V is (B, H_kv, S_k, d_v), d may reach 576; without it d_v = d
     int32_t d_v = 0;
-    // fa2_fwd_kvcache_mla_sparse_ds, _varlen_ds (with `sparse`, `mla`): FA2_KV_FORMAT_FP8_DS, K == V the byte tensor of 656-byte rows,
+    // fa2_fwd_kvcache_mla_sparse_ds, _varlen_ds (with `sparse`, `mla`) and the dense fa2_fwd_kvcache_mla_ds, _varlen_ds (with `mla`, the
+    // second with `packed`): FA2_KV_FORMAT_FP8_DS, K == V the byte tensor of 656-byte rows,
     // k_strides == v_strides in BYTES with a last stride of 1, d = 576, d_v = 512, no descales
     int32_t kv_format = 0;
 };
 
-// The forms of the call (the last two rows: the two list forms over the tile-scaled fp8 cache): fixed N_q, packed queries (query-tiled), the latent cache, packed queries over the latent cache, key
+// The forms of the call (the last four rows: the two list forms, then the two dense latent forms, over the tile-scaled fp8 cache): fixed N_q, packed queries (query-tiled), the latent cache, packed queries over the latent cache, key
 // lists over the latent cache, key lists of packed queries over the latent cache.  Each has a matrix kernel of its own beside a VALU kernel (`generic`: fa2_launch_decode_generic, the
 // lists their own) and the combine, which all share; `variant` is the id that forces the matrix kernel, and AUTO, GENERIC and that id
 // are the variants the form accepts: any other gets `unknown_variant`.
@@ -165,7 +166,7 @@ struct DecodeForm {
     const char *unknown_variant;
     int (*generic)(const Fa2DecodeProblem &) = fa2_launch_decode_generic;
 };
-const DecodeForm kForms[8] = {
+const DecodeForm kForms[10] = {
     {fa2_decode_mfma16_supports, fa2_launch_decode_mfma16, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mfma16_v_supports, fa2_launch_decode_mfma16_v, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mla16_supports, fa2_launch_decode_mla16, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
@@ -179,9 +180,13 @@ const DecodeForm kForms[8] = {
      fa2_launch_decode_sparse_generic},
     {fa2_decode_mla16_sdv_supports, fa2_launch_decode_mla16_sdv, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla sparse: unknown variant %d (auto 0, generic 1, mla16 3)",
      fa2_launch_decode_sparse_generic_v},
+    // rows 2 and 3 over the tile-scaled fp8 cache (fa2_fwd_kvcache_mla_ds, _varlen_ds): dense matrix kernels of their own, the shared
+    // VALU kernel with the layout's loader
+    {fa2_decode_mla16_d_supports, fa2_launch_decode_mla16_d, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla fp8_ds: unknown variant %d (auto 0, generic 1, mla16 3)"},
+    {fa2_decode_mla16_dv_supports, fa2_launch_decode_mla16_dv, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla fp8_ds: unknown variant %d (auto 0, generic 1, mla16 3)"},
 };
 const DecodeForm &form_of(const DecodeCall &c) {
-    if (c.kv_format == FA2_KV_FORMAT_FP8_DS) return kForms[c.packed ? 7 : 6];
+    if (c.kv_format == FA2_KV_FORMAT_FP8_DS) return kForms[c.sparse ? (c.packed ? 7 : 6) : (c.packed ? 9 : 8)];
     return kForms[c.sparse && c.packed ? 5 : c.sparse ? 4 : c.packed && c.mla ? 3 : c.mla ? 2 : c.packed ? 1 : 0];
 }
 
@@ -220,18 +225,19 @@ int check_descales(const char *who, const float *kd, const int64_t *kds, const f
 // Every check of an attention call, before any launch; on FA2_OK `p` is the problem to launch, num_splits resolved.
 int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
     if (c.kv_format == FA2_KV_FORMAT_FP8_DS) {  // what only the tile-scaled cache brings comes first
+        const char *who = c.sparse ? "kvcache mla sparse fp8_ds" : "kvcache mla fp8_ds";  // the list forms, the dense forms
         if (!c.K || !c.k_strides) {
-            fa2_set_error("kvcache mla sparse fp8_ds: null %s", !c.K ? "KV" : "kv_strides");
+            fa2_set_error("%s: null %s", who, !c.K ? "KV" : "kv_strides");
             return FA2_ERR_BAD_ARG;
         }
         for (int k = 0; k < 3; ++k)
             if (c.k_strides[k] < 0) {
-                fa2_set_error("kvcache mla sparse fp8_ds: negative strides are not supported (kv_strides, in bytes)");
+                fa2_set_error("%s: negative strides are not supported (kv_strides, in bytes)", who);
                 return FA2_ERR_BAD_ARG;
             }
         if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16) {
-            fa2_set_error("kvcache mla sparse fp8_ds: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16: the rotary columns of "
-                          "an fp8_ds row are stored in Q's 16-bit dtype", c.dtype_enum);
+            fa2_set_error("%s: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16: the rotary columns of "
+                          "an fp8_ds row are stored in Q's 16-bit dtype", who, c.dtype_enum);
             return FA2_ERR_UNSUPPORTED;
         }
     }
@@ -913,6 +919,49 @@ int fa2_fwd_kvcache_mla_sparse_varlen_ds(const void *Q, const void *KV, void *O,
     c.sparse = true; c.indices = indices; c.topk = topk;
     c.index_strides = index_strides ? is : nullptr;
     if (index_strides) { is[0] = 0; is[1] = index_strides[1]; is[2] = index_strides[0]; is[3] = index_strides[2]; }
+    c.kv_format = FA2_KV_FORMAT_FP8_DS;
+    return decode(c, nullptr);
+}
+
+int fa2_fwd_kvcache_mla_ds(const void *Q, const void *KV, void *O, void *L, const int64_t q_strides[4], const int64_t kv_strides[3],
+                           const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens, const int32_t *block_table,
+                           int64_t block_table_stride, int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t num_blocks,
+                           int32_t page_size, int32_t max_blocks, int32_t dtype_enum, int32_t causal, float scale, int32_t window_left,
+                           int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant,
+                           void *hip_stream) {
+    // fa2_fwd_kvcache_mla's call with the one byte tensor as K and V, its strides in bytes, and the format's d / d_v
+    const int64_t ks[4] = {kv_strides ? kv_strides[0] : 0, kv_strides ? kv_strides[1] : 0, kv_strides ? kv_strides[2] : 0, 1};
+    DecodeCall c;
+    c.Q = Q; c.K = KV; c.V = KV; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = kv_strides ? ks : nullptr; c.v_strides = c.k_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = block_table ? 0 : page_size; c.d = 576; c.dtype_enum = dtype_enum;
+    c.causal = causal; c.scale = scale; c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.mla = true; c.d_v = 512;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.kv_format = FA2_KV_FORMAT_FP8_DS;
+    return decode(c, nullptr);
+}
+
+int fa2_fwd_kvcache_mla_varlen_ds(const void *Q, const void *KV, void *O, void *L, const int64_t q_strides[3], const int64_t kv_strides[3],
+                                  const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
+                                  const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride, int32_t B,
+                                  int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks,
+                                  int32_t page_size, int32_t max_blocks, int32_t dtype_enum, int32_t causal, float scale,
+                                  int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace, int64_t workspace_bytes,
+                                  int32_t variant, void *hip_stream) {
+    // fa2_fwd_kvcache_mla_varlen's call, the cache as above
+    int64_t qs[4], os[4];
+    const int64_t ls[2] = {0, l_head_stride};
+    const int64_t ks[4] = {kv_strides ? kv_strides[0] : 0, kv_strides ? kv_strides[1] : 0, kv_strides ? kv_strides[2] : 0, 1};
+    DecodeCall c;
+    c.Q = Q; c.K = KV; c.V = KV; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = packed4(q_strides, qs); c.k_strides = kv_strides ? ks : nullptr; c.v_strides = c.k_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = S_k; c.d = 576; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.mla = true; c.d_v = 512;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
     c.kv_format = FA2_KV_FORMAT_FP8_DS;
     return decode(c, nullptr);
 }

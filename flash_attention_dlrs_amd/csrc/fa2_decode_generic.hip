@@ -18,6 +18,10 @@
 // softmax scale, vd into the fp32 normalised output before it is rounded or written as a partial.  C and (d, d_v) are independent:
 // fa2_fwd_kvcache_mla_fp8 reaches the fp8 instantiations with d up to 576 and a d_v of its own.
 //
+// Tile-scaled fp8 latent cache (fa2_fwd_kvcache_mla_ds, _varlen_ds): C = CacheFp8DS<E> (fa2_decode.h), K == V the byte tensor, ks == vs in
+// BYTES.  Element x of a row is dequantised and rounded to E as it is loaded, nothing is folded: the result is the E instantiation's on
+// the dequantised cache bit for bit.  Byte and unaligned loads: any alignment, any page size.
+//
 // Paged cache (fa2_fwd_kvcache_paged): PAGED is a template parameter as well, K and V a page pool behind a block table, any
 // page_size >= 1.  Key j of sequence b is row j % page_size of page table[b][j / page_size], the entry clamped to
 // [0, num_blocks - 1] before it becomes an address (a wild entry: a wrong result, never an access outside the pool).  For the
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
     }
     __syncthreads();
 
-    constexpr bool F8 = !__is_same(C, E);
+    constexpr bool F8 = !__is_same(C, E) && !kIsDS<C>;  // (the tile-scaled row carries its scales: no descale is folded)
     A c = sizeof(A) == 8 ? (A)a.c_log2e : (A)(float)a.c_log2e;
     A vd = 1;
     if constexpr (F8) {
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
                 kb = k_off + fa2_decode_page(tab, pg, a.num_blocks) * a.ks[0] + (int64_t)(key - pg * a.page_size) * a.ks[2];
             }
             for (int x = 0; x < d; ++x) {
-                const A kx = C::load(a.K, kb + (int64_t)x * a.ks[3]);
+                const A kx = cache_at<C>(a.K, kb, x, a.ks[3]);
 #pragma unroll
                 for (int r = 0; r < kRowsPerWave; ++r) dot[r] += q_lds[(wave * kRowsPerWave + r) * d + x] * kx;
             }
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
             for (int cc = 0; cc < DPL; ++cc) {
                 const int x = lane + 64 * cc;
                 if (x < dv) {
-                    const A v = C::load(a.V, vb + (int64_t)x * a.vs[3]);
+                    const A v = cache_at<C>(a.V, vb, x, a.vs[3]);
 #pragma unroll
                     for (int r = 0; r < kRowsPerWave; ++r) o[r][cc] += pr[r] * v;
                 }
@@ -271,6 +275,12 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     a.cu_q = p.cu_q; a.total_q = p.total_q; a.max_q = p.max_q;  // (N_q = max_q sizes the query tiles)
+    if (p.kv_format == FA2_KV_FORMAT_FP8_DS) {  // the tile-scaled fp8 cache under 16-bit Q, O, L: strides in bytes
+        if (p.dtype == FA2_DTYPE_F16) return launch_e<ElemF16, CacheFp8DS<ElemF16>>(p, a);
+        if (p.dtype == FA2_DTYPE_BF16) return launch_e<ElemBF16, CacheFp8DS<ElemBF16>>(p, a);
+        fa2_set_error("kvcache mla fp8_ds: the fp8_ds cache needs f16 / bf16 Q (dtype enum %d)", p.dtype);
+        return FA2_ERR_UNSUPPORTED;
+    }
     if (p.kv_dtype != p.dtype) {  // fp8 cache under 16-bit Q, O, L
         const bool e4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
         if ((e4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.dtype == FA2_DTYPE_F16)

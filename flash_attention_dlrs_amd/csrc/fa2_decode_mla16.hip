@@ -93,7 +93,7 @@
 // without rows.  With `start` the packed row and N_q = 1 every expression below is the list-addressed kernel's: the query tiling of
 // VQ (the rotation along x, position-major rows, [q0, q1)) is taken with VQ && !SP alone, the packed partial layout with VQ.
 //
-// Tile-scaled fp8 latent cache (fa2_fwd_kvcache_mla_sparse_ds, _varlen_ds).  C = CacheDS, SP only, instantiated in fa2_decode_mla16_sd.hip
+// Tile-scaled fp8 latent cache (fa2_fwd_kvcache_mla_sparse_ds, _varlen_ds).  C = CacheDS with SP, instantiated in fa2_decode_mla16_sd.hip
 // and _sdv.hip (FA2_DECODE_DS) alone.  A row is 656 bytes (fa2_decode.h): 512 e4m3 bytes, 4 fp32 scales of its 128-column tiles, 64 rotary
 // columns in T.  Only staging differs, 41 loads of 16 bytes a row: 8 passes of latent bytes, a half-wave a row, lane (hv, ld) bytes 16 ld ..
 // + 15 of row 2 ps + hv with the scale of ITS tile ld >> 3 (a dword load of its own); two passes of rotary pieces as the 16-bit tail.
@@ -101,6 +101,13 @@
 // map's chunks 2 ld, 2 ld + 1 -- the LDS image is the 16-bit kernel's over the dequantised row.  Nothing is folded into the softmax scale
 // or the output: O and L are the 16-bit instantiation's on the dequantised cache bit for bit.  A slot that is no key loads neither bytes
 // nor scale.
+//
+// The dense calls over the tile-scaled cache (fa2_fwd_kvcache_mla_ds, _varlen_ds).  C = CacheDS without SP, instantiated in
+// fa2_decode_mla16_d.hip and _dv.hip alone.  Every row of a tile has ONE address rule, tile base + r * row stride -- the base the
+// sequence's, or (paged, page_size % 64 == 0) one scalar table entry per tile -- so the lanes keep three pointers for the whole walk
+// (latent bytes, their scale, rotary piece) and a pass adds a uniform offset: no per-lane row offsets, no shuffles, no lane reads.  The
+// passes, the gate (a row at or past the split's end loads neither bytes nor scale: zeros times 0), stage_write and so the LDS image are
+// the list form's; the band test, the splits and the epilogue the dense kernel's.
 #include "fa2_decode.h"
 #include "fa2_mfma.h"
 
@@ -113,10 +120,6 @@
 #ifndef FA2_DECODE_DS
 #define FA2_DECODE_DS 0
 #endif
-#if FA2_DECODE_DS && !FA2_DECODE_SPARSE
-#error "the tile-scaled cache is read through key lists only"
-#endif
-
 namespace {
 
 struct DecodeMlaArgs {
@@ -172,7 +175,6 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     using M = Mma<T>;
     constexpr bool DS = __is_same(C, CacheDS);  // the tile-scaled row: dequantised to T while it is staged, nothing folded
     constexpr bool F8 = !__is_same(C, T) && !DS;
-    static_assert(!DS || SP, "the tile-scaled cache is read through key lists only");
     using frag = typename M::frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LDS_PTR(char) lds = (LDS_PTR(char))smem;
@@ -273,6 +275,15 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
     const char *kg_b = kbase + (int64_t)sb_row * a.ks[2] + sb_ch * 16;
     auto f8_row = [&](int ps) { return (64 * ps + lane) / kLPR8; };  // < 16
     auto f8_ld = [&](int ps) { return (64 * ps + lane) % kLPR8; };
+    // tile-scaled cache, dense: lane (hv, ld) of latent pass ps reads bytes 16 ld .. + 15 of row 16w + 2 ps + hv and the scale of its
+    // tile ld >> 3; the rotary passes are the 16-bit tail on the row's last 128 bytes.  Three pointers for the whole walk, a uniform
+    // offset per pass and tile
+    [[maybe_unused]] const char *kg_d = nullptr, *kg_s = nullptr, *kg_r = nullptr;
+    if constexpr (DS && !SP) {
+        kg_d = kg_w + (int64_t)(lane >> 5) * a.ks[2] + (lane & 31) * 16;
+        kg_s = kg_w + (int64_t)(lane >> 5) * a.ks[2] + kFa2DsScaleOff + 4 * ((lane & 31) >> 3);
+        kg_r = kbase + (int64_t)sb_row * a.ks[2] + kFa2DsRopeOff + (lane & 7) * 16;
+    }
 
     // paged: the walk over the pages, as in fa2_decode_mfma16.hip: stage_load takes the tiles in order, a tile is 64 keys on a
     // multiple of 64 and page_size is a multiple of 64, so (pg_i, pg_row) advance by 64 rows per tile and wrap at page_size.
@@ -394,7 +405,20 @@ __global__ __launch_bounds__(256, 1) void fa2_decode_mla16_kernel(const DecodeMl
                 ++pg_i;
             }
         }
-        if constexpr (F8) {
+        if constexpr (DS && !SP) {
+            const int hv = lane >> 5;  // (kg_d, kg_s, kg_r: beside kg_a)
+#pragma unroll
+            for (int ps = 0; ps < 8; ++ps) {
+                const bool ok = kb0 + rel + 16 * wave + 2 * ps + hv < ke;  // past the split's end (<= N_k): neither bytes nor scale
+                sreg[ps] = ok ? *(const u32x4 *)(kg_d + toff + (int64_t)(2 * ps) * a.ks[2]) : u32x4{0, 0, 0, 0};
+                dsc[ps] = ok ? *(const float *)(kg_s + toff + (int64_t)(2 * ps) * a.ks[2]) : 0.0f;
+            }
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb) {
+                const bool ok = kb0 + rel + sb_row + 8 * jb < ke;
+                sreg[8 + jb] = ok ? *(const u32x4 *)(kg_r + toff + (int64_t)(8 * jb) * a.ks[2]) : u32x4{0, 0, 0, 0};
+            }
+        } else if constexpr (F8) {
 #pragma unroll
             for (int ps = 0; ps < kStage8; ++ps) {
                 const int row = f8_row(ps);
@@ -758,7 +782,8 @@ int launch(const Fa2DecodeProblem &p) {
     if (kDS && !supports(p)) {
         fa2_set_error("kvcache mla16 kernel over the fp8_ds cache: needs f16/bf16 Q, unit last strides, a 16-byte aligned cache base and row, "
                       "head and batch / block strides that are multiples of 16 bytes (other layouts: the generic kernel), 16-byte aligned "
-                      "Q and O rows (and workspace), scale > 0");
+                      "Q and O rows (and workspace), scale > 0%s",
+                      p.table && !kSP ? ", page_size % 64 == 0 for a paged cache (other page sizes: the generic kernel)" : "");
         return FA2_ERR_UNSUPPORTED;
     }
     if (!supports(p)) {
@@ -793,12 +818,18 @@ int launch(const Fa2DecodeProblem &p) {
 
 }  // namespace
 
-#if FA2_DECODE_DS && FA2_DECODE_VARLEN_Q
+#if FA2_DECODE_DS && FA2_DECODE_SPARSE && FA2_DECODE_VARLEN_Q
 bool fa2_decode_mla16_sdv_supports(const Fa2DecodeProblem &p) { return supports(p); }
 int fa2_launch_decode_mla16_sdv(const Fa2DecodeProblem &p) { return launch(p); }
-#elif FA2_DECODE_DS
+#elif FA2_DECODE_DS && FA2_DECODE_SPARSE
 bool fa2_decode_mla16_sd_supports(const Fa2DecodeProblem &p) { return supports(p); }
 int fa2_launch_decode_mla16_sd(const Fa2DecodeProblem &p) { return launch(p); }
+#elif FA2_DECODE_DS && FA2_DECODE_VARLEN_Q
+bool fa2_decode_mla16_dv_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_dv(const Fa2DecodeProblem &p) { return launch(p); }
+#elif FA2_DECODE_DS
+bool fa2_decode_mla16_d_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla16_d(const Fa2DecodeProblem &p) { return launch(p); }
 #elif FA2_DECODE_SPARSE && FA2_DECODE_VARLEN_Q
 bool fa2_decode_mla16_sv_supports(const Fa2DecodeProblem &p) { return supports(p); }
 int fa2_launch_decode_mla16_sv(const Fa2DecodeProblem &p) { return launch(p); }

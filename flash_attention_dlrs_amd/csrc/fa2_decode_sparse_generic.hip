@@ -54,33 +54,7 @@ struct CacheF8E5M2 {
     }
 };
 
-// The tile-scaled fp8 latent cache (fa2_decode.h, kv_format FP8_DS) under Q's 16-bit type E: `i` is the BYTE offset of the row (the
-// strides of such a cache are in bytes), element x of it is E(fp32(byte x) * scale[x >> 7]) for x < 512 -- one fp32 product, rounded
-// once more to E, what the matrix form leaves in LDS -- and the stored 16-bit element 512 + x' after the scales.  Byte and unaligned
-// dword / 16-bit loads (memcpy): any alignment runs.
-template <class E> struct CacheFp8DS {
-    static __device__ __forceinline__ float load(const void *p, int64_t i, int x) {
-        const uint8_t *row = (const uint8_t *)p + i;
-        if (x < kFa2DsNope) {
-            float sc;
-            __builtin_memcpy(&sc, row + kFa2DsScaleOff + 4 * (x >> 7), 4);
-            float v = __builtin_amdgcn_cvt_f32_fp8((int)row[x], 0) * sc;
-            asm("" : "+v"(v));  // the fp32 product as it stands, then the rounding to E: never one fused operation
-            return E::round(v);
-        }
-        uint16_t h;
-        __builtin_memcpy(&h, row + kFa2DsRopeOff + 2 * (x - kFa2DsNope), 2);
-        return E::load(&h, 0);
-    }
-};
-// Element x of the cache row at offset `row`: the tile-scaled layout by row and column, every other cache type at row + x * stride.
-template <class C> constexpr bool kIsDS = false;
-template <class E> constexpr bool kIsDS<CacheFp8DS<E>> = true;
-template <class C> __device__ __forceinline__ auto cache_at(const void *p, int64_t row, int x, int64_t stride) {
-    if constexpr (kIsDS<C>) return C::load(p, row, x);
-    else return C::load(p, row + (int64_t)x * stride);
-}
-
+// (the tile-scaled fp8 latent cache, kv_format FP8_DS: CacheFp8DS<E> and cache_at of fa2_decode.h)
 struct SparseGenericArgs {
     const void *Q, *K, *V;
     void *O, *L;

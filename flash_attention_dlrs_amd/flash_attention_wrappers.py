@@ -585,7 +585,7 @@ def _kvcache_mla_forward(Q, K_cache, V_cache, cache_seqlens, dev, causal, scale,
 
 def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=512, causal=False, scale=1.0, window=None, num_splits=0,
                                        variant="auto", block_table=None, kv_descale=None, kv_new=None, rotary_cos=None, rotary_sin=None,
-                                       rotary_interleaved=False):
+                                       rotary_interleaved=False, kv_format=None):
     """Multi-head latent attention decode, absorbed form, over the shared latent cache (fa2_fwd_kvcache_mla) -> (O, L).  Q
     (B, H, N_q, d); KV_cache (B, H_kv, S_k, d) or, with block_table, the page pool (num_blocks, H_kv, page_size, d): one row per key,
     d_v latent columns followed by the rotary ones (DeepSeek-V2 / V3 / R1, Kimi: H_kv = 1, d = 576, d_v = 512).  The score takes all
@@ -608,11 +608,35 @@ def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=5
     the new rows at cache_seqlens[b] + t and of Q (a copy: Q itself is not modified) at cache_seqlens[b] + i for row i when the call
     is causal or windowed, every row at cache_seqlens[b] otherwise, as flash-attn does; apply_rotary on those columns is the
     arithmetic, bit for bit.  They need kv_new.  Without kv_new the cache is only read.  Packed (ragged) queries over the same cache:
-    flash_attention_mla_varlen_decode_forward."""
+    flash_attention_mla_varlen_decode_forward.
+
+    kv_format="fp8_ds" (fa2_fwd_kvcache_mla_ds): KV_cache is the tile-scaled fp8 cache of flash_attention_mla_sparse_decode_forward, a
+    torch.uint8 tensor (B, H_kv, S_k, 656) or pool (num_blocks, H_kv, page_size, 656); Q float16 / bfloat16 with d = 576, d_v 512,
+    kv_descale None.  The dense call an engine holding that cache makes where it skips the indexer (at most topk keys, draft-token
+    verification, no sparsity).  The result is this call's on dequantize_mla_cache_ds(KV_cache, Q.dtype) bit for bit at the same
+    num_splits and variant; nothing is dequantised in memory, rows behind cache_seqlens[b] are never read.  "mla16" needs 16-byte
+    aligned rows (base and the three outer strides in bytes) and page_size % 64 == 0; "auto" takes "generic" otherwise.  The append
+    side is mla_kvcache_append(..., kv_format="fp8_ds"), called first: kv_new and the rotary tables are a ValueError here."""
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError("mla decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < KV_cache.shape[3]:
         raise ValueError(f"mla decode: d_v must be an int in [1, d - 1] = [1, {KV_cache.shape[3] - 1}], got {d_v!r}")
+    if kv_format is not None:  # the tile-scaled byte cache: its own rules, then the 16-bit call's on a stand-in of its rows
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 4:
+            raise ValueError(f"mla decode: Q must be a tensor (B, H, N_q, d), got {tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
+        _ds_no_append("mla decode", kv_new, rotary_cos, rotary_sin)
+        stand_in = _check_ds_cache("mla decode", Q, KV_cache, kv_format, d_v, kv_descale)
+        check_kvcache_args(Q, stand_in, stand_in, cache_seqlens, window, num_splits, None, None, block_table)
+        if variant not in _lib.KVCACHE_MLA_VARIANTS:
+            raise ValueError(f"mla decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
+        _check_dev(dev, Q, KV_cache, KV_cache)
+        B, H, N_q, d = Q.shape
+        dtype = convert_triton_dtype(Q.dtype)
+        n = num_splits or _lib.kvcache_mla_num_splits(B, H, KV_cache.shape[1], N_q, _capacity(KV_cache, block_table), d, d_v, dtype)
+        O, L, ws = _kvcache_outputs(Q, (B, H, N_q, d_v), (B, H, N_q), _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0)
+        _lib.fa2_fwd_kvcache_mla_ds(Q, KV_cache, O, L, cache_seqlens, dtype, block_table=block_table, causal=causal, scale=scale,
+                                    window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
     append = None
     if kv_new is not None or rotary_cos is not None or rotary_sin is not None:
         check_mla_append_args(KV_cache, kv_new, cache_seqlens, d_v, kv_descale, block_table, rotary_cos, rotary_sin, Q)
@@ -853,16 +877,20 @@ def flash_attention_varlen_kvcache_forward(Q, K_cache, V_cache, cu_seqlens_q, ma
 
 
 def check_mla_varlen_args(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v=512, window=None, num_splits=0, kv_descale=None,
-                          block_table=None, kv_new=None, rotary_cos=None, rotary_sin=None):
+                          block_table=None, kv_new=None, rotary_cos=None, rotary_sin=None, kv_format=None):
     """ValueError for what flash_attention_mla_varlen_decode_forward cannot take: the packed Q, cu_seqlens_q and max_seqlen_q by the
     rules of check_varlen_kvcache_args, the latent cache, d_v, kv_descale, cache_seqlens, block_table, window and num_splits by those
     of flash_attention_mla_decode_forward, and with kv_new or the rotary tables every rule of check_mla_append_args for packed tokens
-    over the same cu_seqlens_q.  Pure: takes CPU tensors as well."""
+    over the same cu_seqlens_q.  With kv_format the tile-scaled byte cache's own rules, then these on a stand-in of its rows.  Pure:
+    takes CPU tensors as well."""
     if not isinstance(Q, torch.Tensor) or Q.dim() != 3 or Q.shape[0] < 1:
         raise ValueError(f"mla varlen decode: Q must be packed (total_q, H, d) with total_q >= 1, got "
                          f"{tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q).__name__}")
     if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4:
         raise ValueError("mla varlen decode: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d)")
+    if kv_format is not None:  # as in check_mla_sparse_args
+        _ds_no_append("mla varlen decode", kv_new, rotary_cos, rotary_sin)
+        KV_cache = _check_ds_cache("mla varlen decode", Q, KV_cache, kv_format, d_v, kv_descale)
     d = KV_cache.shape[3]
     if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < d:
         raise ValueError(f"mla varlen decode: d_v must be an int in [1, d - 1] = [1, {d - 1}], got {d_v!r}")
@@ -896,7 +924,7 @@ def check_mla_varlen_args(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens
 
 def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, d_v=512, causal=False,
                                               scale=1.0, window=None, num_splits=0, variant="auto", block_table=None, kv_descale=None,
-                                              kv_new=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+                                              kv_new=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=False, kv_format=None):
     """Multi-head latent attention of variable-length (packed) queries over the shared latent cache (include/fa2_fwd.h
     fa2_fwd_kvcache_mla_varlen) -> (O, L): the verification of MTP / draft tokens, a mixed step of a prefill chunk beside one-token
     decodes, a prefix-cached chunk, in one call.  Q (total_q, H, d), any strides; cu_seqlens_q int32 (B + 1,) on Q's device and
@@ -916,9 +944,13 @@ def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seq
     n_q(b) keys (at most the capacity).  cache_seqlens is required, holds the lengths BEFORE the append and is not modified.
     rotary_cos, rotary_sin rotate the columns [d_v, d_v + rotary_dim) of new row t at cache_seqlens[b] + t and of Q (a copy) row i at
     cache_seqlens[b] + i when the call is causal or windowed, every row at cache_seqlens[b] otherwise:
-    flash_attention_mla_decode_forward's rule.  They need kv_new."""
+    flash_attention_mla_decode_forward's rule.  They need kv_new.
+
+    kv_format="fp8_ds" (fa2_fwd_kvcache_mla_varlen_ds): the tile-scaled fp8 byte cache, as in flash_attention_mla_decode_forward; the
+    result is this call's on dequantize_mla_cache_ds(KV_cache, Q.dtype) bit for bit at the same num_splits and variant.  kv_new and
+    the rotary tables are a ValueError: mla_kvcache_append_varlen(..., kv_format="fp8_ds") goes first."""
     check_mla_varlen_args(Q, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, window, num_splits, kv_descale, block_table,
-                          kv_new, rotary_cos, rotary_sin)
+                          kv_new, rotary_cos, rotary_sin, kv_format)
     if variant not in _lib.KVCACHE_MLA_VARIANTS:
         raise ValueError(f"mla varlen decode: variant must be one of {sorted(_lib.KVCACHE_MLA_VARIANTS)}, got {variant!r}")
     _check_dev(dev, Q, KV_cache, KV_cache)
@@ -927,6 +959,11 @@ def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seq
     dtype = convert_triton_dtype(Q.dtype)
     n = num_splits or _lib.kvcache_mla_varlen_num_splits(B, H, H_kv, total_q, max_seqlen_q, _capacity(KV_cache, block_table), d, d_v, dtype)
     O, L, ws = _kvcache_outputs(Q, (total_q, H, d_v), (H, total_q), _lib.kvcache_varlen_workspace_bytes(total_q, H, d_v, n) if n > 1 else 0)
+    if kv_format is not None:
+        _lib.fa2_fwd_kvcache_mla_varlen_ds(Q, KV_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype, block_table=block_table,
+                                           causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
+                                           variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+        return O, L
     kd = _kvcache_descale("kv_descale", kv_descale, Q, B, H_kv)
     if kv_new is not None:
         c_new, pe_new = _mla_sources(kv_new, d_v)
@@ -998,6 +1035,13 @@ def _check_ds_cache(who, Q, KV_cache, kv_format, d_v, kv_descale, q_name="Q"):
     if any(s < 0 for s in KV_cache.stride()):
         raise ValueError(f"{who}: KV_cache with negative strides is not supported")
     return torch.empty((), dtype=Q.dtype, device=Q.device).expand(*KV_cache.shape[:3], DS_NOPE + DS_ROPE)
+
+
+def _ds_no_append(who, kv_new, rotary_cos, rotary_sin):
+    """The dense calls over kv_format="fp8_ds" only read the cache (a fused append is out of scope, as for the sparse calls)."""
+    if kv_new is not None or rotary_cos is not None or rotary_sin is not None:
+        raise ValueError(f"{who}: kv_format='fp8_ds' takes no kv_new / rotary_cos / rotary_sin: write the new rows with "
+                         f"mla_kvcache_append(..., kv_format=\"fp8_ds\") (or mla_kvcache_append_varlen) first, then call this")
 
 
 def _sparse_indices(indices, B, H_kv, N_q):

@@ -955,6 +955,46 @@ int fa2_fwd_kvcache_mla_sparse_varlen_ds(const void *Q, const void *KV, void *O,
                                          void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
 /*
+ * Dense MLA decode over the tile-scaled fp8 latent cache, fixed and packed: fa2_fwd_kvcache_mla and fa2_fwd_kvcache_mla_varlen with the
+ * ONE byte tensor KV of fa2_fwd_kvcache_mla_sparse_ds (its row, its three byte strides) in K's, V's and the descales' place; d = 576
+ * and d_v = 512 are the format's.  What an engine that holds this cache calls where it skips the indexer: a sequence of at most topk
+ * keys, the verification of draft tokens (N_q >= 2 shares one pass over the keys between positions), a model run without sparsity.
+ *
+ *   Result.   The 16-bit call's on the dequantised cache D (above), bit for bit at the same num_splits and variant: the scales are
+ *             applied while a row is staged, nothing is folded into the softmax scale or the output, nothing is dequantised in
+ *             memory.  Neither bytes nor scales of a row at or past a split's end, or behind cache_seqlens[b], are read.  causal, the
+ *             window sides, empty sequences, the splits, the workspace and the combine are the dense MLA calls'.
+ *   Splits.   fa2_kvcache_mla_num_splits / fa2_kvcache_mla_varlen_num_splits at d 576, d_v 512; the workspace is
+ *             fa2_kvcache_workspace_bytes / fa2_kvcache_varlen_workspace_bytes at d_v 512.
+ *   Variants. FA2_KVCACHE_VARIANT_MLA16 needs 16-byte aligned rows (KV's base and the three strides multiples of 16 bytes),
+ *             page_size % 64 == 0 when paged, and the Q / O / workspace rules of fa2_fwd_kvcache_mla.  FA2_KVCACHE_VARIANT_GENERIC: any
+ *             alignment, any page size.  AUTO: MLA16 where it runs, else GENERIC.  A forced MLA16 on a problem it cannot run returns
+ *             FA2_ERR_UNSUPPORTED.
+ *
+ * Errors: FA2_ERR_BAD_ARG for a null KV or kv_strides and a negative kv stride, FA2_ERR_UNSUPPORTED for a dtype_enum other than
+ * F16 / BF16, then the dense MLA calls'; all before any launch.  block_table null: the contiguous cache (the fixed call: page_size
+ * carries S_k, as in fa2_fwd_kvcache_mla).
+ */
+int fa2_fwd_kvcache_mla_ds(const void *Q, const void *KV, void *O, void *L,
+                           const int64_t q_strides[4], const int64_t kv_strides[3],
+                           const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                           const int32_t *block_table, int64_t block_table_stride,
+                           int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                           int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                           int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                           int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+int fa2_fwd_kvcache_mla_varlen_ds(const void *Q, const void *KV, void *O, void *L,
+                                  const int64_t q_strides[3], const int64_t kv_strides[3],
+                                  const int64_t o_strides[3], int64_t l_head_stride,
+                                  const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                  const int32_t *block_table, int64_t block_table_stride,
+                                  int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks,
+                                  int32_t dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                                  int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/*
  * The MLA indexer (DeepSeek-V3.2's lightning indexer): the stage in front of fa2_fwd_kvcache_mla_sparse.  It scores every cached
  * token against every query token and makes the key lists that call takes.  Three entry points: the scores alone, the selection
  * alone over any fp32 logits, and both on one stream.
