@@ -31,8 +31,11 @@ rows: the 16-bit call, the one-descale e4m3 call, `torch` dequantisation of the 
 list at its own auto num_splits (the route the dense form replaces).  The sides ALTERNATE call by call in one traced child, a mark
 kernel between them, as benchmarks/bench_mla_sparse.py --kv-format fp8_ds does; the copies are sized by the smallest row (576 B).
 
+--q-dtype e4m3: the fp8-query call (fa2_fwd_kvcache_mla_q8, variant mla8) against mla16 with bf16 Q over the same e4m3 cache on
+Q8_CASES, each at its own auto num_splits, alternated call by call under device events (kind=q8).
+
 Records:
-  kind=kv_format      --kv-format fp8_ds: per shape the sides' avg / min / max / stddev, fp8_ds over each other side, and for each whether
+  kind=kv_format     --kv-format fp8_ds: per shape the sides' avg / min / max / stddev, fp8_ds over each other side, and for each whether
                       the min-max ranges overlap;
   kind=append        --append: per case, the per-run avg / min / max / stddev of both sides, their ratio, the append launch alone;
   kind=kernels        one per shape and cache form: the sides' avg / min / max / stddev in microseconds, auto_over_generic;
@@ -434,6 +437,64 @@ def run_append(names, args, fh):
              append_hbm_share_at_min=round(c.append_bytes / (a_min * 1e-6) / HBM_COPY_RATE, 6))
 
 
+Q8_CASES = {f"h{H}_q{N_q}_b{B}_n{S}": (B, H, N_q, S) for H in (128, 16) for N_q in (1, 2, 4) for B, S in ((1, 32768), (16, 8192), (128, 4096))}
+
+
+def run_q8(names, args, fh):
+    """--q-dtype e4m3: fa2_fwd_kvcache_mla_q8 (variant mla8: e4m3 Q, the matrix work in fp8) against the route the same e4m3 cache had
+    before it, fa2_fwd_kvcache_mla_fp8 with bf16 Q (variant mla16), each at its own auto num_splits, over rotating copies of the cache.
+    One launch (plus the combine) a side: the sides alternate call by call in this one process, device events around each call,
+    --repeats runs per case for the spread of the averages."""
+    import torch
+    import flash_attention_dlrs_amd as fa
+    from flash_attention_dlrs_amd import _lib
+    dev, e4 = torch.device("cuda:0"), torch.float8_e4m3fn
+    for name in names:
+        B, H, N_q, S = Q8_CASES[name]
+        copies = max(2, math.ceil(300e6 / (D * B * S)))
+        quant = [fa.quantize_kv_cache((torch.randn(B, 1, S, D, device=dev) * 0.8).to(torch.bfloat16), e4) for _ in range(copies)]
+        Q = (torch.randn(B, H, N_q, D, device=dev) * 0.8).to(torch.bfloat16)
+        Q8, qd = fa.quantize_kv_cache(Q.view(B, 1, H * N_q, D), e4)
+        Q8 = Q8.view(B, H, N_q, D)
+        lens = torch.full((B,), S, dtype=torch.int32, device=dev)
+        O, L16 = torch.empty(B, H, N_q, D_V, dtype=torch.bfloat16, device=dev), torch.empty(B, H, N_q, dtype=torch.bfloat16, device=dev)
+        L32 = torch.empty(B, H, N_q, dtype=torch.float32, device=dev)
+        n8 = _lib.kvcache_mla_q8_num_splits(B, H, 1, N_q, S, D, D_V, _lib.FA2_DTYPE_F8E4M3, _lib.FA2_DTYPE_F8E4M3)
+        n16 = _lib.kvcache_mla_num_splits(B, H, 1, N_q, S, D, D_V, _lib.FA2_DTYPE_BF16)
+        ws = torch.empty(max(_lib.kvcache_workspace_bytes(B, H, N_q, D_V, max(n8, n16)) // 4, 1), dtype=torch.float32, device=dev)
+        kw = dict(scale=D ** -0.5, workspace=ws)
+
+        def mla8(i):
+            kv, ds = quant[i % copies]
+            _lib.fa2_fwd_kvcache_mla_q8(Q8, kv, kv[..., :D_V], O, L32, lens, _lib.FA2_DTYPE_BF16, _lib.FA2_DTYPE_F8E4M3, _lib.FA2_DTYPE_F8E4M3,
+                                        q_descale=qd, k_descale=ds, v_descale=ds, num_splits=n8, variant=_lib.KVCACHE_MLA_Q8_VARIANTS["mla8"], **kw)
+
+        def mla16(i):
+            kv, ds = quant[i % copies]
+            _lib.fa2_fwd_kvcache_mla_fp8(Q, kv, kv[..., :D_V], O, L16, lens, _lib.FA2_DTYPE_BF16, _lib.FA2_DTYPE_F8E4M3, k_descale=ds,
+                                         v_descale=ds, num_splits=n16, variant=_lib.KVCACHE_MLA_VARIANTS["mla16"], **kw)
+        sides = (("mla8", mla8), ("mla16", mla16))
+        runs = {k: [] for k, _ in sides}
+        for _ in range(args.repeats):
+            times = {k: [] for k, _ in sides}
+            for it in range(args.iters + 3):
+                for k, f in sides:
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    f(it)
+                    b.record()
+                    b.synchronize()
+                    if it >= 3:
+                        times[k].append(a.elapsed_time(b) * 1e3)
+            for k in times:
+                runs[k].append(stats_us(times[k]))
+        a8, a16 = [r["avg_us"] for r in runs["mla8"]], [r["avg_us"] for r in runs["mla16"]]
+        emit(fh, kind="q8", case=name, B=B, H=H, N_q=N_q, N_k=S, num_splits_mla8=n8, num_splits_mla16=n16, mla8=runs["mla8"],
+             mla16=runs["mla16"], mla8_over_mla16=[round(x / y, 4) for x, y in zip(a8, a16)],
+             ranges_overlap=max(a8) >= min(a16) and max(a16) >= min(a8))
+        del quant
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default=None, help="default: every case (of DS_CASES with --kv-format)")
@@ -454,7 +515,13 @@ def main():
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
+    ap.add_argument("--q-dtype", choices=("e4m3",),
+                    help="time the fp8-query call (mla8) against mla16 with bf16 Q over the same e4m3 cache on Q8_CASES (kind=q8)")
     args = ap.parse_args()
+    if args.q_dtype:
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "a") as fh:
+            return run_q8((args.cases or ",".join(Q8_CASES)).split(","), args, fh)
     if args.format_case:
         return run_format_pass(args.format_case, args)
     names = (args.cases or ",".join(DS_CASES if args.kv_format else CASES)).split(",")

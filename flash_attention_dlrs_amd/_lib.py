@@ -69,7 +69,7 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_mla_indexer_prepare_q", "fa2_mla_indexer_prepare_q_varlen", "fa2_mla_indexer_append_rot",
            "fa2_mla_indexer_append_varlen_rot",
            "fa2_topk_indices_split", "fa2_topk_indices_varlen_split", "fa2_topk_workspace_bytes", "fa2_topk_num_splits",
-           "fa2_fwd_kvcache_mla_ds", "fa2_fwd_kvcache_mla_varlen_ds")
+           "fa2_fwd_kvcache_mla_ds", "fa2_fwd_kvcache_mla_varlen_ds", "fa2_fwd_kvcache_mla_q8", "fa2_kvcache_mla_q8_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -81,6 +81,8 @@ BWD_VARLEN_DV_VARIANTS = {"auto": 0, "generic": 1, "mfma16dv": 4}
 KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
 # ... and the latent-cache call (fa2_fwd_kvcache_mla) its own set: FA2_KVCACHE_VARIANT_MLA16 in the d 64 / 128 matrix form's place
 KVCACHE_MLA_VARIANTS = {"auto": 0, "generic": 1, "mla16": 3}
+# ... and its fp8-query entry point (fa2_fwd_kvcache_mla_q8) its own: FA2_KVCACHE_VARIANT_MLA8 in MLA16's place
+KVCACHE_MLA_Q8_VARIANTS = {"auto": 0, "generic": 1, "mla8": 4}
 # ... and the MLA indexer (fa2_mla_indexer_logits, fa2_mla_indexer_topk) its own: FA2_INDEXER_VARIANT_*
 INDEXER_VARIANTS = {"auto": 0, "generic": 1, "idx16": 2}
 # ... and its fp8-query entry points (the _q8 calls) theirs: FA2_INDEXER_VARIANT_IDX8 in IDX16's place, each set refusing the other's
@@ -241,6 +243,12 @@ def lib():
             [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_mla_num_splits.restype = ctypes.c_int32
         l.fa2_kvcache_mla_num_splits.argtypes = [ctypes.c_int32] * 8
+        # ... with fp8 queries: q_descale and its strides after the cache's, q_dtype_enum after kv_dtype_enum
+        l.fa2_fwd_kvcache_mla_q8.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_q8.argtypes = [vp] * 5 + [i64p] * 5 + [vp, vp, ctypes.c_int64, vp, vp, i64p, i64p, vp, i64p] + \
+            [ctypes.c_int32] * 13 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_mla_q8_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_mla_q8_num_splits.argtypes = [ctypes.c_int32] * 9
         # the latent-cache append: fa2_kvcache_append's order with one cache tensor and one descale, c_new / pe_new in k_new / v_new's
         # place, d_v after d
         l.fa2_kvcache_mla_append.restype = ctypes.c_int
@@ -757,6 +765,30 @@ def fa2_fwd_kvcache_mla_fp8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_e
             None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, *_descale_args(k_descale, v_descale), B, H,
             K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum), int(kv_dtype_enum), int(bool(causal)), float(scale),
             *_window_sides(window), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
+
+
+def kvcache_mla_q8_num_splits(B, H, H_kv, N_q, S_k, d, d_v, q_dtype_enum, kv_dtype_enum):
+    """What num_splits = 0 resolves to for a latent-cache decode call with fp8 queries (fa2_kvcache_mla_q8_num_splits)."""
+    return int(lib().fa2_kvcache_mla_q8_num_splits(B, H, H_kv, N_q, S_k, d, d_v, int(q_dtype_enum), int(kv_dtype_enum)))
+
+
+def fa2_fwd_kvcache_mla_q8(Q, K, V, O, L, cache_seqlens, dtype_enum, kv_dtype_enum, q_dtype_enum, q_descale=None, k_descale=None,
+                           v_descale=None, block_table=None, causal=False, scale=1.0, window=None, num_splits=0, workspace=None,
+                           variant=0):
+    """Launch fa2_fwd_kvcache_mla_fp8 with fp8 queries (include/fa2_fwd.h fa2_fwd_kvcache_mla_q8) on the current stream of Q's device.
+    Q in q_dtype_enum and K / V in kv_dtype_enum are fp8, O is in dtype_enum (f16 / bf16), L is float32; q_descale as the cache's
+    descales: a float32 tensor on the device viewed as (B, H_kv), or None for 1."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    B, H, N_q, d = Q.shape
+    tb_ptr, tb_st, _, nb, _, mb = _table_args(K, block_table)
+    _launch(lib().fa2_fwd_kvcache_mla_q8, Q,
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), L.data_ptr(),
+            _i64(Q.stride()), _i64(K.stride()), _i64(V.stride()), _i64(O.stride()), _i64((L.stride(0), L.stride(1))),
+            None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, *_descale_args(k_descale, v_descale),
+            _ptr(q_descale), None if q_descale is None else _i64(q_descale.stride()), B, H,
+            K.shape[1], N_q, nb, K.shape[2], mb, d, V.shape[3], int(dtype_enum), int(kv_dtype_enum), int(q_dtype_enum), int(bool(causal)),
+            float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace), int(variant), _raw_stream(Q.device.index))
 
 
 def kvcache_mla_sparse_num_splits(B, H, H_kv, N_q, topk, d, d_v, dtype_enum):

@@ -48,6 +48,12 @@ struct Fa2DecodeProblem {
     // tensor of kFa2DsRowBytes-byte rows (below), ks == vs are in BYTES with ks[3] = 1, d = 576, d_v = 512, kv_dtype == dtype (the rotary
     // columns' and the matrix arithmetic's), no descales.  0: every other call.
     int32_t kv_format;
+    // fp8 queries (fa2_fwd_kvcache_mla_q8): q_dtype is the element type of Q, an fp8 format under an fp8 cache, and qd its device descale
+    // at [b * qds[0] + h_kv * qds[1]], null = 1: the query is qd * float(Q8).  `dtype` is then O's alone (f16 / bf16) and L is fp32.
+    // Every other call: q_dtype == dtype, qd null.
+    int32_t q_dtype;
+    const float *qd;
+    int64_t qds[2];
 };
 
 // A row of the tile-scaled fp8 latent cache (vLLM's fp8_ds_mla, FlashMLA's sparse fp8 layout): 512 e4m3fn bytes, 4 fp32 scales (scale t
@@ -164,6 +170,16 @@ static inline bool fa2_decode_mla16_shape(int32_t d, int32_t d_v, int32_t dtype)
 }
 bool fa2_decode_mla16_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla16(const Fa2DecodeProblem &p);
+
+// fp8 queries over the fp8 latent cache (fa2_fwd_kvcache_mla_q8).  Matrix form (fa2_decode_mla8.hip, FA2_KVCACHE_VARIANT_MLA8): e4m3 on
+// both sides at d = 576, d_v = 512, the scores and P.V on v_mfma_f32_32x32x64_f8f6f4, the row tiles of fa2_decode_mla16.hip.  VALU form
+// (fa2_decode_generic_q8.hip): the fp8-query instantiations of fa2_decode_generic.hip, either fp8 format on either side.
+static inline bool fa2_decode_mla8_shape(int32_t d, int32_t d_v, int32_t q_dtype, int32_t kv_dtype) {
+    return q_dtype == FA2_DTYPE_F8E4M3 && kv_dtype == FA2_DTYPE_F8E4M3 && d == 576 && d_v == 512;
+}
+bool fa2_decode_mla8_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla8(const Fa2DecodeProblem &p);
+int fa2_launch_decode_generic_q8(const Fa2DecodeProblem &p);
 
 // The query-tiled matrix form of the packed call (fa2_decode_mfma16_v.hip): a workgroup owns tq consecutive query positions of one
 // sequence for the g heads of a KV group, R = g tq <= 64 rows.

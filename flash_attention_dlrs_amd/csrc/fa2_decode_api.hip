@@ -1,5 +1,5 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache calls
-// _mla, _mla_fp8, _mla_varlen and the key-list calls _mla_sparse and _mla_sparse_varlen, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
+// _mla, _mla_fp8, _mla_q8 (fp8 queries), _mla_varlen and the key-list calls _mla_sparse and _mla_sparse_varlen, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
 // fa2_fwd_kvcache_append, _varlen_append, _mla_append and _mla_varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
 //   1. fill   the entry point names its raw arguments in a DecodeCall (the cache update's in an AppendCall), packed strides through packed4;
 //   2. check  check_decode (check_append) tests every argument, resolves num_splits (split_count on the unsplit workgroup count of the
@@ -56,6 +56,16 @@ int num_splits_mla(const SplitShape &s) {
         return num_splits_auto(valu);
     }
     return split_count(s.B * s.H_kv * ((s.H / s.H_kv * s.N_q + 63) / 64), s.S_k, kMlaSplitWaves, kMlaMinSplitTiles);
+}
+
+// fa2_kvcache_mla_q8_num_splits (s.dtype is Q's): the fp8 matrix form (fa2_decode_mla8.hip) has the row tiles of the 16-bit one and runs
+// one workgroup per CU as well, so it takes num_splits_mla's count and constants.  (Not swept on its own: with two tile buffers a
+// shorter split may pay; the constants stay the measured ones until a sweep says otherwise.)
+int num_splits_mla_q8(const SplitShape &s, int32_t kv_dtype) {
+    SplitShape t = s;
+    t.dtype = FA2_DTYPE_BF16;
+    if (!fa2_decode_mla8_shape(s.d, s.d_v, s.dtype, kv_dtype)) t.d = 0;  // the VALU form
+    return num_splits_mla(t);
 }
 
 // fa2_kvcache_varlen_num_splits: base is the unsplit workgroup count of the packed launch.  A sequence fills ceil(n_q(b) / tq)
@@ -153,6 +163,11 @@ struct DecodeCall {
     // second with `packed`): FA2_KV_FORMAT_FP8_DS, K == V the byte tensor of 656-byte rows,
     // k_strides == v_strides in BYTES with a last stride of 1, d = 576, d_v = 512, no descales
     int32_t kv_format = 0;
+    // fa2_fwd_kvcache_mla_q8 (with `mla`, `fp8`): Q is fp8 in q_dtype_enum with its descale, dtype_enum is O's alone and L is fp32
+    bool q8 = false;
+    int32_t q_dtype_enum = 0;
+    const float *q_descale = nullptr;
+    const int64_t *q_descale_strides = nullptr;
 };
 
 // The forms of the call (the last four rows: the two list forms, then the two dense latent forms, over the tile-scaled fp8 cache): fixed N_q, packed queries (query-tiled), the latent cache, packed queries over the latent cache, key
@@ -166,7 +181,7 @@ struct DecodeForm {
     const char *unknown_variant;
     int (*generic)(const Fa2DecodeProblem &) = fa2_launch_decode_generic;
 };
-const DecodeForm kForms[10] = {
+const DecodeForm kForms[11] = {
     {fa2_decode_mfma16_supports, fa2_launch_decode_mfma16, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mfma16_v_supports, fa2_launch_decode_mfma16_v, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mla16_supports, fa2_launch_decode_mla16, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
@@ -184,8 +199,12 @@ const DecodeForm kForms[10] = {
     // VALU kernel with the layout's loader
     {fa2_decode_mla16_d_supports, fa2_launch_decode_mla16_d, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla fp8_ds: unknown variant %d (auto 0, generic 1, mla16 3)"},
     {fa2_decode_mla16_dv_supports, fa2_launch_decode_mla16_dv, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla fp8_ds: unknown variant %d (auto 0, generic 1, mla16 3)"},
+    // row 2 with fp8 queries (fa2_fwd_kvcache_mla_q8): the fp8 matrix kernel, and the VALU kernel's fp8-query instantiations
+    {fa2_decode_mla8_supports, fa2_launch_decode_mla8, FA2_KVCACHE_VARIANT_MLA8, "kvcache mla q8: unknown variant %d (auto 0, generic 1, mla8 4)",
+     fa2_launch_decode_generic_q8},
 };
 const DecodeForm &form_of(const DecodeCall &c) {
+    if (c.q8) return kForms[10];
     if (c.kv_format == FA2_KV_FORMAT_FP8_DS) return kForms[c.sparse ? (c.packed ? 7 : 6) : (c.packed ? 9 : 8)];
     return kForms[c.sparse && c.packed ? 5 : c.sparse ? 4 : c.packed && c.mla ? 3 : c.mla ? 2 : c.packed ? 1 : 0];
 }
@@ -354,6 +373,20 @@ int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
         fa2_set_error("kvcache: num_splits must be in [0, %d] (0 = auto), got %d", FA2_KVCACHE_MAX_SPLITS, c.num_splits);
         return FA2_ERR_BAD_ARG;
     }
+    if (c.q8) {  // what only the fp8 queries bring comes first
+        if (c.q_descale && !c.q_descale_strides) {
+            fa2_set_error("kvcache mla q8: null q_descale_strides with a non-null q_descale");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.q_descale && (c.q_descale_strides[0] < 0 || c.q_descale_strides[1] < 0)) {
+            fa2_set_error("kvcache mla q8: negative strides are not supported (q_descale_strides)");
+            return FA2_ERR_BAD_ARG;
+        }
+        if (c.q_dtype_enum != FA2_DTYPE_F8E4M3 && c.q_dtype_enum != FA2_DTYPE_F8E5M2) {
+            fa2_set_error("kvcache mla q8: q_dtype_enum %d must be FA2_DTYPE_F8E4M3 or FA2_DTYPE_F8E5M2", c.q_dtype_enum);
+            return FA2_ERR_UNSUPPORTED;
+        }
+    }
     if (c.fp8) {
         const int rc = check_descales("kvcache fp8", c.k_descale, c.k_descale_strides, c.v_descale, c.v_descale_strides);
         if (rc != FA2_OK) return rc;
@@ -362,7 +395,8 @@ int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
             return FA2_ERR_UNSUPPORTED;
         }
         if (c.dtype_enum != FA2_DTYPE_F16 && c.dtype_enum != FA2_DTYPE_BF16) {
-            fa2_set_error("kvcache fp8: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16", c.dtype_enum);
+            fa2_set_error(c.q8 ? "kvcache mla q8: dtype_enum %d (O) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16"
+                               : "kvcache fp8: dtype_enum %d (Q, O, L) must be FA2_DTYPE_F16 or FA2_DTYPE_BF16", c.dtype_enum);
             return FA2_ERR_UNSUPPORTED;
         }
     } else if (c.dtype_enum == FA2_DTYPE_F8E5M2 || c.dtype_enum == FA2_DTYPE_F8E4M3) {
@@ -404,8 +438,13 @@ int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
     p.indices = c.sparse ? c.indices : nullptr; p.topk = c.sparse ? c.topk : 0;
     for (int k = 0; k < 4; ++k) p.is[k] = c.sparse ? c.index_strides[k] : 0;
     p.kv_format = c.kv_format;
+    p.q_dtype = c.q8 ? c.q_dtype_enum : c.dtype_enum;
+    p.qd = c.q8 ? c.q_descale : nullptr;
+    for (int k = 0; k < 2; ++k) p.qds[k] = p.qd ? c.q_descale_strides[k] : 0;
     const SplitShape shape = {c.B, c.H, c.H_kv, c.N_q, c.total_q, c.sparse ? c.topk : S_k, c.d, d_v, c.dtype_enum};  // (the lists: splits over slots)
-    p.num_splits = c.num_splits != 0 ? c.num_splits : c.sparse && c.packed ? num_splits_mla_sparse_varlen(shape) : c.sparse ? num_splits_mla_sparse(shape) : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
+    SplitShape qshape = shape;
+    qshape.dtype = c.q_dtype_enum;
+    p.num_splits = c.num_splits != 0 ? c.num_splits : c.q8 ? num_splits_mla_q8(qshape, c.kv_dtype_enum) : c.sparse && c.packed ? num_splits_mla_sparse_varlen(shape) : c.sparse ? num_splits_mla_sparse(shape) : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
     p.stream = (hipStream_t)c.hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
@@ -807,6 +846,35 @@ int32_t fa2_kvcache_mla_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N
                                    int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
     return num_splits_mla({B, H, H_kv, N_q, 0, S_k, d, d_v, dtype_enum});
+}
+
+int fa2_fwd_kvcache_mla_q8(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],
+                           const int64_t k_strides[4], const int64_t v_strides[4], const int64_t o_strides[4],
+                           const int64_t l_strides[2], const int32_t *cache_seqlens, const int32_t *block_table,
+                           int64_t block_table_stride, const float *k_descale, const float *v_descale,
+                           const int64_t k_descale_strides[2], const int64_t v_descale_strides[2], const float *q_descale,
+                           const int64_t q_descale_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t num_blocks,
+                           int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum,
+                           int32_t q_dtype_enum, int32_t causal, float scale, int32_t window_left, int32_t window_right,
+                           int32_t num_splits, void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    DecodeCall c;
+    c.Q = Q; c.K = K; c.V = V; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = q_strides; c.k_strides = k_strides; c.v_strides = v_strides; c.o_strides = o_strides; c.l_strides = l_strides;
+    // (block_table null: the contiguous cache, page_size carries S_k, as in fa2_fwd_kvcache_mla)
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = N_q; c.S_k = block_table ? 0 : page_size; c.d = d; c.dtype_enum = dtype_enum;
+    c.causal = causal; c.scale = scale; c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = true; c.kv_dtype_enum = kv_dtype_enum;  // (whatever kv_dtype_enum holds: one that is no fp8 format is refused)
+    c.k_descale = k_descale; c.v_descale = v_descale; c.k_descale_strides = k_descale_strides; c.v_descale_strides = v_descale_strides;
+    c.q8 = true; c.q_dtype_enum = q_dtype_enum; c.q_descale = q_descale; c.q_descale_strides = q_descale_strides;
+    return decode(c, nullptr);
+}
+
+int32_t fa2_kvcache_mla_q8_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t d_v,
+                                      int32_t q_dtype_enum, int32_t kv_dtype_enum) {
+    if (B < 1 || H < 1 || H_kv < 1 || N_q < 1 || S_k < 1) return 1;
+    return num_splits_mla_q8({B, H, H_kv, N_q, 0, S_k, d, d_v, q_dtype_enum}, kv_dtype_enum);
 }
 
 int fa2_fwd_kvcache_mla_sparse(const void *Q, const void *K, const void *V, void *O, void *L, const int64_t q_strides[4],

@@ -9,6 +9,8 @@
 // Packed queries (fa2_fwd_kvcache_varlen): the partial rows are [total_q * H], row = token * H + head, and only the rows of a
 // sequence's own n_q(b) tokens were written.  The grid is (blocks, B): the blocks of sequence b stride over its n_q(b) * H rows,
 // so a token outside every sequence is neither read nor written.  The arithmetic of a row is the same.
+//
+// fp8 queries (fa2_fwd_kvcache_mla_q8): O's dtype is the caller's out dtype and L is stored in fp32 (l_f32); nothing else differs.
 #include <math.h>
 
 #include "fa2_decode.h"
@@ -27,6 +29,7 @@ struct CombineArgs {
     int H, N_q, d, num_splits;  // d: the columns of O and of the partials (the value head size)
     const int32_t *cu_q;  // packed queries: B + 1 offsets (os[0] = ls[0] = 0), else null
     int total_q, max_q;
+    bool l_f32;  // fp8 queries (fa2_fwd_kvcache_mla_q8): L is fp32 whatever O's dtype
 };
 
 // One row of the partials, one wave: `row` indexes o_part / l_part, o_off / l_off are the row's element offsets in O and L, w the
@@ -59,7 +62,9 @@ __device__ __forceinline__ void combine_row(const CombineArgs &a, int64_t row, b
             for (int s = 0; s < a.num_splits; ++s) acc += w[s] * a.o_part[((int64_t)s * a.rows + row) * a.d + x];
         E::store(a.O, o_off + (int64_t)x * a.os[3], (A)(acc * inv));
     }
-    if (lane == 0) E::store(a.L, l_off, seen ? (A)(m + log2f(wsum)) : (A)INFINITY);
+    if (lane != 0) return;
+    if (a.l_f32) ((float *)a.L)[l_off] = seen ? m + log2f(wsum) : INFINITY;
+    else E::store(a.L, l_off, seen ? (A)(m + log2f(wsum)) : (A)INFINITY);
 }
 
 
@@ -122,6 +127,7 @@ int fa2_launch_decode_combine(const Fa2DecodeProblem &p) {
     a.H = p.H; a.N_q = p.N_q; a.d = p.d_v; a.num_splits = p.num_splits;
     a.cu_q = p.cu_q; a.total_q = p.total_q; a.max_q = p.max_q;
     if (p.cu_q) a.rows = (int64_t)p.total_q * p.H;
+    a.l_f32 = p.q_dtype != p.dtype;
     switch (p.dtype) {
     case FA2_DTYPE_F32: return launch_e<ElemF32>(p, a);
     case FA2_DTYPE_F16: return launch_e<ElemF16>(p, a);

@@ -31,10 +31,18 @@
 // Variable-length queries (fa2_fwd_kvcache_varlen): with cu_q the rows are packed (total_q, H, d), sequence b owns n_q(b) rows
 // from its start on (fa2_varlen_seq) and the grid's query tiles cover max_seqlen_q: a tile at or past n_q(b) leaves at once, the
 // band is the one of n_q(b) and N_k(b), and rows past n_q(b) -- the next sequence's in the packed layout -- are not stored.
+//
+// fp8 queries (fa2_fwd_kvcache_mla_q8, FA2_DECODE_Q8: the instantiations of fa2_decode_generic_q8.hip alone).  QX, the element type of Q,
+// is a template parameter of its own beside E, which is then O's alone: an fp8 byte converted exactly as it is loaded, its descale qd
+// folded into the softmax scale beside kd.  P stays fp32 between the score and the value loop (no rounding to E), and L is fp32.
 #include <math.h>
 
 #include "fa2_decode.h"
 #include "fa2_elem.h"
+
+#ifndef FA2_DECODE_Q8
+#define FA2_DECODE_Q8 0
+#endif
 
 namespace {
 
@@ -70,13 +78,18 @@ struct DecodeGenericArgs {
     int page_size, num_blocks;
     const int32_t *cu_q;  // packed queries: B + 1 offsets (qs[0] = os[0] = ls[0] = 0), else null
     int total_q, max_q;
+#if FA2_DECODE_Q8
+    const float *qd;  // fp8 queries only (the struct of the other unit is what it was): the descale at [b * qds[0] + h_kv * qds[1]], null = 1
+    int64_t qds[2];
+#endif
 };
 
 // grid (num_splits * nqt, B, H); DPL = output columns per lane = ceil(d_v / 64).  E: Q, O, L; C: K, V (E, or an fp8 format).
-// PAGED: K and V are a page pool behind a block table.
-template <class E, class C, bool PAGED, int DPL>
+// PAGED: K and V are a page pool behind a block table.  QX: Q alone where it is not E (fp8 queries: E is O's, L is fp32).
+template <class E, class C, bool PAGED, int DPL, class QX = E>
 __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const DecodeGenericArgs a) {
     using A = typename E::acc_t;
+    constexpr bool Q8 = !__is_same(QX, E);
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     A *q_lds = (A *)smem_raw;              // [kBr][d]
     A *p_lds = q_lds + (size_t)kBr * a.d;  // [kWaves][kRowsPerWave][kBc]
@@ -102,7 +115,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
         const int r = idx / d, x = idx - r * d;
         int row = i * kBr + r;
         row = row < N ? row : N - 1;
-        q_lds[idx] = E::load(a.Q, q_off + (int64_t)row * a.qs[2] + (int64_t)x * a.qs[3]);
+        q_lds[idx] = QX::load(a.Q, q_off + (int64_t)row * a.qs[2] + (int64_t)x * a.qs[3]);
     }
     __syncthreads();
 
@@ -113,6 +126,9 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
         c *= fa2_decode_descale(a.kd, a.kds[0], a.kds[1], b, hk);
         vd = fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
     }
+#if FA2_DECODE_Q8
+    if constexpr (Q8) c *= fa2_decode_descale(a.qd, a.qds[0], a.qds[1], b, hk);
+#endif
     const int row0 = i * kBr + wave * kRowsPerWave;
     A m[kRowsPerWave], lsum[kRowsPerWave], o[kRowsPerWave][DPL];
 #pragma unroll
@@ -162,7 +178,7 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 #pragma unroll
             for (int cc = 0; cc < DPL; ++cc) o[r][cc] *= coeff;
             m[r] = m_new;
-            p_w[r * kBc + lane] = E::round(p);
+            p_w[r * kBc + lane] = Q8 ? p : E::round(p);
         }
         __syncthreads();
         const int kmax = (kend - kt) < kBc ? (kend - kt) : kBc;
@@ -207,7 +223,9 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
                 const int x = lane + 64 * cc;
                 if (x < dv) E::store(a.O, o_off + (int64_t)x * a.os[3], l > 0 ? (F8 ? o[r][cc] / l * vd : o[r][cc] / l) : (A)0);
             }
-            if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + start + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
+            if constexpr (Q8) {
+                if (lane == 0) ((float *)a.L)[b * a.ls[0] + h * a.ls[1] + start + row] = l > 0 ? (float)(m[r] + log2_acc<A>(l)) : INFINITY;
+            } else if (lane == 0) E::store(a.L, b * a.ls[0] + h * a.ls[1] + start + row, l > 0 ? m[r] + log2_acc<A>(l) : (A)INFINITY);
         } else {  // every (split, row) is written, an empty split as O_s = 0, L_s = -inf: the workspace arrives uninitialised
             const int64_t rows = a.cu_q ? (int64_t)a.total_q * a.H : (int64_t)gridDim.y * a.H * N;
             const int64_t prow = (int64_t)split * rows + (a.cu_q ? (int64_t)(start + row) * a.H + h : ((int64_t)b * a.H + h) * N + row);
@@ -222,18 +240,18 @@ __global__ __launch_bounds__(kWaves * 64) void fa2_decode_generic_kernel(const D
 }
 
 // More than 64 KiB of dynamic LDS (d > 256 in double) is opted into, once per device and instantiation.
-template <class E, class C, bool PAGED, int DPL>
+template <class E, class C, bool PAGED, int DPL, class QX>
 void launch_k(const dim3 &grid, const dim3 &block, size_t smem, hipStream_t stream, const DecodeGenericArgs &a) {
     static Fa2DeviceLatch attr_done;
     if (smem > 64 * 1024 && attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, PAGED, DPL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute((const void *)fa2_decode_generic_kernel<E, C, PAGED, DPL, QX>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(sizeof(typename E::acc_t) * ((size_t)kBr * 576 + (size_t)kWaves * kRowsPerWave * kBc)));
         attr_done.mark();
     }
-    hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, DPL>), grid, block, smem, stream, a);
+    hipLaunchKernelGGL((fa2_decode_generic_kernel<E, C, PAGED, DPL, QX>), grid, block, smem, stream, a);
 }
 
-template <class E, class C, bool PAGED> int launch_p(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
+template <class E, class C, bool PAGED, class QX> int launch_p(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
     const long long gx = (long long)a.num_splits * a.nqt;
     if (gx > 0x7fffffffLL) {
         fa2_set_error("kvcache generic kernel: grid too large (num_splits * ceil(N_q / 16) = %lld)", gx);
@@ -242,10 +260,10 @@ template <class E, class C, bool PAGED> int launch_p(const Fa2DecodeProblem &p, 
     const dim3 grid((unsigned)gx, p.B, p.H), block(kWaves * 64);
     const size_t smem = sizeof(typename E::acc_t) * ((size_t)kBr * (p.d > p.d_v ? p.d : p.d_v) + (size_t)kWaves * kRowsPerWave * kBc);
     const int dpl = (p.d_v + 63) / 64;
-    if (dpl <= 1) launch_k<E, C, PAGED, 1>(grid, block, smem, p.stream, a);
-    else if (dpl <= 2) launch_k<E, C, PAGED, 2>(grid, block, smem, p.stream, a);
-    else if (dpl <= 4) launch_k<E, C, PAGED, 4>(grid, block, smem, p.stream, a);
-    else launch_k<E, C, PAGED, 8>(grid, block, smem, p.stream, a);
+    if (dpl <= 1) launch_k<E, C, PAGED, 1, QX>(grid, block, smem, p.stream, a);
+    else if (dpl <= 2) launch_k<E, C, PAGED, 2, QX>(grid, block, smem, p.stream, a);
+    else if (dpl <= 4) launch_k<E, C, PAGED, 4, QX>(grid, block, smem, p.stream, a);
+    else launch_k<E, C, PAGED, 8, QX>(grid, block, smem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache generic kernel launch failed: %s", hipGetErrorString(e));
@@ -254,13 +272,17 @@ template <class E, class C, bool PAGED> int launch_p(const Fa2DecodeProblem &p, 
     return FA2_OK;
 }
 
-template <class E, class C = E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
-    return p.table ? launch_p<E, C, true>(p, a) : launch_p<E, C, false>(p, a);
+template <class E, class C = E, class QX = E> int launch_e(const Fa2DecodeProblem &p, const DecodeGenericArgs &a) {
+    return p.table ? launch_p<E, C, true, QX>(p, a) : launch_p<E, C, false, QX>(p, a);
 }
 
 }  // namespace
 
+#if FA2_DECODE_Q8
+int fa2_launch_decode_generic_q8(const Fa2DecodeProblem &p) {
+#else
 int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
+#endif
     DecodeGenericArgs a;
     a.Q = p.Q; a.K = p.K; a.V = p.V; a.O = p.O; a.L = p.L;
     for (int k = 0; k < 4; ++k) { a.qs[k] = p.qs[k]; a.ks[k] = p.ks[k]; a.vs[k] = p.vs[k]; a.os[k] = p.os[k]; }
@@ -275,6 +297,21 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     for (int k = 0; k < 2; ++k) { a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     a.cu_q = p.cu_q; a.total_q = p.total_q; a.max_q = p.max_q;  // (N_q = max_q sizes the query tiles)
+#if FA2_DECODE_Q8
+    // fp8 queries over an fp8 cache, O in f16 / bf16: either format on either side
+    a.qd = p.qd; a.qds[0] = p.qds[0]; a.qds[1] = p.qds[1];
+    const bool q4 = p.q_dtype == FA2_DTYPE_F8E4M3, k4 = p.kv_dtype == FA2_DTYPE_F8E4M3;
+    if ((q4 || p.q_dtype == FA2_DTYPE_F8E5M2) && (k4 || p.kv_dtype == FA2_DTYPE_F8E5M2) && p.kv_format == 0) {
+        if (p.dtype == FA2_DTYPE_F16)
+            return q4 ? (k4 ? launch_e<ElemF16, CacheF8E4M3, CacheF8E4M3>(p, a) : launch_e<ElemF16, CacheF8E5M2, CacheF8E4M3>(p, a))
+                      : (k4 ? launch_e<ElemF16, CacheF8E4M3, CacheF8E5M2>(p, a) : launch_e<ElemF16, CacheF8E5M2, CacheF8E5M2>(p, a));
+        if (p.dtype == FA2_DTYPE_BF16)
+            return q4 ? (k4 ? launch_e<ElemBF16, CacheF8E4M3, CacheF8E4M3>(p, a) : launch_e<ElemBF16, CacheF8E5M2, CacheF8E4M3>(p, a))
+                      : (k4 ? launch_e<ElemBF16, CacheF8E4M3, CacheF8E5M2>(p, a) : launch_e<ElemBF16, CacheF8E5M2, CacheF8E5M2>(p, a));
+    }
+    fa2_set_error("kvcache mla q8: Q dtype enum %d over cache dtype enum %d with O dtype enum %d is not supported", p.q_dtype, p.kv_dtype, p.dtype);
+    return FA2_ERR_UNSUPPORTED;
+#else
     if (p.kv_format == FA2_KV_FORMAT_FP8_DS) {  // the tile-scaled fp8 cache under 16-bit Q, O, L: strides in bytes
         if (p.dtype == FA2_DTYPE_F16) return launch_e<ElemF16, CacheFp8DS<ElemF16>>(p, a);
         if (p.dtype == FA2_DTYPE_BF16) return launch_e<ElemBF16, CacheFp8DS<ElemBF16>>(p, a);
@@ -297,4 +334,5 @@ int fa2_launch_decode_generic(const Fa2DecodeProblem &p) {
     case FA2_DTYPE_F64: return launch_e<ElemF64>(p, a);
     default: fa2_set_error("kvcache: dtype enum %d is not supported", p.dtype); return FA2_ERR_UNSUPPORTED;
     }
+#endif
 }

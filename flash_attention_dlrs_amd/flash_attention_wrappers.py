@@ -645,6 +645,61 @@ def flash_attention_mla_decode_forward(Q, KV_cache, cache_seqlens, dev, *, d_v=5
                                 None, block_table, None, None, None, None, latent=True, kv_descale=kv_descale, append=append)
 
 
+def flash_attention_mla_decode_q8_forward(Q8, KV_cache, cache_seqlens, dev, *, d_v=512, q_descale=None, kv_descale=None, causal=False,
+                                          scale=1.0, window=None, num_splits=0, variant="auto", block_table=None,
+                                          out_dtype=torch.bfloat16):
+    """flash_attention_mla_decode_forward with fp8 QUERIES over the fp8 latent cache (fa2_fwd_kvcache_mla_q8) -> (O, L): the absorbed
+    query as an engine with a one-descale e4m3 latent cache holds it.  Q8 (B, H, N_q, d) and KV_cache (B, H_kv, S_k, d) -- or, with
+    block_table, the pool (num_blocks, H_kv, page_size, d) -- in torch.float8_e4m3fn or torch.float8_e5m2; the query is q_descale *
+    float(Q8), a cache row kv_descale * float(KV_cache), both descales float32 tensors on Q8's device that broadcast to (B, H_kv)
+    (None: 1; finite and > 0).  O (B, H, N_q, d_v) in out_dtype (float16 or bfloat16), L (B, H, N_q) in float32, log2 domain.
+    Lengths, the bottom-right mask and window, empty rows (O = 0, L = +inf), num_splits and the block table are the dense call's.
+
+    variant is one of _lib.KVCACHE_MLA_Q8_VARIANTS.  "mla8" (e4m3fn on both sides, d = 576, d_v = 512, 16-byte aligned rows,
+    page_size % 64 == 0) does the matrix work itself in fp8: the scores are (scale q_descale kv_descale) sum q8 k8 with exact products
+    summed in fp32, p = exp2(s - m) and its row sum l are fp32, the operand of P.V is e4m3(256 p) (round to nearest even), and O =
+    kv_descale 2^-8 (sum P8 v8) / l is rounded once.  "generic" converts both sides exactly and keeps P in fp32: e5m2 on either
+    side, any d <= 576 and d_v < d, any page size and alignment.  "auto" is "mla8" where it runs.  Out of scope here (they keep their
+    16-bit-Q calls, after mla_kvcache_append): packed queries, per-query key lists, kv_format="fp8_ds", kv_new and rotary."""
+    check_mla_q8_args(Q8, KV_cache, cache_seqlens, d_v, q_descale, kv_descale, window, num_splits, variant, block_table, out_dtype)
+    _check_dev(dev, Q8, KV_cache, KV_cache)
+    B, H, N_q, d = Q8.shape
+    H_kv = KV_cache.shape[1]
+    qe, ke = convert_triton_dtype(Q8.dtype), convert_triton_dtype(KV_cache.dtype)
+    n = num_splits or _lib.kvcache_mla_q8_num_splits(B, H, H_kv, N_q, _capacity(KV_cache, block_table), d, d_v, qe, ke)
+    O = torch.empty((B, H, N_q, d_v), dtype=out_dtype, device=Q8.device)
+    L = torch.empty((B, H, N_q), dtype=torch.float32, device=Q8.device)
+    nbytes = _lib.kvcache_workspace_bytes(B, H, N_q, d_v, n) if n > 1 else 0
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=Q8.device) if nbytes else None
+    kd = _kvcache_descale("kv_descale", kv_descale, Q8, B, H_kv)
+    _lib.fa2_fwd_kvcache_mla_q8(Q8, KV_cache, KV_cache[..., :d_v], O, L, cache_seqlens, convert_triton_dtype(out_dtype), ke, qe,
+                                q_descale=_kvcache_descale("q_descale", q_descale, Q8, B, H_kv), k_descale=kd, v_descale=kd,
+                                block_table=block_table, causal=causal, scale=scale, window=window, num_splits=n, workspace=ws,
+                                variant=_lib.KVCACHE_MLA_Q8_VARIANTS[variant])
+    return O, L
+
+
+def check_mla_q8_args(Q8, KV_cache, cache_seqlens, d_v=512, q_descale=None, kv_descale=None, window=None, num_splits=0, variant="auto",
+                      block_table=None, out_dtype=torch.bfloat16):
+    """ValueError for what flash_attention_mla_decode_q8_forward cannot take.  Pure: takes CPU tensors as well."""
+    if not isinstance(Q8, torch.Tensor) or Q8.dim() != 4 or Q8.dtype not in FP8_CACHE_DTYPES:
+        raise ValueError("mla decode q8: Q8 must be a tensor (B, H, N_q, d) in torch.float8_e4m3fn or torch.float8_e5m2 "
+                         "(16-bit queries: flash_attention_mla_decode_forward)")
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4 or KV_cache.dtype not in FP8_CACHE_DTYPES:
+        raise ValueError("mla decode q8: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d) in "
+                         "torch.float8_e4m3fn or torch.float8_e5m2")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"mla decode q8: out_dtype must be torch.float16 or torch.bfloat16, got {out_dtype!r}")
+    if isinstance(d_v, bool) or not isinstance(d_v, int) or not 1 <= d_v < KV_cache.shape[3] or d_v > 512 or KV_cache.shape[3] > 576:
+        raise ValueError(f"mla decode q8: d must be <= 576 and d_v an int in [1, min(d - 1, 512)], got d = {KV_cache.shape[3]}, d_v = {d_v!r}")
+    stand_in = torch.empty((), dtype=out_dtype, device=Q8.device).expand(Q8.shape)  # Q's shape and device under the 16-bit rules
+    check_kvcache_args(stand_in, KV_cache, KV_cache, cache_seqlens, window, num_splits, None, None, block_table)
+    _kvcache_descale("q_descale", q_descale, Q8, Q8.shape[0], KV_cache.shape[1])
+    _kvcache_descale("kv_descale", kv_descale, Q8, Q8.shape[0], KV_cache.shape[1])
+    if variant not in _lib.KVCACHE_MLA_Q8_VARIANTS:
+        raise ValueError(f"mla decode q8: variant must be one of {sorted(_lib.KVCACHE_MLA_Q8_VARIANTS)}, got {variant!r}")
+
+
 def _mla_sources(kv_new, d_v):
     """(c_new, pe_new) of a kv_new argument: the pair as it is, or the two views of the one tensor."""
     if isinstance(kv_new, torch.Tensor):

@@ -460,6 +460,50 @@ int fa2_fwd_kvcache_mla_fp8(const void *Q, const void *K, const void *V, void *O
                             void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
 
 /*
+ * fa2_fwd_kvcache_mla_fp8 with fp8 QUERIES: Q is OCP e4m3fn or e5m2 bytes too (q_dtype_enum), the absorbed query as engines with a
+ * one-descale e4m3 latent cache hold it.  The query is q_descale * float(Q8), q_descale as the cache's descales (fp32 on the device at
+ * [b * strides[0] + h_kv * strides[1]], null = 1, finite and > 0); a cache row is k_descale * float(K8) / v_descale * float(V8).  dtype_enum
+ * is O's alone, f16 or bf16; L is FP32 (B, H, N_q) in the log2 domain, whatever dtype_enum: a 16-bit L would throw away what the fp32
+ * accumulation of the scores keeps.  Strides of Q, K and V are in bytes (elements of one byte).  Everything else is
+ * fa2_fwd_kvcache_mla_fp8's: lengths, masks, empty rows (O = 0, L = +inf), paging, fp32 partials and the combine launch.
+ *
+ *   Variants. FA2_KVCACHE_VARIANT_MLA8 (this entry point only): e4m3fn on both sides, d = 576 and d_v = 512, V aliasing K, unit d-stride,
+ *             16-byte aligned rows of Q and K (base and strides multiples of 16 bytes), O rows and the workspace aligned as for MLA16,
+ *             scale > 0, page_size % 64 == 0 when paged.  The matrix work itself is fp8: S = (scale q_descale k_descale) sum_c q8[c] k8[c]
+ *             with exact products and an fp32 sum on v_mfma_f32_32x32x64_f8f6f4; p = exp2(s - m) in fp32, the row sum l over the
+ *             unrounded p; the matrix operand of P.V is P8 = e4m3(256 p) (RTNE; 256 keeps p down to 2^-14 normal, 256 p <= 256 < 448);
+ *             O = v_descale 2^-8 (sum P8 v8) / l rounded once to dtype_enum (or the normalised fp32 partial), L = m + log2 l.
+ *             FA2_KVCACHE_VARIANT_GENERIC: the VALU kernel with the query converted exactly as it is loaded and P kept in fp32: either
+ *             fp8 format on either side, every d <= 576 and d_v <= 512, any strides, any page size.  FA2_KVCACHE_VARIANT_AUTO: MLA8
+ *             where it runs, else GENERIC.  A forced MLA8 on a problem it cannot run returns FA2_ERR_UNSUPPORTED, the message naming
+ *             the rule; MLA16 and MFMA16 are no variants of this call.
+ *   Splits.   num_splits = 0 resolves to fa2_kvcache_mla_q8_num_splits(...); the workspace is fa2_kvcache_workspace_bytes(B, H, N_q, d_v, n).
+ *
+ * Errors: fa2_fwd_kvcache_mla_fp8's, and FA2_ERR_UNSUPPORTED for a q_dtype_enum or kv_dtype_enum that is no fp8 format and a dtype_enum
+ * other than f16 / bf16, FA2_ERR_BAD_ARG for a null q_descale_strides with a non-null q_descale and a negative descale stride.
+ * Not covered: packed queries, key lists, the tile-scaled cache, the fused append (they keep their 16-bit-Q calls).
+ */
+#define FA2_KVCACHE_VARIANT_MLA8 4
+
+int fa2_fwd_kvcache_mla_q8(const void *Q, const void *K, const void *V, void *O, void *L,
+                           const int64_t q_strides[4], const int64_t k_strides[4], const int64_t v_strides[4],
+                           const int64_t o_strides[4], const int64_t l_strides[2], const int32_t *cache_seqlens,
+                           const int32_t *block_table, int64_t block_table_stride,
+                           const float *k_descale, const float *v_descale,
+                           const int64_t k_descale_strides[2], const int64_t v_descale_strides[2],
+                           const float *q_descale, const int64_t q_descale_strides[2],
+                           int32_t B, int32_t H, int32_t H_kv, int32_t N_q,
+                           int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                           int32_t dtype_enum, int32_t kv_dtype_enum, int32_t q_dtype_enum,
+                           int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                           void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* What num_splits = 0 resolves to for fa2_fwd_kvcache_mla_q8: with e4m3fn on both sides at d = 576, d_v = 512 (the matrix form, one
+ * workgroup per CU as MLA16) fa2_kvcache_mla_num_splits' rule on the same workgroup count; any other shape is counted as the VALU form's. */
+int32_t fa2_kvcache_mla_q8_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t N_q, int32_t S_k, int32_t d, int32_t d_v,
+                                      int32_t q_dtype_enum, int32_t kv_dtype_enum);
+
+/*
  * Variable-length (packed) queries over the KV cache: every sequence brings its own number of query tokens -- a chunk of a prompt
  * over its cached prefix (chunked prefill, prefix caching), the draft tokens of speculative decoding, one decode token -- in one
  * call (flash-attn's flash_attn_varlen_func(..., block_table=)).  Forward only.  The keys of a chunk's own tokens are already in
