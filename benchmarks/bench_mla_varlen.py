@@ -29,8 +29,15 @@ list at its own auto num_splits (every key for every row: the list has no causal
 for the first).  The sides ALTERNATE call by call in one traced child, a mark kernel between them, as benchmarks/bench_mla_decode.py
 --kv-format fp8_ds does; the copies are sized by the smallest row (576 B).
 
+--q-dtype e4m3: the packed fp8-query call (fa2_fwd_kvcache_mla_varlen_q8, variant mla8, its own auto num_splits) over the one-descale
+e4m3 cache beside the route that cache had before it -- packed mla16 with bf16 Q converting the same cache -- and the fixed q8 call
+(fa2_fwd_kvcache_mla_q8, mla8) on Q padded to max_seqlen_q for every sequence.  The sides alternate call by call in one traced child, a
+mark kernel between them, as under --kv-format; with --sweep the packed mla8 call then runs under every num_splits of SWEEP_SPLITS.
+
 Records:
-  kind=kv_format      --kv-format fp8_ds: per shape the sides' avg / min / max / stddev, fp8_ds over each other side, ranges_overlap;
+  kind=q8             --q-dtype e4m3: per shape the sides' avg / min / max / stddev, mla8 over each other side, ranges_overlap;
+  kind=q8_sweep       ... with --sweep: mla8 under one num_splits, beside what AUTO resolves to;
+  kind=kv_format     --kv-format fp8_ds: per shape the sides' avg / min / max / stddev, fp8_ds over each other side, ranges_overlap;
   kind=kernels        one per shape: the sides' avg / min / max / stddev in microseconds, auto_over_generic, auto_over_padded,
                       auto_over_per_count and whether AUTO's and generic's min-max ranges overlap;
   kind=sweep_kernels  --sweep: AUTO's variant under num_splits in SWEEP_SPLITS, one traced child per shape."""
@@ -237,6 +244,73 @@ def run_format(names, args, fh):
              ranges_overlap={side: overlap(new, t) for side, t in sides.items() if side != "fp8_ds"}, **sides)
 
 
+Q8_SIDES = ("mla8", "mla16", "padded_q8")
+
+
+def run_q8_pass(name, args):
+    """The traced child of --q-dtype e4m3: e4m3 Q over the one-descale e4m3 cache, one call of each side in turn, a mark after every call;
+    with --sweep the packed mla8 call under each num_splits of SWEEP_SPLITS afterwards, back to back."""
+    import torch
+    import flash_attention_dlrs_amd as fa
+    c = Case(name, torch.device("cuda:0"), copy_row_bytes=D)
+    lib, e4, f8 = c._lib, torch.float8_e4m3fn, c._lib.FA2_DTYPE_F8E4M3
+    kv8 = [fa.quantize_kv_cache(t, e4) for t in c.KV]
+    qd = torch.broadcast_to(torch.maximum(c.Q.abs().max(), c.Qpad.abs().max()).float() / 448, (c.B, 1))
+    Q8, Qpad8 = (c.Q.float() / qd[0, 0]).to(e4), (c.Qpad.float() / qd[0, 0]).to(e4)
+    L32 = torch.empty(c.H, c.total_q, dtype=torch.float32, device=c.dev)
+    Opad = torch.empty(c.B, c.H, c.max_q, D_V, dtype=torch.bfloat16, device=c.dev)
+    Lpad = torch.empty(c.B, c.H, c.max_q, dtype=torch.float32, device=c.dev)
+    n8 = lib.kvcache_mla_varlen_q8_num_splits(c.B, c.H, 1, c.total_q, c.max_q, c.S, D, D_V, f8, f8)
+    n16 = c.auto_splits()
+    npad = lib.kvcache_mla_q8_num_splits(c.B, c.H, 1, c.max_q, c.S, D, D_V, f8, f8)
+    n_max = max((n8, n16) + (SWEEP_SPLITS if args.sweep else ()))
+    ws = torch.empty(max(lib.kvcache_varlen_workspace_bytes(c.total_q, c.H, D_V, n_max) // 4, 1), dtype=torch.float32, device=c.dev)
+    wpad = torch.empty(max(lib.kvcache_workspace_bytes(c.B, c.H, c.max_q, D_V, npad) // 4, 1), dtype=torch.float32, device=c.dev)
+
+    def run(side, i, n=n8):
+        kv, ds = kv8[i]
+        if side == "mla8":
+            lib.fa2_fwd_kvcache_mla_varlen_q8(Q8, kv, c.O, L32, c.cu, c.max_q, c.lens, c.enum, f8, f8, D_V, q_descale=qd, kv_descale=ds, causal=True,
+                                              scale=c.scale, num_splits=n, workspace=ws, variant=lib.KVCACHE_MLA_Q8_VARIANTS["mla8"])
+        elif side == "mla16":  # the route the same cache had before: bf16 Q, the packed 16-bit matrix form converting the cache
+            lib.fa2_fwd_kvcache_mla_varlen(c.Q, kv, c.O, c.L, c.cu, c.max_q, c.lens, c.enum, f8, D_V, kv_descale=ds, causal=True, scale=c.scale,
+                                           num_splits=n16, workspace=ws, variant=lib.KVCACHE_MLA_VARIANTS["mla16"])
+        else:  # the fixed q8 call on Q padded to max_seqlen_q for every sequence
+            lib.fa2_fwd_kvcache_mla_q8(Qpad8, kv, kv[..., :D_V], Opad, Lpad, c.lens, c.enum, f8, f8, q_descale=qd, k_descale=ds, v_descale=ds,
+                                       causal=True, scale=c.scale, num_splits=npad, workspace=wpad, variant=lib.KVCACHE_MLA_Q8_VARIANTS["mla8"])
+    mark = torch.zeros(1, device=c.dev)
+    torch.cuda.synchronize()
+    mark.fill_(0.0)
+    rounds = args.iters + 3
+    for r in range(rounds):
+        for k, side in enumerate(Q8_SIDES):
+            run(side, (r + k * c.copies // len(Q8_SIDES)) % c.copies)
+            mark.fill_(1.0)
+    for n in SWEEP_SPLITS if args.sweep else ():
+        for r in range(rounds):
+            run("mla8", r % c.copies, n)
+            mark.fill_(1.0)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(case=name, rounds=rounds, q_dtype="e4m3", kv_dtype="e4m3", num_splits_mla8=n8, num_splits_mla16=n16,
+                          num_splits_padded=npad, copies=c.copies, sweep=bool(args.sweep), **c.shape)))
+
+
+def run_q8(names, args, fh):
+    from bench_mla_sparse import call_times, stats  # the trace cut at the marks: one segment per call
+    for name in names:
+        out = os.path.join(args.rocprof, "varlen_" + name + "_q8")
+        info = child(out, ["--q8-case", name] + (["--sweep"] if args.sweep else []), args)
+        rounds, swept = info.pop("rounds"), SWEEP_SPLITS if info.pop("sweep") else ()
+        calls = call_times(out, rounds * (len(Q8_SIDES) + len(swept)))
+        sides = {side: stats(calls[k:rounds * len(Q8_SIDES):len(Q8_SIDES)]) for k, side in enumerate(Q8_SIDES)}
+        new = sides["mla8"]
+        emit(fh, kind="q8", **info, mla8_over={side: round(new["avg_us"] / t["avg_us"], 4) for side, t in sides.items() if side != "mla8"},
+             ranges_overlap={side: overlap(new, t) for side, t in sides.items() if side != "mla8"}, **sides)
+        for k, n in enumerate(swept):
+            at = rounds * (len(Q8_SIDES) + k)
+            emit(fh, kind="q8_sweep", case=name, num_splits=n, auto_splits=info["num_splits_mla8"], **stats(calls[at:at + rounds]))
+
+
 def child(out, extra, args):
     os.makedirs(out, exist_ok=True)
     cmd = ["timeout", "-k", "10", str(args.child_timeout), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out,
@@ -287,11 +361,17 @@ def main():
     ap.add_argument("--kv-dtype", choices=KV_DTYPES, default="bf16", help="the latent cache's storage: bf16, or fp8 with its descale")
     ap.add_argument("--kv-format", choices=("fp8_ds",),
                     help="time the packed call over the tile-scaled fp8 cache beside the 16-bit, e4m3, torch-dequantise and list routes (kind=kv_format)")
+    ap.add_argument("--q-dtype", choices=("e4m3",),
+                    help="time the packed fp8-query call (mla8) beside packed mla16 with bf16 Q and the padded fixed q8 call, all over the same "
+                         "e4m3 cache (kind=q8; with --sweep also mla8 under every num_splits, kind=q8_sweep)")
+    ap.add_argument("--q8-case", help=argparse.SUPPRESS)
     ap.add_argument("--format-case", help=argparse.SUPPRESS)
     ap.add_argument("--pass-case", help=argparse.SUPPRESS)
     ap.add_argument("--sweep-case", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
+    if args.q8_case:
+        return run_q8_pass(args.q8_case, args)
     if args.format_case:
         return run_format_pass(args.format_case, args)
     if args.pass_case:
@@ -300,7 +380,7 @@ def main():
         return run_sweep_pass(args.sweep_case, args)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "a") as fh:
-        (run_format if args.kv_format else run_rocprof)(args.cases.split(","), args, fh)
+        (run_q8 if args.q_dtype else run_format if args.kv_format else run_rocprof)(args.cases.split(","), args, fh)
 
 
 if __name__ == "__main__":

@@ -69,7 +69,8 @@ SYMBOLS = ("fa2_fwd", "fa2_fwd_variant", "fa2_query_tile", "fa2_query_tile_ex", 
            "fa2_mla_indexer_prepare_q", "fa2_mla_indexer_prepare_q_varlen", "fa2_mla_indexer_append_rot",
            "fa2_mla_indexer_append_varlen_rot",
            "fa2_topk_indices_split", "fa2_topk_indices_varlen_split", "fa2_topk_workspace_bytes", "fa2_topk_num_splits",
-           "fa2_fwd_kvcache_mla_ds", "fa2_fwd_kvcache_mla_varlen_ds", "fa2_fwd_kvcache_mla_q8", "fa2_kvcache_mla_q8_num_splits")
+           "fa2_fwd_kvcache_mla_ds", "fa2_fwd_kvcache_mla_varlen_ds", "fa2_fwd_kvcache_mla_q8", "fa2_kvcache_mla_q8_num_splits",
+           "fa2_fwd_kvcache_mla_varlen_q8", "fa2_kvcache_mla_varlen_q8_num_splits")
 # ... and include/fa2_bwd.h
 BWD_SYMBOLS = ("fa2_bwd", "fa2_bwd_variant", "fa2_bwd_window", "fa2_bwd_window_variant", "fa2_bwd_varlen", "fa2_bwd_varlen_variant",
                "fa2_bwd_gqa", "fa2_bwd_gqa_variant", "fa2_bwd_varlen_gqa", "fa2_bwd_varlen_gqa_variant",
@@ -81,7 +82,7 @@ BWD_VARLEN_DV_VARIANTS = {"auto": 0, "generic": 1, "mfma16dv": 4}
 KVCACHE_VARIANTS = {"auto": 0, "generic": 1, "mfma16": 2}
 # ... and the latent-cache call (fa2_fwd_kvcache_mla) its own set: FA2_KVCACHE_VARIANT_MLA16 in the d 64 / 128 matrix form's place
 KVCACHE_MLA_VARIANTS = {"auto": 0, "generic": 1, "mla16": 3}
-# ... and its fp8-query entry point (fa2_fwd_kvcache_mla_q8) its own: FA2_KVCACHE_VARIANT_MLA8 in MLA16's place
+# ... and its fp8-query entry points (fa2_fwd_kvcache_mla_q8, _mla_varlen_q8) their own: FA2_KVCACHE_VARIANT_MLA8 in MLA16's place
 KVCACHE_MLA_Q8_VARIANTS = {"auto": 0, "generic": 1, "mla8": 4}
 # ... and the MLA indexer (fa2_mla_indexer_logits, fa2_mla_indexer_topk) its own: FA2_INDEXER_VARIANT_*
 INDEXER_VARIANTS = {"auto": 0, "generic": 1, "idx16": 2}
@@ -300,6 +301,12 @@ def lib():
             [ctypes.c_int32] * 14 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
         l.fa2_kvcache_mla_varlen_num_splits.restype = ctypes.c_int32
         l.fa2_kvcache_mla_varlen_num_splits.argtypes = [ctypes.c_int32] * 9
+        # ... with fp8 queries: q_descale and its strides after the cache's, q_dtype_enum after kv_dtype_enum
+        l.fa2_fwd_kvcache_mla_varlen_q8.restype = ctypes.c_int
+        l.fa2_fwd_kvcache_mla_varlen_q8.argtypes = [vp] * 4 + [i64p] * 3 + [ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, i64p, vp, i64p] + \
+            [ctypes.c_int32] * 15 + [ctypes.c_float] + [ctypes.c_int32] * 3 + [vp, ctypes.c_int64, ctypes.c_int32, vp]
+        l.fa2_kvcache_mla_varlen_q8_num_splits.restype = ctypes.c_int32
+        l.fa2_kvcache_mla_varlen_q8_num_splits.argtypes = [ctypes.c_int32] * 10
         # ... fused with the packed latent-cache append: seqlens_out after cache_seqlens and, after the descale, c_new pe_new + strides,
         # rotary tables + row strides, S_rot rotary_dim interleaved, q_rot
         l.fa2_fwd_kvcache_mla_varlen_append.restype = ctypes.c_int
@@ -1335,6 +1342,35 @@ def fa2_fwd_kvcache_mla_varlen(Q, KV, O, L, cu_q, max_q, cache_seqlens, dtype_en
             cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, kd_ptr, kd_st,
             cu_q.numel() - 1, H, KV.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d, int(d_v), int(dtype_enum), int(kv_dtype_enum),
             int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
+            int(variant), _raw_stream(Q.device.index))
+
+
+def kvcache_mla_varlen_q8_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, d_v, q_dtype_enum, kv_dtype_enum):
+    """What num_splits = 0 resolves to for a packed-query call over the latent cache with fp8 queries
+    (fa2_kvcache_mla_varlen_q8_num_splits)."""
+    return int(lib().fa2_kvcache_mla_varlen_q8_num_splits(B, H, H_kv, total_q, max_seqlen_q, S_k, d, d_v, int(q_dtype_enum),
+                                                          int(kv_dtype_enum)))
+
+
+def fa2_fwd_kvcache_mla_varlen_q8(Q, KV, O, L, cu_q, max_q, cache_seqlens, dtype_enum, kv_dtype_enum, q_dtype_enum, d_v, block_table=None,
+                                  q_descale=None, kv_descale=None, causal=False, scale=1.0, window=None, num_splits=0, workspace=None,
+                                  variant=0):
+    """Launch fa2_fwd_kvcache_mla_varlen with fp8 queries (include/fa2_fwd.h fa2_fwd_kvcache_mla_varlen_q8) on the current stream of Q's
+    device.  Q (total_q, H, d) in q_dtype_enum and KV in kv_dtype_enum are fp8, O (total_q, H, d_v) is in dtype_enum (f16 / bf16), L
+    (H, total_q) is float32 with unit token stride; q_descale and kv_descale: float32 tensors on the device viewed as (B, H_kv), or None
+    for 1.  The workspace holds kvcache_varlen_workspace_bytes(total_q, H, d_v, num_splits) bytes."""
+    if Q.device.type != "cuda":
+        raise NotImplementedError("Q, K, V must be on the same CUDA device")
+    total_q, H, d = Q.shape
+    _check_packed_l("fa2_fwd_kvcache_mla_varlen_q8", L, H, total_q)
+    tb_ptr, tb_st, S_k, nb, ps, mb = _table_args(KV, block_table)
+    kd_ptr, _, kd_st, _ = _descale_args(kv_descale, None)
+    _launch(lib().fa2_fwd_kvcache_mla_varlen_q8, Q,
+            Q.data_ptr(), KV.data_ptr(), O.data_ptr(), L.data_ptr(), _i64(Q.stride()), _i64(KV.stride()), _i64(O.stride()), L.stride(0),
+            cu_q.data_ptr(), None if cache_seqlens is None else cache_seqlens.data_ptr(), tb_ptr, tb_st, kd_ptr, kd_st,
+            _ptr(q_descale), None if q_descale is None else _i64(q_descale.stride()),
+            cu_q.numel() - 1, H, KV.shape[1], total_q, int(max_q), S_k, nb, ps, mb, d, int(d_v), int(dtype_enum), int(kv_dtype_enum),
+            int(q_dtype_enum), int(bool(causal)), float(scale), *_window_sides(window), int(num_splits), *_workspace_args(workspace),
             int(variant), _raw_stream(Q.device.index))
 
 

@@ -180,6 +180,11 @@ static inline bool fa2_decode_mla8_shape(int32_t d, int32_t d_v, int32_t q_dtype
 bool fa2_decode_mla8_supports(const Fa2DecodeProblem &p);
 int fa2_launch_decode_mla8(const Fa2DecodeProblem &p);
 int fa2_launch_decode_generic_q8(const Fa2DecodeProblem &p);
+// ... and packed fp8 queries (fa2_fwd_kvcache_mla_varlen_q8): the query-tiled instantiations of the fp8 matrix kernel
+// (fa2_decode_mla8_v.hip), rows position-major and tiled as fa2_decode_mla16_v.hip tiles them, under the same id; the fixed form
+// refuses cu_q, this one a call without it.  The VALU form is fa2_launch_decode_generic_q8, which takes cu_q at run time.
+bool fa2_decode_mla8_v_supports(const Fa2DecodeProblem &p);
+int fa2_launch_decode_mla8_v(const Fa2DecodeProblem &p);
 
 // The query-tiled matrix form of the packed call (fa2_decode_mfma16_v.hip): a workgroup owns tq consecutive query positions of one
 // sequence for the g heads of a KV group, R = g tq <= 64 rows.

@@ -1,5 +1,5 @@
 // fa2_decode_api.hip -- extern "C" entry points of KV-cache decode attention (fa2_fwd_kvcache, _fp8, _paged, the latent-cache calls
-// _mla, _mla_fp8, _mla_q8 (fp8 queries), _mla_varlen and the key-list calls _mla_sparse and _mla_sparse_varlen, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
+// _mla, _mla_fp8, _mla_q8 (fp8 queries), _mla_varlen, _mla_varlen_q8 and the key-list calls _mla_sparse and _mla_sparse_varlen, the packed-query call _varlen, the cache appends fa2_kvcache_append and _append_varlen, the fused steps
 // fa2_fwd_kvcache_append, _varlen_append, _mla_append and _mla_varlen_append, and their helpers, declared in include/fa2_fwd.h).  Every attention call takes three steps:
 //   1. fill   the entry point names its raw arguments in a DecodeCall (the cache update's in an AppendCall), packed strides through packed4;
 //   2. check  check_decode (check_append) tests every argument, resolves num_splits (split_count on the unsplit workgroup count of the
@@ -99,6 +99,18 @@ int num_splits_mla_varlen(const SplitShape &s) {
     return split_count(s.H_kv * (grid < packed ? grid : packed), s.S_k, kMlaSplitWaves, kMlaVarlenMinSplitTiles);
 }
 
+// fa2_kvcache_mla_varlen_q8_num_splits (s.dtype is Q's): the packed fp8 matrix form (fa2_decode_mla8_v.hip) has the row tiles of the
+// packed 16-bit one, so where fa2_decode_mla8_shape holds it takes num_splits_mla_varlen's count -- the packed bound on the
+// ceil(g rows / 64) tiles, kMlaSplitWaves, kMlaVarlenMinSplitTiles = 8 -- and otherwise the VALU count of num_splits_varlen.  (The
+// constants are the 16-bit packed form's and have NOT been swept for this kernel: they stay the measured ones until a sweep says
+// otherwise.)
+int num_splits_mla_varlen_q8(const SplitShape &s, int32_t kv_dtype) {
+    SplitShape t = s;
+    t.dtype = FA2_DTYPE_BF16;
+    if (!fa2_decode_mla8_shape(s.d, s.d_v, s.dtype, kv_dtype)) t.d = 0;  // the VALU form
+    return num_splits_mla_varlen(t);
+}
+
 // fa2_kvcache_mla_sparse_num_splits: num_splits_mla with the list's topk slots in S_k's place -- the splits run over slots -- and the
 // unsplit launch of the list-addressed latent form (fa2_decode_mla16_s.hip), B * N_q * H_kv * ceil(g / 64) workgroups: a workgroup
 // owns the heads of ONE query position.  The same constants: one wave of the chip, four tiles per split.  Every other shape is
@@ -181,7 +193,7 @@ struct DecodeForm {
     const char *unknown_variant;
     int (*generic)(const Fa2DecodeProblem &) = fa2_launch_decode_generic;
 };
-const DecodeForm kForms[11] = {
+const DecodeForm kForms[12] = {
     {fa2_decode_mfma16_supports, fa2_launch_decode_mfma16, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mfma16_v_supports, fa2_launch_decode_mfma16_v, FA2_KVCACHE_VARIANT_MFMA16, "kvcache: unknown variant %d (auto 0, generic 1, mfma16 2)"},
     {fa2_decode_mla16_supports, fa2_launch_decode_mla16, FA2_KVCACHE_VARIANT_MLA16, "kvcache mla: unknown variant %d (auto 0, generic 1, mla16 3)"},
@@ -202,8 +214,13 @@ const DecodeForm kForms[11] = {
     // row 2 with fp8 queries (fa2_fwd_kvcache_mla_q8): the fp8 matrix kernel, and the VALU kernel's fp8-query instantiations
     {fa2_decode_mla8_supports, fa2_launch_decode_mla8, FA2_KVCACHE_VARIANT_MLA8, "kvcache mla q8: unknown variant %d (auto 0, generic 1, mla8 4)",
      fa2_launch_decode_generic_q8},
+    // row 3 with fp8 queries (fa2_fwd_kvcache_mla_varlen_q8): the query-tiled fp8 matrix kernel under the same id, the same VALU kernel
+    // (it takes cu_q at run time)
+    {fa2_decode_mla8_v_supports, fa2_launch_decode_mla8_v, FA2_KVCACHE_VARIANT_MLA8, "kvcache mla q8: unknown variant %d (auto 0, generic 1, mla8 4)",
+     fa2_launch_decode_generic_q8},
 };
 const DecodeForm &form_of(const DecodeCall &c) {
+    if (c.q8 && c.packed) return kForms[11];
     if (c.q8) return kForms[10];
     if (c.kv_format == FA2_KV_FORMAT_FP8_DS) return kForms[c.sparse ? (c.packed ? 7 : 6) : (c.packed ? 9 : 8)];
     return kForms[c.sparse && c.packed ? 5 : c.sparse ? 4 : c.packed && c.mla ? 3 : c.mla ? 2 : c.packed ? 1 : 0];
@@ -444,7 +461,7 @@ int check_decode(const DecodeCall &c, Fa2DecodeProblem &p) {
     const SplitShape shape = {c.B, c.H, c.H_kv, c.N_q, c.total_q, c.sparse ? c.topk : S_k, c.d, d_v, c.dtype_enum};  // (the lists: splits over slots)
     SplitShape qshape = shape;
     qshape.dtype = c.q_dtype_enum;
-    p.num_splits = c.num_splits != 0 ? c.num_splits : c.q8 ? num_splits_mla_q8(qshape, c.kv_dtype_enum) : c.sparse && c.packed ? num_splits_mla_sparse_varlen(shape) : c.sparse ? num_splits_mla_sparse(shape) : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
+    p.num_splits = c.num_splits != 0 ? c.num_splits : c.q8 && c.packed ? num_splits_mla_varlen_q8(qshape, c.kv_dtype_enum) : c.q8 ? num_splits_mla_q8(qshape, c.kv_dtype_enum) : c.sparse && c.packed ? num_splits_mla_sparse_varlen(shape) : c.sparse ? num_splits_mla_sparse(shape) : c.packed && c.mla ? num_splits_mla_varlen(shape) : c.mla ? num_splits_mla(shape) : c.packed ? num_splits_varlen(shape) : num_splits_auto(shape);
     p.stream = (hipStream_t)c.hip_stream;
     p.o_part = nullptr; p.l_part = nullptr;
     if (p.num_splits > 1) {
@@ -1100,6 +1117,40 @@ int32_t fa2_kvcache_mla_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, in
                                           int32_t d, int32_t d_v, int32_t dtype_enum) {
     if (B < 1 || H < 1 || H_kv < 1 || total_q < 1 || max_seqlen_q < 1 || S_k < 1) return 1;
     return num_splits_mla_varlen({B, H, H_kv, max_seqlen_q, total_q, S_k, d, d_v, dtype_enum});
+}
+
+int fa2_fwd_kvcache_mla_varlen_q8(const void *Q, const void *KV, void *O, void *L, const int64_t q_strides[3], const int64_t kv_strides[4],
+                                  const int64_t o_strides[3], int64_t l_head_stride, const int32_t *cu_seqlens_q,
+                                  const int32_t *cache_seqlens, const int32_t *block_table, int64_t block_table_stride,
+                                  const float *kv_descale, const int64_t kv_descale_strides[2], const float *q_descale,
+                                  const int64_t q_descale_strides[2], int32_t B, int32_t H, int32_t H_kv, int32_t total_q,
+                                  int32_t max_seqlen_q, int32_t S_k, int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d,
+                                  int32_t d_v, int32_t dtype_enum, int32_t kv_dtype_enum, int32_t q_dtype_enum, int32_t causal,
+                                  float scale, int32_t window_left, int32_t window_right, int32_t num_splits, void *workspace,
+                                  int64_t workspace_bytes, int32_t variant, void *hip_stream) {
+    // fa2_fwd_kvcache_mla_varlen's call (the packed tensors in the fixed call's terms, V the first d_v columns of the row K scores, one
+    // descale K's and V's) with the fp8-query fields as fa2_fwd_kvcache_mla_q8 fills them
+    int64_t qs[4], os[4];
+    const int64_t ls[2] = {0, l_head_stride};
+    DecodeCall c;
+    c.Q = Q; c.K = KV; c.V = KV; c.O = O; c.L = L; c.cache_seqlens = cache_seqlens; c.variant = variant; c.hip_stream = hip_stream;
+    c.q_strides = packed4(q_strides, qs); c.k_strides = kv_strides; c.v_strides = kv_strides; c.o_strides = packed4(o_strides, os);
+    c.l_strides = ls;
+    c.B = B; c.H = H; c.H_kv = H_kv; c.N_q = max_seqlen_q; c.S_k = S_k; c.d = d; c.dtype_enum = dtype_enum; c.causal = causal; c.scale = scale;
+    c.window_left = window_left; c.window_right = window_right; c.num_splits = num_splits; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.mla = true; c.d_v = d_v;
+    c.block_table = block_table; c.block_table_stride = block_table_stride; c.num_blocks = num_blocks; c.page_size = page_size; c.max_blocks = max_blocks;
+    c.fp8 = true; c.kv_dtype_enum = kv_dtype_enum;  // (whatever kv_dtype_enum holds: one that is no fp8 format is refused)
+    c.k_descale = kv_descale; c.v_descale = kv_descale; c.k_descale_strides = kv_descale_strides; c.v_descale_strides = kv_descale_strides;
+    c.packed = true; c.cu_seqlens_q = cu_seqlens_q; c.total_q = total_q; c.max_seqlen_q = max_seqlen_q;
+    c.q8 = true; c.q_dtype_enum = q_dtype_enum; c.q_descale = q_descale; c.q_descale_strides = q_descale_strides;
+    return decode(c, nullptr);
+}
+
+int32_t fa2_kvcache_mla_varlen_q8_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                             int32_t d, int32_t d_v, int32_t q_dtype_enum, int32_t kv_dtype_enum) {
+    if (B < 1 || H < 1 || H_kv < 1 || total_q < 1 || max_seqlen_q < 1 || S_k < 1) return 1;
+    return num_splits_mla_varlen_q8({B, H, H_kv, max_seqlen_q, total_q, S_k, d, d_v, q_dtype_enum}, kv_dtype_enum);
 }
 
 int64_t fa2_kvcache_workspace_bytes(int32_t B, int32_t H, int32_t N_q, int32_t d, int32_t num_splits) {

@@ -47,9 +47,34 @@
 // Output: num_splits == 1 writes O in the output dtype and L in fp32 (a row without a visible key: O = 0, L = +inf); otherwise every
 // (split, row) writes the normalised fp32 partial (an empty split: 0 and -inf) for fa2_decode_combine.hip.  Vector stores only, no
 // atomics, no hand-off between workgroups.
+//
+// Packed (ragged) queries (fa2_fwd_kvcache_mla_varlen_q8).  VQ is a template parameter, instantiated in fa2_decode_mla8_v.hip
+// (FA2_DECODE_VARLEN_Q) alone; the argument struct of the fixed unit is what it was.  Q and O are packed (total_q, H, d) / (total_q, H,
+// d_v), L is (H, total_q), sequence b owns n_q(b) rows from start(b) on (fa2_varlen_seq).  The query tiling is fa2_decode_mla16.hip's:
+//   Rows.    The g n_q(b) rows of one (sequence, KV head) are flattened POSITION-major, row = position * g + head-in-group, 64 to a
+//            workgroup: tile t covers the contiguous positions [q0, q1) = [64 t / g, min((64 t + 63) / g + 1, n_q(b))) -- g = 128 two
+//            tiles a token, g = 16 four positions a tile, g = 72 a tile that straddles positions unevenly.  Rows past the sequence's last
+//            repeat that row and are dropped: no neighbour's packed row is read or written.
+//   Grid.    (num_splits * ceil(g max_seqlen_q / 64), H_kv, B).  Sequence b takes its (split, tile) pairs rotated by b along x (a
+//            bijection of the grid), so that the tiles that have rows do not sit gridDim.x workgroup ids apart where short sequences
+//            stand beside a long one (fa2_decode_mla16.hip has the measurement).  A tile with 64 t >= g n_q(b) leaves at once, before
+//            any barrier, and writes nothing.
+//   Band.    That of n_q(b) and N_k(b) (fa2_varlen_band), a row's lo / hi from its own position in the sequence.  The split's key
+//            range is clipped to the band of the tile's own [q0, q1) -- kb0 stays on a 64-key boundary, so the keys are tiled as the
+//            fixed call tiles them -- and the band-edge test of a key tile (lo_max, hi_min) comes from q1 - 1 and q0.  Whole key tiles
+//            outside the band are neither loaded nor looked up in the block table.
+//   Output.  One split: O to packed row start + position, L to head * l_head_stride + start + position.  Otherwise the partial row is
+//            split * total_q * H + (start + position) * H + head, what the combine reads under cu_q.
+// start, n_q(b), q0, q1 and the descales are uniform over the workgroup: scalar loads, scalar registers.  A row's arithmetic does not
+// depend on its tile-mates and a skipped key tile is one whose every score is masked (P8 = 0, factor 1), so the rows of sequence b are
+// the fixed call's on that sequence alone, bit for bit at the same num_splits.  With VQ false q0 = 0, q1 = N_q, start = 0, rows are
+// head-major as above and every expression below is the fixed kernel's.
 #include "fa2_decode.h"
 #include "fa2_mfma.h"
 
+#ifndef FA2_DECODE_VARLEN_Q
+#define FA2_DECODE_VARLEN_Q 0
+#endif
 namespace {
 
 struct DecodeMla8Args {
@@ -67,6 +92,12 @@ struct DecodeMla8Args {
     int page_size, num_blocks;
     const float *qd, *kd, *vd;  // descales at [b * s[0] + h_kv * s[1]], null = 1
     int64_t qds[2], kds[2], vds[2];
+#if FA2_DECODE_VARLEN_Q
+    // VQ only (the struct of the fixed unit is what it was): B + 1 offsets into the packed rows; qs[0] = os[0] = ls[0] = 0, N_q holds
+    // max_seqlen_q
+    const int32_t *cu_q;
+    int total_q;
+#endif
 };
 
 constexpr int kD = 576, kDV = 512, kBC = 64;
@@ -87,8 +118,8 @@ __device__ __forceinline__ int swz8(int row) { return (((row >> 1) & 1) << 1) | 
 // Byte offset of 16-byte chunk `ch` (< 36) of row `row` in a tile buffer.
 __device__ __forceinline__ int lds_off(int row, int ch) { return row * kRowB + ((ch ^ swz8(row)) << 4); }
 
-// T: O's dtype.
-template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_decode_mla8_kernel(const DecodeMla8Args a) {
+// T: O's dtype.  VQ: packed queries, query-tiled, rows position-major (the file's head).
+template <typename T, bool PAGED, bool VQ> __global__ __launch_bounds__(256, 1) void fa2_decode_mla8_kernel(const DecodeMla8Args a) {
     using M = F8<true>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LDS_PTR(char) lds = (LDS_PTR(char))smem;
@@ -98,27 +129,45 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
     const int kb = wave & 1, rb = wave >> 1;  // S phase: key block, row block
     const int i = lane & 31, h = lane >> 5;
     const int hk = blockIdx.y, b = blockIdx.z;
-    const int split = blockIdx.x / a.row_tiles, rt = blockIdx.x - split * a.row_tiles;
-    const int N_q = a.N_q, R = a.g * N_q;
+    unsigned bx = blockIdx.x;
+    if constexpr (VQ) {  // sequence b's (split, tile) pairs rotated by b along x: a bijection of the grid (the file's head)
+        bx += blockIdx.z % gridDim.x;  // (gridDim.x <= 128 splits * 2^18 row tiles: the sum stays far inside 32 bits)
+        bx -= bx >= gridDim.x ? gridDim.x : 0;
+    }
+    const int split = bx / a.row_tiles, rt = bx - split * a.row_tiles;
+    // N_q: the query count of the mask and of the rows, from packed row `start` on; [q0, q1): the positions the tile's rows lie in
+    int N_q = a.N_q, start = 0;
+    if constexpr (VQ) {
+#if FA2_DECODE_VARLEN_Q
+        fa2_varlen_seq(a.cu_q, b, a.total_q, a.N_q, start, N_q);
+#endif
+        if (rt * 64 >= a.g * N_q) return;  // no rows: nothing to write, no partials (uniform: before any barrier)
+    }
+    const int R = a.g * N_q;
+    const int q0 = VQ ? rt * 64 / a.g : 0;
+    const int q1 = VQ ? ((rt * 64 + 63) / a.g + 1 < N_q ? (rt * 64 + 63) / a.g + 1 : N_q) : N_q;
 
     int NK, k0, k1, wl, wr;
     fa2_decode_split(a.seqlens, b, a.S_k, a.num_splits, split, NK, k0, k1);
     fa2_varlen_band(N_q, NK, a.causal, a.wl, a.wr, wl, wr);
-    // the keys of the split that the band of any query position touches: [kb0, ke), kb0 on a 64-key boundary
-    const int lo_t = -wl;
+    // the keys of the split that the band of any query position of the tile touches: [kb0, ke), kb0 on a 64-key boundary
+    const int lo_t = q0 - wl;
     const int kb0 = lo_t > k0 ? (lo_t & ~63) : k0;  // (k0 is a multiple of 64)
-    const int ke = N_q + wr < k1 ? N_q + wr : k1;
+    const int ke = q1 + wr < k1 ? q1 + wr : k1;
     const int nt = ke > kb0 ? (ke - kb0 + kBC - 1) / kBC : 0;
 
-    // ---- S phase: this lane's row (head of the group, query position); padding rows repeat the last row and are not stored
+    // ---- S phase: this lane's row (head of the group, query position); padding rows repeat the last row and are not stored.
+    // Fixed N_q: row = head * N_q + position.  VQ: row = position * g + head.
     const int srow = rt * 64 + rb * 32 + i;
     const int srowc = srow < R ? srow : R - 1;
-    const int shg = srowc / N_q, sqi = srowc - shg * N_q;
+    const int sdiv = srowc / (VQ ? a.g : N_q);
+    const int srem = srowc - sdiv * (VQ ? a.g : N_q);
+    const int shg = VQ ? srem : sdiv, sqi = VQ ? sdiv : srem;
 
     // ---- Q fragments: B operand of S^T = K Q^T.  Lane (i, h), k-step s: Q[row][16 (4s + h) ..+15] | Q[row][16 (4s + 2 + h) ..+15]
     i32x8 qf[kKS];
     {
-        const char *qp = a.Q + b * a.qs[0] + (int64_t)(hk * a.g + shg) * a.qs[1] + (int64_t)sqi * a.qs[2] + h * 16;
+        const char *qp = a.Q + b * a.qs[0] + (int64_t)(hk * a.g + shg) * a.qs[1] + (int64_t)(start + sqi) * a.qs[2] + h * 16;
 #pragma unroll
         for (int s = 0; s < kKS; ++s) {
             const u32x4 qa = *(const u32x4 *)(qp + s * 64), qb = *(const u32x4 *)(qp + s * 64 + 32);
@@ -200,7 +249,7 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
     const float vd = fa2_decode_descale(a.vd, a.vds[0], a.vds[1], b, hk);
     // this row's visible keys [lo, hi], and whether a tile can meet a band edge of any row
     const int lo = sqi - wl, hi = (sqi + wr) < (ke - 1) ? (sqi + wr) : (ke - 1);
-    const int lo_max = N_q - 1 - wl, hi_min = wr < (ke - 1) ? wr : (ke - 1);
+    const int lo_max = q1 - 1 - wl, hi_min = (q0 + wr) < (ke - 1) ? (q0 + wr) : (ke - 1);
 
     if (nt > 0) {
         stage_load(0);
@@ -327,14 +376,16 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
     for (int rbp = 0; rbp < 2; ++rbp) {
         const int row = rt * 64 + 32 * rbp + i;
         if (row >= R) continue;
-        const int hg = row / N_q, qi = row - hg * N_q;
+        const int ediv = row / (VQ ? a.g : N_q);  // (recomputed, not carried from the S phase: no register lives across the loop)
+        const int erem = row - ediv * (VQ ? a.g : N_q);
+        const int hg = VQ ? erem : ediv, qi = VQ ? ediv : erem;
         const int head = hk * a.g + hg;
         const float l = xl[32 * rbp + i] + xl[64 + 32 * rbp + i];
         const float mr = mf[32 * rbp + i];
         const bool seen = l > 0.0f;
         const float inv = seen ? vd * 0.00390625f / l : 0.0f;  // O = vd 2^-8 (P8 V8) / l, in fp32
         if (a.num_splits == 1) {
-            char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)qi * a.os[2] + (128 * wave + 4 * h) * 2;
+            char *op = a.O + b * a.os[0] + head * a.os[1] + (int64_t)(start + qi) * a.os[2] + (128 * wave + 4 * h) * 2;
 #pragma unroll
             for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -345,24 +396,36 @@ template <typename T, bool PAGED> __global__ __launch_bounds__(256, 1) void fa2_
                     for (int j = 0; j < 4; ++j) v[j] = (T)(o[db][rbp][4 * g + j] * inv);
                     *(u32x2 *)(op + db * 64 + g * 16) = __builtin_bit_cast(u32x2, v);
                 }
-            if (wave == 0 && h == 0) a.L[b * a.ls[0] + head * a.ls[1] + qi] = seen ? mr + __builtin_amdgcn_logf(l) : INFINITY;
+            if (wave == 0 && h == 0) a.L[b * a.ls[0] + head * a.ls[1] + start + qi] = seen ? mr + __builtin_amdgcn_logf(l) : INFINITY;
         } else {
+#if FA2_DECODE_VARLEN_Q
+            const int64_t rows = (int64_t)a.total_q * a.H;  // the packed partial rows: token * H + head
+            const int64_t prow = (int64_t)split * rows + (int64_t)(start + qi) * a.H + head;
+#else
             const int64_t rows = (int64_t)gridDim.z * a.H * N_q;
             const int64_t prow = (int64_t)split * rows + ((int64_t)b * a.H + head) * N_q + qi;
+#endif
             float *op = a.o_part + prow * kDV + 128 * wave + 4 * h;
+            float invp = inv;
+            // VQ: the products of this branch are kept apart from the one-split branch's, as in fa2_decode_mla16.hip: a product the
+            // compiler hoists above both branches is rounded twice on its way to f16 where the fixed kernel's v_fma_mixlo_f16 rounds
+            // once, against the bit-for-bit equality with the fixed call
+            if constexpr (VQ) asm volatile("" : "+v"(invp));
 #pragma unroll
             for (int db = 0; db < 4; ++db)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f32x4 v;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = o[db][rbp][4 * g + j] * inv;
+                    for (int j = 0; j < 4; ++j) v[j] = o[db][rbp][4 * g + j] * invp;
                     *(f32x4 *)(op + db * 32 + g * 8) = v;
                 }
             if (wave == 0 && h == 0) a.l_part[prow] = seen ? mr + __builtin_amdgcn_logf(l) : -INFINITY;
         }
     }
 }
+
+constexpr bool kVQ = FA2_DECODE_VARLEN_Q != 0;
 
 template <typename T, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const DecodeMla8Args &a) {
     const long long gx = (long long)p.num_splits * a.row_tiles;
@@ -372,11 +435,11 @@ template <typename T, bool PAGED> int launch_t(const Fa2DecodeProblem &p, const 
     }
     static Fa2DeviceLatch attr_done;  // more than 64 KiB of dynamic LDS: opt in, once per device
     if (attr_done.need()) {
-        (void)hipFuncSetAttribute((const void *)fa2_decode_mla8_kernel<T, PAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
+        (void)hipFuncSetAttribute((const void *)fa2_decode_mla8_kernel<T, PAGED, kVQ>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
         attr_done.mark();
     }
     const dim3 grid((unsigned)gx, p.H_kv, p.B), block(256);
-    hipLaunchKernelGGL((fa2_decode_mla8_kernel<T, PAGED>), grid, block, kSmem, p.stream, a);
+    hipLaunchKernelGGL((fa2_decode_mla8_kernel<T, PAGED, kVQ>), grid, block, kSmem, p.stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fa2_set_error("kvcache mla8 kernel launch failed: %s", hipGetErrorString(e));
@@ -391,11 +454,10 @@ template <typename T> int launch_p(const Fa2DecodeProblem &p, const DecodeMla8Ar
 
 bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
 
-}  // namespace
-
-bool fa2_decode_mla8_supports(const Fa2DecodeProblem &p) {
+// (packed queries: N_q holds max_seqlen_q, so the row bound below is the grid's, and qs / os are the packed rows' strides)
+bool supports(const Fa2DecodeProblem &p) {
     if (!fa2_decode_mla8_shape(p.d, p.d_v, p.q_dtype, p.kv_dtype) || (p.dtype != FA2_DTYPE_F16 && p.dtype != FA2_DTYPE_BF16)) return false;
-    if (p.kv_format != 0 || p.cu_q || p.indices) return false;
+    if (p.kv_format != 0 || (p.cu_q != nullptr) != kVQ || p.indices) return false;
     if (p.V != p.K) return false;  // the value operand is read from K's LDS image
     for (int k = 0; k < 4; ++k)
         if (p.vs[k] != p.ks[k]) return false;
@@ -411,8 +473,8 @@ bool fa2_decode_mla8_supports(const Fa2DecodeProblem &p) {
     return true;
 }
 
-int fa2_launch_decode_mla8(const Fa2DecodeProblem &p) {
-    if (!fa2_decode_mla8_supports(p)) {
+int launch(const Fa2DecodeProblem &p) {
+    if (!supports(p)) {
         fa2_set_error("kvcache mla8 kernel: needs e4m3fn Q over an e4m3fn cache (the generic kernel takes e5m2), d = 576 and d_v = 512, f16/bf16 "
                       "O, V aliasing K (the same pointer and strides), unit d-stride, 16-byte aligned rows of Q and K (base and strides "
                       "multiples of 16 bytes), 16-byte aligned O rows (and workspace), scale > 0%s",
@@ -433,5 +495,18 @@ int fa2_launch_decode_mla8(const Fa2DecodeProblem &p) {
     a.table = p.table; a.table_stride = p.table_stride; a.page_size = p.page_size; a.num_blocks = p.num_blocks;
     a.qd = p.qd; a.kd = p.kd; a.vd = p.vd;
     for (int k = 0; k < 2; ++k) { a.qds[k] = p.qds[k]; a.kds[k] = p.kds[k]; a.vds[k] = p.vds[k]; }
+#if FA2_DECODE_VARLEN_Q
+    a.cu_q = p.cu_q; a.total_q = p.total_q;
+#endif
     return p.dtype == FA2_DTYPE_BF16 ? launch_p<__bf16>(p, a) : launch_p<_Float16>(p, a);
 }
+
+}  // namespace
+
+#if FA2_DECODE_VARLEN_Q
+bool fa2_decode_mla8_v_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla8_v(const Fa2DecodeProblem &p) { return launch(p); }
+#else
+bool fa2_decode_mla8_supports(const Fa2DecodeProblem &p) { return supports(p); }
+int fa2_launch_decode_mla8(const Fa2DecodeProblem &p) { return launch(p); }
+#endif

@@ -659,8 +659,9 @@ def flash_attention_mla_decode_q8_forward(Q8, KV_cache, cache_seqlens, dev, *, d
     page_size % 64 == 0) does the matrix work itself in fp8: the scores are (scale q_descale kv_descale) sum q8 k8 with exact products
     summed in fp32, p = exp2(s - m) and its row sum l are fp32, the operand of P.V is e4m3(256 p) (round to nearest even), and O =
     kv_descale 2^-8 (sum P8 v8) / l is rounded once.  "generic" converts both sides exactly and keeps P in fp32: e5m2 on either
-    side, any d <= 576 and d_v < d, any page size and alignment.  "auto" is "mla8" where it runs.  Out of scope here (they keep their
-    16-bit-Q calls, after mla_kvcache_append): packed queries, per-query key lists, kv_format="fp8_ds", kv_new and rotary."""
+    side, any d <= 576 and d_v < d, any page size and alignment.  "auto" is "mla8" where it runs.  Packed queries:
+    flash_attention_mla_varlen_decode_q8_forward.  Out of scope here (they keep their 16-bit-Q calls, after mla_kvcache_append):
+    per-query key lists, kv_format="fp8_ds", kv_new and rotary."""
     check_mla_q8_args(Q8, KV_cache, cache_seqlens, d_v, q_descale, kv_descale, window, num_splits, variant, block_table, out_dtype)
     _check_dev(dev, Q8, KV_cache, KV_cache)
     B, H, N_q, d = Q8.shape
@@ -1033,6 +1034,64 @@ def flash_attention_mla_varlen_decode_forward(Q, KV_cache, cu_seqlens_q, max_seq
     _lib.fa2_fwd_kvcache_mla_varlen(Q, KV_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, dtype,
                                     convert_triton_dtype(KV_cache.dtype), d_v, block_table=block_table, kv_descale=kd, causal=causal,
                                     scale=scale, window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_VARIANTS[variant])
+    return O, L
+
+
+def check_mla_varlen_q8_args(Q8, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v=512, q_descale=None, kv_descale=None,
+                             window=None, num_splits=0, variant="auto", block_table=None, out_dtype=torch.bfloat16):
+    """ValueError for what flash_attention_mla_varlen_decode_q8_forward cannot take: the dtypes, descales and out_dtype by the rules of
+    check_mla_q8_args, the packed Q8, cu_seqlens_q, max_seqlen_q, the cache, d_v, cache_seqlens, block_table, window and num_splits by
+    those of check_mla_varlen_args (on a stand-in of Q8 in out_dtype).  Pure: takes CPU tensors as well."""
+    if not isinstance(Q8, torch.Tensor) or Q8.dim() != 3 or Q8.dtype not in FP8_CACHE_DTYPES:
+        raise ValueError("mla varlen decode q8: Q8 must be a packed tensor (total_q, H, d) in torch.float8_e4m3fn or torch.float8_e5m2 "
+                         "(16-bit queries: flash_attention_mla_varlen_decode_forward)")
+    if not isinstance(KV_cache, torch.Tensor) or KV_cache.dim() != 4 or KV_cache.dtype not in FP8_CACHE_DTYPES:
+        raise ValueError("mla varlen decode q8: KV_cache must be a tensor (B, H_kv, S_k, d) or a pool (num_blocks, H_kv, page_size, d) in "
+                         "torch.float8_e4m3fn or torch.float8_e5m2")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"mla varlen decode q8: out_dtype must be torch.float16 or torch.bfloat16, got {out_dtype!r}")
+    stand_in = torch.empty((), dtype=out_dtype, device=Q8.device).expand(Q8.shape)  # Q's shape and device under the 16-bit rules
+    check_mla_varlen_args(stand_in, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, window, num_splits, kv_descale, block_table)
+    _kvcache_descale("q_descale", q_descale, Q8, cu_seqlens_q.numel() - 1, KV_cache.shape[1])
+    if variant not in _lib.KVCACHE_MLA_Q8_VARIANTS:
+        raise ValueError(f"mla varlen decode q8: variant must be one of {sorted(_lib.KVCACHE_MLA_Q8_VARIANTS)}, got {variant!r}")
+
+
+def flash_attention_mla_varlen_decode_q8_forward(Q8, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, dev, *, d_v=512, q_descale=None,
+                                                 kv_descale=None, causal=False, scale=1.0, window=None, num_splits=0, variant="auto",
+                                                 block_table=None, out_dtype=torch.bfloat16):
+    """flash_attention_mla_varlen_decode_forward with fp8 QUERIES over the fp8 latent cache (fa2_fwd_kvcache_mla_varlen_q8) -> (O, L): a
+    ragged step -- draft-token verification with a count per sequence, a prefill chunk beside one-token decodes, a prefix-cached chunk
+    -- of an engine that holds its absorbed queries in fp8.  Q8 packed (total_q, H, d) and KV_cache (B, H_kv, S_k, d) -- or, with
+    block_table, the pool (num_blocks, H_kv, page_size, d) -- in torch.float8_e4m3fn or torch.float8_e5m2; the query of sequence b is
+    q_descale * float(Q8), a cache row kv_descale * float(KV_cache), both descales float32 tensors on Q8's device that broadcast to
+    (B, H_kv) (None: 1; finite and > 0).  cu_seqlens_q and max_seqlen_q as in the 16-bit packed call: sequence b owns
+    min(cu[b + 1] - cu[b], max_seqlen_q) rows from cu[b] on, none is legal, and query i of it stands at position cache_seqlens[b] -
+    n_q(b) + i.  O (total_q, H, d_v) in out_dtype (float16 or bfloat16), L (H, total_q) in float32, log2 domain; rows without a visible
+    key get O = 0, L = +inf; rows outside every sequence are not written.
+
+    variant is one of _lib.KVCACHE_MLA_Q8_VARIANTS, as in flash_attention_mla_decode_q8_forward: "mla8" (e4m3fn on both sides, d = 576,
+    d_v = 512, 16-byte aligned packed rows of Q8 and rows of the cache, page_size % 64 == 0) does the matrix work in fp8 with that
+    call's stated arithmetic, 64 position-major rows of a (sequence, KV head) to a workgroup; "generic" takes everything else; "auto"
+    is "mla8" where it runs.  The rows of sequence b equal flash_attention_mla_decode_q8_forward's on that sequence alone at the same
+    explicit num_splits and variant bit for bit.  No kv_new, rotary or kv_format here: the engine rotates before it quantises and
+    calls mla_kvcache_append_varlen first."""
+    check_mla_varlen_q8_args(Q8, KV_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, d_v, q_descale, kv_descale, window, num_splits,
+                             variant, block_table, out_dtype)
+    _check_dev(dev, Q8, KV_cache, KV_cache)
+    total_q, H, d = Q8.shape
+    B, H_kv = cu_seqlens_q.numel() - 1, KV_cache.shape[1]
+    qe, ke = convert_triton_dtype(Q8.dtype), convert_triton_dtype(KV_cache.dtype)
+    n = num_splits or _lib.kvcache_mla_varlen_q8_num_splits(B, H, H_kv, total_q, max_seqlen_q, _capacity(KV_cache, block_table), d, d_v,
+                                                            qe, ke)
+    O = torch.empty((total_q, H, d_v), dtype=out_dtype, device=Q8.device)
+    L = torch.empty((H, total_q), dtype=torch.float32, device=Q8.device)
+    nbytes = _lib.kvcache_varlen_workspace_bytes(total_q, H, d_v, n) if n > 1 else 0
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=Q8.device) if nbytes else None
+    _lib.fa2_fwd_kvcache_mla_varlen_q8(Q8, KV_cache, O, L, cu_seqlens_q, max_seqlen_q, cache_seqlens, convert_triton_dtype(out_dtype), ke,
+                                       qe, d_v, block_table=block_table, q_descale=_kvcache_descale("q_descale", q_descale, Q8, B, H_kv),
+                                       kv_descale=_kvcache_descale("kv_descale", kv_descale, Q8, B, H_kv), causal=causal, scale=scale,
+                                       window=window, num_splits=n, workspace=ws, variant=_lib.KVCACHE_MLA_Q8_VARIANTS[variant])
     return O, L
 
 

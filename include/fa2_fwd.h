@@ -467,7 +467,7 @@ int fa2_fwd_kvcache_mla_fp8(const void *Q, const void *K, const void *V, void *O
  * accumulation of the scores keeps.  Strides of Q, K and V are in bytes (elements of one byte).  Everything else is
  * fa2_fwd_kvcache_mla_fp8's: lengths, masks, empty rows (O = 0, L = +inf), paging, fp32 partials and the combine launch.
  *
- *   Variants. FA2_KVCACHE_VARIANT_MLA8 (this entry point only): e4m3fn on both sides, d = 576 and d_v = 512, V aliasing K, unit d-stride,
+ *   Variants. FA2_KVCACHE_VARIANT_MLA8 (this entry point and its packed form only): e4m3fn on both sides, d = 576 and d_v = 512, V aliasing K, unit d-stride,
  *             16-byte aligned rows of Q and K (base and strides multiples of 16 bytes), O rows and the workspace aligned as for MLA16,
  *             scale > 0, page_size % 64 == 0 when paged.  The matrix work itself is fp8: S = (scale q_descale k_descale) sum_c q8[c] k8[c]
  *             with exact products and an fp32 sum on v_mfma_f32_32x32x64_f8f6f4; p = exp2(s - m) in fp32, the row sum l over the
@@ -481,7 +481,8 @@ int fa2_fwd_kvcache_mla_fp8(const void *Q, const void *K, const void *V, void *O
  *
  * Errors: fa2_fwd_kvcache_mla_fp8's, and FA2_ERR_UNSUPPORTED for a q_dtype_enum or kv_dtype_enum that is no fp8 format and a dtype_enum
  * other than f16 / bf16, FA2_ERR_BAD_ARG for a null q_descale_strides with a non-null q_descale and a negative descale stride.
- * Not covered: packed queries, key lists, the tile-scaled cache, the fused append (they keep their 16-bit-Q calls).
+ * Packed queries: fa2_fwd_kvcache_mla_varlen_q8.  Not covered: key lists, the tile-scaled cache, the fused append (they keep their
+ * 16-bit-Q calls).
  */
 #define FA2_KVCACHE_VARIANT_MLA8 4
 
@@ -860,6 +861,50 @@ int fa2_fwd_kvcache_mla_varlen(const void *Q, const void *KV, void *O, void *L,
  * fa2_kvcache_varlen_num_splits counts the VALU form. */
 int32_t fa2_kvcache_mla_varlen_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
                                           int32_t d, int32_t d_v, int32_t dtype_enum);
+
+/*
+ * fa2_fwd_kvcache_mla_varlen with fp8 QUERIES: the packed queries of fa2_fwd_kvcache_mla_varlen in the bytes of fa2_fwd_kvcache_mla_q8,
+ * over the one-descale fp8 latent cache -- a ragged step (draft-token verification, a prefill chunk beside one-token decodes, a
+ * prefix-cached chunk) of an engine that holds its absorbed queries in fp8.  Forward only.
+ *
+ *   Queries.  Q packed (total_q, H, d) in q_dtype_enum (e4m3fn / e5m2), strides {token, head, dim} in bytes; the query of sequence b
+ *             is q_descale * float(Q8), q_descale fp32 on the device at [b * q_descale_strides[0] + h_kv * q_descale_strides[1]],
+ *             null = 1.  O packed (total_q, H, d_v) in dtype_enum, which is O's alone (f16 / bf16); L is FP32 (H, total_q) with head
+ *             stride l_head_stride.  cu_seqlens_q, max_seqlen_q, n_q(b), the positions (query i of sequence b at cache_seqlens[b] -
+ *             n_q(b) + i), empty sequences and the rows no sequence owns (untouched) are fa2_fwd_kvcache_mla_varlen's.
+ *   Cache.    fa2_fwd_kvcache_mla_varlen's KV tensor in kv_dtype_enum, an fp8 format, with kv_descale as K's and V's descale.
+ *   Mask.     fa2_fwd_kvcache_varlen's.  A row without a visible key: O = 0, L = +inf.
+ *   Splits.   num_splits = 0 picks fa2_kvcache_mla_varlen_q8_num_splits(...).  Workspace: fa2_kvcache_varlen_workspace_bytes(total_q,
+ *             H, d_v, num_splits) bytes, 16-byte aligned.
+ *   Variants. fa2_fwd_kvcache_mla_q8's, under the same ids.  FA2_KVCACHE_VARIANT_MLA8: e4m3fn on both sides, d = 576, d_v = 512, f16 /
+ *             bf16 O, unit d-stride, 16-byte aligned packed rows of Q and rows of the cache (bases and strides multiples of 16
+ *             bytes), O rows and the workspace aligned as for MLA16, scale > 0, page_size % 64 == 0 when paged; any H_kv, any
+ *             g = H / H_kv.  The arithmetic is the one stated at fa2_fwd_kvcache_mla_q8; the g n_q(b) rows of a (sequence, KV head)
+ *             are taken position-major, 64 to a workgroup, as MLA16 takes packed rows.  The rows of sequence b equal
+ *             fa2_fwd_kvcache_mla_q8's on that sequence alone (N_q = n_q(b)) at the same explicit num_splits bit for bit, under MLA8
+ *             and under GENERIC.  GENERIC: either fp8 format on either side, every d <= 576 and d_v <= 512, any strides, any page
+ *             size.  AUTO: MLA8 where it runs, else GENERIC.  A forced MLA8 on a problem it cannot run returns
+ *             FA2_ERR_UNSUPPORTED, the message naming the rule.
+ *
+ * Every error of fa2_fwd_kvcache_mla_varlen and of fa2_fwd_kvcache_mla_q8 applies, with their messages.
+ * Not covered: key lists, the tile-scaled cache, a fused append (append with fa2_kvcache_mla_append_varlen first), a V tensor of its own.
+ */
+int fa2_fwd_kvcache_mla_varlen_q8(const void *Q, const void *KV, void *O, void *L,
+                                  const int64_t q_strides[3], const int64_t kv_strides[4], const int64_t o_strides[3],
+                                  int64_t l_head_stride, const int32_t *cu_seqlens_q, const int32_t *cache_seqlens,
+                                  const int32_t *block_table, int64_t block_table_stride,
+                                  const float *kv_descale, const int64_t kv_descale_strides[2],
+                                  const float *q_descale, const int64_t q_descale_strides[2],
+                                  int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                  int32_t num_blocks, int32_t page_size, int32_t max_blocks, int32_t d, int32_t d_v,
+                                  int32_t dtype_enum, int32_t kv_dtype_enum, int32_t q_dtype_enum,
+                                  int32_t causal, float scale, int32_t window_left, int32_t window_right, int32_t num_splits,
+                                  void *workspace, int64_t workspace_bytes, int32_t variant, void *hip_stream);
+
+/* What num_splits = 0 resolves to for it: with e4m3fn on both sides at d = 576, d_v = 512 (the packed matrix form) the count of
+ * fa2_kvcache_mla_varlen_num_splits at that shape; any other shape is counted as fa2_kvcache_varlen_num_splits counts the VALU form. */
+int32_t fa2_kvcache_mla_varlen_q8_num_splits(int32_t B, int32_t H, int32_t H_kv, int32_t total_q, int32_t max_seqlen_q, int32_t S_k,
+                                             int32_t d, int32_t d_v, int32_t q_dtype_enum, int32_t kv_dtype_enum);
 
 /*
  * Sparse MLA decode: every (sequence, KV head, query position) brings a list of key indices and attends over exactly those keys of
